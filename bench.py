@@ -10,10 +10,23 @@ One process per GPU; gradients are summed by ONE RCCL all-reduce per step inside
 torch bundles its own ROCm runtime, which must not share a process with libdnnca).  The RCCL unique id travels through
 a file keyed by the launcher's pid.  Rank 0 prints one JSON line.
 
-The line's `value` is the headline configuration (BASELINE.json configs[1]).  At N = 1 the same run also times the other two
-single-GPU configurations of BASELINE.json (configs[2] unet_big bf16 B=4, configs[3] mulmo_unet f32 B=8) for a few steps each
-and reports them under `other_workloads` (informative, never `value`).  With fewer than 100 steps the timed region is repeated
-(`repeats`, `region_ms`) and the line carries the median region: `steps` / `ms_per_step` describe ONE region of exactly K steps.
+The line's `value` is the headline configuration (BASELINE.json configs[1]).  A plain run does only what that figure needs: it
+builds the model, runs `--warmup` steps and the settle steps (un-timed), times ONE region of exactly `--steps` steps, writes the
+outputs of the last timed step if `--dump-outputs DIR` is given, and prints the line.  The region's last step starts from the
+initial model, restored outside the clock (restart()), so that its outputs compare from run to run and from build to build.
+
+--full adds everything else the benchmark measures: instrumented steps for the per-kernel roofline (`roofline`, `roofline_all`,
+`roofline_step`, HIP-event brackets in the timed region), and with fewer than 100 steps a repeated timed region (`repeats`,
+`region_ms`; the line carries the median region, `steps` / `ms_per_step` describe ONE region of exactly K steps).  At N = 1 it
+also adds the host-fed leg (`from_host_memory`), the other two single-GPU configurations of BASELINE.json (configs[2] unet_big
+bf16 B=4, configs[3] mulmo_unet f32 B=8) for a few steps each under `other_workloads` (informative, never `value`), and the
+numpy CPU baseline (`cpu_baseline`).
+
+--dump-outputs DIR writes what the timed path (`train_step_dev`) hands its caller after the last timed step, as float32 .npy
+files: the step outputs (loss, positive_rate, weight, label_min, label_max) and the model the step updated (params, state,
+grads, adam_m, adam_v).  A vector longer than DUMP_MAX_ELEMS is written as a fixed, seeded sample of that many entries.  The
+dumped step is one train step from the initial model (seeded weights, fresh Adam state) on the seeded batch: the same in every
+run, plain or --full, whatever --steps and --warmup are.
 
 DNNCA_FORCE_COMM=1 rehearses the N > 1 sequence on one GPU: id exchange through the file, a one-rank RCCL communicator,
 barriers and the max-reduction of the wall time through it (tests/test_engine_gpu.py::test_rccl_one_rank_rehearsal).
@@ -34,7 +47,7 @@ from dnncancerannotator_amd import device as dev                      # noqa: E4
 from dnncancerannotator_amd import distributed                        # noqa: E402
 from dnncancerannotator_amd.synthetic import synthetic_batch         # noqa: E402
 
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md:36 (spec; 6.29 TB/s measured float4 copy)
+HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md:36 (spec; 6.29 TB/s measured float4 copy)
 H = W = 512
 UNET_YAML = dict(n_filters_first=3, n_downsample=3, rate=2, kernel_size=3, conv_stride=1, bn=False, padding='same')
 # the single-GPU configurations of BASELINE.json: configs[1] is the metric's; [2] and [3] ride along under `other_workloads`
@@ -49,6 +62,26 @@ PROF_STEPS = 5
 SETTLE_MS = 100.0              # un-timed steps in front of the timed regions, in addition to --warmup: at least 20 steps and at least
 SETTLE_MIN_STEPS = 20          # this much device time -- the shader / memory clocks are still rising after the first ~30 steps
 CPU_THREADS = 16               # the GPU box gives one GPU's job 16 host cores; numpy's BLAS pool is pinned to that many
+DUMP_MAX_ELEMS = 1 << 20       # --dump-outputs: entries per array (4 MB); five model-sized vectors stay far below 64 MB
+DUMP_SEED = 0
+
+
+def dump_outputs(model, out_dir):
+    """--dump-outputs: the step outputs of the last train step and the model it updated, one float32 .npy per array.  A vector of
+    more than DUMP_MAX_ELEMS entries is sampled at DUMP_MAX_ELEMS fixed positions (seeded, sorted); empty vectors are skipped."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = model.last_step_out()
+    adam_m, adam_v, _ = model.get_opt_state()
+    arrays = [('loss', out.loss), ('positive_rate', out.positive_rate), ('weight', out.weight), ('label_min', out.label_min),
+              ('label_max', out.label_max), ('params', model.get_params()), ('state', model.get_state()),
+              ('grads', model.get_grads()), ('adam_m', adam_m), ('adam_v', adam_v)]
+    for name, a in arrays:
+        a = np.asarray(a, np.float32).ravel()
+        if a.size == 0:
+            continue
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def cpu_baseline(sample_steps=5):
@@ -86,15 +119,23 @@ def cpu_baseline(sample_steps=5):
             'c1_batch1': {'value': round(c1, 3), 'unit': 'slices/s', 'sample': '%d train steps of one 1x%dx%dx1 batch (C1)' % (2 * sample_steps, H, W)}}
 
 
-def time_workload(wname, steps, warmup, ctx, comm, generic=False, repeats=1, host_leg=False):
+def workload_desc(wl):
+    return ('%s train step (fwd + weighted BCE + bwd + Adam), batch %d x 512x512x%d per GPU, %s, random-init weights'
+            % (wl['name'], wl['batch'], wl['C'], wl['dtype']))
+
+
+def time_workload(wname, steps, warmup, ctx, comm, generic=False, repeats=1, host_leg=False, full=True, dump_dir=None):
     """Builds the workload's model on this rank's GPU and times `repeats` regions of exactly `steps` train steps on a batch that is
     resident in HBM, each region bracketed by a barrier + device synchronisation on both sides; the wall time of a region is the
-    maximum over the ranks.  Returns the fields of the JSON line that describe this workload (rank 0's view)."""
+    maximum over the ranks.  Returns the fields of the JSON line that describe this workload (rank 0's view).  full=False: no
+    instrumented steps, no HIP-event brackets, no roofline figures (the plain run); dump_dir: rank 0 writes dump_outputs there
+    right after the last timed region."""
     rank, world = ctx.rank, ctx.world
     wl = WORKLOADS[wname]
     C, B = wl['C'], wl['batch']
     model = dev.DeviceModel(wl['arch'], C, H, W, B, force_generic=generic, dtype=wl['dtype'], **wl['opts'])
     model.init_glorot(seed=2)          # same weights on every rank (random-init weights of the named architecture)
+    start = (model.get_params(), model.get_state(), np.zeros(model.n_trainable, np.float32))      # see restart()
     if comm:                           # (one GPU, not forced: no communicator -- the single-replica step keeps its fused fold + Adam launch)
         uid = distributed.exchange_unique_id(ctx, dev.DeviceModel, force=True, tag=wname)     # 128-byte RCCL id through a file keyed by the launcher's pid
         model.comm_init(rank, world, uid)
@@ -111,53 +152,80 @@ def time_workload(wname, steps, warmup, ctx, comm, generic=False, repeats=1, hos
             model.comm_allreduce([0.0])
         model.sync()
 
+    def restart():
+        """The initial model (weights, BatchNorm state, fresh Adam state) in front of the last timed step of a region, outside the
+        clock: the outputs of that step (what --dump-outputs writes) are then the same in every run.  Across a trajectory of steps
+        the run-to-run noise of the float atomics in the gradient sums grows until outputs no longer compare (relative
+        difference of the gradients between two runs: 4e-9 after one step from the initial model, 7e-2 after 50, 1 after 200)."""
+        model.set_params(start[0])
+        model.set_state(start[1])
+        model.set_opt_state(start[2], start[2], 0)
+
     tw = time.perf_counter()
     for _ in range(warmup):
         model.train_step_dev(xb, yb, B, lr, cfg)
     model.sync()
     tw = 1e3 * (time.perf_counter() - tw) / max(warmup, 1)          # ms per warm-up step (an over-estimate: first launches)
 
-    # which kernel dominates?  a few fully instrumented steps outside the timed region
-    model.profile_reset()
-    model.profile_enable(1)
-    for _ in range(PROF_STEPS):
-        model.train_step_dev(xb, yb, B, lr, cfg)
-    model.sync()
-    full_table = list(model.profile())
-    # (only kernels that move data or compute: under a profiler the bracket of a bookkeeping launch can absorb one-off costs)
-    table = sorted((r for r in model.profile() if r[3] > 0 or r[4] > 0), key=lambda r: -r[2])
-    dominant = table[0][0]
-    dominant_per_step = table[0][1] / float(PROF_STEPS)          # launches of the dominant kernel per step
-    model.profile_enable(0)
-    model.profile_reset()
-    # HIP events around the dominant kernel only, on the launch stream, in every 4th step of the timed region (a bracket
-    # costs ~3 us of dispatch: bracketing every launch would take 1.5 % off `value`)
-    model.profile_enable(2, focus=dominant, period=4)
+    if full:
+        # which kernel dominates?  a few fully instrumented steps outside the timed region
+        model.profile_reset()
+        model.profile_enable(1)
+        for _ in range(PROF_STEPS):
+            model.train_step_dev(xb, yb, B, lr, cfg)
+        model.sync()
+        full_table = list(model.profile())
+        # (only kernels that move data or compute: under a profiler the bracket of a bookkeeping launch can absorb one-off costs)
+        table = sorted((r for r in model.profile() if r[3] > 0 or r[4] > 0), key=lambda r: -r[2])
+        dominant = table[0][0]
+        dominant_per_step = table[0][1] / float(PROF_STEPS)          # launches of the dominant kernel per step
+        model.profile_enable(0)
+        model.profile_reset()
+        # HIP events around the dominant kernel only, on the launch stream, in every 4th step of the timed region (a bracket
+        # costs ~3 us of dispatch: bracketing every launch would take 1.5 % off `value`)
+        model.profile_enable(2, focus=dominant, period=4)
     # settle: the regions' times kept falling by ~1 % per region after 5 + 5 steps (clocks); `steps` / `warmup` stay as given
     settle_steps = max(SETTLE_MIN_STEPS, int(SETTLE_MS / max(tw, 1e-3)))
     for _ in range(settle_steps):
         model.train_step_dev(xb, yb, B, lr, cfg)
     model.sync()
-    model.profile_reset()
+    if full:
+        model.profile_reset()
 
     regions, ev_regions = [], []
     for _ in range(repeats):
-        barrier()
-        t0 = time.perf_counter()
-        model.timer_start()
-        for _ in range(steps):
-            model.train_step_dev(xb, yb, B, lr, cfg)
-        ev_ms = model.timer_stop()
-        barrier()
-        wall = time.perf_counter() - t0
+        wall, ev_ms = 0.0, 0.0
+        for seg, last in ((steps - 1, False), (1, True)):      # two timed segments: steps - 1 steps, restart(), the last step
+            if last:
+                restart()
+            elif seg == 0:
+                continue
+            barrier()
+            t0 = time.perf_counter()
+            if full:
+                model.timer_start()
+            for _ in range(seg):
+                model.train_step_dev(xb, yb, B, lr, cfg)
+            if full:
+                ev_ms += model.timer_stop()
+            barrier()
+            wall += time.perf_counter() - t0
         regions.append(float(model.comm_allreduce([wall], op='max')[0]) if comm else wall)
         ev_regions.append(ev_ms)
     out = model.last_step_out()
-    prof = {r[0]: r for r in model.profile()}
-    model.profile_enable(0)
+    if dump_dir and rank == 0:
+        dump_outputs(model, dump_dir)
+    if full:
+        prof = {r[0]: r for r in model.profile()}
+        model.profile_enable(0)
 
     res = None
-    if rank == 0:
+    if rank == 0 and not full:
+        elapsed = sorted(regions)[repeats // 2]
+        res = {'value': round(world * B * steps / elapsed, 2), 'ms_per_step': round(1e3 * elapsed / steps, 4), 'dtype': wl['dtype'],
+               'batch': B, 'channels': C, 'workload': workload_desc(wl), 'settle_steps': settle_steps,
+               'final_loss': round(float(out.loss), 6)}
+    elif rank == 0:
         order = sorted(range(repeats), key=lambda i: regions[i])
         mid = order[repeats // 2]                    # the median region (repeats is odd or 1)
         elapsed = regions[mid]
@@ -219,8 +287,7 @@ def time_workload(wname, steps, warmup, ctx, comm, generic=False, repeats=1, hos
                                   '--pmc passes over this same command (tools/collect_profiles.sh), not measured in this run')
         res = {
             'value': round(value, 2), 'ms_per_step': round(ms_per_step, 4), 'dtype': wl['dtype'], 'batch': B, 'channels': C,
-            'workload': '%s train step (fwd + weighted BCE + bwd + Adam), batch %d x 512x512x%d per GPU, %s, random-init weights'
-                        % (wl['name'], B, C, wl['dtype']),
+            'workload': workload_desc(wl),
             'repeats': repeats, 'region_ms': [round(1e3 * r, 3) for r in regions], 'settle_steps': settle_steps,
             'roofline': {'bound': bound, 'kernel': dominant, 'achieved': round(achieved, 1), 'peak': peak,
                          'unit': unit, 'frac': round(frac, 4), 'traffic': traffic, 'traffic_source': traffic_source,
@@ -270,8 +337,11 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-other-workloads', action='store_true', help='skip the informative unet_big / mulmo_unet legs')
+    ap.add_argument('--full', action='store_true', help='also the per-kernel roofline, repeated regions, the host-fed leg, the '
+                    'other workloads and the CPU baseline (see the module docstring); off: the headline figure alone')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed step as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the numpy CPU baseline')
+    ap.add_argument('--no-other-workloads', action='store_true', help='with --full: skip the informative unet_big / mulmo_unet legs')
     ap.add_argument('--generic', action='store_true', help='force the untuned generic kernels')
     ap.add_argument('--workload', default='unet', choices=sorted(WORKLOADS), help='default: the metric\'s configuration (unet)')
     args = ap.parse_args()
@@ -287,10 +357,11 @@ def main():
     if force_comm:
         os.environ['DNNCA_FORCE_RCCL'] = '1'
     comm = world > 1 or force_comm
-    repeats = 1 if args.steps >= 100 else 3
+    repeats = 1 if args.steps >= 100 or not args.full else 3
     wl = WORKLOADS[args.workload]
     head = time_workload(args.workload, args.steps, args.warmup, ctx, comm, generic=args.generic, repeats=repeats,
-                         host_leg=(world == 1 and args.workload == 'unet' and not comm))
+                         host_leg=(args.full and world == 1 and args.workload == 'unet' and not comm), full=args.full,
+                         dump_dir=args.dump_outputs)
     if rank == 0:
         line = {
             'metric': 'MRI slices/sec (fwd+bwd) %s 512x512 bs=%d' % (args.workload, wl['batch']), 'value': head['value'], 'unit': 'slices/s',
@@ -302,7 +373,7 @@ def main():
         for k in ('repeats', 'region_ms', 'settle_steps', 'roofline', 'roofline_step', 'roofline_all', 'hip_event_ms_per_step', 'final_loss', 'from_host_memory'):
             if k in head:
                 line[k] = head[k]
-    if world == 1 and not comm and args.workload == 'unet' and not args.generic and not args.no_other_workloads:
+    if args.full and world == 1 and not comm and args.workload == 'unet' and not args.generic and not args.no_other_workloads:
         # BASELINE.json configs[2] and [3], a few steps each (informative; the model of the headline leg is closed by now)
         others = {}
         n_other = max(5, args.steps // 4)
@@ -322,7 +393,7 @@ def main():
                              'top_kernels': r['roofline_all'][:6]}
         line['other_workloads'] = others
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and args.workload == 'unet':
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == 'unet':
             line['cpu_baseline'] = cpu_baseline()
         print(json.dumps(line), flush=True)
     distributed.cleanup(ctx)

@@ -998,7 +998,7 @@ def test_bench_n_gt_1_sequence_on_one_rank(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DNNCA_FORCE_COMM='1')
     env.pop('HSA_ENABLE_IPC_MODE_LEGACY', None)          # _lib.load() must provide it
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '5', '--warmup', '2', '--no-cpu-baseline'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '5', '--warmup', '2', '--full', '--no-cpu-baseline'],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -1008,6 +1008,49 @@ def test_bench_n_gt_1_sequence_on_one_rank(gpu):
     names = [k['kernel'] for k in line['roofline_all']]
     assert 'pg_fold' in names and 'g_adam' in names and 'pg_fold_adam' not in names, names      # the data-parallel sequence ran
     assert 'other_workloads' not in line and 'from_host_memory' not in line
+
+
+def test_bench_plain_run_and_dump_outputs(gpu, tmp_path):
+    """A plain bench.py run: one timed region of exactly --steps steps, the headline fields and nothing of --full; --dump-outputs
+    writes the last timed step's outputs and the model it updated as float32 vectors, consistent with the line -- and equal to one
+    train step of the same initial model on the same batch here (the region's last step starts from the restored initial model)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '3',
+                        '--dump-outputs', str(out_dir)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line['steps'] == 7 and line['warmup'] == 3 and line['dtype'] == 'f32' and line['higher_is_better'] is True
+    assert line['unit'] == 'slices/s' and line['value'] > 1000
+    assert abs(line['value'] - 8 / (line['ms_per_step'] * 1e-3)) <= 0.01 * line['value']
+    for k in ('repeats', 'region_ms', 'roofline', 'roofline_all', 'roofline_step', 'from_host_memory', 'other_workloads', 'cpu_baseline'):
+        assert k not in line, k
+    files = {p.name: np.load(p) for p in out_dir.iterdir()}
+    assert set(files) == {'loss.npy', 'positive_rate.npy', 'weight.npy', 'label_min.npy', 'label_max.npy', 'params.npy', 'grads.npy',
+                          'adam_m.npy', 'adam_v.npy'}, sorted(files)            # configs/unet.yaml has no BatchNorm: no state
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert abs(float(files['loss.npy'][0]) - line['final_loss']) <= 1e-6 * max(1.0, abs(line['final_loss']))
+    n = files['params.npy'].size
+    assert n > 0 and files['grads.npy'].size == n and files['adam_m.npy'].size == n and files['adam_v.npy'].size == n
+    assert (files['adam_v.npy'] >= 0).all() and np.abs(files['grads.npy']).max() > 0
+    assert files['label_min.npy'][0] == 0.0 and files['label_max.npy'][0] == 1.0
+
+    from dnncancerannotator_amd.synthetic import synthetic_batch
+    m = gpu.DeviceModel('unet', 1, 512, 512, 8, **UNET)
+    m.init_glorot(seed=2)                                        # bench.py's weights and batch (rank 0)
+    x, y = synthetic_batch(8, 512, 512, 1, seed_x=100, seed_y=200)
+    out = m.train_step(x, y, 1e-3, m.loss_cfg(weight_mul=3.0))
+    adam_m, adam_v, it = m.get_opt_state()
+    assert it == 1
+    # run to run, one step from the same start differs by ~1e-8 of each vector's scale (float atomics in the gradient sums)
+    for name, ref in (('loss', [out.loss]), ('positive_rate', [out.positive_rate]), ('weight', [out.weight]),
+                      ('params', m.get_params()), ('grads', m.get_grads()), ('adam_m', adam_m), ('adam_v', adam_v)):
+        ref = np.asarray(ref, np.float64)
+        assert np.abs(files[name + '.npy'] - ref).max() <= 1e-5 * np.abs(ref).max(), name
+    m.close()
 
 
 def test_bucketed_gradient_allreduce_rehearsal(gpu):

@@ -1,11 +1,32 @@
 """CPU: the numpy oracle against the committed golden vectors, against an independent torch-autograd statement, and
 against hand-computed known answers.  (The reference holds no fixtures for this path: SURVEY.md 8c "parity unpinned".)"""
 
+import importlib.util
+import os
+import pickle
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
 import helpers as Hp
 from oracle import unet_oracle as O
+
+TORCH_REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'torch_ref.py')
+
+
+def require_torch():
+    if importlib.util.find_spec('torch') is None:
+        pytest.skip('torch is not installed')
+
+
+def torch_ref_run(*args, **kwargs):
+    """tests/torch_ref.py's run() in a child process: torch bundles its own ROCm runtime, which must not share a process with
+    libdnnca (the -m gpu tests of the same session load it; two runtimes in one process abort at exit)."""
+    r = subprocess.run([sys.executable, TORCH_REF], input=pickle.dumps((args, kwargs)), capture_output=True, timeout=600)
+    assert r.returncode == 0, r.stderr.decode(errors='replace')
+    return pickle.loads(r.stdout)
 
 
 @pytest.mark.parametrize('name', Hp.SMALL_CASES + Hp.BIG_CASES)
@@ -37,13 +58,13 @@ def test_oracle_reproduces_golden(name):
           activation={'class_name': 'LeakyReLU', 'config': {'alpha': 0.3}}), 2, 8, 8, dict(weight_mul=2.0, weight_add=0.25)),
 ])
 def test_oracle_matches_torch_autograd(kw, B, H, W, cfg):
-    torch_ref = pytest.importorskip('torch_ref')
+    require_torch()
     spec = O.ModelSpec(**kw)
     params = Hp.perturbed_params(spec, np.float64)
     x, y = O.synthetic_batch(B, H, W, spec.in_channels)
     x = x.astype(np.float64)
     loss, grads, logits, state = O.loss_and_grads(spec, params, x, y, cfg, training=True)
-    ref = torch_ref.run(spec, params, x, y, cfg, training=True)
+    ref = torch_ref_run(spec, params, x, y, cfg, training=True)
     assert abs(loss - ref['loss']) < 1e-10
     assert np.abs(logits - ref['logits']).max() < 1e-10
     for n, g in grads.items():
@@ -53,13 +74,13 @@ def test_oracle_matches_torch_autograd(kw, B, H, W, cfg):
 
 
 def test_valid_padding_forward_matches_torch():
-    torch_ref = pytest.importorskip('torch_ref')
+    require_torch()
     spec = O.ModelSpec('unet', 1, 3, 2, bn=False, padding='valid')
     params = Hp.perturbed_params(spec, np.float64)
     x, _ = O.synthetic_batch(1, 44, 44, 1)
     logits, _, _, _ = O.forward(spec, params, x.astype(np.float64))
     assert logits.shape == (1, 20, 20, 1)            # real centre crop of the skips (components.py:161-163)
-    ref = torch_ref.run(spec, params, x.astype(np.float64), np.zeros((1, 20, 20), np.float32), dict(weight_mul=1.0), False)
+    ref = torch_ref_run(spec, params, x.astype(np.float64), np.zeros((1, 20, 20), np.float32), dict(weight_mul=1.0), False)
     assert np.abs(logits - ref['logits']).max() < 1e-10
 
 

@@ -91,3 +91,13 @@ def run(spec, params, x, y, loss_cfg, training, dtype=torch.float64):
     loss.backward()
     grads = {n: v.grad.numpy() for n, v in P.items() if v.grad is not None}
     return dict(loss=float(loss), logits=logits.detach().permute(0, 2, 3, 1).numpy(), grads=grads, state=state)
+
+
+if __name__ == '__main__':
+    # child-process entry (tests/test_oracle.py): run()'s pickled arguments on stdin, its pickled result on stdout
+    import os
+    import pickle
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))        # oracle/, for the pickled ModelSpec
+    args, kwargs = pickle.load(sys.stdin.buffer)
+    pickle.dump(run(*args, **kwargs), sys.stdout.buffer)
