@@ -52,6 +52,15 @@ class Confusion(C.Structure):
     _fields_ = [('tp', C.c_double), ('fp', C.c_double), ('fn', C.c_double), ('tn', C.c_double)]
 
 
+class RegionSpec(C.Structure):                     # dnnca_region_spec
+    _fields_ = [('thresholds', C.POINTER(C.c_float)), ('n_thresholds', C.c_int32), ('iou_threshold', C.c_float),
+                ('resize_factor', C.c_float), ('morph_filter_size', C.c_int32)]
+
+
+class RegionCounts(C.Structure):                   # dnnca_region_counts
+    _fields_ = [('tp_label', C.c_int64), ('fn', C.c_int64), ('tp_pred', C.c_int64), ('fp', C.c_int64)]
+
+
 _FP = C.POINTER(C.c_float)
 _VP = C.c_void_p
 
@@ -103,6 +112,10 @@ SIGNATURES = {
     'dnnca_eval_end': (C.c_int, [_VP, C.POINTER(Confusion)]),
     'dnnca_pixel_confusion': (C.c_int, [_VP, _FP, C.c_int, _FP, C.c_int, C.POINTER(Confusion)]),
     'dnnca_pixel_confusion_of': (C.c_int, [_VP, _FP, _FP, C.c_int64, _FP, C.c_int, C.POINTER(Confusion)]),
+    'dnnca_region_confusion_of': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.POINTER(RegionSpec), C.POINTER(RegionCounts)]),
+    'dnnca_region_confusion': (C.c_int, [_VP, _FP, C.c_int, C.POINTER(RegionSpec), C.POINTER(RegionCounts)]),
+    'dnnca_eval_region_begin': (C.c_int, [_VP, C.POINTER(RegionSpec), C.c_int]),
+    'dnnca_eval_region_end': (C.c_int, [_VP, C.POINTER(RegionCounts)]),
     'dnnca_comm_unique_id': (C.c_int, [_VP]),
     'dnnca_comm_init': (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_size_t]),
     'dnnca_comm_world': (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -1,0 +1,625 @@
+// kernels_region.hip -- region-based (lesion-level) metrics of the reference (annotator/utils/metrics.py:80-510) on the device.
+//
+// Per batch of slices and per spec (thresholds[T], IoU threshold, resize factor, morphological filter size k):
+//   region_prep     resize (tf.image.resize bilinear, half-pixel centres, no antialias; metrics.py:196-204) and threshold:
+//                   label' > 0.5 -> one bit; prob' >= thresholds[t] -> bit t of the pixel's mask words (T <= 64: two words)
+//   region_open     morphological opening of every prediction mask (utils/image.py:12-26: erosion2d + dilation2d, zero filter,
+//                   SAME, out-of-bounds pixels ignored): AND / OR over the k x k window of the bit words, all thresholds at once;
+//                   row and column passes through one LDS tile with a halo of 2 (k - 1)
+//   region_ccl_*    4-connected components (tfa.image.connected_components) by union-find on int32 parents in HBM: a 32 x 32
+//                   tile is labelled in LDS (ccl_tile), the pixels on tile borders unite across tiles with atomicMin (ccl_merge),
+//                   every pixel then points at its root (ccl_compress).  A root is the smallest pixel index of its component:
+//                   parents only ever point to smaller indices.  The label plane is labelled once per slice and resized size.
+//   region_sizes    component sizes: per-root atomicAdd (a root is a pixel index: no hashing)
+//   region_pairs    intersections |L_i n P_j|: a per-(slice, threshold) open-addressing table keyed by (label root, prediction
+//                   root), 64-bit CAS.  Overlap pixels of two different pairs are never 4-adjacent, so a slice of HW pixels has
+//                   at most ceil(HW / 2) pairs: HW + 1 slots per table keep the load below one half
+//   region_match    IoU = float(I) / float(|L| + |P| - I) > theta marks both roots (idempotent stores: no order dependence)
+//   region_count    roots -> tp_label / fn / tp_pred / fp: wave and block reductions, one uint64 atomicAdd per block and counter
+// Every count is an integer sum, so results are bit-exact and independent of which thread wins a race.
+#include <math.h>
+
+#include <algorithm>
+
+#include "region.h"
+
+namespace dnnca {
+
+namespace {
+
+constexpr int RB = 256;
+constexpr int kTile = 32;                                  // opening and LDS-labelling tile (kTile x kTile pixels)
+constexpr int kOpenE = kTile + 2 * (kRegionMaxK - 1);      // opening: input tile edge with the halo of erosion + dilation
+constexpr unsigned long long kEmpty = ~0ull;
+
+struct Resize {
+    int in_h, in_w, out_h, out_w;
+    float sy, sx;                        // in / out as float (TF's CalculateResizeScale), computed on the host
+    int identity;
+};
+
+#pragma clang fp contract(off)
+// tf.image.resize(method=bilinear, antialias=False) [TF-2.6 resize_bilinear_op.cc, restated]: half-pixel centres, float32,
+// each product and sum rounded on its own (no FMA contraction: the >= comparisons downstream must see the oracle's values)
+__device__ __forceinline__ float resize_at(const float* __restrict__ src, const Resize& r, int i, int j) {
+    if (r.identity) return src[(size_t)i * r.in_w + j];
+    const float fy = ((float)i + 0.5f) * r.sy - 0.5f;
+    const float fx = ((float)j + 0.5f) * r.sx - 0.5f;
+    const float fy0 = floorf(fy), fx0 = floorf(fx);
+    const int y0 = max((int)fy0, 0), y1 = min((int)ceilf(fy), r.in_h - 1);
+    const int x0 = max((int)fx0, 0), x1 = min((int)ceilf(fx), r.in_w - 1);
+    const float ly = fy - fy0, lx = fx - fx0;
+    const float tl = src[(size_t)y0 * r.in_w + x0], tr = src[(size_t)y0 * r.in_w + x1];
+    const float bl = src[(size_t)y1 * r.in_w + x0], br = src[(size_t)y1 * r.in_w + x1];
+    const float top = tl + (tr - tl) * lx;
+    const float bot = bl + (br - bl) * lx;
+    return top + (bot - top) * ly;
+}
+
+// label mode (T = 0): word = label' > 0.5.  Otherwise words[w][q] bit (t - 32 w) = prob' >= thr[t]
+__global__ __launch_bounds__(RB) void k_region_prep(const float* __restrict__ src, Resize r, int nb, const float* __restrict__ thr,
+                                                    int T, uint32_t* __restrict__ words) {
+    __shared__ float sthr[kRegionMaxThr];
+    if (threadIdx.x < T) sthr[threadIdx.x] = thr[threadIdx.x];
+    __syncthreads();
+    const size_t hw = (size_t)r.out_h * r.out_w, n = (size_t)nb * hw;
+    const size_t q = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (q >= n) return;
+    const int b = (int)(q / hw);
+    const int p = (int)(q - (size_t)b * hw);
+    const int i = p / r.out_w, j = p - i * r.out_w;
+    const float v = resize_at(src + (size_t)b * r.in_h * r.in_w, r, i, j);
+    if (T == 0) {
+        words[q] = v > 0.5f ? 1u : 0u;
+        return;
+    }
+    uint32_t lo = 0, hi = 0;
+    for (int t = 0; t < T && t < 32; ++t) lo |= (v >= sthr[t] ? 1u : 0u) << t;
+    for (int t = 32; t < T; ++t) hi |= (v >= sthr[t] ? 1u : 0u) << (t - 32);
+    words[q] = lo;
+    if (T > 32) words[n + q] = hi;
+}
+
+// opening of kTile x kTile output pixels of one word plane: erosion (AND; out-of-bounds input = all ones, i.e. ignored), then
+// dilation (OR; out-of-bounds eroded pixels = 0, i.e. ignored), each as a row pass and a column pass in LDS.  TF SAME offsets:
+// the window of pixel y is [y - (k - 1) / 2, y + k / 2] for both (erosion2d = -dilation2d(-x, reversed zero filter)).
+__global__ __launch_bounds__(RB) void k_region_open(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, int H, int W, int k,
+                                                    size_t plane, int nb) {
+    __shared__ uint32_t A[kOpenE * kOpenE], Bf[kOpenE * kOpenE];
+    const int lo = (k - 1) / 2;
+    const int E = kTile + 2 * (k - 1), E2 = kTile + k - 1;
+    const int w = blockIdx.z / nb, b = blockIdx.z - w * nb;
+    const size_t base = (size_t)w * plane + (size_t)b * H * W;
+    const int y0 = blockIdx.y * kTile, x0 = blockIdx.x * kTile;
+    const int ey0 = y0 - 2 * lo, ex0 = x0 - 2 * lo;
+    for (int i = threadIdx.x; i < E * E; i += RB) {
+        const int r = i / E, c = i - r * E, gy = ey0 + r, gx = ex0 + c;
+        A[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? in[base + (size_t)gy * W + gx] : ~0u;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < E * E2; i += RB) {           // erosion, rows: Bf[E][E2]
+        const int r = i / E2, c = i - r * E2;
+        uint32_t v = ~0u;
+        for (int d = 0; d < k; ++d) v &= A[r * E + c + d];
+        Bf[r * E2 + c] = v;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < E2 * E2; i += RB) {          // erosion, columns: A[E2][E2]; eroded pixels outside the slice -> 0
+        const int r = i / E2, c = i - r * E2, gy = y0 - lo + r, gx = x0 - lo + c;
+        uint32_t v = ~0u;
+        for (int d = 0; d < k; ++d) v &= Bf[(r + d) * E2 + c];
+        A[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? v : 0u;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < E2 * kTile; i += RB) {       // dilation, rows: Bf[E2][kTile]
+        const int r = i / kTile, c = i - r * kTile;
+        uint32_t v = 0u;
+        for (int d = 0; d < k; ++d) v |= A[r * E2 + c + d];
+        Bf[r * kTile + c] = v;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kTile * kTile; i += RB) {    // dilation, columns -> out
+        const int r = i / kTile, c = i - r * kTile, gy = y0 + r, gx = x0 + c;
+        if (gy >= H || gx >= W) continue;
+        uint32_t v = 0u;
+        for (int d = 0; d < k; ++d) v |= Bf[(r + d) * kTile + c];
+        out[base + (size_t)gy * W + gx] = v;
+    }
+}
+
+// ---- connected components.  Plane t of the mask words (bit t & 31 of word plane t >> 5) holds T x nb slices of H x W; a pixel's
+// global index is g = t * n + q (n = nb * H * W, q = b * H * W + y * W + x), its parent L[g] (-1: background).
+__device__ __forceinline__ bool fg_at(const uint32_t* __restrict__ words, size_t n, int t, size_t q) {
+    return (words[(size_t)(t >> 5) * n + q] >> (t & 31)) & 1u;
+}
+
+__device__ __forceinline__ int ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__device__ __forceinline__ int find_root(const int* L, int x) {
+    int y;
+    while ((y = ld_agent(L + x)) != x) x = y;
+    return x;
+}
+
+// union by atomicMin on roots (Playne & Hawick 2018): the larger root is linked to the smaller one; a lost race retries from the
+// value atomicMin returned
+__device__ void unite(int* L, int a, int b) {
+    for (;;) {
+        a = find_root(L, a);
+        b = find_root(L, b);
+        if (a == b) return;
+        if (a > b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(L + b, a);
+        if (old == b) return;
+        b = old;
+    }
+}
+
+__device__ __forceinline__ int lds_find(volatile int* l, int x) {
+    int y;
+    while ((y = l[x]) != x) x = y;
+    return x;
+}
+
+// one kTile x kTile tile of one plane labelled in LDS; L[g] = the global index of the pixel's root inside the tile (the tile's
+// row-major order is the global order, so that root is the smallest global index of the tile-local component)
+__global__ __launch_bounds__(RB) void k_region_ccl_tile(const uint32_t* __restrict__ words, int nb, int H, int W, int* __restrict__ L) {
+    __shared__ int l[kTile * kTile];
+    const int t = blockIdx.z / nb, b = blockIdx.z - t * nb;
+    const size_t hw = (size_t)H * W, n = (size_t)nb * hw;
+    const size_t qb = (size_t)b * hw;
+    const int y0 = blockIdx.y * kTile, x0 = blockIdx.x * kTile;
+    for (int i = threadIdx.x; i < kTile * kTile; i += RB) {
+        const int y = y0 + i / kTile, x = x0 + (i & (kTile - 1));
+        l[i] = (y < H && x < W && fg_at(words, n, t, qb + (size_t)y * W + x)) ? i : -1;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kTile * kTile; i += RB) {
+        if (l[i] < 0) continue;
+        const int c = i & (kTile - 1);
+        for (int side = 0; side < 2; ++side) {
+            const int nbr = side == 0 ? (c > 0 ? i - 1 : -1) : (i >= kTile ? i - kTile : -1);
+            if (nbr < 0 || l[nbr] < 0) continue;
+            int a = i, bb = nbr;
+            for (;;) {
+                a = lds_find(l, a);
+                bb = lds_find(l, bb);
+                if (a == bb) break;
+                if (a > bb) { const int s = a; a = bb; bb = s; }
+                const int old = atomicMin(&l[bb], a);
+                if (old == bb) break;
+                bb = old;
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kTile * kTile; i += RB) {
+        const int y = y0 + i / kTile, x = x0 + (i & (kTile - 1));
+        if (y >= H || x >= W) continue;
+        const size_t g = (size_t)t * n + qb + (size_t)y * W + x;
+        int v = -1;
+        if (l[i] >= 0) {
+            const int r = lds_find(l, i);
+            v = (int)((size_t)t * n + qb + (size_t)(y0 + r / kTile) * W + x0 + (r & (kTile - 1)));
+        }
+        L[g] = v;
+    }
+}
+
+// pixels on a tile's left / top border unite with their neighbour across it
+__global__ __launch_bounds__(RB) void k_region_ccl_merge(int* __restrict__ L, size_t total, int H, int W) {
+    const size_t g = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (g >= total) return;
+    const size_t p = g % ((size_t)H * W);
+    const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
+    const bool bx = x > 0 && (x & (kTile - 1)) == 0, by = y > 0 && (y & (kTile - 1)) == 0;
+    if (!(bx || by) || L[g] < 0) return;
+    if (bx && L[g - 1] >= 0) unite(L, (int)g, (int)(g - 1));
+    if (by && L[g - W] >= 0) unite(L, (int)g, (int)(g - W));
+}
+
+__global__ __launch_bounds__(RB) void k_region_ccl_compress(int* __restrict__ L, size_t total) {
+    const size_t g = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (g >= total) return;
+    const int v = L[g];
+    if (v >= 0 && v != (int)g) L[g] = find_root(L, v);
+}
+
+// lanes of a wave that carry the same key are summed into one atomic by the first of them (usually one or two keys per wave)
+template <typename Fn>
+__device__ __forceinline__ void wave_grouped(bool active, unsigned long long key, Fn&& fn) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long pending = __ballot(active);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const unsigned long long k0 = __shfl(key, leader);
+        const unsigned long long same = __ballot(active && key == k0);
+        if (lane == leader) fn(k0, (unsigned)__popcll(same));
+        if (key == k0) active = false;
+        pending &= ~same;
+    }
+}
+
+__global__ __launch_bounds__(RB) void k_region_sizes(const int* __restrict__ L, size_t total, unsigned* __restrict__ S) {
+    const size_t g = (size_t)blockIdx.x * RB + threadIdx.x;
+    const int r = g < total ? L[g] : -1;
+    wave_grouped(r >= 0, (unsigned long long)(unsigned)r, [&](unsigned long long k, unsigned c) { atomicAdd(S + k, c); });
+}
+
+__device__ __forceinline__ size_t slot_hash(unsigned long long key, size_t cap) {
+    key ^= key >> 33;
+    key *= 0xff51afd7ed558ccdull;
+    key ^= key >> 33;
+    return (size_t)(key % cap);
+}
+
+// overlap pixels of label root rl and prediction root rp (slice-local indices) -> table (t, b): key rl << 32 | rp, count
+__global__ __launch_bounds__(RB) void k_region_pairs(const int* __restrict__ LL, const int* __restrict__ LP, int T, int nb, size_t hw,
+                                                     size_t cap, unsigned long long* __restrict__ keys, unsigned* __restrict__ cnt) {
+    const size_t n = (size_t)nb * hw;
+    const size_t g = (size_t)blockIdx.x * RB + threadIdx.x;
+    bool on = false;
+    unsigned long long key = 0;
+    size_t tb = 0;
+    if (g < (size_t)T * n) {
+        const size_t t = g / n, q = g - t * n, b = q / hw;
+        const int rp = LP[g], rl = LL[q];
+        // roots lie in the pixel's own plane and slice; the range check only guards the table indices against a broken label
+        if (rp >= 0 && rl >= 0 && (size_t)rl - b * hw < hw && (size_t)rp - t * n - b * hw < hw) {
+            on = true;
+            tb = t * nb + b;
+            key = ((unsigned long long)((size_t)rl - b * hw) << 32) | (unsigned long long)((size_t)rp - t * n - b * hw);
+        }
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long pending = __ballot(on);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const unsigned long long key0 = __shfl(key, leader);
+        const size_t tb0 = __shfl(tb, leader);
+        const bool mine = on && key == key0 && tb == tb0;
+        const unsigned long long same = __ballot(mine);
+        if (lane == leader) {
+            const unsigned c = (unsigned)__popcll(same);
+            unsigned long long* kt = keys + tb0 * cap;
+            size_t h = slot_hash(key0, cap);
+            for (size_t probe = 0; probe < cap; ++probe) {
+                const unsigned long long old = atomicCAS(kt + h, kEmpty, key0);
+                if (old == kEmpty || old == key0) {
+                    atomicAdd(cnt + tb0 * cap + h, c);
+                    break;
+                }
+                h = h + 1 == cap ? 0 : h + 1;
+            }
+        }
+        if (mine) on = false;
+        pending &= ~same;
+    }
+}
+
+__global__ __launch_bounds__(RB) void k_region_match(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ cnt,
+                                                     size_t slots, size_t cap, int nb, size_t hw, const unsigned* __restrict__ SL,
+                                                     const unsigned* __restrict__ SP, float theta, uint32_t* __restrict__ ML,
+                                                     unsigned char* __restrict__ MP) {
+    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (i >= slots) return;
+    const unsigned long long key = keys[i];
+    if (key == kEmpty) return;
+    const size_t tb = i / cap, t = tb / nb, b = tb - t * nb, n = (size_t)nb * hw;
+    const size_t rl = (size_t)(key >> 32), rp = (size_t)(key & 0xffffffffu);
+    if (rl >= hw || rp >= hw || t >= 64) return;
+    const size_t ql = b * hw + rl, gp = t * n + b * hw + rp;
+    const unsigned inter = cnt[i];
+    const float iou = (float)inter / (float)(SL[ql] + SP[gp] - inter);
+    if (iou > theta) {
+        atomicOr(ML + (t >> 5) * n + ql, 1u << (t & 31));
+        MP[gp] = 1;
+    }
+}
+
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// grid (blocks, T): acc[t][0..3] += tp_label, fn, tp_pred, fp of plane t
+__global__ __launch_bounds__(RB) void k_region_count(const int* __restrict__ LL, const int* __restrict__ LP, const uint32_t* __restrict__ ML,
+                                                     const unsigned char* __restrict__ MP, size_t n, unsigned long long* __restrict__ acc) {
+    __shared__ unsigned part[RB / 64][4];
+    const int t = blockIdx.y;
+    unsigned c[4] = {0u, 0u, 0u, 0u};
+    const size_t stride = (size_t)gridDim.x * RB;
+    for (size_t q = (size_t)blockIdx.x * RB + threadIdx.x; q < n; q += stride) {
+        if (LL[q] == (int)q) {
+            const unsigned m = (ML[(size_t)(t >> 5) * n + q] >> (t & 31)) & 1u;
+            c[0] += m;
+            c[1] += 1u - m;
+        }
+        const size_t g = (size_t)t * n + q;
+        if (LP[g] == (int)g) {
+            const unsigned m = MP[g];
+            c[2] += m;
+            c[3] += 1u - m;
+        }
+    }
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int j = 0; j < 4; ++j) {
+        const unsigned s = wave_sum(c[j]);
+        if (lane == 0) part[wv][j] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        unsigned long long s = 0;
+        for (int k = 0; k < RB / 64; ++k) s += part[k][threadIdx.x];
+        if (s) atomicAdd(acc + (size_t)t * 4 + threadIdx.x, s);
+    }
+}
+
+inline unsigned nblocks(size_t n) { return (unsigned)((n + RB - 1) / RB); }
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------- host side
+struct RegionState {
+    std::vector<RegionSpecHost> specs;
+    std::vector<int> order;              // specs by resized plane: the label plane is labelled once per size
+    float* thr_dev = nullptr;            // [n_specs][kRegionMaxThr]
+    unsigned long long* acc = nullptr;   // [n_specs][kRegionMaxThr][4]
+    size_t acc_specs = 0;
+    // workspace of one chunk of slices
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    int chunk = 0;                       // slices per chunk
+    float* in_prob = nullptr;            // dnnca_region_confusion_of inputs
+    float* in_y = nullptr;
+    size_t in_n = 0;
+};
+
+static constexpr size_t kRegionBudget = size_t(1) << 24;    // pixel-thresholds per chunk (~21 bytes each)
+
+static size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+
+struct RegionWs {                        // carve-up of the workspace for nb slices of hw pixels and T thresholds
+    uint32_t *wlab, *w0, *w1, *ml;
+    int *ll, *lp;
+    unsigned *sl, *sp, *cnt;
+    unsigned char* mp;
+    unsigned long long* keys;
+    size_t bytes;
+};
+
+static RegionWs region_layout(void* base, size_t nb, size_t hw, size_t T) {
+    const size_t n = nb * hw, cap = hw + 1;
+    RegionWs w;
+    char* p = (char*)base;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += align256(bytes); return (void*)r; };
+    // the label plane first: its place depends on nb and hw only, so the specs of one resized size share it whatever their T
+    w.wlab = (uint32_t*)take(n * 4);
+    w.ll = (int*)take(n * 4);
+    w.sl = (unsigned*)take(n * 4);
+    w.keys = (unsigned long long*)take(T * nb * cap * 8);
+    w.cnt = (unsigned*)take(T * nb * cap * 4);
+    w.w0 = (uint32_t*)take(2 * n * 4);
+    w.w1 = (uint32_t*)take(2 * n * 4);
+    w.ml = (uint32_t*)take(2 * n * 4);
+    w.lp = (int*)take(T * n * 4);
+    w.sp = (unsigned*)take(T * n * 4);
+    w.mp = (unsigned char*)take(T * n);
+    w.bytes = off;
+    return w;
+}
+
+static int fp16_scaled(int n, float rf) {
+    const _Float16 a = (_Float16)(float)n, b = (_Float16)rf;
+    const _Float16 c = (_Float16)(a * b);      // tf.cast(size, float16) * resize_factor: a float16 product (metrics.py:199-200)
+    const float f = (float)c;
+    if (!(f >= 1.f) || f > 1e9f) return 0;
+    return (int)f;                             // tf.cast(..., int32) truncates
+}
+
+int region_spec_check(const dnnca_region_spec* s, int h, int w, RegionSpecHost& out) {
+    if (!s) { set_error("null region spec"); return DNNCA_EINVAL; }
+    if (s->n_thresholds < 1 || s->n_thresholds > kRegionMaxThr || !s->thresholds) {
+        set_error("region spec: %d thresholds (1..%d)", s->n_thresholds, kRegionMaxThr);
+        return DNNCA_EINVAL;
+    }
+    out.thr.assign(s->thresholds, s->thresholds + s->n_thresholds);
+    for (int t = 0; t < s->n_thresholds; ++t)
+        if (!(out.thr[t] >= 0.f)) {                // metrics.py:96 tf.debugging.assert_non_negative(thresholds); NaN too
+            set_error("region spec: threshold %d is %g (must be >= 0)", t, (double)out.thr[t]);
+            return DNNCA_EINVAL;
+        }
+    if (!(s->iou_threshold >= 0.f && s->iou_threshold < 1.f)) {
+        set_error("region spec: IoU threshold %g outside [0, 1)", (double)s->iou_threshold);
+        return DNNCA_EINVAL;
+    }
+    if (!(s->resize_factor > 0.f) || !std::isfinite(s->resize_factor)) {
+        set_error("region spec: resize factor %g", (double)s->resize_factor);
+        return DNNCA_EINVAL;
+    }
+    if (s->morph_filter_size < 1 || s->morph_filter_size > kRegionMaxK) {
+        set_error("region spec: morph_filter_size %d outside 1..%d", s->morph_filter_size, kRegionMaxK);
+        return DNNCA_EINVAL;
+    }
+    out.iou = s->iou_threshold;
+    out.rf = s->resize_factor;
+    out.k = s->morph_filter_size;
+    out.oh = fp16_scaled(h, s->resize_factor);
+    out.ow = fp16_scaled(w, s->resize_factor);
+    if (out.oh < 1 || out.ow < 1) {
+        set_error("region spec: resize factor %g maps %d x %d to an empty image", (double)s->resize_factor, h, w);
+        return DNNCA_EINVAL;
+    }
+    return DNNCA_OK;
+}
+
+static int region_state(Model* M) {
+    if (!M->region) M->region = new RegionState();
+    return DNNCA_OK;
+}
+
+int region_prepare(Model* M, const std::vector<RegionSpecHost>& specs, int max_batch, int h, int w) {
+    (void)h;
+    (void)w;
+    DN_TRY(region_state(M));
+    RegionState& R = *M->region;
+    R.specs = specs;
+    R.order.resize(specs.size());
+    for (size_t i = 0; i < specs.size(); ++i) R.order[i] = (int)i;
+    std::stable_sort(R.order.begin(), R.order.end(), [&](int a, int b) {
+        return std::make_pair(specs[a].oh, specs[a].ow) < std::make_pair(specs[b].oh, specs[b].ow);
+    });
+    size_t hw = 1, T = 1;
+    for (const auto& s : specs) {
+        hw = std::max(hw, (size_t)s.oh * s.ow);
+        T = std::max(T, s.thr.size());
+    }
+    if ((size_t)T * hw * 2 >= (size_t)INT32_MAX) { set_error("region metrics: slices of %zu pixels are too large", hw); return DNNCA_EINVAL; }
+    size_t chunk = std::max<size_t>(1, kRegionBudget / (T * hw));
+    chunk = std::min(chunk, (size_t)std::max(max_batch, 1));
+    chunk = std::min(chunk, (size_t)65535 / T);           // grid z of the tile kernels: T x chunk
+    while (chunk > 1 && T * chunk * hw >= (size_t)INT32_MAX / 2) --chunk;
+    R.chunk = (int)chunk;
+    const size_t need = region_layout(nullptr, chunk, hw, T).bytes;
+    if (need > R.ws_bytes) {
+        if (R.ws) HIP_TRY(hipFree(R.ws));
+        R.ws = nullptr;
+        R.ws_bytes = 0;
+        HIP_TRY(hipMalloc(&R.ws, need));
+        R.ws_bytes = need;
+    }
+    if (specs.size() > R.acc_specs) {
+        if (R.acc) HIP_TRY(hipFree(R.acc));
+        if (R.thr_dev) HIP_TRY(hipFree(R.thr_dev));
+        R.acc = nullptr;
+        R.thr_dev = nullptr;
+        R.acc_specs = 0;
+        HIP_TRY(hipMalloc((void**)&R.acc, specs.size() * kRegionMaxThr * 4 * 8));
+        HIP_TRY(hipMalloc((void**)&R.thr_dev, specs.size() * kRegionMaxThr * 4));
+        R.acc_specs = specs.size();
+    }
+    std::vector<float> thr(specs.size() * kRegionMaxThr, 0.f);
+    for (size_t i = 0; i < specs.size(); ++i) std::copy(specs[i].thr.begin(), specs[i].thr.end(), thr.begin() + i * kRegionMaxThr);
+    HIP_TRY(hipMemcpyAsync(R.thr_dev, thr.data(), thr.size() * 4, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipMemsetAsync(R.acc, 0, specs.size() * kRegionMaxThr * 4 * 8, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));        // `thr` is a local
+    return DNNCA_OK;
+}
+
+// connected components of the T planes of `words` (nb slices of h x w) into L
+static void region_ccl(Model* M, const uint32_t* words, int T, int nb, int h, int w, int* L) {
+    const size_t total = (size_t)T * nb * h * w;
+    const dim3 tiles((w + kTile - 1) / kTile, (h + kTile - 1) / kTile, T * nb);
+    LAUNCH(M, "region_ccl_tile", total * 8.0 / 32 * (T > 32 ? 2 : 1) + total * 4.0, 0,
+           hipLaunchKernelGGL(k_region_ccl_tile, tiles, dim3(RB), 0, M->stream, words, nb, h, w, L));
+    LAUNCH(M, "region_ccl_merge", total * 4.0, 0,
+           hipLaunchKernelGGL(k_region_ccl_merge, dim3(nblocks(total)), dim3(RB), 0, M->stream, L, total, h, w));
+    LAUNCH(M, "region_ccl_compress", total * 8.0, 0,
+           hipLaunchKernelGGL(k_region_ccl_compress, dim3(nblocks(total)), dim3(RB), 0, M->stream, L, total));
+}
+
+int region_accumulate(Model* M, const float* prob, const float* y, int batch, int h, int w) {
+    if (!M->region || M->region->specs.empty()) { set_error("region metrics: no specs prepared"); return DNNCA_ESTATE; }
+    RegionState& R = *M->region;
+    hipStream_t s = M->stream;
+    for (int b0 = 0; b0 < batch; b0 += R.chunk) {
+        const int nb = std::min(R.chunk, batch - b0);
+        const float* pb = prob + (size_t)b0 * h * w;
+        const float* yb = y + (size_t)b0 * h * w;
+        int lab_h = 0, lab_w = 0;
+        for (int si : R.order) {
+            const RegionSpecHost& sp = R.specs[si];
+            const int T = (int)sp.thr.size(), oh = sp.oh, ow = sp.ow;
+            const size_t hw = (size_t)oh * ow, n = (size_t)nb * hw, cap = hw + 1, slots = (size_t)T * nb * cap;
+            const RegionWs ws = region_layout(R.ws, nb, hw, T);
+            Resize rz{h, w, oh, ow, (float)h / (float)oh, (float)w / (float)ow, (oh == h && ow == w) ? 1 : 0};
+            if (oh != lab_h || ow != lab_w) {              // the label plane of this size: once for every spec that shares it
+                LAUNCH(M, "region_prep", n * 4.0 + (double)nb * h * w * 4, 0,
+                       hipLaunchKernelGGL(k_region_prep, dim3(nblocks(n)), dim3(RB), 0, s, yb, rz, nb, (const float*)nullptr, 0, ws.wlab));
+                region_ccl(M, ws.wlab, 1, nb, oh, ow, ws.ll);
+                HIP_TRY(hipMemsetAsync(ws.sl, 0, n * 4, s));
+                LAUNCH(M, "region_sizes", n * 4.0, 0,
+                       hipLaunchKernelGGL(k_region_sizes, dim3(nblocks(n)), dim3(RB), 0, s, ws.ll, n, ws.sl));
+                lab_h = oh;
+                lab_w = ow;
+            }
+            const int nw = T > 32 ? 2 : 1;
+            LAUNCH(M, "region_prep", n * 4.0 * nw + (double)nb * h * w * 4, 0,
+                   hipLaunchKernelGGL(k_region_prep, dim3(nblocks(n)), dim3(RB), 0, s, pb, rz, nb, R.thr_dev + (size_t)si * kRegionMaxThr,
+                                      T, ws.w0));
+            const uint32_t* mask = ws.w0;
+            if (sp.k > 1) {
+                const dim3 tiles((ow + kTile - 1) / kTile, (oh + kTile - 1) / kTile, nw * nb);
+                LAUNCH(M, "region_open", n * 8.0 * nw, 0,
+                       hipLaunchKernelGGL(k_region_open, tiles, dim3(RB), 0, s, ws.w0, ws.w1, oh, ow, sp.k, n, nb));
+                mask = ws.w1;
+            }
+            region_ccl(M, mask, T, nb, oh, ow, ws.lp);
+            HIP_TRY(hipMemsetAsync(ws.sp, 0, (size_t)T * n * 4, s));
+            LAUNCH(M, "region_sizes", (double)T * n * 4, 0,
+                   hipLaunchKernelGGL(k_region_sizes, dim3(nblocks((size_t)T * n)), dim3(RB), 0, s, ws.lp, (size_t)T * n, ws.sp));
+            HIP_TRY(hipMemsetAsync(ws.keys, 0xff, slots * 8, s));
+            HIP_TRY(hipMemsetAsync(ws.cnt, 0, slots * 4, s));
+            HIP_TRY(hipMemsetAsync(ws.ml, 0, (size_t)nw * n * 4, s));
+            HIP_TRY(hipMemsetAsync(ws.mp, 0, (size_t)T * n, s));
+            LAUNCH(M, "region_pairs", (double)T * n * 4 + n * 4.0, 0,
+                   hipLaunchKernelGGL(k_region_pairs, dim3(nblocks((size_t)T * n)), dim3(RB), 0, s, ws.ll, ws.lp, T, nb, hw, cap, ws.keys,
+                                      ws.cnt));
+            LAUNCH(M, "region_match", slots * 12.0, 0,
+                   hipLaunchKernelGGL(k_region_match, dim3(nblocks(slots)), dim3(RB), 0, s, ws.keys, ws.cnt, slots, cap, nb, hw, ws.sl,
+                                      ws.sp, sp.iou, ws.ml, ws.mp));
+            unsigned cb = nblocks(n);
+            if (cb > 256) cb = 256;
+            LAUNCH(M, "region_count", (double)T * n * 5 + n * 8.0, 0,
+                   hipLaunchKernelGGL(k_region_count, dim3(cb, T), dim3(RB), 0, s, ws.ll, ws.lp, ws.ml, ws.mp, n,
+                                      R.acc + (size_t)si * kRegionMaxThr * 4));
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return DNNCA_OK;
+}
+
+int region_read(Model* M, std::vector<std::vector<dnnca_region_counts>>& counts) {
+    if (!M->region) { set_error("region metrics: no specs prepared"); return DNNCA_ESTATE; }
+    RegionState& R = *M->region;
+    std::vector<unsigned long long> h(R.specs.size() * kRegionMaxThr * 4);
+    HIP_TRY(hipMemcpyAsync(h.data(), R.acc, h.size() * 8, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    counts.assign(R.specs.size(), {});
+    for (size_t i = 0; i < R.specs.size(); ++i) {
+        for (size_t t = 0; t < R.specs[i].thr.size(); ++t) {
+            const unsigned long long* a = &h[(i * kRegionMaxThr + t) * 4];
+            counts[i].push_back(dnnca_region_counts{(int64_t)a[0], (int64_t)a[1], (int64_t)a[2], (int64_t)a[3]});
+        }
+    }
+    return DNNCA_OK;
+}
+
+int region_inputs(Model* M, size_t n, float** prob_dev, float** y_dev) {
+    DN_TRY(region_state(M));
+    RegionState& R = *M->region;
+    if (n > R.in_n) {
+        if (R.in_prob) HIP_TRY(hipFree(R.in_prob));
+        if (R.in_y) HIP_TRY(hipFree(R.in_y));
+        R.in_prob = R.in_y = nullptr;
+        R.in_n = 0;
+        HIP_TRY(hipMalloc((void**)&R.in_prob, n * 4));
+        HIP_TRY(hipMalloc((void**)&R.in_y, n * 4));
+        R.in_n = n;
+    }
+    *prob_dev = R.in_prob;
+    *y_dev = R.in_y;
+    return DNNCA_OK;
+}
+
+void region_release(Model* M) {
+    if (!M->region) return;
+    RegionState& R = *M->region;
+    for (void* p : {(void*)R.thr_dev, (void*)R.acc, R.ws, (void*)R.in_prob, (void*)R.in_y})
+        if (p) (void)hipFree(p);
+    delete M->region;
+    M->region = nullptr;
+}
+
+}  // namespace dnnca

@@ -75,6 +75,8 @@ struct KStat {
 constexpr float kBnMomentum = 0.99f;   // Keras BatchNormalization defaults [TF-2.6]
 constexpr float kBnEps = 1e-3f;
 
+struct RegionState;                      // kernels_region.hip
+
 struct Model {
     dnnca_model_desc desc;
     int device = 0;
@@ -180,6 +182,9 @@ struct Model {
     // up over the batches (exact integer counts); it is read once, at the end
     bool eval_active = false;
     std::vector<int> eval_order;         // thresholds: sorted position -> the caller's position
+    // region metrics (kernels_region.hip): specs, accumulators and workspace; region_eval: the staged eval steps add region counts
+    RegionState* region = nullptr;
+    bool region_eval = false;
     float* out_ring = nullptr;           // pinned host memory: kStageSlots x 8 floats (out5 of the step that used the slot)
     // measurement
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -13,6 +13,7 @@
 
 #include "fast.h"
 #include "kernels.h"
+#include "region.h"
 
 namespace dnnca {
 
@@ -28,6 +29,7 @@ void set_error(const char* fmt, ...) {
 enum { kScalars = 8 };
 
 Model::~Model() {
+    region_release(this);
     fast_release(this);
     ig_release(this);
     for (void* a : allocs) (void)hipFree(a);
@@ -1231,6 +1233,7 @@ int dnnca_eval_begin(void* model, const float* thresholds, int n) {
     M->eval_order.clear();
     if (n > 0) DN_TRY(confusion_begin(M, thresholds, n, M->eval_order));
     M->eval_active = true;
+    M->region_eval = false;
     return DNNCA_OK;
 }
 
@@ -1248,6 +1251,7 @@ int dnnca_eval_step_staged(void* model, int slot, const float* x_dev, const floa
     if (n > 0)      // the metrics see the labels as given (a smoothed copy exists only inside the loss, utils/losses.py:62-67)
         g_confusion_hist(M->stream, (size_t)batch * M->outH * M->outW, M->prob, y_dev, M->thr_dev, n,
                          reinterpret_cast<unsigned long long*>(M->conf_dev));
+    if (M->region_eval) DN_TRY(region_accumulate(M, M->prob, y_dev, batch, M->outH, M->outW));
     HIP_TRY(hipMemcpyAsync(M->out_ring + slot * 8, M->out5, 5 * sizeof(float), hipMemcpyDeviceToHost, M->stream));
     HIP_TRY(hipEventRecord(sl.done, M->stream));
     sl.has_done = true;
@@ -1353,6 +1357,63 @@ int dnnca_pixel_confusion_of(void* model, const float* prob_hw, const float* y_h
     HIP_TRY(hipMemcpyAsync(M->prob, prob_hw, (size_t)n_pixels * 4, hipMemcpyHostToDevice, M->stream));
     HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, (size_t)n_pixels * 4, hipMemcpyHostToDevice, M->stream));
     return confusion_counts(M, (size_t)n_pixels, thresholds, n, out);
+}
+
+// ---- region-based metrics (kernels_region.hip) --------------------------------------------------------------------------
+static int region_one(Model* M, const float* prob_dev, const float* y_dev, int batch, int h, int w, const dnnca_region_spec* spec,
+                      dnnca_region_counts* out) {
+    if (M->region_eval) { set_error("dnnca_region_confusion* inside dnnca_eval_region_begin .. dnnca_eval_region_end"); return DNNCA_ESTATE; }
+    std::vector<RegionSpecHost> specs(1);
+    DN_TRY(region_spec_check(spec, h, w, specs[0]));
+    DN_TRY(region_prepare(M, specs, batch, h, w));
+    DN_TRY(region_accumulate(M, prob_dev, y_dev, batch, h, w));
+    std::vector<std::vector<dnnca_region_counts>> counts;
+    DN_TRY(region_read(M, counts));
+    std::copy(counts[0].begin(), counts[0].end(), out);
+    return DNNCA_OK;
+}
+
+int dnnca_region_confusion_of(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w,
+                              const dnnca_region_spec* spec, dnnca_region_counts* out) {
+    MODEL(model);
+    if (!prob_hw || !y_hw || !spec || !out || batch < 1 || h < 1 || w < 1) { set_error("bad region confusion arguments"); return DNNCA_EINVAL; }
+    const size_t n = (size_t)batch * h * w;
+    float *p_dev = nullptr, *y_dev = nullptr;
+    DN_TRY(region_inputs(M, n, &p_dev, &y_dev));
+    HIP_TRY(hipMemcpyAsync(p_dev, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipMemcpyAsync(y_dev, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+    return region_one(M, p_dev, y_dev, batch, h, w, spec, out);
+}
+
+int dnnca_region_confusion(void* model, const float* y_hw, int batch, const dnnca_region_spec* spec, dnnca_region_counts* out) {
+    MODEL(model);
+    if (!y_hw || !spec || !out) { set_error("bad region confusion arguments"); return DNNCA_EINVAL; }
+    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch out of range"); return DNNCA_EINVAL; }
+    const size_t n = (size_t)batch * M->outH * M->outW;
+    HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+    return region_one(M, M->prob, M->y_stage, batch, M->outH, M->outW, spec, out);
+}
+
+int dnnca_eval_region_begin(void* model, const dnnca_region_spec* specs, int n) {
+    MODEL(model);
+    if (!M->eval_active) { set_error("dnnca_eval_region_begin outside dnnca_eval_begin .. dnnca_eval_end"); return DNNCA_ESTATE; }
+    if (n < 1 || !specs) { set_error("dnnca_eval_region_begin: no specs"); return DNNCA_EINVAL; }
+    std::vector<RegionSpecHost> hs(n);
+    for (int i = 0; i < n; ++i) DN_TRY(region_spec_check(specs + i, M->outH, M->outW, hs[i]));
+    DN_TRY(region_prepare(M, hs, M->desc.max_batch, M->outH, M->outW));
+    M->region_eval = true;
+    return DNNCA_OK;
+}
+
+int dnnca_eval_region_end(void* model, dnnca_region_counts* out) {
+    MODEL(model);
+    if (!M->region_eval) { set_error("dnnca_eval_region_end without dnnca_eval_region_begin"); return DNNCA_ESTATE; }
+    M->region_eval = false;
+    if (!out) { set_error("null region counts output"); return DNNCA_EINVAL; }
+    std::vector<std::vector<dnnca_region_counts>> counts;
+    DN_TRY(region_read(M, counts));
+    for (const auto& c : counts) out = std::copy(c.begin(), c.end(), out);
+    return DNNCA_OK;
 }
 
 // ------------------------------------------------------------------------------------------------- data parallel

@@ -1,0 +1,32 @@
+// region.h -- region-based (lesion-level) metrics on the device (kernels_region.hip): the host side of the pipeline that the C ABI
+// of model.hip drives (dnnca_region_confusion*, dnnca_eval_region_*).
+#pragma once
+#include "model.h"
+
+namespace dnnca {
+
+constexpr int kRegionMaxThr = 64;        // thresholds per spec (two 32-bit mask words per pixel)
+constexpr int kRegionMaxK = 15;          // morphological filter size
+
+// one validated spec: the caller's thresholds (in their order), IoU threshold, resize factor, filter size, and the resized plane
+struct RegionSpecHost {
+    std::vector<float> thr;
+    float iou = 0.3f, rf = 1.f;
+    int k = 5;
+    int oh = 0, ow = 0;                  // int(fp16(H) * fp16(rf)), int(fp16(W) * fp16(rf))
+};
+
+// checks one caller spec against slices of h x w; fills `out` or returns DNNCA_EINVAL with the reason in dnnca_last_error
+int region_spec_check(const dnnca_region_spec* s, int h, int w, RegionSpecHost& out);
+// uploads the specs' thresholds and zeroes the uint64 accumulators [n_specs][kRegionMaxThr][4]; sizes the workspace for batches of
+// up to max_batch slices of h x w
+int region_prepare(Model* M, const std::vector<RegionSpecHost>& specs, int max_batch, int h, int w);
+// the counts of `batch` slices prob [batch, h, w] / y [batch, h, w] (device) added to the accumulators of every spec
+int region_accumulate(Model* M, const float* prob, const float* y, int batch, int h, int w);
+// synchronises and reads the accumulators: counts[i] = spec i's T entries in the caller's threshold order
+int region_read(Model* M, std::vector<std::vector<dnnca_region_counts>>& counts);
+// device buffers of the caller-supplied slices (dnnca_region_confusion_of), grown on demand
+int region_inputs(Model* M, size_t n, float** prob_dev, float** y_dev);
+void region_release(Model* M);
+
+}  // namespace dnnca

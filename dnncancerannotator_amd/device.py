@@ -94,6 +94,25 @@ class DeviceView:
         return out
 
 
+def region_specs(specs):
+    """[(thresholds, iou_threshold, resize_factor, morph_filter_size)] -> (dnnca_region_spec array, threshold arrays to keep alive)"""
+    keep = [as_f32(np.atleast_1d(np.asarray(s[0], np.float32))).ravel() for s in specs]
+    arr = (_lib.RegionSpec * max(len(specs), 1))()
+    for a, s, thr in zip(arr, specs, keep):
+        a.thresholds, a.n_thresholds = fptr(thr), thr.size
+        a.iou_threshold, a.resize_factor, a.morph_filter_size = float(s[1]), float(s[2]), int(s[3])
+    return arr, keep
+
+
+def split_region_counts(out, sizes):
+    rows = np.array([(c.tp_label, c.fn, c.tp_pred, c.fp) for c in out[:sum(sizes)]], np.int64).reshape(-1, 4)
+    res, lo = [], 0
+    for n in sizes:
+        res.append(rows[lo:lo + n])
+        lo += n
+    return res
+
+
 class StagingRing:
     """The model's staging slots in HBM + its copy stream (include/dnnca.h, dnnca_stage_*): what ds.prefetch + Keras' asynchronous
     input feeding are for the reference (annotator/data.py:110,143; engine.py:126-135).  `upload` may run on a second thread."""
@@ -150,6 +169,20 @@ class StagingRing:
         out = (_lib.Confusion * max(self._n_thr, 1))()
         check(self.dm.lib.dnnca_eval_end(self.dm.handle, out))
         return [(c.tp, c.fp, c.fn, c.tn) for c in out[:self._n_thr]]
+
+    # region-based metrics of the same evaluation (kernels_region.hip): between eval_begin and the first eval_step
+    def eval_region_begin(self, specs):
+        """specs: [RegionSpec-like (thresholds, iou_threshold, resize_factor, morph_filter_size)]; every later eval_step adds its
+        batch's region counts on the device"""
+        arr, self._region_keep = region_specs(specs)
+        self._region_n = [len(k) for k in self._region_keep]
+        check(self.dm.lib.dnnca_eval_region_begin(self.dm.handle, arr, len(self._region_n)))
+
+    def eval_region_end(self):
+        """[array [T, 4] int64 (tp_label, fn, tp_pred, fp) per spec of eval_region_begin], summed over every eval_step since"""
+        out = (_lib.RegionCounts * sum(self._region_n))()
+        check(self.dm.lib.dnnca_eval_region_end(self.dm.handle, out))
+        return split_region_counts(out, self._region_n)
 
     def out(self, slot):
         """waits for the step that last ran on the slot; raises what train_step would have raised (label / weight assertions)"""
@@ -366,6 +399,28 @@ class DeviceModel:
         out = (_lib.Confusion * thr.size)()
         check(self.lib.dnnca_pixel_confusion_of(self.handle, fptr(prob), fptr(y), prob.size, fptr(thr), thr.size, out))
         return [(c.tp, c.fp, c.fn, c.tn) for c in out]
+
+    def region_confusion(self, y, spec):
+        """region counts of the last forward / eval probabilities against y [B, H, W]: int64 [T, 4] (tp_label, fn, tp_pred, fp).
+        spec: (thresholds, iou_threshold, resize_factor, morph_filter_size)"""
+        y = as_f32(y)
+        arr, keep = region_specs([spec])
+        out = (_lib.RegionCounts * keep[0].size)()
+        check(self.lib.dnnca_region_confusion(self.handle, fptr(y), y.shape[0], arr, out))
+        return split_region_counts(out, [keep[0].size])[0]
+
+    def region_confusion_of(self, prob, y, spec):
+        """region counts of caller-supplied probabilities and labels [B, h, w] (any size): int64 [T, 4]"""
+        prob, y = as_f32(prob), as_f32(y)
+        if prob.ndim == 4:
+            prob = prob[..., 0]
+        if prob.shape != y.shape or prob.ndim != 3:
+            raise ValueError('prob %s and y %s must both be [B, h, w]' % (prob.shape, y.shape))
+        arr, keep = region_specs([spec])
+        out = (_lib.RegionCounts * keep[0].size)()
+        B, h, w = y.shape
+        check(self.lib.dnnca_region_confusion_of(self.handle, fptr(np.ascontiguousarray(prob)), fptr(y), B, h, w, arr, out))
+        return split_region_counts(out, [keep[0].size])[0]
 
     # ---- device-side augmentation (annotator/data.py:62-111 train_ds) ------------------------------------------
     def augment_u8(self, raw, params, out_size, label_index, contrast_channels=None, src_ptr=None):

@@ -19,7 +19,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import augment, device, distributed, losses as custom_losses, metrics as custom_metrics, models
+from . import augment, device, distributed, losses as custom_losses, metrics as custom_metrics, models, region_metrics
 from .feeder import BatchFeeder
 
 
@@ -71,7 +71,17 @@ class TFKerasModel:
         self.learning_rate_scheduler = deploy.pop('LearningRateScheduler', None)
         model = getattr(models, model_config['model'])(**model_config['model_options'])
         self.loss = custom_losses.get(deploy['loss']) if 'loss' in deploy else custom_losses.WeightedCrossentropy()
-        self.metrics = [m for m in map(custom_metrics.solve_metric, deploy.get('metrics', [])) if m is not None]
+        metric_specs = deploy.get('metrics', [])
+        # region_metrics: device -- the region-based metrics of deploy_options.metrics are counted on the GPU
+        # (region_metrics.py); without the key they are skipped with a warning (metrics.solve_metric)
+        region_mode = deploy.pop('region_metrics', None)
+        if region_mode not in (None, 'device'):
+            raise ValueError("deploy_options.region_metrics: only 'device' is supported, got %r" % (region_mode,))
+        self.region_metrics = []
+        if region_mode == 'device':
+            self.region_metrics = [m for m in map(region_metrics.solve_region_metric, metric_specs) if m is not None]
+            metric_specs = [s for s in metric_specs if not region_metrics.is_region_spec(s)]
+        self.metrics = [m for m in map(custom_metrics.solve_metric, metric_specs) if m is not None]
         if deploy.get('optimizer') != 'adam':
             raise NotImplementedError('only the reference\'s optimizer: adam is supported (engine.py:276-284)')
         self.learning_rate = 0.001          # engine.py:278
@@ -347,12 +357,19 @@ class TFKerasModel:
         the dataset is one test step per replica: the positive-rate class weight (utils/losses.py:24-27) is taken over the
         whole per-replica batch, never over a chunk of it."""
         cfg_kw = self.loss.device_cfg()
-        for m in self.metrics:
+        for m in self.metrics + self.region_metrics:
             m.reset_state()
+        region_groups = region_metrics.group_by_spec(self.region_metrics)
+
+        def region_update(dm_, y_):         # region counts of the step's probabilities: one device run per distinct spec
+            for spec, ms in region_groups:
+                c = dm_.region_confusion(y_, spec)
+                for m in ms:
+                    m.add_counts(c)
         total, count = 0.0, 0
         shard = self._shard_fn(dataset)
         if staged and self._staged_eval_possible():
-            total, count, dataset = self._evaluate_staged(dataset, cfg_kw, shard)      # what is left: batches the ring could not take
+            total, count, dataset = self._evaluate_staged(dataset, cfg_kw, shard, region_groups)  # what is left: batches the ring could not take
         for el in dataset:
             x, y = augment.raw_to_float(el) if isinstance(el, augment.RawBatch) else el
             x, y = shard(np.asarray(x), np.asarray(y))
@@ -365,6 +382,7 @@ class TFKerasModel:
                 count += len(x)
                 for m in self.metrics:
                     m.update_state(dm, y)
+                region_update(dm, y)
             elif len(x):
                 # HBM cannot hold the batch in one step: chunks, each with the weight of the WHOLE batch passed explicitly
                 kw = dict(cfg_kw)
@@ -382,15 +400,20 @@ class TFKerasModel:
                     count += len(xb)
                     for m in self.metrics:
                         m.update_state(dm, yb)
+                    region_update(dm, yb)       # region metrics are per slice: chunks give the counts of the whole batch
         if self.ctx.world > 1:
             dm = self.device_model
             total, count = (float(v) for v in dm.comm_allreduce([total, count]))
             for m in self.metrics:                      # counts travel as doubles: exact far beyond 2^24 pixels
                 m.merge(lambda c: np.asarray(dm.comm_allreduce(c.ravel()), np.float64).reshape(c.shape))
+            for m in self.region_metrics:               # integer counts, exact as doubles
+                m.merge(lambda c: np.asarray(dm.comm_allreduce(c.ravel()), np.float64).reshape(c.shape))
         results = OrderedDict(loss=total / max(count, 1))
         for m in self.metrics:
             r = m.result()
             results[m.name] = float(r) if np.ndim(r) == 0 else [float(v) for v in r]
+        for m in self.region_metrics:
+            results[m.name] = m.result()
         return results
 
     def _staged_eval_possible(self):
@@ -398,10 +421,11 @@ class TFKerasModel:
         return (hasattr(self.device_model, 'staging') and not os.environ.get('DNNCA_NO_FEEDER') and n_thr <= 1024 and
                 all(hasattr(m, 'thresholds') and hasattr(m, 'counts') for m in self.metrics))
 
-    def _evaluate_staged(self, dataset, cfg_kw, shard):
+    def _evaluate_staged(self, dataset, cfg_kw, shard, region_groups=()):
         """The test steps of _evaluate over the staging ring (feeder.py): batches travel to HBM on the copy stream while the
         previous one is evaluated, every metric's thresholds share ONE confusion histogram that stays on the device and is read
-        once at the end (exact integer counts), and a batch's loss is read one step late.  Returns (loss sum, sample count,
+        once at the end (exact integer counts), and a batch's loss is read one step late.  Region metrics (region_groups: one
+        device spec each) count on the device beside the histogram and are read once too.  Returns (loss sum, sample count,
         the batches the ring could not take -- larger than max_batch -- for the chunked path)."""
         dm = self.device_model
         source = iter(dataset)
@@ -417,7 +441,11 @@ class TFKerasModel:
         cfg = dm.loss_cfg(**cfg_kw)
         total, count, left, pending = 0.0, 0, [], None
         ring.eval_begin(thr)
+        region_on = False
         try:
+            if region_groups:
+                ring.eval_region_begin([spec for spec, _ in region_groups])
+                region_on = True
             for item in feeder:
                 if item[0] == 'host':
                     left.append(item[1])
@@ -442,11 +470,15 @@ class TFKerasModel:
                 count += pending[1]
         finally:
             feeder.close()
+            region_counts = ring.eval_region_end() if region_on else []
             counts = np.asarray(ring.eval_end(), np.float64).reshape(-1, 4)
         lo = 0
         for m in self.metrics:
             m.counts += counts[lo:lo + len(m.thresholds)]
             lo += len(m.thresholds)
+        for (_, ms), c in zip(region_groups, region_counts):
+            for m in ms:
+                m.add_counts(c)
         return total, count, left
 
     def eval(self, dataset, save_path, viz_ds=None, tag='val', avoid_overwrite=False, export_path=None, export_images=False,

@@ -206,6 +206,37 @@ int dnnca_pixel_confusion(void* model, const float* y_hw, int batch, const float
 int dnnca_pixel_confusion_of(void* model, const float* prob_hw, const float* y_hw, int64_t n_pixels, const float* thresholds,
                              int n, dnnca_confusion* out);
 
+/* ---- region-based (lesion-level) metrics (utils/metrics.py:80-510; the region entries of configs/additionals/metrics.yaml) ------
+ * Per slice: label and probability resized to (int(fp16(H) * fp16(rf)), int(fp16(W) * fp16(rf))) by tf.image.resize bilinear
+ * (rf = 1: identity), label' > 0.5, prediction prob' >= thresholds[t] opened by a k x k erosion + dilation (utils/image.py:12-26,
+ * out-of-bounds pixels ignored), 4-connected components of both, IoU(L_i, P_j) = float(|L_i n P_j|) / float(|L_i u P_j|) > iou.
+ *   tp_label  label components with some IoU > iou_threshold        fn  label components with none
+ *   tp_pred   prediction components with some IoU > iou_threshold   fp  prediction components with none
+ * Counts are exact integers summed over the slices, one entry per threshold in the caller's order.  Limits: 1..64 thresholds, each
+ * >= 0 (metrics.py:96); iou_threshold in [0, 1); resize_factor > 0 with a non-empty result; morph_filter_size 1..15; otherwise
+ * DNNCA_EINVAL. */
+typedef struct dnnca_region_spec {
+    const float* thresholds;     /* host array of n_thresholds */
+    int32_t n_thresholds;
+    float iou_threshold;         /* IoU_threshold, metrics.py:93 (0.30) */
+    float resize_factor;         /* resize_factor (1.0; metrics.yaml: 0.5) */
+    int32_t morph_filter_size;   /* morph_filter_size (5) */
+} dnnca_region_spec;
+typedef struct dnnca_region_counts { int64_t tp_label, fn, tp_pred, fp; } dnnca_region_counts;
+/* region counts of caller-supplied slices: prob_hw / y_hw are host buffers [batch, h, w] of any size (the library grows its own
+ * device buffers); out has spec->n_thresholds entries */
+int dnnca_region_confusion_of(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w,
+                              const dnnca_region_spec* spec, dnnca_region_counts* out);
+/* the same on the probabilities of the last forward / eval step (like dnnca_pixel_confusion); y_hw is a host buffer [batch, H, W] */
+int dnnca_region_confusion(void* model, const float* y_hw, int batch, const dnnca_region_spec* spec, dnnca_region_counts* out);
+/* staged evaluation with region metrics: call dnnca_eval_region_begin after dnnca_eval_begin and before the first
+ * dnnca_eval_step_staged; every staged eval step then also adds the region counts of its batch for each of the n specs (on the
+ * device, no host round trip); dnnca_eval_region_end, after the last step and before or after dnnca_eval_end, synchronises and
+ * writes sum(n_thresholds) entries, spec after spec.  Without dnnca_eval_region_begin a staged evaluation launches nothing of it.
+ * dnnca_region_confusion* must not be called in between. */
+int dnnca_eval_region_begin(void* model, const dnnca_region_spec* specs, int n);
+int dnnca_eval_region_end(void* model, dnnca_region_counts* out);
+
 /* ---- data parallel: tf.distribute.MirroredStrategy (engine.py:260-263) re-done as one process per GPU + RCCL ---- */
 int dnnca_comm_unique_id(void* id_out /* DNNCA_UNIQUE_ID_BYTES */);
 int dnnca_comm_init(void* model, int rank, int world, const void* unique_id, size_t id_len);   /* world == 1: no-op */
