@@ -1,0 +1,142 @@
+"""Host side of the Visualizer of `annotator evaluate` (annotator/utils/callbacks.py:55-446, wired at engine.py:165-208): the
+casewise region counts and composite images come from the device (DeviceModel.region_confusion_slices / render_composite); this
+module names, places and writes them, with the standard library only.
+
+Settings engine.eval gives the reference's Visualizer: ratio 0.5, no prediction threshold, 100 region thresholds i / 99, IoU 0.30,
+export_path_depth 3 and export_casewise_metrics True (hard-coded there, so --export_casewise_metrics changes nothing).
+
+Files under <export_path>/<tag>/ (callbacks.py _emit):
+    images/<last 3 components of the exam path>/<sliceID %02d>/step_<step %08d>.png           (--export_images)
+    csv/<last 3 components of the exam path>/<sliceID %02d>/step_<step %08d>_metrics.csv      (--export_csv)
+    casewise_results.csv: every slice of every evaluated checkpoint, in dataset order          (--export_csv)
+The CSV bytes are those of pandas' to_csv (`pd.DataFrame(series).T.to_csv()`, `pd.DataFrame(rows).to_csv()`): csv-module
+quoting, '\\n' line ends, an empty header cell for the index."""
+
+import csv
+import io
+import os
+import re
+import struct
+import zlib
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+RATIO = 0.5                      # Visualizer(ratio=0.5)
+N_THRESHOLDS = 100               # pr_region_nthreshold
+IOU_THRESHOLD = 0.30             # pr_IoU_threshold
+MORPH_FILTER_SIZE = 5            # RegionBasedConfusionMatrix's default
+EXPORT_PATH_DEPTH = 3
+THRESHOLDS = [i / float(N_THRESHOLDS - 1) for i in range(N_THRESHOLDS)]      # prepare_internal_metrics
+MAX_WORKERS = 16                 # PNG encoding and file writes: zlib releases the GIL
+PNG_LEVEL = 6                    # zlib's default level
+
+_TAG = re.compile(r'^path:(.*),sliceID:(.*)$')
+
+
+def device_spec():
+    """the region spec of the casewise counts: RegionBasedConfusionMatrix(THRESHOLDS, 0.30, resize_factor=RATIO), k = 5"""
+    return (np.asarray(THRESHOLDS, np.float32), IOU_THRESHOLD, RATIO, MORPH_FILTER_SIZE)
+
+
+def column_names(thresholds=THRESHOLDS):
+    """region_tp@PixelThreshold{t:.2} for every threshold, then region_fn@..., region_fp@..., then `tag`"""
+    return ['region_%s@PixelThreshold%s' % (kind, format(t, '.2')) for kind in ('tp', 'fn', 'fp') for t in thresholds] + ['tag']
+
+
+def tag_of(path, slice_id):
+    """make_summary_constructor: 'path:<exam path>,sliceID:<n>'"""
+    return 'path:%s,sliceID:%d' % (path, int(slice_id))
+
+
+def row_values(counts, tag):
+    """device counts [T, 4] (tp_label, fn, tp_pred, fp) of one slice -> the values of its row: tp..., fn..., fp..., tag
+    (get_tp_fn_fp(return_raw=True) counts detected lesions as tp)"""
+    c = np.asarray(counts, np.int64)
+    return [int(v) for v in c[:, 0]] + [int(v) for v in c[:, 1]] + [int(v) for v in c[:, 3]] + [tag]
+
+
+def export_dir(root, kind, tag, depth=EXPORT_PATH_DEPTH):
+    """<root>/<kind>/<last `depth` components of the exam path>/<sliceID %02d> for a tag (callbacks.py _emit)"""
+    m = _TAG.match(tag)
+    if m is None:
+        raise ValueError('not a Visualizer tag: %r' % (tag,))
+    parts = m.group(1).split('/')[-depth:]
+    return os.path.join(root, kind, *parts, '%02d' % int(m.group(2)))
+
+
+def image_path(root, tag, step):
+    return os.path.join(export_dir(root, 'images', tag), 'step_%08d.png' % int(step))
+
+
+def csv_path(root, tag, step):
+    return os.path.join(export_dir(root, 'csv', tag), 'step_%08d_metrics.csv' % int(step))
+
+
+def _csv(rows):
+    buf = io.StringIO()
+    w = csv.writer(buf, lineterminator='\n')
+    for r in rows:
+        w.writerow(r)
+    return buf.getvalue()
+
+
+def series_csv(names, values):
+    """pd.DataFrame(pd.Series(dict(zip(names, values)))).T.to_csv(): a header ',name1,...' and the row '0,v1,...'"""
+    return _csv([[''] + list(names), [0] + list(values)])
+
+
+def table_csv(names, rows):
+    """pd.DataFrame([series, ...]).to_csv(): rows numbered from 0; no rows -> '""\\n' (an empty frame)"""
+    if not rows:
+        return _csv([['']])
+    return _csv([[''] + list(names)] + [[i] + list(r) for i, r in enumerate(rows)])
+
+
+def _chunk(kind, data):
+    return struct.pack('>I', len(data)) + kind + data + struct.pack('>I', zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def encode_png(img, level=PNG_LEVEL):
+    """uint8 [h, w] / [h, w, 1] (8-bit grey) or [h, w, 3] (8-bit RGB) -> PNG bytes: one IDAT chunk, filter 0 on every row"""
+    a = np.ascontiguousarray(img, np.uint8)
+    if a.ndim == 2:
+        a = a[..., None]
+    h, w, c = a.shape
+    if c not in (1, 3):
+        raise ValueError('PNG: 1 or 3 channels, got %d' % c)
+    raw = np.zeros((h, 1 + w * c), np.uint8)
+    raw[:, 1:] = a.reshape(h, w * c)
+    ihdr = struct.pack('>IIBBBBB', w, h, 8, 0 if c == 1 else 2, 0, 0, 0)
+    return b'\x89PNG\r\n\x1a\n' + _chunk(b'IHDR', ihdr) + _chunk(b'IDAT', zlib.compress(raw.tobytes(), level)) + _chunk(b'IEND', b'')
+
+
+def _write(path, make, *args):
+    data = make(*args)
+    if isinstance(data, str):
+        data = data.encode()
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, 'wb') as f:
+        f.write(data)
+
+
+class Writer:
+    """Files of the Visualizer pass, encoded and written on up to MAX_WORKERS threads; at most `backlog` files wait at a time.
+    close() waits for every file and raises the first error."""
+
+    def __init__(self, workers=MAX_WORKERS, backlog=256):
+        self.pool = ThreadPoolExecutor(max(1, min(int(workers), MAX_WORKERS)), thread_name_prefix='dnnca-casewise')
+        self.backlog, self.pending = int(backlog), []
+
+    def submit(self, path, make, *args):
+        """writes make(*args) (bytes or str) to `path`, creating its directory"""
+        self.pending.append(self.pool.submit(_write, path, make, *args))
+        while len(self.pending) > self.backlog:
+            self.pending.pop(0).result()
+
+    def close(self):
+        try:
+            while self.pending:
+                self.pending.pop(0).result()
+        finally:
+            self.pool.shutdown(wait=True)

@@ -15,8 +15,14 @@
 //                   root), 64-bit CAS.  Overlap pixels of two different pairs are never 4-adjacent, so a slice of HW pixels has
 //                   at most ceil(HW / 2) pairs: HW + 1 slots per table keep the load below one half
 //   region_match    IoU = float(I) / float(|L| + |P| - I) > theta marks both roots (idempotent stores: no order dependence)
-//   region_count    roots -> tp_label / fn / tp_pred / fp: wave and block reductions, one uint64 atomicAdd per block and counter
+//   region_count    roots -> tp_label / fn / tp_pred / fp: wave and block reductions, one uint64 atomicAdd per block and counter;
+//                   summed over the chunk's slices (grid z = 1), or per slice (grid z = slice: the Visualizer's casewise counts)
 // Every count is an integer sum, so results are bit-exact and independent of which thread wins a race.
+//
+// The Visualizer's composite image (utils/callbacks.py generate_image + make_summary_constructor) is rendered here too:
+//   region_render   [features | label | probability] panels side by side, resized bilinear by `ratio` (the same float32 arithmetic
+//                   as region_prep), * 255 truncated to uint8; the panels are read in place through an index map, four output
+//                   bytes per thread and one 32-bit store
 #include <math.h>
 
 #include <algorithm>
@@ -322,14 +328,17 @@ __device__ __forceinline__ unsigned wave_sum(unsigned v) {
     return v;
 }
 
-// grid (blocks, T): acc[t][0..3] += tp_label, fn, tp_pred, fp of plane t
+// grid (blocks, T, Z): acc[z * acc_z + t * 4 + 0..3] += tp_label, fn, tp_pred, fp of plane t over pixels [z * per_z, (z + 1) * per_z)
+// of the chunk (Z = 1, per_z = n: the whole chunk; Z = slices, per_z = H W: one slice each)
 __global__ __launch_bounds__(RB) void k_region_count(const int* __restrict__ LL, const int* __restrict__ LP, const uint32_t* __restrict__ ML,
-                                                     const unsigned char* __restrict__ MP, size_t n, unsigned long long* __restrict__ acc) {
+                                                     const unsigned char* __restrict__ MP, size_t n, size_t per_z, size_t acc_z,
+                                                     unsigned long long* __restrict__ acc) {
     __shared__ unsigned part[RB / 64][4];
     const int t = blockIdx.y;
     unsigned c[4] = {0u, 0u, 0u, 0u};
     const size_t stride = (size_t)gridDim.x * RB;
-    for (size_t q = (size_t)blockIdx.x * RB + threadIdx.x; q < n; q += stride) {
+    const size_t q1 = (size_t)(blockIdx.z + 1) * per_z;
+    for (size_t q = (size_t)blockIdx.z * per_z + (size_t)blockIdx.x * RB + threadIdx.x; q < q1; q += stride) {
         if (LL[q] == (int)q) {
             const unsigned m = (ML[(size_t)(t >> 5) * n + q] >> (t & 31)) & 1u;
             c[0] += m;
@@ -351,8 +360,60 @@ __global__ __launch_bounds__(RB) void k_region_count(const int* __restrict__ LL,
     if (threadIdx.x < 4) {
         unsigned long long s = 0;
         for (int k = 0; k < RB / 64; ++k) s += part[k][threadIdx.x];
-        if (s) atomicAdd(acc + (size_t)t * 4 + threadIdx.x, s);
+        if (s) atomicAdd(acc + (size_t)blockIdx.z * acc_z + (size_t)t * 4 + threadIdx.x, s);
     }
+}
+
+// ---- composite image.  Composite column cc of a slice lies in panel cc / W: features 0 .. C-1, then the label (C), then the
+// probability (C + 1).  Overlay (3 channels): a feature panel is grey (the feature in every channel); the label / probability
+// panels are stack([label or prob, f0, f0]).  Without overlay there is one channel.
+struct Composite {
+    int H, W, C, Wc;                     // slices H x W with C feature channels; composite width Wc = W (C + 2)
+    int oh, ow, nch;                     // resized size; channels per pixel (1, overlay 3)
+    float sy, sx;                        // H / oh, Wc / ow as float (TF's CalculateResizeScale)
+};
+
+__device__ __forceinline__ float composite_at(const float* __restrict__ x, const float* __restrict__ lab, const float* __restrict__ prob,
+                                              const Composite& g, size_t slice, int r, int cc, int ch) {
+    const int panel = cc / g.W, col = cc - panel * g.W;
+    const size_t p = slice + (size_t)r * g.W + col;          // pixel index over [B, H, W]
+    if (panel < g.C) return x[p * g.C + panel];
+    if (ch > 0) return x[p * g.C];                            // overlay: green and blue of the label / probability panels = f0
+    return panel == g.C ? lab[p] : prob[p];
+}
+
+// out: uint8 [nb, oh, ow, nch] padded to whole 32-bit words; thread = word (4 bytes, one store)
+__global__ __launch_bounds__(RB) void k_region_render(const float* __restrict__ x, const float* __restrict__ lab, const float* __restrict__ prob,
+                                                      Composite g, int nb, uint32_t* __restrict__ out) {
+    const size_t total = (size_t)nb * g.oh * g.ow * g.nch;
+    const size_t word = (size_t)blockIdx.x * RB + threadIdx.x;
+    const size_t k0 = word * 4;
+    if (k0 >= total) return;
+    const size_t ohw = (size_t)g.oh * g.ow;
+    uint32_t packed = 0;
+    for (int e = 0; e < 4 && k0 + e < total; ++e) {
+        const size_t k = k0 + e, pix = k / g.nch;
+        const int ch = (int)(k - pix * g.nch);
+        const size_t b = pix / ohw;
+        const int q = (int)(pix - b * ohw), i = q / g.ow, j = q - i * g.ow;
+        const size_t slice = b * g.H * g.W;
+        // tf.image.resize bilinear, half-pixel centres, as resize_at (fp contract off: every product and sum rounded)
+        const float fy = ((float)i + 0.5f) * g.sy - 0.5f;
+        const float fx = ((float)j + 0.5f) * g.sx - 0.5f;
+        const float fy0 = floorf(fy), fx0 = floorf(fx);
+        const int y0 = max((int)fy0, 0), y1 = min((int)ceilf(fy), g.H - 1);
+        const int x0 = max((int)fx0, 0), x1 = min((int)ceilf(fx), g.Wc - 1);
+        const float ly = fy - fy0, lx = fx - fx0;
+        const float tl = composite_at(x, lab, prob, g, slice, y0, x0, ch), tr = composite_at(x, lab, prob, g, slice, y0, x1, ch);
+        const float bl = composite_at(x, lab, prob, g, slice, y1, x0, ch), br = composite_at(x, lab, prob, g, slice, y1, x1, ch);
+        const float top = tl + (tr - tl) * lx;
+        const float bot = bl + (br - bl) * lx;
+        const float v = (top + (bot - top) * ly) * 255.f;
+        // tf.cast(image * 255, uint8) truncates; values outside [0, 255] (and NaN) are clamped, where the cast is undefined
+        const float s = v > 0.f ? (v < 255.f ? v : 255.f) : 0.f;
+        packed |= (uint32_t)(int)s << (8 * e);
+    }
+    out[word] = packed;
 }
 
 inline unsigned nblocks(size_t n) { return (unsigned)((n + RB - 1) / RB); }
@@ -373,6 +434,12 @@ struct RegionState {
     float* in_prob = nullptr;            // dnnca_region_confusion_of inputs
     float* in_y = nullptr;
     size_t in_n = 0;
+    int label_batch = 0;                 // in_y holds the labels of dnnca_region_confusion_slices' `label_batch` slices (0: not)
+    // per-slice counts (dnnca_region_confusion_slices): uint64 [slices][n_specs][kRegionMaxThr][4]
+    unsigned long long* slice_acc = nullptr;
+    size_t slice_acc_n = 0, slices = 0;
+    uint32_t* viz = nullptr;             // rendered composites (dnnca_render_composite)
+    size_t viz_bytes = 0;
 };
 
 static constexpr size_t kRegionBudget = size_t(1) << 24;    // pixel-thresholds per chunk (~21 bytes each)
@@ -459,12 +526,13 @@ static int region_state(Model* M) {
     return DNNCA_OK;
 }
 
-int region_prepare(Model* M, const std::vector<RegionSpecHost>& specs, int max_batch, int h, int w) {
+int region_prepare(Model* M, const std::vector<RegionSpecHost>& specs, int max_batch, int h, int w, int slices) {
     (void)h;
     (void)w;
     DN_TRY(region_state(M));
     RegionState& R = *M->region;
     R.specs = specs;
+    R.slices = 0;
     R.order.resize(specs.size());
     for (size_t i = 0; i < specs.size(); ++i) R.order[i] = (int)i;
     std::stable_sort(R.order.begin(), R.order.end(), [&](int a, int b) {
@@ -503,6 +571,18 @@ int region_prepare(Model* M, const std::vector<RegionSpecHost>& specs, int max_b
     for (size_t i = 0; i < specs.size(); ++i) std::copy(specs[i].thr.begin(), specs[i].thr.end(), thr.begin() + i * kRegionMaxThr);
     HIP_TRY(hipMemcpyAsync(R.thr_dev, thr.data(), thr.size() * 4, hipMemcpyHostToDevice, M->stream));
     HIP_TRY(hipMemsetAsync(R.acc, 0, specs.size() * kRegionMaxThr * 4 * 8, M->stream));
+    if (slices > 0) {
+        const size_t na = (size_t)slices * specs.size() * kRegionMaxThr * 4;
+        if (na > R.slice_acc_n) {
+            if (R.slice_acc) HIP_TRY(hipFree(R.slice_acc));
+            R.slice_acc = nullptr;
+            R.slice_acc_n = 0;
+            HIP_TRY(hipMalloc((void**)&R.slice_acc, na * 8));
+            R.slice_acc_n = na;
+        }
+        HIP_TRY(hipMemsetAsync(R.slice_acc, 0, na * 8, M->stream));
+        R.slices = (size_t)slices;
+    }
     HIP_TRY(hipStreamSynchronize(M->stream));        // `thr` is a local
     return DNNCA_OK;
 }
@@ -519,9 +599,11 @@ static void region_ccl(Model* M, const uint32_t* words, int T, int nb, int h, in
            hipLaunchKernelGGL(k_region_ccl_compress, dim3(nblocks(total)), dim3(RB), 0, M->stream, L, total));
 }
 
-int region_accumulate(Model* M, const float* prob, const float* y, int batch, int h, int w) {
+int region_accumulate(Model* M, const float* prob, const float* y, int batch, int h, int w, bool per_slice) {
     if (!M->region || M->region->specs.empty()) { set_error("region metrics: no specs prepared"); return DNNCA_ESTATE; }
     RegionState& R = *M->region;
+    if (per_slice && (size_t)batch > R.slices) { set_error("region metrics: %d slices, %zu prepared", batch, R.slices); return DNNCA_ESTATE; }
+    const size_t acc_slice = R.specs.size() * kRegionMaxThr * 4;       // per-slice accumulator stride
     hipStream_t s = M->stream;
     for (int b0 = 0; b0 < batch; b0 += R.chunk) {
         const int nb = std::min(R.chunk, batch - b0);
@@ -569,11 +651,19 @@ int region_accumulate(Model* M, const float* prob, const float* y, int batch, in
             LAUNCH(M, "region_match", slots * 12.0, 0,
                    hipLaunchKernelGGL(k_region_match, dim3(nblocks(slots)), dim3(RB), 0, s, ws.keys, ws.cnt, slots, cap, nb, hw, ws.sl,
                                       ws.sp, sp.iou, ws.ml, ws.mp));
-            unsigned cb = nblocks(n);
-            if (cb > 256) cb = 256;
-            LAUNCH(M, "region_count", (double)T * n * 5 + n * 8.0, 0,
-                   hipLaunchKernelGGL(k_region_count, dim3(cb, T), dim3(RB), 0, s, ws.ll, ws.lp, ws.ml, ws.mp, n,
-                                      R.acc + (size_t)si * kRegionMaxThr * 4));
+            if (per_slice) {               // one z block row per slice, the counts of slice b0 + z into its own accumulator
+                unsigned cb = nblocks(hw);
+                if (cb > 32) cb = 32;
+                LAUNCH(M, "region_count_slices", (double)T * n * 5 + n * 8.0, 0,
+                       hipLaunchKernelGGL(k_region_count, dim3(cb, T, nb), dim3(RB), 0, s, ws.ll, ws.lp, ws.ml, ws.mp, n, hw, acc_slice,
+                                          R.slice_acc + (size_t)b0 * acc_slice + (size_t)si * kRegionMaxThr * 4));
+            } else {
+                unsigned cb = nblocks(n);
+                if (cb > 256) cb = 256;
+                LAUNCH(M, "region_count", (double)T * n * 5 + n * 8.0, 0,
+                       hipLaunchKernelGGL(k_region_count, dim3(cb, T), dim3(RB), 0, s, ws.ll, ws.lp, ws.ml, ws.mp, n, n, (size_t)0,
+                                          R.acc + (size_t)si * kRegionMaxThr * 4));
+            }
         }
     }
     HIP_TRY(hipGetLastError());
@@ -596,9 +686,26 @@ int region_read(Model* M, std::vector<std::vector<dnnca_region_counts>>& counts)
     return DNNCA_OK;
 }
 
+int region_read_slices(Model* M, int batch, dnnca_region_counts* out) {
+    if (!M->region || (size_t)batch > M->region->slices) { set_error("region metrics: no per-slice counts prepared"); return DNNCA_ESTATE; }
+    RegionState& R = *M->region;
+    const size_t ns = R.specs.size();
+    std::vector<unsigned long long> h((size_t)batch * ns * kRegionMaxThr * 4);
+    HIP_TRY(hipMemcpyAsync(h.data(), R.slice_acc, h.size() * 8, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    for (int b = 0; b < batch; ++b)
+        for (size_t i = 0; i < ns; ++i)
+            for (size_t t = 0; t < R.specs[i].thr.size(); ++t) {
+                const unsigned long long* a = &h[(((size_t)b * ns + i) * kRegionMaxThr + t) * 4];
+                *out++ = dnnca_region_counts{(int64_t)a[0], (int64_t)a[1], (int64_t)a[2], (int64_t)a[3]};
+            }
+    return DNNCA_OK;
+}
+
 int region_inputs(Model* M, size_t n, float** prob_dev, float** y_dev) {
     DN_TRY(region_state(M));
     RegionState& R = *M->region;
+    R.label_batch = 0;
     if (n > R.in_n) {
         if (R.in_prob) HIP_TRY(hipFree(R.in_prob));
         if (R.in_y) HIP_TRY(hipFree(R.in_y));
@@ -613,10 +720,59 @@ int region_inputs(Model* M, size_t n, float** prob_dev, float** y_dev) {
     return DNNCA_OK;
 }
 
+void region_set_label_batch(Model* M, int batch) {
+    if (M->region) M->region->label_batch = batch;
+}
+
+const float* region_label_of(Model* M, int batch) {
+    return M->region && batch > 0 && M->region->label_batch == batch ? M->region->in_y : nullptr;
+}
+
+int region_render(Model* M, const float* x, const float* lab, const float* prob, int batch, int h, int w, int c, float ratio,
+                  int overlay, unsigned char* out, size_t capacity, int* out_hwc) {
+    if (!(ratio > 0.f) || !std::isfinite(ratio)) { set_error("render: ratio %g", (double)ratio); return DNNCA_EINVAL; }
+    Composite g;
+    g.H = h;
+    g.W = w;
+    g.C = c;
+    g.Wc = w * (c + 2);
+    const float fh = (float)h * ratio, fw = (float)g.Wc * ratio;   // tf.cast(tf.cast(shape, float32) * ratio, int32)
+    if (!(fh >= 1.f && fw >= 1.f) || fh > 65536.f || fw > 65536.f) {
+        set_error("render: ratio %g maps %d x %d to %g x %g", (double)ratio, h, g.Wc, (double)fh, (double)fw);
+        return DNNCA_EINVAL;
+    }
+    g.oh = (int)fh;
+    g.ow = (int)fw;
+    g.nch = overlay ? 3 : 1;
+    g.sy = (float)g.H / (float)g.oh;
+    g.sx = (float)g.Wc / (float)g.ow;
+    out_hwc[0] = g.oh;
+    out_hwc[1] = g.ow;
+    out_hwc[2] = g.nch;
+    const size_t total = (size_t)batch * g.oh * g.ow * g.nch;
+    if (!out) return DNNCA_OK;                    // size query
+    if (capacity < total) { set_error("render: %zu bytes needed, capacity %zu", total, capacity); return DNNCA_EINVAL; }
+    DN_TRY(region_state(M));
+    RegionState& R = *M->region;
+    const size_t words = (total + 3) / 4;
+    if (words * 4 > R.viz_bytes) {
+        if (R.viz) HIP_TRY(hipFree(R.viz));
+        R.viz = nullptr;
+        R.viz_bytes = 0;
+        HIP_TRY(hipMalloc((void**)&R.viz, words * 4));
+        R.viz_bytes = words * 4;
+    }
+    LAUNCH(M, "region_render", (double)total + (double)batch * h * w * (c + 2) * 4, (double)total * 8,
+           hipLaunchKernelGGL(k_region_render, dim3(nblocks(words)), dim3(RB), 0, M->stream, x, lab, prob, g, batch, R.viz));
+    HIP_TRY(hipMemcpyAsync(out, R.viz, total, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return DNNCA_OK;
+}
+
 void region_release(Model* M) {
     if (!M->region) return;
     RegionState& R = *M->region;
-    for (void* p : {(void*)R.thr_dev, (void*)R.acc, R.ws, (void*)R.in_prob, (void*)R.in_y})
+    for (void* p : {(void*)R.thr_dev, (void*)R.acc, R.ws, (void*)R.in_prob, (void*)R.in_y, (void*)R.slice_acc, (void*)R.viz})
         if (p) (void)hipFree(p);
     delete M->region;
     M->region = nullptr;

@@ -1394,6 +1394,51 @@ int dnnca_region_confusion(void* model, const float* y_hw, int batch, const dnnc
     return region_one(M, M->prob, M->y_stage, batch, M->outH, M->outW, spec, out);
 }
 
+int dnnca_region_confusion_slices(void* model, const float* prob_hw, const float* y_hw, int batch, const dnnca_region_spec* specs,
+                                  int n, dnnca_region_counts* out) {
+    MODEL(model);
+    if (!y_hw || !specs || !out || n < 1) { set_error("bad region confusion arguments"); return DNNCA_EINVAL; }
+    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch out of range"); return DNNCA_EINVAL; }
+    if (M->region_eval) { set_error("dnnca_region_confusion* inside dnnca_eval_region_begin .. dnnca_eval_region_end"); return DNNCA_ESTATE; }
+    std::vector<RegionSpecHost> hs(n);
+    for (int i = 0; i < n; ++i) DN_TRY(region_spec_check(specs + i, M->outH, M->outW, hs[i]));
+    const size_t npix = (size_t)batch * M->outH * M->outW;
+    float *p_dev = nullptr, *y_dev = nullptr;
+    DN_TRY(region_inputs(M, npix, &p_dev, &y_dev));       // the labels stay there for dnnca_render_composite
+    HIP_TRY(hipMemcpyAsync(y_dev, y_hw, npix * 4, hipMemcpyHostToDevice, M->stream));
+    if (prob_hw) HIP_TRY(hipMemcpyAsync(p_dev, prob_hw, npix * 4, hipMemcpyHostToDevice, M->stream));
+    DN_TRY(region_prepare(M, hs, batch, M->outH, M->outW, batch));
+    DN_TRY(region_accumulate(M, prob_hw ? p_dev : M->prob, y_dev, batch, M->outH, M->outW, true));
+    DN_TRY(region_read_slices(M, batch, out));
+    region_set_label_batch(M, batch);
+    return DNNCA_OK;
+}
+
+int dnnca_render_composite(void* model, const float* y_hw, int batch, float ratio, int overlay, uint8_t* out, int64_t capacity,
+                           int32_t* out_hwc) {
+    MODEL(model);
+    if (!out_hwc || capacity < 0 || (out && capacity == 0)) { set_error("bad render arguments"); return DNNCA_EINVAL; }
+    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch out of range"); return DNNCA_EINVAL; }
+    if (M->outH != M->desc.height || M->outW != M->desc.width) {
+        set_error("render: the output (%d x %d) differs from the input (%d x %d)", M->outH, M->outW, M->desc.height, M->desc.width);
+        return DNNCA_EINVAL;
+    }
+    int hwc[3];
+    const int H = M->desc.height, W = M->desc.width, C = M->desc.in_channels;
+    DN_TRY(region_render(M, nullptr, nullptr, nullptr, batch, H, W, C, ratio, overlay, nullptr, 0, hwc));
+    std::copy(hwc, hwc + 3, out_hwc);
+    if (!out) return DNNCA_OK;
+    const float* lab = y_hw ? nullptr : region_label_of(M, batch);
+    if (y_hw) {
+        HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, (size_t)batch * H * W * 4, hipMemcpyHostToDevice, M->stream));
+        lab = M->y_stage;
+    } else if (!lab) {
+        set_error("render: no labels given and none kept from dnnca_region_confusion_slices of %d slices", batch);
+        return DNNCA_ESTATE;
+    }
+    return region_render(M, M->x_stage, lab, M->prob, batch, H, W, C, ratio, overlay, out, (size_t)capacity, hwc);
+}
+
 int dnnca_eval_region_begin(void* model, const dnnca_region_spec* specs, int n) {
     MODEL(model);
     if (!M->eval_active) { set_error("dnnca_eval_region_begin outside dnnca_eval_begin .. dnnca_eval_end"); return DNNCA_ESTATE; }

@@ -19,14 +19,26 @@ struct RegionSpecHost {
 // checks one caller spec against slices of h x w; fills `out` or returns DNNCA_EINVAL with the reason in dnnca_last_error
 int region_spec_check(const dnnca_region_spec* s, int h, int w, RegionSpecHost& out);
 // uploads the specs' thresholds and zeroes the uint64 accumulators [n_specs][kRegionMaxThr][4]; sizes the workspace for batches of
-// up to max_batch slices of h x w
-int region_prepare(Model* M, const std::vector<RegionSpecHost>& specs, int max_batch, int h, int w);
-// the counts of `batch` slices prob [batch, h, w] / y [batch, h, w] (device) added to the accumulators of every spec
-int region_accumulate(Model* M, const float* prob, const float* y, int batch, int h, int w);
+// up to max_batch slices of h x w.  slices > 0: also zeroes per-slice accumulators [slices][n_specs][kRegionMaxThr][4]
+int region_prepare(Model* M, const std::vector<RegionSpecHost>& specs, int max_batch, int h, int w, int slices = 0);
+// the counts of `batch` slices prob [batch, h, w] / y [batch, h, w] (device) added to the accumulators of every spec (per_slice:
+// slice b's counts to its own accumulator instead)
+int region_accumulate(Model* M, const float* prob, const float* y, int batch, int h, int w, bool per_slice = false);
+// synchronises and reads the per-slice accumulators: batch x sum(n_thresholds) entries, slice after slice, spec after spec
+int region_read_slices(Model* M, int batch, dnnca_region_counts* out);
 // synchronises and reads the accumulators: counts[i] = spec i's T entries in the caller's threshold order
 int region_read(Model* M, std::vector<std::vector<dnnca_region_counts>>& counts);
-// device buffers of the caller-supplied slices (dnnca_region_confusion_of), grown on demand
+// device buffers of the caller-supplied slices (dnnca_region_confusion_of, the labels of dnnca_region_confusion_slices), grown on
+// demand; the labels kept for dnnca_render_composite are forgotten
 int region_inputs(Model* M, size_t n, float** prob_dev, float** y_dev);
+// the label buffer holds the labels of `batch` slices that dnnca_render_composite may reuse; region_label_of(M, batch): that
+// buffer if it holds `batch` slices' labels, else nullptr
+void region_set_label_batch(Model* M, int batch);
+const float* region_label_of(Model* M, int batch);
+// the Visualizer's composite of `batch` slices (device x [batch, h, w, c], lab / prob [batch, h, w]) into host `out` (uint8
+// [batch, oh, ow, overlay ? 3 : 1]); out_hwc = (oh, ow, channels).  out == nullptr: size query only
+int region_render(Model* M, const float* x, const float* lab, const float* prob, int batch, int h, int w, int c, float ratio,
+                  int overlay, unsigned char* out, size_t capacity, int* out_hwc);
 void region_release(Model* M);
 
 }  // namespace dnnca

@@ -319,9 +319,13 @@ class DeviceModel:
             raise ValueError('batch %d outside [1, %d]' % (x.shape[0], self.max_batch))
         return x
 
-    def forward(self, x, training=False, return_logits=False):
+    def forward(self, x, training=False, return_logits=False, return_prob=True):
+        """return_prob=False: the probabilities stay on the device (for region_confusion* / render_composite); returns None"""
         x = self._check_x(x)
         B = x.shape[0]
+        if not return_prob:
+            check(self.lib.dnnca_forward(self.handle, fptr(x), B, int(training), None, None))
+            return None
         prob = np.empty((B, self.in_shape[0], self.in_shape[1], 1), np.float32)
         logits = np.empty_like(prob) if return_logits else None
         check(self.lib.dnnca_forward(self.handle, fptr(x), B, int(training), fptr(prob),
@@ -421,6 +425,42 @@ class DeviceModel:
         B, h, w = y.shape
         check(self.lib.dnnca_region_confusion_of(self.handle, fptr(np.ascontiguousarray(prob)), fptr(y), B, h, w, arr, out))
         return split_region_counts(out, [keep[0].size])[0]
+
+    # ---- the Visualizer of `annotator evaluate` (casewise.py) ---------------------------------------------------
+    def region_confusion_slices(self, y, specs, prob=None):
+        """per-slice region counts of the last forward's probabilities (or of `prob` [B, H, W(, 1)], host) against y [B, H, W]:
+        int64 [B, T, 4] (tp_label, fn, tp_pred, fp), T = all thresholds of `specs` in order.  A spec of more than 64 thresholds runs as several device specs (one label
+        labelling for all of them).  The labels stay on the device for render_composite(None, ...)."""
+        y = as_f32(y)
+        if y.ndim != 3:
+            raise ValueError('y must be [B, H, W], got %s' % (y.shape,))
+        if prob is not None:
+            prob = as_f32(prob)
+            if prob.size != y.size:
+                raise ValueError('prob %s and y %s differ in size' % (prob.shape, y.shape))
+        pieces = []
+        for thr, iou, rf, k in specs:
+            thr = np.atleast_1d(np.asarray(thr, np.float32)).ravel()
+            n = -(-thr.size // 64)
+            pieces += [(part, iou, rf, k) for part in np.array_split(thr, n)] if n > 1 else [(thr, iou, rf, k)]
+        arr, keep = region_specs(pieces)
+        T = sum(k.size for k in keep)
+        out = (_lib.RegionCounts * (y.shape[0] * T))()
+        check(self.lib.dnnca_region_confusion_slices(self.handle, None if prob is None else fptr(prob), fptr(y), y.shape[0], arr,
+                                                     len(pieces), out))
+        return split_region_counts(out, [y.shape[0] * T])[0].reshape(y.shape[0], T, 4)
+
+    def render_composite(self, y, batch, ratio=0.5, overlay=False):
+        """the Visualizer's composite of the last forward's `batch` slices: uint8 [batch, oh, ow, 1 or 3] (input features | label |
+        probability, resized by `ratio`).  y [batch, H, W], or None: the labels of the region_confusion_slices call just before."""
+        hwc = (C.c_int32 * 3)()
+        ya = None if y is None else as_f32(y)
+        yp = None if ya is None else fptr(ya)
+        check(self.lib.dnnca_render_composite(self.handle, yp, int(batch), float(ratio), int(bool(overlay)), None, 0, hwc))
+        out = np.empty((int(batch), hwc[0], hwc[1], hwc[2]), np.uint8)
+        check(self.lib.dnnca_render_composite(self.handle, yp, int(batch), float(ratio), int(bool(overlay)),
+                                              out.ctypes.data_as(C.c_void_p), out.nbytes, hwc))
+        return out
 
     # ---- device-side augmentation (annotator/data.py:62-111 train_ds) ------------------------------------------
     def augment_u8(self, raw, params, out_size, label_index, contrast_channels=None, src_ptr=None):

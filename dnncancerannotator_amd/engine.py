@@ -19,7 +19,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from . import augment, device, distributed, losses as custom_losses, metrics as custom_metrics, models, region_metrics
+from . import augment, casewise, device, distributed, losses as custom_losses, metrics as custom_metrics, models, region_metrics
 from .feeder import BatchFeeder
 
 
@@ -499,8 +499,14 @@ class TFKerasModel:
         else:
             assert len(step_range) == 2
             assert 0 <= step_range[0] <= step_range[1]
-        if viz_ds is not None or export_images or visualize_sensitivity or overlay:
-            logging.warning('visualisation / image export are outside the accelerated path: ignored')
+        if visualize_sensitivity:
+            logging.warning('visualize_sensitivity is outside the accelerated path: ignored')
+        # the Visualizer (engine.py:171-183, callbacks.py): casewise counts and images of viz_ds after each checkpoint's evaluation,
+        # on rank 0 alone over the whole of viz_ds (data parallel: the other ranks skip it)
+        visualize = viz_ds is not None and (export_csv or export_images) and self.ctx.rank == 0
+        viz_root = os.path.join(export_path, tag)
+        casewise_rows = []
+        writer = casewise.Writer() if visualize else None
         rows = OrderedDict()
         previous_step = None
         for ckpt_step, ckpt_path_ in self.get_ckpts(ckpt_path).items():
@@ -512,6 +518,10 @@ class TFKerasModel:
             previous_step = ckpt_step
             self.load(ckpt_path_)
             rows[ckpt_step] = self._evaluate(dataset, staged=True)
+            if visualize:
+                self._visualize(viz_ds, ckpt_step, viz_root, export_csv, export_images, overlay, casewise_rows, writer)
+        if writer is not None:
+            writer.close()
         if export_csv and self.ctx.rank == 0:
             os.makedirs(os.path.join(export_path, tag), exist_ok=True)
             with open(os.path.join(export_path, tag, 'results.csv'), 'w') as f:
@@ -519,7 +529,39 @@ class TFKerasModel:
                 f.write('step,' + ','.join(cols) + '\n')
                 for step, r in rows.items():
                     f.write(str(step) + ',' + ','.join(str(r[c]) for c in cols) + '\n')
+            if visualize:
+                with open(os.path.join(export_path, tag, 'casewise_results.csv'), 'w', newline='') as f:
+                    f.write(casewise.table_csv(casewise.column_names(), casewise_rows))
         return rows
+
+    def _visualize(self, viz_ds, step, root, export_csv, export_images, overlay, casewise_rows, writer):
+        """One Visualizer pass (callbacks.py process_batch / _emit) over viz_ds batches (x, y, paths, sliceIDs): forward
+        (training=False), the per-slice region counts (export_csv), the composite images (export_images), then the files.  The
+        probabilities stay on the device; only the counts and the uint8 images come back.  casewise_rows gains one row per slice,
+        in dataset order."""
+        spec = casewise.device_spec()
+        names = casewise.column_names()
+        for x, y, paths, ids in viz_ds:
+            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
+            if not len(x):
+                continue
+            self._ensure_capacity(len(x))
+            dm = self.device_model
+            for i in range(0, len(x), dm.max_batch):
+                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
+                tags = [casewise.tag_of(p, k) for p, k in zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch])]
+                dm.forward(xb, training=False, return_prob=False)
+                if export_csv:
+                    counts = dm.region_confusion_slices(yb, [spec])
+                    for t, c in zip(tags, counts):
+                        values = casewise.row_values(c, t)
+                        casewise_rows.append(values)
+                        writer.submit(casewise.csv_path(root, t, step), casewise.series_csv, names, values)
+                if export_images:
+                    # the labels went up with the counts already: the renderer reuses them
+                    images = dm.render_composite(None if export_csv else yb, len(xb), casewise.RATIO, overlay)
+                    for t, im in zip(tags, images):
+                        writer.submit(casewise.image_path(root, t, step), casewise.encode_png, im)
 
     def predict(self, dataset):
         """Probabilities [N, H, W, 1] for every element of `dataset` (elements are x or (x, ...))."""

@@ -15,8 +15,11 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
     else:
         config = saved_config
     ds = make_dataset(data_path, config.get('data_options', {}).get('eval', {}), training=False)
+    # the Visualizer's data set (runs/evaluate.py:72-73 of the reference): the same slices with their exam path and sliceID
+    viz_ds = None if skip_visualization else make_dataset(data_path, config.get('data_options', {}).get('eval', {}), training=False,
+                                                          include_meta=True)
     model = engine.TFKerasModel(config)
-    return model.eval(ds, viz_ds=None, tag=tag, save_path=os.path.join(save_path), avoid_overwrite=avoid_overwrite,
+    return model.eval(ds, viz_ds=viz_ds, tag=tag, save_path=os.path.join(save_path), avoid_overwrite=avoid_overwrite,
                       export_path=export_path, export_images=export_images, export_csv=export_csv,
                       visualize_sensitivity=visualize_sensitivity, min_interval=min_interval, step_range=step_range,
                       overlay=overlay, export_casewise_metrics=export_casewise_metrics)

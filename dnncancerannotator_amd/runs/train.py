@@ -5,18 +5,24 @@ import os
 from .. import data, dump, engine, load
 
 
-def make_dataset(paths, options, training):
+def make_dataset(paths, options, training, include_meta=False):
     """Dataset for `--data_path`.  Supported sources: the reference's `.tfrecords` exam files (tfrecord.py; for training with the
     `augment_options` of data_options.train -- random crop / flip / contrast run on the device, random_warp is skipped),
     `synthetic[:HxW[xC]]` (seeded synthetic slices) and `.npz` files holding `x` [N,H,W,C] in [0,1] and `y` [N,H,W].
-    The image-folder pipeline (data.py:170-180) is outside the accelerated hot path."""
+    The image-folder pipeline (data.py:170-180) is outside the accelerated hot path.
+    include_meta (evaluation only; eval_ds(include_meta=True) of the reference): batches (x, y, paths, sliceIDs) with the same x
+    and y as without it, every rank reading all of them (the Visualizer pass runs on rank 0 alone).  Exam files give each
+    slice's exam `path` and its index in the exam; .npz / synthetic sources give the source string and the running index."""
     batch_size = options.get('batch_size', 8)
     first = paths[0]
+    if include_meta and training:
+        raise ValueError('include_meta is for evaluation datasets')
     if first.startswith('synthetic'):
         dims = [int(v) for v in first.split(':')[1].split('x')] if ':' in first else []
         h, w = (dims + [512, 512])[:2] if len(dims) >= 2 else (512, 512)
         c = dims[2] if len(dims) > 2 else 1
-        return data.SyntheticDataset(batch_size, h, w, c, repeat=training, n_batches=4 if training else 2)
+        return data.SyntheticDataset(batch_size, h, w, c, repeat=training, n_batches=4 if training else 2,
+                                     meta_path=first if include_meta else None)
     if all(p.endswith('.tfrecords') for p in paths):          # the reference's exam files (data.py:166-169)
         from .. import distributed
         from ..tfrecord import TFRecordDataset
@@ -29,13 +35,15 @@ def make_dataset(paths, options, training):
                                repeat=training, drop_remainder=training,
                                augment_options=options.get('augment_options') if training else False,
                                buffer_size=options.get('buffer_size', 0) if training else 0,
-                               device_convert=not training,      # evaluation: uint8 to the device, / 255 and the split there
-                               shard=(ctx.rank, ctx.world),      # data parallel: every rank assembles only its part of a batch
+                               device_convert=not training and not include_meta,   # evaluation: uint8 to the device, / 255 and the split there
+                               shard=None if include_meta else (ctx.rank, ctx.world),  # data parallel: every rank assembles only its part of a batch
+                               include_meta=include_meta,
                                normalize_exams=bool(options.get('normalize_exams', True)) if training else False)   # data.py:68,137
     if all(p.endswith('.npz') for p in paths):
         import numpy as np
         xs, ys = zip(*((z['x'], z['y']) for z in map(np.load, paths)))
-        return data.ArrayDataset(np.concatenate(xs), np.concatenate(ys), batch_size, repeat=training, drop_remainder=training)
+        return data.ArrayDataset(np.concatenate(xs), np.concatenate(ys), batch_size, repeat=training, drop_remainder=training,
+                                 meta_path=','.join(paths) if include_meta else None)
     raise NotImplementedError('data_path %r: supported sources are .tfrecords, synthetic[:HxW[xC]] and .npz files' % (paths,))
 
 

@@ -310,11 +310,14 @@ class TFRecordDataset:
     Training (`augment_options` a dict or None, data.py:62-111 train_ds): the slices are centre-cropped to 512 x 512 (the `base`
     call of train_ds, data.py:95-100), shuffled through a buffer of `buffer_size` slices (data.py:106) and handed on as uint8
     `augment.RawBatch`es with their random draws; crop / flip / contrast / the /255 and the feature-label split then run on the
-    device (`dnnca_augment_u8` / `dnnca_warp_f32`, engine.train)."""
+    device (`dnnca_augment_u8` / `dnnca_warp_f32`, engine.train).
+
+    include_meta (evaluation only, eval_ds(include_meta=True), data.py:488-510): batches (x, y, paths, sliceIDs) -- the same x and
+    y as without it, each slice's exam `path` feature and its 0-based index in the exam record (tf.data.experimental.Counter)."""
 
     def __init__(self, paths, slice_types, batch_size, output_size=(512, 512), repeat=False, drop_remainder=False,
                  augment_options=False, buffer_size=0, seed=0, normalize_exams=False, device_convert=False, workers=None,
-                 cache_bytes=8 << 30, shard=None, **ignored):
+                 cache_bytes=8 << 30, shard=None, include_meta=False, **ignored):
         from . import augment
         self.paths = list(paths)
         self.slice_types = list(slice_types)
@@ -326,6 +329,9 @@ class TFRecordDataset:
         self.plan = None if augment_options is False else augment.parse_augment_options(augment_options, self.output_size)
         if self.plan is not None:
             self.output_size = self.plan.output_size
+        self.include_meta = bool(include_meta)
+        if self.include_meta and self.plan is not None:
+            raise ValueError('include_meta is for evaluation datasets (augment_options=False)')
         self.buffer_size = int(buffer_size)
         self.workers = workers                # reader threads (None: half the cores, at most eight)
         # data parallel, one process per GPU: shard = (rank, world) makes every batch this rank's contiguous part of the global
@@ -343,7 +349,7 @@ class TFRecordDataset:
         # evaluation with device_convert: the centre-cropped uint8 slices travel as `augment.RawBatch`es without draws (params None)
         # -- a quarter of the float bytes over PCIe, no float copy of an exam on the host; the engine converts them on the device
         # (or, without one, with augment.raw_to_float)
-        self.device_convert = bool(device_convert) and self.plan is None
+        self.device_convert = bool(device_convert) and self.plan is None and not self.include_meta
         # data.py:517-525 (base_from_tfrecords, normalize=True; data_options.yaml:5 for training): the files are interleaved one
         # slice at a time, each file's slice stream repeated for ever, so that every exam file contributes equally however many
         # slices it holds.  (tf.data's interleave only ever opens `cycle_length` = #cores files when the streams are infinite;
@@ -468,13 +474,29 @@ class TFRecordDataset:
             buf[k], buf[-1] = buf[-1], buf[k]
             yield buf.pop()
 
-    def _slices(self):
+    def _slices(self, meta=False):
         oh, ow = self.output_size
         for exams in self._exam_lists():
             for exam in exams:
                 s = self._centre(exam.slices, oh, ow).astype(np.float32) / np.float32(255.0)
                 for k in range(len(s)):
-                    yield s[k][..., self.feature_idx], s[k][..., self.label_idx]
+                    if meta:
+                        yield s[k][..., self.feature_idx], s[k][..., self.label_idx], exam.path, k
+                    else:
+                        yield s[k][..., self.feature_idx], s[k][..., self.label_idx]
+
+    def _with_meta(self):
+        xs, ys, ps, ks = [], [], [], []
+        for x, y, p, k in self._slices(meta=True):
+            xs.append(x)
+            ys.append(y)
+            ps.append(p)
+            ks.append(k)
+            if len(xs) == self.batch_size:
+                yield self._stacked(xs, ys) + (self._mine(ps), np.asarray(self._mine(ks), np.int64))
+                xs, ys, ps, ks = [], [], [], []
+        if xs and not self.drop_remainder:
+            yield self._stacked(xs, ys) + (self._mine(ps), np.asarray(self._mine(ks), np.int64))
 
     def _augmented(self):
         from . import augment
@@ -534,6 +556,8 @@ class TFRecordDataset:
         while True:
             if self.plan is not None:
                 yield from self._augmented()
+            elif self.include_meta:
+                yield from self._with_meta()
             elif self.device_convert:
                 yield from self._eval_raw()
             else:

@@ -237,6 +237,23 @@ int dnnca_region_confusion(void* model, const float* y_hw, int batch, const dnnc
 int dnnca_eval_region_begin(void* model, const dnnca_region_spec* specs, int n);
 int dnnca_eval_region_end(void* model, dnnca_region_counts* out);
 
+/* ---- the Visualizer of `annotator evaluate` (utils/callbacks.py:55-446): casewise region counts and composite images ----------
+ * dnnca_region_confusion_slices: the region counts of the last forward's probabilities (or of prob_hw, host [batch, H, W], when
+ * it is not NULL) against y_hw (host [batch, H, W]), PER SLICE, for n specs (each as above, up to 64 thresholds; specs of one resized size share the label labelling).  out holds
+ * batch * sum(n_thresholds) entries: slice after slice, spec after spec within a slice.  The labels stay on the device for
+ * dnnca_render_composite.
+ * dnnca_render_composite: generate_image + make_summary_constructor + `* 255` cast of the reference for the last forward's
+ * input and probabilities: the C feature channels, the label and the probability side by side ([H, W (C + 2)]; overlay: the
+ * feature panels grey, the label and probability panels stack([v, f0, f0])), resized by tf.image.resize bilinear (half-pixel
+ * centres, float32) to (int(f32(H) * ratio), int(f32(W (C + 2)) * ratio)), then uint8(trunc(v * 255)) (clamped to 0..255).
+ * out: host uint8 [batch, oh, ow, overlay ? 3 : 1] of `capacity` bytes; out_hwc receives (oh, ow, channels); out == NULL only
+ * queries the size.  y_hw == NULL reuses the labels of the dnnca_region_confusion_slices call just before (same batch): each
+ * label crosses the bus once.  The model's output must have the input's size (padding 'same'). */
+int dnnca_region_confusion_slices(void* model, const float* prob_hw, const float* y_hw, int batch, const dnnca_region_spec* specs,
+                                  int n, dnnca_region_counts* out);
+int dnnca_render_composite(void* model, const float* y_hw, int batch, float ratio, int overlay, uint8_t* out, int64_t capacity,
+                           int32_t* out_hwc);
+
 /* ---- data parallel: tf.distribute.MirroredStrategy (engine.py:260-263) re-done as one process per GPU + RCCL ---- */
 int dnnca_comm_unique_id(void* id_out /* DNNCA_UNIQUE_ID_BYTES */);
 int dnnca_comm_init(void* model, int rank, int world, const void* unique_id, size_t id_len);   /* world == 1: no-op */
