@@ -110,6 +110,10 @@ SIGNATURES = {
     'dnnca_eval_begin': (C.c_int, [_VP, _VP, C.c_int]),
     'dnnca_eval_step_staged': (C.c_int, [_VP, C.c_int, _VP, _VP, C.c_int, C.POINTER(LossCfg)]),
     'dnnca_eval_end': (C.c_int, [_VP, C.POINTER(Confusion)]),
+    'dnnca_train_metrics': (C.c_int, [_VP, _FP, C.c_int]),
+    'dnnca_last_step_confusion': (C.c_int, [_VP, C.POINTER(Confusion)]),
+    'dnnca_staged_confusion': (C.c_int, [_VP, C.c_int, C.POINTER(Confusion)]),
+    'dnnca_get_prob': (C.c_int, [_VP, _FP, C.c_int64]),
     'dnnca_pixel_confusion': (C.c_int, [_VP, _FP, C.c_int, _FP, C.c_int, C.POINTER(Confusion)]),
     'dnnca_pixel_confusion_of': (C.c_int, [_VP, _FP, _FP, C.c_int64, _FP, C.c_int, C.POINTER(Confusion)]),
     'dnnca_region_confusion_of': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.POINTER(RegionSpec), C.POINTER(RegionCounts)]),

@@ -123,9 +123,16 @@ struct FwdArgs {
     int hmask;               // multiply dfeat by act'(feat)
     float halpha;
 };
+// the PROB variant's arguments (a struct of their own: the argument block of PROB = false stays as it is)
+struct FwdProbArgs : FwdArgs {
+    float* hprob;            // the step's sigmoid [B, H, W] (per-step training metrics)
+};
+__device__ __forceinline__ float* fwd_prob(const FwdArgs&) { return nullptr; }
+__device__ __forceinline__ float* fwd_prob(const FwdProbArgs& a) { return a.hprob; }
 
-template <int C, int NSRC, int CO, int NT, bool DB, bool HEAD = false>
-__global__ __launch_bounds__(NT) void k_pgfwd(FwdArgs p) {
+// PROB (HEAD only): the epilogue also stores each pixel's sigmoid into p.hprob; the arithmetic is the same
+template <int C, int NSRC, int CO, int NT, bool DB, bool HEAD = false, bool PROB = false>
+__global__ __launch_bounds__(NT) void k_pgfwd(std::conditional_t<PROB, FwdProbArgs, FwdArgs> p) {
     constexpr int G = 12 / CO, TX = 2, TW = 16 * G * TX, N = G * CO, NW = NT / 64;
     using T = TG<C, TW>;
     constexpr int WR = (G + 2) * C, SR = (WR + 3) / 4, KS = NSRC * 3 * SR, LS = T::LS;
@@ -321,6 +328,9 @@ __global__ __launch_bounds__(NT) void k_pgfwd(FwdArgs p) {
                     const float e = expf(-fabsf(xl));
                     const float sig = xl >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
                     const float dl = ok ? mk * (sig - z) * p.hgscale : 0.f;
+                    if constexpr (PROB) {
+                        if (ok) fwd_prob(p)[((size_t)b * p.H + y) * p.W + px] = sig;
+                    }
                     if (ok) hsum[CO + 1] = fmaf(fmaxf(xl, 0.f) - xl * z + log1pf(e), mk, hsum[CO + 1]);
                     hsum[CO] += dl;
 #pragma unroll
@@ -2230,8 +2240,16 @@ bool fast_conv_fwd_head(Model* m, int B, Op& o, Op& head, const float* y, const 
     const int ntiles = a.tiles_x * a.tiles_y * B;
     static const int fit = resident_blocks(k_pgfwd<3, 1, 3, 512, false, true>, 2048);      // partials table: 2048 rows
     const int g = ntiles < fit ? ntiles : fit;
-    LAUNCH(m, "pgfwd_head_3x1_3", bytes, flops,
-           hipLaunchKernelGGL((k_pgfwd<3, 1, 3, 512, false, true>), dim3(g), dim3(512), 0, m->stream, a));
+    if (m->train_metrics_on()) {         // + the step's probabilities (dnnca_train_metrics): the same grid
+        FwdProbArgs pa{};
+        static_cast<FwdArgs&>(pa) = a;
+        pa.hprob = m->prob;
+        LAUNCH(m, "pgfwd_head_3x1_3", bytes + 4.0 * a.H * a.W * B, flops,
+               hipLaunchKernelGGL((k_pgfwd<3, 1, 3, 512, false, true, true>), dim3(g), dim3(512), 0, m->stream, pa));
+    } else {
+        LAUNCH(m, "pgfwd_head_3x1_3", bytes, flops,
+               hipLaunchKernelGGL((k_pgfwd<3, 1, 3, 512, false, true>), dim3(g), dim3(512), 0, m->stream, a));
+    }
     // the partial sums wait for the launch that ends the backward pass (k_pg_fold)
     m->head_pending.partials = m->head_partials; m->head_pending.nblocks = g; m->head_pending.C = 3;
     m->head_pending.dw = m->g + head.w_off; m->head_pending.dbias = m->g + head.b_off;
@@ -2381,8 +2399,16 @@ bool fast_tail3(Model* m, int B, Op& o, Op& head, const float* y, const dnnca_lo
 #endif
     // algorithmic bytes / FLOPs of the layers this launch stands for (every layer reads its inputs and writes its output):
     // conv forward 3 + 3, head + loss + head backward 3 + 1 + 3, conv backward (dz, x in; dx out) 3 + 3 + 3 floats per pixel
-    LAUNCH(m, "tail3_3x1_3", 4.0 * npx * 22, 2.0 * npx * (81 * 3 + 15),
-           hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), tail3_lds, m->stream, a));
+    if (m->train_metrics_on()) {         // + the step's probabilities (dnnca_train_metrics): one 4-byte store per owned pixel
+        TailProbArgs pa{};
+        static_cast<TailArgs&>(pa) = a;
+        pa.prob = m->prob;
+        LAUNCH(m, "tail3_3x1_3", 4.0 * npx * 23, 2.0 * npx * (81 * 3 + 15),
+               hipLaunchKernelGGL((k_tail3<3, 27, true, 0, 1, true>), dim3(nblk), dim3(256), tail3_lds, m->stream, pa));
+    } else {
+        LAUNCH(m, "tail3_3x1_3", 4.0 * npx * 22, 2.0 * npx * (81 * 3 + 15),
+               hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), tail3_lds, m->stream, a));
+    }
     m->head_pending.partials = m->head_partials; m->head_pending.nblocks = nblk; m->head_pending.C = 3;
     m->head_pending.dw = m->g + head.w_off; m->head_pending.dbias = m->g + head.b_off;
     m->tail_done = &o;

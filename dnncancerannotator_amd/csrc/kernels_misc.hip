@@ -5,6 +5,7 @@
 // the non-power-of-two pixel sizes stay 16-byte aligned.
 #include "fast.h"
 #include "kernels.h"
+#include <type_traits>
 
 namespace dnnca {
 
@@ -250,9 +251,17 @@ struct HeadArgs {
     float alpha;
     int n4;                // number of PX-pixel chunks (PX = 4 for C = 3, 1 for wide heads)
 };
+// the PROB variants' arguments (a struct of their own: the argument block of PROB = false stays as it is)
+struct HeadProbArgs : HeadArgs {
+    float* prob;           // the step's sigmoid [B, H, W] (per-step training metrics)
+};
+DEVINL float* head_prob(const HeadArgs&) { return nullptr; }
+DEVINL float* head_prob(const HeadProbArgs& a) { return a.prob; }
+template <bool PROB> using HeadArgsT = std::conditional_t<PROB, HeadProbArgs, HeadArgs>;
 
-template <int C, int PX>
-__global__ __launch_bounds__(256) void k_head_train(HeadArgs p) {
+// PROB: also store each pixel's sigmoid into p.prob beside dfeat; the arithmetic is the same
+template <int C, int PX, bool PROB = false>
+__global__ __launch_bounds__(256) void k_head_train(HeadArgsT<PROB> p) {
     __shared__ float red[4][C + 2];
     float wv[C];
 #pragma unroll
@@ -271,7 +280,7 @@ __global__ __launch_bounds__(256) void k_head_train(HeadArgs p) {
 #pragma unroll
     for (int c = 0; c < C; ++c) sdw[c] = 0.f;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < p.n4; i += gridDim.x * 256) {
-        float f[PX * C], z[PX], df[PX * C];
+        float f[PX * C], z[PX], df[PX * C], sg[PX];
 #pragma unroll
         for (int v = 0; v < PX * C / 4; ++v) ld4(f + 4 * v, p.feat + (size_t)i * PX * C + 4 * v);
         if constexpr (PX == 4) ld4(z, p.y + (size_t)i * 4);
@@ -285,6 +294,7 @@ __global__ __launch_bounds__(256) void k_head_train(HeadArgs p) {
             const float e = expf(-fabsf(x));
             sloss = fmaf(fmaxf(x, 0.f) - x * z[px] + log1pf(e), mk, sloss);
             const float sig = x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+            sg[px] = sig;
             const float dl = mk * (sig - z[px]) * p.gscale;
             sdb += dl;
 #pragma unroll
@@ -298,6 +308,10 @@ __global__ __launch_bounds__(256) void k_head_train(HeadArgs p) {
         }
 #pragma unroll
         for (int v = 0; v < PX * C / 4; ++v) st4(p.dfeat + (size_t)i * PX * C + 4 * v, df + 4 * v);
+        if constexpr (PROB) {
+            if constexpr (PX == 4) st4(head_prob(p) + (size_t)i * 4, sg);
+            else head_prob(p)[i] = sg[0];
+        }
     }
     // block reduction: wave shuffles, then 4 partials through LDS, one atomic per value per block
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -322,8 +336,8 @@ __global__ __launch_bounds__(256) void k_head_train(HeadArgs p) {
 // The same for wide heads (C = 16, 64): C / 4 adjacent lanes share a pixel, each holds four channels -- every load and store
 // is one coalesced 16-byte access per lane (the one-thread-per-pixel kernel above walks 256-byte rows with 64 lanes at once
 // and keeps 4 C floats per thread); the logit is folded across the lane group with shuffles.  Same partials layout.
-template <int C>
-__global__ __launch_bounds__(256) void k_head_train_wide(HeadArgs p) {
+template <int C, bool PROB = false>
+__global__ __launch_bounds__(256) void k_head_train_wide(HeadArgsT<PROB> p) {
     constexpr int G = C / 4, PPW = 64 / G, U = 4;        // lanes per pixel, pixels per wave and load, loads in flight
     static_assert(C % 4 == 0 && 64 % G == 0, "lane groups");
     __shared__ float red[4][C + 2];
@@ -367,6 +381,9 @@ __global__ __launch_bounds__(256) void k_head_train_wide(HeadArgs p) {
             const float sig = x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
             const bool ok = px < p.n4;
             const float dl = ok ? mk * (sig - z[u]) * p.gscale : 0.f;
+            if constexpr (PROB) {
+                if (ok && cq == 0) head_prob(p)[px] = sig;
+            }
             if (ok && cq == 0) {
                 sloss = fmaf(fmaxf(x, 0.f) - x * z[u] + log1pf(e), mk, sloss);
                 sdb += dl;
@@ -452,12 +469,19 @@ bool fast_head_train(Model* m, int B, Op& o, const float* y, const dnnca_loss_cf
     int blocks = (a.n4 + 255) / 256;
     if (blocks > 2048) blocks = 2048;          // partials buffer: 2048 x 72 floats
     a.partials = m->head_partials;
+    const bool pm = m->train_metrics_on();      // + the step's probabilities (dnnca_train_metrics)
+    HeadProbArgs pa{};
+    static_cast<HeadArgs&>(pa) = a;
+    pa.prob = m->prob;
 #define HEAD_CASE(c, px)                                                                                               \
     if (C == c) {                                                                                                      \
-        if constexpr (c >= 16)                                                                                         \
-            LAUNCH(m, "head_train_" #c, bytes, 30.0 * npix, hipLaunchKernelGGL((k_head_train_wide<c>), dim3(blocks), dim3(256), 0, m->stream, a)); \
-        else                                                                                                           \
-            LAUNCH(m, "head_train_" #c, bytes, 30.0 * npix, hipLaunchKernelGGL((k_head_train<c, px>), dim3(blocks), dim3(256), 0, m->stream, a)); \
+        if constexpr (c >= 16) {                                                                                       \
+            if (pm) LAUNCH(m, "head_train_" #c, bytes + 4.0 * npix, 30.0 * npix, hipLaunchKernelGGL((k_head_train_wide<c, true>), dim3(blocks), dim3(256), 0, m->stream, pa)); \
+            else LAUNCH(m, "head_train_" #c, bytes, 30.0 * npix, hipLaunchKernelGGL((k_head_train_wide<c>), dim3(blocks), dim3(256), 0, m->stream, a)); \
+        } else {                                                                                                       \
+            if (pm) LAUNCH(m, "head_train_" #c, bytes + 4.0 * npix, 30.0 * npix, hipLaunchKernelGGL((k_head_train<c, px, true>), dim3(blocks), dim3(256), 0, m->stream, pa)); \
+            else LAUNCH(m, "head_train_" #c, bytes, 30.0 * npix, hipLaunchKernelGGL((k_head_train<c, px>), dim3(blocks), dim3(256), 0, m->stream, a)); \
+        }                                                                                                              \
         if (m->head_defer_ok && m->merged_launches()) {       /* reduced by the launch that ends the backward pass (k_pg_fold) */ \
             m->head_pending.partials = m->head_partials; m->head_pending.nblocks = blocks; m->head_pending.C = c;       \
             m->head_pending.dw = a.dw; m->head_pending.dbias = a.dbias;                                                \

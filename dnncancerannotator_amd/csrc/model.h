@@ -186,6 +186,17 @@ struct Model {
     RegionState* region = nullptr;
     bool region_eval = false;
     float* out_ring = nullptr;           // pinned host memory: kStageSlots x 8 floats (out5 of the step that used the slot)
+    // per-step training metrics (dnnca_train_metrics): the fused head kernels store the step's probabilities into `prob` (their
+    // PROB variants), one histogram launch counts them against the raw labels at the sorted thresholds tm_thr into the step's own
+    // row of tm_hist (row kStageSlots: the unstaged entry points), and the row goes to the same row of the pinned tm_pin behind it.
+    // tm_scratch: the launch's accumulator + ticket; its last block moves the counts out and leaves it zeroed (no memset launch)
+    static constexpr int kTmRow = 2 * (1024 + 1);      // u64 per histogram row (1024 = DNNCA_CONF_MAX_THR, kernels.h)
+    int tm_n = 0;                        // thresholds; 0 = off
+    std::vector<int> tm_order;           // sorted position -> the caller's position
+    float* tm_thr = nullptr;
+    unsigned long long *tm_scratch = nullptr, *tm_hist = nullptr, *tm_pin = nullptr;
+    int tm_ran[kStageSlots + 1] = {};    // thresholds counted by the step that last ran on the row (0: none)
+    bool train_metrics_on() const { return tm_n > 0; }
     // measurement
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int prof_mode = 0;                   // 0 off, 1 every launch, 2 only `focus`, 3 every launch keyed by kernel@layer

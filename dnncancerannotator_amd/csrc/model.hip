@@ -51,6 +51,7 @@ Model::~Model() {
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
     if (out_ring) (void)hipHostFree(out_ring);
     if (aug_pin) (void)hipHostFree(aug_pin);
+    if (tm_pin) (void)hipHostFree(tm_pin);
     for (auto e : aug_ev)
         if (e) (void)hipEventDestroy(e);
     if (wg_fork) (void)hipEventDestroy(wg_fork);
@@ -1036,6 +1037,8 @@ int dnnca_set_adam(void* model, float beta1, float beta2, float epsilon) {
 static int convert_out(Model* M, const float* h, dnnca_step_out* out);
 static int confusion_begin(Model* M, const float* thresholds, int n, std::vector<int>& order);
 static int confusion_finish(Model* M, int n, const std::vector<int>& order, dnnca_confusion* out);
+static void confusion_from_hist(const unsigned long long* h, int n, const std::vector<int>& order, dnnca_confusion* out);
+static int train_metrics_count(Model* M, const float* y_dev, int batch, int row);
 
 static int read_out(Model* M, dnnca_step_out* out) {
     float h[5];
@@ -1078,9 +1081,9 @@ int dnnca_forward(void* model, const float* x_nhwc, int batch, int training, flo
     return M->flush_profile();
 }
 
-int dnnca_train_step_dev(void* model, const float* x_dev, const float* y_dev, int batch, float lr, const dnnca_loss_cfg* cfg,
-                         dnnca_step_out* out) {
-    MODEL(model);
+// row: the tm_hist / tm_pin row of the step's training-metric counts (its staging slot, or kStageSlots)
+static int train_step_impl(Model* M, const float* x_dev, const float* y_dev, int batch, float lr, const dnnca_loss_cfg* cfg,
+                           dnnca_step_out* out, int row) {
     if (!cfg) { set_error("null loss cfg"); return DNNCA_EINVAL; }
     M->defer_head = true;
     // (label smoothing blurs the labels in loss_and_backward first: then the head cannot run inside the forward pass)
@@ -1093,8 +1096,16 @@ int dnnca_train_step_dev(void* model, const float* x_dev, const float* y_dev, in
     DN_TRY(frc);
     DN_TRY(M->loss_and_backward(y_dev, batch, *cfg, true));
     DN_TRY(M->optimizer_step(lr));
+    M->tm_ran[row] = 0;
+    if (M->train_metrics_on()) DN_TRY(train_metrics_count(M, y_dev, batch, row));      // the raw labels, never y_smooth
     if (out) return read_out(M, out);
     return DNNCA_OK;
+}
+
+int dnnca_train_step_dev(void* model, const float* x_dev, const float* y_dev, int batch, float lr, const dnnca_loss_cfg* cfg,
+                         dnnca_step_out* out) {
+    MODEL(model);
+    return train_step_impl(M, x_dev, y_dev, batch, lr, cfg, out, Model::kStageSlots);
 }
 
 int dnnca_train_step(void* model, const float* x_nhwc, const float* y_hw, int batch, float lr, const dnnca_loss_cfg* cfg,
@@ -1203,7 +1214,7 @@ int dnnca_train_step_staged(void* model, int slot, const float* x_dev, const flo
     if (batch < 1 || batch > M->desc.max_batch) { set_error("batch %d outside [1, %d]", batch, M->desc.max_batch); return DNNCA_EINVAL; }
     Model::StageSlot& sl = M->stage[slot];
     HIP_TRY(hipStreamWaitEvent(M->stream, sl.uploaded, 0));
-    DN_TRY(dnnca_train_step_dev(model, x_dev, y_dev, batch, lr, cfg, nullptr));
+    DN_TRY(train_step_impl(M, x_dev, y_dev, batch, lr, cfg, nullptr, slot));
     HIP_TRY(hipMemcpyAsync(M->out_ring + slot * 8, M->out5, 5 * sizeof(float), hipMemcpyDeviceToHost, M->stream));
     HIP_TRY(hipEventRecord(sl.done, M->stream));
     sl.has_done = true;
@@ -1271,6 +1282,82 @@ int dnnca_eval_end(void* model, dnnca_confusion* out) {
     return DNNCA_OK;
 }
 
+// ---- per-step training metrics (dnnca_train_metrics) ---------------------------------------------------------------------
+static_assert(Model::kTmRow == 2 * (DNNCA_CONF_MAX_THR + 1), "training-metric histogram rows");
+int dnnca_train_metrics(void* model, const float* thresholds, int n) {
+    MODEL(model);
+    if (n < 0 || n > DNNCA_CONF_MAX_THR || (n > 0 && !thresholds)) { set_error("bad thresholds (0..%d)", DNNCA_CONF_MAX_THR); return DNNCA_EINVAL; }
+    HIP_TRY(hipStreamSynchronize(M->stream));          // steps in flight keep the thresholds they were enqueued with
+    for (int& r : M->tm_ran) r = 0;
+    M->tm_n = 0;
+    M->tm_order.clear();
+    if (n == 0) return DNNCA_OK;
+    if (!M->tm_thr) {
+        DN_TRY(M->alloc((void**)&M->tm_thr, DNNCA_CONF_MAX_THR * 4));
+        DN_TRY(M->alloc((void**)&M->tm_scratch, (Model::kTmRow + 1) * 8));
+        DN_TRY(M->alloc((void**)&M->tm_hist, (size_t)(Model::kStageSlots + 1) * Model::kTmRow * 8));
+        HIP_TRY(hipHostMalloc((void**)&M->tm_pin, (size_t)(Model::kStageSlots + 1) * Model::kTmRow * 8, hipHostMallocDefault));
+    }
+    std::vector<int> order(n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return thresholds[a] < thresholds[b]; });
+    std::vector<float> sorted(n);
+    for (int i = 0; i < n; ++i) {
+        sorted[i] = thresholds[order[i]];
+        if (sorted[i] != sorted[i]) { set_error("threshold %d is NaN", order[i]); return DNNCA_EINVAL; }
+    }
+    HIP_TRY(hipMemcpyAsync(M->tm_thr, sorted.data(), (size_t)n * 4, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));          // `sorted` is a local
+    M->tm_order = order;
+    M->tm_n = n;
+    return DNNCA_OK;
+}
+
+// the step just enqueued: its probabilities (M->prob, written by the head) against its raw labels -> tm_hist[row] -> tm_pin[row]
+static int train_metrics_count(Model* M, const float* y_dev, int batch, int row) {
+    const size_t npix = (size_t)batch * M->outH * M->outW;
+    const int n = M->tm_n;
+    unsigned long long* hist = M->tm_hist + (size_t)row * Model::kTmRow;
+    LAUNCH(M, "train_conf_hist", 8.0 * npix, 10.0 * npix,
+           g_train_conf_hist(M->stream, npix, M->prob, y_dev, M->tm_thr, n, M->tm_scratch, hist));
+    if (M->dry) return DNNCA_OK;
+    HIP_TRY(hipMemcpyAsync(M->tm_pin + (size_t)row * Model::kTmRow, hist, (size_t)2 * (n + 1) * 8, hipMemcpyDeviceToHost, M->stream));
+    M->tm_ran[row] = n;
+    return DNNCA_OK;
+}
+
+static int train_metrics_read(Model* M, int row, dnnca_confusion* out) {
+    if (!out) { set_error("null confusion output"); return DNNCA_EINVAL; }
+    const int n = M->tm_ran[row];
+    if (n == 0 || n != M->tm_n) { set_error("the step has no training-metric counts (dnnca_train_metrics off when it ran)"); return DNNCA_ESTATE; }
+    confusion_from_hist(M->tm_pin + (size_t)row * Model::kTmRow, n, M->tm_order, out);
+    return DNNCA_OK;
+}
+
+int dnnca_last_step_confusion(void* model, dnnca_confusion* out) {
+    MODEL(model);
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return train_metrics_read(M, Model::kStageSlots, out);
+}
+
+int dnnca_staged_confusion(void* model, int slot, dnnca_confusion* out) {
+    MODEL(model);
+    if (slot < 0 || slot >= M->stage_slots || !M->stage[slot].has_done || M->stage[slot].is_eval) {
+        set_error("staging slot %d has run no train step", slot);
+        return DNNCA_ESTATE;
+    }
+    HIP_TRY(hipEventSynchronize(M->stage[slot].done));
+    return train_metrics_read(M, slot, out);
+}
+
+int dnnca_get_prob(void* model, float* prob_out, int64_t n_pixels) {
+    MODEL(model);
+    if (!prob_out || n_pixels < 0 || n_pixels > (int64_t)M->desc.max_batch * M->outH * M->outW) { set_error("bad probability read"); return DNNCA_EINVAL; }
+    HIP_TRY(hipMemcpyAsync(prob_out, M->prob, (size_t)n_pixels * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return DNNCA_OK;
+}
+
 int dnnca_sync(void* model) {
     MODEL(model);
     HIP_TRY(hipStreamSynchronize(M->stream));
@@ -1308,8 +1395,13 @@ static int confusion_finish(Model* M, int n, const std::vector<int>& order, dnnc
     std::vector<unsigned long long> h((size_t)2 * (n + 1));
     HIP_TRY(hipMemcpyAsync(h.data(), M->conf_dev, hbytes, hipMemcpyDeviceToHost, M->stream));
     HIP_TRY(hipStreamSynchronize(M->stream));
-    const unsigned long long* pos = h.data();
-    const unsigned long long* neg = h.data() + (n + 1);
+    confusion_from_hist(h.data(), n, order, out);
+    return DNNCA_OK;
+}
+
+static void confusion_from_hist(const unsigned long long* h, int n, const std::vector<int>& order, dnnca_confusion* out) {
+    const unsigned long long* pos = h;
+    const unsigned long long* neg = h + (n + 1);
     unsigned long long P = 0, N = 0;
     for (int b = 0; b <= n; ++b) { P += pos[b]; N += neg[b]; }
     unsigned long long tp = 0, fp = 0;            // suffix sums: prob > sorted[t]  <=>  bin > t
@@ -1322,7 +1414,6 @@ static int confusion_finish(Model* M, int n, const std::vector<int>& order, dnnc
         o.fn = (double)(P - tp);
         o.tn = (double)(N - fp);
     }
-    return DNNCA_OK;
 }
 
 static int confusion_counts(Model* M, size_t npix, const float* thresholds, int n, dnnca_confusion* out) {
@@ -1650,6 +1741,7 @@ int dnnca_plan_dump(void* model, char* buf, size_t cap) {
     M->head_in_conv.requested = false;
     if (rc == DNNCA_OK) rc = M->loss_and_backward(M->y_stage, B, cfg, true);
     if (rc == DNNCA_OK) rc = M->optimizer_step(1e-3f);
+    if (rc == DNNCA_OK && M->train_metrics_on()) rc = train_metrics_count(M, M->y_stage, B, Model::kStageSlots);
     M->dry = false;
     snprintf(buf, cap, "%s", M->plan_text.c_str());
     return rc;

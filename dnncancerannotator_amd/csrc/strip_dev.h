@@ -86,9 +86,17 @@ struct TailArgs {
     int B, H, W;
     int nstrips, nchunks;    // strips of STRIP columns; row chunks per image
 };
+// the PROB variant's arguments (a struct of their own: the argument block of PROB = false stays as it is)
+struct TailProbArgs : TailArgs {
+    float* prob;             // the step's sigmoid [B, H, W] (per-step training metrics)
+};
+__device__ __forceinline__ float* tail_prob(const TailArgs&) { return nullptr; }
+__device__ __forceinline__ float* tail_prob(const TailProbArgs& a) { return a.prob; }
 
-template <int PFD, int WSCALAR, bool MIDBAR, int ABL = 0, int SHIFT = 0>      // ABL (tuning builds): bit mask of parts left out
-__global__ __launch_bounds__(256, 2) void k_tail3(TailArgs p) {
+// PROB: also store the head's sigmoid of every owned pixel into p.prob (the step's probabilities for the training metrics); the
+// arithmetic is the same, PROB = false compiles to the kernel without the store
+template <int PFD, int WSCALAR, bool MIDBAR, int ABL = 0, int SHIFT = 0, bool PROB = false>      // ABL (tuning builds): bit mask of parts left out
+__global__ __launch_bounds__(256, 2) void k_tail3(std::conditional_t<PROB, TailProbArgs, TailArgs> p) {
     static_assert(PFD == 6 || PFD == 3, "the row loop is unrolled lcm(3 window slots, PFD prefetch slots) times");
     constexpr int NACC = 84, NH = 5, NRED = NACC + NH, WRw = 18, MT = 4, NBK = kPgBuckets;      // slab geometry of k_pgbwd<3,1,3>
     __shared__ float red[4 * NRED + 32];
@@ -120,6 +128,10 @@ __global__ __launch_bounds__(256, 2) void k_tail3(TailArgs p) {
     float colf = col_ok ? 1.0f : 0.f, ownf = lane_own ? 1.0f : 0.f;
     int la = ((lane + 63) & 63) * 4, ra = ((lane + 1) & 63) * 4;      // neighbour lanes (the wrap-around lands in halo lanes)
     asm volatile("" : "+v"(colx), "+v"(coll), "+v"(cold), "+v"(colf), "+v"(ownf), "+v"(la), "+v"(ra));
+    // PROB: the probability store takes the STRIP_HALF offsets of the owned columns (halo and out-of-range lanes drop it)
+    unsigned colp = lane_own ? (unsigned)c * 4u : STRIP_HALF;
+    const __amdgpu_buffer_rsrc_t rsp = __builtin_amdgcn_make_buffer_rsrc((void*)tail_prob(p), 0, npix * 4u, STRIP_RSRC);      // (PROB only)
+    if constexpr (PROB) asm volatile("" : "+v"(colp));
     const unsigned img0 = (unsigned)b * p.H;                  // first row of this image, counted through the batch
     // (uniform row conditions as bit masks: as `cond ? a : b` hipcc turned them into branches around duplicated loads, with
     //  s_waitcnt vmcnt(0) on the joins)
@@ -270,6 +282,7 @@ __global__ __launch_bounds__(256, 2) void k_tail3(TailArgs p) {
             const float e = (ABL & 8) ? 0.5f : __builtin_amdgcn_exp2f(-1.44269504f * fabsf(xl));
             const float r1e = (ABL & 8) ? 0.66f : __builtin_amdgcn_rcpf(1.0f + e);
             const float sig = xl >= 0.f ? r1e : e * r1e;
+            if constexpr (PROB) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sig), rsp, colp + rowpart(rf, inside(rf, r0, r1), 4u), 0, 0);
             const float dl = mk * (sig - z) * gsc * imgf;
             const float dlo = dl * ownm;
             hsum[4] = fmaf(fmaxf(xl, 0.f) - xl * z + 0.693147181f * ((ABL & 8) ? 0.58f : __builtin_amdgcn_logf(1.0f + e)), mk * ownm, hsum[4]);

@@ -184,6 +184,14 @@ class StagingRing:
         check(self.dm.lib.dnnca_eval_region_end(self.dm.handle, out))
         return split_region_counts(out, self._region_n)
 
+    def confusion(self, slot):
+        """[(tp, fp, fn, tn)] per threshold of DeviceModel.train_metrics for the train step that last ran on the slot (exact
+        integers); waits for that step like out(slot) does -- read it before the slot takes its next batch"""
+        n = self.dm._tm_n
+        out = (_lib.Confusion * max(n, 1))()
+        check(self.dm.lib.dnnca_staged_confusion(self.dm.handle, int(slot), out))
+        return [(c.tp, c.fp, c.fn, c.tn) for c in out[:n]]
+
     def out(self, slot):
         """waits for the step that last ran on the slot; raises what train_step would have raised (label / weight assertions)"""
         out = _lib.StepOut()
@@ -216,6 +224,7 @@ class DeviceModel:
         self.n_trainable = n.value
         check(self.lib.dnnca_num_state(self.handle, C.byref(n)))
         self.n_state = n.value
+        self._tm_n = 0
 
     # ---- life-cycle -------------------------------------------------------------------------------------------
     def close(self):
@@ -371,6 +380,27 @@ class DeviceModel:
         out = _lib.StepOut() if want_out else None
         check(self.lib.dnnca_train_step_dev(self.handle, xbuf.ptr, ybuf.ptr, int(batch), float(lr), C.byref(cfg),
                                             C.byref(out) if want_out else None))
+        return out
+
+    # ---- per-step training metrics (Keras fit's compiled metrics, engine.py:273,286) ------------------------------
+    def train_metrics(self, thresholds):
+        """every later train step also counts its own probabilities (training=True forward pass, before the update) against its
+        raw labels at these thresholds (any order, at most 1024); None or empty switches it off"""
+        thr = as_f32(np.asarray(() if thresholds is None else thresholds, np.float32)).ravel()
+        check(self.lib.dnnca_train_metrics(self.handle, fptr(thr) if thr.size else None, int(thr.size)))
+        self._tm_n = int(thr.size)
+
+    def last_step_confusion(self):
+        """[(tp, fp, fn, tn)] per threshold of train_metrics for the last train_step / train_step_dev (exact integers)"""
+        n = self._tm_n
+        out = (_lib.Confusion * max(n, 1))()
+        check(self.lib.dnnca_last_step_confusion(self.handle, out))
+        return [(c.tp, c.fp, c.fn, c.tn) for c in out[:n]]
+
+    def last_prob(self, batch):
+        """the probability buffer [batch, H, W] (last forward / eval step, or a train step with train_metrics on)"""
+        out = np.empty((int(batch), self.in_shape[0], self.in_shape[1]), np.float32)
+        check(self.lib.dnnca_get_prob(self.handle, fptr(out), out.size))
         return out
 
     def last_step_out(self):

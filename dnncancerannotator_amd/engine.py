@@ -48,6 +48,13 @@ def _element_shape(dataset):
     raise ValueError('empty dataset')
 
 
+def _csv_value(v):
+    """one value of a train_log.csv line: %.8g, a list of them in brackets (a metric of several thresholds)"""
+    if isinstance(v, (list, tuple)):
+        return '[%s]' % ' '.join('%.8g' % x for x in v)
+    return '%.8g' % v
+
+
 class TFKerasModel:
     """Encapsulates the DNN model and the library behind it (name kept from the reference for drop-in use)."""
 
@@ -82,6 +89,15 @@ class TFKerasModel:
             self.region_metrics = [m for m in map(region_metrics.solve_region_metric, metric_specs) if m is not None]
             metric_specs = [s for s in metric_specs if not region_metrics.is_region_spec(s)]
         self.metrics = [m for m in map(custom_metrics.solve_metric, metric_specs) if m is not None]
+        # train_metrics: device -- every train step also reports the pixel metrics of its own batch, counted on the GPU from the
+        # probabilities of the step's training=True forward pass (Keras fit updates the compiled metrics per step, engine.py:273,286);
+        # without the key a train step logs loss and lr only
+        train_mode = deploy.pop('train_metrics', None)
+        if train_mode not in (None, 'device'):
+            raise ValueError("deploy_options.train_metrics: only 'device' is supported, got %r" % (train_mode,))
+        self.train_metrics = train_mode == 'device'
+        if self.train_metrics and any(region_metrics.is_region_spec(s) for s in deploy.get('metrics', [])):
+            logging.warning('train_metrics: region-based metrics are not counted per train step (validation still runs them)')
         if deploy.get('optimizer') != 'adam':
             raise NotImplementedError('only the reference\'s optimizer: adam is supported (engine.py:276-284)')
         self.learning_rate = 0.001          # engine.py:278
@@ -254,14 +270,18 @@ class TFKerasModel:
                 source = iter(())
         pending = None          # (slot, step, lr) of an enqueued step whose scalars have not been read
         t0 = time.time()
+        train_objs = self._train_metrics_begin(dm)      # None: the option is off
 
-        def log_step(at, out, lr, extra=None):
-            logs = dict(loss=float(out.loss), lr=lr)
+        def log_step(at, out, lr, extra=None, counts=None):
+            logs = dict(loss=float(out.loss))
+            if train_objs is not None:
+                logs.update(self._train_metric_logs(train_objs, counts))
+            logs['lr'] = lr
             if extra:
                 logs.update(extra)
             results.log(at - 1, logs)
             if log_file is not None:
-                log_file.write('%d,%s\n' % (at, ','.join('%s=%.8g' % kv for kv in logs.items())))
+                log_file.write('%d,%s\n' % (at, ','.join('%s=%s' % (k, _csv_value(v)) for k, v in logs.items())))
             if self.ctx.rank == 0 and (at % 100 == 0 or at == max_steps):
                 logging.info('step %d loss %.6f lr %.3g (%.1f steps/s)', at, out.loss, lr,
                              (at - results.epoch[0]) / max(time.time() - t0, 1e-9))
@@ -272,8 +292,9 @@ class TFKerasModel:
                 slot_, at, lr = pending
                 pending = None
                 out_ = feeder.ring.out(slot_)       # waits for that step only; raises its label / weight assertions
+                counts_ = feeder.ring.confusion(slot_) if train_objs is not None else None
                 feeder.release(slot_)
-                log_step(at, out_, lr)
+                log_step(at, out_, lr, counts=counts_)
 
         try:
             while max_steps is None or step < max_steps:
@@ -286,7 +307,7 @@ class TFKerasModel:
                     self.learning_rate = float(schedule(step, self.learning_rate))
                 if feeder is None:
                     item = ('host', item)
-                slot, out = None, None
+                slot, out, counts = None, None, None
                 if item[0] == 'staged':              # float (x, y), already on its way into a staging slot
                     _, slot, px, py, n = item
                     feeder.ring.train_step(slot, px, py, n, self.learning_rate, cfg)
@@ -312,6 +333,7 @@ class TFKerasModel:
                     else:
                         x, y = shard(np.asarray(batch[0]), np.asarray(batch[1]))
                         out = dm.train_step(x, y, self.learning_rate, cfg)
+                    counts = dm.last_step_confusion() if train_objs is not None else None
                 step += 1
                 self.current_step = step
                 read_pending()                       # the step before this one (its slot goes back to the feeder)
@@ -321,6 +343,8 @@ class TFKerasModel:
                         pending = (slot, step, self.learning_rate)
                         continue
                     out = feeder.ring.out(slot)
+                    if train_objs is not None:
+                        counts = feeder.ring.confusion(slot)
                     feeder.release(slot)
                 extra = {}
                 if save_path is not None and step % save_freq == 0:
@@ -335,7 +359,7 @@ class TFKerasModel:
                         else:
                             wait += 1
                             stop = wait >= early_stop_steps
-                log_step(step, out, self.learning_rate, extra)
+                log_step(step, out, self.learning_rate, extra, counts)
                 if stop:
                     logging.warning('early stopping at step %d', step)
                     break
@@ -343,6 +367,8 @@ class TFKerasModel:
         finally:
             if feeder is not None:
                 feeder.close()
+            if train_objs is not None and self.device_model is dm:
+                dm.train_metrics(None)
         if log_file is not None:
             log_file.close()
         if profile and save_path is not None and self.ctx.rank == 0:
@@ -350,6 +376,33 @@ class TFKerasModel:
                 for row in sorted(dm.profile(), key=lambda r: -r[2]):
                     f.write('%-28s launches %8d  total %10.3f ms\n' % row[:3])
         return results
+
+    def _train_metrics_begin(self, dm):
+        """train_metrics: device -- a set of pixel metric objects of the train steps' own (never the validation objects), their
+        thresholds (all metrics' at once, as _evaluate_staged takes them) switched on in the device model.  None when off."""
+        if not self.train_metrics:
+            return None
+        objs = [copy.deepcopy(m) for m in self.metrics]
+        thr = np.concatenate([m.thresholds for m in objs]) if objs else np.zeros(0, np.float32)
+        if thr.size > 1024:
+            raise ValueError('train_metrics: %d thresholds over all pixel metrics, at most 1024' % thr.size)
+        dm.train_metrics(thr)
+        return objs
+
+    def _train_metric_logs(self, objs, counts):
+        """the step's (tp, fp, fn, tn) rows of every threshold -> {metric name: result()}.  Data parallel: the counts are summed
+        over ranks first (as doubles: exact integers), as MirroredStrategy's sync-on-read metric variables are"""
+        counts = np.asarray(counts if counts is not None else [], np.float64).reshape(-1, 4)
+        if self.ctx.world > 1:
+            counts = np.asarray(self.device_model.comm_allreduce(counts.ravel()), np.float64).reshape(-1, 4)
+        logs, lo = OrderedDict(), 0
+        for m in objs:
+            m.reset_state()
+            m.counts += counts[lo:lo + len(m.thresholds)]
+            lo += len(m.thresholds)
+            r = m.result()
+            logs[m.name] = float(r) if np.ndim(r) == 0 else [float(v) for v in r]
+        return logs
 
     # ---- evaluation (engine.py:139-210) ----------------------------------------------------------------------
     def _evaluate(self, dataset, staged=False):

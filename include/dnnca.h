@@ -197,6 +197,23 @@ int dnnca_eval_begin(void* model, const float* thresholds, int n);
 int dnnca_eval_step_staged(void* model, int slot, const float* x_dev, const float* y_dev, int batch, const dnnca_loss_cfg* cfg);
 int dnnca_eval_end(void* model, dnnca_confusion* out /* n entries, the caller's threshold order */);
 
+/* per-step training metrics (Keras fit updates the compiled metrics on every train step, from that step's training=True forward
+ * pass, engine.py:273,286): with n > 0 thresholds (at most 1024, any order) every later train step stores its own
+ * sigmoid into the model's probability buffer (the fused head kernels' PROB variants) and counts it against the step's RAW labels
+ * (never the label-smoothed copy of the loss) into a histogram of its own: one extra launch, exact integer counts.  n = 0 switches
+ * it off.  The call waits for the model's stream.
+ *   dnnca_last_step_confusion  TP/FP/FN/TN per threshold (the caller's order) of the last dnnca_train_step / _dev; waits for it
+ *   dnnca_staged_confusion     ... of the train step that last ran on the staging slot; waits for it like dnnca_staged_out, so
+ *                              reading both adds no second synchronisation.  Call it before the slot takes its next batch.
+ * Counts are rank-local (data parallel: the caller sums them).  While the option is on, a train step leaves its probabilities in
+ * the buffer that dnnca_pixel_confusion reads; with it off, train steps do not write that buffer (as before). */
+int dnnca_train_metrics(void* model, const float* thresholds, int n);
+int dnnca_last_step_confusion(void* model, dnnca_confusion* out);
+int dnnca_staged_confusion(void* model, int slot, dnnca_confusion* out);
+/* the model's probability buffer (the last forward / eval step, or a train step with the training metrics on): the first n_pixels
+ * floats [B, H, W] to host; waits for the stream */
+int dnnca_get_prob(void* model, float* prob_out, int64_t n_pixels);
+
 /* pixel TP/FP/FN/TN of the last forward/eval probabilities against y at n thresholds (metrics.yaml:2-23 pixel metrics;
  * utils/metrics.py:37-77 FBetaScore builds on them). y_hw is a host buffer [B,H,W]. */
 int dnnca_pixel_confusion(void* model, const float* y_hw, int batch, const float* thresholds, int n, dnnca_confusion* out);
