@@ -683,66 +683,27 @@ void g_adam_finalize(hipStream_t s, size_t n, float* p, const float* g, float* m
 // per-threshold counts are suffix sums of a (positive, negative) histogram over bins 0..nthr -- finished on the host in
 // exact 64-bit integers.  Integer work: bit-exact against numpy by construction.  HBM-bound: 8 B per pixel, read once.
 // NaN probabilities compare false against everything and land in bin 0, as `nan > t` does.
-__global__ __launch_bounds__(256) void k_confusion_hist(size_t n, const float* __restrict__ prob, const float* __restrict__ y,
-                                                        const float* __restrict__ thr, int nthr,
-                                                        unsigned long long* __restrict__ hist /* [2][nthr + 1] */) {
-    __shared__ float sthr[DNNCA_CONF_MAX_THR];
-    __shared__ unsigned h[2][DNNCA_CONF_MAX_THR + 1];
-    for (int i = threadIdx.x; i < nthr; i += 256) sthr[i] = thr[i];
-    for (int i = threadIdx.x; i < 2 * (DNNCA_CONF_MAX_THR + 1); i += 256) (&h[0][0])[i] = 0u;
-    __syncthreads();
-    // most pixels of a segmentation map sit below every threshold or above all of them: those two bins stay in registers
-    unsigned lo[2] = {0u, 0u}, hi[2] = {0u, 0u};
-    size_t T = (size_t)gridDim.x * 256;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += T) {
-        float p = prob[i];
-        int yy = y[i] > 0.5f ? 0 : 1;          // labels are cast to bool [TF-2.6 metrics_utils]; row 0 = positives
-        int a = 0, b = nthr;                   // first index with !(thr[idx] < p)
-        while (a < b) {
-            int mid = (a + b) >> 1;
-            if (sthr[mid] < p) a = mid + 1; else b = mid;
-        }
-        if (a == 0) ++lo[yy];
-        else if (a == nthr) ++hi[yy];
-        else atomicAdd(&h[yy][a], 1u);
-    }
-    for (int r = 0; r < 2; ++r) {
-        if (lo[r]) atomicAdd(&h[r][0], lo[r]);
-        if (hi[r]) atomicAdd(&h[r][nthr], hi[r]);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 2 * (nthr + 1); i += 256) {
-        int r = i / (nthr + 1), bin = i - r * (nthr + 1);
-        unsigned v = h[r][bin];
-        if (v) atomicAdd(hist + i, (unsigned long long)v);
-    }
-}
-
-void g_confusion_hist(hipStream_t s, size_t n, const float* prob, const float* y, const float* thr_sorted, int nthr,
-                      unsigned long long* hist) {
-    unsigned blocks = nblk(n, 256 * 16);
-    if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(k_confusion_hist, dim3(blocks), dim3(256), 0, s, n, prob, y, thr_sorted, nthr, hist);
-}
-
-// the counts of one train step (dnnca_train_metrics): k_confusion_hist's binning, with bin 1 also kept in registers (the AUC
-// thresholds start at -1e-7 and 1/149: the confident background of a trained model lands there, and one LDS word would take it all).
-// Blocks add into `scratch`; the last block to finish (ticket in scratch[2 * (nthr + 1)]) moves the table into `out` and leaves
-// scratch and ticket zeroed for the next step, so the step needs no memset and no second launch.
-__global__ __launch_bounds__(256) void k_train_conf_hist(size_t n, const float* __restrict__ prob, const float* __restrict__ y,
-                                                         const float* __restrict__ thr, int nthr, unsigned long long* scratch,
-                                                         unsigned long long* __restrict__ out) {
+// Every block adds its table into `hist`.  MOVE_OUT = false (evaluation, one-shot counts): `hist` keeps adding up over launches.
+// MOVE_OUT = true (the counts of one train step): `hist` is a scratch table with a ticket in hist[2 * (nthr + 1)]; the last block
+// to finish moves the table into `out` and leaves scratch and ticket zeroed for the next step: no memset, no second launch.
+template <bool MOVE_OUT>
+__global__ __launch_bounds__(256) void k_conf_hist(size_t n, const float* __restrict__ prob, const float* __restrict__ y,
+                                                   const float* __restrict__ thr, int nthr, unsigned long long* hist,
+                                                   unsigned long long* __restrict__ out) {
     __shared__ float sthr[DNNCA_CONF_MAX_THR];
     __shared__ unsigned h[2][DNNCA_CONF_MAX_THR + 1];
     __shared__ bool last;
     for (int i = threadIdx.x; i < nthr; i += 256) sthr[i] = thr[i];
     for (int i = threadIdx.x; i < 2 * (DNNCA_CONF_MAX_THR + 1); i += 256) (&h[0][0])[i] = 0u;
     __syncthreads();
+    // most pixels of a segmentation map sit below every threshold or above all of them: those two bins stay in registers, and so
+    // does bin 1 (the AUC thresholds start at -1e-7 and 1/149: the confident background of a trained model lands there, and one
+    // LDS word would take it all)
     unsigned lo[2] = {0u, 0u}, one[2] = {0u, 0u}, hi[2] = {0u, 0u};
     const size_t T = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += T) {
         const float p = prob[i];
-        const int yy = y[i] > 0.5f ? 0 : 1;    // as k_confusion_hist: labels cast to bool, row 0 = positives
+        const int yy = y[i] > 0.5f ? 0 : 1;    // labels are cast to bool [TF-2.6 metrics_utils]; row 0 = positives
         int a = 0, b = nthr;                   // first index with !(thr[idx] < p)
         while (a < b) {
             const int mid = (a + b) >> 1;
@@ -763,23 +724,25 @@ __global__ __launch_bounds__(256) void k_train_conf_hist(size_t n, const float* 
     for (int i = threadIdx.x; i < nb; i += 256) {
         const int r = i / (nthr + 1), bin = i - r * (nthr + 1);
         const unsigned v = h[r][bin];
-        if (v) atomicAdd(scratch + i, (unsigned long long)v);
+        if (v) atomicAdd(hist + i, (unsigned long long)v);
     }
+    if (!MOVE_OUT) return;
     __threadfence();
     __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(scratch + nb, 1ull) == (unsigned long long)gridDim.x - 1;
+    if (threadIdx.x == 0) last = atomicAdd(hist + nb, 1ull) == (unsigned long long)gridDim.x - 1;
     __syncthreads();
     if (!last) return;
     __threadfence();
-    for (int i = threadIdx.x; i < nb; i += 256) out[i] = atomicExch(scratch + i, 0ull);
-    if (threadIdx.x == 0) atomicExch(scratch + nb, 0ull);
+    for (int i = threadIdx.x; i < nb; i += 256) out[i] = atomicExch(hist + i, 0ull);
+    if (threadIdx.x == 0) atomicExch(hist + nb, 0ull);
 }
 
-void g_train_conf_hist(hipStream_t s, size_t n, const float* prob, const float* y, const float* thr_sorted, int nthr,
-                       unsigned long long* scratch, unsigned long long* out) {
+void g_conf_hist(hipStream_t s, size_t n, const float* prob, const float* y, const float* thr_sorted, int nthr,
+                 unsigned long long* hist, unsigned long long* out) {
     unsigned blocks = nblk(n, 256 * 16);
     if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(k_train_conf_hist, dim3(blocks), dim3(256), 0, s, n, prob, y, thr_sorted, nthr, scratch, out);
+    if (out) hipLaunchKernelGGL(k_conf_hist<true>, dim3(blocks), dim3(256), 0, s, n, prob, y, thr_sorted, nthr, hist, out);
+    else hipLaunchKernelGGL(k_conf_hist<false>, dim3(blocks), dim3(256), 0, s, n, prob, y, thr_sorted, nthr, hist, out);
 }
 
 // one launch at the top of a step: scalar block, flat gradient vector and the weight-gradient slabs

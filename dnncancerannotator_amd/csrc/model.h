@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "common.h"
+#include "kernels.h"                     // DNNCA_CONF_MAX_THR
 
 typedef struct ncclComm* ncclComm_t;
 
@@ -77,6 +78,14 @@ constexpr float kBnEps = 1e-3f;
 
 struct RegionState;                      // kernels_region.hip
 
+// the thresholds of a pixel-confusion histogram: sorted ascending on the device (the kernel bins by binary search); the counts go
+// back to the caller's order through `order`
+struct ConfThresholds {
+    float* dev = nullptr;                // DNNCA_CONF_MAX_THR floats
+    std::vector<int> order;              // sorted position -> the caller's position
+    int n = 0;                           // 0: none
+};
+
 struct Model {
     dnnca_model_desc desc;
     int device = 0;
@@ -89,7 +98,6 @@ struct Model {
     double* scalars = nullptr;           // kScalars doubles
     float* out5 = nullptr;               // = g + nT : [loss, positive_rate, weight, ymin, ymax]
     float *x_stage = nullptr, *y_stage = nullptr, *logits = nullptr, *dlogits = nullptr, *prob = nullptr;
-    float* thr_dev = nullptr;
     // the fused head's partial sums wait for the launch that ends the backward pass (k_pg_fold reduces them: one launch less)
     struct HeadPending { const float* partials = nullptr; int nblocks = 0, C = 0; float* dw = nullptr; float* dbias = nullptr; } head_pending;
     bool head_defer_ok = false;           // set by the pixel-group plan when a k_pg_fold launch exists
@@ -181,22 +189,21 @@ struct Model {
     // staged evaluation (dnnca_eval_begin .. dnnca_eval_end): the pixel-confusion histogram stays on the device and keeps adding
     // up over the batches (exact integer counts); it is read once, at the end
     bool eval_active = false;
-    std::vector<int> eval_order;         // thresholds: sorted position -> the caller's position
+    ConfThresholds eval_thr;             // also the one-shot dnnca_pixel_confusion* (never inside an evaluation); counts in conf_dev
     // region metrics (kernels_region.hip): specs, accumulators and workspace; region_eval: the staged eval steps add region counts
     RegionState* region = nullptr;
     bool region_eval = false;
     float* out_ring = nullptr;           // pinned host memory: kStageSlots x 8 floats (out5 of the step that used the slot)
     // per-step training metrics (dnnca_train_metrics): the fused head kernels store the step's probabilities into `prob` (their
-    // PROB variants), one histogram launch counts them against the raw labels at the sorted thresholds tm_thr into the step's own
-    // row of tm_hist (row kStageSlots: the unstaged entry points), and the row goes to the same row of the pinned tm_pin behind it.
+    // PROB variants), one histogram launch counts them against the raw labels at the thresholds tm_thr (a table of its own:
+    // validation's staged evaluation runs between train steps) into the step's own row of tm_hist (row kStageSlots: the unstaged
+    // entry points), and the row goes to the same row of the pinned tm_pin behind it.
     // tm_scratch: the launch's accumulator + ticket; its last block moves the counts out and leaves it zeroed (no memset launch)
-    static constexpr int kTmRow = 2 * (1024 + 1);      // u64 per histogram row (1024 = DNNCA_CONF_MAX_THR, kernels.h)
-    int tm_n = 0;                        // thresholds; 0 = off
-    std::vector<int> tm_order;           // sorted position -> the caller's position
-    float* tm_thr = nullptr;
+    static constexpr int kTmRow = 2 * (DNNCA_CONF_MAX_THR + 1);      // u64 per histogram row
+    ConfThresholds tm_thr;               // n = 0: off
     unsigned long long *tm_scratch = nullptr, *tm_hist = nullptr, *tm_pin = nullptr;
     int tm_ran[kStageSlots + 1] = {};    // thresholds counted by the step that last ran on the row (0: none)
-    bool train_metrics_on() const { return tm_n > 0; }
+    bool train_metrics_on() const { return tm_thr.n > 0; }
     // measurement
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int prof_mode = 0;                   // 0 off, 1 every launch, 2 only `focus`, 3 every launch keyed by kernel@layer

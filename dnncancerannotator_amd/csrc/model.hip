@@ -427,7 +427,7 @@ int Model::build() {
     DN_TRY(alloc((void**)&logits, npix * 4));
     DN_TRY(alloc((void**)&dlogits, npix * 4));
     DN_TRY(alloc((void**)&prob, npix * 4));
-    DN_TRY(alloc((void**)&thr_dev, DNNCA_CONF_MAX_THR * 4));
+    DN_TRY(alloc((void**)&eval_thr.dev, DNNCA_CONF_MAX_THR * 4));
     DN_TRY(alloc((void**)&head_partials, 2048 * 72 * 4));
     DN_TRY(alloc((void**)&conf_dev, 2 * (DNNCA_CONF_MAX_THR + 1) * 8));     // confusion histogram / host all-reduce staging
     // Keras defaults for the non-trainable / BN variables: gamma 1, moving_variance 1 (the rest 0)
@@ -1034,22 +1034,31 @@ int dnnca_set_adam(void* model, float beta1, float beta2, float epsilon) {
     return DNNCA_OK;
 }
 
-static int convert_out(Model* M, const float* h, dnnca_step_out* out);
-static int confusion_begin(Model* M, const float* thresholds, int n, std::vector<int>& order);
-static int confusion_finish(Model* M, int n, const std::vector<int>& order, dnnca_confusion* out);
-static void confusion_from_hist(const unsigned long long* h, int n, const std::vector<int>& order, dnnca_confusion* out);
-static int train_metrics_count(Model* M, const float* y_dev, int batch, int row);
-
-static int read_out(Model* M, dnnca_step_out* out) {
-    float h[5];
-    HIP_TRY(hipMemcpyAsync(h, M->out5, sizeof(h), hipMemcpyDeviceToHost, M->stream));
-    HIP_TRY(hipStreamSynchronize(M->stream));
-    DN_TRY(M->flush_profile());
-    return convert_out(M, h, out);
+// ---- helpers of the step entry points ----------------------------------------------------------------------------------------
+static int check_batch(Model* M, int batch) {
+    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch %d outside [1, %d]", batch, M->desc.max_batch); return DNNCA_EINVAL; }
+    return DNNCA_OK;
 }
 
-static int convert_out(Model* M, const float* h, dnnca_step_out* out) {
-    out->loss = h[0] / (float)M->world;   // after the all-reduce the slot holds the sum over ranks of the local means
+static int check_slot(Model* M, int slot) {
+    if (slot < 0 || slot >= M->stage_slots) { set_error("staging slot %d outside [0, %d)", slot, M->stage_slots); return DNNCA_EINVAL; }
+    return DNNCA_OK;
+}
+
+// a host batch -> x_stage and, with `labels`, y_stage
+static int stage_inputs(Model* M, int batch, const float* x_nhwc, const float* y_hw, bool labels) {
+    DN_TRY(check_batch(M, batch));
+    const size_t nx = (size_t)batch * M->desc.height * M->desc.width * M->desc.in_channels;
+    const size_t npix = (size_t)batch * M->outH * M->outW;
+    HIP_TRY(hipMemcpyAsync(M->x_stage, x_nhwc, nx * 4, hipMemcpyHostToDevice, M->stream));
+    if (labels) HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, npix * 4, hipMemcpyHostToDevice, M->stream));
+    return DNNCA_OK;
+}
+
+// h: the five step outputs; ranks: how many ranks' local means the loss slot holds the sum of (train steps are all-reduced:
+// the world size; evaluation is rank-local: 1)
+static int convert_out(const float* h, int ranks, dnnca_step_out* out) {
+    out->loss = h[0] / (float)ranks;
     out->positive_rate = h[1];
     out->weight = h[2];
     out->label_min = h[3];
@@ -1060,6 +1069,93 @@ static int convert_out(Model* M, const float* h, dnnca_step_out* out) {
     return DNNCA_OK;
 }
 
+static int read_out(Model* M, int ranks, dnnca_step_out* out) {
+    float h[5];
+    HIP_TRY(hipMemcpyAsync(h, M->out5, sizeof(h), hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    DN_TRY(M->flush_profile());
+    return convert_out(h, ranks, out);
+}
+
+// ---- pixel confusion: one threshold table type, one histogram kernel (g_conf_hist) -------------------------------------------
+static int check_thresholds(const float* thresholds, int n) {
+    if (n < 0 || n > DNNCA_CONF_MAX_THR || (n > 0 && !thresholds)) { set_error("bad thresholds (0..%d)", DNNCA_CONF_MAX_THR); return DNNCA_EINVAL; }
+    return DNNCA_OK;
+}
+
+// thresholds -> ascending in t.dev (the histogram kernel wants them sorted); t.order[i] = the caller's position of sorted i.
+// Returns with the upload done; on an error the table is empty.
+static int conf_thresholds_set(Model* M, ConfThresholds& t, const float* thresholds, int n) {
+    t.n = 0;
+    t.order.resize(n);
+    if (n == 0) return DNNCA_OK;
+    for (int i = 0; i < n; ++i) t.order[i] = i;
+    std::stable_sort(t.order.begin(), t.order.end(), [&](int a, int b) { return thresholds[a] < thresholds[b]; });
+    std::vector<float> sorted(n);
+    for (int i = 0; i < n; ++i) {
+        sorted[i] = thresholds[t.order[i]];
+        if (sorted[i] != sorted[i]) { set_error("threshold %d is NaN", t.order[i]); return DNNCA_EINVAL; }
+    }
+    HIP_TRY(hipMemcpyAsync(t.dev, sorted.data(), (size_t)n * 4, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));          // `sorted` is a local
+    t.n = n;
+    return DNNCA_OK;
+}
+
+// histogram [positives | negatives][n + 1 bins] -> TP / FP / FN / TN per threshold, in the caller's order
+static void confusion_from_hist(const unsigned long long* h, const ConfThresholds& t, dnnca_confusion* out) {
+    const int n = t.n;
+    const unsigned long long* pos = h;
+    const unsigned long long* neg = h + (n + 1);
+    unsigned long long P = 0, N = 0;
+    for (int b = 0; b <= n; ++b) { P += pos[b]; N += neg[b]; }
+    unsigned long long tp = 0, fp = 0;            // suffix sums: prob > sorted[t]  <=>  bin > t
+    for (int i = n - 1; i >= 0; --i) {
+        tp += pos[i + 1];
+        fp += neg[i + 1];
+        dnnca_confusion& o = out[t.order[i]];
+        o.tp = (double)tp;
+        o.fp = (double)fp;
+        o.fn = (double)(P - tp);
+        o.tn = (double)(N - fp);
+    }
+}
+
+// evaluation and the one-shot counts: eval_thr + the histogram conf_dev, which keeps adding up until it is read
+static int confusion_begin(Model* M, const float* thresholds, int n) {
+    DN_TRY(conf_thresholds_set(M, M->eval_thr, thresholds, n));
+    HIP_TRY(hipMemsetAsync(M->conf_dev, 0, (size_t)2 * (n + 1) * 8, M->stream));
+    return DNNCA_OK;
+}
+
+static void confusion_add(Model* M, size_t npix, const float* y_dev) {
+    g_conf_hist(M->stream, npix, M->prob, y_dev, M->eval_thr.dev, M->eval_thr.n, reinterpret_cast<unsigned long long*>(M->conf_dev),
+                nullptr);
+}
+
+static int confusion_finish(Model* M, dnnca_confusion* out) {
+    std::vector<unsigned long long> h((size_t)2 * (M->eval_thr.n + 1));
+    HIP_TRY(hipMemcpyAsync(h.data(), M->conf_dev, h.size() * 8, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    confusion_from_hist(h.data(), M->eval_thr, out);
+    return DNNCA_OK;
+}
+
+// per-step training metrics: the step just enqueued, its probabilities (M->prob, written by the head) against its raw labels at
+// tm_thr -> tm_hist[row] -> tm_pin[row]
+static int train_metrics_count(Model* M, const float* y_dev, int batch, int row) {
+    const size_t npix = (size_t)batch * M->outH * M->outW;
+    const int n = M->tm_thr.n;
+    unsigned long long* hist = M->tm_hist + (size_t)row * Model::kTmRow;
+    LAUNCH(M, "train_conf_hist", 8.0 * npix, 10.0 * npix,
+           g_conf_hist(M->stream, npix, M->prob, y_dev, M->tm_thr.dev, n, M->tm_scratch, hist));
+    if (M->dry) return DNNCA_OK;
+    HIP_TRY(hipMemcpyAsync(M->tm_pin + (size_t)row * Model::kTmRow, hist, (size_t)2 * (n + 1) * 8, hipMemcpyDeviceToHost, M->stream));
+    M->tm_ran[row] = n;
+    return DNNCA_OK;
+}
+
+// ---- steps on host or device batches ------------------------------------------------------------------------------------------
 int dnnca_forward_dev(void* model, const float* x_dev, int batch, int training) {
     MODEL(model);
     DN_TRY(M->forward(x_dev, batch, training != 0));
@@ -1070,10 +1166,8 @@ int dnnca_forward_dev(void* model, const float* x_dev, int batch, int training) 
 
 int dnnca_forward(void* model, const float* x_nhwc, int batch, int training, float* prob_out, float* logit_out) {
     MODEL(model);
-    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch %d outside [1, %d]", batch, M->desc.max_batch); return DNNCA_EINVAL; }
-    size_t nx = (size_t)batch * M->desc.height * M->desc.width * M->desc.in_channels;
-    size_t npix = (size_t)batch * M->outH * M->outW;
-    HIP_TRY(hipMemcpyAsync(M->x_stage, x_nhwc, nx * 4, hipMemcpyHostToDevice, M->stream));
+    DN_TRY(stage_inputs(M, batch, x_nhwc, nullptr, false));
+    const size_t npix = (size_t)batch * M->outH * M->outW;
     DN_TRY(dnnca_forward_dev(model, M->x_stage, batch, training));
     if (prob_out) HIP_TRY(hipMemcpyAsync(prob_out, M->prob, npix * 4, hipMemcpyDeviceToHost, M->stream));
     if (logit_out) HIP_TRY(hipMemcpyAsync(logit_out, M->logits, npix * 4, hipMemcpyDeviceToHost, M->stream));
@@ -1098,7 +1192,7 @@ static int train_step_impl(Model* M, const float* x_dev, const float* y_dev, int
     DN_TRY(M->optimizer_step(lr));
     M->tm_ran[row] = 0;
     if (M->train_metrics_on()) DN_TRY(train_metrics_count(M, y_dev, batch, row));      // the raw labels, never y_smooth
-    if (out) return read_out(M, out);
+    if (out) return read_out(M, M->world, out);      // after the all-reduce the loss slot holds the sum over ranks of the local means
     return DNNCA_OK;
 }
 
@@ -1111,11 +1205,7 @@ int dnnca_train_step_dev(void* model, const float* x_dev, const float* y_dev, in
 int dnnca_train_step(void* model, const float* x_nhwc, const float* y_hw, int batch, float lr, const dnnca_loss_cfg* cfg,
                      dnnca_step_out* out) {
     MODEL(model);
-    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch %d outside [1, %d]", batch, M->desc.max_batch); return DNNCA_EINVAL; }
-    size_t nx = (size_t)batch * M->desc.height * M->desc.width * M->desc.in_channels;
-    size_t npix = (size_t)batch * M->outH * M->outW;
-    HIP_TRY(hipMemcpyAsync(M->x_stage, x_nhwc, nx * 4, hipMemcpyHostToDevice, M->stream));
-    HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, npix * 4, hipMemcpyHostToDevice, M->stream));
+    DN_TRY(stage_inputs(M, batch, x_nhwc, y_hw, true));
     dnnca_step_out tmp;
     return dnnca_train_step_dev(model, M->x_stage, M->y_stage, batch, lr, cfg, out ? out : &tmp);
 }
@@ -1124,26 +1214,18 @@ int dnnca_eval_step(void* model, const float* x_nhwc, const float* y_hw, int bat
                     dnnca_step_out* out, float* prob_out) {
     MODEL(model);
     if (!cfg) { set_error("null loss cfg"); return DNNCA_EINVAL; }
-    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch %d outside [1, %d]", batch, M->desc.max_batch); return DNNCA_EINVAL; }
-    size_t nx = (size_t)batch * M->desc.height * M->desc.width * M->desc.in_channels;
-    size_t npix = (size_t)batch * M->outH * M->outW;
-    HIP_TRY(hipMemcpyAsync(M->x_stage, x_nhwc, nx * 4, hipMemcpyHostToDevice, M->stream));
-    HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, npix * 4, hipMemcpyHostToDevice, M->stream));
+    DN_TRY(stage_inputs(M, batch, x_nhwc, y_hw, true));
     DN_TRY(M->forward(M->x_stage, batch, false));
     DN_TRY(M->loss_and_backward(M->y_stage, batch, *cfg, false));
-    if (prob_out) HIP_TRY(hipMemcpyAsync(prob_out, M->prob, npix * 4, hipMemcpyDeviceToHost, M->stream));
+    if (prob_out) HIP_TRY(hipMemcpyAsync(prob_out, M->prob, (size_t)batch * M->outH * M->outW * 4, hipMemcpyDeviceToHost, M->stream));
     dnnca_step_out tmp;
-    int world = M->world;
-    M->world = 1;   // evaluation is rank-local: the loss slot was not all-reduced
-    int rc = read_out(M, out ? out : &tmp);
-    M->world = world;
-    return rc;
+    return read_out(M, 1, out ? out : &tmp);         // evaluation is rank-local: the loss slot was not all-reduced
 }
 
 int dnnca_last_step_out(void* model, dnnca_step_out* out) {
     MODEL(model);
     if (!out) return DNNCA_EINVAL;
-    return read_out(M, out);
+    return read_out(M, M->world, out);
 }
 
 // ---- input pipeline: staging ring + copy stream (model.h) ------------------------------------------------------------------
@@ -1176,7 +1258,7 @@ int dnnca_stage_init(void* model, int slots, size_t bytes_per_slot) {
 int dnnca_stage_upload(void* model, int slot, const void* host_a, size_t bytes_a, const void* host_b, size_t bytes_b,
                        void** a_dev, void** b_dev) {
     MODEL(model);
-    if (slot < 0 || slot >= M->stage_slots) { set_error("staging slot %d outside [0, %d)", slot, M->stage_slots); return DNNCA_EINVAL; }
+    DN_TRY(check_slot(M, slot));
     if (stage_align(bytes_a) + bytes_b > M->stage_bytes) {
         set_error("staging slot holds %zu bytes, asked for %zu + %zu", M->stage_bytes, bytes_a, bytes_b);
         return DNNCA_EINVAL;
@@ -1195,32 +1277,43 @@ int dnnca_stage_upload(void* model, int slot, const void* host_a, size_t bytes_a
 
 int dnnca_stage_uploaded(void* model, int slot) {
     MODEL(model);
-    if (slot < 0 || slot >= M->stage_slots) { set_error("staging slot %d outside [0, %d)", slot, M->stage_slots); return DNNCA_EINVAL; }
+    DN_TRY(check_slot(M, slot));
     HIP_TRY(hipEventSynchronize(M->stage[slot].uploaded));
     return DNNCA_OK;
 }
 
 int dnnca_stage_wait(void* model, int slot) {
     MODEL(model);
-    if (slot < 0 || slot >= M->stage_slots) { set_error("staging slot %d outside [0, %d)", slot, M->stage_slots); return DNNCA_EINVAL; }
+    DN_TRY(check_slot(M, slot));
     HIP_TRY(hipStreamWaitEvent(M->stream, M->stage[slot].uploaded, 0));
+    return DNNCA_OK;
+}
+
+// a staged step: the main stream waits for the slot's upload ...
+static int staged_begin(Model* M, int slot, int batch) {
+    DN_TRY(check_slot(M, slot));
+    DN_TRY(check_batch(M, batch));
+    HIP_TRY(hipStreamWaitEvent(M->stream, M->stage[slot].uploaded, 0));
+    return DNNCA_OK;
+}
+
+// ... and sends its outputs to the slot's row of the pinned ring, `done` behind them
+static int staged_end(Model* M, int slot, int batch, bool is_eval) {
+    Model::StageSlot& sl = M->stage[slot];
+    HIP_TRY(hipMemcpyAsync(M->out_ring + slot * 8, M->out5, 5 * sizeof(float), hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipEventRecord(sl.done, M->stream));
+    sl.has_done = true;
+    sl.is_eval = is_eval;
+    sl.batch = batch;
     return DNNCA_OK;
 }
 
 int dnnca_train_step_staged(void* model, int slot, const float* x_dev, const float* y_dev, int batch, float lr,
                             const dnnca_loss_cfg* cfg) {
     MODEL(model);
-    if (slot < 0 || slot >= M->stage_slots) { set_error("staging slot %d outside [0, %d)", slot, M->stage_slots); return DNNCA_EINVAL; }
-    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch %d outside [1, %d]", batch, M->desc.max_batch); return DNNCA_EINVAL; }
-    Model::StageSlot& sl = M->stage[slot];
-    HIP_TRY(hipStreamWaitEvent(M->stream, sl.uploaded, 0));
+    DN_TRY(staged_begin(M, slot, batch));
     DN_TRY(train_step_impl(M, x_dev, y_dev, batch, lr, cfg, nullptr, slot));
-    HIP_TRY(hipMemcpyAsync(M->out_ring + slot * 8, M->out5, 5 * sizeof(float), hipMemcpyDeviceToHost, M->stream));
-    HIP_TRY(hipEventRecord(sl.done, M->stream));
-    sl.has_done = true;
-    sl.is_eval = false;
-    sl.batch = batch;
-    return DNNCA_OK;
+    return staged_end(M, slot, batch, false);
 }
 
 int dnnca_staged_out(void* model, int slot, dnnca_step_out* out) {
@@ -1229,20 +1322,17 @@ int dnnca_staged_out(void* model, int slot, dnnca_step_out* out) {
     if (slot < 0 || slot >= M->stage_slots || !M->stage[slot].has_done) { set_error("staging slot %d has run no step", slot); return DNNCA_ESTATE; }
     HIP_TRY(hipEventSynchronize(M->stage[slot].done));
     if (M->prof_mode) DN_TRY(M->flush_profile());
-    const int world = M->world;
-    if (M->stage[slot].is_eval) M->world = 1;      // evaluation is rank-local: the loss slot was not all-reduced
-    const int rc = convert_out(M, M->out_ring + slot * 8, out);
-    M->world = world;
-    return rc;
+    // evaluation is rank-local: the loss slot was not all-reduced
+    return convert_out(M->out_ring + slot * 8, M->stage[slot].is_eval ? 1 : M->world, out);
 }
 
 // ---- staged evaluation: keras Model.evaluate (engine.py:198-203) over the staging ring ---------------------------------
 int dnnca_eval_begin(void* model, const float* thresholds, int n) {
     MODEL(model);
-    if (n < 0 || n > DNNCA_CONF_MAX_THR || (n > 0 && !thresholds)) { set_error("bad thresholds (0..%d)", DNNCA_CONF_MAX_THR); return DNNCA_EINVAL; }
+    DN_TRY(check_thresholds(thresholds, n));
     if (!M->stage_slots) { set_error("dnnca_eval_begin before dnnca_stage_init"); return DNNCA_ESTATE; }
-    M->eval_order.clear();
-    if (n > 0) DN_TRY(confusion_begin(M, thresholds, n, M->eval_order));
+    M->eval_thr.n = 0;
+    if (n > 0) DN_TRY(confusion_begin(M, thresholds, n));
     M->eval_active = true;
     M->region_eval = false;
     return DNNCA_OK;
@@ -1252,85 +1342,47 @@ int dnnca_eval_step_staged(void* model, int slot, const float* x_dev, const floa
     MODEL(model);
     if (!M->eval_active) { set_error("dnnca_eval_step_staged outside dnnca_eval_begin .. dnnca_eval_end"); return DNNCA_ESTATE; }
     if (!cfg) { set_error("null loss cfg"); return DNNCA_EINVAL; }
-    if (slot < 0 || slot >= M->stage_slots) { set_error("staging slot %d outside [0, %d)", slot, M->stage_slots); return DNNCA_EINVAL; }
-    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch %d outside [1, %d]", batch, M->desc.max_batch); return DNNCA_EINVAL; }
-    Model::StageSlot& sl = M->stage[slot];
-    HIP_TRY(hipStreamWaitEvent(M->stream, sl.uploaded, 0));
+    DN_TRY(staged_begin(M, slot, batch));
     DN_TRY(M->forward(x_dev, batch, false));
     DN_TRY(M->loss_and_backward(y_dev, batch, *cfg, false));
-    const int n = (int)M->eval_order.size();
-    if (n > 0)      // the metrics see the labels as given (a smoothed copy exists only inside the loss, utils/losses.py:62-67)
-        g_confusion_hist(M->stream, (size_t)batch * M->outH * M->outW, M->prob, y_dev, M->thr_dev, n,
-                         reinterpret_cast<unsigned long long*>(M->conf_dev));
+    // the metrics see the labels as given (a smoothed copy exists only inside the loss, utils/losses.py:62-67)
+    if (M->eval_thr.n > 0) confusion_add(M, (size_t)batch * M->outH * M->outW, y_dev);
     if (M->region_eval) DN_TRY(region_accumulate(M, M->prob, y_dev, batch, M->outH, M->outW));
-    HIP_TRY(hipMemcpyAsync(M->out_ring + slot * 8, M->out5, 5 * sizeof(float), hipMemcpyDeviceToHost, M->stream));
-    HIP_TRY(hipEventRecord(sl.done, M->stream));
-    sl.has_done = true;
-    sl.is_eval = true;
-    sl.batch = batch;
-    return DNNCA_OK;
+    return staged_end(M, slot, batch, true);
 }
 
 int dnnca_eval_end(void* model, dnnca_confusion* out) {
     MODEL(model);
     if (!M->eval_active) { set_error("dnnca_eval_end without dnnca_eval_begin"); return DNNCA_ESTATE; }
     M->eval_active = false;
-    const int n = (int)M->eval_order.size();
-    if (n > 0 && !out) { set_error("null confusion output"); return DNNCA_EINVAL; }
-    if (n > 0) return confusion_finish(M, n, M->eval_order, out);
+    if (M->eval_thr.n > 0 && !out) { set_error("null confusion output"); return DNNCA_EINVAL; }
+    if (M->eval_thr.n > 0) return confusion_finish(M, out);
     HIP_TRY(hipStreamSynchronize(M->stream));
     return DNNCA_OK;
 }
 
 // ---- per-step training metrics (dnnca_train_metrics) ---------------------------------------------------------------------
-static_assert(Model::kTmRow == 2 * (DNNCA_CONF_MAX_THR + 1), "training-metric histogram rows");
 int dnnca_train_metrics(void* model, const float* thresholds, int n) {
     MODEL(model);
-    if (n < 0 || n > DNNCA_CONF_MAX_THR || (n > 0 && !thresholds)) { set_error("bad thresholds (0..%d)", DNNCA_CONF_MAX_THR); return DNNCA_EINVAL; }
+    DN_TRY(check_thresholds(thresholds, n));
     HIP_TRY(hipStreamSynchronize(M->stream));          // steps in flight keep the thresholds they were enqueued with
     for (int& r : M->tm_ran) r = 0;
-    M->tm_n = 0;
-    M->tm_order.clear();
+    M->tm_thr.n = 0;
     if (n == 0) return DNNCA_OK;
-    if (!M->tm_thr) {
-        DN_TRY(M->alloc((void**)&M->tm_thr, DNNCA_CONF_MAX_THR * 4));
+    if (!M->tm_thr.dev) {
+        DN_TRY(M->alloc((void**)&M->tm_thr.dev, DNNCA_CONF_MAX_THR * 4));
         DN_TRY(M->alloc((void**)&M->tm_scratch, (Model::kTmRow + 1) * 8));
         DN_TRY(M->alloc((void**)&M->tm_hist, (size_t)(Model::kStageSlots + 1) * Model::kTmRow * 8));
         HIP_TRY(hipHostMalloc((void**)&M->tm_pin, (size_t)(Model::kStageSlots + 1) * Model::kTmRow * 8, hipHostMallocDefault));
     }
-    std::vector<int> order(n);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return thresholds[a] < thresholds[b]; });
-    std::vector<float> sorted(n);
-    for (int i = 0; i < n; ++i) {
-        sorted[i] = thresholds[order[i]];
-        if (sorted[i] != sorted[i]) { set_error("threshold %d is NaN", order[i]); return DNNCA_EINVAL; }
-    }
-    HIP_TRY(hipMemcpyAsync(M->tm_thr, sorted.data(), (size_t)n * 4, hipMemcpyHostToDevice, M->stream));
-    HIP_TRY(hipStreamSynchronize(M->stream));          // `sorted` is a local
-    M->tm_order = order;
-    M->tm_n = n;
-    return DNNCA_OK;
-}
-
-// the step just enqueued: its probabilities (M->prob, written by the head) against its raw labels -> tm_hist[row] -> tm_pin[row]
-static int train_metrics_count(Model* M, const float* y_dev, int batch, int row) {
-    const size_t npix = (size_t)batch * M->outH * M->outW;
-    const int n = M->tm_n;
-    unsigned long long* hist = M->tm_hist + (size_t)row * Model::kTmRow;
-    LAUNCH(M, "train_conf_hist", 8.0 * npix, 10.0 * npix,
-           g_train_conf_hist(M->stream, npix, M->prob, y_dev, M->tm_thr, n, M->tm_scratch, hist));
-    if (M->dry) return DNNCA_OK;
-    HIP_TRY(hipMemcpyAsync(M->tm_pin + (size_t)row * Model::kTmRow, hist, (size_t)2 * (n + 1) * 8, hipMemcpyDeviceToHost, M->stream));
-    M->tm_ran[row] = n;
-    return DNNCA_OK;
+    return conf_thresholds_set(M, M->tm_thr, thresholds, n);
 }
 
 static int train_metrics_read(Model* M, int row, dnnca_confusion* out) {
     if (!out) { set_error("null confusion output"); return DNNCA_EINVAL; }
     const int n = M->tm_ran[row];
-    if (n == 0 || n != M->tm_n) { set_error("the step has no training-metric counts (dnnca_train_metrics off when it ran)"); return DNNCA_ESTATE; }
-    confusion_from_hist(M->tm_pin + (size_t)row * Model::kTmRow, n, M->tm_order, out);
+    if (n == 0 || n != M->tm_thr.n) { set_error("the step has no training-metric counts (dnnca_train_metrics off when it ran)"); return DNNCA_ESTATE; }
+    confusion_from_hist(M->tm_pin + (size_t)row * Model::kTmRow, M->tm_thr, out);
     return DNNCA_OK;
 }
 
@@ -1373,55 +1425,12 @@ int dnnca_dev_free(void* dev_ptr) { HIP_TRY(hipFree(dev_ptr)); return DNNCA_OK; 
 int dnnca_memcpy_h2d(void* dev_dst, const void* host_src, size_t bytes) { HIP_TRY(hipMemcpy(dev_dst, host_src, bytes, hipMemcpyHostToDevice)); return DNNCA_OK; }
 int dnnca_memcpy_d2h(void* host_dst, const void* dev_src, size_t bytes) { HIP_TRY(hipMemcpy(host_dst, dev_src, bytes, hipMemcpyDeviceToHost)); return DNNCA_OK; }
 
-// thresholds -> ascending on the device (the histogram kernel wants them sorted), histogram zeroed; order[t] = caller's position
-static int confusion_begin(Model* M, const float* thresholds, int n, std::vector<int>& order) {
-    order.resize(n);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return thresholds[a] < thresholds[b]; });
-    std::vector<float> sorted(n);
-    for (int i = 0; i < n; ++i) {
-        sorted[i] = thresholds[order[i]];
-        if (sorted[i] != sorted[i]) { set_error("threshold %d is NaN", order[i]); return DNNCA_EINVAL; }
-    }
-    HIP_TRY(hipMemcpyAsync(M->thr_dev, sorted.data(), (size_t)n * 4, hipMemcpyHostToDevice, M->stream));
-    HIP_TRY(hipMemsetAsync(M->conf_dev, 0, (size_t)2 * (n + 1) * 8, M->stream));
-    HIP_TRY(hipStreamSynchronize(M->stream));          // `sorted` is a local
-    return DNNCA_OK;
-}
-
-// histogram [positives | negatives][n + 1 bins] -> TP / FP / FN / TN per threshold, in the caller's order
-static int confusion_finish(Model* M, int n, const std::vector<int>& order, dnnca_confusion* out) {
-    const size_t hbytes = (size_t)2 * (n + 1) * 8;
-    std::vector<unsigned long long> h((size_t)2 * (n + 1));
-    HIP_TRY(hipMemcpyAsync(h.data(), M->conf_dev, hbytes, hipMemcpyDeviceToHost, M->stream));
-    HIP_TRY(hipStreamSynchronize(M->stream));
-    confusion_from_hist(h.data(), n, order, out);
-    return DNNCA_OK;
-}
-
-static void confusion_from_hist(const unsigned long long* h, int n, const std::vector<int>& order, dnnca_confusion* out) {
-    const unsigned long long* pos = h;
-    const unsigned long long* neg = h + (n + 1);
-    unsigned long long P = 0, N = 0;
-    for (int b = 0; b <= n; ++b) { P += pos[b]; N += neg[b]; }
-    unsigned long long tp = 0, fp = 0;            // suffix sums: prob > sorted[t]  <=>  bin > t
-    for (int t = n - 1; t >= 0; --t) {
-        tp += pos[t + 1];
-        fp += neg[t + 1];
-        dnnca_confusion& o = out[order[t]];
-        o.tp = (double)tp;
-        o.fp = (double)fp;
-        o.fn = (double)(P - tp);
-        o.tn = (double)(N - fp);
-    }
-}
-
+// ---- one-shot pixel confusion of M->prob against y_stage ---------------------------------------------------------------------
 static int confusion_counts(Model* M, size_t npix, const float* thresholds, int n, dnnca_confusion* out) {
     if (M->eval_active) { set_error("dnnca_pixel_confusion* inside dnnca_eval_begin .. dnnca_eval_end (the histogram is in use)"); return DNNCA_ESTATE; }
-    std::vector<int> order;
-    DN_TRY(confusion_begin(M, thresholds, n, order));
-    g_confusion_hist(M->stream, npix, M->prob, M->y_stage, M->thr_dev, n, reinterpret_cast<unsigned long long*>(M->conf_dev));
-    return confusion_finish(M, n, order, out);
+    DN_TRY(confusion_begin(M, thresholds, n));
+    confusion_add(M, npix, M->y_stage);
+    return confusion_finish(M, out);
 }
 
 int dnnca_pixel_confusion(void* model, const float* y_hw, int batch, const float* thresholds, int n, dnnca_confusion* out) {
@@ -1430,8 +1439,8 @@ int dnnca_pixel_confusion(void* model, const float* y_hw, int batch, const float
         set_error("bad confusion arguments (1..%d thresholds)", DNNCA_CONF_MAX_THR);
         return DNNCA_EINVAL;
     }
-    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch out of range"); return DNNCA_EINVAL; }
-    size_t npix = (size_t)batch * M->outH * M->outW;
+    DN_TRY(check_batch(M, batch));
+    const size_t npix = (size_t)batch * M->outH * M->outW;
     HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, npix * 4, hipMemcpyHostToDevice, M->stream));
     return confusion_counts(M, npix, thresholds, n, out);
 }
@@ -1479,7 +1488,7 @@ int dnnca_region_confusion_of(void* model, const float* prob_hw, const float* y_
 int dnnca_region_confusion(void* model, const float* y_hw, int batch, const dnnca_region_spec* spec, dnnca_region_counts* out) {
     MODEL(model);
     if (!y_hw || !spec || !out) { set_error("bad region confusion arguments"); return DNNCA_EINVAL; }
-    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch out of range"); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
     const size_t n = (size_t)batch * M->outH * M->outW;
     HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
     return region_one(M, M->prob, M->y_stage, batch, M->outH, M->outW, spec, out);
@@ -1489,7 +1498,7 @@ int dnnca_region_confusion_slices(void* model, const float* prob_hw, const float
                                   int n, dnnca_region_counts* out) {
     MODEL(model);
     if (!y_hw || !specs || !out || n < 1) { set_error("bad region confusion arguments"); return DNNCA_EINVAL; }
-    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch out of range"); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
     if (M->region_eval) { set_error("dnnca_region_confusion* inside dnnca_eval_region_begin .. dnnca_eval_region_end"); return DNNCA_ESTATE; }
     std::vector<RegionSpecHost> hs(n);
     for (int i = 0; i < n; ++i) DN_TRY(region_spec_check(specs + i, M->outH, M->outW, hs[i]));
@@ -1509,7 +1518,7 @@ int dnnca_render_composite(void* model, const float* y_hw, int batch, float rati
                            int32_t* out_hwc) {
     MODEL(model);
     if (!out_hwc || capacity < 0 || (out && capacity == 0)) { set_error("bad render arguments"); return DNNCA_EINVAL; }
-    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch out of range"); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
     if (M->outH != M->desc.height || M->outW != M->desc.width) {
         set_error("render: the output (%d x %d) differs from the input (%d x %d)", M->outH, M->outW, M->desc.height, M->desc.width);
         return DNNCA_EINVAL;

@@ -94,9 +94,21 @@ class DeviceView:
         return out
 
 
+def threshold_vector(thresholds):
+    """a scalar, a sequence or None -> the contiguous float32 vector the library takes"""
+    return as_f32(() if thresholds is None else thresholds).ravel()
+
+
+def confusion_rows(n, fill):
+    """[(tp, fp, fn, tn)] per threshold: `fill` has the library write an array of n dnnca_confusion records"""
+    out = (_lib.Confusion * max(n, 1))()
+    fill(out)
+    return [(c.tp, c.fp, c.fn, c.tn) for c in out[:n]]
+
+
 def region_specs(specs):
     """[(thresholds, iou_threshold, resize_factor, morph_filter_size)] -> (dnnca_region_spec array, threshold arrays to keep alive)"""
-    keep = [as_f32(np.atleast_1d(np.asarray(s[0], np.float32))).ravel() for s in specs]
+    keep = [threshold_vector(s[0]) for s in specs]
     arr = (_lib.RegionSpec * max(len(specs), 1))()
     for a, s, thr in zip(arr, specs, keep):
         a.thresholds, a.n_thresholds = fptr(thr), thr.size
@@ -134,18 +146,14 @@ class StagingRing:
         addresses (c_void_p) of a and b.  wait=True blocks the CALLING thread until the copy has completed, so the arrays may be
         reused or freed afterwards; with wait=False the caller keeps them alive and unchanged until the slot's step has run."""
         a = np.ascontiguousarray(a)
+        b = None if b is None else np.ascontiguousarray(b)
         pa, pb = C.c_void_p(), C.c_void_p()
-        if b is None:
-            check(self.dm.lib.dnnca_stage_upload(self.dm.handle, int(slot), a.ctypes.data_as(C.c_void_p), a.nbytes, None, 0,
-                                                 C.byref(pa), C.byref(pb)))
-            pb = None
-        else:
-            b = np.ascontiguousarray(b)
-            check(self.dm.lib.dnnca_stage_upload(self.dm.handle, int(slot), a.ctypes.data_as(C.c_void_p), a.nbytes,
-                                                 b.ctypes.data_as(C.c_void_p), b.nbytes, C.byref(pa), C.byref(pb)))
+        check(self.dm.lib.dnnca_stage_upload(self.dm.handle, int(slot), a.ctypes.data_as(C.c_void_p), a.nbytes,
+                                             None if b is None else b.ctypes.data_as(C.c_void_p), 0 if b is None else b.nbytes,
+                                             C.byref(pa), C.byref(pb)))
         if wait:
             check(self.dm.lib.dnnca_stage_uploaded(self.dm.handle, int(slot)))
-        return pa, pb
+        return pa, (None if b is None else pb)
 
     def wait(self, slot):
         """the model's stream waits for the slot's upload (before kernels other than the train step read it)"""
@@ -157,7 +165,7 @@ class StagingRing:
 
     # keras Model.evaluate (engine.py:198-203) over the ring: the confusion histogram of ALL thresholds stays on the device
     def eval_begin(self, thresholds=()):
-        thr = as_f32(np.asarray(thresholds, np.float32)).ravel()
+        thr = threshold_vector(thresholds)
         self._n_thr = int(thr.size)
         check(self.dm.lib.dnnca_eval_begin(self.dm.handle, thr.ctypes.data_as(C.c_void_p) if thr.size else None, self._n_thr))
 
@@ -166,9 +174,7 @@ class StagingRing:
 
     def eval_end(self):
         """[(tp, fp, fn, tn)] per threshold of eval_begin, summed over every eval_step since (exact integers)"""
-        out = (_lib.Confusion * max(self._n_thr, 1))()
-        check(self.dm.lib.dnnca_eval_end(self.dm.handle, out))
-        return [(c.tp, c.fp, c.fn, c.tn) for c in out[:self._n_thr]]
+        return confusion_rows(self._n_thr, lambda out: check(self.dm.lib.dnnca_eval_end(self.dm.handle, out)))
 
     # region-based metrics of the same evaluation (kernels_region.hip): between eval_begin and the first eval_step
     def eval_region_begin(self, specs):
@@ -187,10 +193,7 @@ class StagingRing:
     def confusion(self, slot):
         """[(tp, fp, fn, tn)] per threshold of DeviceModel.train_metrics for the train step that last ran on the slot (exact
         integers); waits for that step like out(slot) does -- read it before the slot takes its next batch"""
-        n = self.dm._tm_n
-        out = (_lib.Confusion * max(n, 1))()
-        check(self.dm.lib.dnnca_staged_confusion(self.dm.handle, int(slot), out))
-        return [(c.tp, c.fp, c.fn, c.tn) for c in out[:n]]
+        return confusion_rows(self.dm._tm_n, lambda out: check(self.dm.lib.dnnca_staged_confusion(self.dm.handle, int(slot), out)))
 
     def out(self, slot):
         """waits for the step that last ran on the slot; raises what train_step would have raised (label / weight assertions)"""
@@ -386,16 +389,13 @@ class DeviceModel:
     def train_metrics(self, thresholds):
         """every later train step also counts its own probabilities (training=True forward pass, before the update) against its
         raw labels at these thresholds (any order, at most 1024); None or empty switches it off"""
-        thr = as_f32(np.asarray(() if thresholds is None else thresholds, np.float32)).ravel()
+        thr = threshold_vector(thresholds)
         check(self.lib.dnnca_train_metrics(self.handle, fptr(thr) if thr.size else None, int(thr.size)))
         self._tm_n = int(thr.size)
 
     def last_step_confusion(self):
         """[(tp, fp, fn, tn)] per threshold of train_metrics for the last train_step / train_step_dev (exact integers)"""
-        n = self._tm_n
-        out = (_lib.Confusion * max(n, 1))()
-        check(self.lib.dnnca_last_step_confusion(self.handle, out))
-        return [(c.tp, c.fp, c.fn, c.tn) for c in out[:n]]
+        return confusion_rows(self._tm_n, lambda out: check(self.lib.dnnca_last_step_confusion(self.handle, out)))
 
     def last_prob(self, batch):
         """the probability buffer [batch, H, W] (last forward / eval step, or a train step with train_metrics on)"""
@@ -418,21 +418,18 @@ class DeviceModel:
         return self._ring
 
     def pixel_confusion(self, y, thresholds):
-        y = as_f32(y)
-        thr = as_f32(thresholds).ravel()
-        out = (_lib.Confusion * thr.size)()
-        check(self.lib.dnnca_pixel_confusion(self.handle, fptr(y), y.shape[0], fptr(thr), thr.size, out))
-        return [(c.tp, c.fp, c.fn, c.tn) for c in out]
+        y, thr = as_f32(y), threshold_vector(thresholds)
+        return confusion_rows(thr.size, lambda out: check(
+            self.lib.dnnca_pixel_confusion(self.handle, fptr(y), y.shape[0], fptr(thr), thr.size, out)))
 
     def pixel_confusion_of(self, prob, y, thresholds):
         """Metric.update_state(y_true, y_pred) on caller-supplied probabilities: [(tp, fp, fn, tn)] per threshold (exact)."""
         prob, y = as_f32(prob).ravel(), as_f32(y).ravel()
         if prob.size != y.size:
             raise ValueError('prob and y differ in size: %d vs %d' % (prob.size, y.size))
-        thr = as_f32(thresholds).ravel()
-        out = (_lib.Confusion * thr.size)()
-        check(self.lib.dnnca_pixel_confusion_of(self.handle, fptr(prob), fptr(y), prob.size, fptr(thr), thr.size, out))
-        return [(c.tp, c.fp, c.fn, c.tn) for c in out]
+        thr = threshold_vector(thresholds)
+        return confusion_rows(thr.size, lambda out: check(
+            self.lib.dnnca_pixel_confusion_of(self.handle, fptr(prob), fptr(y), prob.size, fptr(thr), thr.size, out)))
 
     def region_confusion(self, y, spec):
         """region counts of the last forward / eval probabilities against y [B, H, W]: int64 [T, 4] (tp_label, fn, tp_pred, fp).
@@ -470,7 +467,7 @@ class DeviceModel:
                 raise ValueError('prob %s and y %s differ in size' % (prob.shape, y.shape))
         pieces = []
         for thr, iou, rf, k in specs:
-            thr = np.atleast_1d(np.asarray(thr, np.float32)).ravel()
+            thr = threshold_vector(thr)
             n = -(-thr.size // 64)
             pieces += [(part, iou, rf, k) for part in np.array_split(thr, n)] if n > 1 else [(thr, iou, rf, k)]
         arr, keep = region_specs(pieces)

@@ -55,6 +55,20 @@ def _csv_value(v):
     return '%.8g' % v
 
 
+def _spread_counts(metric_objs, counts):
+    """a [T, 4] count array over the concatenated thresholds of `metric_objs` -> added onto each metric's own rows"""
+    lo = 0
+    for m in metric_objs:
+        m.counts += counts[lo:lo + len(m.thresholds)]
+        lo += len(m.thresholds)
+
+
+def _log_value(metric):
+    """a pixel metric's result() for a log line: a float, or a list of floats (several thresholds)"""
+    r = metric.result()
+    return float(r) if np.ndim(r) == 0 else [float(v) for v in r]
+
+
 class TFKerasModel:
     """Encapsulates the DNN model and the library behind it (name kept from the reference for drop-in use)."""
 
@@ -171,6 +185,10 @@ class TFKerasModel:
             return x, y
         lo, hi = distributed.shard_bounds(len(x), self.ctx.rank, self.ctx.world, even=False)
         return x[lo:hi], (None if y is None else y[lo:hi])
+
+    def _rank_sum(self, a):
+        """the sum of an array over the ranks (counts travel as doubles: exact integers far beyond 2^24 pixels)"""
+        return np.asarray(self.device_model.comm_allreduce(a.ravel()), np.float64).reshape(a.shape)
 
     def _shard_fn(self, dataset):
         """the split for the elements of `dataset`: none for one rank and for datasets that hand every rank its part already
@@ -394,15 +412,11 @@ class TFKerasModel:
         over ranks first (as doubles: exact integers), as MirroredStrategy's sync-on-read metric variables are"""
         counts = np.asarray(counts if counts is not None else [], np.float64).reshape(-1, 4)
         if self.ctx.world > 1:
-            counts = np.asarray(self.device_model.comm_allreduce(counts.ravel()), np.float64).reshape(-1, 4)
-        logs, lo = OrderedDict(), 0
+            counts = self._rank_sum(counts)
         for m in objs:
             m.reset_state()
-            m.counts += counts[lo:lo + len(m.thresholds)]
-            lo += len(m.thresholds)
-            r = m.result()
-            logs[m.name] = float(r) if np.ndim(r) == 0 else [float(v) for v in r]
-        return logs
+        _spread_counts(objs, counts)
+        return OrderedDict((m.name, _log_value(m)) for m in objs)
 
     # ---- evaluation (engine.py:139-210) ----------------------------------------------------------------------
     def _evaluate(self, dataset, staged=False):
@@ -414,12 +428,19 @@ class TFKerasModel:
             m.reset_state()
         region_groups = region_metrics.group_by_spec(self.region_metrics)
 
-        def region_update(dm_, y_):         # region counts of the step's probabilities: one device run per distinct spec
+        total, count = 0.0, 0
+
+        def step(dm_, xb, yb, cfg):         # one test step: loss, pixel metrics, region counts (one device run per distinct spec)
+            nonlocal total, count
+            out = dm_.eval_step(xb, yb, cfg)
+            total += float(out.loss) * len(xb)
+            count += len(xb)
+            for m in self.metrics:
+                m.update_state(dm_, yb)
             for spec, ms in region_groups:
-                c = dm_.region_confusion(y_, spec)
+                c = dm_.region_confusion(yb, spec)
                 for m in ms:
                     m.add_counts(c)
-        total, count = 0.0, 0
         shard = self._shard_fn(dataset)
         if staged and self._staged_eval_possible():
             total, count, dataset = self._evaluate_staged(dataset, cfg_kw, shard, region_groups)  # what is left: batches the ring could not take
@@ -430,12 +451,7 @@ class TFKerasModel:
                 self._ensure_capacity(len(x))
             dm = self.device_model
             if 0 < len(x) <= dm.max_batch:
-                out = dm.eval_step(x, y, dm.loss_cfg(**cfg_kw))
-                total += float(out.loss) * len(x)
-                count += len(x)
-                for m in self.metrics:
-                    m.update_state(dm, y)
-                region_update(dm, y)
+                step(dm, x, y, dm.loss_cfg(**cfg_kw))
             elif len(x):
                 # HBM cannot hold the batch in one step: chunks, each with the weight of the WHOLE batch passed explicitly
                 kw = dict(cfg_kw)
@@ -446,25 +462,15 @@ class TFKerasModel:
                         rate = float(np.asarray(y, np.float64).mean())
                         kw['weight'] = 1.0 / rate if rate > 0 else 1.0          # utils/losses.py:25-27
                 cfg = dm.loss_cfg(**kw)
-                for i in range(0, len(x), dm.max_batch):
-                    xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
-                    out = dm.eval_step(xb, yb, cfg)
-                    total += float(out.loss) * len(xb)
-                    count += len(xb)
-                    for m in self.metrics:
-                        m.update_state(dm, yb)
-                    region_update(dm, yb)       # region metrics are per slice: chunks give the counts of the whole batch
+                for i in range(0, len(x), dm.max_batch):        # (region metrics are per slice: chunks give the whole batch's counts)
+                    step(dm, x[i:i + dm.max_batch], y[i:i + dm.max_batch], cfg)
         if self.ctx.world > 1:
-            dm = self.device_model
-            total, count = (float(v) for v in dm.comm_allreduce([total, count]))
-            for m in self.metrics:                      # counts travel as doubles: exact far beyond 2^24 pixels
-                m.merge(lambda c: np.asarray(dm.comm_allreduce(c.ravel()), np.float64).reshape(c.shape))
-            for m in self.region_metrics:               # integer counts, exact as doubles
-                m.merge(lambda c: np.asarray(dm.comm_allreduce(c.ravel()), np.float64).reshape(c.shape))
+            total, count = (float(v) for v in self.device_model.comm_allreduce([total, count]))
+            for m in self.metrics + self.region_metrics:
+                m.merge(self._rank_sum)
         results = OrderedDict(loss=total / max(count, 1))
         for m in self.metrics:
-            r = m.result()
-            results[m.name] = float(r) if np.ndim(r) == 0 else [float(v) for v in r]
+            results[m.name] = _log_value(m)
         for m in self.region_metrics:
             results[m.name] = m.result()
         return results
@@ -525,10 +531,7 @@ class TFKerasModel:
             feeder.close()
             region_counts = ring.eval_region_end() if region_on else []
             counts = np.asarray(ring.eval_end(), np.float64).reshape(-1, 4)
-        lo = 0
-        for m in self.metrics:
-            m.counts += counts[lo:lo + len(m.thresholds)]
-            lo += len(m.thresholds)
+        _spread_counts(self.metrics, counts)
         for (_, ms), c in zip(region_groups, region_counts):
             for m in ms:
                 m.add_counts(c)

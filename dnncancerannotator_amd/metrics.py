@@ -1,7 +1,7 @@
 """Pixel metrics on top of device-side confusion counts (utils/metrics.py:19-77 + the Keras metrics named in
 configs/additionals/metrics.yaml:2-23).  TP/FP/FN/TN are counted on the GPU (dnnca_pixel_confusion: prediction > threshold,
-the Keras Precision/Recall convention); region-based metrics (metrics.py:80-510: connected components on the CPU) are
-outside the accelerated path and are skipped with a warning."""
+the Keras Precision/Recall convention).  The region-based metrics (metrics.py:80-510) live in region_metrics.py and are counted
+on the GPU with deploy_options.region_metrics: device; without that key solve_metric skips them with a warning."""
 
 import logging
 
@@ -28,25 +28,28 @@ class _ConfusionMetric:
     def merge(self, reduce_fn):
         self.counts = reduce_fn(self.counts)
 
+    def result(self):
+        """a float for one threshold, an array for several (the Keras metrics' convention); subclasses give values()"""
+        r = self.values()
+        return float(r[0]) if len(r) == 1 else r
+
 
 class Precision(_ConfusionMetric):
     def __init__(self, thresholds=0.5, name='precision', **kw):
         super().__init__(thresholds, name)
 
-    def result(self):
+    def values(self):
         tp, fp = self.counts[:, 0], self.counts[:, 1]
-        r = _div_no_nan(tp, tp + fp)
-        return float(r[0]) if len(r) == 1 else r
+        return _div_no_nan(tp, tp + fp)
 
 
 class Recall(_ConfusionMetric):
     def __init__(self, thresholds=0.5, name='recall', **kw):
         super().__init__(thresholds, name)
 
-    def result(self):
+    def values(self):
         tp, fn = self.counts[:, 0], self.counts[:, 2]
-        r = _div_no_nan(tp, tp + fn)
-        return float(r[0]) if len(r) == 1 else r
+        return _div_no_nan(tp, tp + fn)
 
 
 class FBetaScore(_ConfusionMetric):
@@ -57,11 +60,10 @@ class FBetaScore(_ConfusionMetric):
         super().__init__(thresholds, name)
         self.beta, self.epsilon = beta, epsilon
 
-    def result(self):
+    def values(self):
         tp, fp, fn = self.counts[:, 0], self.counts[:, 1], self.counts[:, 2]
         p, r = _div_no_nan(tp, tp + fp), _div_no_nan(tp, tp + fn)
-        s = (1 + self.beta ** 2) * p * r / (self.beta ** 2 * p + r + self.epsilon)
-        return float(s[0]) if len(s) == 1 else s
+        return (1 + self.beta ** 2) * p * r / (self.beta ** 2 * p + r + self.epsilon)
 
 
 class AUC(_ConfusionMetric):

@@ -1,7 +1,7 @@
 """Test double for the per-step training metrics (deploy_options.train_metrics: device): tests/fake_device.FakeDeviceModel plus
 the DeviceModel methods the engine calls when the option is on.  A train step keeps the sigmoid of its own training=True forward
 pass (the oracle's logits before the update) and counts it against the raw labels, prob > threshold, labels > 0.5, like
-k_train_conf_hist.  Test infrastructure only."""
+k_conf_hist<true>.  Test infrastructure only."""
 
 import numpy as np
 

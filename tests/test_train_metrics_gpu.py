@@ -31,7 +31,7 @@ def _thresholds():
 
 
 def np_counts(prob, y, thr):
-    """(tp, fp, fn, tn) per threshold, prob > thr in float32, labels > 0.5 (k_confusion_hist's rule)"""
+    """(tp, fp, fn, tn) per threshold, prob > thr in float32, labels > 0.5 (k_conf_hist's rule)"""
     p, pos = np.asarray(prob, np.float32).ravel(), np.asarray(y, np.float32).ravel() > 0.5
     pp, pn = np.sort(p[pos]), np.sort(p[~pos])
     thr = np.asarray(thr, np.float32)
