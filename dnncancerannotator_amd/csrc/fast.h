@@ -58,14 +58,76 @@ bool fast_bn_bwd(Model* m, int B, Op& o);
 bool fast_pool_into_bn(Model* m, Op& pool, Op& bn);      // the pool's backward rides in the backward passes of the BatchNorm in front of it
 bool fast_bn_supported(const Model* m, const Op& o);
 void fast_plan_masks(Model* m);
-// Path-selecting switches of the dense kernels (tuning aids / A-B arms), read ONCE per process at their first use: the plan made at
-// model creation (which BatchNorm apply passes are elided, ig_norm_on_load_ok) and every later launch decision must see the same
-// values -- a conv must never read a normalised tensor that was never written.  (The per-model switches DNNCA_NO_HALF* are read when
-// a model is built; the unet.yaml fusion switches are read per call: each of those paths falls back on the launches it replaced.)
+// Switch table of the dense path, read ONCE per process at its first use: the plan made at model creation (which
+// BatchNorm apply passes are elided, which tensors are stored as bf16) and every later launch decision must see the same values -- a
+// conv must never read a normalised tensor that was never written.  Deliberately NOT here, because tests flip them in-process:
+// DNNCA_NO_HALF, _NO_HALF_Z, _NO_HALF_DY (read when a model is built, ig_plan_half) and DNNCA_FOLD_BATCH (read per step, ig_prepare).
+// (The unet.yaml fusion switches are read per call: each of those paths falls back on the launches it replaced.)
 struct DenseSwitches {
-    bool igconv1, wgrad1, no_bn_fusion, no_pool_stats, no_wg_buckets, tcwgrad1;
+    // first-generation kernels (the fallbacks beyond the 32-bit offset limits)
+    bool igconv1, wgrad1, tcwgrad1, tconv_fwd1;
+    // the exact-fp32 MFMA kernels in place of the split-bf16 ones (fallbacks for more than 1024 output channels / oversized planes)
+    bool no_x3, no_x3_wgrad;
+    // weight-gradient slabs: float atomics instead of plain stores, no bucket copies, four-wave bf16 kernel for bf16-stored operands
+    bool no_wg_plain, no_wg_buckets, wgrad64_narrow;
+    // BatchNorm riders
+    bool no_bn_fusion, no_pool_stats, no_norm_on_load, no_bn_bwd_ride, no_pool_bn_bwd;
+    // tuning aids: waves per block (4 | 8; 0: by the eight-wave rule), split-bf16 channel tile cap / resident-block cap / no channel
+    // split of the waves, grid caps of the BatchNorm and pool passes
+    int ig_nw, igb_nw, x3_nn, x3_blocks;
+    bool x3_no_split, x3_no_db;      // ... and no second LDS buffer
+    int bn_blocks, pool_blocks;
 };
 const DenseSwitches& dense_switches();
+
+// ---- the launch a dense layer gets.  Pure functions of the model description, the op, the batch size and the switch table: they touch
+// no device memory and launch nothing.  The planners (ig_plan_half, ig_prepare, ig_norm_on_load_ok) ask them what WILL run; the
+// launchers call the same functions and execute the answer.
+enum DenseKernel {
+    DK_NONE,
+    // 3x3 conv forward / data gradient: split-bf16 persistent (ig3x::k_ig3x_conv3), exact-fp32 persistent (ig::k_ig_conv3),
+    // first-generation fp32 (ig::k_ig_conv), bf16 persistent (igb::k_igb_conv3), first-generation bf16 (igb::k_igb_conv)
+    DK_X3_CONV3, DK_F32_CONV3, DK_F32_CONV, DK_B16_CONV3, DK_B16_CONV,
+    // 3x3 conv weight gradient of one source: split-bf16 (ig3x::k_ig3x_wgrad), second- / first-generation fp32 (ig::k_ig_wgrad2,
+    // k_ig_wgrad), bf16 on 64-channel tiles with eight waves and bf16-stored operands (igb::k_igb_wgrad64w) / with four waves
+    // (k_igb_wgrad64), first-generation bf16 (k_igb_wgrad)
+    DK_X3_WGRAD, DK_F32_WGRAD2, DK_F32_WGRAD, DK_B16_WGRAD64W, DK_B16_WGRAD64, DK_B16_WGRAD,
+    // transposed conv forward (bf16 / fp32, second / first generation), data gradient, weight gradient
+    DK_B16_TCONV2, DK_B16_TCONV, DK_F32_TCONV2, DK_F32_TCONV, DK_B16_TCONV_DGRAD, DK_F32_TCONV_DGRAD,
+    DK_B16_TCONV_WGRAD64, DK_F32_TCONV_WGRAD2, DK_F32_TCONV_WGRAD,
+};
+struct DenseLaunch {
+    DenseKernel kern = DK_NONE;
+    int nn = 0, mw = 0;             // channel tile: 16 nn output channels (N of the GEMM) x 16 mw (weight gradients: M)
+    int nw = 4, wn = 1;             // waves per block; how many of them split the channel tile
+    bool db = false;                // two LDS buffers
+    bool a16 = false, x16 = false, g16 = false;      // bf16-stored conv source / weight-gradient activations / output gradient
+    bool k64 = false;               // 64-channel K chunks (bf16 transposed-conv data gradient)
+    bool plain = false, bucketed = false;            // weight-gradient slabs: one per pixel-split block / WG_BUCKETS shared copies
+    // forward: the batch statistics of the BatchNorm behind it can ride in the epilogue; data gradient: the backward sums of the
+    // BatchNorm in front of it can
+    bool stats = false, bnb = false;
+    int tiles_x = 0, tiles_y = 0, psplit = 0;
+    unsigned units = 0, block = 256;          // units: work items of a persistent kernel (grid.x = min(units, resident blocks))
+    dim3 grid;
+};
+DenseLaunch dense_conv_fwd(const Model* m, int B, const Op& o, const DenseSwitches& sw);
+DenseLaunch dense_conv_dgrad(const Model* m, int B, const Op& o, const DenseSwitches& sw);
+DenseLaunch dense_conv_wgrad(const Model* m, int B, const Op& o, int source, const DenseSwitches& sw);
+DenseLaunch dense_tconv_fwd(const Model* m, int B, const Op& o, const DenseSwitches& sw);
+DenseLaunch dense_tconv_dgrad(const Model* m, int B, const Op& o, const DenseSwitches& sw);
+DenseLaunch dense_tconv_wgrad(const Model* m, int B, const Op& o, const DenseSwitches& sw);
+// the three rules every dense launch shares
+inline bool fits32(double bytes) { return bytes < 2.0e9; }          // the kernel's 32-bit byte offsets reach the whole tensor
+inline int pixel_split(int combos, int ntiles, int blocks = 256) {  // pixel-split blocks per channel-block pair: `blocks` in all
+    const int ps = (blocks + combos - 1) / combos;
+    return ps > ntiles ? (ntiles < 1 ? 1 : ntiles) : ps;
+}
+// eight waves per block on 32 x 16-pixel tiles once that still gives every CU a unit
+inline bool eight_waves(int B, int H, int W, int channel_tiles) {
+    const long units8 = (long)((W + 15) / 16) * ((H + 31) / 32) * B * channel_tiles;
+    return units8 >= 256;
+}
 // implicit-GEMM MFMA path for channel counts that are multiples of 16 (kernels_igemm.hip)
 bool ig_conv_supported(const Model* m, const Op& o);
 int ig_prepare(Model* m);
@@ -76,6 +138,7 @@ void ig_release(Model* m);
 bool ig_conv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_next);   // bn_next: BatchNorm of the output whose statistics may ride in the epilogue
 bool ig_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, double flops);
 // will this conv's forward and weight-gradient launches (batch B) be the kernels that can normalise a BatchNorm's input while staging it?
+// (Model::forward elides the BatchNorm's apply pass on this answer)
 bool ig_norm_on_load_ok(const Model* m, int B, const Op& o);
 struct BnSelfFold;
 struct BnBwdFold;
@@ -88,13 +151,12 @@ namespace ig { struct ConvArgs; struct WgArgs; }
 bool ig3x_enabled(const Model* m);
 int ig3x_prepare(Model* m);
 void ig3x_release(Model* m);
-bool ig3x_accepts(Model* m, const ig::ConvArgs& a, int cout);
-int ig3x_max_bnb_channels();
-// bnb_rode: (data gradient with ConvArgs::bnb filled) did the chosen kernel take the BatchNorm backward sums along?
-bool ig3x_launch(Model* m, int mode, const ig::ConvArgs& a, size_t w_off, int cout, int nn, const char* name, double bytes, double flops,
-                 bool* bnb_rode = nullptr);
-bool ig3x_wgrad_launch(Model* m, ig::WgArgs w, int co, const char* name, double bytes, double flops);
-int ig3x_wgrad_psplit(const Model* m, const ig::WgArgs& w, int co);      // pixel-split blocks of that launch; 0: not this path
+// the split-bf16 part of dense_conv_fwd / _dgrad / _wgrad (pure): fills *d and returns true when these kernels take the launch.
+// mode 0 forward / 1 data gradient; cin: all sources; nn: channel tile of the exact-fp32 kernel; any_half: a bf16-stored tensor takes part
+bool ig3x_conv_decide(const Model* m, const DenseSwitches& sw, int mode, int B, int H, int W, int cin, int cout, int nn, bool any_half, DenseLaunch* d);
+bool ig3x_wgrad_decide(const Model* m, const DenseSwitches& sw, int B, int H, int W, int cs, int co, DenseLaunch* d);
+void ig3x_launch(Model* m, const DenseLaunch& d, int mode, const ig::ConvArgs& a, size_t w_off, const char* name, double bytes, double flops);
+void ig3x_wgrad_launch(Model* m, const DenseLaunch& d, ig::WgArgs w, const char* name, double bytes, double flops);
 bool ig_tconv_supported(const Model* m, const Op& o);
 bool ig_tconv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_next);
 bool ig_tconv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, double flops);   // decides maskA/maskB/premasked for every op (static per model)

@@ -92,7 +92,7 @@ __device__ __forceinline__ void conv3_epilogue(const ConvArgs& p, const f32x4 (&
         if (y >= p.H) continue;                 // wave-uniform
         float v[4][NN];
         bool ok[4];
-        // element offsets in 32 bits (conv3_path checks that every destination has fewer than 2^32 elements): with size_t the address
+        // element offsets in 32 bits (conv_decide checks that every destination has fewer than 2^32 elements): with size_t the address
         // arithmetic of the 16 NN stores was most of the epilogue -- 5.7 k of the 17.8 k ticks a 16-channel unit takes (tools/cv_stamps.py)
         unsigned o[4];
         const unsigned orow = (unsigned)(b * p.H + y) * (unsigned)p.W;

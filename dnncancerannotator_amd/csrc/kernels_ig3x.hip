@@ -894,11 +894,10 @@ static std::map<Model*, Ig3xPlan> g_ig3x;
 
 void ig3x_release(Model* m) { g_ig3x.erase(m); }
 
-// fp32 models only; DNNCA_NO_X3=1 keeps the exact-fp32 MFMA kernels (read once per process)
-bool ig3x_enabled(const Model* m) {
-    static const bool off = getenv("DNNCA_NO_X3") != nullptr;
-    return !off && m->desc.dtype == DNNCA_F32 && !(m->desc.flags & 1);
-}
+// fp32 models only; DNNCA_NO_X3=1 keeps the exact-fp32 MFMA kernels
+bool ig3x_enabled(const Model* m) { return !dense_switches().no_x3 && m->desc.dtype == DNNCA_F32 && !(m->desc.flags & 1); }
+// elements between two of the three bf16 planes of the weights
+static unsigned ig3x_pstride(const Model* m) { return (unsigned)((m->nT + 15) / 16 * 16); }
 
 int ig3x_prepare(Model* m) {
     if (!ig3x_enabled(m)) return DNNCA_OK;
@@ -913,7 +912,7 @@ int ig3x_prepare(Model* m) {
             if (n > pl.max_w) pl.max_w = n;
         }
         if (!pl.preps.empty()) {
-            pl.pstride = (unsigned)((m->nT + 15) / 16 * 16);
+            pl.pstride = ig3x_pstride(m);
             DN_TRY(m->alloc((void**)&pl.preps_dev, pl.preps.size() * sizeof(ig3x::PrepDesc)));
             DN_TRY(m->alloc((void**)&pl.wf, (size_t)pl.pstride * 3 * 2 + 64));
             DN_TRY(m->alloc((void**)&pl.wd, (size_t)pl.pstride * 3 * 2 + 64));
@@ -931,47 +930,42 @@ int ig3x_prepare(Model* m) {
     return DNNCA_OK;
 }
 
-// launches the conv (mode 0 forward / 1 data gradient) described by `a` (tiles_x / tiles_y are set here) on the split-bf16 kernel with
-// channel tiles of 16 nn; false: not this path (the caller goes on to the exact-fp32 kernels).
+// Does the split-bf16 kernel take this conv (mode 0 forward / 1 data gradient), and in which layout?  (fast.h; pure)
 // Wave layout: eight waves on 32 x 16-pixel tiles while that gives every CU a unit; else (nn >= 2) eight waves on 16 x 16 tiles, split
 // 4 row groups x 2 channel halves; else four waves on 16 x 16 tiles.  DNNCA_IG_NW=4|8 forces the first / last (tuning aid, tests).
-// would ig3x_launch take this conv?  (ig_conv_bwd asks before it hands the BatchNorm backward sums to the launch: ConvArgs::bnb)
-bool ig3x_accepts(Model* m, const ig::ConvArgs& a, int cout) {
+bool ig3x_conv_decide(const Model* m, const DenseSwitches& sw, int mode, int B, int H, int W, int cin, int cout, int nn, bool any_half, DenseLaunch* d) {
     if (!ig3x_enabled(m)) return false;
-    Ig3xPlan& pl = g_ig3x[m];
-    if (!m->dry && (!pl.wf || !pl.wd)) return false;
-    if (a.src_half || a.dst_half || a.dsth[0] || a.dsth[1] || cout > ig3x::kMaxBias) return false;          // bf16-stored tensors: dtype bf16 only
-    if (9.0 * cout * (a.c_src0 + a.c_src1) + 2.0 * pl.pstride > 1.0e9) return false;          // 32-bit byte offsets into the planes
-    return true;
-}
-int ig3x_max_bnb_channels() { return ig3x::kMaxBias / 2; }          // mean and 1 / sigma share the bias table
-
-bool ig3x_launch(Model* m, int mode, const ig::ConvArgs& a, size_t w_off, int cout, int nn, const char* name, double bytes, double flops,
-                 bool* bnb_rode) {
-    if (bnb_rode) *bnb_rode = false;
-    if (!ig3x_accepts(m, a, cout)) return false;
-    Ig3xPlan& pl = g_ig3x[m];
-    static const int forced = getenv("DNNCA_IG_NW") ? atoi(getenv("DNNCA_IG_NW")) : 0;
-    static const bool no_split = getenv("DNNCA_X3_NO_SPLIT") != nullptr;          // tuning aid
-    static const bool no_db = getenv("DNNCA_X3_NO_DB") != nullptr;                // tuning aid / A-B arm
-    const long units8 = (long)((a.W + 15) / 16) * ((a.H + 31) / 32) * a.B * (cout / (16 * nn));
+    if (any_half || cout > ig3x::kMaxBias) return false;          // bf16-stored tensors: dtype bf16 only
+    if (9.0 * cout * cin + 2.0 * ig3x_pstride(m) > 1.0e9) return false;          // 32-bit byte offsets into the planes
+    const int forced = sw.ig_nw;
     int nw = 8, wn = 1;
     if (forced == 4) nw = 4;
-    else if (forced != 8 && units8 < 256) {
-        if (nn >= 2 && !no_split) wn = 2;
+    else if (forced != 8 && !eight_waves(B, H, W, cout / (16 * nn))) {
+        if (nn >= 2 && !sw.x3_no_split) wn = 2;
         else nw = 4;
     }
     // two LDS buffers where they fit: 16-channel tiles on 32 x 16 pixels, 32-channel tiles on the split 16 x 16 layout
-    if (nn == 2 && nw == 8 && !no_db && !no_split && forced != 8) wn = 2;
-    const bool db = !no_db && nw == 8 && ((nn == 1 && wn == 1) || (nn == 2 && wn == 2));
+    if (nn == 2 && nw == 8 && !sw.x3_no_db && !sw.x3_no_split && forced != 8) wn = 2;
+    d->kern = DK_X3_CONV3;
+    d->nn = nn; d->nw = nw; d->wn = wn;
+    d->db = !sw.x3_no_db && nw == 8 && ((nn == 1 && wn == 1) || (nn == 2 && wn == 2));
+    // mean and 1 / sigma of the BatchNorm backward sums share the bias table; the <4, 2, 8> layout has no instance with the sums
+    d->bnb = mode == 1 && cout <= ig3x::kMaxBias / 2 && !(nn == 4 && nw == 8 && wn == 1);
     const int rows = 4 * (nw / wn);
-    ig::ConvArgs a2 = a;
-    a2.tiles_x = (a.W + ig3x::T - 1) / ig3x::T;
-    a2.tiles_y = (a.H + rows - 1) / rows;
-    const unsigned units = (unsigned)(a2.tiles_x * a2.tiles_y * a2.B * (cout / (16 * nn)));
+    d->tiles_x = (W + ig3x::T - 1) / ig3x::T;
+    d->tiles_y = (H + rows - 1) / rows;
+    d->units = (unsigned)(d->tiles_x * d->tiles_y * B * (cout / (16 * nn)));
+    d->grid = dim3(d->units);          // (ig3x_launch clamps it to the resident blocks: that query needs the device)
+    d->block = 64 * nw;
+    return true;
+}
+
+// executes a DK_X3_CONV3 decision for the conv described by `a` (tiles already set from the decision)
+void ig3x_launch(Model* m, const DenseLaunch& d, int mode, const ig::ConvArgs& a, size_t w_off, const char* name, double bytes, double flops) {
+    Ig3xPlan& pl = g_ig3x[m];
     typedef void (*Kern)(ig::ConvArgs, const ig3x::bf16_t*, unsigned);
     // [mode: forward, data gradient, data gradient + BatchNorm backward sums][nn index][layout: 4 waves, 8 waves, 8 waves split]
-    // (no <4, 2, 8>: that layout has no registers left for the sums -- such launches leave them to the BatchNorm's reduction pass)
+    // (no <4, 2, 8>: that layout has no registers left for the sums -- ig3x_conv_decide leaves them to the BatchNorm's reduction pass)
     static const Kern kerns[3][3][3] = {
         {{ig3x::k_ig3x_conv3<1, 0, 4>, ig3x::k_ig3x_conv3<1, 0, 8>, nullptr},
          {ig3x::k_ig3x_conv3<2, 0, 4>, ig3x::k_ig3x_conv3<2, 0, 8>, ig3x::k_ig3x_conv3<2, 0, 8, 2>},
@@ -982,80 +976,62 @@ bool ig3x_launch(Model* m, int mode, const ig::ConvArgs& a, size_t w_off, int co
         {{ig3x::k_ig3x_conv3<1, 2, 4>, ig3x::k_ig3x_conv3<1, 2, 8>, nullptr},
          {ig3x::k_ig3x_conv3<2, 2, 4>, ig3x::k_ig3x_conv3<2, 2, 8>, ig3x::k_ig3x_conv3<2, 2, 8, 2>},
          {ig3x::k_ig3x_conv3<4, 2, 4>, nullptr, ig3x::k_ig3x_conv3<4, 2, 8, 2>}}};
-    const int ni = nn == 4 ? 2 : (nn == 2 ? 1 : 0), li = wn == 2 ? 2 : (nw == 8 ? 1 : 0);
+    // two LDS buffers (DenseLaunch::db): [mode][nn index]
     static const Kern kerns_db[3][2] = {{ig3x::k_ig3x_conv3<1, 0, 8, 1, true>, ig3x::k_ig3x_conv3<2, 0, 8, 2, true>},
                                         {ig3x::k_ig3x_conv3<1, 1, 8, 1, true>, ig3x::k_ig3x_conv3<2, 1, 8, 2, true>},
                                         {ig3x::k_ig3x_conv3<1, 2, 8, 1, true>, ig3x::k_ig3x_conv3<2, 2, 8, 2, true>}};
-    int mi = mode ? 1 : 0;
-    if (mode == 1 && a.bnb.C > 0 && (db ? kerns_db[2][ni] : kerns[2][ni][li]) != nullptr) mi = 2;
-    if (bnb_rode) *bnb_rode = mi == 2;
-    const Kern kern = db ? kerns_db[mi][ni] : kerns[mi][ni][li];
+    const int ni = d.nn == 4 ? 2 : (d.nn == 2 ? 1 : 0), li = d.wn == 2 ? 2 : (d.nw == 8 ? 1 : 0);
+    const int mi = mode == 1 && a.bnb.C > 0 ? 2 : mode;          // (the caller fills ConvArgs::bnb only where DenseLaunch::bnb allows)
+    const Kern kern = d.db ? kerns_db[mi][ni] : kerns[mi][ni][li];
     // a persistent kernel's grid is the number of blocks that are resident at once: several per CU where LDS and registers allow
     // (a block alternates between committing an item and running its MFMAs; co-resident blocks fill each other's commit phases)
     static int occ[3][3][4] = {};
-    int& oc = occ[mi][ni][db ? 3 : li];
+    int& oc = occ[mi][ni][d.db ? 3 : li];
     if (oc == 0) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), 64 * nw, 0) != hipSuccess || nb < 1) nb = 1;
-        static const int cap = getenv("DNNCA_X3_BLOCKS") ? atoi(getenv("DNNCA_X3_BLOCKS")) : 0;          // tuning aid
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), d.block, 0) != hipSuccess || nb < 1) nb = 1;
+        const int cap = dense_switches().x3_blocks;          // tuning aid
         if (cap > 0 && nb > cap) nb = cap;
         oc = nb;
     }
     const unsigned resident = 256u * (unsigned)oc;
-    const unsigned g = units < resident ? units : resident;
+    const unsigned g = d.units < resident ? d.units : resident;
     const ig3x::bf16_t* w3 = (mode == 0 ? pl.wf : pl.wd) + w_off;
-    m->set_variant("x3n%dw%d%s%s%s", nn, nw, wn == 2 ? "s" : "", db ? "d" : "", mi == 2 ? "b" : "");      // b: BatchNorm backward sums ride
-    LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL(kern, dim3(g), dim3(64 * nw), 0, m->stream, a2, w3, pl.pstride));
+    m->set_variant("x3n%dw%d%s%s%s", d.nn, d.nw, d.wn == 2 ? "s" : "", d.db ? "d" : "", mi == 2 ? "b" : "");      // b: BatchNorm backward sums ride
+    LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL(kern, dim3(g), dim3(d.block), 0, m->stream, a, w3, pl.pstride));
+}
+
+// the split-bf16 weight-gradient kernel's shape for one source: channel tiles, wave roles (nj = nn / wn channel tiles per wave,
+// wk = 8 / mw / wn waves along K), pixel-split blocks; false: not this path
+bool ig3x_wgrad_decide(const Model* m, const DenseSwitches& sw, int B, int H, int W, int cs, int co, DenseLaunch* d) {
+    if (!ig3x_enabled(m) || sw.no_x3_wgrad) return false;
+    d->kern = DK_X3_WGRAD;
+    d->mw = cs % 64 == 0 ? 4 : (cs % 32 == 0 ? 2 : 1);
+    d->nn = co % 64 == 0 ? 4 : (co % 32 == 0 ? 2 : 1);
+    d->nw = 8;
+    d->wn = (d->nn >= 2 && 8 / d->mw >= 2) ? 2 : 1;
+    const int cit = 16 * d->mw, cot = 16 * d->nn;
+    const int tyw = 8 * ig3x::wg_tm(cit, cot);
+    d->tiles_x = (W + ig3x::T - 1) / ig3x::T;
+    d->tiles_y = (H + tyw - 1) / tyw;
+    d->psplit = pixel_split((cs / cit) * (co / cot), d->tiles_x * d->tiles_y * B);
+    d->grid = dim3(d->psplit, cs / cit, co / cot);
+    d->block = 512;
     return true;
 }
 
-// the split-bf16 weight-gradient kernel's shape for one source: channel tiles, wave roles, pixel-split blocks; false: not this path
-struct Wg3Shape { int mw, nn, wn, nj, wk, tyw, ps; };
-static bool wg3_shape(const Model* m, const ig::WgArgs& w, int co, Wg3Shape* sh) {
-    if (!ig3x_enabled(m)) return false;
-    static const bool off = getenv("DNNCA_NO_X3_WGRAD") != nullptr;
-    if (off) return false;
-    const int cs = w.cs;
-    if (cs % 16 || co % 16) return false;
-    if ((double)w.B * w.H * w.W * (cs > co ? cs : co) * 4.0 >= 2.0e9) return false;          // 32-bit byte offsets
-    sh->mw = cs % 64 == 0 ? 4 : (cs % 32 == 0 ? 2 : 1);
-    sh->nn = co % 64 == 0 ? 4 : (co % 32 == 0 ? 2 : 1);
-    const int rest = 8 / sh->mw;
-    sh->wn = (sh->nn >= 2 && rest >= 2) ? 2 : 1;
-    sh->nj = sh->nn / sh->wn;
-    sh->wk = rest / sh->wn;
-    const int cit = 16 * sh->mw, cot = 16 * sh->nn;
-    sh->tyw = 8 * ig3x::wg_tm(cit, cot);
-    const int nt = ((w.W + ig3x::T - 1) / ig3x::T) * ((w.H + sh->tyw - 1) / sh->tyw) * w.B;
-    const int combos = (cs / cit) * (co / cot);
-    int ps = (256 + combos - 1) / combos;
-    if (ps > nt) ps = nt;
-    sh->ps = ps < 1 ? 1 : ps;
-    return true;
-}
-
-// pixel-split blocks (= slabs in plain mode) of the launch ig3x_wgrad_launch would make; 0: not this path
-int ig3x_wgrad_psplit(const Model* m, const ig::WgArgs& w, int co) {
-    Wg3Shape sh;
-    return wg3_shape(m, w, co, &sh) ? sh.ps : 0;
-}
-
-// weight gradient of one source on the split-bf16 kernel; w: geometry and pointers filled by the caller (psplit is set here).
-// false: not this path.
-bool ig3x_wgrad_launch(Model* m, ig::WgArgs w, int co, const char* name, double bytes, double flops) {
-    Wg3Shape sh;
-    if (!wg3_shape(m, w, co, &sh)) return false;
-    const int mw = sh.mw, nn = sh.nn, cit = 16 * mw, cot = 16 * nn;
-    w.tiles_x = (w.W + ig3x::T - 1) / ig3x::T;
-    w.psplit = sh.ps;
-    const dim3 g(w.psplit, w.cs / cit, co / cot);
-    m->set_variant("x3m%dj%dn%dk%d%s", mw, sh.nj, sh.wn, sh.wk, w.plain ? "p" : "");
-#define WG3(MWv, NJv, WNv, WKv) LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL((ig3x::k_ig3x_wgrad<MWv, NJv, WNv, WKv>), g, dim3(512), 0, m->stream, w))
-    if (mw == 4) { if (nn == 4) WG3(4, 2, 2, 1); else if (nn == 2) WG3(4, 1, 2, 1); else WG3(4, 1, 1, 2); }
-    else if (mw == 2) { if (nn == 4) WG3(2, 2, 2, 2); else if (nn == 2) WG3(2, 1, 2, 2); else WG3(2, 1, 1, 4); }
-    else { if (nn == 4) WG3(1, 2, 2, 4); else if (nn == 2) WG3(1, 1, 2, 4); else WG3(1, 1, 1, 8); }
-#undef WG3
-    return true;
+// executes a DK_X3_WGRAD decision; w: geometry and pointers filled by the caller
+void ig3x_wgrad_launch(Model* m, const DenseLaunch& d, ig::WgArgs w, const char* name, double bytes, double flops) {
+    w.tiles_x = d.tiles_x;
+    w.psplit = d.psplit;
+    typedef void (*Kern)(ig::WgArgs);
+    // [mw = 4, 2, 1][nn = 4, 2, 1]: <MW, NJ, WN, WK>
+    static const Kern kerns[3][3] = {
+        {ig3x::k_ig3x_wgrad<4, 2, 2, 1>, ig3x::k_ig3x_wgrad<4, 1, 2, 1>, ig3x::k_ig3x_wgrad<4, 1, 1, 2>},
+        {ig3x::k_ig3x_wgrad<2, 2, 2, 2>, ig3x::k_ig3x_wgrad<2, 1, 2, 2>, ig3x::k_ig3x_wgrad<2, 1, 1, 4>},
+        {ig3x::k_ig3x_wgrad<1, 2, 2, 4>, ig3x::k_ig3x_wgrad<1, 1, 2, 4>, ig3x::k_ig3x_wgrad<1, 1, 1, 8>}};
+    m->set_variant("x3m%dj%dn%dk%d%s", d.mw, d.nn / d.wn, d.wn, 8 / d.mw / d.wn, w.plain ? "p" : "");
+    LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL(kerns[2 - d.mw / 2][2 - d.nn / 2], d.grid, dim3(d.block), 0, m->stream, w));
 }
 
 }  // namespace dnnca

@@ -8,6 +8,7 @@
 // 288 (NN = 4) MFMAs per wave between two barriers; the decoder concat is two sources, never materialised; bias +
 // activation (forward) or act' mask + accumulate + destination split (data gradient) are fused into the store.
 // The data gradient is the forward kernel on a transposed + flipped copy of the weights (k_ig_flip, once per step).
+#include <climits>
 #include <cstring>
 #include <type_traits>
 
@@ -2668,9 +2669,7 @@ __global__ __launch_bounds__(256, 1) void k_igb_tconv_wgrad64(TcArgs p) {
 // ================================================================================================ host side
 struct IgPlan {
     bool built = false;
-    std::vector<ig::FlipDesc> flips;          // eager ones first (n_eager), then the convs the split-bf16 kernels cover (flipped only on demand)
-    int n_eager = 0;
-    std::map<size_t, int> flip_index;         // w_off -> index in flips
+    std::vector<ig::FlipDesc> flips;          // the convs whose data gradient runs on the exact-fp32 kernels
     ig::FlipDesc* flips_dev = nullptr;
     float* flipped = nullptr;        // same layout / offsets as the parameter vector (only conv kernels are filled)
     int max_w = 0;
@@ -2713,18 +2712,26 @@ static float* wg_plain_slabs(Model* m, const Op& o, int s, size_t floats) {
     pl.plain[key] = std::make_pair(ptr, floats);
     return ptr;
 }
-static bool wg_plain_on() {
-    static const bool off = getenv("DNNCA_NO_WG_PLAIN") != nullptr;          // keep the float atomics (A/B)
-    return !off;
-}
 // DNNCA_FOLD_BATCH=1: one fold launch per backward pass instead of one per weight-gradient launch -- unless this step sends gradient
 // buckets while the backward pass runs (they need each layer's gradient final as soon as its launches are)
 static bool wg_fold_batched(Model* m) { return g_ig[m].fold_batch && !m->bucketing; }
 
+// the one place that reads the dense path's environment (fast.h; DESIGN section 8 lists every name)
 const DenseSwitches& dense_switches() {
-    static const DenseSwitches sw = {getenv("DNNCA_IGCONV1") != nullptr, getenv("DNNCA_WGRAD1") != nullptr, getenv("DNNCA_NO_BN_FUSION") != nullptr,
-                                     getenv("DNNCA_NO_POOL_STATS") != nullptr, getenv("DNNCA_NO_WG_BUCKETS") != nullptr,
-                                     getenv("DNNCA_TCWGRAD1") != nullptr};
+    static const DenseSwitches sw = [] {
+        auto on = [](const char* name) { return getenv(name) != nullptr; };
+        auto num = [](const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; };
+        DenseSwitches t{};
+        t.igconv1 = on("DNNCA_IGCONV1"); t.wgrad1 = on("DNNCA_WGRAD1"); t.tcwgrad1 = on("DNNCA_TCWGRAD1"); t.tconv_fwd1 = on("DNNCA_TCONV_FWD1");
+        t.no_x3 = on("DNNCA_NO_X3"); t.no_x3_wgrad = on("DNNCA_NO_X3_WGRAD");
+        t.no_wg_plain = on("DNNCA_NO_WG_PLAIN"); t.no_wg_buckets = on("DNNCA_NO_WG_BUCKETS"); t.wgrad64_narrow = on("DNNCA_WGRAD64_NARROW");
+        t.no_bn_fusion = on("DNNCA_NO_BN_FUSION"); t.no_pool_stats = on("DNNCA_NO_POOL_STATS"); t.no_norm_on_load = on("DNNCA_NO_NORM_ON_LOAD");
+        t.no_bn_bwd_ride = on("DNNCA_NO_BN_BWD_RIDE"); t.no_pool_bn_bwd = on("DNNCA_NO_POOL_BN_BWD");
+        t.ig_nw = num("DNNCA_IG_NW", 0); t.igb_nw = num("DNNCA_IGB_NW", 0);
+        t.x3_nn = num("DNNCA_X3_NN", 4); t.x3_blocks = num("DNNCA_X3_BLOCKS", 0); t.x3_no_split = on("DNNCA_X3_NO_SPLIT"); t.x3_no_db = on("DNNCA_X3_NO_DB");
+        t.bn_blocks = num("DNNCA_BN_BLOCKS", 512); t.pool_blocks = num("DNNCA_POOL_BLOCKS", 1024);
+        return t;
+    }();
     return sw;
 }
 
@@ -2749,20 +2756,204 @@ static bool use_bf16_tc(const Model* m, const Op& o) {
     return m->desc.dtype == DNNCA_BF16 && o.inA.d.C % 64 == 0 && o.out.d.C % 64 == 0;
 }
 
+// ---------------------------------------------------------------------------------------------- launch decisions (fast.h)
+// Geometry of a 3x3 conv launch as the kernels see it: the forward pass reads the op's sources and writes its output, the data
+// gradient reads the output gradient (one source of CO channels) and writes one gradient per source (cout = CA + CB).
+struct ConvGeom { int mode, B, H, W, c_src0, c_src1, n_dst0, n_dst1, cout; bool src_half, any_half; };
+
+static DenseLaunch conv_decide(const Model* m, const Op& o, const ConvGeom& g, const DenseSwitches& sw) {
+    DenseLaunch d;
+    const bool bf16 = use_bf16(m, o);
+    // the persistent kernels address their sources with 32-bit byte offsets (bit 31 marks "outside the image"), their epilogues use
+    // 32-bit element offsets
+    const int cmax = g.c_src0 > g.c_src1 ? g.c_src0 : g.c_src1, dmax = g.n_dst0 > g.n_dst1 ? g.n_dst0 : g.n_dst1;
+    const bool fits = fits32((double)g.B * g.H * g.W * cmax * 4.0) && fits32(9.0 * g.cout * (g.c_src0 + g.c_src1) * 4.0) &&
+                      (double)g.B * g.H * g.W * dmax < 4.0e9;
+    const bool persistent = bf16 ? fits && g.cout % 64 == 0 && g.c_src0 % 32 == 0 && g.c_src1 % 32 == 0 && g.n_dst0 % 64 == 0 : fits && !sw.igconv1;
+    d.a16 = g.src_half;
+    if (!persistent) {          // first generation: one block per 8 x 16-pixel tile and channel tile
+        d.kern = bf16 ? DK_B16_CONV : DK_F32_CONV;
+        d.nn = pick_nn(g.cout);
+        d.tiles_x = (g.W + ig::TX - 1) / ig::TX;
+        d.tiles_y = (g.H + ig::TY - 1) / ig::TY;
+        d.grid = dim3(d.tiles_x * d.tiles_y * g.B, g.cout / (16 * d.nn));
+        return d;
+    }
+    d.stats = g.mode == 0 && !sw.no_bn_fusion;
+    if (bf16) {          // 64-channel tiles; eight waves (32 x 16-pixel tiles, two waves per SIMD) by the eight-wave rule
+        d.kern = DK_B16_CONV3;
+        d.nn = 4;
+        d.nw = (sw.igb_nw == 4 || sw.igb_nw == 8) ? sw.igb_nw : (eight_waves(g.B, g.H, g.W, g.cout / 64) ? 8 : 4);
+    } else {             // channel tile 16 nn must divide both destinations
+        const int d1 = g.n_dst1 ? g.n_dst1 : 64;
+        d.nn = (g.n_dst0 % 64 == 0 && d1 % 64 == 0) ? 4 : ((g.n_dst0 % 32 == 0 && d1 % 32 == 0) ? 2 : 1);
+        // fp32 by three bf16 planes on the bf16 matrix pipe (kernels_ig3x.hip), unless switched off.  DNNCA_X3_NN: channel tile at most 16 x this
+        const int nnx = d.nn > sw.x3_nn && (sw.x3_nn == 1 || sw.x3_nn == 2) ? sw.x3_nn : d.nn;
+        if (ig3x_conv_decide(m, sw, g.mode, g.B, g.H, g.W, g.c_src0 + g.c_src1, g.cout, nnx, g.any_half, &d)) return d;
+        d.kern = DK_F32_CONV3;          // eight waves for 16- / 32-channel tiles with enough units
+        d.nw = (d.nn == 4 || sw.ig_nw == 4) ? 4 : ((sw.ig_nw == 8 || eight_waves(g.B, g.H, g.W, g.cout / (16 * d.nn))) ? 8 : 4);
+    }
+    d.tiles_x = bf16 ? (g.W + igb::T2 - 1) / igb::T2 : (g.W + ig::F3T - 1) / ig::F3T;          // 4 rows per wave
+    d.tiles_y = (g.H + 4 * d.nw - 1) / (4 * d.nw);
+    d.units = (unsigned)(d.tiles_x * d.tiles_y * g.B * (g.cout / (16 * d.nn)));
+    d.grid = dim3(d.units < 256u ? d.units : 256u);
+    d.block = 64 * d.nw;
+    return d;
+}
+
+DenseLaunch dense_conv_fwd(const Model* m, int B, const Op& o, const DenseSwitches& sw) {
+    // (ig_plan_half keeps both sources of a conv in the same format)
+    const ConvGeom g{0, B, o.out.d.H, o.out.d.W, o.inA.d.C, o.inB.d.C, o.out.d.C, 0, o.out.d.C, o.inA.d.h != 0, o.inA.d.h || o.out.d.h};
+    return conv_decide(m, o, g, sw);
+}
+
+DenseLaunch dense_conv_dgrad(const Model* m, int B, const Op& o, const DenseSwitches& sw) {
+    const int CA = o.inA.d.C, CB = o.inB.d.C;
+    const ConvGeom g{1, B, o.out.d.H, o.out.d.W, o.out.d.C, 0, CA, CB, CA + CB, o.out.g.h != 0, o.out.g.h || o.inA.g.h || o.inB.g.h};
+    DenseLaunch d = conv_decide(m, o, g, sw);
+    // this launch writes ALL of the gradient arriving at the BatchNorm that feeds the conv (its only reader, nothing accumulated, no act'
+    // mask): the BatchNorm's backward sums can ride in the epilogue (ConvArgs::bnb; split-bf16 kernel, f32 tensors)
+    if (d.bnb) {
+        const Op* bn = !sw.no_bn_bwd_ride && CB == 0 && o.src_bn[0] >= 0 && !o.accA && !o.maskA ? &m->ops[o.src_bn[0]] : nullptr;
+        d.bnb = bn && bn->out_readers.size() == 1 && bn->out_readers[0] == (int)(&o - m->ops.data()) && bn->out.g.p == o.inA.g.p && bn->out.g.C == CA;
+    }
+    return d;
+}
+
+// kernel family of the weight gradient of source s (everything but the slab mode, which looks at both sources: dense_conv_wgrad)
+static DenseLaunch wgrad_decide(const Model* m, int B, const Op& o, int s, const DenseSwitches& sw) {
+    DenseLaunch d;
+    const int cs = s ? o.inB.d.C : o.inA.d.C, CO = o.out.d.C, H = o.out.d.H, W = o.out.d.W;
+    const bool bf16 = use_bf16(m, o);
+    const double reach = (double)B * H * W * (cs > CO ? cs : CO);          // elements the 32-bit byte offsets must reach
+    d.nn = pick_nn(CO);
+    d.tiles_x = (W + ig::TX - 1) / ig::TX;
+    d.tiles_y = (H + ig::TY - 1) / ig::TY;
+    const int ntiles = d.tiles_x * d.tiles_y * B;
+    if (bf16 && CO % 64 == 0 && cs % 64 == 0) {
+        d.x16 = (s ? o.inB.d.h : o.inA.d.h) != 0;
+        d.g16 = o.out.g.h != 0;
+        d.mw = 4;
+        d.psplit = pixel_split((cs / 64) * (CO / 64), ntiles);
+        d.grid = dim3(d.psplit, cs / 64, CO / 64);
+        // eight waves per block: bf16-stored operands, 32-bit byte offsets
+        d.kern = d.x16 && d.g16 && !sw.wgrad64_narrow && fits32(reach * 2.0) ? DK_B16_WGRAD64W : DK_B16_WGRAD64;
+        d.nw = d.kern == DK_B16_WGRAD64W ? 8 : 4;
+    } else if (!bf16 && fits32(reach * 4.0) && !sw.wgrad1) {
+        // fp32 by three bf16 planes on the bf16 matrix pipe (kernels_ig3x.hip), unless switched off
+        if (ig3x_wgrad_decide(m, sw, B, H, W, cs, CO, &d)) return d;
+        d.kern = DK_F32_WGRAD2;
+        d.mw = cs % 64 == 0 ? 4 : (cs % 32 == 0 ? 2 : 1);
+        d.nw = d.nn == 4 ? 4 : 8;
+        const int tm = (4 / d.mw) < (4 / d.nn) ? (4 / d.mw) : (4 / d.nn);
+        const int nt2 = d.tiles_x * ((H + 8 * tm - 1) / (8 * tm)) * B;
+        d.psplit = pixel_split((cs / (16 * d.mw)) * (CO / (16 * d.nn)), nt2);
+        d.grid = dim3(d.psplit, cs / (16 * d.mw), CO / (16 * d.nn));
+    } else {
+        d.kern = bf16 ? DK_B16_WGRAD : DK_F32_WGRAD;
+        d.mw = 1;
+        d.psplit = pixel_split((cs / ig::CK) * (CO / (16 * d.nn)), ntiles, 1024);
+        d.grid = dim3(d.psplit, cs / ig::CK, CO / (16 * d.nn));
+    }
+    d.block = 64 * d.nw;
+    return d;
+}
+
+DenseLaunch dense_conv_wgrad(const Model* m, int B, const Op& o, int s, const DenseSwitches& sw) {
+    DenseLaunch d = wgrad_decide(m, B, o, s, sw);
+    const int CA = o.inA.d.C, CB = o.inB.d.C, CO = o.out.d.C;
+    // Small gradients shared by many blocks go through bucket copies (WgArgs::nbuckets): fp32 second-generation kernel, both sources;
+    // the split-bf16 kernel in plain mode needs none (every block stores into its own slab).  The block count is that of k_ig_wgrad2
+    // for the first source, before the clamp to the number of pixel tiles.
+    auto fp32_2nd = [&](int k) {
+        const DenseKernel f = k == s ? d.kern : wgrad_decide(m, B, o, k, sw).kern;
+        return f == DK_F32_WGRAD2 || (f == DK_X3_WGRAD && sw.no_wg_plain);
+    };
+    const int mwA = CA % 64 == 0 ? 4 : (CA % 32 == 0 ? 2 : 1), nn = pick_nn(CO);
+    d.bucketed = !sw.no_wg_buckets && fp32_2nd(0) && (!CB || fp32_2nd(1)) && 9 * (CA + CB) * CO + CO <= WG_SLAB_FLOATS &&
+                 pixel_split((CA / (16 * mwA)) * (CO / (16 * nn)), INT_MAX) > 32;
+    d.plain = (d.kern == DK_X3_WGRAD || d.kern == DK_B16_WGRAD64W) && !sw.no_wg_plain && !d.bucketed;
+    return d;
+}
+
+// transposed 2x2 / stride-2 convs: npix input pixels, 128 per block
+DenseLaunch dense_tconv_fwd(const Model* m, int B, const Op& o, const DenseSwitches& sw) {
+    DenseLaunch d;
+    const int cin = o.inA.d.C, cout = o.out.d.C, npix = B * o.inA.d.H * o.inA.d.W;
+    const bool reach = fits32((double)npix * 4.0 * cout);
+    d.a16 = o.inA.d.h != 0;
+    if (use_bf16_tc(m, o)) {
+        d.kern = !sw.tconv_fwd1 && o.out.d.h && reach ? DK_B16_TCONV2 : DK_B16_TCONV;
+        d.nn = 4;
+        d.stats = !sw.no_bn_fusion;
+        d.grid = dim3((npix + 127) / 128, cout / 64);
+        d.block = d.kern == DK_B16_TCONV2 ? 512 : 256;
+        return d;
+    }
+    d.nn = pick_nn(cout);
+    d.kern = !sw.tconv_fwd1 && !o.inA.d.h && !o.out.d.h && cin % ig::CK == 0 && reach ? DK_F32_TCONV2 : DK_F32_TCONV;
+    d.stats = d.kern == DK_F32_TCONV2 && !sw.no_bn_fusion;
+    d.grid = dim3((npix + 127) / 128, cout / (16 * d.nn), d.kern == DK_F32_TCONV2 ? 1 : 4);
+    return d;
+}
+
+DenseLaunch dense_tconv_dgrad(const Model* m, int B, const Op& o, const DenseSwitches& sw) {
+    DenseLaunch d;
+    const int cin = o.inA.d.C, npix = B * o.inA.d.H * o.inA.d.W;
+    const bool bf16 = use_bf16_tc(m, o);          // (then cout % 64 == 0: a bf16-stored gradient is always read in 64-channel chunks)
+    d.kern = bf16 ? DK_B16_TCONV_DGRAD : DK_F32_TCONV_DGRAD;
+    d.nn = bf16 ? 4 : pick_nn(cin);
+    d.g16 = d.k64 = bf16 && o.out.g.h != 0;
+    d.grid = dim3((npix + 127) / 128, cin / (16 * d.nn));
+    return d;
+}
+
+DenseLaunch dense_tconv_wgrad(const Model* m, int B, const Op& o, const DenseSwitches& sw) {
+    DenseLaunch d;
+    const int cin = o.inA.d.C, cout = o.out.d.C, npix = B * o.inA.d.H * o.inA.d.W;
+    if (use_bf16_tc(m, o)) {
+        d.kern = DK_B16_TCONV_WGRAD64;
+        d.mw = d.nn = 4;
+        d.x16 = o.inA.d.h != 0;
+        d.g16 = o.out.g.h != 0;
+        d.psplit = pixel_split((cout / 64) * (cin / 64), (npix + 127) / 128);
+        d.grid = dim3(d.psplit, cout / 64, cin / 64);
+    } else if (fits32((double)npix * 4.0 * cout * 4.0) && fits32((double)npix * cin * 4.0) && !sw.tcwgrad1) {
+        // second generation: (16 mw x 16 nn) channel tiles x 4 parities, 32-bit byte offsets
+        d.kern = DK_F32_TCONV_WGRAD2;
+        d.mw = cout % 64 == 0 ? 4 : (cout % 32 == 0 ? 2 : 1);
+        d.nn = pick_nn(cin);
+        const int tm = (4 / d.mw) < (4 / d.nn) ? (4 / d.mw) : (4 / d.nn);
+        d.psplit = pixel_split((cout / (16 * d.mw)) * (cin / (16 * d.nn)), (npix + 64 * tm - 1) / (64 * tm));
+        d.grid = dim3(d.psplit, cout / (16 * d.mw), cin / (16 * d.nn));
+    } else {
+        d.kern = DK_F32_TCONV_WGRAD;
+        d.mw = 1;
+        d.nn = pick_nn(cin);
+        d.psplit = pixel_split((cout / 16) * 4 * (cin / (16 * d.nn)), (npix + 127) / 128, 1024);
+        d.grid = dim3(d.psplit, cout / 16, 4 * (cin / (16 * d.nn)));
+    }
+    return d;
+}
+
+// forward, data gradient and weight gradients of this conv all take the 64-channel bf16 kernels that read and write bf16-stored
+// tensors (asked at max_batch; the conditions only relax with a smaller batch)
+static bool conv_takes_half(const Model* m, const Op& c) {
+    if (!ig_conv_supported(m, c)) return false;
+    const DenseSwitches& sw = dense_switches();
+    const int B = m->desc.max_batch;
+    auto wg64 = [&](int s) { const DenseKernel k = dense_conv_wgrad(m, B, c, s, sw).kern; return k == DK_B16_WGRAD64 || k == DK_B16_WGRAD64W; };
+    return dense_conv_fwd(m, B, c, sw).kern == DK_B16_CONV3 && dense_conv_dgrad(m, B, c, sw).kern == DK_B16_CONV3 && wg64(0) &&
+           (!c.inB.d.C || wg64(1));
+}
+static bool tconv_takes_half(const Model* m, const Op& c) { return ig_tconv_supported(m, c) && use_bf16_tc(m, c); }
+
 // Which tensors are stored as bf16 (View::h)?  Under dtype bf16 the 64-channel conv / transposed-conv kernels round their
 // operands to bf16 while staging them, so a tensor whose every reader is one of those kernels can live in HBM as bf16 with
 // bit-identical results: the outputs of BatchNorm layers that feed only such kernels (and the fused max-pool, which records
 // the positions of its maxima for the backward pass), and the conv-output gradients the BatchNorm backward hands to them.
 int ig_plan_half(Model* m) {
     if (m->desc.dtype != DNNCA_BF16 || (m->desc.flags & 1) || getenv("DNNCA_NO_HALF")) return DNNCA_OK;
-    const double MB = m->desc.max_batch;
-    auto conv_ok = [&](const Op& c) {     // forward, data gradient and weight gradient all take the 64-channel bf16 kernels
-        if (!ig_conv_supported(m, c) || !use_bf16(m, c)) return false;
-        const int CA = c.inA.d.C, CB = c.inB.d.C, CO = c.out.d.C;
-        if (CA % 64 || CB % 64 || CO % 64) return false;
-        const int cmax = CA > CB ? (CA > CO ? CA : CO) : (CB > CO ? CB : CO);
-        return MB * c.out.d.H * c.out.d.W * cmax * 4.0 < 2.0e9 && 9.0 * CO * (CA + CB) * 4.0 < 2.0e9;      // conv3_path()
-    };
     std::map<float*, bool> hd, hg;
     for (const Op& bn : m->ops) {
         if (bn.type != OP_BN || !fast_bn_supported(m, bn) || !dense(bn.out.d) || !dense(bn.inA.g)) continue;
@@ -2772,8 +2963,8 @@ int ig_plan_half(Model* m) {
             const bool a = c.inA.d.C && c.inA.d.p == bn.out.d.p, b = c.type == OP_CONV && c.inB.d.C && c.inB.d.p == bn.out.d.p;
             if (!a && !b) continue;
             ++users;
-            if (c.type == OP_CONV) ok = ok && conv_ok(c);
-            else if (c.type == OP_TCONV) ok = ok && ig_tconv_supported(m, c) && use_bf16_tc(m, c);
+            if (c.type == OP_CONV) ok = ok && conv_takes_half(m, c);
+            else if (c.type == OP_TCONV) ok = ok && tconv_takes_half(m, c);
             else if (c.type == OP_POOL) ok = ok && fast_bn_pool_fusable(m, bn, c) && dense(c.inA.g) && dense(c.out.g) && !c.maskA;
             else ok = false;
         }
@@ -2803,7 +2994,7 @@ int ig_plan_half(Model* m) {
             }
             const bool pre = prod && (prod->type != OP_CONV || prod->alpha < 0.f || prod->premasked);     // no g_act_bwd pass reads z in f32
             if (readers == 1 && pre &&
-                ((prod->type == OP_CONV && conv_ok(*prod)) || (prod->type == OP_TCONV && ig_tconv_supported(m, *prod) && use_bf16_tc(m, *prod))))
+                ((prod->type == OP_CONV && conv_takes_half(m, *prod)) || (prod->type == OP_TCONV && tconv_takes_half(m, *prod))))
                 hd[bn.inA.d.p] = true;
         }
         // the gradient this BN's backward writes: read only by the backward of the op that produced the BN's input
@@ -2811,7 +3002,7 @@ int ig_plan_half(Model* m) {
         for (const Op& c : m->ops) {
             if (c.out.d.p != bn.inA.d.p || !c.out.d.C) continue;
             const bool pre = c.type != OP_CONV || c.alpha < 0.f || c.premasked;      // nobody rewrites it in f32 (g_act_bwd)
-            if ((c.type == OP_CONV && conv_ok(c) && c.need_din && pre) || (c.type == OP_TCONV && ig_tconv_supported(m, c) && use_bf16_tc(m, c)))
+            if ((c.type == OP_CONV && conv_takes_half(m, c) && c.need_din && pre) || (c.type == OP_TCONV && tconv_takes_half(m, c)))
                 hg[bn.inA.g.p] = true;
         }
     }
@@ -2840,34 +3031,20 @@ int ig_plan_half(Model* m) {
     return DNNCA_OK;
 }
 
-static bool conv3_path(const ig::ConvArgs& a, int cout, bool bf16);
-
 int ig_prepare(Model* m) {
     if (m->desc.flags & 1) return DNNCA_OK;
     IgPlan& pl = g_ig[m];
     if (!pl.built) {
         pl.built = true;
-        // the data-gradient kernels of the fp32 MFMA path read flipped / transposed weights (k_ig_flip, once per backward pass); the
-        // split-bf16 kernels have their own planes (ig3x_prepare), so convs they will take (the same static conditions ig3x_launch checks,
-        // at max_batch) are only flipped on demand (launch_ig, should the split-bf16 launch ever decline)
-        for (int pass = 0; pass < 2; ++pass) {
-            for (const Op& o : m->ops) {
-                if (!ig_conv_supported(m, o) || !o.need_din || use_bf16(m, o)) continue;
-                const int cin = o.inA.d.C + o.inB.d.C, cout = o.out.d.C;
-                ig::ConvArgs gd{};
-                gd.c_src0 = cout; gd.n_dst0 = o.inA.d.C; gd.n_dst1 = o.inB.d.C;
-                gd.B = m->desc.max_batch; gd.H = o.out.d.H; gd.W = o.out.d.W;
-                const bool covered = ig3x_enabled(m) && conv3_path(gd, cin, false) && cin <= 1024 && 9.0 * cin * cout + 2.0 * (m->nT + 16) <= 1.0e9;
-                if (covered != (pass == 1)) continue;
-                ig::FlipDesc d{(int)o.w_off, cin, cout};
-                pl.flip_index[o.w_off] = (int)pl.flips.size();
-                pl.flips.push_back(d);
-                if (pass == 0) {
-                    ++pl.n_eager;
-                    int n = 9 * d.cin * d.cout;
-                    if (n > pl.max_w) pl.max_w = n;
-                }
-            }
+        // the data-gradient kernels of the exact-fp32 MFMA path read flipped / transposed weights (k_ig_flip, once per backward pass); the
+        // split-bf16 kernels have their own planes (ig3x_prepare).  A conv they take at max_batch they take at every batch size (the
+        // limits of dense_conv_dgrad only relax), so it is never flipped
+        for (const Op& o : m->ops) {
+            if (!ig_conv_supported(m, o) || !o.need_din || use_bf16(m, o)) continue;
+            if (dense_conv_dgrad(m, m->desc.max_batch, o, dense_switches()).kern == DK_X3_CONV3) continue;
+            const int cin = o.inA.d.C + o.inB.d.C, cout = o.out.d.C;
+            pl.flips.push_back(ig::FlipDesc{(int)o.w_off, cin, cout});
+            if (9 * cin * cout > pl.max_w) pl.max_w = 9 * cin * cout;
         }
         for (const Op& o : m->ops) {
             if (!ig_conv_supported(m, o) || !use_bf16(m, o)) continue;
@@ -2915,134 +3092,76 @@ int ig_begin_backward(Model* m) {
     for (Op& o : m->ops) o.bwd_sums_rode = false;          // (a pass that stopped on an error may have left one set)
     if (m->desc.flags & 1) return DNNCA_OK;
     IgPlan& pl = g_ig[m];
-    if (pl.n_eager == 0) return DNNCA_OK;
+    if (pl.flips.empty()) return DNNCA_OK;
     int bx = (pl.max_w + 255) / 256;
     if (bx > 1024) bx = 1024;
     LAUNCH(m, "ig_flip", 8.0 * m->nT, 0,
-           hipLaunchKernelGGL(ig::k_ig_flip, dim3(bx, (unsigned)pl.n_eager), dim3(256), 0, m->stream, pl.flips_dev, m->p, pl.flipped));
+           hipLaunchKernelGGL(ig::k_ig_flip, dim3(bx, (unsigned)pl.flips.size()), dim3(256), 0, m->stream, pl.flips_dev, m->p, pl.flipped));
     return DNNCA_OK;
 }
 
-// will launch_ig / launch_igb take the persistent kernel (k_ig_conv3 / k_igb_conv3) for these arguments?
-static bool conv3_path(const ig::ConvArgs& a, int cout, bool bf16) {
-    // the persistent kernels address their sources with 32-bit byte offsets (bit 31 marks "outside the image")
-    const int cmax = a.c_src0 > a.c_src1 ? a.c_src0 : a.c_src1;
-    const int dmax = a.n_dst0 > a.n_dst1 ? a.n_dst0 : a.n_dst1;          // (the epilogue's 32-bit element offsets)
-    const bool fits = (double)a.B * a.H * a.W * cmax * 4.0 < 2.0e9 && 9.0 * cout * (a.c_src0 + a.c_src1) * 4.0 < 2.0e9 &&
-                      (double)a.B * a.H * a.W * dmax < 4.0e9;
-    if (bf16) return fits && cout % 64 == 0 && a.c_src0 % 32 == 0 && a.c_src1 % 32 == 0 && a.n_dst0 % 64 == 0;
-    return fits && !dense_switches().igconv1;
-}
-// waves per block of igb::k_igb_conv3: 8 (32 x 16-pixel tiles, two waves per SIMD) once that still gives every CU a unit
-static int igb_waves(const ig::ConvArgs& a, int cout) {
-    static const int forced = getenv("DNNCA_IGB_NW") ? atoi(getenv("DNNCA_IGB_NW")) : 0;      // tuning aid: 4 or 8
-    if (forced == 4 || forced == 8) return forced;
-    const long units8 = (long)((a.W + 15) / 16) * ((a.H + 31) / 32) * a.B * (cout / 64);
-    return units8 >= 256 ? 8 : 4;
-}
-// waves per block of ig::k_ig_conv3 (f32): 8 for 16- / 32-channel tiles (the channel tile launch_ig picks) with enough units
-static int ig_nn3(const ig::ConvArgs& a) {
-    const int d1 = a.n_dst1 ? a.n_dst1 : 64;
-    return (a.n_dst0 % 64 == 0 && d1 % 64 == 0) ? 4 : ((a.n_dst0 % 32 == 0 && d1 % 32 == 0) ? 2 : 1);
-}
-static int ig_waves(const ig::ConvArgs& a, int cout) {
-    static const int forced = getenv("DNNCA_IG_NW") ? atoi(getenv("DNNCA_IG_NW")) : 0;        // tuning aid: 4 or 8
-    const int nn3 = ig_nn3(a);
-    if (nn3 == 4 || forced == 4) return 4;
-    const long units8 = (long)((a.W + 15) / 16) * ((a.H + 31) / 32) * a.B * (cout / (16 * nn3));
-    return (forced == 8 || units8 >= 256) ? 8 : 4;
-}
+// ---------------------------------------------------------------------------------------------- launchers: execute a decision
+typedef void (*ConvKern)(ig::ConvArgs);
+typedef void (*ConvKernB)(ig::ConvArgs, const igb::bf16_t*);
+typedef void (*WgKern)(ig::WgArgs);
+typedef void (*TcKern)(ig::TcArgs);
+typedef void (*TcKernB)(ig::TcArgs, const igb::bf16_t*);
+// instance tables are indexed by the channel tile: nn or mw = 1, 2, 4 -> 0, 1, 2
+static inline int ti(int n) { return n / 2; }
 
+// a 3x3 conv, MODE 0 forward / 1 data gradient, as `d` says; `a` holds the pointers and the geometry but not the tiles
 template <int MODE>
-static void launch_ig(Model* m, const ig::ConvArgs& a, size_t w_off, int cout, const char* name, double bytes, double flops, bool* bnb_rode = nullptr) {
-    if (bnb_rode) *bnb_rode = false;
-    {   // pipelined persistent kernel: channel tile 16 nn3 must divide both destinations; 32-bit byte offsets
-        const int nn3 = ig_nn3(a);
-        if (conv3_path(a, cout, false)) {
-            static const int x3_nn_cap = getenv("DNNCA_X3_NN") ? atoi(getenv("DNNCA_X3_NN")) : 4;          // tuning aid: channel tile at most 16 x this
-            const int nnx = nn3 > x3_nn_cap && (x3_nn_cap == 1 || x3_nn_cap == 2) ? x3_nn_cap : nn3;
-            // fp32 by three bf16 planes on the bf16 matrix pipe (kernels_ig3x.hip), unless switched off
-            if (ig3x_launch(m, MODE, a, w_off, cout, nnx, MODE == 0 ? "ig3x_conv_fwd" : "ig3x_conv_dgrad", bytes, flops, bnb_rode))
-                return;
-            if (MODE == 1) {          // declined although the plan expected it: this conv's flipped weights were not made at ig_begin_backward
-                IgPlan& plz = g_ig[m];
-                auto it = plz.flip_index.find(w_off);
-                if (it != plz.flip_index.end() && it->second >= plz.n_eager) {
-                    const ig::FlipDesc& fd = plz.flips[it->second];
-                    int bx = (9 * fd.cin * fd.cout + 255) / 256;
-                    if (bx > 1024) bx = 1024;
-                    LAUNCH(m, "ig_flip", 8.0 * 9 * fd.cin * fd.cout, 0,
-                           hipLaunchKernelGGL(ig::k_ig_flip, dim3(bx, 1), dim3(256), 0, m->stream, plz.flips_dev + it->second, m->p, plz.flipped));
-                }
-            }
-            ig::ConvArgs a2 = a;
-            const int nw = ig_waves(a, cout);
-            a2.tiles_x = (a.W + ig::F3T - 1) / ig::F3T;
-            a2.tiles_y = (a.H + 4 * nw - 1) / (4 * nw);
-            const unsigned units = (unsigned)(a2.tiles_x * a2.tiles_y * a2.B * (cout / (16 * nn3)));
-            const unsigned g = units < 256u ? units : 256u;
-            m->set_variant("3n%dw%d", nn3, nn3 == 4 ? 4 : nw);
-            if (nn3 == 4) LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL((ig::k_ig_conv3<4, MODE, 4>), dim3(g), dim3(256), 0, m->stream, a2));
-            else if (nn3 == 2 && nw == 8) LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL((ig::k_ig_conv3<2, MODE, 8>), dim3(g), dim3(512), 0, m->stream, a2));
-            else if (nn3 == 2) LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL((ig::k_ig_conv3<2, MODE, 4>), dim3(g), dim3(256), 0, m->stream, a2));
-            else if (nw == 8) LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL((ig::k_ig_conv3<1, MODE, 8>), dim3(g), dim3(512), 0, m->stream, a2));
-            else LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL((ig::k_ig_conv3<1, MODE, 4>), dim3(g), dim3(256), 0, m->stream, a2));
-            return;
-        }
+static void launch_conv(Model* m, const DenseLaunch& d, ig::ConvArgs a, size_t w_off, double bytes, double flops) {
+    a.tiles_x = d.tiles_x;
+    a.tiles_y = d.tiles_y;
+    const char* name = MODE == 0 ? "ig_conv_fwd" : "ig_conv_dgrad";
+    const char* bname = MODE == 0 ? "igb_conv_fwd" : "igb_conv_dgrad";
+    const int w8 = d.nw == 8;
+    const igb::bf16_t* w16 = (MODE == 0 ? g_ig[m].wf : g_ig[m].wd) + w_off;          // (bf16 kernels)
+    switch (d.kern) {
+    case DK_X3_CONV3:
+        ig3x_launch(m, d, MODE, a, w_off, MODE == 0 ? "ig3x_conv_fwd" : "ig3x_conv_dgrad", bytes, flops);
+        break;
+    case DK_F32_CONV3: {          // (64-channel tiles run on four waves only)
+        static const ConvKern k[3][2] = {{ig::k_ig_conv3<1, MODE, 4>, ig::k_ig_conv3<1, MODE, 8>},
+                                         {ig::k_ig_conv3<2, MODE, 4>, ig::k_ig_conv3<2, MODE, 8>},
+                                         {ig::k_ig_conv3<4, MODE, 4>, nullptr}};
+        m->set_variant("3n%dw%d", d.nn, d.nw);
+        LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL(k[ti(d.nn)][w8], d.grid, dim3(d.block), 0, m->stream, a));
+        break;
     }
-    const int nn = pick_nn(cout);
-    dim3 grid(a.tiles_x * a.tiles_y * a.B, cout / (16 * nn));
-    m->set_variant("n%d", nn);
-    if (nn == 4) LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL((ig::k_ig_conv<4, MODE>), grid, dim3(256), 0, m->stream, a));
-    else if (nn == 2) LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL((ig::k_ig_conv<2, MODE>), grid, dim3(256), 0, m->stream, a));
-    else LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL((ig::k_ig_conv<1, MODE>), grid, dim3(256), 0, m->stream, a));
-}
-
-template <int MODE>
-static void launch_igb(Model* m, const ig::ConvArgs& a, const igb::bf16_t* w16, int cout, const char* name, double bytes,
-                       double flops) {
-    const int nn = pick_nn(cout);
-    if (conv3_path(a, cout, true)) {
-        ig::ConvArgs a2 = a;
-        const int nw = igb_waves(a, cout);
-        a2.tiles_x = (a.W + igb::T2 - 1) / igb::T2;
-        a2.tiles_y = (a.H + 4 * nw - 1) / (4 * nw);
-        const unsigned nblocks = (unsigned)(a2.tiles_x * a2.tiles_y * a2.B * (cout / 64));
-        const unsigned g = nblocks < 256u ? nblocks : 256u;
+    case DK_F32_CONV: {
+        static const ConvKern k[3] = {ig::k_ig_conv<1, MODE>, ig::k_ig_conv<2, MODE>, ig::k_ig_conv<4, MODE>};
+        m->set_variant("n%d", d.nn);
+        LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL(k[ti(d.nn)], d.grid, dim3(d.block), 0, m->stream, a));
+        break;
+    }
+    case DK_B16_CONV3: {
         // the launch name carries the variant (waves per block, bf16-stored source) so that tests and profiles can tell
         // which instantiation ran: igb_conv_fwd_w8 / _w4 [+ _a16]
+        static const ConvKernB k[2][2] = {{igb::k_igb_conv3<MODE, false, 4>, igb::k_igb_conv3<MODE, false, 8>},
+                                          {igb::k_igb_conv3<MODE, true, 4>, igb::k_igb_conv3<MODE, true, 8>}};
         char vname[64];
-        snprintf(vname, sizeof(vname), "%s_w%d%s", name, nw, a.src_half ? "_a16" : "");
-#define IGB3(A16v, NWv) LAUNCH(m, vname, bytes, flops, hipLaunchKernelGGL((igb::k_igb_conv3<MODE, A16v, NWv>), dim3(g), dim3(64 * NWv), 0, m->stream, a2, w16))
-        if (a.src_half) { if (nw == 8) IGB3(true, 8); else IGB3(true, 4); }
-        else { if (nw == 8) IGB3(false, 8); else IGB3(false, 4); }
-#undef IGB3
-        return;
+        snprintf(vname, sizeof(vname), "%s_w%d%s", bname, d.nw, d.a16 ? "_a16" : "");
+        LAUNCH(m, vname, bytes, flops, hipLaunchKernelGGL(k[d.a16][w8], d.grid, dim3(d.block), 0, m->stream, a, w16));
+        break;
     }
-    dim3 grid(a.tiles_x * a.tiles_y * a.B, cout / (16 * nn));
-    m->set_variant("n%d", nn);
-    if (nn == 4) LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL((igb::k_igb_conv<4, MODE>), grid, dim3(256), 0, m->stream, a, w16));
-    else LAUNCH(m, name, bytes, flops, hipLaunchKernelGGL((igb::k_igb_conv<2, MODE>), grid, dim3(256), 0, m->stream, a, w16));
-}
-
-// the launch condition of k_ig_wgrad2 (second-generation fp32 weight gradient) for a source of cs channels
-static bool wgrad2_ok(const Model* m, const Op& o, int B, int cs) {
-    const int CO = o.out.d.C;
-    return !use_bf16(m, o) && (double)B * o.out.d.H * o.out.d.W * (cs > CO ? cs : CO) * 4.0 < 2.0e9 && !dense_switches().wgrad1;
-}
-
-static ig::ConvArgs conv_fwd_geometry(int B, const Op& o) {
-    ig::ConvArgs a{};
-    a.c_src0 = o.inA.d.C; a.c_src1 = o.inB.d.C;
-    a.n_dst0 = o.out.d.C; a.n_dst1 = 0;
-    a.B = B; a.H = o.out.d.H; a.W = o.out.d.W;
-    return a;
+    case DK_B16_CONV: {          // (bf16 needs 32-channel multiples: use_bf16)
+        static const ConvKernB k[3] = {nullptr, igb::k_igb_conv<2, MODE>, igb::k_igb_conv<4, MODE>};
+        m->set_variant("n%d", d.nn);
+        LAUNCH(m, bname, bytes, flops, hipLaunchKernelGGL(k[ti(d.nn)], d.grid, dim3(d.block), 0, m->stream, a, w16));
+        break;
+    }
+    default: break;
+    }
 }
 
 bool ig_norm_on_load_ok(const Model* m, int B, const Op& o) {
-    static const bool off = getenv("DNNCA_NO_NORM_ON_LOAD") != nullptr;
-    if (off || m->desc.dtype != DNNCA_F32 || !ig_conv_supported(m, o) || use_bf16(m, o)) return false;
-    return conv3_path(conv_fwd_geometry(B, o), o.out.d.C, false) && wgrad2_ok(m, o, B, o.inA.d.C) && (!o.inB.d.C || wgrad2_ok(m, o, B, o.inB.d.C));
+    const DenseSwitches& sw = dense_switches();
+    if (sw.no_norm_on_load || m->desc.dtype != DNNCA_F32 || !ig_conv_supported(m, o) || use_bf16(m, o)) return false;
+    auto stages = [&](int s) { const DenseKernel k = dense_conv_wgrad(m, B, o, s, sw).kern; return k == DK_X3_WGRAD || k == DK_F32_WGRAD2; };
+    const DenseKernel f = dense_conv_fwd(m, B, o, sw).kern;
+    return (f == DK_X3_CONV3 || f == DK_F32_CONV3) && stages(0) && (!o.inB.d.C || stages(1));
 }
 
 // source k of conv o for the kernels that normalise on load: the BatchNorm's input + coefficient table when its apply pass was elided
@@ -3059,6 +3178,9 @@ static const float* conv_source(Model* m, const Op& o, int k, const float** norm
 
 bool ig_conv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_next) {
     if (!ig_conv_supported(m, o)) return false;
+    // (a bf16-stored source always meets DK_B16_CONV3 here: ig_plan_half asked this function at max_batch, and its limits only relax
+    // with a smaller batch)
+    const DenseLaunch d = dense_conv_fwd(m, B, o, dense_switches());
     ig::ConvArgs a{};
     a.src[0] = conv_source(m, o, 0, &a.norm[0]);
     a.src[1] = o.inB.d.C ? conv_source(m, o, 1, &a.norm[1]) : o.inB.d.p;
@@ -3067,210 +3189,134 @@ bool ig_conv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_next
     a.bias = m->p + o.b_off;
     a.dst[0] = o.out.d.p; a.n_dst0 = o.out.d.C; a.n_dst1 = 0;
     a.B = B; a.H = o.out.d.H; a.W = o.out.d.W;
-    a.tiles_x = (a.W + ig::TX - 1) / ig::TX;
-    a.tiles_y = (a.H + ig::TY - 1) / ig::TY;
     a.alpha = o.alpha;
     a.src_half = o.inA.d.h;          // ig_plan_half keeps both sources of a conv in the same format
     a.dst_half = o.out.d.h;
-    if (bn_next && !dense_switches().no_bn_fusion && conv3_path(a, o.out.d.C, use_bf16(m, o))) {
-        // the BatchNorm behind this conv takes its batch statistics (and coefficients) from the conv's epilogue
-        (void)bn_self_fold_args(m, *bn_next, B, &a.bnf);
-    }
-    if (a.src_half && !(use_bf16(m, o) && conv3_path(a, o.out.d.C, true))) return false;      // cannot happen (ig_plan_half); the caller reports it
-    if (use_bf16(m, o)) {
-        IgPlan& pl = g_ig[m];
-        launch_igb<0>(m, a, pl.wf + o.w_off, o.out.d.C, "igb_conv_fwd", bytes, flops);
-        return true;
-    }
-    launch_ig<0>(m, a, o.w_off, o.out.d.C, "ig_conv_fwd", bytes, flops);
+    // the BatchNorm behind this conv takes its batch statistics (and coefficients) from the conv's epilogue
+    if (bn_next && d.stats) (void)bn_self_fold_args(m, *bn_next, B, &a.bnf);
+    launch_conv<0>(m, d, a, o.w_off, bytes, flops);
     return true;
+}
+
+// folds the ps slabs of a plain-mode weight-gradient launch (source s of conv o) into the gradient -- now, or with the others of this
+// backward pass (ig_finish_wgrad)
+static void fold_plain(Model* m, const Op& o, int s, float* slabs, int ps, int pstride) {
+    IgPlan& pl = g_ig[m];
+    const int CA = o.inA.d.C, CO = o.out.d.C, cs = s == 0 ? CA : o.inB.d.C, n_ws = 9 * cs * CO, n_b = s == 0 ? CO : 0;
+    const ig::FoldSeg f{slabs, m->g + o.w_off, m->g + o.b_off, ps, pstride, cs, CO, CA + o.inB.d.C, s == 0 ? 0 : CA, n_b, n_ws + n_b < 32768};
+    if (wg_fold_batched(m)) {
+        pl.fold_pending.push_back(f);
+        pl.fold_bytes += 4.0 * ps * (n_ws + n_b);
+        return;
+    }
+    const auto kern = !f.g16 ? ig::k_wg_fold_plain<1> : ig::k_wg_fold_plain<16>;
+    const int per = f.g16 ? 64 : 1024;          // gradient elements per block
+    LAUNCH(m, "wg_fold", 4.0 * ps * (n_ws + n_b), 0, hipLaunchKernelGGL(kern, dim3((n_ws + n_b + per - 1) / per), dim3(256), 0, m->stream, f));
+}
+
+// weight (+ bias, with source 0) gradient of source s.  bucketed: the launches of this conv add into the WG_BUCKETS shared slabs
+static void conv_wgrad(Model* m, int B, const Op& o, int s, bool bucketed, double bytes, double flops) {
+    IgPlan& pl = g_ig[m];
+    const DenseLaunch d = dense_conv_wgrad(m, B, o, s, dense_switches());
+    const int CA = o.inA.d.C, CB = o.inB.d.C, CO = o.out.d.C, n_w = 9 * (CA + CB) * CO;
+    ig::WgArgs w{};
+    w.x = conv_source(m, o, s, &w.norm);
+    w.dz = o.out.g.p;
+    w.dw = bucketed ? pl.wg_slabs : m->g + o.w_off;
+    w.dbias = s == 0 ? (bucketed ? pl.wg_slabs + n_w : m->g + o.b_off) : nullptr;
+    w.nbuckets = bucketed ? WG_BUCKETS : 1; w.bucket_stride = WG_SLAB_FLOATS;
+    w.cs = s == 0 ? CA : CB; w.ci_off = s == 0 ? 0 : CA; w.cin_total = CA + CB; w.cout = CO;
+    w.B = B; w.H = o.out.d.H; w.W = o.out.d.W;
+    w.tiles_x = d.tiles_x; w.tiles_y = d.tiles_y;
+    w.psplit = d.psplit;
+    // plain mode (WgArgs::plain): every pixel-split block stores into a slab of its own instead of adding into the gradient.  (Should
+    // the slabs not be had, the launch keeps the float atomics.)
+    const int n_ws = 9 * w.cs * CO, pstride = (n_ws + CO + 3) / 4 * 4;
+    float* slabs = d.plain && !m->dry ? wg_plain_slabs(m, o, s, (size_t)d.psplit * pstride) : nullptr;
+    const bool plain = d.plain && (m->dry || slabs);
+    if (plain) {
+        w.plain = 1; w.nbuckets = 1; w.bucket_stride = pstride;
+        w.dw = slabs; w.dbias = s == 0 ? slabs + n_ws : nullptr;
+        w.cin_total = w.cs; w.ci_off = 0;
+    }
+    switch (d.kern) {
+    case DK_B16_WGRAD64W:
+        m->set_variant(plain ? "w8p" : "w8");
+        LAUNCH(m, "igb_wgrad64", bytes, flops, hipLaunchKernelGGL(igb::k_igb_wgrad64w<2>, d.grid, dim3(d.block), 0, m->stream, w));
+        break;
+    case DK_B16_WGRAD64: {
+        static const WgKern k[2][2] = {{igb::k_igb_wgrad64<false, false>, igb::k_igb_wgrad64<false, true>},
+                                       {igb::k_igb_wgrad64<true, false>, igb::k_igb_wgrad64<true, true>}};
+        m->set_variant("x%dg%d", (int)d.x16, (int)d.g16);
+        LAUNCH(m, "igb_wgrad64", bytes, flops, hipLaunchKernelGGL(k[d.x16][d.g16], d.grid, dim3(d.block), 0, m->stream, w));
+        break;
+    }
+    case DK_X3_WGRAD:
+        ig3x_wgrad_launch(m, d, w, "ig3x_wgrad", bytes, flops);
+        break;
+    case DK_F32_WGRAD2: {          // eight waves except on 64-channel output tiles
+        static const WgKern k[3][3] = {{ig::k_ig_wgrad2<1, 1, 8>, ig::k_ig_wgrad2<1, 2, 8>, ig::k_ig_wgrad2<1, 4, 4>},
+                                       {ig::k_ig_wgrad2<2, 1, 8>, ig::k_ig_wgrad2<2, 2, 8>, ig::k_ig_wgrad2<2, 4, 4>},
+                                       {ig::k_ig_wgrad2<4, 1, 8>, ig::k_ig_wgrad2<4, 2, 8>, ig::k_ig_wgrad2<4, 4, 4>}};
+        m->set_variant("m%dn%dw%d", d.mw, d.nn, d.nw);
+        LAUNCH(m, "ig_wgrad2", bytes, flops, hipLaunchKernelGGL(k[ti(d.mw)][ti(d.nn)], d.grid, dim3(d.block), 0, m->stream, w));
+        break;
+    }
+    default: {          // first generation, bf16 (32-channel multiples: use_bf16) / fp32
+        static const WgKern k[2][3] = {{nullptr, igb::k_igb_wgrad<2>, igb::k_igb_wgrad<4>}, {ig::k_ig_wgrad<1>, ig::k_ig_wgrad<2>, ig::k_ig_wgrad<4>}};
+        const bool f32 = d.kern == DK_F32_WGRAD;
+        m->set_variant("n%d", d.nn);
+        LAUNCH(m, f32 ? "ig_wgrad" : "igb_wgrad", bytes, flops, hipLaunchKernelGGL(k[f32][ti(d.nn)], d.grid, dim3(d.block), 0, m->stream, w));
+        break;
+    }
+    }
+    if (plain) fold_plain(m, o, s, slabs, d.psplit, pstride);
+}
+
+static void conv_dgrad(Model* m, int B, Op& o, double bytes, double flops) {
+    IgPlan& pl = g_ig[m];
+    const DenseLaunch d = dense_conv_dgrad(m, B, o, dense_switches());
+    ig::ConvArgs a{};
+    a.src[0] = o.out.g.p; a.c_src0 = o.out.d.C; a.c_src1 = 0;
+    a.src_half = o.out.g.h;
+    a.w = pl.flipped + o.w_off;
+    a.dst[0] = o.inA.g.p; a.dst[1] = o.inB.g.p;
+    a.n_dst0 = o.inA.d.C; a.n_dst1 = o.inB.d.C;
+    a.mask[0] = o.maskA ? o.inA.d.p : nullptr;
+    a.mask[1] = o.maskB ? o.inB.d.p : nullptr;
+    a.acc[0] = o.accA; a.acc[1] = o.accB;
+    a.dsth[0] = o.inA.g.h; a.dsth[1] = o.inB.g.h;
+    a.B = B; a.H = o.out.d.H; a.W = o.out.d.W;
+    a.alpha = o.mask_alpha;
+    // the backward sums of the BatchNorm that feeds the conv ride in the epilogue, and its reduction pass is not launched
+    if (d.bnb && !bn_bwd_fold_args(m, m->ops[o.src_bn[0]], &a.bnb)) a.bnb = BnBwdFold{};
+    launch_conv<1>(m, d, a, o.w_off, bytes, flops);
 }
 
 bool ig_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, double flops) {
     if (!ig_conv_supported(m, o)) return false;
     IgPlan& pl = g_ig[m];
-    const int CA = o.inA.d.C, CB = o.inB.d.C, CO = o.out.d.C;
+    const int CA = o.inA.d.C, CB = o.inB.d.C, CO = o.out.d.C, n_w = 9 * (CA + CB) * CO, nsrc = CB ? 2 : 1;
     if (o.alpha >= 0.f && !o.premasked)
         LAUNCH(m, "g_act_bwd", 3 * out_bytes, out_bytes / 4,
                g_act_bwd(m->stream, (size_t)B * o.out.d.H * o.out.d.W * CO, o.out.g.p, o.out.d.p, o.alpha));
-    const int tiles_x = (o.out.d.W + ig::TX - 1) / ig::TX, tiles_y = (o.out.d.H + ig::TY - 1) / ig::TY;
-    // small gradients shared by many blocks go through bucket copies (see WgArgs::nbuckets); fp32 second-generation kernel only
-    const int n_w = 9 * (CA + CB) * CO;
-    bool bucketed = false;
-    auto wgrad2_path = [&](int cs) { return wgrad2_ok(m, o, B, cs); };        // the launch condition of k_ig_wgrad2 below
-    auto wgrad2_psplit = [&](int cs) {
-        const int mw = cs % 64 == 0 ? 4 : (cs % 32 == 0 ? 2 : 1), nn = pick_nn(CO);
-        const int combos = (cs / (16 * mw)) * (CO / (16 * nn));
-        return (256 + combos - 1) / combos;
-    };
-    // (the split-bf16 kernel in plain mode needs no buckets: every block stores into its own slab)
-    static const bool x3_wgrad_off = getenv("DNNCA_NO_X3_WGRAD") != nullptr;
-    const bool plain3 = ig3x_enabled(m) && !x3_wgrad_off && wg_plain_on();
-    if (!plain3 && wgrad2_path(CA) && (!CB || wgrad2_path(CB)) && n_w + CO <= WG_SLAB_FLOATS && wgrad2_psplit(CA) > 32 &&
-        !dense_switches().no_wg_buckets) {
-        if (!pl.wg_slabs && !m->dry && m->alloc((void**)&pl.wg_slabs, (size_t)WG_BUCKETS * WG_SLAB_FLOATS * 4) != DNNCA_OK) pl.wg_slabs = nullptr;
-        bucketed = m->dry || pl.wg_slabs != nullptr;          // the dry run lists the launches of the real one
+    // The weight (+ bias) gradient goes first, one launch per source, on the side stream where the step allows (Model::wg_stream): the
+    // fork sits in front of the data gradient (measured: forking behind it, so that the weight gradient meets only the next layer's
+    // HBM-bound BatchNorm passes, is 1.5 - 2.5 % slower on both dense configs)
+    bool bucketed = dense_conv_wgrad(m, B, o, 0, dense_switches()).bucketed;
+    if (bucketed && !pl.wg_slabs && !m->dry && m->alloc((void**)&pl.wg_slabs, (size_t)WG_BUCKETS * WG_SLAB_FLOATS * 4) != DNNCA_OK) {
+        pl.wg_slabs = nullptr;
+        bucketed = false;          // (the launches add into the gradient itself)
     }
-    // weight (+bias) gradient, one launch per source -- on the side stream where the step allows (Model::wg_stream)
-    auto weight_gradient = [&]() {
-        hipStream_t main_stream = m->stream;
-        const bool side = m->wg_side_begin();
-        for (int s = 0; s < (CB ? 2 : 1); ++s) {
-            ig::WgArgs w{};
-            w.x = conv_source(m, o, s, &w.norm);
-            w.dz = o.out.g.p;
-            w.dw = bucketed ? pl.wg_slabs : m->g + o.w_off;
-            w.dbias = s == 0 ? (bucketed ? pl.wg_slabs + n_w : m->g + o.b_off) : nullptr;
-            w.nbuckets = bucketed ? WG_BUCKETS : 1;
-            w.bucket_stride = WG_SLAB_FLOATS;
-            w.cs = s == 0 ? CA : CB;
-            w.ci_off = s == 0 ? 0 : CA;
-            w.cin_total = CA + CB;
-            w.cout = CO;
-            w.B = B; w.H = o.out.d.H; w.W = o.out.d.W;
-            w.tiles_x = tiles_x; w.tiles_y = tiles_y;
-            const int nn = pick_nn(CO);
-            const int combos = (w.cs / ig::CK) * (CO / (16 * nn));
-            const int ntiles = tiles_x * tiles_y * B;
-            int psplit = (1024 + combos - 1) / combos;
-            if (psplit > ntiles) psplit = ntiles;
-            if (psplit < 1) psplit = 1;
-            w.psplit = psplit;
-            dim3 grid(psplit, w.cs / ig::CK, CO / (16 * nn));
-            const double bb = (out_bytes + in_bytes) / (CB ? 2 : 1), ff = flops / (CB ? 2 : 1);
-            // plain mode (WgArgs::plain) for a launch of `ps` pixel-split blocks per channel-block pair: slabs instead of the gradient
-            const int n_ws = 9 * w.cs * CO, pstride = (n_ws + CO + 3) / 4 * 4;
-            auto go_plain = [&](int ps) {
-                if (!wg_plain_on() || bucketed) return false;
-                float* slabs = m->dry ? nullptr : wg_plain_slabs(m, o, s, (size_t)ps * pstride);
-                if (!m->dry && !slabs) return false;
-                w.nbuckets = 1;
-                w.plain = 1;
-                w.dw = slabs;
-                w.dbias = s == 0 ? slabs + n_ws : nullptr;
-                w.cin_total = w.cs;
-                w.ci_off = 0;
-                w.bucket_stride = pstride;
-                return true;
-            };
-            auto fold_plain = [&](int ps) {
-                const int n_b = s == 0 ? CO : 0;
-                const ig::FoldSeg f{w.dw, m->g + o.w_off, m->g + o.b_off, ps, pstride, w.cs, CO, CA + CB, s == 0 ? 0 : CA, n_b, n_ws + n_b < 32768};
-                if (wg_fold_batched(m)) {
-                    pl.fold_pending.push_back(f);
-                    pl.fold_bytes += 4.0 * ps * (n_ws + n_b);
-                    return;
-                }
-                if (!f.g16)
-                    LAUNCH(m, "wg_fold", 4.0 * ps * (n_ws + n_b), 0,
-                           hipLaunchKernelGGL(ig::k_wg_fold_plain<1>, dim3((n_ws + n_b + 1023) / 1024), dim3(256), 0, m->stream, f));
-                else
-                    LAUNCH(m, "wg_fold", 4.0 * ps * (n_ws + n_b), 0,
-                           hipLaunchKernelGGL(ig::k_wg_fold_plain<16>, dim3((n_ws + n_b + 63) / 64), dim3(256), 0, m->stream, f));
-            };
-            if (use_bf16(m, o) && CO % 64 == 0 && w.cs % 64 == 0) {
-                const int combos64 = (w.cs / 64) * (CO / 64);
-                int ps = (256 + combos64 - 1) / combos64;
-                if (ps > ntiles) ps = ntiles;
-                w.psplit = ps < 1 ? 1 : ps;
-                const dim3 g64(w.psplit, w.cs / 64, CO / 64);
-                const bool xh = (s == 0 ? o.inA.d.h : o.inB.d.h) != 0, gh = o.out.g.h != 0;
-                static const int narrow = getenv("DNNCA_WGRAD64_NARROW") != nullptr;          // tuning aid
-                if (xh && gh && !narrow && (double)B * w.H * w.W * (w.cs > CO ? w.cs : CO) * 2.0 < 2.0e9) {         // eight waves per block (bf16-stored operands, 32-bit byte offsets)
-                    const bool plain = go_plain(w.psplit);
-                    m->set_variant(plain ? "w8p" : "w8");
-                    LAUNCH(m, "igb_wgrad64", bb, ff, hipLaunchKernelGGL(igb::k_igb_wgrad64w<2>, g64, dim3(512), 0, m->stream, w));
-                    if (plain) fold_plain(w.psplit);
-                    continue;
-                }
-    #define WG64(XH, GH) LAUNCH(m, "igb_wgrad64", bb, ff, hipLaunchKernelGGL((igb::k_igb_wgrad64<XH, GH>), g64, dim3(256), 0, m->stream, w))
-                m->set_variant("x%dg%d", (int)xh, (int)gh);
-                if (xh) { if (gh) WG64(true, true); else WG64(true, false); }
-                else { if (gh) WG64(false, true); else WG64(false, false); }
-    #undef WG64
-            } else if (!use_bf16(m, o) && (double)B * o.out.d.H * o.out.d.W * (w.cs > CO ? w.cs : CO) * 4.0 < 2.0e9 &&
-                       !dense_switches().wgrad1) {
-                // fp32 by three bf16 planes on the bf16 matrix pipe (kernels_ig3x.hip), unless switched off
-                {
-                    const int ps3 = ig3x_wgrad_psplit(m, w, CO);
-                    if (ps3 > 0) {
-                        const bool plain = go_plain(ps3);
-                        if (ig3x_wgrad_launch(m, w, CO, "ig3x_wgrad", bb, ff)) {
-                            if (plain) fold_plain(ps3);
-                            continue;
-                        }
-                    }
-                }
-                const int mw = w.cs % 64 == 0 ? 4 : (w.cs % 32 == 0 ? 2 : 1);
-                const int tm = (4 / mw) < (4 / nn) ? (4 / mw) : (4 / nn);
-                const int nt2 = tiles_x * ((o.out.d.H + 8 * tm - 1) / (8 * tm)) * B;
-                const int combos2 = (w.cs / (16 * mw)) * (CO / (16 * nn));
-                int ps = (256 + combos2 - 1) / combos2;
-                if (ps > nt2) ps = nt2;
-                w.psplit = ps < 1 ? 1 : ps;
-                dim3 g2(w.psplit, w.cs / (16 * mw), CO / (16 * nn));
-                static const int wg2_narrow = getenv("DNNCA_WGRAD2_NARROW") != nullptr;        // tuning aid
-    #define WG2(MWv, NNv, NWv) LAUNCH(m, "ig_wgrad2", bb, ff, hipLaunchKernelGGL((ig::k_ig_wgrad2<MWv, NNv, NWv>), g2, dim3(64 * NWv), 0, m->stream, w))
-    #define WG2N(MWv) do { if (nn == 4) WG2(MWv, 4, 4); \
-                           else if (nn == 2) { if (wg2_narrow) WG2(MWv, 2, 4); else WG2(MWv, 2, 8); } \
-                           else { if (wg2_narrow) WG2(MWv, 1, 4); else WG2(MWv, 1, 8); } } while (0)
-                m->set_variant("m%dn%dw%d", mw, nn, nn == 4 || wg2_narrow ? 4 : 8);
-                if (mw == 4) WG2N(4); else if (mw == 2) WG2N(2); else WG2N(1);
-    #undef WG2N
-    #undef WG2
-            } else if (m->set_variant("n%d", nn), use_bf16(m, o) && nn == 4) LAUNCH(m, "igb_wgrad", bb, ff, hipLaunchKernelGGL((igb::k_igb_wgrad<4>), grid, dim3(256), 0, m->stream, w));
-            else if (use_bf16(m, o) && nn == 2) LAUNCH(m, "igb_wgrad", bb, ff, hipLaunchKernelGGL((igb::k_igb_wgrad<2>), grid, dim3(256), 0, m->stream, w));
-            else if (nn == 4) LAUNCH(m, "ig_wgrad", bb, ff, hipLaunchKernelGGL((ig::k_ig_wgrad<4>), grid, dim3(256), 0, m->stream, w));
-            else if (nn == 2) LAUNCH(m, "ig_wgrad", bb, ff, hipLaunchKernelGGL((ig::k_ig_wgrad<2>), grid, dim3(256), 0, m->stream, w));
-            else LAUNCH(m, "ig_wgrad", bb, ff, hipLaunchKernelGGL((ig::k_ig_wgrad<1>), grid, dim3(256), 0, m->stream, w));
-        }
-        if (bucketed)
-            LAUNCH(m, "wg_fold", 4.0 * WG_BUCKETS * (n_w + CO), 0,
-                   hipLaunchKernelGGL(ig::k_wg_fold, dim3((n_w + CO + 255) / 256), dim3(256), 0, m->stream, pl.wg_slabs, WG_BUCKETS,
-                                      WG_SLAB_FLOATS, n_w, m->g + o.w_off, m->g + o.b_off, CO));
-        if (side) m->wg_side_end(main_stream);
-    };
-    auto data_gradient = [&]() {
-        if (o.need_din) {
-            ig::ConvArgs a{};
-            a.src[0] = o.out.g.p; a.c_src0 = CO; a.c_src1 = 0;
-            a.src_half = o.out.g.h;
-            a.w = pl.flipped + o.w_off;
-            a.dst[0] = o.inA.g.p; a.dst[1] = o.inB.g.p;
-            a.n_dst0 = CA; a.n_dst1 = CB;
-            a.mask[0] = o.maskA ? o.inA.d.p : nullptr;
-            a.mask[1] = o.maskB ? o.inB.d.p : nullptr;
-            a.acc[0] = o.accA; a.acc[1] = o.accB;
-            a.dsth[0] = o.inA.g.h; a.dsth[1] = o.inB.g.h;
-            a.B = B; a.H = o.out.d.H; a.W = o.out.d.W;
-            a.tiles_x = tiles_x; a.tiles_y = tiles_y;
-            a.alpha = o.mask_alpha;
-            // this launch writes ALL of the gradient arriving at the BatchNorm that feeds the conv (its only reader, nothing accumulated,
-            // no act' mask): the BatchNorm's backward sums ride in the epilogue and its reduction pass is not launched (ConvArgs::bnb;
-            // split-bf16 kernel, f32 tensors)
-            static const bool no_bnb = getenv("DNNCA_NO_BN_BWD_RIDE") != nullptr;          // A/B
-            Op* bnb_op = nullptr;
-            if (!no_bnb && !use_bf16(m, o) && CB == 0 && o.src_bn[0] >= 0 && !o.accA && !o.maskA && CA <= ig3x_max_bnb_channels()) {
-                Op& bn = m->ops[o.src_bn[0]];
-                const bool sole = bn.out_readers.size() == 1 && bn.out_readers[0] == (int)(&o - m->ops.data());
-                if (sole && bn.out.g.p == o.inA.g.p && bn.out.g.C == CA && conv3_path(a, CA, false) && ig3x_accepts(m, a, CA) &&
-                    bn_bwd_fold_args(m, bn, &a.bnb))
-                    bnb_op = &bn;
-            }
-            if (use_bf16(m, o))
-                launch_igb<1>(m, a, pl.wd + o.w_off, CA + CB, "igb_conv_dgrad", out_bytes + in_bytes, flops);
-            else {
-                bool rode = false;
-                launch_ig<1>(m, a, o.w_off, CA + CB, "ig_conv_dgrad", out_bytes + in_bytes, flops, &rode);
-                if (bnb_op && !rode) bnb_op->bwd_sums_rode = false;          // (a layout without the sums: the reduction pass runs as before)
-            }
-        }
-    };
-    // the fork sits in front of the data gradient (measured: forking behind it, so that the weight gradient meets only the next
-    // layer's HBM-bound BatchNorm passes, is 1.5 - 2.5 % slower on both dense configs; DNNCA_WG_LAST=1 selects that order)
-    static const bool wg_last = getenv("DNNCA_WG_LAST") != nullptr;
-    if (!wg_last) { weight_gradient(); data_gradient(); }
-    else { data_gradient(); weight_gradient(); }
+    hipStream_t main_stream = m->stream;
+    const bool side = m->wg_side_begin();
+    for (int s = 0; s < nsrc; ++s) conv_wgrad(m, B, o, s, bucketed, (out_bytes + in_bytes) / nsrc, flops / nsrc);
+    if (bucketed)
+        LAUNCH(m, "wg_fold", 4.0 * WG_BUCKETS * (n_w + CO), 0,
+               hipLaunchKernelGGL(ig::k_wg_fold, dim3((n_w + CO + 255) / 256), dim3(256), 0, m->stream, pl.wg_slabs, WG_BUCKETS,
+                                  WG_SLAB_FLOATS, n_w, m->g + o.w_off, m->g + o.b_off, CO));
+    if (side) m->wg_side_end(main_stream);
+    if (o.need_din) conv_dgrad(m, B, o, out_bytes + in_bytes, flops);
     return true;
 }
 
@@ -3346,118 +3392,81 @@ static ig::TcArgs tc_args(Model* m, int B, Op& o) {
 
 bool ig_tconv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_next) {
     if (!ig_tconv_supported(m, o)) return false;
+    const DenseLaunch d = dense_tconv_fwd(m, B, o, dense_switches());
     ig::TcArgs a = tc_args(m, B, o);
-    if (use_bf16_tc(m, o)) {
-        IgPlan& pl = g_ig[m];
-        if (bn_next && !dense_switches().no_bn_fusion)       // batch statistics of the BatchNorm behind it ride in the epilogue
-            (void)bn_self_fold_args(m, *bn_next, B, &a.bnf);
-        const dim3 grid((a.npix + 127) / 128, a.cout / 64);
-        static const bool gen1 = getenv("DNNCA_TCONV_FWD1") != nullptr;          // A/B: the first-generation kernel
-        if (!gen1 && a.out_half && (double)a.npix * 4.0 * a.cout < 2.0e9) {
-            m->set_variant("2h%d", (int)(o.inA.d.h != 0));
-            if (o.inA.d.h)
-                LAUNCH(m, "igb_tconv_fwd", bytes, flops, hipLaunchKernelGGL(igb::k_igb_tconv_fwd2<true>, grid, dim3(512), 0, m->stream, a, pl.wf + o.w_off));
-            else
-                LAUNCH(m, "igb_tconv_fwd", bytes, flops, hipLaunchKernelGGL(igb::k_igb_tconv_fwd2<false>, grid, dim3(512), 0, m->stream, a, pl.wf + o.w_off));
-            return true;
-        }
-        m->set_variant("h%d", (int)(o.inA.d.h != 0));
-        if (o.inA.d.h)
-            LAUNCH(m, "igb_tconv_fwd", bytes, flops, hipLaunchKernelGGL(igb::k_igb_tconv_fwd<true>, grid, dim3(256), 0, m->stream, a, pl.wf + o.w_off));
-        else
-            LAUNCH(m, "igb_tconv_fwd", bytes, flops, hipLaunchKernelGGL(igb::k_igb_tconv_fwd<false>, grid, dim3(256), 0, m->stream, a, pl.wf + o.w_off));
-        return true;
+    // batch statistics of the BatchNorm behind it ride in the epilogue
+    const bool stats = bn_next && d.stats && bn_self_fold_args(m, *bn_next, B, &a.bnf);
+    switch (d.kern) {
+    case DK_B16_TCONV2: case DK_B16_TCONV: {
+        static const TcKernB k[2][2] = {{igb::k_igb_tconv_fwd<false>, igb::k_igb_tconv_fwd<true>},
+                                        {igb::k_igb_tconv_fwd2<false>, igb::k_igb_tconv_fwd2<true>}};
+        m->set_variant(d.kern == DK_B16_TCONV2 ? "2h%d" : "h%d", (int)d.a16);
+        LAUNCH(m, "igb_tconv_fwd", bytes, flops,
+               hipLaunchKernelGGL(k[d.kern == DK_B16_TCONV2][d.a16], d.grid, dim3(d.block), 0, m->stream, a, g_ig[m].wf + o.w_off));
+        break;
     }
-    const int nn = pick_nn(a.cout);
-    static const bool gen1f = getenv("DNNCA_TCONV_FWD1") != nullptr;          // A/B: the first-generation kernel
-    if (!gen1f && !o.inA.d.h && !o.out.d.h && a.cin % ig::CK == 0 && (double)a.npix * 4.0 * a.cout < 2.0e9) {
-        // batch statistics of the BatchNorm behind it ride in the epilogue
-        const bool stats = bn_next && !dense_switches().no_bn_fusion && bn_self_fold_args(m, *bn_next, B, &a.bnf);
-        const dim3 g2((a.npix + 127) / 128, a.cout / (16 * nn));
-        m->set_variant("2n%d%s", nn, stats ? "s" : "");
-        if (nn == 4) LAUNCH(m, "ig_tconv_fwd", bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_fwd2<4>), g2, dim3(256), 0, m->stream, a));
-        else if (nn == 2) LAUNCH(m, "ig_tconv_fwd", bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_fwd2<2>), g2, dim3(256), 0, m->stream, a));
-        else LAUNCH(m, "ig_tconv_fwd", bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_fwd2<1>), g2, dim3(256), 0, m->stream, a));
-        return true;
+    default: {          // fp32, second / first generation
+        static const TcKern k[2][3] = {{ig::k_ig_tconv_fwd2<1>, ig::k_ig_tconv_fwd2<2>, ig::k_ig_tconv_fwd2<4>},
+                                       {ig::k_ig_tconv_fwd<1>, ig::k_ig_tconv_fwd<2>, ig::k_ig_tconv_fwd<4>}};
+        const bool gen1 = d.kern == DK_F32_TCONV;
+        m->set_variant(gen1 ? "n%d%s" : "2n%d%s", d.nn, stats ? "s" : "");
+        LAUNCH(m, "ig_tconv_fwd", bytes, flops, hipLaunchKernelGGL(k[gen1][ti(d.nn)], d.grid, dim3(d.block), 0, m->stream, a));
+        break;
     }
-    dim3 grid((a.npix + 127) / 128, a.cout / (16 * nn), 4);
-    m->set_variant("n%d", nn);
-    if (nn == 4) LAUNCH(m, "ig_tconv_fwd", bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_fwd<4>), grid, dim3(256), 0, m->stream, a));
-    else if (nn == 2) LAUNCH(m, "ig_tconv_fwd", bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_fwd<2>), grid, dim3(256), 0, m->stream, a));
-    else LAUNCH(m, "ig_tconv_fwd", bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_fwd<1>), grid, dim3(256), 0, m->stream, a));
+    }
     return true;
+}
+
+// weight (+ bias) gradient of a transposed conv: a leaf of the backward pass, on the side stream where the step allows
+static void tconv_wgrad(Model* m, int B, const Op& o, ig::TcArgs a, double bytes, double flops) {
+    const DenseLaunch d = dense_tconv_wgrad(m, B, o, dense_switches());
+    a.psplit = d.psplit;
+    hipStream_t main_stream = m->stream;
+    const bool side = m->wg_side_begin();
+    switch (d.kern) {
+    case DK_B16_TCONV_WGRAD64: {
+        static const TcKern k[2][2] = {{igb::k_igb_tconv_wgrad64<false, false>, igb::k_igb_tconv_wgrad64<false, true>},
+                                       {igb::k_igb_tconv_wgrad64<true, false>, igb::k_igb_tconv_wgrad64<true, true>}};
+        m->set_variant("x%dg%d", (int)d.x16, (int)d.g16);
+        LAUNCH(m, "igb_tconv_wgrad", bytes, flops, hipLaunchKernelGGL(k[d.x16][d.g16], d.grid, dim3(d.block), 0, m->stream, a));
+        break;
+    }
+    case DK_F32_TCONV_WGRAD2: {
+        static const TcKern k[3][3] = {{ig::k_ig_tconv_wgrad2<1, 1>, ig::k_ig_tconv_wgrad2<1, 2>, ig::k_ig_tconv_wgrad2<1, 4>},
+                                       {ig::k_ig_tconv_wgrad2<2, 1>, ig::k_ig_tconv_wgrad2<2, 2>, ig::k_ig_tconv_wgrad2<2, 4>},
+                                       {ig::k_ig_tconv_wgrad2<4, 1>, ig::k_ig_tconv_wgrad2<4, 2>, ig::k_ig_tconv_wgrad2<4, 4>}};
+        m->set_variant("m%dn%d", d.mw, d.nn);
+        LAUNCH(m, "ig_tconv_wgrad2", bytes, flops, hipLaunchKernelGGL(k[ti(d.mw)][ti(d.nn)], d.grid, dim3(d.block), 0, m->stream, a));
+        break;
+    }
+    default: {
+        static const TcKern k[3] = {ig::k_ig_tconv_wgrad<1>, ig::k_ig_tconv_wgrad<2>, ig::k_ig_tconv_wgrad<4>};
+        m->set_variant("n%d", d.nn);
+        LAUNCH(m, "ig_tconv_wgrad", bytes, flops, hipLaunchKernelGGL(k[ti(d.nn)], d.grid, dim3(d.block), 0, m->stream, a));
+        break;
+    }
+    }
+    if (side) m->wg_side_end(main_stream);
+}
+
+static void tconv_dgrad(Model* m, int B, const Op& o, const ig::TcArgs& a, double bytes, double flops) {
+    const DenseLaunch d = dense_tconv_dgrad(m, B, o, dense_switches());
+    if (d.kern == DK_B16_TCONV_DGRAD) {
+        const TcKernB k = d.k64 ? igb::k_igb_tconv_dgrad<true, 64> : igb::k_igb_tconv_dgrad<false, 32>;
+        m->set_variant("g%d%s", (int)d.g16, d.k64 ? "k64" : "");
+        LAUNCH(m, "igb_tconv_dgrad", bytes, flops, hipLaunchKernelGGL(k, d.grid, dim3(d.block), 0, m->stream, a, g_ig[m].wd + o.w_off));
+        return;
+    }
+    static const TcKern k[3] = {ig::k_ig_tconv_dgrad<1>, ig::k_ig_tconv_dgrad<2>, ig::k_ig_tconv_dgrad<4>};
+    m->set_variant("n%d", d.nn);
+    LAUNCH(m, "ig_tconv_dgrad", bytes, flops, hipLaunchKernelGGL(k[ti(d.nn)], d.grid, dim3(d.block), 0, m->stream, a));
 }
 
 bool ig_tconv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, double flops) {
     if (!ig_tconv_supported(m, o)) return false;
-    ig::TcArgs a = tc_args(m, B, o);
-    if (use_bf16_tc(m, o)) {
-        IgPlan& pl = g_ig[m];
-        const int ntiles = (a.npix + 127) / 128, combos = (a.cout / 64) * (a.cin / 64);
-        int ps = (256 + combos - 1) / combos;
-        if (ps > ntiles) ps = ntiles;
-        a.psplit = ps < 1 ? 1 : ps;
-        const dim3 gw(a.psplit, a.cout / 64, a.cin / 64), gd((a.npix + 127) / 128, a.cin / 64);
-        const bool xh = o.inA.d.h != 0, gh = o.out.g.h != 0;
-#define TW64(XH, GH) LAUNCH(m, "igb_tconv_wgrad", out_bytes + in_bytes, flops, hipLaunchKernelGGL((igb::k_igb_tconv_wgrad64<XH, GH>), gw, dim3(256), 0, m->stream, a))
-        hipStream_t main_stream = m->stream;
-        const bool side = m->wg_side_begin();          // a leaf of the backward pass: on the side stream where the step allows
-        m->set_variant("x%dg%d", (int)xh, (int)gh);
-        if (xh) { if (gh) TW64(true, true); else TW64(true, false); }
-        else { if (gh) TW64(false, true); else TW64(false, false); }
-        if (side) m->wg_side_end(main_stream);
-#undef TW64
-        static const bool k32 = getenv("DNNCA_TCONV_DGRAD_K32") != nullptr;          // A/B: 32-channel chunks
-        const bool k64 = gh && !k32 && a.cout % 64 == 0;
-        m->set_variant("g%d%s", (int)gh, k64 ? "k64" : "");
-        if (k64)
-            LAUNCH(m, "igb_tconv_dgrad", out_bytes + in_bytes, flops, hipLaunchKernelGGL((igb::k_igb_tconv_dgrad<true, 64>), gd, dim3(256), 0, m->stream, a, pl.wd + o.w_off));
-        else if (gh)
-            LAUNCH(m, "igb_tconv_dgrad", out_bytes + in_bytes, flops, hipLaunchKernelGGL((igb::k_igb_tconv_dgrad<true, 32>), gd, dim3(256), 0, m->stream, a, pl.wd + o.w_off));
-        else
-            LAUNCH(m, "igb_tconv_dgrad", out_bytes + in_bytes, flops, hipLaunchKernelGGL((igb::k_igb_tconv_dgrad<false, 32>), gd, dim3(256), 0, m->stream, a, pl.wd + o.w_off));
-        return true;
-    }
-    hipStream_t main_stream = m->stream;
-    const bool side = m->wg_side_begin();
-    if ((double)a.npix * 4.0 * a.cout * 4.0 < 2.0e9 && (double)a.npix * a.cin * 4.0 < 2.0e9 && !dense_switches().tcwgrad1) {
-        // second generation: (16 mw x 16 nn) channel tiles x 4 parities, 32-bit byte offsets
-        const int mw = a.cout % 64 == 0 ? 4 : (a.cout % 32 == 0 ? 2 : 1), nn = pick_nn(a.cin);
-        const int tm = (4 / mw) < (4 / nn) ? (4 / mw) : (4 / nn);
-        const int ntiles = (a.npix + 64 * tm - 1) / (64 * tm);
-        const int combos = (a.cout / (16 * mw)) * (a.cin / (16 * nn));
-        int ps = (256 + combos - 1) / combos;
-        if (ps > ntiles) ps = ntiles;
-        a.psplit = ps < 1 ? 1 : ps;
-        dim3 g2(a.psplit, a.cout / (16 * mw), a.cin / (16 * nn));
-#define TW2(MWv, NNv) LAUNCH(m, "ig_tconv_wgrad2", out_bytes + in_bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_wgrad2<MWv, NNv>), g2, dim3(256), 0, m->stream, a))
-        m->set_variant("m%dn%d", mw, nn);
-        if (mw == 4) { if (nn == 4) TW2(4, 4); else if (nn == 2) TW2(4, 2); else TW2(4, 1); }
-        else if (mw == 2) { if (nn == 4) TW2(2, 4); else if (nn == 2) TW2(2, 2); else TW2(2, 1); }
-        else { if (nn == 4) TW2(1, 4); else if (nn == 2) TW2(1, 2); else TW2(1, 1); }
-#undef TW2
-    } else {
-        const int nn = pick_nn(a.cin);
-        const int ntiles = (a.npix + 127) / 128;
-        const int combos = (a.cout / 16) * 4 * (a.cin / (16 * nn));
-        int psplit = (1024 + combos - 1) / combos;
-        if (psplit > ntiles) psplit = ntiles;
-        a.psplit = psplit < 1 ? 1 : psplit;
-        dim3 grid(a.psplit, a.cout / 16, 4 * (a.cin / (16 * nn)));
-        m->set_variant("n%d", nn);
-        if (nn == 4) LAUNCH(m, "ig_tconv_wgrad", out_bytes + in_bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_wgrad<4>), grid, dim3(256), 0, m->stream, a));
-        else if (nn == 2) LAUNCH(m, "ig_tconv_wgrad", out_bytes + in_bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_wgrad<2>), grid, dim3(256), 0, m->stream, a));
-        else LAUNCH(m, "ig_tconv_wgrad", out_bytes + in_bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_wgrad<1>), grid, dim3(256), 0, m->stream, a));
-    }
-    if (side) m->wg_side_end(main_stream);
-    {
-        const int nn = pick_nn(a.cin);
-        dim3 grid((a.npix + 127) / 128, a.cin / (16 * nn));
-        m->set_variant("n%d", nn);
-        if (nn == 4) LAUNCH(m, "ig_tconv_dgrad", out_bytes + in_bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_dgrad<4>), grid, dim3(256), 0, m->stream, a));
-        else if (nn == 2) LAUNCH(m, "ig_tconv_dgrad", out_bytes + in_bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_dgrad<2>), grid, dim3(256), 0, m->stream, a));
-        else LAUNCH(m, "ig_tconv_dgrad", out_bytes + in_bytes, flops, hipLaunchKernelGGL((ig::k_ig_tconv_dgrad<1>), grid, dim3(256), 0, m->stream, a));
-    }
+    const ig::TcArgs a = tc_args(m, B, o);
+    tconv_wgrad(m, B, o, a, out_bytes + in_bytes, flops);
+    tconv_dgrad(m, B, o, a, out_bytes + in_bytes, flops);
     return true;
 }
 

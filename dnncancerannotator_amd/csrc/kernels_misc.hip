@@ -983,7 +983,7 @@ bool bn_self_fold_args(Model* m, Op& bn, int B, BnSelfFold* f) {
 static unsigned bn_blocks(size_t npix, int C) {
     const size_t PL = 256 / (C / 4);
     size_t b = (npix + PL * 32 - 1) / (PL * 32);
-    static const size_t cap = getenv("DNNCA_BN_BLOCKS") ? (size_t)atoi(getenv("DNNCA_BN_BLOCKS")) : 512;          // tuning aid
+    const size_t cap = (size_t)dense_switches().bn_blocks;          // DNNCA_BN_BLOCKS (tuning aid), 512
     if (b > cap) b = cap;
     if (b < 1) b = 1;
     return (unsigned)b;
@@ -1032,7 +1032,7 @@ bool fast_bn_fwd(Model* m, int B, Op& o, bool training, float momentum, float ep
         // grid-stride: at most 1024 blocks (the statistics of the pooled tensor cost one LDS fold and one ticket per block: measured
         // per launch on unet_big 37.7 / 41.0 / 45.9 / 54.8 us with 1024 / 2048 / 4096 / 8192 blocks); the stride 256 x blocks is a
         // multiple of the channel groups (C / 4 divides 256: bn_fast_ok)
-        static const unsigned max_blocks = getenv("DNNCA_POOL_BLOCKS") ? (unsigned)atoi(getenv("DNNCA_POOL_BLOCKS")) : 1024u;      // tuning aid
+        const unsigned max_blocks = (unsigned)dense_switches().pool_blocks;      // DNNCA_POOL_BLOCKS (tuning aid)
         const size_t need = (n4 / 4 + 255) / 256;
         const dim3 grid((unsigned)(need < max_blocks ? need : max_blocks));
         unsigned* ix = reinterpret_cast<unsigned*>(pool->pool_idx);
@@ -1073,8 +1073,7 @@ bool fast_bn_supported(const Model* m, const Op& o) {
 // the pool's backward rides in the backward passes of the BatchNorm in front of it (PoolGrad): decided when the backward pass reaches
 // the pool; fast_bn_bwd finds Op::pool_grad
 bool fast_pool_into_bn(Model* m, Op& pool, Op& bn) {
-    static const bool off = getenv("DNNCA_NO_POOL_BN_BWD") != nullptr;
-    if (off || bn.type != OP_BN || pool.type != OP_POOL || pool.k != 2 || !fast_bn_supported(m, bn)) return false;
+    if (dense_switches().no_pool_bn_bwd || bn.type != OP_BN || pool.type != OP_POOL || pool.k != 2 || !fast_bn_supported(m, bn)) return false;
     if (bn.out.g.p != pool.inA.g.p || bn.out.g.C != pool.inA.g.C || !dense(pool.inA.g) || !dense(pool.out.g) || pool.out.g.h || pool.maskA) return false;
     if (!(pool.pool_idx_valid && (pool.pool_idx || m->dry))) return false;          // this step's forward recorded the positions
     if (bn.out.g.H % 2 || bn.out.g.W % 2 || (double)m->desc.max_batch * bn.out.g.H * bn.out.g.W * bn.out.g.W >= 4.0e9) return false;
