@@ -139,6 +139,7 @@ SIGNATURES = {
     'dnnca_profile_get': (C.c_int, [_VP, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                     C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'dnnca_plan_dump': (C.c_int, [_VP, C.c_char_p, C.c_size_t]),
+    'dnnca_plan_dump_pass': (C.c_int, [_VP, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

@@ -1734,26 +1734,45 @@ int dnnca_debug_launch_cost(void* model, int n, int blocks, float* us_per_launch
     return DNNCA_OK;
 }
 
-int dnnca_plan_dump(void* model, char* buf, size_t cap) {
+// pass DNNCA_PLAN_TRAIN: forward(training) + backward + optimizer, exactly what dnnca_train_step enqueues; DNNCA_PLAN_EVAL: what
+// dnnca_eval_step / dnnca_eval_step_staged enqueue (without the metric accumulation the caller switches on); DNNCA_PLAN_FORWARD:
+// dnnca_forward / dnnca_forward_dev with training = 0.  Nothing is launched and no variable, state or later result changes (the one-time plan
+// tables of the first forward pass may be built by it).
+int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap) {
     MODEL(model);
     if (!buf || !cap) return DNNCA_EINVAL;
+    if (pass != DNNCA_PLAN_TRAIN && pass != DNNCA_PLAN_EVAL && pass != DNNCA_PLAN_FORWARD) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
     M->plan_text.clear();
     M->dry = true;
     dnnca_loss_cfg cfg = {0, 0.f, 0.f, 1.f};
-    int B = M->desc.max_batch;
-    M->defer_head = true;
-    M->head_in_conv.requested = !getenv("DNNCA_NO_HEAD_IN_CONV");
-    M->head_in_conv.y = M->y_stage;
-    M->head_in_conv.cfg = cfg;
-    int rc = M->forward(M->x_stage, B, true);
-    M->defer_head = false;
-    M->head_in_conv.requested = false;
-    if (rc == DNNCA_OK) rc = M->loss_and_backward(M->y_stage, B, cfg, true);
-    if (rc == DNNCA_OK) rc = M->optimizer_step(1e-3f);
-    if (rc == DNNCA_OK && M->train_metrics_on()) rc = train_metrics_count(M, M->y_stage, B, Model::kStageSlots);
+    const int B = batch;
+    int rc;
+    if (pass == DNNCA_PLAN_TRAIN) {
+        M->defer_head = true;
+        M->head_in_conv.requested = !getenv("DNNCA_NO_HEAD_IN_CONV");
+        M->head_in_conv.y = M->y_stage;
+        M->head_in_conv.cfg = cfg;
+        rc = M->forward(M->x_stage, B, true);
+        M->defer_head = false;
+        M->head_in_conv.requested = false;
+        if (rc == DNNCA_OK) rc = M->loss_and_backward(M->y_stage, B, cfg, true);
+        if (rc == DNNCA_OK) rc = M->optimizer_step(1e-3f);
+        if (rc == DNNCA_OK && M->train_metrics_on()) rc = train_metrics_count(M, M->y_stage, B, Model::kStageSlots);
+    } else if (pass == DNNCA_PLAN_EVAL) {
+        rc = M->forward(M->x_stage, B, false);
+        if (rc == DNNCA_OK) rc = M->loss_and_backward(M->y_stage, B, cfg, false);
+    } else {
+        rc = dnnca_forward_dev(model, M->x_stage, B, 0);
+    }
     M->dry = false;
     snprintf(buf, cap, "%s", M->plan_text.c_str());
     return rc;
+}
+
+int dnnca_plan_dump(void* model, char* buf, size_t cap) {
+    MODEL(model);
+    return dnnca_plan_dump_pass(model, DNNCA_PLAN_TRAIN, M->desc.max_batch, buf, cap);
 }
 
 }  // extern "C"

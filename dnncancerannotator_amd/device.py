@@ -594,11 +594,21 @@ class DeviceModel:
             out.append((name.value.decode(), n.value, ms.value, by.value, fl.value))
         return out
 
-    def plan(self, variants=False):
-        """The launch schedule of one train step at max_batch: [(kernel, algorithmic bytes, flops)].  variants: keep the template
-        variant the library appends to a launch name (`ig_conv_fwd#3n2w8`): the kernel-coverage test tells them apart."""
+    PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2}
+
+    def plan(self, variants=False, mode='train', batch=None):
+        """The launch schedule of one pass: [(kernel, algorithmic bytes, flops)].  mode 'train': one train step; 'eval': one
+        eval_step (inference forward + loss; a staged evaluation step launches the same); 'forward': forward(training=False).
+        batch: None = max_batch.  variants: keep the template variant the library appends to a launch name
+        (`ig_conv_fwd#3n2w8`): the kernel-coverage test tells them apart.  A dry run: the model is unchanged."""
+        if mode not in self.PLAN_PASSES:
+            raise ValueError('plan mode %r is none of %s' % (mode, sorted(self.PLAN_PASSES)))
         buf = C.create_string_buffer(1 << 20)
-        check(self.lib.dnnca_plan_dump(self.handle, buf, len(buf)))
+        if mode == 'train' and batch is None:
+            check(self.lib.dnnca_plan_dump(self.handle, buf, len(buf)))
+        else:
+            check(self.lib.dnnca_plan_dump_pass(self.handle, self.PLAN_PASSES[mode], int(self.max_batch if batch is None else batch),
+                                                buf, len(buf)))
         out = []
         for line in buf.value.decode().splitlines():
             k, b, f = line.split('\t')

@@ -298,6 +298,11 @@ int dnnca_profile_get(void* model, int index, char* name, size_t name_cap, int64
                       double* algorithmic_bytes, double* flops);   /* bytes/flops are per launch (mean) */
 /* the launch schedule of one train step: name + algorithmic bytes/flops per launch (for DESIGN.md and bench.py) */
 int dnnca_plan_dump(void* model, char* buf, size_t cap);
+/* the same for one pass at one batch size in [1, max_batch]: the train step (dnnca_plan_dump is this at max_batch), an evaluation
+   step (dnnca_eval_step / dnnca_eval_step_staged: inference forward + loss), or a prediction (dnnca_forward with training = 0:
+   inference forward + sigmoid).  A dry run: nothing is launched and the model is left as it was. */
+enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2 };
+int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap);
 
 #ifdef __cplusplus
 }

@@ -118,6 +118,11 @@ def run(device, f0, S, B=2, bn=False, cin=32, n_down=2):
         m.set_state(O.flatten(spec, params, trainable=False))
     _, lg = m.forward(x, training=False, return_logits=True)
     dl = np.abs(lg - logits)
+    # inference against the emulating oracle's OWN inference pass (with BatchNorm: the moving statistics, not the batch's)
+    with bf16_oracle(round_z=bn):
+        _, l_eval = O.predict(spec, params, x.astype(np.float64))
+    dl_eval = np.abs(lg - l_eval)
+    names_eval = Hp.inference_plan_names(m)
     out = m.train_step(x, y, 0.0, m.loss_cfg(**cfg))
     g, gref = m.get_grads().astype(np.float64), O.flatten(spec, grads)
     errs = Hp.per_tensor_err(spec, g, gref)
@@ -126,7 +131,9 @@ def run(device, f0, S, B=2, bn=False, cin=32, n_down=2):
     deg = Hp.degenerate_tensors(spec)
     errs = {n: e for n, e in errs.items() if n not in deg}
     return dict(f0=f0, S=S, dl_max=float(dl.max()), dl_median=float(np.median(dl)), loss=float(out.loss), loss_ref=float(loss),
-                err_l2=float(np.linalg.norm(g - gref) / np.linalg.norm(gref)), per_tensor=errs, plan=names)
+                err_l2=float(np.linalg.norm(g - gref) / np.linalg.norm(gref)), per_tensor=errs, plan=names,
+                dl_eval_max=float(dl_eval.max()), dl_eval_median=float(np.median(dl_eval)), l_eval_max=float(np.abs(l_eval).max()),
+                plan_eval=names_eval)
 
 
 if __name__ == '__main__':

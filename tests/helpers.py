@@ -20,15 +20,37 @@ PARAM_SEED = 2
 # closes the loop: every launch of the three BASELINE configurations at full size must be in this set.
 ORACLE_KERNELS = set()
 ORACLE_TESTS = set()
+# ... and the same for the inference passes (eval_step / forward(training=False)), a set of its own: the same kernel reads other
+# coefficients (moving statistics) and takes other arms there, so a name met only in a train step does not count for inference and
+# vice versa.  Registered by the tests that compare INFERENCE output with the oracle, after the comparison.
+ORACLE_EVAL_KERNELS = set()
+ORACLE_EVAL_TESTS = set()
 
 
-def record_oracle_plan(model_or_names, test):
-    """`model_or_names`: a DeviceModel (its plan() -- the launch schedule of one train step under the current switches) or an
-    iterable of launch names (a child process's); `test`: the registering test function's name."""
-    names = model_or_names if isinstance(model_or_names, (list, tuple, set)) else [r[0] for r in model_or_names.plan(variants=True)]
-    ORACLE_KERNELS.update(names)
-    ORACLE_TESTS.add(test)
+def record_oracle_plan(model_or_names, test, mode='train', batch=None):
+    """`model_or_names`: a DeviceModel (its plan() -- the launch schedule of one pass under the current switches) or an iterable of
+    launch names (a child process's); `test`: the registering test function's name.  mode 'train' (one train step at max_batch, or
+    at `batch`) registers into ORACLE_KERNELS; mode 'eval' registers BOTH inference passes at `batch` (eval_step and
+    forward(training=False): the same forward pass, then g_loss or g_sigmoid) into ORACLE_EVAL_KERNELS."""
+    if mode not in ('train', 'eval'):
+        raise ValueError(mode)
+    if isinstance(model_or_names, (list, tuple, set)):
+        names = list(model_or_names)
+    elif mode == 'train':
+        names = [r[0] for r in model_or_names.plan(variants=True, batch=batch)]
+    else:
+        names = inference_plan_names(model_or_names, batch)
+    if mode == 'train':
+        ORACLE_KERNELS.update(names)
+        ORACLE_TESTS.add(test)
+    else:
+        ORACLE_EVAL_KERNELS.update(names)
+        ORACLE_EVAL_TESTS.add(test)
 
+
+def inference_plan_names(model, batch=None):
+    """launch names (with variants) of eval_step and forward(training=False) at `batch` (None: max_batch)"""
+    return sorted(set(r[0] for mode in ('eval', 'forward') for r in model.plan(variants=True, mode=mode, batch=batch)))
 
 
 def perturbed_params(spec, dtype):

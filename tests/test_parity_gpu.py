@@ -54,6 +54,8 @@ def _run_case(gpu, name, force_generic):
             assert np.array_equal((prob > thr)[decided], z[key][decided]), 'mask flip away from the threshold'
         out = m.eval_step(x, y, cfg)
         assert abs(out.loss - (float(z['loss_eval']) + O.l2_penalty(spec, O.unflatten(spec, p0)))) <= 1e-4 * max(1, abs(out.loss))
+        if not force_generic:
+            Hp.record_oracle_plan(m, 'test_golden_tuned_kernels', mode='eval', batch=B)
 
         # one training step
         out = m.train_step(x, y, float(z['lr']), cfg)
