@@ -5,9 +5,11 @@ The reference applies, per image and in the order of `data_options.train.augment
     random_flip      tf.image.random_flip_left_right: flip when U[0,1) < 0.5                              (data.py:620-625)
     random_contrast  tf.image.random_contrast(lower, upper) on the feature channels                       (data.py:586-609)
     random_warp      tfa.image.sparse_image_warp                                                          (data.py:725-763)
-All four run on the device (`dnnca_augment_u8`, `dnnca_warp_f32`); this module draws their per-image parameters with a numpy
-generator (TensorFlow's own random streams cannot be reproduced without TensorFlow, so the draws are not bit-compatible with a TF
-run -- their distributions are the reference's) and solves the small spline system of the warp.
+and, from the overlays configs/additionals/intra_channelwarp_std{3,5,10,20}.yaml,
+    random_intrachannelwarp   a random_warp of its own for every channel group of the slice, label included (data.py:656-715)
+All five run on the device (`dnnca_augment_u8`, `dnnca_warp_f32`, `dnnca_warp_groups_f32`); this module draws their per-image
+parameters with a numpy generator (TensorFlow's own random streams cannot be reproduced without TensorFlow, so the draws are not
+bit-compatible with a TF run -- their distributions are the reference's) and solves the small spline systems of the warps.
 """
 
 import logging
@@ -15,8 +17,9 @@ from collections import namedtuple
 
 import numpy as np
 
-AugmentPlan = namedtuple('AugmentPlan', ['crop', 'flip', 'contrast', 'warp', 'output_size'])
-RawBatch = namedtuple('RawBatch', ['raw', 'params', 'output_size', 'label_index', 'warp'])      # warp: (ctrl, wv) or None
+AugmentPlan = namedtuple('AugmentPlan', ['crop', 'flip', 'contrast', 'warp', 'output_size', 'intrawarp'], defaults=(None,))
+# warp: (ctrl, wv) or None; intrawarp: (ctrl [B, G, n, 2], wv [B, G, n + 3, 2], group_of [Cs]: group of every raw-slice channel) or None
+RawBatch = namedtuple('RawBatch', ['raw', 'params', 'output_size', 'label_index', 'warp', 'intrawarp'], defaults=(None,))
 
 
 
@@ -44,7 +47,8 @@ def raw_to_float(batch):
     return x, y
 
 
-_KNOWN = ('random_crop', 'random_flip', 'random_contrast', 'random_warp')
+_KNOWN = ('random_crop', 'random_flip', 'random_contrast', 'random_warp', 'random_intrachannelwarp')
+INTRAWARP_POINTS = 100          # data.py:706 passes n_points=100 to every group's random_warp, whatever the option says
 _warned = set()
 
 
@@ -52,7 +56,7 @@ def parse_augment_options(options, output_size):
     """data.py:538-551 + the defaults of train_ds (data.py:87-93).  options None -> {'random_crop': {}} like train_ds."""
     if options is None:
         options = {'random_crop': {}}
-    crop, flip, contrast, warp = None, False, None, None
+    crop, flip, contrast, warp, intrawarp = None, False, None, None, None
     for name, conf in options.items():
         conf = dict(conf or {})
         if name not in _KNOWN:
@@ -71,7 +75,21 @@ def parse_augment_options(options, output_size):
         elif name == 'random_warp':
             warp = dict(n_points=100, max_diff=5, stddev=2.0)                  # data.py:725 random_warp defaults
             warp.update({k: v for k, v in conf.items() if k != 'process_in_batch'})
-    return AugmentPlan(crop, flip, contrast, warp, tuple(output_size))
+        elif name == 'random_intrachannelwarp':
+            # data.py:656 `paired=((0, -1),)`, data.py:692 random_intrachannelwarp defaults; the option's n_points never reaches
+            # random_warp (data.py:706), so the shipped `n_points: 50` has no effect in the reference
+            intrawarp = dict(n_points=INTRAWARP_POINTS, max_diff=5, stddev=2.0, paired=((0, -1),))
+            intrawarp.update({k: v for k, v in conf.items() if k in ('max_diff', 'stddev')})
+            if 'paired' in conf:
+                intrawarp['paired'] = tuple(tuple(int(i) for i in pair) for pair in conf['paired'])
+            unknown = set(conf) - {'n_points', 'max_diff', 'stddev', 'paired'}
+            if unknown:
+                raise TypeError('random_intrachannelwarp got unexpected options %s (data.py:692)' % sorted(unknown))
+            if conf.get('n_points', INTRAWARP_POINTS) != INTRAWARP_POINTS and 'intrawarp_n_points' not in _warned:
+                _warned.add('intrawarp_n_points')
+                logging.warning('random_intrachannelwarp: n_points %r is ignored, every group is warped with %d control points '
+                                '(annotator/data.py:706)', conf['n_points'], INTRAWARP_POINTS)
+    return AugmentPlan(crop, flip, contrast, warp, tuple(output_size), intrawarp)
 
 
 def draw_params(rng, n, plan):
@@ -95,6 +113,51 @@ def draw_warp(rng, n, size, n_points=100, max_diff=5, stddev=2.0):
     raw = rng.uniform(0.0, float(size), (n, n_points, 2)).astype(np.float32)
     diff = np.clip(rng.normal(0.0, stddev, (n, n_points, 2)), -max_diff, max_diff).astype(np.float32)
     return raw, raw + diff
+
+
+def channel_groups(n_channels, paired=((0, -1),)):
+    """The channel groups of random_intrachannelwarp (data.py:693-704) for a raw slice of `n_channels` channels (`slice_types`
+    order, label included, before the feature/label split): the `paired` lists in their order with negative indices counted from
+    the end, then every channel in no pair on its own, ascending.  An index out of range or named twice is a ValueError (the
+    reference would fail in tf.gather, or stack a channel short)."""
+    groups, seen = [], set()
+    for pair in paired:
+        group = []
+        for ch in pair:
+            i = int(ch) + n_channels if int(ch) < 0 else int(ch)
+            if not 0 <= i < n_channels:
+                raise ValueError('random_intrachannelwarp: channel %d of paired=%r is out of range for %d channels' % (ch, paired, n_channels))
+            if i in seen:
+                raise ValueError('random_intrachannelwarp: channel %d is named twice in paired=%r' % (i, paired))
+            seen.add(i)
+            group.append(i)
+        groups.append(group)
+    return groups + [[i] for i in range(n_channels) if i not in seen]
+
+
+def group_table(groups, n_channels):
+    """int32 [n_channels]: the group every channel belongs to"""
+    table = np.full(n_channels, -1, np.int32)
+    for g, group in enumerate(groups):
+        table[group] = g
+    assert (table >= 0).all()
+    return table
+
+
+def draw_intrawarp(rng, n, size, n_groups, max_diff=5, stddev=2.0):
+    """Control points of random_intrachannelwarp for `n` square images of edge `size`: an independent random_warp draw
+    (data.py:748-752, always INTRAWARP_POINTS points: data.py:706) for each of the `n_groups` channel groups of every image.
+    Returns (source, dest) float32 [n, n_groups, 100, 2]."""
+    src, dst = draw_warp(rng, n * n_groups, size, INTRAWARP_POINTS, max_diff, stddev)
+    shape = (n, n_groups, INTRAWARP_POINTS, 2)
+    return src.reshape(shape), dst.reshape(shape)
+
+
+def solve_intrawarp(source, dest):
+    """solve_warp over the n * G systems of [n, G, k, 2] control points: (ctrl [n, G, k, 2], wv [n, G, k + 3, 2]) float64"""
+    n, g, k, _ = np.shape(dest)
+    ctrl, wv = solve_warp(np.reshape(source, (n * g, k, 2)), np.reshape(dest, (n * g, k, 2)))
+    return ctrl.reshape(n, g, k, 2), wv.reshape(n, g, k + 3, 2)
 
 
 def _phi2(r):

@@ -6,7 +6,8 @@
 //   to_feature_label() label channel -> y, the others in order -> x                        (data.py:766-788)
 // in two launches over a uint8 batch that was uploaded as stored (a quarter of the float bytes over PCIe).  The random draws are
 // made by the host (augment.py) and passed per image, so the arithmetic is checkable against the oracle draw for draw.
-// random_warp (tfa.image.sparse_image_warp) follows below as dnnca_warp_f32.
+// random_warp (tfa.image.sparse_image_warp) follows below as dnnca_warp_f32, random_intrachannelwarp as dnnca_warp_groups_f32.
+#include <stdlib.h>
 #include <string.h>
 #include "fast.h"
 #include "kernels.h"
@@ -245,5 +246,168 @@ int dnnca_warp_f32(void* model, const float* x_dev, const float* y_dev, int batc
     LAUNCH(M, "aug_warp", (double)batch * h * w * (c + 1) * 8.0, (double)batch * h * w * n_points * 8.0,
            hipLaunchKernelGGL(k_warp, dim3((h * w + 255) / 256, batch), dim3(256), (size_t)(n_points * 4 + 6) * 8, M->stream, a));
     HIP_TRY(hipStreamSynchronize(M->stream));
+    return DNNCA_OK;
+}
+
+// ------------------------------------------------------------------------------------- random_intrachannelwarp (dense part)
+// annotator/data.py:692-715 random_intrachannelwarp: the channels of a slice, label included, are split into groups (the `paired`
+// lists, then every other channel on its own) and every group goes through a random_warp of its own (data.py:706), so the
+// modalities slide against each other while a paired channel stays on its label.  The arithmetic per group is that of k_warp; here
+// one launch serves every group of every image.
+namespace dnnca {
+
+struct WarpGroupsArgs {
+    const float* x;          // [B, H, W, C] source features
+    const float* y;          // [B, H, W] source label
+    const double* ctrl;      // [B, G, n, 2] control points (row, column) of every group
+    const double* wv;        // [B, G, n + 3, 2] spline weights of every group (rows as in WarpArgs)
+    const int* group_of;     // [C + 1] group of feature channel c; entry C: the label
+    float* xo;
+    float* yo;
+    int B, H, W, C, G, n;
+};
+
+// control points + weights of group g of image b into sm (n * 4 + 6 doubles, the layout of k_warp); the caller synchronises
+__device__ __forceinline__ void warp_coeffs_to_lds(const WarpGroupsArgs& p, int b, int g, double* sm) {
+    const size_t bg = (size_t)b * p.G + g;
+    for (int i = threadIdx.x; i < p.n * 2; i += 256) {
+        sm[i] = p.ctrl[bg * p.n * 2 + i];
+        sm[p.n * 2 + i] = p.wv[bg * (p.n + 3) * 2 + i];
+    }
+    if (threadIdx.x < 6) sm[p.n * 4 + threadIdx.x] = p.wv[(bg * (p.n + 3) + p.n) * 2 + threadIdx.x];
+}
+
+// the bilinear taps of output pixel (qy, qx) under the spline in sm: flow in double (see k_warp), then tfa's interpolate_bilinear
+// at q - flow with the floor clamped to [0, size - 2] and alpha clipped to [0, 1] -- the clamps keep every tap inside the image
+// however far the flow throws the position (max_diff 100 in the shipped overlays)
+struct WarpTaps {
+    int iy, ix;
+    float ay, ax;
+    __device__ __forceinline__ float operator()(float tl, float tr, float bl, float br) const {
+        const float top = ax * (tr - tl) + tl, bot = ax * (br - bl) + bl;
+        return ay * (bot - top) + top;
+    }
+};
+
+__device__ __forceinline__ WarpTaps warp_taps(const double* sm, int n, int H, int W, int qy, int qx) {
+    const double* v = sm + n * 4;
+    double d0 = qy * v[0] + qx * v[2] + v[4];
+    double d1 = qy * v[1] + qx * v[3] + v[5];
+    for (int i = 0; i < n; ++i) {
+        const double dy = qy - sm[2 * i], dx = qx - sm[2 * i + 1];
+        const double r = dy * dy + dx * dx;
+        const double ph = 0.5 * r * log(fmax(r, 1e-10));
+        d0 = fma(ph, sm[n * 2 + 2 * i], d0);
+        d1 = fma(ph, sm[n * 2 + 2 * i + 1], d1);
+    }
+    const float sy = (float)qy - (float)d0, sx = (float)qx - (float)d1;
+    const float fy = fminf(fmaxf(floorf(sy), 0.f), (float)(H - 2)), fx = fminf(fmaxf(floorf(sx), 0.f), (float)(W - 2));
+    WarpTaps t;
+    t.ay = fminf(fmaxf(sy - fy, 0.f), 1.f);
+    t.ax = fminf(fmaxf(sx - fx, 0.f), 1.f);
+    t.iy = (int)fy;
+    t.ix = (int)fx;
+    return t;
+}
+
+// the channels of group g (and the label when it is in g) of output pixel (qy, qx) of image b
+__device__ __forceinline__ void warp_group_sample(const WarpGroupsArgs& p, int b, int g, int qy, int qx, const WarpTaps& t) {
+    const size_t o00 = ((size_t)b * p.H + t.iy) * p.W + t.ix, o01 = o00 + 1, o10 = o00 + p.W, o11 = o10 + 1;
+    const size_t oq = ((size_t)b * p.H + qy) * p.W + qx;
+    for (int c = 0; c < p.C; ++c)
+        if (p.group_of[c] == g)
+            p.xo[oq * p.C + c] = t(p.x[o00 * p.C + c], p.x[o01 * p.C + c], p.x[o10 * p.C + c], p.x[o11 * p.C + c]);
+    if (p.group_of[p.C] == g) p.yo[oq] = t(p.y[o00], p.y[o01], p.y[o10], p.y[o11]);
+}
+
+// PIXEL false: one group per block (blockIdx.z): n * 4 + 6 doubles of LDS, every lane of the block in the same n-term loop; a thread
+//              writes only its group's channels of the pixel.
+// PIXEL true:  one pixel per thread, the groups in a loop: G * (n * 4 + 6) doubles of LDS, the pixel is written by one thread.
+template <bool PIXEL>
+__global__ __launch_bounds__(256) void k_warp_groups(WarpGroupsArgs p) {
+    extern __shared__ double sm[];
+    const int b = blockIdx.y, stride = p.n * 4 + 6;
+    if (PIXEL)
+        for (int g = 0; g < p.G; ++g) warp_coeffs_to_lds(p, b, g, sm + g * stride);
+    else
+        warp_coeffs_to_lds(p, b, blockIdx.z, sm);
+    __syncthreads();
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id >= p.H * p.W) return;
+    const int qy = id / p.W, qx = id - qy * p.W;
+    if (PIXEL) {
+        for (int g = 0; g < p.G; ++g) warp_group_sample(p, b, g, qy, qx, warp_taps(sm + g * stride, p.n, p.H, p.W, qy, qx));
+    } else {
+        warp_group_sample(p, b, blockIdx.z, qy, qx, warp_taps(sm, p.n, p.H, p.W, qy, qx));
+    }
+}
+
+}  // namespace dnnca
+
+int dnnca_warp_groups_f32(void* model, const float* x_dev, const float* y_dev, int batch, int h, int w, int c, int n_groups,
+                          const int* group_of, int n_points, const double* ctrl_host, const double* wv_host, float* x_out_dev,
+                          float* y_out_dev) {
+    Model* M = reinterpret_cast<Model*>(model);
+    if (!M) { set_error("null model"); return DNNCA_EINVAL; }
+    if (!x_dev || !y_dev || !group_of || !ctrl_host || !wv_host || !x_out_dev || !y_out_dev || batch < 1 || batch > 65535 || h < 2 || w < 2 ||
+        c < 1 || n_points < 1 || n_points > 2048 || x_out_dev == x_dev || y_out_dev == y_dev) {
+        set_error("dnnca_warp_groups_f32: bad arguments");
+        return DNNCA_EINVAL;
+    }
+    if (n_groups < 1 || n_groups > c + 1) {
+        set_error("dnnca_warp_groups_f32: %d groups for %d channels + label", n_groups, c);
+        return DNNCA_EINVAL;
+    }
+    for (int i = 0; i <= c; ++i)
+        if (group_of[i] < 0 || group_of[i] >= n_groups) {
+            set_error("dnnca_warp_groups_f32: group_of[%d] = %d is not one of %d groups", i, group_of[i], n_groups);
+            return DNNCA_EINVAL;
+        }
+    // one row: control points, weights, group table -- the device copy has the same layout, so the row travels in one copy
+    const size_t nc = (size_t)batch * n_groups * n_points * 2 * 8, nw = (size_t)batch * n_groups * (n_points + 3) * 2 * 8;
+    const size_t row = nc + nw + (size_t)(c + 1) * 4;
+    if (row > M->warpg_scratch_bytes) {
+        void* p = nullptr;
+        DN_TRY(M->alloc(&p, row));
+        M->warpg_scratch = p;
+        M->warpg_scratch_bytes = row;
+    }
+    // like the draws of dnnca_augment_u8 the coefficients wait for their upload in a ring of pinned rows: the caller's buffers are
+    // free when this call returns and the call does not wait for the stream (a row is waited for when it comes round again)
+    if (row > M->warpg_pin_bytes) {
+        HIP_TRY(hipStreamSynchronize(M->stream));         // uploads from the old rows are complete
+        if (M->warpg_pin) (void)hipHostFree(M->warpg_pin);
+        M->warpg_pin = nullptr;
+        M->warpg_pin_bytes = 0;
+        HIP_TRY(hipHostMalloc(&M->warpg_pin, row * Model::kAugRing, hipHostMallocDefault));
+        M->warpg_pin_bytes = row;
+    }
+    const int k = M->warpg_k;
+    M->warpg_k = (k + 1) % Model::kAugRing;
+    if (!M->warpg_ev[k]) HIP_TRY(hipEventCreateWithFlags(&M->warpg_ev[k], hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(M->warpg_ev[k]));
+    char* pin = (char*)M->warpg_pin + (size_t)k * M->warpg_pin_bytes;
+    memcpy(pin, ctrl_host, nc);
+    memcpy(pin + nc, wv_host, nw);
+    memcpy(pin + nc + nw, group_of, (size_t)(c + 1) * 4);
+    HIP_TRY(hipMemcpyAsync(M->warpg_scratch, pin, row, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipEventRecord(M->warpg_ev[k], M->stream));
+    WarpGroupsArgs a{};
+    a.x = x_dev; a.y = y_dev; a.xo = x_out_dev; a.yo = y_out_dev;
+    a.ctrl = (const double*)M->warpg_scratch;
+    a.wv = (const double*)((char*)M->warpg_scratch + nc);
+    a.group_of = (const int*)((char*)M->warpg_scratch + nc + nw);
+    a.B = batch; a.H = h; a.W = w; a.C = c; a.G = n_groups; a.n = n_points;
+    const size_t lds = (size_t)(n_points * 4 + 6) * 8;
+    const unsigned bx = (unsigned)(((size_t)h * w + 255) / 256);
+    const double bytes = (double)batch * h * w * (c + 1) * 8.0, flops = (double)batch * h * w * n_groups * n_points * 8.0;
+    // DNNCA_WARP_GROUPS_PIXEL (tuning aid, read per call: tools/intrawarp_rate.py flips it): the pixel-per-thread layout, where its
+    // G coefficient sets fit the 64 KB of LDS a launch gets without opting in
+    if (getenv("DNNCA_WARP_GROUPS_PIXEL") != nullptr && lds * n_groups <= (64u << 10))
+        LAUNCH(M, "aug_warp_groups", bytes, flops,
+               hipLaunchKernelGGL(k_warp_groups<true>, dim3(bx, batch), dim3(256), lds * n_groups, M->stream, a));
+    else
+        LAUNCH(M, "aug_warp_groups", bytes, flops,
+               hipLaunchKernelGGL(k_warp_groups<false>, dim3(bx, batch, n_groups), dim3(256), lds, M->stream, a));
     return DNNCA_OK;
 }

@@ -116,6 +116,14 @@ struct Model {
     size_t aug_pin_bytes = 0;
     hipEvent_t aug_ev[kAugRing] = {nullptr, nullptr, nullptr, nullptr};      // recorded behind the upload that read row k
     int aug_k = 0;
+    // dnnca_warp_groups_f32: control points, spline weights and group table of every group of every image -- one device row, and
+    // a pinned ring of the same rows for the asynchronous upload (as aug_pin)
+    void* warpg_scratch = nullptr;
+    size_t warpg_scratch_bytes = 0;
+    void* warpg_pin = nullptr;           // kAugRing x warpg_pin_bytes, pinned
+    size_t warpg_pin_bytes = 0;
+    hipEvent_t warpg_ev[kAugRing] = {nullptr, nullptr, nullptr, nullptr};
+    int warpg_k = 0;
     float* first_slabs = nullptr;        // bucket copies of the first-layer weight gradient (kernels_first.hip; kept zeroed)
     // bucket rows of the BN reductions that fold themselves (bn_dev.h): kBnTab doubles, then the ticket counter; kept zeroed
     static constexpr int kBnTab = 4096;

@@ -54,6 +54,9 @@ Model::~Model() {
     if (tm_pin) (void)hipHostFree(tm_pin);
     for (auto e : aug_ev)
         if (e) (void)hipEventDestroy(e);
+    if (warpg_pin) (void)hipHostFree(warpg_pin);
+    for (auto e : warpg_ev)
+        if (e) (void)hipEventDestroy(e);
     if (wg_fork) (void)hipEventDestroy(wg_fork);
     if (wg_join) (void)hipEventDestroy(wg_join);
     if (wg_bucket) (void)hipEventDestroy(wg_bucket);

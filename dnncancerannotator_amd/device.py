@@ -537,6 +537,31 @@ class DeviceModel:
         check(self.lib.dnnca_warp_f32(self.handle, xv.ptr, yv.ptr, B, h, w, c, ctrl.shape[1], dptr(ctrl), dptr(wv), xo.ptr, yo.ptr))
         return DeviceView(xo, xv.shape), DeviceView(yo, yv.shape)
 
+    def warp_groups(self, xv, yv, group_of, ctrl, wv, label_index=None):
+        """random_intrachannelwarp's dense part on device-resident (x, y) views, one launch for every group of every image:
+        ctrl [B, G, n, 2], wv [B, G, n + 3, 2] from augment.solve_intrawarp.  group_of: the group of every feature channel, then
+        the label's ([c + 1]); with `label_index` it is the table of the raw slice's channels (augment.group_table, label at
+        label_index) and is reordered here.  Asynchronous on the model's stream; the views are valid until the next call."""
+        B, h, w, c = xv.shape
+        ctrl, wv = np.ascontiguousarray(ctrl, np.float64), np.ascontiguousarray(wv, np.float64)
+        group_of = np.asarray(group_of, np.int32).ravel()
+        if label_index is not None:
+            group_of = np.concatenate([np.delete(group_of, label_index), group_of[label_index:label_index + 1]])
+        group_of = np.ascontiguousarray(group_of, np.int32)
+        if group_of.size != c + 1:
+            raise ValueError('%d group entries for %d feature channels + label' % (group_of.size, c))
+        if ctrl.ndim != 4 or ctrl.shape[0] != B or wv.shape != ctrl.shape[:2] + (ctrl.shape[2] + 3, 2):
+            raise ValueError('ctrl %s / wv %s are not [B, G, n, 2] / [B, G, n + 3, 2] for a batch of %d' % (ctrl.shape, wv.shape, B))
+        dptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))        # noqa: E731
+        if not hasattr(self, '_warp_groups'):
+            self._warp_groups = (RawDeviceBuffer(), RawDeviceBuffer())
+        xo, yo = self._warp_groups
+        xo.reserve(xv.nbytes)
+        yo.reserve(yv.nbytes)
+        check(self.lib.dnnca_warp_groups_f32(self.handle, xv.ptr, yv.ptr, B, h, w, c, ctrl.shape[1], group_of.ctypes.data_as(C.POINTER(C.c_int)),
+                                             ctrl.shape[2], dptr(ctrl), dptr(wv), xo.ptr, yo.ptr))
+        return DeviceView(xo, xv.shape), DeviceView(yo, yv.shape)
+
     # ---- data parallel ----------------------------------------------------------------------------------------
     @staticmethod
     def comm_unique_id():

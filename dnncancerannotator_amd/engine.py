@@ -336,6 +336,9 @@ class TFKerasModel:
                     xb, yb = dm.augment_u8(shard(batch.raw)[0], params, batch.output_size, batch.label_index, src_ptr=src)
                     if batch.warp is not None:
                         xb, yb = dm.warp(xb, yb, shard(batch.warp[0])[0], shard(batch.warp[1])[0])
+                    if batch.intrawarp is not None:      # after random_warp: the overlay's key comes behind data_options.yaml's
+                        xb, yb = dm.warp_groups(xb, yb, batch.intrawarp[2], shard(batch.intrawarp[0])[0], shard(batch.intrawarp[1])[0],
+                                                label_index=batch.label_index)
                     dm.check_dev(xb, yb, n)
                     feeder.ring.train_step(slot, xb.ptr, yb.ptr, n, self.learning_rate, cfg)
                 else:
@@ -347,6 +350,9 @@ class TFKerasModel:
                         xb, yb = dm.augment_u8(raw, params, batch.output_size, batch.label_index)
                         if batch.warp is not None:
                             xb, yb = dm.warp(xb, yb, shard(batch.warp[0])[0], shard(batch.warp[1])[0])
+                        if batch.intrawarp is not None:
+                            xb, yb = dm.warp_groups(xb, yb, batch.intrawarp[2], shard(batch.intrawarp[0])[0], shard(batch.intrawarp[1])[0],
+                                                    label_index=batch.label_index)
                         out = dm.train_step_dev(xb, yb, len(raw), self.learning_rate, cfg, want_out=True)
                     else:
                         x, y = shard(np.asarray(batch[0]), np.asarray(batch[1]))

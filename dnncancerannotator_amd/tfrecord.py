@@ -310,7 +310,7 @@ class TFRecordDataset:
     Training (`augment_options` a dict or None, data.py:62-111 train_ds): the slices are centre-cropped to 512 x 512 (the `base`
     call of train_ds, data.py:95-100), shuffled through a buffer of `buffer_size` slices (data.py:106) and handed on as uint8
     `augment.RawBatch`es with their random draws; crop / flip / contrast / the /255 and the feature-label split then run on the
-    device (`dnnca_augment_u8` / `dnnca_warp_f32`, engine.train).
+    device (`dnnca_augment_u8` / `dnnca_warp_f32` / `dnnca_warp_groups_f32`, engine.train).
 
     include_meta (evaluation only, eval_ds(include_meta=True), data.py:488-510): batches (x, y, paths, sliceIDs) -- the same x and
     y as without it, each slice's exam `path` feature and its 0-based index in the exam record (tf.data.experimental.Counter)."""
@@ -517,13 +517,21 @@ class TFRecordDataset:
                 raise ValueError('random_warp supports square images only (data.py:746 asserts width == height)')
             src, dst = augment.draw_warp(self.rng, len(raws), self.output_size[0], **self.plan.warp)      # draws for the global batch
             warp = augment.solve_warp(self._mine(src), self._mine(dst))
+        intrawarp = None
+        if self.plan.intrawarp is not None:
+            if self.output_size[0] != self.output_size[1]:
+                raise ValueError('random_intrachannelwarp supports square images only (data.py:706 -> random_warp, data.py:746)')
+            opt = self.plan.intrawarp
+            groups = augment.channel_groups(len(self.slice_types), opt['paired'])
+            src, dst = augment.draw_intrawarp(self.rng, len(raws), self.output_size[0], len(groups), opt['max_diff'], opt['stddev'])
+            intrawarp = augment.solve_intrawarp(self._mine(src), self._mine(dst)) + (augment.group_table(groups, len(self.slice_types)),)
         params = self._mine(augment.draw_params(self.rng, len(raws), self.plan))
         # only the window the random crop can reach travels on (centre +- the jitter bound: the same centre, so the same pixels
         # come out of dnnca_augment_u8): 268 x 268 of 512 x 512 for the default crop -- a quarter of the bytes to stack and upload
         m = max(abs(int(self.plan.crop['min_'])), abs(int(self.plan.crop['max_']))) if self.plan.crop is not None else 0
         oh, ow = self.output_size
         mine = [self._centre(r[None], min(r.shape[0], oh + 2 * m), min(r.shape[1], ow + 2 * m))[0] for r in self._mine(raws)]
-        return augment.RawBatch(np.stack(mine), params, self.output_size, self.label_idx, warp)
+        return augment.RawBatch(np.stack(mine), params, self.output_size, self.label_idx, warp, intrawarp)
 
     def _stacked(self, xs, ys):
         mx, my = self._mine(xs), self._mine(ys)

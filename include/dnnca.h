@@ -155,6 +155,16 @@ int dnnca_augment_u8(void* model, const void* src_dev, int batch, int hs, int ws
    y [batch, h, w] bilinearly at q - flow(q) (tfa dense_image_warp); outputs must not alias the inputs. */
 int dnnca_warp_f32(void* model, const float* x_dev, const float* y_dev, int batch, int h, int w, int c, int n_points,
                    const double* ctrl_host, const double* wv_host, float* x_out_dev, float* y_out_dev);
+/* random_intrachannelwarp (annotator/data.py:656-715): the channels of a slice, label included, are split into n_groups groups
+   and every group is warped by a random_warp of its own (data.py:706), in ONE launch for all groups of all images.
+   group_of [c + 1]: the group (0 .. n_groups - 1) of feature channel i; entry c is the label's.  ctrl_host [batch, n_groups,
+   n_points, 2] and wv_host [batch, n_groups, n_points + 3, 2] as for dnnca_warp_f32, one spline per image and group.  Arithmetic
+   and bilinear clamping are those of dnnca_warp_f32; 1 <= n_groups <= c + 1; outputs must not alias the inputs.
+   Asynchronous on the model's stream like dnnca_augment_u8: the host arrays have been copied when the call returns; a host read
+   of the outputs needs dnnca_sync first. */
+int dnnca_warp_groups_f32(void* model, const float* x_dev, const float* y_dev, int batch, int h, int w, int c, int n_groups,
+                          const int* group_of, int n_points, const double* ctrl_host, const double* wv_host, float* x_out_dev,
+                          float* y_out_dev);
 /* same as dnnca_train_step with x/y already in HBM; asynchronous on the model's stream; out may be NULL (no sync) */
 int dnnca_train_step_dev(void* model, const float* x_dev, const float* y_dev, int batch, float lr,
                          const dnnca_loss_cfg* cfg, dnnca_step_out* out);
