@@ -124,6 +124,7 @@ SIGNATURES = {
     'dnnca_eval_region_end': (C.c_int, [_VP, C.POINTER(RegionCounts)]),
     'dnnca_region_confusion_slices': (C.c_int, [_VP, _FP, _FP, C.c_int, C.POINTER(RegionSpec), C.c_int, C.POINTER(RegionCounts)]),
     'dnnca_render_composite': (C.c_int, [_VP, _FP, C.c_int, C.c_float, C.c_int, _VP, C.c_int64, C.POINTER(C.c_int32)]),
+    'dnnca_input_sensitivity': (C.c_int, [_VP, _FP, C.c_int, C.POINTER(C.c_double)]),
     'dnnca_comm_unique_id': (C.c_int, [_VP]),
     'dnnca_comm_init': (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_size_t]),
     'dnnca_comm_world': (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -9,6 +9,7 @@ Files under <export_path>/<tag>/ (callbacks.py _emit):
     images/<last 3 components of the exam path>/<sliceID %02d>/step_<step %08d>.png           (--export_images)
     csv/<last 3 components of the exam path>/<sliceID %02d>/step_<step %08d>_metrics.csv      (--export_csv)
     casewise_results.csv: every slice of every evaluated checkpoint, in dataset order          (--export_csv)
+    images/.../step_<step %08d>_sensitivity.png and csv/.../step_<step %08d>_sensitivity.csv  (--visualize_sensitivity, per slice)
 The CSV bytes are those of pandas' to_csv (`pd.DataFrame(series).T.to_csv()`, `pd.DataFrame(rows).to_csv()`): csv-module
 quoting, '\\n' line ends, an empty header cell for the index."""
 
@@ -91,6 +92,78 @@ def table_csv(names, rows):
     if not rows:
         return _csv([['']])
     return _csv([[''] + list(names)] + [[i] + list(r) for i, r in enumerate(rows)])
+
+
+# ---- channel sensitivity (callbacks.py:290-313, 352-398): DeviceModel.input_sensitivity gives the raw sums -----------------------
+def sensitivity_path(root, tag, step, kind):
+    """kind 'csv' -> csv/<exam>/<slice>/step_<step>_sensitivity.csv, 'images' -> images/<exam>/<slice>/step_<step>_sensitivity.png"""
+    ext = {'csv': 'csv', 'images': 'png'}[kind]
+    return os.path.join(export_dir(root, kind, tag), 'step_%08d_sensitivity.%s' % (int(step), ext))
+
+
+def modality_names(slice_types, n_channels):
+    """the dataset's slice_types without the label, in their order; a dataset without them (synthetic, .npz): ch0, ch1, ..."""
+    if slice_types:
+        names = [str(t) for t in slice_types if t != 'label']
+        if len(names) == int(n_channels):
+            return names
+    return ['ch%d' % i for i in range(int(n_channels))]
+
+
+def normalise_sensitivity(sums):
+    """raw sums [B, C] -> rows divided by their sum; an all-zero row is 0 / 0 = NaN, as in the reference"""
+    s = np.asarray(sums, np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return s / s.sum(axis=-1, keepdims=True)
+
+
+def sensitivity_csv(names, values):
+    """pd.Series(values, index=names).to_csv(): the header ',0', then 'name,value' per modality (repr of the float64; NaN: empty)"""
+    rows = [['', 0]]
+    for n, v in zip(names, values):
+        v = float(v)
+        rows.append([n, '' if v != v else repr(v)])
+    return _csv(rows)
+
+
+# the bar chart: a white canvas, a black frame around the plot area (y from 0 at its bottom to 1 at its top), one bar per modality
+CHART_PLOT_H = 200               # pixels of y = 0 .. 1
+CHART_MARGIN = 20
+CHART_SLOT = 48                  # horizontal room of one modality; its bar is the middle CHART_BAR pixels
+CHART_BAR = 32
+CHART_BAR_RGB = (31, 119, 180)
+
+
+def chart_bar_columns(n):
+    """[(x0, x1)] pixel columns [x0, x1) of each of the n bars"""
+    off = CHART_MARGIN + 1 + (CHART_SLOT - CHART_BAR) // 2
+    return [(off + i * CHART_SLOT, off + i * CHART_SLOT + CHART_BAR) for i in range(int(n))]
+
+
+def chart_bar_height(v):
+    """pixels of a bar of value v: round(v * CHART_PLOT_H), v clipped to [0, 1]; NaN: no bar"""
+    v = float(v)
+    if v != v:
+        return 0
+    return int(round(min(max(v, 0.0), 1.0) * CHART_PLOT_H))
+
+
+def sensitivity_chart(values):
+    """normalised sensitivities of one slice -> uint8 RGB [h, w, 3] bar chart (modality order = value order, y range 0 .. 1).
+    Plain numpy: not the pixels of the reference's matplotlib figure."""
+    n = len(values)
+    h, w = CHART_PLOT_H + 2 * CHART_MARGIN + 2, n * CHART_SLOT + 2 * CHART_MARGIN + 2
+    img = np.full((h, w, 3), 255, np.uint8)
+    top, bottom, left, right = CHART_MARGIN, CHART_MARGIN + CHART_PLOT_H + 1, CHART_MARGIN, w - CHART_MARGIN - 1
+    img[top, left:right + 1] = 0
+    img[bottom, left:right + 1] = 0
+    img[top:bottom + 1, left] = 0
+    img[top:bottom + 1, right] = 0
+    for (x0, x1), v in zip(chart_bar_columns(n), values):
+        bh = chart_bar_height(v)
+        if bh:
+            img[bottom - bh:bottom, x0:x1] = CHART_BAR_RGB
+    return img
 
 
 def _chunk(kind, data):

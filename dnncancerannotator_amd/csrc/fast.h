@@ -137,6 +137,10 @@ int ig_begin_backward(Model* m);
 void ig_release(Model* m);
 bool ig_conv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_next);   // bn_next: BatchNorm of the output whose statistics may ride in the epilogue
 bool ig_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, double flops);
+// the data gradient of a dense conv / transposed conv without its weight-gradient half, activation mask or BatchNorm sums (the
+// input-sensitivity pass: o.out.g holds the pre-activation gradient); false: not a dense layer
+bool ig_conv_dgrad_only(Model* m, int B, Op& o, double bytes, double flops);
+bool ig_tconv_dgrad_only(Model* m, int B, Op& o, double bytes, double flops);
 // will this conv's forward and weight-gradient launches (batch B) be the kernels that can normalise a BatchNorm's input while staging it?
 // (Model::forward elides the BatchNorm's apply pass on this answer)
 bool ig_norm_on_load_ok(const Model* m, int B, const Op& o);

@@ -3273,7 +3273,8 @@ static void conv_wgrad(Model* m, int B, const Op& o, int s, bool bucketed, doubl
     if (plain) fold_plain(m, o, s, slabs, d.psplit, pstride);
 }
 
-static void conv_dgrad(Model* m, int B, Op& o, double bytes, double flops) {
+// bare: the data gradient and nothing else (the input-sensitivity pass) -- no activation mask on the stores, no BatchNorm sums
+static void conv_dgrad(Model* m, int B, Op& o, double bytes, double flops, bool bare = false) {
     IgPlan& pl = g_ig[m];
     const DenseLaunch d = dense_conv_dgrad(m, B, o, dense_switches());
     ig::ConvArgs a{};
@@ -3282,14 +3283,14 @@ static void conv_dgrad(Model* m, int B, Op& o, double bytes, double flops) {
     a.w = pl.flipped + o.w_off;
     a.dst[0] = o.inA.g.p; a.dst[1] = o.inB.g.p;
     a.n_dst0 = o.inA.d.C; a.n_dst1 = o.inB.d.C;
-    a.mask[0] = o.maskA ? o.inA.d.p : nullptr;
-    a.mask[1] = o.maskB ? o.inB.d.p : nullptr;
+    a.mask[0] = o.maskA && !bare ? o.inA.d.p : nullptr;
+    a.mask[1] = o.maskB && !bare ? o.inB.d.p : nullptr;
     a.acc[0] = o.accA; a.acc[1] = o.accB;
     a.dsth[0] = o.inA.g.h; a.dsth[1] = o.inB.g.h;
     a.B = B; a.H = o.out.d.H; a.W = o.out.d.W;
     a.alpha = o.mask_alpha;
     // the backward sums of the BatchNorm that feeds the conv ride in the epilogue, and its reduction pass is not launched
-    if (d.bnb && !bn_bwd_fold_args(m, m->ops[o.src_bn[0]], &a.bnb)) a.bnb = BnBwdFold{};
+    if (d.bnb && (bare || !bn_bwd_fold_args(m, m->ops[o.src_bn[0]], &a.bnb))) a.bnb = BnBwdFold{};
     launch_conv<1>(m, d, a, o.w_off, bytes, flops);
 }
 
@@ -3317,6 +3318,12 @@ bool ig_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, doub
                                   WG_SLAB_FLOATS, n_w, m->g + o.w_off, m->g + o.b_off, CO));
     if (side) m->wg_side_end(main_stream);
     if (o.need_din) conv_dgrad(m, B, o, out_bytes + in_bytes, flops);
+    return true;
+}
+
+bool ig_conv_dgrad_only(Model* m, int B, Op& o, double bytes, double flops) {
+    if (!ig_conv_supported(m, o) || !o.need_din) return false;
+    conv_dgrad(m, B, o, bytes, flops, true);
     return true;
 }
 
@@ -3467,6 +3474,14 @@ bool ig_tconv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, dou
     const ig::TcArgs a = tc_args(m, B, o);
     tconv_wgrad(m, B, o, a, out_bytes + in_bytes, flops);
     tconv_dgrad(m, B, o, a, out_bytes + in_bytes, flops);
+    return true;
+}
+
+bool ig_tconv_dgrad_only(Model* m, int B, Op& o, double bytes, double flops) {
+    if (!ig_tconv_supported(m, o)) return false;
+    ig::TcArgs a = tc_args(m, B, o);
+    a.mask = nullptr;
+    tconv_dgrad(m, B, o, a, bytes, flops);
     return true;
 }
 

@@ -244,6 +244,17 @@ struct Model {
     std::vector<int> pass_order(bool backward) const;      // op indices in the order a pass visits them
     std::vector<char> op_done;                              // per pass: this op's work rode in an earlier launch of the pass
 
+    // input sensitivity (dnnca_input_sensitivity): while sens_pass is set the inference forward keeps every tensor a backward pass
+    // reads (no fused, elided or riding op) and leaves its logits in `dlogits`; the tensors' .g views are the pass's scratch.
+    // sens_descs: the first-layer table (sens.h SensFirst x sens_nz, static per model); sens_part: block partials; sens_ticket: one
+    // counter per (image, table entry), kept zeroed; sens_sums: [max_batch, in_channels] doubles
+    bool sens_pass = false;
+    void* sens_descs = nullptr;
+    int sens_nz = 0;
+    double *sens_part = nullptr, *sens_sums = nullptr;
+    unsigned* sens_ticket = nullptr;
+    int input_sensitivity(const float* x_dev, int B);      // enqueues the pass; the sums are in sens_sums behind it
+
     ~Model();
     int build();
     int alloc(void** ptr, size_t bytes);

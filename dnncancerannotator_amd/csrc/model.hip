@@ -14,6 +14,7 @@
 #include "fast.h"
 #include "kernels.h"
 #include "region.h"
+#include "sens.h"
 
 namespace dnnca {
 
@@ -498,7 +499,8 @@ std::vector<int> Model::pass_order(bool backward) const {
 int Model::forward(const float* x_dev, int B, bool training) {
     if (B < 1 || B > desc.max_batch) { set_error("batch %d outside [1, max_batch=%d]", B, desc.max_batch); return DNNCA_EINVAL; }
     last_batch = B;
-    const bool generic = desc.flags & 1;
+    // (the input-sensitivity pass walks the per-op arms too: every tensor its backward pass reads is then stored)
+    const bool generic = (desc.flags & 1) || sens_pass;
     // input ops carry a channel offset relative to xin; rebase them on this batch
     for (Op& o : ops)
         if (o.type == OP_CONV && !o.need_din) {
@@ -507,7 +509,7 @@ int Model::forward(const float* x_dev, int B, bool training) {
         }
     xin.d.p = const_cast<float*>(x_dev);
     step_init_done = false;
-    DN_TRY(fast_prepare(this));
+    if (!sens_pass) DN_TRY(fast_prepare(this));
     DN_TRY(ig_prepare(this));
     head_in_conv.done = false;
     tail_done = first_done = tconv_done = nullptr;
@@ -580,6 +582,7 @@ int Model::forward(const float* x_dev, int B, bool training) {
                 Op* bn_next = (training && oi + 1 < ops.size() && ops[oi + 1].type == OP_BN && ops[oi + 1].inA.d.p == o.out.d.p &&
                                fast_bn_supported(this, ops[oi + 1])) ? &ops[oi + 1] : nullptr;
                 if (!generic && (fast_first_conv_fwd(this, B, o, bytes, flops, bn_next) || ig_conv_fwd(this, B, o, bytes, flops, bn_next))) break;
+                if (sens_pass && !(desc.flags & 1) && ig_conv_fwd(this, B, o, bytes, flops, nullptr)) break;      // dense conv, output stored, nothing riding
                 if (!all_f32(o)) return DNNCA_ESTATE;
                 LAUNCH(this, "g_conv_fwd", bytes, flops,
                        g_conv_fwd(stream, B, o.inA.d, o.inB.d, p + o.w_off, p + o.b_off, o.out.d, o.k, o.alpha));
@@ -638,6 +641,7 @@ int Model::forward(const float* x_dev, int B, bool training) {
                 Op* bn_next = (training && oi + 1 < ops.size() && ops[oi + 1].type == OP_BN && ops[oi + 1].inA.d.p == o.out.d.p &&
                                fast_bn_supported(this, ops[oi + 1])) ? &ops[oi + 1] : nullptr;
                 if (!generic && (fast_tconv_fwd(this, B, o, bytes, flops) || ig_tconv_fwd(this, B, o, bytes, flops, bn_next))) break;
+                if (sens_pass && !(desc.flags & 1) && ig_tconv_fwd(this, B, o, bytes, flops, nullptr)) break;
                 if (!all_f32(o)) return DNNCA_ESTATE;
                 LAUNCH(this, "g_tconv_fwd", bytes, flops,
                        g_tconv_fwd(stream, B, o.inA.d, p + o.w_off, p + o.b_off, o.out.d, o.k));
@@ -652,7 +656,7 @@ int Model::forward(const float* x_dev, int B, bool training) {
                 }
                 if (!all_f32(o)) return DNNCA_ESTATE;
                 LAUNCH(this, "g_head_fwd", 4.0 * (nelem(B, o.inA.d) + npix), 2.0 * nelem(B, o.inA.d),
-                       g_head_fwd(stream, B, o.inA.d, p + o.w_off, p + o.b_off, logits));
+                       g_head_fwd(stream, B, o.inA.d, p + o.w_off, p + o.b_off, sens_pass ? dlogits : logits));
                 break;
             }
         }
@@ -864,6 +868,103 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
     }
     LAUNCH(this, "g_finalize_scalars", 0, 0,
            g_finalize_scalars(stream, scalars, cfg, (double)npix, 1.0 / ((double)outH * outW * B), out5));
+    return DNNCA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- input sensitivity
+// s[b, c] = sum over the image of |d sum(sigmoid(logits)) / d x[b, :, :, c]| with the model in inference mode (utils/callbacks.py:290-313):
+// an inference forward that stores every tensor, then the data gradients alone over `ops` in reverse -- no weight gradient, no
+// optimizer step, no BatchNorm state.  Scratch: the tensors' .g views, `dlogits` (the pass's logits: `logits` / `prob` keep the last
+// forward's) and the BatchNorm coefficient tables.  The convs that read the network input get no dx tensor: one launch forms |dx| and
+// reduces it (k_sens_first).
+int Model::input_sensitivity(const float* x_dev, int B) {
+    if (desc.dtype != DNNCA_F32) { set_error("input sensitivity needs a dtype f32 model (this one is bf16)"); return DNNCA_EINVAL; }
+    if (desc.kernel_size > kSensMaxK) { set_error("input sensitivity: kernel_size %d above %d", desc.kernel_size, kSensMaxK); return DNNCA_EINVAL; }
+    sens_pass = true;
+    const int frc = forward(x_dev, B, false);
+    sens_pass = false;
+    DN_TRY(frc);
+    cur_op = nullptr;
+    const bool dense_ok = !(desc.flags & 1);
+    const int C = desc.in_channels, H = desc.height, W = desc.width;
+    if (!sens_descs) {
+        std::vector<SensFirst> hd;
+        for (const Op& o : ops) {
+            if (o.type != OP_CONV || o.need_din) continue;
+            if (o.out.d.ps != o.out.d.C || o.out.g.ps != o.out.d.C || o.inB.d.C || o.out.d.H != H || o.out.d.W != W) {
+                set_error("internal: input sensitivity: %s is not a plain conv of the network input", o.name.c_str());
+                return DNNCA_ESTATE;
+            }
+            const int chan = (int)(o.inA.d.p - xin.d.p);
+            for (int c0 = 0; c0 < o.inA.d.C; c0 += kSensCi)
+                hd.push_back(SensFirst{o.out.g.p, o.out.d.p, p + o.w_off, o.inA.d.C, c0, std::min(kSensCi, o.inA.d.C - c0), o.out.d.C, chan + c0, o.alpha});
+        }
+        if (hd.empty()) { set_error("internal: input sensitivity: no conv reads the network input"); return DNNCA_ESTATE; }
+        const SensFirstGrid g = sens_first_grid(1, H, W, 1);
+        void* dd = nullptr;
+        DN_TRY(alloc(&dd, hd.size() * sizeof(SensFirst)));
+        DN_TRY(alloc((void**)&sens_part, (size_t)desc.max_batch * C * g.ntiles * 8));
+        DN_TRY(alloc((void**)&sens_ticket, (size_t)desc.max_batch * hd.size() * 4));
+        DN_TRY(alloc((void**)&sens_sums, (size_t)desc.max_batch * C * 8));
+        HIP_TRY(hipMemcpyAsync(dd, hd.data(), hd.size() * sizeof(SensFirst), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));          // `hd` is a local
+        sens_descs = dd;
+        sens_nz = (int)hd.size();
+    }
+    DN_TRY(ig_begin_backward(this));          // the dense data-gradient kernels read flipped weights
+    for (int i = (int)ops.size() - 1; i >= 0; --i) {
+        Op& o = ops[i];
+        cur_op = &o.name;
+        switch (o.type) {
+            case OP_HEAD: {
+                const double npix = (double)B * outH * outW;
+                LAUNCH(this, "sens_head", 4.0 * (npix + nelem(B, o.inA.d)), 12.0 * nelem(B, o.inA.d),
+                       g_sens_head(stream, B, outH, outW, dlogits, p + o.w_off, o.inA.g, o.accA));
+                break;
+            }
+            case OP_CONV: {
+                if (!o.need_din) break;          // the first layer: one launch behind the loop
+                const int Cin = o.inA.d.C + o.inB.d.C;
+                const double ob = 4.0 * nelem(B, o.out.d), ib = 4.0 * (nelem(B, o.inA.d) + nelem(B, o.inB.d));
+                const double flops = 2.0 * B * o.out.d.H * o.out.d.W * o.k * o.k * Cin * o.out.d.C;
+                if (o.out.g.h || o.out.d.h) { set_error("internal: input sensitivity met a bf16-stored tensor at %s", o.name.c_str()); return DNNCA_ESTATE; }
+                if (o.alpha >= 0.f)
+                    LAUNCH(this, "g_act_bwd", 3 * ob, ob / 4, g_act_bwd(stream, (size_t)nelem(B, o.out.d), o.out.g.p, o.out.d.p, o.alpha));
+                if (dense_ok && ig_conv_dgrad_only(this, B, o, ob + ib, flops)) break;
+                LAUNCH(this, "g_conv_dgrad", ob + ib, flops,
+                       g_conv_dgrad(stream, B, o.out.g, p + o.w_off, o.inA.g, o.accA, o.inB.g, o.accB, o.k));
+                break;
+            }
+            case OP_BN: {
+                const double tb = 4.0 * nelem(B, o.inA.d);
+                LAUNCH(this, "bn_infer_bwd", (o.accA ? 3 : 2) * tb, tb / 4,
+                       g_bn_infer_bwd(stream, B, o.out.g, o.inA.g, o.accA, p + o.w_off, state + o.mv_off, kBnEps));
+                break;
+            }
+            case OP_POOL: {
+                const double bytes = 4.0 * (2 * nelem(B, o.inA.d) + 2 * nelem(B, o.out.d));
+                LAUNCH(this, "g_pool_bwd", bytes, 0, g_pool_bwd(stream, B, o.inA.d, o.out.d, o.out.g, o.inA.g, o.accA, o.k));
+                break;
+            }
+            case OP_TCONV: {
+                const double ob = 4.0 * nelem(B, o.out.d), ib = 4.0 * nelem(B, o.inA.d);
+                const double flops = 2.0 * nelem(B, o.out.d) * o.inA.d.C;
+                if (dense_ok && ig_tconv_dgrad_only(this, B, o, ob + ib, flops)) break;
+                LAUNCH(this, "g_tconv_dgrad", ob + ib, flops, g_tconv_dgrad(stream, B, o.out.g, p + o.w_off, o.inA.g, o.accA, o.k));
+                break;
+            }
+        }
+    }
+    cur_op = nullptr;
+    const SensFirstGrid g = sens_first_grid(B, H, W, sens_nz);
+    double fb = 0, ff = 0;
+    for (const Op& o : ops)
+        if (o.type == OP_CONV && !o.need_din) {
+            fb += 8.0 * nelem(B, o.out.d);
+            ff += 2.0 * B * H * W * o.k * o.k * o.inA.d.C * o.out.d.C;
+        }
+    LAUNCH(this, "sens_first", fb, ff,
+           g_sens_first(stream, (const SensFirst*)sens_descs, sens_nz, B, H, W, desc.kernel_size, C, g, sens_part, sens_ticket, sens_sums));
     return DNNCA_OK;
 }
 
@@ -1223,6 +1324,18 @@ int dnnca_eval_step(void* model, const float* x_nhwc, const float* y_hw, int bat
     if (prob_out) HIP_TRY(hipMemcpyAsync(prob_out, M->prob, (size_t)batch * M->outH * M->outW * 4, hipMemcpyDeviceToHost, M->stream));
     dnnca_step_out tmp;
     return read_out(M, 1, out ? out : &tmp);         // evaluation is rank-local: the loss slot was not all-reduced
+}
+
+int dnnca_input_sensitivity(void* model, const float* x_nhwc, int batch, double* sums) {
+    MODEL(model);
+    if (!sums) { set_error("null sums"); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
+    if (x_nhwc) DN_TRY(stage_inputs(M, batch, x_nhwc, nullptr, false));
+    else if (M->last_batch != batch) { set_error("input sensitivity without x: the last forward had %d slices, not %d", M->last_batch, batch); return DNNCA_ESTATE; }
+    DN_TRY(M->input_sensitivity(M->x_stage, batch));
+    HIP_TRY(hipMemcpyAsync(sums, M->sens_sums, (size_t)batch * M->desc.in_channels * 8, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return M->flush_profile();
 }
 
 int dnnca_last_step_out(void* model, dnnca_step_out* out) {
@@ -1744,7 +1857,7 @@ int dnnca_debug_launch_cost(void* model, int n, int blocks, float* us_per_launch
 int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap) {
     MODEL(model);
     if (!buf || !cap) return DNNCA_EINVAL;
-    if (pass != DNNCA_PLAN_TRAIN && pass != DNNCA_PLAN_EVAL && pass != DNNCA_PLAN_FORWARD) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
+    if (pass != DNNCA_PLAN_TRAIN && pass != DNNCA_PLAN_EVAL && pass != DNNCA_PLAN_FORWARD && pass != DNNCA_PLAN_SENSITIVITY) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
     DN_TRY(check_batch(M, batch));
     M->plan_text.clear();
     M->dry = true;
@@ -1765,6 +1878,8 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
     } else if (pass == DNNCA_PLAN_EVAL) {
         rc = M->forward(M->x_stage, B, false);
         if (rc == DNNCA_OK) rc = M->loss_and_backward(M->y_stage, B, cfg, false);
+    } else if (pass == DNNCA_PLAN_SENSITIVITY) {
+        rc = M->input_sensitivity(M->x_stage, B);
     } else {
         rc = dnnca_forward_dev(model, M->x_stage, B, 0);
     }

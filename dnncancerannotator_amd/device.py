@@ -489,6 +489,19 @@ class DeviceModel:
                                               out.ctypes.data_as(C.c_void_p), out.nbytes, hwc))
         return out
 
+    def input_sensitivity(self, x=None, batch=None):
+        """float64 [B, C]: sum over the image of |d sum(prob of slice b) / d x[b, :, :, c]| in inference mode (the raw sums of the
+        reference's sensitivity map; casewise.normalise_sensitivity divides each row by its sum).  x [B, H, W, C], or None with
+        `batch`: the slices the last forward(x) left on the device.  dtype f32 models only."""
+        if x is None:
+            B, xp = int(batch), None
+        else:
+            x = self._check_x(x)
+            B, xp = x.shape[0], fptr(x)
+        out = np.empty((B, self.in_shape[2]), np.float64)
+        check(self.lib.dnnca_input_sensitivity(self.handle, xp, B, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
     # ---- device-side augmentation (annotator/data.py:62-111 train_ds) ------------------------------------------
     def augment_u8(self, raw, params, out_size, label_index, contrast_channels=None, src_ptr=None):
         """raw uint8 [B, Hs, Ws, Cs] (host) + per-image draws [(dy, dx, flip, contrast)] -> device-resident (x [B, Ho, Wo, Cs-1],
@@ -619,11 +632,12 @@ class DeviceModel:
             out.append((name.value.decode(), n.value, ms.value, by.value, fl.value))
         return out
 
-    PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2}
+    PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3}
 
     def plan(self, variants=False, mode='train', batch=None):
         """The launch schedule of one pass: [(kernel, algorithmic bytes, flops)].  mode 'train': one train step; 'eval': one
-        eval_step (inference forward + loss; a staged evaluation step launches the same); 'forward': forward(training=False).
+        eval_step (inference forward + loss; a staged evaluation step launches the same); 'forward': forward(training=False);
+        'sensitivity': input_sensitivity.
         batch: None = max_batch.  variants: keep the template variant the library appends to a launch name
         (`ig_conv_fwd#3n2w8`): the kernel-coverage test tells them apart.  A dry run: the model is unchanged."""
         if mode not in self.PLAN_PASSES:

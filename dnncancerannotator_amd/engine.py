@@ -561,8 +561,6 @@ class TFKerasModel:
         else:
             assert len(step_range) == 2
             assert 0 <= step_range[0] <= step_range[1]
-        if visualize_sensitivity:
-            logging.warning('visualize_sensitivity is outside the accelerated path: ignored')
         # the Visualizer (engine.py:171-183, callbacks.py): casewise counts and images of viz_ds after each checkpoint's evaluation,
         # on rank 0 alone over the whole of viz_ds (data parallel: the other ranks skip it)
         visualize = viz_ds is not None and (export_csv or export_images) and self.ctx.rank == 0
@@ -581,7 +579,8 @@ class TFKerasModel:
             self.load(ckpt_path_)
             rows[ckpt_step] = self._evaluate(dataset, staged=True)
             if visualize:
-                self._visualize(viz_ds, ckpt_step, viz_root, export_csv, export_images, overlay, casewise_rows, writer)
+                self._visualize(viz_ds, ckpt_step, viz_root, export_csv, export_images, overlay, casewise_rows, writer,
+                                sensitivity=bool(visualize_sensitivity))
         if writer is not None:
             writer.close()
         if export_csv and self.ctx.rank == 0:
@@ -596,11 +595,12 @@ class TFKerasModel:
                     f.write(casewise.table_csv(casewise.column_names(), casewise_rows))
         return rows
 
-    def _visualize(self, viz_ds, step, root, export_csv, export_images, overlay, casewise_rows, writer):
+    def _visualize(self, viz_ds, step, root, export_csv, export_images, overlay, casewise_rows, writer, sensitivity=False):
         """One Visualizer pass (callbacks.py process_batch / _emit) over viz_ds batches (x, y, paths, sliceIDs): forward
         (training=False), the per-slice region counts (export_csv), the composite images (export_images), then the files.  The
         probabilities stay on the device; only the counts and the uint8 images come back.  casewise_rows gains one row per slice,
-        in dataset order."""
+        in dataset order.  sensitivity (--visualize_sensitivity, callbacks.py:290-313): the input-gradient pass on the slices the
+        forward left on the device; per slice a CSV (export_csv) and a bar chart (export_images) of the normalised channel sums."""
         spec = casewise.device_spec()
         names = casewise.column_names()
         for x, y, paths, ids in viz_ds:
@@ -624,6 +624,15 @@ class TFKerasModel:
                     images = dm.render_composite(None if export_csv else yb, len(xb), casewise.RATIO, overlay)
                     for t, im in zip(tags, images):
                         writer.submit(casewise.image_path(root, t, step), casewise.encode_png, im)
+                if sensitivity:
+                    sens = casewise.normalise_sensitivity(dm.input_sensitivity(batch=len(xb)))
+                    mods = casewise.modality_names(getattr(viz_ds, 'slice_types', None), sens.shape[1])
+                    for t, row in zip(tags, sens):
+                        if export_csv:
+                            writer.submit(casewise.sensitivity_path(root, t, step, 'csv'), casewise.sensitivity_csv, mods, row)
+                        if export_images:
+                            writer.submit(casewise.sensitivity_path(root, t, step, 'images'),
+                                          lambda r: casewise.encode_png(casewise.sensitivity_chart(r)), row)
 
     def predict(self, dataset):
         """Probabilities [N, H, W, 1] for every element of `dataset` (elements are x or (x, ...))."""

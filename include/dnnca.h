@@ -281,6 +281,18 @@ int dnnca_region_confusion_slices(void* model, const float* prob_hw, const float
 int dnnca_render_composite(void* model, const float* y_hw, int batch, float ratio, int overlay, uint8_t* out, int64_t capacity,
                            int32_t* out_hwc);
 
+/* ---- channel sensitivity of `annotator evaluate --visualize_sensitivity` (utils/callbacks.py:290-313) ---------------------------
+ * With the model in inference mode (BatchNorm on its moving statistics, sigmoid output):
+ *     sums[b * in_channels + c] = sum over H, W of | d (sum of all probabilities of slice b) / d x[b, h, w, c] |
+ * The caller normalises a slice's row by its sum (an all-zero row gives the reference's 0 / 0 = NaN).  x_nhwc: host [batch, H, W,
+ * in_channels], or NULL for the batch the last dnnca_forward of the same size left on the device.  One inference forward that keeps
+ * every tensor plus the data gradients alone: no weight gradient, no optimizer step; variables, optimizer slots, BatchNorm state,
+ * the iteration count and the probabilities / logits of the last forward are untouched (the gradient vector and the tensors'
+ * gradient views are scratch, as between any two train steps).  The sums are float64 and bit-identical from run to run.
+ * dtype f32 models only: a DNNCA_BF16 model returns DNNCA_EINVAL; so do a batch outside [1, max_batch] and sums == NULL.
+ * Synchronises. */
+int dnnca_input_sensitivity(void* model, const float* x_nhwc, int batch, double* sums /* [batch * in_channels] */);
+
 /* ---- data parallel: tf.distribute.MirroredStrategy (engine.py:260-263) re-done as one process per GPU + RCCL ---- */
 int dnnca_comm_unique_id(void* id_out /* DNNCA_UNIQUE_ID_BYTES */);
 int dnnca_comm_init(void* model, int rank, int world, const void* unique_id, size_t id_len);   /* world == 1: no-op */
@@ -310,8 +322,8 @@ int dnnca_profile_get(void* model, int index, char* name, size_t name_cap, int64
 int dnnca_plan_dump(void* model, char* buf, size_t cap);
 /* the same for one pass at one batch size in [1, max_batch]: the train step (dnnca_plan_dump is this at max_batch), an evaluation
    step (dnnca_eval_step / dnnca_eval_step_staged: inference forward + loss), or a prediction (dnnca_forward with training = 0:
-   inference forward + sigmoid).  A dry run: nothing is launched and the model is left as it was. */
-enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2 };
+   inference forward + sigmoid), or dnnca_input_sensitivity.  A dry run: nothing is launched and the model is left as it was. */
+enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2, DNNCA_PLAN_SENSITIVITY = 3 };
 int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap);
 
 #ifdef __cplusplus
