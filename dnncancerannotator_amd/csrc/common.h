@@ -46,6 +46,8 @@ __device__ __forceinline__ hbf16x4 to_bf16x4(const float4& v) {
     return r;
 }
 
+inline bool dense(const View& v) { return v.C == 0 || v.ps == v.C; }      // no channel slice of a wider buffer (or no tensor at all)
+
 inline View slice(const View& v, int c0, int c) {
     View o = v;
     o.p = v.p + c0;

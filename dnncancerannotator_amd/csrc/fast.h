@@ -62,7 +62,7 @@ void fast_plan_masks(Model* m);
 // BatchNorm apply passes are elided, which tensors are stored as bf16) and every later launch decision must see the same values -- a
 // conv must never read a normalised tensor that was never written.  Deliberately NOT here, because tests flip them in-process:
 // DNNCA_NO_HALF, _NO_HALF_Z, _NO_HALF_DY (read when a model is built, ig_plan_half) and DNNCA_FOLD_BATCH (read per step, ig_prepare).
-// (The unet.yaml fusion switches are read per call: each of those paths falls back on the launches it replaced.)
+// (The switches of the small-channel step are per MODEL: StepSwitches, model.h.)
 struct DenseSwitches {
     // first-generation kernels (the fallbacks beyond the 32-bit offset limits)
     bool igconv1, wgrad1, tcwgrad1, tconv_fwd1;
@@ -127,6 +127,18 @@ inline int pixel_split(int combos, int ntiles, int blocks = 256) {  // pixel-spl
 inline bool eight_waves(int B, int H, int W, int channel_tiles) {
     const long units8 = (long)((W + 15) / 16) * ((H + 31) / 32) * B * channel_tiles;
     return units8 >= 256;
+}
+// Grid of a persistent kernel of the small-channel step: one block per work item, at most the blocks that are resident at once on
+// the 256 CUs -- what the occupancy calculator allows per CU, capped at per_cu_cap.  The calculator is asked once per kernel; the
+// cap is applied per call (it may come from a model's switches).
+template <auto Kernel, int Threads>
+inline int resident_grid(int per_cu_cap, int items) {
+    static const int occupancy = [] {
+        int n = 0;
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, Kernel, Threads, 0) == hipSuccess && n >= 1 ? n : 1;
+    }();
+    const int fit = 256 * (occupancy < per_cu_cap ? occupancy : per_cu_cap);
+    return items < fit ? items : fit;
 }
 // implicit-GEMM MFMA path for channel counts that are multiples of 16 (kernels_igemm.hip)
 bool ig_conv_supported(const Model* m, const Op& o);

@@ -471,33 +471,18 @@ __global__ __launch_bounds__(NT, MINW) void k_fz_up(UpArgs p) {
 // ================================================================================================ host side
 const float* fast_conv_bmat(Model* m, const Op& o);       // kernels_mfma.hip: prepared forward B operand of a pixel-group conv
 
-static inline bool dense(const View& v) { return v.C == 0 || v.ps == v.C; }
 
-template <typename K>
-static int fz_resident(K kernel, int nt) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nt, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    if (per_cu > 6) per_cu = 6;
-    return 256 * per_cu;
-}
+constexpr int kFzPerCu = 6;      // resident blocks per CU that the persistent grids of this file count on, at most
 
-static bool fz_enabled() {
-    static const bool on = getenv("DNNCA_NO_FUSED") == nullptr;
-    return on;
-}
 // tuning aid: DNNCA_FZ_ONLY=down0|down1|down2|up0|up1|up2 fuses only that block (level = log2(512 / block height) at 512 x 512)
-static bool fz_selected(const char* kind, int level) {
-    const char* e = getenv("DNNCA_FZ_ONLY");
-    if (!e) return true;
-    char want[16];
-    snprintf(want, sizeof(want), "%s%d", kind, level);
-    return strcmp(e, want) == 0;
+static bool fz_selected(const Model* m, const char* kind, int level) {
+    return m->sw.fz_only.empty() || m->sw.fz_only == kind + std::to_string(level);
 }
 
 // ops[oi .. oi+2] = conv3x3(CIN -> C1), conv3x3(C1 -> C1), MaxPool2D(2) of one Downsample block without BatchNorm?
 // Launches the fused kernel and returns true; false: not this shape (the caller runs the layers one by one).
 bool fused_down_fwd(Model* m, int B, size_t oi, bool store_mid, const float* labels) {
-    if (!fz_enabled() || (m->desc.flags & 1) || m->desc.dtype != DNNCA_F32) return false;
+    if (m->sw.no_fused || (m->desc.flags & 1) || m->desc.dtype != DNNCA_F32) return false;
     if (oi + 2 >= m->ops.size()) return false;
     Op &c1 = m->ops[oi], &c2 = m->ops[oi + 1], &pl = m->ops[oi + 2];
     if (c1.type != OP_CONV || c2.type != OP_CONV || pl.type != OP_POOL || c1.k != 3 || c2.k != 3 || pl.k != 2) return false;
@@ -505,7 +490,7 @@ bool fused_down_fwd(Model* m, int B, size_t oi, bool store_mid, const float* lab
     if (!dense(c1.inA.d) || !dense(c1.out.d) || !dense(c2.out.d) || !dense(pl.out.d)) return false;
     const int CIN = c1.inA.d.C, C1 = c1.out.d.C, H = c1.out.d.H, W = c1.out.d.W;
     if (c2.out.d.C != C1) return false;
-    if (!fz_selected("down", C1 == 3 ? 0 : (C1 == 6 ? 1 : 2))) return false;
+    if (!fz_selected(m, "down", C1 == 3 ? 0 : (C1 == 6 ? 1 : 2))) return false;
     const float *b1 = fast_conv_bmat(m, c1), *b2 = fast_conv_bmat(m, c2);
     if (!b1 || !b2) return false;
     fz::DownArgs a{};
@@ -545,18 +530,13 @@ bool fused_down_fwd(Model* m, int B, size_t oi, bool store_mid, const float* lab
     if (CIN == cin && C1 == c1v && W % tw == 0 && H % th == 0) {                                                  \
         a.tiles_x = W / tw; a.tiles_y = H / th;                                                                   \
         const int ntiles = a.tiles_x * a.tiles_y * B;                                                             \
-        static const int fit = fz_resident(fz::k_fz_down<cin, c1v, tw, th, nt, mw>, nt);                            \
-        const int g = ntiles < fit ? ntiles : fit;                                                                \
+        const int g = resident_grid<fz::k_fz_down<cin, c1v, tw, th, nt, mw>, nt>(kFzPerCu, ntiles);                 \
         if (labels && (g > 2048 || W != c1.out.d.W)) return false;                                                \
         LAUNCH(m, "fz_down_" #cin "_" #c1v, bytes, flops,                                                         \
                hipLaunchKernelGGL((fz::k_fz_down<cin, c1v, tw, th, nt, mw>), dim3(g), dim3(nt), 0, m->stream, a));   \
         if (labels) { m->label_part_valid = true; m->label_part_nblk = g; }                                       \
         pl.pool_idx_valid = store_mid && (m->dry || a.pool_idx != nullptr);                                       \
         return true;                                                                                              \
-    }
-    static const int alt = getenv("DNNCA_FZ_NT") ? atoi(getenv("DNNCA_FZ_NT")) : 0;      // tuning aid
-    if (alt == 256) {
-        X(1, 3, 128, 8, 256, 2) X(3, 6, 64, 8, 256, 2) X(6, 12, 32, 8, 256, 2)
     }
     X(1, 3, 128, 8, 512, 4) X(3, 6, 64, 8, 512, 4) X(6, 12, 32, 8, 512, 4)
 #undef X
@@ -566,7 +546,7 @@ bool fused_down_fwd(Model* m, int B, size_t oi, bool store_mid, const float* lab
 // ops[oi .. oi+2] = Conv2DTranspose(CIN -> F, 2x2/2), conv3x3([up | skip] -> F), conv3x3(F -> F) of one Upsample block without BatchNorm?
 bool fused_up_fwd(Model* m, int B, size_t oi, bool store_mid, int* consumed) {
     if (consumed) *consumed = 3;
-    if (!fz_enabled() || (m->desc.flags & 1) || m->desc.dtype != DNNCA_F32) return false;
+    if (m->sw.no_fused || (m->desc.flags & 1) || m->desc.dtype != DNNCA_F32) return false;
     if (oi + 2 >= m->ops.size()) return false;
     Op &tc = m->ops[oi], &c0 = m->ops[oi + 1], &c1 = m->ops[oi + 2];
     if (tc.type != OP_TCONV || c0.type != OP_CONV || c1.type != OP_CONV || tc.k != 2 || c0.k != 3 || c1.k != 3) return false;
@@ -574,12 +554,11 @@ bool fused_up_fwd(Model* m, int B, size_t oi, bool store_mid, int* consumed) {
     if (!dense(tc.inA.d) || !dense(tc.out.d) || !dense(c0.inB.d) || !dense(c0.out.d) || !dense(c1.out.d)) return false;
     const int CIN = tc.inA.d.C, F = tc.out.d.C, H = tc.out.d.H, W = tc.out.d.W;
     if (c0.inB.d.C != F || c0.out.d.C != F || c1.out.d.C != F || c0.inB.d.H != H || c0.inB.d.W != W) return false;
-    if (!fz_selected("up", F == 3 ? 0 : (F == 6 ? 1 : 2))) return false;
+    if (!fz_selected(m, "up", F == 3 ? 0 : (F == 6 ? 1 : 2))) return false;
     // measured on MI355X (tools/fz_ab.py, profiles/r02_fused_ab.txt): the fused decoder block beats its three per-layer launches
     // only at 128^2 (12 channels); at 256^2 / 512^2 the block is bound by the fp32 matrix pipe (two 3x3 convs on a halo-enlarged
     // tile) and the per-layer kernels, which overlap it better with their memory traffic, stay ahead.  DNNCA_FZ_ALL=1 fuses all.
-    static const bool all = getenv("DNNCA_FZ_ALL") != nullptr || getenv("DNNCA_FZ_ONLY") != nullptr;
-    if (!all && F != 12) return false;
+    if (F != 12 && !m->sw.fz_all && m->sw.fz_only.empty()) return false;
     const float *b0 = fast_conv_bmat(m, c0), *b1 = fast_conv_bmat(m, c1);
     if (!b0 || !b1) return false;
     fz::UpArgs a{};
@@ -595,7 +574,7 @@ bool fused_up_fwd(Model* m, int B, size_t oi, bool store_mid, int* consumed) {
     double bytes = 4.0 * B * H * W * (0.25 * CIN + F + 2 * F + F + F + F);        // tconv (in + out) + conv0 (2 in + out) + conv1 (in + out)
     double flops = 2.0 * B * H * W * (F * CIN + 9.0 * (2 * F * F + F * F));
     // the next block's Conv2DTranspose(12 -> 6) rides in the epilogue (its input is c1's output tile, still in LDS)
-    if (!getenv("DNNCA_NO_TCONV_RIDE") && consumed && CIN == 12 && F == 12 && W % 32 == 0 && H % 8 == 0 && oi + 3 < m->ops.size()) {
+    if (!m->sw.no_tconv_ride && consumed && CIN == 12 && F == 12 && W % 32 == 0 && H % 8 == 0 && oi + 3 < m->ops.size()) {
         Op& nt2 = m->ops[oi + 3];
         if (nt2.type == OP_TCONV && nt2.k == 2 && nt2.inA.d.p == c1.out.d.p && nt2.inA.d.C == 12 && nt2.out.d.C == 6 && dense(nt2.inA.d) &&
             dense(nt2.out.d) && nt2.out.d.H == 2 * H && nt2.out.d.W == 2 * W) {
@@ -604,8 +583,7 @@ bool fused_up_fwd(Model* m, int B, size_t oi, bool store_mid, int* consumed) {
             bytes += 4.0 * B * H * W * (F + 4 * 6);
             flops += 2.0 * B * H * W * 4 * 6 * F;
             const int ntiles = a.tiles_x * a.tiles_y * B;
-            static const int fit = fz_resident(fz::k_fz_up<12, 12, 32, 8, 512, 2, 6>, 512);
-            const int g = ntiles < fit ? ntiles : fit;
+            const int g = resident_grid<fz::k_fz_up<12, 12, 32, 8, 512, 2, 6>, 512>(kFzPerCu, ntiles);
             LAUNCH(m, "fz_up_tc_12_12", bytes, flops,
                    hipLaunchKernelGGL((fz::k_fz_up<12, 12, 32, 8, 512, 2, 6>), dim3(g), dim3(512), 0, m->stream, a));
             *consumed = 4;
@@ -616,15 +594,10 @@ bool fused_up_fwd(Model* m, int B, size_t oi, bool store_mid, int* consumed) {
     if (CIN == cin && F == f && W % tw == 0 && H % th == 0) {                                                     \
         a.tiles_x = W / tw; a.tiles_y = H / th;                                                                   \
         const int ntiles = a.tiles_x * a.tiles_y * B;                                                             \
-        static const int fit = fz_resident(fz::k_fz_up<cin, f, tw, th, nt, mw>, nt);                                \
-        const int g = ntiles < fit ? ntiles : fit;                                                                \
+        const int g = resident_grid<fz::k_fz_up<cin, f, tw, th, nt, mw>, nt>(kFzPerCu, ntiles);                     \
         LAUNCH(m, "fz_up_" #cin "_" #f, bytes, flops,                                                             \
                hipLaunchKernelGGL((fz::k_fz_up<cin, f, tw, th, nt, mw>), dim3(g), dim3(nt), 0, m->stream, a));       \
         return true;                                                                                              \
-    }
-    static const int alt = getenv("DNNCA_FZ_NT") ? atoi(getenv("DNNCA_FZ_NT")) : 0;      // tuning aid
-    if (alt == 256) {
-        X(12, 12, 32, 8, 256, 2) X(12, 6, 64, 8, 256, 2) X(6, 3, 128, 8, 256, 2)
     }
     X(12, 12, 32, 8, 512, 2) X(12, 6, 64, 8, 512, 2) X(6, 3, 128, 8, 512, 4)
 #undef X
@@ -637,8 +610,8 @@ bool fused_up2_fwd(Model* m, int B, size_t oi, bool store_mid) {
     // OFF by default.  Measured on MI355X (round 4, bench.py --steps 50, same box): fz_up2_6 34.4 us against pgfwd_6x2_6 + pgfwd_6x1_6
     // 21.5 + 14.3 us under event brackets, the step 0.4059 ms (14 launches) against 0.4034 ms (15): the launch it saves is paid back by
     // the halo recompute of conv0 on the fp32 matrix pipe (+29 % MFMAs on a 64 x 8 tile), as round 2 found for the whole block.
-    // DNNCA_FZ_UP2=1 enables it (read per call: the test flips it).
-    if (!getenv("DNNCA_FZ_UP2") || !fz_enabled() || (m->desc.flags & 1) || m->desc.dtype != DNNCA_F32) return false;
+    // DNNCA_FZ_UP2=1 enables it.
+    if (!m->sw.fz_up2 || m->sw.no_fused || (m->desc.flags & 1) || m->desc.dtype != DNNCA_F32) return false;
     if (oi + 1 >= m->ops.size()) return false;
     Op &c0 = m->ops[oi], &c1 = m->ops[oi + 1];
     if (c0.type != OP_CONV || c1.type != OP_CONV || c0.k != 3 || c1.k != 3) return false;
@@ -662,8 +635,7 @@ bool fused_up2_fwd(Model* m, int B, size_t oi, bool store_mid) {
     const double bytes = 4.0 * B * H * W * (2 * F + F + F + F);        // conv0 (2 in + out) + conv1 (in + out)
     const double flops = 2.0 * B * H * W * 9.0 * (2 * F * F + F * F);
     const int ntiles = a.tiles_x * a.tiles_y * B;
-    static const int fit = fz_resident(fz::k_fz_up<12, 6, 64, 8, 512, 2, 0, true>, 512);
-    const int g = ntiles < fit ? ntiles : fit;
+    const int g = resident_grid<fz::k_fz_up<12, 6, 64, 8, 512, 2, 0, true>, 512>(kFzPerCu, ntiles);
     LAUNCH(m, "fz_up2_6", bytes, flops, hipLaunchKernelGGL((fz::k_fz_up<12, 6, 64, 8, 512, 2, 0, true>), dim3(g), dim3(512), 0, m->stream, a));
     return true;
 }

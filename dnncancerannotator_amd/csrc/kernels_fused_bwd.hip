@@ -654,30 +654,18 @@ __global__ __launch_bounds__(NT, 1) void k_fzb(BArgs p) {
 }  // namespace fzb
 
 // ================================================================================================ host side
-static inline bool dense(const View& v) { return v.C == 0 || v.ps == v.C; }
 
-static bool fzb_enabled() { return getenv("DNNCA_NO_FUSED_BWD") == nullptr; }      // read per call: the tests flip it
+constexpr int kFzbPerCu = 2;     // resident blocks per CU that the persistent grids of this file count on, at most
+
 // tuning aid: DNNCA_FZB_ONLY=down1|down2|up0|up1 fuses only that block's backward (the number is the level: log2(512 / height) at 512 x 512)
-static bool fzb_selected(const char* kind, int F) {
-    const char* e = getenv("DNNCA_FZB_ONLY");
-    if (!e) return true;
-    char want[16];
-    snprintf(want, sizeof(want), "%s%d", kind, F == 6 ? 1 : 2);
-    return strcmp(e, want) == 0;
-}
-
-template <typename K>
-static int fzb_grid(K kernel, int nt, int ntiles) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nt, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    const int fit = 256 * (per_cu > 2 ? 2 : per_cu);
-    return ntiles < fit ? ntiles : fit;
+static bool fzb_selected(const Model* m, const char* kind, int F) {
+    return m->sw.fzb_only.empty() || m->sw.fzb_only == kind + std::to_string(F == 6 ? 1 : 2);
 }
 
 // ops[oi - 2 .. oi] = Conv2DTranspose(12 -> F, 2x2/2), conv3x3([up | skip] -> F), conv3x3(F -> F) of one Upsample block (no BatchNorm):
 // the block's whole backward in one launch.  false: not this shape / these flags (the caller runs the layers one by one).
 bool fused_up_bwd(Model* m, int B, size_t oi) {
-    if (!fzb_enabled() || (m->desc.flags & 1) || m->desc.dtype != DNNCA_F32 || oi < 2 || oi >= m->ops.size()) return false;
+    if (m->sw.no_fused_bwd || (m->desc.flags & 1) || m->desc.dtype != DNNCA_F32 || oi < 2 || oi >= m->ops.size()) return false;
     Op &tc = m->ops[oi - 2], &c0 = m->ops[oi - 1], &c1 = m->ops[oi];
     if (tc.type != OP_TCONV || c0.type != OP_CONV || c1.type != OP_CONV || tc.k != 2 || c0.k != 3 || c1.k != 3) return false;
     if (!fast_pg_conv_supported(m, c0) || !fast_pg_conv_supported(m, c1) || !fast_tconv_supported(m, tc)) return false;
@@ -693,7 +681,7 @@ bool fused_up_bwd(Model* m, int B, size_t oi) {
     if (c1.alpha >= 0.f && !c1.premasked) return false;
     if (!c1.need_din || !c0.need_din || c1.accA || c0.accA || c0.accB || c0.maskA || c0.maskB || tc.accA) return false;
     if ((c0.alpha >= 0.f) != (c1.maskA != 0) || (c0.alpha >= 0.f && !c0.premasked)) return false;
-    if (!fzb_selected("up", F)) return false;
+    if (!fzb_selected(m, "up", F)) return false;
     fzb::BArgs a{};
     a.dz1 = c1.out.g.p;
     a.y0 = c0.out.d.p;
@@ -708,7 +696,7 @@ bool fused_up_bwd(Model* m, int B, size_t oi) {
     if (!a.bm1 || !a.bm0 || !a.slabs1 || !a.slabs0[0] || !a.slabs0[1] || !a.tc_slabs) return false;
     a.B = B; a.H = H; a.W = W;
     a.tiles_x = W / TW; a.tiles_y = H / 8;
-    if (const char* e = getenv("DNNCA_FZB_DBG")) a.dbg = atoi(e);
+    a.dbg = m->sw.fzb_dbg;
     const int ntiles = a.tiles_x * a.tiles_y * B;
     const double npx = (double)B * H * W;
     // algorithmic bytes / FLOPs of the three layers' backward (out-gradient + 2 x inputs per layer)
@@ -716,7 +704,7 @@ bool fused_up_bwd(Model* m, int B, size_t oi) {
     const double flops = 2.0 * (2.0 * npx * 9.0 * (F * F + 2 * F * F)) + 2.0 * (2.0 * npx * F * 12);
 #define X(f, tw)                                                                                                   \
     if (F == f) {                                                                                                  \
-        const int g = fzb_grid(fzb::k_fzb<true, f, f, tw, 512>, 512, ntiles);                                      \
+        const int g = resident_grid<fzb::k_fzb<true, f, f, tw, 512>, 512>(kFzbPerCu, ntiles);                      \
         if (a.dbg & 2) {        /* tuning aid: the same launch first without its slab atomics (what does a warm start look like?) */ \
             fzb::BArgs a2 = a;                                                                                     \
             a2.dbg |= 1;                                                                                           \
@@ -735,7 +723,7 @@ bool fused_up_bwd(Model* m, int B, size_t oi) {
 // ops[oi - 2 .. oi] = conv3x3(CA -> F), conv3x3(F -> F), MaxPool2D(2) of one Downsample block (no BatchNorm) whose forward pass
 // recorded the pool's window positions (k_fz_down): pool backward + both convs' backward in one launch.
 bool fused_down_bwd(Model* m, int B, size_t oi) {
-    if (!fzb_enabled() || (m->desc.flags & 1) || m->desc.dtype != DNNCA_F32 || oi < 2 || oi >= m->ops.size()) return false;
+    if (m->sw.no_fused_bwd || (m->desc.flags & 1) || m->desc.dtype != DNNCA_F32 || oi < 2 || oi >= m->ops.size()) return false;
     Op &c1 = m->ops[oi - 2], &c2 = m->ops[oi - 1], &pl = m->ops[oi];
     if (c1.type != OP_CONV || c2.type != OP_CONV || pl.type != OP_POOL || c1.k != 3 || c2.k != 3 || pl.k != 2) return false;
     if (!fast_pg_conv_supported(m, c1) || !fast_pg_conv_supported(m, c2)) return false;
@@ -749,7 +737,7 @@ bool fused_down_bwd(Model* m, int B, size_t oi) {
     if (!pl.pool_idx_valid || !(pl.pool_idx || m->dry) || !pl.accA || !pl.maskA || pl.mask_alpha != 0.f || !c2.premasked) return false;
     if (!c1.need_din || !c2.need_din || c1.accA || c1.maskA || c2.accA) return false;
     if ((c1.alpha >= 0.f) != (c2.maskA != 0) || (c1.alpha >= 0.f && !c1.premasked)) return false;
-    if (!fzb_selected("down", F)) return false;
+    if (!fzb_selected(m, "down", F)) return false;
     fzb::BArgs a{};
     a.dz1 = c2.out.g.p;
     a.y1 = c2.out.d.p;
@@ -764,7 +752,7 @@ bool fused_down_bwd(Model* m, int B, size_t oi) {
     if (!a.bm1 || !a.bm0 || !a.slabs1 || !a.slabs0[0]) return false;
     a.B = B; a.H = H; a.W = W;
     a.tiles_x = W / TW; a.tiles_y = H / 8;
-    if (const char* e = getenv("DNNCA_FZB_DBG")) a.dbg = atoi(e);
+    a.dbg = m->sw.fzb_dbg;
     const int ntiles = a.tiles_x * a.tiles_y * B;
     const double npx = (double)B * H * W;
     // pool backward (y, dy in; dx in/out; pooled gradient), second conv backward, first conv backward
@@ -773,7 +761,7 @@ bool fused_down_bwd(Model* m, int B, size_t oi) {
     pl.pool_idx_valid = false;
 #define X(ca, f, tw)                                                                                               \
     if (CA == ca && F == f) {                                                                                      \
-        const int g = fzb_grid(fzb::k_fzb<false, ca, f, tw, 512>, 512, ntiles);                                    \
+        const int g = resident_grid<fzb::k_fzb<false, ca, f, tw, 512>, 512>(kFzbPerCu, ntiles);                    \
         LAUNCH(m, "fzb_down_" #ca "_" #f, bytes, flops,                                                            \
                hipLaunchKernelGGL((fzb::k_fzb<false, ca, f, tw, 512>), dim3(g), dim3(512), 0, m->stream, a));      \
         return true;                                                                                               \

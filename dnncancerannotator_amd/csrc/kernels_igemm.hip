@@ -2735,7 +2735,6 @@ const DenseSwitches& dense_switches() {
     return sw;
 }
 
-static inline bool dense(const View& v) { return v.C == 0 || v.ps == v.C; }
 
 bool ig_conv_supported(const Model* m, const Op& o) {
     if (o.type != OP_CONV || o.k != 3) return false;

@@ -131,15 +131,14 @@ __device__ __forceinline__ float* fwd_prob(const FwdArgs&) { return nullptr; }
 __device__ __forceinline__ float* fwd_prob(const FwdProbArgs& a) { return a.hprob; }
 
 // PROB (HEAD only): the epilogue also stores each pixel's sigmoid into p.hprob; the arithmetic is the same
-template <int C, int NSRC, int CO, int NT, bool DB, bool HEAD = false, bool PROB = false>
+template <int C, int NSRC, int CO, int NT, bool HEAD = false, bool PROB = false>
 __global__ __launch_bounds__(NT) void k_pgfwd(std::conditional_t<PROB, FwdProbArgs, FwdArgs> p) {
     constexpr int G = 12 / CO, TX = 2, TW = 16 * G * TX, N = G * CO, NW = NT / 64;
     using T = TG<C, TW>;
     constexpr int WR = (G + 2) * C, SR = (WR + 3) / 4, KS = NSRC * 3 * SR, LS = T::LS;
-    // DB: two stage buffers -> the next tile is committed while other waves still read the current one, one barrier per tile
-    constexpr int STAGE4 = NSRC * T::N4, NBUF = DB ? 2 : 1;
-    __shared__ float4 lds4[NBUF * STAGE4 + NW * 96];   // staged tiles + two 16x12 output rows per wave
-    float* orow = reinterpret_cast<float*>(lds4 + NBUF * STAGE4) + (threadIdx.x >> 6) * 384;
+    constexpr int STAGE4 = NSRC * T::N4;
+    __shared__ float4 lds4[STAGE4 + NW * 96];   // staged tiles + two 16x12 output rows per wave
+    float* orow = reinterpret_cast<float*>(lds4 + STAGE4) + (threadIdx.x >> 6) * 384;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int m = lane & 15, q = lane >> 4, n = m;
@@ -235,22 +234,14 @@ __global__ __launch_bounds__(NT) void k_pgfwd(std::conditional_t<PROB, FwdProbAr
     }
     if constexpr (!HEAD) drain_breg();
 
-    int buf = 0;
-    if (DB && tile < ntiles) {
-#pragma unroll
-        for (int s = 0; s < NSRC; ++s) tile_commit<C, TW, NT>(pre[s], okm, lds4 + s * T::N4, tid);
-        lds_barrier();
-    }
 #pragma unroll 1
     while (tile < ntiles) {
         int b, x0, y0;
         decode(tile, b, x0, y0);
-        if (!DB) {
 #pragma unroll
-            for (int s = 0; s < NSRC; ++s) tile_commit<C, TW, NT>(pre[s], okm, lds4 + s * T::N4, tid);
-            lds_barrier();
-        }
-        const float* lds = reinterpret_cast<const float*>(lds4 + buf * STAGE4);
+        for (int s = 0; s < NSRC; ++s) tile_commit<C, TW, NT>(pre[s], okm, lds4 + s * T::N4, tid);
+        lds_barrier();
+        const float* lds = reinterpret_cast<const float*>(lds4);
         // HEAD: this tile's labels are loaded BEFORE the next tile's prefetch is issued: vmcnt retires in order, so a label load
         // behind the prefetch would make the epilogue wait for the whole prefetch (an HBM round trip per tile)
         float zlab[2] = {0.f, 0.f};
@@ -367,13 +358,6 @@ __global__ __launch_bounds__(NT) void k_pgfwd(std::conditional_t<PROB, FwdProbAr
                 }
             }
             __builtin_amdgcn_wave_barrier();
-        }
-        if (DB) {
-            if (next < ntiles) {
-#pragma unroll
-                for (int s = 0; s < NSRC; ++s) tile_commit<C, TW, NT>(pre[s], okm, lds4 + (buf ^ 1) * STAGE4 + s * T::N4, tid);
-            }
-            buf ^= 1;
         }
         lds_barrier();
         tile = next;
@@ -498,12 +482,12 @@ __device__ __forceinline__ int slab_index(int mrow, int n);
 //   T2  dW[(a,e,co)][ci] += sum_pixels dup[..](a,e,co) * in[i][j][ci]         M = (a, e, co), N = ci (+ an all-ones column: the bias
 //       gradient), K = the tile's input pixels, split over the waves; the accumulators live across tiles and leave through the
 //       transposed conv's slabs in the D layout k_pg_fold expects (kind 1) -- the layout k_tconv_bwd leaves there.
-template <int C, int NSRC, int CO, bool DGRAD, int NT, bool DB, bool VW = false, bool PF = false, bool TCF = false, bool TCM = false>
+template <int C, int NSRC, int CO, bool DGRAD, int NT, bool VW = false, bool PF = false, bool TCF = false, bool TCM = false>
 __global__ __launch_bounds__(NT, (VW && NSRC == 1) ? 4 : 1) void k_pgbwd(BwdArgs p) {
     constexpr int NW = NT / 64;
     static_assert(!TCF || (VW && NSRC == 2 && C == 3 && CO == 3), "TCF rides in the two-source 3-channel VW kernel");
-    static_assert(!TCM || (!VW && !PF && !DB && !TCF && NSRC == 2 && DGRAD && C == CO && (C == 6 || C == 12)), "TCM: two-source C -> C conv");
-    static_assert(!PF || (NSRC == 1 && C == CO && DGRAD && !VW && !DB), "PF: single-source C -> C conv with data gradient");
+    static_assert(!TCM || (!VW && !PF && !TCF && NSRC == 2 && DGRAD && C == CO && (C == 6 || C == 12)), "TCM: two-source C -> C conv");
+    static_assert(!PF || (NSRC == 1 && C == CO && DGRAD && !VW), "PF: single-source C -> C conv with data gradient");
     static_assert(!VW || (C == 3 && CO == 3 && NT == 512 && DGRAD), "VW: 3 -> 3 channels, eight waves, with data gradient");
     constexpr int NWD = VW ? NW / 2 : NW;          // waves that run the data gradient
     using Wc = BW<C, NSRC, CO>;
@@ -512,9 +496,7 @@ __global__ __launch_bounds__(NT, (VW && NSRC == 1) ? 4 : 1) void k_pgbwd(BwdArgs
     constexpr int TW = Wc::TW, Gw = Wc::Gw, Gd = Wc::Gd, COd = Wc::COd, NPASS = Wc::NPASS, SRd = Wc::SRd, KSd = Wc::KSd;
     constexpr int MT = Wc::MT, WRw = Wc::WRw, LSg = TGg::LS, LSx = TGx::LS, Nw = Gw * CO, Nd = Gd * COd;
     static_assert(TW % (16 * Gd) == 0, "tile width must hold whole dgrad M-tiles");
-    // DB: two stage buffers -> the next tile is committed while other waves still read the current one, one barrier per tile
-    constexpr int STAGE4 = Wc::STAGE4, NBUF = DB ? 2 : 1;
-    constexpr int MAIN4 = NBUF * STAGE4 > Wc::RED4 ? NBUF * STAGE4 : Wc::RED4;
+    constexpr int MAIN4 = Wc::LDS4;      // the staged tiles; after the tile loop the waves' reduction area
     // PF: pooled-gradient tile (floats) and window-position tile (bytes), TH/2 + 2 rows of TW/2 + 2 pixels, lead as for a halo-1 tile
     constexpr int PFR = TH / 2 + 2, PFW = Wc::TW / 2 + 2, PFLEAD = (4 - CO % 4) % 4;
     constexpr int PFLS = (PFLEAD + PFW * CO + 3) / 4 * 4, PFN4 = PF ? PFR * PFLS / 4 : 0, PFLI = PFLS / 4, PFNI = PF ? PFR * PFLI : 0;
@@ -686,7 +668,7 @@ __global__ __launch_bounds__(NT, (VW && NSRC == 1) ? 4 : 1) void k_pgbwd(BwdArgs
         y0 = by * TH;
     };
     int tile = blockIdx.x;
-    int it = 0, buf = 0;
+    int it = 0;
     (void)it;          // read by the tuning build's stamps only
     STAMP(6);
     if (tile < ntiles) {
@@ -705,29 +687,21 @@ __global__ __launch_bounds__(NT, (VW && NSRC == 1) ? 4 : 1) void k_pgbwd(BwdArgs
         for (int s = 0; s < NPASS * KSd; ++s) asm volatile("" : "+v"(breg[s]));
     }
 
-    if (DB && tile < ntiles) {
-        tile_commit<CO, TW, NT>(preg, okg, lds4, tid);
-#pragma unroll
-        for (int s = 0; s < NSRC; ++s) tile_commit<C, TW, NT>(prex[s], okx, lds4 + TGg::N4 + s * TGx::N4, tid);
-        lds_barrier();
-    }
 #pragma unroll 1
     while (tile < ntiles) {
         int b, x0, y0;
         decode(tile, b, x0, y0);
         STAMP(0);
-        if (!DB) {
-            if constexpr (PF) {
-                pf_commit_pooled();
-                lds_barrier();
-                pf_transform(okg);
-            }
-            tile_commit<CO, TW, NT>(preg, okg, lds4, tid);
-#pragma unroll
-            for (int s = 0; s < NSRC; ++s) tile_commit<C, TW, NT>(prex[s], okx, lds4 + TGg::N4 + s * TGx::N4, tid);
+        if constexpr (PF) {
+            pf_commit_pooled();
             lds_barrier();
+            pf_transform(okg);
         }
-        const int GOFF = buf * (STAGE4 * 4), XOFF = GOFF + TGg::N4 * 4;      // float indices of the dz / x tiles in use
+        tile_commit<CO, TW, NT>(preg, okg, lds4, tid);
+#pragma unroll
+        for (int s = 0; s < NSRC; ++s) tile_commit<C, TW, NT>(prex[s], okx, lds4 + TGg::N4 + s * TGx::N4, tid);
+        lds_barrier();
+        constexpr int GOFF = 0, XOFF = TGg::N4 * 4;      // float indices of the dz / x tiles
         const float* gl = ldsf + GOFF;
         const float* xl = ldsf + XOFF;
         STAMP(1);
@@ -1050,15 +1024,6 @@ __global__ __launch_bounds__(NT, (VW && NSRC == 1) ? 4 : 1) void k_pgbwd(BwdArgs
         }
         }
         STAMP(4);
-        if (DB) {
-            if (next < ntiles) {
-                tile_commit<CO, TW, NT>(preg, okg, lds4 + (buf ^ 1) * STAGE4, tid);
-#pragma unroll
-                for (int s = 0; s < NSRC; ++s)
-                    tile_commit<C, TW, NT>(prex[s], okx, lds4 + (buf ^ 1) * STAGE4 + TGg::N4 + s * TGx::N4, tid);
-            }
-            buf ^= 1;
-        }
         lds_barrier();
         STAMP(5);
         ++it;
@@ -1712,10 +1677,7 @@ struct PgPlan {                      // per-model table built lazily on the firs
     PrepRide prep{};                // this step's k_pg_prep arguments (fast_prepare)
     int64_t fold_outputs = 0;      // gradient elements k_pg_fold writes (all folds); with the head's C + 1: == nT when the plan covers the model
     HeadTail pending_head{};       // fast_finish_backward -> fast_fold_adam
-    int nblocks_cap = 512;
-    bool nblocks_forced = false;       // DNNCA_NBLOCKS (tuning aid) overrides the occupancy-derived grids
-    int nthreads = 512;
-    bool double_buffer = true;
+    std::map<const Op*, Op*> first3;   // second conv of a first encoder block -> its first conv, where k_first3 takes the pair's backward
     unsigned long long* stamps = nullptr;
 };
 
@@ -1723,8 +1685,6 @@ static std::map<Model*, PgPlan> g_plans;
 
 void fast_release(Model* m) { g_plans.erase(m); }
 unsigned long long* fast_debug_stamps(Model* m) { return g_plans[m].stamps; }
-
-static inline bool dense(const View& v) { return v.C == 0 || v.ps == v.C; }
 
 static bool conv_supported(const Model* m, const Op& o) {
     if (o.type != OP_CONV || o.k != 3) return false;
@@ -1744,6 +1704,40 @@ static bool conv_supported(const Model* m, const Op& o) {
 bool fast_pool_fusable(const Model* m, const Op& conv, const Op& pool) {
     return conv_supported(m, conv) && pool.type == OP_POOL && pool.k == 2 && pool.inA.d.p == conv.out.d.p && dense(pool.out.d) &&
            conv.out.d.H % 2 == 0 && conv.out.d.W % 2 == 0 && ((conv.out.d.W / 2) * conv.out.d.C) % 4 == 0;
+}
+
+// Column-strip kernels (strip_dev.h): an image is cut into strips of STRIP columns and every strip into row chunks of at least 8
+// rows, as many as `slots` tasks allow; a block of four waves takes four tasks.
+struct StripGrid { int nstrips, nchunks, nblocks; };
+static StripGrid strip_grid(int B, int H, int W, int slots) {
+    StripGrid s;
+    s.nstrips = (W + STRIP - 1) / STRIP;
+    s.nchunks = slots / (B * s.nstrips);
+    if (s.nchunks > H / 8) s.nchunks = H / 8;
+    if (s.nchunks < 1) s.nchunks = 1;
+    s.nblocks = (B * s.nchunks * s.nstrips + 3) / 4;
+    return s;
+}
+// ... and what they ask of the image: at least 8 x 8 pixels, byte offsets of a 3-channel tensor below STRIP_HALF; `even`: a 2x2
+// pool or transposed conv is part of the launch
+static bool strip_shape_ok(int B, int H, int W, bool even) {
+    return W >= 8 && H >= 8 && !(even && ((H | W) & 1)) && (double)B * H * W * 12.0 < 1073741824.0;
+}
+
+// The first conv of the network when `conv` is the second conv of the first encoder block and the pair can run its backward in
+// one column-strip launch (k_first3, strip_dev.h); nullptr otherwise.  Static per model: build_plan keeps the answer in
+// PgPlan::first3, where fast_pool_fold (does the pool hand its backward over?) and fast_conv_bwd (to which launch?) both read it.
+static Op* first3_conv0(Model* m, const PgPlan& pl, Op& conv) {
+    if (m->sw.no_first3) return nullptr;
+    const size_t i = (size_t)(&conv - m->ops.data());
+    Op& c0 = m->ops[i - 1];
+    if (c0.type != OP_CONV || c0.need_din || c0.inB.d.C || c0.inA.d.C != 1 || c0.out.d.C != 3 || c0.k != 3 || c0.out.d.p != conv.inA.d.p) return nullptr;
+    if (!conv_supported(m, c0) || !conv_supported(m, conv) || conv.inB.d.C || conv.inA.d.C != 3 || conv.out.d.C != 3 || conv.accA) return nullptr;
+    if (!dense(c0.inA.d) || !dense(conv.inA.d) || !dense(conv.out.d) || !dense(conv.out.g) || (c0.alpha >= 0.f && !c0.premasked)) return nullptr;
+    if ((c0.alpha >= 0.f) != (conv.maskA != 0)) return nullptr;       // the activation derivative of the first conv rides in this launch
+    if (!strip_shape_ok(m->desc.max_batch, conv.out.d.H, conv.out.d.W, true)) return nullptr;      // (any batch of the model)
+    if (pl.wslot.find({&c0, 0}) == pl.wslot.end() || pl.wslot.find({&conv, 0}) == pl.wslot.end()) return nullptr;
+    return &c0;
 }
 
 static int build_plan(Model* m, PgPlan& pl) {
@@ -1812,8 +1806,8 @@ static int build_plan(Model* m, PgPlan& pl) {
         pl.fold_outputs += outs;
     }
     pl.built = true;
-    if (const char* e = getenv("DNNCA_DB")) pl.double_buffer = atoi(e) != 0;            // tuning aid
-    if (const char* e = getenv("DNNCA_NBLOCKS")) { pl.nblocks_cap = atoi(e) > 0 ? atoi(e) : pl.nblocks_cap; pl.nblocks_forced = atoi(e) > 0; }   // tuning aid
+    for (size_t i = 1; i < m->ops.size(); ++i)
+        if (Op* c0 = first3_conv0(m, pl, m->ops[i])) pl.first3[&m->ops[i]] = c0;
     if (pl.folds.empty() && pl.descs.empty()) return DNNCA_OK;
     pl.fold_chunks = (max_out + 255) / 256;
     pl.slab_floats = slab_floats;
@@ -1878,7 +1872,7 @@ int fast_prepare(Model* m) {
         m->step_init_done = true;
     }
     pl.prep = PrepRide{pl.bindex, m->p, pl.bmat, pl.bmat_n, nprep, nprep + nz, z};
-    if (nz && !getenv("DNNCA_NO_PREP_RIDE")) {
+    if (nz && !m->sw.no_prep_ride) {
         // train step: the first launch of the forward pass decides -- the first encoder block's strip kernel takes the preparation
         // along as extra blocks (it needs none of its results); any other launch flushes it first (LAUNCH)
         m->prep_flush = [](Model* mm) {
@@ -1897,14 +1891,10 @@ int fast_prepare(Model* m) {
 // Grid of a persistent pixel-group kernel: as many 512-thread blocks as fit the chip at once (two or three per CU for the kernels whose
 // registers allow it, one for the heavy backward kernels -- launching 512 blocks of those ran them in two rounds and paid the
 // per-block prologue twice: 4-6 us on each of six kernels of the unet.yaml step).
-template <typename K>
-static int resident_blocks(K kernel, int cap, int nt = 512) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nt, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    static const int maxocc = getenv("DNNCA_PG_MAXOCC") ? atoi(getenv("DNNCA_PG_MAXOCC")) : 3;      // tuning aid (2: -0.3 %, 4: same)
-    if (per_cu > maxocc) per_cu = maxocc;
-    const int n = 256 * per_cu;
-    return n < cap ? n : cap;
+template <auto Kernel, int NT = 512>
+static int pg_grid(const Model* m, int ntiles) {
+    if (m->sw.nblocks > 0) return ntiles < m->sw.nblocks ? ntiles : m->sw.nblocks;      // tuning aid: a fixed grid
+    return resident_grid<Kernel, NT>(m->sw.pg_maxocc, ntiles);
 }
 
 #define CONV_SHAPES(X) X(1, 1, 3) X(3, 1, 3) X(3, 2, 3) X(3, 1, 6) X(6, 1, 6) X(6, 2, 6) X(6, 1, 12) X(12, 1, 12) X(12, 2, 12)
@@ -1926,16 +1916,12 @@ bool fast_conv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* pool)
     const int TW = 32 * (12 / CO);
     a.tiles_x = (a.W + TW - 1) / TW;
     a.tiles_y = (a.H + TH - 1) / TH;
-    int ntiles = a.tiles_x * a.tiles_y * B;
-    int nb = ntiles < pl.nblocks_cap ? ntiles : pl.nblocks_cap;
-    const bool db = pl.double_buffer && ntiles >= 3 * nb;     // LDS double buffering pays when a block walks several tiles
+    const int ntiles = a.tiles_x * a.tiles_y * B;
 #define X(c, ns, co)                                                                                            \
     if (C == c && NS == ns && CO == co) {                                                                       \
-        (void)db;                                                                                               \
-        static const int fit = resident_blocks(k_pgfwd<c, ns, co, 512, false>, 1 << 20);                        \
-        const int g = pl.nblocks_forced ? nb : (ntiles < fit ? ntiles : fit);                                   \
+        const int g = pg_grid<k_pgfwd<c, ns, co, 512>>(m, ntiles);                                              \
         LAUNCH(m, "pgfwd_" #c "x" #ns "_" #co, bytes, flops,                                                    \
-               hipLaunchKernelGGL((k_pgfwd<c, ns, co, 512, false>), dim3(g), dim3(512), 0, m->stream, a));      \
+               hipLaunchKernelGGL((k_pgfwd<c, ns, co, 512>), dim3(g), dim3(512), 0, m->stream, a));             \
         return true;                                                                                            \
     }
     CONV_SHAPES(X)
@@ -1943,22 +1929,23 @@ bool fast_conv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* pool)
     return false;
 }
 
-// The first conv of the network when `conv` is the second conv of the first encoder block and the pair can run its backward in
-// one column-strip launch (k_first3, strip_dev.h); nullptr otherwise.
-static Op* first3_conv0(Model* m, Op& conv) {
-    if (getenv("DNNCA_NO_FIRST3")) return nullptr;
-    const size_t i = (size_t)(&conv - m->ops.data());
-    if (i < 1 || i >= m->ops.size()) return nullptr;
-    Op& c0 = m->ops[i - 1];
-    if (c0.type != OP_CONV || c0.need_din || c0.inB.d.C || c0.inA.d.C != 1 || c0.out.d.C != 3 || c0.k != 3 || c0.out.d.p != conv.inA.d.p) return nullptr;
-    if (!conv_supported(m, c0) || !conv_supported(m, conv) || conv.inB.d.C || conv.inA.d.C != 3 || conv.out.d.C != 3 || conv.accA) return nullptr;
-    if (!dense(c0.inA.d) || !dense(conv.inA.d) || !dense(conv.out.d) || !dense(conv.out.g) || (c0.alpha >= 0.f && !c0.premasked)) return nullptr;
-    if ((c0.alpha >= 0.f) != (conv.maskA != 0)) return nullptr;       // the activation derivative of the first conv rides in this launch
-    const int H = conv.out.d.H, W = conv.out.d.W;
-    if ((H & 1) || (W & 1) || W < 8 || H < 8 || (double)m->desc.max_batch * H * W * 12.0 >= 1073741824.0) return nullptr;
-    PgPlan& pl = g_plans[m];
-    if (pl.wslot.find({&c0, 0}) == pl.wslot.end() || pl.wslot.find({&conv, 0}) == pl.wslot.end()) return nullptr;
-    return &c0;
+// The op in front of conv `o` (C -> C channels, two sources) when it is a k = 2 transposed conv cin -> C that produces o's first
+// source and whose backward can ride in o's backward launch: whole tiles, and nothing accumulates or is masked on the way.  Fills
+// the launch's tc_* arguments; nullptr otherwise.
+static Op* riding_tconv(Model* m, PgPlan& pl, Op& o, int cin, BwdArgs& a) {
+    const size_t oi = (size_t)(&o - m->ops.data());
+    if (oi < 1 || oi >= m->ops.size()) return nullptr;
+    Op* tc = &m->ops[oi - 1];
+    auto tw = pl.wslot.find({tc, 0});
+    const int C = o.inA.d.C, TW = 32 * (12 / C);
+    if (tc->type != OP_TCONV || tc->k != 2 || tc->inA.d.C != cin || tc->out.d.C != C || tc->out.d.p != o.inA.d.p || tw == pl.wslot.end() ||
+        !fast_tconv_supported(m, *tc) || tc->accA || o.accA || o.maskA || !dense(tc->inA.d) || !dense(tc->inA.g) || !dense(o.inA.d) ||
+        tc->inA.d.H * 2 != a.H || tc->inA.d.W * 2 != a.W || a.W % TW || a.H % TH)
+        return nullptr;
+    a.tc_in = tc->inA.d.p; a.tc_din = tc->inA.g.p; a.tc_w = m->p + tc->w_off;
+    a.tc_slabs = pl.slabs + pl.folds[tw->second].slab_off;
+    a.tc_mask = tc->maskA; a.tc_alpha = tc->mask_alpha;
+    return tc;
 }
 
 bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, double flops) {
@@ -1981,15 +1968,11 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
     a.acc[0] = o.accA; a.acc[1] = o.accB;
     a.mask[0] = o.maskA; a.mask[1] = o.maskB;
     a.alpha = o.mask_alpha;
-    if (const char* e = getenv("DNNCA_DBG")) a.dbg = atoi(e);
-    if (const char* e = getenv("DNNCA_STAMPS")) {      // e = "C,NS,CO" of the kernel to stamp
-        int sc = 0, sn = 0, so = 0;
-        if (sscanf(e, "%d,%d,%d", &sc, &sn, &so) == 3 && sc == C && sn == NS && so == CO) {
-            if (!pl.stamps) {
-                if (m->alloc((void**)&pl.stamps, 1024 * 4 * 8 * 8) != DNNCA_OK) return false;
-            }
-            a.stamps = pl.stamps;
-        }
+    const StepSwitches& sw = m->sw;
+    a.dbg = sw.dbg;
+    if (sw.stamp_c == C && sw.stamp_ns == NS && sw.stamp_co == CO) {      // tuning aid: this is the kernel to stamp
+        if (!pl.stamps && m->alloc((void**)&pl.stamps, 1024 * 4 * 8 * 8) != DNNCA_OK) return false;
+        a.stamps = pl.stamps;
     }
     for (int s = 0; s < NS; ++s) {
         auto it = pl.wslot.find({&o, s});
@@ -2000,15 +1983,15 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
     const int TW = 32 * (12 / CO);
     a.tiles_x = (a.W + TW - 1) / TW;
     a.tiles_y = (a.H + TH - 1) / TH;
-    int ntiles = a.tiles_x * a.tiles_y * B;
-    int nb = ntiles < pl.nblocks_cap ? ntiles : pl.nblocks_cap;
-    const bool db = pl.double_buffer && ntiles >= 3 * nb;
+    const int ntiles = a.tiles_x * a.tiles_y * B;
     const double bytes = out_bytes + (o.need_din ? 2 : 1) * in_bytes;
     const double fl = (o.need_din ? 2 : 1) * flops;
     // single-source 3 -> 3 channels: the all-vector-ALU backward (k_bwd3v), with or without the pool fold
     // the first encoder block: the second conv's backward (with the pool fold) and the first conv's weight gradient in one launch
     if (m->pool_fold.conv == &o) {
-        if (Op* c0 = first3_conv0(m, o)) {
+        auto f3 = pl.first3.find(&o);
+        if (f3 != pl.first3.end()) {
+            Op* c0 = f3->second;
             const Op& pool = *m->pool_fold.pool;
             m->pool_fold.conv = nullptr;
             FirstArgs f{};
@@ -2021,23 +2004,18 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
             f.slabs1 = a.slabs[0];
             f.slabs0 = pl.slabs + pl.folds[pl.wslot.find({c0, 0})->second].slab_off;
             f.B = B; f.H = a.H; f.W = a.W;
-            f.nstrips = (a.W + STRIP - 1) / STRIP;
-            int nchunks = 2048 / (B * f.nstrips);
-            if (nchunks > a.H / 8) nchunks = a.H / 8;
-            if (nchunks < 1) nchunks = 1;
-            f.nchunks = nchunks;
-            const int nblk = (B * nchunks * f.nstrips + 3) / 4;
+            const StripGrid sg = strip_grid(B, a.H, a.W, 2048);
+            f.nstrips = sg.nstrips; f.nchunks = sg.nchunks;
             const double npx = (double)B * a.H * a.W;
             // algorithmic bytes of the layers this launch stands for: pool backward (y, dy in; dx in/out; pooled gradient) 3 + 3 + 0.75 + 0.75,
             // second conv backward 3 + 3 + 3, first conv weight gradient 3 + 1 floats per pixel
             LAUNCH(m, "first3_bwd", 4.0 * npx * 20.5, 2.0 * npx * (162 + 30),
-                   hipLaunchKernelGGL((k_first3<2, 40>), dim3(nblk), dim3(256), 0, m->stream, f));
+                   hipLaunchKernelGGL((k_first3<2, 40>), dim3(sg.nblocks), dim3(256), 0, m->stream, f));
             m->first_done = c0;
             return true;
         }
     }
-    static const bool v3_on = getenv("DNNCA_NO_BWD3V") == nullptr;
-    if (v3_on && o.need_din && C == 3 && CO == 3 && NS == 1 && !o.accA && a.W % 128 == 0 && a.H % TH == 0) {
+    if (!sw.no_bwd3v && o.need_din && C == 3 && CO == 3 && NS == 1 && !o.accA && a.W % 128 == 0 && a.H % TH == 0) {
         const bool pf = m->pool_fold.conv == &o;
         double pb = 0.0;
         if (pf) {
@@ -2050,17 +2028,14 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
             pb = 4.0 * (2 * (double)B * o.out.d.H * o.out.d.W * CO + 2 * (double)B * pool.out.d.H * pool.out.d.W * CO);
         }
         const float* wts = m->p + o.w_off;
-        if (a.stamps && pf != (getenv("DNNCA_STAMPS_PF") != nullptr)) a.stamps = nullptr;       // tuning aid: which of the two launches is stamped
+        if (a.stamps && pf != sw.stamps_pf) a.stamps = nullptr;       // tuning aid: which of the two launches is stamped
         if (pf) {
-            static const int fit = resident_blocks(k_bwd3v<true>, 1 << 20, 256);
-            const int g = pl.nblocks_forced ? nb : (ntiles < fit ? ntiles : fit);
+            const int g = pg_grid<k_bwd3v<true>, 256>(m, ntiles);
             LAUNCH(m, "bwd3v_pool_3x1_3", bytes + pb, fl, hipLaunchKernelGGL(k_bwd3v<true>, dim3(g), dim3(256), 0, m->stream, a, wts));
         } else {
-            static const int fit = resident_blocks(k_bwd3v<false>, 1 << 20, 256);
-            const int g = pl.nblocks_forced ? nb : (ntiles < fit ? ntiles : fit);
+            const int g = pg_grid<k_bwd3v<false>, 256>(m, ntiles);
 #ifdef DNNCA_TUNING
-            static const int abl = getenv("DNNCA_ABL") ? atoi(getenv("DNNCA_ABL")) : 0;
-            if (abl == 1) {
+            if (sw.abl == 1) {
                 LAUNCH(m, "bwd3v_3x1_3", bytes, fl, hipLaunchKernelGGL((k_bwd3v<false, 1>), dim3(g), dim3(256), 0, m->stream, a, wts));
                 return true;
             }
@@ -2080,74 +2055,42 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
         const double pb = 4.0 * (2 * (double)B * o.out.d.H * o.out.d.W * CO + 2 * (double)B * pool.out.d.H * pool.out.d.W * CO);
 #define PFX(c)                                                                                                          \
         if (C == c) {                                                                                                   \
-            static const int fit = resident_blocks(k_pgbwd<c, 1, c, true, 512, false, false, true>, 1 << 20);           \
-            const int g = pl.nblocks_forced ? nb : (ntiles < fit ? ntiles : fit);                                       \
+            const int g = pg_grid<k_pgbwd<c, 1, c, true, 512, false, true>>(m, ntiles);                                 \
             LAUNCH(m, "pgbwd_pool_" #c "x1_" #c, bytes + pb, fl,                                                        \
-                   hipLaunchKernelGGL((k_pgbwd<c, 1, c, true, 512, false, false, true>), dim3(g), dim3(512), 0, m->stream, a)); \
+                   hipLaunchKernelGGL((k_pgbwd<c, 1, c, true, 512, false, true>), dim3(g), dim3(512), 0, m->stream, a)); \
             return true;                                                                                                \
         }
         PFX(3) PFX(6) PFX(12)
 #undef PFX
         return false;
     }
-    // 3 -> 3 channels: the variant whose weight gradient runs on the vector ALU beside the data-gradient MFMAs
+    // 3 -> 3 channels, two sources: the variant whose weight gradient runs on the vector ALU beside the data-gradient MFMAs
     // (measured, profiles/r02_vw_ab.txt: two sources 52.4 -> 48.2 us; one source 31.4 -> 32.0 us -- there the matrix pipe is not
-    //  what the data-gradient waves wait for -- so the single-source conv keeps the all-MFMA kernel unless DNNCA_VW_ALL is set)
-    static const bool vw_on = getenv("DNNCA_NO_VW") == nullptr;
-    static const bool vw_all = getenv("DNNCA_VW_ALL") != nullptr;
-    if (vw_on && o.need_din && C == 3 && CO == 3 && (NS == 2 || vw_all)) {
-        if (NS == 1) {
-            static const int fit = resident_blocks(k_pgbwd<3, 1, 3, true, 512, false, true>, 1 << 20);
-            const int g = pl.nblocks_forced ? nb : (ntiles < fit ? ntiles : fit);
-            LAUNCH(m, "pgbwd_3x1_3", bytes, fl,
-                   hipLaunchKernelGGL((k_pgbwd<3, 1, 3, true, 512, false, true>), dim3(g), dim3(512), 0, m->stream, a));
-        } else {
-            // the first source is the output of a 6 -> 3 transposed conv (the last decoder block): that layer's backward rides along
-            const size_t oi = (size_t)(&o - m->ops.data());
-            Op* tc = oi >= 1 && oi < m->ops.size() ? &m->ops[oi - 1] : nullptr;
-            auto tw = tc ? pl.wslot.find({tc, 0}) : pl.wslot.end();
-            if (tc && !getenv("DNNCA_NO_TCF") && tc->type == OP_TCONV && tc->k == 2 && tc->inA.d.C == 6 && tc->out.d.C == 3 &&
-                tc->out.d.p == o.inA.d.p && tw != pl.wslot.end() && fast_tconv_supported(m, *tc) && !tc->accA && !o.accA && !o.maskA &&
-                dense(tc->inA.d) && dense(tc->inA.g) && dense(o.inA.d) && tc->inA.d.H * 2 == a.H && tc->inA.d.W * 2 == a.W && a.W % 128 == 0 &&
-                a.H % TH == 0) {
-                a.tc_in = tc->inA.d.p; a.tc_din = tc->inA.g.p; a.tc_w = m->p + tc->w_off;
-                a.tc_slabs = pl.slabs + pl.folds[tw->second].slab_off;
-                a.tc_mask = tc->maskA; a.tc_alpha = tc->mask_alpha;
-                static const int fit = resident_blocks(k_pgbwd<3, 2, 3, true, 512, false, true, false, true>, 1 << 20);
-                const int g = pl.nblocks_forced ? nb : (ntiles < fit ? ntiles : fit);
-                const double tb = 4.0 * ((double)B * a.H * a.W * 3 + (double)B * (a.H / 2) * (a.W / 2) * 6);      // the transposed conv's out + in
-                LAUNCH(m, "pgbwd_tc_3x2_3", bytes + 2 * tb, fl + 4.0 * B * a.H * a.W * 3 * 6,
-                       hipLaunchKernelGGL((k_pgbwd<3, 2, 3, true, 512, false, true, false, true>), dim3(g), dim3(512), 0, m->stream, a));
-                m->tconv_done = tc;
-                return true;
-            }
-            static const int fit = resident_blocks(k_pgbwd<3, 2, 3, true, 512, false, true>, 1 << 20);
-            const int g = pl.nblocks_forced ? nb : (ntiles < fit ? ntiles : fit);
-            LAUNCH(m, "pgbwd_3x2_3", bytes, fl,
-                   hipLaunchKernelGGL((k_pgbwd<3, 2, 3, true, 512, false, true>), dim3(g), dim3(512), 0, m->stream, a));
+    //  what the data-gradient waves wait for -- so the single-source conv keeps the all-MFMA kernel)
+    if (!sw.no_vw && o.need_din && C == 3 && CO == 3 && NS == 2) {
+        // the first source is the output of a 6 -> 3 transposed conv (the last decoder block): that layer's backward rides along (TCF)
+        if (Op* tc = sw.no_tcf ? nullptr : riding_tconv(m, pl, o, 6, a)) {
+            const int g = pg_grid<k_pgbwd<3, 2, 3, true, 512, true, false, true>>(m, ntiles);
+            const double tb = 4.0 * ((double)B * a.H * a.W * 3 + (double)B * (a.H / 2) * (a.W / 2) * 6);      // the transposed conv's out + in
+            LAUNCH(m, "pgbwd_tc_3x2_3", bytes + 2 * tb, fl + 4.0 * B * a.H * a.W * 3 * 6,
+                   hipLaunchKernelGGL((k_pgbwd<3, 2, 3, true, 512, true, false, true>), dim3(g), dim3(512), 0, m->stream, a));
+            m->tconv_done = tc;
+            return true;
         }
+        const int g = pg_grid<k_pgbwd<3, 2, 3, true, 512, true>>(m, ntiles);
+        LAUNCH(m, "pgbwd_3x2_3", bytes, fl, hipLaunchKernelGGL((k_pgbwd<3, 2, 3, true, 512, true>), dim3(g), dim3(512), 0, m->stream, a));
         return true;
     }
     // 6 / 12 channels, two sources, the first one the output of a 12 -> C transposed conv: that layer's backward rides along (TCM)
-    if (o.need_din && NS == 2 && C == CO && (C == 6 || C == 12) && !getenv("DNNCA_NO_TCM")) {
-        const size_t oi = (size_t)(&o - m->ops.data());
-        Op* tc = oi >= 1 && oi < m->ops.size() ? &m->ops[oi - 1] : nullptr;
-        auto tw = tc ? pl.wslot.find({tc, 0}) : pl.wslot.end();
-        const int TWc = 32 * (12 / CO);
-        if (tc && tc->type == OP_TCONV && tc->k == 2 && tc->inA.d.C == 12 && tc->out.d.C == C && tc->out.d.p == o.inA.d.p &&
-            tw != pl.wslot.end() && fast_tconv_supported(m, *tc) && !tc->accA && !o.accA && !o.maskA && dense(tc->inA.d) && dense(tc->inA.g) &&
-            dense(o.inA.d) && tc->inA.d.H * 2 == a.H && tc->inA.d.W * 2 == a.W && a.W % TWc == 0 && a.H % TH == 0) {
-            a.tc_in = tc->inA.d.p; a.tc_din = tc->inA.g.p; a.tc_w = m->p + tc->w_off;
-            a.tc_slabs = pl.slabs + pl.folds[tw->second].slab_off;
-            a.tc_mask = tc->maskA; a.tc_alpha = tc->mask_alpha;
+    if (o.need_din && NS == 2 && C == CO && (C == 6 || C == 12) && !sw.no_tcm) {
+        if (Op* tc = riding_tconv(m, pl, o, 12, a)) {
             const double tb = 4.0 * ((double)B * a.H * a.W * C + (double)B * (a.H / 2) * (a.W / 2) * 12);      // the transposed conv's out + in
             const double tfl = 4.0 * B * a.H * a.W * C * 12;
 #define TCMX(c)                                                                                                         \
             if (C == c) {                                                                                               \
-                static const int fit = resident_blocks(k_pgbwd<c, 2, c, true, 512, false, false, false, false, true>, 1 << 20); \
-                const int g = pl.nblocks_forced ? nb : (ntiles < fit ? ntiles : fit);                                   \
+                const int g = pg_grid<k_pgbwd<c, 2, c, true, 512, false, false, false, true>>(m, ntiles);               \
                 LAUNCH(m, "pgbwd_tc_" #c "x2_" #c, bytes + 2 * tb, fl + tfl,                                            \
-                       hipLaunchKernelGGL((k_pgbwd<c, 2, c, true, 512, false, false, false, false, true>), dim3(g), dim3(512), 0, m->stream, a)); \
+                       hipLaunchKernelGGL((k_pgbwd<c, 2, c, true, 512, false, false, false, true>), dim3(g), dim3(512), 0, m->stream, a)); \
                 m->tconv_done = tc;                                                                                     \
                 return true;                                                                                            \
             }
@@ -2157,17 +2100,14 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
     }
 #define X(c, ns, co)                                                                                            \
     if (C == c && NS == ns && CO == co) {                                                                       \
-        (void)db;                                                                                               \
         if (o.need_din) {                                                                                       \
-            static const int fit = resident_blocks(k_pgbwd<c, ns, co, true, 512, false>, 1 << 20);              \
-            const int g = pl.nblocks_forced ? nb : (ntiles < fit ? ntiles : fit);                               \
+            const int g = pg_grid<k_pgbwd<c, ns, co, true, 512>>(m, ntiles);                                    \
             LAUNCH(m, "pgbwd_" #c "x" #ns "_" #co, bytes, fl,                                                   \
-                   hipLaunchKernelGGL((k_pgbwd<c, ns, co, true, 512, false>), dim3(g), dim3(512), 0, m->stream, a)); \
+                   hipLaunchKernelGGL((k_pgbwd<c, ns, co, true, 512>), dim3(g), dim3(512), 0, m->stream, a));   \
         } else {                                                                                                \
-            static const int fit = resident_blocks(k_pgbwd<c, ns, co, false, 512, false>, 1 << 20);             \
-            const int g = pl.nblocks_forced ? nb : (ntiles < fit ? ntiles : fit);                               \
+            const int g = pg_grid<k_pgbwd<c, ns, co, false, 512>>(m, ntiles);                                   \
             LAUNCH(m, "pgbwd_w_" #c "x" #ns "_" #co, bytes, fl,                                                 \
-                   hipLaunchKernelGGL((k_pgbwd<c, ns, co, false, 512, false>), dim3(g), dim3(512), 0, m->stream, a)); \
+                   hipLaunchKernelGGL((k_pgbwd<c, ns, co, false, 512>), dim3(g), dim3(512), 0, m->stream, a));  \
         }                                                                                                       \
         return true;                                                                                            \
     }
@@ -2181,15 +2121,14 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
 // (accumulate) and the pool applies act' of that conv (ReLU: ties at zero are killed by act'(0) = 0).  The caller then skips the
 // pool's own launch; the very next fast_conv_bwd call must be for `conv`.
 bool fast_pool_fold(Model* m, Op& pool, Op& conv) {
-    static const bool on = getenv("DNNCA_NO_POOL_FOLD") == nullptr;
-    if (!on || pool.type != OP_POOL || pool.k != 2 || !pool.pool_idx_valid || !(pool.pool_idx || m->dry)) return false;
+    if (m->sw.no_pool_fold || pool.type != OP_POOL || pool.k != 2 || !pool.pool_idx_valid || !(pool.pool_idx || m->dry)) return false;
     if (!pool.accA || !pool.maskA || pool.mask_alpha != 0.f) return false;
     if (!conv_supported(m, conv) || conv.inB.d.C || !conv.need_din || conv.out.d.p != pool.inA.d.p || !conv.premasked) return false;
     const int C = conv.inA.d.C, CO = conv.out.d.C;
     if (C != CO || !(C == 3 || C == 6 || C == 12)) return false;
     const int TW = 32 * (12 / CO);
     if (!dense(pool.out.g) || !dense(pool.out.d)) return false;
-    if ((conv.out.d.W % TW || conv.out.d.H % TH) && !first3_conv0(m, conv)) return false;      // the tile kernels fold whole tiles only
+    if ((conv.out.d.W % TW || conv.out.d.H % TH) && !g_plans[m].first3.count(&conv)) return false;      // the tile kernels fold whole tiles only
     pool.pool_idx_valid = false;
     m->pool_fold.conv = &conv;
     m->pool_fold.pool = &pool;
@@ -2202,6 +2141,26 @@ bool fast_head_in_conv_possible(Model* m) {
     const Op& o = m->ops[m->ops.size() - 2];
     if (head.type != OP_HEAD || !conv_supported(m, o)) return false;
     return o.inA.d.C == 3 && !o.inB.d.C && o.out.d.C == 3 && head.inA.d.p == o.out.d.p && head.inA.d.C == 3 && dense(head.inA.d);
+}
+
+// The head / loss / label-statistics arguments of a launch that runs the head of a training step (FwdArgs, TailArgs) ...
+template <typename A>
+static void head_args(A& a, const Model* m, const Op& head, const float* y, const dnnca_loss_cfg& cfg, float gscale, double n_label) {
+    a.hy = y;
+    a.hw = m->p + head.w_off; a.hb = m->p + head.b_off;
+    a.hpartials = m->head_partials;
+    a.hscalars = m->scalars;
+    a.hlabel_part = m->label_part_valid ? m->label_part : nullptr;
+    a.hlabel_nblk = m->label_part_nblk;
+    a.hcfg = cfg;
+    a.hn_label = n_label;
+    a.hgscale = gscale;
+    a.hmask = head.maskA; a.halpha = head.mask_alpha;
+}
+// ... and behind it: the block partial sums wait for the launch that ends the backward pass (k_pg_fold)
+static void head_launched(Model* m, const Op& head, int nblocks) {
+    m->head_pending.partials = m->head_partials; m->head_pending.nblocks = nblocks; m->head_pending.C = 3;
+    m->head_pending.dw = m->g + head.w_off; m->head_pending.dbias = m->g + head.b_off;
 }
 
 // The conv that feeds the annotator head, in a training step: its forward launch also runs the head, the weighted BCE and the
@@ -2223,36 +2182,24 @@ bool fast_conv_fwd_head(Model* m, int B, Op& o, Op& head, const float* y, const 
     a.pool_dst = nullptr;
     a.B = B; a.H = o.out.d.H; a.W = o.out.d.W;
     a.alpha = o.alpha;
-    a.hy = y;
-    a.hw = m->p + head.w_off; a.hb = m->p + head.b_off;
+    head_args(a, m, head, y, cfg, gscale, (double)B * a.H * a.W);
     a.hdfeat = head.inA.g.p;
-    a.hpartials = m->head_partials;
-    a.hscalars = m->scalars;
-    a.hlabel_part = m->label_part_valid ? m->label_part : nullptr;
-    a.hlabel_nblk = m->label_part_nblk;
-    a.hcfg = cfg;
-    a.hn_label = (double)B * a.H * a.W;
-    a.hgscale = gscale;
-    a.hmask = head.maskA; a.halpha = head.mask_alpha;
     const int TW = 32 * (12 / CO);
     a.tiles_x = (a.W + TW - 1) / TW;
     a.tiles_y = (a.H + TH - 1) / TH;
     const int ntiles = a.tiles_x * a.tiles_y * B;
-    static const int fit = resident_blocks(k_pgfwd<3, 1, 3, 512, false, true>, 2048);      // partials table: 2048 rows
-    const int g = ntiles < fit ? ntiles : fit;
+    const int g = resident_grid<k_pgfwd<3, 1, 3, 512, true>, 512>(m->sw.pg_maxocc, ntiles < 2048 ? ntiles : 2048);      // partials table: 2048 rows
     if (m->train_metrics_on()) {         // + the step's probabilities (dnnca_train_metrics): the same grid
         FwdProbArgs pa{};
         static_cast<FwdArgs&>(pa) = a;
         pa.hprob = m->prob;
         LAUNCH(m, "pgfwd_head_3x1_3", bytes + 4.0 * a.H * a.W * B, flops,
-               hipLaunchKernelGGL((k_pgfwd<3, 1, 3, 512, false, true, true>), dim3(g), dim3(512), 0, m->stream, pa));
+               hipLaunchKernelGGL((k_pgfwd<3, 1, 3, 512, true, true>), dim3(g), dim3(512), 0, m->stream, pa));
     } else {
         LAUNCH(m, "pgfwd_head_3x1_3", bytes, flops,
-               hipLaunchKernelGGL((k_pgfwd<3, 1, 3, 512, false, true>), dim3(g), dim3(512), 0, m->stream, a));
+               hipLaunchKernelGGL((k_pgfwd<3, 1, 3, 512, true>), dim3(g), dim3(512), 0, m->stream, a));
     }
-    // the partial sums wait for the launch that ends the backward pass (k_pg_fold)
-    m->head_pending.partials = m->head_partials; m->head_pending.nblocks = g; m->head_pending.C = 3;
-    m->head_pending.dw = m->g + head.w_off; m->head_pending.dbias = m->g + head.b_off;
+    head_launched(m, head, g);
     return true;
 }
 
@@ -2260,9 +2207,9 @@ bool fast_conv_fwd_head(Model* m, int B, Op& o, Op& head, const float* y, const 
 // (kernels_fused.hip), which owns the block's bookkeeping (pool positions, label partials).  nblocks: rows of the label table.
 bool fast_first3_fwd(Model* m, int B, Op& c1, Op& c2, Op& pool, float* y0, unsigned char* pool_idx, const float* labels, float* label_part,
                      double bytes, double flops, int* nblocks) {
-    if (getenv("DNNCA_NO_FIRST3F") || c1.inA.d.C != 1 || c1.out.d.C != 3 || c2.out.d.C != 3) return false;
+    if (m->sw.no_first3f || c1.inA.d.C != 1 || c1.out.d.C != 3 || c2.out.d.C != 3) return false;
     const int H = c1.out.d.H, W = c1.out.d.W;
-    if ((H & 1) || (W & 1) || W < 8 || H < 8 || (double)B * H * W * 12.0 >= 1073741824.0 || c1.alpha > 1.f || c2.alpha > 1.f) return false;
+    if (!strip_shape_ok(B, H, W, true) || c1.alpha > 1.f || c2.alpha > 1.f) return false;
     FirstFwdArgs a{};
     a.xin = c1.inA.d.p;
     a.w0 = m->p + c1.w_off; a.b0 = m->p + c1.b_off;
@@ -2270,20 +2217,13 @@ bool fast_first3_fwd(Model* m, int B, Op& c1, Op& c2, Op& pool, float* y0, unsig
     a.alpha0 = c1.alpha; a.alpha1 = c2.alpha;
     a.y0 = y0; a.y1 = c2.out.d.p;
     a.pool = pool.out.d.p; a.pool_idx = pool_idx;
-    if (const char* e = getenv("DNNCA_F3F_ABL")) {      // tuning aid (wrong results): drop output tensors
-        const int abl = atoi(e);
-        if (abl & 1) a.y0 = nullptr;
-        if (abl & 2) a.pool_idx = nullptr;
-    }
+    if (m->sw.f3f_abl & 1) a.y0 = nullptr;      // tuning aid (wrong results): drop output tensors
+    if (m->sw.f3f_abl & 2) a.pool_idx = nullptr;
     a.labels = labels; a.label_part = label_part;
     a.B = B; a.H = H; a.W = W;
-    a.nstrips = (W + STRIP - 1) / STRIP;
-    static const int wps = getenv("DNNCA_F3F_WPS") ? atoi(getenv("DNNCA_F3F_WPS")) : 2;      // tuning aid: waves per SIMD
-    int nchunks = 1024 * wps / (B * a.nstrips);
-    if (nchunks > H / 8) nchunks = H / 8;
-    if (nchunks < 1) nchunks = 1;
-    a.nchunks = nchunks;
-    const int nblk = (B * nchunks * a.nstrips + 3) / 4;
+    const StripGrid sg = strip_grid(B, H, W, 2048);      // two waves per SIMD
+    a.nstrips = sg.nstrips; a.nchunks = sg.nchunks;
+    const int nblk = sg.nblocks;
     if (nblk > 2048) return false;
     a.nstrip_blocks = nblk;
     int nride = 0;
@@ -2292,15 +2232,7 @@ bool fast_first3_fwd(Model* m, int B, Op& c1, Op& c2, Op& pool, float* y0, unsig
         a.prep = g_plans[m].prep;
         nride = a.prep.nblocks;
     }
-    if (nride) {
-        LAUNCH(m, "first3_fwd", bytes, flops, hipLaunchKernelGGL((k_first3_fwd<0, 27>), dim3(nblk + nride), dim3(256), 0, m->stream, a));
-        *nblocks = nblk;
-        return true;
-    }
-    if (wps == 3)
-        LAUNCH(m, "first3_fwd", bytes, flops, hipLaunchKernelGGL((k_first3_fwd<0, 27, 3>), dim3(nblk), dim3(256), 0, m->stream, a));
-    else
-        LAUNCH(m, "first3_fwd", bytes, flops, hipLaunchKernelGGL((k_first3_fwd<0, 27>), dim3(nblk), dim3(256), 0, m->stream, a));
+    LAUNCH(m, "first3_fwd", bytes, flops, hipLaunchKernelGGL((k_first3_fwd<0, 27>), dim3(nblk + nride), dim3(256), 0, m->stream, a));
     *nblocks = nblk;
     return true;
 }
@@ -2308,7 +2240,7 @@ bool fast_first3_fwd(Model* m, int B, Op& c1, Op& c2, Op& pool, float* y0, unsig
 // Conv2DTranspose 6 -> 3 followed by the two-source conv 6 -> 3 of the last decoder block (forward) as one column-strip launch
 // (k_up3_fwd, strip_dev.h); ops[oi], ops[oi + 1] are consumed when it returns true.
 bool fast_up3_fwd(Model* m, int B, size_t oi) {
-    if (getenv("DNNCA_NO_UP3F") || (m->desc.flags & 1) || oi + 1 >= m->ops.size()) return false;
+    if (m->sw.no_up3f || (m->desc.flags & 1) || oi + 1 >= m->ops.size()) return false;
     Op &tc = m->ops[oi], &c0 = m->ops[oi + 1];
     if (tc.type != OP_TCONV || c0.type != OP_CONV || tc.k != 2 || c0.k != 3) return false;
     if (tc.inA.d.C != 6 || tc.out.d.C != 3 || c0.inA.d.C != 3 || c0.inB.d.C != 3 || c0.out.d.C != 3) return false;
@@ -2316,7 +2248,7 @@ bool fast_up3_fwd(Model* m, int B, size_t oi) {
     if (!conv_supported(m, c0) || !fast_tconv_supported(m, tc)) return false;
     const int H = c0.out.d.H, W = c0.out.d.W;
     if (tc.out.d.H != H || tc.out.d.W != W || c0.inB.d.H != H || c0.inB.d.W != W || tc.inA.d.H * 2 != H || tc.inA.d.W * 2 != W) return false;
-    if ((H & 1) || (W & 1) || W < 8 || H < 8 || (double)B * H * W * 12.0 >= 1073741824.0 || c0.alpha > 1.f) return false;
+    if (!strip_shape_ok(B, H, W, true) || c0.alpha > 1.f) return false;
     UpFwdArgs a{};
     a.in = tc.inA.d.p; a.skip = c0.inB.d.p;
     a.wt = m->p + tc.w_off; a.bt = m->p + tc.b_off;
@@ -2324,16 +2256,12 @@ bool fast_up3_fwd(Model* m, int B, size_t oi) {
     a.alpha = c0.alpha;
     a.tout = tc.out.d.p; a.out = c0.out.d.p;
     a.B = B; a.H = H; a.W = W;
-    a.nstrips = (W + STRIP - 1) / STRIP;
-    int nchunks = 2048 / (B * a.nstrips);
-    if (nchunks > H / 8) nchunks = H / 8;
-    if (nchunks < 1) nchunks = 1;
-    a.nchunks = nchunks;
-    const int nblk = (B * nchunks * a.nstrips + 3) / 4;
+    const StripGrid sg = strip_grid(B, H, W, 2048);
+    a.nstrips = sg.nstrips; a.nchunks = sg.nchunks;
     const double npx = (double)B * H * W;
     // algorithmic bytes of the two layers: transposed conv (1.5 in, 3 out), conv (3 + 3 in, 3 out) floats per pixel
     LAUNCH(m, "up3_fwd", 4.0 * npx * 13.5, 2.0 * npx * (18 + 162),
-           hipLaunchKernelGGL((k_up3_fwd<2, 48>), dim3(nblk), dim3(256), 0, m->stream, a));
+           hipLaunchKernelGGL((k_up3_fwd<2, 48>), dim3(sg.nblocks), dim3(256), 0, m->stream, a));
     return true;
 }
 
@@ -2341,12 +2269,12 @@ bool fast_up3_fwd(Model* m, int B, size_t oi) {
 // in one column-strip launch (k_tail3, strip_dev.h).  The conv's output and its gradient are never written; the caller skips the
 // conv's backward launch (Model::tail_done).  Returns false when the shape has no such kernel.
 bool fast_tail3(Model* m, int B, Op& o, Op& head, const float* y, const dnnca_loss_cfg& cfg, float gscale) {
-    if (getenv("DNNCA_NO_TAIL3") || !conv_supported(m, o) || !m->head_defer_ok) return false;      // (read per call: the tests flip it)
+    if (m->sw.no_tail3 || !conv_supported(m, o) || !m->head_defer_ok) return false;
     const int C = o.inA.d.C, NS = o.inB.d.C ? 2 : 1, CO = o.out.d.C;
     if (C != 3 || NS != 1 || CO != 3 || head.inA.d.p != o.out.d.p || head.inA.d.C != 3 || !dense(head.inA.d)) return false;
     if (!o.need_din || o.accA || !dense(o.inA.d) || !dense(o.inA.g) || (o.alpha >= 0.f && !o.premasked)) return false;
     const int H = o.out.d.H, W = o.out.d.W;
-    if ((double)B * H * W * 12.0 >= 1073741824.0 || W < 8 || H < 8 || o.alpha > 1.f) return false;      // byte offsets below STRIP_HALF
+    if (!strip_shape_ok(B, H, W, false) || o.alpha > 1.f) return false;
     PgPlan& pl = g_plans[m];
     auto it = pl.wslot.find({&o, 0});
     if (it == pl.wslot.end()) return false;
@@ -2354,34 +2282,20 @@ bool fast_tail3(Model* m, int B, Op& o, Op& head, const float* y, const dnnca_lo
     a.x = o.inA.d.p;
     a.w = m->p + o.w_off; a.bias = m->p + o.b_off;
     a.alpha = o.alpha;
-    a.hy = y;
-    a.hw = m->p + head.w_off; a.hb = m->p + head.b_off;
-    a.hpartials = m->head_partials;
-    a.hscalars = m->scalars;
-    a.hlabel_part = m->label_part_valid ? m->label_part : nullptr;
-    a.hlabel_nblk = m->label_part_nblk;
-    a.hcfg = cfg;
-    a.hn_label = (double)B * H * W;
-    a.hgscale = gscale;
-    a.hmask = head.maskA; a.halpha = head.mask_alpha;
+    head_args(a, m, head, y, cfg, gscale, (double)B * H * W);
     a.dx = o.inA.g.p;
     a.mask = o.maskA; a.mask_alpha = o.mask_alpha;
     a.slabs = pl.slabs + pl.folds[it->second].slab_off;
     a.B = B; a.H = H; a.W = W;
-    a.nstrips = (W + STRIP - 1) / STRIP;
-    // one round of waves: 2 per SIMD on 256 CUs = 2048 tasks at most, in chunks of at least 8 rows
-    static const int slots = getenv("DNNCA_TAIL3_SLOTS") ? atoi(getenv("DNNCA_TAIL3_SLOTS")) : 2048;      // tuning aid
-    int nchunks = slots / (B * a.nstrips);
-    if (nchunks > H / 8) nchunks = H / 8;
-    if (nchunks < 1) nchunks = 1;
-    a.nchunks = nchunks;
-    const int ntasks = B * nchunks * a.nstrips, nblk = (ntasks + 3) / 4;
+    // one round of waves: 2 per SIMD on 256 CUs = 2048 tasks at most
+    const StripGrid sg = strip_grid(B, H, W, m->sw.tail3_slots);
+    a.nstrips = sg.nstrips; a.nchunks = sg.nchunks;
+    const int nblk = sg.nblocks, tail3_lds = m->sw.tail3_lds;
     if (nblk > 2048) return false;                      // rows of the head's partials table
     const double npx = (double)B * H * W;
-    static const int tail3_lds = getenv("DNNCA_TAIL3_LDS") ? atoi(getenv("DNNCA_TAIL3_LDS")) : 0;      // tuning aid: dynamic LDS bytes (limits blocks per CU)
     auto kern = k_tail3<3, 27, true, 0, 1>;
 #ifdef DNNCA_TUNING
-    static const int variant = getenv("DNNCA_TAIL3_VARIANT") ? atoi(getenv("DNNCA_TAIL3_VARIANT")) : 0;      // tuning aid
+    const int variant = m->sw.tail3_variant;      // tuning aid
     if (variant == 1) kern = k_tail3<3, 27, true>;
     if (variant == 2) kern = k_tail3<6, 27, true>;
     if (variant == 3) kern = k_tail3<3, 0, true>;
@@ -2409,8 +2323,7 @@ bool fast_tail3(Model* m, int B, Op& o, Op& head, const float* y, const dnnca_lo
         LAUNCH(m, "tail3_3x1_3", 4.0 * npx * 22, 2.0 * npx * (81 * 3 + 15),
                hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), tail3_lds, m->stream, a));
     }
-    m->head_pending.partials = m->head_partials; m->head_pending.nblocks = nblk; m->head_pending.C = 3;
-    m->head_pending.dw = m->g + head.w_off; m->head_pending.dbias = m->g + head.b_off;
+    head_launched(m, head, nblk);
     m->tail_done = &o;
     return true;
 }
@@ -2460,7 +2373,7 @@ int fast_finish_backward(Model* m) {
     // single-replica train step whose every gradient (and the loss) comes out of this launch: wait for optimizer_step and let the
     // fold apply Adam as well (fast_fold_adam)
     if (extra && !m->comm && !m->dry && m->merged_launches() && m->desc.l2 == 0.f && pl.fold_outputs + h.C + 1 == m->nT &&
-        !getenv("DNNCA_NO_FOLD_ADAM")) {
+        !m->sw.no_fold_adam) {
         m->fold_deferred = true;
         pl.pending_head = h;
         return DNNCA_OK;

@@ -17,7 +17,6 @@ DEVINL void ld4(float* d, const float* p) {
 }
 DEVINL void st4(float* p, const float* s) { *reinterpret_cast<float4*>(p) = make_float4(s[0], s[1], s[2], s[3]); }
 
-static inline bool dense(const View& v) { return v.C == 0 || v.ps == v.C; }
 
 // ------------------------------------------------------------------------------------------------ max pool 2x2 / 2
 // one thread = 12 output floats = 24 input floats of each of the two input rows

@@ -86,8 +86,35 @@ struct ConfThresholds {
     int n = 0;                           // 0: none
 };
 
+// Switch table of the small-channel step: every DNNCA_ variable that the pixel-group, column-strip and block-fused
+// launchers and the model's own passes consult.  Read ONCE PER MODEL, at the top of Model::build(); a variable set after
+// dnnca_model_create does not affect that model, and no two decisions of one model can see different values.  A field is named
+// after its variable (DNNCA_NO_TAIL3 -> no_tail3).
+struct StepSwitches {
+    // fallbacks: the fused / riding launch is off and the launches it replaced run
+    bool no_fused = false, no_fused_bwd = false, no_first3 = false, no_first3f = false, no_up3f = false, no_tail3 = false;
+    bool no_tcf = false, no_tcm = false, no_tconv_ride = false, no_prep_ride = false, no_fold_adam = false, no_pool_fold = false;
+    bool no_bwd3v = false, no_vw = false, no_head_in_conv = false, no_label_fusion = false, no_wg_stream = false;
+    // opt-in
+    bool fz_up2 = false, fz_all = false, lockstep = false, force_rccl = false;
+    // tuning aids.  fz_only / fzb_only: the one block that fuses ("down1", "up2", ...; empty: all); stamp_*: (C, NSRC, CO) of the
+    // backward kernel that writes in-kernel stamps (0: none), stamps_pf: its pool-fold launch; nblocks > 0 replaces the
+    // occupancy-derived grids of the pixel-group kernels, pg_maxocc caps their blocks per CU (2: -0.3 %, 4: same)
+    std::string fz_only, fzb_only;
+    int stamp_c = 0, stamp_ns = 0, stamp_co = 0;
+    bool stamps_pf = false;
+    int dbg = 0, fzb_dbg = 0, f3f_abl = 0, abl = 0, tail3_variant = 0;      // (abl, tail3_variant: DNNCA_TUNING builds only)
+    int nblocks = 0, pg_maxocc = 3;
+    int tail3_slots = 2048, tail3_lds = 0;      // k_tail3: task budget, dynamic LDS bytes (limits blocks per CU)
+    int lockstep_maxh = 128;
+    int wg_prio = 1;                            // side stream: 0 normal, 1 least urgent, 2 most urgent
+    size_t bucket_bytes = 8u << 20;             // gradient all-reduce bucket (at least 4096)
+};
+StepSwitches step_switches();                   // model.hip: fills the table from the environment
+
 struct Model {
     dnnca_model_desc desc;
+    StepSwitches sw;
     int device = 0;
     hipStream_t stream = nullptr;
     std::vector<ParamInfo> params;
@@ -176,7 +203,6 @@ struct Model {
     int bucket_state = 0;                // 0 undecided, 1 the op order finalises a suffix (bucketing possible), -1 it does not
     bool bucketing = false;              // this step's backward pass sends buckets
     int64_t bucket_hi = 0, bucket_fin = 0;   // [bucket_fin, bucket_hi) is final and not yet sent
-    size_t bucket_bytes = 8u << 20;
     int collectives_last_step = 0;       // gradient all-reduce calls issued by the last train step
     int send_bucket(int64_t lo, int64_t hi);
     // Input pipeline (dnnca_stage_*): a batch travels host -> HBM on its own copy stream into one of a ring of staging slots

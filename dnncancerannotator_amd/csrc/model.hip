@@ -29,6 +29,58 @@ void set_error(const char* fmt, ...) {
 
 enum { kScalars = 8 };
 
+// The one place the small-channel step reads its environment (model.h StepSwitches; Model::build stores the answer in Model::sw).
+StepSwitches step_switches() {
+    auto on = [](const char* name) { return getenv(name) != nullptr; };
+    auto num = [](const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; };
+    auto str = [](const char* name) { return std::string(getenv(name) ? getenv(name) : ""); };
+    StepSwitches s;
+    s.no_fused = on("DNNCA_NO_FUSED");
+    s.no_fused_bwd = on("DNNCA_NO_FUSED_BWD");
+    s.no_first3 = on("DNNCA_NO_FIRST3");
+    s.no_first3f = on("DNNCA_NO_FIRST3F");
+    s.no_up3f = on("DNNCA_NO_UP3F");
+    s.no_tail3 = on("DNNCA_NO_TAIL3");
+    s.no_tcf = on("DNNCA_NO_TCF");
+    s.no_tcm = on("DNNCA_NO_TCM");
+    s.no_tconv_ride = on("DNNCA_NO_TCONV_RIDE");
+    s.no_prep_ride = on("DNNCA_NO_PREP_RIDE");
+    s.no_fold_adam = on("DNNCA_NO_FOLD_ADAM");
+    s.no_pool_fold = on("DNNCA_NO_POOL_FOLD");
+    s.no_bwd3v = on("DNNCA_NO_BWD3V");
+    s.no_vw = on("DNNCA_NO_VW");
+    s.no_head_in_conv = on("DNNCA_NO_HEAD_IN_CONV");
+    s.no_label_fusion = on("DNNCA_NO_LABEL_FUSION");
+    s.no_wg_stream = on("DNNCA_NO_WG_STREAM");
+    s.fz_up2 = on("DNNCA_FZ_UP2");
+    s.fz_all = on("DNNCA_FZ_ALL");
+    s.lockstep = on("DNNCA_LOCKSTEP");
+    s.force_rccl = on("DNNCA_FORCE_RCCL");
+    s.fz_only = str("DNNCA_FZ_ONLY");
+    s.fzb_only = str("DNNCA_FZB_ONLY");
+    if (sscanf(str("DNNCA_STAMPS").c_str(), "%d,%d,%d", &s.stamp_c, &s.stamp_ns, &s.stamp_co) != 3) s.stamp_c = s.stamp_ns = s.stamp_co = 0;
+    s.stamps_pf = on("DNNCA_STAMPS_PF");
+    s.dbg = num("DNNCA_DBG", 0);
+    s.fzb_dbg = num("DNNCA_FZB_DBG", 0);
+    s.f3f_abl = num("DNNCA_F3F_ABL", 0);
+    s.abl = num("DNNCA_ABL", 0);
+    s.tail3_variant = num("DNNCA_TAIL3_VARIANT", 0);
+    s.nblocks = std::max(num("DNNCA_NBLOCKS", 0), 0);
+    s.pg_maxocc = num("DNNCA_PG_MAXOCC", 3);
+    s.tail3_slots = num("DNNCA_TAIL3_SLOTS", 2048);
+    s.tail3_lds = num("DNNCA_TAIL3_LDS", 0);
+    s.lockstep_maxh = num("DNNCA_LOCKSTEP_MAXH", 128);
+    s.wg_prio = num("DNNCA_WG_PRIO", 1);
+    if (const char* e = getenv("DNNCA_BUCKET_BYTES")) s.bucket_bytes = std::max((size_t)atol(e), (size_t)4096);
+    return s;
+}
+
+// train step / its plan dump: the head is to ride in the epilogue of the conv that feeds it (Model::forward decides whether it can).
+// Label smoothing blurs the labels in loss_and_backward first: then the head cannot run inside the forward pass.
+static bool head_in_conv_requested(const Model* M, const dnnca_loss_cfg& cfg) {
+    return !cfg.label_smoothing && M->merged_launches() && !M->sw.no_head_in_conv;
+}
+
 Model::~Model() {
     region_release(this);
     fast_release(this);
@@ -66,15 +118,14 @@ Model::~Model() {
 }
 
 bool Model::wg_side_begin() {
-    const bool off = getenv("DNNCA_NO_WG_STREAM") != nullptr;          // read per call: the tests flip it
+    const bool off = sw.no_wg_stream;
     // full profiles (modes 1, 3) time one launch after the other (the sampled bracket of mode 2 goes where its kernel goes); the
     // dry run launches nothing.  (With a communicator a gradient bucket also waits for the side stream: send_bucket.)
     if (off || dry || prof_mode == 1 || prof_mode == 3) return false;
     if (!wg_stream) {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);           // lo: the numerically largest = least urgent
-        const char* pe = getenv("DNNCA_WG_PRIO");                   // tuning aid: 0 normal, 1 least urgent (default), 2 most urgent
-        const int prio = !pe || atoi(pe) == 1 ? lo : (atoi(pe) == 2 ? hi : 0);
+        const int prio = sw.wg_prio == 1 ? lo : (sw.wg_prio == 2 ? hi : 0);
         if (hipStreamCreateWithPriority(&wg_stream, hipStreamNonBlocking, prio) != hipSuccess) { wg_stream = nullptr; return false; }
         if (hipEventCreateWithFlags(&wg_fork, hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&wg_join, hipEventDisableTiming) != hipSuccess ||
@@ -187,6 +238,7 @@ int Model::flush_profile() {
 
 // ---------------------------------------------------------------------------------------------- plan
 int Model::build() {
+    sw = step_switches();
     const dnnca_model_desc& d = desc;
     if (d.arch != DNNCA_ARCH_UNET && d.arch != DNNCA_ARCH_MULMO) { set_error("unknown arch %d", d.arch); return DNNCA_EINVAL; }
     if (d.conv_stride != 1) { set_error("conv_stride %d unsupported (reference configs use 1)", d.conv_stride); return DNNCA_EINVAL; }
@@ -466,8 +518,7 @@ static bool all_f32(const Op& o) {
 bool Model::lockstep() const {
     // OFF by default: nothing shares a launch across the encoders yet, and the order alone costs cache locality (pass_order).
     // DNNCA_LOCKSTEP=1 walks the encoders in lockstep (the groundwork for one launch per twin-op triple; results are unchanged).
-    static const bool on = getenv("DNNCA_LOCKSTEP") != nullptr;
-    return on && enc_ops > 0 && !(desc.flags & 1);
+    return sw.lockstep && enc_ops > 0 && !(desc.flags & 1);
 }
 
 std::vector<int> Model::pass_order(bool backward) const {
@@ -477,7 +528,7 @@ std::vector<int> Model::pass_order(bool backward) const {
     // what the next op of the SAME encoder reads, largely out of the 256 MB Infinity Cache; with the other encoders' ops in between it
     // comes from HBM.  Measured on mulmo_unet (8.93 ms sequential, same box): lockstep over all four levels 9.23 ms, levels <= 256^2
     // 9.14, <= 128^2 9.00, <= 64^2 9.02 -- so only the two deep levels are candidates for shared launches.
-    static const int max_h = getenv("DNNCA_LOCKSTEP_MAXH") ? atoi(getenv("DNNCA_LOCKSTEP_MAXH")) : 128;
+    const int max_h = sw.lockstep_maxh;
     int j0 = 0;          // first op (relative index) of the lockstep part
     while (ne && j0 < enc_ops && ops[j0].out.d.H > max_h) ++j0;
     if (!backward) {
@@ -523,8 +574,7 @@ int Model::forward(const float* x_dev, int B, bool training) {
     label_part_valid = false;
     const float* labels_in_first_block = nullptr;
     if (head_in_conv_ok) {
-        static const bool fuse_labels = getenv("DNNCA_NO_LABEL_FUSION") == nullptr;
-        if (fuse_labels && fast_head_in_conv_possible(this) && ops[0].type == OP_CONV && !ops[0].need_din && ops[0].out.d.H == outH &&
+        if (!sw.no_label_fusion && fast_head_in_conv_possible(this) && ops[0].type == OP_CONV && !ops[0].need_din && ops[0].out.d.H == outH &&
             ops[0].out.d.W == outW)
             labels_in_first_block = head_in_conv.y;
         else
@@ -731,7 +781,6 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
                     if (lo <= prev) { bucket_state = -1; break; }
                     prev = lo;
                 }
-                if (const char* e = getenv("DNNCA_BUCKET_BYTES")) bucket_bytes = (size_t)atol(e) > 4096 ? (size_t)atol(e) : 4096;
             }
             bucketing = bucket_state == 1;
             bucket_hi = bucket_fin = nT;
@@ -749,7 +798,7 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
                 int64_t lo = d.w_off >= 0 ? d.w_off : d.b_off;
                 if (d.b_off >= 0 && d.b_off < lo) lo = d.b_off;
                 if (lo >= 0 && lo < bucket_fin) bucket_fin = lo;
-                if ((size_t)(bucket_hi - bucket_fin) * 4 >= bucket_bytes) {
+                if ((size_t)(bucket_hi - bucket_fin) * 4 >= sw.bucket_bytes) {
                     DN_TRY(send_bucket(bucket_fin, bucket_hi));
                     bucket_hi = bucket_fin;
                 }
@@ -1284,8 +1333,7 @@ static int train_step_impl(Model* M, const float* x_dev, const float* y_dev, int
                            dnnca_step_out* out, int row) {
     if (!cfg) { set_error("null loss cfg"); return DNNCA_EINVAL; }
     M->defer_head = true;
-    // (label smoothing blurs the labels in loss_and_backward first: then the head cannot run inside the forward pass)
-    M->head_in_conv.requested = !cfg->label_smoothing && M->merged_launches() && !getenv("DNNCA_NO_HEAD_IN_CONV");
+    M->head_in_conv.requested = head_in_conv_requested(M, *cfg);
     M->head_in_conv.y = y_dev;
     M->head_in_conv.cfg = *cfg;
     int frc = M->forward(x_dev, batch, true);
@@ -1695,7 +1743,7 @@ int dnnca_comm_init(void* model, int rank, int world, const void* unique_id, siz
     M->rank = rank;
     M->world = world;
     // DNNCA_FORCE_RCCL: build a one-rank communicator too, so every collective of the DP path can be exercised on one GPU
-    if (world == 1 && !(getenv("DNNCA_FORCE_RCCL") && unique_id)) return DNNCA_OK;
+    if (world == 1 && !(M->sw.force_rccl && unique_id)) return DNNCA_OK;
     if (!unique_id || id_len < sizeof(ncclUniqueId)) { set_error("unique id too short"); return DNNCA_EINVAL; }
     ncclUniqueId id;
     memcpy(&id, unique_id, sizeof(id));
@@ -1866,7 +1914,7 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
     int rc;
     if (pass == DNNCA_PLAN_TRAIN) {
         M->defer_head = true;
-        M->head_in_conv.requested = !getenv("DNNCA_NO_HEAD_IN_CONV");
+        M->head_in_conv.requested = head_in_conv_requested(M, cfg);
         M->head_in_conv.y = M->y_stage;
         M->head_in_conv.cfg = cfg;
         rc = M->forward(M->x_stage, B, true);

@@ -980,6 +980,46 @@ def test_strip_kernels_match_the_per_layer_kernels(gpu, monkeypatch, B, H, W):
     del rng
 
 
+def test_switches_are_fixed_when_the_model_is_built(gpu, monkeypatch):
+    """The step's switch table is read once per model (StepSwitches, Model::build): a variable set after a model was created does not
+    reach it, so no two launch decisions of one model can disagree.  (2, 64, 256): whole tiles at every level, every fused launcher
+    is in the default plan.  Model A is built with a clean environment; then the ten switches of
+    test_strip_kernels_match_the_per_layer_kernels are set and model B is built: A's plans and A's train step are unchanged, B
+    runs the per-layer launches, and both compute the same loss."""
+    from dnncancerannotator_amd.synthetic import synthetic_batch
+    B, H, W = 2, 64, 256
+    ten = ('DNNCA_NO_TAIL3', 'DNNCA_NO_FIRST3', 'DNNCA_NO_FIRST3F', 'DNNCA_NO_UP3F', 'DNNCA_NO_TCF', 'DNNCA_NO_FOLD_ADAM', 'DNNCA_NO_PREP_RIDE',
+           'DNNCA_NO_TCONV_RIDE', 'DNNCA_NO_TCM', 'DNNCA_NO_FUSED_BWD')
+    for k in ten:
+        monkeypatch.delenv(k, raising=False)
+    x, y = synthetic_batch(B, H, W, 1)
+
+    def plans(m):
+        return [m.plan(variants=True, mode=mode) for mode in ('train', 'eval', 'forward')]
+
+    a = gpu.DeviceModel('unet', 1, H, W, B, **UNET)
+    a.init_glorot(seed=2)
+    params = a.get_params()
+    recorded = plans(a)
+    for k in ten:
+        monkeypatch.setenv(k, '1')
+    b = gpu.DeviceModel('unet', 1, H, W, B, **UNET)
+    b.set_params(params)
+    assert plans(a) == recorded
+    a.profile_enable(1)
+    la = a.train_step(x, y, 0.0, a.loss_cfg(weight_mul=3.0)).loss
+    ran = set(r[0] for r in a.profile())
+    assert {'tail3_3x1_3', 'first3_fwd', 'fzb_up_6'} <= ran, ran
+    fused = {'tail3_3x1_3', 'first3_fwd', 'up3_fwd', 'fz_up_tc_12_12', 'fzb_up_6', 'fzb_up_12', 'fzb_down_6_12', 'fzb_down_3_6', 'first3_bwd'}
+    plan_b = set(r[0] for r in b.plan())
+    assert not (fused & plan_b), plan_b
+    lb = b.train_step(x, y, 0.0, b.loss_cfg(weight_mul=3.0)).loss
+    print('loss A %r, loss B %r' % (la, lb))
+    assert abs(la - lb) <= 1e-5 * max(1.0, abs(lb))
+    a.close()
+    b.close()
+
+
 def test_rccl_one_rank_rehearsal(gpu):
     """The RCCL calls of the DP path (unique id, communicator, gradient all-reduce on the step's stream, broadcast,
     state average, host all-reduce) on a one-rank communicator: a sum over one rank is the identity, so weights, BN

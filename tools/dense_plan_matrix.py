@@ -6,7 +6,11 @@ libraries are compared by running it once per library and diffing the two output
     DNNCA_LIB=<b>/libdnnca.so python tools/dense_plan_matrix.py dump out_b
     python tools/dense_plan_matrix.py compare out_a out_b
 
-A dry plan launches nothing, so the whole matrix takes a minute or two."""
+A dry plan launches nothing, so the whole matrix takes a minute or two.
+
+A third argument `step` (`dump out_a step`) takes the matrix of the small-channel step instead: the configs/unet.yaml model at the
+shapes that reach its pixel-group, column-strip and block-fused launchers, the train, eval and forward plans at max_batch and at one
+image, by default and under every switch of the per-model table (StepSwitches), one child process per arm."""
 
 import filecmp
 import os
@@ -49,13 +53,45 @@ ARMS = [{}] + [{k: '1'} for k in (
     {'DNNCA_NO_X3': '1', 'DNNCA_NO_WG_PLAIN': '1'}, {'DNNCA_NO_X3_WGRAD': '1', 'DNNCA_IG_NW': '8'}]
 
 
+YAML = dict(FULL, n_filters_first=3, n_downsample=3, bn=False)
+# (name, batch, H, W, further DeviceModel options, train_metrics): whole tiles at every level / partial strips, the 12-channel level on
+# the generic conv / one chunk / ... / the pool fold declines / the PROB variants of the head launches
+STEP_SHAPES = [
+    ('yaml_512_b8', 8, 512, 512, {}, False), ('b2_64x256', 2, 64, 256, {}, False), ('b3_24x200', 3, 24, 200, {}, False),
+    ('b1_8x64', 1, 8, 64, {}, False), ('b2_40x128', 2, 40, 128, {}, False), ('b5_32x248', 5, 32, 248, {}, False),
+    ('b2_64x256_leaky', 2, 64, 256, dict(leaky_alpha=0.3), False), ('b2_64x256_metrics', 2, 64, 256, {}, True),
+]
+TEN = ('DNNCA_NO_TAIL3', 'DNNCA_NO_FIRST3', 'DNNCA_NO_FIRST3F', 'DNNCA_NO_UP3F', 'DNNCA_NO_TCF', 'DNNCA_NO_FOLD_ADAM', 'DNNCA_NO_PREP_RIDE',
+       'DNNCA_NO_TCONV_RIDE', 'DNNCA_NO_TCM', 'DNNCA_NO_FUSED_BWD')      # tests/test_engine_gpu.py: the strip kernels against the per-layer ones
+STEP_ARMS = [{}] + [{k: '1'} for k in TEN + (
+    'DNNCA_NO_FUSED', 'DNNCA_NO_POOL_FOLD', 'DNNCA_NO_BWD3V', 'DNNCA_NO_VW', 'DNNCA_NO_HEAD_IN_CONV', 'DNNCA_NO_LABEL_FUSION',
+    'DNNCA_NO_WG_STREAM', 'DNNCA_FZ_UP2', 'DNNCA_FZ_ALL', 'DNNCA_LOCKSTEP', 'DNNCA_FORCE_RCCL', 'DNNCA_STAMPS_PF', 'DNNCA_DBG', 'DNNCA_FZB_DBG',
+    'DNNCA_F3F_ABL', 'DNNCA_ABL', 'DNNCA_TAIL3_VARIANT')] + [
+    {'DNNCA_FZ_ONLY': 'down1'}, {'DNNCA_FZ_ONLY': 'up1'}, {'DNNCA_FZB_ONLY': 'down2'}, {'DNNCA_FZB_ONLY': 'up1'}, {'DNNCA_STAMPS': '3,2,3'},
+    {'DNNCA_NBLOCKS': '64'}, {'DNNCA_PG_MAXOCC': '2'}, {'DNNCA_TAIL3_SLOTS': '1024'}, {'DNNCA_TAIL3_LDS': '32768'}, {'DNNCA_LOCKSTEP_MAXH': '64'},
+    {'DNNCA_WG_PRIO': '2'}, {'DNNCA_BUCKET_BYTES': '262144'},
+    {k: '1' for k in TEN}, {'DNNCA_NO_TAIL3': '1', 'DNNCA_NO_FIRST3': '1'}, {'DNNCA_NO_TAIL3': '1', 'DNNCA_NO_HEAD_IN_CONV': '1'}]
+
+
 def arm_name(arm):
     return '+'.join('%s=%s' % kv for kv in sorted(arm.items())) or 'default'
 
 
-def child(out_dir):
+def child(out_dir, step):
     from dnncancerannotator_amd import device
     device.init_device(0)
+    for name, B, H, W, opts, metrics in STEP_SHAPES if step else []:
+        m = device.DeviceModel('unet', 1, H, W, B, **YAML, **opts)
+        if metrics:
+            m.train_metrics([0.25, 0.5, 0.75])
+        for mode in ('train', 'eval', 'forward'):
+            for batch in sorted({B, 1}):
+                with open(os.path.join(out_dir, '%s.%s.b%d.plan' % (name, mode, batch)), 'w') as f:
+                    for k, b, fl in m.plan(variants=True, mode=mode, batch=batch):
+                        f.write('%s\t%r\t%r\n' % (k, b, fl))
+        m.close()
+    if step:
+        return
     for name, arch, C, H, W, B, opts in SHAPES:
         for dtype in ('f32', 'bf16'):
             m = device.DeviceModel(arch, C, H, W, B, dtype=dtype, **opts)
@@ -65,11 +101,12 @@ def child(out_dir):
             m.close()
 
 
-def dump(out):
-    for arm in ARMS:
-        d = os.path.join(out, arm_name(arm))
+def dump(out, step):
+    for arm in STEP_ARMS if step else ARMS:
+        d = os.path.join(out, arm_name(arm) if len(arm) < 10 else 'TEN')
         os.makedirs(d, exist_ok=True)
-        subprocess.run([sys.executable, os.path.abspath(__file__), 'child', d], env=dict(os.environ, **arm), check=True, timeout=300)
+        subprocess.run([sys.executable, os.path.abspath(__file__), 'child', d] + ['step'] * step, env=dict(os.environ, **arm), check=True,
+                       timeout=300)
         print('dumped', arm_name(arm), flush=True)
 
 
@@ -90,8 +127,8 @@ def compare(a, b):
 
 if __name__ == '__main__':
     if sys.argv[1] == 'child':
-        child(sys.argv[2])
+        child(sys.argv[2], sys.argv[3:] == ['step'])
     elif sys.argv[1] == 'dump':
-        dump(sys.argv[2])
+        dump(sys.argv[2], sys.argv[3:] == ['step'])
     else:
         sys.exit(compare(sys.argv[2], sys.argv[3]))

@@ -71,7 +71,7 @@ def run_big(force, bucket_bytes=None):
 def main():
     dev.init_device(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'big':
-        # DNNCA_BUCKET_BYTES is read once per process: this process runs with the value the parent chose
+        # DNNCA_BUCKET_BYTES is read when a model is created: this process runs with the value the parent chose
         p, q, r = run_big(False), run_big(True), run_big(False)
         rel = lambda u, v: float(np.abs(u - v).max() / (np.abs(u).max() + 1e-30))       # noqa: E731
         print(json.dumps(dict(n=q['n'], calls=q['calls'], calls_plain=p['calls'], diff_params=rel(p['params'], q['params']),
