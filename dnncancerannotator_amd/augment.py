@@ -19,7 +19,27 @@ import numpy as np
 
 AugmentPlan = namedtuple('AugmentPlan', ['crop', 'flip', 'contrast', 'warp', 'output_size', 'intrawarp'], defaults=(None,))
 # warp: (ctrl, wv) or None; intrawarp: (ctrl [B, G, n, 2], wv [B, G, n + 3, 2], group_of [Cs]: group of every raw-slice channel) or None
-RawBatch = namedtuple('RawBatch', ['raw', 'params', 'output_size', 'label_index', 'warp', 'intrawarp'], defaults=(None,))
+# contrast_channels: the raw-slice channels random_contrast adjusts (target_channels), None: every feature channel
+RawBatch = namedtuple('RawBatch', ['raw', 'params', 'output_size', 'label_index', 'warp', 'intrawarp', 'contrast_channels'],
+                      defaults=(None, None))
+
+
+def contrast_channels(plan, n_channels, label_index):
+    """random_contrast's `target_channels` (data.py:586-609 gathers exactly the named channels of the raw slice, adjusts them and
+    puts them back) as the tuple dnnca_augment_u8 takes, checked against the slice: an index outside the `n_channels` raw channels,
+    or the label's, is a ValueError (the reference would fail in tf.gather, or adjust the label).  None -- no random_contrast, or no
+    `target_channels` -- keeps this project's default: EVERY feature channel, wherever the label stands.  The reference's own
+    default is range(len(slice_types) - 1) (data.py:91), which is the same set only when the label is the last slice type; with
+    the label elsewhere it would adjust the label and skip the last feature channel.  The project keeps "every feature channel"."""
+    if plan is None or plan.contrast is None or plan.contrast.get('target_channels') is None:
+        return None
+    out = tuple(int(c) for c in plan.contrast['target_channels'])
+    for c in out:
+        if not 0 <= c < n_channels:
+            raise ValueError('random_contrast: target channel %d is outside the %d channels of the raw slice' % (c, n_channels))
+        if c == label_index:
+            raise ValueError('random_contrast: target channel %d is the label channel' % c)
+    return out
 
 
 

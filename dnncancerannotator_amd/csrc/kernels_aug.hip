@@ -166,6 +166,10 @@ int dnnca_augment_u8(void* model, const void* src_dev, int batch, int hs, int ws
 // n control points c_i (the *destination* points) and the weights (w, v), and samples features and label with the same flow.
 namespace dnnca {
 
+// a launch gets 64 KB of dynamic LDS without opting in; the coefficients of one spline take n * 4 + 6 doubles of it
+constexpr size_t WARP_LDS_MAX = 64u << 10;
+constexpr int WARP_MAX_POINTS = (int)((WARP_LDS_MAX / 8 - 6) / 4);      // 2046
+
 struct WarpArgs {
     const float* x;          // [B, H, W, C] source features
     const float* y;          // [B, H, W] source label
@@ -225,8 +229,13 @@ int dnnca_warp_f32(void* model, const float* x_dev, const float* y_dev, int batc
     Model* M = reinterpret_cast<Model*>(model);
     if (!M) { set_error("null model"); return DNNCA_EINVAL; }
     if (!x_dev || !y_dev || !ctrl_host || !wv_host || !x_out_dev || !y_out_dev || batch < 1 || h < 2 || w < 2 || c < 1 || n_points < 1 ||
-        n_points > 2048 || x_out_dev == x_dev || y_out_dev == y_dev) {
+        x_out_dev == x_dev || y_out_dev == y_dev) {
         set_error("dnnca_warp_f32: bad arguments");
+        return DNNCA_EINVAL;
+    }
+    if (n_points > WARP_MAX_POINTS) {
+        set_error("dnnca_warp_f32: %d control points, at most %d (their %zu bytes of coefficients must fit %zu bytes of LDS)", n_points,
+                  WARP_MAX_POINTS, (size_t)(n_points * 4 + 6) * 8, WARP_LDS_MAX);
         return DNNCA_EINVAL;
     }
     const size_t nc = (size_t)batch * n_points * 2 * 8, nw = (size_t)batch * (n_points + 3) * 2 * 8;
@@ -350,8 +359,13 @@ int dnnca_warp_groups_f32(void* model, const float* x_dev, const float* y_dev, i
     Model* M = reinterpret_cast<Model*>(model);
     if (!M) { set_error("null model"); return DNNCA_EINVAL; }
     if (!x_dev || !y_dev || !group_of || !ctrl_host || !wv_host || !x_out_dev || !y_out_dev || batch < 1 || batch > 65535 || h < 2 || w < 2 ||
-        c < 1 || n_points < 1 || n_points > 2048 || x_out_dev == x_dev || y_out_dev == y_dev) {
+        c < 1 || n_points < 1 || x_out_dev == x_dev || y_out_dev == y_dev) {
         set_error("dnnca_warp_groups_f32: bad arguments");
+        return DNNCA_EINVAL;
+    }
+    if (n_points > WARP_MAX_POINTS) {
+        set_error("dnnca_warp_groups_f32: %d control points, at most %d (their %zu bytes of coefficients must fit %zu bytes of LDS)",
+                  n_points, WARP_MAX_POINTS, (size_t)(n_points * 4 + 6) * 8, WARP_LDS_MAX);
         return DNNCA_EINVAL;
     }
     if (n_groups < 1 || n_groups > c + 1) {
@@ -403,7 +417,7 @@ int dnnca_warp_groups_f32(void* model, const float* x_dev, const float* y_dev, i
     const double bytes = (double)batch * h * w * (c + 1) * 8.0, flops = (double)batch * h * w * n_groups * n_points * 8.0;
     // DNNCA_WARP_GROUPS_PIXEL (tuning aid, read per call: tools/intrawarp_rate.py flips it): the pixel-per-thread layout, where its
     // G coefficient sets fit the 64 KB of LDS a launch gets without opting in
-    if (getenv("DNNCA_WARP_GROUPS_PIXEL") != nullptr && lds * n_groups <= (64u << 10))
+    if (getenv("DNNCA_WARP_GROUPS_PIXEL") != nullptr && lds * n_groups <= WARP_LDS_MAX)
         LAUNCH(M, "aug_warp_groups", bytes, flops,
                hipLaunchKernelGGL(k_warp_groups<true>, dim3(bx, batch), dim3(256), lds * n_groups, M->stream, a));
     else

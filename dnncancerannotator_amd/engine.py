@@ -333,7 +333,8 @@ class TFKerasModel:
                     _, slot, src, batch, n = item
                     feeder.ring.wait(slot)
                     params, _ = shard(batch.params)
-                    xb, yb = dm.augment_u8(shard(batch.raw)[0], params, batch.output_size, batch.label_index, src_ptr=src)
+                    xb, yb = dm.augment_u8(shard(batch.raw)[0], params, batch.output_size, batch.label_index,
+                                           contrast_channels=batch.contrast_channels, src_ptr=src)
                     if batch.warp is not None:
                         xb, yb = dm.warp(xb, yb, shard(batch.warp[0])[0], shard(batch.warp[1])[0])
                     if batch.intrawarp is not None:      # after random_warp: the overlay's key comes behind data_options.yaml's
@@ -347,7 +348,7 @@ class TFKerasModel:
                         # uint8 slices + their random draws: crop / flip / contrast / 255 / feature-label split on the device
                         raw, _ = shard(batch.raw)
                         params, _ = shard(batch.params)
-                        xb, yb = dm.augment_u8(raw, params, batch.output_size, batch.label_index)
+                        xb, yb = dm.augment_u8(raw, params, batch.output_size, batch.label_index, contrast_channels=batch.contrast_channels)
                         if batch.warp is not None:
                             xb, yb = dm.warp(xb, yb, shard(batch.warp[0])[0], shard(batch.warp[1])[0])
                         if batch.intrawarp is not None:

@@ -329,6 +329,8 @@ class TFRecordDataset:
         self.plan = None if augment_options is False else augment.parse_augment_options(augment_options, self.output_size)
         if self.plan is not None:
             self.output_size = self.plan.output_size
+        # random_contrast.target_channels, checked here so that a bad index fails when the dataset is built
+        self.contrast_channels = augment.contrast_channels(self.plan, len(self.slice_types), self.label_idx)
         self.include_meta = bool(include_meta)
         if self.include_meta and self.plan is not None:
             raise ValueError('include_meta is for evaluation datasets (augment_options=False)')
@@ -531,7 +533,7 @@ class TFRecordDataset:
         m = max(abs(int(self.plan.crop['min_'])), abs(int(self.plan.crop['max_']))) if self.plan.crop is not None else 0
         oh, ow = self.output_size
         mine = [self._centre(r[None], min(r.shape[0], oh + 2 * m), min(r.shape[1], ow + 2 * m))[0] for r in self._mine(raws)]
-        return augment.RawBatch(np.stack(mine), params, self.output_size, self.label_idx, warp, intrawarp)
+        return augment.RawBatch(np.stack(mine), params, self.output_size, self.label_idx, warp, intrawarp, self.contrast_channels)
 
     def _stacked(self, xs, ys):
         mx, my = self._mine(xs), self._mine(ys)

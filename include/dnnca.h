@@ -152,7 +152,10 @@ int dnnca_augment_u8(void* model, const void* src_dev, int batch, int hs, int ws
    ctrl_host [batch, n_points, 2] = the destination control points (row, column); wv_host [batch, n_points + 3, 2] = the solution
    (w; v) of the polyharmonic-spline system for the control-point flows (dest - source), solved by the caller
    (dnncancerannotator_amd/augment.py solve_warp).  Every output pixel q evaluates flow(q) and samples x [batch, h, w, c] and
-   y [batch, h, w] bilinearly at q - flow(q) (tfa dense_image_warp); outputs must not alias the inputs. */
+   y [batch, h, w] bilinearly at q - flow(q) (tfa dense_image_warp); outputs must not alias the inputs.
+   1 <= n_points <= 2046: the n_points * 4 + 6 doubles of one spline live in LDS and must fit the 64 KB a launch gets without
+   opting in; more is DNNCA_EINVAL (the message names the limit) and nothing is launched.  The same bound holds for
+   dnnca_warp_groups_f32. */
 int dnnca_warp_f32(void* model, const float* x_dev, const float* y_dev, int batch, int h, int w, int c, int n_points,
                    const double* ctrl_host, const double* wv_host, float* x_out_dev, float* y_out_dev);
 /* random_intrachannelwarp (annotator/data.py:656-715): the channels of a slice, label included, are split into n_groups groups

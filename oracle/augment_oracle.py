@@ -49,26 +49,44 @@ def augment_batch(raw_u8, params, output_size, label_index, target_channels=None
     return np.stack(xs), np.stack(ys)
 
 
-def warp_image(img, source, dest):
-    """tfa.image.sparse_image_warp on one float image [H, W, C] (float64 arithmetic); source / dest [n, 2] (row, column)."""
-    img = np.asarray(img, np.float64)
-    h, w, _ = img.shape
+def _phi(r):
+    return 0.5 * r * np.log(np.maximum(r, 1e-10))
+
+
+def solve_warp_coeffs(source, dest):
+    """tfa interpolate_spline's system (order 2, no regularisation): (ctrl [n, 2] = dest, wv [n + 3, 2]), float64"""
     c = np.asarray(dest, np.float64)
     f = c - np.asarray(source, np.float64)
     k = len(c)
-    phi = lambda r: 0.5 * r * np.log(np.maximum(r, 1e-10))                      # noqa: E731
     lhs = np.zeros((k + 3, k + 3))
-    lhs[:k, :k] = phi(((c[:, None] - c[None]) ** 2).sum(-1))
+    lhs[:k, :k] = _phi(((c[:, None] - c[None]) ** 2).sum(-1))
     lhs[:k, k:k + 2] = c
     lhs[:k, k + 2] = 1.0
     lhs[k:, :k] = lhs[:k, k:].T
     rhs = np.zeros((k + 3, 2))
     rhs[:k] = f
-    wv = np.linalg.solve(lhs, rhs)
+    return c, np.linalg.solve(lhs, rhs)
+
+
+def warp_flow(h, w, ctrl, wv):
+    """the float64 flow [h * w, 2] of the spline (ctrl [n, 2], wv [n + 3, 2]: n weight rows, then the rows of the linear term
+    [q, 1] v) at every pixel q = (row, column), rows first"""
+    c, wv = np.asarray(ctrl, np.float64), np.asarray(wv, np.float64)
+    k = len(c)
     qy, qx = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing='ij')
     q = np.stack([qy, qx], -1).reshape(-1, 2)
-    flow = phi(((q[:, None] - c[None]) ** 2).sum(-1)) @ wv[:k] + np.concatenate([q, np.ones((len(q), 1))], 1) @ wv[k:]
-    s = q - flow
+    return _phi(((q[:, None] - c[None]) ** 2).sum(-1)) @ wv[:k] + np.concatenate([q, np.ones((len(q), 1))], 1) @ wv[k:]
+
+
+def warp_image_coeffs(img, ctrl, wv):
+    """tfa dense_image_warp of one float image [H, W, C] under the spline given by its coefficients (float64 arithmetic): bilinear
+    sampling at q - flow(q), floor clamped to [0, size - 2], alpha clipped to [0, 1].  The coefficients need not come from a solve:
+    a test may choose them (zero, a pure shift in the linear rows, many points with small weights)."""
+    img = np.asarray(img, np.float64)
+    h, w, _ = img.shape
+    qy, qx = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing='ij')
+    q = np.stack([qy, qx], -1).reshape(-1, 2)
+    s = q - warp_flow(h, w, ctrl, wv)
     fy = np.clip(np.floor(s[:, 0]), 0, h - 2)
     fx = np.clip(np.floor(s[:, 1]), 0, w - 2)
     ay = np.clip(s[:, 0] - fy, 0, 1)[:, None]
@@ -77,3 +95,8 @@ def warp_image(img, source, dest):
     tl, tr, bl, br = img[iy, ix], img[iy, ix + 1], img[iy + 1, ix], img[iy + 1, ix + 1]
     top, bot = ax * (tr - tl) + tl, ax * (br - bl) + bl
     return (ay * (bot - top) + top).reshape(h, w, -1)
+
+
+def warp_image(img, source, dest):
+    """tfa.image.sparse_image_warp on one float image [H, W, C] (float64 arithmetic); source / dest [n, 2] (row, column)."""
+    return warp_image_coeffs(img, *solve_warp_coeffs(source, dest))
