@@ -1,4 +1,4 @@
-"""CLI: `python3 -m dnncancerannotator_amd {train,evaluate} ...` (also reachable as `python3 -m annotator ...`).
+"""CLI: `python3 -m dnncancerannotator_amd {train,evaluate,predict} ...` (also reachable as `python3 -m annotator ...`).
 
 Flag surface of the reference (README.md:16-120; runs/train.py:21-54, runs/evaluate.py:21-64), re-stated with argparse
 because dsargparse (requirements.txt:11) is not available."""
@@ -37,6 +37,18 @@ def build_parser(prog='python3 -m annotator'):
     e.add_argument('--overlay', action='store_true')
     e.add_argument('--skip_visualization', action='store_true')
     e.add_argument('--export_casewise_metrics', action='store_true')
+    p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
+    p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
+    p.add_argument('--data_path', nargs='+', required=True)
+    p.add_argument('--output', required=True, help='where lesions.csv, slices.csv and the masks go')
+    p.add_argument('--config', nargs='+', default=None)
+    p.add_argument('--step', type=int, default=None, help='checkpoint step (default: the latest)')
+    p.add_argument('--threshold', type=float, default=0.5, help='probability threshold (default: 0.5)')
+    p.add_argument('--min_area', type=int, default=0, help='smallest lesion kept, in pixels of the analysed plane')
+    p.add_argument('--filter_size', type=int, default=5, help='morphological opening, 1..15 (1: none; default: 5)')
+    p.add_argument('--resize_factor', type=float, default=1.0, help='analyse the probabilities resized by this factor')
+    p.add_argument('--max_lesions', type=int, default=256, help='lesions per slice in lesions.csv (default: 256)')
+    p.add_argument('--export_images', action='store_true', help='also write <exam>/<slice>/mask.png')
     return parser
 
 
@@ -53,6 +65,9 @@ def main(argv=None, prog='python3 -m annotator'):
         rows = evaluate(**args)
         for step, r in (rows or {}).items():
             print(step, dict(r))
+    elif command == 'predict':
+        from .runs.predict import predict
+        print(predict(**args))
     else:
         parser.print_help()
         return 2

@@ -61,6 +61,16 @@ class RegionCounts(C.Structure):                   # dnnca_region_counts
     _fields_ = [('tp_label', C.c_int64), ('fn', C.c_int64), ('tp_pred', C.c_int64), ('fp', C.c_int64)]
 
 
+class LesionRow(C.Structure):                      # dnnca_lesion_row (56 bytes, no padding)
+    _fields_ = [('slice', C.c_int32), ('row', C.c_int32), ('area', C.c_int32), ('x0', C.c_int32), ('y0', C.c_int32),
+                ('x1', C.c_int32), ('y1', C.c_int32), ('max_prob', C.c_float), ('sum_x', C.c_uint64), ('sum_y', C.c_uint64),
+                ('sum_prob_q24', C.c_uint64)]
+
+
+# the same record as a numpy dtype: DeviceModel.lesion_table returns its rows as a structured array
+LESION_ROW_DTYPE = np.dtype([('slice', '<i4'), ('row', '<i4'), ('area', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'),
+                             ('y1', '<i4'), ('max_prob', '<f4'), ('sum_x', '<u8'), ('sum_y', '<u8'), ('sum_prob_q24', '<u8')])
+
 _FP = C.POINTER(C.c_float)
 _VP = C.c_void_p
 
@@ -124,6 +134,9 @@ SIGNATURES = {
     'dnnca_eval_region_end': (C.c_int, [_VP, C.POINTER(RegionCounts)]),
     'dnnca_region_confusion_slices': (C.c_int, [_VP, _FP, _FP, C.c_int, C.POINTER(RegionSpec), C.c_int, C.POINTER(RegionCounts)]),
     'dnnca_render_composite': (C.c_int, [_VP, _FP, C.c_int, C.c_float, C.c_int, _VP, C.c_int64, C.POINTER(C.c_int32)]),
+    'dnnca_lesion_table': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
+                                     C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
+                                     C.POINTER(C.c_int32)]),
     'dnnca_input_sensitivity': (C.c_int, [_VP, _FP, C.c_int, C.POINTER(C.c_double)]),
     'dnnca_comm_unique_id': (C.c_int, [_VP]),
     'dnnca_comm_init': (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_size_t]),

@@ -166,6 +166,38 @@ def sensitivity_chart(values):
     return img
 
 
+# ---- `annotator predict`: the lesion table of slices without a label (DeviceModel.lesion_table gives the integer sums) ----------
+LESION_COLUMNS = ['exam', 'slice', 'lesion', 'area_px', 'x0', 'y0', 'x1', 'y1', 'centroid_x', 'centroid_y', 'mean_prob', 'max_prob']
+SLICE_COLUMNS = ['exam', 'slice', 'n_lesions', 'lesion_area_px', 'max_prob', 'truncated']
+Q24 = float(1 << 24)             # sum_prob_q24 is the sum of rint(p * 2^24)
+
+
+def lesion_values(exam, slice_id, row):
+    """one record of lesion_table's rows -> the values of its lesions.csv line.  centroid = sum / area and mean = sum_q24 / area /
+    2^24 in float64 (repr, so they read back exactly); max_prob with the 9 digits that give the float32 back"""
+    area = int(row['area'])
+    return [exam, int(slice_id), int(row['row']), area, int(row['x0']), int(row['y0']), int(row['x1']), int(row['y1']),
+            repr(int(row['sum_x']) / area), repr(int(row['sum_y']) / area), repr(int(row['sum_prob_q24']) / area / Q24),
+            '%.9g' % float(row['max_prob'])]
+
+
+def slice_values(exam, slice_id, rows, total):
+    """the slices.csv line of one slice: `rows` are the slice's records (at most max_lesions), `total` its kept components.
+    n_lesions = total; lesion_area_px and max_prob cover the rows that came back; truncated = 1 when total exceeds them"""
+    return [exam, int(slice_id), int(total), int(sum(int(r['area']) for r in rows)),
+            '%.9g' % max([float(r['max_prob']) for r in rows], default=0.0), int(int(total) > len(rows))]
+
+
+def plain_csv(names, rows):
+    """a header line and one line per row, csv-module quoting, no index column"""
+    return _csv([list(names)] + [list(r) for r in rows])
+
+
+def mask_path(root, tag):
+    """<root>/<last 3 components of the exam path>/<sliceID %02d>/mask.png"""
+    return os.path.join(export_dir(root, '', tag), 'mask.png')
+
+
 def _chunk(kind, data):
     return struct.pack('>I', len(data)) + kind + data + struct.pack('>I', zlib.crc32(kind + data) & 0xFFFFFFFF)
 

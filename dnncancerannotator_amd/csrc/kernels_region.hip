@@ -24,6 +24,7 @@
 //                   as region_prep), * 255 truncated to uint8; the panels are read in place through an index map, four output
 //                   bytes per thread and one 32-bit store
 #include <math.h>
+#include <string.h>
 
 #include <algorithm>
 
@@ -416,6 +417,150 @@ __global__ __launch_bounds__(RB) void k_region_render(const float* __restrict__ 
     out[word] = packed;
 }
 
+// ---- lesion table (dnnca_lesion_table).  One prediction plane (T = 1): a pixel's index over the chunk is g = b * hw + p and its
+// parent L[g]; S[g] is the size of the component rooted at g.
+constexpr int kScanU = 16;               // lesion_scan: pixels per thread and pass (kScanU x RB / 64 = 64 wave counts: one wave scans them)
+static_assert(kScanU * (RB / 64) == 64, "lesion_scan scans its wave counts with one wave");
+
+// Kept roots (L[g] == g, S[g] >= min_area) numbered per slice in raster order: row[g] = the number at a kept root, -1 at every other
+// pixel; total[b] = kept roots of slice b.  One block per slice walks it in passes of kScanU * RB pixels: a ballot per wave and 64
+// pixels, the pass's 64 wave counts scanned by every wave on its own (shuffles, no second barrier; the count buffer alternates
+// between passes), and the running count carried from pass to pass in a register.  No atomic: the order is the data's.
+__global__ __launch_bounds__(RB) void k_lesion_scan(const int* __restrict__ L, const unsigned* __restrict__ S, int hw, unsigned min_area,
+                                                    int* __restrict__ row, int* __restrict__ total) {
+    __shared__ int cnt[2][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t g0 = (size_t)blockIdx.x * hw;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int carry = 0, buf = 0;
+    for (int base = 0; base < hw; base += kScanU * RB, buf ^= 1) {
+        unsigned keep = 0;               // bit u: this thread's pixel u of the pass is a kept root
+        int pre[kScanU];                 // kept roots of the same wave and u on lower lanes
+#pragma unroll
+        for (int u = 0; u < kScanU; ++u) {
+            const int p = base + u * RB + (int)threadIdx.x;
+            bool k = false;
+            if (p < hw) {
+                const size_t g = g0 + p;
+                k = L[g] == (int)g && S[g] >= min_area;
+            }
+            const unsigned long long bal = __ballot(k);
+            pre[u] = __popcll(bal & below);
+            keep |= (k ? 1u : 0u) << u;
+            if (lane == 0) cnt[buf][u * (RB / 64) + wv] = __popcll(bal);
+        }
+        __syncthreads();
+        // inclusive scan of the 64 counts over the lanes (count u * 4 + wave in lane u * 4 + wave: raster order)
+        const int c = cnt[buf][lane];
+        int inc = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(inc, o);
+            if (lane >= o) inc += t;
+        }
+        const int exc = inc - c, pass_total = __shfl(inc, 63);
+#pragma unroll
+        for (int u = 0; u < kScanU; ++u) {
+            const int off = __shfl(exc, u * (RB / 64) + wv);
+            const int p = base + u * RB + (int)threadIdx.x;
+            if (p < hw) row[g0 + p] = ((keep >> u) & 1u) ? carry + off + pre[u] : -1;
+        }
+        carry += pass_total;
+    }
+    if (threadIdx.x == 0) total[blockIdx.x] = carry;
+}
+
+struct LesionAcc {                       // one row of the device table, zeroed by a memset: nx0 / ny0 hold max(~x) = ~min(x)
+    unsigned long long sx, sy, sq;
+    unsigned area, nx0, ny0, x1, y1, mp;
+};
+
+__device__ __forceinline__ unsigned wave_max(unsigned v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// every foreground pixel adds itself to the row of its root (rows below `cap` only).  The lanes of a wave that carry the same row
+// are reduced first -- wave_grouped's loop over the distinct keys of the wave, here with sums and extrema instead of a count -- and
+// the group's first lane issues the atomics: a lesion of 260 k pixels is 4 k groups, not 260 k atomics per field.  The probability
+// is the one region_prep thresholded (resize_at); max through the bits (non-negative floats order like their bits).
+__global__ __launch_bounds__(RB) void k_lesion_stats(const float* __restrict__ src, Resize r, int nb, const int* __restrict__ L,
+                                                     const int* __restrict__ row, int cap, LesionAcc* __restrict__ acc) {
+    const size_t hw = (size_t)r.out_h * r.out_w, n = (size_t)nb * hw;
+    const size_t g = (size_t)blockIdx.x * RB + threadIdx.x;
+    bool on = false;
+    unsigned long long key = 0;
+    unsigned x = 0, y = 0, bits = 0;
+    unsigned long long q = 0;
+    if (g < n) {
+        const int root = L[g];
+        if (root >= 0) {
+            const int rw = row[root];
+            if (rw >= 0 && rw < cap) {
+                const size_t b = g / hw;
+                const int p = (int)(g - b * hw);
+                y = (unsigned)(p / r.out_w);
+                x = (unsigned)(p - (int)y * r.out_w);
+                const float v = resize_at(src + b * (size_t)r.in_h * r.in_w, r, (int)y, (int)x);
+                on = true;
+                key = (unsigned long long)b * (unsigned)cap + (unsigned)rw;
+                bits = v > 0.f ? __float_as_uint(v) : 0u;
+                q = (unsigned long long)rintf(v * 16777216.f);
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long pending = __ballot(on);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const unsigned long long k0 = __shfl(key, leader);
+        const bool mine = on && key == k0;
+        const unsigned long long same = __ballot(mine);
+        const unsigned sx = wave_sum(mine ? x : 0u), sy = wave_sum(mine ? y : 0u);
+        const unsigned long long sq = wave_sum64(mine ? q : 0ull);
+        const unsigned nx0 = wave_max(mine ? ~x : 0u), ny0 = wave_max(mine ? ~y : 0u);
+        const unsigned x1 = wave_max(mine ? x : 0u), y1 = wave_max(mine ? y : 0u), mp = wave_max(mine ? bits : 0u);
+        if (lane == leader) {
+            LesionAcc* a = acc + k0;
+            atomicAdd(&a->area, (unsigned)__popcll(same));
+            atomicAdd(&a->sx, (unsigned long long)sx);
+            atomicAdd(&a->sy, (unsigned long long)sy);
+            atomicAdd(&a->sq, sq);
+            atomicMax(&a->nx0, nx0);
+            atomicMax(&a->ny0, ny0);
+            atomicMax(&a->x1, x1);
+            atomicMax(&a->y1, y1);
+            atomicMax(&a->mp, mp);
+        }
+        if (mine) on = false;
+        pending &= ~same;
+    }
+}
+
+// out: uint8 [nb, oh, ow] padded to whole 32-bit words: 255 where the pixel's component is kept; thread = word (4 bytes, one store)
+__global__ __launch_bounds__(RB) void k_lesion_mask(const int* __restrict__ L, const int* __restrict__ row, size_t total,
+                                                    uint32_t* __restrict__ out) {
+    const size_t word = (size_t)blockIdx.x * RB + threadIdx.x;
+    const size_t k0 = word * 4;
+    if (k0 >= total) return;
+    int root[4] = {-1, -1, -1, -1};
+    if (k0 + 4 <= total) {
+        const int4 v = *reinterpret_cast<const int4*>(L + k0);       // L is 256-byte aligned and k0 a multiple of 4
+        root[0] = v.x, root[1] = v.y, root[2] = v.z, root[3] = v.w;
+    } else {
+        for (int e = 0; k0 + e < total; ++e) root[e] = L[k0 + e];
+    }
+    uint32_t packed = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (root[e] >= 0 && row[root[e]] >= 0) packed |= 0xffu << (8 * e);
+    out[word] = packed;
+}
+
 inline unsigned nblocks(size_t n) { return (unsigned)((n + RB - 1) / RB); }
 
 }  // namespace
@@ -440,6 +585,9 @@ struct RegionState {
     size_t slice_acc_n = 0, slices = 0;
     uint32_t* viz = nullptr;             // rendered composites (dnnca_render_composite)
     size_t viz_bytes = 0;
+    float lesion_rf = 1.f;               // the last dnnca_lesion_table: what DNNCA_PLAN_LESION replays
+    int lesion_k = 5;
+    bool lesion_mask = true;
 };
 
 static constexpr size_t kRegionBudget = size_t(1) << 24;    // pixel-thresholds per chunk (~21 bytes each)
@@ -526,6 +674,26 @@ static int region_state(Model* M) {
     return DNNCA_OK;
 }
 
+// slices per chunk: kRegionBudget pixel-thresholds, the grid z of the tile kernels (T x chunk) and int32 pixel indices
+static size_t region_chunk(size_t T, size_t hw, int max_batch) {
+    size_t chunk = std::max<size_t>(1, kRegionBudget / (T * hw));
+    chunk = std::min(chunk, (size_t)std::max(max_batch, 1));
+    chunk = std::min(chunk, (size_t)65535 / T);
+    while (chunk > 1 && T * chunk * hw >= (size_t)INT32_MAX / 2) --chunk;
+    return chunk;
+}
+
+// the one workspace of the region passes, grown on demand (its content is scratch between calls)
+static int region_ws_reserve(RegionState& R, size_t need) {
+    if (need <= R.ws_bytes) return DNNCA_OK;
+    if (R.ws) HIP_TRY(hipFree(R.ws));
+    R.ws = nullptr;
+    R.ws_bytes = 0;
+    HIP_TRY(hipMalloc(&R.ws, need));
+    R.ws_bytes = need;
+    return DNNCA_OK;
+}
+
 int region_prepare(Model* M, const std::vector<RegionSpecHost>& specs, int max_batch, int h, int w, int slices) {
     (void)h;
     (void)w;
@@ -544,19 +712,9 @@ int region_prepare(Model* M, const std::vector<RegionSpecHost>& specs, int max_b
         T = std::max(T, s.thr.size());
     }
     if ((size_t)T * hw * 2 >= (size_t)INT32_MAX) { set_error("region metrics: slices of %zu pixels are too large", hw); return DNNCA_EINVAL; }
-    size_t chunk = std::max<size_t>(1, kRegionBudget / (T * hw));
-    chunk = std::min(chunk, (size_t)std::max(max_batch, 1));
-    chunk = std::min(chunk, (size_t)65535 / T);           // grid z of the tile kernels: T x chunk
-    while (chunk > 1 && T * chunk * hw >= (size_t)INT32_MAX / 2) --chunk;
+    const size_t chunk = region_chunk(T, hw, max_batch);
     R.chunk = (int)chunk;
-    const size_t need = region_layout(nullptr, chunk, hw, T).bytes;
-    if (need > R.ws_bytes) {
-        if (R.ws) HIP_TRY(hipFree(R.ws));
-        R.ws = nullptr;
-        R.ws_bytes = 0;
-        HIP_TRY(hipMalloc(&R.ws, need));
-        R.ws_bytes = need;
-    }
+    DN_TRY(region_ws_reserve(R, region_layout(nullptr, chunk, hw, T).bytes));
     if (specs.size() > R.acc_specs) {
         if (R.acc) HIP_TRY(hipFree(R.acc));
         if (R.thr_dev) HIP_TRY(hipFree(R.thr_dev));
@@ -767,6 +925,144 @@ int region_render(Model* M, const float* x, const float* lab, const float* prob,
     HIP_TRY(hipMemcpyAsync(out, R.viz, total, hipMemcpyDeviceToHost, M->stream));
     HIP_TRY(hipStreamSynchronize(M->stream));
     return DNNCA_OK;
+}
+
+// ---- lesion table ----------------------------------------------------------------------------------------------------------
+struct LesionWs {                        // carve-up of the workspace for nb slices of hw pixels and `cap` rows per slice
+    uint32_t *w0, *w1, *mask;
+    int *lp, *row, *tot;
+    unsigned* sp;
+    float* thr;                          // the one threshold (region_prep reads its thresholds from the device)
+    LesionAcc* acc;
+    size_t bytes;
+};
+
+static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap) {
+    const size_t n = nb * hw;
+    LesionWs w;
+    char* p = (char*)base;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += align256(bytes); return (void*)r; };
+    w.w0 = (uint32_t*)take(n * 4);
+    w.w1 = (uint32_t*)take(n * 4);
+    w.lp = (int*)take(n * 4);
+    w.sp = (unsigned*)take(n * 4);
+    w.row = (int*)take(n * 4);
+    w.tot = (int*)take(nb * 4);
+    w.thr = (float*)take(4);
+    w.acc = (LesionAcc*)take(nb * cap * sizeof(LesionAcc));
+    w.mask = (uint32_t*)take((n + 3) / 4 * 4);
+    w.bytes = off;
+    return w;
+}
+
+int lesion_check(LesionArgs& a, int h, int w) {
+    if (h < 1 || w < 1) { set_error("lesion table: slices of %d x %d", h, w); return DNNCA_EINVAL; }
+    if (!(a.threshold >= 0.f)) { set_error("lesion table: threshold %g (must be >= 0)", (double)a.threshold); return DNNCA_EINVAL; }
+    if (!(a.rf > 0.f) || !std::isfinite(a.rf)) { set_error("lesion table: resize factor %g", (double)a.rf); return DNNCA_EINVAL; }
+    if (a.k < 1 || a.k > kRegionMaxK) { set_error("lesion table: filter_size %d outside 1..%d", a.k, kRegionMaxK); return DNNCA_EINVAL; }
+    if (a.min_area < 0) { set_error("lesion table: min_area %d (must be >= 0)", a.min_area); return DNNCA_EINVAL; }
+    if (a.max_lesions < 1) { set_error("lesion table: max_lesions %d (must be >= 1)", a.max_lesions); return DNNCA_EINVAL; }
+    a.oh = fp16_scaled(h, a.rf);
+    a.ow = fp16_scaled(w, a.rf);
+    if (a.oh < 1 || a.ow < 1) {
+        set_error("lesion table: resize factor %g maps %d x %d to an empty image", (double)a.rf, h, w);
+        return DNNCA_EINVAL;
+    }
+    const size_t hw = (size_t)a.oh * a.ow;
+    if (hw * 2 >= (size_t)INT32_MAX) { set_error("lesion table: slices of %zu pixels are too large", hw); return DNNCA_EINVAL; }
+    a.cap = (int)std::min<size_t>((size_t)a.max_lesions, (hw + 1) / 2);      // 4-connected components of hw pixels: at most ceil(hw / 2)
+    return DNNCA_OK;
+}
+
+int lesion_table(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows, int64_t* n_rows,
+                 int32_t* totals, uint8_t* mask, bool want_mask) {
+    DN_TRY(region_state(M));
+    RegionState& R = *M->region;
+    R.lesion_rf = a.rf;
+    R.lesion_k = a.k;
+    R.lesion_mask = want_mask;
+    const int oh = a.oh, ow = a.ow;
+    const size_t hw = (size_t)oh * ow, cap = (size_t)a.cap;
+    const int chunk = (int)region_chunk(1, hw, batch);
+    if (!M->dry) DN_TRY(region_ws_reserve(R, lesion_layout(nullptr, chunk, hw, cap).bytes));
+    hipStream_t s = M->stream;
+    std::vector<LesionAcc> acc;
+    std::vector<int> tot;
+    std::vector<size_t> first;
+    int64_t out = 0;
+    Resize rz{h, w, oh, ow, (float)h / (float)oh, (float)w / (float)ow, (oh == h && ow == w) ? 1 : 0};
+    for (int b0 = 0; b0 < batch; b0 += chunk) {
+        const int nb = std::min(chunk, batch - b0);
+        const size_t n = (size_t)nb * hw;
+        const LesionWs ws = lesion_layout(R.ws, nb, hw, cap);
+        const float* pb = prob + (size_t)b0 * h * w;
+        if (!M->dry) HIP_TRY(hipMemcpyAsync(ws.thr, &a.threshold, 4, hipMemcpyHostToDevice, s));   // `a` outlives the chunk's sync
+        LAUNCH(M, "region_prep", n * 4.0 + (double)nb * h * w * 4, 0,
+               hipLaunchKernelGGL(k_region_prep, dim3(nblocks(n)), dim3(RB), 0, s, pb, rz, nb, (const float*)ws.thr, 1, ws.w0));
+        const uint32_t* fg = ws.w0;
+        if (a.k > 1) {
+            const dim3 tiles((ow + kTile - 1) / kTile, (oh + kTile - 1) / kTile, nb);
+            LAUNCH(M, "region_open", n * 8.0, 0,
+                   hipLaunchKernelGGL(k_region_open, tiles, dim3(RB), 0, s, ws.w0, ws.w1, oh, ow, a.k, n, nb));
+            fg = ws.w1;
+        }
+        region_ccl(M, fg, 1, nb, oh, ow, ws.lp);
+        if (!M->dry) {
+            HIP_TRY(hipMemsetAsync(ws.sp, 0, n * 4, s));
+            HIP_TRY(hipMemsetAsync(ws.acc, 0, (size_t)nb * cap * sizeof(LesionAcc), s));
+        }
+        LAUNCH(M, "region_sizes", n * 4.0, 0, hipLaunchKernelGGL(k_region_sizes, dim3(nblocks(n)), dim3(RB), 0, s, ws.lp, n, ws.sp));
+        LAUNCH(M, "lesion_scan", n * 12.0, 0,
+               hipLaunchKernelGGL(k_lesion_scan, dim3(nb), dim3(RB), 0, s, ws.lp, ws.sp, (int)hw, (unsigned)a.min_area, ws.row, ws.tot));
+        LAUNCH(M, "lesion_stats", n * 8.0 + (double)nb * h * w * 4, 0,
+               hipLaunchKernelGGL(k_lesion_stats, dim3(nblocks(n)), dim3(RB), 0, s, pb, rz, nb, ws.lp, ws.row, (int)cap, ws.acc));
+        if (want_mask)
+            LAUNCH(M, "lesion_mask", n * 9.0, 0,
+                   hipLaunchKernelGGL(k_lesion_mask, dim3(nblocks((n + 3) / 4)), dim3(RB), 0, s, ws.lp, ws.row, n, ws.mask));
+        if (M->dry) continue;
+        HIP_TRY(hipGetLastError());
+        tot.resize(nb);
+        HIP_TRY(hipMemcpyAsync(tot.data(), ws.tot, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        if (mask) HIP_TRY(hipMemcpyAsync(mask + (size_t)b0 * hw, ws.mask, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        first.assign(nb + 1, 0);         // only the rows a slice filled come back
+        for (int b = 0; b < nb; ++b) first[b + 1] = first[b] + std::min<size_t>((size_t)std::max(tot[b], 0), cap);
+        acc.resize(first[nb]);
+        for (int b = 0; b < nb; ++b)
+            if (first[b + 1] > first[b])
+                HIP_TRY(hipMemcpyAsync(acc.data() + first[b], ws.acc + (size_t)b * cap, (first[b + 1] - first[b]) * sizeof(LesionAcc),
+                                       hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int b = 0; b < nb; ++b) {
+            totals[b0 + b] = tot[b];
+            for (size_t r = 0; r < first[b + 1] - first[b]; ++r) {
+                const LesionAcc& v = acc[first[b] + r];
+                dnnca_lesion_row& o = rows[out++];
+                o.slice = b0 + b;
+                o.row = (int32_t)r;
+                o.area = (int32_t)v.area;
+                o.x0 = (int32_t)~v.nx0;
+                o.y0 = (int32_t)~v.ny0;
+                o.x1 = (int32_t)v.x1;
+                o.y1 = (int32_t)v.y1;
+                memcpy(&o.max_prob, &v.mp, 4);
+                o.sum_x = v.sx;
+                o.sum_y = v.sy;
+                o.sum_prob_q24 = v.sq;
+            }
+        }
+    }
+    if (!M->dry && n_rows) *n_rows = out;
+    return DNNCA_OK;
+}
+
+void lesion_last(Model* M, float* rf, int* k, bool* want_mask) {
+    RegionState def;
+    const RegionState& R = M->region ? *M->region : def;
+    *rf = R.lesion_rf;
+    *k = R.lesion_k;
+    *want_mask = R.lesion_mask;
 }
 
 void region_release(Model* M) {

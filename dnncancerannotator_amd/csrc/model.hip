@@ -1703,6 +1703,52 @@ int dnnca_render_composite(void* model, const float* y_hw, int batch, float rati
     return region_render(M, M->x_stage, lab, M->prob, batch, H, W, C, ratio, overlay, out, (size_t)capacity, hwc);
 }
 
+// ---- `annotator predict`: the lesion table (kernels_region.hip) ---------------------------------------------------------------
+int dnnca_lesion_table(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
+                       int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
+                       int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw) {
+    MODEL(model);
+    DN_TRY(check_batch(M, batch));
+    if (!prob_hw) {
+        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
+            set_error("lesion table: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
+            return DNNCA_EINVAL;
+        }
+        h = M->outH;
+        w = M->outW;
+    }
+    LesionArgs a;
+    a.threshold = threshold;
+    a.rf = resize_factor;
+    a.k = filter_size;
+    a.min_area = min_area;
+    a.max_lesions = max_lesions;
+    DN_TRY(lesion_check(a, h, w));
+    if (!out_hw) { set_error("lesion table: null out_hw"); return DNNCA_EINVAL; }
+    out_hw[0] = a.oh;
+    out_hw[1] = a.ow;
+    if (!rows) return DNNCA_OK;                   // size query
+    if (!totals || !n_rows) { set_error("lesion table: null totals / n_rows"); return DNNCA_EINVAL; }
+    if (rows_capacity < (int64_t)batch * a.cap) {
+        set_error("lesion table: %lld rows needed (%d slices x %d), capacity %lld", (long long)batch * a.cap, batch, a.cap,
+                  (long long)rows_capacity);
+        return DNNCA_EINVAL;
+    }
+    if (mask && mask_capacity < (int64_t)batch * a.oh * a.ow) {
+        set_error("lesion table: mask of %lld bytes needed, capacity %lld", (long long)batch * a.oh * a.ow, (long long)mask_capacity);
+        return DNNCA_EINVAL;
+    }
+    const float* p_dev = M->prob;
+    if (prob_hw) {
+        const size_t n = (size_t)batch * h * w;
+        float *pd = nullptr, *yd = nullptr;
+        DN_TRY(region_inputs(M, n, &pd, &yd));
+        HIP_TRY(hipMemcpyAsync(pd, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+        p_dev = pd;
+    }
+    return lesion_table(M, p_dev, batch, h, w, a, rows, n_rows, totals, mask, mask != nullptr);
+}
+
 int dnnca_eval_region_begin(void* model, const dnnca_region_spec* specs, int n) {
     MODEL(model);
     if (!M->eval_active) { set_error("dnnca_eval_region_begin outside dnnca_eval_begin .. dnnca_eval_end"); return DNNCA_ESTATE; }
@@ -1905,7 +1951,8 @@ int dnnca_debug_launch_cost(void* model, int n, int blocks, float* us_per_launch
 int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap) {
     MODEL(model);
     if (!buf || !cap) return DNNCA_EINVAL;
-    if (pass != DNNCA_PLAN_TRAIN && pass != DNNCA_PLAN_EVAL && pass != DNNCA_PLAN_FORWARD && pass != DNNCA_PLAN_SENSITIVITY) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
+    if (pass != DNNCA_PLAN_TRAIN && pass != DNNCA_PLAN_EVAL && pass != DNNCA_PLAN_FORWARD && pass != DNNCA_PLAN_SENSITIVITY &&
+        pass != DNNCA_PLAN_LESION) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
     DN_TRY(check_batch(M, batch));
     M->plan_text.clear();
     M->dry = true;
@@ -1928,6 +1975,12 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
         if (rc == DNNCA_OK) rc = M->loss_and_backward(M->y_stage, B, cfg, false);
     } else if (pass == DNNCA_PLAN_SENSITIVITY) {
         rc = M->input_sensitivity(M->x_stage, B);
+    } else if (pass == DNNCA_PLAN_LESION) {
+        LesionArgs a;
+        bool want_mask = true;
+        lesion_last(M, &a.rf, &a.k, &want_mask);
+        rc = lesion_check(a, M->outH, M->outW);
+        if (rc == DNNCA_OK) rc = lesion_table(M, M->prob, B, M->outH, M->outW, a, nullptr, nullptr, nullptr, nullptr, want_mask);
     } else {
         rc = dnnca_forward_dev(model, M->x_stage, B, 0);
     }

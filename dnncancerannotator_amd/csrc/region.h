@@ -39,6 +39,22 @@ const float* region_label_of(Model* M, int batch);
 // [batch, oh, ow, overlay ? 3 : 1]); out_hwc = (oh, ow, channels).  out == nullptr: size query only
 int region_render(Model* M, const float* x, const float* lab, const float* prob, int batch, int h, int w, int c, float ratio,
                   int overlay, unsigned char* out, size_t capacity, int* out_hwc);
+// ---- the lesion table of dnnca_lesion_table (`annotator predict`): the prediction plane alone through prep (T = 1), open, ccl and
+// sizes, then lesion_scan / lesion_stats / lesion_mask, chunked like region_accumulate in the same workspace
+struct LesionArgs {
+    float threshold = 0.5f, rf = 1.f;
+    int k = 5, min_area = 0, max_lesions = 256;
+    int oh = 0, ow = 0, cap = 0;         // filled by lesion_check: the analysed plane, rows per slice min(max_lesions, (oh ow + 1) / 2)
+};
+// checks the caller's arguments against slices of h x w and fills oh / ow / cap; DNNCA_EINVAL with the reason otherwise
+int lesion_check(LesionArgs& a, int h, int w);
+// prob: device [batch, h, w].  rows (host, batch * a.cap entries at least) receives *n_rows rows, totals (host [batch]) the kept
+// components per slice, mask (host uint8 [batch, oh, ow], or nullptr: no mask launch) the cleaned mask.  Synchronises.  In a dry
+// run (M->dry) the host outputs are not touched and want_mask stands for `mask != nullptr`
+int lesion_table(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows, int64_t* n_rows,
+                 int32_t* totals, uint8_t* mask, bool want_mask);
+// resize factor, filter size and mask choice of the last lesion_table (DNNCA_PLAN_LESION); the defaults before any
+void lesion_last(Model* M, float* rf, int* k, bool* want_mask);
 void region_release(Model* M);
 
 }  // namespace dnnca

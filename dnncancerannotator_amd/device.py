@@ -489,6 +489,43 @@ class DeviceModel:
                                               out.ctypes.data_as(C.c_void_p), out.nbytes, hwc))
         return out
 
+    # ---- `annotator predict` (kernels_region.hip: lesion_scan / lesion_stats / lesion_mask) ---------------------
+    def lesion_table(self, batch=None, prob=None, threshold=0.5, resize_factor=1.0, filter_size=5, min_area=0, max_lesions=256,
+                     mask=True):
+        """the lesions of the last forward's `batch` slices, or of `prob` [B, h, w(, 1)] (host, any size): (rows, totals, masks).
+        Per slice: resize by resize_factor, >= threshold, filter_size x filter_size opening (1: none), 4-connected components of at
+        least min_area pixels, numbered in raster order of their first pixel.  rows: structured array (_lib.LESION_ROW_DTYPE: slice,
+        row, area, x0, y0, x1, y1 inclusive, max_prob, sum_x, sum_y, sum_prob_q24), slice after slice, at most max_lesions per
+        slice; totals int32 [B]: the kept components of every slice (> max_lesions: its rows are truncated); masks uint8
+        [B, oh, ow], 255 on every kept component (None with mask=False).  Exact integers: bit-identical from run to run."""
+        pp, h, w = None, 0, 0
+        if prob is not None:
+            prob = as_f32(prob)
+            if prob.ndim == 4 and prob.shape[-1] == 1:
+                prob = np.ascontiguousarray(prob[..., 0])
+            if prob.ndim != 3:
+                raise ValueError('prob must be [B, h, w], got %s' % (prob.shape,))
+            if batch is not None and int(batch) != prob.shape[0]:
+                raise ValueError('batch %d but prob holds %d slices' % (batch, prob.shape[0]))
+            (batch, h, w), pp = prob.shape, fptr(prob)
+        elif batch is None:
+            raise ValueError('lesion_table needs `batch` (the slices of the last forward) or `prob`')
+        B = int(batch)
+        args = (self.handle, pp, B, int(h), int(w), float(threshold), float(resize_factor), int(filter_size), int(min_area),
+                int(max_lesions))
+        hw = (C.c_int32 * 2)()
+        check(self.lib.dnnca_lesion_table(*args, None, 0, None, None, None, 0, hw))
+        oh, ow = hw[0], hw[1]
+        cap = B * min(int(max_lesions), (oh * ow + 1) // 2)
+        rows = np.zeros(cap, _lib.LESION_ROW_DTYPE)
+        totals = np.zeros(B, np.int32)
+        masks = np.empty((B, oh, ow), np.uint8) if mask else None
+        n = C.c_int64()
+        check(self.lib.dnnca_lesion_table(*args, rows.ctypes.data_as(C.POINTER(_lib.LesionRow)), cap, C.byref(n),
+                                          totals.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          masks.ctypes.data_as(C.c_void_p) if mask else None, masks.nbytes if mask else 0, hw))
+        return rows[:n.value].copy(), totals, masks
+
     def input_sensitivity(self, x=None, batch=None):
         """float64 [B, C]: sum over the image of |d sum(prob of slice b) / d x[b, :, :, c]| in inference mode (the raw sums of the
         reference's sensitivity map; casewise.normalise_sensitivity divides each row by its sum).  x [B, H, W, C], or None with
@@ -632,12 +669,13 @@ class DeviceModel:
             out.append((name.value.decode(), n.value, ms.value, by.value, fl.value))
         return out
 
-    PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3}
+    PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3, 'lesion': 4}
 
     def plan(self, variants=False, mode='train', batch=None):
         """The launch schedule of one pass: [(kernel, algorithmic bytes, flops)].  mode 'train': one train step; 'eval': one
         eval_step (inference forward + loss; a staged evaluation step launches the same); 'forward': forward(training=False);
-        'sensitivity': input_sensitivity.
+        'sensitivity': input_sensitivity; 'lesion': lesion_table on the last forward's probabilities, with the resize factor,
+        filter size and mask choice of the last lesion_table call.
         batch: None = max_batch.  variants: keep the template variant the library appends to a launch name
         (`ig_conv_fwd#3n2w8`): the kernel-coverage test tells them apart.  A dry run: the model is unchanged."""
         if mode not in self.PLAN_PASSES:

@@ -646,5 +646,55 @@ class TFKerasModel:
                 outs.append(dm.forward(x[i:i + dm.max_batch], training=False))
         return np.concatenate(outs) if outs else np.zeros((0,))
 
+    def annotate(self, dataset, save_path, output, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
+                 max_lesions=256, export_images=False):
+        """`annotator predict`: the lesions of slices that have no label.  Loads checkpoint `step` of save_path (None: the latest);
+        per batch (x, paths, sliceIDs) of `dataset` (make_dataset(..., include_meta=True, labels=False)) one forward whose
+        probabilities stay on the device, then DeviceModel.lesion_table: threshold, filter_size x filter_size opening, components
+        of at least min_area pixels -- only the table and the uint8 masks come back.  Files under `output`: lesions.csv (one line
+        per lesion, dataset order then row order), slices.csv (one line per slice; truncated = 1: more than max_lesions
+        components, lesions.csv holds the first max_lesions) and, with export_images, <exam>/<slice>/mask.png (the opened,
+        area-filtered mask).  Returns {'step', 'slices', 'lesions'}."""
+        if self.ctx.world > 1:
+            raise RuntimeError('annotate runs in a single process (WORLD_SIZE is %d): start it without the launcher' % self.ctx.world)
+        self._build(dataset)
+        ckpts = self.get_ckpts(os.path.join(save_path, 'checkpoints'))
+        if not ckpts:
+            raise ValueError(f'no checkpoint under {save_path}/checkpoints')
+        if step is None:
+            step = max(ckpts)
+        if step not in ckpts:
+            raise ValueError(f'no checkpoint of step {step} under {save_path}/checkpoints (have {sorted(ckpts)})')
+        self.load(ckpts[step])
+        lesion_rows, slice_rows = [], []
+        writer = casewise.Writer() if export_images else None
+        try:
+            for el in dataset:
+                x, paths, ids = np.asarray(el[0], np.float32), el[-2], el[-1]      # a label between them is never looked at
+                if not len(x):
+                    continue
+                self._ensure_capacity(len(x))
+                dm = self.device_model
+                for i in range(0, len(x), dm.max_batch):
+                    xb = x[i:i + dm.max_batch]
+                    dm.forward(xb, training=False, return_prob=False)
+                    rows, totals, masks = dm.lesion_table(batch=len(xb), threshold=threshold, resize_factor=resize_factor,
+                                                          filter_size=filter_size, min_area=min_area, max_lesions=max_lesions,
+                                                          mask=bool(export_images))
+                    for b, (p, k) in enumerate(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch])):
+                        mine = rows[rows['slice'] == b]
+                        lesion_rows += [casewise.lesion_values(p, k, r) for r in mine]
+                        slice_rows.append(casewise.slice_values(p, k, mine, totals[b]))
+                        if export_images:
+                            writer.submit(casewise.mask_path(output, casewise.tag_of(p, k)), casewise.encode_png, masks[b])
+        finally:
+            if writer is not None:
+                writer.close()
+        os.makedirs(output, exist_ok=True)
+        for name, cols, table in (('lesions.csv', casewise.LESION_COLUMNS, lesion_rows), ('slices.csv', casewise.SLICE_COLUMNS, slice_rows)):
+            with open(os.path.join(output, name), 'w', newline='') as f:
+                f.write(casewise.plain_csv(cols, table))
+        return dict(step=int(step), slices=len(slice_rows), lesions=len(lesion_rows))
+
     def get_config(self):
         return self.model_config

@@ -313,19 +313,26 @@ class TFRecordDataset:
     device (`dnnca_augment_u8` / `dnnca_warp_f32` / `dnnca_warp_groups_f32`, engine.train).
 
     include_meta (evaluation only, eval_ds(include_meta=True), data.py:488-510): batches (x, y, paths, sliceIDs) -- the same x and
-    y as without it, each slice's exam `path` feature and its 0-based index in the exam record (tf.data.experimental.Counter)."""
+    y as without it, each slice's exam `path` feature and its 0-based index in the exam record (tf.data.experimental.Counter).
+
+    labels=False (evaluation only; `annotator predict`): `slice_types` names no label, every channel read is a feature and the
+    batches are (x,) or, with include_meta, (x, paths, sliceIDs), converted on the host."""
 
     def __init__(self, paths, slice_types, batch_size, output_size=(512, 512), repeat=False, drop_remainder=False,
                  augment_options=False, buffer_size=0, seed=0, normalize_exams=False, device_convert=False, workers=None,
-                 cache_bytes=8 << 30, shard=None, include_meta=False, **ignored):
+                 cache_bytes=8 << 30, shard=None, include_meta=False, labels=True, **ignored):
         from . import augment
         self.paths = list(paths)
         self.slice_types = list(slice_types)
-        assert 'label' in self.slice_types, 'slice_types must name the label channel (data.py:771)'
+        self.labels = bool(labels)
+        if self.labels:
+            assert 'label' in self.slice_types, 'slice_types must name the label channel (data.py:771)'
+        elif 'label' in self.slice_types or augment_options is not False:
+            raise ValueError('labels=False: an evaluation dataset (augment_options=False) whose slice_types name no label')
         self.batch_size, self.output_size = int(batch_size), tuple(output_size)
         self.repeat, self.drop_remainder = repeat, drop_remainder
         self.feature_idx = [i for i, t in enumerate(self.slice_types) if t != 'label']
-        self.label_idx = self.slice_types.index('label')
+        self.label_idx = self.slice_types.index('label') if self.labels else None
         self.plan = None if augment_options is False else augment.parse_augment_options(augment_options, self.output_size)
         if self.plan is not None:
             self.output_size = self.plan.output_size
@@ -351,7 +358,7 @@ class TFRecordDataset:
         # evaluation with device_convert: the centre-cropped uint8 slices travel as `augment.RawBatch`es without draws (params None)
         # -- a quarter of the float bytes over PCIe, no float copy of an exam on the host; the engine converts them on the device
         # (or, without one, with augment.raw_to_float)
-        self.device_convert = bool(device_convert) and self.plan is None and not self.include_meta
+        self.device_convert = bool(device_convert) and self.plan is None and not self.include_meta and self.labels
         # data.py:517-525 (base_from_tfrecords, normalize=True; data_options.yaml:5 for training): the files are interleaved one
         # slice at a time, each file's slice stream repeated for ever, so that every exam file contributes equally however many
         # slices it holds.  (tf.data's interleave only ever opens `cycle_length` = #cores files when the streams are infinite;
@@ -360,8 +367,9 @@ class TFRecordDataset:
         if self.normalize_exams and not (self.repeat and self.plan is not None):
             raise ValueError('normalize_exams makes an endless training stream: it needs repeat=True and augment_options')
         self.rng = np.random.default_rng(seed)
-        self.element_spec = (Spec((self.batch_size,) + self.output_size + (len(self.feature_idx),), np.float32),
-                             Spec((self.batch_size,) + self.output_size, np.float32))
+        self.element_spec = (Spec((self.batch_size,) + self.output_size + (len(self.feature_idx),), np.float32),)
+        if self.labels:
+            self.element_spec += (Spec((self.batch_size,) + self.output_size, np.float32),)
 
     def _exams_of(self, path, exams=None):
         """the decoded exams of one file, from the cache when they are there (`exams`: just read by the caller -> remember them).
@@ -482,10 +490,11 @@ class TFRecordDataset:
             for exam in exams:
                 s = self._centre(exam.slices, oh, ow).astype(np.float32) / np.float32(255.0)
                 for k in range(len(s)):
+                    y = s[k][..., self.label_idx] if self.labels else None
                     if meta:
-                        yield s[k][..., self.feature_idx], s[k][..., self.label_idx], exam.path, k
+                        yield s[k][..., self.feature_idx], y, exam.path, k
                     else:
-                        yield s[k][..., self.feature_idx], s[k][..., self.label_idx]
+                        yield s[k][..., self.feature_idx], y
 
     def _with_meta(self):
         xs, ys, ps, ks = [], [], [], []
@@ -536,6 +545,9 @@ class TFRecordDataset:
         return augment.RawBatch(np.stack(mine), params, self.output_size, self.label_idx, warp, intrawarp, self.contrast_channels)
 
     def _stacked(self, xs, ys):
+        if not self.labels:                     # (x,): there is no label to stack
+            mx = self._mine(xs)
+            return (np.stack(mx) if mx else np.zeros((0,) + xs[0].shape, np.float32),)
         mx, my = self._mine(xs), self._mine(ys)
         if not mx:
             return np.zeros((0,) + xs[0].shape, np.float32), np.zeros((0,) + ys[0].shape, np.float32)

@@ -284,6 +284,35 @@ int dnnca_region_confusion_slices(void* model, const float* prob_hw, const float
 int dnnca_render_composite(void* model, const float* y_hw, int batch, float ratio, int overlay, uint8_t* out, int64_t capacity,
                            int32_t* out_hwc);
 
+/* ---- `annotator predict`: the lesions of slices that have no label (the reference left runs/predict.py empty) -------------------
+ * dnnca_lesion_table works on the probabilities of the last forward (prob_hw == NULL; h and w are then 0 or the model's output
+ * size) or on prob_hw, host [batch, h, w] of any size.  Per slice: resize by resize_factor as above (1: identity), prob' >=
+ * threshold, k x k opening (filter_size 1: none), 4-connected components; a component is KEPT when it has at least min_area
+ * pixels.  Kept components are numbered per slice in raster order of their first (smallest-index) pixel; the first max_lesions of
+ * a slice give one row each:
+ *   slice, row             the slice in the batch, the component's number in the slice
+ *   area                   pixels
+ *   x0, y0, x1, y1         bounding box, inclusive, in pixels of the analysed (resized) plane
+ *   max_prob               the largest prob' of its pixels
+ *   sum_x, sum_y           sums of the pixel coordinates (centroid = sum / area)
+ *   sum_prob_q24           sum of rint(prob' * 2^24) over its pixels (mean = sum / area / 2^24); prob' is expected in [0, 1]
+ * Every field is an integer sum or an extremum: the table is bit-identical from run to run.  rows receives the rows slice after
+ * slice (*n_rows of them); rows_capacity must be at least batch * min(max_lesions, (oh * ow + 1) / 2).  totals [batch]: the kept
+ * components of each slice, which may exceed max_lesions (the slice's table is then truncated).  mask: NULL, or host uint8
+ * [batch, oh, ow] of mask_capacity bytes: 255 on every kept component (truncated or not), 0 elsewhere -- the opened and
+ * area-filtered mask.  out_hw receives (oh, ow); rows == NULL only queries it.
+ * DNNCA_EINVAL, with nothing launched: batch outside [1, max_batch], filter_size outside 1..15, a threshold that is NaN or negative,
+ * a resize factor that is not positive or gives an empty plane, min_area < 0, max_lesions < 1, a buffer that is too small.
+ * Variables, state and the probabilities of the last forward are untouched.  Synchronises. */
+typedef struct dnnca_lesion_row {
+    int32_t slice, row, area, x0, y0, x1, y1;
+    float max_prob;
+    uint64_t sum_x, sum_y, sum_prob_q24;
+} dnnca_lesion_row;                                 /* 56 bytes, no padding */
+int dnnca_lesion_table(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
+                       int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
+                       int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw);
+
 /* ---- channel sensitivity of `annotator evaluate --visualize_sensitivity` (utils/callbacks.py:290-313) ---------------------------
  * With the model in inference mode (BatchNorm on its moving statistics, sigmoid output):
  *     sums[b * in_channels + c] = sum over H, W of | d (sum of all probabilities of slice b) / d x[b, h, w, c] |
@@ -325,8 +354,10 @@ int dnnca_profile_get(void* model, int index, char* name, size_t name_cap, int64
 int dnnca_plan_dump(void* model, char* buf, size_t cap);
 /* the same for one pass at one batch size in [1, max_batch]: the train step (dnnca_plan_dump is this at max_batch), an evaluation
    step (dnnca_eval_step / dnnca_eval_step_staged: inference forward + loss), or a prediction (dnnca_forward with training = 0:
-   inference forward + sigmoid), or dnnca_input_sensitivity.  A dry run: nothing is launched and the model is left as it was. */
-enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2, DNNCA_PLAN_SENSITIVITY = 3 };
+   inference forward + sigmoid), or dnnca_input_sensitivity, or dnnca_lesion_table on the last forward's probabilities with the
+   resize factor, filter size and mask choice of the last dnnca_lesion_table call (before any: 1.0, 5, with mask).  A dry run:
+   nothing is launched and the model is left as it was. */
+enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2, DNNCA_PLAN_SENSITIVITY = 3, DNNCA_PLAN_LESION = 4 };
 int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap);
 
 #ifdef __cplusplus

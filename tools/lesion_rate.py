@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""lesion_rate.py -- cost of the lesion table of `annotator predict` at 8 x 512 x 512 (configs/unet.yaml): the dnnca_lesion_table
+call alone on probabilities resident in the model's buffer (wall time per call and device time per launch, HIP events around
+every launch), `annotate` with and without masks, and the forward alone for scale.  The yardstick is
+dnnca_region_confusion_slices with one one-threshold spec on the same probabilities: it runs the shared stages twice (label plane
+and prediction plane) plus pairs, match and count.
+
+    python tools/lesion_rate.py [--batch 8] [--size 512] [--reps 20] [--out profiles/lesion_rate.txt]
+    DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --yardstick      # the yardstick alone
+
+The probabilities are drawn: the synthetic labels' discs at 0.55 .. 0.95 on a background of 0 .. 0.45 (a few lesions per slice,
+as a trained model gives), put into the model's probability buffer by pixel_confusion_of."""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from dnncancerannotator_amd import _lib                           # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--batch', type=int, default=8)
+ap.add_argument('--size', type=int, default=512)
+ap.add_argument('--reps', type=int, default=20)
+ap.add_argument('--batches', type=int, default=8)
+ap.add_argument('--yardstick', action='store_true', help='region_confusion_slices alone (also on a library without the lesion table)')
+ap.add_argument('--out', default=None, help='append the report to this file as well')
+a = ap.parse_args()
+if a.yardstick:
+    _lib.SIGNATURES.pop('dnnca_lesion_table', None)              # a library built from the parent does not export it
+
+from dnncancerannotator_amd import device as dev                  # noqa: E402
+from dnncancerannotator_amd.data import ArrayDataset              # noqa: E402
+from dnncancerannotator_amd.engine import TFKerasModel            # noqa: E402
+from dnncancerannotator_amd.synthetic import synthetic_batch      # noqa: E402
+import numpy as np                                                # noqa: E402
+
+B, S, R, NB = a.batch, a.size, a.reps, a.batches
+lines = []
+
+
+def say(text):
+    print(text, flush=True)
+    lines.append(text)
+
+
+def wall(fn):
+    fn()                                                          # warm-up (workspace, buffers)
+    ts = []
+    for _ in range(R):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    ts.sort()
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def per_launch(dm, fn, prefixes):
+    dm.profile_reset()
+    dm.profile_enable(1)
+    for _ in range(R):
+        fn()
+    dm.sync()
+    rows = [r for r in dm.profile() if r[0].startswith(prefixes)]
+    dm.profile_enable(0)
+    dm.profile_reset()
+    say('    device time %.3f ms per call (event-bracketed launches)' % (sum(r[2] for r in rows) / R))
+    for name, n, ms, by, fl in sorted(rows, key=lambda r: -r[2]):
+        say('      %-22s launches/call %4.1f  %9.2f us per launch' % (name, n / R, ms / n * 1e3))
+
+
+dev.init_device(0)
+x, y = synthetic_batch(B, S, S, 1, seed_x=3, seed_y=4)
+yy, xx = np.mgrid[0:S, 0:S]
+prob = np.where(y > 0.5, 0.55 + ((xx * 5 + yy * 3) % 27) / 64.0, ((xx * 7 + yy * 11) % 30) / 64.0).astype(np.float32)
+DEPLOY = dict(optimizer='adam', enable_multigpu=False)
+e = TFKerasModel(dict(model='UNetAnnotator', deploy_options=DEPLOY,
+                      model_options=dict(rate=2, kernel_size=3, conv_stride=1, padding='same', n_filters_first=3, n_downsample=3, bn=False)))
+ds = ArrayDataset(np.concatenate([x] * NB), None, B, meta_path='/synthetic/p0/e0/mri', labels=False) if not a.yardstick else \
+    ArrayDataset(x, y, B)
+e._build(ds)
+dm = e.device_model
+say('%s: %d x %d x %d, library %s' % ('yardstick' if a.yardstick else 'lesion table', B, S, S, os.path.basename(_lib.LIB_PATH)))
+dm.pixel_confusion_of(prob, y, [0.5])                             # the drawn probabilities into the model's buffer
+spec = ([0.5], 0.30, 1.0, 5)
+med, lo, hi = wall(lambda: dm.region_confusion_slices(y, [spec]))
+say('  region_confusion_slices, 1 spec x 1 threshold: %.3f ms per call (median of %d; %.3f .. %.3f)' % (med, R, lo, hi))
+per_launch(dm, lambda: dm.region_confusion_slices(y, [spec]), ('region_',))
+if not a.yardstick:
+    for mask in (True, False):
+        med, lo, hi = wall(lambda: dm.lesion_table(batch=B, threshold=0.5, filter_size=5, mask=mask))
+        say('  lesion_table(mask=%s): %.3f ms per call (median of %d; %.3f .. %.3f)' % (mask, med, R, lo, hi))
+    rows, totals, _ = dm.lesion_table(batch=B, threshold=0.5, filter_size=5)
+    say('    %d lesions in %d slices, largest %d pixels' % (len(rows), B, int(rows['area'].max()) if len(rows) else 0))
+    per_launch(dm, lambda: dm.lesion_table(batch=B, threshold=0.5, filter_size=5), ('region_', 'lesion_'))
+    one = np.ones((B, S, S), np.float32)                          # the worst case of lesion_stats: one lesion of S x S pixels per slice
+    dm.pixel_confusion_of(one, y, [0.5])
+    med, lo, hi = wall(lambda: dm.lesion_table(batch=B, threshold=0.5, filter_size=5))
+    say('  lesion_table, every pixel one lesion: %.3f ms per call (median; %.3f .. %.3f)' % (med, lo, hi))
+    per_launch(dm, lambda: dm.lesion_table(batch=B, threshold=0.5, filter_size=5), ('lesion_',))
+    for xb, _, _ in ds:
+        dm.forward(xb, return_prob=False)
+    t0 = time.perf_counter()
+    for xb, _, _ in ds:
+        dm.forward(xb, return_prob=False)
+    dm.sync()
+    say('  %-34s %9.1f slices/s' % ('forward only', B * NB / (time.perf_counter() - t0)))
+    with tempfile.TemporaryDirectory() as tmp:
+        e.current_step = 1
+        e.save(os.path.join(tmp, 'run', 'checkpoints', 'ckpt-1'))
+        thr = float(np.median(dm.forward(x, training=False)))
+        for images in (False, True, False, True):
+            t0 = time.perf_counter()
+            res = e.annotate(ds, os.path.join(tmp, 'run'), os.path.join(tmp, 'out%d' % images), threshold=thr, export_images=images)
+            dt = time.perf_counter() - t0
+            say('  %-34s %9.1f slices/s  (%.2f ms per batch; %d lesions)' % ('annotate' + (' + mask.png' if images else ''),
+                                                                            B * NB / dt, dt / NB * 1e3, res['lesions']))
+dm.close()
+if a.out:
+    with open(a.out, 'a') as f:
+        f.write('\n'.join(lines) + '\n')
