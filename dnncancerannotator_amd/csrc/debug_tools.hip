@@ -84,4 +84,27 @@ int dnnca_debug_bn_table(void* model, double* abs_sum, unsigned* ticket_sum, int
     return DNNCA_OK;
 }
 
+// test aid (tests/test_pgbwd_tc3_gpu.py): the two data gradients the backward launch of the last decoder block writes (k_pgbwd TCF),
+// as they stand in their buffers after a train step of `batch` images: the gradient of the skip source of the two-source 3-channel conv
+// [batch, H, W, 3] and the gradient of the 6 -> 3 transposed conv's input [batch, H/2, W/2, 6].  Sizes in floats; synchronises.
+// (Every tensor of the plan has a data and a gradient buffer of its own for the life of the model -- nothing is reused within a step;
+// later backward launches read these two buffers and do not write them, except the in-place act' of a conv that is not `premasked`.)
+int dnnca_debug_tcf_dgrads(void* model, int batch, float* dskip, size_t n_skip, float* dtcin, size_t n_tcin) {
+    MODEL(model);
+    for (size_t i = M->ops.size(); i-- > 1;) {
+        const Op& o = M->ops[i];
+        const Op& tc = M->ops[i - 1];
+        if (o.type != OP_CONV || !o.inB.d.C || o.inA.d.C != 3 || o.inB.d.C != 3 || o.out.d.C != 3) continue;
+        if (tc.type != OP_TCONV || tc.inA.d.C != 6 || tc.out.d.p != o.inA.d.p) continue;
+        const size_t ns = (size_t)batch * o.out.d.H * o.out.d.W * 3, nt = (size_t)batch * tc.inA.d.H * tc.inA.d.W * 6;
+        if (ns != n_skip || nt != n_tcin || !o.inB.g.p || !tc.inA.g.p) { set_error("dnnca_debug_tcf_dgrads: sizes %zu / %zu expected", ns, nt); return DNNCA_EINVAL; }
+        HIP_TRY(hipStreamSynchronize(M->stream));
+        HIP_TRY(hipMemcpy(dskip, o.inB.g.p, ns * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(dtcin, tc.inA.g.p, nt * 4, hipMemcpyDeviceToHost));
+        return DNNCA_OK;
+    }
+    set_error("dnnca_debug_tcf_dgrads: no two-source 3-channel conv behind a 6 -> 3 transposed conv");
+    return DNNCA_EINVAL;
+}
+
 }  // extern "C"

@@ -95,6 +95,7 @@ struct StepSwitches {
     bool no_fused = false, no_fused_bwd = false, no_first3 = false, no_first3f = false, no_up3f = false, no_tail3 = false;
     bool no_tcf = false, no_tcm = false, no_tconv_ride = false, no_prep_ride = false, no_fold_adam = false, no_pool_fold = false;
     bool no_bwd3v = false, no_vw = false, no_head_in_conv = false, no_label_fusion = false, no_wg_stream = false;
+    bool pgbwd_old = false;      // pgbwd_tc_3x2_3 without the counted waits (the kernel the A/B of that change compares against)
     // opt-in
     bool fz_up2 = false, fz_all = false, lockstep = false, force_rccl = false;
     // tuning aids.  fz_only / fzb_only: the one block that fuses ("down1", "up2", ...; empty: all); stamp_*: (C, NSRC, CO) of the

@@ -52,6 +52,7 @@ StepSwitches step_switches() {
     s.no_head_in_conv = on("DNNCA_NO_HEAD_IN_CONV");
     s.no_label_fusion = on("DNNCA_NO_LABEL_FUSION");
     s.no_wg_stream = on("DNNCA_NO_WG_STREAM");
+    s.pgbwd_old = on("DNNCA_PGBWD_OLD");
     s.fz_up2 = on("DNNCA_FZ_UP2");
     s.fz_all = on("DNNCA_FZ_ALL");
     s.lockstep = on("DNNCA_LOCKSTEP");
