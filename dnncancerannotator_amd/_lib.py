@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DNNCA_LIB') or os.path.join(HERE, 'libdnnca.so')      # DNNCA_LIB: A/B of two builds (development aid)
 
 OK = 0
-ARCH_UNET, ARCH_MULMO = 0, 1
+ARCH_UNET, ARCH_MULMO, ARCH_MULTIRES = 0, 1, 2
 PAD_VALID, PAD_SAME = 0, 1
 F32, BF16 = 0, 1
 UNIQUE_ID_BYTES = 128

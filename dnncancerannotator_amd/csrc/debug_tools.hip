@@ -1,6 +1,8 @@
 // debug_tools.hip -- development aids (NOT part of include/dnnca.h and not used by the product path):
-// micro-benchmarks that calibrate what the conv kernels can expect from the f32 matrix pipe, and a read-back of the BatchNorm
-// reduction table for the tests.
+// micro-benchmarks that calibrate what the conv kernels can expect from the f32 matrix pipe, a read-back of the BatchNorm
+// reduction table for the tests, and the residual-join kernels on caller-supplied tensors.
+#include "fast.h"
+#include "kernels.h"
 #include "model.h"
 #include <vector>
 
@@ -105,6 +107,69 @@ int dnnca_debug_tcf_dgrads(void* model, int batch, float* dskip, size_t n_skip, 
     }
     set_error("dnnca_debug_tcf_dgrads: no two-source 3-channel conv behind a 6 -> 3 transposed conv");
     return DNNCA_EINVAL;
+}
+
+// test aid (tests/test_multires_gpu.py): the residual-join kernels (kernels_join.hip; generic != 0: g_join_fwd / g_join_bwd) alone.
+// Every tensor is a host array of npix = B * H * W pixels with `ps` floats each, of which the kernels see channels [c0, c0 + C)
+// (ps == C, c0 == 0: dense, the float4 walk; else the strided walk).  grid > 0 forces that many blocks.
+//   what 0  forward, training: in0 = a, in1 = b -> io0 = relu(a + b) (channels outside the view keep what io0 held), sums[C] = channel sums
+//   what 1  inference: coef[2 C] = scale, shift -> io0 = relu(a + b) * scale + shift
+//   what 2  backward: in0 = dr, in1 = r; io0 = dA, io1 = dB in and out, acc0 / acc1: add to what they hold
+int dnnca_debug_join(void* model, int what, int B, int H, int W, int C, int ps, int c0, int grid, int generic, const float* in0,
+                     const float* in1, float* io0, float* io1, const float* coef, double* sums, int acc0, int acc1) {
+    MODEL(model);
+    if (what < 0 || what > 2 || B < 1 || H < 1 || W < 1 || C < 1 || c0 < 0 || c0 + C > ps || !in0 || !in1 || !io0 || (what == 2 && !io1) ||
+        (what == 1 && !coef) || (generic && what == 1)) { set_error("dnnca_debug_join: bad arguments"); return DNNCA_EINVAL; }
+    const size_t n = (size_t)B * H * W * ps;
+    float* dev = nullptr;          // four tensors, each padded to a multiple of four floats so that every base stays 16-byte aligned
+    const size_t n4 = (n + 3) / 4 * 4;
+    double* dsum = nullptr;
+    unsigned* ticket = nullptr;
+    float* dcoef = nullptr;
+    const unsigned rows = (unsigned)(grid > 0 ? grid : 0) + (unsigned)((C + 255) / 256);
+    const size_t part = std::max(join_part_doubles(C), (size_t)rows * C);
+    hipStream_t s = M->stream;
+    int rc = DNNCA_OK;
+    auto body = [&]() -> int {          // (whatever it allocated is freed behind it, on an error too)
+        HIP_TRY(hipMalloc(&dev, 4 * n4 * 4));
+        HIP_TRY(hipMalloc(&dsum, (2 * (size_t)C + part) * 8));
+        HIP_TRY(hipMalloc(&ticket, 16));
+        HIP_TRY(hipMalloc(&dcoef, 2 * (size_t)C * 4));
+        HIP_TRY(hipMemsetAsync(ticket, 0, 16, s));
+        HIP_TRY(hipMemsetAsync(dsum, 0xff, (2 * (size_t)C + part) * 8, s));          // NaN patterns: whatever is read must have been written
+        HIP_TRY(hipMemcpyAsync(dev, in0, n * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(dev + n4, in1, n * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(dev + 2 * n4, io0, n * 4, hipMemcpyHostToDevice, s));
+        if (io1) HIP_TRY(hipMemcpyAsync(dev + 3 * n4, io1, n * 4, hipMemcpyHostToDevice, s));
+        if (coef) HIP_TRY(hipMemcpyAsync(dcoef, coef, 2 * (size_t)C * 4, hipMemcpyHostToDevice, s));
+        View v[4];
+        for (int k = 0; k < 4; ++k) { v[k].p = dev + k * n4 + c0; v[k].H = H; v[k].W = W; v[k].C = C; v[k].ps = ps; }
+        if (what == 0) {
+            if (generic) g_join_fwd(s, B, v[0], v[1], v[2]);
+            else join_fwd(s, B, v[0], v[1], v[2], sums ? dsum : nullptr, dsum + 2 * C, ticket, grid);
+        } else if (what == 1) {
+            join_infer(s, B, v[0], v[1], v[2], dcoef, grid);
+        } else {
+            if (generic) g_join_bwd(s, B, v[0], v[1], v[2], acc0, v[3], acc1);
+            else join_bwd(s, B, v[0], v[1], v[2], acc0, v[3], acc1, grid);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(io0, dev + 2 * n4, n * 4, hipMemcpyDeviceToHost, s));
+        if (io1) HIP_TRY(hipMemcpyAsync(io1, dev + 3 * n4, n * 4, hipMemcpyDeviceToHost, s));
+        if (sums && what == 0 && !generic) HIP_TRY(hipMemcpyAsync(sums, dsum, (size_t)C * 8, hipMemcpyDeviceToHost, s));
+        unsigned t[4] = {0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(t, ticket, 16, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (t[0]) { set_error("dnnca_debug_join: the ticket reads %u after the launch, not 0", t[0]); return DNNCA_ESTATE; }
+        return DNNCA_OK;
+    };
+    rc = body();
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(dev);
+    (void)hipFree(dsum);
+    (void)hipFree(ticket);
+    (void)hipFree(dcoef);
+    return rc;
 }
 
 }  // extern "C"

@@ -173,6 +173,16 @@ bool ig3x_conv_decide(const Model* m, const DenseSwitches& sw, int mode, int B, 
 bool ig3x_wgrad_decide(const Model* m, const DenseSwitches& sw, int B, int H, int W, int cs, int co, DenseLaunch* d);
 void ig3x_launch(Model* m, const DenseLaunch& d, int mode, const ig::ConvArgs& a, size_t w_off, const char* name, double bytes, double flops);
 void ig3x_wgrad_launch(Model* m, const DenseLaunch& d, ig::WgArgs w, const char* name, double bytes, double flops);
+// kernels_join.hip: the residual join of MultiResUnet, out = relu(a + b) in front of a BatchNorm, as streaming passes (float4 over
+// the flat tensor when every view is dense and 16-byte aligned, else strided scalars).  ws != nullptr: also the per-channel sums of
+// the output into ws[0 .. C) (and ws[C .. 2C) = 0), folded from block partials in `part` (join_part_doubles(C) doubles) by the block
+// that draws the last `ticket` (kept zeroed).  force_grid > 0: that many blocks (tests)
+void join_fwd(hipStream_t s, int B, View a, View b, View r, double* ws, double* part, unsigned* ticket, int force_grid = 0);
+// y = relu(a + b) * coef[c] + coef[C + c]: join + the BatchNorm's inference affine, the joined tensor itself is not stored
+void join_infer(hipStream_t s, int B, View a, View b, View y, const float* coef, int force_grid = 0);
+void join_bwd(hipStream_t s, int B, View dr, View r, View dA, int accA, View dB, int accB, int force_grid = 0);
+unsigned join_fwd_grid(size_t npix, const View& a, const View& b, const View& r, int force);
+size_t join_part_doubles(int C);
 bool ig_tconv_supported(const Model* m, const Op& o);
 bool ig_tconv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_next);
 bool ig_tconv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, double flops);   // decides maskA/maskB/premasked for every op (static per model)

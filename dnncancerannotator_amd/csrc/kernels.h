@@ -5,11 +5,13 @@
 namespace dnnca {
 
 // ----------------------------------------------------------------------------- generic (any shape, untuned) kernels
-// y = act(conv_kxk(concat(A, Bv)) + bias); Bv.C may be 0.  Weight layout HWIO with I = A.C + Bv.C.
+// y = act(conv_kxk(concat(A, Bv)) + bias); Bv.C may be 0.  Weight layout HWIO with I = A.C + Bv.C.  bias / dbias may be null
+// (a conv without bias); gamma may be null in g_bn_finalize / g_bn_bwd_apply (a BatchNorm without scale: gamma = 1).
 // alpha < 0 -> no activation, alpha == 0 -> relu, alpha > 0 -> leaky relu.
 void g_conv_fwd(hipStream_t s, int B, View A, View Bv, const float* w, const float* bias, View out, int K, float alpha);
 // dz = dy * act'(y) in place on dy (dense tensors)
 void g_act_bwd(hipStream_t s, size_t n, float* dy, const float* y, float alpha);
+void g_act_bwd_view(hipStream_t s, int B, View dy, View y, float alpha);      // the same on views (channel slices)
 // dA / dB (beta 0 = overwrite, 1 = accumulate) from dz (view of the conv output gradient, C = Cout)
 void g_conv_dgrad(hipStream_t s, int B, View dz, const float* w, View dA, int accA, View dB, int accB, int K);
 // dW (HWIO) += ..., dbias += ...   (atomic accumulation into pre-zeroed buffers)
@@ -30,10 +32,15 @@ void g_bn_stats_mean(hipStream_t s, int B, View x, double* ws);
 void g_bn_stats_var(hipStream_t s, int B, View x, double* ws);   // uses mean = ws[c]/n
 void g_bn_finalize(hipStream_t s, int C, double n, const double* ws, const float* gamma, const float* beta,
                    float* mmean, float* mvar, float* coef, int training, float momentum, float eps);
-void g_bn_apply(hipStream_t s, int B, View x, View y, const float* coef);
+// alpha: activation of the normalised value (as g_conv_fwd; MultiResUnet's conv -> BatchNorm -> ReLU)
+void g_bn_apply(hipStream_t s, int B, View x, View y, const float* coef, float alpha = -1.f);
 void g_bn_bwd_reduce(hipStream_t s, int B, View x, View dy, const float* coef, float* dgamma, float* dbeta);
 void g_bn_bwd_apply(hipStream_t s, int B, View x, View dy, View dx, int acc, const float* coef, const float* gamma,
                     const float* dgamma, const float* dbeta, double n);
+
+// residual join (MultiResUnet): out = relu(a + b); da, db (+)= dout * [out > 0].  The in-library cross-check of kernels_join.hip
+void g_join_fwd(hipStream_t s, int B, View a, View b, View out);
+void g_join_bwd(hipStream_t s, int B, View dout, View out, View da, int acca, View db, int accb);
 
 // head: logits[b,y,x] = sum_c feat*w[c] + bias  (Conv2D(1, 1), unet.py:241-244)
 void g_head_fwd(hipStream_t s, int B, View feat, const float* w, const float* bias, float* logits);

@@ -27,7 +27,7 @@ __global__ void k_conv_fwd(int B, View A, View Bv, const float* __restrict__ w, 
     int x = pix % W;
     int y = (pix / W) % H;
     int b = pix / ((size_t)W * H);
-    float acc = bias[co];
+    float acc = bias ? bias[co] : 0.f;
     for (int ky = 0; ky < K; ++ky) {
         int iy = y + ky - pad;
         if (iy < 0 || iy >= H) continue;
@@ -58,6 +58,21 @@ __global__ void k_act_bwd(size_t n, float* __restrict__ dy, const float* __restr
 
 void g_act_bwd(hipStream_t s, size_t n, float* dy, const float* y, float alpha) {
     hipLaunchKernelGGL(k_act_bwd, dim3(nblk(n)), dim3(TB), 0, s, n, dy, y, alpha);
+}
+
+__global__ void k_act_bwd_view(size_t npix, View dy, View y, float alpha) {
+    const int C = y.C;
+    size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= npix * C) return;
+    int c = i % C;
+    size_t p = i / C;
+    float* d = dy.p + p * dy.ps + c;
+    *d = *d * (y.p[p * y.ps + c] > 0.f ? 1.f : alpha);
+}
+
+void g_act_bwd_view(hipStream_t s, int B, View dy, View y, float alpha) {
+    size_t npix = (size_t)B * y.H * y.W;
+    hipLaunchKernelGGL(k_act_bwd_view, dim3(nblk(npix * y.C)), dim3(TB), 0, s, npix, dy, y, alpha);
 }
 
 // ------------------------------------------------------------------------------------------------ conv dgrad
@@ -108,7 +123,7 @@ __global__ void k_conv_wgrad(int B, View A, View Bv, View dz, float* __restrict_
     const size_t p0 = (size_t)blockIdx.x * ppb;
     const size_t p1 = p0 + ppb < npix ? p0 + ppb : npix;
     const int nW = K * K * Cin * Cout;
-    for (int wi = threadIdx.x; wi < nW + Cout; wi += TB) {
+    for (int wi = threadIdx.x; wi < nW + (dbias ? Cout : 0); wi += TB) {
         float acc = 0.f;
         if (wi >= nW) {
             int co = wi - nW;
@@ -357,7 +372,7 @@ __global__ void k_bn_finalize(int C, double n, const double* __restrict__ ws, co
         var = mvar[c];
     }
     float inv = 1.0f / sqrtf(var + eps);
-    float sc = gamma[c] * inv;
+    float sc = (gamma ? gamma[c] : 1.f) * inv;
     coef[c] = sc;
     coef[C + c] = beta[c] - mean * sc;
     coef[2 * C + c] = mean;
@@ -370,18 +385,18 @@ void g_bn_finalize(hipStream_t s, int C, double n, const double* ws, const float
                        momentum, eps);
 }
 
-__global__ void k_bn_apply(size_t npix, View x, View y, const float* __restrict__ coef) {
+__global__ void k_bn_apply(size_t npix, View x, View y, const float* __restrict__ coef, float alpha) {
     const int C = x.C;
     size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     if (i >= npix * C) return;
     int c = i % C;
     size_t p = i / C;
-    y.p[p * y.ps + c] = fmaf(x.p[p * x.ps + c], coef[c], coef[C + c]);
+    y.p[p * y.ps + c] = act_apply(fmaf(x.p[p * x.ps + c], coef[c], coef[C + c]), alpha);
 }
 
-void g_bn_apply(hipStream_t s, int B, View x, View y, const float* coef) {
+void g_bn_apply(hipStream_t s, int B, View x, View y, const float* coef, float alpha) {
     size_t npix = (size_t)B * x.H * x.W;
-    hipLaunchKernelGGL(k_bn_apply, dim3(nblk(npix * x.C)), dim3(TB), 0, s, npix, x, y, coef);
+    hipLaunchKernelGGL(k_bn_apply, dim3(nblk(npix * x.C)), dim3(TB), 0, s, npix, x, y, coef, alpha);
 }
 
 __global__ void k_bn_bwd_reduce(size_t npix, View x, View dy, const float* __restrict__ coef, float* __restrict__ dgamma,
@@ -422,7 +437,7 @@ __global__ void k_bn_bwd_apply(size_t npix, View x, View dy, View dx, int acc, c
     float mean = coef[2 * C + c], inv = coef[3 * C + c];
     float xh = (x.p[p * x.ps + c] - mean) * inv;
     float d = dy.p[p * dy.ps + c];
-    float r = gamma[c] * inv * (d - inv_n * (dbeta[c] + xh * dgamma[c]));
+    float r = (gamma ? gamma[c] : 1.f) * inv * (d - inv_n * (dbeta[c] + xh * dgamma[c]));
     float* o = dx.p + p * dx.ps + c;
     *o = acc ? *o + r : r;
 }
@@ -432,6 +447,40 @@ void g_bn_bwd_apply(hipStream_t s, int B, View x, View dy, View dx, int acc, con
     size_t npix = (size_t)B * x.H * x.W;
     hipLaunchKernelGGL(k_bn_bwd_apply, dim3(nblk(npix * x.C)), dim3(TB), 0, s, npix, x, dy, dx, acc, coef, gamma, dgamma,
                        dbeta, (float)(1.0 / n));
+}
+
+// ------------------------------------------------------------------------------------------------ residual join
+__global__ void k_gjoin_fwd(size_t npix, View a, View b, View out) {
+    const int C = out.C;
+    size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= npix * C) return;
+    int c = i % C;
+    size_t p = i / C;
+    float v = a.p[p * a.ps + c] + b.p[p * b.ps + c];
+    out.p[p * out.ps + c] = v > 0.f ? v : 0.f;
+}
+
+void g_join_fwd(hipStream_t s, int B, View a, View b, View out) {
+    size_t npix = (size_t)B * out.H * out.W;
+    hipLaunchKernelGGL(k_gjoin_fwd, dim3(nblk(npix * out.C)), dim3(TB), 0, s, npix, a, b, out);
+}
+
+__global__ void k_gjoin_bwd(size_t npix, View dout, View out, View da, int acca, View db, int accb) {
+    const int C = out.C;
+    size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
+    if (i >= npix * C) return;
+    int c = i % C;
+    size_t p = i / C;
+    float d = out.p[p * out.ps + c] > 0.f ? dout.p[p * dout.ps + c] : 0.f;
+    float* pa = da.p + p * da.ps + c;
+    float* pb = db.p + p * db.ps + c;
+    *pa = acca ? *pa + d : d;
+    *pb = accb ? *pb + d : d;
+}
+
+void g_join_bwd(hipStream_t s, int B, View dout, View out, View da, int acca, View db, int accb) {
+    size_t npix = (size_t)B * out.H * out.W;
+    hipLaunchKernelGGL(k_gjoin_bwd, dim3(nblk(npix * out.C)), dim3(TB), 0, s, npix, dout, out, da, acca, db, accb);
 }
 
 // ------------------------------------------------------------------------------------------------ head

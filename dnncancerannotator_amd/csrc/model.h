@@ -1,5 +1,6 @@
 // model.h -- the layer plan of one annotator model and its device state.
 #pragma once
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -17,7 +18,8 @@ struct T {          // a tensor = data view + gradient view of identical geometr
 
 inline T tslice(const T& t, int c0, int c) { return T{slice(t.d, c0, c), slice(t.g, c0, c)}; }
 
-enum OpType { OP_CONV = 0, OP_BN, OP_POOL, OP_TCONV, OP_HEAD };
+// OP_JOIN (MultiResUnet): out = relu(inA + inB), the residual join of a MultiRes block / ResPath unit; the BatchNorm behind it is an OP_BN
+enum OpType { OP_CONV = 0, OP_BN, OP_POOL, OP_TCONV, OP_HEAD, OP_JOIN };
 
 struct Op {
     OpType type;
@@ -25,8 +27,14 @@ struct Op {
     T inA, inB, out;
     int64_t w_off = -1, b_off = -1;      // trainable offsets: kernel/bias, or gamma/beta for BN
     int64_t mm_off = -1, mv_off = -1;    // state offsets (BN moving mean / variance)
-    float alpha = -1.f;                  // conv activation: <0 none, 0 relu, >0 leaky
+    float alpha = -1.f;                  // conv activation (MultiResUnet: of a BatchNorm's output): <0 none, 0 relu, >0 leaky
     int k = 0;                           // conv kernel size / pool+tconv rate
+    // conv without bias: b_off < 0, no bias add and no dbias.  BatchNorm without gamma (Keras scale=False): w_off < 0, gamma is 1
+    // and sum(dy xhat), which the data gradient still needs, goes to nogamma_sum instead of the gradient vector
+    float* nogamma_sum = nullptr;        // C floats inside Model::nogamma_scratch (zeroed at the top of every backward pass)
+    // BN, training forward: the launch that produced the input (join_fwd) left the channel sums in ws[0 .. C) and zeroed
+    // ws[C .. 2C): no memset, no mean pass (set by that launch, consumed by the BatchNorm's forward)
+    bool mean_ready = false;
     bool need_din = true;                // false for the convs that read the network input
     bool accA = false, accB = false;     // backward: accumulate into (instead of overwrite) the input gradients
     // activation-derivative fusion: the LAST gradient contributor of a conv+activation output multiplies the summed
@@ -110,6 +118,8 @@ struct StepSwitches {
     int lockstep_maxh = 128;
     int wg_prio = 1;                            // side stream: 0 normal, 1 least urgent, 2 most urgent
     size_t bucket_bytes = 8u << 20;             // gradient all-reduce bucket (at least 4096)
+    // MultiResUnet: the residual joins run as g_join_fwd / g_join_bwd + the generic BatchNorm passes instead of kernels_join.hip
+    bool no_join = false;
 };
 StepSwitches step_switches();                   // model.hip: fills the table from the environment
 
@@ -158,6 +168,13 @@ struct Model {
     double* bn_tab = nullptr;
     float* extra_zero = nullptr;         // buffer the tuned kernels need zeroed at the top of every backward pass
     size_t extra_zero_n = 0;
+    // MultiResUnet: sum(dy xhat) of the BatchNorms without gamma (Op::nogamma_sum), zeroed with the gradient vector by g_step_init;
+    // block partials [grid][C] + ticket of join_fwd's channel sums (kernels_join.hip; the ticket is left zeroed by every launch)
+    float* nogamma_scratch = nullptr;
+    size_t nogamma_n = 0;
+    double* join_part = nullptr;
+    unsigned* join_ticket = nullptr;
+    bool multires() const { return desc.arch == DNNCA_ARCH_MULTIRES; }
     float* head_partials = nullptr;      // [2048][8] block partials of the fused head kernel
     double* conf_dev = nullptr;
     T xin;                               // network input view (points at the current batch)
@@ -284,6 +301,10 @@ struct Model {
 
     ~Model();
     int build();
+    int64_t add_param(const std::string& name, std::initializer_list<int64_t> shape, int trainable);      // appends to `params`; returns the offset
+    T new_tensor(int H, int W, int C, int* rc);      // data + gradient buffers for max_batch images (no-op once *rc is an error)
+    int build_multires();                // the MultiResUnet plan (desc.arch == DNNCA_ARCH_MULTIRES)
+    int build_buffers();                 // flat parameter / gradient / optimizer vectors, staging and output buffers, Keras defaults
     int alloc(void** ptr, size_t bytes);
     int forward(const float* x_dev, int B, bool training);
     int loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cfg, bool backward);

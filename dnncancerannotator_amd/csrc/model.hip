@@ -57,6 +57,7 @@ StepSwitches step_switches() {
     s.fz_all = on("DNNCA_FZ_ALL");
     s.lockstep = on("DNNCA_LOCKSTEP");
     s.force_rccl = on("DNNCA_FORCE_RCCL");
+    s.no_join = on("DNNCA_NO_JOIN");
     s.fz_only = str("DNNCA_FZ_ONLY");
     s.fzb_only = str("DNNCA_FZB_ONLY");
     if (sscanf(str("DNNCA_STAMPS").c_str(), "%d,%d,%d", &s.stamp_c, &s.stamp_ns, &s.stamp_co) != 3) s.stamp_c = s.stamp_ns = s.stamp_co = 0;
@@ -238,8 +239,41 @@ int Model::flush_profile() {
 }
 
 // ---------------------------------------------------------------------------------------------- plan
+int64_t Model::add_param(const std::string& name, std::initializer_list<int64_t> shape, int trainable) {
+    ParamInfo pi;
+    pi.name = name;
+    pi.ndim = (int)shape.size();
+    pi.size = 1;
+    int i = 0;
+    for (int k = 0; k < 4; ++k) pi.shape[k] = 1;
+    for (auto s : shape) {
+        pi.shape[i++] = s;
+        pi.size *= s;
+    }
+    pi.trainable = trainable;
+    int64_t& n = trainable ? nT : nS;
+    pi.offset = n;
+    n += pi.size;
+    params.push_back(pi);
+    return pi.offset;
+}
+
+// tensors are allocated immediately (stream-ordered memset) -- simple and the sizes are static
+T Model::new_tensor(int H, int W, int C, int* rc) {
+    T t;
+    size_t n = (size_t)desc.max_batch * H * W * C;
+    float *dp = nullptr, *gp = nullptr;
+    if (*rc == DNNCA_OK) *rc = alloc((void**)&dp, n * 4);
+    if (*rc == DNNCA_OK) *rc = alloc((void**)&gp, n * 4);
+    t.d.p = dp; t.d.H = H; t.d.W = W; t.d.C = C; t.d.ps = C;
+    t.g = t.d;
+    t.g.p = gp;
+    return t;
+}
+
 int Model::build() {
     sw = step_switches();
+    if (desc.arch == DNNCA_ARCH_MULTIRES) return build_multires();
     const dnnca_model_desc& d = desc;
     if (d.arch != DNNCA_ARCH_UNET && d.arch != DNNCA_ARCH_MULMO) { set_error("unknown arch %d", d.arch); return DNNCA_EINVAL; }
     if (d.conv_stride != 1) { set_error("conv_stride %d unsupported (reference configs use 1)", d.conv_stride); return DNNCA_EINVAL; }
@@ -254,44 +288,11 @@ int Model::build() {
     const int nenc = mulmo ? d.in_channels : 1;
     if (mulmo && (d.reference_index < 0 || d.reference_index >= nenc)) { set_error("reference_index out of range"); return DNNCA_EINVAL; }
     const int K = d.kernel_size, r = d.rate, L = d.n_downsample;
-    const size_t MB = (size_t)d.max_batch;
     const float act = d.leaky_alpha;   // 0 relu, >0 leaky
 
-    auto add_param = [&](const std::string& name, std::initializer_list<int64_t> shape, int trainable) -> int64_t {
-        ParamInfo pi;
-        pi.name = name;
-        pi.ndim = (int)shape.size();
-        pi.size = 1;
-        int i = 0;
-        for (int k = 0; k < 4; ++k) pi.shape[k] = 1;
-        for (auto s : shape) {
-            pi.shape[i++] = s;
-            pi.size *= s;
-        }
-        pi.trainable = trainable;
-        int64_t& n = trainable ? nT : nS;
-        pi.offset = n;
-        n += pi.size;
-        params.push_back(pi);
-        return pi.offset;
-    };
-
-    std::vector<std::pair<float**, size_t>> pending;   // tensors to allocate: (slot, floats)
-    struct Slot { float* d; float* g; };
-    std::vector<Slot*> slots;
-    // tensors are allocated immediately (stream-ordered memset) -- simple and the sizes are static
+    auto add_param = [&](const std::string& name, std::initializer_list<int64_t> shape, int trainable) { return this->add_param(name, shape, trainable); };
     int rc = DNNCA_OK;
-    auto new_tensor = [&](int H, int W, int C) -> T {
-        T t;
-        size_t n = MB * H * W * C;
-        float *dp = nullptr, *gp = nullptr;
-        if (rc == DNNCA_OK) rc = alloc((void**)&dp, n * 4);
-        if (rc == DNNCA_OK) rc = alloc((void**)&gp, n * 4);
-        t.d.p = dp; t.d.H = H; t.d.W = W; t.d.C = C; t.d.ps = C;
-        t.g = t.d;
-        t.g.p = gp;
-        return t;
-    };
+    auto new_tensor = [&](int H, int W, int C) { return this->new_tensor(H, W, C, &rc); };
 
     auto add_bn = [&](const std::string& prefix, const T& in, const T& out) {
         Op o;
@@ -469,7 +470,12 @@ int Model::build() {
     }
     fast_plan_masks(this);
     DN_TRY(ig_plan_half(this));
+    return build_buffers();
+}
 
+int Model::build_buffers() {
+    const dnnca_model_desc& d = desc;
+    const size_t MB = (size_t)d.max_batch;
     // flat buffers
     DN_TRY(alloc((void**)&p, (size_t)nT * 4));
     DN_TRY(alloc((void**)&g, (size_t)(nT + 8 + 4) * 4));
@@ -503,6 +509,201 @@ int Model::build() {
     }
     HIP_TRY(hipEventCreate(&ev0));
     HIP_TRY(hipEventCreate(&ev1));
+    return DNNCA_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------- MultiResUnet plan
+// models/tf_models/multiresunet.py, in the order in which its code calls the layers (= Keras variable creation order):
+//   conv2d_bn(x, f, k):  conv k x k, same, no bias -> BatchNorm without gamma -> ReLU | nothing        (OP_CONV, OP_BN with alpha)
+//   MultiResBlock(U):    shortcut = conv2d_bn 1x1 (c1 + c2 + c3, none); a, b, c = conv2d_bn 3x3 chained (c1, c2, c3, relu);
+//                        out = BN(concat[a, b, c]); out = BN(relu(shortcut + out))                      (OP_JOIN + OP_BN)
+//   ResPath(f, length):  length x { s = conv2d_bn 1x1 (none); o = conv2d_bn 3x3 (relu); x = BN(relu(s + o)) }
+// Concats are never materialised: a, b, c are channel slices of one tensor that the concat BatchNorm reads whole; the decoder's
+// concat[tconv, respath] is the two-source input (inA, inB) of the block's shortcut conv and first 3x3 conv.
+static void multires_widths(int U, int* c1, int* c2, int* c3) {
+    const double W = 1.67 * U;          // evaluated in double, as Python does (alpha = 1.67)
+    *c1 = (int)(W * 0.167);
+    *c2 = (int)(W * 0.333);
+    *c3 = (int)(W * 0.5);
+}
+
+int Model::build_multires() {
+    dnnca_model_desc& d = desc;
+    if (d.in_channels < 1 || d.n_filters_first < 1 || d.max_batch < 1 || d.height < 1 || d.width < 1) { set_error("bad model_options"); return DNNCA_EINVAL; }
+    if (d.dtype != DNNCA_F32) { set_error("MultiResUnet runs in dtype f32 only (bf16 is not implemented for this model)"); return DNNCA_EINVAL; }
+    if (d.height % 16 || d.width % 16) { set_error("MultiResUnet: H, W (%d, %d) must be multiples of 16 (four 2x2 poolings)", d.height, d.width); return DNNCA_EINVAL; }
+    for (int l = 0, U = d.n_filters_first; l < 5; ++l, U *= 2) {
+        int c1, c2, c3;
+        multires_widths(U, &c1, &c2, &c3);
+        if (c1 < 1 || c2 < 1 || c3 < 1) { set_error("MultiResUnet: n_filters_first %d gives an empty conv at U = %d (widths %d, %d, %d)", d.n_filters_first, U, c1, c2, c3); return DNNCA_EINVAL; }
+    }
+    // the arch implies what FLAG_GENERIC implies: no tuned launcher and no fused, riding or elided arm takes an op of this plan
+    // (its widths are no multiples of 16, its convs have no bias and its BatchNorms no gamma); the joins have kernels of their own
+    d.flags |= 1;
+    d.n_downsample = 4; d.rate = 2; d.kernel_size = 3; d.conv_stride = 1; d.bn = 1; d.padding = DNNCA_PAD_SAME;
+    d.n_conv = 3; d.leaky_alpha = 0.f; d.l2 = 0.f; d.reference_index = 0;
+
+    int rc = DNNCA_OK;
+    auto tensor = [&](int H, int W, int C) { return this->new_tensor(H, W, C, &rc); };
+    xin.d.H = d.height; xin.d.W = d.width; xin.d.C = d.in_channels; xin.d.ps = d.in_channels;
+    xin.g = xin.d;
+    const T none;                        // C = 0
+    bool reads_input = true;             // until the first block's two convs of the network input have been added
+
+    auto bn = [&](const std::string& prefix, const T& in, const T& out, bool gamma, float alpha) {
+        Op o;
+        o.type = OP_BN;
+        o.name = prefix;
+        o.inA = in;
+        o.out = out;
+        o.alpha = alpha;
+        const int C = in.d.C;
+        if (gamma) o.w_off = add_param(prefix + ".gamma", {C}, 1);
+        o.b_off = add_param(prefix + ".beta", {C}, 1);
+        o.mm_off = add_param(prefix + ".moving_mean", {C}, 0);
+        o.mv_off = add_param(prefix + ".moving_variance", {C}, 0);
+        if (rc == DNNCA_OK) rc = alloc((void**)&o.coef, (size_t)4 * C * 4);
+        if (rc == DNNCA_OK) rc = alloc((void**)&o.ws, (size_t)2 * C * 8);
+        if (!gamma) nogamma_n += (size_t)C;
+        ops.push_back(o);
+    };
+    // conv2d_bn: `out` receives the BatchNorm's (activated) output
+    auto conv_bn = [&](const std::string& prefix, const T& inA, const T& inB, const T& out, int k, float alpha) {
+        Op o;
+        o.type = OP_CONV;
+        o.name = prefix;
+        o.inA = inA;
+        o.inB = inB;
+        o.out = tensor(out.d.H, out.d.W, out.d.C);
+        o.k = k;
+        o.alpha = -1.f;
+        o.need_din = !reads_input;
+        o.w_off = add_param(prefix + ".kernel", {k, k, inA.d.C + inB.d.C, out.d.C}, 1);
+        ops.push_back(o);
+        bn(prefix + ".bn", o.out, out, false, alpha);
+    };
+    auto join_bn = [&](const std::string& prefix, const T& a, const T& b) -> T {
+        Op o;
+        o.type = OP_JOIN;
+        o.name = prefix + ".join";
+        o.inA = a;
+        o.inB = b;
+        o.out = tensor(a.d.H, a.d.W, a.d.C);
+        ops.push_back(o);
+        T out = tensor(a.d.H, a.d.W, a.d.C);
+        bn(prefix + ".out_bn", o.out, out, true, -1.f);
+        return out;
+    };
+    auto block = [&](const std::string& p, int U, const T& inA, const T& inB) -> T {
+        int c1, c2, c3;
+        multires_widths(U, &c1, &c2, &c3);
+        const int H = inA.d.H, W = inA.d.W, Cs = c1 + c2 + c3;
+        T shortcut = tensor(H, W, Cs), cat = tensor(H, W, Cs), cat_n = tensor(H, W, Cs);
+        const T a = tslice(cat, 0, c1), b = tslice(cat, c1, c2), c = tslice(cat, c1 + c2, c3);
+        conv_bn(p + ".shortcut", inA, inB, shortcut, 1, -1.f);
+        conv_bn(p + ".conv3", inA, inB, a, 3, 0.f);
+        reads_input = false;
+        conv_bn(p + ".conv5", a, none, b, 3, 0.f);
+        conv_bn(p + ".conv7", b, none, c, 3, 0.f);
+        bn(p + ".cat_bn", cat, cat_n, true, -1.f);
+        return join_bn(p, shortcut, cat_n);
+    };
+    auto respath = [&](const std::string& p, int f, int length, T x) -> T {
+        for (int i = 0; i < length; ++i) {
+            const std::string q = p + "." + std::to_string(i);
+            T s = tensor(x.d.H, x.d.W, f), o = tensor(x.d.H, x.d.W, f);
+            conv_bn(q + ".shortcut", x, none, s, 1, -1.f);
+            conv_bn(q + ".conv", x, none, o, 3, 0.f);
+            x = join_bn(q, s, o);
+        }
+        return x;
+    };
+
+    const int U0 = d.n_filters_first;
+    T cur = xin, skip[4];
+    for (int l = 0; l < 5; ++l) {
+        const std::string n = std::to_string(l + 1);
+        T out = block("block" + n, U0 << l, cur, none);
+        if (l == 4) { cur = out; break; }
+        Op o;
+        o.type = OP_POOL;
+        o.name = "pool" + n;
+        o.inA = out;
+        o.out = tensor(out.d.H / 2, out.d.W / 2, out.d.C);
+        o.k = 2;
+        ops.push_back(o);
+        cur = o.out;
+        skip[l] = respath("respath" + n, U0 << l, 4 - l, out);
+    }
+    for (int u = 0; u < 4; ++u) {
+        const int l = 3 - u, U = U0 << l;
+        const std::string n = std::to_string(6 + u);
+        Op o;
+        o.type = OP_TCONV;
+        o.name = "up" + n + ".tconv";
+        o.inA = cur;
+        o.out = tensor(cur.d.H * 2, cur.d.W * 2, U);
+        o.k = 2;
+        o.w_off = add_param("up" + n + ".tconv.kernel", {2, 2, U, cur.d.C}, 1);
+        o.b_off = add_param("up" + n + ".tconv.bias", {U}, 1);
+        ops.push_back(o);
+        cur = block("block" + n, U, o.out, skip[l]);
+    }
+    // head: conv2d_bn 1x1 -> 1 channel; the logits the loss consumes are the output of that BatchNorm (losses.py reads
+    // y_pred._keras_logits), the sigmoid is the loss kernel's / g_sigmoid's
+    T head = tensor(d.height, d.width, 1);
+    conv_bn("head", cur, none, head, 1, -1.f);
+    outH = d.height;
+    outW = d.width;
+    if (rc != DNNCA_OK) return rc;
+
+    // sum(dy xhat) of the BatchNorms without gamma, and the partial table of the widest join
+    DN_TRY(alloc((void**)&nogamma_scratch, (nogamma_n + 4) * 4));
+    size_t at = 0, part = 1;
+    for (Op& o : ops) {
+        if (o.type == OP_BN && o.w_off < 0) { o.nogamma_sum = nogamma_scratch + at; at += (size_t)o.inA.d.C; }
+        if (o.type == OP_JOIN) part = std::max(part, join_part_doubles(o.out.d.C));
+    }
+    DN_TRY(alloc((void**)&join_part, part * 8));
+    DN_TRY(alloc((void**)&join_ticket, 16));
+
+    // backward accumulation flags: the first op (in backward order) to produce a gradient overwrites, later ones add -- by channel
+    // INTERVAL of the gradient buffer, not by pointer: the concat BatchNorm's backward writes slices a, b and c through the base
+    // pointer, which only slice a shares, so conv7's backward must ADD to slice b.  A later writer must lie inside what an earlier
+    // one wrote (a wider one would add to channels nobody has written)
+    struct Span { const float* p; int C; };
+    std::vector<Span> written;
+    int bad = 0;
+    auto claim = [&](const View& g) -> bool {
+        bool overlap = false, inside = false;
+        for (const Span& w : written) {
+            if (g.p < w.p + w.C && w.p < g.p + g.C) overlap = true;
+            if (g.p >= w.p && g.p + g.C <= w.p + w.C) inside = true;
+        }
+        if (overlap && !inside) ++bad;
+        if (!inside) written.push_back(Span{g.p, g.C});
+        return overlap;
+    };
+    for (int i = (int)ops.size() - 1; i >= 0; --i) {
+        Op& o = ops[i];
+        if (!o.need_din) continue;
+        o.accA = claim(o.inA.g);
+        if ((o.type == OP_CONV || o.type == OP_JOIN) && o.inB.d.C) o.accB = claim(o.inB.g);
+    }
+    if (bad) { set_error("internal: MultiResUnet plan: %d gradient writers partly overlap an earlier one", bad); return DNNCA_ESTATE; }
+    // what the forward pass relies on: the op behind a join is the BatchNorm (with gamma) of the joined tensor
+    for (size_t i = 0; i < ops.size(); ++i) {
+        if (ops[i].type != OP_JOIN) continue;
+        const bool ok = i + 1 < ops.size() && ops[i + 1].type == OP_BN && ops[i + 1].inA.d.p == ops[i].out.d.p &&
+                        ops[i + 1].inA.d.C == ops[i].out.d.C && ops[i + 1].w_off >= 0;
+        if (!ok) { set_error("internal: MultiResUnet plan: %s is not followed by its BatchNorm", ops[i].name.c_str()); return DNNCA_ESTATE; }
+    }
+
+    DN_TRY(build_buffers());
+    // the head BatchNorm's output and output gradient ARE the logits and their gradient
+    logits = ops.back().out.d.p;
+    dlogits = ops.back().out.g.p;
     return DNNCA_OK;
 }
 
@@ -636,7 +837,7 @@ int Model::forward(const float* x_dev, int B, bool training) {
                 if (sens_pass && !(desc.flags & 1) && ig_conv_fwd(this, B, o, bytes, flops, nullptr)) break;      // dense conv, output stored, nothing riding
                 if (!all_f32(o)) return DNNCA_ESTATE;
                 LAUNCH(this, "g_conv_fwd", bytes, flops,
-                       g_conv_fwd(stream, B, o.inA.d, o.inB.d, p + o.w_off, p + o.b_off, o.out.d, o.k, o.alpha));
+                       g_conv_fwd(stream, B, o.inA.d, o.inB.d, p + o.w_off, o.b_off >= 0 ? p + o.b_off : nullptr, o.out.d, o.k, o.alpha));
                 break;
             }
             case OP_BN: {
@@ -659,14 +860,40 @@ int Model::forward(const float* x_dev, int B, bool training) {
                 }
                 if (!all_f32(o)) return DNNCA_ESTATE;
                 if (training) {
-                    if (!dry) HIP_TRY(hipMemsetAsync(o.ws, 0, (size_t)2 * C * 8, stream));
-                    LAUNCH(this, "g_bn_stats_mean", tb, tb / 4, g_bn_stats_mean(stream, B, o.inA.d, o.ws));
+                    if (!o.mean_ready) {          // (else: join_fwd left the sums and zeroed the squares' row)
+                        if (!dry) HIP_TRY(hipMemsetAsync(o.ws, 0, (size_t)2 * C * 8, stream));
+                        LAUNCH(this, "g_bn_stats_mean", tb, tb / 4, g_bn_stats_mean(stream, B, o.inA.d, o.ws));
+                    }
+                    o.mean_ready = false;
                     LAUNCH(this, "g_bn_stats_var", tb, tb / 2, g_bn_stats_var(stream, B, o.inA.d, o.ws));
                 }
                 LAUNCH(this, "g_bn_finalize", 0, 0,
-                       g_bn_finalize(stream, C, n, o.ws, p + o.w_off, p + o.b_off, state + o.mm_off, state + o.mv_off,
+                       g_bn_finalize(stream, C, n, o.ws, o.w_off >= 0 ? p + o.w_off : nullptr, p + o.b_off, state + o.mm_off, state + o.mv_off,
                                      o.coef, training ? 1 : 0, kBnMomentum, kBnEps));
-                LAUNCH(this, "g_bn_apply", 2 * tb, tb / 2, g_bn_apply(stream, B, o.inA.d, o.out.d, o.coef));
+                LAUNCH(this, "g_bn_apply", 2 * tb, tb / 2, g_bn_apply(stream, B, o.inA.d, o.out.d, o.coef, o.alpha));
+                break;
+            }
+            case OP_JOIN: {
+                // out = relu(inA + inB); the BatchNorm behind it is ops[oi + 1] (build_multires)
+                const double tb = 4.0 * nelem(B, o.out.d);
+                Op& nb = ops[oi + 1];
+                if (sw.no_join) {
+                    LAUNCH(this, "g_join_fwd", 3 * tb, tb / 4, g_join_fwd(stream, B, o.inA.d, o.inB.d, o.out.d));
+                    break;
+                }
+                if (training) {
+                    // one pass: the joined tensor and the channel sums of the BatchNorm's mean; the BatchNorm's own arm runs the
+                    // variance pass, finalize and apply
+                    LAUNCH(this, "join_fwd", 3 * tb, tb / 2, join_fwd(stream, B, o.inA.d, o.inB.d, o.out.d, nb.ws, join_part, join_ticket));
+                    nb.mean_ready = true;
+                    break;
+                }
+                // inference: add, ReLU and the BatchNorm's affine from the moving statistics in one pass; the joined tensor is not stored
+                LAUNCH(this, "g_bn_finalize", 0, 0,
+                       g_bn_finalize(stream, nb.inA.d.C, 1.0, nb.ws, p + nb.w_off, p + nb.b_off, state + nb.mm_off, state + nb.mv_off,
+                                     nb.coef, 0, kBnMomentum, kBnEps));
+                LAUNCH(this, "join_infer", 3 * tb, tb, join_infer(stream, B, o.inA.d, o.inB.d, nb.out.d, nb.coef));
+                op_done[oi + 1] = 1;
                 break;
             }
             case OP_POOL: {
@@ -738,8 +965,8 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
     // scalars: label sum 0, min +inf, max -inf, loss 0, l2 0
     if (!(step_init_done && backward))
         LAUNCH(this, "g_step_init", 0, 0,
-               g_step_init(stream, scalars, g, backward ? (size_t)(nT + 8) : 0, extra_zero,
-                           backward && !generic ? extra_zero_n : 0));
+               g_step_init(stream, scalars, g, backward ? (size_t)(nT + 8) : 0, multires() ? nogamma_scratch : extra_zero,
+                           !backward ? 0 : (multires() ? nogamma_n : (generic ? 0 : extra_zero_n))));
     step_init_done = false;
     if (labels_done) {
         // the forward pass of this train step already ran the label statistics (and maybe the head, in its last conv's epilogue)
@@ -837,7 +1064,7 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
                         LAUNCH(this, "g_act_bwd", 3 * ob, ob / 4,
                                g_act_bwd(stream, (size_t)nelem(B, o.out.d), o.out.g.p, o.out.d.p, o.alpha));
                     LAUNCH(this, "g_conv_wgrad", ob + ib, flops,
-                           g_conv_wgrad(stream, B, o.inA.d, o.inB.d, o.out.g, g + o.w_off, g + o.b_off, o.k));
+                           g_conv_wgrad(stream, B, o.inA.d, o.inB.d, o.out.g, g + o.w_off, o.b_off >= 0 ? g + o.b_off : nullptr, o.k));
                     if (o.need_din)
                         LAUNCH(this, "g_conv_dgrad", ob + ib, flops,
                                g_conv_dgrad(stream, B, o.out.g, p + o.w_off, o.inA.g, o.accA, o.inB.g, o.accB, o.k));
@@ -849,11 +1076,26 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
                     if (!generic && fast_bn_bwd(this, B, o)) break;
                     if (!all_f32(o)) return DNNCA_ESTATE;
                     if (o.maskA) { set_error("internal: masked batch-norm gradient has no tuned kernel"); return DNNCA_ESTATE; }
+                    // (MultiResUnet) conv -> BatchNorm -> ReLU: the activation's derivative first, in place on the output gradient
+                    if (o.alpha >= 0.f)
+                        LAUNCH(this, "g_act_bwd", 3 * tb, tb / 4, g_act_bwd_view(stream, B, o.out.g, o.out.d, o.alpha));
+                    // a BatchNorm without gamma still needs sum(dy xhat) for its data gradient: it goes to the op's scratch row
+                    float* dgamma = o.w_off >= 0 ? g + o.w_off : o.nogamma_sum;
                     LAUNCH(this, "g_bn_bwd_reduce", 2 * tb, tb,
-                           g_bn_bwd_reduce(stream, B, o.inA.d, o.out.g, o.coef, g + o.w_off, g + o.b_off));
+                           g_bn_bwd_reduce(stream, B, o.inA.d, o.out.g, o.coef, dgamma, g + o.b_off));
                     LAUNCH(this, "g_bn_bwd_apply", 3 * tb, 2 * tb,
-                           g_bn_bwd_apply(stream, B, o.inA.d, o.out.g, o.inA.g, o.accA, o.coef, p + o.w_off, g + o.w_off,
+                           g_bn_bwd_apply(stream, B, o.inA.d, o.out.g, o.inA.g, o.accA, o.coef, o.w_off >= 0 ? p + o.w_off : nullptr, dgamma,
                                           g + o.b_off, n));
+                    break;
+                }
+                case OP_JOIN: {
+                    const double tb = 4.0 * nelem(B, o.out.d);
+                    if (sw.no_join)
+                        LAUNCH(this, "g_join_bwd", (4 + o.accA + o.accB) * tb, tb / 4,
+                               g_join_bwd(stream, B, o.out.g, o.out.d, o.inA.g, o.accA, o.inB.g, o.accB));
+                    else
+                        LAUNCH(this, "join_bwd", (4 + o.accA + o.accB) * tb, tb / 4,
+                               join_bwd(stream, B, o.out.g, o.out.d, o.inA.g, o.accA, o.inB.g, o.accB));
                     break;
                 }
                 case OP_POOL: {
@@ -928,6 +1170,7 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
 // forward's) and the BatchNorm coefficient tables.  The convs that read the network input get no dx tensor: one launch forms |dx| and
 // reduces it (k_sens_first).
 int Model::input_sensitivity(const float* x_dev, int B) {
+    if (multires()) { set_error("input sensitivity is not implemented for MultiResUnet (its pass knows the U-Net op types only)"); return DNNCA_EINVAL; }
     if (desc.dtype != DNNCA_F32) { set_error("input sensitivity needs a dtype f32 model (this one is bf16)"); return DNNCA_EINVAL; }
     if (desc.kernel_size > kSensMaxK) { set_error("input sensitivity: kernel_size %d above %d", desc.kernel_size, kSensMaxK); return DNNCA_EINVAL; }
     sens_pass = true;
@@ -966,6 +1209,7 @@ int Model::input_sensitivity(const float* x_dev, int B) {
         Op& o = ops[i];
         cur_op = &o.name;
         switch (o.type) {
+            case OP_JOIN: break;          // (never reached: refused above)
             case OP_HEAD: {
                 const double npix = (double)B * outH * outW;
                 LAUNCH(this, "sens_head", 4.0 * (npix + nelem(B, o.inA.d)), 12.0 * nelem(B, o.inA.d),

@@ -208,7 +208,7 @@ class DeviceModel:
                  dtype='f32', force_generic=False):
         self.lib = _lib.load()
         d = _lib.ModelDesc()
-        d.arch = {'unet': _lib.ARCH_UNET, 'mulmo': _lib.ARCH_MULMO}[arch]
+        d.arch = {'unet': _lib.ARCH_UNET, 'mulmo': _lib.ARCH_MULMO, 'multires': _lib.ARCH_MULTIRES}[arch]
         d.in_channels, d.height, d.width, d.max_batch = int(in_channels), int(height), int(width), int(max_batch)
         d.n_filters_first, d.n_downsample, d.rate = int(n_filters_first), int(n_downsample), int(rate)
         d.kernel_size, d.conv_stride, d.bn = int(kernel_size), int(conv_stride), int(bool(bn))

@@ -547,6 +547,9 @@ class TFKerasModel:
     def eval(self, dataset, save_path, viz_ds=None, tag='val', avoid_overwrite=False, export_path=None, export_images=False,
              visualize_sensitivity=False, export_csv=False, min_interval=1, step_range=None, overlay=False,
              export_casewise_metrics=False):
+        if visualize_sensitivity and not getattr(self.model, 'supports_sensitivity', True):
+            raise NotImplementedError('--visualize_sensitivity is not implemented for model: %s (the input-gradient pass covers the '
+                                      'U-Net models only)' % self.model_config['model'])
         self._build(dataset)
         ckpt_path = os.path.join(save_path, 'checkpoints')
         if not export_path:

@@ -30,6 +30,11 @@ extern "C" {
 #define DNNCA_EASSERT (-5)     /* a reference-side tf.debugging.assert_* would have fired (utils/losses.py:30,91-99) */
 
 enum { DNNCA_ARCH_UNET = 0, DNNCA_ARCH_MULMO = 1 };     /* models/tf_models/unet.py:194 UNetAnnotator, :285 MulmoUNetAnnotator */
+/* models/tf_models/multiresunet.py MultiResUnet (configs/multiresunet.yaml).  Of dnnca_model_desc it reads arch, in_channels, height,
+   width (multiples of 16), max_batch, n_filters_first (the U of the first MultiRes block, doubled per level; the reference uses 32)
+   and dtype (DNNCA_F32 only); every other field is ignored: the graph is fixed (five levels, 2x2 pooling, 1x1 and 3x3 convs without
+   bias, BatchNorm everywhere, ReLU, no regulariser).  It always runs on the shape-generic kernels plus the residual-join kernels. */
+enum { DNNCA_ARCH_MULTIRES = 2 };
 enum { DNNCA_PAD_VALID = 0, DNNCA_PAD_SAME = 1 };       /* model_options.padding (configs/unet.yaml:9) */
 /* arithmetic type of the conv contractions.  DNNCA_BF16: the operands of the 3x3 convolutions with >= 32 channels and of the
    transposed convolutions with channel counts that are multiples of 64 are rounded to bfloat16 (round to nearest even) on
