@@ -8,6 +8,13 @@ import logging
 import sys
 
 
+def _at_least_one(text):
+    n = int(text)
+    if n < 1:
+        raise argparse.ArgumentTypeError('must be at least 1, got %d' % n)
+    return n
+
+
 def build_parser(prog='python3 -m annotator'):
     parser = argparse.ArgumentParser(prog=prog, description='DNNAnnotator: DNN model to predict cancer segmentation (MI355X engine)')
     sub = parser.add_subparsers(dest='command', help='command')
@@ -49,6 +56,11 @@ def build_parser(prog='python3 -m annotator'):
     p.add_argument('--resize_factor', type=float, default=1.0, help='analyse the probabilities resized by this factor')
     p.add_argument('--max_lesions', type=int, default=256, help='lesions per slice in lesions.csv (default: 256)')
     p.add_argument('--export_images', action='store_true', help='also write <exam>/<slice>/mask.png')
+    # absent unless given (the defaults are those of runs.predict.predict)
+    p.add_argument('--link_slices', action='store_true', default=argparse.SUPPRESS,
+                   help='join the lesions of neighbouring slices of an exam: also write exam_lesions.csv and exam_lesion_parts.csv')
+    p.add_argument('--link_min_overlap', type=_at_least_one, default=argparse.SUPPRESS,
+                   help='common pixels that join two lesions of neighbouring slices (default: 1)')
     return parser
 
 

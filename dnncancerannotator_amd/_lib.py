@@ -71,6 +71,14 @@ class LesionRow(C.Structure):                      # dnnca_lesion_row (56 bytes,
 LESION_ROW_DTYPE = np.dtype([('slice', '<i4'), ('row', '<i4'), ('area', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'),
                              ('y1', '<i4'), ('max_prob', '<f4'), ('sum_x', '<u8'), ('sum_y', '<u8'), ('sum_prob_q24', '<u8')])
 
+
+class LesionLink(C.Structure):                     # dnnca_lesion_link (16 bytes)
+    _fields_ = [('slice', C.c_int32), ('row_prev', C.c_int32), ('row', C.c_int32), ('overlap', C.c_int32)]
+
+
+# DeviceModel.lesion_table_linked returns its links as a structured array of this dtype
+LESION_LINK_DTYPE = np.dtype([('slice', '<i4'), ('row_prev', '<i4'), ('row', '<i4'), ('overlap', '<i4')])
+
 _FP = C.POINTER(C.c_float)
 _VP = C.c_void_p
 
@@ -137,6 +145,10 @@ SIGNATURES = {
     'dnnca_lesion_table': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
                                      C.POINTER(C.c_int32)]),
+    'dnnca_lesion_table_linked': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
+                                            C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(LesionLink), C.c_int64,
+                                            C.POINTER(C.c_int64)]),
     'dnnca_input_sensitivity': (C.c_int, [_VP, _FP, C.c_int, C.POINTER(C.c_double)]),
     'dnnca_comm_unique_id': (C.c_int, [_VP]),
     'dnnca_comm_init': (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_size_t]),

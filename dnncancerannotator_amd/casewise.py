@@ -188,6 +188,69 @@ def slice_values(exam, slice_id, rows, total):
             '%.9g' % max([float(r['max_prob']) for r in rows], default=0.0), int(int(total) > len(rows))]
 
 
+# ---- `annotator predict --link_slices`: the 2-D lesions of an exam joined through its slices -----------------------------------
+EXAM_LESION_COLUMNS = ['exam', 'exam_lesion', 'first_slice', 'last_slice', 'n_slices', 'n_parts', 'volume_px', 'x0', 'y0', 'x1', 'y1',
+                       'centroid_x', 'centroid_y', 'centroid_slice', 'mean_prob', 'max_prob', 'truncated']
+EXAM_PART_COLUMNS = ['exam', 'slice', 'lesion', 'exam_lesion']
+
+
+def link_lesions(exam, slices, links, min_overlap=1):
+    """The lesions of one exam joined across its slices: (exam_lesions.csv values, exam_lesion_parts.csv values).
+
+    slices: [(slice_id, rows, total)] in the order the exam's slices were analysed -- `rows` the slice's records of lesion_table (at
+    most max_lesions), `total` its kept components.  links: one sequence per entry of `slices`: the (row_prev, row, overlap) of
+    lesion_table_linked between the entry before (row_prev) and this one (row); empty where the slice does not continue the one
+    before (the first slice, a gap in the slice numbers).  Two lesions belong together when a link of at least min_overlap pixels
+    joins them, directly or through others (union-find).  Exam lesions are numbered by their first member in (slice order, lesion
+    number) order.  Volume, bounding box, sums and the maximum are integer sums / extrema over the members; the centroids (the
+    slice's is the area-weighted mean slice_id) and mean_prob are float64 quotients written with repr; truncated = 1 when a
+    slice the lesion touches had more components than rows (those beyond max_lesions are in no table and link to nothing).
+    The parts come one per row, slice after slice: the order of the exam's lines in lesions.csv."""
+    if len(links) != len(slices):
+        raise ValueError('link_lesions: %d slices but %d link lists' % (len(slices), len(links)))
+    first, nodes = [], []                                           # first[i]: the node of row 0 of slices[i]; nodes: (i, row record)
+    for i, (_, rows, _) in enumerate(slices):
+        first.append(len(nodes))
+        nodes += [(i, r) for r in rows]
+    parent = list(range(len(nodes)))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    for i, mine in enumerate(links):
+        for row_prev, row, overlap in mine:
+            if i == 0 or not (0 <= int(row_prev) < len(slices[i - 1][1]) and 0 <= int(row) < len(slices[i][1])):
+                raise ValueError('link_lesions: link (%d, %d) into slice %d of the exam joins no rows' % (row_prev, row, i))
+            if int(overlap) >= min_overlap:
+                a, b = find(first[i - 1] + int(row_prev)), find(first[i] + int(row))
+                parent[max(a, b)] = min(a, b)                       # the root is the first member
+    number, members = {}, []
+    for n in range(len(nodes)):
+        root = find(n)
+        if root not in number:
+            number[root] = len(members)
+            members.append([])
+        members[number[root]].append(n)
+    table = []
+    for e, ms in enumerate(members):
+        rows = [nodes[n][1] for n in ms]
+        ids = [int(slices[nodes[n][0]][0]) for n in ms]
+        area = [int(r['area']) for r in rows]
+        volume = sum(area)
+        touched = sorted(set(nodes[n][0] for n in ms))
+        table.append([exam, e, min(ids), max(ids), len(touched), len(ms), volume,
+                      min(int(r['x0']) for r in rows), min(int(r['y0']) for r in rows), max(int(r['x1']) for r in rows),
+                      max(int(r['y1']) for r in rows), repr(sum(int(r['sum_x']) for r in rows) / volume),
+                      repr(sum(int(r['sum_y']) for r in rows) / volume), repr(sum(k * a for k, a in zip(ids, area)) / volume),
+                      repr(sum(int(r['sum_prob_q24']) for r in rows) / volume / Q24), '%.9g' % max(float(r['max_prob']) for r in rows),
+                      int(any(int(slices[i][2]) > len(slices[i][1]) for i in touched))])
+    parts = [[exam, int(slices[i][0]), int(r['row']), number[find(n)]] for n, (i, r) in enumerate(nodes)]
+    return table, parts
+
+
 def plain_csv(names, rows):
     """a header line and one line per row, csv-module quoting, no index column"""
     return _csv([list(names)] + [list(r) for r in rows])

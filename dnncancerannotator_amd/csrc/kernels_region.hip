@@ -27,6 +27,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <tuple>
 
 #include "region.h"
 
@@ -260,6 +261,36 @@ __device__ __forceinline__ size_t slot_hash(unsigned long long key, size_t cap) 
     return (size_t)(key % cap);
 }
 
+// wave_grouped over several tables: lanes that carry the same (table, key) are summed into one call by the first of them
+template <typename Fn>
+__device__ __forceinline__ void wave_grouped_at(bool on, size_t tb, unsigned long long key, Fn&& fn) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long pending = __ballot(on);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const unsigned long long key0 = __shfl(key, leader);
+        const size_t tb0 = __shfl(tb, leader);
+        const bool mine = on && key == key0 && tb == tb0;
+        const unsigned long long same = __ballot(mine);
+        if (lane == leader) fn(tb0, key0, (unsigned)__popcll(same));
+        if (mine) on = false;
+        pending &= ~same;
+    }
+}
+
+// `c` added to the count of `key` in one open-addressing table of `cap` slots (keys kEmpty, counts 0 before the first insert)
+__device__ __forceinline__ void table_add(unsigned long long* kt, unsigned* ct, size_t cap, unsigned long long key, unsigned c) {
+    size_t h = slot_hash(key, cap);
+    for (size_t probe = 0; probe < cap; ++probe) {
+        const unsigned long long old = atomicCAS(kt + h, kEmpty, key);
+        if (old == kEmpty || old == key) {
+            atomicAdd(ct + h, c);
+            break;
+        }
+        h = h + 1 == cap ? 0 : h + 1;
+    }
+}
+
 // overlap pixels of label root rl and prediction root rp (slice-local indices) -> table (t, b): key rl << 32 | rp, count
 __global__ __launch_bounds__(RB) void k_region_pairs(const int* __restrict__ LL, const int* __restrict__ LP, int T, int nb, size_t hw,
                                                      size_t cap, unsigned long long* __restrict__ keys, unsigned* __restrict__ cnt) {
@@ -278,30 +309,9 @@ __global__ __launch_bounds__(RB) void k_region_pairs(const int* __restrict__ LL,
             key = ((unsigned long long)((size_t)rl - b * hw) << 32) | (unsigned long long)((size_t)rp - t * n - b * hw);
         }
     }
-    const int lane = threadIdx.x & 63;
-    unsigned long long pending = __ballot(on);
-    while (pending) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const unsigned long long key0 = __shfl(key, leader);
-        const size_t tb0 = __shfl(tb, leader);
-        const bool mine = on && key == key0 && tb == tb0;
-        const unsigned long long same = __ballot(mine);
-        if (lane == leader) {
-            const unsigned c = (unsigned)__popcll(same);
-            unsigned long long* kt = keys + tb0 * cap;
-            size_t h = slot_hash(key0, cap);
-            for (size_t probe = 0; probe < cap; ++probe) {
-                const unsigned long long old = atomicCAS(kt + h, kEmpty, key0);
-                if (old == kEmpty || old == key0) {
-                    atomicAdd(cnt + tb0 * cap + h, c);
-                    break;
-                }
-                h = h + 1 == cap ? 0 : h + 1;
-            }
-        }
-        if (mine) on = false;
-        pending &= ~same;
-    }
+    wave_grouped_at(on, tb, key, [&](size_t tb0, unsigned long long key0, unsigned c) {
+        table_add(keys + tb0 * cap, cnt + tb0 * cap, cap, key0, c);
+    });
 }
 
 __global__ __launch_bounds__(RB) void k_region_match(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ cnt,
@@ -561,6 +571,77 @@ __global__ __launch_bounds__(RB) void k_lesion_mask(const int* __restrict__ L, c
     out[word] = packed;
 }
 
+// ---- links between neighbouring slices (dnnca_lesion_table_linked).  A pixel's lesion is row[L[g]]: the row number of its root,
+// taken as -1 on background, in a component below min_area and at rows >= cap (they are in no table).
+__device__ __forceinline__ int lesion_row_at(const int* __restrict__ L, const int* __restrict__ row, size_t g, int cap) {
+    const int root = L[g];
+    if (root < 0) return -1;
+    const int r = row[root];
+    return r < cap ? r : -1;
+}
+
+// pixel p of slice b whose flag is set counts one towards key (prev << 32 | cur) of slice b's table when it lies in a lesion of
+// the slice (cur) and pixel p of the slice before lies in one too (prev): the slice before is b - 1 of the chunk, or for b = 0
+// the carry plane (the last slice of the chunk or of the call before).  Wave-grouped like region_pairs.
+// A table has hw + 1 slots: distinct pairs of one slice number at most ceil(hw / 2).  Take one witness pixel per pair; two
+// 4-adjacent pixels that both lie in lesions of both slices lie in the same lesion of either slice, i.e. in the same pair, so
+// witnesses of different pairs are never 4-adjacent: they are an independent set of the hw-pixel grid, which has at most
+// ceil(hw / 2) members.  hw + 1 slots keep the load below one half.
+__global__ __launch_bounds__(RB) void k_lesion_link(const int* __restrict__ L, const int* __restrict__ row, const int* __restrict__ carry,
+                                                    const unsigned char* __restrict__ cont, int nb, size_t hw, int cap, size_t slots,
+                                                    unsigned long long* __restrict__ keys, unsigned* __restrict__ cnt) {
+    const size_t g = (size_t)blockIdx.x * RB + threadIdx.x;
+    bool on = false;
+    unsigned long long key = 0;
+    size_t b = 0;
+    if (g < (size_t)nb * hw) {
+        b = g / hw;
+        if (cont[b]) {
+            const int cur = lesion_row_at(L, row, g, cap);
+            if (cur >= 0) {
+                const int prev = b > 0 ? lesion_row_at(L, row, g - hw, cap) : carry[g];
+                if (prev >= 0 && prev < cap) {
+                    on = true;
+                    key = ((unsigned long long)(unsigned)prev << 32) | (unsigned)cur;
+                }
+            }
+        }
+    }
+    wave_grouped_at(on, b, key, [&](size_t b0, unsigned long long key0, unsigned c) {
+        table_add(keys + b0 * slots, cnt + b0 * slots, slots, key0, c);
+    });
+}
+
+struct LesionLink {                      // dnnca_lesion_link
+    int slice, row_prev, row, overlap;
+};
+static_assert(sizeof(LesionLink) == sizeof(dnnca_lesion_link), "the device list is copied into the caller's records");
+
+// one thread per slot of the chunk's tables: a filled slot appends its link to the list (in the order of the atomics: the host
+// sorts).  One atomic per wave: its filled slots take consecutive places
+__global__ __launch_bounds__(RB) void k_lesion_link_emit(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ cnt,
+                                                         size_t total, size_t slots, int slice0, unsigned list_cap,
+                                                         LesionLink* __restrict__ list, unsigned* __restrict__ n_list) {
+    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
+    const unsigned long long key = i < total ? keys[i] : kEmpty;
+    const bool has = key != kEmpty;
+    const unsigned long long bal = __ballot(has);
+    if (!bal) return;
+    const int lane = threadIdx.x & 63, leader = __ffsll((long long)bal) - 1;
+    unsigned base = 0;
+    if (lane == leader) base = atomicAdd(n_list, (unsigned)__popcll(bal));
+    base = __shfl(base, leader);
+    const unsigned at = base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
+    if (has && at < list_cap) list[at] = LesionLink{slice0 + (int)(i / slots), (int)(key >> 32), (int)(key & 0xffffffffu), (int)cnt[i]};
+}
+
+// the carry plane: the lesion (or -1) of every pixel of the chunk's last slice (L / row of that slice's first pixel at g0)
+__global__ __launch_bounds__(RB) void k_lesion_carry(const int* __restrict__ L, const int* __restrict__ row, size_t g0, size_t hw, int cap,
+                                                     int* __restrict__ carry) {
+    const size_t p = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (p < hw) carry[p] = lesion_row_at(L, row, g0 + p, cap);
+}
+
 inline unsigned nblocks(size_t n) { return (unsigned)((n + RB - 1) / RB); }
 
 }  // namespace
@@ -585,9 +666,15 @@ struct RegionState {
     size_t slice_acc_n = 0, slices = 0;
     uint32_t* viz = nullptr;             // rendered composites (dnnca_render_composite)
     size_t viz_bytes = 0;
-    float lesion_rf = 1.f;               // the last dnnca_lesion_table: what DNNCA_PLAN_LESION replays
+    float lesion_rf = 1.f;               // the last dnnca_lesion_table(_linked): what DNNCA_PLAN_LESION(_LINKED) replays
     int lesion_k = 5;
     bool lesion_mask = true;
+    // the carry plane of dnnca_lesion_table_linked: the row number (or -1) of every pixel of the last slice of the last linked
+    // chunk.  A buffer of its own, not part of `ws`: it outlives every other call on the model
+    int* carry = nullptr;
+    size_t carry_n = 0;                  // allocated pixels
+    bool carry_valid = false;            // written by a linked call that succeeded ...
+    int carry_oh = 0, carry_ow = 0;      // ... on planes of this size
 };
 
 static constexpr size_t kRegionBudget = size_t(1) << 24;    // pixel-thresholds per chunk (~21 bytes each)
@@ -934,10 +1021,16 @@ struct LesionWs {                        // carve-up of the workspace for nb sli
     unsigned* sp;
     float* thr;                          // the one threshold (region_prep reads its thresholds from the device)
     LesionAcc* acc;
+    // linked calls only, behind everything else: per-slice pair tables of hw + 1 slots, the chunk's flags, the link list
+    unsigned long long* lkeys;
+    unsigned* lcnt;
+    unsigned char* cont;
+    LesionLink* list;
+    unsigned* n_list;
     size_t bytes;
 };
 
-static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap) {
+static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap, size_t links_per_slice = 0) {
     const size_t n = nb * hw;
     LesionWs w;
     char* p = (char*)base;
@@ -952,6 +1045,14 @@ static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap) {
     w.thr = (float*)take(4);
     w.acc = (LesionAcc*)take(nb * cap * sizeof(LesionAcc));
     w.mask = (uint32_t*)take((n + 3) / 4 * 4);
+    w.lkeys = nullptr, w.lcnt = nullptr, w.cont = nullptr, w.list = nullptr, w.n_list = nullptr;
+    if (links_per_slice) {
+        w.lkeys = (unsigned long long*)take(nb * (hw + 1) * 8);
+        w.lcnt = (unsigned*)take(nb * (hw + 1) * 4);
+        w.cont = (unsigned char*)take(nb);
+        w.list = (LesionLink*)take(nb * links_per_slice * sizeof(LesionLink));
+        w.n_list = (unsigned*)take(4);
+    }
     w.bytes = off;
     return w;
 }
@@ -975,29 +1076,49 @@ int lesion_check(LesionArgs& a, int h, int w) {
     return DNNCA_OK;
 }
 
-int lesion_table(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows, int64_t* n_rows,
-                 int32_t* totals, uint8_t* mask, bool want_mask) {
+struct LesionLinkIO {                    // what a linked call adds to the chunk loop (host pointers)
+    const uint8_t* continues;
+    dnnca_lesion_link* links;
+    int64_t* n_links;
+};
+
+// the chunk loop of lesion_table and lesion_table_linked (link != nullptr: the three link launches behind every chunk's table)
+static int lesion_run(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows, int64_t* n_rows,
+                      int32_t* totals, uint8_t* mask, bool want_mask, const LesionLinkIO* link) {
     DN_TRY(region_state(M));
     RegionState& R = *M->region;
     R.lesion_rf = a.rf;
     R.lesion_k = a.k;
     R.lesion_mask = want_mask;
     const int oh = a.oh, ow = a.ow;
-    const size_t hw = (size_t)oh * ow, cap = (size_t)a.cap;
+    const size_t hw = (size_t)oh * ow, cap = (size_t)a.cap, slots = hw + 1;
+    const size_t per_slice = link ? (size_t)a.links_per_slice() : 0;
     const int chunk = (int)region_chunk(1, hw, batch);
-    if (!M->dry) DN_TRY(region_ws_reserve(R, lesion_layout(nullptr, chunk, hw, cap).bytes));
+    if (!M->dry) DN_TRY(region_ws_reserve(R, lesion_layout(nullptr, chunk, hw, cap, per_slice).bytes));
+    if (link && !M->dry) {               // from here on the carry is this call's: valid again once every chunk has gone through
+        R.carry_valid = false;
+        if (hw > R.carry_n) {            // (a set continues[0] was checked against a carry of this size: that one is never regrown)
+            if (R.carry) HIP_TRY(hipFree(R.carry));
+            R.carry = nullptr;
+            R.carry_n = 0;
+            HIP_TRY(hipMalloc((void**)&R.carry, hw * 4));
+            R.carry_n = hw;
+        }
+    }
     hipStream_t s = M->stream;
     std::vector<LesionAcc> acc;
     std::vector<int> tot;
     std::vector<size_t> first;
-    int64_t out = 0;
+    std::vector<LesionLink> found;
+    int64_t out = 0, out_links = 0;
     Resize rz{h, w, oh, ow, (float)h / (float)oh, (float)w / (float)ow, (oh == h && ow == w) ? 1 : 0};
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
         const size_t n = (size_t)nb * hw;
-        const LesionWs ws = lesion_layout(R.ws, nb, hw, cap);
+        const LesionWs ws = lesion_layout(R.ws, nb, hw, cap, per_slice);
         const float* pb = prob + (size_t)b0 * h * w;
         if (!M->dry) HIP_TRY(hipMemcpyAsync(ws.thr, &a.threshold, 4, hipMemcpyHostToDevice, s));   // `a` outlives the chunk's sync
+        if (link && !M->dry) HIP_TRY(hipMemcpyAsync(ws.cont, link->continues + b0, (size_t)nb, hipMemcpyHostToDevice, s));
         LAUNCH(M, "region_prep", n * 4.0 + (double)nb * h * w * 4, 0,
                hipLaunchKernelGGL(k_region_prep, dim3(nblocks(n)), dim3(RB), 0, s, pb, rz, nb, (const float*)ws.thr, 1, ws.w0));
         const uint32_t* fg = ws.w0;
@@ -1020,12 +1141,40 @@ int lesion_table(Model* M, const float* prob, int batch, int h, int w, const Les
         if (want_mask)
             LAUNCH(M, "lesion_mask", n * 9.0, 0,
                    hipLaunchKernelGGL(k_lesion_mask, dim3(nblocks((n + 3) / 4)), dim3(RB), 0, s, ws.lp, ws.row, n, ws.mask));
+        if (link) {                      // on every chunk, whatever the flags say: they are device data
+            const size_t total = (size_t)nb * slots, list_cap = (size_t)nb * per_slice;
+            if (!M->dry) {
+                HIP_TRY(hipMemsetAsync(ws.lkeys, 0xff, total * 8, s));
+                HIP_TRY(hipMemsetAsync(ws.lcnt, 0, total * 4, s));
+                HIP_TRY(hipMemsetAsync(ws.n_list, 0, 4, s));
+            }
+            LAUNCH(M, "lesion_link", n * 16.0 + (double)nb, 0,
+                   hipLaunchKernelGGL(k_lesion_link, dim3(nblocks(n)), dim3(RB), 0, s, ws.lp, ws.row, (const int*)R.carry, ws.cont, nb, hw,
+                                      (int)cap, slots, ws.lkeys, ws.lcnt));
+            LAUNCH(M, "lesion_link_emit", total * 12.0, 0,
+                   hipLaunchKernelGGL(k_lesion_link_emit, dim3(nblocks(total)), dim3(RB), 0, s, ws.lkeys, ws.lcnt, total, slots, b0,
+                                      (unsigned)list_cap, ws.list, ws.n_list));
+            // after lesion_link on the same stream: the link kernel of this chunk has read the carry of the chunk before
+            LAUNCH(M, "lesion_carry", hw * 12.0, 0,
+                   hipLaunchKernelGGL(k_lesion_carry, dim3(nblocks(hw)), dim3(RB), 0, s, ws.lp, ws.row, (size_t)(nb - 1) * hw, hw, (int)cap,
+                                      R.carry));
+        }
         if (M->dry) continue;
         HIP_TRY(hipGetLastError());
         tot.resize(nb);
+        unsigned n_found = 0;
         HIP_TRY(hipMemcpyAsync(tot.data(), ws.tot, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
         if (mask) HIP_TRY(hipMemcpyAsync(mask + (size_t)b0 * hw, ws.mask, n, hipMemcpyDeviceToHost, s));
+        if (link) HIP_TRY(hipMemcpyAsync(&n_found, ws.n_list, 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
+        if (link) {                      // only the counted links come back; their order is the atomics': sorted here
+            if ((size_t)n_found > (size_t)nb * per_slice) {
+                set_error("lesion table: %u links in %d slices exceed the bound of %zu per slice", n_found, nb, per_slice);
+                return DNNCA_ESTATE;
+            }
+            found.resize(n_found);
+            if (n_found) HIP_TRY(hipMemcpyAsync(found.data(), ws.list, (size_t)n_found * sizeof(LesionLink), hipMemcpyDeviceToHost, s));
+        }
         first.assign(nb + 1, 0);         // only the rows a slice filled come back
         for (int b = 0; b < nb; ++b) first[b + 1] = first[b] + std::min<size_t>((size_t)std::max(tot[b], 0), cap);
         acc.resize(first[nb]);
@@ -1052,9 +1201,37 @@ int lesion_table(Model* M, const float* prob, int batch, int h, int w, const Les
                 o.sum_prob_q24 = v.sq;
             }
         }
+        if (link) {
+            std::sort(found.begin(), found.end(), [](const LesionLink& x, const LesionLink& y) {
+                return std::make_tuple(x.slice, x.row_prev, x.row) < std::make_tuple(y.slice, y.row_prev, y.row);
+            });
+            for (const LesionLink& v : found) link->links[out_links++] = dnnca_lesion_link{v.slice, v.row_prev, v.row, v.overlap};
+        }
     }
     if (!M->dry && n_rows) *n_rows = out;
+    if (link && !M->dry) {
+        *link->n_links = out_links;
+        R.carry_valid = true;
+        R.carry_oh = oh;
+        R.carry_ow = ow;
+    }
     return DNNCA_OK;
+}
+
+int lesion_table(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows, int64_t* n_rows,
+                 int32_t* totals, uint8_t* mask, bool want_mask) {
+    return lesion_run(M, prob, batch, h, w, a, rows, n_rows, totals, mask, want_mask, nullptr);
+}
+
+int lesion_table_linked(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows,
+                        int64_t* n_rows, int32_t* totals, uint8_t* mask, bool want_mask, const uint8_t* continues,
+                        dnnca_lesion_link* links, int64_t* n_links) {
+    const LesionLinkIO io{continues, links, n_links};
+    return lesion_run(M, prob, batch, h, w, a, rows, n_rows, totals, mask, want_mask, &io);
+}
+
+bool lesion_carry_is(Model* M, int oh, int ow) {
+    return M->region && M->region->carry_valid && M->region->carry_oh == oh && M->region->carry_ow == ow;
 }
 
 void lesion_last(Model* M, float* rf, int* k, bool* want_mask) {
@@ -1068,7 +1245,7 @@ void lesion_last(Model* M, float* rf, int* k, bool* want_mask) {
 void region_release(Model* M) {
     if (!M->region) return;
     RegionState& R = *M->region;
-    for (void* p : {(void*)R.thr_dev, (void*)R.acc, R.ws, (void*)R.in_prob, (void*)R.in_y, (void*)R.slice_acc, (void*)R.viz})
+    for (void* p : {(void*)R.thr_dev, (void*)R.acc, R.ws, (void*)R.in_prob, (void*)R.in_y, (void*)R.slice_acc, (void*)R.viz, (void*)R.carry})
         if (p) (void)hipFree(p);
     delete M->region;
     M->region = nullptr;

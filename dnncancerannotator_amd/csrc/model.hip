@@ -1949,9 +1949,11 @@ int dnnca_render_composite(void* model, const float* y_hw, int batch, float rati
 }
 
 // ---- `annotator predict`: the lesion table (kernels_region.hip) ---------------------------------------------------------------
-int dnnca_lesion_table(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
-                       int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
-                       int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw) {
+// dnnca_lesion_table (link == false; the last four arguments are not looked at) and dnnca_lesion_table_linked
+static int lesion_call(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor, int filter_size,
+                       int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity, int64_t* n_rows, int32_t* totals,
+                       uint8_t* mask, int64_t mask_capacity, int32_t* out_hw, bool link, const uint8_t* continues,
+                       dnnca_lesion_link* links, int64_t links_capacity, int64_t* n_links) {
     MODEL(model);
     DN_TRY(check_batch(M, batch));
     if (!prob_hw) {
@@ -1983,6 +1985,18 @@ int dnnca_lesion_table(void* model, const float* prob_hw, int batch, int h, int 
         set_error("lesion table: mask of %lld bytes needed, capacity %lld", (long long)batch * a.oh * a.ow, (long long)mask_capacity);
         return DNNCA_EINVAL;
     }
+    if (link) {
+        if (!continues) { set_error("lesion table: null continues"); return DNNCA_EINVAL; }
+        if (!links || !n_links || links_capacity < (int64_t)batch * a.links_per_slice()) {
+            set_error("lesion table: %lld links needed (%d slices x %lld), capacity %lld", (long long)batch * a.links_per_slice(), batch,
+                      (long long)a.links_per_slice(), links && n_links ? (long long)links_capacity : 0ll);
+            return DNNCA_EINVAL;
+        }
+        if (continues[0] && !lesion_carry_is(M, a.oh, a.ow)) {
+            set_error("lesion table: continues[0] is set, but no linked call on planes of %d x %d precedes this one", a.oh, a.ow);
+            return DNNCA_EINVAL;
+        }
+    }
     const float* p_dev = M->prob;
     if (prob_hw) {
         const size_t n = (size_t)batch * h * w;
@@ -1991,7 +2005,23 @@ int dnnca_lesion_table(void* model, const float* prob_hw, int batch, int h, int 
         HIP_TRY(hipMemcpyAsync(pd, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
         p_dev = pd;
     }
+    if (link) return lesion_table_linked(M, p_dev, batch, h, w, a, rows, n_rows, totals, mask, mask != nullptr, continues, links, n_links);
     return lesion_table(M, p_dev, batch, h, w, a, rows, n_rows, totals, mask, mask != nullptr);
+}
+
+int dnnca_lesion_table(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
+                       int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
+                       int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw) {
+    return lesion_call(model, prob_hw, batch, h, w, threshold, resize_factor, filter_size, min_area, max_lesions, rows, rows_capacity,
+                       n_rows, totals, mask, mask_capacity, out_hw, false, nullptr, nullptr, 0, nullptr);
+}
+
+int dnnca_lesion_table_linked(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
+                              int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
+                              int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw,
+                              const uint8_t* continues, dnnca_lesion_link* links, int64_t links_capacity, int64_t* n_links) {
+    return lesion_call(model, prob_hw, batch, h, w, threshold, resize_factor, filter_size, min_area, max_lesions, rows, rows_capacity,
+                       n_rows, totals, mask, mask_capacity, out_hw, true, continues, links, links_capacity, n_links);
 }
 
 int dnnca_eval_region_begin(void* model, const dnnca_region_spec* specs, int n) {
@@ -2197,7 +2227,7 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
     MODEL(model);
     if (!buf || !cap) return DNNCA_EINVAL;
     if (pass != DNNCA_PLAN_TRAIN && pass != DNNCA_PLAN_EVAL && pass != DNNCA_PLAN_FORWARD && pass != DNNCA_PLAN_SENSITIVITY &&
-        pass != DNNCA_PLAN_LESION) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
+        pass != DNNCA_PLAN_LESION && pass != DNNCA_PLAN_LESION_LINKED) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
     DN_TRY(check_batch(M, batch));
     M->plan_text.clear();
     M->dry = true;
@@ -2220,12 +2250,16 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
         if (rc == DNNCA_OK) rc = M->loss_and_backward(M->y_stage, B, cfg, false);
     } else if (pass == DNNCA_PLAN_SENSITIVITY) {
         rc = M->input_sensitivity(M->x_stage, B);
-    } else if (pass == DNNCA_PLAN_LESION) {
+    } else if (pass == DNNCA_PLAN_LESION || pass == DNNCA_PLAN_LESION_LINKED) {
         LesionArgs a;
         bool want_mask = true;
         lesion_last(M, &a.rf, &a.k, &want_mask);
         rc = lesion_check(a, M->outH, M->outW);
-        if (rc == DNNCA_OK) rc = lesion_table(M, M->prob, B, M->outH, M->outW, a, nullptr, nullptr, nullptr, nullptr, want_mask);
+        if (rc == DNNCA_OK && pass == DNNCA_PLAN_LESION)
+            rc = lesion_table(M, M->prob, B, M->outH, M->outW, a, nullptr, nullptr, nullptr, nullptr, want_mask);
+        else if (rc == DNNCA_OK)
+            rc = lesion_table_linked(M, M->prob, B, M->outH, M->outW, a, nullptr, nullptr, nullptr, nullptr, want_mask, nullptr, nullptr,
+                                     nullptr);
     } else {
         rc = dnnca_forward_dev(model, M->x_stage, B, 0);
     }

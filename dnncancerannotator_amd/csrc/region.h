@@ -1,6 +1,8 @@
 // region.h -- region-based (lesion-level) metrics on the device (kernels_region.hip): the host side of the pipeline that the C ABI
 // of model.hip drives (dnnca_region_confusion*, dnnca_eval_region_*).
 #pragma once
+#include <algorithm>
+
 #include "model.h"
 
 namespace dnnca {
@@ -45,6 +47,8 @@ struct LesionArgs {
     float threshold = 0.5f, rf = 1.f;
     int k = 5, min_area = 0, max_lesions = 256;
     int oh = 0, ow = 0, cap = 0;         // filled by lesion_check: the analysed plane, rows per slice min(max_lesions, (oh ow + 1) / 2)
+    // links into one slice: distinct (row_prev, row) pairs, at most cap^2 and at most ceil(oh ow / 2) (kernels_region.hip, lesion_link)
+    int64_t links_per_slice() const { return std::min<int64_t>((int64_t)cap * cap, ((int64_t)oh * ow + 1) / 2); }
 };
 // checks the caller's arguments against slices of h x w and fills oh / ow / cap; DNNCA_EINVAL with the reason otherwise
 int lesion_check(LesionArgs& a, int h, int w);
@@ -53,7 +57,18 @@ int lesion_check(LesionArgs& a, int h, int w);
 // run (M->dry) the host outputs are not touched and want_mask stands for `mask != nullptr`
 int lesion_table(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows, int64_t* n_rows,
                  int32_t* totals, uint8_t* mask, bool want_mask);
-// resize factor, filter size and mask choice of the last lesion_table (DNNCA_PLAN_LESION); the defaults before any
+// lesion_table plus the overlap links between neighbouring slices (dnnca_lesion_table_linked): the same chunk loop with the same
+// launches, then lesion_link / lesion_link_emit / lesion_carry per chunk.  continues (host [batch]): slice b follows slice b - 1 of
+// its exam; the predecessor of a chunk's first slice is the carry plane, i.e. the last slice of the chunk or of the linked call
+// before.  links (host, batch * a.links_per_slice() entries at least) receives *n_links links sorted by (slice, row_prev, row).  The caller
+// has checked lesion_carry_is(M, a.oh, a.ow) where continues[0] is set.  In a dry run continues / links / n_links are not read
+int lesion_table_linked(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows,
+                        int64_t* n_rows, int32_t* totals, uint8_t* mask, bool want_mask, const uint8_t* continues,
+                        dnnca_lesion_link* links, int64_t* n_links);
+// the carry plane holds the rows of the last slice of a successful lesion_table_linked on planes of oh x ow
+bool lesion_carry_is(Model* M, int oh, int ow);
+// resize factor, filter size and mask choice of the last lesion_table / lesion_table_linked (DNNCA_PLAN_LESION,
+// DNNCA_PLAN_LESION_LINKED); the defaults before any
 void lesion_last(Model* M, float* rf, int* k, bool* want_mask);
 void region_release(Model* M);
 

@@ -498,6 +498,22 @@ class DeviceModel:
         row, area, x0, y0, x1, y1 inclusive, max_prob, sum_x, sum_y, sum_prob_q24), slice after slice, at most max_lesions per
         slice; totals int32 [B]: the kept components of every slice (> max_lesions: its rows are truncated); masks uint8
         [B, oh, ow], 255 on every kept component (None with mask=False).  Exact integers: bit-identical from run to run."""
+        return self._lesion_call(batch, prob, None, threshold, resize_factor, filter_size, min_area, max_lesions, mask)
+
+    def lesion_table_linked(self, batch=None, prob=None, continues=None, threshold=0.5, resize_factor=1.0, filter_size=5, min_area=0,
+                            max_lesions=256, mask=True):
+        """lesion_table plus the links between neighbouring slices: (rows, totals, masks, links); the first three are what
+        lesion_table returns.  continues [B] (bool): slice b is the next slice of the exam of slice b - 1; continues[0] refers to the
+        last slice of the previous lesion_table_linked call on this model (an error when there was none, or one on planes of
+        another size).  links: structured array (_lib.LESION_LINK_DTYPE: slice, row_prev, row, overlap), one entry per pair of a
+        lesion of slice - 1 (row_prev) and a lesion of slice (row) that share `overlap` pixels, sorted by (slice, row_prev, row);
+        lesions beyond max_lesions link to nothing."""
+        if continues is None:
+            raise ValueError('lesion_table_linked needs `continues`, one flag per slice')
+        return self._lesion_call(batch, prob, continues, threshold, resize_factor, filter_size, min_area, max_lesions, mask)
+
+    def _lesion_call(self, batch, prob, continues, threshold, resize_factor, filter_size, min_area, max_lesions, mask):
+        """dnnca_lesion_table, or with `continues` dnnca_lesion_table_linked: the size query, then the call on buffers of that size"""
         pp, h, w = None, 0, 0
         if prob is not None:
             prob = as_f32(prob)
@@ -516,15 +532,26 @@ class DeviceModel:
         hw = (C.c_int32 * 2)()
         check(self.lib.dnnca_lesion_table(*args, None, 0, None, None, None, 0, hw))
         oh, ow = hw[0], hw[1]
-        cap = B * min(int(max_lesions), (oh * ow + 1) // 2)
+        per_slice = min(int(max_lesions), (oh * ow + 1) // 2)
+        cap = B * per_slice
         rows = np.zeros(cap, _lib.LESION_ROW_DTYPE)
         totals = np.zeros(B, np.int32)
         masks = np.empty((B, oh, ow), np.uint8) if mask else None
         n = C.c_int64()
-        check(self.lib.dnnca_lesion_table(*args, rows.ctypes.data_as(C.POINTER(_lib.LesionRow)), cap, C.byref(n),
-                                          totals.ctypes.data_as(C.POINTER(C.c_int32)),
-                                          masks.ctypes.data_as(C.c_void_p) if mask else None, masks.nbytes if mask else 0, hw))
-        return rows[:n.value].copy(), totals, masks
+        out = (rows.ctypes.data_as(C.POINTER(_lib.LesionRow)), cap, C.byref(n), totals.ctypes.data_as(C.POINTER(C.c_int32)),
+               masks.ctypes.data_as(C.c_void_p) if mask else None, masks.nbytes if mask else 0, hw)
+        if continues is None:
+            check(self.lib.dnnca_lesion_table(*args, *out))
+            return rows[:n.value].copy(), totals, masks
+        flags = np.ascontiguousarray(np.asarray(continues).astype(bool), np.uint8)
+        if flags.shape != (B,):
+            raise ValueError('continues must hold one flag per slice (%d), got shape %s' % (B, flags.shape))
+        lcap = B * min(per_slice * per_slice, (oh * ow + 1) // 2)
+        links = np.zeros(lcap, _lib.LESION_LINK_DTYPE)
+        nl = C.c_int64()
+        check(self.lib.dnnca_lesion_table_linked(*args, *out, flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                 links.ctypes.data_as(C.POINTER(_lib.LesionLink)), lcap, C.byref(nl)))
+        return rows[:n.value].copy(), totals, masks, links[:nl.value].copy()
 
     def input_sensitivity(self, x=None, batch=None):
         """float64 [B, C]: sum over the image of |d sum(prob of slice b) / d x[b, :, :, c]| in inference mode (the raw sums of the
@@ -669,13 +696,13 @@ class DeviceModel:
             out.append((name.value.decode(), n.value, ms.value, by.value, fl.value))
         return out
 
-    PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3, 'lesion': 4}
+    PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3, 'lesion': 4, 'lesion_linked': 5}
 
     def plan(self, variants=False, mode='train', batch=None):
         """The launch schedule of one pass: [(kernel, algorithmic bytes, flops)].  mode 'train': one train step; 'eval': one
         eval_step (inference forward + loss; a staged evaluation step launches the same); 'forward': forward(training=False);
         'sensitivity': input_sensitivity; 'lesion': lesion_table on the last forward's probabilities, with the resize factor,
-        filter size and mask choice of the last lesion_table call.
+        filter size and mask choice of the last lesion_table / lesion_table_linked call; 'lesion_linked': lesion_table_linked likewise.
         batch: None = max_batch.  variants: keep the template variant the library appends to a launch name
         (`ig_conv_fwd#3n2w8`): the kernel-coverage test tells them apart.  A dry run: the model is unchanged."""
         if mode not in self.PLAN_PASSES:

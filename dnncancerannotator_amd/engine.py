@@ -650,14 +650,20 @@ class TFKerasModel:
         return np.concatenate(outs) if outs else np.zeros((0,))
 
     def annotate(self, dataset, save_path, output, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
-                 max_lesions=256, export_images=False):
+                 max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1):
         """`annotator predict`: the lesions of slices that have no label.  Loads checkpoint `step` of save_path (None: the latest);
         per batch (x, paths, sliceIDs) of `dataset` (make_dataset(..., include_meta=True, labels=False)) one forward whose
         probabilities stay on the device, then DeviceModel.lesion_table: threshold, filter_size x filter_size opening, components
         of at least min_area pixels -- only the table and the uint8 masks come back.  Files under `output`: lesions.csv (one line
         per lesion, dataset order then row order), slices.csv (one line per slice; truncated = 1: more than max_lesions
         components, lesions.csv holds the first max_lesions) and, with export_images, <exam>/<slice>/mask.png (the opened,
-        area-filtered mask).  Returns {'step', 'slices', 'lesions'}."""
+        area-filtered mask).  Returns {'step', 'slices', 'lesions'}.
+        link_slices: DeviceModel.lesion_table_linked instead, which also counts the common pixels of the lesions of neighbouring
+        slices.  A slice continues the one before it when it has the same exam path and the next slice number -- across max_batch
+        splits and across batches of `dataset`; the first slice of the run continues nothing.  casewise.link_lesions joins lesions
+        that share at least link_min_overlap pixels into exam lesions: exam_lesions.csv (one line per exam lesion) and
+        exam_lesion_parts.csv (one line per line of lesions.csv, in its order) are written beside the other files, which are
+        what they are without the flag; the returned dict gains 'exam_lesions'."""
         if self.ctx.world > 1:
             raise RuntimeError('annotate runs in a single process (WORLD_SIZE is %d): start it without the launcher' % self.ctx.world)
         self._build(dataset)
@@ -670,6 +676,8 @@ class TFKerasModel:
             raise ValueError(f'no checkpoint of step {step} under {save_path}/checkpoints (have {sorted(ckpts)})')
         self.load(ckpts[step])
         lesion_rows, slice_rows = [], []
+        dm = None
+        linked, last = [], None          # link_slices: (exam, slice, rows, total, links into it) per slice; the slice before: (exam, slice)
         writer = casewise.Writer() if export_images else None
         try:
             for el in dataset:
@@ -677,15 +685,30 @@ class TFKerasModel:
                 if not len(x):
                     continue
                 self._ensure_capacity(len(x))
+                if link_slices and last is not None and dm is not self.device_model:
+                    # the row numbers of the slice before stayed behind on the model this batch outgrew: the chain breaks here
+                    logging.warning('predict: the model was re-sized before slice %s of %s: it is not linked to the slice before', ids[0], paths[0])
+                    last = None
                 dm = self.device_model
                 for i in range(0, len(x), dm.max_batch):
                     xb = x[i:i + dm.max_batch]
                     dm.forward(xb, training=False, return_prob=False)
-                    rows, totals, masks = dm.lesion_table(batch=len(xb), threshold=threshold, resize_factor=resize_factor,
-                                                          filter_size=filter_size, min_area=min_area, max_lesions=max_lesions,
-                                                          mask=bool(export_images))
-                    for b, (p, k) in enumerate(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch])):
+                    pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
+                    kw = dict(batch=len(xb), threshold=threshold, resize_factor=resize_factor, filter_size=filter_size,
+                              min_area=min_area, max_lesions=max_lesions, mask=bool(export_images))
+                    if link_slices:
+                        continues = []
+                        for p, k in pk:
+                            continues.append(last is not None and p == last[0] and int(k) == last[1] + 1)
+                            last = (p, int(k))
+                        rows, totals, masks, links = dm.lesion_table_linked(continues=continues, **kw)
+                    else:
+                        rows, totals, masks = dm.lesion_table(**kw)
+                    for b, (p, k) in enumerate(pk):
                         mine = rows[rows['slice'] == b]
+                        if link_slices:
+                            into = links[links['slice'] == b]
+                            linked.append((p, int(k), mine, totals[b], [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in into]))
                         lesion_rows += [casewise.lesion_values(p, k, r) for r in mine]
                         slice_rows.append(casewise.slice_values(p, k, mine, totals[b]))
                         if export_images:
@@ -694,10 +717,27 @@ class TFKerasModel:
             if writer is not None:
                 writer.close()
         os.makedirs(output, exist_ok=True)
-        for name, cols, table in (('lesions.csv', casewise.LESION_COLUMNS, lesion_rows), ('slices.csv', casewise.SLICE_COLUMNS, slice_rows)):
+        tables = [('lesions.csv', casewise.LESION_COLUMNS, lesion_rows), ('slices.csv', casewise.SLICE_COLUMNS, slice_rows)]
+        res = dict(step=int(step), slices=len(slice_rows), lesions=len(lesion_rows))
+        if link_slices:
+            exams = {}                   # exam path -> the positions of its slices in `linked`, in the order of the data set
+            for pos, rec in enumerate(linked):
+                exams.setdefault(rec[0], []).append(pos)
+            exam_rows, parts_of = [], [None] * len(linked)
+            for exam, where in exams.items():
+                table, parts = casewise.link_lesions(exam, [linked[pos][1:4] for pos in where], [linked[pos][4] for pos in where],
+                                                     min_overlap=link_min_overlap)
+                exam_rows += table
+                for pos in where:        # the parts come slice after slice; lesions.csv is in the order of the data set
+                    n = len(linked[pos][2])
+                    parts_of[pos], parts = parts[:n], parts[n:]
+            tables += [('exam_lesions.csv', casewise.EXAM_LESION_COLUMNS, exam_rows),
+                       ('exam_lesion_parts.csv', casewise.EXAM_PART_COLUMNS, sum(parts_of, []))]
+            res['exam_lesions'] = len(exam_rows)
+        for name, cols, table in tables:
             with open(os.path.join(output, name), 'w', newline='') as f:
                 f.write(casewise.plain_csv(cols, table))
-        return dict(step=int(step), slices=len(slice_rows), lesions=len(lesion_rows))
+        return res
 
     def get_config(self):
         return self.model_config

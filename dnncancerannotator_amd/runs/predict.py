@@ -1,5 +1,6 @@
 """`annotator predict` -- the reference left annotator/runs/predict.py empty: annotate slices that have no label with a trained
-checkpoint (lesions.csv, slices.csv and, with --export_images, one mask.png per slice; engine.TFKerasModel.annotate)."""
+checkpoint (lesions.csv, slices.csv and, with --export_images, one mask.png per slice; with --link_slices also exam_lesions.csv and
+exam_lesion_parts.csv: the lesions joined through the slices of an exam; engine.TFKerasModel.annotate)."""
 
 import os
 
@@ -8,11 +9,13 @@ from .train import make_dataset
 
 
 def predict(save_path, data_path, output, config=None, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
-            max_lesions=256, export_images=False):
+            max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1):
+    if link_min_overlap < 1:
+        raise ValueError('link_min_overlap must be at least 1, got %d' % link_min_overlap)
     saved_config = load.load_config(os.path.join(save_path, 'options.yaml'))['config']
     config = load._apply_config(saved_config, load.load_config(config)) if config else saved_config
     ds = make_dataset(data_path, config.get('data_options', {}).get('eval', {}), training=False, include_meta=True, labels=False)
     model = engine.TFKerasModel(config)
     return model.annotate(ds, save_path=save_path, output=output, step=step, threshold=threshold, min_area=min_area,
                           filter_size=filter_size, resize_factor=resize_factor, max_lesions=max_lesions,
-                          export_images=export_images)
+                          export_images=export_images, link_slices=link_slices, link_min_overlap=link_min_overlap)

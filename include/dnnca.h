@@ -318,6 +318,24 @@ int dnnca_lesion_table(void* model, const float* prob_hw, int batch, int h, int 
                        int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
                        int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw);
 
+/* ---- the same table plus the links between neighbouring slices of an exam (`annotator predict --link_slices`) ------------------
+ * Every argument up to out_hw means what it means for dnnca_lesion_table (the size query with rows == NULL included), and rows,
+ * totals and mask are bit-identical to that call's.  continues [batch]: continues[b] != 0 says that slice b is the next slice of
+ * the exam of slice b - 1; for b == 0 the predecessor is the last slice of the previous successful dnnca_lesion_table_linked call
+ * on this model (its row numbers are kept on the device, whatever else the model was used for in between).  For every such slice
+ * and every pair of a lesion of the predecessor (row_prev: its number there) and a lesion of slice `slice` (row) that share
+ * pixels, links receives one entry with the number of common pixels; lesions beyond max_lesions or below min_area link to nothing.
+ * *n_links entries, sorted by (slice, row_prev, row); links_capacity must be at least batch * min(cap * cap, (oh * ow + 1) / 2)
+ * with cap = min(max_lesions, (oh * ow + 1) / 2).
+ * DNNCA_EINVAL, with nothing launched and the kept predecessor untouched: everything dnnca_lesion_table refuses, continues ==
+ * NULL, a links buffer that is too small, continues[0] set while no linked call has succeeded on this model or the last one
+ * analysed planes of another oh x ow.  Synchronises. */
+typedef struct dnnca_lesion_link { int32_t slice, row_prev, row, overlap; } dnnca_lesion_link;   /* 16 bytes */
+int dnnca_lesion_table_linked(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
+                              int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
+                              int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw,
+                              const uint8_t* continues, dnnca_lesion_link* links, int64_t links_capacity, int64_t* n_links);
+
 /* ---- channel sensitivity of `annotator evaluate --visualize_sensitivity` (utils/callbacks.py:290-313) ---------------------------
  * With the model in inference mode (BatchNorm on its moving statistics, sigmoid output):
  *     sums[b * in_channels + c] = sum over H, W of | d (sum of all probabilities of slice b) / d x[b, h, w, c] |
@@ -360,9 +378,11 @@ int dnnca_plan_dump(void* model, char* buf, size_t cap);
 /* the same for one pass at one batch size in [1, max_batch]: the train step (dnnca_plan_dump is this at max_batch), an evaluation
    step (dnnca_eval_step / dnnca_eval_step_staged: inference forward + loss), or a prediction (dnnca_forward with training = 0:
    inference forward + sigmoid), or dnnca_input_sensitivity, or dnnca_lesion_table on the last forward's probabilities with the
-   resize factor, filter size and mask choice of the last dnnca_lesion_table call (before any: 1.0, 5, with mask).  A dry run:
-   nothing is launched and the model is left as it was. */
-enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2, DNNCA_PLAN_SENSITIVITY = 3, DNNCA_PLAN_LESION = 4 };
+   resize factor, filter size and mask choice of the last dnnca_lesion_table / dnnca_lesion_table_linked call (before any: 1.0, 5,
+   with mask), or dnnca_lesion_table_linked with the same three values.  A dry run: nothing is launched and the model is left as
+   it was. */
+enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2, DNNCA_PLAN_SENSITIVITY = 3, DNNCA_PLAN_LESION = 4,
+       DNNCA_PLAN_LESION_LINKED = 5 };
 int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap);
 
 #ifdef __cplusplus

@@ -7,6 +7,12 @@ and prediction plane) plus pairs, match and count.
 
     python tools/lesion_rate.py [--batch 8] [--size 512] [--reps 20] [--out profiles/lesion_rate.txt]
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --yardstick      # the yardstick alone
+    python tools/lesion_rate.py --link              # also: lesion_table_linked, annotate(link_slices=True), the pair table's worst case
+    DNNCA_LIB=<a library from before the links> python tools/lesion_rate.py                         # the unlinked legs on it
+
+--link adds the cost of linking neighbouring slices: lesion_table_linked against lesion_table (wall time per call, device time of
+the three link launches), its worst case for the pair table (a checkerboard on itself: every other pixel a lesion of its own in
+both slices, (hw + 1) / 2 keys per slice) and `annotate` with link_slices.
 
 The probabilities are drawn: the synthetic labels' discs at 0.55 .. 0.95 on a background of 0 .. 0.45 (a few lesions per slice,
 as a trained model gives), put into the model's probability buffer by pixel_confusion_of."""
@@ -26,10 +32,13 @@ ap.add_argument('--size', type=int, default=512)
 ap.add_argument('--reps', type=int, default=20)
 ap.add_argument('--batches', type=int, default=8)
 ap.add_argument('--yardstick', action='store_true', help='region_confusion_slices alone (also on a library without the lesion table)')
+ap.add_argument('--link', action='store_true', help='also measure lesion_table_linked and annotate(link_slices=True)')
 ap.add_argument('--out', default=None, help='append the report to this file as well')
 a = ap.parse_args()
 if a.yardstick:
     _lib.SIGNATURES.pop('dnnca_lesion_table', None)              # a library built from the parent does not export it
+if not a.link:
+    _lib.SIGNATURES.pop('dnnca_lesion_table_linked', None)       # nor does one from before the links
 
 from dnncancerannotator_amd import device as dev                  # noqa: E402
 from dnncancerannotator_amd.data import ArrayDataset              # noqa: E402
@@ -100,6 +109,25 @@ if not a.yardstick:
     med, lo, hi = wall(lambda: dm.lesion_table(batch=B, threshold=0.5, filter_size=5))
     say('  lesion_table, every pixel one lesion: %.3f ms per call (median; %.3f .. %.3f)' % (med, lo, hi))
     per_launch(dm, lambda: dm.lesion_table(batch=B, threshold=0.5, filter_size=5), ('lesion_',))
+    if a.link:
+        dm.pixel_confusion_of(prob, y, [0.5])
+        flags = [b > 0 for b in range(B)]
+        kw = dict(batch=B, threshold=0.5, filter_size=5)
+        for mask in (True, False):
+            med, lo, hi = wall(lambda: dm.lesion_table_linked(continues=flags, mask=mask, **kw))
+            say('  lesion_table_linked(mask=%s): %.3f ms per call (median of %d; %.3f .. %.3f)' % (mask, med, R, lo, hi))
+        say('    %d links between %d slices' % (len(dm.lesion_table_linked(continues=flags, **kw)[3]), B))
+        per_launch(dm, lambda: dm.lesion_table_linked(continues=flags, **kw), ('lesion_link', 'lesion_carry'))
+        # the worst case of the pair table: a checkerboard on itself, k = 1: S S / 2 lesions per slice, as many keys per table
+        board = np.broadcast_to(((xx + yy) % 2 == 0).astype(np.float32), (B, S, S)).copy()
+        dm.pixel_confusion_of(board, y, [0.5])
+        wkw = dict(batch=B, threshold=0.5, filter_size=1, max_lesions=S * S)
+        med, lo, hi = wall(lambda: dm.lesion_table(**wkw))
+        say('  lesion_table, checkerboard (k = 1, no row limit): %.3f ms per call (median; %.3f .. %.3f)' % (med, lo, hi))
+        med, lo, hi = wall(lambda: dm.lesion_table_linked(continues=flags, **wkw))
+        say('  lesion_table_linked, checkerboard on itself: %.3f ms per call (median; %.3f .. %.3f)' % (med, lo, hi))
+        say('    %d links between %d slices' % (len(dm.lesion_table_linked(continues=flags, **wkw)[3]), B))
+        per_launch(dm, lambda: dm.lesion_table_linked(continues=flags, **wkw), ('lesion_link', 'lesion_carry'))
     for xb, _, _ in ds:
         dm.forward(xb, return_prob=False)
     t0 = time.perf_counter()
@@ -117,6 +145,17 @@ if not a.yardstick:
             dt = time.perf_counter() - t0
             say('  %-34s %9.1f slices/s  (%.2f ms per batch; %d lesions)' % ('annotate' + (' + mask.png' if images else ''),
                                                                             B * NB / dt, dt / NB * 1e3, res['lesions']))
+        if a.link:
+            rate = {}
+            for i, linked in enumerate((False, True, False, True)):
+                t0 = time.perf_counter()
+                res = e.annotate(ds, os.path.join(tmp, 'run'), os.path.join(tmp, 'link%d' % i), threshold=thr, link_slices=linked)
+                dt = time.perf_counter() - t0
+                rate[linked] = dt
+                say('  %-34s %9.1f slices/s  (%.2f ms per batch; %d lesions%s)' % (
+                    'annotate' + (' --link_slices' if linked else ''), B * NB / dt, dt / NB * 1e3, res['lesions'],
+                    ', %d exam lesions' % res['exam_lesions'] if linked else ''))
+            say('  linked / unlinked annotate (the second pass of each): %.3f' % (rate[True] / rate[False]))
 dm.close()
 if a.out:
     with open(a.out, 'a') as f:
