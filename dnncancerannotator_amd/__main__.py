@@ -44,6 +44,20 @@ def build_parser(prog='python3 -m annotator'):
     e.add_argument('--overlay', action='store_true')
     e.add_argument('--skip_visualization', action='store_true')
     e.add_argument('--export_casewise_metrics', action='store_true')
+    # absent unless given (the defaults are those of runs.evaluate.evaluate)
+    e.add_argument('--exam_lesions', action='store_true', default=argparse.SUPPRESS,
+                   help='score the lesions linked through the slices of an exam against the labelled ones: also write '
+                        'exam_lesion_results.csv, exam_lesion_cases.csv and exam_lesion_matches.csv')
+    e.add_argument('--exam_threshold', type=float, nargs='+', default=argparse.SUPPRESS, metavar='T',
+                   help='probability threshold(s) of --exam_lesions (default: 0.5)')
+    e.add_argument('--exam_iou', type=float, default=argparse.SUPPRESS, help='3-D IoU at which two tumours hit (default: 0.30)')
+    e.add_argument('--exam_min_area', type=int, default=argparse.SUPPRESS, help='smallest predicted lesion kept per slice (default: 0)')
+    e.add_argument('--exam_filter_size', type=int, default=argparse.SUPPRESS, help='opening of the prediction, 1..15 (default: 5)')
+    e.add_argument('--exam_resize_factor', type=float, default=argparse.SUPPRESS,
+                   help='analyse probabilities and labels resized by this factor (default: 1.0)')
+    e.add_argument('--exam_max_lesions', type=_at_least_one, default=argparse.SUPPRESS, help='lesions per slice and plane (default: 256)')
+    e.add_argument('--exam_link_min_overlap', type=_at_least_one, default=argparse.SUPPRESS,
+                   help='common pixels that join two lesions of neighbouring slices (default: 1)')
     p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
     p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
     p.add_argument('--data_path', nargs='+', required=True)

@@ -79,6 +79,25 @@ class LesionLink(C.Structure):                     # dnnca_lesion_link (16 bytes
 # DeviceModel.lesion_table_linked returns its links as a structured array of this dtype
 LESION_LINK_DTYPE = np.dtype([('slice', '<i4'), ('row_prev', '<i4'), ('row', '<i4'), ('overlap', '<i4')])
 
+
+
+class LesionPair(C.Structure):                     # dnnca_lesion_pair (16 bytes)
+    _fields_ = [('slice', C.c_int32), ('row_true', C.c_int32), ('row', C.c_int32), ('overlap', C.c_int32)]
+
+
+# DeviceModel.lesion_table_matched returns its pairs as a structured array of this dtype
+LESION_PAIR_DTYPE = np.dtype([('slice', '<i4'), ('row_true', '<i4'), ('row', '<i4'), ('overlap', '<i4')])
+
+
+class LesionPlaneOut(C.Structure):                 # dnnca_lesion_plane_out: buffers and capacities in, counts out
+    _fields_ = [('rows', C.POINTER(LesionRow)), ('rows_capacity', C.c_int64), ('n_rows', C.c_int64), ('totals', C.POINTER(C.c_int32)),
+                ('links', C.POINTER(LesionLink)), ('links_capacity', C.c_int64), ('n_links', C.c_int64)]
+
+
+class LesionPairsOut(C.Structure):                 # dnnca_lesion_pairs_out
+    _fields_ = [('pairs', C.POINTER(LesionPair)), ('capacity', C.c_int64), ('n_pairs', C.c_int64)]
+
+
 _FP = C.POINTER(C.c_float)
 _VP = C.c_void_p
 
@@ -149,6 +168,9 @@ SIGNATURES = {
                                             C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
                                             C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(LesionLink), C.c_int64,
                                             C.POINTER(C.c_int64)]),
+    'dnnca_lesion_table_matched': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(C.c_uint8), C.POINTER(LesionPlaneOut), _VP, C.c_int64, C.POINTER(LesionPlaneOut),
+                                             C.POINTER(LesionPairsOut), C.POINTER(C.c_int32)]),
     'dnnca_input_sensitivity': (C.c_int, [_VP, _FP, C.c_int, C.POINTER(C.c_double)]),
     'dnnca_comm_unique_id': (C.c_int, [_VP]),
     'dnnca_comm_init': (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_size_t]),

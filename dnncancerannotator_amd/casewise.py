@@ -251,6 +251,87 @@ def link_lesions(exam, slices, links, min_overlap=1):
     return table, parts
 
 
+# ---- `annotator evaluate --exam_lesions`: the predicted exam lesions of link_lesions scored against the labelled ones --------------
+EXAM_MATCH_COLUMNS = ['kind', 'exam', 'exam_lesion', 'first_slice', 'last_slice', 'n_slices', 'volume_px', 'partner', 'overlap_px', 'iou',
+                      'dice', 'hit']
+EXAM_CASE_COLUMNS = ['exam', 'true', 'predicted', 'detected', 'missed', 'matched', 'false', 'truncated']
+EXAM_RESULT_COLUMNS = ['exams', 'true', 'predicted', 'detected', 'missed', 'matched', 'false', 'recall', 'precision', 'f1',
+                       'false_per_exam']
+EXAM_IOU = 0.30                  # IoU_threshold / pr_IoU_threshold of the reference
+EXAM_EPSILON = 1e-07             # region_metrics._RegionBasedMetric's epsilon
+
+
+def match_exam_lesions(exam, true_slices, pred_slices, true_linked, pred_linked, pairs, iou=EXAM_IOU):
+    """The labelled and the predicted exam lesions of one exam held against each other: (case values, match values).
+
+    true_slices / pred_slices: [(slice_id, rows, total)] of the two planes as link_lesions takes them (the same slices in the same
+    order); true_linked / pred_linked: what link_lesions returned for them, (table, parts); pairs: one sequence per slice, the
+    (row_true, row, overlap) of lesion_table_matched.  The 3-D overlap of a labelled tumour T and a predicted tumour P is the sum
+    of `overlap` over the pairs whose row_true is a part of T and whose row is a part of P; union = volume(T) + volume(P) -
+    overlap.  T and P hit when overlap >= 1 and overlap / union >= iou (plain float division).  A labelled tumour is detected when
+    some P hits it; a predicted tumour is matched when it hits some T, else false (the two directions of the reference's
+    get_tp_fn / get_tp_fp).
+    Case values (EXAM_CASE_COLUMNS): the counts of the exam; truncated = 1 when a slice of either plane had more components than
+    rows.  Match values (EXAM_MATCH_COLUMNS): one line per tumour, the labelled ones (kind 'true') before the predicted ones, each
+    with its best partner on the other side -- the largest IoU, the smaller number on a tie; -1, 0, 0.0, 0.0 without any -- and
+    hit = 1 for detected / matched.  iou and dice (2 overlap / (volume(T) + volume(P))) are float64 quotients written with repr."""
+    if not len(true_slices) == len(pred_slices) == len(pairs):
+        raise ValueError('match_exam_lesions: %d / %d slices and %d pair lists' % (len(true_slices), len(pred_slices), len(pairs)))
+
+    def part_numbers(slices, parts):
+        """[slice][row] -> the exam lesion; the parts come one per row, slice after slice"""
+        out, at = [], 0
+        for _, rows, _ in slices:
+            out.append([int(p[3]) for p in parts[at:at + len(rows)]])
+            at += len(rows)
+        if at != len(parts):
+            raise ValueError('match_exam_lesions: %d parts for %d rows' % (len(parts), at))
+        return out
+    of_true, of_pred = part_numbers(true_slices, true_linked[1]), part_numbers(pred_slices, pred_linked[1])
+    overlap = {}                                                    # (T, P) -> common voxels
+    for i, mine in enumerate(pairs):
+        for row_true, row, n in mine:
+            if not (0 <= int(row_true) < len(of_true[i]) and 0 <= int(row) < len(of_pred[i])):
+                raise ValueError('match_exam_lesions: pair (%d, %d) of slice %d of the exam joins no rows' % (row_true, row, i))
+            key = of_true[i][int(row_true)], of_pred[i][int(row)]
+            overlap[key] = overlap.get(key, 0) + int(n)
+    vol_true, vol_pred = [int(r[6]) for r in true_linked[0]], [int(r[6]) for r in pred_linked[0]]
+    best = {'true': [None] * len(vol_true), 'predicted': [None] * len(vol_pred)}      # (iou, -partner, overlap, dice, hit)
+    hit = {'true': [0] * len(vol_true), 'predicted': [0] * len(vol_pred)}
+    for (t, q), n in sorted(overlap.items()):
+        union = vol_true[t] + vol_pred[q] - n
+        score, dice = n / union, 2 * n / (vol_true[t] + vol_pred[q])
+        hits = int(n >= 1 and score >= iou)
+        for kind, me, other in (('true', t, q), ('predicted', q, t)):
+            hit[kind][me] |= hits
+            cand = (score, -other, n, dice)
+            if n >= 1 and (best[kind][me] is None or cand[:2] > best[kind][me][:2]):
+                best[kind][me] = cand
+    lines = []
+    for kind, table in (('true', true_linked[0]), ('predicted', pred_linked[0])):
+        for e, r in enumerate(table):
+            b = best[kind][e]
+            lines.append([kind, exam, int(r[1]), int(r[2]), int(r[3]), int(r[4]), int(r[6])] +
+                         ([-1, 0, repr(0.0), repr(0.0)] if b is None else [-b[1], b[2], repr(b[0]), repr(b[3])]) + [hit[kind][e]])
+    detected, matched = sum(hit['true']), sum(hit['predicted'])
+    truncated = int(any(int(total) > len(rows) for sl in (true_slices, pred_slices) for _, rows, total in sl))
+    case = [exam, len(vol_true), len(vol_pred), detected, len(vol_true) - detected, matched, len(vol_pred) - matched, truncated]
+    return case, lines
+
+
+def exam_match_summary(cases):
+    """the EXAM_CASE_COLUMNS values of every exam -> the EXAM_RESULT_COLUMNS values: the summed counts, recall = detected / true and
+    precision = matched / predicted as region_metrics writes region/recall and region/precision (float32 count / (float32 sum +
+    epsilon)), F1 = 2 P R / (P + R + epsilon) likewise, false_per_exam = false / exams (0.0 without exams)"""
+    f32 = np.float32
+    n = [sum(int(c[i]) for c in cases) for i in range(1, 7)]        # true, predicted, detected, missed, matched, false
+    recall = f32(n[2]) / (f32(n[2] + n[3]) + f32(EXAM_EPSILON))
+    precision = f32(n[4]) / (f32(n[4] + n[5]) + f32(EXAM_EPSILON))
+    f1 = f32(2) * precision * recall / (precision + recall + f32(EXAM_EPSILON))
+    return [len(cases)] + n + [repr(float(recall)), repr(float(precision)), repr(float(f1)),
+                               repr(n[5] / len(cases) if cases else 0.0)]
+
+
 def plain_csv(names, rows):
     """a header line and one line per row, csv-module quoting, no index column"""
     return _csv([list(names)] + [list(r) for r in rows])

@@ -618,21 +618,25 @@ struct LesionLink {                      // dnnca_lesion_link
 static_assert(sizeof(LesionLink) == sizeof(dnnca_lesion_link), "the device list is copied into the caller's records");
 
 // one thread per slot of the chunk's tables: a filled slot appends its link to the list (in the order of the atomics: the host
-// sorts).  One atomic per wave: its filled slots take consecutive places
+// sorts).  One atomic per wave: its filled slots take consecutive places.  Grid y = 1 serves the linked call's one set of tables;
+// the matched call's three sets (`total` slots each, one behind the other) go through one launch with grid y = 3: set y fills
+// the list at list + y * list_cap and counts in n_list[y].  A wave lies in one set
 __global__ __launch_bounds__(RB) void k_lesion_link_emit(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ cnt,
                                                          size_t total, size_t slots, int slice0, unsigned list_cap,
                                                          LesionLink* __restrict__ list, unsigned* __restrict__ n_list) {
-    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x;
-    const unsigned long long key = i < total ? keys[i] : kEmpty;
+    const size_t i = (size_t)blockIdx.x * RB + threadIdx.x, at0 = (size_t)blockIdx.y * total;
+    const unsigned long long key = i < total ? keys[at0 + i] : kEmpty;
     const bool has = key != kEmpty;
     const unsigned long long bal = __ballot(has);
     if (!bal) return;
     const int lane = threadIdx.x & 63, leader = __ffsll((long long)bal) - 1;
     unsigned base = 0;
-    if (lane == leader) base = atomicAdd(n_list, (unsigned)__popcll(bal));
+    if (lane == leader) base = atomicAdd(n_list + blockIdx.y, (unsigned)__popcll(bal));
     base = __shfl(base, leader);
     const unsigned at = base + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
-    if (has && at < list_cap) list[at] = LesionLink{slice0 + (int)(i / slots), (int)(key >> 32), (int)(key & 0xffffffffu), (int)cnt[i]};
+    if (has && at < list_cap)
+        list[(size_t)blockIdx.y * list_cap + at] =
+            LesionLink{slice0 + (int)(i / slots), (int)(key >> 32), (int)(key & 0xffffffffu), (int)cnt[at0 + i]};
 }
 
 // the carry plane: the lesion (or -1) of every pixel of the chunk's last slice (L / row of that slice's first pixel at g0)
@@ -640,6 +644,67 @@ __global__ __launch_bounds__(RB) void k_lesion_carry(const int* __restrict__ L, 
                                                      int* __restrict__ carry) {
     const size_t p = (size_t)blockIdx.x * RB + threadIdx.x;
     if (p < hw) carry[p] = lesion_row_at(L, row, g0 + p, cap);
+}
+
+// ---- the matched call (dnnca_lesion_table_matched): the prediction plane (L / row) and the label plane (LT / rowT) of the same
+// slices, each numbered by lesion_scan.  One pass over the pixels fills three sets of per-slice tables, `set` slots apart:
+//   0  links of the prediction plane   key (prev << 32 | cur)        exactly what k_lesion_link counts
+//   1  links of the label plane        key (prev_true << 32 | cur_true)
+//   2  pairs of the slice itself       key (cur_true << 32 | cur)    whatever the slice's flag says
+// A pixel reads its two rows once and, where the slice's flag is set, the two rows of the same pixel of the slice before: slice
+// b - 1 of the chunk, or for b = 0 the two carry planes of the matched call.  Up to three wave-grouped table_adds per pixel.
+// The bound of the pairs is the links' (above k_lesion_link), with the label map in the place of the slice before: take one
+// witness pixel per pair (row_true, row); two 4-adjacent pixels that both lie in lesions of both maps lie in the same labelled
+// lesion and in the same predicted lesion, i.e. in the same pair, so witnesses of different pairs are never 4-adjacent: they are
+// an independent set of the hw-pixel grid, at most ceil(hw / 2) members.  Every table has hw + 1 slots: load below one half.
+__global__ __launch_bounds__(RB) void k_lesion_match(const int* __restrict__ L, const int* __restrict__ row, const int* __restrict__ LT,
+                                                     const int* __restrict__ rowT, const int* __restrict__ carry,
+                                                     const int* __restrict__ carryT, const unsigned char* __restrict__ cont, int nb,
+                                                     size_t hw, int cap, size_t slots, unsigned long long* __restrict__ keys,
+                                                     unsigned* __restrict__ cnt) {
+    const size_t g = (size_t)blockIdx.x * RB + threadIdx.x;
+    bool on_link = false, on_true = false, on_pair = false;
+    unsigned long long key_link = 0, key_true = 0, key_pair = 0;
+    size_t b = 0;
+    if (g < (size_t)nb * hw) {
+        b = g / hw;
+        const int cur = lesion_row_at(L, row, g, cap), curT = lesion_row_at(LT, rowT, g, cap);
+        if (cur >= 0 && curT >= 0) {
+            on_pair = true;
+            key_pair = ((unsigned long long)(unsigned)curT << 32) | (unsigned)cur;
+        }
+        if (cont[b] && (cur >= 0 || curT >= 0)) {
+            const size_t p = g - b * hw;
+            if (cur >= 0) {
+                const int prev = b > 0 ? lesion_row_at(L, row, g - hw, cap) : carry[p];
+                if (prev >= 0 && prev < cap) {
+                    on_link = true;
+                    key_link = ((unsigned long long)(unsigned)prev << 32) | (unsigned)cur;
+                }
+            }
+            if (curT >= 0) {
+                const int prevT = b > 0 ? lesion_row_at(LT, rowT, g - hw, cap) : carryT[p];
+                if (prevT >= 0 && prevT < cap) {
+                    on_true = true;
+                    key_true = ((unsigned long long)(unsigned)prevT << 32) | (unsigned)curT;
+                }
+            }
+        }
+    }
+    auto add = [&](size_t tb, unsigned long long key0, unsigned c) { table_add(keys + tb * slots, cnt + tb * slots, slots, key0, c); };
+    wave_grouped_at(on_link, b, key_link, add);                       // table b of set s is table s * nb + b
+    wave_grouped_at(on_true, (size_t)nb + b, key_true, add);
+    wave_grouped_at(on_pair, 2 * (size_t)nb + b, key_pair, add);
+}
+
+// the two carry planes of the matched call: grid y = 0 the prediction's rows, 1 the label's rows of the chunk's last slice
+__global__ __launch_bounds__(RB) void k_lesion_match_carry(const int* __restrict__ L, const int* __restrict__ row, const int* __restrict__ LT,
+                                                           const int* __restrict__ rowT, size_t g0, size_t hw, int cap,
+                                                           int* __restrict__ carry, int* __restrict__ carryT) {
+    const size_t p = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (p >= hw) return;
+    if (blockIdx.y == 0) carry[p] = lesion_row_at(L, row, g0 + p, cap);
+    else carryT[p] = lesion_row_at(LT, rowT, g0 + p, cap);
 }
 
 inline unsigned nblocks(size_t n) { return (unsigned)((n + RB - 1) / RB); }
@@ -675,6 +740,15 @@ struct RegionState {
     size_t carry_n = 0;                  // allocated pixels
     bool carry_valid = false;            // written by a linked call that succeeded ...
     int carry_oh = 0, carry_ow = 0;      // ... on planes of this size
+    // dnnca_lesion_table_matched keeps all of this apart from the linked call's: two carry planes in one buffer (the prediction's
+    // rows, then from mcarry + mcarry_n the label's rows) and what DNNCA_PLAN_LESION_MATCHED replays
+    int* mcarry = nullptr;
+    size_t mcarry_n = 0;                 // allocated pixels per plane
+    bool mcarry_valid = false;
+    int mcarry_oh = 0, mcarry_ow = 0;
+    float match_rf = 1.f;
+    int match_k = 5;
+    bool match_mask = true;
 };
 
 static constexpr size_t kRegionBudget = size_t(1) << 24;    // pixel-thresholds per chunk (~21 bytes each)
@@ -1027,10 +1101,17 @@ struct LesionWs {                        // carve-up of the workspace for nb sli
     unsigned char* cont;
     LesionLink* list;
     unsigned* n_list;
+    // matched calls only: the label plane's own words, parents, sizes, rows, totals, threshold and table.  Their lkeys / lcnt hold
+    // three sets of tables, list three lists of nb * links_per_slice entries and n_list three counts (lesion_match)
+    uint32_t* yw;
+    int *ylp, *yrow, *ytot;
+    unsigned* ysp;
+    float* ythr;
+    LesionAcc* yacc;
     size_t bytes;
 };
 
-static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap, size_t links_per_slice = 0) {
+static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap, size_t links_per_slice = 0, bool matched = false) {
     const size_t n = nb * hw;
     LesionWs w;
     char* p = (char*)base;
@@ -1047,11 +1128,22 @@ static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap, size
     w.mask = (uint32_t*)take((n + 3) / 4 * 4);
     w.lkeys = nullptr, w.lcnt = nullptr, w.cont = nullptr, w.list = nullptr, w.n_list = nullptr;
     if (links_per_slice) {
-        w.lkeys = (unsigned long long*)take(nb * (hw + 1) * 8);
-        w.lcnt = (unsigned*)take(nb * (hw + 1) * 4);
+        const size_t sets = matched ? 3 : 1;
+        w.lkeys = (unsigned long long*)take(sets * nb * (hw + 1) * 8);
+        w.lcnt = (unsigned*)take(sets * nb * (hw + 1) * 4);
         w.cont = (unsigned char*)take(nb);
-        w.list = (LesionLink*)take(nb * links_per_slice * sizeof(LesionLink));
-        w.n_list = (unsigned*)take(4);
+        w.list = (LesionLink*)take(sets * nb * links_per_slice * sizeof(LesionLink));
+        w.n_list = (unsigned*)take(sets * 4);
+    }
+    w.yw = nullptr, w.ylp = nullptr, w.yrow = nullptr, w.ytot = nullptr, w.ysp = nullptr, w.ythr = nullptr, w.yacc = nullptr;
+    if (matched) {
+        w.yw = (uint32_t*)take(n * 4);
+        w.ylp = (int*)take(n * 4);
+        w.ysp = (unsigned*)take(n * 4);
+        w.yrow = (int*)take(n * 4);
+        w.ytot = (int*)take(nb * 4);
+        w.ythr = (float*)take(4);
+        w.yacc = (LesionAcc*)take(nb * cap * sizeof(LesionAcc));
     }
     w.bytes = off;
     return w;
@@ -1082,20 +1174,100 @@ struct LesionLinkIO {                    // what a linked call adds to the chunk
     int64_t* n_links;
 };
 
-// the chunk loop of lesion_table and lesion_table_linked (link != nullptr: the three link launches behind every chunk's table)
+struct LesionMatchIO {                   // what a matched call adds to a linked one: the labels (device) and the host outputs
+    const float* y;
+    dnnca_lesion_row* rows;
+    int64_t* n_rows;
+    int32_t* totals;
+    dnnca_lesion_link* links;
+    int64_t* n_links;
+    dnnca_lesion_pair* pairs;
+    int64_t* n_pairs;
+};
+
+static_assert(sizeof(LesionLink) == sizeof(dnnca_lesion_pair), "the device list is copied into the caller's records");
+
+// label' > 0.5 as a >= threshold of region_prep (T = 1): the float32 after 0.5
+static const float kLabelThreshold = nextafterf(0.5f, 1.f);
+
+// one plane of nb slices from its thresholded words to its numbered components and their table: ccl, sizes, lesion_scan,
+// lesion_stats (`src`: what was thresholded)
+static int lesion_plane(Model* M, const float* src, const Resize& rz, int nb, const uint32_t* fg, int min_area, size_t cap, int* lp,
+                        unsigned* sp, int* row, int* tot, LesionAcc* acc) {
+    hipStream_t s = M->stream;
+    const size_t hw = (size_t)rz.out_h * rz.out_w, n = (size_t)nb * hw;
+    region_ccl(M, fg, 1, nb, rz.out_h, rz.out_w, lp);
+    if (!M->dry) {
+        HIP_TRY(hipMemsetAsync(sp, 0, n * 4, s));
+        HIP_TRY(hipMemsetAsync(acc, 0, (size_t)nb * cap * sizeof(LesionAcc), s));
+    }
+    LAUNCH(M, "region_sizes", n * 4.0, 0, hipLaunchKernelGGL(k_region_sizes, dim3(nblocks(n)), dim3(RB), 0, s, lp, n, sp));
+    LAUNCH(M, "lesion_scan", n * 12.0, 0,
+           hipLaunchKernelGGL(k_lesion_scan, dim3(nb), dim3(RB), 0, s, lp, sp, (int)hw, (unsigned)min_area, row, tot));
+    LAUNCH(M, "lesion_stats", n * 8.0 + (double)nb * rz.in_h * rz.in_w * 4, 0,
+           hipLaunchKernelGGL(k_lesion_stats, dim3(nblocks(n)), dim3(RB), 0, s, src, rz, nb, lp, row, (int)cap, acc));
+    return DNNCA_OK;
+}
+
+// the rows that the slices of a chunk filled (tot: their kept components, already on the host) from the device table to the
+// caller's records; synchronises
+static int lesion_rows_read(Model* M, const LesionAcc* acc_dev, const std::vector<int>& tot, int b0, size_t cap, std::vector<LesionAcc>& acc,
+                            dnnca_lesion_row* rows, int64_t& out, int32_t* totals) {
+    hipStream_t s = M->stream;
+    const int nb = (int)tot.size();
+    std::vector<size_t> first(nb + 1, 0);         // only the rows a slice filled come back
+    for (int b = 0; b < nb; ++b) first[b + 1] = first[b] + std::min<size_t>((size_t)std::max(tot[b], 0), cap);
+    acc.resize(first[nb]);
+    for (int b = 0; b < nb; ++b)
+        if (first[b + 1] > first[b])
+            HIP_TRY(hipMemcpyAsync(acc.data() + first[b], acc_dev + (size_t)b * cap, (first[b + 1] - first[b]) * sizeof(LesionAcc),
+                                   hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < nb; ++b) {
+        totals[b0 + b] = tot[b];
+        for (size_t r = 0; r < first[b + 1] - first[b]; ++r) {
+            const LesionAcc& v = acc[first[b] + r];
+            dnnca_lesion_row& o = rows[out++];
+            o.slice = b0 + b;
+            o.row = (int32_t)r;
+            o.area = (int32_t)v.area;
+            o.x0 = (int32_t)~v.nx0;
+            o.y0 = (int32_t)~v.ny0;
+            o.x1 = (int32_t)v.x1;
+            o.y1 = (int32_t)v.y1;
+            memcpy(&o.max_prob, &v.mp, 4);
+            o.sum_x = v.sx;
+            o.sum_y = v.sy;
+            o.sum_prob_q24 = v.sq;
+        }
+    }
+    return DNNCA_OK;
+}
+
+// the chunk loop of lesion_table, lesion_table_linked (link != nullptr: the three link launches behind every chunk's table) and
+// lesion_table_matched (link and match: the label plane's table as well, then lesion_match / lesion_link_emit over the three
+// sets of tables / lesion_match_carry in the place of the link launches).  A matched chunk holds two planes and three sets of
+// tables and lists: its slices are a third of a linked chunk's (region_chunk with T = 3), which changes no result
 static int lesion_run(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows, int64_t* n_rows,
-                      int32_t* totals, uint8_t* mask, bool want_mask, const LesionLinkIO* link) {
+                      int32_t* totals, uint8_t* mask, bool want_mask, const LesionLinkIO* link, const LesionMatchIO* match = nullptr) {
     DN_TRY(region_state(M));
     RegionState& R = *M->region;
-    R.lesion_rf = a.rf;
-    R.lesion_k = a.k;
-    R.lesion_mask = want_mask;
+    if (match) {
+        R.match_rf = a.rf;
+        R.match_k = a.k;
+        R.match_mask = want_mask;
+    } else {
+        R.lesion_rf = a.rf;
+        R.lesion_k = a.k;
+        R.lesion_mask = want_mask;
+    }
     const int oh = a.oh, ow = a.ow;
     const size_t hw = (size_t)oh * ow, cap = (size_t)a.cap, slots = hw + 1;
     const size_t per_slice = link ? (size_t)a.links_per_slice() : 0;
-    const int chunk = (int)region_chunk(1, hw, batch);
-    if (!M->dry) DN_TRY(region_ws_reserve(R, lesion_layout(nullptr, chunk, hw, cap, per_slice).bytes));
-    if (link && !M->dry) {               // from here on the carry is this call's: valid again once every chunk has gone through
+    const int sets = match ? 3 : 1;
+    const int chunk = (int)region_chunk(match ? 3 : 1, hw, batch);
+    if (!M->dry) DN_TRY(region_ws_reserve(R, lesion_layout(nullptr, chunk, hw, cap, per_slice, match != nullptr).bytes));
+    if (link && !match && !M->dry) {     // from here on the carry is this call's: valid again once every chunk has gone through
         R.carry_valid = false;
         if (hw > R.carry_n) {            // (a set continues[0] was checked against a carry of this size: that one is never regrown)
             if (R.carry) HIP_TRY(hipFree(R.carry));
@@ -1105,18 +1277,29 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
             R.carry_n = hw;
         }
     }
+    if (match && !M->dry) {              // the same for the two carry planes of the matched calls
+        R.mcarry_valid = false;
+        if (hw > R.mcarry_n) {
+            if (R.mcarry) HIP_TRY(hipFree(R.mcarry));
+            R.mcarry = nullptr;
+            R.mcarry_n = 0;
+            HIP_TRY(hipMalloc((void**)&R.mcarry, 2 * hw * 4));
+            R.mcarry_n = hw;
+        }
+    }
+    int* const carry_t = R.mcarry ? R.mcarry + R.mcarry_n : nullptr;
     hipStream_t s = M->stream;
     std::vector<LesionAcc> acc;
-    std::vector<int> tot;
-    std::vector<size_t> first;
-    std::vector<LesionLink> found;
-    int64_t out = 0, out_links = 0;
+    std::vector<int> tot, ytot;
+    std::vector<LesionLink> found[3];
+    int64_t out = 0, out_true = 0, out_list[3] = {0, 0, 0};
     Resize rz{h, w, oh, ow, (float)h / (float)oh, (float)w / (float)ow, (oh == h && ow == w) ? 1 : 0};
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
         const size_t n = (size_t)nb * hw;
-        const LesionWs ws = lesion_layout(R.ws, nb, hw, cap, per_slice);
+        const LesionWs ws = lesion_layout(R.ws, nb, hw, cap, per_slice, match != nullptr);
         const float* pb = prob + (size_t)b0 * h * w;
+        const float* yb = match ? match->y + (size_t)b0 * h * w : nullptr;
         if (!M->dry) HIP_TRY(hipMemcpyAsync(ws.thr, &a.threshold, 4, hipMemcpyHostToDevice, s));   // `a` outlives the chunk's sync
         if (link && !M->dry) HIP_TRY(hipMemcpyAsync(ws.cont, link->continues + b0, (size_t)nb, hipMemcpyHostToDevice, s));
         LAUNCH(M, "region_prep", n * 4.0 + (double)nb * h * w * 4, 0,
@@ -1128,92 +1311,94 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
                    hipLaunchKernelGGL(k_region_open, tiles, dim3(RB), 0, s, ws.w0, ws.w1, oh, ow, a.k, n, nb));
             fg = ws.w1;
         }
-        region_ccl(M, fg, 1, nb, oh, ow, ws.lp);
-        if (!M->dry) {
-            HIP_TRY(hipMemsetAsync(ws.sp, 0, n * 4, s));
-            HIP_TRY(hipMemsetAsync(ws.acc, 0, (size_t)nb * cap * sizeof(LesionAcc), s));
-        }
-        LAUNCH(M, "region_sizes", n * 4.0, 0, hipLaunchKernelGGL(k_region_sizes, dim3(nblocks(n)), dim3(RB), 0, s, ws.lp, n, ws.sp));
-        LAUNCH(M, "lesion_scan", n * 12.0, 0,
-               hipLaunchKernelGGL(k_lesion_scan, dim3(nb), dim3(RB), 0, s, ws.lp, ws.sp, (int)hw, (unsigned)a.min_area, ws.row, ws.tot));
-        LAUNCH(M, "lesion_stats", n * 8.0 + (double)nb * h * w * 4, 0,
-               hipLaunchKernelGGL(k_lesion_stats, dim3(nblocks(n)), dim3(RB), 0, s, pb, rz, nb, ws.lp, ws.row, (int)cap, ws.acc));
+        DN_TRY(lesion_plane(M, pb, rz, nb, fg, a.min_area, cap, ws.lp, ws.sp, ws.row, ws.tot, ws.acc));
         if (want_mask)
             LAUNCH(M, "lesion_mask", n * 9.0, 0,
                    hipLaunchKernelGGL(k_lesion_mask, dim3(nblocks((n + 3) / 4)), dim3(RB), 0, s, ws.lp, ws.row, n, ws.mask));
+        if (match) {                     // the label plane: label' > 0.5, no opening, no area filter
+            if (!M->dry) HIP_TRY(hipMemcpyAsync(ws.ythr, &kLabelThreshold, 4, hipMemcpyHostToDevice, s));
+            LAUNCH(M, "region_prep", n * 4.0 + (double)nb * h * w * 4, 0,
+                   hipLaunchKernelGGL(k_region_prep, dim3(nblocks(n)), dim3(RB), 0, s, yb, rz, nb, (const float*)ws.ythr, 1, ws.yw));
+            DN_TRY(lesion_plane(M, yb, rz, nb, ws.yw, 0, cap, ws.ylp, ws.ysp, ws.yrow, ws.ytot, ws.yacc));
+        }
         if (link) {                      // on every chunk, whatever the flags say: they are device data
             const size_t total = (size_t)nb * slots, list_cap = (size_t)nb * per_slice;
             if (!M->dry) {
-                HIP_TRY(hipMemsetAsync(ws.lkeys, 0xff, total * 8, s));
-                HIP_TRY(hipMemsetAsync(ws.lcnt, 0, total * 4, s));
-                HIP_TRY(hipMemsetAsync(ws.n_list, 0, 4, s));
+                HIP_TRY(hipMemsetAsync(ws.lkeys, 0xff, sets * total * 8, s));
+                HIP_TRY(hipMemsetAsync(ws.lcnt, 0, sets * total * 4, s));
+                HIP_TRY(hipMemsetAsync(ws.n_list, 0, sets * 4, s));
             }
-            LAUNCH(M, "lesion_link", n * 16.0 + (double)nb, 0,
-                   hipLaunchKernelGGL(k_lesion_link, dim3(nblocks(n)), dim3(RB), 0, s, ws.lp, ws.row, (const int*)R.carry, ws.cont, nb, hw,
-                                      (int)cap, slots, ws.lkeys, ws.lcnt));
-            LAUNCH(M, "lesion_link_emit", total * 12.0, 0,
-                   hipLaunchKernelGGL(k_lesion_link_emit, dim3(nblocks(total)), dim3(RB), 0, s, ws.lkeys, ws.lcnt, total, slots, b0,
+            if (match)
+                LAUNCH(M, "lesion_match", n * 32.0 + (double)nb, 0,
+                       hipLaunchKernelGGL(k_lesion_match, dim3(nblocks(n)), dim3(RB), 0, s, ws.lp, ws.row, ws.ylp, ws.yrow,
+                                          (const int*)R.mcarry, (const int*)carry_t, ws.cont, nb, hw, (int)cap, slots, ws.lkeys, ws.lcnt));
+            else
+                LAUNCH(M, "lesion_link", n * 16.0 + (double)nb, 0,
+                       hipLaunchKernelGGL(k_lesion_link, dim3(nblocks(n)), dim3(RB), 0, s, ws.lp, ws.row, (const int*)R.carry, ws.cont, nb,
+                                          hw, (int)cap, slots, ws.lkeys, ws.lcnt));
+            LAUNCH(M, "lesion_link_emit", sets * total * 12.0, 0,
+                   hipLaunchKernelGGL(k_lesion_link_emit, dim3(nblocks(total), sets), dim3(RB), 0, s, ws.lkeys, ws.lcnt, total, slots, b0,
                                       (unsigned)list_cap, ws.list, ws.n_list));
-            // after lesion_link on the same stream: the link kernel of this chunk has read the carry of the chunk before
-            LAUNCH(M, "lesion_carry", hw * 12.0, 0,
-                   hipLaunchKernelGGL(k_lesion_carry, dim3(nblocks(hw)), dim3(RB), 0, s, ws.lp, ws.row, (size_t)(nb - 1) * hw, hw, (int)cap,
-                                      R.carry));
+            // after lesion_link / lesion_match on the same stream: that kernel of this chunk has read the carry of the chunk before
+            if (match)
+                LAUNCH(M, "lesion_match_carry", hw * 24.0, 0,
+                       hipLaunchKernelGGL(k_lesion_match_carry, dim3(nblocks(hw), 2), dim3(RB), 0, s, ws.lp, ws.row, ws.ylp, ws.yrow,
+                                          (size_t)(nb - 1) * hw, hw, (int)cap, R.mcarry, carry_t));
+            else
+                LAUNCH(M, "lesion_carry", hw * 12.0, 0,
+                       hipLaunchKernelGGL(k_lesion_carry, dim3(nblocks(hw)), dim3(RB), 0, s, ws.lp, ws.row, (size_t)(nb - 1) * hw, hw,
+                                          (int)cap, R.carry));
         }
         if (M->dry) continue;
         HIP_TRY(hipGetLastError());
         tot.resize(nb);
-        unsigned n_found = 0;
+        unsigned n_found[3] = {0, 0, 0};
         HIP_TRY(hipMemcpyAsync(tot.data(), ws.tot, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        if (match) {
+            ytot.resize(nb);
+            HIP_TRY(hipMemcpyAsync(ytot.data(), ws.ytot, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        }
         if (mask) HIP_TRY(hipMemcpyAsync(mask + (size_t)b0 * hw, ws.mask, n, hipMemcpyDeviceToHost, s));
-        if (link) HIP_TRY(hipMemcpyAsync(&n_found, ws.n_list, 4, hipMemcpyDeviceToHost, s));
+        if (link) HIP_TRY(hipMemcpyAsync(n_found, ws.n_list, sets * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        if (link) {                      // only the counted links come back; their order is the atomics': sorted here
-            if ((size_t)n_found > (size_t)nb * per_slice) {
-                set_error("lesion table: %u links in %d slices exceed the bound of %zu per slice", n_found, nb, per_slice);
+        for (int t = 0; t < sets && link; ++t) {     // only the counted entries come back; their order is the atomics': sorted below
+            if ((size_t)n_found[t] > (size_t)nb * per_slice) {
+                set_error("lesion table: %u %s in %d slices exceed the bound of %zu per slice", n_found[t], t == 2 ? "pairs" : "links", nb,
+                          per_slice);
                 return DNNCA_ESTATE;
             }
-            found.resize(n_found);
-            if (n_found) HIP_TRY(hipMemcpyAsync(found.data(), ws.list, (size_t)n_found * sizeof(LesionLink), hipMemcpyDeviceToHost, s));
-        }
-        first.assign(nb + 1, 0);         // only the rows a slice filled come back
-        for (int b = 0; b < nb; ++b) first[b + 1] = first[b] + std::min<size_t>((size_t)std::max(tot[b], 0), cap);
-        acc.resize(first[nb]);
-        for (int b = 0; b < nb; ++b)
-            if (first[b + 1] > first[b])
-                HIP_TRY(hipMemcpyAsync(acc.data() + first[b], ws.acc + (size_t)b * cap, (first[b + 1] - first[b]) * sizeof(LesionAcc),
+            found[t].resize(n_found[t]);
+            if (n_found[t])
+                HIP_TRY(hipMemcpyAsync(found[t].data(), ws.list + (size_t)t * nb * per_slice, (size_t)n_found[t] * sizeof(LesionLink),
                                        hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        for (int b = 0; b < nb; ++b) {
-            totals[b0 + b] = tot[b];
-            for (size_t r = 0; r < first[b + 1] - first[b]; ++r) {
-                const LesionAcc& v = acc[first[b] + r];
-                dnnca_lesion_row& o = rows[out++];
-                o.slice = b0 + b;
-                o.row = (int32_t)r;
-                o.area = (int32_t)v.area;
-                o.x0 = (int32_t)~v.nx0;
-                o.y0 = (int32_t)~v.ny0;
-                o.x1 = (int32_t)v.x1;
-                o.y1 = (int32_t)v.y1;
-                memcpy(&o.max_prob, &v.mp, 4);
-                o.sum_x = v.sx;
-                o.sum_y = v.sy;
-                o.sum_prob_q24 = v.sq;
-            }
         }
-        if (link) {
-            std::sort(found.begin(), found.end(), [](const LesionLink& x, const LesionLink& y) {
+        DN_TRY(lesion_rows_read(M, ws.acc, tot, b0, cap, acc, rows, out, totals));
+        if (match) DN_TRY(lesion_rows_read(M, ws.yacc, ytot, b0, cap, acc, match->rows, out_true, match->totals));
+        for (int t = 0; t < sets && link; ++t) {
+            std::sort(found[t].begin(), found[t].end(), [](const LesionLink& x, const LesionLink& y) {
                 return std::make_tuple(x.slice, x.row_prev, x.row) < std::make_tuple(y.slice, y.row_prev, y.row);
             });
-            for (const LesionLink& v : found) link->links[out_links++] = dnnca_lesion_link{v.slice, v.row_prev, v.row, v.overlap};
+            for (const LesionLink& v : found[t]) {
+                if (t == 0) link->links[out_list[0]++] = dnnca_lesion_link{v.slice, v.row_prev, v.row, v.overlap};
+                else if (t == 1) match->links[out_list[1]++] = dnnca_lesion_link{v.slice, v.row_prev, v.row, v.overlap};
+                else match->pairs[out_list[2]++] = dnnca_lesion_pair{v.slice, v.row_prev, v.row, v.overlap};
+            }
         }
     }
     if (!M->dry && n_rows) *n_rows = out;
-    if (link && !M->dry) {
-        *link->n_links = out_links;
+    if (link && !M->dry) *link->n_links = out_list[0];
+    if (link && !match && !M->dry) {
         R.carry_valid = true;
         R.carry_oh = oh;
         R.carry_ow = ow;
+    }
+    if (match && !M->dry) {
+        *match->n_rows = out_true;
+        *match->n_links = out_list[1];
+        *match->n_pairs = out_list[2];
+        R.mcarry_valid = true;
+        R.mcarry_oh = oh;
+        R.mcarry_ow = ow;
     }
     return DNNCA_OK;
 }
@@ -1228,6 +1413,31 @@ int lesion_table_linked(Model* M, const float* prob, int batch, int h, int w, co
                         dnnca_lesion_link* links, int64_t* n_links) {
     const LesionLinkIO io{continues, links, n_links};
     return lesion_run(M, prob, batch, h, w, a, rows, n_rows, totals, mask, want_mask, &io);
+}
+
+int lesion_table_matched(Model* M, const float* prob, const float* y, int batch, int h, int w, const LesionArgs& a,
+                         const uint8_t* continues, dnnca_lesion_plane_out* pred, uint8_t* mask, bool want_mask,
+                         dnnca_lesion_plane_out* truth, dnnca_lesion_pairs_out* pairs) {
+    if (M->dry) {
+        const LesionLinkIO io{nullptr, nullptr, nullptr};
+        const LesionMatchIO mo{y, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        return lesion_run(M, prob, batch, h, w, a, nullptr, nullptr, nullptr, nullptr, want_mask, &io, &mo);
+    }
+    const LesionLinkIO io{continues, pred->links, &pred->n_links};
+    const LesionMatchIO mo{y, truth->rows, &truth->n_rows, truth->totals, truth->links, &truth->n_links, pairs->pairs, &pairs->n_pairs};
+    return lesion_run(M, prob, batch, h, w, a, pred->rows, &pred->n_rows, pred->totals, mask, want_mask, &io, &mo);
+}
+
+bool lesion_match_carry_is(Model* M, int oh, int ow) {
+    return M->region && M->region->mcarry_valid && M->region->mcarry_oh == oh && M->region->mcarry_ow == ow;
+}
+
+void lesion_match_last(Model* M, float* rf, int* k, bool* want_mask) {
+    RegionState def;
+    const RegionState& R = M->region ? *M->region : def;
+    *rf = R.match_rf;
+    *k = R.match_k;
+    *want_mask = R.match_mask;
 }
 
 bool lesion_carry_is(Model* M, int oh, int ow) {
@@ -1245,7 +1455,8 @@ void lesion_last(Model* M, float* rf, int* k, bool* want_mask) {
 void region_release(Model* M) {
     if (!M->region) return;
     RegionState& R = *M->region;
-    for (void* p : {(void*)R.thr_dev, (void*)R.acc, R.ws, (void*)R.in_prob, (void*)R.in_y, (void*)R.slice_acc, (void*)R.viz, (void*)R.carry})
+    for (void* p : {(void*)R.thr_dev, (void*)R.acc, R.ws, (void*)R.in_prob, (void*)R.in_y, (void*)R.slice_acc, (void*)R.viz, (void*)R.carry,
+                    (void*)R.mcarry})
         if (p) (void)hipFree(p);
     delete M->region;
     M->region = nullptr;

@@ -2024,6 +2024,80 @@ int dnnca_lesion_table_linked(void* model, const float* prob_hw, int batch, int 
                        n_rows, totals, mask, mask_capacity, out_hw, true, continues, links, links_capacity, n_links);
 }
 
+int dnnca_lesion_table_matched(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w, float threshold,
+                               float resize_factor, int filter_size, int min_area, int max_lesions, const uint8_t* continues,
+                               dnnca_lesion_plane_out* pred, uint8_t* mask, int64_t mask_capacity, dnnca_lesion_plane_out* truth,
+                               dnnca_lesion_pairs_out* pairs, int32_t* out_hw) {
+    MODEL(model);
+    DN_TRY(check_batch(M, batch));
+    if (!prob_hw) {
+        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
+            set_error("lesion table: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
+            return DNNCA_EINVAL;
+        }
+        h = M->outH;
+        w = M->outW;
+    }
+    LesionArgs a;
+    a.threshold = threshold;
+    a.rf = resize_factor;
+    a.k = filter_size;
+    a.min_area = min_area;
+    a.max_lesions = max_lesions;
+    DN_TRY(lesion_check(a, h, w));
+    if (!out_hw) { set_error("lesion table: null out_hw"); return DNNCA_EINVAL; }
+    out_hw[0] = a.oh;
+    out_hw[1] = a.ow;
+    if (!pred || !pred->rows) return DNNCA_OK;      // size query
+    if (!y_hw) { set_error("lesion table: null y_hw (the matched call needs the labels)"); return DNNCA_EINVAL; }
+    if (!truth || !pairs) { set_error("lesion table: null truth / pairs"); return DNNCA_EINVAL; }
+    const long long need_rows = (long long)batch * a.cap, need_links = (long long)batch * a.links_per_slice();
+    if (!pred->totals || !truth->totals) { set_error("lesion table: null totals"); return DNNCA_EINVAL; }
+    if (pred->rows_capacity < need_rows) {
+        set_error("lesion table: %lld rows needed (%d slices x %d), capacity %lld", need_rows, batch, a.cap, (long long)pred->rows_capacity);
+        return DNNCA_EINVAL;
+    }
+    if (mask && mask_capacity < (int64_t)batch * a.oh * a.ow) {
+        set_error("lesion table: mask of %lld bytes needed, capacity %lld", (long long)batch * a.oh * a.ow, (long long)mask_capacity);
+        return DNNCA_EINVAL;
+    }
+    if (!continues) { set_error("lesion table: null continues"); return DNNCA_EINVAL; }
+    if (!pred->links || pred->links_capacity < need_links) {
+        set_error("lesion table: %lld links needed (%d slices x %lld), capacity %lld", need_links, batch, (long long)a.links_per_slice(),
+                  pred->links ? (long long)pred->links_capacity : 0ll);
+        return DNNCA_EINVAL;
+    }
+    if (!truth->rows || truth->rows_capacity < need_rows) {
+        set_error("lesion table: %lld true_rows needed (%d slices x %d), capacity %lld", need_rows, batch, a.cap,
+                  truth->rows ? (long long)truth->rows_capacity : 0ll);
+        return DNNCA_EINVAL;
+    }
+    if (!truth->links || truth->links_capacity < need_links) {
+        set_error("lesion table: %lld true_links needed (%d slices x %lld), capacity %lld", need_links, batch,
+                  (long long)a.links_per_slice(), truth->links ? (long long)truth->links_capacity : 0ll);
+        return DNNCA_EINVAL;
+    }
+    if (!pairs->pairs || pairs->capacity < need_links) {
+        set_error("lesion table: %lld pairs needed (%d slices x %lld), capacity %lld", need_links, batch, (long long)a.links_per_slice(),
+                  pairs->pairs ? (long long)pairs->capacity : 0ll);
+        return DNNCA_EINVAL;
+    }
+    if (continues[0] && !lesion_match_carry_is(M, a.oh, a.ow)) {
+        set_error("lesion table: continues[0] is set, but no matched call on planes of %d x %d precedes this one", a.oh, a.ow);
+        return DNNCA_EINVAL;
+    }
+    const size_t n = (size_t)batch * h * w;
+    float *pd = nullptr, *yd = nullptr;
+    DN_TRY(region_inputs(M, n, &pd, &yd));
+    const float* p_dev = M->prob;
+    if (prob_hw) {
+        HIP_TRY(hipMemcpyAsync(pd, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+        p_dev = pd;
+    }
+    HIP_TRY(hipMemcpyAsync(yd, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+    return lesion_table_matched(M, p_dev, yd, batch, h, w, a, continues, pred, mask, mask != nullptr, truth, pairs);
+}
+
 int dnnca_eval_region_begin(void* model, const dnnca_region_spec* specs, int n) {
     MODEL(model);
     if (!M->eval_active) { set_error("dnnca_eval_region_begin outside dnnca_eval_begin .. dnnca_eval_end"); return DNNCA_ESTATE; }
@@ -2227,7 +2301,7 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
     MODEL(model);
     if (!buf || !cap) return DNNCA_EINVAL;
     if (pass != DNNCA_PLAN_TRAIN && pass != DNNCA_PLAN_EVAL && pass != DNNCA_PLAN_FORWARD && pass != DNNCA_PLAN_SENSITIVITY &&
-        pass != DNNCA_PLAN_LESION && pass != DNNCA_PLAN_LESION_LINKED) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
+        pass != DNNCA_PLAN_LESION && pass != DNNCA_PLAN_LESION_LINKED && pass != DNNCA_PLAN_LESION_MATCHED) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
     DN_TRY(check_batch(M, batch));
     M->plan_text.clear();
     M->dry = true;
@@ -2260,6 +2334,13 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
         else if (rc == DNNCA_OK)
             rc = lesion_table_linked(M, M->prob, B, M->outH, M->outW, a, nullptr, nullptr, nullptr, nullptr, want_mask, nullptr, nullptr,
                                      nullptr);
+    } else if (pass == DNNCA_PLAN_LESION_MATCHED) {
+        LesionArgs a;
+        bool want_mask = true;
+        lesion_match_last(M, &a.rf, &a.k, &want_mask);
+        rc = lesion_check(a, M->outH, M->outW);
+        if (rc == DNNCA_OK)
+            rc = lesion_table_matched(M, M->prob, M->y_stage, B, M->outH, M->outW, a, nullptr, nullptr, nullptr, want_mask, nullptr, nullptr);
     } else {
         rc = dnnca_forward_dev(model, M->x_stage, B, 0);
     }

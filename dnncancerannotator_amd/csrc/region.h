@@ -47,7 +47,8 @@ struct LesionArgs {
     float threshold = 0.5f, rf = 1.f;
     int k = 5, min_area = 0, max_lesions = 256;
     int oh = 0, ow = 0, cap = 0;         // filled by lesion_check: the analysed plane, rows per slice min(max_lesions, (oh ow + 1) / 2)
-    // links into one slice: distinct (row_prev, row) pairs, at most cap^2 and at most ceil(oh ow / 2) (kernels_region.hip, lesion_link)
+    // links into one slice: distinct (row_prev, row) pairs, at most cap^2 and at most ceil(oh ow / 2) (kernels_region.hip, lesion_link);
+    // the (row_true, row) pairs of one slice have the same bound (lesion_match)
     int64_t links_per_slice() const { return std::min<int64_t>((int64_t)cap * cap, ((int64_t)oh * ow + 1) / 2); }
 };
 // checks the caller's arguments against slices of h x w and fills oh / ow / cap; DNNCA_EINVAL with the reason otherwise
@@ -67,6 +68,18 @@ int lesion_table_linked(Model* M, const float* prob, int batch, int h, int w, co
                         dnnca_lesion_link* links, int64_t* n_links);
 // the carry plane holds the rows of the last slice of a successful lesion_table_linked on planes of oh x ow
 bool lesion_carry_is(Model* M, int oh, int ow);
+// lesion_table_linked on prob plus the same on the labels y (device [batch, h, w]: label' > 0.5, no opening, no area filter, the
+// same cap) plus the pairs of a labelled and a predicted lesion of one slice (dnnca_lesion_table_matched): per chunk the launches
+// of lesion_table for either plane, then lesion_match (the three kinds of pairs in one pass), lesion_link_emit over the three
+// sets of tables, lesion_match_carry.  pred / truth / pairs: the caller's buffers (checked by the caller) and the counts written
+// back; every list sorted as lesion_table_linked sorts its links.  The two carry planes are this call's own: the caller has
+// checked lesion_match_carry_is(M, a.oh, a.ow) where continues[0] is set.  In a dry run none of the host pointers is read
+int lesion_table_matched(Model* M, const float* prob, const float* y, int batch, int h, int w, const LesionArgs& a,
+                         const uint8_t* continues, dnnca_lesion_plane_out* pred, uint8_t* mask, bool want_mask,
+                         dnnca_lesion_plane_out* truth, dnnca_lesion_pairs_out* pairs);
+bool lesion_match_carry_is(Model* M, int oh, int ow);
+// resize factor, filter size and mask choice of the last lesion_table_matched (DNNCA_PLAN_LESION_MATCHED); the defaults before any
+void lesion_match_last(Model* M, float* rf, int* k, bool* want_mask);
 // resize factor, filter size and mask choice of the last lesion_table / lesion_table_linked (DNNCA_PLAN_LESION,
 // DNNCA_PLAN_LESION_LINKED); the defaults before any
 void lesion_last(Model* M, float* rf, int* k, bool* want_mask);

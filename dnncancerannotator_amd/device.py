@@ -553,6 +553,64 @@ class DeviceModel:
                                                  links.ctypes.data_as(C.POINTER(_lib.LesionLink)), lcap, C.byref(nl)))
         return rows[:n.value].copy(), totals, masks, links[:nl.value].copy()
 
+    def lesion_table_matched(self, y, batch=None, prob=None, continues=None, threshold=0.5, resize_factor=1.0, filter_size=5,
+                             min_area=0, max_lesions=256, mask=False):
+        """lesion_table_linked on the probabilities, the same on the labels `y` [B, h, w(, 1)] (y' > 0.5, no opening, no area
+        filter, the same max_lesions) and the common pixels of labelled and predicted lesions, in one call:
+        (rows, totals, masks, links, true_rows, true_totals, true_links, pairs).  The first four are what lesion_table_linked
+        returns, the next three what it returns for `y` in the place of the probabilities.  pairs: structured array
+        (_lib.LESION_PAIR_DTYPE: slice, row_true, row, overlap), one entry per labelled lesion (row_true) and predicted lesion (row)
+        of one slice that share `overlap` pixels, sorted by (slice, row_true, row).  continues[0] refers to the last slice of the
+        previous lesion_table_matched call on this model; the chain of lesion_table_linked is a separate one."""
+        if continues is None:
+            raise ValueError('lesion_table_matched needs `continues`, one flag per slice')
+        y = as_f32(y)
+        if y.ndim == 4 and y.shape[-1] == 1:
+            y = np.ascontiguousarray(y[..., 0])
+        if y.ndim != 3:
+            raise ValueError('y must be [B, h, w], got %s' % (y.shape,))
+        pp, h, w = None, 0, 0
+        if prob is not None:
+            prob = as_f32(prob)
+            if prob.ndim == 4 and prob.shape[-1] == 1:
+                prob = np.ascontiguousarray(prob[..., 0])
+            if prob.shape != y.shape:
+                raise ValueError('prob %s and y %s differ in shape' % (prob.shape, y.shape))
+            if batch is not None and int(batch) != prob.shape[0]:
+                raise ValueError('batch %d but prob holds %d slices' % (batch, prob.shape[0]))
+            (batch, h, w), pp = prob.shape, fptr(prob)
+        elif batch is None:
+            batch = len(y)
+        B = int(batch)
+        if len(y) != B:
+            raise ValueError('batch %d but y holds %d slices' % (B, len(y)))
+        h, w = y.shape[1:]               # without `prob` the library holds them against the size of the last forward
+        flags = np.ascontiguousarray(np.asarray(continues).astype(bool), np.uint8)
+        if flags.shape != (B,):
+            raise ValueError('continues must hold one flag per slice (%d), got shape %s' % (B, flags.shape))
+        args = (self.handle, pp, fptr(y), B, int(h), int(w), float(threshold), float(resize_factor), int(filter_size), int(min_area),
+                int(max_lesions), flags.ctypes.data_as(C.POINTER(C.c_uint8)))
+        hw = (C.c_int32 * 2)()
+        check(self.lib.dnnca_lesion_table_matched(*args, None, None, 0, None, None, hw))
+        oh, ow = hw[0], hw[1]
+        per_slice = min(int(max_lesions), (oh * ow + 1) // 2)
+        cap, lcap = B * per_slice, B * min(per_slice * per_slice, (oh * ow + 1) // 2)
+        masks = np.empty((B, oh, ow), np.uint8) if mask else None
+
+        def plane():
+            rows, totals, links = np.zeros(cap, _lib.LESION_ROW_DTYPE), np.zeros(B, np.int32), np.zeros(lcap, _lib.LESION_LINK_DTYPE)
+            out = _lib.LesionPlaneOut(rows.ctypes.data_as(C.POINTER(_lib.LesionRow)), cap, 0, totals.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      links.ctypes.data_as(C.POINTER(_lib.LesionLink)), lcap, 0)
+            return rows, totals, links, out
+        rows, totals, links, pred = plane()
+        true_rows, true_totals, true_links, truth = plane()
+        pairs = np.zeros(lcap, _lib.LESION_PAIR_DTYPE)
+        po = _lib.LesionPairsOut(pairs.ctypes.data_as(C.POINTER(_lib.LesionPair)), lcap, 0)
+        check(self.lib.dnnca_lesion_table_matched(*args, C.byref(pred), masks.ctypes.data_as(C.c_void_p) if mask else None,
+                                                  masks.nbytes if mask else 0, C.byref(truth), C.byref(po), hw))
+        return (rows[:pred.n_rows].copy(), totals, masks, links[:pred.n_links].copy(), true_rows[:truth.n_rows].copy(), true_totals,
+                true_links[:truth.n_links].copy(), pairs[:po.n_pairs].copy())
+
     def input_sensitivity(self, x=None, batch=None):
         """float64 [B, C]: sum over the image of |d sum(prob of slice b) / d x[b, :, :, c]| in inference mode (the raw sums of the
         reference's sensitivity map; casewise.normalise_sensitivity divides each row by its sum).  x [B, H, W, C], or None with
@@ -696,13 +754,14 @@ class DeviceModel:
             out.append((name.value.decode(), n.value, ms.value, by.value, fl.value))
         return out
 
-    PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3, 'lesion': 4, 'lesion_linked': 5}
+    PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3, 'lesion': 4, 'lesion_linked': 5, 'lesion_matched': 6}
 
     def plan(self, variants=False, mode='train', batch=None):
         """The launch schedule of one pass: [(kernel, algorithmic bytes, flops)].  mode 'train': one train step; 'eval': one
         eval_step (inference forward + loss; a staged evaluation step launches the same); 'forward': forward(training=False);
         'sensitivity': input_sensitivity; 'lesion': lesion_table on the last forward's probabilities, with the resize factor,
-        filter size and mask choice of the last lesion_table / lesion_table_linked call; 'lesion_linked': lesion_table_linked likewise.
+        filter size and mask choice of the last lesion_table / lesion_table_linked call; 'lesion_linked': lesion_table_linked likewise;
+        'lesion_matched': lesion_table_matched with the three values of the last lesion_table_matched call.
         batch: None = max_batch.  variants: keep the template variant the library appends to a launch name
         (`ig_conv_fwd#3n2w8`): the kernel-coverage test tells them apart.  A dry run: the model is unchanged."""
         if mode not in self.PLAN_PASSES:

@@ -546,7 +546,11 @@ class TFKerasModel:
 
     def eval(self, dataset, save_path, viz_ds=None, tag='val', avoid_overwrite=False, export_path=None, export_images=False,
              visualize_sensitivity=False, export_csv=False, min_interval=1, step_range=None, overlay=False,
-             export_casewise_metrics=False):
+             export_casewise_metrics=False, exam_ds=None, exam_lesions=False, exam_threshold=(0.5,), exam_iou=casewise.EXAM_IOU,
+             exam_min_area=0, exam_filter_size=5, exam_resize_factor=1.0, exam_max_lesions=256, exam_link_min_overlap=1):
+        """exam_lesions (`evaluate --exam_lesions`): after every checkpoint's evaluation rank 0 also runs _exam_lesion_pass over
+        exam_ds (batches (x, y, paths, sliceIDs), a data set of its own: viz_ds is not needed) and writes exam_lesion_results.csv,
+        exam_lesion_cases.csv and exam_lesion_matches.csv under <export_path>/<tag>/; every other file is what it is without it."""
         if visualize_sensitivity and not getattr(self.model, 'supports_sensitivity', True):
             raise NotImplementedError('--visualize_sensitivity is not implemented for model: %s (the input-gradient pass covers the '
                                       'U-Net models only)' % self.model_config['model'])
@@ -571,6 +575,8 @@ class TFKerasModel:
         viz_root = os.path.join(export_path, tag)
         casewise_rows = []
         writer = casewise.Writer() if visualize else None
+        exam_pass = bool(exam_lesions) and exam_ds is not None and self.ctx.rank == 0
+        exam_tables = [], [], []         # the lines of the three exam_lesion_*.csv files
         rows = OrderedDict()
         previous_step = None
         for ckpt_step, ckpt_path_ in self.get_ckpts(ckpt_path).items():
@@ -585,6 +591,19 @@ class TFKerasModel:
             if visualize:
                 self._visualize(viz_ds, ckpt_step, viz_root, export_csv, export_images, overlay, casewise_rows, writer,
                                 sensitivity=bool(visualize_sensitivity))
+            if exam_pass:
+                for t, new in zip(exam_tables, self._exam_lesion_pass(
+                        exam_ds, ckpt_step, [float(t) for t in exam_threshold], exam_iou, exam_link_min_overlap,
+                        dict(resize_factor=exam_resize_factor, filter_size=exam_filter_size, min_area=exam_min_area,
+                             max_lesions=exam_max_lesions))):
+                    t += new
+        if exam_pass:
+            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
+            for name, cols, table in zip(('exam_lesion_results.csv', 'exam_lesion_cases.csv', 'exam_lesion_matches.csv'),
+                                         (casewise.EXAM_RESULT_COLUMNS, casewise.EXAM_CASE_COLUMNS, casewise.EXAM_MATCH_COLUMNS),
+                                         exam_tables):
+                with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
+                    f.write(casewise.plain_csv(['step', 'threshold'] + cols, table))
         if writer is not None:
             writer.close()
         if export_csv and self.ctx.rank == 0:
@@ -637,6 +656,69 @@ class TFKerasModel:
                         if export_images:
                             writer.submit(casewise.sensitivity_path(root, t, step, 'images'),
                                           lambda r: casewise.encode_png(casewise.sensitivity_chart(r)), row)
+
+    def _exam_lesion_pass(self, ds, step, thresholds, iou, min_overlap, kw):
+        """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --exam_lesions`: per max_batch split one forward whose
+        probabilities stay on the device and one DeviceModel.lesion_table_matched per threshold; then per threshold and exam
+        casewise.link_lesions on either plane and casewise.match_exam_lesions.  Returns the new lines of (exam_lesion_results.csv,
+        exam_lesion_cases.csv, exam_lesion_matches.csv), each led by step and threshold.
+        A slice continues the one before it by annotate's rule: the same exam path and the next slice number, across splits and
+        batches.  continues[0] of a matched call refers to the model's last matched call, which with several thresholds was
+        another threshold's: the call is then led by a one-slice call that puts this threshold's rows of the slice before back
+        (its probabilities and labels are kept on the host for that; a single threshold needs neither)."""
+        several = len(thresholds) > 1
+        found = [[] for _ in thresholds]     # per threshold and slice: (exam, slice, rows, total, links, true rows, total, links, pairs)
+        dm, last, tail, carry_of = None, None, None, None
+        for x, y, paths, ids in ds:
+            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
+            if not len(x):
+                continue
+            self._ensure_capacity(len(x))
+            if last is not None and dm is not self.device_model:
+                # the row numbers of the slice before stayed behind on the model this batch outgrew: the chain breaks here
+                logging.warning('evaluate: the model was re-sized before slice %s of %s: it is not linked to the slice before', ids[0], paths[0])
+                last = None
+            dm = self.device_model
+            for i in range(0, len(x), dm.max_batch):
+                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
+                pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
+                dm.forward(xb, training=False, return_prob=False)
+                continues = []
+                for p, k in pk:
+                    continues.append(last is not None and p == last[0] and int(k) == last[1] + 1)
+                    last = (p, int(k))
+                for ti, thr in enumerate(thresholds):
+                    if continues[0] and carry_of != ti:
+                        dm.lesion_table_matched(tail[1], prob=tail[0], continues=[False], threshold=thr, **kw)
+                    out = dm.lesion_table_matched(yb, batch=len(xb), continues=continues, threshold=thr, **kw)
+                    carry_of = ti
+                    by_slice = [[o[o['slice'] == b] for b in range(len(xb))] for o in (out[0], out[3], out[4], out[6], out[7])]
+                    for b, (p, k) in enumerate(pk):
+                        rows, links, true_rows, true_links, pairs = [s[b] for s in by_slice]
+                        found[ti].append((p, int(k), rows, out[1][b], [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in links],
+                                          true_rows, out[5][b],
+                                          [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in true_links],
+                                          [(int(q['row_true']), int(q['row']), int(q['overlap'])) for q in pairs]))
+                if several:
+                    tail = dm.last_prob(len(xb))[-1:], yb[-1:].reshape(1, *yb.shape[1:3])
+        results, cases, matches = [], [], []
+        for thr, mine in zip(thresholds, found):
+            lead = [int(step), repr(thr)]
+            exams = OrderedDict()            # exam path -> its slices, in the order of the data set
+            for rec in mine:
+                exams.setdefault(rec[0], []).append(rec)
+            mine_cases = []
+            for exam, recs in exams.items():
+                pred_slices, true_slices = [r[1:4] for r in recs], [(r[1], r[5], r[6]) for r in recs]
+                pred_linked = casewise.link_lesions(exam, pred_slices, [r[4] for r in recs], min_overlap=min_overlap)
+                true_linked = casewise.link_lesions(exam, true_slices, [r[7] for r in recs], min_overlap=min_overlap)
+                case, lines = casewise.match_exam_lesions(exam, true_slices, pred_slices, true_linked, pred_linked, [r[8] for r in recs],
+                                                          iou=iou)
+                mine_cases.append(case)
+                matches += [lead + l for l in lines]
+            cases += [lead + c for c in mine_cases]
+            results.append(lead + casewise.exam_match_summary(mine_cases))
+        return results, cases, matches
 
     def predict(self, dataset):
         """Probabilities [N, H, W, 1] for every element of `dataset` (elements are x or (x, ...))."""

@@ -8,7 +8,8 @@ from .train import make_dataset
 
 def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, export_path=None, export_images=False,
              export_csv=False, visualize_sensitivity=False, min_interval=1, step_range=None, overlay=False,
-             skip_visualization=False, export_casewise_metrics=False):
+             skip_visualization=False, export_casewise_metrics=False, exam_lesions=False, exam_threshold=(0.5,), exam_iou=0.30,
+             exam_min_area=0, exam_filter_size=5, exam_resize_factor=1.0, exam_max_lesions=256, exam_link_min_overlap=1):
     saved_config = load.load_config(os.path.join(save_path, 'options.yaml'))['config']
     if config:
         config = load._apply_config(saved_config, load.load_config(config))
@@ -18,8 +19,15 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
     # the Visualizer's data set (runs/evaluate.py:72-73 of the reference): the same slices with their exam path and sliceID
     viz_ds = None if skip_visualization else make_dataset(data_path, config.get('data_options', {}).get('eval', {}), training=False,
                                                           include_meta=True)
+    # --exam_lesions has a data set of its own (the slices with their labels, exam path and sliceID): --skip_visualization does
+    # not touch it
+    exam_ds = make_dataset(data_path, config.get('data_options', {}).get('eval', {}), training=False, include_meta=True) \
+        if exam_lesions else None
     model = engine.TFKerasModel(config)
     return model.eval(ds, viz_ds=viz_ds, tag=tag, save_path=os.path.join(save_path), avoid_overwrite=avoid_overwrite,
                       export_path=export_path, export_images=export_images, export_csv=export_csv,
                       visualize_sensitivity=visualize_sensitivity, min_interval=min_interval, step_range=step_range,
-                      overlay=overlay, export_casewise_metrics=export_casewise_metrics)
+                      overlay=overlay, export_casewise_metrics=export_casewise_metrics, exam_ds=exam_ds, exam_lesions=exam_lesions,
+                      exam_threshold=exam_threshold, exam_iou=exam_iou, exam_min_area=exam_min_area, exam_filter_size=exam_filter_size,
+                      exam_resize_factor=exam_resize_factor, exam_max_lesions=exam_max_lesions,
+                      exam_link_min_overlap=exam_link_min_overlap)

@@ -336,6 +336,48 @@ int dnnca_lesion_table_linked(void* model, const float* prob_hw, int batch, int 
                               int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw,
                               const uint8_t* continues, dnnca_lesion_link* links, int64_t links_capacity, int64_t* n_links);
 
+/* ---- both planes at once: predicted and labelled lesions and their common pixels (`annotator evaluate --exam_lesions`) ----------
+ * prob_hw (NULL: the last forward's probabilities) and every argument from batch to continues mean what they mean for
+ * dnnca_lesion_table_linked; `pred` (rows, totals, links), `mask` and out_hw receive bit for bit what that call writes.
+ * y_hw: the labels, host [batch, h, w], required.  The label plane is resized by the same resize_factor; foreground is
+ * y' > 0.5 (utils/metrics.py:125), there is no opening and no area filter; its 4-connected components are numbered in the same
+ * way under the same max_lesions.  `truth` receives their rows (the sums and the maximum taken on y'), totals and the links
+ * between neighbouring slices under the same continues flags -- what dnnca_lesion_table_linked gives for y_hw with threshold
+ * nextafterf(0.5, 1), filter_size 1 and min_area 0.
+ * pairs: for every slice, whatever its flag, and every pair of a labelled lesion (row_true) and a predicted lesion (row) of that
+ * slice that share pixels, one entry with the number of common pixels, sorted by (slice, row_true, row); lesions beyond
+ * max_lesions or below min_area pair with nothing.
+ * A plane group carries the caller's buffers and their capacities in, and the counts out: rows_capacity at least batch * cap,
+ * links_capacity and pairs->capacity at least batch * min(cap * cap, (oh * ow + 1) / 2), cap = min(max_lesions, (oh * ow + 1) / 2).
+ * pred == NULL or pred->rows == NULL only queries out_hw.
+ * continues[0] refers to the last slice of the previous successful dnnca_lesion_table_matched call on this model: the call keeps
+ * the row numbers of both planes of its last slice on the device.  It neither reads nor writes what dnnca_lesion_table_linked
+ * keeps, and that call neither reads nor writes this.
+ * DNNCA_EINVAL, with nothing launched and both kept planes untouched: everything dnnca_lesion_table_linked refuses, y_hw ==
+ * NULL, truth == NULL or pairs == NULL or one of their buffers NULL, one of the three new capacities too small, continues[0] set
+ * while no matched call has succeeded on this model or the last one analysed planes of another oh x ow.
+ * Variables, state and the probabilities of the last forward are untouched.  Every output is an integer or an extremum:
+ * bit-identical from run to run.  Synchronises. */
+typedef struct dnnca_lesion_pair { int32_t slice, row_true, row, overlap; } dnnca_lesion_pair;   /* 16 bytes */
+typedef struct dnnca_lesion_plane_out {
+    dnnca_lesion_row* rows;      /* in: host buffer of rows_capacity records */
+    int64_t rows_capacity;
+    int64_t n_rows;              /* out */
+    int32_t* totals;             /* in: host [batch] */
+    dnnca_lesion_link* links;    /* in: host buffer of links_capacity records */
+    int64_t links_capacity;
+    int64_t n_links;             /* out */
+} dnnca_lesion_plane_out;
+typedef struct dnnca_lesion_pairs_out {
+    dnnca_lesion_pair* pairs;    /* in: host buffer of `capacity` records */
+    int64_t capacity;
+    int64_t n_pairs;             /* out */
+} dnnca_lesion_pairs_out;
+int dnnca_lesion_table_matched(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w, float threshold,
+                               float resize_factor, int filter_size, int min_area, int max_lesions, const uint8_t* continues,
+                               dnnca_lesion_plane_out* pred, uint8_t* mask, int64_t mask_capacity, dnnca_lesion_plane_out* truth,
+                               dnnca_lesion_pairs_out* pairs, int32_t* out_hw);
+
 /* ---- channel sensitivity of `annotator evaluate --visualize_sensitivity` (utils/callbacks.py:290-313) ---------------------------
  * With the model in inference mode (BatchNorm on its moving statistics, sigmoid output):
  *     sums[b * in_channels + c] = sum over H, W of | d (sum of all probabilities of slice b) / d x[b, h, w, c] |
@@ -379,10 +421,11 @@ int dnnca_plan_dump(void* model, char* buf, size_t cap);
    step (dnnca_eval_step / dnnca_eval_step_staged: inference forward + loss), or a prediction (dnnca_forward with training = 0:
    inference forward + sigmoid), or dnnca_input_sensitivity, or dnnca_lesion_table on the last forward's probabilities with the
    resize factor, filter size and mask choice of the last dnnca_lesion_table / dnnca_lesion_table_linked call (before any: 1.0, 5,
-   with mask), or dnnca_lesion_table_linked with the same three values.  A dry run: nothing is launched and the model is left as
+   with mask), or dnnca_lesion_table_linked with the same three values, or dnnca_lesion_table_matched with the three values of the
+   last dnnca_lesion_table_matched call (before any: the same defaults).  A dry run: nothing is launched and the model is left as
    it was. */
 enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2, DNNCA_PLAN_SENSITIVITY = 3, DNNCA_PLAN_LESION = 4,
-       DNNCA_PLAN_LESION_LINKED = 5 };
+       DNNCA_PLAN_LESION_LINKED = 5, DNNCA_PLAN_LESION_MATCHED = 6 };
 int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap);
 
 #ifdef __cplusplus

@@ -9,10 +9,16 @@ and prediction plane) plus pairs, match and count.
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --yardstick      # the yardstick alone
     python tools/lesion_rate.py --link              # also: lesion_table_linked, annotate(link_slices=True), the pair table's worst case
     DNNCA_LIB=<a library from before the links> python tools/lesion_rate.py                         # the unlinked legs on it
+    python tools/lesion_rate.py --link --match      # also: lesion_table_matched against lesion_table_linked
+    DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --link            # the linked legs on it
 
 --link adds the cost of linking neighbouring slices: lesion_table_linked against lesion_table (wall time per call, device time of
 the three link launches), its worst case for the pair table (a checkerboard on itself: every other pixel a lesion of its own in
 both slices, (hw + 1) / 2 keys per slice) and `annotate` with link_slices.
+
+--match adds the cost of `evaluate --exam_lesions`: lesion_table_matched (both planes, three sets of pair tables) against
+lesion_table_linked on the same probabilities, and passes over the data set in the manner of `annotate` -- a forward and one call
+per batch, the flags from the slice numbers -- with the linked and the matched call alternated in one process.
 
 The probabilities are drawn: the synthetic labels' discs at 0.55 .. 0.95 on a background of 0 .. 0.45 (a few lesions per slice,
 as a trained model gives), put into the model's probability buffer by pixel_confusion_of."""
@@ -33,12 +39,18 @@ ap.add_argument('--reps', type=int, default=20)
 ap.add_argument('--batches', type=int, default=8)
 ap.add_argument('--yardstick', action='store_true', help='region_confusion_slices alone (also on a library without the lesion table)')
 ap.add_argument('--link', action='store_true', help='also measure lesion_table_linked and annotate(link_slices=True)')
+ap.add_argument('--match', action='store_true', help='also measure lesion_table_matched against lesion_table_linked (needs --link)')
 ap.add_argument('--out', default=None, help='append the report to this file as well')
 a = ap.parse_args()
 if a.yardstick:
     _lib.SIGNATURES.pop('dnnca_lesion_table', None)              # a library built from the parent does not export it
 if not a.link:
     _lib.SIGNATURES.pop('dnnca_lesion_table_linked', None)       # nor does one from before the links
+
+if a.match and not a.link:
+    ap.error('--match needs --link')
+if not a.match:
+    _lib.SIGNATURES.pop('dnnca_lesion_table_matched', None)      # nor does one from before the matched call
 
 from dnncancerannotator_amd import device as dev                  # noqa: E402
 from dnncancerannotator_amd.data import ArrayDataset              # noqa: E402
@@ -128,6 +140,37 @@ if not a.yardstick:
         say('  lesion_table_linked, checkerboard on itself: %.3f ms per call (median; %.3f .. %.3f)' % (med, lo, hi))
         say('    %d links between %d slices' % (len(dm.lesion_table_linked(continues=flags, **wkw)[3]), B))
         per_launch(dm, lambda: dm.lesion_table_linked(continues=flags, **wkw), ('lesion_link', 'lesion_carry'))
+    if a.match:
+        dm.pixel_confusion_of(prob, y, [0.5])
+        flags = [b > 0 for b in range(B)]
+        kw = dict(batch=B, threshold=0.5, filter_size=5)
+        med, lo, hi = wall(lambda: dm.lesion_table_matched(y, continues=flags, **kw))
+        say('  lesion_table_matched(mask=False): %.3f ms per call (median of %d; %.3f .. %.3f)' % (med, R, lo, hi))
+        out = dm.lesion_table_matched(y, continues=flags, **kw)
+        say('    %d predicted and %d labelled lesions, %d / %d links, %d pairs in %d slices' % (len(out[0]), len(out[4]), len(out[3]),
+                                                                                             len(out[6]), len(out[7]), B))
+        per_launch(dm, lambda: dm.lesion_table_matched(y, continues=flags, **kw), ('region_', 'lesion_'))
+        ys = np.concatenate([y] * NB)
+
+        def one_pass(matched):
+            """a forward and one call per batch; slice b of batch i is slice i * B + b of one exam"""
+            t0 = time.perf_counter()
+            for i, (xb, _, _) in enumerate(ds):
+                dm.forward(xb, return_prob=False)
+                cont = [i > 0 or b > 0 for b in range(len(xb))]
+                if matched:
+                    dm.lesion_table_matched(ys[i * B:i * B + len(xb)], batch=len(xb), continues=cont, threshold=0.5, filter_size=5)
+                else:
+                    dm.lesion_table_linked(batch=len(xb), continues=cont, threshold=0.5, filter_size=5, mask=False)
+            return time.perf_counter() - t0
+        one_pass(False), one_pass(True)                           # warm-up: both carries, the larger workspace
+        took = {False: [], True: []}
+        for i in range(8):
+            took[bool(i % 2)].append(one_pass(bool(i % 2)))
+            say('  %-34s %9.1f slices/s  (%.2f ms per batch)' % ('forward + ' + ('matched' if i % 2 else 'linked') + ' pass',
+                                                                 B * NB / took[bool(i % 2)][-1], took[bool(i % 2)][-1] / NB * 1e3))
+        mt, lk = sorted(took[True])[len(took[True]) // 2], sorted(took[False])[len(took[False]) // 2]
+        say('  matched / linked pass (medians of 4, alternated): %.3f' % (mt / lk))
     for xb, _, _ in ds:
         dm.forward(xb, return_prob=False)
     t0 = time.perf_counter()
