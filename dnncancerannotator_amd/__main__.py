@@ -58,6 +58,19 @@ def build_parser(prog='python3 -m annotator'):
     e.add_argument('--exam_max_lesions', type=_at_least_one, default=argparse.SUPPRESS, help='lesions per slice and plane (default: 256)')
     e.add_argument('--exam_link_min_overlap', type=_at_least_one, default=argparse.SUPPRESS,
                    help='common pixels that join two lesions of neighbouring slices (default: 1)')
+    e.add_argument('--surface_distances', action='store_true', default=argparse.SUPPRESS,
+                   help='measure the predicted outline against the labelled one (Hausdorff, its percentile, ASSD, Dice): also write '
+                        'surface_results.csv, surface_cases.csv and surface_slices.csv')
+    e.add_argument('--surface_threshold', type=float, nargs='+', default=argparse.SUPPRESS, metavar='T',
+                   help='probability threshold(s) of --surface_distances (default: 0.5)')
+    e.add_argument('--surface_percentile', type=float, default=argparse.SUPPRESS, help='percentile of the distances reported beside '
+                   'the largest (default: 95)')
+    e.add_argument('--surface_min_area', type=int, default=argparse.SUPPRESS, help='smallest predicted lesion kept per slice (default: 0)')
+    e.add_argument('--surface_filter_size', type=int, default=argparse.SUPPRESS, help='opening of the prediction, 1..15 (default: 5)')
+    e.add_argument('--surface_resize_factor', type=float, default=argparse.SUPPRESS,
+                   help='analyse probabilities and labels resized by this factor (default: 1.0)')
+    e.add_argument('--surface_max_samples', type=_at_least_one, default=argparse.SUPPRESS,
+                   help='boundary pixels per slice and side; a slice with more reports no distance (default: 65536)')
     p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
     p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
     p.add_argument('--data_path', nargs='+', required=True)

@@ -89,6 +89,14 @@ class LesionPair(C.Structure):                     # dnnca_lesion_pair (16 bytes
 LESION_PAIR_DTYPE = np.dtype([('slice', '<i4'), ('row_true', '<i4'), ('row', '<i4'), ('overlap', '<i4')])
 
 
+class SurfaceSample(C.Structure):                  # dnnca_surface_sample (16 bytes)
+    _fields_ = [('slice', C.c_int32), ('side', C.c_int32), ('pixel', C.c_int32), ('d2', C.c_int32)]
+
+
+# DeviceModel.surface_distances returns its samples as a structured array of this dtype
+SURFACE_SAMPLE_DTYPE = np.dtype([('slice', '<i4'), ('side', '<i4'), ('pixel', '<i4'), ('d2', '<i4')])
+
+
 class LesionPlaneOut(C.Structure):                 # dnnca_lesion_plane_out: buffers and capacities in, counts out
     _fields_ = [('rows', C.POINTER(LesionRow)), ('rows_capacity', C.c_int64), ('n_rows', C.c_int64), ('totals', C.POINTER(C.c_int32)),
                 ('links', C.POINTER(LesionLink)), ('links_capacity', C.c_int64), ('n_links', C.c_int64)]
@@ -171,6 +179,9 @@ SIGNATURES = {
     'dnnca_lesion_table_matched': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                              C.POINTER(C.c_uint8), C.POINTER(LesionPlaneOut), _VP, C.c_int64, C.POINTER(LesionPlaneOut),
                                              C.POINTER(LesionPairsOut), C.POINTER(C.c_int32)]),
+    'dnnca_surface_distances': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_int32), C.POINTER(SurfaceSample), C.c_int64, C.POINTER(C.c_int64), _VP, C.c_int64,
+                                          C.POINTER(C.c_int32)]),
     'dnnca_input_sensitivity': (C.c_int, [_VP, _FP, C.c_int, C.POINTER(C.c_double)]),
     'dnnca_comm_unique_id': (C.c_int, [_VP]),
     'dnnca_comm_init': (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_size_t]),

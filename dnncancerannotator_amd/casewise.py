@@ -332,6 +332,80 @@ def exam_match_summary(cases):
                                repr(n[5] / len(cases) if cases else 0.0)]
 
 
+# ---- `annotator evaluate --surface_distances`: how far the predicted outline lies from the labelled one ----------------------------
+# DeviceModel.surface_distances gives, per boundary pixel of either mask, the exact squared distance to the nearest boundary pixel of
+# the other mask; everything here is float64 from those integers, d = sqrt(d2).  Distances are in pixels of the analysed plane and
+# in-plane: slices have no spacing.
+SURFACE_STATUSES = ['both', 'pred_only', 'label_only', 'neither', 'truncated']
+SURFACE_SLICE_COLUMNS = ['exam', 'slice', 'status', 'area_pred', 'area_true', 'common', 'edge_pred', 'edge_true', 'dice', 'hd',
+                         'hd_percentile', 'assd']
+SURFACE_CASE_COLUMNS = ['exam', 'slices'] + SURFACE_STATUSES + ['hd', 'hd_percentile', 'assd']
+SURFACE_RESULT_COLUMNS = ['slices'] + SURFACE_STATUSES + ['exams', 'dice', 'hd', 'hd_percentile', 'assd', 'exam_hd',
+                                                           'exam_hd_percentile', 'exam_assd']
+SURFACE_PERCENTILE = 95.0
+
+
+def surface_distance_values(d2_pred, d2_true, percentile=SURFACE_PERCENTILE):
+    """squared distances of the prediction's and of the label's boundary pixels (both non-empty) -> (hd, hd_percentile, assd) as
+    float64: the largest d of either side, numpy.percentile (linear interpolation) over the d of both sides concatenated, the mean
+    of the two sides' mean d"""
+    dp, dt = np.sqrt(np.asarray(d2_pred, np.float64)), np.sqrt(np.asarray(d2_true, np.float64))
+    if not (dp.size and dt.size):
+        raise ValueError('surface distances need samples of both sides, got %d and %d' % (dp.size, dt.size))
+    both = np.concatenate([dp, dt])
+    return float(both.max()), float(np.percentile(both, float(percentile))), float((dp.mean() + dt.mean()) / 2.0)
+
+
+def surface_status(counts, n_pred, n_true):
+    """counts (area_pred, area_true, common, edge_pred, edge_true) of one slice and the samples that came back for either side ->
+    its status.  A slice with both outlines and no samples was cut by max_samples"""
+    edge_pred, edge_true = int(counts[3]), int(counts[4])
+    if edge_pred > 0 and edge_true > 0:
+        if n_pred == 0 and n_true == 0:
+            return 'truncated'
+        if (n_pred, n_true) != (edge_pred, edge_true):
+            raise ValueError('surface distances: %d / %d samples for %d / %d boundary pixels' % (n_pred, n_true, edge_pred, edge_true))
+        return 'both'
+    if n_pred or n_true:
+        raise ValueError('surface distances: samples of a slice with an empty outline')
+    return 'pred_only' if edge_pred > 0 else 'label_only' if edge_true > 0 else 'neither'
+
+
+def surface_slice_values(exam, slice_id, counts, d2_pred, d2_true, percentile=SURFACE_PERCENTILE):
+    """the surface_slices.csv values of one slice (SURFACE_SLICE_COLUMNS).  dice = 2 common / (area_pred + area_true), blank when
+    both masks are empty; hd, hd_percentile and assd (surface_distance_values) are blank unless the status is `both`.  Floats are
+    written with repr"""
+    status = surface_status(counts, len(d2_pred), len(d2_true))
+    total = int(counts[0]) + int(counts[1])
+    dice = repr(2 * int(counts[2]) / total) if total else ''
+    dist = [repr(v) for v in surface_distance_values(d2_pred, d2_true, percentile)] if status == 'both' else ['', '', '']
+    return [exam, int(slice_id), status] + [int(c) for c in counts[:5]] + [dice] + dist
+
+
+def surface_exam_values(exam, slices, percentile=SURFACE_PERCENTILE):
+    """the surface_cases.csv values of one exam (SURFACE_CASE_COLUMNS).  slices: [(counts, d2_pred, d2_true)] of the exam's slices;
+    the samples of its `both` slices are pooled per side and go through surface_distance_values; blank without such a slice"""
+    status = [surface_status(c, len(p), len(t)) for c, p, t in slices]
+    pooled = [[np.asarray(sl[side], np.int64) for sl, st in zip(slices, status) if st == 'both'] for side in (1, 2)]
+    dist = ['', '', '']
+    if pooled[0]:
+        dist = [repr(v) for v in surface_distance_values(np.concatenate(pooled[0]), np.concatenate(pooled[1]), percentile)]
+    return [exam, len(slices)] + [status.count(s) for s in SURFACE_STATUSES] + dist
+
+
+def surface_summary(slice_values, exam_values):
+    """the SURFACE_SLICE_COLUMNS values of every slice and the SURFACE_CASE_COLUMNS values of every exam -> the
+    SURFACE_RESULT_COLUMNS values: the slice counts per status, the exams that have a `both` slice, the means of dice, hd,
+    hd_percentile and assd over the `both` slices and of the three per-exam distances over those exams (blank without any)"""
+    def mean(values):
+        values = [float(v) for v in values]
+        return repr(float(np.mean(np.asarray(values, np.float64)))) if values else ''
+    both = [v for v in slice_values if v[2] == 'both']
+    exams = [v for v in exam_values if v[-1] != '']
+    return ([len(slice_values)] + [sum(1 for v in slice_values if v[2] == s) for s in SURFACE_STATUSES] + [len(exams)] +
+            [mean(v[i] for v in both) for i in (8, 9, 10, 11)] + [mean(v[i] for v in exams) for i in (-3, -2, -1)])
+
+
 def plain_csv(names, rows):
     """a header line and one line per row, csv-module quoting, no index column"""
     return _csv([list(names)] + [list(r) for r in rows])

@@ -23,6 +23,10 @@
 //   region_render   [features | label | probability] panels side by side, resized bilinear by `ratio` (the same float32 arithmetic
 //                   as region_prep), * 255 truncated to uint8; the panels are read in place through an index map, four output
 //                   bytes per thread and one 32-bit store
+//
+// The lesion table of `annotator predict` (lesion_scan / lesion_stats / lesion_mask), its links and pairs (lesion_link, lesion_match)
+// and the boundary distances of `evaluate --surface_distances` (surface_edges / surface_cols / surface_sample) start from the same
+// prep / open / ccl / sizes launches; each is described above its kernels.
 #include <math.h>
 #include <string.h>
 
@@ -707,6 +711,166 @@ __global__ __launch_bounds__(RB) void k_lesion_match_carry(const int* __restrict
     else carryT[p] = lesion_row_at(LT, rowT, g0 + p, cap);
 }
 
+// ---- boundary distances (dnnca_surface_distances).  Side 0 is the prediction mask -- the mask of the lesion table: a foreground
+// pixel of the opened words whose component has at least min_area pixels -- side 1 the label foreground (bit 0 of its words).
+// A boundary pixel of a side is one of its pixels with a 4-neighbour off the side or off the plane.  A 4-neighbour that is
+// foreground lies in the pixel's own component and is kept or dropped with it, so the neighbours are read from the words alone.
+//   surface_edges   E[g] = bit 0: boundary of side 0, bit 1: boundary of side 1; counts[b] += {area_pred, area_true, common,
+//                   edge_pred, edge_true}: one block reduction, one atomic per block and counter.  Grid y = slice
+//   surface_cols    V[side][g] = rows between pixel g and the nearest boundary pixel of `side` in its column (kSurfaceFar: none):
+//                   one launch for both sides and all slices, a thread per column and 32 rows
+//   surface_sample  a boundary pixel (x, y) of side s takes d2 = min over x' of (x - x')^2 + V[1 - s][y][x']^2: the exact squared
+//                   distance to the nearest boundary pixel of the other side (the lower envelope of the row's parabolas, evaluated at
+//                   this pixel only).  It walks outward from x and stops where (x - x')^2 alone reaches the best so far.  The
+//                   samples of a wave take consecutive places of the list behind one atomic (the host sorts).  A slice whose edge
+//                   counts are 0 or above max_samples emits nothing: the counts are complete when this kernel starts
+// kSurfaceFar^2 + (ow - 1)^2 < 2^31 for planes of up to kSurfaceMaxSide pixels a side, and every real distance is below it.
+constexpr unsigned kSurfaceFar = 0x7fffu;
+
+struct SurfaceSample {                   // dnnca_surface_sample
+    int slice, side, pixel, d2;
+};
+static_assert(sizeof(SurfaceSample) == sizeof(dnnca_surface_sample), "the device list is copied into the caller's records");
+static_assert((long long)kSurfaceFar * kSurfaceFar + (long long)(kSurfaceMaxSide - 1) * (kSurfaceMaxSide - 1) < (1ll << 31) &&
+                  kSurfaceFar >= (unsigned)kSurfaceMaxSide,
+              "the sentinel's square plus any offset fits an int32 and no real distance reaches it");
+
+__global__ __launch_bounds__(RB) void k_surface_edges(const uint32_t* __restrict__ fg, const int* __restrict__ L,
+                                                      const unsigned* __restrict__ S, unsigned min_area,
+                                                      const uint32_t* __restrict__ yw, int H, int W, unsigned char* __restrict__ E,
+                                                      unsigned* __restrict__ counts) {
+    __shared__ unsigned part[RB / 64][5];
+    const int hw = H * W, p = (int)(blockIdx.x * RB + threadIdx.x);
+    const size_t g0 = (size_t)blockIdx.y * hw;
+    unsigned c[5] = {0u, 0u, 0u, 0u, 0u};
+    if (p < hw) {
+        const size_t g = g0 + p;
+        const int y = p / W, x = p - y * W;
+        const bool l = x > 0, r = x + 1 < W, u = y > 0, d = y + 1 < H;
+        unsigned pred = fg[g] & 1u;
+        if (pred) {
+            const int root = L[g];
+            pred = root >= 0 && S[root] >= min_area ? 1u : 0u;
+        }
+        const unsigned lab = yw[g] & 1u;
+        unsigned ep = 0, et = 0;
+        if (pred) ep = !(l && (fg[g - 1] & 1u) && r && (fg[g + 1] & 1u) && u && (fg[g - W] & 1u) && d && (fg[g + W] & 1u));
+        if (lab) et = !(l && (yw[g - 1] & 1u) && r && (yw[g + 1] & 1u) && u && (yw[g - W] & 1u) && d && (yw[g + W] & 1u));
+        E[g] = (unsigned char)(ep | (et << 1));
+        c[0] = pred, c[1] = lab, c[2] = pred & lab, c[3] = ep, c[4] = et;
+    }
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int j = 0; j < 5; ++j) {
+        const unsigned s = wave_sum(c[j]);
+        if (lane == 0) part[wv][j] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        unsigned s = 0;
+        for (int k = 0; k < RB / 64; ++k) s += part[k][threadIdx.x];
+        if (s) atomicAdd(counts + (size_t)blockIdx.y * 5 + threadIdx.x, s);
+    }
+}
+
+// a block takes kColsX columns of one side of one slice; thread (column, lane) takes the 32-row pieces lane, lane + kColsL, ... of its
+// column.  Pass 1 packs a piece's boundary bits into one word (32 independent loads) and leaves it in LDS; pass 2 finds the nearest
+// boundary row above and below the piece in the column's words and every row's distance with bit counts, in registers
+constexpr int kColsX = 16, kColsL = RB / kColsX;
+
+__global__ __launch_bounds__(RB) void k_surface_cols(const unsigned char* __restrict__ E, int nb, int H, int W,
+                                                     unsigned short* __restrict__ V) {
+    extern __shared__ uint32_t words[];  // [pieces][kColsX]
+    const int col = threadIdx.x & (kColsX - 1), lane = threadIdx.x / kColsX;
+    const int x = (int)blockIdx.x * kColsX + col, side = (int)(blockIdx.y & 1u), b = (int)(blockIdx.y >> 1);
+    const int pieces = (H + 31) / 32;
+    const size_t hw = (size_t)H * W, at = (size_t)b * hw + x;
+    const unsigned char* e = E + at;
+    unsigned short* v = V + (size_t)side * nb * hw + at;
+    for (int c = lane; c < pieces; c += kColsL) {
+        uint32_t m = 0;
+        if (x < W) {
+#pragma unroll
+            for (int j = 0; j < 32; ++j) {
+                const int y = c * 32 + j;
+                if (y < H) m |= (uint32_t)((e[(size_t)y * W] >> side) & 1u) << j;
+            }
+        }
+        words[c * kColsX + col] = m;
+    }
+    __syncthreads();
+    if (x >= W) return;
+    for (int c = lane; c < pieces; c += kColsL) {
+        const uint32_t m = words[c * kColsX + col];
+        int above = -1, below = -1;      // the nearest boundary row before and behind the piece
+        for (int cc = c - 1; cc >= 0; --cc) {
+            const uint32_t o = words[cc * kColsX + col];
+            if (o) { above = cc * 32 + 31 - __clz((int)o); break; }
+        }
+        for (int cc = c + 1; cc < pieces; ++cc) {
+            const uint32_t o = words[cc * kColsX + col];
+            if (o) { below = cc * 32 + __ffs((int)o) - 1; break; }
+        }
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            const int y = c * 32 + j;
+            if (y >= H) break;
+            const uint32_t upto = m & (0xffffffffu >> (31 - j)), from = m >> j;
+            const int yu = upto ? c * 32 + 31 - __clz((int)upto) : above;
+            const int yd = from ? y + __ffs((int)from) - 1 : below;
+            const unsigned du = yu >= 0 ? (unsigned)(y - yu) : kSurfaceFar, dd = yd >= 0 ? (unsigned)(yd - y) : kSurfaceFar;
+            v[(size_t)y * W] = (unsigned short)min(du, dd);
+        }
+    }
+}
+
+__global__ __launch_bounds__(RB) void k_surface_sample(const unsigned char* __restrict__ E, const unsigned short* __restrict__ V,
+                                                       const unsigned* __restrict__ counts, int nb, int H, int W, unsigned max_samples,
+                                                       int slice0, unsigned list_cap, SurfaceSample* __restrict__ list,
+                                                       unsigned* __restrict__ n_list) {
+    const int b = blockIdx.y, hw = H * W, p = (int)(blockIdx.x * RB + threadIdx.x);
+    const unsigned np = counts[(size_t)b * 5 + 3], nt = counts[(size_t)b * 5 + 4];
+    if (np == 0u || nt == 0u || np > max_samples || nt > max_samples) return;      // the whole block: its slice gives no samples
+    const size_t n = (size_t)nb * hw;
+    const unsigned bits = p < hw ? E[(size_t)b * hw + p] : 0u;
+    const unsigned long long bal0 = __ballot(bits & 1u), bal1 = __ballot(bits & 2u);
+    if (!(bal0 | bal1)) return;
+    int d2[2] = {0, 0};
+    if (bits) {
+        const int y = p / W, x = p - y * W;
+        const int reach = max(x, W - 1 - x);
+        for (int side = 0; side < 2; ++side) {
+            if (!((bits >> side) & 1u)) continue;
+            const unsigned short* row = V + (size_t)(1 - side) * n + (size_t)b * hw + (size_t)y * W;
+            int best = (int)row[x] * (int)row[x];
+            for (int dx = 1; dx <= reach && dx * dx < best; ++dx) {
+                if (x - dx >= 0) {
+                    const int v = row[x - dx];
+                    best = min(best, dx * dx + v * v);
+                }
+                if (x + dx < W) {
+                    const int v = row[x + dx];
+                    best = min(best, dx * dx + v * v);
+                }
+            }
+            d2[side] = best;
+        }
+    }
+    const int lane = threadIdx.x & 63, leader = __ffsll((long long)(bal0 | bal1)) - 1;
+    const unsigned n0 = (unsigned)__popcll(bal0);
+    unsigned base = 0;
+    if (lane == leader) base = atomicAdd(n_list, n0 + (unsigned)__popcll(bal1));
+    base = __shfl(base, leader);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (bits & 1u) {
+        const unsigned at = base + (unsigned)__popcll(bal0 & below);
+        if (at < list_cap) list[at] = SurfaceSample{slice0 + b, 0, p, d2[0]};
+    }
+    if (bits & 2u) {
+        const unsigned at = base + n0 + (unsigned)__popcll(bal1 & below);
+        if (at < list_cap) list[at] = SurfaceSample{slice0 + b, 1, p, d2[1]};
+    }
+}
+
 inline unsigned nblocks(size_t n) { return (unsigned)((n + RB - 1) / RB); }
 
 }  // namespace
@@ -749,6 +913,8 @@ struct RegionState {
     float match_rf = 1.f;
     int match_k = 5;
     bool match_mask = true;
+    float surface_rf = 1.f;              // the last dnnca_surface_distances: what DNNCA_PLAN_SURFACE replays
+    int surface_k = 5;
 };
 
 static constexpr size_t kRegionBudget = size_t(1) << 24;    // pixel-thresholds per chunk (~21 bytes each)
@@ -1426,6 +1592,124 @@ int lesion_table_matched(Model* M, const float* prob, const float* y, int batch,
     const LesionLinkIO io{continues, pred->links, &pred->n_links};
     const LesionMatchIO mo{y, truth->rows, &truth->n_rows, truth->totals, truth->links, &truth->n_links, pairs->pairs, &pairs->n_pairs};
     return lesion_run(M, prob, batch, h, w, a, pred->rows, &pred->n_rows, pred->totals, mask, want_mask, &io, &mo);
+}
+
+// ---- boundary distances ------------------------------------------------------------------------------------------------------
+struct SurfaceWs {                       // carve-up of the workspace for nb slices of hw pixels and `per` samples per slice and side
+    uint32_t *w0, *w1, *yw;
+    int* lp;
+    unsigned *sp, *counts, *n_list;
+    float *thr, *ythr;
+    unsigned char* edges;
+    unsigned short* cols;
+    SurfaceSample* list;
+    size_t bytes;
+};
+
+static SurfaceWs surface_layout(void* base, size_t nb, size_t hw, size_t per) {
+    const size_t n = nb * hw;
+    SurfaceWs w;
+    char* p = (char*)base;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += align256(bytes); return (void*)r; };
+    w.w0 = (uint32_t*)take(n * 4);
+    w.w1 = (uint32_t*)take(n * 4);
+    w.lp = (int*)take(n * 4);
+    w.sp = (unsigned*)take(n * 4);
+    w.yw = (uint32_t*)take(n * 4);
+    w.thr = (float*)take(4);
+    w.ythr = (float*)take(4);
+    w.edges = (unsigned char*)take(n);
+    w.cols = (unsigned short*)take(2 * n * 2);
+    w.counts = (unsigned*)take(nb * 5 * 4);
+    w.list = (SurfaceSample*)take(nb * 2 * per * sizeof(SurfaceSample));
+    w.n_list = (unsigned*)take(4);
+    w.bytes = off;
+    return w;
+}
+
+int surface_distances(Model* M, const float* prob, const float* y, int batch, int h, int w, const LesionArgs& a, int max_samples,
+                      int32_t* counts, dnnca_surface_sample* samples, int64_t* n_samples, uint8_t* edges) {
+    DN_TRY(region_state(M));
+    RegionState& R = *M->region;
+    R.surface_rf = a.rf;
+    R.surface_k = a.k;
+    const int oh = a.oh, ow = a.ow;
+    const size_t hw = (size_t)oh * ow, per = std::min<size_t>((size_t)max_samples, hw);
+    const int chunk = (int)region_chunk(3, hw, batch);       // two word planes, the column planes and the list: a matched chunk's room
+    if (!M->dry) DN_TRY(region_ws_reserve(R, surface_layout(nullptr, chunk, hw, per).bytes));
+    hipStream_t s = M->stream;
+    std::vector<SurfaceSample> found;
+    int64_t out = 0;
+    Resize rz{h, w, oh, ow, (float)h / (float)oh, (float)w / (float)ow, (oh == h && ow == w) ? 1 : 0};
+    for (int b0 = 0; b0 < batch; b0 += chunk) {
+        const int nb = std::min(chunk, batch - b0);
+        const size_t n = (size_t)nb * hw, list_cap = (size_t)nb * 2 * per;
+        const SurfaceWs ws = surface_layout(R.ws, nb, hw, per);
+        const float* pb = prob + (size_t)b0 * h * w;
+        const float* yb = y + (size_t)b0 * h * w;
+        if (!M->dry) {
+            HIP_TRY(hipMemcpyAsync(ws.thr, &a.threshold, 4, hipMemcpyHostToDevice, s));       // `a` outlives the chunk's sync
+            HIP_TRY(hipMemcpyAsync(ws.ythr, &kLabelThreshold, 4, hipMemcpyHostToDevice, s));
+        }
+        LAUNCH(M, "region_prep", n * 4.0 + (double)nb * h * w * 4, 0,
+               hipLaunchKernelGGL(k_region_prep, dim3(nblocks(n)), dim3(RB), 0, s, pb, rz, nb, (const float*)ws.thr, 1, ws.w0));
+        const uint32_t* fg = ws.w0;
+        if (a.k > 1) {
+            const dim3 tiles((ow + kTile - 1) / kTile, (oh + kTile - 1) / kTile, nb);
+            LAUNCH(M, "region_open", n * 8.0, 0,
+                   hipLaunchKernelGGL(k_region_open, tiles, dim3(RB), 0, s, ws.w0, ws.w1, oh, ow, a.k, n, nb));
+            fg = ws.w1;
+        }
+        region_ccl(M, fg, 1, nb, oh, ow, ws.lp);
+        if (!M->dry) {
+            HIP_TRY(hipMemsetAsync(ws.sp, 0, n * 4, s));
+            HIP_TRY(hipMemsetAsync(ws.counts, 0, (size_t)nb * 5 * 4, s));
+            HIP_TRY(hipMemsetAsync(ws.n_list, 0, 4, s));
+        }
+        LAUNCH(M, "region_sizes", n * 4.0, 0, hipLaunchKernelGGL(k_region_sizes, dim3(nblocks(n)), dim3(RB), 0, s, ws.lp, n, ws.sp));
+        LAUNCH(M, "region_prep", n * 4.0 + (double)nb * h * w * 4, 0,
+               hipLaunchKernelGGL(k_region_prep, dim3(nblocks(n)), dim3(RB), 0, s, yb, rz, nb, (const float*)ws.ythr, 1, ws.yw));
+        LAUNCH(M, "surface_edges", n * 17.0, 0,
+               hipLaunchKernelGGL(k_surface_edges, dim3(nblocks(hw), nb), dim3(RB), 0, s, fg, (const int*)ws.lp, (const unsigned*)ws.sp,
+                                  (unsigned)a.min_area, (const uint32_t*)ws.yw, oh, ow, ws.edges, ws.counts));
+        LAUNCH(M, "surface_cols", n * 6.0, 0,
+               hipLaunchKernelGGL(k_surface_cols, dim3((ow + kColsX - 1) / kColsX, 2 * nb), dim3(RB), (size_t)((oh + 31) / 32) * kColsX * 4, s,
+                                  (const unsigned char*)ws.edges, nb, oh, ow, ws.cols));
+        LAUNCH(M, "surface_sample", n * 1.0 + (double)list_cap * 16, 0,
+               hipLaunchKernelGGL(k_surface_sample, dim3(nblocks(hw), nb), dim3(RB), 0, s, (const unsigned char*)ws.edges,
+                                  (const unsigned short*)ws.cols, (const unsigned*)ws.counts, nb, oh, ow, (unsigned)max_samples, b0,
+                                  (unsigned)list_cap, ws.list, ws.n_list));
+        if (M->dry) continue;
+        HIP_TRY(hipGetLastError());
+        unsigned n_found = 0;
+        HIP_TRY(hipMemcpyAsync(counts + (size_t)b0 * 5, ws.counts, (size_t)nb * 5 * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&n_found, ws.n_list, 4, hipMemcpyDeviceToHost, s));
+        if (edges) HIP_TRY(hipMemcpyAsync(edges + (size_t)b0 * hw, ws.edges, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if ((size_t)n_found > list_cap) {
+            set_error("surface distances: %u samples in %d slices exceed the bound of %zu per slice", n_found, nb, 2 * per);
+            return DNNCA_ESTATE;
+        }
+        found.resize(n_found);           // only the counted entries come back; their order is the atomics': sorted below
+        if (n_found) {
+            HIP_TRY(hipMemcpyAsync(found.data(), ws.list, (size_t)n_found * sizeof(SurfaceSample), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        std::sort(found.begin(), found.end(), [](const SurfaceSample& x, const SurfaceSample& y) {
+            return std::make_tuple(x.slice, x.side, x.pixel) < std::make_tuple(y.slice, y.side, y.pixel);
+        });
+        for (const SurfaceSample& v : found) samples[out++] = dnnca_surface_sample{v.slice, v.side, v.pixel, v.d2};
+    }
+    if (!M->dry) *n_samples = out;
+    return DNNCA_OK;
+}
+
+void surface_last(Model* M, float* rf, int* k) {
+    RegionState def;
+    const RegionState& R = M->region ? *M->region : def;
+    *rf = R.surface_rf;
+    *k = R.surface_k;
 }
 
 bool lesion_match_carry_is(Model* M, int oh, int ow) {

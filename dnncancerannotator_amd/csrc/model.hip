@@ -2098,6 +2098,59 @@ int dnnca_lesion_table_matched(void* model, const float* prob_hw, const float* y
     return lesion_table_matched(M, p_dev, yd, batch, h, w, a, continues, pred, mask, mask != nullptr, truth, pairs);
 }
 
+int dnnca_surface_distances(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w, float threshold,
+                            float resize_factor, int filter_size, int min_area, int max_samples, int32_t* counts,
+                            dnnca_surface_sample* samples, int64_t capacity, int64_t* n_samples, uint8_t* edges,
+                            int64_t edges_capacity, int32_t* out_hw) {
+    MODEL(model);
+    DN_TRY(check_batch(M, batch));
+    if (!prob_hw) {
+        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
+            set_error("surface distances: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
+            return DNNCA_EINVAL;
+        }
+        h = M->outH;
+        w = M->outW;
+    }
+    LesionArgs a;
+    a.threshold = threshold;
+    a.rf = resize_factor;
+    a.k = filter_size;
+    a.min_area = min_area;
+    DN_TRY(lesion_check(a, h, w));
+    if (a.oh > kSurfaceMaxSide || a.ow > kSurfaceMaxSide) {
+        set_error("surface distances: planes of %d x %d exceed %d pixels a side", a.oh, a.ow, kSurfaceMaxSide);
+        return DNNCA_EINVAL;
+    }
+    if (!out_hw) { set_error("surface distances: null out_hw"); return DNNCA_EINVAL; }
+    out_hw[0] = a.oh;
+    out_hw[1] = a.ow;
+    if (!counts) return DNNCA_OK;                 // size query
+    if (!y_hw) { set_error("surface distances: null y_hw (the call needs the labels)"); return DNNCA_EINVAL; }
+    if (max_samples < 1) { set_error("surface distances: max_samples %d (must be >= 1)", max_samples); return DNNCA_EINVAL; }
+    if (!samples || !n_samples) { set_error("surface distances: null samples / n_samples"); return DNNCA_EINVAL; }
+    const long long plane = (long long)a.oh * a.ow, need = (long long)batch * 2 * std::min<long long>(max_samples, plane);
+    if (capacity < need) {
+        set_error("surface distances: %lld samples needed (%d slices x 2 x %lld), capacity %lld", need, batch, need / (2 * batch),
+                  (long long)capacity);
+        return DNNCA_EINVAL;
+    }
+    if (edges && edges_capacity < (int64_t)batch * plane) {
+        set_error("surface distances: edges of %lld bytes needed, capacity %lld", (long long)batch * plane, (long long)edges_capacity);
+        return DNNCA_EINVAL;
+    }
+    const size_t n = (size_t)batch * h * w;
+    float *pd = nullptr, *yd = nullptr;
+    DN_TRY(region_inputs(M, n, &pd, &yd));
+    const float* p_dev = M->prob;
+    if (prob_hw) {
+        HIP_TRY(hipMemcpyAsync(pd, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+        p_dev = pd;
+    }
+    HIP_TRY(hipMemcpyAsync(yd, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+    return surface_distances(M, p_dev, yd, batch, h, w, a, max_samples, counts, samples, n_samples, edges);
+}
+
 int dnnca_eval_region_begin(void* model, const dnnca_region_spec* specs, int n) {
     MODEL(model);
     if (!M->eval_active) { set_error("dnnca_eval_region_begin outside dnnca_eval_begin .. dnnca_eval_end"); return DNNCA_ESTATE; }
@@ -2301,7 +2354,8 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
     MODEL(model);
     if (!buf || !cap) return DNNCA_EINVAL;
     if (pass != DNNCA_PLAN_TRAIN && pass != DNNCA_PLAN_EVAL && pass != DNNCA_PLAN_FORWARD && pass != DNNCA_PLAN_SENSITIVITY &&
-        pass != DNNCA_PLAN_LESION && pass != DNNCA_PLAN_LESION_LINKED && pass != DNNCA_PLAN_LESION_MATCHED) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
+        pass != DNNCA_PLAN_LESION && pass != DNNCA_PLAN_LESION_LINKED && pass != DNNCA_PLAN_LESION_MATCHED &&
+        pass != DNNCA_PLAN_SURFACE) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
     DN_TRY(check_batch(M, batch));
     M->plan_text.clear();
     M->dry = true;
@@ -2341,6 +2395,12 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
         rc = lesion_check(a, M->outH, M->outW);
         if (rc == DNNCA_OK)
             rc = lesion_table_matched(M, M->prob, M->y_stage, B, M->outH, M->outW, a, nullptr, nullptr, nullptr, want_mask, nullptr, nullptr);
+    } else if (pass == DNNCA_PLAN_SURFACE) {
+        LesionArgs a;
+        surface_last(M, &a.rf, &a.k);
+        rc = lesion_check(a, M->outH, M->outW);
+        if (rc == DNNCA_OK)
+            rc = surface_distances(M, M->prob, M->y_stage, B, M->outH, M->outW, a, 1, nullptr, nullptr, nullptr, nullptr);
     } else {
         rc = dnnca_forward_dev(model, M->x_stage, B, 0);
     }

@@ -9,6 +9,7 @@ namespace dnnca {
 
 constexpr int kRegionMaxThr = 64;        // thresholds per spec (two 32-bit mask words per pixel)
 constexpr int kRegionMaxK = 15;          // morphological filter size
+constexpr int kSurfaceMaxSide = 16384;   // boundary distances: analysed planes of up to this many pixels a side (squares in int32)
 
 // one validated spec: the caller's thresholds (in their order), IoU threshold, resize factor, filter size, and the resized plane
 struct RegionSpecHost {
@@ -83,6 +84,16 @@ void lesion_match_last(Model* M, float* rf, int* k, bool* want_mask);
 // resize factor, filter size and mask choice of the last lesion_table / lesion_table_linked (DNNCA_PLAN_LESION,
 // DNNCA_PLAN_LESION_LINKED); the defaults before any
 void lesion_last(Model* M, float* rf, int* k, bool* want_mask);
+// ---- the boundary distances of dnnca_surface_distances: the prediction plane through prep, open, ccl and sizes as lesion_table puts
+// it (a.max_lesions is not looked at), the label plane through prep alone (label' > 0.5), then surface_edges / surface_cols /
+// surface_sample per chunk, in the same workspace.  prob, y: device [batch, h, w].  counts (host [batch][5]), samples (host,
+// batch * 2 * min(max_samples, a.oh * a.ow) entries at least, sorted by (slice, side, pixel)) and *n_samples are written; edges
+// (host uint8 [batch, oh, ow]) where it is not nullptr.  No carry plane is read or written.  Synchronises.  In a dry run none of the
+// host pointers is touched
+int surface_distances(Model* M, const float* prob, const float* y, int batch, int h, int w, const LesionArgs& a, int max_samples,
+                      int32_t* counts, dnnca_surface_sample* samples, int64_t* n_samples, uint8_t* edges);
+// resize factor and filter size of the last surface_distances (DNNCA_PLAN_SURFACE); the defaults before any
+void surface_last(Model* M, float* rf, int* k);
 void region_release(Model* M);
 
 }  // namespace dnnca

@@ -611,6 +611,47 @@ class DeviceModel:
         return (rows[:pred.n_rows].copy(), totals, masks, links[:pred.n_links].copy(), true_rows[:truth.n_rows].copy(), true_totals,
                 true_links[:truth.n_links].copy(), pairs[:po.n_pairs].copy())
 
+    def surface_distances(self, y, batch=None, prob=None, threshold=0.5, resize_factor=1.0, filter_size=5, min_area=0,
+                          max_samples=65536, edges=False):
+        """the squared distances between the outline of the prediction mask (side 0: lesion_table's mask for the same arguments) and
+        the outline of the label foreground (side 1: y' > 0.5 of `y` [B, h, w(, 1)]), of the last forward's `batch` slices or of
+        `prob`: (counts, samples, edges).  counts int32 [B, 5]: area_pred, area_true, common, edge_pred, edge_true.  samples:
+        structured array (_lib.SURFACE_SAMPLE_DTYPE: slice, side, pixel = y * ow + x, d2), one entry per boundary pixel of either
+        side with the exact squared distance to the nearest boundary pixel of the other side, sorted by (slice, side, pixel); a
+        slice with an empty outline or more than max_samples boundary pixels on a side gives none.  edges: uint8 [B, oh, ow], bit 0
+        on the prediction's boundary, bit 1 on the label's (None with edges=False)."""
+        y = as_f32(y)
+        if y.ndim == 4 and y.shape[-1] == 1:
+            y = np.ascontiguousarray(y[..., 0])
+        if y.ndim != 3:
+            raise ValueError('y must be [B, h, w], got %s' % (y.shape,))
+        pp = None
+        if prob is not None:
+            prob = as_f32(prob)
+            if prob.ndim == 4 and prob.shape[-1] == 1:
+                prob = np.ascontiguousarray(prob[..., 0])
+            if prob.shape != y.shape:
+                raise ValueError('prob %s and y %s differ in shape' % (prob.shape, y.shape))
+            pp = fptr(prob)
+        B = len(y) if batch is None else int(batch)
+        if len(y) != B:
+            raise ValueError('batch %d but y holds %d slices' % (B, len(y)))
+        h, w = y.shape[1:]               # without `prob` the library holds them against the size of the last forward
+        args = (self.handle, pp, fptr(y), B, int(h), int(w), float(threshold), float(resize_factor), int(filter_size), int(min_area),
+                int(max_samples))
+        hw = (C.c_int32 * 2)()
+        check(self.lib.dnnca_surface_distances(*args, None, None, 0, None, None, 0, hw))
+        oh, ow = hw[0], hw[1]
+        cap = B * 2 * min(int(max_samples), oh * ow)
+        counts = np.zeros((B, 5), np.int32)
+        samples = np.zeros(max(cap, 0), _lib.SURFACE_SAMPLE_DTYPE)
+        planes = np.empty((B, oh, ow), np.uint8) if edges else None
+        n = C.c_int64()
+        check(self.lib.dnnca_surface_distances(*args, counts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               samples.ctypes.data_as(C.POINTER(_lib.SurfaceSample)), cap, C.byref(n),
+                                               planes.ctypes.data_as(C.c_void_p) if edges else None, planes.nbytes if edges else 0, hw))
+        return counts, samples[:n.value].copy(), planes
+
     def input_sensitivity(self, x=None, batch=None):
         """float64 [B, C]: sum over the image of |d sum(prob of slice b) / d x[b, :, :, c]| in inference mode (the raw sums of the
         reference's sensitivity map; casewise.normalise_sensitivity divides each row by its sum).  x [B, H, W, C], or None with
@@ -754,14 +795,16 @@ class DeviceModel:
             out.append((name.value.decode(), n.value, ms.value, by.value, fl.value))
         return out
 
-    PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3, 'lesion': 4, 'lesion_linked': 5, 'lesion_matched': 6}
+    PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3, 'lesion': 4, 'lesion_linked': 5, 'lesion_matched': 6,
+                   'surface': 7}
 
     def plan(self, variants=False, mode='train', batch=None):
         """The launch schedule of one pass: [(kernel, algorithmic bytes, flops)].  mode 'train': one train step; 'eval': one
         eval_step (inference forward + loss; a staged evaluation step launches the same); 'forward': forward(training=False);
         'sensitivity': input_sensitivity; 'lesion': lesion_table on the last forward's probabilities, with the resize factor,
         filter size and mask choice of the last lesion_table / lesion_table_linked call; 'lesion_linked': lesion_table_linked likewise;
-        'lesion_matched': lesion_table_matched with the three values of the last lesion_table_matched call.
+        'lesion_matched': lesion_table_matched with the three values of the last lesion_table_matched call; 'surface':
+        surface_distances with the resize factor and filter size of the last surface_distances call.
         batch: None = max_batch.  variants: keep the template variant the library appends to a launch name
         (`ig_conv_fwd#3n2w8`): the kernel-coverage test tells them apart.  A dry run: the model is unchanged."""
         if mode not in self.PLAN_PASSES:

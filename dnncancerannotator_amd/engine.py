@@ -547,10 +547,14 @@ class TFKerasModel:
     def eval(self, dataset, save_path, viz_ds=None, tag='val', avoid_overwrite=False, export_path=None, export_images=False,
              visualize_sensitivity=False, export_csv=False, min_interval=1, step_range=None, overlay=False,
              export_casewise_metrics=False, exam_ds=None, exam_lesions=False, exam_threshold=(0.5,), exam_iou=casewise.EXAM_IOU,
-             exam_min_area=0, exam_filter_size=5, exam_resize_factor=1.0, exam_max_lesions=256, exam_link_min_overlap=1):
+             exam_min_area=0, exam_filter_size=5, exam_resize_factor=1.0, exam_max_lesions=256, exam_link_min_overlap=1,
+             surface_ds=None, surface_distances=False, surface_threshold=(0.5,), surface_percentile=casewise.SURFACE_PERCENTILE,
+             surface_min_area=0, surface_filter_size=5, surface_resize_factor=1.0, surface_max_samples=65536):
         """exam_lesions (`evaluate --exam_lesions`): after every checkpoint's evaluation rank 0 also runs _exam_lesion_pass over
         exam_ds (batches (x, y, paths, sliceIDs), a data set of its own: viz_ds is not needed) and writes exam_lesion_results.csv,
-        exam_lesion_cases.csv and exam_lesion_matches.csv under <export_path>/<tag>/; every other file is what it is without it."""
+        exam_lesion_cases.csv and exam_lesion_matches.csv under <export_path>/<tag>/; every other file is what it is without it.
+        surface_distances (`evaluate --surface_distances`): likewise rank 0 runs _surface_pass over surface_ds (the same kind of data
+        set; the two flags may share one) and writes surface_results.csv, surface_cases.csv and surface_slices.csv there."""
         if visualize_sensitivity and not getattr(self.model, 'supports_sensitivity', True):
             raise NotImplementedError('--visualize_sensitivity is not implemented for model: %s (the input-gradient pass covers the '
                                       'U-Net models only)' % self.model_config['model'])
@@ -577,6 +581,8 @@ class TFKerasModel:
         writer = casewise.Writer() if visualize else None
         exam_pass = bool(exam_lesions) and exam_ds is not None and self.ctx.rank == 0
         exam_tables = [], [], []         # the lines of the three exam_lesion_*.csv files
+        surface_pass = bool(surface_distances) and surface_ds is not None and self.ctx.rank == 0
+        surface_tables = [], [], []      # the lines of surface_results.csv, surface_cases.csv and surface_slices.csv
         rows = OrderedDict()
         previous_step = None
         for ckpt_step, ckpt_path_ in self.get_ckpts(ckpt_path).items():
@@ -597,6 +603,19 @@ class TFKerasModel:
                         dict(resize_factor=exam_resize_factor, filter_size=exam_filter_size, min_area=exam_min_area,
                              max_lesions=exam_max_lesions))):
                     t += new
+            if surface_pass:
+                for t, new in zip(surface_tables, self._surface_pass(
+                        surface_ds, ckpt_step, [float(t) for t in surface_threshold], float(surface_percentile),
+                        dict(resize_factor=surface_resize_factor, filter_size=surface_filter_size, min_area=surface_min_area,
+                             max_samples=surface_max_samples))):
+                    t += new
+        if surface_pass:
+            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
+            for name, cols, table in zip(('surface_results.csv', 'surface_cases.csv', 'surface_slices.csv'),
+                                         (casewise.SURFACE_RESULT_COLUMNS, casewise.SURFACE_CASE_COLUMNS, casewise.SURFACE_SLICE_COLUMNS),
+                                         surface_tables):
+                with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
+                    f.write(casewise.plain_csv(['step', 'threshold'] + cols, table))
         if exam_pass:
             os.makedirs(os.path.join(export_path, tag), exist_ok=True)
             for name, cols, table in zip(('exam_lesion_results.csv', 'exam_lesion_cases.csv', 'exam_lesion_matches.csv'),
@@ -719,6 +738,42 @@ class TFKerasModel:
             cases += [lead + c for c in mine_cases]
             results.append(lead + casewise.exam_match_summary(mine_cases))
         return results, cases, matches
+
+    def _surface_pass(self, ds, step, thresholds, percentile, kw):
+        """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --surface_distances`: per max_batch split one forward whose
+        probabilities stay on the device and one DeviceModel.surface_distances per threshold; only the counts and the boundary
+        pixels' squared distances come back.  Then per threshold casewise.surface_slice_values per slice, surface_exam_values per
+        exam (the slices of one exam path, in the order of the data set) and surface_summary.  Returns the new lines of
+        (surface_results.csv, surface_cases.csv, surface_slices.csv), each led by step and threshold.  No slice depends on another:
+        nothing is carried between calls."""
+        found = [[] for _ in thresholds]     # per threshold and slice: (exam, slice, counts, d2 of the prediction, d2 of the label)
+        for x, y, paths, ids in ds:
+            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
+            if not len(x):
+                continue
+            self._ensure_capacity(len(x))
+            dm = self.device_model
+            for i in range(0, len(x), dm.max_batch):
+                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
+                pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
+                dm.forward(xb, training=False, return_prob=False)
+                for ti, thr in enumerate(thresholds):
+                    counts, samples, _ = dm.surface_distances(yb, batch=len(xb), threshold=thr, **kw)
+                    for b, (p, k) in enumerate(pk):
+                        mine = samples[samples['slice'] == b]
+                        found[ti].append((p, int(k), counts[b], mine['d2'][mine['side'] == 0], mine['d2'][mine['side'] == 1]))
+        results, cases, slices = [], [], []
+        for thr, mine in zip(thresholds, found):
+            lead = [int(step), repr(thr)]
+            exams = OrderedDict()            # exam path -> its slices, in the order of the data set
+            for rec in mine:
+                exams.setdefault(rec[0], []).append(rec)
+            slice_values = [casewise.surface_slice_values(*rec, percentile=percentile) for rec in mine]
+            exam_values = [casewise.surface_exam_values(exam, [r[2:] for r in recs], percentile=percentile) for exam, recs in exams.items()]
+            slices += [lead + v for v in slice_values]
+            cases += [lead + v for v in exam_values]
+            results.append(lead + casewise.surface_summary(slice_values, exam_values))
+        return results, cases, slices
 
     def predict(self, dataset):
         """Probabilities [N, H, W, 1] for every element of `dataset` (elements are x or (x, ...))."""

@@ -378,6 +378,33 @@ int dnnca_lesion_table_matched(void* model, const float* prob_hw, const float* y
                                dnnca_lesion_plane_out* pred, uint8_t* mask, int64_t mask_capacity, dnnca_lesion_plane_out* truth,
                                dnnca_lesion_pairs_out* pairs, int32_t* out_hw);
 
+/* ---- how far the predicted outline lies from the labelled one (`annotator evaluate --surface_distances`) -------------------------
+ * Two masks per slice, on the analysed (resized) plane of oh x ow pixels.  Side 0 is the prediction mask: bit for bit the `mask`
+ * that dnnca_lesion_table writes for the same prob_hw (NULL: the last forward's probabilities), threshold, resize_factor,
+ * filter_size and min_area -- every kept component, whatever max_lesions would be.  Side 1 is the label foreground of
+ * dnnca_lesion_table_matched: y_hw (host [batch, h, w], required) resized by the same factor, y' > 0.5, no opening, no area filter.
+ * A BOUNDARY pixel of a mask is a foreground pixel with at least one of its four neighbours in the background or outside the plane.
+ * For a boundary pixel a of side s, d2 is the smallest (ax - bx)^2 + (ay - by)^2 over the boundary pixels b of the OTHER side: an
+ * exact integer, boundary to boundary (a pixel deep inside the other mask is not at distance 0).
+ *   counts [batch][5]      area_pred, area_true, common (pixels in both masks), edge_pred, edge_true (boundary pixels); always exact
+ *   samples                one entry (slice, side, pixel = y * ow + x, d2) per boundary pixel of either side, sorted by (slice,
+ *                          side, pixel), *n_samples of them.  A slice gives samples only when edge_pred > 0, edge_true > 0 and both
+ *                          are at most max_samples; otherwise it gives none, for neither side (never a subset).  capacity must be at
+ *                          least batch * 2 * min(max_samples, oh * ow)
+ *   edges                  NULL, or host uint8 [batch, oh, ow] of edges_capacity bytes: bit 0 on the prediction's boundary pixels,
+ *                          bit 1 on the label's, truncated or not
+ * out_hw receives (oh, ow); counts == NULL only queries it.  Everything is an integer: bit-identical from run to run.
+ * DNNCA_EINVAL, with nothing launched: everything dnnca_lesion_table refuses, y_hw == NULL, max_samples < 1, samples == NULL or
+ * n_samples == NULL, a buffer that is too small, an analysed plane of more than 16384 pixels a side (d2 would leave int32).
+ * Variables, state and the probabilities of the last forward are untouched; so is what dnnca_lesion_table_linked and
+ * dnnca_lesion_table_matched keep of their last slice: a chain of either continues as if this call had not happened.
+ * Synchronises. */
+typedef struct dnnca_surface_sample { int32_t slice, side, pixel, d2; } dnnca_surface_sample;   /* 16 bytes */
+int dnnca_surface_distances(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w, float threshold,
+                            float resize_factor, int filter_size, int min_area, int max_samples, int32_t* counts /* [batch][5] */,
+                            dnnca_surface_sample* samples, int64_t capacity, int64_t* n_samples, uint8_t* edges,
+                            int64_t edges_capacity, int32_t* out_hw);
+
 /* ---- channel sensitivity of `annotator evaluate --visualize_sensitivity` (utils/callbacks.py:290-313) ---------------------------
  * With the model in inference mode (BatchNorm on its moving statistics, sigmoid output):
  *     sums[b * in_channels + c] = sum over H, W of | d (sum of all probabilities of slice b) / d x[b, h, w, c] |
@@ -422,10 +449,11 @@ int dnnca_plan_dump(void* model, char* buf, size_t cap);
    inference forward + sigmoid), or dnnca_input_sensitivity, or dnnca_lesion_table on the last forward's probabilities with the
    resize factor, filter size and mask choice of the last dnnca_lesion_table / dnnca_lesion_table_linked call (before any: 1.0, 5,
    with mask), or dnnca_lesion_table_linked with the same three values, or dnnca_lesion_table_matched with the three values of the
-   last dnnca_lesion_table_matched call (before any: the same defaults).  A dry run: nothing is launched and the model is left as
-   it was. */
+   last dnnca_lesion_table_matched call (before any: the same defaults), or dnnca_surface_distances with the resize factor and
+   filter size of the last dnnca_surface_distances call (before any: 1.0, 5).  A dry run: nothing is launched and the model is left
+   as it was. */
 enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2, DNNCA_PLAN_SENSITIVITY = 3, DNNCA_PLAN_LESION = 4,
-       DNNCA_PLAN_LESION_LINKED = 5, DNNCA_PLAN_LESION_MATCHED = 6 };
+       DNNCA_PLAN_LESION_LINKED = 5, DNNCA_PLAN_LESION_MATCHED = 6, DNNCA_PLAN_SURFACE = 7 };
 int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap);
 
 #ifdef __cplusplus

@@ -11,6 +11,8 @@ and prediction plane) plus pairs, match and count.
     DNNCA_LIB=<a library from before the links> python tools/lesion_rate.py                         # the unlinked legs on it
     python tools/lesion_rate.py --link --match      # also: lesion_table_matched against lesion_table_linked
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --link            # the linked legs on it
+    python tools/lesion_rate.py --link --match --surface         # also: surface_distances against lesion_table_matched
+    DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --link --match    # the matched legs on it
 
 --link adds the cost of linking neighbouring slices: lesion_table_linked against lesion_table (wall time per call, device time of
 the three link launches), its worst case for the pair table (a checkerboard on itself: every other pixel a lesion of its own in
@@ -19,6 +21,10 @@ both slices, (hw + 1) / 2 keys per slice) and `annotate` with link_slices.
 --match adds the cost of `evaluate --exam_lesions`: lesion_table_matched (both planes, three sets of pair tables) against
 lesion_table_linked on the same probabilities, and passes over the data set in the manner of `annotate` -- a forward and one call
 per batch, the flags from the slice numbers -- with the linked and the matched call alternated in one process.
+
+--surface adds the cost of `evaluate --surface_distances`: surface_distances (the prediction plane's shared stages, the label's
+prep, then surface_edges / surface_cols / surface_sample) per call with its launches event-bracketed, and a forward + surface pass
+against a forward + matched pass over the same batches, alternated in one process.
 
 The probabilities are drawn: the synthetic labels' discs at 0.55 .. 0.95 on a background of 0 .. 0.45 (a few lesions per slice,
 as a trained model gives), put into the model's probability buffer by pixel_confusion_of."""
@@ -40,6 +46,7 @@ ap.add_argument('--batches', type=int, default=8)
 ap.add_argument('--yardstick', action='store_true', help='region_confusion_slices alone (also on a library without the lesion table)')
 ap.add_argument('--link', action='store_true', help='also measure lesion_table_linked and annotate(link_slices=True)')
 ap.add_argument('--match', action='store_true', help='also measure lesion_table_matched against lesion_table_linked (needs --link)')
+ap.add_argument('--surface', action='store_true', help='also measure surface_distances against lesion_table_matched (needs --match)')
 ap.add_argument('--out', default=None, help='append the report to this file as well')
 a = ap.parse_args()
 if a.yardstick:
@@ -51,6 +58,11 @@ if a.match and not a.link:
     ap.error('--match needs --link')
 if not a.match:
     _lib.SIGNATURES.pop('dnnca_lesion_table_matched', None)      # nor does one from before the matched call
+
+if a.surface and not a.match:
+    ap.error('--surface needs --link --match')
+if not a.surface:
+    _lib.SIGNATURES.pop('dnnca_surface_distances', None)         # nor does one from before the boundary distances
 
 from dnncancerannotator_amd import device as dev                  # noqa: E402
 from dnncancerannotator_amd.data import ArrayDataset              # noqa: E402
@@ -171,6 +183,38 @@ if not a.yardstick:
                                                                  B * NB / took[bool(i % 2)][-1], took[bool(i % 2)][-1] / NB * 1e3))
         mt, lk = sorted(took[True])[len(took[True]) // 2], sorted(took[False])[len(took[False]) // 2]
         say('  matched / linked pass (medians of 4, alternated): %.3f' % (mt / lk))
+    if a.surface:
+        dm.pixel_confusion_of(prob, y, [0.5])
+        kw = dict(batch=B, threshold=0.5, filter_size=5)
+        med, lo, hi = wall(lambda: dm.surface_distances(y, **kw))
+        say('  surface_distances(edges=False): %.3f ms per call (median of %d; %.3f .. %.3f)' % (med, R, lo, hi))
+        counts, samples, _ = dm.surface_distances(y, **kw)
+        say('    %d / %d boundary pixels of %d / %d, %d samples in %d slices, largest distance %.3f' % (
+            counts[:, 3].sum(), counts[:, 4].sum(), counts[:, 0].sum(), counts[:, 1].sum(), len(samples), B,
+            float(np.sqrt(samples['d2'].max())) if len(samples) else 0.0))
+        per_launch(dm, lambda: dm.surface_distances(y, **kw), ('region_', 'surface_'))
+        ys = np.concatenate([y] * NB)
+
+        def eval_pass(surface):
+            """a forward and one call per batch, as engine._surface_pass / _exam_lesion_pass make them"""
+            t0 = time.perf_counter()
+            for i, (xb, _, _) in enumerate(ds):
+                dm.forward(xb, return_prob=False)
+                yb = ys[i * B:i * B + len(xb)]
+                if surface:
+                    dm.surface_distances(yb, batch=len(xb), threshold=0.5, filter_size=5)
+                else:
+                    dm.lesion_table_matched(yb, batch=len(xb), continues=[i > 0 or b > 0 for b in range(len(xb))], threshold=0.5,
+                                            filter_size=5)
+            return time.perf_counter() - t0
+        eval_pass(False), eval_pass(True)                         # warm-up: the carries, either workspace
+        took = {False: [], True: []}
+        for i in range(8):
+            took[bool(i % 2)].append(eval_pass(bool(i % 2)))
+            say('  %-34s %9.1f slices/s  (%.2f ms per batch)' % ('forward + ' + ('surface' if i % 2 else 'matched') + ' pass',
+                                                                 B * NB / took[bool(i % 2)][-1], took[bool(i % 2)][-1] / NB * 1e3))
+        sf, mt = sorted(took[True])[len(took[True]) // 2], sorted(took[False])[len(took[False]) // 2]
+        say('  surface / matched pass (medians of 4, alternated): %.3f' % (sf / mt))
     for xb, _, _ in ds:
         dm.forward(xb, return_prob=False)
     t0 = time.perf_counter()
