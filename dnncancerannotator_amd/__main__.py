@@ -7,6 +7,8 @@ import argparse
 import logging
 import sys
 
+from .tta import MODES as TTA_MODES
+
 
 def _at_least_one(text):
     n = int(text)
@@ -71,6 +73,9 @@ def build_parser(prog='python3 -m annotator'):
                    help='analyse probabilities and labels resized by this factor (default: 1.0)')
     e.add_argument('--surface_max_samples', type=_at_least_one, default=argparse.SUPPRESS,
                    help='boundary pixels per slice and side; a slice with more reports no distance (default: 65536)')
+    e.add_argument('--tta', choices=TTA_MODES, default=argparse.SUPPRESS,
+                   help='test-time augmentation: every probability read is the mean over the flip views (flips) or over all eight '
+                        'flip / transpose views (d4, square slices only); default: none')
     p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
     p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
     p.add_argument('--data_path', nargs='+', required=True)
@@ -88,6 +93,9 @@ def build_parser(prog='python3 -m annotator'):
                    help='join the lesions of neighbouring slices of an exam: also write exam_lesions.csv and exam_lesion_parts.csv')
     p.add_argument('--link_min_overlap', type=_at_least_one, default=argparse.SUPPRESS,
                    help='common pixels that join two lesions of neighbouring slices (default: 1)')
+    p.add_argument('--tta', choices=TTA_MODES, default=argparse.SUPPRESS,
+                   help='test-time augmentation: the lesions of the mean probability over the flip views (flips) or over all eight '
+                        'flip / transpose views (d4, square slices only); default: none')
     return parser
 
 

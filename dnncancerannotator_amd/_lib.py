@@ -131,6 +131,9 @@ SIGNATURES = {
     'dnnca_get_opt_state': (C.c_int, [_VP, _FP, _FP, C.c_int64, C.POINTER(C.c_int64)]),
     'dnnca_set_adam': (C.c_int, [_VP, C.c_float, C.c_float, C.c_float]),
     'dnnca_forward': (C.c_int, [_VP, _FP, C.c_int, C.c_int, _FP, _FP]),
+    'dnnca_forward_tta': (C.c_int, [_VP, _FP, C.c_int, C.c_uint, _FP]),
+    'dnnca_tta_view_of': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _FP]),
+    'dnnca_tta_mean_of': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, _FP]),
     'dnnca_train_step': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_float, C.POINTER(LossCfg), C.POINTER(StepOut)]),
     'dnnca_eval_step': (C.c_int, [_VP, _FP, _FP, C.c_int, C.POINTER(LossCfg), C.POINTER(StepOut), _FP]),
     'dnnca_dev_alloc': (C.c_int, [C.POINTER(_VP), C.c_size_t]),

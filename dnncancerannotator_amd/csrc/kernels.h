@@ -4,6 +4,15 @@
 
 namespace dnnca {
 
+#define DEVINL __device__ __forceinline__
+
+// the model's output activation: the one expression behind every probability the library hands out for a logit (k_sigmoid and the
+// test-time-augmentation mean), so that they agree bit for bit
+DEVINL float sigmoid_of_logit(float x) {
+    float e = expf(-fabsf(x));
+    return x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+}
+
 // ----------------------------------------------------------------------------- generic (any shape, untuned) kernels
 // y = act(conv_kxk(concat(A, Bv)) + bias); Bv.C may be 0.  Weight layout HWIO with I = A.C + Bv.C.  bias / dbias may be null
 // (a conv without bias); gamma may be null in g_bn_finalize / g_bn_bwd_apply (a BatchNorm without scale: gamma = 1).
@@ -52,6 +61,15 @@ void g_label_stats(hipStream_t s, size_t n, const float* y, double* scalars);
 void g_loss(hipStream_t s, size_t n, const float* logits, const float* y, const dnnca_loss_cfg cfg, double n_label,
             double* scalars, float* dlogits, float* prob, float grad_scale);
 void g_sigmoid(hipStream_t s, size_t n, const float* logits, float* prob);
+
+// ----------------------------------------------------------------------------- test-time augmentation (kernels_tta.hip)
+// A view k = 4 t + 2 v + h of the dihedral group: flips first (v: rows, h: columns), then, with t, the transpose (H == W).
+// dst[b,i,j,c] = view k of src [B,H,W,C]; dst must not alias src
+void g_tta_view_in(hipStream_t s, const float* src, float* dst, int B, int H, int W, int C, int k);
+// prob[b,i,j] (op)= p at the position of view k's plane `src` [B,H,W] that original pixel (i,j) went to; p = src or, with is_logits,
+// sigmoid_of_logit(src).  first: prob = p, otherwise prob += p; last: the sum is then divided by n.  prob must not alias src
+void g_tta_accumulate(hipStream_t s, const float* src, float* prob, int B, int H, int W, int k, bool is_logits, bool first, bool last,
+                      int n);
 
 void g_l2(hipStream_t s, size_t n, const float* w, float* g, float l2, double* scalars);   // g += 2*l2*w ; penalty += l2*sum w^2
 // writes [loss, positive_rate, weight, ymin, ymax] floats to out5 (device) from the scalar block

@@ -636,9 +636,7 @@ void g_loss(hipStream_t s, size_t n, const float* logits, const float* y, const 
 __global__ void k_sigmoid(size_t n, const float* __restrict__ logits, float* __restrict__ prob) {
     size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     if (i >= n) return;
-    float x = logits[i];
-    float e = expf(-fabsf(x));
-    prob[i] = x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+    prob[i] = sigmoid_of_logit(logits[i]);
 }
 
 void g_sigmoid(hipStream_t s, size_t n, const float* logits, float* prob) {

@@ -9,8 +9,6 @@
 
 namespace dnnca {
 
-#define DEVINL __device__ __forceinline__
-
 DEVINL void ld4(float* d, const float* p) {
     float4 t = *reinterpret_cast<const float4*>(p);
     d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;

@@ -299,6 +299,13 @@ struct Model {
     unsigned* sens_ticket = nullptr;
     int input_sensitivity(const float* x_dev, int B);      // enqueues the pass; the sums are in sens_sums behind it
 
+    // test-time augmentation (dnnca_forward_tta): the flipped / transposed copy of the batch that a view's forward reads, allocated
+    // for max_batch by the first call (x_stage keeps the untransformed batch); tta_io: the device buffers of dnnca_tta_view_of /
+    // dnnca_tta_mean_of (input, then output), grown on demand
+    float* tta_view = nullptr;
+    float* tta_io = nullptr;
+    size_t tta_io_n = 0;
+
     ~Model();
     int build();
     int64_t add_param(const std::string& name, std::initializer_list<int64_t> shape, int trainable);      // appends to `params`; returns the offset

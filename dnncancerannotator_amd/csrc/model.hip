@@ -88,6 +88,7 @@ Model::~Model() {
     fast_release(this);
     ig_release(this);
     for (void* a : allocs) (void)hipFree(a);
+    if (tta_io) (void)hipFree(tta_io);
     for (auto& r : recs) {
         (void)hipEventDestroy(r.a);
         (void)hipEventDestroy(r.b);
@@ -1569,6 +1570,120 @@ int dnnca_forward(void* model, const float* x_nhwc, int batch, int training, flo
     DN_TRY(dnnca_forward_dev(model, M->x_stage, batch, training));
     if (prob_out) HIP_TRY(hipMemcpyAsync(prob_out, M->prob, npix * 4, hipMemcpyDeviceToHost, M->stream));
     if (logit_out) HIP_TRY(hipMemcpyAsync(logit_out, M->logits, npix * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return M->flush_profile();
+}
+
+// ---- test-time augmentation (kernels_tta.hip) ---------------------------------------------------------------------------------
+// the views of a mask in ascending order; 0 with the error set when the mask or a transposed view on h x w is refused
+static int tta_views_of(unsigned views, int h, int w, int* ks) {
+    if (views < 1u || views > 255u) { set_error("tta: views mask %u outside 1..255", views); return 0; }
+    if ((views & 0xF0u) && h != w) { set_error("tta: a transposed view (mask 0x%02X) needs a square plane, not %d x %d", views, h, w); return 0; }
+    int n = 0;
+    for (int k = 0; k < 8; ++k)
+        if (views >> k & 1u) ks[n++] = k;
+    return n;
+}
+
+static void tta_launch_view_in(Model* M, const float* src, float* dst, int B, int H, int W, int C, int k) {
+    const double nx = (double)B * H * W * C;
+    LAUNCH(M, "tta_view_in", 8.0 * nx, 0.0, g_tta_view_in(M->stream, src, dst, B, H, W, C, k));
+}
+
+static void tta_launch_accumulate(Model* M, const float* src, float* prob, int B, int H, int W, int k, bool is_logits, int pos, int n) {
+    const double npix = (double)B * H * W;
+    LAUNCH(M, "tta_accumulate", (pos ? 12.0 : 8.0) * npix, (is_logits ? 5.0 : 1.0) * npix,
+           g_tta_accumulate(M->stream, src, prob, B, H, W, k, is_logits, pos == 0, pos == n - 1, n));
+}
+
+// the buffers of the two stand-alone entries: n_in floats in, n_out floats out, one allocation
+static int tta_io_buffers(Model* M, size_t n_in, size_t n_out, float** in, float** out) {
+    if (n_in + n_out > M->tta_io_n) {
+        if (M->tta_io) HIP_TRY(hipFree(M->tta_io));
+        M->tta_io = nullptr;
+        M->tta_io_n = 0;
+        HIP_TRY(hipMalloc((void**)&M->tta_io, (n_in + n_out) * 4));
+        M->tta_io_n = n_in + n_out;
+    }
+    *in = M->tta_io;
+    *out = M->tta_io + n_in;
+    return DNNCA_OK;
+}
+
+// the launch grids carry the rows and the slices in their y and z dimensions
+static int tta_check_plane(int batch, int h, int w, int c) {
+    if (batch < 1 || h < 1 || w < 1 || c < 1 || h > 65535 || batch > 65535 || (int64_t)w * c > INT32_MAX) {
+        set_error("tta: bad plane %d x %d x %d x %d (at most 65535 slices and rows, w * c below 2^31)", batch, h, w, c);
+        return DNNCA_EINVAL;
+    }
+    return DNNCA_OK;
+}
+
+int dnnca_forward_tta(void* model, const float* x_nhwc, int batch, unsigned views, float* prob_out) {
+    MODEL(model);
+    const int H = M->desc.height, W = M->desc.width, C = M->desc.in_channels;
+    int ks[8];
+    const int n = tta_views_of(views, H, W, ks);
+    if (!n) return DNNCA_EINVAL;
+    if (!x_nhwc) { set_error("tta: null x"); return DNNCA_EINVAL; }
+    if (M->outH != H || M->outW != W) {
+        set_error("tta: the output (%d x %d) differs from the input (%d x %d)", M->outH, M->outW, H, W);
+        return DNNCA_EINVAL;
+    }
+    DN_TRY(check_batch(M, batch));
+    DN_TRY(tta_check_plane(batch, H, W, C));
+    if (!M->tta_view && views != 1u) DN_TRY(M->alloc((void**)&M->tta_view, (size_t)M->desc.max_batch * H * W * C * 4));
+    DN_TRY(stage_inputs(M, batch, x_nhwc, nullptr, false));
+    for (int i = 0; i < n; ++i) {
+        const float* x = M->x_stage;                      // view 0 forwards from the staged batch itself
+        if (ks[i]) {
+            tta_launch_view_in(M, M->x_stage, M->tta_view, batch, H, W, C, ks[i]);
+            x = M->tta_view;
+        }
+        DN_TRY(M->forward(x, batch, false));
+        tta_launch_accumulate(M, M->logits, M->prob, batch, H, W, ks[i], true, i, n);
+    }
+    const size_t npix = (size_t)batch * H * W;
+    if (prob_out) {
+        HIP_TRY(hipMemcpyAsync(prob_out, M->prob, npix * 4, hipMemcpyDeviceToHost, M->stream));
+        HIP_TRY(hipStreamSynchronize(M->stream));
+        return M->flush_profile();
+    }
+    return DNNCA_OK;
+}
+
+int dnnca_tta_view_of(void* model, const float* src, int batch, int h, int w, int c, int view, float* dst) {
+    MODEL(model);
+    if (!src || !dst) { set_error("tta: null buffer"); return DNNCA_EINVAL; }
+    if (view < 0 || view > 7) { set_error("tta: view %d outside 0..7", view); return DNNCA_EINVAL; }
+    int ks[8];
+    if (!tta_views_of(1u << view, h, w, ks)) return DNNCA_EINVAL;
+    DN_TRY(check_batch(M, batch));
+    DN_TRY(tta_check_plane(batch, h, w, c));
+    const size_t nx = (size_t)batch * h * w * c;
+    float *in = nullptr, *out = nullptr;
+    DN_TRY(tta_io_buffers(M, nx, nx, &in, &out));
+    HIP_TRY(hipMemcpyAsync(in, src, nx * 4, hipMemcpyHostToDevice, M->stream));
+    tta_launch_view_in(M, in, out, batch, h, w, c, view);
+    HIP_TRY(hipMemcpyAsync(dst, out, nx * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return M->flush_profile();
+}
+
+int dnnca_tta_mean_of(void* model, const float* vals, int batch, int h, int w, unsigned views, int is_logits, float* prob_out) {
+    MODEL(model);
+    int ks[8];
+    const int n = tta_views_of(views, h, w, ks);
+    if (!n) return DNNCA_EINVAL;
+    if (!vals || !prob_out) { set_error("tta: null buffer"); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
+    DN_TRY(tta_check_plane(batch, h, w, 1));
+    const size_t npix = (size_t)batch * h * w;
+    float *in = nullptr, *out = nullptr;
+    DN_TRY(tta_io_buffers(M, npix * n, npix, &in, &out));
+    HIP_TRY(hipMemcpyAsync(in, vals, npix * n * 4, hipMemcpyHostToDevice, M->stream));
+    for (int i = 0; i < n; ++i) tta_launch_accumulate(M, in + npix * i, out, batch, h, w, ks[i], is_logits != 0, i, n);
+    HIP_TRY(hipMemcpyAsync(prob_out, out, npix * 4, hipMemcpyDeviceToHost, M->stream));
     HIP_TRY(hipStreamSynchronize(M->stream));
     return M->flush_profile();
 }

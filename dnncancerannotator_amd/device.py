@@ -344,6 +344,16 @@ class DeviceModel:
                                      fptr(logits) if return_logits else None))
         return (prob, logits) if return_logits else prob
 
+    def forward_tta(self, x, views, return_prob=True):
+        """Test-time augmentation (dnnca_forward_tta): one inference forward per view of the bit mask `views` (tta.mask_of), the mean
+        of the mapped-back probabilities in the model's probability buffer, where every consumer of the last forward reads it.
+        return_prob=False: it stays on the device; returns None"""
+        x = self._check_x(x)
+        B = x.shape[0]
+        prob = np.empty((B, self.in_shape[0], self.in_shape[1], 1), np.float32) if return_prob else None
+        check(self.lib.dnnca_forward_tta(self.handle, fptr(x), B, int(views), fptr(prob) if return_prob else None))
+        return prob
+
     def train_step(self, x, y, lr, cfg):
         x = self._check_x(x)
         y = as_f32(y)

@@ -20,6 +20,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import augment, casewise, device, distributed, losses as custom_losses, metrics as custom_metrics, models, region_metrics
+from . import tta as tta_modes
 from .feeder import BatchFeeder
 
 
@@ -46,6 +47,15 @@ def _element_shape(dataset):
     for element in dataset:          # (x, y) for train / eval, (x,) for predict
         return tuple(np.shape(element[0]))
     raise ValueError('empty dataset')
+
+
+def _forward_on_device(dm, xb, tta_mask):
+    """the inference forward whose probabilities stay on the device: the plain one or, with a view mask (tta.mask_of), the test-time
+    augmented one"""
+    if tta_mask is None:
+        dm.forward(xb, training=False, return_prob=False)
+    else:
+        dm.forward_tta(xb, tta_mask, return_prob=False)
 
 
 def _csv_value(v):
@@ -426,10 +436,12 @@ class TFKerasModel:
         return OrderedDict((m.name, _log_value(m)) for m in objs)
 
     # ---- evaluation (engine.py:139-210) ----------------------------------------------------------------------
-    def _evaluate(self, dataset, staged=False):
+    def _evaluate(self, dataset, staged=False, tta_mask=None):
         """keras Model.evaluate(return_dict=True): mean loss over batches + pixel metrics, training=False.  One batch of
         the dataset is one test step per replica: the positive-rate class weight (utils/losses.py:24-27) is taken over the
-        whole per-replica batch, never over a chunk of it."""
+        whole per-replica batch, never over a chunk of it.
+        tta_mask (evaluate --tta): after a batch's test step DeviceModel.forward_tta runs on the same slices, so the pixel and
+        region metrics read the mean over the views; `loss` stays the loss of the untransformed view (the test step's own)."""
         cfg_kw = self.loss.device_cfg()
         for m in self.metrics + self.region_metrics:
             m.reset_state()
@@ -442,6 +454,8 @@ class TFKerasModel:
             out = dm_.eval_step(xb, yb, cfg)
             total += float(out.loss) * len(xb)
             count += len(xb)
+            if tta_mask is not None:
+                dm_.forward_tta(xb, tta_mask, return_prob=False)
             for m in self.metrics:
                 m.update_state(dm_, yb)
             for spec, ms in region_groups:
@@ -549,16 +563,23 @@ class TFKerasModel:
              export_casewise_metrics=False, exam_ds=None, exam_lesions=False, exam_threshold=(0.5,), exam_iou=casewise.EXAM_IOU,
              exam_min_area=0, exam_filter_size=5, exam_resize_factor=1.0, exam_max_lesions=256, exam_link_min_overlap=1,
              surface_ds=None, surface_distances=False, surface_threshold=(0.5,), surface_percentile=casewise.SURFACE_PERCENTILE,
-             surface_min_area=0, surface_filter_size=5, surface_resize_factor=1.0, surface_max_samples=65536):
+             surface_min_area=0, surface_filter_size=5, surface_resize_factor=1.0, surface_max_samples=65536, tta='none'):
         """exam_lesions (`evaluate --exam_lesions`): after every checkpoint's evaluation rank 0 also runs _exam_lesion_pass over
         exam_ds (batches (x, y, paths, sliceIDs), a data set of its own: viz_ds is not needed) and writes exam_lesion_results.csv,
         exam_lesion_cases.csv and exam_lesion_matches.csv under <export_path>/<tag>/; every other file is what it is without it.
         surface_distances (`evaluate --surface_distances`): likewise rank 0 runs _surface_pass over surface_ds (the same kind of data
-        set; the two flags may share one) and writes surface_results.csv, surface_cases.csv and surface_slices.csv there."""
+        set; the two flags may share one) and writes surface_results.csv, surface_cases.csv and surface_slices.csv there.
+        tta (`evaluate --tta`, tta.MODES): with a mode other than 'none' the probabilities every pass reads -- the pixel and region
+        metrics of the per-batch test step, the Visualizer, the exam-lesion and the surface pass -- are the mean over the mode's
+        flip / transpose views (DeviceModel.forward_tta).  The evaluation then runs batch by batch, not over the staged ring;
+        `loss` stays the loss of the untransformed view, and --visualize_sensitivity the gradient of the plain forward."""
         if visualize_sensitivity and not getattr(self.model, 'supports_sensitivity', True):
             raise NotImplementedError('--visualize_sensitivity is not implemented for model: %s (the input-gradient pass covers the '
                                       'U-Net models only)' % self.model_config['model'])
+        tta_mask = None if tta == tta_modes.NONE else tta_modes.mask_of(tta, *_element_shape(dataset)[1:3])
         self._build(dataset)
+        if tta_mask is not None:
+            logging.info('evaluate --tta %s: the evaluation runs batch by batch (the staged ring has no test-time augmentation)', tta)
         ckpt_path = os.path.join(save_path, 'checkpoints')
         if not export_path:
             export_path = os.path.join(save_path, 'tfevents')
@@ -593,21 +614,22 @@ class TFKerasModel:
                 continue
             previous_step = ckpt_step
             self.load(ckpt_path_)
-            rows[ckpt_step] = self._evaluate(dataset, staged=True)
+            rows[ckpt_step] = self._evaluate(dataset, staged=True) if tta_mask is None else \
+                self._evaluate(dataset, staged=False, tta_mask=tta_mask)
             if visualize:
                 self._visualize(viz_ds, ckpt_step, viz_root, export_csv, export_images, overlay, casewise_rows, writer,
-                                sensitivity=bool(visualize_sensitivity))
+                                sensitivity=bool(visualize_sensitivity), tta_mask=tta_mask)
             if exam_pass:
                 for t, new in zip(exam_tables, self._exam_lesion_pass(
                         exam_ds, ckpt_step, [float(t) for t in exam_threshold], exam_iou, exam_link_min_overlap,
                         dict(resize_factor=exam_resize_factor, filter_size=exam_filter_size, min_area=exam_min_area,
-                             max_lesions=exam_max_lesions))):
+                             max_lesions=exam_max_lesions), tta_mask=tta_mask)):
                     t += new
             if surface_pass:
                 for t, new in zip(surface_tables, self._surface_pass(
                         surface_ds, ckpt_step, [float(t) for t in surface_threshold], float(surface_percentile),
                         dict(resize_factor=surface_resize_factor, filter_size=surface_filter_size, min_area=surface_min_area,
-                             max_samples=surface_max_samples))):
+                             max_samples=surface_max_samples), tta_mask=tta_mask)):
                     t += new
         if surface_pass:
             os.makedirs(os.path.join(export_path, tag), exist_ok=True)
@@ -637,7 +659,8 @@ class TFKerasModel:
                     f.write(casewise.table_csv(casewise.column_names(), casewise_rows))
         return rows
 
-    def _visualize(self, viz_ds, step, root, export_csv, export_images, overlay, casewise_rows, writer, sensitivity=False):
+    def _visualize(self, viz_ds, step, root, export_csv, export_images, overlay, casewise_rows, writer, sensitivity=False,
+                   tta_mask=None):
         """One Visualizer pass (callbacks.py process_batch / _emit) over viz_ds batches (x, y, paths, sliceIDs): forward
         (training=False), the per-slice region counts (export_csv), the composite images (export_images), then the files.  The
         probabilities stay on the device; only the counts and the uint8 images come back.  casewise_rows gains one row per slice,
@@ -654,7 +677,7 @@ class TFKerasModel:
             for i in range(0, len(x), dm.max_batch):
                 xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
                 tags = [casewise.tag_of(p, k) for p, k in zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch])]
-                dm.forward(xb, training=False, return_prob=False)
+                _forward_on_device(dm, xb, tta_mask)
                 if export_csv:
                     counts = dm.region_confusion_slices(yb, [spec])
                     for t, c in zip(tags, counts):
@@ -676,7 +699,7 @@ class TFKerasModel:
                             writer.submit(casewise.sensitivity_path(root, t, step, 'images'),
                                           lambda r: casewise.encode_png(casewise.sensitivity_chart(r)), row)
 
-    def _exam_lesion_pass(self, ds, step, thresholds, iou, min_overlap, kw):
+    def _exam_lesion_pass(self, ds, step, thresholds, iou, min_overlap, kw, tta_mask=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --exam_lesions`: per max_batch split one forward whose
         probabilities stay on the device and one DeviceModel.lesion_table_matched per threshold; then per threshold and exam
         casewise.link_lesions on either plane and casewise.match_exam_lesions.  Returns the new lines of (exam_lesion_results.csv,
@@ -701,7 +724,7 @@ class TFKerasModel:
             for i in range(0, len(x), dm.max_batch):
                 xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
                 pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
-                dm.forward(xb, training=False, return_prob=False)
+                _forward_on_device(dm, xb, tta_mask)
                 continues = []
                 for p, k in pk:
                     continues.append(last is not None and p == last[0] and int(k) == last[1] + 1)
@@ -739,7 +762,7 @@ class TFKerasModel:
             results.append(lead + casewise.exam_match_summary(mine_cases))
         return results, cases, matches
 
-    def _surface_pass(self, ds, step, thresholds, percentile, kw):
+    def _surface_pass(self, ds, step, thresholds, percentile, kw, tta_mask=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --surface_distances`: per max_batch split one forward whose
         probabilities stay on the device and one DeviceModel.surface_distances per threshold; only the counts and the boundary
         pixels' squared distances come back.  Then per threshold casewise.surface_slice_values per slice, surface_exam_values per
@@ -756,7 +779,7 @@ class TFKerasModel:
             for i in range(0, len(x), dm.max_batch):
                 xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
                 pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
-                dm.forward(xb, training=False, return_prob=False)
+                _forward_on_device(dm, xb, tta_mask)
                 for ti, thr in enumerate(thresholds):
                     counts, samples, _ = dm.surface_distances(yb, batch=len(xb), threshold=thr, **kw)
                     for b, (p, k) in enumerate(pk):
@@ -787,7 +810,7 @@ class TFKerasModel:
         return np.concatenate(outs) if outs else np.zeros((0,))
 
     def annotate(self, dataset, save_path, output, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
-                 max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1):
+                 max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none'):
         """`annotator predict`: the lesions of slices that have no label.  Loads checkpoint `step` of save_path (None: the latest);
         per batch (x, paths, sliceIDs) of `dataset` (make_dataset(..., include_meta=True, labels=False)) one forward whose
         probabilities stay on the device, then DeviceModel.lesion_table: threshold, filter_size x filter_size opening, components
@@ -800,9 +823,12 @@ class TFKerasModel:
         splits and across batches of `dataset`; the first slice of the run continues nothing.  casewise.link_lesions joins lesions
         that share at least link_min_overlap pixels into exam lesions: exam_lesions.csv (one line per exam lesion) and
         exam_lesion_parts.csv (one line per line of lesions.csv, in its order) are written beside the other files, which are
-        what they are without the flag; the returned dict gains 'exam_lesions'."""
+        what they are without the flag; the returned dict gains 'exam_lesions'.
+        tta (`predict --tta`, tta.MODES): with a mode other than 'none' the one forward per chunk is DeviceModel.forward_tta with the
+        mode's view mask: the tables and masks are those of the mean probability over the views."""
         if self.ctx.world > 1:
             raise RuntimeError('annotate runs in a single process (WORLD_SIZE is %d): start it without the launcher' % self.ctx.world)
+        tta_mask = None if tta == tta_modes.NONE else tta_modes.mask_of(tta, *_element_shape(dataset)[1:3])
         self._build(dataset)
         ckpts = self.get_ckpts(os.path.join(save_path, 'checkpoints'))
         if not ckpts:
@@ -829,7 +855,7 @@ class TFKerasModel:
                 dm = self.device_model
                 for i in range(0, len(x), dm.max_batch):
                     xb = x[i:i + dm.max_batch]
-                    dm.forward(xb, training=False, return_prob=False)
+                    _forward_on_device(dm, xb, tta_mask)
                     pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
                     kw = dict(batch=len(xb), threshold=threshold, resize_factor=resize_factor, filter_size=filter_size,
                               min_area=min_area, max_lesions=max_lesions, mask=bool(export_images))

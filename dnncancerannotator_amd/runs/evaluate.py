@@ -11,7 +11,7 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
              skip_visualization=False, export_casewise_metrics=False, exam_lesions=False, exam_threshold=(0.5,), exam_iou=0.30,
              exam_min_area=0, exam_filter_size=5, exam_resize_factor=1.0, exam_max_lesions=256, exam_link_min_overlap=1,
              surface_distances=False, surface_threshold=(0.5,), surface_percentile=95.0, surface_min_area=0, surface_filter_size=5,
-             surface_resize_factor=1.0, surface_max_samples=65536):
+             surface_resize_factor=1.0, surface_max_samples=65536, tta='none'):
     saved_config = load.load_config(os.path.join(save_path, 'options.yaml'))['config']
     if config:
         config = load._apply_config(saved_config, load.load_config(config))
@@ -30,6 +30,7 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
     surface = dict(surface_ds=meta_ds, surface_distances=surface_distances, surface_threshold=surface_threshold,
                    surface_percentile=surface_percentile, surface_min_area=surface_min_area, surface_filter_size=surface_filter_size,
                    surface_resize_factor=surface_resize_factor, surface_max_samples=surface_max_samples) if surface_distances else {}
+    more = dict(tta=tta) if tta != 'none' else {}      # the keyword of --tta goes to model.eval only with a mode
     model = engine.TFKerasModel(config)
     return model.eval(ds, viz_ds=viz_ds, tag=tag, save_path=os.path.join(save_path), avoid_overwrite=avoid_overwrite,
                       export_path=export_path, export_images=export_images, export_csv=export_csv,
@@ -37,4 +38,4 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
                       overlay=overlay, export_casewise_metrics=export_casewise_metrics, exam_ds=exam_ds, exam_lesions=exam_lesions,
                       exam_threshold=exam_threshold, exam_iou=exam_iou, exam_min_area=exam_min_area, exam_filter_size=exam_filter_size,
                       exam_resize_factor=exam_resize_factor, exam_max_lesions=exam_max_lesions,
-                      exam_link_min_overlap=exam_link_min_overlap, **surface)
+                      exam_link_min_overlap=exam_link_min_overlap, **surface, **more)

@@ -9,13 +9,16 @@ from .train import make_dataset
 
 
 def predict(save_path, data_path, output, config=None, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
-            max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1):
+            max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none'):
     if link_min_overlap < 1:
         raise ValueError('link_min_overlap must be at least 1, got %d' % link_min_overlap)
     saved_config = load.load_config(os.path.join(save_path, 'options.yaml'))['config']
     config = load._apply_config(saved_config, load.load_config(config)) if config else saved_config
     ds = make_dataset(data_path, config.get('data_options', {}).get('eval', {}), training=False, include_meta=True, labels=False)
+    # the keyword of --tta goes to model.annotate only with a mode (tta.mask_of refuses d4 on non-square slices there, before any
+    # checkpoint is read)
+    more = dict(tta=tta) if tta != 'none' else {}
     model = engine.TFKerasModel(config)
     return model.annotate(ds, save_path=save_path, output=output, step=step, threshold=threshold, min_area=min_area,
                           filter_size=filter_size, resize_factor=resize_factor, max_lesions=max_lesions,
-                          export_images=export_images, link_slices=link_slices, link_min_overlap=link_min_overlap)
+                          export_images=export_images, link_slices=link_slices, link_min_overlap=link_min_overlap, **more)

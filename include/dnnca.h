@@ -127,6 +127,31 @@ int dnnca_set_adam(void* model, float beta1, float beta2, float epsilon);
 /* ---- the hot path, host buffers ------------------------------------------------------------------------------ */
 /* UNetAnnotator.call (unet.py:279-282): probabilities [B,H,W,1]; logits = the tensor Keras caches as _keras_logits */
 int dnnca_forward(void* model, const float* x_nhwc, int batch, int training, float* prob_out, float* logit_out);
+/* ---- test-time augmentation (`annotator predict --tta`, `annotator evaluate --tta`; the reference has none) --------------------------
+ * A view is a number k = 4 t + 2 v + h in 0..7 (the dihedral group of the square).  Applied to x [B,H,W,C]: first the flips,
+ * xf[b,i,j,c] = x[b, v ? H-1-i : i, h ? W-1-j : j, c], then, with t, the transpose xk[b,i,j,c] = xf[b,j,i,c] (H == W).  `views` is a
+ * bit mask in 1..255: bit k selects view k (0x0F: identity and the three flips; 0xFF: all eight).
+ * dnnca_forward_tta stages x as dnnca_forward does and runs, for every selected view in ascending order, one inference forward
+ * (training = 0) on that view of the batch; with p_k the sigmoid of its logits (the expression of dnnca_forward), i' = v ? H-1-i : i
+ * and j' = h ? W-1-j : j the model's probability buffer receives
+ *     prob[b,i,j] = (sum over the selected k, ascending, in float32, of p_k[b, t ? (j',i') : (i',j')]) / n      (float32 division)
+ * n = the number of views.  No atomics: bit-identical from run to run.  Every consumer of "the last forward's probabilities"
+ * (dnnca_get_prob, dnnca_pixel_confusion, dnnca_region_confusion*, dnnca_lesion_table*, dnnca_surface_distances,
+ * dnnca_render_composite) then works on the mean; the staged batch that dnnca_render_composite and dnnca_input_sensitivity read is
+ * the untransformed x (the views live in a buffer of their own, allocated for max_batch by the first call that needs it).  The
+ * logits buffer holds the LAST selected view's logits, in that view's geometry, not the mean's.  Variables, BatchNorm state and
+ * optimizer slots are untouched.  prob_out: NULL, or host [batch, H, W]; synchronises when it is given.
+ * DNNCA_EINVAL, with nothing launched and nothing allocated: views of 0 or above 255; a transposed view (bits 4..7) when H != W; a
+ * model whose output size is not its input size; batch outside [1, max_batch]. */
+int dnnca_forward_tta(void* model, const float* x_nhwc, int batch, unsigned views, float* prob_out /* nullable */);
+/* the two kernels of dnnca_forward_tta alone, on host buffers [batch, h, w(, c)] of any plane size (the library grows its own device
+ * buffers); 1 <= batch <= max_batch, at most 65535 rows; both synchronise.
+ *   dnnca_tta_view_of   dst = view `view` (0..7) of src [batch, h, w, c], c >= 1
+ *   dnnca_tta_mean_of   prob_out [batch, h, w] = the mean above of the planes vals [n, batch, h, w], which hold the selected views'
+ *                       outputs in ascending view order: probabilities (is_logits = 0), or logits that first go through the sigmoid
+ * Both refuse what dnnca_forward_tta refuses, with h != w standing in for H != W. */
+int dnnca_tta_view_of(void* model, const float* src, int batch, int h, int w, int c, int view, float* dst);
+int dnnca_tta_mean_of(void* model, const float* vals, int batch, int h, int w, unsigned views, int is_logits, float* prob_out);
 /* keras Model.train_step under engine.py:126-135: forward(training=True) + TFWeightedCrossentropy (losses.py:60-72)
  * + backward + [RCCL all-reduce] + Adam apply with learning rate lr (LearningRateScheduler, engine.py:97-100) */
 int dnnca_train_step(void* model, const float* x_nhwc, const float* y_hw, int batch, float lr,

@@ -13,6 +13,7 @@ and prediction plane) plus pairs, match and count.
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --link            # the linked legs on it
     python tools/lesion_rate.py --link --match --surface         # also: surface_distances against lesion_table_matched
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --link --match    # the matched legs on it
+    python tools/lesion_rate.py --tta flips         # test-time augmentation alone: forward_tta against the plain forward
 
 --link adds the cost of linking neighbouring slices: lesion_table_linked against lesion_table (wall time per call, device time of
 the three link launches), its worst case for the pair table (a checkerboard on itself: every other pixel a lesion of its own in
@@ -25,6 +26,10 @@ per batch, the flags from the slice numbers -- with the linked and the matched c
 --surface adds the cost of `evaluate --surface_distances`: surface_distances (the prediction plane's shared stages, the label's
 prep, then surface_edges / surface_cols / surface_sample) per call with its launches event-bracketed, and a forward + surface pass
 against a forward + matched pass over the same batches, alternated in one process.
+
+--tta MODE (flips, d4) measures DeviceModel.forward_tta against DeviceModel.forward on the same host batch and nothing else: wall time
+per call (both upload the batch once), device time per call (every launch event-bracketed) and the share of the two kernels of
+kernels_tta.hip (tta_view_in, tta_accumulate) in it.
 
 The probabilities are drawn: the synthetic labels' discs at 0.55 .. 0.95 on a background of 0 .. 0.45 (a few lesions per slice,
 as a trained model gives), put into the model's probability buffer by pixel_confusion_of."""
@@ -47,6 +52,7 @@ ap.add_argument('--yardstick', action='store_true', help='region_confusion_slice
 ap.add_argument('--link', action='store_true', help='also measure lesion_table_linked and annotate(link_slices=True)')
 ap.add_argument('--match', action='store_true', help='also measure lesion_table_matched against lesion_table_linked (needs --link)')
 ap.add_argument('--surface', action='store_true', help='also measure surface_distances against lesion_table_matched (needs --match)')
+ap.add_argument('--tta', default=None, metavar='MODE', help='measure forward_tta(MODE) against the plain forward, and nothing else')
 ap.add_argument('--out', default=None, help='append the report to this file as well')
 a = ap.parse_args()
 if a.yardstick:
@@ -63,6 +69,10 @@ if a.surface and not a.match:
     ap.error('--surface needs --link --match')
 if not a.surface:
     _lib.SIGNATURES.pop('dnnca_surface_distances', None)         # nor does one from before the boundary distances
+
+if not a.tta:
+    for name in ('dnnca_forward_tta', 'dnnca_tta_view_of', 'dnnca_tta_mean_of'):
+        _lib.SIGNATURES.pop(name, None)                          # nor does one from before test-time augmentation
 
 from dnncancerannotator_amd import device as dev                  # noqa: E402
 from dnncancerannotator_amd.data import ArrayDataset              # noqa: E402
@@ -115,7 +125,50 @@ ds = ArrayDataset(np.concatenate([x] * NB), None, B, meta_path='/synthetic/p0/e0
     ArrayDataset(x, y, B)
 e._build(ds)
 dm = e.device_model
-say('%s: %d x %d x %d, library %s' % ('yardstick' if a.yardstick else 'lesion table', B, S, S, os.path.basename(_lib.LIB_PATH)))
+say('%s: %d x %d x %d, library %s' % ('yardstick' if a.yardstick else 'test-time augmentation' if a.tta else 'lesion table', B, S, S,
+                                      os.path.basename(_lib.LIB_PATH)))
+if a.tta:
+    from dnncancerannotator_amd import tta as tta_modes
+    views = tta_modes.mask_of(a.tta, S, S)
+    n_views = bin(views).count('1')
+
+    def plain():
+        dm.forward(x, return_prob=False)
+
+    def augmented():
+        dm.forward_tta(x, views, return_prob=False)
+        dm.sync()
+
+    def device_rows(fn):
+        dm.profile_reset()
+        dm.profile_enable(1)
+        for _ in range(R):
+            fn()
+        dm.sync()
+        rows = dm.profile()
+        dm.profile_enable(0)
+        dm.profile_reset()
+        return rows
+    took = {}
+    for name, fn in (('forward', plain), ('forward_tta', augmented)) * 2:          # alternated
+        took.setdefault(name, []).append(wall(fn))
+    for name, runs in took.items():
+        for med, lo, hi in runs:
+            say('  %-28s %.3f ms per call, upload included (median of %d; %.3f .. %.3f)' % (name, med, R, lo, hi))
+    say('  forward_tta(%s, %d views) / forward, wall: %.2f' % (a.tta, n_views, min(r[0] for r in took['forward_tta']) /
+                                                                min(r[0] for r in took['forward'])))
+    rows_p, rows_t = device_rows(plain), device_rows(augmented)
+    dev_p, dev_t = sum(r[2] for r in rows_p) / R, sum(r[2] for r in rows_t) / R
+    say('  device time per call (event-bracketed launches): forward %.3f ms, forward_tta %.3f ms: ratio %.2f' % (dev_p, dev_t, dev_t / dev_p))
+    mine = [r for r in rows_t if r[0].startswith('tta_')]
+    for name, n, ms, by, fl in mine:
+        say('    %-22s launches/call %4.1f  %9.2f us per launch  %7.1f GB/s' % (name, n / R, ms / n * 1e3, by / (ms / n * 1e-3) / 1e9))
+    say('    share of the two tta kernels in forward_tta: %.2f %%' % (100.0 * sum(r[2] for r in mine) / R / dev_t))
+    dm.close()
+    if a.out:
+        with open(a.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    sys.exit(0)
 dm.pixel_confusion_of(prob, y, [0.5])                             # the drawn probabilities into the model's buffer
 spec = ([0.5], 0.30, 1.0, 5)
 med, lo, hi = wall(lambda: dm.region_confusion_slices(y, [spec]))
