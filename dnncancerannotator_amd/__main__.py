@@ -76,6 +76,11 @@ def build_parser(prog='python3 -m annotator'):
     e.add_argument('--tta', choices=TTA_MODES, default=argparse.SUPPRESS,
                    help='test-time augmentation: every probability read is the mean over the flip views (flips) or over all eight '
                         'flip / transpose views (d4, square slices only); default: none')
+    e.add_argument('--uncertainty', action='store_true', default=argparse.SUPPRESS,
+                   help='with --tta flips / d4: how much the views disagree (their standard deviation per pixel) on wrong and on right '
+                        'pixels: also write uncertainty_results.csv and uncertainty_slices.csv')
+    e.add_argument('--uncertainty_threshold', type=float, nargs='+', default=argparse.SUPPRESS, metavar='T',
+                   help='probability threshold(s) of --uncertainty (default: 0.5)')
     p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
     p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
     p.add_argument('--data_path', nargs='+', required=True)
@@ -96,6 +101,9 @@ def build_parser(prog='python3 -m annotator'):
     p.add_argument('--tta', choices=TTA_MODES, default=argparse.SUPPRESS,
                    help='test-time augmentation: the lesions of the mean probability over the flip views (flips) or over all eight '
                         'flip / transpose views (d4, square slices only); default: none')
+    p.add_argument('--uncertainty', action='store_true', default=argparse.SUPPRESS,
+                   help='with --tta flips / d4: how much the views disagree (their standard deviation per pixel) per lesion and slice: '
+                        'also write lesion_uncertainty.csv, slice_uncertainty.csv and, with --export_images, uncertainty.png')
     return parser
 
 

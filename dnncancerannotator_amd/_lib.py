@@ -97,6 +97,24 @@ class SurfaceSample(C.Structure):                  # dnnca_surface_sample (16 by
 SURFACE_SAMPLE_DTYPE = np.dtype([('slice', '<i4'), ('side', '<i4'), ('pixel', '<i4'), ('d2', '<i4')])
 
 
+class LesionSpread(C.Structure):                   # dnnca_lesion_spread (24 bytes, no padding)
+    _fields_ = [('slice', C.c_int32), ('row', C.c_int32), ('area', C.c_int32), ('max_spread', C.c_float), ('sum_spread_q24', C.c_uint64)]
+
+
+class SliceSpread(C.Structure):                    # dnnca_slice_spread (16 bytes, no padding)
+    _fields_ = [('pixels', C.c_int32), ('max_spread', C.c_float), ('sum_spread_q24', C.c_uint64)]
+
+
+class SpreadOutcome(C.Structure):                  # dnnca_spread_outcome (64 bytes): classes TN, FP, FN, TP
+    _fields_ = [('n', C.c_uint64 * 4), ('sum_q24', C.c_uint64 * 4)]
+
+
+# DeviceModel.lesion_table_spread / spread_by_outcome return structured arrays of these dtypes
+LESION_SPREAD_DTYPE = np.dtype([('slice', '<i4'), ('row', '<i4'), ('area', '<i4'), ('max_spread', '<f4'), ('sum_spread_q24', '<u8')])
+SLICE_SPREAD_DTYPE = np.dtype([('pixels', '<i4'), ('max_spread', '<f4'), ('sum_spread_q24', '<u8')])
+SPREAD_OUTCOME_DTYPE = np.dtype([('n', '<u8', (4,)), ('sum_q24', '<u8', (4,))])
+
+
 class LesionPlaneOut(C.Structure):                 # dnnca_lesion_plane_out: buffers and capacities in, counts out
     _fields_ = [('rows', C.POINTER(LesionRow)), ('rows_capacity', C.c_int64), ('n_rows', C.c_int64), ('totals', C.POINTER(C.c_int32)),
                 ('links', C.POINTER(LesionLink)), ('links_capacity', C.c_int64), ('n_links', C.c_int64)]
@@ -134,6 +152,9 @@ SIGNATURES = {
     'dnnca_forward_tta': (C.c_int, [_VP, _FP, C.c_int, C.c_uint, _FP]),
     'dnnca_tta_view_of': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _FP]),
     'dnnca_tta_mean_of': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, _FP]),
+    'dnnca_forward_tta_spread': (C.c_int, [_VP, _FP, C.c_int, C.c_uint, _FP, _FP]),
+    'dnnca_tta_spread_of': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, _FP, _FP]),
+    'dnnca_get_tta_spread': (C.c_int, [_VP, C.c_int, _FP]),
     'dnnca_train_step': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_float, C.POINTER(LossCfg), C.POINTER(StepOut)]),
     'dnnca_eval_step': (C.c_int, [_VP, _FP, _FP, C.c_int, C.POINTER(LossCfg), C.POINTER(StepOut), _FP]),
     'dnnca_dev_alloc': (C.c_int, [C.POINTER(_VP), C.c_size_t]),
@@ -175,6 +196,10 @@ SIGNATURES = {
     'dnnca_lesion_table': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
                                      C.POINTER(C.c_int32)]),
+    'dnnca_lesion_table_spread': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
+                                            C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
+                                            C.POINTER(C.c_int32), _FP, C.POINTER(LesionSpread), C.POINTER(SliceSpread)]),
+    'dnnca_spread_by_outcome': (C.c_int, [_VP, _FP, _FP, _FP, C.c_int, C.c_int, C.c_int, _FP, C.c_int, C.POINTER(SpreadOutcome)]),
     'dnnca_lesion_table_linked': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                             C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
                                             C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(LesionLink), C.c_int64,

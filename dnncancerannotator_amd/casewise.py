@@ -406,6 +406,67 @@ def surface_summary(slice_values, exam_values):
             [mean(v[i] for v in both) for i in (8, 9, 10, 11)] + [mean(v[i] for v in exams) for i in (-3, -2, -1)])
 
 
+# ---- `--uncertainty`: how much the test-time-augmentation views disagree ------------------------------------------------------------
+# DeviceModel.lesion_table_spread and spread_by_outcome give integer sums of rint(spread * 2^24) and float32 maxima; a mean is
+# sum / pixels / 2^24 in float64 (repr), a maximum is written with the 9 digits that give the float32 back.
+LESION_UNCERTAINTY_COLUMNS = ['exam', 'slice', 'lesion', 'mean_spread', 'max_spread']
+SLICE_UNCERTAINTY_COLUMNS = ['exam', 'slice', 'mean_spread', 'max_spread', 'mean_spread_in_lesions', 'truncated']
+OUTCOMES = ['tn', 'fp', 'fn', 'tp']      # class 2 (y > 0.5) + (prob >= threshold)
+UNCERTAINTY_SLICE_COLUMNS = (['exam', 'slice'] + ['%s_px' % o for o in OUTCOMES] + ['mean_spread_%s' % o for o in OUTCOMES] +
+                             ['mean_spread_wrong', 'mean_spread_right', 'wrong_to_right'])
+UNCERTAINTY_RESULT_COLUMNS = ['slices'] + UNCERTAINTY_SLICE_COLUMNS[2:]
+UNCERTAINTY_WHITE = 510.0        # uncertainty.png: grey = min(255, rint(spread * 510)), a spread of 0.5 is white
+
+
+def _mean_q24(total, pixels):
+    return repr(int(total) / int(pixels) / Q24) if int(pixels) else ''
+
+
+def lesion_uncertainty_values(exam, slice_id, row, srow):
+    """the lesion_uncertainty.csv line of one lesion: `row` its record of lesion_table's rows, `srow` the spread record beside it"""
+    if (int(srow['row']), int(srow['area'])) != (int(row['row']), int(row['area'])):
+        raise ValueError('spread record of lesion %d (%d px) beside lesion %d (%d px)' % (srow['row'], srow['area'], row['row'], row['area']))
+    return [exam, int(slice_id), int(row['row']), _mean_q24(srow['sum_spread_q24'], row['area']), '%.9g' % float(srow['max_spread'])]
+
+
+def slice_uncertainty_values(exam, slice_id, rows, srows, total, stotal):
+    """the slice_uncertainty.csv line of one slice: mean and maximum over every pixel of the analysed plane (`stotal`), the mean over
+    the pixels of the listed lesions (blank without any), truncated as in slices.csv"""
+    area = sum(int(r['area']) for r in rows)
+    return [exam, int(slice_id), _mean_q24(stotal['sum_spread_q24'], stotal['pixels']), '%.9g' % float(stotal['max_spread']),
+            _mean_q24(sum(int(r['sum_spread_q24']) for r in srows), area), int(int(total) > len(rows))]
+
+
+def _outcome_values(n, q):
+    """pixels n [4] and q24 sums q [4] of TN, FP, FN, TP -> the values from tn_px on"""
+    n, q = [int(v) for v in n], [int(v) for v in q]
+    wrong, right = _mean_q24(q[1] + q[2], n[1] + n[2]), _mean_q24(q[0] + q[3], n[0] + n[3])
+    ratio = repr(float(wrong) / float(right)) if wrong and right and float(right) > 0 else ''
+    return n + [_mean_q24(q[c], n[c]) for c in range(4)] + [wrong, right, ratio]
+
+
+def outcome_slice_values(exam, slice_id, outcome):
+    """one entry of spread_by_outcome (n [4], sum_q24 [4]) -> the uncertainty_slices.csv values of its slice"""
+    return [exam, int(slice_id)] + _outcome_values(outcome['n'], outcome['sum_q24'])
+
+
+def outcome_summary(outcomes):
+    """the entries of all slices at one threshold -> the uncertainty_results.csv values: the sums over the slices"""
+    n = [sum(int(o['n'][c]) for o in outcomes) for c in range(4)]
+    q = [sum(int(o['sum_q24'][c]) for o in outcomes) for c in range(4)]
+    return [len(outcomes)] + _outcome_values(n, q)
+
+
+def uncertainty_image(spread):
+    """float32 spread [h, w] -> uint8 grey: min(255, rint(spread * 510)) (the product is exact in float64)"""
+    return np.minimum(255, np.rint(np.asarray(spread, np.float32).astype(np.float64) * UNCERTAINTY_WHITE)).astype(np.uint8)
+
+
+def uncertainty_path(root, tag):
+    """<root>/<last 3 components of the exam path>/<sliceID %02d>/uncertainty.png"""
+    return os.path.join(export_dir(root, '', tag), 'uncertainty.png')
+
+
 def plain_csv(names, rows):
     """a header line and one line per row, csv-module quoting, no index column"""
     return _csv([list(names)] + [list(r) for r in rows])

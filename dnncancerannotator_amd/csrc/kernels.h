@@ -70,6 +70,11 @@ void g_tta_view_in(hipStream_t s, const float* src, float* dst, int B, int H, in
 // sigmoid_of_logit(src).  first: prob = p, otherwise prob += p; last: the sum is then divided by n.  prob must not alias src
 void g_tta_accumulate(hipStream_t s, const float* src, float* prob, int B, int H, int W, int k, bool is_logits, bool first, bool last,
                       int n);
+// g_tta_accumulate plus the views' spread: view number `pos` (0 .. n - 1, in launch order) of n.  mom: three planes of `plane` floats
+// of running state (the first view's value, the sums of the differences to it and of their squares); the last view writes the mean
+// into prob (bit for bit g_tta_accumulate's) and sqrt((1/n) sum (p_k - mean)^2) into spread.  No buffer may alias another
+void g_tta_moments(hipStream_t s, const float* src, float* prob, float* mom, float* spread, size_t plane, int B, int H, int W, int k,
+                   bool is_logits, int pos, int n);
 
 void g_l2(hipStream_t s, size_t n, const float* w, float* g, float l2, double* scalars);   // g += 2*l2*w ; penalty += l2*sum w^2
 // writes [loss, positive_rate, weight, ymin, ymax] floats to out5 (device) from the scalar block

@@ -24,7 +24,8 @@
 //                   as region_prep), * 255 truncated to uint8; the panels are read in place through an index map, four output
 //                   bytes per thread and one 32-bit store
 //
-// The lesion table of `annotator predict` (lesion_scan / lesion_stats / lesion_mask), its links and pairs (lesion_link, lesion_match)
+// The lesion table of `annotator predict` (lesion_scan / lesion_stats / lesion_mask), its links and pairs (lesion_link, lesion_match),
+// the spread of the test-time-augmentation views per lesion, slice and pixel outcome (lesion_spread, spread_outcome)
 // and the boundary distances of `evaluate --surface_distances` (surface_edges / surface_cols / surface_sample) start from the same
 // prep / open / ccl / sizes launches; each is described above its kernels.
 #include <math.h>
@@ -573,6 +574,123 @@ __global__ __launch_bounds__(RB) void k_lesion_mask(const int* __restrict__ L, c
     for (int e = 0; e < 4; ++e)
         if (root[e] >= 0 && row[root[e]] >= 0) packed |= 0xffu << (8 * e);
     out[word] = packed;
+}
+
+// ---- the spread of the test-time-augmentation views under the lesion table (dnnca_lesion_table_spread) and per pixel outcome
+// (dnnca_spread_by_outcome).  A spread enters every sum as rint(max(spread', 0) * 2^24) and every maximum through its bits.
+struct SpreadAcc {                       // a lesion's row or a slice's total, zeroed by a memset
+    unsigned long long sq;
+    unsigned area, mx;
+};
+
+// lesion_stats for the spread plane.  grid (ceil(hw / (RB kSpreadU)), slices): a block walks kSpreadU runs of RB pixels of ONE slice.
+// Every pixel of a kept, numbered component adds its spread -- read through the resize_at that the probability went through -- to its
+// row, the lanes of a wave grouped by row as in lesion_stats; and EVERY pixel adds to the slice's total, kept in registers over the
+// block's runs and reduced over the wave and the block: three atomics per block (64 blocks per slice at 512 x 512; one block per
+// 256 pixels had 1024 blocks queue up on a slice's one cache line and took 232 us at 8 x 512 x 512).
+constexpr int kSpreadU = 16;
+__global__ __launch_bounds__(RB) void k_lesion_spread(const float* __restrict__ src, Resize r, const int* __restrict__ L,
+                                                      const int* __restrict__ row, int cap, SpreadAcc* __restrict__ acc,
+                                                      SpreadAcc* __restrict__ tot) {
+    __shared__ unsigned long long wsq[RB / 64];
+    __shared__ unsigned wmx[RB / 64];
+    const int hw = r.out_h * r.out_w, b = blockIdx.y;
+    const size_t g0 = (size_t)b * hw;
+    const float* plane = src + (size_t)b * r.in_h * r.in_w;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int p0 = blockIdx.x * (RB * kSpreadU) + (int)threadIdx.x;
+    unsigned long long tsq = 0;
+    unsigned tmx = 0;
+    for (int u = 0; u < kSpreadU; ++u) {
+        const int p = p0 + u * RB;
+        if (p - (int)threadIdx.x >= hw) break;           // the whole run lies behind the slice: the same for every thread of the block
+        bool on = false;
+        unsigned long long q = 0;
+        unsigned key = 0, bits = 0;
+        if (p < hw) {
+            const int y = p / r.out_w, x = p - y * r.out_w;
+            const float v = fmaxf(resize_at(plane, r, y, x), 0.f);
+            bits = __float_as_uint(v);
+            q = (unsigned long long)rintf(v * 16777216.f);
+            tsq += q;
+            tmx = max(tmx, bits);
+            const int root = L[g0 + p];
+            if (root >= 0) {
+                const int rw = row[root];
+                if (rw >= 0 && rw < cap) {
+                    on = true;
+                    key = (unsigned)rw;
+                }
+            }
+        }
+        unsigned long long pending = __ballot(on);
+        while (pending) {
+            const int leader = __ffsll((long long)pending) - 1;
+            const unsigned k0 = __shfl(key, leader);
+            const bool mine = on && key == k0;
+            const unsigned long long same = __ballot(mine);
+            const unsigned long long sq = wave_sum64(mine ? q : 0ull);
+            const unsigned mx = wave_max(mine ? bits : 0u);
+            if (lane == leader) {
+                SpreadAcc* a = acc + (size_t)b * cap + k0;
+                atomicAdd(&a->area, (unsigned)__popcll(same));
+                atomicAdd(&a->sq, sq);
+                atomicMax(&a->mx, mx);
+            }
+            if (mine) on = false;
+            pending &= ~same;
+        }
+    }
+    tsq = wave_sum64(tsq);
+    tmx = wave_max(tmx);
+    if (lane == 0) wsq[wv] = tsq, wmx[wv] = tmx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < RB / 64; ++w) tsq += wsq[w], tmx = max(tmx, wmx[w]);
+        const int first = blockIdx.x * (RB * kSpreadU);
+        SpreadAcc* a = tot + b;
+        atomicAdd(&a->area, (unsigned)min(RB * kSpreadU, hw - first));
+        atomicAdd(&a->sq, tsq);
+        atomicMax(&a->mx, tmx);
+    }
+}
+
+// grid (ceil(hw / (RB kOutcomeU)), thresholds, slices).  A pixel's class is 2 (y > 0.5) + (prob >= threshold): TN 0, FP 1, FN 2, TP 3.
+// A thread keeps the four counts and the four q24 sums of its kOutcomeU pixels in registers, a wave and then the block reduce them,
+// and eight threads add what is not zero to out [thresholds][slices][8] (n[4], then sum_q24[4]): at most eight atomics per block.
+constexpr int kOutcomeU = 16;
+__global__ __launch_bounds__(RB) void k_spread_outcome(const float* __restrict__ prob, const float* __restrict__ spread,
+                                                       const float* __restrict__ y, const float* __restrict__ thr, size_t hw,
+                                                       unsigned long long* __restrict__ out) {
+    __shared__ unsigned long long part[RB / 64][8];
+    const float th = thr[blockIdx.y];
+    const size_t base = (size_t)blockIdx.z * hw, p0 = (size_t)blockIdx.x * RB * kOutcomeU + threadIdx.x;
+    unsigned long long v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int u = 0; u < kOutcomeU; ++u) {
+        const size_t p = p0 + (size_t)u * RB;
+        if (p < hw) {
+            const int cls = (y[base + p] > 0.5f ? 2 : 0) + (prob[base + p] >= th ? 1 : 0);
+            const unsigned long long q = (unsigned long long)rintf(fmaxf(spread[base + p], 0.f) * 16777216.f);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                v[c] += cls == c ? 1ull : 0ull;
+                v[4 + c] += cls == c ? q : 0ull;
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const unsigned long long s = wave_sum64(v[c]);
+        if (lane == 0) part[wv][c] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        unsigned long long s = 0;
+        for (int w = 0; w < RB / 64; ++w) s += part[w][threadIdx.x];
+        if (s) atomicAdd(out + ((size_t)blockIdx.y * gridDim.z + blockIdx.z) * 8 + threadIdx.x, s);
+    }
 }
 
 // ---- links between neighbouring slices (dnnca_lesion_table_linked).  A pixel's lesion is row[L[g]]: the row number of its root,
@@ -1274,10 +1392,13 @@ struct LesionWs {                        // carve-up of the workspace for nb sli
     unsigned* ysp;
     float* ythr;
     LesionAcc* yacc;
+    // spread calls only, behind everything else: the spread rows beside acc and the slices' totals
+    SpreadAcc *sacc, *stot;
     size_t bytes;
 };
 
-static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap, size_t links_per_slice = 0, bool matched = false) {
+static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap, size_t links_per_slice = 0, bool matched = false,
+                              bool spread = false) {
     const size_t n = nb * hw;
     LesionWs w;
     char* p = (char*)base;
@@ -1310,6 +1431,11 @@ static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap, size
         w.ytot = (int*)take(nb * 4);
         w.ythr = (float*)take(4);
         w.yacc = (LesionAcc*)take(nb * cap * sizeof(LesionAcc));
+    }
+    w.sacc = nullptr, w.stot = nullptr;
+    if (spread) {
+        w.sacc = (SpreadAcc*)take(nb * cap * sizeof(SpreadAcc));
+        w.stot = (SpreadAcc*)take(nb * sizeof(SpreadAcc));
     }
     w.bytes = off;
     return w;
@@ -1349,6 +1475,12 @@ struct LesionMatchIO {                   // what a matched call adds to a linked
     int64_t* n_links;
     dnnca_lesion_pair* pairs;
     int64_t* n_pairs;
+};
+
+struct LesionSpreadIO {                  // what a spread call adds: the spread plane (device [batch, h, w]) and the host outputs
+    const float* spread;
+    dnnca_lesion_spread* srows;
+    dnnca_slice_spread* stotals;
 };
 
 static_assert(sizeof(LesionLink) == sizeof(dnnca_lesion_pair), "the device list is copied into the caller's records");
@@ -1410,12 +1542,46 @@ static int lesion_rows_read(Model* M, const LesionAcc* acc_dev, const std::vecto
     return DNNCA_OK;
 }
 
+// the spread rows beside the rows that lesion_rows_read has just delivered (srows: the record of the chunk's first row) and the
+// slices' totals; synchronises
+static int lesion_spread_read(Model* M, const SpreadAcc* sacc_dev, const SpreadAcc* stot_dev, const std::vector<int>& tot, int b0, size_t cap,
+                              dnnca_lesion_spread* srows, dnnca_slice_spread* stotals) {
+    hipStream_t s = M->stream;
+    const int nb = (int)tot.size();
+    std::vector<size_t> first(nb + 1, 0);
+    for (int b = 0; b < nb; ++b) first[b + 1] = first[b] + std::min<size_t>((size_t)std::max(tot[b], 0), cap);
+    std::vector<SpreadAcc> acc(first[nb] + nb);          // the rows, then the totals
+    for (int b = 0; b < nb; ++b)
+        if (first[b + 1] > first[b])
+            HIP_TRY(hipMemcpyAsync(acc.data() + first[b], sacc_dev + (size_t)b * cap, (first[b + 1] - first[b]) * sizeof(SpreadAcc),
+                                   hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(acc.data() + first[nb], stot_dev, (size_t)nb * sizeof(SpreadAcc), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < nb; ++b) {
+        for (size_t r = first[b]; r < first[b + 1]; ++r) {
+            dnnca_lesion_spread& o = srows[r];
+            o.slice = b0 + b;
+            o.row = (int32_t)(r - first[b]);
+            o.area = (int32_t)acc[r].area;
+            memcpy(&o.max_spread, &acc[r].mx, 4);
+            o.sum_spread_q24 = acc[r].sq;
+        }
+        const SpreadAcc& t = acc[first[nb] + b];
+        dnnca_slice_spread& o = stotals[b0 + b];
+        o.pixels = (int32_t)t.area;
+        memcpy(&o.max_spread, &t.mx, 4);
+        o.sum_spread_q24 = t.sq;
+    }
+    return DNNCA_OK;
+}
+
 // the chunk loop of lesion_table, lesion_table_linked (link != nullptr: the three link launches behind every chunk's table) and
 // lesion_table_matched (link and match: the label plane's table as well, then lesion_match / lesion_link_emit over the three
 // sets of tables / lesion_match_carry in the place of the link launches).  A matched chunk holds two planes and three sets of
 // tables and lists: its slices are a third of a linked chunk's (region_chunk with T = 3), which changes no result
 static int lesion_run(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows, int64_t* n_rows,
-                      int32_t* totals, uint8_t* mask, bool want_mask, const LesionLinkIO* link, const LesionMatchIO* match = nullptr) {
+                      int32_t* totals, uint8_t* mask, bool want_mask, const LesionLinkIO* link, const LesionMatchIO* match = nullptr,
+                      const LesionSpreadIO* sp = nullptr) {
     DN_TRY(region_state(M));
     RegionState& R = *M->region;
     if (match) {
@@ -1432,7 +1598,7 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
     const size_t per_slice = link ? (size_t)a.links_per_slice() : 0;
     const int sets = match ? 3 : 1;
     const int chunk = (int)region_chunk(match ? 3 : 1, hw, batch);
-    if (!M->dry) DN_TRY(region_ws_reserve(R, lesion_layout(nullptr, chunk, hw, cap, per_slice, match != nullptr).bytes));
+    if (!M->dry) DN_TRY(region_ws_reserve(R, lesion_layout(nullptr, chunk, hw, cap, per_slice, match != nullptr, sp != nullptr).bytes));
     if (link && !match && !M->dry) {     // from here on the carry is this call's: valid again once every chunk has gone through
         R.carry_valid = false;
         if (hw > R.carry_n) {            // (a set continues[0] was checked against a carry of this size: that one is never regrown)
@@ -1463,7 +1629,7 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
         const size_t n = (size_t)nb * hw;
-        const LesionWs ws = lesion_layout(R.ws, nb, hw, cap, per_slice, match != nullptr);
+        const LesionWs ws = lesion_layout(R.ws, nb, hw, cap, per_slice, match != nullptr, sp != nullptr);
         const float* pb = prob + (size_t)b0 * h * w;
         const float* yb = match ? match->y + (size_t)b0 * h * w : nullptr;
         if (!M->dry) HIP_TRY(hipMemcpyAsync(ws.thr, &a.threshold, 4, hipMemcpyHostToDevice, s));   // `a` outlives the chunk's sync
@@ -1481,6 +1647,16 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
         if (want_mask)
             LAUNCH(M, "lesion_mask", n * 9.0, 0,
                    hipLaunchKernelGGL(k_lesion_mask, dim3(nblocks((n + 3) / 4)), dim3(RB), 0, s, ws.lp, ws.row, n, ws.mask));
+        if (sp) {                        // the spread plane under the prediction plane's rows
+            if (!M->dry) {
+                HIP_TRY(hipMemsetAsync(ws.sacc, 0, (size_t)nb * cap * sizeof(SpreadAcc), s));
+                HIP_TRY(hipMemsetAsync(ws.stot, 0, (size_t)nb * sizeof(SpreadAcc), s));
+            }
+            const dim3 grid((unsigned)((hw + RB * kSpreadU - 1) / (RB * kSpreadU)), nb);
+            LAUNCH(M, "lesion_spread", n * 8.0 + (double)nb * h * w * 4, 0,
+                   hipLaunchKernelGGL(k_lesion_spread, grid, dim3(RB), 0, s, sp->spread + (size_t)b0 * h * w, rz, ws.lp, ws.row, (int)cap,
+                                      ws.sacc, ws.stot));
+        }
         if (match) {                     // the label plane: label' > 0.5, no opening, no area filter
             if (!M->dry) HIP_TRY(hipMemcpyAsync(ws.ythr, &kLabelThreshold, 4, hipMemcpyHostToDevice, s));
             LAUNCH(M, "region_prep", n * 4.0 + (double)nb * h * w * 4, 0,
@@ -1538,7 +1714,9 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
                 HIP_TRY(hipMemcpyAsync(found[t].data(), ws.list + (size_t)t * nb * per_slice, (size_t)n_found[t] * sizeof(LesionLink),
                                        hipMemcpyDeviceToHost, s));
         }
+        const int64_t out_before = out;
         DN_TRY(lesion_rows_read(M, ws.acc, tot, b0, cap, acc, rows, out, totals));
+        if (sp) DN_TRY(lesion_spread_read(M, ws.sacc, ws.stot, tot, b0, cap, sp->srows + out_before, sp->stotals));
         if (match) DN_TRY(lesion_rows_read(M, ws.yacc, ytot, b0, cap, acc, match->rows, out_true, match->totals));
         for (int t = 0; t < sets && link; ++t) {
             std::sort(found[t].begin(), found[t].end(), [](const LesionLink& x, const LesionLink& y) {
@@ -1572,6 +1750,34 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
 int lesion_table(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows, int64_t* n_rows,
                  int32_t* totals, uint8_t* mask, bool want_mask) {
     return lesion_run(M, prob, batch, h, w, a, rows, n_rows, totals, mask, want_mask, nullptr);
+}
+
+int lesion_table_spread(Model* M, const float* prob, const float* spread, int batch, int h, int w, const LesionArgs& a,
+                        dnnca_lesion_row* rows, int64_t* n_rows, int32_t* totals, uint8_t* mask, bool want_mask,
+                        dnnca_lesion_spread* srows, dnnca_slice_spread* stotals) {
+    const LesionSpreadIO io{spread, srows, stotals};
+    return lesion_run(M, prob, batch, h, w, a, rows, n_rows, totals, mask, want_mask, nullptr, nullptr, &io);
+}
+
+int spread_by_outcome(Model* M, const float* prob, const float* spread, const float* y, int batch, size_t hw, const float* thresholds,
+                      int n_thresholds, dnnca_spread_outcome* out) {
+    DN_TRY(region_state(M));
+    RegionState& R = *M->region;
+    hipStream_t s = M->stream;
+    const size_t acc_bytes = align256((size_t)n_thresholds * batch * sizeof(dnnca_spread_outcome));
+    DN_TRY(region_ws_reserve(R, acc_bytes + align256((size_t)n_thresholds * 4)));
+    unsigned long long* acc = (unsigned long long*)R.ws;
+    float* thr = (float*)((char*)R.ws + acc_bytes);
+    HIP_TRY(hipMemsetAsync(acc, 0, acc_bytes, s));
+    HIP_TRY(hipMemcpyAsync(thr, thresholds, (size_t)n_thresholds * 4, hipMemcpyHostToDevice, s));
+    const size_t per_block = (size_t)RB * kOutcomeU;
+    const dim3 grid((unsigned)((hw + per_block - 1) / per_block), n_thresholds, batch);
+    LAUNCH(M, "spread_outcome", (double)n_thresholds * batch * hw * 12.0, 0,
+           hipLaunchKernelGGL(k_spread_outcome, grid, dim3(RB), 0, s, prob, spread, y, (const float*)thr, hw, acc));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, acc, (size_t)n_thresholds * batch * sizeof(dnnca_spread_outcome), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return DNNCA_OK;
 }
 
 int lesion_table_linked(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows,

@@ -305,6 +305,12 @@ struct Model {
     float* tta_view = nullptr;
     float* tta_io = nullptr;
     size_t tta_io_n = 0;
+    // the spread of the views (dnnca_forward_tta_spread): the plane [max_batch, H, W] and the three planes of running moments, both
+    // allocated by the first call of that function; valid from such a call (for its batch) until anything else rewrites `prob`
+    float* tta_spread = nullptr;
+    float* tta_mom = nullptr;
+    bool tta_spread_valid = false;
+    int tta_spread_batch = 0;
 
     ~Model();
     int build();

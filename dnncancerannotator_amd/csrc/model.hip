@@ -753,6 +753,7 @@ std::vector<int> Model::pass_order(bool backward) const {
 int Model::forward(const float* x_dev, int B, bool training) {
     if (B < 1 || B > desc.max_batch) { set_error("batch %d outside [1, max_batch=%d]", B, desc.max_batch); return DNNCA_EINVAL; }
     last_batch = B;
+    if (!dry && !sens_pass) tta_spread_valid = false;   // the probabilities are about to change (dnnca_forward_tta_spread sets it again)
     // (the input-sensitivity pass walks the per-op arms too: every tensor its backward pass reads is then stored)
     const bool generic = (desc.flags & 1) || sens_pass;
     // input ops carry a channel offset relative to xin; rebase them on this batch
@@ -1596,6 +1597,17 @@ static void tta_launch_accumulate(Model* M, const float* src, float* prob, int B
            g_tta_accumulate(M->stream, src, prob, B, H, W, k, is_logits, pos == 0, pos == n - 1, n));
 }
 
+static void tta_launch_moments(Model* M, const float* src, float* prob, float* mom, float* spread, size_t plane, int B, int H, int W,
+                               int k, bool is_logits, int pos, int n) {
+    const double npix = (double)B * H * W;
+    // floats moved per pixel: the view in; p0 out (view 0) or in; the two sums in (from view 2 on) and out (up to the last but one);
+    // the running sum in (from view 1 on) and out; the spread out (last view)
+    const bool last = pos == n - 1;
+    const double moved = 1 + (last && !pos ? 0 : 1) + (pos > 1 ? 2 : 0) + (pos && !last ? 2 : 0) + (pos ? 1 : 0) + 1 + (last ? 1 : 0);
+    LAUNCH(M, "tta_moments", 4.0 * moved * npix, (is_logits ? 11.0 : 7.0) * npix,
+           g_tta_moments(M->stream, src, prob, mom, spread, plane, B, H, W, k, is_logits, pos, n));
+}
+
 // the buffers of the two stand-alone entries: n_in floats in, n_out floats out, one allocation
 static int tta_io_buffers(Model* M, size_t n_in, size_t n_out, float** in, float** out) {
     if (n_in + n_out > M->tta_io_n) {
@@ -1686,6 +1698,88 @@ int dnnca_tta_mean_of(void* model, const float* vals, int batch, int h, int w, u
     HIP_TRY(hipMemcpyAsync(prob_out, out, npix * 4, hipMemcpyDeviceToHost, M->stream));
     HIP_TRY(hipStreamSynchronize(M->stream));
     return M->flush_profile();
+}
+
+static const char* kSpreadState = "dnnca_forward_tta_spread makes it valid, until the next call that rewrites the probabilities";
+
+// the model's own spread plane for `batch` slices, or DNNCA_ESTATE
+static int tta_spread_plane(Model* M, int batch, const char* who) {
+    if (!M->tta_spread_valid) { set_error("%s: the model's spread plane is not valid (%s)", who, kSpreadState); return DNNCA_ESTATE; }
+    if (batch > M->tta_spread_batch) {
+        set_error("%s: %d slices asked for, the model's spread plane holds %d (%s)", who, batch, M->tta_spread_batch, kSpreadState);
+        return DNNCA_ESTATE;
+    }
+    return DNNCA_OK;
+}
+
+int dnnca_forward_tta_spread(void* model, const float* x_nhwc, int batch, unsigned views, float* prob_out, float* spread_out) {
+    MODEL(model);
+    const int H = M->desc.height, W = M->desc.width, C = M->desc.in_channels;
+    int ks[8];
+    const int n = tta_views_of(views, H, W, ks);
+    if (!n) return DNNCA_EINVAL;
+    if (!x_nhwc) { set_error("tta: null x"); return DNNCA_EINVAL; }
+    if (M->outH != H || M->outW != W) {
+        set_error("tta: the output (%d x %d) differs from the input (%d x %d)", M->outH, M->outW, H, W);
+        return DNNCA_EINVAL;
+    }
+    DN_TRY(check_batch(M, batch));
+    DN_TRY(tta_check_plane(batch, H, W, C));
+    const size_t plane = (size_t)M->desc.max_batch * H * W;
+    if (!M->tta_view && views != 1u) DN_TRY(M->alloc((void**)&M->tta_view, plane * C * 4));
+    if (!M->tta_spread) DN_TRY(M->alloc((void**)&M->tta_spread, plane * 4));
+    if (!M->tta_mom) DN_TRY(M->alloc((void**)&M->tta_mom, 3 * plane * 4));
+    DN_TRY(stage_inputs(M, batch, x_nhwc, nullptr, false));
+    for (int i = 0; i < n; ++i) {
+        const float* x = M->x_stage;                      // view 0 forwards from the staged batch itself
+        if (ks[i]) {
+            tta_launch_view_in(M, M->x_stage, M->tta_view, batch, H, W, C, ks[i]);
+            x = M->tta_view;
+        }
+        DN_TRY(M->forward(x, batch, false));
+        tta_launch_moments(M, M->logits, M->prob, M->tta_mom, M->tta_spread, plane, batch, H, W, ks[i], true, i, n);
+    }
+    M->tta_spread_valid = true;
+    M->tta_spread_batch = batch;
+    const size_t npix = (size_t)batch * H * W;
+    if (prob_out) HIP_TRY(hipMemcpyAsync(prob_out, M->prob, npix * 4, hipMemcpyDeviceToHost, M->stream));
+    if (spread_out) HIP_TRY(hipMemcpyAsync(spread_out, M->tta_spread, npix * 4, hipMemcpyDeviceToHost, M->stream));
+    if (prob_out || spread_out) {
+        HIP_TRY(hipStreamSynchronize(M->stream));
+        return M->flush_profile();
+    }
+    return DNNCA_OK;
+}
+
+int dnnca_tta_spread_of(void* model, const float* vals, int batch, int h, int w, unsigned views, int is_logits, float* prob_out,
+                        float* spread_out) {
+    MODEL(model);
+    int ks[8];
+    const int n = tta_views_of(views, h, w, ks);
+    if (!n) return DNNCA_EINVAL;
+    if (!vals || !prob_out || !spread_out) { set_error("tta: null buffer"); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
+    DN_TRY(tta_check_plane(batch, h, w, 1));
+    const size_t npix = (size_t)batch * h * w;
+    float *in = nullptr, *out = nullptr;                 // out: the mean, the spread, then the three planes of moments
+    DN_TRY(tta_io_buffers(M, npix * n, npix * 5, &in, &out));
+    HIP_TRY(hipMemcpyAsync(in, vals, npix * n * 4, hipMemcpyHostToDevice, M->stream));
+    for (int i = 0; i < n; ++i)
+        tta_launch_moments(M, in + npix * i, out, out + 2 * npix, out + npix, npix, batch, h, w, ks[i], is_logits != 0, i, n);
+    HIP_TRY(hipMemcpyAsync(prob_out, out, npix * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipMemcpyAsync(spread_out, out + npix, npix * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return M->flush_profile();
+}
+
+int dnnca_get_tta_spread(void* model, int batch, float* out) {
+    MODEL(model);
+    if (!out) { set_error("tta: null buffer"); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
+    DN_TRY(tta_spread_plane(M, batch, "dnnca_get_tta_spread"));
+    HIP_TRY(hipMemcpyAsync(out, M->tta_spread, (size_t)batch * M->outH * M->outW * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return DNNCA_OK;
 }
 
 // row: the tm_hist / tm_pin row of the step's training-metric counts (its staging slot, or kStageSlots)
@@ -1978,6 +2072,7 @@ int dnnca_pixel_confusion_of(void* model, const float* prob_hw, const float* y_h
     }
     int64_t cap = (int64_t)M->desc.max_batch * M->outH * M->outW;
     if (n_pixels < 1 || n_pixels > cap) { set_error("n_pixels %lld outside 1..%lld", (long long)n_pixels, (long long)cap); return DNNCA_EINVAL; }
+    M->tta_spread_valid = false;
     HIP_TRY(hipMemcpyAsync(M->prob, prob_hw, (size_t)n_pixels * 4, hipMemcpyHostToDevice, M->stream));
     HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, (size_t)n_pixels * 4, hipMemcpyHostToDevice, M->stream));
     return confusion_counts(M, (size_t)n_pixels, thresholds, n, out);
@@ -2064,11 +2159,13 @@ int dnnca_render_composite(void* model, const float* y_hw, int batch, float rati
 }
 
 // ---- `annotator predict`: the lesion table (kernels_region.hip) ---------------------------------------------------------------
-// dnnca_lesion_table (link == false; the last four arguments are not looked at) and dnnca_lesion_table_linked
+// dnnca_lesion_table (link == false; the four link arguments are not looked at), dnnca_lesion_table_linked and, with_spread,
+// dnnca_lesion_table_spread (never linked)
 static int lesion_call(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor, int filter_size,
                        int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity, int64_t* n_rows, int32_t* totals,
                        uint8_t* mask, int64_t mask_capacity, int32_t* out_hw, bool link, const uint8_t* continues,
-                       dnnca_lesion_link* links, int64_t links_capacity, int64_t* n_links) {
+                       dnnca_lesion_link* links, int64_t links_capacity, int64_t* n_links, bool with_spread = false,
+                       const float* spread_hw = nullptr, dnnca_lesion_spread* srows = nullptr, dnnca_slice_spread* stotals = nullptr) {
     MODEL(model);
     DN_TRY(check_batch(M, batch));
     if (!prob_hw) {
@@ -2112,14 +2209,29 @@ static int lesion_call(void* model, const float* prob_hw, int batch, int h, int 
             return DNNCA_EINVAL;
         }
     }
+    if (with_spread) {
+        if ((prob_hw == nullptr) != (spread_hw == nullptr)) {
+            set_error("lesion table: prob_hw and spread_hw go together (both host planes, or both NULL for the model's own)");
+            return DNNCA_EINVAL;
+        }
+        if (!srows || !stotals) { set_error("lesion table: null srows / stotals"); return DNNCA_EINVAL; }
+        if (!spread_hw) DN_TRY(tta_spread_plane(M, batch, "dnnca_lesion_table_spread"));
+    }
     const float* p_dev = M->prob;
+    const float* s_dev = M->tta_spread;
     if (prob_hw) {
         const size_t n = (size_t)batch * h * w;
         float *pd = nullptr, *yd = nullptr;
         DN_TRY(region_inputs(M, n, &pd, &yd));
         HIP_TRY(hipMemcpyAsync(pd, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
         p_dev = pd;
+        if (with_spread) {               // the label buffer of region_inputs carries the spread plane
+            HIP_TRY(hipMemcpyAsync(yd, spread_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+            s_dev = yd;
+        }
     }
+    if (with_spread)
+        return lesion_table_spread(M, p_dev, s_dev, batch, h, w, a, rows, n_rows, totals, mask, mask != nullptr, srows, stotals);
     if (link) return lesion_table_linked(M, p_dev, batch, h, w, a, rows, n_rows, totals, mask, mask != nullptr, continues, links, n_links);
     return lesion_table(M, p_dev, batch, h, w, a, rows, n_rows, totals, mask, mask != nullptr);
 }
@@ -2129,6 +2241,58 @@ int dnnca_lesion_table(void* model, const float* prob_hw, int batch, int h, int 
                        int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw) {
     return lesion_call(model, prob_hw, batch, h, w, threshold, resize_factor, filter_size, min_area, max_lesions, rows, rows_capacity,
                        n_rows, totals, mask, mask_capacity, out_hw, false, nullptr, nullptr, 0, nullptr);
+}
+
+int dnnca_lesion_table_spread(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
+                              int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
+                              int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw,
+                              const float* spread_hw, dnnca_lesion_spread* srows, dnnca_slice_spread* stotals) {
+    return lesion_call(model, prob_hw, batch, h, w, threshold, resize_factor, filter_size, min_area, max_lesions, rows, rows_capacity,
+                       n_rows, totals, mask, mask_capacity, out_hw, false, nullptr, nullptr, 0, nullptr, true, spread_hw, srows, stotals);
+}
+
+int dnnca_spread_by_outcome(void* model, const float* prob_hw, const float* spread_hw, const float* y_hw, int batch, int h, int w,
+                            const float* thresholds, int n_thresholds, dnnca_spread_outcome* out) {
+    MODEL(model);
+    DN_TRY(check_batch(M, batch));
+    if (!y_hw || !thresholds || !out) { set_error("spread by outcome: null y_hw / thresholds / out"); return DNNCA_EINVAL; }
+    if (n_thresholds < 1 || n_thresholds > kRegionMaxThr) {
+        set_error("spread by outcome: %d thresholds outside 1..%d", n_thresholds, kRegionMaxThr);
+        return DNNCA_EINVAL;
+    }
+    for (int t = 0; t < n_thresholds; ++t)
+        if (thresholds[t] != thresholds[t]) { set_error("spread by outcome: threshold %d is NaN", t); return DNNCA_EINVAL; }
+    if ((prob_hw == nullptr) != (spread_hw == nullptr)) {
+        set_error("spread by outcome: prob_hw and spread_hw go together (both host planes, or both NULL for the model's own)");
+        return DNNCA_EINVAL;
+    }
+    if (!prob_hw) {
+        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
+            set_error("spread by outcome: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
+            return DNNCA_EINVAL;
+        }
+        h = M->outH;
+        w = M->outW;
+    }
+    if (h < 1 || w < 1 || (int64_t)h * w > INT32_MAX || batch > 65535) {
+        set_error("spread by outcome: bad plane %d x %d x %d", batch, h, w);
+        return DNNCA_EINVAL;
+    }
+    const size_t hw = (size_t)h * w, n = (size_t)batch * hw;
+    const float *p_dev = M->prob, *s_dev = M->tta_spread, *y_dev = M->y_stage;
+    if (!prob_hw) {
+        DN_TRY(tta_spread_plane(M, batch, "dnnca_spread_by_outcome"));
+        HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+    } else {
+        float *in = nullptr, *yd = nullptr;               // probabilities, then the spread; the labels behind them
+        DN_TRY(tta_io_buffers(M, 2 * n, n, &in, &yd));
+        HIP_TRY(hipMemcpyAsync(in, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+        HIP_TRY(hipMemcpyAsync(in + n, spread_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+        HIP_TRY(hipMemcpyAsync(yd, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+        p_dev = in, s_dev = in + n, y_dev = yd;
+    }
+    DN_TRY(spread_by_outcome(M, p_dev, s_dev, y_dev, batch, hw, thresholds, n_thresholds, out));
+    return M->flush_profile();
 }
 
 int dnnca_lesion_table_linked(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,

@@ -59,6 +59,16 @@ int lesion_check(LesionArgs& a, int h, int w);
 // run (M->dry) the host outputs are not touched and want_mask stands for `mask != nullptr`
 int lesion_table(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows, int64_t* n_rows,
                  int32_t* totals, uint8_t* mask, bool want_mask);
+// lesion_table plus the spread of the test-time-augmentation views under it (dnnca_lesion_table_spread): the same chunk loop with the
+// same launches and, per chunk, lesion_spread on `spread` (device [batch, h, w], read through the resize of the probabilities).
+// srows (host, as many records as rows) receives one record per row of `rows`, stotals (host [batch]) every slice's total
+int lesion_table_spread(Model* M, const float* prob, const float* spread, int batch, int h, int w, const LesionArgs& a,
+                        dnnca_lesion_row* rows, int64_t* n_rows, int32_t* totals, uint8_t* mask, bool want_mask,
+                        dnnca_lesion_spread* srows, dnnca_slice_spread* stotals);
+// pixels and q24 spread sums per outcome class (dnnca_spread_by_outcome) of the device planes prob / spread / y [batch, hw] at
+// n_thresholds host thresholds: one spread_outcome launch; out (host) [n_thresholds][batch].  Synchronises
+int spread_by_outcome(Model* M, const float* prob, const float* spread, const float* y, int batch, size_t hw, const float* thresholds,
+                      int n_thresholds, dnnca_spread_outcome* out);
 // lesion_table plus the overlap links between neighbouring slices (dnnca_lesion_table_linked): the same chunk loop with the same
 // launches, then lesion_link / lesion_link_emit / lesion_carry per chunk.  continues (host [batch]): slice b follows slice b - 1 of
 // its exam; the predecessor of a chunk's first slice is the carry plane, i.e. the last slice of the chunk or of the linked call

@@ -354,6 +354,25 @@ class DeviceModel:
         check(self.lib.dnnca_forward_tta(self.handle, fptr(x), B, int(views), fptr(prob) if return_prob else None))
         return prob
 
+    def forward_tta_spread(self, x, views, return_prob=True, return_spread=True):
+        """forward_tta that also keeps how much the views disagree (dnnca_forward_tta_spread): the probability buffer receives bit for
+        bit forward_tta's mean, the model's spread plane the population standard deviation of the views per pixel (float32, in
+        [0, 0.5]; 0 where all views agree).  The plane stays valid -- for lesion_table_spread / spread_by_outcome / last_spread --
+        until the next call that rewrites the probabilities.  Returns (prob [B, H, W, 1] or None, spread [B, H, W] or None)"""
+        x = self._check_x(x)
+        B = x.shape[0]
+        prob = np.empty((B, self.in_shape[0], self.in_shape[1], 1), np.float32) if return_prob else None
+        spread = np.empty((B, self.in_shape[0], self.in_shape[1]), np.float32) if return_spread else None
+        check(self.lib.dnnca_forward_tta_spread(self.handle, fptr(x), B, int(views), fptr(prob) if return_prob else None,
+                                                fptr(spread) if return_spread else None))
+        return prob, spread
+
+    def last_spread(self, batch):
+        """the spread plane [batch, H, W] of the last forward_tta_spread (an error once it is no longer valid)"""
+        out = np.empty((int(batch), self.in_shape[0], self.in_shape[1]), np.float32)
+        check(self.lib.dnnca_get_tta_spread(self.handle, int(batch), fptr(out)))
+        return out
+
     def train_step(self, x, y, lr, cfg):
         x = self._check_x(x)
         y = as_f32(y)
@@ -510,6 +529,52 @@ class DeviceModel:
         [B, oh, ow], 255 on every kept component (None with mask=False).  Exact integers: bit-identical from run to run."""
         return self._lesion_call(batch, prob, None, threshold, resize_factor, filter_size, min_area, max_lesions, mask)
 
+    def lesion_table_spread(self, batch=None, prob=None, spread=None, threshold=0.5, resize_factor=1.0, filter_size=5, min_area=0,
+                            max_lesions=256, mask=True):
+        """lesion_table plus the spread of the test-time-augmentation views under it: (rows, totals, masks, srows, stotals); the first
+        three are what lesion_table returns.  The spread is that of the last forward_tta_spread (batch=...), or `spread` [B, h, w]
+        beside `prob` (both host planes, or neither).  srows: structured array (_lib.LESION_SPREAD_DTYPE: slice, row, area,
+        max_spread, sum_spread_q24), srows[i] belongs to rows[i] (mean = sum / area / 2^24); stotals (_lib.SLICE_SPREAD_DTYPE:
+        pixels, max_spread, sum_spread_q24) [B]: every pixel of the analysed plane of a slice.  Exact integers and extrema."""
+        if (prob is None) != (spread is None):
+            raise ValueError('lesion_table_spread: prob and spread go together (both host planes, or neither)')
+        if spread is not None:
+            spread = as_f32(spread)
+            if spread.ndim == 4 and spread.shape[-1] == 1:
+                spread = np.ascontiguousarray(spread[..., 0])
+            p = np.asarray(prob)
+            if spread.shape != (p[..., 0].shape if p.ndim == 4 else p.shape):
+                raise ValueError('spread %s and prob %s differ in shape' % (spread.shape, p.shape))
+        return self._lesion_call(batch, prob, None, threshold, resize_factor, filter_size, min_area, max_lesions, mask, spread=spread,
+                                 with_spread=True)
+
+    def spread_by_outcome(self, y, thresholds=(0.5,), batch=None, prob=None, spread=None):
+        """pixels and spread per pixel outcome (dnnca_spread_by_outcome): structured array (_lib.SPREAD_OUTCOME_DTYPE: n [4],
+        sum_q24 [4]) [T, B] over the classes TN, FP, FN, TP = 2 (y > 0.5) + (prob >= threshold).  y [B, h, w]; the probabilities
+        and the spread are those of the last forward_tta_spread, or the host planes `prob` and `spread` [B, h, w] (both or neither).
+        At most 64 thresholds.  Exact integers."""
+        y = as_f32(y)
+        if y.ndim == 4 and y.shape[-1] == 1:
+            y = np.ascontiguousarray(y[..., 0])
+        if y.ndim != 3:
+            raise ValueError('y must be [B, h, w], got %s' % (y.shape,))
+        if (prob is None) != (spread is None):
+            raise ValueError('spread_by_outcome: prob and spread go together (both host planes, or neither)')
+        if batch is not None and int(batch) != y.shape[0]:
+            raise ValueError('batch %d but y holds %d slices' % (batch, y.shape[0]))
+        B, h, w = y.shape
+        pp = sp = None
+        if prob is not None:
+            prob, spread = as_f32(prob).reshape(-1), as_f32(spread).reshape(-1)
+            if prob.size != y.size or spread.size != y.size:
+                raise ValueError('prob, spread and y differ in size')
+            pp, sp = fptr(prob), fptr(spread)
+        thr = threshold_vector(thresholds)
+        out = np.zeros((thr.size, B), _lib.SPREAD_OUTCOME_DTYPE)
+        check(self.lib.dnnca_spread_by_outcome(self.handle, pp, sp, fptr(y), B, h if pp is not None else 0, w if pp is not None else 0,
+                                               fptr(thr), thr.size, out.ctypes.data_as(C.POINTER(_lib.SpreadOutcome))))
+        return out
+
     def lesion_table_linked(self, batch=None, prob=None, continues=None, threshold=0.5, resize_factor=1.0, filter_size=5, min_area=0,
                             max_lesions=256, mask=True):
         """lesion_table plus the links between neighbouring slices: (rows, totals, masks, links); the first three are what
@@ -522,8 +587,10 @@ class DeviceModel:
             raise ValueError('lesion_table_linked needs `continues`, one flag per slice')
         return self._lesion_call(batch, prob, continues, threshold, resize_factor, filter_size, min_area, max_lesions, mask)
 
-    def _lesion_call(self, batch, prob, continues, threshold, resize_factor, filter_size, min_area, max_lesions, mask):
-        """dnnca_lesion_table, or with `continues` dnnca_lesion_table_linked: the size query, then the call on buffers of that size"""
+    def _lesion_call(self, batch, prob, continues, threshold, resize_factor, filter_size, min_area, max_lesions, mask, spread=None,
+                     with_spread=False):
+        """dnnca_lesion_table, with `continues` dnnca_lesion_table_linked, with_spread dnnca_lesion_table_spread: the size query, then
+        the call on buffers of that size"""
         pp, h, w = None, 0, 0
         if prob is not None:
             prob = as_f32(prob)
@@ -550,6 +617,13 @@ class DeviceModel:
         n = C.c_int64()
         out = (rows.ctypes.data_as(C.POINTER(_lib.LesionRow)), cap, C.byref(n), totals.ctypes.data_as(C.POINTER(C.c_int32)),
                masks.ctypes.data_as(C.c_void_p) if mask else None, masks.nbytes if mask else 0, hw)
+        if with_spread:
+            srows = np.zeros(cap, _lib.LESION_SPREAD_DTYPE)
+            stotals = np.zeros(B, _lib.SLICE_SPREAD_DTYPE)
+            check(self.lib.dnnca_lesion_table_spread(*args, *out, None if spread is None else fptr(spread),
+                                                     srows.ctypes.data_as(C.POINTER(_lib.LesionSpread)),
+                                                     stotals.ctypes.data_as(C.POINTER(_lib.SliceSpread))))
+            return rows[:n.value].copy(), totals, masks, srows[:n.value].copy(), stotals
         if continues is None:
             check(self.lib.dnnca_lesion_table(*args, *out))
             return rows[:n.value].copy(), totals, masks

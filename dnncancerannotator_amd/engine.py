@@ -49,13 +49,21 @@ def _element_shape(dataset):
     raise ValueError('empty dataset')
 
 
-def _forward_on_device(dm, xb, tta_mask):
+def _forward_on_device(dm, xb, tta_mask, spread=False):
     """the inference forward whose probabilities stay on the device: the plain one or, with a view mask (tta.mask_of), the test-time
-    augmented one"""
+    augmented one; with `spread` the augmented one that also keeps the views' spread on the device (--uncertainty)"""
     if tta_mask is None:
         dm.forward(xb, training=False, return_prob=False)
+    elif spread:
+        dm.forward_tta_spread(xb, tta_mask, return_prob=False, return_spread=False)
     else:
         dm.forward_tta(xb, tta_mask, return_prob=False)
+
+
+def check_uncertainty(uncertainty, tta):
+    """--uncertainty measures the disagreement of the test-time-augmentation views: without views there is nothing to measure"""
+    if uncertainty and tta == tta_modes.NONE:
+        raise ValueError('--uncertainty needs the views of test-time augmentation: add --tta flips (or --tta d4 on square slices)')
 
 
 def _csv_value(v):
@@ -563,7 +571,8 @@ class TFKerasModel:
              export_casewise_metrics=False, exam_ds=None, exam_lesions=False, exam_threshold=(0.5,), exam_iou=casewise.EXAM_IOU,
              exam_min_area=0, exam_filter_size=5, exam_resize_factor=1.0, exam_max_lesions=256, exam_link_min_overlap=1,
              surface_ds=None, surface_distances=False, surface_threshold=(0.5,), surface_percentile=casewise.SURFACE_PERCENTILE,
-             surface_min_area=0, surface_filter_size=5, surface_resize_factor=1.0, surface_max_samples=65536, tta='none'):
+             surface_min_area=0, surface_filter_size=5, surface_resize_factor=1.0, surface_max_samples=65536, tta='none',
+             uncertainty_ds=None, uncertainty=False, uncertainty_thresholds=(0.5,)):
         """exam_lesions (`evaluate --exam_lesions`): after every checkpoint's evaluation rank 0 also runs _exam_lesion_pass over
         exam_ds (batches (x, y, paths, sliceIDs), a data set of its own: viz_ds is not needed) and writes exam_lesion_results.csv,
         exam_lesion_cases.csv and exam_lesion_matches.csv under <export_path>/<tag>/; every other file is what it is without it.
@@ -572,7 +581,12 @@ class TFKerasModel:
         tta (`evaluate --tta`, tta.MODES): with a mode other than 'none' the probabilities every pass reads -- the pixel and region
         metrics of the per-batch test step, the Visualizer, the exam-lesion and the surface pass -- are the mean over the mode's
         flip / transpose views (DeviceModel.forward_tta).  The evaluation then runs batch by batch, not over the staged ring;
-        `loss` stays the loss of the untransformed view, and --visualize_sensitivity the gradient of the plain forward."""
+        `loss` stays the loss of the untransformed view, and --visualize_sensitivity the gradient of the plain forward.
+        uncertainty (`evaluate --tta MODE --uncertainty`): after every checkpoint's evaluation rank 0 also runs _uncertainty_pass
+        over uncertainty_ds (the same kind of data set as exam_ds; the flags may share one) and writes uncertainty_results.csv and
+        uncertainty_slices.csv under <export_path>/<tag>/: pixels and mean spread of the views per pixel outcome at every one of
+        uncertainty_thresholds.  Every other file is what it is without the flag.  Needs a tta mode other than 'none'."""
+        check_uncertainty(uncertainty, tta)
         if visualize_sensitivity and not getattr(self.model, 'supports_sensitivity', True):
             raise NotImplementedError('--visualize_sensitivity is not implemented for model: %s (the input-gradient pass covers the '
                                       'U-Net models only)' % self.model_config['model'])
@@ -604,6 +618,8 @@ class TFKerasModel:
         exam_tables = [], [], []         # the lines of the three exam_lesion_*.csv files
         surface_pass = bool(surface_distances) and surface_ds is not None and self.ctx.rank == 0
         surface_tables = [], [], []      # the lines of surface_results.csv, surface_cases.csv and surface_slices.csv
+        uncertainty_pass = bool(uncertainty) and uncertainty_ds is not None and self.ctx.rank == 0
+        uncertainty_tables = [], []      # the lines of uncertainty_results.csv and uncertainty_slices.csv
         rows = OrderedDict()
         previous_step = None
         for ckpt_step, ckpt_path_ in self.get_ckpts(ckpt_path).items():
@@ -631,6 +647,16 @@ class TFKerasModel:
                         dict(resize_factor=surface_resize_factor, filter_size=surface_filter_size, min_area=surface_min_area,
                              max_samples=surface_max_samples), tta_mask=tta_mask)):
                     t += new
+            if uncertainty_pass:
+                for t, new in zip(uncertainty_tables, self._uncertainty_pass(uncertainty_ds, ckpt_step,
+                                                                             [float(t) for t in uncertainty_thresholds], tta_mask)):
+                    t += new
+        if uncertainty_pass:
+            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
+            for name, cols, table in zip(('uncertainty_results.csv', 'uncertainty_slices.csv'),
+                                         (casewise.UNCERTAINTY_RESULT_COLUMNS, casewise.UNCERTAINTY_SLICE_COLUMNS), uncertainty_tables):
+                with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
+                    f.write(casewise.plain_csv(['step', 'threshold'] + cols, table))
         if surface_pass:
             os.makedirs(os.path.join(export_path, tag), exist_ok=True)
             for name, cols, table in zip(('surface_results.csv', 'surface_cases.csv', 'surface_slices.csv'),
@@ -798,6 +824,33 @@ class TFKerasModel:
             results.append(lead + casewise.surface_summary(slice_values, exam_values))
         return results, cases, slices
 
+    def _uncertainty_pass(self, ds, step, thresholds, tta_mask):
+        """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --tta MODE --uncertainty`: per max_batch split one
+        DeviceModel.forward_tta_spread whose mean and spread stay on the device and one DeviceModel.spread_by_outcome for all
+        thresholds (in runs of 64); only the counts and sums per outcome come back.  Returns the new lines of
+        (uncertainty_results.csv, uncertainty_slices.csv), each led by step and threshold."""
+        found = [[] for _ in thresholds]     # per threshold and slice: (exam, slice, outcome entry)
+        for x, y, paths, ids in ds:
+            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
+            if not len(x):
+                continue
+            self._ensure_capacity(len(x))
+            dm = self.device_model
+            for i in range(0, len(x), dm.max_batch):
+                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
+                pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
+                _forward_on_device(dm, xb, tta_mask, spread=True)
+                for t0 in range(0, len(thresholds), 64):
+                    out = dm.spread_by_outcome(yb.reshape(len(xb), *yb.shape[1:3]), thresholds[t0:t0 + 64], batch=len(xb))
+                    for ti, per_slice in enumerate(out, t0):
+                        found[ti] += [(p, int(k), o) for (p, k), o in zip(pk, per_slice)]
+        results, slices = [], []
+        for thr, mine in zip(thresholds, found):
+            lead = [int(step), repr(thr)]
+            slices += [lead + casewise.outcome_slice_values(*rec) for rec in mine]
+            results.append(lead + casewise.outcome_summary([rec[2] for rec in mine]))
+        return results, slices
+
     def predict(self, dataset):
         """Probabilities [N, H, W, 1] for every element of `dataset` (elements are x or (x, ...))."""
         self._build(dataset)
@@ -810,7 +863,7 @@ class TFKerasModel:
         return np.concatenate(outs) if outs else np.zeros((0,))
 
     def annotate(self, dataset, save_path, output, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
-                 max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none'):
+                 max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False):
         """`annotator predict`: the lesions of slices that have no label.  Loads checkpoint `step` of save_path (None: the latest);
         per batch (x, paths, sliceIDs) of `dataset` (make_dataset(..., include_meta=True, labels=False)) one forward whose
         probabilities stay on the device, then DeviceModel.lesion_table: threshold, filter_size x filter_size opening, components
@@ -825,7 +878,13 @@ class TFKerasModel:
         exam_lesion_parts.csv (one line per line of lesions.csv, in its order) are written beside the other files, which are
         what they are without the flag; the returned dict gains 'exam_lesions'.
         tta (`predict --tta`, tta.MODES): with a mode other than 'none' the one forward per chunk is DeviceModel.forward_tta with the
-        mode's view mask: the tables and masks are those of the mean probability over the views."""
+        mode's view mask: the tables and masks are those of the mean probability over the views.
+        uncertainty (`predict --tta MODE --uncertainty`): the forward is DeviceModel.forward_tta_spread and the table comes from
+        DeviceModel.lesion_table_spread (with link_slices lesion_table_linked runs as it does without the flag and the spread records
+        come from a second call); lesion_uncertainty.csv (one line per line of lesions.csv, in its order) and slice_uncertainty.csv
+        are written beside the other files, which are what they are without the flag, and with export_images
+        <exam>/<slice>/uncertainty.png (only then does a spread plane leave the device).  Needs a tta mode other than 'none'."""
+        check_uncertainty(uncertainty, tta)
         if self.ctx.world > 1:
             raise RuntimeError('annotate runs in a single process (WORLD_SIZE is %d): start it without the launcher' % self.ctx.world)
         tta_mask = None if tta == tta_modes.NONE else tta_modes.mask_of(tta, *_element_shape(dataset)[1:3])
@@ -839,6 +898,7 @@ class TFKerasModel:
             raise ValueError(f'no checkpoint of step {step} under {save_path}/checkpoints (have {sorted(ckpts)})')
         self.load(ckpts[step])
         lesion_rows, slice_rows = [], []
+        lesion_spread_rows, slice_spread_rows = [], []
         dm = None
         linked, last = [], None          # link_slices: (exam, slice, rows, total, links into it) per slice; the slice before: (exam, slice)
         writer = casewise.Writer() if export_images else None
@@ -855,7 +915,7 @@ class TFKerasModel:
                 dm = self.device_model
                 for i in range(0, len(x), dm.max_batch):
                     xb = x[i:i + dm.max_batch]
-                    _forward_on_device(dm, xb, tta_mask)
+                    _forward_on_device(dm, xb, tta_mask, spread=bool(uncertainty))
                     pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
                     kw = dict(batch=len(xb), threshold=threshold, resize_factor=resize_factor, filter_size=filter_size,
                               min_area=min_area, max_lesions=max_lesions, mask=bool(export_images))
@@ -865,8 +925,16 @@ class TFKerasModel:
                             continues.append(last is not None and p == last[0] and int(k) == last[1] + 1)
                             last = (p, int(k))
                         rows, totals, masks, links = dm.lesion_table_linked(continues=continues, **kw)
+                        if uncertainty:              # the spread records of the same rows (there is no linked table with spread)
+                            _, _, _, srows, stotals = dm.lesion_table_spread(**dict(kw, mask=False))
+                    elif uncertainty:
+                        rows, totals, masks, srows, stotals = dm.lesion_table_spread(**kw)
                     else:
                         rows, totals, masks = dm.lesion_table(**kw)
+                    if uncertainty:
+                        if len(srows) != len(rows):
+                            raise RuntimeError('predict: %d spread records beside %d lesions' % (len(srows), len(rows)))
+                        spread = dm.last_spread(len(xb)) if export_images else None
                     for b, (p, k) in enumerate(pk):
                         mine = rows[rows['slice'] == b]
                         if link_slices:
@@ -876,12 +944,22 @@ class TFKerasModel:
                         slice_rows.append(casewise.slice_values(p, k, mine, totals[b]))
                         if export_images:
                             writer.submit(casewise.mask_path(output, casewise.tag_of(p, k)), casewise.encode_png, masks[b])
+                        if uncertainty:
+                            smine = srows[rows['slice'] == b]
+                            lesion_spread_rows += [casewise.lesion_uncertainty_values(p, k, r, q) for r, q in zip(mine, smine)]
+                            slice_spread_rows.append(casewise.slice_uncertainty_values(p, k, mine, smine, totals[b], stotals[b]))
+                            if export_images:
+                                writer.submit(casewise.uncertainty_path(output, casewise.tag_of(p, k)),
+                                              lambda s_: casewise.encode_png(casewise.uncertainty_image(s_)), spread[b])
         finally:
             if writer is not None:
                 writer.close()
         os.makedirs(output, exist_ok=True)
         tables = [('lesions.csv', casewise.LESION_COLUMNS, lesion_rows), ('slices.csv', casewise.SLICE_COLUMNS, slice_rows)]
         res = dict(step=int(step), slices=len(slice_rows), lesions=len(lesion_rows))
+        if uncertainty:
+            tables += [('lesion_uncertainty.csv', casewise.LESION_UNCERTAINTY_COLUMNS, lesion_spread_rows),
+                       ('slice_uncertainty.csv', casewise.SLICE_UNCERTAINTY_COLUMNS, slice_spread_rows)]
         if link_slices:
             exams = {}                   # exam path -> the positions of its slices in `linked`, in the order of the data set
             for pos, rec in enumerate(linked):

@@ -1,6 +1,7 @@
 """`annotator predict` -- the reference left annotator/runs/predict.py empty: annotate slices that have no label with a trained
 checkpoint (lesions.csv, slices.csv and, with --export_images, one mask.png per slice; with --link_slices also exam_lesions.csv and
-exam_lesion_parts.csv: the lesions joined through the slices of an exam; engine.TFKerasModel.annotate)."""
+exam_lesion_parts.csv: the lesions joined through the slices of an exam; with --tta MODE --uncertainty also lesion_uncertainty.csv,
+slice_uncertainty.csv and uncertainty.png: how much the views disagree; engine.TFKerasModel.annotate)."""
 
 import os
 
@@ -9,7 +10,8 @@ from .train import make_dataset
 
 
 def predict(save_path, data_path, output, config=None, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
-            max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none'):
+            max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False):
+    engine.check_uncertainty(uncertainty, tta)       # before anything is read
     if link_min_overlap < 1:
         raise ValueError('link_min_overlap must be at least 1, got %d' % link_min_overlap)
     saved_config = load.load_config(os.path.join(save_path, 'options.yaml'))['config']
@@ -18,6 +20,8 @@ def predict(save_path, data_path, output, config=None, step=None, threshold=0.5,
     # the keyword of --tta goes to model.annotate only with a mode (tta.mask_of refuses d4 on non-square slices there, before any
     # checkpoint is read)
     more = dict(tta=tta) if tta != 'none' else {}
+    if uncertainty:                      # likewise only with the flag
+        more['uncertainty'] = True
     model = engine.TFKerasModel(config)
     return model.annotate(ds, save_path=save_path, output=output, step=step, threshold=threshold, min_area=min_area,
                           filter_size=filter_size, resize_factor=resize_factor, max_lesions=max_lesions,

@@ -152,6 +152,27 @@ int dnnca_forward_tta(void* model, const float* x_nhwc, int batch, unsigned view
  * Both refuse what dnnca_forward_tta refuses, with h != w standing in for H != W. */
 int dnnca_tta_view_of(void* model, const float* src, int batch, int h, int w, int c, int view, float* dst);
 int dnnca_tta_mean_of(void* model, const float* vals, int batch, int h, int w, unsigned views, int is_logits, float* prob_out);
+/* ---- how much the views disagree (`predict --tta MODE --uncertainty`, `evaluate --tta MODE --uncertainty`) ------------------------------
+ * With p_k and n as above and the mean taken in exact arithmetic,
+ *     spread[b,i,j] = sqrt((1/n) * sum over the selected k of (p_k - mean)^2)        (population standard deviation, float32)
+ * computed in the shifted form d_k = p_k - p_first, var = (sum d^2 - (sum d)^2 / n) / n: |spread - want| <= 2^-18 want + 2^-23 against
+ * the float64 standard deviation `want` of the same float32 p_k; exactly 0 where all selected p_k are the same float32 (so for a
+ * single view everywhere); at most 0.5 up to that error.
+ * dnnca_forward_tta_spread does and refuses everything dnnca_forward_tta does -- the probability buffer receives bit for bit that
+ * call's mean -- with tta_moments in the place of tta_accumulate: the spread lands in a plane [max_batch, H, W] of the model's own,
+ * allocated with three planes of running moments by the first call of this function (a model that never calls it allocates
+ * neither).  The call marks the plane VALID for its batch; every other call that rewrites the probability buffer (dnnca_forward*,
+ * dnnca_forward_tta, the train and eval steps, dnnca_pixel_confusion_of) marks it invalid.  prob_out, spread_out: NULL, or host
+ * [batch, H, W]; synchronises when one is given.
+ *   dnnca_tta_spread_of    the kernel alone on host planes vals [n, batch, h, w], as dnnca_tta_mean_of (its refusals included):
+ *                          prob_out receives bit for bit that call's mean, spread_out the spread; both required; synchronises
+ *   dnnca_get_tta_spread   the valid plane's first `batch` slices to host [batch, H, W]; DNNCA_ESTATE while it is not valid or holds
+ *                          fewer slices; waits for the stream */
+int dnnca_forward_tta_spread(void* model, const float* x_nhwc, int batch, unsigned views, float* prob_out /* nullable */,
+                             float* spread_out /* nullable */);
+int dnnca_tta_spread_of(void* model, const float* vals, int batch, int h, int w, unsigned views, int is_logits, float* prob_out,
+                        float* spread_out);
+int dnnca_get_tta_spread(void* model, int batch, float* out);
 /* keras Model.train_step under engine.py:126-135: forward(training=True) + TFWeightedCrossentropy (losses.py:60-72)
  * + backward + [RCCL all-reduce] + Adam apply with learning rate lr (LearningRateScheduler, engine.py:97-100) */
 int dnnca_train_step(void* model, const float* x_nhwc, const float* y_hw, int batch, float lr,
@@ -342,6 +363,49 @@ typedef struct dnnca_lesion_row {
 int dnnca_lesion_table(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
                        int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
                        int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw);
+
+/* ---- the same table plus the spread of the views under it (`annotator predict --tta MODE --uncertainty`) -----------------------------
+ * Every argument up to out_hw means what it means for dnnca_lesion_table (the size query with rows == NULL included), and rows,
+ * totals, mask and out_hw are bit-identical to that call's.  The spread plane is resized like the probabilities (the same bilinear
+ * resize: resize_factor != 1 analyses the same plane); a pixel's spread' enters every sum as rint(max(spread', 0) * 2^24) and every
+ * maximum through the float's bits, so all of this is bit-identical from run to run too.
+ *   srows[i]     belongs to rows[i]: slice, row, area (the pixels that added to it: rows[i].area), max_spread, sum_spread_q24
+ *                (mean = sum / area / 2^24)
+ *   stotals[b]   pixels (oh * ow), max_spread and sum_spread_q24 over EVERY pixel of the analysed plane of slice b, lesion or not
+ * srows holds rows_capacity records, stotals `batch`.  spread_hw == NULL: the model's own plane, which must be valid
+ * (dnnca_forward_tta_spread) for at least `batch` slices -- DNNCA_ESTATE otherwise -- and prob_hw must be NULL as well; otherwise
+ * spread_hw is a host plane [batch, h, w] beside prob_hw, which must then be given too.
+ * DNNCA_EINVAL, with nothing launched and no output touched: everything dnnca_lesion_table refuses, one of prob_hw / spread_hw given
+ * without the other, srows == NULL or stotals == NULL beside rows.  Synchronises. */
+typedef struct dnnca_lesion_spread {
+    int32_t slice, row, area;
+    float max_spread;
+    uint64_t sum_spread_q24;
+} dnnca_lesion_spread;                              /* 24 bytes, no padding */
+typedef struct dnnca_slice_spread {
+    int32_t pixels;
+    float max_spread;
+    uint64_t sum_spread_q24;
+} dnnca_slice_spread;                               /* 16 bytes, no padding */
+int dnnca_lesion_table_spread(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
+                              int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
+                              int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw,
+                              const float* spread_hw, dnnca_lesion_spread* srows, dnnca_slice_spread* stotals);
+
+/* ---- is the spread larger where the model is wrong? (`annotator evaluate --tta MODE --uncertainty`) ---------------------------------
+ * Per threshold t and slice b every pixel falls into the class 2 (y > 0.5) + (prob >= thresholds[t]): TN 0, FP 1, FN 2, TP 3 (the
+ * label rule of dnnca_lesion_table_matched); out[t * batch + b] receives the pixels n[c] and the sums sum_q24[c] of
+ * rint(max(spread, 0) * 2^24) of every class.  Raw planes: no resize, no opening.  prob_hw and spread_hw: both NULL -- the model's
+ * probabilities and its spread plane, which must be valid for at least `batch` slices (DNNCA_ESTATE otherwise); h and w are then 0
+ * or the model's output size -- or both host planes [batch, h, w] of any size.  y_hw: host [batch, h, w], required.
+ * DNNCA_EINVAL, with nothing launched and no output touched: batch outside [1, max_batch], n_thresholds outside 1..64, a NaN
+ * threshold, a NULL thresholds / y_hw / out, one of prob_hw / spread_hw given without the other, a plane that is empty or has 2^31
+ * pixels or more, more than 65535 slices.  Exact integers: bit-identical from run to run.  Synchronises. */
+typedef struct dnnca_spread_outcome {
+    uint64_t n[4], sum_q24[4];
+} dnnca_spread_outcome;                             /* 64 bytes, no padding */
+int dnnca_spread_by_outcome(void* model, const float* prob_hw, const float* spread_hw, const float* y_hw, int batch, int h, int w,
+                            const float* thresholds, int n_thresholds, dnnca_spread_outcome* out /* [n_thresholds][batch] */);
 
 /* ---- the same table plus the links between neighbouring slices of an exam (`annotator predict --link_slices`) ------------------
  * Every argument up to out_hw means what it means for dnnca_lesion_table (the size query with rows == NULL included), and rows,

@@ -14,6 +14,7 @@ and prediction plane) plus pairs, match and count.
     python tools/lesion_rate.py --link --match --surface         # also: surface_distances against lesion_table_matched
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --link --match    # the matched legs on it
     python tools/lesion_rate.py --tta flips         # test-time augmentation alone: forward_tta against the plain forward
+    python tools/lesion_rate.py --tta flips --uncertainty        # also: the spread of the views against the mean alone
 
 --link adds the cost of linking neighbouring slices: lesion_table_linked against lesion_table (wall time per call, device time of
 the three link launches), its worst case for the pair table (a checkerboard on itself: every other pixel a lesion of its own in
@@ -30,6 +31,10 @@ against a forward + matched pass over the same batches, alternated in one proces
 --tta MODE (flips, d4) measures DeviceModel.forward_tta against DeviceModel.forward on the same host batch and nothing else: wall time
 per call (both upload the batch once), device time per call (every launch event-bracketed) and the share of the two kernels of
 kernels_tta.hip (tta_view_in, tta_accumulate) in it.
+
+--tta MODE --uncertainty adds the spread of the views: forward_tta_spread against forward_tta (wall and device time per call, the
+two alternated), tta_moments against tta_accumulate per launch, lesion_table_spread against lesion_table on the mean and spread that
+forward_tta_spread left on the device, and spread_by_outcome alone (one and three thresholds).
 
 The probabilities are drawn: the synthetic labels' discs at 0.55 .. 0.95 on a background of 0 .. 0.45 (a few lesions per slice,
 as a trained model gives), put into the model's probability buffer by pixel_confusion_of."""
@@ -53,6 +58,7 @@ ap.add_argument('--link', action='store_true', help='also measure lesion_table_l
 ap.add_argument('--match', action='store_true', help='also measure lesion_table_matched against lesion_table_linked (needs --link)')
 ap.add_argument('--surface', action='store_true', help='also measure surface_distances against lesion_table_matched (needs --match)')
 ap.add_argument('--tta', default=None, metavar='MODE', help='measure forward_tta(MODE) against the plain forward, and nothing else')
+ap.add_argument('--uncertainty', action='store_true', help='with --tta: also measure forward_tta_spread, lesion_table_spread, spread_by_outcome')
 ap.add_argument('--out', default=None, help='append the report to this file as well')
 a = ap.parse_args()
 if a.yardstick:
@@ -73,6 +79,13 @@ if not a.surface:
 if not a.tta:
     for name in ('dnnca_forward_tta', 'dnnca_tta_view_of', 'dnnca_tta_mean_of'):
         _lib.SIGNATURES.pop(name, None)                          # nor does one from before test-time augmentation
+
+if a.uncertainty and not a.tta:
+    ap.error('--uncertainty needs --tta MODE')
+if not a.uncertainty:
+    for name in ('dnnca_forward_tta_spread', 'dnnca_tta_spread_of', 'dnnca_get_tta_spread', 'dnnca_lesion_table_spread',
+                 'dnnca_spread_by_outcome'):
+        _lib.SIGNATURES.pop(name, None)                          # nor does one from before the spread
 
 from dnncancerannotator_amd import device as dev                  # noqa: E402
 from dnncancerannotator_amd.data import ArrayDataset              # noqa: E402
@@ -164,6 +177,46 @@ if a.tta:
     for name, n, ms, by, fl in mine:
         say('    %-22s launches/call %4.1f  %9.2f us per launch  %7.1f GB/s' % (name, n / R, ms / n * 1e3, by / (ms / n * 1e-3) / 1e9))
     say('    share of the two tta kernels in forward_tta: %.2f %%' % (100.0 * sum(r[2] for r in mine) / R / dev_t))
+    if a.uncertainty:
+        def with_spread():
+            dm.forward_tta_spread(x, views, return_prob=False, return_spread=False)
+            dm.sync()
+        took = {}
+        for name, fn in (('forward_tta', augmented), ('forward_tta_spread', with_spread)) * 3:      # alternated
+            took.setdefault(name, []).append(wall(fn))
+        for name, runs in took.items():
+            for med, lo, hi in runs:
+                say('  %-28s %.3f ms per call, upload included (median of %d; %.3f .. %.3f)' % (name, med, R, lo, hi))
+        say('  forward_tta_spread / forward_tta, wall (best medians): %.3f' % (min(r[0] for r in took['forward_tta_spread']) /
+                                                                              min(r[0] for r in took['forward_tta'])))
+        rows_s = device_rows(with_spread)
+        dev_s = sum(r[2] for r in rows_s) / R
+        say('  device time per call: forward_tta %.3f ms, forward_tta_spread %.3f ms: ratio %.3f' % (dev_t, dev_s, dev_s / dev_t))
+        per = {}
+        for name, n, ms, by, fl in [r for r in rows_s if r[0].startswith('tta_')] + [r for r in mine if r[0] == 'tta_accumulate']:
+            per[name] = ms / n * 1e3
+            say('    %-22s launches/call %4.1f  %9.2f us per launch  %7.1f GB/s' % (name, n / R, ms / n * 1e3, by / (ms / n * 1e-3) / 1e9))
+        say('    tta_moments / tta_accumulate per launch: %.2f' % (per['tta_moments'] / per['tta_accumulate']))
+        with_spread()
+        last = dm.last_prob(B)
+        # a random network draws no tumours: the median under a 5 x 5 opening leaves next to nothing, the 99th percentile without
+        # an opening thousands of specks -- the two ends between which a trained model's few lesions per slice lie
+        for thr, k in ((float(np.median(last)), 5), (float(np.percentile(last, 99.0)), 1)):
+            kw = dict(batch=B, threshold=thr, filter_size=k, mask=False, max_lesions=4096)
+            say('  threshold %.6f, filter_size %d' % (thr, k))
+            took = {}
+            for name, fn in (('lesion_table', lambda: dm.lesion_table(**kw)), ('lesion_table_spread', lambda: dm.lesion_table_spread(**kw))) * 2:
+                took.setdefault(name, []).append(wall(fn))
+            for name, runs in took.items():
+                for med, lo, hi in runs:
+                    say('  %-28s %.3f ms per call (median of %d; %.3f .. %.3f)' % (name, med, R, lo, hi))
+            say('  lesion_table_spread / lesion_table, wall (best medians): %.3f; %d lesions' % (
+                min(r[0] for r in took['lesion_table_spread']) / min(r[0] for r in took['lesion_table']), len(dm.lesion_table_spread(**kw)[0])))
+            per_launch(dm, lambda: dm.lesion_table_spread(**kw), ('region_', 'lesion_'))
+        for thrs in ([thr], [0.25, thr, 0.75]):
+            med, lo, hi = wall(lambda: dm.spread_by_outcome(y, thrs))
+            say('  spread_by_outcome, %d threshold(s): %.3f ms per call, labels uploaded (median of %d; %.3f .. %.3f)' % (len(thrs), med, R, lo, hi))
+            per_launch(dm, lambda: dm.spread_by_outcome(y, thrs), ('spread_',))
     dm.close()
     if a.out:
         with open(a.out, 'a') as f:
