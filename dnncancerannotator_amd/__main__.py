@@ -81,6 +81,17 @@ def build_parser(prog='python3 -m annotator'):
                         'pixels: also write uncertainty_results.csv and uncertainty_slices.csv')
     e.add_argument('--uncertainty_threshold', type=float, nargs='+', default=argparse.SUPPRESS, metavar='T',
                    help='probability threshold(s) of --uncertainty (default: 0.5)')
+    e.add_argument('--calibration', action='store_true', default=argparse.SUPPRESS,
+                   help='can the probability be believed: reliability table, ECE, MCE, Brier score, NLL and the temperature that '
+                        'minimises the NLL: also write calibration_results.csv, calibration_bins.csv and calibration_slices.csv')
+    e.add_argument('--calibration_bins', type=_at_least_one, default=argparse.SUPPRESS,
+                   help='equal-width probability bins of --calibration, at most 256 (default: 15)')
+    e.add_argument('--calibration_temperatures', type=float, nargs='+', default=argparse.SUPPRESS, metavar='T',
+                   help='temperature grid of --calibration, each in [0.05, 20], at most 64 with T = 1, which is always added '
+                        '(default: 41 points from 0.25 to 4)')
+    e.add_argument('--temperature', type=float, default=argparse.SUPPRESS, metavar='T',
+                   help='temperature scaling: every probability read is sigmoid(logit(p) / T), T in [0.05, 20]; --calibration then '
+                        'measures the scaled probabilities (default: 1, no scaling)')
     p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
     p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
     p.add_argument('--data_path', nargs='+', required=True)
@@ -104,6 +115,9 @@ def build_parser(prog='python3 -m annotator'):
     p.add_argument('--uncertainty', action='store_true', default=argparse.SUPPRESS,
                    help='with --tta flips / d4: how much the views disagree (their standard deviation per pixel) per lesion and slice: '
                         'also write lesion_uncertainty.csv, slice_uncertainty.csv and, with --export_images, uncertainty.png')
+    p.add_argument('--temperature', type=float, default=argparse.SUPPRESS, metavar='T',
+                   help='temperature scaling: the tables and masks of sigmoid(logit(p) / T), T in [0.05, 20], e.g. the temperature '
+                        '`evaluate --calibration` fitted (default: 1, no scaling)')
     return parser
 
 

@@ -109,6 +109,21 @@ class SpreadOutcome(C.Structure):                  # dnnca_spread_outcome (64 by
     _fields_ = [('n', C.c_uint64 * 4), ('sum_q24', C.c_uint64 * 4)]
 
 
+class CalibBin(C.Structure):                       # dnnca_calib_bin (32 bytes): classes 0 (y <= 0.5) and 1
+    _fields_ = [('n', C.c_uint64 * 2), ('sum_q24', C.c_uint64 * 2)]
+
+
+class CalibTotal(C.Structure):                     # dnnca_calib_total (64 bytes): sum q^2 = sq_hi * 2^32 + sq_lo
+    _fields_ = [('n', C.c_uint64 * 2), ('sum_q24', C.c_uint64 * 2), ('sq_lo', C.c_uint64 * 2), ('sq_hi', C.c_uint64 * 2)]
+
+
+# DeviceModel.calibration returns structured arrays of these dtypes
+CALIB_BIN_DTYPE = np.dtype([('n', '<u8', (2,)), ('sum_q24', '<u8', (2,))])
+CALIB_TOTAL_DTYPE = np.dtype([('n', '<u8', (2,)), ('sum_q24', '<u8', (2,)), ('sq_lo', '<u8', (2,)), ('sq_hi', '<u8', (2,))])
+CALIB_MAX_BINS, CALIB_MAX_TEMPERATURES = 256, 64
+CALIB_MIN_T, CALIB_MAX_T = 0.05, 20.0              # the temperatures the library accepts
+
+
 # DeviceModel.lesion_table_spread / spread_by_outcome return structured arrays of these dtypes
 LESION_SPREAD_DTYPE = np.dtype([('slice', '<i4'), ('row', '<i4'), ('area', '<i4'), ('max_spread', '<f4'), ('sum_spread_q24', '<u8')])
 SLICE_SPREAD_DTYPE = np.dtype([('pixels', '<i4'), ('max_spread', '<f4'), ('sum_spread_q24', '<u8')])
@@ -200,6 +215,9 @@ SIGNATURES = {
                                             C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
                                             C.POINTER(C.c_int32), _FP, C.POINTER(LesionSpread), C.POINTER(SliceSpread)]),
     'dnnca_spread_by_outcome': (C.c_int, [_VP, _FP, _FP, _FP, C.c_int, C.c_int, C.c_int, _FP, C.c_int, C.POINTER(SpreadOutcome)]),
+    'dnnca_calibration': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, _FP, C.c_int, C.POINTER(CalibBin),
+                                    C.POINTER(CalibTotal), C.POINTER(C.c_double)]),
+    'dnnca_prob_temperature': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, _FP]),
     'dnnca_lesion_table_linked': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                             C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
                                             C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(LesionLink), C.c_int64,

@@ -15,6 +15,7 @@ quoting, '\\n' line ends, an empty header cell for the index."""
 
 import csv
 import io
+import math
 import os
 import re
 import struct
@@ -465,6 +466,125 @@ def uncertainty_image(spread):
 def uncertainty_path(root, tag):
     """<root>/<last 3 components of the exam path>/<sliceID %02d>/uncertainty.png"""
     return os.path.join(export_dir(root, '', tag), 'uncertainty.png')
+
+
+# ---- `--calibration`: can the probability be believed? ------------------------------------------------------------------------------
+# DeviceModel.calibration gives exact integers per slice -- pixels and sums of q = rint(p * 2^24) per bin and class, the sum of q^2
+# per class in two words -- and the NLL sums at a grid of temperatures in float64.  Everything here is Python integers and float64:
+# a pooled value comes from the integer tables summed over the slices and from the NLL rows summed, never from per-slice values.
+CALIBRATION_RESULT_COLUMNS = ['pixels', 'positives', 'mean_prob', 'prevalence', 'ece', 'mce', 'brier', 'nll', 'temperature',
+                              'nll_at_temperature', 'at_grid_edge']
+CALIBRATION_BIN_COLUMNS = ['bin', 'lower', 'upper', 'pixels', 'positives', 'mean_prob', 'frequency', 'gap']
+CALIBRATION_SLICE_COLUMNS = ['exam', 'slice', 'pixels', 'positives', 'ece', 'brier', 'nll']
+CALIBRATION_BINS = 15
+CALIBRATION_GRID = tuple(2.0 ** ((j - 20) / 10.0) for j in range(41))       # 0.25 .. 4, ten points per octave
+CALIBRATION_MAX_TEMPERATURES = 64                                            # one DeviceModel.calibration call
+TEMPERATURE_RANGE = (0.05, 20.0)                                             # what the library accepts
+
+
+def calibration_grid(temperatures=None):
+    """the temperatures of one calibration call: the given ones (None: CALIBRATION_GRID) as float32 values, sorted, without
+    duplicates, with T = 1 added when it is missing"""
+    t = sorted(set(float(np.float32(v)) for v in (CALIBRATION_GRID if temperatures is None else temperatures)) | {1.0})
+    if len(t) > CALIBRATION_MAX_TEMPERATURES:
+        raise ValueError('--calibration_temperatures: %d temperatures (T = 1 included), at most %d' % (len(t), CALIBRATION_MAX_TEMPERATURES))
+    if not all(TEMPERATURE_RANGE[0] <= v <= TEMPERATURE_RANGE[1] for v in t):
+        raise ValueError('--calibration_temperatures: every temperature must lie in [%g, %g]' % TEMPERATURE_RANGE)
+    return t
+
+
+def calibration_counts(bins):
+    """bin records (n [2], sum_q24 [2]) of one slice [n_bins], or of several slices [S, n_bins] -> (n, q): per bin the Python
+    integers [class 0, class 1], summed over the slices"""
+    bins = np.asarray(bins)
+    bins = bins.reshape((-1, bins.shape[-1]))
+    n = [[sum(int(v) for v in bins['n'][:, k, c]) for c in (0, 1)] for k in range(bins.shape[1])]
+    q = [[sum(int(v) for v in bins['sum_q24'][:, k, c]) for c in (0, 1)] for k in range(bins.shape[1])]
+    return n, q
+
+
+def calibration_table(bins):
+    """the reliability table: per bin [bin, lower edge, upper edge, pixels, positives, mean probability, observed frequency, gap =
+    |mean probability - frequency|]; the last three are None in an empty bin"""
+    n, q = calibration_counts(bins)
+    rows = []
+    for k, ((n0, n1), (q0, q1)) in enumerate(zip(n, q)):
+        pixels = n0 + n1
+        mean = (q0 + q1) / Q24 / pixels if pixels else None
+        freq = n1 / pixels if pixels else None
+        rows.append([k, k / len(n), (k + 1) / len(n), pixels, n1, mean, freq, abs(mean - freq) if pixels else None])
+    return rows
+
+
+def calibration_errors(table):
+    """(ECE, MCE) of a calibration_table: sum_k n_k / N |mean probability - frequency| over the non-empty bins, and the largest gap"""
+    total = sum(r[3] for r in table)
+    gaps = [(r[3], r[7]) for r in table if r[3]]
+    if not total:
+        return None, None
+    return sum(n / total * g for n, g in gaps), max(g for _, g in gaps)
+
+
+def brier_score(totals):
+    """the mean of (p - class)^2 from the integers of one total record or of several: class 0 adds sum q^2, class 1
+    n 2^48 - 2^25 sum q + sum q^2; all of it over 2^48 N"""
+    totals = np.asarray(totals).reshape(-1)
+    tot = lambda f, c: sum(int(v) for v in totals[f][:, c])
+    sq = [(tot('sq_hi', c) << 32) + tot('sq_lo', c) for c in (0, 1)]
+    n = [tot('n', c) for c in (0, 1)]
+    if not n[0] + n[1]:
+        return None
+    return (sq[0] + (n[1] << 48) - (tot('sum_q24', 1) << 25) + sq[1]) / ((n[0] + n[1]) << 48)      # integers: one rounding
+
+
+def fit_temperature(temperatures, nll):
+    """the temperature with the smallest NLL: (temperature, NLL there, at_grid_edge).  The grid point with the smallest NLL; when it
+    is interior, the vertex of the parabola through it and its two neighbours in (log T, NLL), clamped to their interval, and the
+    parabola's value there; at an end of the grid that end, the grid's value and at_grid_edge = 1"""
+    pts = sorted((float(t), float(v)) for t, v in zip(temperatures, nll))
+    if not pts:
+        raise ValueError('fit_temperature: no temperatures')
+    i = min(range(len(pts)), key=lambda j: pts[j][1])
+    if i == 0 or i == len(pts) - 1:
+        return pts[i][0], pts[i][1], 1
+    (x0, y0), (x1, y1), (x2, y2) = [(math.log(t), v) for t, v in pts[i - 1:i + 2]]
+    den = (x1 - x0) * (y1 - y2) - (x1 - x2) * (y1 - y0)
+    if den == 0:                                 # three equal values: the grid point
+        return pts[i][0], y1, 0
+    x = x1 - 0.5 * ((x1 - x0) ** 2 * (y1 - y2) - (x1 - x2) ** 2 * (y1 - y0)) / den
+    x = min(max(x, x0), x2)
+    y = (y0 * (x - x1) * (x - x2) / ((x0 - x1) * (x0 - x2)) + y1 * (x - x0) * (x - x2) / ((x1 - x0) * (x1 - x2)) +
+         y2 * (x - x0) * (x - x1) / ((x2 - x0) * (x2 - x1)))
+    return math.exp(x), y, 0
+
+
+def _blank(v):
+    return '' if v is None else repr(float(v))
+
+
+def calibration_slice_values(exam, slice_id, bins, total, nll_at_1):
+    """the calibration_slices.csv line of one slice: `bins` its [n_bins] records, `total` its total record, the NLL per pixel"""
+    pixels = int(total['n'][0]) + int(total['n'][1])
+    ece, _ = calibration_errors(calibration_table(bins))
+    return [exam, int(slice_id), pixels, int(total['n'][1]), _blank(ece), _blank(brier_score(total)),
+            _blank(float(nll_at_1) / pixels if pixels else None)]
+
+
+def calibration_summary(bins, totals, temperatures, nll):
+    """bins [S, n_bins], totals [S] and nll [S, T] of all slices -> (the calibration_results.csv values, the calibration_bins.csv
+    lines): everything pooled from the summed integers and the summed NLL rows; NLL values are per pixel"""
+    table = calibration_table(bins)
+    pixels, positives = sum(r[3] for r in table), sum(r[4] for r in table)
+    _, q = calibration_counts(bins)
+    ece, mce = calibration_errors(table)
+    curve = [math.fsum(col) / pixels if pixels else 0.0 for col in np.asarray(nll, np.float64).reshape(-1, len(temperatures)).T]
+    at_1 = curve[[float(t) for t in temperatures].index(1.0)]
+    t_fit, v_fit, edge = fit_temperature(temperatures, curve)
+    result = [pixels, positives, _blank(sum(a + b for a, b in q) / Q24 / pixels if pixels else None),
+              _blank(positives / pixels if pixels else None), _blank(ece), _blank(mce), _blank(brier_score(totals)), _blank(at_1),
+              repr(t_fit), repr(v_fit), edge]
+    lines = [r[:1] + [repr(r[1]), repr(r[2])] + r[3:5] + [_blank(v) for v in r[5:]] for r in table]
+    return result, lines
 
 
 def plain_csv(names, rows):

@@ -311,6 +311,9 @@ struct Model {
     float* tta_mom = nullptr;
     bool tta_spread_valid = false;
     int tta_spread_batch = 0;
+    // calibration (dnnca_calibration): the device tables, the temperatures and the block partials of the NLL, grown on demand
+    void* calib_ws = nullptr;
+    size_t calib_ws_bytes = 0;
 
     ~Model();
     int build();

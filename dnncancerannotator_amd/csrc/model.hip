@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "calib.h"
 #include "fast.h"
 #include "kernels.h"
 #include "region.h"
@@ -89,6 +90,7 @@ Model::~Model() {
     ig_release(this);
     for (void* a : allocs) (void)hipFree(a);
     if (tta_io) (void)hipFree(tta_io);
+    if (calib_ws) (void)hipFree(calib_ws);
     for (auto& r : recs) {
         (void)hipEventDestroy(r.a);
         (void)hipEventDestroy(r.b);
@@ -2292,6 +2294,146 @@ int dnnca_spread_by_outcome(void* model, const float* prob_hw, const float* spre
         p_dev = in, s_dev = in + n, y_dev = yd;
     }
     DN_TRY(spread_by_outcome(M, p_dev, s_dev, y_dev, batch, hw, thresholds, n_thresholds, out));
+    return M->flush_profile();
+}
+
+// ---- calibration (kernels_calib.hip) ------------------------------------------------------------------------------------------
+static bool calib_temperature_ok(float t) { return t >= kCalibMinT && t <= kCalibMaxT; }      // false for a NaN
+
+int dnnca_calibration(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w, int n_bins,
+                      const float* temperatures, int n_temperatures, dnnca_calib_bin* bins, dnnca_calib_total* totals, double* nll) {
+    MODEL(model);
+    DN_TRY(check_batch(M, batch));
+    if (!y_hw || !bins || !totals) { set_error("calibration: null y_hw / bins / totals"); return DNNCA_EINVAL; }
+    if (n_bins < 1 || n_bins > kCalibMaxBins) { set_error("calibration: %d bins outside 1..%d", n_bins, kCalibMaxBins); return DNNCA_EINVAL; }
+    if (n_temperatures < 0 || n_temperatures > kCalibMaxTemps) {
+        set_error("calibration: %d temperatures outside 0..%d", n_temperatures, kCalibMaxTemps);
+        return DNNCA_EINVAL;
+    }
+    if (n_temperatures > 0 && (!temperatures || !nll)) { set_error("calibration: temperatures without their array or without nll"); return DNNCA_EINVAL; }
+    for (int t = 0; t < n_temperatures; ++t)
+        if (!calib_temperature_ok(temperatures[t])) {
+            set_error("calibration: temperature %d is %g (outside [%g, %g])", t, (double)temperatures[t], (double)kCalibMinT, (double)kCalibMaxT);
+            return DNNCA_EINVAL;
+        }
+    if (!prob_hw) {
+        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
+            set_error("calibration: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
+            return DNNCA_EINVAL;
+        }
+        h = M->outH;
+        w = M->outW;
+    }
+    if (h < 1 || w < 1 || (int64_t)h * w > INT32_MAX || batch > 65535) {
+        set_error("calibration: bad plane %d x %d x %d", batch, h, w);
+        return DNNCA_EINVAL;
+    }
+    if (!prob_hw && batch > M->last_batch) {
+        set_error("calibration: %d slices asked for, the model's probabilities hold %d (the last forward's)", batch, M->last_batch);
+        return DNNCA_ESTATE;
+    }
+    const size_t hw = (size_t)h * w, n = (size_t)batch * hw;
+    const float *p_dev = M->prob, *y_dev = M->y_stage;
+    if (!prob_hw) {
+        HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+    } else {
+        float *in = nullptr, *yd = nullptr;
+        DN_TRY(tta_io_buffers(M, n, n, &in, &yd));
+        HIP_TRY(hipMemcpyAsync(in, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+        HIP_TRY(hipMemcpyAsync(yd, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+        p_dev = in, y_dev = yd;
+    }
+    // workspace: the bin table, the squares (both zeroed), 1 / T, the sums per slice and temperature, the block partials
+    int runs = 0, blocks = 0;
+    calib_nll_shape(hw, &runs, &blocks);
+    const int nt = n_temperatures;
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t bins_bytes = (size_t)batch * n_bins * sizeof(dnnca_calib_bin), sq_bytes = (size_t)batch * 32;
+    const size_t zero_bytes = up(bins_bytes) + up(sq_bytes), it_bytes = up((size_t)kCalibMaxTemps * 8);
+    const size_t sum_bytes = up((size_t)batch * nt * 8), part_bytes = up((size_t)batch * blocks * nt * 8);
+    const size_t need = zero_bytes + it_bytes + sum_bytes + part_bytes;
+    if (need > M->calib_ws_bytes) {
+        if (M->calib_ws) HIP_TRY(hipFree(M->calib_ws));
+        M->calib_ws = nullptr;
+        M->calib_ws_bytes = 0;
+        HIP_TRY(hipMalloc(&M->calib_ws, need));
+        M->calib_ws_bytes = need;
+    }
+    char* ws = (char*)M->calib_ws;
+    unsigned long long* bins_dev = (unsigned long long*)ws;
+    unsigned long long* sq_dev = (unsigned long long*)(ws + up(bins_bytes));
+    double* it_dev = (double*)(ws + zero_bytes);
+    double* sum_dev = (double*)(ws + zero_bytes + it_bytes);
+    double* part_dev = (double*)(ws + zero_bytes + it_bytes + sum_bytes);
+    hipStream_t s = M->stream;
+    HIP_TRY(hipMemsetAsync(ws, 0, zero_bytes, s));
+    LAUNCH(M, "calib_bins", 8.0 * n, 0, g_calib_bins(s, p_dev, y_dev, batch, hw, n_bins, bins_dev, sq_dev));
+    HIP_TRY(hipGetLastError());
+    double inv_t[kCalibMaxTemps];
+    if (nt) {
+        for (int t = 0; t < nt; ++t) inv_t[t] = 1.0 / (double)temperatures[t];
+        HIP_TRY(hipMemcpyAsync(it_dev, inv_t, (size_t)nt * 8, hipMemcpyHostToDevice, s));
+        // per pixel and temperature one exp and one log1p in double beside the product and the sum; the logit once per pixel and chunk
+        LAUNCH(M, "calib_nll", 8.0 * n * ((nt + 7) / 8), 60.0 * n * nt, g_calib_nll(s, p_dev, y_dev, batch, hw, it_dev, nt, part_dev));
+        HIP_TRY(hipGetLastError());
+        LAUNCH(M, "calib_nll_sum", 8.0 * batch * blocks * nt, (double)batch * blocks * nt, g_calib_nll_sum(s, part_dev, batch, hw, nt, sum_dev));
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<unsigned long long> sq((size_t)batch * 4);
+    std::vector<double> sums((size_t)batch * nt);
+    HIP_TRY(hipMemcpyAsync(bins, bins_dev, bins_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(sq.data(), sq_dev, sq_bytes, hipMemcpyDeviceToHost, s));
+    if (nt) HIP_TRY(hipMemcpyAsync(sums.data(), sum_dev, (size_t)batch * nt * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));      // inv_t, sq and sums are read and written by the copies up to here
+    // a slice's pixels and q sums per class are those of its bins
+    for (int b = 0; b < batch; ++b) {
+        dnnca_calib_total t = {};
+        for (int k = 0; k < n_bins; ++k)
+            for (int c = 0; c < 2; ++c) {
+                t.n[c] += bins[(size_t)b * n_bins + k].n[c];
+                t.sum_q24[c] += bins[(size_t)b * n_bins + k].sum_q24[c];
+            }
+        for (int c = 0; c < 2; ++c) t.sq_lo[c] = sq[(size_t)b * 4 + c], t.sq_hi[c] = sq[(size_t)b * 4 + 2 + c];
+        totals[b] = t;
+    }
+    for (size_t i = 0; i < sums.size(); ++i) nll[i] = sums[i];
+    return M->flush_profile();
+}
+
+int dnnca_prob_temperature(void* model, const float* prob_hw, int batch, int h, int w, float temperature, float* out_hw) {
+    MODEL(model);
+    DN_TRY(check_batch(M, batch));
+    if (!calib_temperature_ok(temperature)) {
+        set_error("temperature %g outside [%g, %g]", (double)temperature, (double)kCalibMinT, (double)kCalibMaxT);
+        return DNNCA_EINVAL;
+    }
+    if (prob_hw && !out_hw) { set_error("temperature: a host plane needs out_hw"); return DNNCA_EINVAL; }
+    if (!prob_hw) {
+        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
+            set_error("temperature: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
+            return DNNCA_EINVAL;
+        }
+        h = M->outH;
+        w = M->outW;
+    }
+    if (h < 1 || w < 1 || (int64_t)h * w > INT32_MAX) { set_error("temperature: bad plane %d x %d x %d", batch, h, w); return DNNCA_EINVAL; }
+    if (!prob_hw && batch > M->last_batch) {
+        set_error("temperature: %d slices asked for, the model's probabilities hold %d (the last forward's)", batch, M->last_batch);
+        return DNNCA_ESTATE;
+    }
+    const size_t n = (size_t)batch * h * w;
+    const float* src = M->prob;
+    float* dst = M->prob;
+    if (prob_hw) {
+        float *in = nullptr, *out = nullptr;
+        DN_TRY(tta_io_buffers(M, n, n, &in, &out));
+        HIP_TRY(hipMemcpyAsync(in, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
+        src = in, dst = out;
+    }
+    LAUNCH(M, "prob_temperature", 8.0 * n, 40.0 * n, g_prob_temperature(M->stream, src, dst, n, temperature));
+    HIP_TRY(hipGetLastError());
+    if (out_hw) HIP_TRY(hipMemcpyAsync(out_hw, dst, n * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
     return M->flush_profile();
 }
 

@@ -575,6 +575,57 @@ class DeviceModel:
                                                fptr(thr), thr.size, out.ctypes.data_as(C.POINTER(_lib.SpreadOutcome))))
         return out
 
+    # ---- `evaluate --calibration`, `--temperature` (kernels_calib.hip) ---------------------------------------------
+    def calibration(self, y, n_bins=15, temperatures=(), batch=None, prob=None):
+        """the reliability table of the probabilities against the labels y [B, h, w] (dnnca_calibration): (bins, totals, nll).  bins:
+        structured array (_lib.CALIB_BIN_DTYPE: n [2], sum_q24 [2] per class 0 / 1 = y > 0.5) [B, n_bins], bin k = min(n_bins - 1,
+        floor(p * n_bins)) of the probability clamped to [0, 1]; totals (_lib.CALIB_TOTAL_DTYPE: n, sum_q24, sq_lo, sq_hi) [B] with
+        sum q^2 = sq_hi * 2^32 + sq_lo; nll float64 [B, T]: the negative log-likelihood summed over the slice at every one of
+        `temperatures` (at most 64, each in [0.05, 20]; none: an empty array and no NLL launch).  The probabilities are those of the
+        last forward / forward_tta, or the host plane `prob` [B, h, w].  casewise.calibration_* turn the integers into ECE, MCE and
+        Brier score.  The tables are exact integers; everything is bit-identical from run to run."""
+        y = as_f32(y)
+        if y.ndim == 4 and y.shape[-1] == 1:
+            y = np.ascontiguousarray(y[..., 0])
+        if y.ndim != 3:
+            raise ValueError('y must be [B, h, w], got %s' % (y.shape,))
+        if batch is not None and int(batch) != y.shape[0]:
+            raise ValueError('batch %d but y holds %d slices' % (batch, y.shape[0]))
+        B, h, w = y.shape
+        pp = None
+        if prob is not None:
+            prob = as_f32(prob).reshape(-1)
+            if prob.size != y.size:
+                raise ValueError('prob and y differ in size')
+            pp = fptr(prob)
+        temps = np.ascontiguousarray(np.asarray(temperatures, np.float32).reshape(-1))
+        bins = np.zeros((B, int(n_bins)), _lib.CALIB_BIN_DTYPE)
+        totals = np.zeros(B, _lib.CALIB_TOTAL_DTYPE)
+        nll = np.zeros((B, temps.size), np.float64)
+        check(self.lib.dnnca_calibration(self.handle, pp, fptr(y), B, h if pp is not None else 0, w if pp is not None else 0, int(n_bins),
+                                         fptr(temps) if temps.size else None, int(temps.size),
+                                         bins.ctypes.data_as(C.POINTER(_lib.CalibBin)), totals.ctypes.data_as(C.POINTER(_lib.CalibTotal)),
+                                         nll.ctypes.data_as(C.POINTER(C.c_double)) if temps.size else None))
+        return bins, totals, nll
+
+    def scale_temperature(self, temperature, batch, prob=None):
+        """temperature scaling (dnnca_prob_temperature): p -> sigmoid(logit(p) / temperature), in double, rounded once.  Without
+        `prob` the model's probability buffer is scaled in place for the last forward's `batch` slices -- every consumer that reads
+        it afterwards sees the calibrated values; call it ONCE per forward, a second call scales again -- and None is returned.
+        With a host plane `prob` [B, h, w] the scaled plane is returned and the model's buffer stays untouched."""
+        if prob is None:
+            check(self.lib.dnnca_prob_temperature(self.handle, None, int(batch), 0, 0, float(temperature), None))
+            return None
+        prob = as_f32(prob)
+        if prob.ndim == 4 and prob.shape[-1] == 1:
+            prob = np.ascontiguousarray(prob[..., 0])
+        if prob.ndim != 3 or (batch is not None and int(batch) != prob.shape[0]):
+            raise ValueError('prob must be [B, h, w] of batch slices, got %s' % (prob.shape,))
+        out = np.empty_like(prob)
+        check(self.lib.dnnca_prob_temperature(self.handle, fptr(prob), prob.shape[0], prob.shape[1], prob.shape[2], float(temperature),
+                                              fptr(out)))
+        return out
+
     def lesion_table_linked(self, batch=None, prob=None, continues=None, threshold=0.5, resize_factor=1.0, filter_size=5, min_area=0,
                             max_lesions=256, mask=True):
         """lesion_table plus the links between neighbouring slices: (rows, totals, masks, links); the first three are what

@@ -49,21 +49,43 @@ def _element_shape(dataset):
     raise ValueError('empty dataset')
 
 
-def _forward_on_device(dm, xb, tta_mask, spread=False):
+def _forward_on_device(dm, xb, tta_mask, spread=False, temperature=None):
     """the inference forward whose probabilities stay on the device: the plain one or, with a view mask (tta.mask_of), the test-time
-    augmented one; with `spread` the augmented one that also keeps the views' spread on the device (--uncertainty)"""
+    augmented one; with `spread` the augmented one that also keeps the views' spread on the device (--uncertainty).  With a
+    temperature (--temperature, check_temperature) the probabilities are then scaled once, in place: every consumer reads the
+    calibrated values; the spread stays that of the unscaled views"""
     if tta_mask is None:
         dm.forward(xb, training=False, return_prob=False)
     elif spread:
         dm.forward_tta_spread(xb, tta_mask, return_prob=False, return_spread=False)
     else:
         dm.forward_tta(xb, tta_mask, return_prob=False)
+    if temperature is not None:
+        dm.scale_temperature(temperature, len(xb))
 
 
 def check_uncertainty(uncertainty, tta):
     """--uncertainty measures the disagreement of the test-time-augmentation views: without views there is nothing to measure"""
     if uncertainty and tta == tta_modes.NONE:
         raise ValueError('--uncertainty needs the views of test-time augmentation: add --tta flips (or --tta d4 on square slices)')
+
+
+def check_temperature(temperature):
+    """--temperature T: None for no scaling (no flag, or T = 1: no new call runs), else the float; outside the range the library
+    accepts (casewise.TEMPERATURE_RANGE) or NaN: a ValueError, before anything is read"""
+    if temperature is None:
+        return None
+    t = float(temperature)
+    if not casewise.TEMPERATURE_RANGE[0] <= t <= casewise.TEMPERATURE_RANGE[1]:
+        raise ValueError('--temperature must lie in [%g, %g], got %r' % (casewise.TEMPERATURE_RANGE + (temperature,)))
+    return None if t == 1.0 else t
+
+
+def check_calibration(n_bins, temperatures):
+    """--calibration_bins and --calibration_temperatures: (bins, the temperature grid of casewise.calibration_grid) or a ValueError"""
+    if not 1 <= int(n_bins) <= 256:
+        raise ValueError('--calibration_bins must lie in 1..256, got %r' % (n_bins,))
+    return int(n_bins), casewise.calibration_grid(temperatures)
 
 
 def _csv_value(v):
@@ -444,12 +466,14 @@ class TFKerasModel:
         return OrderedDict((m.name, _log_value(m)) for m in objs)
 
     # ---- evaluation (engine.py:139-210) ----------------------------------------------------------------------
-    def _evaluate(self, dataset, staged=False, tta_mask=None):
+    def _evaluate(self, dataset, staged=False, tta_mask=None, temperature=None):
         """keras Model.evaluate(return_dict=True): mean loss over batches + pixel metrics, training=False.  One batch of
         the dataset is one test step per replica: the positive-rate class weight (utils/losses.py:24-27) is taken over the
         whole per-replica batch, never over a chunk of it.
         tta_mask (evaluate --tta): after a batch's test step DeviceModel.forward_tta runs on the same slices, so the pixel and
-        region metrics read the mean over the views; `loss` stays the loss of the untransformed view (the test step's own)."""
+        region metrics read the mean over the views; `loss` stays the loss of the untransformed view (the test step's own).
+        temperature (evaluate --temperature): the probabilities the metrics read are scaled once behind the test step (and behind
+        forward_tta when that runs); `loss` stays the unscaled test step's."""
         cfg_kw = self.loss.device_cfg()
         for m in self.metrics + self.region_metrics:
             m.reset_state()
@@ -464,6 +488,8 @@ class TFKerasModel:
             count += len(xb)
             if tta_mask is not None:
                 dm_.forward_tta(xb, tta_mask, return_prob=False)
+            if temperature is not None:
+                dm_.scale_temperature(temperature, len(xb))
             for m in self.metrics:
                 m.update_state(dm_, yb)
             for spec, ms in region_groups:
@@ -572,7 +598,8 @@ class TFKerasModel:
              exam_min_area=0, exam_filter_size=5, exam_resize_factor=1.0, exam_max_lesions=256, exam_link_min_overlap=1,
              surface_ds=None, surface_distances=False, surface_threshold=(0.5,), surface_percentile=casewise.SURFACE_PERCENTILE,
              surface_min_area=0, surface_filter_size=5, surface_resize_factor=1.0, surface_max_samples=65536, tta='none',
-             uncertainty_ds=None, uncertainty=False, uncertainty_thresholds=(0.5,)):
+             uncertainty_ds=None, uncertainty=False, uncertainty_thresholds=(0.5,), calibration_ds=None, calibration=False,
+             calibration_bins=casewise.CALIBRATION_BINS, calibration_temperatures=None, temperature=None):
         """exam_lesions (`evaluate --exam_lesions`): after every checkpoint's evaluation rank 0 also runs _exam_lesion_pass over
         exam_ds (batches (x, y, paths, sliceIDs), a data set of its own: viz_ds is not needed) and writes exam_lesion_results.csv,
         exam_lesion_cases.csv and exam_lesion_matches.csv under <export_path>/<tag>/; every other file is what it is without it.
@@ -585,8 +612,20 @@ class TFKerasModel:
         uncertainty (`evaluate --tta MODE --uncertainty`): after every checkpoint's evaluation rank 0 also runs _uncertainty_pass
         over uncertainty_ds (the same kind of data set as exam_ds; the flags may share one) and writes uncertainty_results.csv and
         uncertainty_slices.csv under <export_path>/<tag>/: pixels and mean spread of the views per pixel outcome at every one of
-        uncertainty_thresholds.  Every other file is what it is without the flag.  Needs a tta mode other than 'none'."""
+        uncertainty_thresholds.  Every other file is what it is without the flag.  Needs a tta mode other than 'none'.
+        calibration (`evaluate --calibration`): after every checkpoint's evaluation rank 0 also runs _calibration_pass over
+        calibration_ds (the same kind of data set; the flags may share one) and writes calibration_results.csv, calibration_bins.csv
+        and calibration_slices.csv under <export_path>/<tag>/: reliability table, ECE, MCE, Brier score, NLL and the temperature
+        that minimises the NLL over calibration_temperatures (None: casewise.CALIBRATION_GRID; T = 1 is always in).  With and
+        without a tta mode.
+        temperature (`evaluate --temperature T`): every probability read -- by the pixel and region metrics, the Visualizer and every
+        extra pass, --calibration included -- is scaled by DeviceModel.scale_temperature, once per forward.  The evaluation then
+        runs batch by batch, `loss` stays the unscaled test step's and the spread of --uncertainty that of the unscaled views.
+        None or 1: nothing new runs."""
         check_uncertainty(uncertainty, tta)
+        temperature = check_temperature(temperature)
+        if calibration:
+            calibration_bins, calibration_grid = check_calibration(calibration_bins, calibration_temperatures)
         if visualize_sensitivity and not getattr(self.model, 'supports_sensitivity', True):
             raise NotImplementedError('--visualize_sensitivity is not implemented for model: %s (the input-gradient pass covers the '
                                       'U-Net models only)' % self.model_config['model'])
@@ -594,6 +633,9 @@ class TFKerasModel:
         self._build(dataset)
         if tta_mask is not None:
             logging.info('evaluate --tta %s: the evaluation runs batch by batch (the staged ring has no test-time augmentation)', tta)
+        if temperature is not None:
+            logging.info('evaluate --temperature %g: the evaluation runs batch by batch (the staged ring does not scale)', temperature)
+        more = {} if temperature is None else dict(temperature=temperature)     # the passes get the keyword only with a temperature
         ckpt_path = os.path.join(save_path, 'checkpoints')
         if not export_path:
             export_path = os.path.join(save_path, 'tfevents')
@@ -620,6 +662,8 @@ class TFKerasModel:
         surface_tables = [], [], []      # the lines of surface_results.csv, surface_cases.csv and surface_slices.csv
         uncertainty_pass = bool(uncertainty) and uncertainty_ds is not None and self.ctx.rank == 0
         uncertainty_tables = [], []      # the lines of uncertainty_results.csv and uncertainty_slices.csv
+        calibration_pass = bool(calibration) and calibration_ds is not None and self.ctx.rank == 0
+        calibration_tables = [], [], []  # the lines of calibration_results.csv, calibration_bins.csv and calibration_slices.csv
         rows = OrderedDict()
         previous_step = None
         for ckpt_step, ckpt_path_ in self.get_ckpts(ckpt_path).items():
@@ -630,27 +674,39 @@ class TFKerasModel:
                 continue
             previous_step = ckpt_step
             self.load(ckpt_path_)
-            rows[ckpt_step] = self._evaluate(dataset, staged=True) if tta_mask is None else \
-                self._evaluate(dataset, staged=False, tta_mask=tta_mask)
+            rows[ckpt_step] = self._evaluate(dataset, staged=True) if tta_mask is None and temperature is None else \
+                self._evaluate(dataset, staged=False, tta_mask=tta_mask, **more)
             if visualize:
                 self._visualize(viz_ds, ckpt_step, viz_root, export_csv, export_images, overlay, casewise_rows, writer,
-                                sensitivity=bool(visualize_sensitivity), tta_mask=tta_mask)
+                                sensitivity=bool(visualize_sensitivity), tta_mask=tta_mask, **more)
             if exam_pass:
                 for t, new in zip(exam_tables, self._exam_lesion_pass(
                         exam_ds, ckpt_step, [float(t) for t in exam_threshold], exam_iou, exam_link_min_overlap,
                         dict(resize_factor=exam_resize_factor, filter_size=exam_filter_size, min_area=exam_min_area,
-                             max_lesions=exam_max_lesions), tta_mask=tta_mask)):
+                             max_lesions=exam_max_lesions), tta_mask=tta_mask, **more)):
                     t += new
             if surface_pass:
                 for t, new in zip(surface_tables, self._surface_pass(
                         surface_ds, ckpt_step, [float(t) for t in surface_threshold], float(surface_percentile),
                         dict(resize_factor=surface_resize_factor, filter_size=surface_filter_size, min_area=surface_min_area,
-                             max_samples=surface_max_samples), tta_mask=tta_mask)):
+                             max_samples=surface_max_samples), tta_mask=tta_mask, **more)):
                     t += new
             if uncertainty_pass:
                 for t, new in zip(uncertainty_tables, self._uncertainty_pass(uncertainty_ds, ckpt_step,
-                                                                             [float(t) for t in uncertainty_thresholds], tta_mask)):
+                                                                             [float(t) for t in uncertainty_thresholds], tta_mask,
+                                                                             **more)):
                     t += new
+            if calibration_pass:
+                for t, new in zip(calibration_tables, self._calibration_pass(calibration_ds, ckpt_step, calibration_bins,
+                                                                             calibration_grid, tta_mask, **more)):
+                    t += new
+        if calibration_pass:
+            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
+            for name, cols, table in zip(('calibration_results.csv', 'calibration_bins.csv', 'calibration_slices.csv'),
+                                         (casewise.CALIBRATION_RESULT_COLUMNS, casewise.CALIBRATION_BIN_COLUMNS,
+                                          casewise.CALIBRATION_SLICE_COLUMNS), calibration_tables):
+                with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
+                    f.write(casewise.plain_csv(['step'] + cols, table))
         if uncertainty_pass:
             os.makedirs(os.path.join(export_path, tag), exist_ok=True)
             for name, cols, table in zip(('uncertainty_results.csv', 'uncertainty_slices.csv'),
@@ -686,7 +742,7 @@ class TFKerasModel:
         return rows
 
     def _visualize(self, viz_ds, step, root, export_csv, export_images, overlay, casewise_rows, writer, sensitivity=False,
-                   tta_mask=None):
+                   tta_mask=None, temperature=None):
         """One Visualizer pass (callbacks.py process_batch / _emit) over viz_ds batches (x, y, paths, sliceIDs): forward
         (training=False), the per-slice region counts (export_csv), the composite images (export_images), then the files.  The
         probabilities stay on the device; only the counts and the uint8 images come back.  casewise_rows gains one row per slice,
@@ -703,7 +759,7 @@ class TFKerasModel:
             for i in range(0, len(x), dm.max_batch):
                 xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
                 tags = [casewise.tag_of(p, k) for p, k in zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch])]
-                _forward_on_device(dm, xb, tta_mask)
+                _forward_on_device(dm, xb, tta_mask, temperature=temperature)
                 if export_csv:
                     counts = dm.region_confusion_slices(yb, [spec])
                     for t, c in zip(tags, counts):
@@ -725,7 +781,7 @@ class TFKerasModel:
                             writer.submit(casewise.sensitivity_path(root, t, step, 'images'),
                                           lambda r: casewise.encode_png(casewise.sensitivity_chart(r)), row)
 
-    def _exam_lesion_pass(self, ds, step, thresholds, iou, min_overlap, kw, tta_mask=None):
+    def _exam_lesion_pass(self, ds, step, thresholds, iou, min_overlap, kw, tta_mask=None, temperature=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --exam_lesions`: per max_batch split one forward whose
         probabilities stay on the device and one DeviceModel.lesion_table_matched per threshold; then per threshold and exam
         casewise.link_lesions on either plane and casewise.match_exam_lesions.  Returns the new lines of (exam_lesion_results.csv,
@@ -750,7 +806,7 @@ class TFKerasModel:
             for i in range(0, len(x), dm.max_batch):
                 xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
                 pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
-                _forward_on_device(dm, xb, tta_mask)
+                _forward_on_device(dm, xb, tta_mask, temperature=temperature)
                 continues = []
                 for p, k in pk:
                     continues.append(last is not None and p == last[0] and int(k) == last[1] + 1)
@@ -788,7 +844,7 @@ class TFKerasModel:
             results.append(lead + casewise.exam_match_summary(mine_cases))
         return results, cases, matches
 
-    def _surface_pass(self, ds, step, thresholds, percentile, kw, tta_mask=None):
+    def _surface_pass(self, ds, step, thresholds, percentile, kw, tta_mask=None, temperature=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --surface_distances`: per max_batch split one forward whose
         probabilities stay on the device and one DeviceModel.surface_distances per threshold; only the counts and the boundary
         pixels' squared distances come back.  Then per threshold casewise.surface_slice_values per slice, surface_exam_values per
@@ -805,7 +861,7 @@ class TFKerasModel:
             for i in range(0, len(x), dm.max_batch):
                 xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
                 pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
-                _forward_on_device(dm, xb, tta_mask)
+                _forward_on_device(dm, xb, tta_mask, temperature=temperature)
                 for ti, thr in enumerate(thresholds):
                     counts, samples, _ = dm.surface_distances(yb, batch=len(xb), threshold=thr, **kw)
                     for b, (p, k) in enumerate(pk):
@@ -824,7 +880,7 @@ class TFKerasModel:
             results.append(lead + casewise.surface_summary(slice_values, exam_values))
         return results, cases, slices
 
-    def _uncertainty_pass(self, ds, step, thresholds, tta_mask):
+    def _uncertainty_pass(self, ds, step, thresholds, tta_mask, temperature=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --tta MODE --uncertainty`: per max_batch split one
         DeviceModel.forward_tta_spread whose mean and spread stay on the device and one DeviceModel.spread_by_outcome for all
         thresholds (in runs of 64); only the counts and sums per outcome come back.  Returns the new lines of
@@ -839,7 +895,7 @@ class TFKerasModel:
             for i in range(0, len(x), dm.max_batch):
                 xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
                 pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
-                _forward_on_device(dm, xb, tta_mask, spread=True)
+                _forward_on_device(dm, xb, tta_mask, spread=True, temperature=temperature)
                 for t0 in range(0, len(thresholds), 64):
                     out = dm.spread_by_outcome(yb.reshape(len(xb), *yb.shape[1:3]), thresholds[t0:t0 + 64], batch=len(xb))
                     for ti, per_slice in enumerate(out, t0):
@@ -850,6 +906,31 @@ class TFKerasModel:
             slices += [lead + casewise.outcome_slice_values(*rec) for rec in mine]
             results.append(lead + casewise.outcome_summary([rec[2] for rec in mine]))
         return results, slices
+
+    def _calibration_pass(self, ds, step, n_bins, temperatures, tta_mask=None, temperature=None):
+        """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --calibration`: per max_batch split one forward whose
+        probabilities stay on the device and one DeviceModel.calibration for all temperatures; only the integer tables and the NLL
+        sums come back.  Returns the new lines of (calibration_results.csv, calibration_bins.csv, calibration_slices.csv), each led
+        by step; the pooled values come from the tables and NLL rows of all slices summed (casewise.calibration_summary)."""
+        at_1 = [float(t) for t in temperatures].index(1.0)
+        bins, totals, nll, slices = [], [], [], []
+        for x, y, paths, ids in ds:
+            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
+            if not len(x):
+                continue
+            self._ensure_capacity(len(x))
+            dm = self.device_model
+            for i in range(0, len(x), dm.max_batch):
+                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
+                _forward_on_device(dm, xb, tta_mask, temperature=temperature)
+                b, t, n = dm.calibration(yb.reshape(len(xb), *yb.shape[1:3]), n_bins, temperatures, batch=len(xb))
+                bins.append(b), totals.append(t), nll.append(n)
+                slices += [[int(step)] + casewise.calibration_slice_values(p, k, b[j], t[j], n[j, at_1])
+                           for j, (p, k) in enumerate(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))]
+        if not bins:
+            return [], [], []
+        result, lines = casewise.calibration_summary(np.concatenate(bins), np.concatenate(totals), temperatures, np.concatenate(nll))
+        return [[int(step)] + result], [[int(step)] + l for l in lines], slices
 
     def predict(self, dataset):
         """Probabilities [N, H, W, 1] for every element of `dataset` (elements are x or (x, ...))."""
@@ -863,7 +944,8 @@ class TFKerasModel:
         return np.concatenate(outs) if outs else np.zeros((0,))
 
     def annotate(self, dataset, save_path, output, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
-                 max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False):
+                 max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
+                 temperature=None):
         """`annotator predict`: the lesions of slices that have no label.  Loads checkpoint `step` of save_path (None: the latest);
         per batch (x, paths, sliceIDs) of `dataset` (make_dataset(..., include_meta=True, labels=False)) one forward whose
         probabilities stay on the device, then DeviceModel.lesion_table: threshold, filter_size x filter_size opening, components
@@ -883,8 +965,11 @@ class TFKerasModel:
         DeviceModel.lesion_table_spread (with link_slices lesion_table_linked runs as it does without the flag and the spread records
         come from a second call); lesion_uncertainty.csv (one line per line of lesions.csv, in its order) and slice_uncertainty.csv
         are written beside the other files, which are what they are without the flag, and with export_images
-        <exam>/<slice>/uncertainty.png (only then does a spread plane leave the device).  Needs a tta mode other than 'none'."""
+        <exam>/<slice>/uncertainty.png (only then does a spread plane leave the device).  Needs a tta mode other than 'none'.
+        temperature (`predict --temperature T`): the probabilities are scaled by DeviceModel.scale_temperature, once behind every
+        forward, before the table reads them; the spread stays that of the unscaled views.  None or 1: nothing new runs."""
         check_uncertainty(uncertainty, tta)
+        temperature = check_temperature(temperature)
         if self.ctx.world > 1:
             raise RuntimeError('annotate runs in a single process (WORLD_SIZE is %d): start it without the launcher' % self.ctx.world)
         tta_mask = None if tta == tta_modes.NONE else tta_modes.mask_of(tta, *_element_shape(dataset)[1:3])
@@ -899,6 +984,7 @@ class TFKerasModel:
         self.load(ckpts[step])
         lesion_rows, slice_rows = [], []
         lesion_spread_rows, slice_spread_rows = [], []
+        scale = {} if temperature is None else dict(temperature=temperature)      # the forward gets the keyword only with a temperature
         dm = None
         linked, last = [], None          # link_slices: (exam, slice, rows, total, links into it) per slice; the slice before: (exam, slice)
         writer = casewise.Writer() if export_images else None
@@ -915,7 +1001,7 @@ class TFKerasModel:
                 dm = self.device_model
                 for i in range(0, len(x), dm.max_batch):
                     xb = x[i:i + dm.max_batch]
-                    _forward_on_device(dm, xb, tta_mask, spread=bool(uncertainty))
+                    _forward_on_device(dm, xb, tta_mask, spread=bool(uncertainty), **scale)
                     pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
                     kw = dict(batch=len(xb), threshold=threshold, resize_factor=resize_factor, filter_size=filter_size,
                               min_area=min_area, max_lesions=max_lesions, mask=bool(export_images))

@@ -11,8 +11,12 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
              skip_visualization=False, export_casewise_metrics=False, exam_lesions=False, exam_threshold=(0.5,), exam_iou=0.30,
              exam_min_area=0, exam_filter_size=5, exam_resize_factor=1.0, exam_max_lesions=256, exam_link_min_overlap=1,
              surface_distances=False, surface_threshold=(0.5,), surface_percentile=95.0, surface_min_area=0, surface_filter_size=5,
-             surface_resize_factor=1.0, surface_max_samples=65536, tta='none', uncertainty=False, uncertainty_threshold=(0.5,)):
+             surface_resize_factor=1.0, surface_max_samples=65536, tta='none', uncertainty=False, uncertainty_threshold=(0.5,),
+             calibration=False, calibration_bins=15, calibration_temperatures=None, temperature=None):
     engine.check_uncertainty(uncertainty, tta)       # before anything is read
+    scaled = engine.check_temperature(temperature)   # likewise; None without the flag and with --temperature 1
+    if calibration:
+        engine.check_calibration(calibration_bins, calibration_temperatures)
     saved_config = load.load_config(os.path.join(save_path, 'options.yaml'))['config']
     if config:
         config = load._apply_config(saved_config, load.load_config(config))
@@ -22,10 +26,10 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
     # the Visualizer's data set (runs/evaluate.py:72-73 of the reference): the same slices with their exam path and sliceID
     viz_ds = None if skip_visualization else make_dataset(data_path, config.get('data_options', {}).get('eval', {}), training=False,
                                                           include_meta=True)
-    # --exam_lesions, --surface_distances and --uncertainty read a data set of their own (the slices with their labels, exam path and sliceID;
+    # --exam_lesions, --surface_distances, --uncertainty and --calibration read a data set of their own (the slices with their labels, exam path and sliceID;
     # --skip_visualization does not touch it): one is built and shared when several are given
     meta_ds = make_dataset(data_path, config.get('data_options', {}).get('eval', {}), training=False, include_meta=True) \
-        if exam_lesions or surface_distances or uncertainty else None
+        if exam_lesions or surface_distances or uncertainty or calibration else None
     exam_ds = meta_ds if exam_lesions else None
     # the keywords of --surface_distances go to model.eval only with the flag
     surface = dict(surface_ds=meta_ds, surface_distances=surface_distances, surface_threshold=surface_threshold,
@@ -34,6 +38,11 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
     more = dict(tta=tta) if tta != 'none' else {}      # the keyword of --tta goes to model.eval only with a mode
     if uncertainty:                      # likewise the keywords of --uncertainty only with the flag
         more.update(uncertainty_ds=meta_ds, uncertainty=True, uncertainty_thresholds=tuple(uncertainty_threshold))
+    if calibration:                      # and those of --calibration
+        more.update(calibration_ds=meta_ds, calibration=True, calibration_bins=int(calibration_bins),
+                    calibration_temperatures=None if calibration_temperatures is None else tuple(calibration_temperatures))
+    if scaled is not None:               # the keyword of --temperature only with a temperature other than 1
+        more['temperature'] = scaled
     model = engine.TFKerasModel(config)
     return model.eval(ds, viz_ds=viz_ds, tag=tag, save_path=os.path.join(save_path), avoid_overwrite=avoid_overwrite,
                       export_path=export_path, export_images=export_images, export_csv=export_csv,

@@ -1,7 +1,8 @@
 """`annotator predict` -- the reference left annotator/runs/predict.py empty: annotate slices that have no label with a trained
 checkpoint (lesions.csv, slices.csv and, with --export_images, one mask.png per slice; with --link_slices also exam_lesions.csv and
 exam_lesion_parts.csv: the lesions joined through the slices of an exam; with --tta MODE --uncertainty also lesion_uncertainty.csv,
-slice_uncertainty.csv and uncertainty.png: how much the views disagree; engine.TFKerasModel.annotate)."""
+slice_uncertainty.csv and uncertainty.png: how much the views disagree; with --temperature T every table reads the probabilities
+scaled by T; engine.TFKerasModel.annotate)."""
 
 import os
 
@@ -10,8 +11,10 @@ from .train import make_dataset
 
 
 def predict(save_path, data_path, output, config=None, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
-            max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False):
+            max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
+            temperature=None):
     engine.check_uncertainty(uncertainty, tta)       # before anything is read
+    scaled = engine.check_temperature(temperature)   # likewise; None without the flag and with --temperature 1
     if link_min_overlap < 1:
         raise ValueError('link_min_overlap must be at least 1, got %d' % link_min_overlap)
     saved_config = load.load_config(os.path.join(save_path, 'options.yaml'))['config']
@@ -22,6 +25,8 @@ def predict(save_path, data_path, output, config=None, step=None, threshold=0.5,
     more = dict(tta=tta) if tta != 'none' else {}
     if uncertainty:                      # likewise only with the flag
         more['uncertainty'] = True
+    if scaled is not None:               # and the keyword of --temperature only with a temperature other than 1
+        more['temperature'] = scaled
     model = engine.TFKerasModel(config)
     return model.annotate(ds, save_path=save_path, output=output, step=step, threshold=threshold, min_area=min_area,
                           filter_size=filter_size, resize_factor=resize_factor, max_lesions=max_lesions,

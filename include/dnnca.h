@@ -407,6 +407,39 @@ typedef struct dnnca_spread_outcome {
 int dnnca_spread_by_outcome(void* model, const float* prob_hw, const float* spread_hw, const float* y_hw, int batch, int h, int w,
                             const float* thresholds, int n_thresholds, dnnca_spread_outcome* out /* [n_thresholds][batch] */);
 
+/* ---- can the probability be believed? (`annotator evaluate --calibration`, `--temperature`) ---------------------------------------
+ * dnnca_calibration: the reliability table of a probability plane against its labels and its negative log-likelihood at a set of
+ * temperatures.  A pixel is of class 1 when y > 0.5, else 0 (the rule above); its probability is clamped, p' = min(max(p, 0), 1) (a NaN
+ * counts as 0), enters every sum as q = rint(p' * 2^24) (float32 product) and falls into bin k = min(n_bins - 1, (int) floor(p' *
+ * (float) n_bins)) (float32 product).  bins[b * n_bins + k]: the pixels n[c] and the sums sum_q24[c] of q of slice b, bin k and class
+ * c.  totals[b]: the same over all bins, and the sum of q^2 per class as two exact words, sq_lo = sum (q^2 & 0xffffffff) and sq_hi =
+ * sum (q^2 >> 32): sum q^2 = sq_hi * 2^32 + sq_lo (the Brier score).  Integers: bit-identical from run to run.
+ * nll[b * n_temperatures + t]: the sum over the pixels of slice b of softplus(-a) (class 1) or softplus(a) (class 0) in double, with
+ * a = z * (1 / (double) temperatures[t]), z = log(pc) - log1p(-pc), pc = p' clamped to [2^-24, 1 - 2^-24] (an exact 0 or 1 counts as
+ * z = -+16.64) and softplus(a) = max(a, 0) + log1p(exp(-|a|)).  Block partials summed in a fixed order: bit-identical from run to
+ * run.  With n_temperatures == 0 nothing of it runs and nll is not touched.
+ * prob_hw == NULL: the model's own probabilities (the last forward's, or the mean dnnca_forward_tta left); h and w are then 0 or the
+ * output size, and DNNCA_ESTATE is returned when the last forward had fewer than `batch` slices.  Otherwise prob_hw is a host plane
+ * [batch, h, w] of any size.  y_hw: host [batch, h, w], required.
+ * DNNCA_EINVAL, with nothing launched and no output touched: batch outside [1, max_batch], n_bins outside 1..256, n_temperatures
+ * outside 0..64, n_temperatures > 0 with a NULL temperatures or nll, a temperature that is NaN or outside [0.05, 20], a NULL y_hw /
+ * bins / totals, a plane that is empty or has 2^31 pixels or more, more than 65535 slices.  Variables and state stay untouched.
+ * Synchronises. */
+typedef struct dnnca_calib_bin { uint64_t n[2], sum_q24[2]; } dnnca_calib_bin;                          /* 32 bytes */
+typedef struct dnnca_calib_total { uint64_t n[2], sum_q24[2], sq_lo[2], sq_hi[2]; } dnnca_calib_total;  /* 64 bytes */
+int dnnca_calibration(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w, int n_bins,
+                      const float* temperatures, int n_temperatures, dnnca_calib_bin* bins /* [batch][n_bins] */,
+                      dnnca_calib_total* totals /* [batch] */, double* nll /* [batch][n_temperatures] */);
+/* dnnca_prob_temperature: p -> (float) (1 / (1 + exp(-z / T))) with z as above, in double, rounded once to float32.  0.5 stays 0.5
+ * and the rounded map is non-decreasing: a mask at threshold 0.5 changes at most where a probability lay within a rounding of 0.5.  prob_hw == NULL: the model's probability buffer is scaled IN
+ * PLACE for `batch` slices (DNNCA_ESTATE when the last forward had fewer) -- every later consumer of it reads the scaled values, the
+ * spread plane of dnnca_forward_tta_spread stays what it is and stays valid, and a second call scales the scaled values again: call
+ * it once per forward; out_hw may be NULL, or receives a copy.  With a host plane prob_hw [batch, h, w] out_hw is required and the
+ * model's buffer stays untouched.  DNNCA_EINVAL, with nothing launched and nothing touched: batch outside [1, max_batch], a
+ * temperature that is NaN or outside [0.05, 20], a host plane without out_hw, a plane that is empty or has 2^31 pixels or more.
+ * Variables and state stay untouched.  Synchronises. */
+int dnnca_prob_temperature(void* model, const float* prob_hw, int batch, int h, int w, float temperature, float* out_hw);
+
 /* ---- the same table plus the links between neighbouring slices of an exam (`annotator predict --link_slices`) ------------------
  * Every argument up to out_hw means what it means for dnnca_lesion_table (the size query with rows == NULL included), and rows,
  * totals and mask are bit-identical to that call's.  continues [batch]: continues[b] != 0 says that slice b is the next slice of

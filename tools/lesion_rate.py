@@ -15,6 +15,8 @@ and prediction plane) plus pairs, match and count.
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --link --match    # the matched legs on it
     python tools/lesion_rate.py --tta flips         # test-time augmentation alone: forward_tta against the plain forward
     python tools/lesion_rate.py --tta flips --uncertainty        # also: the spread of the views against the mean alone
+    python tools/lesion_rate.py --calibration       # calibration and temperature scaling alone
+    DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --tta flips      # forward / forward_tta on it
 
 --link adds the cost of linking neighbouring slices: lesion_table_linked against lesion_table (wall time per call, device time of
 the three link launches), its worst case for the pair table (a checkerboard on itself: every other pixel a lesion of its own in
@@ -35,6 +37,12 @@ kernels_tta.hip (tta_view_in, tta_accumulate) in it.
 --tta MODE --uncertainty adds the spread of the views: forward_tta_spread against forward_tta (wall and device time per call, the
 two alternated), tta_moments against tta_accumulate per launch, lesion_table_spread against lesion_table on the mean and spread that
 forward_tta_spread left on the device, and spread_by_outcome alone (one and three thresholds).
+
+--calibration measures DeviceModel.calibration and DeviceModel.scale_temperature and nothing else: device time per launch of
+calib_bins on a uniform random plane and on a real-like one (99 % of the pixels below 0.01 and of class 0: what the grouping of a
+wave's lanes by key is for), of calib_nll / calib_nll_sum at the 41 temperatures of casewise.CALIBRATION_GRID and of prob_temperature;
+wall time per call; and a forward_tta_spread + calibration pass against a forward_tta_spread + spread_by_outcome pass (the pass of
+`evaluate --uncertainty`: the same forward, one table call), alternated in one process.
 
 The probabilities are drawn: the synthetic labels' discs at 0.55 .. 0.95 on a background of 0 .. 0.45 (a few lesions per slice,
 as a trained model gives), put into the model's probability buffer by pixel_confusion_of."""
@@ -59,8 +67,14 @@ ap.add_argument('--match', action='store_true', help='also measure lesion_table_
 ap.add_argument('--surface', action='store_true', help='also measure surface_distances against lesion_table_matched (needs --match)')
 ap.add_argument('--tta', default=None, metavar='MODE', help='measure forward_tta(MODE) against the plain forward, and nothing else')
 ap.add_argument('--uncertainty', action='store_true', help='with --tta: also measure forward_tta_spread, lesion_table_spread, spread_by_outcome')
+ap.add_argument('--calibration', action='store_true', help='measure calibration and scale_temperature, and nothing else')
 ap.add_argument('--out', default=None, help='append the report to this file as well')
 a = ap.parse_args()
+if a.calibration:                                                # its yardstick is the pass of --tta flips --uncertainty
+    a.tta, a.uncertainty = a.tta or 'flips', True
+else:
+    for name in ('dnnca_calibration', 'dnnca_prob_temperature'):
+        _lib.SIGNATURES.pop(name, None)                          # a library built from the parent does not export them
 if a.yardstick:
     _lib.SIGNATURES.pop('dnnca_lesion_table', None)              # a library built from the parent does not export it
 if not a.link:
@@ -138,8 +152,78 @@ ds = ArrayDataset(np.concatenate([x] * NB), None, B, meta_path='/synthetic/p0/e0
     ArrayDataset(x, y, B)
 e._build(ds)
 dm = e.device_model
-say('%s: %d x %d x %d, library %s' % ('yardstick' if a.yardstick else 'test-time augmentation' if a.tta else 'lesion table', B, S, S,
-                                      os.path.basename(_lib.LIB_PATH)))
+say('%s: %d x %d x %d, library %s' % ('yardstick' if a.yardstick else 'calibration' if a.calibration else
+                                      'test-time augmentation' if a.tta else 'lesion table', B, S, S, os.path.basename(_lib.LIB_PATH)))
+if a.calibration:
+    from dnncancerannotator_amd import casewise, tta as tta_modes
+    views = tta_modes.mask_of(a.tta, S, S)
+    grid = casewise.calibration_grid()
+    rng = np.random.default_rng(5)
+    uniform = rng.random((B, S, S)).astype(np.float32)
+    hot = rng.random((B, S, S)) < 0.01
+    real = np.where(hot, rng.random((B, S, S)), 0.01 * rng.random((B, S, S))).astype(np.float32)
+    y_real = (hot & (rng.random((B, S, S)) < 0.7)).astype(np.float32)
+    for what, p, lab in (('uniform plane, labels 30 % positive', uniform, (rng.random((B, S, S)) < 0.3).astype(np.float32)),
+                         ('real-like plane (99 % below 0.01, class 0)', real, y_real)):
+        dm.forward(x, return_prob=False)                          # a forward of B slices, then the plane into the model's buffer
+        dm.pixel_confusion_of(p, lab, [0.5])
+        bins, totals, nll = dm.calibration(lab, 15, grid, batch=B)
+        table = casewise.calibration_table(bins)
+        say('  %s: %d of %d pixels in bin 0, ECE %.4f, fitted temperature %.3f' % (
+            what, table[0][3], B * S * S, casewise.calibration_errors(table)[0], casewise.fit_temperature(grid, nll.sum(axis=0))[0]))
+        for name, temps in (('15 bins, no temperatures', ()), ('15 bins, 41 temperatures', grid)):
+            med, lo, hi = wall(lambda: dm.calibration(lab, 15, temps, batch=B))
+            say('  calibration, %s: %.3f ms per call, labels uploaded (median of %d; %.3f .. %.3f)' % (name, med, R, lo, hi))
+            per_launch(dm, lambda: dm.calibration(lab, 15, temps, batch=B), ('calib_',))
+        med, lo, hi = wall(lambda: dm.calibration(lab, 256, (), batch=B))
+        say('  calibration, 256 bins, no temperatures: %.3f ms per call (median of %d; %.3f .. %.3f)' % (med, R, lo, hi))
+        per_launch(dm, lambda: dm.calibration(lab, 256, (), batch=B), ('calib_',))
+    med, lo, hi = wall(lambda: dm.scale_temperature(1.0, B))          # T = 1 keeps the plane where it is, rep after rep
+    say('  scale_temperature in place: %.3f ms per call (median of %d; %.3f .. %.3f)' % (med, R, lo, hi))
+    per_launch(dm, lambda: dm.scale_temperature(1.0, B), ('prob_temperature',))
+    ys = np.concatenate([y] * NB)
+
+    def tta_pass(calibrate):
+        """the forward of `evaluate --tta flips --uncertainty` and one table call per batch"""
+        t0 = time.perf_counter()
+        for i, (xb, _, _) in enumerate(ds):
+            dm.forward_tta_spread(xb, views, return_prob=False, return_spread=False)
+            yb = ys[i * B:i * B + len(xb)]
+            if calibrate:
+                dm.calibration(yb, 15, grid, batch=len(xb))
+            else:
+                dm.spread_by_outcome(yb, [0.5], batch=len(xb))
+        return time.perf_counter() - t0
+    tta_pass(False), tta_pass(True)                               # warm-up: the spread planes, either workspace
+    took = {False: [], True: []}
+    for i in range(8):
+        took[bool(i % 2)].append(tta_pass(bool(i % 2)))
+        say('  %-44s %9.1f slices/s  (%.2f ms per batch)' % ('forward_tta_spread + ' + ('calibration' if i % 2 else 'spread_by_outcome') + ' pass',
+                                                             B * NB / took[bool(i % 2)][-1], took[bool(i % 2)][-1] / NB * 1e3))
+    cal, out = sorted(took[True])[2], sorted(took[False])[2]
+    say('  calibration / spread_by_outcome pass (medians of 4, alternated): %.3f' % (cal / out))
+
+    def plain_pass(calibrate, scale):
+        t0 = time.perf_counter()
+        for i, (xb, _, _) in enumerate(ds):
+            dm.forward(xb, return_prob=False)
+            if scale:
+                dm.scale_temperature(1.7, len(xb))
+            if calibrate:
+                dm.calibration(ys[i * B:i * B + len(xb)], 15, grid, batch=len(xb))
+        dm.sync()
+        return time.perf_counter() - t0
+    plain_pass(True, True)
+    for i in range(2):
+        for name, args in (('forward', (False, False)), ('forward + scale_temperature', (False, True)),
+                           ('forward + calibration', (True, False)), ('forward + scale_temperature + calibration', (True, True))):
+            dt = plain_pass(*args)
+            say('  %-44s %9.1f slices/s  (%.2f ms per batch)' % (name + ' pass', B * NB / dt, dt / NB * 1e3))
+    dm.close()
+    if a.out:
+        with open(a.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    sys.exit(0)
 if a.tta:
     from dnncancerannotator_amd import tta as tta_modes
     views = tta_modes.mask_of(a.tta, S, S)
