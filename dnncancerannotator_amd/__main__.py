@@ -92,6 +92,15 @@ def build_parser(prog='python3 -m annotator'):
     e.add_argument('--temperature', type=float, default=argparse.SUPPRESS, metavar='T',
                    help='temperature scaling: every probability read is sigmoid(logit(p) / T), T in [0.05, 20]; --calibration then '
                         'measures the scaled probabilities (default: 1, no scaling)')
+    e.add_argument('--visualize_attribution', action='store_true', default=argparse.SUPPRESS,
+                   help='with --export_csv / --export_images: integrated-gradients attribution of every slice -- which modality, and '
+                        'where in it, the prediction rests on: also write step_<step>_attribution.csv / .png per slice and '
+                        'attribution_results.csv')
+    e.add_argument('--attribution_steps', type=int, default=argparse.SUPPRESS, metavar='M',
+                   help='path points of --visualize_attribution, 1..256; costs M + 2 forwards and M backward passes per batch (default: 32)')
+    e.add_argument('--attribution_baseline', choices=('black', 'mean'), default=argparse.SUPPRESS,
+                   help='where the path of --visualize_attribution starts: a zero image or the mean of each slice and modality '
+                        '(default: black)')
     p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
     p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
     p.add_argument('--data_path', nargs='+', required=True)

@@ -229,6 +229,8 @@ SIGNATURES = {
                                           C.POINTER(C.c_int32), C.POINTER(SurfaceSample), C.c_int64, C.POINTER(C.c_int64), _VP, C.c_int64,
                                           C.POINTER(C.c_int32)]),
     'dnnca_input_sensitivity': (C.c_int, [_VP, _FP, C.c_int, C.POINTER(C.c_double)]),
+    'dnnca_integrated_gradients': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double), _FP]),
     'dnnca_comm_unique_id': (C.c_int, [_VP]),
     'dnnca_comm_init': (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_size_t]),
     'dnnca_comm_world': (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

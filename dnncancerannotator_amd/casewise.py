@@ -10,6 +10,8 @@ Files under <export_path>/<tag>/ (callbacks.py _emit):
     csv/<last 3 components of the exam path>/<sliceID %02d>/step_<step %08d>_metrics.csv      (--export_csv)
     casewise_results.csv: every slice of every evaluated checkpoint, in dataset order          (--export_csv)
     images/.../step_<step %08d>_sensitivity.png and csv/.../step_<step %08d>_sensitivity.csv  (--visualize_sensitivity, per slice)
+    images/.../step_<step %08d>_attribution.png and csv/.../step_<step %08d>_attribution.csv  (--visualize_attribution, per slice)
+    attribution_results.csv: one line per evaluated checkpoint                                (--visualize_attribution)
 The CSV bytes are those of pandas' to_csv (`pd.DataFrame(series).T.to_csv()`, `pd.DataFrame(rows).to_csv()`): csv-module
 quoting, '\\n' line ends, an empty header cell for the index."""
 
@@ -165,6 +167,91 @@ def sensitivity_chart(values):
         if bh:
             img[bottom - bh:bottom, x0:x1] = CHART_BAR_RGB
     return img
+
+
+# ---- integrated-gradients attribution (--visualize_attribution): DeviceModel.integrated_gradients gives sums, endpoints and map --
+ATTRIBUTION_STEPS = 32                   # --attribution_steps
+ATTRIBUTION_STEP_RANGE = (1, 256)        # what the library accepts
+ATTRIBUTION_BASELINES = ('black', 'mean')
+ATTRIBUTION_RESULT_COLUMNS = ['steps', 'baseline', 'slices']     # then share_<modality>..., mean_relative_gap, max_relative_gap
+ATTRIBUTION_GAP = 2                      # white pixels between two panels of attribution_image
+ATTRIBUTION_FOR_RGB = (255, 0, 0)        # the colour of +scale (evidence for a lesion); 0 is white
+ATTRIBUTION_AGAINST_RGB = (0, 0, 255)    # the colour of -scale (evidence against)
+
+
+def attribution_path(root, tag, step, kind):
+    """kind 'csv' -> csv/<exam>/<slice>/step_<step>_attribution.csv, 'images' -> images/<exam>/<slice>/step_<step>_attribution.png"""
+    ext = {'csv': 'csv', 'images': 'png'}[kind]
+    return os.path.join(export_dir(root, kind, tag), 'step_%08d_attribution.%s' % (int(step), ext))
+
+
+def attribution_shares(absolute):
+    """sums of |attr| [B, C] -> rows divided by their sum: the share of each modality; an all-zero row is NaN, as in
+    normalise_sensitivity"""
+    return normalise_sensitivity(absolute)
+
+
+def attribution_gap(signed, endpoints):
+    """(gap, relative gap) per slice, float64 [B] each: gap = sum over the modalities of signed[b] - (F(x) - F(baseline)), the
+    completeness error of the quadrature; relative to |F(x) - F(baseline)| (NaN where that is 0)"""
+    s, e = np.asarray(signed, np.float64), np.asarray(endpoints, np.float64)
+    delta = e[..., 0] - e[..., 1]
+    gap = s.sum(axis=-1) - delta
+    with np.errstate(invalid='ignore', divide='ignore'):
+        rel = np.where(delta != 0, gap / np.abs(delta), np.nan)
+    return gap, rel
+
+
+def _float_cell(v):
+    v = float(v)
+    return '' if v != v else repr(v)
+
+
+def attribution_csv(names, shares, signed, absolute, endpoints):
+    """the per-slice file: 'modality,share,signed,absolute' and one line per modality, then the lines f_x, f_baseline, gap and
+    relative_gap with their value in the second cell (repr of the float64; NaN: empty)"""
+    gap, rel = attribution_gap(signed, endpoints)
+    rows = [['modality', 'share', 'signed', 'absolute']]
+    for n, sh, s, a in zip(names, shares, signed, absolute):
+        rows.append([n, _float_cell(sh), _float_cell(s), _float_cell(a)])
+    rows += [['f_x', _float_cell(endpoints[0])], ['f_baseline', _float_cell(endpoints[1])], ['gap', _float_cell(gap)],
+             ['relative_gap', _float_cell(rel)]]
+    return _csv(rows)
+
+
+def attribution_image(amap, names=None):
+    """attr of one slice [H, W, C] -> uint8 RGB [H, C * W + (C - 1) * ATTRIBUTION_GAP, 3]: one panel per modality (the order of
+    `names`; they only fix the number of panels), side by side, white columns between them.  Diverging colours on one common scale
+    s = the slice's largest |attr|: 0 is white, +s ATTRIBUTION_FOR_RGB (red: evidence for), -s ATTRIBUTION_AGAINST_RGB (blue: evidence
+    against), linear in between, rounded to nearest.  An all-zero or non-finite map is all white.  Plain numpy."""
+    a = np.asarray(amap, np.float64)
+    if a.ndim != 3 or (names is not None and len(names) != a.shape[2]):
+        raise ValueError('attribution_image: a map [H, W, C] and C names, got %s and %r' % (a.shape, names))
+    h, w, c = a.shape
+    img = np.full((h, c * w + (c - 1) * ATTRIBUTION_GAP, 3), 255, np.uint8)
+    scale = float(np.abs(a).max()) if a.size else 0.0
+    if not (scale > 0 and math.isfinite(scale)):
+        return img
+    t = a / scale                                                        # in [-1, 1]
+    white = np.array([255.0, 255.0, 255.0])
+    for j in range(c):
+        u = t[:, :, j, None]
+        tip = np.where(u >= 0, np.array(ATTRIBUTION_FOR_RGB, np.float64), np.array(ATTRIBUTION_AGAINST_RGB, np.float64))
+        panel = white + np.abs(u) * (tip - white)
+        img[:, j * (w + ATTRIBUTION_GAP):j * (w + ATTRIBUTION_GAP) + w] = np.rint(panel).astype(np.uint8)
+    return img
+
+
+def attribution_summary(steps, baseline, shares, relative_gaps):
+    """the attribution_results.csv values of one checkpoint: steps, baseline, slices, the mean share per modality over the slices
+    whose shares are numbers, the mean and the largest |relative gap| over the slices where it is a number ('' where none is)"""
+    sh, rel = np.asarray(shares, np.float64), np.abs(np.asarray(relative_gaps, np.float64)).ravel()
+    sh = sh.reshape(len(sh), -1) if len(sh) else np.zeros((0, sh.shape[1] if sh.ndim == 2 else 0))
+    ok = ~np.isnan(sh).any(axis=1)
+    mean_share = sh[ok].mean(axis=0) if ok.any() else np.full(sh.shape[1], np.nan)
+    rel = rel[~np.isnan(rel)]
+    return [int(steps), str(baseline), len(sh)] + [_float_cell(v) for v in mean_share] + \
+        [_float_cell(rel.mean() if len(rel) else np.nan), _float_cell(rel.max() if len(rel) else np.nan)]
 
 
 # ---- `annotator predict`: the lesion table of slices without a label (DeviceModel.lesion_table gives the integer sums) ----------

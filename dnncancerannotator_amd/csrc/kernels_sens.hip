@@ -3,7 +3,7 @@
 //   k_bn_infer_bwd  BatchNorm backward in inference mode: a per-channel scale by gamma / sqrt(moving_variance + eps)
 //   k_sens_first    data gradient of the convs that read the network input, never stored: |dx| summed over the image per (b, channel)
 // Everything else of the pass is a data-gradient launch the train step already has (kernels_generic.hip, kernels_igemm.hip).
-#include "sens.h"
+#include "sens_first_dev.h"
 
 namespace dnnca {
 
@@ -52,10 +52,8 @@ void g_bn_infer_bwd(hipStream_t s, int B, View dy, View dx, int acc, const float
 
 // ------------------------------------------------------------------------------------------------ first layer
 // One block = `tpb` consecutive 16 x 16 tiles (row-major tile order) of image b for the input channels [ci0, ci0 + nci) of first conv
-// blockIdx.z.  Per tile and chunk of 16 output channels the block stages dz = dy act'(y) with its halo (channel planes, odd plane
-// stride: conflict-free reads) and the chunk's weights in LDS; thread (ly, lx) forms
-//     dx[iy, ix, ci] = sum over ky, kx, co of dz[iy - ky + pad, ix - kx + pad, co] w[ky, kx, ci, co]
-// in registers, adds |dx| to its running sums and drops dx.  End of the block: the lane sums go through a wave reduction (__shfl_down)
+// blockIdx.z.  Per tile thread (ly, lx) gets its pixel's dx in registers (sens_first_tile, sens_first_dev.h: shared with
+// k_attr_first), adds |dx| to its running sums and drops dx.  End of the block: the lane sums go through a wave reduction (__shfl_down)
 // and a fixed-order sum of the waves to ONE double per channel, stored in the block's slot of the partial row of (b, channel).  The
 // block that draws the last ticket of its (b, z) pair adds the row up in a fixed order, so two runs give the same bits whatever order
 // the blocks finish in.  The partials travel as device-scope atomic stores / loads with the storing thread's vmcnt(0) wait in front
@@ -80,9 +78,6 @@ __global__ __launch_bounds__(TB) void k_sens_first(const SensFirst* __restrict__
     __shared__ unsigned is_last;
     const SensFirst d = descs[blockIdx.z];
     const int b = blockIdx.y, tid = threadIdx.x, lx = tid % kSensTile, ly = tid / kSensTile;
-    const int pad = (K - 1) / 2, TH = kSensTile + K - 1, plane = (TH * TH) | 1;
-    float* s_dz = lds;                                 // [kSensCo][plane]
-    float* s_w = lds + kSensCo * plane;                // [K * K][kSensCi][kSensCo]
     const unsigned nblk_pair = gridDim.x;
     float tsum[kSensCi];
 #pragma unroll
@@ -91,39 +86,7 @@ __global__ __launch_bounds__(TB) void k_sens_first(const SensFirst* __restrict__
     for (int t = (int)blockIdx.x * tpb; t < t_end; ++t) {
         const int ty0 = (t / tiles_x) * kSensTile, tx0 = (t % tiles_x) * kSensTile;
         float acc[kSensCi];
-#pragma unroll
-        for (int j = 0; j < kSensCi; ++j) acc[j] = 0.f;
-        for (int co0 = 0; co0 < d.cout; co0 += kSensCo) {
-            const int nco = min(kSensCo, d.cout - co0);
-            __syncthreads();                           // the previous chunk's readers are done
-            for (int i = tid; i < TH * TH * kSensCo; i += TB) {
-                const int c = i % kSensCo, pix = i / kSensCo;
-                const int gy = ty0 + pix / TH - pad, gx = tx0 + pix % TH - pad;
-                float v = 0.f;
-                if (c < nco && gy >= 0 && gy < H && gx >= 0 && gx < W) {
-                    const size_t idx = (((size_t)b * H + gy) * W + gx) * d.cout + co0 + c;
-                    v = d.dy[idx];
-                    if (d.alpha >= 0.f) v *= d.y[idx] > 0.f ? 1.f : d.alpha;          // as g_act_bwd
-                }
-                s_dz[c * plane + pix] = v;
-            }
-            for (int i = tid; i < K * K * kSensCi * kSensCo; i += TB) {
-                const int c = i % kSensCo, j = (i / kSensCo) % kSensCi, kk = i / (kSensCo * kSensCi);
-                s_w[i] = (j < d.nci && c < nco) ? d.w[((size_t)kk * d.cin + d.ci0 + j) * d.cout + co0 + c] : 0.f;
-            }
-            __syncthreads();
-            for (int ky = 0; ky < K; ++ky)
-                for (int kx = 0; kx < K; ++kx) {
-                    const float* zp = s_dz + (ly + 2 * pad - ky) * TH + (lx + 2 * pad - kx);
-                    const float* wp = s_w + (ky * K + kx) * kSensCi * kSensCo;
-#pragma unroll
-                    for (int c = 0; c < kSensCo; ++c) {
-                        const float v = zp[c * plane];
-#pragma unroll
-                        for (int j = 0; j < kSensCi; ++j) acc[j] = fmaf(v, wp[j * kSensCo + c], acc[j]);
-                    }
-                }
-        }
+        sens_first_tile<TB>(d, b, H, W, K, ty0, tx0, lds, acc);
         if (ty0 + ly < H && tx0 + lx < W) {
 #pragma unroll
             for (int j = 0; j < kSensCi; ++j) tsum[j] += fabsf(acc[j]);

@@ -298,6 +298,19 @@ struct Model {
     double *sens_part = nullptr, *sens_sums = nullptr;
     unsigned* sens_ticket = nullptr;
     int input_sensitivity(const float* x_dev, int B);      // enqueues the pass; the sums are in sens_sums behind it
+    int sens_refusal(const char* what);                    // the models neither input-gradient pass takes
+    int sens_backward(const float* x_dev, int B);          // the part both passes share: forward + data gradients down to the first convs
+    void sens_first_cost(int B, double* bytes, double* flops) const;
+
+    // integrated gradients (dnnca_integrated_gradients): scratch allocated for max_batch by the first call.  attr_acc: the
+    // accumulator / map [max_batch, H, W, C]; attr_in: the path input the steps' forwards read (x_stage stays as it is); attr_x0:
+    // the baseline table [max_batch, C]; attr_part: block partials; attr_out: the sums and endpoints (Model::integrated_gradients).
+    // attr_steps_last / attr_baseline_last: what DNNCA_PLAN_ATTRIBUTION replays (before any call: 32, black)
+    static constexpr int kAttrMaxSteps = 256;
+    float *attr_acc = nullptr, *attr_in = nullptr, *attr_x0 = nullptr;
+    double *attr_part = nullptr, *attr_out = nullptr;
+    int attr_steps_last = 32, attr_baseline_last = 0;
+    int integrated_gradients(const float* x_dev, int B, int steps, int baseline, bool want_map);
 
     // test-time augmentation (dnnca_forward_tta): the flipped / transposed copy of the batch that a view's forward reads, allocated
     // for max_batch by the first call (x_stage keeps the untransformed batch); tta_io: the device buffers of dnnca_tta_view_of /

@@ -16,6 +16,7 @@
 #include "kernels.h"
 #include "region.h"
 #include "sens.h"
+#include "attr.h"
 
 namespace dnnca {
 
@@ -1173,10 +1174,19 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
 // optimizer step, no BatchNorm state.  Scratch: the tensors' .g views, `dlogits` (the pass's logits: `logits` / `prob` keep the last
 // forward's) and the BatchNorm coefficient tables.  The convs that read the network input get no dx tensor: one launch forms |dx| and
 // reduces it (k_sens_first).
-int Model::input_sensitivity(const float* x_dev, int B) {
-    if (multires()) { set_error("input sensitivity is not implemented for MultiResUnet (its pass knows the U-Net op types only)"); return DNNCA_EINVAL; }
-    if (desc.dtype != DNNCA_F32) { set_error("input sensitivity needs a dtype f32 model (this one is bf16)"); return DNNCA_EINVAL; }
-    if (desc.kernel_size > kSensMaxK) { set_error("input sensitivity: kernel_size %d above %d", desc.kernel_size, kSensMaxK); return DNNCA_EINVAL; }
+
+// the refusals the input-gradient passes share; `what`: the pass's name in the message
+int Model::sens_refusal(const char* what) {
+    if (multires()) { set_error("%s is not implemented for MultiResUnet (its pass knows the U-Net op types only)", what); return DNNCA_EINVAL; }
+    if (desc.dtype != DNNCA_F32) { set_error("%s needs a dtype f32 model (this one is bf16)", what); return DNNCA_EINVAL; }
+    if (desc.kernel_size > kSensMaxK) { set_error("%s: kernel_size %d above %d", what, desc.kernel_size, kSensMaxK); return DNNCA_EINVAL; }
+    return DNNCA_OK;
+}
+
+// What input_sensitivity and integrated_gradients share: the inference forward of x_dev that stores every tensor (logits in
+// `dlogits`), the first-layer table (built once), and the data gradients over `ops` in reverse down to the gradients of the first
+// convs' outputs.  The caller launches the first-layer kernel of its choice behind it.
+int Model::sens_backward(const float* x_dev, int B) {
     sens_pass = true;
     const int frc = forward(x_dev, B, false);
     sens_pass = false;
@@ -1197,6 +1207,15 @@ int Model::input_sensitivity(const float* x_dev, int B) {
                 hd.push_back(SensFirst{o.out.g.p, o.out.d.p, p + o.w_off, o.inA.d.C, c0, std::min(kSensCi, o.inA.d.C - c0), o.out.d.C, chan + c0, o.alpha});
         }
         if (hd.empty()) { set_error("internal: input sensitivity: no conv reads the network input"); return DNNCA_ESTATE; }
+        // every network input channel belongs to exactly one entry: k_attr_first then has one writer per (pixel, channel)
+        std::vector<int> owners(C, 0);
+        for (const SensFirst& e : hd)
+            for (int j = 0; j < e.nci; ++j) {
+                if (e.chan + j < 0 || e.chan + j >= C) { set_error("internal: input sensitivity: first-layer entry outside the %d input channels", C); return DNNCA_ESTATE; }
+                ++owners[e.chan + j];
+            }
+        for (int c = 0; c < C; ++c)
+            if (owners[c] != 1) { set_error("internal: input sensitivity: input channel %d is read by %d first convs, not 1", c, owners[c]); return DNNCA_ESTATE; }
         const SensFirstGrid g = sens_first_grid(1, H, W, 1);
         void* dd = nullptr;
         DN_TRY(alloc(&dd, hd.size() * sizeof(SensFirst)));
@@ -1254,15 +1273,97 @@ int Model::input_sensitivity(const float* x_dev, int B) {
         }
     }
     cur_op = nullptr;
-    const SensFirstGrid g = sens_first_grid(B, H, W, sens_nz);
+    return DNNCA_OK;
+}
+
+// algorithmic bytes (dy and y of the first convs) and flops of one first-layer launch
+void Model::sens_first_cost(int B, double* bytes, double* flops) const {
     double fb = 0, ff = 0;
     for (const Op& o : ops)
         if (o.type == OP_CONV && !o.need_din) {
             fb += 8.0 * nelem(B, o.out.d);
-            ff += 2.0 * B * H * W * o.k * o.k * o.inA.d.C * o.out.d.C;
+            ff += 2.0 * B * desc.height * desc.width * o.k * o.k * o.inA.d.C * o.out.d.C;
         }
+    *bytes = fb;
+    *flops = ff;
+}
+
+int Model::input_sensitivity(const float* x_dev, int B) {
+    DN_TRY(sens_refusal("input sensitivity"));
+    DN_TRY(sens_backward(x_dev, B));
+    const int C = desc.in_channels, H = desc.height, W = desc.width;
+    const SensFirstGrid g = sens_first_grid(B, H, W, sens_nz);
+    double fb = 0, ff = 0;
+    sens_first_cost(B, &fb, &ff);
     LAUNCH(this, "sens_first", fb, ff,
            g_sens_first(stream, (const SensFirst*)sens_descs, sens_nz, B, H, W, desc.kernel_size, C, g, sens_part, sens_ticket, sens_sums));
+    return DNNCA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- integrated gradients
+// attr[b, h, w, c] = (x - x0) (1 / m) sum over k of d F_b / d x at x0 + alpha_k (x - x0), alpha_k = (k + 0.5) / m, F_b = sum over
+// the image of sigmoid(logits_b), model in inference mode (include/dnnca.h).  Per step: the path input into a buffer of its own
+// (x_dev is only read), sens_backward on it, and k_attr_first adds the signed first-layer dx into the accumulator -- step 0 stores,
+// the later ones add, in ascending k, one writer per element: bit-identical from run to run.  Then attr_finish, and two more
+// forwards (alpha = 0, then alpha = 1 on x_dev itself: the pass ends with the tensors and the input pointers of a forward of x_dev).
+// Results: attr_out = [B, C, 2] (signed, absolute), then B x F(x), then B x F(x0); with want_map attr_acc holds attr.
+int Model::integrated_gradients(const float* x_dev, int B, int steps, int baseline, bool want_map) {
+    DN_TRY(sens_refusal("integrated gradients"));
+    if (B < 1 || B > desc.max_batch) { set_error("batch %d outside [1, max_batch=%d]", B, desc.max_batch); return DNNCA_EINVAL; }
+    if (steps < 1 || steps > kAttrMaxSteps) { set_error("integrated gradients: steps %d outside [1, %d]", steps, kAttrMaxSteps); return DNNCA_EINVAL; }
+    if (baseline != 0 && baseline != 1) { set_error("integrated gradients: baseline %d is neither 0 (black) nor 1 (slice mean)", baseline); return DNNCA_EINVAL; }
+    const int C = desc.in_channels, H = desc.height, W = desc.width;
+    if (C > kAttrMaxC) { set_error("integrated gradients: %d input channels above %d", C, kAttrMaxC); return DNNCA_EINVAL; }
+    const size_t hw = (size_t)H * W, hw_out = (size_t)outH * outW;
+    if (!attr_acc) {
+        const size_t mb = (size_t)desc.max_batch, nb = (size_t)std::max(attr_blocks(hw), attr_blocks(hw_out));
+        DN_TRY(alloc((void**)&attr_acc, mb * hw * C * 4));
+        DN_TRY(alloc((void**)&attr_in, mb * hw * C * 4));
+        DN_TRY(alloc((void**)&attr_x0, mb * C * 4));
+        DN_TRY(alloc((void**)&attr_part, mb * C * 2 * nb * 8));
+        DN_TRY(alloc((void**)&attr_out, mb * (2 * C + 2) * 8));
+    }
+    attr_steps_last = steps;
+    attr_baseline_last = baseline;
+    const double xb = 4.0 * B * hw * C;
+    const float* x0 = nullptr;
+    if (baseline == 1) {
+        LAUNCH(this, "attr_baseline_part", xb, (double)B * hw * C, g_attr_baseline_part(stream, x_dev, B, hw, C, attr_part));
+        LAUNCH(this, "attr_baseline", 8.0 * B * C * attr_blocks(hw), (double)B * C * attr_blocks(hw),
+               g_attr_baseline(stream, attr_part, B, hw, C, attr_x0));
+        x0 = attr_x0;
+    }
+    double fb = 0, ff = 0;
+    sens_first_cost(B, &fb, &ff);
+    for (int k = 0; k < steps; ++k) {
+        const float alpha = (float)(((double)k + 0.5) / (double)steps);
+        LAUNCH(this, "attr_path_in", 2 * xb, 2.0 * B * hw * C, g_attr_path_in(stream, x_dev, x0, alpha, B, hw, C, attr_in));
+        DN_TRY(sens_backward(attr_in, B));
+        const SensFirstGrid g = sens_first_grid(B, H, W, sens_nz);
+        LAUNCH(this, "attr_first", fb + (k ? 2 : 1) * xb, ff,
+               g_attr_first(stream, (const SensFirst*)sens_descs, sens_nz, B, H, W, desc.kernel_size, C, g, attr_acc, k == 0));
+    }
+    const int nb = attr_blocks(hw), nbo = attr_blocks(hw_out);
+    LAUNCH(this, "attr_finish", (want_map ? 3 : 2) * xb, 4.0 * B * hw * C,
+           g_attr_finish(stream, attr_acc, x_dev, x0, steps, B, hw, C, want_map ? 1 : 0, attr_part));
+    LAUNCH(this, "attr_sums", 8.0 * B * C * 2 * nb, (double)B * C * 2 * nb, g_attr_sums(stream, attr_part, B * C * 2, nb, attr_out));
+    // the endpoints: F(x0) first, F(x) last
+    for (int e = 1; e >= 0; --e) {
+        const float* xe = x_dev;
+        if (e == 1) {
+            LAUNCH(this, "attr_base_in", 2 * xb, 2.0 * B * hw * C, g_attr_path_in(stream, x_dev, x0, 0.f, B, hw, C, attr_in));
+            xe = attr_in;
+        }
+        sens_pass = true;
+        const int frc = forward(xe, B, false);
+        sens_pass = false;
+        DN_TRY(frc);
+        cur_op = nullptr;
+        LAUNCH(this, "attr_prob_part", 4.0 * B * hw_out, 20.0 * B * hw_out, g_attr_prob_part(stream, dlogits, B, hw_out, attr_part));
+        // row b of the [B, nbo] table -> entry b of endpoint e's run behind the [B, C, 2] sums
+        LAUNCH(this, "attr_prob_sum", 8.0 * B * nbo, (double)B * nbo,
+               g_attr_sums(stream, attr_part, B, nbo, attr_out + (size_t)B * C * 2 + (size_t)e * B));
+    }
     return DNNCA_OK;
 }
 
@@ -1839,6 +1940,34 @@ int dnnca_input_sensitivity(void* model, const float* x_nhwc, int batch, double*
     DN_TRY(M->input_sensitivity(M->x_stage, batch));
     HIP_TRY(hipMemcpyAsync(sums, M->sens_sums, (size_t)batch * M->desc.in_channels * 8, hipMemcpyDeviceToHost, M->stream));
     HIP_TRY(hipStreamSynchronize(M->stream));
+    return M->flush_profile();
+}
+
+int dnnca_integrated_gradients(void* model, const float* x_nhwc, int batch, int steps, int baseline, double* signed_sums, double* abs_sums,
+                               double* endpoints, float* map) {
+    MODEL(model);
+    if (!signed_sums || !abs_sums || !endpoints) { set_error("null sums or endpoints"); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
+    if (steps < 1 || steps > Model::kAttrMaxSteps) { set_error("integrated gradients: steps %d outside [1, %d]", steps, Model::kAttrMaxSteps); return DNNCA_EINVAL; }
+    if (baseline != 0 && baseline != 1) { set_error("integrated gradients: baseline %d is neither 0 (black) nor 1 (slice mean)", baseline); return DNNCA_EINVAL; }
+    DN_TRY(M->sens_refusal("integrated gradients"));
+    if (x_nhwc) DN_TRY(stage_inputs(M, batch, x_nhwc, nullptr, false));
+    else if (M->last_batch != batch) { set_error("integrated gradients without x: the last forward had %d slices, not %d", M->last_batch, batch); return DNNCA_ESTATE; }
+    DN_TRY(M->integrated_gradients(M->x_stage, batch, steps, baseline, map != nullptr));
+    const int C = M->desc.in_channels;
+    std::vector<double> h((size_t)batch * (2 * C + 2));
+    HIP_TRY(hipMemcpyAsync(h.data(), M->attr_out, h.size() * 8, hipMemcpyDeviceToHost, M->stream));
+    if (map) HIP_TRY(hipMemcpyAsync(map, M->attr_acc, (size_t)batch * M->desc.height * M->desc.width * C * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    for (int i = 0; i < batch * C; ++i) {
+        signed_sums[i] = h[(size_t)2 * i];
+        abs_sums[i] = h[(size_t)2 * i + 1];
+    }
+    const double* e = h.data() + (size_t)batch * C * 2;
+    for (int b = 0; b < batch; ++b) {
+        endpoints[2 * b] = e[b];                  // F(x)
+        endpoints[2 * b + 1] = e[batch + b];      // F(x0)
+    }
     return M->flush_profile();
 }
 
@@ -2776,7 +2905,7 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
     if (!buf || !cap) return DNNCA_EINVAL;
     if (pass != DNNCA_PLAN_TRAIN && pass != DNNCA_PLAN_EVAL && pass != DNNCA_PLAN_FORWARD && pass != DNNCA_PLAN_SENSITIVITY &&
         pass != DNNCA_PLAN_LESION && pass != DNNCA_PLAN_LESION_LINKED && pass != DNNCA_PLAN_LESION_MATCHED &&
-        pass != DNNCA_PLAN_SURFACE) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
+        pass != DNNCA_PLAN_SURFACE && pass != DNNCA_PLAN_ATTRIBUTION) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
     DN_TRY(check_batch(M, batch));
     M->plan_text.clear();
     M->dry = true;
@@ -2799,6 +2928,8 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
         if (rc == DNNCA_OK) rc = M->loss_and_backward(M->y_stage, B, cfg, false);
     } else if (pass == DNNCA_PLAN_SENSITIVITY) {
         rc = M->input_sensitivity(M->x_stage, B);
+    } else if (pass == DNNCA_PLAN_ATTRIBUTION) {
+        rc = M->integrated_gradients(M->x_stage, B, M->attr_steps_last, M->attr_baseline_last, true);
     } else if (pass == DNNCA_PLAN_LESION || pass == DNNCA_PLAN_LESION_LINKED) {
         LesionArgs a;
         bool want_mask = true;

@@ -4,12 +4,15 @@ This is the object that replaces the compiled tf.keras.Model of the reference (e
 weights, the Adam slots and the activations in HBM and exposes forward / train_step / eval_step."""
 
 import ctypes as C
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 
 from . import _lib
 from ._lib import check, fptr, as_f32
+
+# what DeviceModel.integrated_gradients returns
+Attribution = namedtuple('Attribution', 'signed absolute endpoints map')
 
 
 def init_device(ordinal=0):
@@ -800,6 +803,32 @@ class DeviceModel:
         check(self.lib.dnnca_input_sensitivity(self.handle, xp, B, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
+    ATTRIBUTION_BASELINES = {'black': 0, 'mean': 1}
+
+    def integrated_gradients(self, x=None, batch=None, steps=32, baseline='black', return_map=False):
+        """Integrated gradients of F_b = sum(prob of slice b) in inference mode along the straight path from a constant baseline
+        plane per (slice, channel) -- 'black': 0, 'mean': the plane's mean -- to the slice, midpoint rule with `steps` points
+        (include/dnnca.h: dnnca_integrated_gradients).  Returns Attribution(signed, absolute, endpoints, map): float64 [B, C] sums of
+        attr and of |attr| over the image, float64 [B, 2] (F(x), F(baseline)), and attr itself as float32 [B, H, W, C] with
+        return_map (else None).  x [B, H, W, C], or None with `batch`: the slices the last forward(x) left on the device.
+        dtype f32 U-Net / mulmo models only."""
+        if baseline not in self.ATTRIBUTION_BASELINES:
+            raise ValueError('baseline %r is none of %s' % (baseline, sorted(self.ATTRIBUTION_BASELINES)))
+        if x is None:
+            B, xp = int(batch), None
+        else:
+            x = self._check_x(x)
+            B, xp = x.shape[0], fptr(x)
+        n = max(B, 0)
+        H, W, Cn = self.in_shape
+        dp = C.POINTER(C.c_double)
+        signed, absolute, ends = np.empty((n, Cn), np.float64), np.empty((n, Cn), np.float64), np.empty((n, 2), np.float64)
+        amap = np.empty((n, H, W, Cn), np.float32) if return_map else None
+        check(self.lib.dnnca_integrated_gradients(self.handle, xp, B, int(steps), self.ATTRIBUTION_BASELINES[baseline],
+                                                  signed.ctypes.data_as(dp), absolute.ctypes.data_as(dp), ends.ctypes.data_as(dp),
+                                                  fptr(amap) if return_map else None))
+        return Attribution(signed, absolute, ends, amap)
+
     # ---- device-side augmentation (annotator/data.py:62-111 train_ds) ------------------------------------------
     def augment_u8(self, raw, params, out_size, label_index, contrast_channels=None, src_ptr=None):
         """raw uint8 [B, Hs, Ws, Cs] (host) + per-image draws [(dy, dx, flip, contrast)] -> device-resident (x [B, Ho, Wo, Cs-1],
@@ -931,7 +960,7 @@ class DeviceModel:
         return out
 
     PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3, 'lesion': 4, 'lesion_linked': 5, 'lesion_matched': 6,
-                   'surface': 7}
+                   'surface': 7, 'attribution': 8}
 
     def plan(self, variants=False, mode='train', batch=None):
         """The launch schedule of one pass: [(kernel, algorithmic bytes, flops)].  mode 'train': one train step; 'eval': one
@@ -939,12 +968,13 @@ class DeviceModel:
         'sensitivity': input_sensitivity; 'lesion': lesion_table on the last forward's probabilities, with the resize factor,
         filter size and mask choice of the last lesion_table / lesion_table_linked call; 'lesion_linked': lesion_table_linked likewise;
         'lesion_matched': lesion_table_matched with the three values of the last lesion_table_matched call; 'surface':
-        surface_distances with the resize factor and filter size of the last surface_distances call.
+        surface_distances with the resize factor and filter size of the last surface_distances call; 'attribution':
+        integrated_gradients with the steps and baseline of the last integrated_gradients call (before any: 32, 'black') and the map.
         batch: None = max_batch.  variants: keep the template variant the library appends to a launch name
         (`ig_conv_fwd#3n2w8`): the kernel-coverage test tells them apart.  A dry run: the model is unchanged."""
         if mode not in self.PLAN_PASSES:
             raise ValueError('plan mode %r is none of %s' % (mode, sorted(self.PLAN_PASSES)))
-        buf = C.create_string_buffer(1 << 20)
+        buf = C.create_string_buffer(1 << (24 if mode == 'attribution' else 20))      # up to 256 passes in one plan
         if mode == 'train' and batch is None:
             check(self.lib.dnnca_plan_dump(self.handle, buf, len(buf)))
         else:

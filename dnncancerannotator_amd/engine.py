@@ -81,6 +81,26 @@ def check_temperature(temperature):
     return None if t == 1.0 else t
 
 
+def check_attribution(attribution, steps, baseline, export_csv, export_images):
+    """--visualize_attribution writes per-slice files: it needs --export_csv and / or --export_images; --attribution_steps must lie
+    in casewise.ATTRIBUTION_STEP_RANGE and --attribution_baseline be one of casewise.ATTRIBUTION_BASELINES.  A ValueError, before
+    anything is read; the two options without the flag are an error too.  Returns (steps, baseline)"""
+    if not attribution:
+        if steps is not None or baseline is not None:
+            raise ValueError('--attribution_steps / --attribution_baseline need --visualize_attribution')
+        return None
+    if not (export_csv or export_images):
+        raise ValueError('--visualize_attribution writes per-slice files: add --export_csv and / or --export_images')
+    steps = casewise.ATTRIBUTION_STEPS if steps is None else int(steps)
+    lo, hi = casewise.ATTRIBUTION_STEP_RANGE
+    if not lo <= steps <= hi:
+        raise ValueError('--attribution_steps must lie in %d..%d, got %r' % (lo, hi, steps))
+    baseline = casewise.ATTRIBUTION_BASELINES[0] if baseline is None else baseline
+    if baseline not in casewise.ATTRIBUTION_BASELINES:
+        raise ValueError('--attribution_baseline must be one of %s, got %r' % (', '.join(casewise.ATTRIBUTION_BASELINES), baseline))
+    return steps, baseline
+
+
 def check_calibration(n_bins, temperatures):
     """--calibration_bins and --calibration_temperatures: (bins, the temperature grid of casewise.calibration_grid) or a ValueError"""
     if not 1 <= int(n_bins) <= 256:
@@ -599,7 +619,8 @@ class TFKerasModel:
              surface_ds=None, surface_distances=False, surface_threshold=(0.5,), surface_percentile=casewise.SURFACE_PERCENTILE,
              surface_min_area=0, surface_filter_size=5, surface_resize_factor=1.0, surface_max_samples=65536, tta='none',
              uncertainty_ds=None, uncertainty=False, uncertainty_thresholds=(0.5,), calibration_ds=None, calibration=False,
-             calibration_bins=casewise.CALIBRATION_BINS, calibration_temperatures=None, temperature=None):
+             calibration_bins=casewise.CALIBRATION_BINS, calibration_temperatures=None, temperature=None,
+             visualize_attribution=False, attribution_steps=None, attribution_baseline=None):
         """exam_lesions (`evaluate --exam_lesions`): after every checkpoint's evaluation rank 0 also runs _exam_lesion_pass over
         exam_ds (batches (x, y, paths, sliceIDs), a data set of its own: viz_ds is not needed) and writes exam_lesion_results.csv,
         exam_lesion_cases.csv and exam_lesion_matches.csv under <export_path>/<tag>/; every other file is what it is without it.
@@ -621,13 +642,23 @@ class TFKerasModel:
         temperature (`evaluate --temperature T`): every probability read -- by the pixel and region metrics, the Visualizer and every
         extra pass, --calibration included -- is scaled by DeviceModel.scale_temperature, once per forward.  The evaluation then
         runs batch by batch, `loss` stays the unscaled test step's and the spread of --uncertainty that of the unscaled views.
-        None or 1: nothing new runs."""
+        None or 1: nothing new runs.
+        visualize_attribution (`evaluate --visualize_attribution`): the Visualizer pass also runs DeviceModel.integrated_gradients
+        (attribution_steps path points, default casewise.ATTRIBUTION_STEPS; attribution_baseline 'black' or 'mean') on the slices
+        each plain forward left on the device and writes per slice step_<step>_attribution.csv (export_csv) and
+        step_<step>_attribution.png (export_images: only then does a map leave the device), and per checkpoint a line of
+        attribution_results.csv under <export_path>/<tag>/.  Like the sensitivity it is the attribution of the plain forward, also
+        under tta / temperature.  Needs export_csv or export_images; every other file is what it is without the flag."""
         check_uncertainty(uncertainty, tta)
+        attribution = check_attribution(visualize_attribution, attribution_steps, attribution_baseline, export_csv, export_images)
         temperature = check_temperature(temperature)
         if calibration:
             calibration_bins, calibration_grid = check_calibration(calibration_bins, calibration_temperatures)
         if visualize_sensitivity and not getattr(self.model, 'supports_sensitivity', True):
             raise NotImplementedError('--visualize_sensitivity is not implemented for model: %s (the input-gradient pass covers the '
+                                      'U-Net models only)' % self.model_config['model'])
+        if attribution and not getattr(self.model, 'supports_sensitivity', True):
+            raise NotImplementedError('--visualize_attribution is not implemented for model: %s (the input-gradient pass covers the '
                                       'U-Net models only)' % self.model_config['model'])
         tta_mask = None if tta == tta_modes.NONE else tta_modes.mask_of(tta, *_element_shape(dataset)[1:3])
         self._build(dataset)
@@ -664,6 +695,7 @@ class TFKerasModel:
         uncertainty_tables = [], []      # the lines of uncertainty_results.csv and uncertainty_slices.csv
         calibration_pass = bool(calibration) and calibration_ds is not None and self.ctx.rank == 0
         calibration_tables = [], [], []  # the lines of calibration_results.csv, calibration_bins.csv and calibration_slices.csv
+        attribution_table, attribution_names = [], []      # the lines of attribution_results.csv; the modalities of its share columns
         rows = OrderedDict()
         previous_step = None
         for ckpt_step, ckpt_path_ in self.get_ckpts(ckpt_path).items():
@@ -678,7 +710,8 @@ class TFKerasModel:
                 self._evaluate(dataset, staged=False, tta_mask=tta_mask, **more)
             if visualize:
                 self._visualize(viz_ds, ckpt_step, viz_root, export_csv, export_images, overlay, casewise_rows, writer,
-                                sensitivity=bool(visualize_sensitivity), tta_mask=tta_mask, **more)
+                                sensitivity=bool(visualize_sensitivity), tta_mask=tta_mask, **more,
+                                **(dict(attribution=attribution + (attribution_table, attribution_names)) if attribution else {}))
             if exam_pass:
                 for t, new in zip(exam_tables, self._exam_lesion_pass(
                         exam_ds, ckpt_step, [float(t) for t in exam_threshold], exam_iou, exam_link_min_overlap,
@@ -727,6 +760,12 @@ class TFKerasModel:
                                          exam_tables):
                 with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
                     f.write(casewise.plain_csv(['step', 'threshold'] + cols, table))
+        if attribution and visualize:
+            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
+            with open(os.path.join(export_path, tag, 'attribution_results.csv'), 'w', newline='') as f:
+                cols = casewise.ATTRIBUTION_RESULT_COLUMNS + ['share_%s' % n for n in attribution_names] + \
+                    ['mean_relative_gap', 'max_relative_gap']
+                f.write(casewise.plain_csv(['step'] + cols, attribution_table))
         if writer is not None:
             writer.close()
         if export_csv and self.ctx.rank == 0:
@@ -742,13 +781,17 @@ class TFKerasModel:
         return rows
 
     def _visualize(self, viz_ds, step, root, export_csv, export_images, overlay, casewise_rows, writer, sensitivity=False,
-                   tta_mask=None, temperature=None):
+                   tta_mask=None, temperature=None, attribution=None):
         """One Visualizer pass (callbacks.py process_batch / _emit) over viz_ds batches (x, y, paths, sliceIDs): forward
         (training=False), the per-slice region counts (export_csv), the composite images (export_images), then the files.  The
         probabilities stay on the device; only the counts and the uint8 images come back.  casewise_rows gains one row per slice,
         in dataset order.  sensitivity (--visualize_sensitivity, callbacks.py:290-313): the input-gradient pass on the slices the
-        forward left on the device; per slice a CSV (export_csv) and a bar chart (export_images) of the normalised channel sums."""
+        forward left on the device; per slice a CSV (export_csv) and a bar chart (export_images) of the normalised channel sums.
+        attribution (--visualize_attribution): (steps, baseline, table, names) -- DeviceModel.integrated_gradients on the same
+        slices; per slice a CSV (export_csv) and the per-modality maps (export_images: the map is fetched only then); `table` gains
+        this checkpoint's line of attribution_results.csv and `names` is set to the modalities."""
         spec = casewise.device_spec()
+        attr_shares, attr_gaps = [], []
         names = casewise.column_names()
         for x, y, paths, ids in viz_ds:
             x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
@@ -780,6 +823,23 @@ class TFKerasModel:
                         if export_images:
                             writer.submit(casewise.sensitivity_path(root, t, step, 'images'),
                                           lambda r: casewise.encode_png(casewise.sensitivity_chart(r)), row)
+                if attribution:
+                    ig = dm.integrated_gradients(batch=len(xb), steps=attribution[0], baseline=attribution[1],
+                                                 return_map=bool(export_images))
+                    shares = casewise.attribution_shares(ig.absolute)
+                    mods = casewise.modality_names(getattr(viz_ds, 'slice_types', None), shares.shape[1])
+                    attribution[3][:] = mods
+                    attr_shares += list(shares)
+                    attr_gaps += list(casewise.attribution_gap(ig.signed, ig.endpoints)[1])
+                    for b, t in enumerate(tags):
+                        if export_csv:
+                            writer.submit(casewise.attribution_path(root, t, step, 'csv'), casewise.attribution_csv, mods, shares[b],
+                                          ig.signed[b], ig.absolute[b], ig.endpoints[b])
+                        if export_images:
+                            writer.submit(casewise.attribution_path(root, t, step, 'images'),
+                                          lambda m, n: casewise.encode_png(casewise.attribution_image(m, n)), ig.map[b], mods)
+        if attribution:
+            attribution[2].append([int(step)] + casewise.attribution_summary(attribution[0], attribution[1], attr_shares, attr_gaps))
 
     def _exam_lesion_pass(self, ds, step, thresholds, iou, min_overlap, kw, tta_mask=None, temperature=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --exam_lesions`: per max_batch split one forward whose

@@ -12,8 +12,10 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
              exam_min_area=0, exam_filter_size=5, exam_resize_factor=1.0, exam_max_lesions=256, exam_link_min_overlap=1,
              surface_distances=False, surface_threshold=(0.5,), surface_percentile=95.0, surface_min_area=0, surface_filter_size=5,
              surface_resize_factor=1.0, surface_max_samples=65536, tta='none', uncertainty=False, uncertainty_threshold=(0.5,),
-             calibration=False, calibration_bins=15, calibration_temperatures=None, temperature=None):
+             calibration=False, calibration_bins=15, calibration_temperatures=None, temperature=None, visualize_attribution=False,
+             attribution_steps=None, attribution_baseline=None):
     engine.check_uncertainty(uncertainty, tta)       # before anything is read
+    attribution = engine.check_attribution(visualize_attribution, attribution_steps, attribution_baseline, export_csv, export_images)
     scaled = engine.check_temperature(temperature)   # likewise; None without the flag and with --temperature 1
     if calibration:
         engine.check_calibration(calibration_bins, calibration_temperatures)
@@ -43,6 +45,8 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
                     calibration_temperatures=None if calibration_temperatures is None else tuple(calibration_temperatures))
     if scaled is not None:               # the keyword of --temperature only with a temperature other than 1
         more['temperature'] = scaled
+    if attribution:                      # and those of --visualize_attribution only with the flag
+        more.update(visualize_attribution=True, attribution_steps=attribution[0], attribution_baseline=attribution[1])
     model = engine.TFKerasModel(config)
     return model.eval(ds, viz_ds=viz_ds, tag=tag, save_path=os.path.join(save_path), avoid_overwrite=avoid_overwrite,
                       export_path=export_path, export_images=export_images, export_csv=export_csv,

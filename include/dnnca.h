@@ -539,6 +539,29 @@ int dnnca_surface_distances(void* model, const float* prob_hw, const float* y_hw
  * Synchronises. */
 int dnnca_input_sensitivity(void* model, const float* x_nhwc, int batch, double* sums /* [batch * in_channels] */);
 
+/* ---- integrated-gradients attribution of `annotator evaluate --visualize_attribution` (Sundararajan et al. 2017) ------------------
+ * The plain gradient of dnnca_input_sensitivity vanishes where the sigmoid saturates; this pass integrates it along the straight
+ * path from a baseline image to the slice.  With the model in inference mode and F_b(x) = sum over H, W of sigmoid(logits_b(x)):
+ *     baseline  x0[b, :, :, c] is a constant plane: 0 (baseline = 0, black) or the mean of x[b, :, :, c] (baseline = 1), the mean
+ *               formed on the device in double in a fixed order and rounded once to float32
+ *     path      x(alpha) = x0 + alpha (x - x0), alpha_k = (k + 0.5) / steps for k = 0 .. steps - 1 (midpoint rule), steps in 1..256
+ *     attr[b, h, w, c] = (x - x0)[b, h, w, c] * (1 / steps) * sum over k of (d F_b / d x)(x(alpha_k))[b, h, w, c]
+ *     signed_sums[b * C + c] = sum over H, W of attr;  abs_sums[b * C + c] = sum over H, W of |attr|
+ *     endpoints[2 b] = F_b(x), endpoints[2 b + 1] = F_b(x0), from two more forwards
+ * The attributions of a slice sum to F_b(x) - F_b(x0) up to the error of the quadrature (completeness): the caller forms the gap
+ * sum over c of signed_sums[b, c] - (endpoints[2 b] - endpoints[2 b + 1]).  map: NULL, or host [batch, H, W, C] for attr itself.
+ * x_nhwc as in dnnca_input_sensitivity (NULL: the slices the last forward left staged; DNNCA_ESTATE when `batch` is not that
+ * forward's).  Cost: steps + 2 inference forwards and `steps` data-gradient backward passes.  Untouched: variables, BatchNorm state,
+ * optimizer slots, the staged slices and the last forward's logits and probabilities (scratch: the gradient views and four buffers
+ * of the pass's own, allocated for max_batch by the first call).  All sums are float64; sums and map are bit-identical from run
+ * to run (no atomics: every element has one writer, every sum a fixed order).  dtype f32 U-Net / mulmo models only: a DNNCA_BF16 or
+ * MultiResUnet model returns DNNCA_EINVAL; so do a batch outside [1, max_batch], steps outside [1, 256], a baseline other than 0 / 1
+ * and a NULL signed_sums, abs_sums or endpoints.  Synchronises. */
+int dnnca_integrated_gradients(void* model, const float* x_nhwc /* NULL: the slices the last forward left */, int batch,
+                               int steps, int baseline /* 0 black, 1 slice mean */,
+                               double* signed_sums /* [B,C] */, double* abs_sums /* [B,C] */, double* endpoints /* [B,2] */,
+                               float* map /* [B,H,W,C] or NULL */);
+
 /* ---- data parallel: tf.distribute.MirroredStrategy (engine.py:260-263) re-done as one process per GPU + RCCL ---- */
 int dnnca_comm_unique_id(void* id_out /* DNNCA_UNIQUE_ID_BYTES */);
 int dnnca_comm_init(void* model, int rank, int world, const void* unique_id, size_t id_len);   /* world == 1: no-op */
@@ -572,10 +595,11 @@ int dnnca_plan_dump(void* model, char* buf, size_t cap);
    resize factor, filter size and mask choice of the last dnnca_lesion_table / dnnca_lesion_table_linked call (before any: 1.0, 5,
    with mask), or dnnca_lesion_table_linked with the same three values, or dnnca_lesion_table_matched with the three values of the
    last dnnca_lesion_table_matched call (before any: the same defaults), or dnnca_surface_distances with the resize factor and
-   filter size of the last dnnca_surface_distances call (before any: 1.0, 5).  A dry run: nothing is launched and the model is left
+   filter size of the last dnnca_surface_distances call (before any: 1.0, 5), or dnnca_integrated_gradients with the steps and
+   baseline of the last dnnca_integrated_gradients call (before any: 32, black) and the map requested.  A dry run: nothing is launched and the model is left
    as it was. */
 enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2, DNNCA_PLAN_SENSITIVITY = 3, DNNCA_PLAN_LESION = 4,
-       DNNCA_PLAN_LESION_LINKED = 5, DNNCA_PLAN_LESION_MATCHED = 6, DNNCA_PLAN_SURFACE = 7 };
+       DNNCA_PLAN_LESION_LINKED = 5, DNNCA_PLAN_LESION_MATCHED = 6, DNNCA_PLAN_SURFACE = 7, DNNCA_PLAN_ATTRIBUTION = 8 };
 int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap);
 
 #ifdef __cplusplus
