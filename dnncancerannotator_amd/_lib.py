@@ -39,6 +39,11 @@ class LossCfg(C.Structure):
                 ('label_smoothing', C.c_int32), ('label_smoothing_filter_size', C.c_int32), ('label_smoothing_sigma', C.c_float)]
 
 
+class RegionLoss(C.Structure):                     # dnnca_region_loss
+    _fields_ = [('region_weight', C.c_float), ('crossentropy_weight', C.c_float), ('alpha', C.c_float), ('beta', C.c_float),
+                ('smooth', C.c_float)]
+
+
 class StepOut(C.Structure):
     _fields_ = [('loss', C.c_float), ('positive_rate', C.c_float), ('weight', C.c_float),
                 ('label_min', C.c_float), ('label_max', C.c_float)]
@@ -200,6 +205,8 @@ SIGNATURES = {
     'dnnca_last_step_confusion': (C.c_int, [_VP, C.POINTER(Confusion)]),
     'dnnca_staged_confusion': (C.c_int, [_VP, C.c_int, C.POINTER(Confusion)]),
     'dnnca_get_prob': (C.c_int, [_VP, _FP, C.c_int64]),
+    'dnnca_model_set_region_loss': (C.c_int, [_VP, C.POINTER(RegionLoss)]),
+    'dnnca_region_loss_sums': (C.c_int, [_VP, C.c_int, C.POINTER(C.c_double)]),
     'dnnca_pixel_confusion': (C.c_int, [_VP, _FP, C.c_int, _FP, C.c_int, C.POINTER(Confusion)]),
     'dnnca_pixel_confusion_of': (C.c_int, [_VP, _FP, _FP, C.c_int64, _FP, C.c_int, C.POINTER(Confusion)]),
     'dnnca_region_confusion_of': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.POINTER(RegionSpec), C.POINTER(RegionCounts)]),

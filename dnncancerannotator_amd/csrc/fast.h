@@ -48,6 +48,7 @@ bool fast_pool_supported(const Model* m, const Op& o);
 bool fast_tconv_supported(const Model* m, const Op& o);
 bool fast_head_supported(const Model* m, const Op& o);
 bool fast_head_train(Model* m, int B, Op& o, const float* y, const dnnca_loss_cfg& cfg, float gscale, double bytes);
+void fast_head_partials_done(Model* m, int C, int blocks, float* dw, float* dbias);      // C in {3, 16, 64}: rows of C + 2 partials are in head_partials
 // utils/losses.py:62-67 label_smoothing: Gaussian blur of the labels (false: unsupported filter size / image smaller than the pad)
 bool fast_label_smooth(Model* m, int B, int H, int W, const float* y, float* out, int k, float sigma);
 bool fast_label_stats(Model* m, size_t n, const float* y);

@@ -494,6 +494,22 @@ bool fast_head_train(Model* m, int B, Op& o, const float* y, const dnnca_loss_cf
     return false;
 }
 
+// the same hand-over for a head kernel of another file (kernels_region_loss.hip) that left `blocks` rows of C + 2 partials in
+// Model::head_partials: the fold launch reduces them, or head_reduce does
+void fast_head_partials_done(Model* m, int C, int blocks, float* dw, float* dbias) {
+    if (m->head_defer_ok && m->merged_launches()) {
+        m->head_pending.partials = m->head_partials; m->head_pending.nblocks = blocks; m->head_pending.C = C;
+        m->head_pending.dw = dw; m->head_pending.dbias = dbias;
+        return;
+    }
+#define HEAD_CASE(c)                                                                                                   \
+    if (C == c)                                                                                                        \
+        LAUNCH(m, "head_reduce", 0, 0,                                                                                 \
+               hipLaunchKernelGGL(k_head_reduce<c>, dim3(c + 2), dim3(256), 0, m->stream, m->head_partials, blocks, dw, dbias, m->scalars));
+    HEAD_CASE(3) HEAD_CASE(16) HEAD_CASE(64)
+#undef HEAD_CASE
+}
+
 // ------------------------------------------------------------------------------------------------ label smoothing
 // utils/losses.py:62-67: y_true = tfa.image.gaussian_filter2d(y_true[..., None], filter_shape = k, sigma) -- REFLECT padding of
 // (k-1)/2 before / k-1-(k-1)/2 after (tf.pad REFLECT: the edge sample is not repeated), then a VALID depthwise conv with the

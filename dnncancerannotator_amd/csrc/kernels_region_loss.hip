@@ -1,0 +1,574 @@
+// kernels_region_loss.hip -- the region (Tversky / Dice) term of the training loss (dnnca_model_set_region_loss).
+//
+// Per image b, p = sigmoid(logit), y the step's label, sums over that image's H x W pixels:
+//   I = sum p y, P = sum p, Y = sum y;  N = I + s,  D = (1 - a - b) I + a P + b Y + s,  T = N / D
+//   loss = mean_b [ l_ce wBCE_b + l_r (1 - T_b) ]
+//   dloss/dlogit_i = l_ce mask_i (p_i - y_i) / (H W B) + l_r (C_b - A_b y_i) p_i (1 - p_i) / B
+//   A_b = (D - (1 - a - b) N) / D^2,  C_b = a N / D^2
+// The gradient of a pixel needs the sums of its whole image, so a step runs three launches where the plain loss runs one:
+//   head_region_fwd_<C>    feat -> logit -> p; stores the logits (and p for the per-step metrics); block partials of I, P, Y
+//   region_loss_finish     one block: the partials in a fixed order, in double -> I, P, Y, A, C per image; adds
+//                          l_r mean_b (1 - T_b) to the scalar block's regulariser slot (the finalize code reports it inside `loss`)
+//   head_region_train_<C>  reads feat and the stored logit, forms dlogit, writes dfeat (activation mask as k_head_train) and the
+//                          C + 2 block partials (dW, db, l_ce x BCE sum) in the layout k_head_reduce / the fold launch consume
+// and from a logits buffer (eval steps, generic models, heads without a fused kernel):
+//   region_sums            block partials of I, P, Y and of the weighted BCE sum
+//   region_loss_finish     ... also adds l_ce x BCE sum to the loss slot
+//   region_loss_grad       p, and dlogit when a backward pass follows
+// Every launch has a grid (blocks per image, images): a block works inside ONE image, so a partial belongs to one image by
+// construction, whatever H x W is.  No atomics: one row of partials per block, summed in ascending block order.
+#include <algorithm>
+#include <cmath>
+
+#include "fast.h"
+#include "kernels.h"
+#include "region_loss.h"
+
+namespace dnnca {
+
+namespace {
+
+DEVINL void rl_ld4(float* d, const float* p) {
+    const float4 v = *reinterpret_cast<const float4*>(p);
+    d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+}
+DEVINL void rl_st4(float* p, const float* s) { *reinterpret_cast<float4*>(p) = make_float4(s[0], s[1], s[2], s[3]); }
+
+// the positive-class weight of the step (kernels_generic.hip loss_weight; utils/losses.py:24-29)
+DEVINL float rl_weight(const dnnca_loss_cfg& cfg, double label_sum, double n_label) {
+    float w;
+    if (cfg.has_weight) {
+        w = cfg.weight;
+    } else {
+        const float pr = (float)(label_sum / n_label);
+        w = pr > 0.f ? 1.0f / pr : 1.0f;
+    }
+    return cfg.weight_mul * w + cfg.weight_add;
+}
+
+// the same butterfly in every run
+DEVINL double rl_wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// 256 threads: K sums of the block into dst[0 .. K), in a fixed order
+template <int K>
+DEVINL void rl_block_store(const double (&v)[K], double* dst) {
+    __shared__ double red[4][K];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double s = rl_wave_sum(v[k]);
+        if (lane == 0) red[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < K) dst[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// ------------------------------------------------------------------------------------------------ head, forward half
+struct RlHeadFwdArgs {
+    const float* feat;     // [B, hw, C]
+    const float* y;        // [B, hw]
+    const float* w;
+    const float* bias;
+    float* logits;         // [B, hw]
+    float* prob;           // [B, hw] or null
+    double* part;          // [gridDim.y][gridDim.x][kRlPart]
+    int hw;                // pixels per image (a multiple of 4: fast_head_supported)
+};
+
+// C = 3: one thread = 4 pixels of image blockIdx.y (three 16-byte loads of feat, one of y; 16-byte stores)
+template <int C>
+__global__ __launch_bounds__(256) void k_head_region_fwd(RlHeadFwdArgs p) {
+    float wv[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) wv[c] = p.w[c];
+    const float bias = p.bias[0];
+    const size_t img = (size_t)blockIdx.y * p.hw;
+    const int n4 = p.hw / 4;
+    double acc[kRlPart] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const size_t px0 = img + (size_t)i * 4;
+        float f[4 * C], z[4], lg[4], sg[4];
+#pragma unroll
+        for (int v = 0; v < C; ++v) rl_ld4(f + 4 * v, p.feat + px0 * C + 4 * v);
+        rl_ld4(z, p.y + px0);
+#pragma unroll
+        for (int px = 0; px < 4; ++px) {
+            float x = bias;
+#pragma unroll
+            for (int c = 0; c < C; ++c) x = fmaf(f[px * C + c], wv[c], x);
+            const float sig = sigmoid_of_logit(x);
+            lg[px] = x;
+            sg[px] = sig;
+            acc[0] += (double)sig * (double)z[px];
+            acc[1] += (double)sig;
+            acc[2] += (double)z[px];
+        }
+        rl_st4(p.logits + px0, lg);
+        if (p.prob) rl_st4(p.prob + px0, sg);
+    }
+    rl_block_store<kRlPart>(acc, p.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kRlPart);
+}
+
+// C = 16, 64: C / 4 adjacent lanes share a pixel (k_head_train_wide's layout: one 16-byte load per lane)
+template <int C>
+__global__ __launch_bounds__(256) void k_head_region_fwd_wide(RlHeadFwdArgs p) {
+    constexpr int G = C / 4, PPW = 64 / G, U = 4;
+    static_assert(C % 4 == 0 && 64 % G == 0, "lane groups");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cq = lane % G, pl = lane / G;
+    const float4 wv = *reinterpret_cast<const float4*>(p.w + 4 * cq);
+    const float bias = p.bias[0];
+    const size_t img = (size_t)blockIdx.y * p.hw;
+    const float* feat = p.feat + img * C;
+    const float* y = p.y + img;
+    double acc[kRlPart] = {0.0, 0.0, 0.0, 0.0};
+    for (int p0 = (blockIdx.x * 4 + wave) * (PPW * U); p0 < p.hw; p0 += gridDim.x * 4 * (PPW * U)) {
+        float4 f[U];
+        float z[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int px = p0 + u * PPW + pl;
+            f[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            z[u] = 0.f;
+            if (px < p.hw) {
+                f[u] = *reinterpret_cast<const float4*>(feat + (size_t)px * C + 4 * cq);
+                z[u] = y[px];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int px = p0 + u * PPW + pl;
+            float x = fmaf(f[u].x, wv.x, fmaf(f[u].y, wv.y, fmaf(f[u].z, wv.z, f[u].w * wv.w)));
+#pragma unroll
+            for (int o = G / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+            x += bias;
+            const float sig = sigmoid_of_logit(x);
+            if (px < p.hw && cq == 0) {
+                p.logits[img + px] = x;
+                if (p.prob) p.prob[img + px] = sig;
+                acc[0] += (double)sig * (double)z[u];
+                acc[1] += (double)sig;
+                acc[2] += (double)z[u];
+            }
+        }
+    }
+    rl_block_store<kRlPart>(acc, p.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kRlPart);
+}
+
+// ------------------------------------------------------------------------------------------------ the sums' finish
+struct RlFinishArgs {
+    const double* part;    // [B][gx][kRlPart]
+    double* stat;          // [B][kRlStat]
+    double* scalars;
+    int B, gx;
+    float lam_r, lam_ce, alpha, beta, smooth;
+    int add_bce;           // the partials carry the weighted BCE sum: add l_ce x it to the loss slot
+};
+
+// one block.  stat[b]: 0 I, 1 P, 2 Y, 3 A, 4 C, 5 BCE sum, 6 1 - T
+__global__ __launch_bounds__(256) void k_region_loss_finish(RlFinishArgs p) {
+    // one wave per (image, value): lane l adds rows l, l + 64, ... in ascending order, then the butterfly -- the same order every run
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int t = wave; t < p.B * kRlPart; t += 4) {
+        const int b = t / kRlPart, k = t % kRlPart;
+        const double* row = p.part + (size_t)b * p.gx * kRlPart + k;
+        double s = 0.0;
+        for (int i = lane; i < p.gx; i += 64) s += row[(size_t)i * kRlPart];
+        s = rl_wave_sum(s);
+        if (lane == 0) p.stat[b * kRlStat + (k < 3 ? k : 5)] = s;
+    }
+    __threadfence_block();
+    __syncthreads();
+    for (int b = threadIdx.x; b < p.B; b += 256) {
+        double* st = p.stat + b * kRlStat;
+        const double a = (double)p.alpha, be = (double)p.beta, s = (double)p.smooth;
+        const double N = st[0] + s;
+        const double D = (1.0 - a - be) * st[0] + a * st[1] + be * st[2] + s;
+        st[3] = (D - (1.0 - a - be) * N) / (D * D);
+        st[4] = a * N / (D * D);
+        st[6] = (D - N) / D;
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = 0.0, bce = 0.0;
+        for (int b = 0; b < p.B; ++b) {
+            r += p.stat[b * kRlStat + 6];
+            bce += p.stat[b * kRlStat + 5];
+        }
+        p.scalars[4] += (double)p.lam_r * r / (double)p.B;
+        if (p.add_bce) p.scalars[3] += (double)p.lam_ce * bce;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ head, backward half
+struct RlHeadTrainArgs {
+    const float* feat;
+    const float* y;
+    const float* logits;
+    const float* w;
+    float* dfeat;
+    const double* stat;
+    const double* scalars;
+    float* partials;       // [gridDim.y * gridDim.x][C + 2]: dW..., db, l_ce x BCE sum
+    dnnca_loss_cfg cfg;
+    double n_label;
+    float gscale;          // 1 / (H W B)
+    float lam_ce, lam_r_b; // l_ce, l_r / B
+    int mask;
+    float alpha;
+    int hw;
+};
+
+// dlogit of one pixel (and the pixel's weighted BCE into *bce when l_ce > 0)
+DEVINL float rl_dlogit(float x, float z, float wgt, float gscale, float lam_ce, float lam_r_b, float Ab, float Cb, float* bce) {
+    const float e = expf(-fabsf(x));
+    const float sig = x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+    float dl = lam_r_b * (Cb - Ab * z) * (sig * (1.0f - sig));
+    if (lam_ce != 0.f) {
+        const float mk = fmaf(z, wgt - 1.0f, 1.0f);
+        *bce = (fmaxf(x, 0.f) - x * z + log1pf(e)) * mk;
+        dl = fmaf(lam_ce, mk * (sig - z) * gscale, dl);
+    } else {
+        *bce = 0.f;
+    }
+    return dl;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void k_head_region_train(RlHeadTrainArgs p) {
+    __shared__ float red[4][C + 2];
+    float wv[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) wv[c] = p.w[c];
+    const float wgt = rl_weight(p.cfg, p.scalars[0], p.n_label);
+    const float Ab = (float)p.stat[blockIdx.y * kRlStat + 3], Cb = (float)p.stat[blockIdx.y * kRlStat + 4];
+    const size_t img = (size_t)blockIdx.y * p.hw;
+    const int n4 = p.hw / 4;
+    float sdw[C], sdb = 0.f, sloss = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) sdw[c] = 0.f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const size_t px0 = img + (size_t)i * 4;
+        float f[4 * C], z[4], lg[4], df[4 * C];
+#pragma unroll
+        for (int v = 0; v < C; ++v) rl_ld4(f + 4 * v, p.feat + px0 * C + 4 * v);
+        rl_ld4(z, p.y + px0);
+        rl_ld4(lg, p.logits + px0);
+#pragma unroll
+        for (int px = 0; px < 4; ++px) {
+            float bce;
+            const float dl = rl_dlogit(lg[px], z[px], wgt, p.gscale, p.lam_ce, p.lam_r_b, Ab, Cb, &bce);
+            sloss += bce;
+            sdb += dl;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float fv = f[px * C + c];
+                sdw[c] = fmaf(fv, dl, sdw[c]);
+                float d = dl * wv[c];
+                if (p.mask) d *= fv > 0.f ? 1.0f : p.alpha;
+                df[px * C + c] = d;
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < C; ++v) rl_st4(p.dfeat + px0 * C + 4 * v, df + 4 * v);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float vals[C + 2];
+#pragma unroll
+    for (int c = 0; c < C; ++c) vals[c] = sdw[c];
+    vals[C] = sdb;
+    vals[C + 1] = sloss * p.lam_ce;
+#pragma unroll
+    for (int k = 0; k < C + 2; ++k) {
+        float v = vals[k];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if (lane == 0) red[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < C + 2) {
+        const int k = threadIdx.x;
+        p.partials[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (C + 2) + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void k_head_region_train_wide(RlHeadTrainArgs p) {
+    constexpr int G = C / 4, PPW = 64 / G, U = 4;
+    static_assert(C % 4 == 0 && 64 % G == 0, "lane groups");
+    __shared__ float red[4][C + 2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cq = lane % G, pl = lane / G;
+    const float4 wv = *reinterpret_cast<const float4*>(p.w + 4 * cq);
+    const float wgt = rl_weight(p.cfg, p.scalars[0], p.n_label);
+    const float Ab = (float)p.stat[blockIdx.y * kRlStat + 3], Cb = (float)p.stat[blockIdx.y * kRlStat + 4];
+    const size_t img = (size_t)blockIdx.y * p.hw;
+    const float* feat = p.feat + img * C;
+    float* dfeat = p.dfeat + img * C;
+    float4 sdw = make_float4(0.f, 0.f, 0.f, 0.f);
+    float sdb = 0.f, sloss = 0.f;
+    for (int p0 = (blockIdx.x * 4 + wave) * (PPW * U); p0 < p.hw; p0 += gridDim.x * 4 * (PPW * U)) {
+        float4 f[U];
+        float z[U], lg[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int px = p0 + u * PPW + pl;
+            f[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            z[u] = lg[u] = 0.f;
+            if (px < p.hw) {
+                f[u] = *reinterpret_cast<const float4*>(feat + (size_t)px * C + 4 * cq);
+                z[u] = p.y[img + px];
+                lg[u] = p.logits[img + px];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int px = p0 + u * PPW + pl;
+            const bool ok = px < p.hw;
+            float bce;
+            float dl = rl_dlogit(lg[u], z[u], wgt, p.gscale, p.lam_ce, p.lam_r_b, Ab, Cb, &bce);
+            if (!ok) dl = 0.f;
+            if (ok && cq == 0) {
+                sloss += bce;
+                sdb += dl;
+            }
+            sdw.x = fmaf(f[u].x, dl, sdw.x); sdw.y = fmaf(f[u].y, dl, sdw.y);
+            sdw.z = fmaf(f[u].z, dl, sdw.z); sdw.w = fmaf(f[u].w, dl, sdw.w);
+            float4 d = make_float4(dl * wv.x, dl * wv.y, dl * wv.z, dl * wv.w);
+            if (p.mask) {
+                d.x *= f[u].x > 0.f ? 1.0f : p.alpha; d.y *= f[u].y > 0.f ? 1.0f : p.alpha;
+                d.z *= f[u].z > 0.f ? 1.0f : p.alpha; d.w *= f[u].w > 0.f ? 1.0f : p.alpha;
+            }
+            if (ok) *reinterpret_cast<float4*>(dfeat + (size_t)px * C + 4 * cq) = d;
+        }
+    }
+#pragma unroll
+    for (int o = G; o < 64; o <<= 1) {
+        sdw.x += __shfl_xor(sdw.x, o, 64); sdw.y += __shfl_xor(sdw.y, o, 64);
+        sdw.z += __shfl_xor(sdw.z, o, 64); sdw.w += __shfl_xor(sdw.w, o, 64);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { sdb += __shfl_xor(sdb, o, 64); sloss += __shfl_xor(sloss, o, 64); }
+    if (lane < G) {
+        red[wave][4 * cq] = sdw.x; red[wave][4 * cq + 1] = sdw.y; red[wave][4 * cq + 2] = sdw.z; red[wave][4 * cq + 3] = sdw.w;
+    }
+    if (lane == 0) { red[wave][C] = sdb; red[wave][C + 1] = sloss * p.lam_ce; }
+    __syncthreads();
+    if (threadIdx.x < C + 2) {
+        const int k = threadIdx.x;
+        p.partials[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (C + 2) + k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ from the logits
+struct RlLogitArgs {
+    const float* logits;   // [B, hw]
+    const float* y;
+    float* dlogits;        // region_loss_grad: null without a backward pass
+    float* prob;
+    double* part;          // region_sums
+    const double* stat;    // region_loss_grad
+    const double* scalars;
+    dnnca_loss_cfg cfg;
+    double n_label;
+    float gscale, lam_ce, lam_r_b;
+    int hw;
+};
+
+// VEC: hw is a multiple of 4 -- one thread = 4 pixels, 16-byte accesses; else one pixel
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_region_sums(RlLogitArgs p) {
+    constexpr int PX = VEC ? 4 : 1;
+    const float wgt = rl_weight(p.cfg, p.scalars[0], p.n_label);
+    const size_t img = (size_t)blockIdx.y * p.hw;
+    const int n = p.hw / PX;
+    double acc[kRlPart] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const size_t px0 = img + (size_t)i * PX;
+        float x[PX], z[PX];
+        if constexpr (VEC) {
+            rl_ld4(x, p.logits + px0);
+            rl_ld4(z, p.y + px0);
+        } else {
+            x[0] = p.logits[px0];
+            z[0] = p.y[px0];
+        }
+#pragma unroll
+        for (int k = 0; k < PX; ++k) {
+            const float e = expf(-fabsf(x[k]));
+            const float sig = x[k] >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+            acc[0] += (double)sig * (double)z[k];
+            acc[1] += (double)sig;
+            acc[2] += (double)z[k];
+            if (p.lam_ce != 0.f) {
+                const float mk = fmaf(z[k], wgt - 1.0f, 1.0f);
+                acc[3] += (double)((fmaxf(x[k], 0.f) - x[k] * z[k] + log1pf(e)) * mk);
+            }
+        }
+    }
+    rl_block_store<kRlPart>(acc, p.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kRlPart);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_region_loss_grad(RlLogitArgs p) {
+    constexpr int PX = VEC ? 4 : 1;
+    const float wgt = rl_weight(p.cfg, p.scalars[0], p.n_label);
+    const float Ab = (float)p.stat[blockIdx.y * kRlStat + 3], Cb = (float)p.stat[blockIdx.y * kRlStat + 4];
+    const size_t img = (size_t)blockIdx.y * p.hw;
+    const int n = p.hw / PX;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const size_t px0 = img + (size_t)i * PX;
+        float x[PX], z[PX], dl[PX], sg[PX];
+        if constexpr (VEC) {
+            rl_ld4(x, p.logits + px0);
+            rl_ld4(z, p.y + px0);
+        } else {
+            x[0] = p.logits[px0];
+            z[0] = p.y[px0];
+        }
+#pragma unroll
+        for (int k = 0; k < PX; ++k) {
+            float bce;
+            dl[k] = rl_dlogit(x[k], z[k], wgt, p.gscale, p.lam_ce, p.lam_r_b, Ab, Cb, &bce);
+            sg[k] = sigmoid_of_logit(x[k]);
+        }
+        if constexpr (VEC) {
+            if (p.dlogits) rl_st4(p.dlogits + px0, dl);
+            rl_st4(p.prob + px0, sg);
+        } else {
+            if (p.dlogits) p.dlogits[px0] = dl[0];
+            p.prob[px0] = sg[0];
+        }
+    }
+}
+
+// blocks per image of a launch whose block takes `per_block` pixels per trip: every image's partial rows fit kRlMaxBlocks
+int rl_blocks_per_image(int hw, int per_block, int B) {
+    const int want = (hw + per_block - 1) / per_block;
+    return std::max(1, std::min(want, kRlMaxBlocks / B));
+}
+
+void rl_finish(Model* m, int B, int gx, bool add_bce) {
+    const dnnca_region_loss& c = m->region_loss.cfg;
+    RlFinishArgs f;
+    f.part = m->region_loss.ws + (size_t)m->desc.max_batch * kRlStat;
+    f.stat = m->region_loss.ws;
+    f.scalars = m->scalars;
+    f.B = B;
+    f.gx = gx;
+    f.lam_r = c.region_weight;
+    f.lam_ce = c.crossentropy_weight;
+    f.alpha = c.alpha;
+    f.beta = c.beta;
+    f.smooth = c.smooth;
+    f.add_bce = add_bce ? 1 : 0;
+    LAUNCH(m, "region_loss_finish", 8.0 * kRlPart * B * gx, 0, hipLaunchKernelGGL(k_region_loss_finish, dim3(1), dim3(256), 0, m->stream, f));
+    if (!m->dry) m->region_loss.sums_batch = B;
+}
+
+}  // namespace
+
+const char* region_loss_invalid(const dnnca_region_loss& c) {
+    if (!(std::isfinite(c.region_weight) && c.region_weight > 0.f)) return "region_weight must be > 0";
+    if (!(std::isfinite(c.crossentropy_weight) && c.crossentropy_weight >= 0.f)) return "crossentropy_weight must be >= 0";
+    if (!(std::isfinite(c.alpha) && c.alpha >= 0.f) || !(std::isfinite(c.beta) && c.beta >= 0.f)) return "alpha and beta must be >= 0";
+    if (!(c.alpha + c.beta > 0.f)) return "alpha + beta must be > 0";
+    if (!(std::isfinite(c.smooth) && c.smooth > 0.f)) return "smooth must be > 0";
+    return nullptr;
+}
+
+int region_loss_prepare(Model* m) {
+    if (m->region_loss.ws) return DNNCA_OK;
+    if (m->desc.max_batch > kRlMaxBlocks) { set_error("region loss: max_batch %d above %d", m->desc.max_batch, kRlMaxBlocks); return DNNCA_EINVAL; }
+    const size_t n = (size_t)m->desc.max_batch * kRlStat + (size_t)kRlMaxBlocks * kRlPart;
+    DN_TRY(m->alloc((void**)&m->region_loss.ws, n * 8));
+    HIP_TRY(hipMemsetAsync(m->region_loss.ws, 0, n * 8, m->stream));
+    return DNNCA_OK;
+}
+
+bool region_loss_head_train(Model* m, int B, Op& o, const float* y, const dnnca_loss_cfg& cfg, float gscale) {
+    if (!fast_head_supported(m, o) || !m->region_loss.ws) return false;
+    const dnnca_region_loss& rc = m->region_loss.cfg;
+    const int C = o.inA.d.C, hw = o.inA.d.H * o.inA.d.W;
+    // pixels a block takes per trip: 256 threads x 4 pixels (C = 3); 4 waves x (64 / (C / 4)) pixels x 4 loads (wide)
+    const int per_block = C == 3 ? 1024 : 4 * (64 / (C / 4)) * 4;
+    const int gx = rl_blocks_per_image(hw, per_block, B);
+    const double npix = (double)B * hw, fb = 4.0 * npix * C;
+    const bool pm = m->train_metrics_on();
+    RlHeadFwdArgs a;
+    a.feat = o.inA.d.p;
+    a.y = y;
+    a.w = m->p + o.w_off;
+    a.bias = m->p + o.b_off;
+    a.logits = m->logits;
+    a.prob = pm ? m->prob : nullptr;
+    a.part = m->region_loss.ws + (size_t)m->desc.max_batch * kRlStat;
+    a.hw = hw;
+    RlHeadTrainArgs t;
+    t.feat = o.inA.d.p;
+    t.y = y;
+    t.logits = m->logits;
+    t.w = m->p + o.w_off;
+    t.dfeat = o.inA.g.p;
+    t.stat = m->region_loss.ws;
+    t.scalars = m->scalars;
+    t.partials = m->head_partials;
+    t.cfg = cfg;
+    t.n_label = npix;
+    t.gscale = gscale;
+    t.lam_ce = rc.crossentropy_weight;
+    t.lam_r_b = rc.region_weight / (float)B;
+    t.mask = o.maskA;
+    t.alpha = o.mask_alpha;
+    t.hw = hw;
+    const dim3 grid(gx, B);
+#define RL_HEAD_CASE(c, FWD, TRAIN)                                                                                           \
+    if (C == c) {                                                                                                              \
+        LAUNCH(m, "head_region_fwd_" #c, fb + 4.0 * npix * (pm ? 3 : 2), 2.0 * npix * c + 12.0 * npix,                         \
+               hipLaunchKernelGGL(FWD<c>, grid, dim3(256), 0, m->stream, a));                                                  \
+        rl_finish(m, B, gx, false);                                                                                            \
+        LAUNCH(m, "head_region_train_" #c, 2 * fb + 8.0 * npix, 4.0 * npix * c + 30.0 * npix,                                  \
+               hipLaunchKernelGGL(TRAIN<c>, grid, dim3(256), 0, m->stream, t));                                                \
+        fast_head_partials_done(m, c, gx * B, m->g + o.w_off, m->g + o.b_off);                                                 \
+        return true;                                                                                                           \
+    }
+    RL_HEAD_CASE(3, k_head_region_fwd, k_head_region_train)
+    RL_HEAD_CASE(16, k_head_region_fwd_wide, k_head_region_train_wide)
+    RL_HEAD_CASE(64, k_head_region_fwd_wide, k_head_region_train_wide)
+#undef RL_HEAD_CASE
+    return false;
+}
+
+int region_loss_from_logits(Model* m, int B, const float* y, const dnnca_loss_cfg& cfg, float gscale, float* dlogits) {
+    if (!m->region_loss.ws) { set_error("internal: region loss without its workspace"); return DNNCA_ESTATE; }
+    const dnnca_region_loss& rc = m->region_loss.cfg;
+    const int hw = m->outH * m->outW;
+    const bool vec = hw % 4 == 0;
+    const int gx = rl_blocks_per_image(hw, vec ? 1024 : 256, B);
+    const double npix = (double)B * hw;
+    RlLogitArgs a;
+    a.logits = m->logits;
+    a.y = y;
+    a.dlogits = dlogits;
+    a.prob = m->prob;
+    a.part = m->region_loss.ws + (size_t)m->desc.max_batch * kRlStat;
+    a.stat = m->region_loss.ws;
+    a.scalars = m->scalars;
+    a.cfg = cfg;
+    a.n_label = npix;
+    a.gscale = gscale;
+    a.lam_ce = rc.crossentropy_weight;
+    a.lam_r_b = rc.region_weight / (float)B;
+    a.hw = hw;
+    const dim3 grid(gx, B);
+    if (vec) LAUNCH(m, "region_sums", 8.0 * npix, 20.0 * npix, hipLaunchKernelGGL(k_region_sums<true>, grid, dim3(256), 0, m->stream, a));
+    else LAUNCH(m, "region_sums", 8.0 * npix, 20.0 * npix, hipLaunchKernelGGL(k_region_sums<false>, grid, dim3(256), 0, m->stream, a));
+    rl_finish(m, B, gx, true);
+    const double gb = 4.0 * npix * (dlogits ? 4 : 3);
+    if (vec) LAUNCH(m, "region_loss_grad", gb, 30.0 * npix, hipLaunchKernelGGL(k_region_loss_grad<true>, grid, dim3(256), 0, m->stream, a));
+    else LAUNCH(m, "region_loss_grad", gb, 30.0 * npix, hipLaunchKernelGGL(k_region_loss_grad<false>, grid, dim3(256), 0, m->stream, a));
+    return DNNCA_OK;
+}
+
+}  // namespace dnnca

@@ -143,6 +143,9 @@ struct Model {
     // single-replica training steps: the step outputs are written by the Adam launch instead of a launch of their own
     struct FinalizePending { bool on = false; dnnca_loss_cfg cfg; double n_label = 0, inv_batch_hw = 0; } fin_pending;
     float* y_smooth = nullptr;           // smoothed labels of the step (label_smoothing, utils/losses.py:62-67)
+    // region (Tversky) term of the loss (dnnca_model_set_region_loss, kernels_region_loss.hip).  ws: per image kRlStat doubles
+    // (I, P, Y, A, C of the last step), then the block partials of the step's sums; sums_batch: images of the last step that wrote it
+    struct RegionLoss { bool on = false; dnnca_region_loss cfg{}; double* ws = nullptr; int sums_batch = 0; } region_loss;
     void* warp_scratch = nullptr;        // control points + spline weights of dnnca_warp_f32
     size_t warp_scratch_bytes = 0;
     void* aug_scratch = nullptr;         // per-image augmentation draws + channel sums (kernels_aug.hip)

@@ -15,6 +15,7 @@
 #include "fast.h"
 #include "kernels.h"
 #include "region.h"
+#include "region_loss.h"
 #include "sens.h"
 #include "attr.h"
 
@@ -80,9 +81,10 @@ StepSwitches step_switches() {
 }
 
 // train step / its plan dump: the head is to ride in the epilogue of the conv that feeds it (Model::forward decides whether it can).
-// Label smoothing blurs the labels in loss_and_backward first: then the head cannot run inside the forward pass.
+// Label smoothing blurs the labels in loss_and_backward first: then the head cannot run inside the forward pass.  Nor can it with
+// the region loss: a pixel's gradient needs the sums over its whole image (kernels_region_loss.hip).
 static bool head_in_conv_requested(const Model* M, const dnnca_loss_cfg& cfg) {
-    return !cfg.label_smoothing && M->merged_launches() && !M->sw.no_head_in_conv;
+    return !cfg.label_smoothing && !M->region_loss.on && M->merged_launches() && !M->sw.no_head_in_conv;
 }
 
 Model::~Model() {
@@ -981,7 +983,19 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
     // local mean; the cross-rank 1/world is applied to the all-reduced gradient in the optimizer step.
     float gscale = (float)(1.0 / ((double)outH * outW * B));
     bool head_done = false;
-    if (head_was_in_conv) {
+    if (region_loss.on) {
+        // the region (Tversky) term: sums per image first, then the gradient (kernels_region_loss.hip)
+        if (head_was_in_conv) { set_error("internal: region loss behind a head that ran in the forward pass"); return DNNCA_ESTATE; }
+        if (backward && head_deferred) {
+            if (!region_loss_head_train(this, B, ops.back(), y_dev, cfg, gscale)) {
+                set_error("internal: deferred head has no region-loss kernel");
+                return DNNCA_ESTATE;
+            }
+            head_done = true;
+        } else {
+            DN_TRY(region_loss_from_logits(this, B, y_dev, cfg, gscale, backward ? dlogits : nullptr));
+        }
+    } else if (head_was_in_conv) {
         head_done = true;
     } else if (backward && head_deferred) {
         Op& ho = ops.back();
@@ -2156,6 +2170,40 @@ int dnnca_get_prob(void* model, float* prob_out, int64_t n_pixels) {
     if (!prob_out || n_pixels < 0 || n_pixels > (int64_t)M->desc.max_batch * M->outH * M->outW) { set_error("bad probability read"); return DNNCA_EINVAL; }
     HIP_TRY(hipMemcpyAsync(prob_out, M->prob, (size_t)n_pixels * 4, hipMemcpyDeviceToHost, M->stream));
     HIP_TRY(hipStreamSynchronize(M->stream));
+    return DNNCA_OK;
+}
+
+// ---- region (Tversky) term of the loss (kernels_region_loss.hip) ---------------------------------------------------------
+int dnnca_model_set_region_loss(void* model, const dnnca_region_loss* cfg) {
+    MODEL(model);
+    if (cfg) {
+        if (const char* why = region_loss_invalid(*cfg)) { set_error("region loss: %s", why); return DNNCA_EINVAL; }
+        // left out for want of a reference: the bf16-emulating oracle has no statement of this loss to test a bf16 step against
+        if (M->desc.dtype != DNNCA_F32) { set_error("region loss needs a dtype f32 model (this one is bf16)"); return DNNCA_EINVAL; }
+    }
+    HIP_TRY(hipStreamSynchronize(M->stream));          // steps in flight keep the loss they were enqueued with
+    M->region_loss.on = false;
+    M->region_loss.sums_batch = 0;
+    if (!cfg) return DNNCA_OK;
+    DN_TRY(region_loss_prepare(M));
+    M->region_loss.cfg = *cfg;
+    M->region_loss.on = true;
+    return DNNCA_OK;
+}
+
+int dnnca_region_loss_sums(void* model, int batch, double* out) {
+    MODEL(model);
+    if (!out) { set_error("null region-loss sums"); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
+    if (!M->region_loss.ws || M->region_loss.sums_batch < batch) {
+        set_error("no step with the region loss has run on %d images (dnnca_model_set_region_loss)", batch);
+        return DNNCA_ESTATE;
+    }
+    std::vector<double> st((size_t)batch * kRlStat);
+    HIP_TRY(hipMemcpyAsync(st.data(), M->region_loss.ws, st.size() * 8, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    for (int b = 0; b < batch; ++b)
+        for (int k = 0; k < 3; ++k) out[b * 3 + k] = st[(size_t)b * kRlStat + k];
     return DNNCA_OK;
 }
 

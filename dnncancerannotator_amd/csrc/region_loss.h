@@ -1,0 +1,24 @@
+// region_loss.h -- the region (Tversky / Dice) term of the training loss: launchers of kernels_region_loss.hip.
+#pragma once
+#include "model.h"
+
+namespace dnnca {
+
+constexpr int kRlStat = 8;             // doubles per image in Model::region_loss.ws: I, P, Y, A, C (three spare)
+constexpr int kRlMaxBlocks = 2048;     // blocks of a sums / head launch over the whole batch (Model::head_partials holds as many rows)
+constexpr int kRlPart = 4;             // doubles per block partial: I, P, Y, weighted BCE sum
+
+// nullptr when the values are accepted, else what is wrong with them
+const char* region_loss_invalid(const dnnca_region_loss& c);
+// the model's workspace (allocated once, for max_batch)
+int region_loss_prepare(Model* m);
+
+// Train step, head of 3 / 16 / 64 channels still to run (Model::head_deferred): head_region_fwd_<C>, region_loss_finish,
+// head_region_train_<C>; the head's gradient partials go where fast_head_train puts them (head_pending or head_reduce).
+// false: no kernel for this head.
+bool region_loss_head_train(Model* m, int B, Op& head, const float* y, const dnnca_loss_cfg& cfg, float gscale);
+// From the logits buffer: region_sums, region_loss_finish, region_loss_grad (dlogits may be null: no backward pass); always
+// writes the probabilities and adds the weighted BCE sum to the step's scalar block.
+int region_loss_from_logits(Model* m, int B, const float* y, const dnnca_loss_cfg& cfg, float gscale, float* dlogits);
+
+}  // namespace dnnca

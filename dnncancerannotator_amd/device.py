@@ -435,6 +435,30 @@ class DeviceModel:
         check(self.lib.dnnca_get_prob(self.handle, fptr(out), out.size))
         return out
 
+    # ---- region (Tversky / Dice) term of the loss (losses.TverskyCrossentropy) ----------------------------------------
+    def set_region_loss(self, cfg=None, **kw):
+        """every later train / eval step adds region_weight * mean_b (1 - Tversky index of image b) to crossentropy_weight * the
+        weighted cross-entropy (dnnca_model_set_region_loss).  cfg: a dict of region_weight, crossentropy_weight, alpha, beta,
+        smooth (or the same as keywords; defaults 1, 1, 0.5, 0.5, 1); None with no keyword switches it off"""
+        if cfg is None and not kw:
+            check(self.lib.dnnca_model_set_region_loss(self.handle, None))
+            return
+        v = dict(region_weight=1.0, crossentropy_weight=1.0, alpha=0.5, beta=0.5, smooth=1.0)
+        given = dict(cfg or {}, **kw)
+        unknown = sorted(set(given) - set(v))
+        if unknown:
+            raise ValueError('set_region_loss: unknown keys %s' % unknown)
+        v.update(given)
+        c = _lib.RegionLoss(*(float(v[k]) for k in ('region_weight', 'crossentropy_weight', 'alpha', 'beta', 'smooth')))
+        check(self.lib.dnnca_model_set_region_loss(self.handle, C.byref(c)))
+
+    def region_loss_sums(self, batch=None):
+        """[batch, 3] float64: I = sum p y, P = sum p, Y = sum y per image of the last step that ran with the region loss"""
+        batch = self.max_batch if batch is None else int(batch)
+        out = np.empty((batch, 3), np.float64)
+        check(self.lib.dnnca_region_loss_sums(self.handle, batch, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
     def last_step_out(self):
         out = _lib.StepOut()
         check(self.lib.dnnca_last_step_out(self.handle, C.byref(out)))

@@ -205,7 +205,14 @@ class TFKerasModel:
         self._input_shape = list(shape[1:])
         self.device_model = self.model.build([per_rank] + self._input_shape, seed=0)
         self.device_model.set_adam(**self.adam)
+        self._set_region_loss(self.device_model)
         self._join_ranks()
+
+    def _set_region_loss(self, dm):
+        """loss: TverskyCrossentropy / DiceCrossentropy -- the region term is stored in the device model once, and every later
+        train / eval step reads it there; any other loss leaves the model as it was built (no call)"""
+        if isinstance(self.loss, custom_losses.TverskyCrossentropy):
+            dm.set_region_loss(self.loss.region_cfg())
 
     def _join_ranks(self):
         if self.ctx.world > 1:
@@ -235,6 +242,7 @@ class TFKerasModel:
             bigger.set_state(state)
         bigger.set_opt_state(m, v, it)
         bigger.set_adam(**self.adam)
+        self._set_region_loss(bigger)
         self.device_model = bigger
         return True
 

@@ -30,7 +30,56 @@ class WeightedCrossentropy:
                     label_smoothing_sigma=float(self.label_smoothing_sigma))
 
 
-_REGISTRY = {'WeightedCrossentropy': WeightedCrossentropy, 'weighted_crossentropy': WeightedCrossentropy}
+class TverskyCrossentropy(WeightedCrossentropy):
+    """crossentropy_weight * weighted cross-entropy + region_weight * (1 - Tversky index), the index per image:
+        T = (I + s) / ((1 - alpha - beta) I + alpha P + beta Y + s),  I = sum p y, P = sum p, Y = sum y over the image's pixels
+    alpha weighs the false positives P - I, beta the false negatives Y - I; alpha = beta = 0.5 is soft Dice.  Not in the reference:
+    every key of WeightedCrossentropy keeps its meaning, and the region term travels beside dnnca_loss_cfg (region_cfg)."""
+
+    name = 'tversky_crossentropy'
+
+    def __init__(self, region_weight=1.0, crossentropy_weight=1.0, alpha=0.5, beta=0.5, smooth=1.0, **kwargs):
+        super().__init__(**kwargs)
+        vals = dict(region_weight=region_weight, crossentropy_weight=crossentropy_weight, alpha=alpha, beta=beta, smooth=smooth)
+        for k, v in vals.items():
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float('inf'), float('-inf')):
+                raise ValueError('%s: %s must be a finite number, got %r' % (type(self).__name__, k, v))
+        if not region_weight > 0:
+            raise ValueError('region_weight must be > 0, got %r' % (region_weight,))
+        if not crossentropy_weight >= 0:
+            raise ValueError('crossentropy_weight must be >= 0, got %r' % (crossentropy_weight,))
+        if not (alpha >= 0 and beta >= 0):
+            raise ValueError('alpha and beta must be >= 0, got %r and %r' % (alpha, beta))
+        if not alpha + beta > 0:
+            raise ValueError('alpha + beta must be > 0')
+        if not smooth > 0:
+            raise ValueError('smooth must be > 0, got %r' % (smooth,))
+        self.region_weight, self.crossentropy_weight = float(region_weight), float(crossentropy_weight)
+        self.alpha, self.beta, self.smooth = float(alpha), float(beta), float(smooth)
+
+    def region_cfg(self):
+        """what DeviceModel.set_region_loss takes"""
+        return dict(region_weight=self.region_weight, crossentropy_weight=self.crossentropy_weight, alpha=self.alpha,
+                    beta=self.beta, smooth=self.smooth)
+
+    def get_config(self):
+        return dict(super().get_config(), **self.region_cfg())
+
+
+class DiceCrossentropy(TverskyCrossentropy):
+    """TverskyCrossentropy at alpha = beta = 0.5: 1 - (2 I + 2 s) / (P + Y + 2 s), soft Dice"""
+
+    name = 'dice_crossentropy'
+
+    def __init__(self, **kwargs):
+        if kwargs.get('alpha', 0.5) != 0.5 or kwargs.get('beta', 0.5) != 0.5:
+            raise ValueError('DiceCrossentropy is alpha = beta = 0.5; use TverskyCrossentropy for other values')
+        super().__init__(**kwargs)
+
+
+_REGISTRY = {'WeightedCrossentropy': WeightedCrossentropy, 'weighted_crossentropy': WeightedCrossentropy,
+             'TverskyCrossentropy': TverskyCrossentropy, 'tversky_crossentropy': TverskyCrossentropy,
+             'DiceCrossentropy': DiceCrossentropy, 'dice_crossentropy': DiceCrossentropy}
 
 
 def get(identifier):

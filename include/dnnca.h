@@ -278,6 +278,30 @@ int dnnca_staged_confusion(void* model, int slot, dnnca_confusion* out);
  * floats [B, H, W] to host; waits for the stream */
 int dnnca_get_prob(void* model, float* prob_out, int64_t n_pixels);
 
+/* ---- region (Tversky / Dice) term of the training loss ----------------------------------------------------------------------
+ * Per image b, with p = sigmoid(logit), y the step's label (the blurred one under label_smoothing) and sums over that image's
+ * H x W pixels only: I = sum p y, P = sum p, Y = sum y,
+ *   N = I + smooth,  D = (1 - alpha - beta) I + alpha P + beta Y + smooth,  T = N / D    (alpha = beta = 0.5: soft Dice)
+ *   loss = mean_b [ crossentropy_weight * wBCE_b + region_weight * (1 - T_b) ] (+ L2)
+ * where wBCE_b is the weighted cross-entropy of dnnca_loss_cfg as without this call.  The configuration is stored in the model and
+ * read by every later train / eval step of every entry point (host, _dev, _staged); cfg == NULL switches it off and the steps run
+ * the launches they ran before.  With it on, a train step declines the head-in-conv / tail3 fusions (as label_smoothing does) and
+ * runs head_region_fwd_<C>, region_loss_finish, head_region_train_<C> (heads of 3, 16, 64 channels) or, from the logits,
+ * region_sums, region_loss_finish, region_loss_grad (eval steps, DNNCA generic flag, any other head).  No float atomics: sums, loss
+ * and gradients are bit-identical from run to run.  Every statistic is per image: nothing changes under data parallel.
+ * DNNCA_EINVAL unless region_weight > 0, crossentropy_weight >= 0, alpha >= 0, beta >= 0, alpha + beta > 0, smooth > 0 (all
+ * finite), and for dtype bf16 models.  The call waits for the model's stream. */
+typedef struct dnnca_region_loss {
+    float region_weight;        /* lambda_r */
+    float crossentropy_weight;  /* lambda_ce; 0 skips the cross-entropy arithmetic (label statistics and assertions stay) */
+    float alpha;                /* weight of the false positives P - I */
+    float beta;                 /* weight of the false negatives Y - I */
+    float smooth;               /* s */
+} dnnca_region_loss;
+int dnnca_model_set_region_loss(void* model, const dnnca_region_loss* cfg);
+/* I, P, Y per image of the last train / eval step that ran with the region loss on (out: batch x 3 doubles); waits for the stream */
+int dnnca_region_loss_sums(void* model, int batch, double* out);
+
 /* pixel TP/FP/FN/TN of the last forward/eval probabilities against y at n thresholds (metrics.yaml:2-23 pixel metrics;
  * utils/metrics.py:37-77 FBetaScore builds on them). y_hw is a host buffer [B,H,W]. */
 int dnnca_pixel_confusion(void* model, const float* y_hw, int batch, const float* thresholds, int n, dnnca_confusion* out);

@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""region_loss_rate.py -- what the region (Tversky / Dice) term of the loss costs: ms per train step at 8 x 512 x 512 (f32, device-
+resident batches, DeviceModel.train_step_dev) for configs/unet.yaml, mulmo_unet.yaml and unet_big.yaml without and with
+DeviceModel.set_region_loss, and the device time of every launch that the region loss adds or changes (dnnca_profile_*).
+
+The plain step is also measured on a second library, built from the parent commit
+    git stash / git checkout <parent>;  DNNCA_BUILD_TAG=parent python -m dnncancerannotator_amd.build;  come back
+(-> dnncancerannotator_amd/libdnnca_parent.so), alternated with this build's in one visit: the untouched path must be untouched.
+Every arm is a child process of its own (a library is chosen when it is loaded, DNNCA_LIB), one at a time.
+
+    python tools/region_loss_rate.py [--steps 100] [--only unet] [--parent-lib PATH] [--out profiles/region_loss_rate.txt]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+BASE = dict(rate=2, kernel_size=3, conv_stride=1, padding='same')
+# name -> (arch, options, channels, batch, size): the shipped configs at their train batch
+CONFIGS = {
+    'unet': ('unet', dict(BASE, n_filters_first=3, n_downsample=3, bn=False), 1, 8, 512),
+    'mulmo_unet': ('mulmo', dict(BASE, n_filters_first=16, n_downsample=4, bn=True), 3, 8, 512),
+    'unet_big': ('unet', dict(BASE, n_filters_first=64, n_downsample=4, bn=True), 1, 8, 512),
+}
+CHANGED = ('head_region', 'region_', 'head_reduce', 'head_train', 'tail3', 'pgfwd_head', 'g_loss', 'pg_fold', 'fold_adam')
+
+
+def child(name, region, steps, profile):
+    from dnncancerannotator_amd import _lib, device as dev
+    from dnncancerannotator_amd.synthetic import synthetic_batch
+    if os.environ.get('DNNCA_LIB') and not region:       # the parent build has no region-loss entry points to bind
+        for sym in ('dnnca_model_set_region_loss', 'dnnca_region_loss_sums'):
+            _lib.SIGNATURES.pop(sym, None)
+    arch, opts, C, B, S = CONFIGS[name]
+    dev.init_device(0)
+    m = dev.DeviceModel(arch, C, S, S, B, **opts)
+    m.init_glorot(seed=2)
+    if region:
+        m.set_region_loss({})
+    x, y = synthetic_batch(B, S, S, C, seed_x=100, seed_y=200)
+    xb, yb = dev.DeviceBuffer(x), dev.DeviceBuffer(y)
+    cfg = m.loss_cfg(weight_mul=3.0)
+    for _ in range(20):
+        m.train_step_dev(xb, yb, B, 1e-3, cfg)
+    m.sync()
+    res = dict(name=name, region=region)
+    if profile:
+        m.profile_reset()
+        m.profile_enable(1)
+        for _ in range(steps):
+            m.train_step_dev(xb, yb, B, 1e-3, cfg)
+        m.sync()
+        res['kernels'] = [(k, n / steps, ms / n * 1e3) for k, n, ms, by, fl in m.profile() if n and k.startswith(CHANGED)]
+        res['plan'] = [r[0] for r in m.plan()]
+    else:
+        best = None
+        for _ in range(3):
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                m.train_step_dev(xb, yb, B, 1e-3, cfg)
+            m.sync()
+            dt = (time.perf_counter() - t0) / steps * 1e3
+            best = dt if best is None else min(best, dt)
+        res['ms'] = best
+    m.close()
+    print('RESULT ' + json.dumps(res), flush=True)
+
+
+def run_child(name, region, steps, profile=False, lib=None):
+    env = dict(os.environ)
+    if lib:
+        env['DNNCA_LIB'] = lib
+    cmd = [sys.executable, os.path.abspath(__file__), '--child', name, '--steps', str(steps)] + (['--region'] if region else []) + \
+        (['--profile'] if profile else [])
+    out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
+    if out.returncode != 0:
+        raise RuntimeError('%s failed (%d): %s' % (' '.join(cmd), out.returncode, out.stderr[-2000:]))
+    return json.loads([l for l in out.stdout.splitlines() if l.startswith('RESULT ')][-1][7:])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=100)
+    ap.add_argument('--only', default=None)
+    ap.add_argument('--parent-lib', default=os.path.join(ROOT, 'dnncancerannotator_amd', 'libdnnca_parent.so'))
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'region_loss_rate.txt'))
+    ap.add_argument('--child', default=None)
+    ap.add_argument('--region', action='store_true')
+    ap.add_argument('--profile', action='store_true')
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child, a.region, a.steps, a.profile)
+    parent = a.parent_lib if os.path.exists(a.parent_lib) else None
+    lines = ['region loss: ms per train step at 8 x 512 x 512 f32, %d steps x 3 (best), device-resident batches' % a.steps]
+    if not parent:
+        lines.append('parent-commit library %s not found: the plain step on the parent build was not measured' % a.parent_lib)
+    for name in CONFIGS:
+        if a.only and name != a.only:
+            continue
+        plain, par, reg = [], [], []
+        for _ in range(2):                       # alternated: drift shows as a difference between the two runs of an arm
+            if parent:
+                par.append(run_child(name, False, a.steps, lib=parent)['ms'])
+            plain.append(run_child(name, False, a.steps)['ms'])
+            reg.append(run_child(name, True, a.steps)['ms'])
+        fmt = lambda v: ' '.join('%.4f' % t for t in v)      # noqa: E731
+        lines.append('%-11s plain %.4f ms (%s)%s  region loss %.4f ms (%s)  +%.1f us per step' % (
+            name, min(plain), fmt(plain), '  parent build %.4f ms (%s)' % (min(par), fmt(par)) if par else '', min(reg), fmt(reg),
+            (min(reg) - min(plain)) * 1e3))
+        for region in (False, True):
+            r = run_child(name, region, 40, profile=True)
+            for k, per_step, us in sorted(r['kernels']):
+                lines.append('  %-6s %-24s %4.1f launches per step  %8.2f us per launch' % ('region' if region else 'plain', k, per_step, us))
+        print('\n'.join(lines[-12:]), flush=True)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write('\n'.join(lines) + '\n')
+    print('wrote', a.out)
+
+
+if __name__ == '__main__':
+    main()
