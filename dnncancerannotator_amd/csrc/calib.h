@@ -1,7 +1,7 @@
 // calib.h -- host-side launchers of kernels_calib.hip (reliability table, NLL at a set of temperatures, temperature scaling); the
 // definitions the kernels share with tests/calib_oracle.py are at the top of that file.  All planes are device [slices, hw] float32.
 #pragma once
-#include "common.h"
+#include "model.h"
 
 namespace dnnca {
 
@@ -21,5 +21,14 @@ void g_calib_nll(hipStream_t s, const float* prob, const float* y, int slices, s
 void g_calib_nll_sum(hipStream_t s, const double* part, int slices, size_t hw, int nt, double* out);
 // dst[i] = the probability src[i] at `temperature`; dst may be src
 void g_prob_temperature(hipStream_t s, const float* src, float* dst, size_t n, float temperature);
+
+// ---- the host side of dnnca_calibration and dnnca_prob_temperature: device planes in, host tables out -----------------------------
+// prob, y: device [batch, hw], batch <= 65535.  calib_bins and, with nt > 0 host `temperatures`, calib_nll and calib_nll_sum in the
+// model's calibration workspace (grown on demand).  bins (host [batch][n_bins]), totals (host [batch]: every slice's pixels and sums
+// over its bins, and its squares) and nll (host [batch][nt]; not touched with nt == 0) are written.  Synchronises
+int calibration(Model* M, const float* prob, const float* y, int batch, size_t hw, int n_bins, const float* temperatures, int nt,
+                dnnca_calib_bin* bins, dnnca_calib_total* totals, double* nll);
+// prob_temperature on n device floats, src -> dst (dst may be src); out_hw (host, or nullptr) receives a copy of dst.  Synchronises
+int prob_temperature(Model* M, const float* src, float* dst, size_t n, float temperature, float* out_hw);
 
 }  // namespace dnnca

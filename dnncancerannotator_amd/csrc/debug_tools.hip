@@ -1,9 +1,9 @@
 // debug_tools.hip -- development aids (NOT part of include/dnnca.h and not used by the product path):
 // micro-benchmarks that calibrate what the conv kernels can expect from the f32 matrix pipe, a read-back of the BatchNorm
 // reduction table for the tests, and the residual-join kernels on caller-supplied tensors.
+#include "abi.h"
 #include "fast.h"
 #include "kernels.h"
-#include "model.h"
 #include <vector>
 
 using namespace dnnca;
@@ -35,11 +35,6 @@ __global__ __launch_bounds__(512) void k_mfma_rate(float* out, int iters) {
     for (int c = 0; c < NCH; ++c) s += acc[c][0] + acc[c][1] + acc[c][2] + acc[c][3];
     out[blockIdx.x * 512 + threadIdx.x] = s;
 }
-
-
-#define MODEL(h)                                             \
-    Model* M = reinterpret_cast<Model*>(h);                  \
-    if (!M) { set_error("null model handle"); return DNNCA_EINVAL; }
 
 extern "C" {
 

@@ -196,4 +196,71 @@ void g_prob_temperature(hipStream_t s, const float* src, float* dst, size_t n, f
     hipLaunchKernelGGL(k_prob_temperature, dim3((unsigned)blocks), dim3(CB), 0, s, src, dst, n, (double)temperature);
 }
 
+// workspace: the bin table, the squares (both zeroed), 1 / T, the sums per slice and temperature, the block partials
+int calibration(Model* M, const float* prob, const float* y, int batch, size_t hw, int n_bins, const float* temperatures, int nt,
+                dnnca_calib_bin* bins, dnnca_calib_total* totals, double* nll) {
+    const size_t n = (size_t)batch * hw;
+    int runs = 0, blocks = 0;
+    calib_nll_shape(hw, &runs, &blocks);
+    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t bins_bytes = (size_t)batch * n_bins * sizeof(dnnca_calib_bin), sq_bytes = (size_t)batch * 32;
+    const size_t zero_bytes = up(bins_bytes) + up(sq_bytes), it_bytes = up((size_t)kCalibMaxTemps * 8);
+    const size_t sum_bytes = up((size_t)batch * nt * 8), part_bytes = up((size_t)batch * blocks * nt * 8);
+    const size_t need = zero_bytes + it_bytes + sum_bytes + part_bytes;
+    if (need > M->calib_ws_bytes) {
+        if (M->calib_ws) HIP_TRY(hipFree(M->calib_ws));
+        M->calib_ws = nullptr;
+        M->calib_ws_bytes = 0;
+        HIP_TRY(hipMalloc(&M->calib_ws, need));
+        M->calib_ws_bytes = need;
+    }
+    char* ws = (char*)M->calib_ws;
+    unsigned long long* bins_dev = (unsigned long long*)ws;
+    unsigned long long* sq_dev = (unsigned long long*)(ws + up(bins_bytes));
+    double* it_dev = (double*)(ws + zero_bytes);
+    double* sum_dev = (double*)(ws + zero_bytes + it_bytes);
+    double* part_dev = (double*)(ws + zero_bytes + it_bytes + sum_bytes);
+    hipStream_t s = M->stream;
+    HIP_TRY(hipMemsetAsync(ws, 0, zero_bytes, s));
+    LAUNCH(M, "calib_bins", 8.0 * n, 0, g_calib_bins(s, prob, y, batch, hw, n_bins, bins_dev, sq_dev));
+    HIP_TRY(hipGetLastError());
+    double inv_t[kCalibMaxTemps];
+    if (nt) {
+        for (int t = 0; t < nt; ++t) inv_t[t] = 1.0 / (double)temperatures[t];
+        HIP_TRY(hipMemcpyAsync(it_dev, inv_t, (size_t)nt * 8, hipMemcpyHostToDevice, s));
+        // per pixel and temperature one exp and one log1p in double beside the product and the sum; the logit once per pixel and chunk
+        LAUNCH(M, "calib_nll", 8.0 * n * ((nt + 7) / 8), 60.0 * n * nt, g_calib_nll(s, prob, y, batch, hw, it_dev, nt, part_dev));
+        HIP_TRY(hipGetLastError());
+        LAUNCH(M, "calib_nll_sum", 8.0 * batch * blocks * nt, (double)batch * blocks * nt, g_calib_nll_sum(s, part_dev, batch, hw, nt, sum_dev));
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<unsigned long long> sq((size_t)batch * 4);
+    std::vector<double> sums((size_t)batch * nt);
+    HIP_TRY(hipMemcpyAsync(bins, bins_dev, bins_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(sq.data(), sq_dev, sq_bytes, hipMemcpyDeviceToHost, s));
+    if (nt) HIP_TRY(hipMemcpyAsync(sums.data(), sum_dev, (size_t)batch * nt * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));      // inv_t, sq and sums are read and written by the copies up to here
+    // a slice's pixels and q sums per class are those of its bins
+    for (int b = 0; b < batch; ++b) {
+        dnnca_calib_total t = {};
+        for (int k = 0; k < n_bins; ++k)
+            for (int c = 0; c < 2; ++c) {
+                t.n[c] += bins[(size_t)b * n_bins + k].n[c];
+                t.sum_q24[c] += bins[(size_t)b * n_bins + k].sum_q24[c];
+            }
+        for (int c = 0; c < 2; ++c) t.sq_lo[c] = sq[(size_t)b * 4 + c], t.sq_hi[c] = sq[(size_t)b * 4 + 2 + c];
+        totals[b] = t;
+    }
+    for (size_t i = 0; i < sums.size(); ++i) nll[i] = sums[i];
+    return DNNCA_OK;
+}
+
+int prob_temperature(Model* M, const float* src, float* dst, size_t n, float temperature, float* out_hw) {
+    LAUNCH(M, "prob_temperature", 8.0 * n, 40.0 * n, g_prob_temperature(M->stream, src, dst, n, temperature));
+    HIP_TRY(hipGetLastError());
+    if (out_hw) HIP_TRY(hipMemcpyAsync(out_hw, dst, n * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return DNNCA_OK;
+}
+
 }  // namespace dnnca

@@ -2,7 +2,7 @@
 //
 // Reference structure followed (annotator/models/tf_models): components.py:16-81 Downsample, :84-166 Upsample,
 // :169-247 Encoder, :250-320 Decoder; unet.py:19-88 UNet, :91-191 MulmoUNet, :194-300 annotators.
-#include "model.h"
+#include "abi.h"
 
 #include <rccl/rccl.h>
 #include <stdarg.h>
@@ -11,7 +11,6 @@
 #include <algorithm>
 #include <cmath>
 
-#include "calib.h"
 #include "fast.h"
 #include "kernels.h"
 #include "region.h"
@@ -1442,11 +1441,9 @@ int Model::optimizer_step(float lr) {
 }  // namespace dnnca
 
 // =================================================================================================== C ABI
+// (test-time augmentation and the analysis entry points -- confusion, region metrics, lesion tables, boundary distances, spread,
+// calibration -- are in abi_analysis.hip)
 using namespace dnnca;
-
-#define MODEL(h)                                             \
-    Model* M = reinterpret_cast<Model*>(h);                  \
-    if (!M) { set_error("null model handle"); return DNNCA_EINVAL; }
 
 extern "C" {
 
@@ -1551,19 +1548,13 @@ int dnnca_set_adam(void* model, float beta1, float beta2, float epsilon) {
     return DNNCA_OK;
 }
 
-// ---- helpers of the step entry points ----------------------------------------------------------------------------------------
-static int check_batch(Model* M, int batch) {
-    if (batch < 1 || batch > M->desc.max_batch) { set_error("batch %d outside [1, %d]", batch, M->desc.max_batch); return DNNCA_EINVAL; }
-    return DNNCA_OK;
-}
+}  // extern "C"
 
-static int check_slot(Model* M, int slot) {
-    if (slot < 0 || slot >= M->stage_slots) { set_error("staging slot %d outside [0, %d)", slot, M->stage_slots); return DNNCA_EINVAL; }
-    return DNNCA_OK;
-}
+// ---- helpers of the step entry points (those without `static` are declared in abi.h) -----------------------------------------
+namespace dnnca {
 
 // a host batch -> x_stage and, with `labels`, y_stage
-static int stage_inputs(Model* M, int batch, const float* x_nhwc, const float* y_hw, bool labels) {
+int stage_inputs(Model* M, int batch, const float* x_nhwc, const float* y_hw, bool labels) {
     DN_TRY(check_batch(M, batch));
     const size_t nx = (size_t)batch * M->desc.height * M->desc.width * M->desc.in_channels;
     const size_t npix = (size_t)batch * M->outH * M->outW;
@@ -1639,18 +1630,18 @@ static void confusion_from_hist(const unsigned long long* h, const ConfThreshold
 }
 
 // evaluation and the one-shot counts: eval_thr + the histogram conf_dev, which keeps adding up until it is read
-static int confusion_begin(Model* M, const float* thresholds, int n) {
+int confusion_begin(Model* M, const float* thresholds, int n) {
     DN_TRY(conf_thresholds_set(M, M->eval_thr, thresholds, n));
     HIP_TRY(hipMemsetAsync(M->conf_dev, 0, (size_t)2 * (n + 1) * 8, M->stream));
     return DNNCA_OK;
 }
 
-static void confusion_add(Model* M, size_t npix, const float* y_dev) {
+void confusion_add(Model* M, size_t npix, const float* y_dev) {
     g_conf_hist(M->stream, npix, M->prob, y_dev, M->eval_thr.dev, M->eval_thr.n, reinterpret_cast<unsigned long long*>(M->conf_dev),
                 nullptr);
 }
 
-static int confusion_finish(Model* M, dnnca_confusion* out) {
+int confusion_finish(Model* M, dnnca_confusion* out) {
     std::vector<unsigned long long> h((size_t)2 * (M->eval_thr.n + 1));
     HIP_TRY(hipMemcpyAsync(h.data(), M->conf_dev, h.size() * 8, hipMemcpyDeviceToHost, M->stream));
     HIP_TRY(hipStreamSynchronize(M->stream));
@@ -1672,6 +1663,10 @@ static int train_metrics_count(Model* M, const float* y_dev, int batch, int row)
     return DNNCA_OK;
 }
 
+}  // namespace dnnca
+
+extern "C" {
+
 // ---- steps on host or device batches ------------------------------------------------------------------------------------------
 int dnnca_forward_dev(void* model, const float* x_dev, int batch, int training) {
     MODEL(model);
@@ -1690,213 +1685,6 @@ int dnnca_forward(void* model, const float* x_nhwc, int batch, int training, flo
     if (logit_out) HIP_TRY(hipMemcpyAsync(logit_out, M->logits, npix * 4, hipMemcpyDeviceToHost, M->stream));
     HIP_TRY(hipStreamSynchronize(M->stream));
     return M->flush_profile();
-}
-
-// ---- test-time augmentation (kernels_tta.hip) ---------------------------------------------------------------------------------
-// the views of a mask in ascending order; 0 with the error set when the mask or a transposed view on h x w is refused
-static int tta_views_of(unsigned views, int h, int w, int* ks) {
-    if (views < 1u || views > 255u) { set_error("tta: views mask %u outside 1..255", views); return 0; }
-    if ((views & 0xF0u) && h != w) { set_error("tta: a transposed view (mask 0x%02X) needs a square plane, not %d x %d", views, h, w); return 0; }
-    int n = 0;
-    for (int k = 0; k < 8; ++k)
-        if (views >> k & 1u) ks[n++] = k;
-    return n;
-}
-
-static void tta_launch_view_in(Model* M, const float* src, float* dst, int B, int H, int W, int C, int k) {
-    const double nx = (double)B * H * W * C;
-    LAUNCH(M, "tta_view_in", 8.0 * nx, 0.0, g_tta_view_in(M->stream, src, dst, B, H, W, C, k));
-}
-
-static void tta_launch_accumulate(Model* M, const float* src, float* prob, int B, int H, int W, int k, bool is_logits, int pos, int n) {
-    const double npix = (double)B * H * W;
-    LAUNCH(M, "tta_accumulate", (pos ? 12.0 : 8.0) * npix, (is_logits ? 5.0 : 1.0) * npix,
-           g_tta_accumulate(M->stream, src, prob, B, H, W, k, is_logits, pos == 0, pos == n - 1, n));
-}
-
-static void tta_launch_moments(Model* M, const float* src, float* prob, float* mom, float* spread, size_t plane, int B, int H, int W,
-                               int k, bool is_logits, int pos, int n) {
-    const double npix = (double)B * H * W;
-    // floats moved per pixel: the view in; p0 out (view 0) or in; the two sums in (from view 2 on) and out (up to the last but one);
-    // the running sum in (from view 1 on) and out; the spread out (last view)
-    const bool last = pos == n - 1;
-    const double moved = 1 + (last && !pos ? 0 : 1) + (pos > 1 ? 2 : 0) + (pos && !last ? 2 : 0) + (pos ? 1 : 0) + 1 + (last ? 1 : 0);
-    LAUNCH(M, "tta_moments", 4.0 * moved * npix, (is_logits ? 11.0 : 7.0) * npix,
-           g_tta_moments(M->stream, src, prob, mom, spread, plane, B, H, W, k, is_logits, pos, n));
-}
-
-// the buffers of the two stand-alone entries: n_in floats in, n_out floats out, one allocation
-static int tta_io_buffers(Model* M, size_t n_in, size_t n_out, float** in, float** out) {
-    if (n_in + n_out > M->tta_io_n) {
-        if (M->tta_io) HIP_TRY(hipFree(M->tta_io));
-        M->tta_io = nullptr;
-        M->tta_io_n = 0;
-        HIP_TRY(hipMalloc((void**)&M->tta_io, (n_in + n_out) * 4));
-        M->tta_io_n = n_in + n_out;
-    }
-    *in = M->tta_io;
-    *out = M->tta_io + n_in;
-    return DNNCA_OK;
-}
-
-// the launch grids carry the rows and the slices in their y and z dimensions
-static int tta_check_plane(int batch, int h, int w, int c) {
-    if (batch < 1 || h < 1 || w < 1 || c < 1 || h > 65535 || batch > 65535 || (int64_t)w * c > INT32_MAX) {
-        set_error("tta: bad plane %d x %d x %d x %d (at most 65535 slices and rows, w * c below 2^31)", batch, h, w, c);
-        return DNNCA_EINVAL;
-    }
-    return DNNCA_OK;
-}
-
-int dnnca_forward_tta(void* model, const float* x_nhwc, int batch, unsigned views, float* prob_out) {
-    MODEL(model);
-    const int H = M->desc.height, W = M->desc.width, C = M->desc.in_channels;
-    int ks[8];
-    const int n = tta_views_of(views, H, W, ks);
-    if (!n) return DNNCA_EINVAL;
-    if (!x_nhwc) { set_error("tta: null x"); return DNNCA_EINVAL; }
-    if (M->outH != H || M->outW != W) {
-        set_error("tta: the output (%d x %d) differs from the input (%d x %d)", M->outH, M->outW, H, W);
-        return DNNCA_EINVAL;
-    }
-    DN_TRY(check_batch(M, batch));
-    DN_TRY(tta_check_plane(batch, H, W, C));
-    if (!M->tta_view && views != 1u) DN_TRY(M->alloc((void**)&M->tta_view, (size_t)M->desc.max_batch * H * W * C * 4));
-    DN_TRY(stage_inputs(M, batch, x_nhwc, nullptr, false));
-    for (int i = 0; i < n; ++i) {
-        const float* x = M->x_stage;                      // view 0 forwards from the staged batch itself
-        if (ks[i]) {
-            tta_launch_view_in(M, M->x_stage, M->tta_view, batch, H, W, C, ks[i]);
-            x = M->tta_view;
-        }
-        DN_TRY(M->forward(x, batch, false));
-        tta_launch_accumulate(M, M->logits, M->prob, batch, H, W, ks[i], true, i, n);
-    }
-    const size_t npix = (size_t)batch * H * W;
-    if (prob_out) {
-        HIP_TRY(hipMemcpyAsync(prob_out, M->prob, npix * 4, hipMemcpyDeviceToHost, M->stream));
-        HIP_TRY(hipStreamSynchronize(M->stream));
-        return M->flush_profile();
-    }
-    return DNNCA_OK;
-}
-
-int dnnca_tta_view_of(void* model, const float* src, int batch, int h, int w, int c, int view, float* dst) {
-    MODEL(model);
-    if (!src || !dst) { set_error("tta: null buffer"); return DNNCA_EINVAL; }
-    if (view < 0 || view > 7) { set_error("tta: view %d outside 0..7", view); return DNNCA_EINVAL; }
-    int ks[8];
-    if (!tta_views_of(1u << view, h, w, ks)) return DNNCA_EINVAL;
-    DN_TRY(check_batch(M, batch));
-    DN_TRY(tta_check_plane(batch, h, w, c));
-    const size_t nx = (size_t)batch * h * w * c;
-    float *in = nullptr, *out = nullptr;
-    DN_TRY(tta_io_buffers(M, nx, nx, &in, &out));
-    HIP_TRY(hipMemcpyAsync(in, src, nx * 4, hipMemcpyHostToDevice, M->stream));
-    tta_launch_view_in(M, in, out, batch, h, w, c, view);
-    HIP_TRY(hipMemcpyAsync(dst, out, nx * 4, hipMemcpyDeviceToHost, M->stream));
-    HIP_TRY(hipStreamSynchronize(M->stream));
-    return M->flush_profile();
-}
-
-int dnnca_tta_mean_of(void* model, const float* vals, int batch, int h, int w, unsigned views, int is_logits, float* prob_out) {
-    MODEL(model);
-    int ks[8];
-    const int n = tta_views_of(views, h, w, ks);
-    if (!n) return DNNCA_EINVAL;
-    if (!vals || !prob_out) { set_error("tta: null buffer"); return DNNCA_EINVAL; }
-    DN_TRY(check_batch(M, batch));
-    DN_TRY(tta_check_plane(batch, h, w, 1));
-    const size_t npix = (size_t)batch * h * w;
-    float *in = nullptr, *out = nullptr;
-    DN_TRY(tta_io_buffers(M, npix * n, npix, &in, &out));
-    HIP_TRY(hipMemcpyAsync(in, vals, npix * n * 4, hipMemcpyHostToDevice, M->stream));
-    for (int i = 0; i < n; ++i) tta_launch_accumulate(M, in + npix * i, out, batch, h, w, ks[i], is_logits != 0, i, n);
-    HIP_TRY(hipMemcpyAsync(prob_out, out, npix * 4, hipMemcpyDeviceToHost, M->stream));
-    HIP_TRY(hipStreamSynchronize(M->stream));
-    return M->flush_profile();
-}
-
-static const char* kSpreadState = "dnnca_forward_tta_spread makes it valid, until the next call that rewrites the probabilities";
-
-// the model's own spread plane for `batch` slices, or DNNCA_ESTATE
-static int tta_spread_plane(Model* M, int batch, const char* who) {
-    if (!M->tta_spread_valid) { set_error("%s: the model's spread plane is not valid (%s)", who, kSpreadState); return DNNCA_ESTATE; }
-    if (batch > M->tta_spread_batch) {
-        set_error("%s: %d slices asked for, the model's spread plane holds %d (%s)", who, batch, M->tta_spread_batch, kSpreadState);
-        return DNNCA_ESTATE;
-    }
-    return DNNCA_OK;
-}
-
-int dnnca_forward_tta_spread(void* model, const float* x_nhwc, int batch, unsigned views, float* prob_out, float* spread_out) {
-    MODEL(model);
-    const int H = M->desc.height, W = M->desc.width, C = M->desc.in_channels;
-    int ks[8];
-    const int n = tta_views_of(views, H, W, ks);
-    if (!n) return DNNCA_EINVAL;
-    if (!x_nhwc) { set_error("tta: null x"); return DNNCA_EINVAL; }
-    if (M->outH != H || M->outW != W) {
-        set_error("tta: the output (%d x %d) differs from the input (%d x %d)", M->outH, M->outW, H, W);
-        return DNNCA_EINVAL;
-    }
-    DN_TRY(check_batch(M, batch));
-    DN_TRY(tta_check_plane(batch, H, W, C));
-    const size_t plane = (size_t)M->desc.max_batch * H * W;
-    if (!M->tta_view && views != 1u) DN_TRY(M->alloc((void**)&M->tta_view, plane * C * 4));
-    if (!M->tta_spread) DN_TRY(M->alloc((void**)&M->tta_spread, plane * 4));
-    if (!M->tta_mom) DN_TRY(M->alloc((void**)&M->tta_mom, 3 * plane * 4));
-    DN_TRY(stage_inputs(M, batch, x_nhwc, nullptr, false));
-    for (int i = 0; i < n; ++i) {
-        const float* x = M->x_stage;                      // view 0 forwards from the staged batch itself
-        if (ks[i]) {
-            tta_launch_view_in(M, M->x_stage, M->tta_view, batch, H, W, C, ks[i]);
-            x = M->tta_view;
-        }
-        DN_TRY(M->forward(x, batch, false));
-        tta_launch_moments(M, M->logits, M->prob, M->tta_mom, M->tta_spread, plane, batch, H, W, ks[i], true, i, n);
-    }
-    M->tta_spread_valid = true;
-    M->tta_spread_batch = batch;
-    const size_t npix = (size_t)batch * H * W;
-    if (prob_out) HIP_TRY(hipMemcpyAsync(prob_out, M->prob, npix * 4, hipMemcpyDeviceToHost, M->stream));
-    if (spread_out) HIP_TRY(hipMemcpyAsync(spread_out, M->tta_spread, npix * 4, hipMemcpyDeviceToHost, M->stream));
-    if (prob_out || spread_out) {
-        HIP_TRY(hipStreamSynchronize(M->stream));
-        return M->flush_profile();
-    }
-    return DNNCA_OK;
-}
-
-int dnnca_tta_spread_of(void* model, const float* vals, int batch, int h, int w, unsigned views, int is_logits, float* prob_out,
-                        float* spread_out) {
-    MODEL(model);
-    int ks[8];
-    const int n = tta_views_of(views, h, w, ks);
-    if (!n) return DNNCA_EINVAL;
-    if (!vals || !prob_out || !spread_out) { set_error("tta: null buffer"); return DNNCA_EINVAL; }
-    DN_TRY(check_batch(M, batch));
-    DN_TRY(tta_check_plane(batch, h, w, 1));
-    const size_t npix = (size_t)batch * h * w;
-    float *in = nullptr, *out = nullptr;                 // out: the mean, the spread, then the three planes of moments
-    DN_TRY(tta_io_buffers(M, npix * n, npix * 5, &in, &out));
-    HIP_TRY(hipMemcpyAsync(in, vals, npix * n * 4, hipMemcpyHostToDevice, M->stream));
-    for (int i = 0; i < n; ++i)
-        tta_launch_moments(M, in + npix * i, out, out + 2 * npix, out + npix, npix, batch, h, w, ks[i], is_logits != 0, i, n);
-    HIP_TRY(hipMemcpyAsync(prob_out, out, npix * 4, hipMemcpyDeviceToHost, M->stream));
-    HIP_TRY(hipMemcpyAsync(spread_out, out + npix, npix * 4, hipMemcpyDeviceToHost, M->stream));
-    HIP_TRY(hipStreamSynchronize(M->stream));
-    return M->flush_profile();
-}
-
-int dnnca_get_tta_spread(void* model, int batch, float* out) {
-    MODEL(model);
-    if (!out) { set_error("tta: null buffer"); return DNNCA_EINVAL; }
-    DN_TRY(check_batch(M, batch));
-    DN_TRY(tta_spread_plane(M, batch, "dnnca_get_tta_spread"));
-    HIP_TRY(hipMemcpyAsync(out, M->tta_spread, (size_t)batch * M->outH * M->outW * 4, hipMemcpyDeviceToHost, M->stream));
-    HIP_TRY(hipStreamSynchronize(M->stream));
-    return DNNCA_OK;
 }
 
 // row: the tm_hist / tm_pin row of the step's training-metric counts (its staging slot, or kStageSlots)
@@ -2221,555 +2009,6 @@ int dnnca_dev_alloc(void** dev_ptr, size_t bytes) {
 int dnnca_dev_free(void* dev_ptr) { HIP_TRY(hipFree(dev_ptr)); return DNNCA_OK; }
 int dnnca_memcpy_h2d(void* dev_dst, const void* host_src, size_t bytes) { HIP_TRY(hipMemcpy(dev_dst, host_src, bytes, hipMemcpyHostToDevice)); return DNNCA_OK; }
 int dnnca_memcpy_d2h(void* host_dst, const void* dev_src, size_t bytes) { HIP_TRY(hipMemcpy(host_dst, dev_src, bytes, hipMemcpyDeviceToHost)); return DNNCA_OK; }
-
-// ---- one-shot pixel confusion of M->prob against y_stage ---------------------------------------------------------------------
-static int confusion_counts(Model* M, size_t npix, const float* thresholds, int n, dnnca_confusion* out) {
-    if (M->eval_active) { set_error("dnnca_pixel_confusion* inside dnnca_eval_begin .. dnnca_eval_end (the histogram is in use)"); return DNNCA_ESTATE; }
-    DN_TRY(confusion_begin(M, thresholds, n));
-    confusion_add(M, npix, M->y_stage);
-    return confusion_finish(M, out);
-}
-
-int dnnca_pixel_confusion(void* model, const float* y_hw, int batch, const float* thresholds, int n, dnnca_confusion* out) {
-    MODEL(model);
-    if (n < 1 || n > DNNCA_CONF_MAX_THR || !out || !thresholds || !y_hw) {
-        set_error("bad confusion arguments (1..%d thresholds)", DNNCA_CONF_MAX_THR);
-        return DNNCA_EINVAL;
-    }
-    DN_TRY(check_batch(M, batch));
-    const size_t npix = (size_t)batch * M->outH * M->outW;
-    HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, npix * 4, hipMemcpyHostToDevice, M->stream));
-    return confusion_counts(M, npix, thresholds, n, out);
-}
-
-int dnnca_pixel_confusion_of(void* model, const float* prob_hw, const float* y_hw, int64_t n_pixels, const float* thresholds,
-                             int n, dnnca_confusion* out) {
-    MODEL(model);
-    if (n < 1 || n > DNNCA_CONF_MAX_THR || !out || !thresholds || !y_hw || !prob_hw) {
-        set_error("bad confusion arguments (1..%d thresholds)", DNNCA_CONF_MAX_THR);
-        return DNNCA_EINVAL;
-    }
-    int64_t cap = (int64_t)M->desc.max_batch * M->outH * M->outW;
-    if (n_pixels < 1 || n_pixels > cap) { set_error("n_pixels %lld outside 1..%lld", (long long)n_pixels, (long long)cap); return DNNCA_EINVAL; }
-    M->tta_spread_valid = false;
-    HIP_TRY(hipMemcpyAsync(M->prob, prob_hw, (size_t)n_pixels * 4, hipMemcpyHostToDevice, M->stream));
-    HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, (size_t)n_pixels * 4, hipMemcpyHostToDevice, M->stream));
-    return confusion_counts(M, (size_t)n_pixels, thresholds, n, out);
-}
-
-// ---- region-based metrics (kernels_region.hip) --------------------------------------------------------------------------
-static int region_one(Model* M, const float* prob_dev, const float* y_dev, int batch, int h, int w, const dnnca_region_spec* spec,
-                      dnnca_region_counts* out) {
-    if (M->region_eval) { set_error("dnnca_region_confusion* inside dnnca_eval_region_begin .. dnnca_eval_region_end"); return DNNCA_ESTATE; }
-    std::vector<RegionSpecHost> specs(1);
-    DN_TRY(region_spec_check(spec, h, w, specs[0]));
-    DN_TRY(region_prepare(M, specs, batch, h, w));
-    DN_TRY(region_accumulate(M, prob_dev, y_dev, batch, h, w));
-    std::vector<std::vector<dnnca_region_counts>> counts;
-    DN_TRY(region_read(M, counts));
-    std::copy(counts[0].begin(), counts[0].end(), out);
-    return DNNCA_OK;
-}
-
-int dnnca_region_confusion_of(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w,
-                              const dnnca_region_spec* spec, dnnca_region_counts* out) {
-    MODEL(model);
-    if (!prob_hw || !y_hw || !spec || !out || batch < 1 || h < 1 || w < 1) { set_error("bad region confusion arguments"); return DNNCA_EINVAL; }
-    const size_t n = (size_t)batch * h * w;
-    float *p_dev = nullptr, *y_dev = nullptr;
-    DN_TRY(region_inputs(M, n, &p_dev, &y_dev));
-    HIP_TRY(hipMemcpyAsync(p_dev, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-    HIP_TRY(hipMemcpyAsync(y_dev, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-    return region_one(M, p_dev, y_dev, batch, h, w, spec, out);
-}
-
-int dnnca_region_confusion(void* model, const float* y_hw, int batch, const dnnca_region_spec* spec, dnnca_region_counts* out) {
-    MODEL(model);
-    if (!y_hw || !spec || !out) { set_error("bad region confusion arguments"); return DNNCA_EINVAL; }
-    DN_TRY(check_batch(M, batch));
-    const size_t n = (size_t)batch * M->outH * M->outW;
-    HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-    return region_one(M, M->prob, M->y_stage, batch, M->outH, M->outW, spec, out);
-}
-
-int dnnca_region_confusion_slices(void* model, const float* prob_hw, const float* y_hw, int batch, const dnnca_region_spec* specs,
-                                  int n, dnnca_region_counts* out) {
-    MODEL(model);
-    if (!y_hw || !specs || !out || n < 1) { set_error("bad region confusion arguments"); return DNNCA_EINVAL; }
-    DN_TRY(check_batch(M, batch));
-    if (M->region_eval) { set_error("dnnca_region_confusion* inside dnnca_eval_region_begin .. dnnca_eval_region_end"); return DNNCA_ESTATE; }
-    std::vector<RegionSpecHost> hs(n);
-    for (int i = 0; i < n; ++i) DN_TRY(region_spec_check(specs + i, M->outH, M->outW, hs[i]));
-    const size_t npix = (size_t)batch * M->outH * M->outW;
-    float *p_dev = nullptr, *y_dev = nullptr;
-    DN_TRY(region_inputs(M, npix, &p_dev, &y_dev));       // the labels stay there for dnnca_render_composite
-    HIP_TRY(hipMemcpyAsync(y_dev, y_hw, npix * 4, hipMemcpyHostToDevice, M->stream));
-    if (prob_hw) HIP_TRY(hipMemcpyAsync(p_dev, prob_hw, npix * 4, hipMemcpyHostToDevice, M->stream));
-    DN_TRY(region_prepare(M, hs, batch, M->outH, M->outW, batch));
-    DN_TRY(region_accumulate(M, prob_hw ? p_dev : M->prob, y_dev, batch, M->outH, M->outW, true));
-    DN_TRY(region_read_slices(M, batch, out));
-    region_set_label_batch(M, batch);
-    return DNNCA_OK;
-}
-
-int dnnca_render_composite(void* model, const float* y_hw, int batch, float ratio, int overlay, uint8_t* out, int64_t capacity,
-                           int32_t* out_hwc) {
-    MODEL(model);
-    if (!out_hwc || capacity < 0 || (out && capacity == 0)) { set_error("bad render arguments"); return DNNCA_EINVAL; }
-    DN_TRY(check_batch(M, batch));
-    if (M->outH != M->desc.height || M->outW != M->desc.width) {
-        set_error("render: the output (%d x %d) differs from the input (%d x %d)", M->outH, M->outW, M->desc.height, M->desc.width);
-        return DNNCA_EINVAL;
-    }
-    int hwc[3];
-    const int H = M->desc.height, W = M->desc.width, C = M->desc.in_channels;
-    DN_TRY(region_render(M, nullptr, nullptr, nullptr, batch, H, W, C, ratio, overlay, nullptr, 0, hwc));
-    std::copy(hwc, hwc + 3, out_hwc);
-    if (!out) return DNNCA_OK;
-    const float* lab = y_hw ? nullptr : region_label_of(M, batch);
-    if (y_hw) {
-        HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, (size_t)batch * H * W * 4, hipMemcpyHostToDevice, M->stream));
-        lab = M->y_stage;
-    } else if (!lab) {
-        set_error("render: no labels given and none kept from dnnca_region_confusion_slices of %d slices", batch);
-        return DNNCA_ESTATE;
-    }
-    return region_render(M, M->x_stage, lab, M->prob, batch, H, W, C, ratio, overlay, out, (size_t)capacity, hwc);
-}
-
-// ---- `annotator predict`: the lesion table (kernels_region.hip) ---------------------------------------------------------------
-// dnnca_lesion_table (link == false; the four link arguments are not looked at), dnnca_lesion_table_linked and, with_spread,
-// dnnca_lesion_table_spread (never linked)
-static int lesion_call(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor, int filter_size,
-                       int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity, int64_t* n_rows, int32_t* totals,
-                       uint8_t* mask, int64_t mask_capacity, int32_t* out_hw, bool link, const uint8_t* continues,
-                       dnnca_lesion_link* links, int64_t links_capacity, int64_t* n_links, bool with_spread = false,
-                       const float* spread_hw = nullptr, dnnca_lesion_spread* srows = nullptr, dnnca_slice_spread* stotals = nullptr) {
-    MODEL(model);
-    DN_TRY(check_batch(M, batch));
-    if (!prob_hw) {
-        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
-            set_error("lesion table: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
-            return DNNCA_EINVAL;
-        }
-        h = M->outH;
-        w = M->outW;
-    }
-    LesionArgs a;
-    a.threshold = threshold;
-    a.rf = resize_factor;
-    a.k = filter_size;
-    a.min_area = min_area;
-    a.max_lesions = max_lesions;
-    DN_TRY(lesion_check(a, h, w));
-    if (!out_hw) { set_error("lesion table: null out_hw"); return DNNCA_EINVAL; }
-    out_hw[0] = a.oh;
-    out_hw[1] = a.ow;
-    if (!rows) return DNNCA_OK;                   // size query
-    if (!totals || !n_rows) { set_error("lesion table: null totals / n_rows"); return DNNCA_EINVAL; }
-    if (rows_capacity < (int64_t)batch * a.cap) {
-        set_error("lesion table: %lld rows needed (%d slices x %d), capacity %lld", (long long)batch * a.cap, batch, a.cap,
-                  (long long)rows_capacity);
-        return DNNCA_EINVAL;
-    }
-    if (mask && mask_capacity < (int64_t)batch * a.oh * a.ow) {
-        set_error("lesion table: mask of %lld bytes needed, capacity %lld", (long long)batch * a.oh * a.ow, (long long)mask_capacity);
-        return DNNCA_EINVAL;
-    }
-    if (link) {
-        if (!continues) { set_error("lesion table: null continues"); return DNNCA_EINVAL; }
-        if (!links || !n_links || links_capacity < (int64_t)batch * a.links_per_slice()) {
-            set_error("lesion table: %lld links needed (%d slices x %lld), capacity %lld", (long long)batch * a.links_per_slice(), batch,
-                      (long long)a.links_per_slice(), links && n_links ? (long long)links_capacity : 0ll);
-            return DNNCA_EINVAL;
-        }
-        if (continues[0] && !lesion_carry_is(M, a.oh, a.ow)) {
-            set_error("lesion table: continues[0] is set, but no linked call on planes of %d x %d precedes this one", a.oh, a.ow);
-            return DNNCA_EINVAL;
-        }
-    }
-    if (with_spread) {
-        if ((prob_hw == nullptr) != (spread_hw == nullptr)) {
-            set_error("lesion table: prob_hw and spread_hw go together (both host planes, or both NULL for the model's own)");
-            return DNNCA_EINVAL;
-        }
-        if (!srows || !stotals) { set_error("lesion table: null srows / stotals"); return DNNCA_EINVAL; }
-        if (!spread_hw) DN_TRY(tta_spread_plane(M, batch, "dnnca_lesion_table_spread"));
-    }
-    const float* p_dev = M->prob;
-    const float* s_dev = M->tta_spread;
-    if (prob_hw) {
-        const size_t n = (size_t)batch * h * w;
-        float *pd = nullptr, *yd = nullptr;
-        DN_TRY(region_inputs(M, n, &pd, &yd));
-        HIP_TRY(hipMemcpyAsync(pd, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-        p_dev = pd;
-        if (with_spread) {               // the label buffer of region_inputs carries the spread plane
-            HIP_TRY(hipMemcpyAsync(yd, spread_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-            s_dev = yd;
-        }
-    }
-    if (with_spread)
-        return lesion_table_spread(M, p_dev, s_dev, batch, h, w, a, rows, n_rows, totals, mask, mask != nullptr, srows, stotals);
-    if (link) return lesion_table_linked(M, p_dev, batch, h, w, a, rows, n_rows, totals, mask, mask != nullptr, continues, links, n_links);
-    return lesion_table(M, p_dev, batch, h, w, a, rows, n_rows, totals, mask, mask != nullptr);
-}
-
-int dnnca_lesion_table(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
-                       int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
-                       int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw) {
-    return lesion_call(model, prob_hw, batch, h, w, threshold, resize_factor, filter_size, min_area, max_lesions, rows, rows_capacity,
-                       n_rows, totals, mask, mask_capacity, out_hw, false, nullptr, nullptr, 0, nullptr);
-}
-
-int dnnca_lesion_table_spread(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
-                              int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
-                              int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw,
-                              const float* spread_hw, dnnca_lesion_spread* srows, dnnca_slice_spread* stotals) {
-    return lesion_call(model, prob_hw, batch, h, w, threshold, resize_factor, filter_size, min_area, max_lesions, rows, rows_capacity,
-                       n_rows, totals, mask, mask_capacity, out_hw, false, nullptr, nullptr, 0, nullptr, true, spread_hw, srows, stotals);
-}
-
-int dnnca_spread_by_outcome(void* model, const float* prob_hw, const float* spread_hw, const float* y_hw, int batch, int h, int w,
-                            const float* thresholds, int n_thresholds, dnnca_spread_outcome* out) {
-    MODEL(model);
-    DN_TRY(check_batch(M, batch));
-    if (!y_hw || !thresholds || !out) { set_error("spread by outcome: null y_hw / thresholds / out"); return DNNCA_EINVAL; }
-    if (n_thresholds < 1 || n_thresholds > kRegionMaxThr) {
-        set_error("spread by outcome: %d thresholds outside 1..%d", n_thresholds, kRegionMaxThr);
-        return DNNCA_EINVAL;
-    }
-    for (int t = 0; t < n_thresholds; ++t)
-        if (thresholds[t] != thresholds[t]) { set_error("spread by outcome: threshold %d is NaN", t); return DNNCA_EINVAL; }
-    if ((prob_hw == nullptr) != (spread_hw == nullptr)) {
-        set_error("spread by outcome: prob_hw and spread_hw go together (both host planes, or both NULL for the model's own)");
-        return DNNCA_EINVAL;
-    }
-    if (!prob_hw) {
-        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
-            set_error("spread by outcome: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
-            return DNNCA_EINVAL;
-        }
-        h = M->outH;
-        w = M->outW;
-    }
-    if (h < 1 || w < 1 || (int64_t)h * w > INT32_MAX || batch > 65535) {
-        set_error("spread by outcome: bad plane %d x %d x %d", batch, h, w);
-        return DNNCA_EINVAL;
-    }
-    const size_t hw = (size_t)h * w, n = (size_t)batch * hw;
-    const float *p_dev = M->prob, *s_dev = M->tta_spread, *y_dev = M->y_stage;
-    if (!prob_hw) {
-        DN_TRY(tta_spread_plane(M, batch, "dnnca_spread_by_outcome"));
-        HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-    } else {
-        float *in = nullptr, *yd = nullptr;               // probabilities, then the spread; the labels behind them
-        DN_TRY(tta_io_buffers(M, 2 * n, n, &in, &yd));
-        HIP_TRY(hipMemcpyAsync(in, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-        HIP_TRY(hipMemcpyAsync(in + n, spread_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-        HIP_TRY(hipMemcpyAsync(yd, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-        p_dev = in, s_dev = in + n, y_dev = yd;
-    }
-    DN_TRY(spread_by_outcome(M, p_dev, s_dev, y_dev, batch, hw, thresholds, n_thresholds, out));
-    return M->flush_profile();
-}
-
-// ---- calibration (kernels_calib.hip) ------------------------------------------------------------------------------------------
-static bool calib_temperature_ok(float t) { return t >= kCalibMinT && t <= kCalibMaxT; }      // false for a NaN
-
-int dnnca_calibration(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w, int n_bins,
-                      const float* temperatures, int n_temperatures, dnnca_calib_bin* bins, dnnca_calib_total* totals, double* nll) {
-    MODEL(model);
-    DN_TRY(check_batch(M, batch));
-    if (!y_hw || !bins || !totals) { set_error("calibration: null y_hw / bins / totals"); return DNNCA_EINVAL; }
-    if (n_bins < 1 || n_bins > kCalibMaxBins) { set_error("calibration: %d bins outside 1..%d", n_bins, kCalibMaxBins); return DNNCA_EINVAL; }
-    if (n_temperatures < 0 || n_temperatures > kCalibMaxTemps) {
-        set_error("calibration: %d temperatures outside 0..%d", n_temperatures, kCalibMaxTemps);
-        return DNNCA_EINVAL;
-    }
-    if (n_temperatures > 0 && (!temperatures || !nll)) { set_error("calibration: temperatures without their array or without nll"); return DNNCA_EINVAL; }
-    for (int t = 0; t < n_temperatures; ++t)
-        if (!calib_temperature_ok(temperatures[t])) {
-            set_error("calibration: temperature %d is %g (outside [%g, %g])", t, (double)temperatures[t], (double)kCalibMinT, (double)kCalibMaxT);
-            return DNNCA_EINVAL;
-        }
-    if (!prob_hw) {
-        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
-            set_error("calibration: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
-            return DNNCA_EINVAL;
-        }
-        h = M->outH;
-        w = M->outW;
-    }
-    if (h < 1 || w < 1 || (int64_t)h * w > INT32_MAX || batch > 65535) {
-        set_error("calibration: bad plane %d x %d x %d", batch, h, w);
-        return DNNCA_EINVAL;
-    }
-    if (!prob_hw && batch > M->last_batch) {
-        set_error("calibration: %d slices asked for, the model's probabilities hold %d (the last forward's)", batch, M->last_batch);
-        return DNNCA_ESTATE;
-    }
-    const size_t hw = (size_t)h * w, n = (size_t)batch * hw;
-    const float *p_dev = M->prob, *y_dev = M->y_stage;
-    if (!prob_hw) {
-        HIP_TRY(hipMemcpyAsync(M->y_stage, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-    } else {
-        float *in = nullptr, *yd = nullptr;
-        DN_TRY(tta_io_buffers(M, n, n, &in, &yd));
-        HIP_TRY(hipMemcpyAsync(in, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-        HIP_TRY(hipMemcpyAsync(yd, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-        p_dev = in, y_dev = yd;
-    }
-    // workspace: the bin table, the squares (both zeroed), 1 / T, the sums per slice and temperature, the block partials
-    int runs = 0, blocks = 0;
-    calib_nll_shape(hw, &runs, &blocks);
-    const int nt = n_temperatures;
-    auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t bins_bytes = (size_t)batch * n_bins * sizeof(dnnca_calib_bin), sq_bytes = (size_t)batch * 32;
-    const size_t zero_bytes = up(bins_bytes) + up(sq_bytes), it_bytes = up((size_t)kCalibMaxTemps * 8);
-    const size_t sum_bytes = up((size_t)batch * nt * 8), part_bytes = up((size_t)batch * blocks * nt * 8);
-    const size_t need = zero_bytes + it_bytes + sum_bytes + part_bytes;
-    if (need > M->calib_ws_bytes) {
-        if (M->calib_ws) HIP_TRY(hipFree(M->calib_ws));
-        M->calib_ws = nullptr;
-        M->calib_ws_bytes = 0;
-        HIP_TRY(hipMalloc(&M->calib_ws, need));
-        M->calib_ws_bytes = need;
-    }
-    char* ws = (char*)M->calib_ws;
-    unsigned long long* bins_dev = (unsigned long long*)ws;
-    unsigned long long* sq_dev = (unsigned long long*)(ws + up(bins_bytes));
-    double* it_dev = (double*)(ws + zero_bytes);
-    double* sum_dev = (double*)(ws + zero_bytes + it_bytes);
-    double* part_dev = (double*)(ws + zero_bytes + it_bytes + sum_bytes);
-    hipStream_t s = M->stream;
-    HIP_TRY(hipMemsetAsync(ws, 0, zero_bytes, s));
-    LAUNCH(M, "calib_bins", 8.0 * n, 0, g_calib_bins(s, p_dev, y_dev, batch, hw, n_bins, bins_dev, sq_dev));
-    HIP_TRY(hipGetLastError());
-    double inv_t[kCalibMaxTemps];
-    if (nt) {
-        for (int t = 0; t < nt; ++t) inv_t[t] = 1.0 / (double)temperatures[t];
-        HIP_TRY(hipMemcpyAsync(it_dev, inv_t, (size_t)nt * 8, hipMemcpyHostToDevice, s));
-        // per pixel and temperature one exp and one log1p in double beside the product and the sum; the logit once per pixel and chunk
-        LAUNCH(M, "calib_nll", 8.0 * n * ((nt + 7) / 8), 60.0 * n * nt, g_calib_nll(s, p_dev, y_dev, batch, hw, it_dev, nt, part_dev));
-        HIP_TRY(hipGetLastError());
-        LAUNCH(M, "calib_nll_sum", 8.0 * batch * blocks * nt, (double)batch * blocks * nt, g_calib_nll_sum(s, part_dev, batch, hw, nt, sum_dev));
-        HIP_TRY(hipGetLastError());
-    }
-    std::vector<unsigned long long> sq((size_t)batch * 4);
-    std::vector<double> sums((size_t)batch * nt);
-    HIP_TRY(hipMemcpyAsync(bins, bins_dev, bins_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(sq.data(), sq_dev, sq_bytes, hipMemcpyDeviceToHost, s));
-    if (nt) HIP_TRY(hipMemcpyAsync(sums.data(), sum_dev, (size_t)batch * nt * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));      // inv_t, sq and sums are read and written by the copies up to here
-    // a slice's pixels and q sums per class are those of its bins
-    for (int b = 0; b < batch; ++b) {
-        dnnca_calib_total t = {};
-        for (int k = 0; k < n_bins; ++k)
-            for (int c = 0; c < 2; ++c) {
-                t.n[c] += bins[(size_t)b * n_bins + k].n[c];
-                t.sum_q24[c] += bins[(size_t)b * n_bins + k].sum_q24[c];
-            }
-        for (int c = 0; c < 2; ++c) t.sq_lo[c] = sq[(size_t)b * 4 + c], t.sq_hi[c] = sq[(size_t)b * 4 + 2 + c];
-        totals[b] = t;
-    }
-    for (size_t i = 0; i < sums.size(); ++i) nll[i] = sums[i];
-    return M->flush_profile();
-}
-
-int dnnca_prob_temperature(void* model, const float* prob_hw, int batch, int h, int w, float temperature, float* out_hw) {
-    MODEL(model);
-    DN_TRY(check_batch(M, batch));
-    if (!calib_temperature_ok(temperature)) {
-        set_error("temperature %g outside [%g, %g]", (double)temperature, (double)kCalibMinT, (double)kCalibMaxT);
-        return DNNCA_EINVAL;
-    }
-    if (prob_hw && !out_hw) { set_error("temperature: a host plane needs out_hw"); return DNNCA_EINVAL; }
-    if (!prob_hw) {
-        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
-            set_error("temperature: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
-            return DNNCA_EINVAL;
-        }
-        h = M->outH;
-        w = M->outW;
-    }
-    if (h < 1 || w < 1 || (int64_t)h * w > INT32_MAX) { set_error("temperature: bad plane %d x %d x %d", batch, h, w); return DNNCA_EINVAL; }
-    if (!prob_hw && batch > M->last_batch) {
-        set_error("temperature: %d slices asked for, the model's probabilities hold %d (the last forward's)", batch, M->last_batch);
-        return DNNCA_ESTATE;
-    }
-    const size_t n = (size_t)batch * h * w;
-    const float* src = M->prob;
-    float* dst = M->prob;
-    if (prob_hw) {
-        float *in = nullptr, *out = nullptr;
-        DN_TRY(tta_io_buffers(M, n, n, &in, &out));
-        HIP_TRY(hipMemcpyAsync(in, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-        src = in, dst = out;
-    }
-    LAUNCH(M, "prob_temperature", 8.0 * n, 40.0 * n, g_prob_temperature(M->stream, src, dst, n, temperature));
-    HIP_TRY(hipGetLastError());
-    if (out_hw) HIP_TRY(hipMemcpyAsync(out_hw, dst, n * 4, hipMemcpyDeviceToHost, M->stream));
-    HIP_TRY(hipStreamSynchronize(M->stream));
-    return M->flush_profile();
-}
-
-int dnnca_lesion_table_linked(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
-                              int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
-                              int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw,
-                              const uint8_t* continues, dnnca_lesion_link* links, int64_t links_capacity, int64_t* n_links) {
-    return lesion_call(model, prob_hw, batch, h, w, threshold, resize_factor, filter_size, min_area, max_lesions, rows, rows_capacity,
-                       n_rows, totals, mask, mask_capacity, out_hw, true, continues, links, links_capacity, n_links);
-}
-
-int dnnca_lesion_table_matched(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w, float threshold,
-                               float resize_factor, int filter_size, int min_area, int max_lesions, const uint8_t* continues,
-                               dnnca_lesion_plane_out* pred, uint8_t* mask, int64_t mask_capacity, dnnca_lesion_plane_out* truth,
-                               dnnca_lesion_pairs_out* pairs, int32_t* out_hw) {
-    MODEL(model);
-    DN_TRY(check_batch(M, batch));
-    if (!prob_hw) {
-        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
-            set_error("lesion table: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
-            return DNNCA_EINVAL;
-        }
-        h = M->outH;
-        w = M->outW;
-    }
-    LesionArgs a;
-    a.threshold = threshold;
-    a.rf = resize_factor;
-    a.k = filter_size;
-    a.min_area = min_area;
-    a.max_lesions = max_lesions;
-    DN_TRY(lesion_check(a, h, w));
-    if (!out_hw) { set_error("lesion table: null out_hw"); return DNNCA_EINVAL; }
-    out_hw[0] = a.oh;
-    out_hw[1] = a.ow;
-    if (!pred || !pred->rows) return DNNCA_OK;      // size query
-    if (!y_hw) { set_error("lesion table: null y_hw (the matched call needs the labels)"); return DNNCA_EINVAL; }
-    if (!truth || !pairs) { set_error("lesion table: null truth / pairs"); return DNNCA_EINVAL; }
-    const long long need_rows = (long long)batch * a.cap, need_links = (long long)batch * a.links_per_slice();
-    if (!pred->totals || !truth->totals) { set_error("lesion table: null totals"); return DNNCA_EINVAL; }
-    if (pred->rows_capacity < need_rows) {
-        set_error("lesion table: %lld rows needed (%d slices x %d), capacity %lld", need_rows, batch, a.cap, (long long)pred->rows_capacity);
-        return DNNCA_EINVAL;
-    }
-    if (mask && mask_capacity < (int64_t)batch * a.oh * a.ow) {
-        set_error("lesion table: mask of %lld bytes needed, capacity %lld", (long long)batch * a.oh * a.ow, (long long)mask_capacity);
-        return DNNCA_EINVAL;
-    }
-    if (!continues) { set_error("lesion table: null continues"); return DNNCA_EINVAL; }
-    if (!pred->links || pred->links_capacity < need_links) {
-        set_error("lesion table: %lld links needed (%d slices x %lld), capacity %lld", need_links, batch, (long long)a.links_per_slice(),
-                  pred->links ? (long long)pred->links_capacity : 0ll);
-        return DNNCA_EINVAL;
-    }
-    if (!truth->rows || truth->rows_capacity < need_rows) {
-        set_error("lesion table: %lld true_rows needed (%d slices x %d), capacity %lld", need_rows, batch, a.cap,
-                  truth->rows ? (long long)truth->rows_capacity : 0ll);
-        return DNNCA_EINVAL;
-    }
-    if (!truth->links || truth->links_capacity < need_links) {
-        set_error("lesion table: %lld true_links needed (%d slices x %lld), capacity %lld", need_links, batch,
-                  (long long)a.links_per_slice(), truth->links ? (long long)truth->links_capacity : 0ll);
-        return DNNCA_EINVAL;
-    }
-    if (!pairs->pairs || pairs->capacity < need_links) {
-        set_error("lesion table: %lld pairs needed (%d slices x %lld), capacity %lld", need_links, batch, (long long)a.links_per_slice(),
-                  pairs->pairs ? (long long)pairs->capacity : 0ll);
-        return DNNCA_EINVAL;
-    }
-    if (continues[0] && !lesion_match_carry_is(M, a.oh, a.ow)) {
-        set_error("lesion table: continues[0] is set, but no matched call on planes of %d x %d precedes this one", a.oh, a.ow);
-        return DNNCA_EINVAL;
-    }
-    const size_t n = (size_t)batch * h * w;
-    float *pd = nullptr, *yd = nullptr;
-    DN_TRY(region_inputs(M, n, &pd, &yd));
-    const float* p_dev = M->prob;
-    if (prob_hw) {
-        HIP_TRY(hipMemcpyAsync(pd, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-        p_dev = pd;
-    }
-    HIP_TRY(hipMemcpyAsync(yd, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-    return lesion_table_matched(M, p_dev, yd, batch, h, w, a, continues, pred, mask, mask != nullptr, truth, pairs);
-}
-
-int dnnca_surface_distances(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w, float threshold,
-                            float resize_factor, int filter_size, int min_area, int max_samples, int32_t* counts,
-                            dnnca_surface_sample* samples, int64_t capacity, int64_t* n_samples, uint8_t* edges,
-                            int64_t edges_capacity, int32_t* out_hw) {
-    MODEL(model);
-    DN_TRY(check_batch(M, batch));
-    if (!prob_hw) {
-        if ((h != 0 || w != 0) && (h != M->outH || w != M->outW)) {
-            set_error("surface distances: %d x %d given, the last forward's probabilities are %d x %d", h, w, M->outH, M->outW);
-            return DNNCA_EINVAL;
-        }
-        h = M->outH;
-        w = M->outW;
-    }
-    LesionArgs a;
-    a.threshold = threshold;
-    a.rf = resize_factor;
-    a.k = filter_size;
-    a.min_area = min_area;
-    DN_TRY(lesion_check(a, h, w));
-    if (a.oh > kSurfaceMaxSide || a.ow > kSurfaceMaxSide) {
-        set_error("surface distances: planes of %d x %d exceed %d pixels a side", a.oh, a.ow, kSurfaceMaxSide);
-        return DNNCA_EINVAL;
-    }
-    if (!out_hw) { set_error("surface distances: null out_hw"); return DNNCA_EINVAL; }
-    out_hw[0] = a.oh;
-    out_hw[1] = a.ow;
-    if (!counts) return DNNCA_OK;                 // size query
-    if (!y_hw) { set_error("surface distances: null y_hw (the call needs the labels)"); return DNNCA_EINVAL; }
-    if (max_samples < 1) { set_error("surface distances: max_samples %d (must be >= 1)", max_samples); return DNNCA_EINVAL; }
-    if (!samples || !n_samples) { set_error("surface distances: null samples / n_samples"); return DNNCA_EINVAL; }
-    const long long plane = (long long)a.oh * a.ow, need = (long long)batch * 2 * std::min<long long>(max_samples, plane);
-    if (capacity < need) {
-        set_error("surface distances: %lld samples needed (%d slices x 2 x %lld), capacity %lld", need, batch, need / (2 * batch),
-                  (long long)capacity);
-        return DNNCA_EINVAL;
-    }
-    if (edges && edges_capacity < (int64_t)batch * plane) {
-        set_error("surface distances: edges of %lld bytes needed, capacity %lld", (long long)batch * plane, (long long)edges_capacity);
-        return DNNCA_EINVAL;
-    }
-    const size_t n = (size_t)batch * h * w;
-    float *pd = nullptr, *yd = nullptr;
-    DN_TRY(region_inputs(M, n, &pd, &yd));
-    const float* p_dev = M->prob;
-    if (prob_hw) {
-        HIP_TRY(hipMemcpyAsync(pd, prob_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-        p_dev = pd;
-    }
-    HIP_TRY(hipMemcpyAsync(yd, y_hw, n * 4, hipMemcpyHostToDevice, M->stream));
-    return surface_distances(M, p_dev, yd, batch, h, w, a, max_samples, counts, samples, n_samples, edges);
-}
-
-int dnnca_eval_region_begin(void* model, const dnnca_region_spec* specs, int n) {
-    MODEL(model);
-    if (!M->eval_active) { set_error("dnnca_eval_region_begin outside dnnca_eval_begin .. dnnca_eval_end"); return DNNCA_ESTATE; }
-    if (n < 1 || !specs) { set_error("dnnca_eval_region_begin: no specs"); return DNNCA_EINVAL; }
-    std::vector<RegionSpecHost> hs(n);
-    for (int i = 0; i < n; ++i) DN_TRY(region_spec_check(specs + i, M->outH, M->outW, hs[i]));
-    DN_TRY(region_prepare(M, hs, M->desc.max_batch, M->outH, M->outW));
-    M->region_eval = true;
-    return DNNCA_OK;
-}
-
-int dnnca_eval_region_end(void* model, dnnca_region_counts* out) {
-    MODEL(model);
-    if (!M->region_eval) { set_error("dnnca_eval_region_end without dnnca_eval_region_begin"); return DNNCA_ESTATE; }
-    M->region_eval = false;
-    if (!out) { set_error("null region counts output"); return DNNCA_EINVAL; }
-    std::vector<std::vector<dnnca_region_counts>> counts;
-    DN_TRY(region_read(M, counts));
-    for (const auto& c : counts) out = std::copy(c.begin(), c.end(), out);
-    return DNNCA_OK;
-}
 
 // ------------------------------------------------------------------------------------------------- data parallel
 int dnnca_comm_unique_id(void* id_out) {

@@ -1,5 +1,5 @@
 // region.h -- region-based (lesion-level) metrics on the device (kernels_region.hip): the host side of the pipeline that the C ABI
-// of model.hip drives (dnnca_region_confusion*, dnnca_eval_region_*).
+// of abi_analysis.hip drives (dnnca_region_confusion*, dnnca_eval_region_*, the lesion tables, the boundary distances).
 #pragma once
 #include <algorithm>
 

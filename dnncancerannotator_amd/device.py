@@ -128,6 +128,61 @@ def split_region_counts(out, sizes):
     return res
 
 
+# ---- the plane inputs of the analysis calls (lesion tables, boundary distances, spread, calibration) ----------------------------
+def _slices(a, what):
+    """`a` [B, h, w] or [B, h, w, 1] -> contiguous float32 [B, h, w]"""
+    a = as_f32(a)
+    if a.ndim == 4 and a.shape[-1] == 1:
+        a = np.ascontiguousarray(a[..., 0])
+    if a.ndim != 3:
+        raise ValueError('%s must be [B, h, w], got %s' % (what, a.shape))
+    return a
+
+
+def _labels(y, batch=None):
+    """the labels of an analysis call -> float32 [B, h, w], of `batch` slices where that is given"""
+    y = _slices(y, 'y')
+    if batch is not None and int(batch) != y.shape[0]:
+        raise ValueError('batch %d but y holds %d slices' % (batch, y.shape[0]))
+    return y
+
+
+def _host_prob(prob, y, same_shape):
+    """host probabilities beside the labels y [B, h, w]: [B, h, w(, 1)] like y (same_shape), else anything of y's size"""
+    if same_shape:
+        prob = _slices(prob, 'prob')
+        if prob.shape != y.shape:
+            raise ValueError('prob %s and y %s differ in shape' % (prob.shape, y.shape))
+        return prob
+    prob = as_f32(prob).reshape(-1)
+    if prob.size != y.size:
+        raise ValueError('prob and y differ in size')
+    return prob
+
+
+def _continues(continues, batch):
+    """one flag per slice -> uint8 [batch]"""
+    flags = np.ascontiguousarray(np.asarray(continues).astype(bool), np.uint8)
+    if flags.shape != (batch,):
+        raise ValueError('continues must hold one flag per slice (%d), got shape %s' % (batch, flags.shape))
+    return flags
+
+
+def _analysed_plane(query):
+    """the size query of a lesion or boundary call (`query(hw)`: the call without output buffers) -> (hw, oh, ow)"""
+    hw = (C.c_int32 * 2)()
+    check(query(hw))
+    return hw, hw[0], hw[1]
+
+
+def _lesion_table_buffers(batch, oh, ow, max_lesions, mask, links):
+    """the buffers of one lesion table on planes of oh x ow: (rows, totals, links or None, masks or None)"""
+    per_slice = min(int(max_lesions), (oh * ow + 1) // 2)
+    rows = np.zeros(batch * per_slice, _lib.LESION_ROW_DTYPE)
+    links = np.zeros(batch * min(per_slice * per_slice, (oh * ow + 1) // 2), _lib.LESION_LINK_DTYPE) if links else None
+    return rows, np.zeros(batch, np.int32), links, np.empty((batch, oh, ow), np.uint8) if mask else None
+
+
 class StagingRing:
     """The model's staging slots in HBM + its copy stream (include/dnnca.h, dnnca_stage_*): what ds.prefetch + Keras' asynchronous
     input feeding are for the reference (annotator/data.py:110,143; engine.py:126-135).  `upload` may run on a second thread."""
@@ -566,12 +621,9 @@ class DeviceModel:
         if (prob is None) != (spread is None):
             raise ValueError('lesion_table_spread: prob and spread go together (both host planes, or neither)')
         if spread is not None:
-            spread = as_f32(spread)
-            if spread.ndim == 4 and spread.shape[-1] == 1:
-                spread = np.ascontiguousarray(spread[..., 0])
-            p = np.asarray(prob)
-            if spread.shape != (p[..., 0].shape if p.ndim == 4 else p.shape):
-                raise ValueError('spread %s and prob %s differ in shape' % (spread.shape, p.shape))
+            spread, prob = _slices(spread, 'spread'), _slices(prob, 'prob')
+            if spread.shape != prob.shape:
+                raise ValueError('spread %s and prob %s differ in shape' % (spread.shape, prob.shape))
         return self._lesion_call(batch, prob, None, threshold, resize_factor, filter_size, min_area, max_lesions, mask, spread=spread,
                                  with_spread=True)
 
@@ -580,21 +632,13 @@ class DeviceModel:
         sum_q24 [4]) [T, B] over the classes TN, FP, FN, TP = 2 (y > 0.5) + (prob >= threshold).  y [B, h, w]; the probabilities
         and the spread are those of the last forward_tta_spread, or the host planes `prob` and `spread` [B, h, w] (both or neither).
         At most 64 thresholds.  Exact integers."""
-        y = as_f32(y)
-        if y.ndim == 4 and y.shape[-1] == 1:
-            y = np.ascontiguousarray(y[..., 0])
-        if y.ndim != 3:
-            raise ValueError('y must be [B, h, w], got %s' % (y.shape,))
+        y = _labels(y, batch)
         if (prob is None) != (spread is None):
             raise ValueError('spread_by_outcome: prob and spread go together (both host planes, or neither)')
-        if batch is not None and int(batch) != y.shape[0]:
-            raise ValueError('batch %d but y holds %d slices' % (batch, y.shape[0]))
         B, h, w = y.shape
         pp = sp = None
         if prob is not None:
-            prob, spread = as_f32(prob).reshape(-1), as_f32(spread).reshape(-1)
-            if prob.size != y.size or spread.size != y.size:
-                raise ValueError('prob, spread and y differ in size')
+            prob, spread = _host_prob(prob, y, False), _host_prob(spread, y, False)
             pp, sp = fptr(prob), fptr(spread)
         thr = threshold_vector(thresholds)
         out = np.zeros((thr.size, B), _lib.SPREAD_OUTCOME_DTYPE)
@@ -611,19 +655,11 @@ class DeviceModel:
         `temperatures` (at most 64, each in [0.05, 20]; none: an empty array and no NLL launch).  The probabilities are those of the
         last forward / forward_tta, or the host plane `prob` [B, h, w].  casewise.calibration_* turn the integers into ECE, MCE and
         Brier score.  The tables are exact integers; everything is bit-identical from run to run."""
-        y = as_f32(y)
-        if y.ndim == 4 and y.shape[-1] == 1:
-            y = np.ascontiguousarray(y[..., 0])
-        if y.ndim != 3:
-            raise ValueError('y must be [B, h, w], got %s' % (y.shape,))
-        if batch is not None and int(batch) != y.shape[0]:
-            raise ValueError('batch %d but y holds %d slices' % (batch, y.shape[0]))
+        y = _labels(y, batch)
         B, h, w = y.shape
         pp = None
         if prob is not None:
-            prob = as_f32(prob).reshape(-1)
-            if prob.size != y.size:
-                raise ValueError('prob and y differ in size')
+            prob = _host_prob(prob, y, False)
             pp = fptr(prob)
         temps = np.ascontiguousarray(np.asarray(temperatures, np.float32).reshape(-1))
         bins = np.zeros((B, int(n_bins)), _lib.CALIB_BIN_DTYPE)
@@ -643,10 +679,8 @@ class DeviceModel:
         if prob is None:
             check(self.lib.dnnca_prob_temperature(self.handle, None, int(batch), 0, 0, float(temperature), None))
             return None
-        prob = as_f32(prob)
-        if prob.ndim == 4 and prob.shape[-1] == 1:
-            prob = np.ascontiguousarray(prob[..., 0])
-        if prob.ndim != 3 or (batch is not None and int(batch) != prob.shape[0]):
+        prob = _slices(prob, 'prob')
+        if batch is not None and int(batch) != prob.shape[0]:
             raise ValueError('prob must be [B, h, w] of batch slices, got %s' % (prob.shape,))
         out = np.empty_like(prob)
         check(self.lib.dnnca_prob_temperature(self.handle, fptr(prob), prob.shape[0], prob.shape[1], prob.shape[2], float(temperature),
@@ -671,11 +705,7 @@ class DeviceModel:
         the call on buffers of that size"""
         pp, h, w = None, 0, 0
         if prob is not None:
-            prob = as_f32(prob)
-            if prob.ndim == 4 and prob.shape[-1] == 1:
-                prob = np.ascontiguousarray(prob[..., 0])
-            if prob.ndim != 3:
-                raise ValueError('prob must be [B, h, w], got %s' % (prob.shape,))
+            prob = _slices(prob, 'prob')
             if batch is not None and int(batch) != prob.shape[0]:
                 raise ValueError('batch %d but prob holds %d slices' % (batch, prob.shape[0]))
             (batch, h, w), pp = prob.shape, fptr(prob)
@@ -684,19 +714,13 @@ class DeviceModel:
         B = int(batch)
         args = (self.handle, pp, B, int(h), int(w), float(threshold), float(resize_factor), int(filter_size), int(min_area),
                 int(max_lesions))
-        hw = (C.c_int32 * 2)()
-        check(self.lib.dnnca_lesion_table(*args, None, 0, None, None, None, 0, hw))
-        oh, ow = hw[0], hw[1]
-        per_slice = min(int(max_lesions), (oh * ow + 1) // 2)
-        cap = B * per_slice
-        rows = np.zeros(cap, _lib.LESION_ROW_DTYPE)
-        totals = np.zeros(B, np.int32)
-        masks = np.empty((B, oh, ow), np.uint8) if mask else None
+        hw, oh, ow = _analysed_plane(lambda hw: self.lib.dnnca_lesion_table(*args, None, 0, None, None, None, 0, hw))
+        rows, totals, links, masks = _lesion_table_buffers(B, oh, ow, max_lesions, mask, links=continues is not None)
         n = C.c_int64()
-        out = (rows.ctypes.data_as(C.POINTER(_lib.LesionRow)), cap, C.byref(n), totals.ctypes.data_as(C.POINTER(C.c_int32)),
+        out = (rows.ctypes.data_as(C.POINTER(_lib.LesionRow)), len(rows), C.byref(n), totals.ctypes.data_as(C.POINTER(C.c_int32)),
                masks.ctypes.data_as(C.c_void_p) if mask else None, masks.nbytes if mask else 0, hw)
         if with_spread:
-            srows = np.zeros(cap, _lib.LESION_SPREAD_DTYPE)
+            srows = np.zeros(len(rows), _lib.LESION_SPREAD_DTYPE)
             stotals = np.zeros(B, _lib.SLICE_SPREAD_DTYPE)
             check(self.lib.dnnca_lesion_table_spread(*args, *out, None if spread is None else fptr(spread),
                                                      srows.ctypes.data_as(C.POINTER(_lib.LesionSpread)),
@@ -705,14 +729,10 @@ class DeviceModel:
         if continues is None:
             check(self.lib.dnnca_lesion_table(*args, *out))
             return rows[:n.value].copy(), totals, masks
-        flags = np.ascontiguousarray(np.asarray(continues).astype(bool), np.uint8)
-        if flags.shape != (B,):
-            raise ValueError('continues must hold one flag per slice (%d), got shape %s' % (B, flags.shape))
-        lcap = B * min(per_slice * per_slice, (oh * ow + 1) // 2)
-        links = np.zeros(lcap, _lib.LESION_LINK_DTYPE)
+        flags = _continues(continues, B)
         nl = C.c_int64()
         check(self.lib.dnnca_lesion_table_linked(*args, *out, flags.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                 links.ctypes.data_as(C.POINTER(_lib.LesionLink)), lcap, C.byref(nl)))
+                                                 links.ctypes.data_as(C.POINTER(_lib.LesionLink)), len(links), C.byref(nl)))
         return rows[:n.value].copy(), totals, masks, links[:nl.value].copy()
 
     def lesion_table_matched(self, y, batch=None, prob=None, continues=None, threshold=0.5, resize_factor=1.0, filter_size=5,
@@ -726,48 +746,25 @@ class DeviceModel:
         previous lesion_table_matched call on this model; the chain of lesion_table_linked is a separate one."""
         if continues is None:
             raise ValueError('lesion_table_matched needs `continues`, one flag per slice')
-        y = as_f32(y)
-        if y.ndim == 4 and y.shape[-1] == 1:
-            y = np.ascontiguousarray(y[..., 0])
-        if y.ndim != 3:
-            raise ValueError('y must be [B, h, w], got %s' % (y.shape,))
-        pp, h, w = None, 0, 0
+        y = _labels(y, batch)
         if prob is not None:
-            prob = as_f32(prob)
-            if prob.ndim == 4 and prob.shape[-1] == 1:
-                prob = np.ascontiguousarray(prob[..., 0])
-            if prob.shape != y.shape:
-                raise ValueError('prob %s and y %s differ in shape' % (prob.shape, y.shape))
-            if batch is not None and int(batch) != prob.shape[0]:
-                raise ValueError('batch %d but prob holds %d slices' % (batch, prob.shape[0]))
-            (batch, h, w), pp = prob.shape, fptr(prob)
-        elif batch is None:
-            batch = len(y)
-        B = int(batch)
-        if len(y) != B:
-            raise ValueError('batch %d but y holds %d slices' % (B, len(y)))
-        h, w = y.shape[1:]               # without `prob` the library holds them against the size of the last forward
-        flags = np.ascontiguousarray(np.asarray(continues).astype(bool), np.uint8)
-        if flags.shape != (B,):
-            raise ValueError('continues must hold one flag per slice (%d), got shape %s' % (B, flags.shape))
-        args = (self.handle, pp, fptr(y), B, int(h), int(w), float(threshold), float(resize_factor), int(filter_size), int(min_area),
-                int(max_lesions), flags.ctypes.data_as(C.POINTER(C.c_uint8)))
-        hw = (C.c_int32 * 2)()
-        check(self.lib.dnnca_lesion_table_matched(*args, None, None, 0, None, None, hw))
-        oh, ow = hw[0], hw[1]
-        per_slice = min(int(max_lesions), (oh * ow + 1) // 2)
-        cap, lcap = B * per_slice, B * min(per_slice * per_slice, (oh * ow + 1) // 2)
-        masks = np.empty((B, oh, ow), np.uint8) if mask else None
+            prob = _host_prob(prob, y, True)
+        B, h, w = y.shape                # without `prob` the library holds h and w against the size of the last forward
+        flags = _continues(continues, B)
+        args = (self.handle, None if prob is None else fptr(prob), fptr(y), B, h, w, float(threshold), float(resize_factor),
+                int(filter_size), int(min_area), int(max_lesions), flags.ctypes.data_as(C.POINTER(C.c_uint8)))
+        hw, oh, ow = _analysed_plane(lambda hw: self.lib.dnnca_lesion_table_matched(*args, None, None, 0, None, None, hw))
 
-        def plane():
-            rows, totals, links = np.zeros(cap, _lib.LESION_ROW_DTYPE), np.zeros(B, np.int32), np.zeros(lcap, _lib.LESION_LINK_DTYPE)
-            out = _lib.LesionPlaneOut(rows.ctypes.data_as(C.POINTER(_lib.LesionRow)), cap, 0, totals.ctypes.data_as(C.POINTER(C.c_int32)),
-                                      links.ctypes.data_as(C.POINTER(_lib.LesionLink)), lcap, 0)
-            return rows, totals, links, out
-        rows, totals, links, pred = plane()
-        true_rows, true_totals, true_links, truth = plane()
-        pairs = np.zeros(lcap, _lib.LESION_PAIR_DTYPE)
-        po = _lib.LesionPairsOut(pairs.ctypes.data_as(C.POINTER(_lib.LesionPair)), lcap, 0)
+        def plane(mask):
+            rows, totals, links, masks = _lesion_table_buffers(B, oh, ow, max_lesions, mask, links=True)
+            out = _lib.LesionPlaneOut(rows.ctypes.data_as(C.POINTER(_lib.LesionRow)), len(rows), 0,
+                                      totals.ctypes.data_as(C.POINTER(C.c_int32)), links.ctypes.data_as(C.POINTER(_lib.LesionLink)),
+                                      len(links), 0)
+            return rows, totals, links, masks, out
+        rows, totals, links, masks, pred = plane(mask)
+        true_rows, true_totals, true_links, _, truth = plane(False)
+        pairs = np.zeros(len(links), _lib.LESION_PAIR_DTYPE)
+        po = _lib.LesionPairsOut(pairs.ctypes.data_as(C.POINTER(_lib.LesionPair)), len(pairs), 0)
         check(self.lib.dnnca_lesion_table_matched(*args, C.byref(pred), masks.ctypes.data_as(C.c_void_p) if mask else None,
                                                   masks.nbytes if mask else 0, C.byref(truth), C.byref(po), hw))
         return (rows[:pred.n_rows].copy(), totals, masks, links[:pred.n_links].copy(), true_rows[:truth.n_rows].copy(), true_totals,
@@ -782,28 +779,13 @@ class DeviceModel:
         side with the exact squared distance to the nearest boundary pixel of the other side, sorted by (slice, side, pixel); a
         slice with an empty outline or more than max_samples boundary pixels on a side gives none.  edges: uint8 [B, oh, ow], bit 0
         on the prediction's boundary, bit 1 on the label's (None with edges=False)."""
-        y = as_f32(y)
-        if y.ndim == 4 and y.shape[-1] == 1:
-            y = np.ascontiguousarray(y[..., 0])
-        if y.ndim != 3:
-            raise ValueError('y must be [B, h, w], got %s' % (y.shape,))
-        pp = None
+        y = _labels(y, batch)
         if prob is not None:
-            prob = as_f32(prob)
-            if prob.ndim == 4 and prob.shape[-1] == 1:
-                prob = np.ascontiguousarray(prob[..., 0])
-            if prob.shape != y.shape:
-                raise ValueError('prob %s and y %s differ in shape' % (prob.shape, y.shape))
-            pp = fptr(prob)
-        B = len(y) if batch is None else int(batch)
-        if len(y) != B:
-            raise ValueError('batch %d but y holds %d slices' % (B, len(y)))
-        h, w = y.shape[1:]               # without `prob` the library holds them against the size of the last forward
-        args = (self.handle, pp, fptr(y), B, int(h), int(w), float(threshold), float(resize_factor), int(filter_size), int(min_area),
-                int(max_samples))
-        hw = (C.c_int32 * 2)()
-        check(self.lib.dnnca_surface_distances(*args, None, None, 0, None, None, 0, hw))
-        oh, ow = hw[0], hw[1]
+            prob = _host_prob(prob, y, True)
+        B, h, w = y.shape                # without `prob` the library holds h and w against the size of the last forward
+        args = (self.handle, None if prob is None else fptr(prob), fptr(y), B, h, w, float(threshold), float(resize_factor),
+                int(filter_size), int(min_area), int(max_samples))
+        hw, oh, ow = _analysed_plane(lambda hw: self.lib.dnnca_surface_distances(*args, None, None, 0, None, None, 0, hw))
         cap = B * 2 * min(int(max_samples), oh * ow)
         counts = np.zeros((B, 5), np.int32)
         samples = np.zeros(max(cap, 0), _lib.SURFACE_SAMPLE_DTYPE)

@@ -849,6 +849,21 @@ class TFKerasModel:
         if attribution:
             attribution[2].append([int(step)] + casewise.attribution_summary(attribution[0], attribution[1], attr_shares, attr_gaps))
 
+    def _forwarded_splits(self, ds, tta_mask, spread=False, temperature=None):
+        """The analysis passes' walk over ds batches (x, y, paths, sliceIDs): empty batches skipped, the model grown to the batch,
+        the batch split by max_batch and every split forwarded with its probabilities left on the device (_forward_on_device).
+        Yields (the device model, x and y of the split, [(path, sliceID)] of its slices)."""
+        for x, y, paths, ids in ds:
+            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
+            if not len(x):
+                continue
+            self._ensure_capacity(len(x))
+            dm = self.device_model
+            for i in range(0, len(x), dm.max_batch):
+                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
+                _forward_on_device(dm, xb, tta_mask, spread=spread, temperature=temperature)
+                yield dm, xb, yb, list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
+
     def _exam_lesion_pass(self, ds, step, thresholds, iou, min_overlap, kw, tta_mask=None, temperature=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --exam_lesions`: per max_batch split one forward whose
         probabilities stay on the device and one DeviceModel.lesion_table_matched per threshold; then per threshold and exam
@@ -860,39 +875,31 @@ class TFKerasModel:
         (its probabilities and labels are kept on the host for that; a single threshold needs neither)."""
         several = len(thresholds) > 1
         found = [[] for _ in thresholds]     # per threshold and slice: (exam, slice, rows, total, links, true rows, total, links, pairs)
-        dm, last, tail, carry_of = None, None, None, None
-        for x, y, paths, ids in ds:
-            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
-            if not len(x):
-                continue
-            self._ensure_capacity(len(x))
-            if last is not None and dm is not self.device_model:
+        before, last, tail, carry_of = None, None, None, None
+        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature):
+            if last is not None and dm is not before:
                 # the row numbers of the slice before stayed behind on the model this batch outgrew: the chain breaks here
-                logging.warning('evaluate: the model was re-sized before slice %s of %s: it is not linked to the slice before', ids[0], paths[0])
+                logging.warning('evaluate: the model was re-sized before slice %s of %s: it is not linked to the slice before', pk[0][1], pk[0][0])
                 last = None
-            dm = self.device_model
-            for i in range(0, len(x), dm.max_batch):
-                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
-                pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
-                _forward_on_device(dm, xb, tta_mask, temperature=temperature)
-                continues = []
-                for p, k in pk:
-                    continues.append(last is not None and p == last[0] and int(k) == last[1] + 1)
-                    last = (p, int(k))
-                for ti, thr in enumerate(thresholds):
-                    if continues[0] and carry_of != ti:
-                        dm.lesion_table_matched(tail[1], prob=tail[0], continues=[False], threshold=thr, **kw)
-                    out = dm.lesion_table_matched(yb, batch=len(xb), continues=continues, threshold=thr, **kw)
-                    carry_of = ti
-                    by_slice = [[o[o['slice'] == b] for b in range(len(xb))] for o in (out[0], out[3], out[4], out[6], out[7])]
-                    for b, (p, k) in enumerate(pk):
-                        rows, links, true_rows, true_links, pairs = [s[b] for s in by_slice]
-                        found[ti].append((p, int(k), rows, out[1][b], [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in links],
-                                          true_rows, out[5][b],
-                                          [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in true_links],
-                                          [(int(q['row_true']), int(q['row']), int(q['overlap'])) for q in pairs]))
-                if several:
-                    tail = dm.last_prob(len(xb))[-1:], yb[-1:].reshape(1, *yb.shape[1:3])
+            before = dm
+            continues = []
+            for p, k in pk:
+                continues.append(last is not None and p == last[0] and int(k) == last[1] + 1)
+                last = (p, int(k))
+            for ti, thr in enumerate(thresholds):
+                if continues[0] and carry_of != ti:
+                    dm.lesion_table_matched(tail[1], prob=tail[0], continues=[False], threshold=thr, **kw)
+                out = dm.lesion_table_matched(yb, batch=len(xb), continues=continues, threshold=thr, **kw)
+                carry_of = ti
+                by_slice = [[o[o['slice'] == b] for b in range(len(xb))] for o in (out[0], out[3], out[4], out[6], out[7])]
+                for b, (p, k) in enumerate(pk):
+                    rows, links, true_rows, true_links, pairs = [s[b] for s in by_slice]
+                    found[ti].append((p, int(k), rows, out[1][b], [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in links],
+                                      true_rows, out[5][b],
+                                      [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in true_links],
+                                      [(int(q['row_true']), int(q['row']), int(q['overlap'])) for q in pairs]))
+            if several:
+                tail = dm.last_prob(len(xb))[-1:], yb[-1:].reshape(1, *yb.shape[1:3])
         results, cases, matches = [], [], []
         for thr, mine in zip(thresholds, found):
             lead = [int(step), repr(thr)]
@@ -920,21 +927,12 @@ class TFKerasModel:
         (surface_results.csv, surface_cases.csv, surface_slices.csv), each led by step and threshold.  No slice depends on another:
         nothing is carried between calls."""
         found = [[] for _ in thresholds]     # per threshold and slice: (exam, slice, counts, d2 of the prediction, d2 of the label)
-        for x, y, paths, ids in ds:
-            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
-            if not len(x):
-                continue
-            self._ensure_capacity(len(x))
-            dm = self.device_model
-            for i in range(0, len(x), dm.max_batch):
-                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
-                pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
-                _forward_on_device(dm, xb, tta_mask, temperature=temperature)
-                for ti, thr in enumerate(thresholds):
-                    counts, samples, _ = dm.surface_distances(yb, batch=len(xb), threshold=thr, **kw)
-                    for b, (p, k) in enumerate(pk):
-                        mine = samples[samples['slice'] == b]
-                        found[ti].append((p, int(k), counts[b], mine['d2'][mine['side'] == 0], mine['d2'][mine['side'] == 1]))
+        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature):
+            for ti, thr in enumerate(thresholds):
+                counts, samples, _ = dm.surface_distances(yb, batch=len(xb), threshold=thr, **kw)
+                for b, (p, k) in enumerate(pk):
+                    mine = samples[samples['slice'] == b]
+                    found[ti].append((p, int(k), counts[b], mine['d2'][mine['side'] == 0], mine['d2'][mine['side'] == 1]))
         results, cases, slices = [], [], []
         for thr, mine in zip(thresholds, found):
             lead = [int(step), repr(thr)]
@@ -954,20 +952,11 @@ class TFKerasModel:
         thresholds (in runs of 64); only the counts and sums per outcome come back.  Returns the new lines of
         (uncertainty_results.csv, uncertainty_slices.csv), each led by step and threshold."""
         found = [[] for _ in thresholds]     # per threshold and slice: (exam, slice, outcome entry)
-        for x, y, paths, ids in ds:
-            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
-            if not len(x):
-                continue
-            self._ensure_capacity(len(x))
-            dm = self.device_model
-            for i in range(0, len(x), dm.max_batch):
-                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
-                pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
-                _forward_on_device(dm, xb, tta_mask, spread=True, temperature=temperature)
-                for t0 in range(0, len(thresholds), 64):
-                    out = dm.spread_by_outcome(yb.reshape(len(xb), *yb.shape[1:3]), thresholds[t0:t0 + 64], batch=len(xb))
-                    for ti, per_slice in enumerate(out, t0):
-                        found[ti] += [(p, int(k), o) for (p, k), o in zip(pk, per_slice)]
+        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, spread=True, temperature=temperature):
+            for t0 in range(0, len(thresholds), 64):
+                out = dm.spread_by_outcome(yb.reshape(len(xb), *yb.shape[1:3]), thresholds[t0:t0 + 64], batch=len(xb))
+                for ti, per_slice in enumerate(out, t0):
+                    found[ti] += [(p, int(k), o) for (p, k), o in zip(pk, per_slice)]
         results, slices = [], []
         for thr, mine in zip(thresholds, found):
             lead = [int(step), repr(thr)]
@@ -982,19 +971,10 @@ class TFKerasModel:
         by step; the pooled values come from the tables and NLL rows of all slices summed (casewise.calibration_summary)."""
         at_1 = [float(t) for t in temperatures].index(1.0)
         bins, totals, nll, slices = [], [], [], []
-        for x, y, paths, ids in ds:
-            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
-            if not len(x):
-                continue
-            self._ensure_capacity(len(x))
-            dm = self.device_model
-            for i in range(0, len(x), dm.max_batch):
-                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
-                _forward_on_device(dm, xb, tta_mask, temperature=temperature)
-                b, t, n = dm.calibration(yb.reshape(len(xb), *yb.shape[1:3]), n_bins, temperatures, batch=len(xb))
-                bins.append(b), totals.append(t), nll.append(n)
-                slices += [[int(step)] + casewise.calibration_slice_values(p, k, b[j], t[j], n[j, at_1])
-                           for j, (p, k) in enumerate(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))]
+        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature):
+            b, t, n = dm.calibration(yb.reshape(len(xb), *yb.shape[1:3]), n_bins, temperatures, batch=len(xb))
+            bins.append(b), totals.append(t), nll.append(n)
+            slices += [[int(step)] + casewise.calibration_slice_values(p, k, b[j], t[j], n[j, at_1]) for j, (p, k) in enumerate(pk)]
         if not bins:
             return [], [], []
         result, lines = casewise.calibration_summary(np.concatenate(bins), np.concatenate(totals), temperatures, np.concatenate(nll))

@@ -58,8 +58,8 @@ def test_dense_environment_is_read_in_one_table_and_documented():
     assert not missing, 'not in DESIGN section 8: %s' % sorted(missing)
 
 
-STEP_FILES = ('model.hip', 'kernels_mfma.hip', 'kernels_fused.hip', 'kernels_fused_bwd.hip', 'kernels_first.hip', 'kernels_misc.hip',
-              'kernels_generic.hip', 'kernels_region.hip', 'kernels_sens.hip')
+STEP_FILES = ('model.hip', 'abi_analysis.hip', 'kernels_mfma.hip', 'kernels_fused.hip', 'kernels_fused_bwd.hip', 'kernels_first.hip',
+              'kernels_misc.hip', 'kernels_generic.hip', 'kernels_region.hip', 'kernels_sens.hip')
 
 
 def test_step_environment_is_read_once_per_model_and_documented():
