@@ -1,11 +1,12 @@
 // abi_analysis.hip -- the C ABI of everything that analyses probabilities (include/dnnca.h): test-time augmentation, pixel and region
-// confusion, the composite, lesion tables (plain, linked, with spread, matched), boundary distances, spread by outcome, calibration
-// and temperature scaling.  The kernels and their host drivers are in kernels_tta.hip, kernels_region.hip (region.h) and
+// confusion, the composite, lesion tables (plain, linked, with spread, matched), boundary distances, spread by outcome, calibration,
+// temperature scaling and the signed distance map of label planes.  The kernels and their host drivers are in kernels_tta.hip, kernels_region.hip (region.h) and
 // kernels_calib.hip (calib.h); what is here validates, resolves which planes are meant, stages them and calls the driver.
 #include "abi.h"
 
 #include <algorithm>
 
+#include "boundary.h"
 #include "calib.h"
 #include "kernels.h"
 #include "region.h"
@@ -248,9 +249,9 @@ enum Scratch { kScratchRegion, kScratchTtaIo };
 // nullptr: the model's own probabilities and spread plane, and the result goes where it came from.
 //   kScratchRegion  no host plane: nothing is touched.  Else the probabilities into the first buffer of region_inputs, the labels
 //                   (or, for an entry without labels, the spread) into the second
-//   kScratchTtaIo   with host probabilities one allocation for every host plane and, want_out, the result, in the order prob,
-//                   spread, y, out; with the model's own the labels go to M->y_stage
-static int plane_stage(Model* M, Scratch which, size_t n, const Planes& host, bool want_out, Planes* dev) {
+//   kScratchTtaIo   with host probabilities one allocation for every host plane and the want_out planes of the result, in the order
+//                   prob, spread, y, out; with the model's own the labels go to M->y_stage
+static int plane_stage(Model* M, Scratch which, size_t n, const Planes& host, int want_out, Planes* dev) {
     float* slot[4] = {nullptr, nullptr, nullptr, nullptr};          // prob, spread, y, out
     const float* src[3] = {host.prob, host.spread, host.y};
     if (which == kScratchRegion && (host.prob || host.y)) {
@@ -631,6 +632,30 @@ int dnnca_prob_temperature(void* model, const float* prob_hw, int batch, int h, 
     Planes dev;      // a host plane is scaled into a buffer behind it, the model's own in place
     DN_TRY(plane_stage(M, kScratchTtaIo, pl.n, {prob_hw, nullptr, nullptr, nullptr}, true, &dev));
     DN_TRY(prob_temperature(M, dev.prob, dev.out, pl.n, temperature, out_hw));
+    return M->flush_profile();
+}
+
+// ---- the signed distance map of label planes (kernels_boundary.hip) ----------------------------------------------------------
+int dnnca_signed_distance_of(void* model, const float* y_hw, int batch, int h, int w, float* phi_out, int32_t* d2_out) {
+    MODEL(model);
+    if (!y_hw || !phi_out) { set_error("signed distance: null y_hw / phi_out"); return DNNCA_EINVAL; }
+    Plane pl;
+    DN_TRY(plane_resolve(M, "signed distance", y_hw, batch, h, w, kPlaneBelow2G | kPlaneGridBatch, &pl));
+    if (pl.h > kSurfaceMaxSide || pl.w > kSurfaceMaxSide) {
+        set_error("signed distance: planes of %d x %d exceed %d pixels a side", pl.h, pl.w, kSurfaceMaxSide);
+        return DNNCA_EINVAL;
+    }
+    // the labels travel as the call's one host plane; behind them the map, the squares and the column pass: a scratch of the call's
+    // own, no tensor of the model and no map of a step
+    Planes dev;
+    DN_TRY(plane_stage(M, kScratchTtaIo, pl.n, {y_hw, nullptr, nullptr, nullptr}, 3, &dev));
+    float* phi = dev.out;
+    int32_t* d2 = reinterpret_cast<int32_t*>(dev.out + pl.n);
+    uint32_t* cols = reinterpret_cast<uint32_t*>(dev.out + 2 * pl.n);
+    boundary_transform(M, dev.prob, batch, pl.h, pl.w, cols, phi, d2_out ? d2 : nullptr);
+    HIP_TRY(hipMemcpyAsync(phi_out, phi, pl.n * 4, hipMemcpyDeviceToHost, M->stream));
+    if (d2_out) HIP_TRY(hipMemcpyAsync(d2_out, d2, pl.n * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
     return M->flush_profile();
 }
 

@@ -842,8 +842,7 @@ __global__ __launch_bounds__(RB) void k_lesion_match_carry(const int* __restrict
 //                   this pixel only).  It walks outward from x and stops where (x - x')^2 alone reaches the best so far.  The
 //                   samples of a wave take consecutive places of the list behind one atomic (the host sorts).  A slice whose edge
 //                   counts are 0 or above max_samples emits nothing: the counts are complete when this kernel starts
-// kSurfaceFar^2 + (ow - 1)^2 < 2^31 for planes of up to kSurfaceMaxSide pixels a side, and every real distance is below it.
-constexpr unsigned kSurfaceFar = 0x7fffu;
+// kSurfaceFar^2 + (ow - 1)^2 < 2^31 for planes of up to kSurfaceMaxSide pixels a side, and every real distance is below it (region.h).
 
 struct SurfaceSample {                   // dnnca_surface_sample
     int slice, side, pixel, d2;

@@ -17,6 +17,13 @@
 //   region_loss_grad       p, and dlogit when a backward pass follows
 // Every launch has a grid (blocks per image, images): a block works inside ONE image, so a partial belongs to one image by
 // construction, whatever H x W is.  No atomics: one row of partials per block, summed in ascending block order.
+//
+// The boundary term (dnnca_model_set_boundary_loss; Kervadec et al., MIDL 2019) rides these launches.  phi is the signed distance
+// map of the step's raw labels (kernels_boundary.hip), a constant of the step:
+//   S_b = sum_i p_i phi_i (double),  loss += l_bd mean_b S_b / (H W),  dloss/dlogit_i += l_bd phi_i p_i (1 - p_i) / (H W B)
+// S is a fifth block partial, region_loss_finish adds the term where it adds the Tversky term, and phi_i l_bd / (H W B) joins the
+// coefficient of p (1 - p).  The kernels that read phi are instantiations of their own (BD) with arguments of their own (RlWith):
+// a step without the term launches the code and the arguments it launched before.
 #include <algorithm>
 #include <cmath>
 
@@ -33,6 +40,15 @@ DEVINL void rl_ld4(float* d, const float* p) {
     d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
 }
 DEVINL void rl_st4(float* p, const float* s) { *reinterpret_cast<float4*>(p) = make_float4(s[0], s[1], s[2], s[3]); }
+
+// the arguments of a launch; with the boundary term, phi [B, hw] and bd_scale = l_bd / (H W B) behind them
+template <class A, bool BD>
+struct RlWith : A {};
+template <class A>
+struct RlWith<A, true> : A {
+    const float* phi;
+    double bd_scale;
+};
 
 // the positive-class weight of the step (kernels_generic.hip loss_weight; utils/losses.py:24-29)
 DEVINL float rl_weight(const dnnca_loss_cfg& cfg, double label_sum, double n_label) {
@@ -79,21 +95,23 @@ struct RlHeadFwdArgs {
 };
 
 // C = 3: one thread = 4 pixels of image blockIdx.y (three 16-byte loads of feat, one of y; 16-byte stores)
-template <int C>
-__global__ __launch_bounds__(256) void k_head_region_fwd(RlHeadFwdArgs p) {
+template <int C, bool BD>
+__global__ __launch_bounds__(256) void k_head_region_fwd(RlWith<RlHeadFwdArgs, BD> p) {
+    constexpr int PART = BD ? kRlPartBd : kRlPart;
     float wv[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) wv[c] = p.w[c];
     const float bias = p.bias[0];
     const size_t img = (size_t)blockIdx.y * p.hw;
     const int n4 = p.hw / 4;
-    double acc[kRlPart] = {0.0, 0.0, 0.0, 0.0};
+    double acc[PART] = {};
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const size_t px0 = img + (size_t)i * 4;
-        float f[4 * C], z[4], lg[4], sg[4];
+        float f[4 * C], z[4], lg[4], sg[4], ph[4];
 #pragma unroll
         for (int v = 0; v < C; ++v) rl_ld4(f + 4 * v, p.feat + px0 * C + 4 * v);
         rl_ld4(z, p.y + px0);
+        if constexpr (BD) rl_ld4(ph, p.phi + px0);
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
             float x = bias;
@@ -105,17 +123,18 @@ __global__ __launch_bounds__(256) void k_head_region_fwd(RlHeadFwdArgs p) {
             acc[0] += (double)sig * (double)z[px];
             acc[1] += (double)sig;
             acc[2] += (double)z[px];
+            if constexpr (BD) acc[4] += (double)sig * (double)ph[px];
         }
         rl_st4(p.logits + px0, lg);
         if (p.prob) rl_st4(p.prob + px0, sg);
     }
-    rl_block_store<kRlPart>(acc, p.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kRlPart);
+    rl_block_store<PART>(acc, p.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * PART);
 }
 
 // C = 16, 64: C / 4 adjacent lanes share a pixel (k_head_train_wide's layout: one 16-byte load per lane)
-template <int C>
-__global__ __launch_bounds__(256) void k_head_region_fwd_wide(RlHeadFwdArgs p) {
-    constexpr int G = C / 4, PPW = 64 / G, U = 4;
+template <int C, bool BD>
+__global__ __launch_bounds__(256) void k_head_region_fwd_wide(RlWith<RlHeadFwdArgs, BD> p) {
+    constexpr int G = C / 4, PPW = 64 / G, U = 4, PART = BD ? kRlPartBd : kRlPart;
     static_assert(C % 4 == 0 && 64 % G == 0, "lane groups");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, cq = lane % G, pl = lane / G;
     const float4 wv = *reinterpret_cast<const float4*>(p.w + 4 * cq);
@@ -123,18 +142,19 @@ __global__ __launch_bounds__(256) void k_head_region_fwd_wide(RlHeadFwdArgs p) {
     const size_t img = (size_t)blockIdx.y * p.hw;
     const float* feat = p.feat + img * C;
     const float* y = p.y + img;
-    double acc[kRlPart] = {0.0, 0.0, 0.0, 0.0};
+    double acc[PART] = {};
     for (int p0 = (blockIdx.x * 4 + wave) * (PPW * U); p0 < p.hw; p0 += gridDim.x * 4 * (PPW * U)) {
         float4 f[U];
-        float z[U];
+        float z[U], ph[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int px = p0 + u * PPW + pl;
             f[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            z[u] = 0.f;
+            z[u] = ph[u] = 0.f;
             if (px < p.hw) {
                 f[u] = *reinterpret_cast<const float4*>(feat + (size_t)px * C + 4 * cq);
                 z[u] = y[px];
+                if constexpr (BD) ph[u] = p.phi[img + px];
             }
         }
 #pragma unroll
@@ -151,10 +171,11 @@ __global__ __launch_bounds__(256) void k_head_region_fwd_wide(RlHeadFwdArgs p) {
                 acc[0] += (double)sig * (double)z[u];
                 acc[1] += (double)sig;
                 acc[2] += (double)z[u];
+                if constexpr (BD) acc[4] += (double)sig * (double)ph[u];
             }
         }
     }
-    rl_block_store<kRlPart>(acc, p.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kRlPart);
+    rl_block_store<PART>(acc, p.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * PART);
 }
 
 // ------------------------------------------------------------------------------------------------ the sums' finish
@@ -167,17 +188,19 @@ struct RlFinishArgs {
     int add_bce;           // the partials carry the weighted BCE sum: add l_ce x it to the loss slot
 };
 
-// one block.  stat[b]: 0 I, 1 P, 2 Y, 3 A, 4 C, 5 BCE sum, 6 1 - T
-__global__ __launch_bounds__(256) void k_region_loss_finish(RlFinishArgs p) {
+// one block.  stat[b]: 0 I, 1 P, 2 Y, 3 A, 4 C, 5 BCE sum, 6 1 - T, 7 S (the boundary term's sum of p phi)
+template <bool BD>
+__global__ __launch_bounds__(256) void k_region_loss_finish(RlWith<RlFinishArgs, BD> p) {
+    constexpr int PART = BD ? kRlPartBd : kRlPart;
     // one wave per (image, value): lane l adds rows l, l + 64, ... in ascending order, then the butterfly -- the same order every run
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int t = wave; t < p.B * kRlPart; t += 4) {
-        const int b = t / kRlPart, k = t % kRlPart;
-        const double* row = p.part + (size_t)b * p.gx * kRlPart + k;
+    for (int t = wave; t < p.B * PART; t += 4) {
+        const int b = t / PART, k = t % PART;
+        const double* row = p.part + (size_t)b * p.gx * PART + k;
         double s = 0.0;
-        for (int i = lane; i < p.gx; i += 64) s += row[(size_t)i * kRlPart];
+        for (int i = lane; i < p.gx; i += 64) s += row[(size_t)i * PART];
         s = rl_wave_sum(s);
-        if (lane == 0) p.stat[b * kRlStat + (k < 3 ? k : 5)] = s;
+        if (lane == 0) p.stat[b * kRlStat + (k < 3 ? k : k == 3 ? 5 : 7)] = s;
     }
     __threadfence_block();
     __syncthreads();
@@ -198,7 +221,13 @@ __global__ __launch_bounds__(256) void k_region_loss_finish(RlFinishArgs p) {
             r += p.stat[b * kRlStat + 6];
             bce += p.stat[b * kRlStat + 5];
         }
-        p.scalars[4] += (double)p.lam_r * r / (double)p.B;
+        double term = (double)p.lam_r * r / (double)p.B;
+        if constexpr (BD) {
+            double sb = 0.0;
+            for (int b = 0; b < p.B; ++b) sb += p.stat[b * kRlStat + 7];
+            term += p.bd_scale * sb;
+        }
+        p.scalars[4] += term;
         if (p.add_bce) p.scalars[3] += (double)p.lam_ce * bce;
     }
 }
@@ -222,11 +251,15 @@ struct RlHeadTrainArgs {
     int hw;
 };
 
-// dlogit of one pixel (and the pixel's weighted BCE into *bce when l_ce > 0)
-DEVINL float rl_dlogit(float x, float z, float wgt, float gscale, float lam_ce, float lam_r_b, float Ab, float Cb, float* bce) {
+// dlogit of one pixel (and the pixel's weighted BCE into *bce when l_ce > 0); BD: phi_i l_bd / (H W B) joins the coefficient of p (1 - p)
+template <bool BD>
+DEVINL float rl_dlogit(float x, float z, float wgt, float gscale, float lam_ce, float lam_r_b, float Ab, float Cb, float* bce,
+                       float phi = 0.f, float bd = 0.f) {
     const float e = expf(-fabsf(x));
     const float sig = x >= 0.f ? 1.0f / (1.0f + e) : e / (1.0f + e);
-    float dl = lam_r_b * (Cb - Ab * z) * (sig * (1.0f - sig));
+    float coef = lam_r_b * (Cb - Ab * z);
+    if constexpr (BD) coef = fmaf(phi, bd, coef);
+    float dl = coef * (sig * (1.0f - sig));
     if (lam_ce != 0.f) {
         const float mk = fmaf(z, wgt - 1.0f, 1.0f);
         *bce = (fmaxf(x, 0.f) - x * z + log1pf(e)) * mk;
@@ -237,14 +270,16 @@ DEVINL float rl_dlogit(float x, float z, float wgt, float gscale, float lam_ce, 
     return dl;
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void k_head_region_train(RlHeadTrainArgs p) {
+template <int C, bool BD>
+__global__ __launch_bounds__(256) void k_head_region_train(RlWith<RlHeadTrainArgs, BD> p) {
     __shared__ float red[4][C + 2];
     float wv[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) wv[c] = p.w[c];
     const float wgt = rl_weight(p.cfg, p.scalars[0], p.n_label);
     const float Ab = (float)p.stat[blockIdx.y * kRlStat + 3], Cb = (float)p.stat[blockIdx.y * kRlStat + 4];
+    float bd = 0.f;
+    if constexpr (BD) bd = (float)p.bd_scale;
     const size_t img = (size_t)blockIdx.y * p.hw;
     const int n4 = p.hw / 4;
     float sdw[C], sdb = 0.f, sloss = 0.f;
@@ -252,15 +287,16 @@ __global__ __launch_bounds__(256) void k_head_region_train(RlHeadTrainArgs p) {
     for (int c = 0; c < C; ++c) sdw[c] = 0.f;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const size_t px0 = img + (size_t)i * 4;
-        float f[4 * C], z[4], lg[4], df[4 * C];
+        float f[4 * C], z[4], lg[4], df[4 * C], ph[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int v = 0; v < C; ++v) rl_ld4(f + 4 * v, p.feat + px0 * C + 4 * v);
         rl_ld4(z, p.y + px0);
         rl_ld4(lg, p.logits + px0);
+        if constexpr (BD) rl_ld4(ph, p.phi + px0);
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
             float bce;
-            const float dl = rl_dlogit(lg[px], z[px], wgt, p.gscale, p.lam_ce, p.lam_r_b, Ab, Cb, &bce);
+            const float dl = rl_dlogit<BD>(lg[px], z[px], wgt, p.gscale, p.lam_ce, p.lam_r_b, Ab, Cb, &bce, ph[px], bd);
             sloss += bce;
             sdb += dl;
 #pragma unroll
@@ -294,8 +330,8 @@ __global__ __launch_bounds__(256) void k_head_region_train(RlHeadTrainArgs p) {
     }
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void k_head_region_train_wide(RlHeadTrainArgs p) {
+template <int C, bool BD>
+__global__ __launch_bounds__(256) void k_head_region_train_wide(RlWith<RlHeadTrainArgs, BD> p) {
     constexpr int G = C / 4, PPW = 64 / G, U = 4;
     static_assert(C % 4 == 0 && 64 % G == 0, "lane groups");
     __shared__ float red[4][C + 2];
@@ -303,6 +339,8 @@ __global__ __launch_bounds__(256) void k_head_region_train_wide(RlHeadTrainArgs 
     const float4 wv = *reinterpret_cast<const float4*>(p.w + 4 * cq);
     const float wgt = rl_weight(p.cfg, p.scalars[0], p.n_label);
     const float Ab = (float)p.stat[blockIdx.y * kRlStat + 3], Cb = (float)p.stat[blockIdx.y * kRlStat + 4];
+    float bd = 0.f;
+    if constexpr (BD) bd = (float)p.bd_scale;
     const size_t img = (size_t)blockIdx.y * p.hw;
     const float* feat = p.feat + img * C;
     float* dfeat = p.dfeat + img * C;
@@ -310,16 +348,17 @@ __global__ __launch_bounds__(256) void k_head_region_train_wide(RlHeadTrainArgs 
     float sdb = 0.f, sloss = 0.f;
     for (int p0 = (blockIdx.x * 4 + wave) * (PPW * U); p0 < p.hw; p0 += gridDim.x * 4 * (PPW * U)) {
         float4 f[U];
-        float z[U], lg[U];
+        float z[U], lg[U], ph[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int px = p0 + u * PPW + pl;
             f[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            z[u] = lg[u] = 0.f;
+            z[u] = lg[u] = ph[u] = 0.f;
             if (px < p.hw) {
                 f[u] = *reinterpret_cast<const float4*>(feat + (size_t)px * C + 4 * cq);
                 z[u] = p.y[img + px];
                 lg[u] = p.logits[img + px];
+                if constexpr (BD) ph[u] = p.phi[img + px];
             }
         }
 #pragma unroll
@@ -327,7 +366,7 @@ __global__ __launch_bounds__(256) void k_head_region_train_wide(RlHeadTrainArgs 
             const int px = p0 + u * PPW + pl;
             const bool ok = px < p.hw;
             float bce;
-            float dl = rl_dlogit(lg[u], z[u], wgt, p.gscale, p.lam_ce, p.lam_r_b, Ab, Cb, &bce);
+            float dl = rl_dlogit<BD>(lg[u], z[u], wgt, p.gscale, p.lam_ce, p.lam_r_b, Ab, Cb, &bce, ph[u], bd);
             if (!ok) dl = 0.f;
             if (ok && cq == 0) {
                 sloss += bce;
@@ -377,22 +416,24 @@ struct RlLogitArgs {
 };
 
 // VEC: hw is a multiple of 4 -- one thread = 4 pixels, 16-byte accesses; else one pixel
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_region_sums(RlLogitArgs p) {
-    constexpr int PX = VEC ? 4 : 1;
+template <bool VEC, bool BD>
+__global__ __launch_bounds__(256) void k_region_sums(RlWith<RlLogitArgs, BD> p) {
+    constexpr int PX = VEC ? 4 : 1, PART = BD ? kRlPartBd : kRlPart;
     const float wgt = rl_weight(p.cfg, p.scalars[0], p.n_label);
     const size_t img = (size_t)blockIdx.y * p.hw;
     const int n = p.hw / PX;
-    double acc[kRlPart] = {0.0, 0.0, 0.0, 0.0};
+    double acc[PART] = {};
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const size_t px0 = img + (size_t)i * PX;
-        float x[PX], z[PX];
+        float x[PX], z[PX], ph[PX];
         if constexpr (VEC) {
             rl_ld4(x, p.logits + px0);
             rl_ld4(z, p.y + px0);
+            if constexpr (BD) rl_ld4(ph, p.phi + px0);
         } else {
             x[0] = p.logits[px0];
             z[0] = p.y[px0];
+            if constexpr (BD) ph[0] = p.phi[px0];
         }
 #pragma unroll
         for (int k = 0; k < PX; ++k) {
@@ -401,36 +442,41 @@ __global__ __launch_bounds__(256) void k_region_sums(RlLogitArgs p) {
             acc[0] += (double)sig * (double)z[k];
             acc[1] += (double)sig;
             acc[2] += (double)z[k];
+            if constexpr (BD) acc[4] += (double)sig * (double)ph[k];
             if (p.lam_ce != 0.f) {
                 const float mk = fmaf(z[k], wgt - 1.0f, 1.0f);
                 acc[3] += (double)((fmaxf(x[k], 0.f) - x[k] * z[k] + log1pf(e)) * mk);
             }
         }
     }
-    rl_block_store<kRlPart>(acc, p.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kRlPart);
+    rl_block_store<PART>(acc, p.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * PART);
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void k_region_loss_grad(RlLogitArgs p) {
+template <bool VEC, bool BD>
+__global__ __launch_bounds__(256) void k_region_loss_grad(RlWith<RlLogitArgs, BD> p) {
     constexpr int PX = VEC ? 4 : 1;
+    float bd = 0.f;
+    if constexpr (BD) bd = (float)p.bd_scale;
     const float wgt = rl_weight(p.cfg, p.scalars[0], p.n_label);
     const float Ab = (float)p.stat[blockIdx.y * kRlStat + 3], Cb = (float)p.stat[blockIdx.y * kRlStat + 4];
     const size_t img = (size_t)blockIdx.y * p.hw;
     const int n = p.hw / PX;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const size_t px0 = img + (size_t)i * PX;
-        float x[PX], z[PX], dl[PX], sg[PX];
+        float x[PX], z[PX], dl[PX], sg[PX], ph[PX] = {};
         if constexpr (VEC) {
             rl_ld4(x, p.logits + px0);
             rl_ld4(z, p.y + px0);
+            if constexpr (BD) rl_ld4(ph, p.phi + px0);
         } else {
             x[0] = p.logits[px0];
             z[0] = p.y[px0];
+            if constexpr (BD) ph[0] = p.phi[px0];
         }
 #pragma unroll
         for (int k = 0; k < PX; ++k) {
             float bce;
-            dl[k] = rl_dlogit(x[k], z[k], wgt, p.gscale, p.lam_ce, p.lam_r_b, Ab, Cb, &bce);
+            dl[k] = rl_dlogit<BD>(x[k], z[k], wgt, p.gscale, p.lam_ce, p.lam_r_b, Ab, Cb, &bce, ph[k], bd);
             sg[k] = sigmoid_of_logit(x[k]);
         }
         if constexpr (VEC) {
@@ -449,9 +495,25 @@ int rl_blocks_per_image(int hw, int per_block, int B) {
     return std::max(1, std::min(want, kRlMaxBlocks / B));
 }
 
-void rl_finish(Model* m, int B, int gx, bool add_bce) {
+// what a BD launch gets behind its arguments
+template <class A>
+void rl_with_boundary(Model* m, int B, int hw, RlWith<A, true>& a) {
+    a.phi = m->boundary.phi;
+    a.bd_scale = (double)m->boundary.weight / ((double)hw * B);
+}
+template <class A>
+void rl_with_boundary(Model*, int, int, RlWith<A, false>&) {}
+
+// in front of a LAUNCH: the plan shows a BD launch as the variant `bd` of its name
+template <bool BD>
+void rl_variant(Model* m) {
+    if (BD) m->set_variant("bd");
+}
+
+template <bool BD>
+void rl_finish(Model* m, int B, int hw, int gx, bool add_bce) {
     const dnnca_region_loss& c = m->region_loss.cfg;
-    RlFinishArgs f;
+    RlWith<RlFinishArgs, BD> f;
     f.part = m->region_loss.ws + (size_t)m->desc.max_batch * kRlStat;
     f.stat = m->region_loss.ws;
     f.scalars = m->scalars;
@@ -463,8 +525,14 @@ void rl_finish(Model* m, int B, int gx, bool add_bce) {
     f.beta = c.beta;
     f.smooth = c.smooth;
     f.add_bce = add_bce ? 1 : 0;
-    LAUNCH(m, "region_loss_finish", 8.0 * kRlPart * B * gx, 0, hipLaunchKernelGGL(k_region_loss_finish, dim3(1), dim3(256), 0, m->stream, f));
-    if (!m->dry) m->region_loss.sums_batch = B;
+    rl_with_boundary(m, B, hw, f);
+    rl_variant<BD>(m);
+    LAUNCH(m, "region_loss_finish", 8.0 * (BD ? kRlPartBd : kRlPart) * B * gx, 0,
+           hipLaunchKernelGGL(k_region_loss_finish<BD>, dim3(1), dim3(256), 0, m->stream, f));
+    if (!m->dry) {
+        m->region_loss.sums_batch = B;
+        m->boundary.sums_batch = BD ? B : 0;
+    }
 }
 
 }  // namespace
@@ -481,14 +549,16 @@ const char* region_loss_invalid(const dnnca_region_loss& c) {
 int region_loss_prepare(Model* m) {
     if (m->region_loss.ws) return DNNCA_OK;
     if (m->desc.max_batch > kRlMaxBlocks) { set_error("region loss: max_batch %d above %d", m->desc.max_batch, kRlMaxBlocks); return DNNCA_EINVAL; }
-    const size_t n = (size_t)m->desc.max_batch * kRlStat + (size_t)kRlMaxBlocks * kRlPart;
+    const size_t n = (size_t)m->desc.max_batch * kRlStat + (size_t)kRlMaxBlocks * kRlPartBd;
     DN_TRY(m->alloc((void**)&m->region_loss.ws, n * 8));
     HIP_TRY(hipMemsetAsync(m->region_loss.ws, 0, n * 8, m->stream));
     return DNNCA_OK;
 }
 
-bool region_loss_head_train(Model* m, int B, Op& o, const float* y, const dnnca_loss_cfg& cfg, float gscale) {
-    if (!fast_head_supported(m, o) || !m->region_loss.ws) return false;
+namespace {
+
+template <bool BD>
+bool rl_head_train(Model* m, int B, Op& o, const float* y, const dnnca_loss_cfg& cfg, float gscale) {
     const dnnca_region_loss& rc = m->region_loss.cfg;
     const int C = o.inA.d.C, hw = o.inA.d.H * o.inA.d.W;
     // pixels a block takes per trip: 256 threads x 4 pixels (C = 3); 4 waves x (64 / (C / 4)) pixels x 4 loads (wide)
@@ -496,7 +566,8 @@ bool region_loss_head_train(Model* m, int B, Op& o, const float* y, const dnnca_
     const int gx = rl_blocks_per_image(hw, per_block, B);
     const double npix = (double)B * hw, fb = 4.0 * npix * C;
     const bool pm = m->train_metrics_on();
-    RlHeadFwdArgs a;
+    RlWith<RlHeadFwdArgs, BD> a;
+    rl_with_boundary(m, B, hw, a);
     a.feat = o.inA.d.p;
     a.y = y;
     a.w = m->p + o.w_off;
@@ -505,7 +576,8 @@ bool region_loss_head_train(Model* m, int B, Op& o, const float* y, const dnnca_
     a.prob = pm ? m->prob : nullptr;
     a.part = m->region_loss.ws + (size_t)m->desc.max_batch * kRlStat;
     a.hw = hw;
-    RlHeadTrainArgs t;
+    RlWith<RlHeadTrainArgs, BD> t;
+    rl_with_boundary(m, B, hw, t);
     t.feat = o.inA.d.p;
     t.y = y;
     t.logits = m->logits;
@@ -525,11 +597,13 @@ bool region_loss_head_train(Model* m, int B, Op& o, const float* y, const dnnca_
     const dim3 grid(gx, B);
 #define RL_HEAD_CASE(c, FWD, TRAIN)                                                                                           \
     if (C == c) {                                                                                                              \
-        LAUNCH(m, "head_region_fwd_" #c, fb + 4.0 * npix * (pm ? 3 : 2), 2.0 * npix * c + 12.0 * npix,                         \
-               hipLaunchKernelGGL(FWD<c>, grid, dim3(256), 0, m->stream, a));                                                  \
-        rl_finish(m, B, gx, false);                                                                                            \
-        LAUNCH(m, "head_region_train_" #c, 2 * fb + 8.0 * npix, 4.0 * npix * c + 30.0 * npix,                                  \
-               hipLaunchKernelGGL(TRAIN<c>, grid, dim3(256), 0, m->stream, t));                                                \
+        rl_variant<BD>(m);                                                                                                     \
+        LAUNCH(m, "head_region_fwd_" #c, fb + 4.0 * npix * ((pm ? 3 : 2) + BD), 2.0 * npix * c + 12.0 * npix,                  \
+               hipLaunchKernelGGL((FWD<c, BD>), grid, dim3(256), 0, m->stream, a));                                            \
+        rl_finish<BD>(m, B, hw, gx, false);                                                                                    \
+        rl_variant<BD>(m);                                                                                                     \
+        LAUNCH(m, "head_region_train_" #c, 2 * fb + 4.0 * npix * (2 + BD), 4.0 * npix * c + 30.0 * npix,                       \
+               hipLaunchKernelGGL((TRAIN<c, BD>), grid, dim3(256), 0, m->stream, t));                                          \
         fast_head_partials_done(m, c, gx * B, m->g + o.w_off, m->g + o.b_off);                                                 \
         return true;                                                                                                           \
     }
@@ -540,14 +614,15 @@ bool region_loss_head_train(Model* m, int B, Op& o, const float* y, const dnnca_
     return false;
 }
 
-int region_loss_from_logits(Model* m, int B, const float* y, const dnnca_loss_cfg& cfg, float gscale, float* dlogits) {
-    if (!m->region_loss.ws) { set_error("internal: region loss without its workspace"); return DNNCA_ESTATE; }
+template <bool BD>
+void rl_from_logits(Model* m, int B, const float* y, const dnnca_loss_cfg& cfg, float gscale, float* dlogits) {
     const dnnca_region_loss& rc = m->region_loss.cfg;
     const int hw = m->outH * m->outW;
     const bool vec = hw % 4 == 0;
     const int gx = rl_blocks_per_image(hw, vec ? 1024 : 256, B);
     const double npix = (double)B * hw;
-    RlLogitArgs a;
+    RlWith<RlLogitArgs, BD> a;
+    rl_with_boundary(m, B, hw, a);
     a.logits = m->logits;
     a.y = y;
     a.dlogits = dlogits;
@@ -562,12 +637,29 @@ int region_loss_from_logits(Model* m, int B, const float* y, const dnnca_loss_cf
     a.lam_r_b = rc.region_weight / (float)B;
     a.hw = hw;
     const dim3 grid(gx, B);
-    if (vec) LAUNCH(m, "region_sums", 8.0 * npix, 20.0 * npix, hipLaunchKernelGGL(k_region_sums<true>, grid, dim3(256), 0, m->stream, a));
-    else LAUNCH(m, "region_sums", 8.0 * npix, 20.0 * npix, hipLaunchKernelGGL(k_region_sums<false>, grid, dim3(256), 0, m->stream, a));
-    rl_finish(m, B, gx, true);
-    const double gb = 4.0 * npix * (dlogits ? 4 : 3);
-    if (vec) LAUNCH(m, "region_loss_grad", gb, 30.0 * npix, hipLaunchKernelGGL(k_region_loss_grad<true>, grid, dim3(256), 0, m->stream, a));
-    else LAUNCH(m, "region_loss_grad", gb, 30.0 * npix, hipLaunchKernelGGL(k_region_loss_grad<false>, grid, dim3(256), 0, m->stream, a));
+    const double sb = 4.0 * npix * (2 + BD);
+    rl_variant<BD>(m);
+    if (vec) LAUNCH(m, "region_sums", sb, 20.0 * npix, hipLaunchKernelGGL((k_region_sums<true, BD>), grid, dim3(256), 0, m->stream, a));
+    else LAUNCH(m, "region_sums", sb, 20.0 * npix, hipLaunchKernelGGL((k_region_sums<false, BD>), grid, dim3(256), 0, m->stream, a));
+    rl_finish<BD>(m, B, hw, gx, true);
+    const double gb = 4.0 * npix * ((dlogits ? 4 : 3) + BD);
+    rl_variant<BD>(m);
+    if (vec) LAUNCH(m, "region_loss_grad", gb, 30.0 * npix, hipLaunchKernelGGL((k_region_loss_grad<true, BD>), grid, dim3(256), 0, m->stream, a));
+    else LAUNCH(m, "region_loss_grad", gb, 30.0 * npix, hipLaunchKernelGGL((k_region_loss_grad<false, BD>), grid, dim3(256), 0, m->stream, a));
+}
+
+}  // namespace
+
+// with the boundary term on (Model::boundary, its phi already written for this step) the BD instantiations run
+bool region_loss_head_train(Model* m, int B, Op& o, const float* y, const dnnca_loss_cfg& cfg, float gscale) {
+    if (!fast_head_supported(m, o) || !m->region_loss.ws) return false;
+    return m->boundary.weight > 0.f ? rl_head_train<true>(m, B, o, y, cfg, gscale) : rl_head_train<false>(m, B, o, y, cfg, gscale);
+}
+
+int region_loss_from_logits(Model* m, int B, const float* y, const dnnca_loss_cfg& cfg, float gscale, float* dlogits) {
+    if (!m->region_loss.ws) { set_error("internal: region loss without its workspace"); return DNNCA_ESTATE; }
+    if (m->boundary.weight > 0.f) rl_from_logits<true>(m, B, y, cfg, gscale, dlogits);
+    else rl_from_logits<false>(m, B, y, cfg, gscale, dlogits);
     return DNNCA_OK;
 }
 

@@ -146,6 +146,10 @@ struct Model {
     // region (Tversky) term of the loss (dnnca_model_set_region_loss, kernels_region_loss.hip).  ws: per image kRlStat doubles
     // (I, P, Y, A, C of the last step), then the block partials of the step's sums; sums_batch: images of the last step that wrote it
     struct RegionLoss { bool on = false; dnnca_region_loss cfg{}; double* ws = nullptr; int sums_batch = 0; } region_loss;
+    // boundary term of the loss (dnnca_model_set_boundary_loss): weight > 0 is on, and only beside the region loss, whose launches
+    // it rides.  phi [max_batch, outH, outW]: the signed distance map of the last step's raw labels (kernels_boundary.hip), cols its
+    // column pass; both allocated once.  batch: images of the last step that wrote phi; sums_batch: ... that wrote S into region_loss.ws
+    struct Boundary { float weight = 0.f; float* phi = nullptr; uint32_t* cols = nullptr; int batch = 0, sums_batch = 0; } boundary;
     void* warp_scratch = nullptr;        // control points + spline weights of dnnca_warp_f32
     size_t warp_scratch_bytes = 0;
     void* aug_scratch = nullptr;         // per-image augmentation draws + channel sums (kernels_aug.hip)

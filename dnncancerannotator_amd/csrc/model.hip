@@ -15,6 +15,7 @@
 #include "kernels.h"
 #include "region.h"
 #include "region_loss.h"
+#include "boundary.h"
 #include "sens.h"
 #include "attr.h"
 
@@ -954,6 +955,7 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
     if (!(backward && head_in_conv.done && y_dev == head_in_conv.y))
         head_pending.partials = nullptr;    // leftovers of a step that stopped on an error (not: the head that just ran in the forward pass)
     fin_pending.on = false;
+    const float* y_raw = y_dev;         // the boundary term's distance map comes from the labels before the blur
     if (cfg.label_smoothing) {          // utils/losses.py:62-67: every later use of y_true (positive rate, assertions, loss) sees the blurred labels
         if (!y_smooth) DN_TRY(alloc((void**)&y_smooth, (size_t)desc.max_batch * outH * outW * 4));
         if (!fast_label_smooth(this, B, outH, outW, y_dev, y_smooth, cfg.label_smoothing_filter_size, cfg.label_smoothing_sigma)) {
@@ -985,6 +987,10 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
     if (region_loss.on) {
         // the region (Tversky) term: sums per image first, then the gradient (kernels_region_loss.hip)
         if (head_was_in_conv) { set_error("internal: region loss behind a head that ran in the forward pass"); return DNNCA_ESTATE; }
+        if (boundary.weight > 0.f) {     // the signed distance map of this step's raw labels, a constant of the step (kernels_boundary.hip)
+            boundary_transform(this, y_raw, B, outH, outW, boundary.cols, boundary.phi, nullptr);
+            if (!dry) boundary.batch = B;
+        }
         if (backward && head_deferred) {
             if (!region_loss_head_train(this, B, ops.back(), y_dev, cfg, gscale)) {
                 set_error("internal: deferred head has no region-loss kernel");
@@ -1972,7 +1978,12 @@ int dnnca_model_set_region_loss(void* model, const dnnca_region_loss* cfg) {
     HIP_TRY(hipStreamSynchronize(M->stream));          // steps in flight keep the loss they were enqueued with
     M->region_loss.on = false;
     M->region_loss.sums_batch = 0;
-    if (!cfg) return DNNCA_OK;
+    M->boundary.sums_batch = 0;
+    if (!cfg) {                                         // the boundary term rides the region loss's launches: it goes with them
+        M->boundary.weight = 0.f;
+        M->boundary.batch = 0;
+        return DNNCA_OK;
+    }
     DN_TRY(region_loss_prepare(M));
     M->region_loss.cfg = *cfg;
     M->region_loss.on = true;
@@ -1992,6 +2003,57 @@ int dnnca_region_loss_sums(void* model, int batch, double* out) {
     HIP_TRY(hipStreamSynchronize(M->stream));
     for (int b = 0; b < batch; ++b)
         for (int k = 0; k < 3; ++k) out[b * 3 + k] = st[(size_t)b * kRlStat + k];
+    return DNNCA_OK;
+}
+
+// ---- boundary (signed-distance) term of the loss (kernels_boundary.hip, kernels_region_loss.hip) ----------------------------
+int dnnca_model_set_boundary_loss(void* model, float boundary_weight) {
+    MODEL(model);
+    if (!(std::isfinite(boundary_weight) && boundary_weight >= 0.f)) { set_error("boundary loss: boundary_weight must be >= 0 and finite"); return DNNCA_EINVAL; }
+    if (!M->region_loss.on) {
+        set_error("boundary loss: no region loss is set (dnnca_model_set_region_loss): the term rides its launches");
+        return DNNCA_EINVAL;
+    }
+    if (M->outH > kSurfaceMaxSide || M->outW > kSurfaceMaxSide) {
+        set_error("boundary loss: labels of %d x %d exceed %d pixels a side", M->outH, M->outW, kSurfaceMaxSide);
+        return DNNCA_EINVAL;
+    }
+    HIP_TRY(hipStreamSynchronize(M->stream));          // steps in flight keep the loss they were enqueued with
+    if (boundary_weight > 0.f && !M->boundary.phi) {
+        const size_t n = (size_t)M->desc.max_batch * M->outH * M->outW;
+        DN_TRY(M->alloc((void**)&M->boundary.cols, n * 4));
+        DN_TRY(M->alloc((void**)&M->boundary.phi, n * 4));
+    }
+    M->boundary.weight = boundary_weight;
+    M->boundary.batch = M->boundary.sums_batch = 0;
+    return DNNCA_OK;
+}
+
+int dnnca_boundary_loss_sums(void* model, int batch, double* out) {
+    MODEL(model);
+    if (!out) { set_error("null boundary-loss sums"); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
+    if (!M->region_loss.ws || M->boundary.sums_batch < batch) {
+        set_error("no step with the boundary loss has run on %d images (dnnca_model_set_boundary_loss)", batch);
+        return DNNCA_ESTATE;
+    }
+    std::vector<double> st((size_t)batch * kRlStat);
+    HIP_TRY(hipMemcpyAsync(st.data(), M->region_loss.ws, st.size() * 8, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    for (int b = 0; b < batch; ++b) out[b] = st[(size_t)b * kRlStat + 7];
+    return DNNCA_OK;
+}
+
+int dnnca_boundary_distance(void* model, int batch, float* phi_out) {
+    MODEL(model);
+    if (!phi_out) { set_error("null boundary distance map"); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
+    if (!M->boundary.phi || M->boundary.batch < batch) {
+        set_error("no step with the boundary loss has run on %d images (dnnca_model_set_boundary_loss)", batch);
+        return DNNCA_ESTATE;
+    }
+    HIP_TRY(hipMemcpyAsync(phi_out, M->boundary.phi, (size_t)batch * M->outH * M->outW * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
     return DNNCA_OK;
 }
 

@@ -10,6 +10,7 @@ namespace dnnca {
 constexpr int kRegionMaxThr = 64;        // thresholds per spec (two 32-bit mask words per pixel)
 constexpr int kRegionMaxK = 15;          // morphological filter size
 constexpr int kSurfaceMaxSide = 16384;   // boundary distances: analysed planes of up to this many pixels a side (squares in int32)
+constexpr unsigned kSurfaceFar = 0x7fffu;   // column distance "none" of surface_cols / boundary_cols: above every real distance
 
 // one validated spec: the caller's thresholds (in their order), IoU threshold, resize factor, filter size, and the resized plane
 struct RegionSpecHost {

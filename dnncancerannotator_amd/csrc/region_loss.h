@@ -4,9 +4,10 @@
 
 namespace dnnca {
 
-constexpr int kRlStat = 8;             // doubles per image in Model::region_loss.ws: I, P, Y, A, C (three spare)
+constexpr int kRlStat = 8;             // doubles per image in Model::region_loss.ws: I, P, Y, A, C, BCE sum, 1 - T, S (boundary term)
 constexpr int kRlMaxBlocks = 2048;     // blocks of a sums / head launch over the whole batch (Model::head_partials holds as many rows)
 constexpr int kRlPart = 4;             // doubles per block partial: I, P, Y, weighted BCE sum
+constexpr int kRlPartBd = 5;           // ... with the boundary term (Model::boundary): and S = sum p phi
 
 // nullptr when the values are accepted, else what is wrong with them
 const char* region_loss_invalid(const dnnca_region_loss& c);

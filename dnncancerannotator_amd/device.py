@@ -514,6 +514,40 @@ class DeviceModel:
         check(self.lib.dnnca_region_loss_sums(self.handle, batch, out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
 
+    # ---- boundary (signed-distance) term of the loss (losses.BoundaryCrossentropy) --------------------------------------
+    def set_boundary_loss(self, boundary_weight):
+        """every later train / eval step adds boundary_weight * mean_b sum_i p_i phi_i / (H W), phi the signed Euclidean distance map
+        of the step's raw labels (dnnca_model_set_boundary_loss).  Needs set_region_loss first (the term rides its launches); 0
+        switches it off, and so does set_region_loss(None)"""
+        check(self.lib.dnnca_model_set_boundary_loss(self.handle, float(boundary_weight)))
+
+    def boundary_loss_sums(self, batch=None):
+        """[batch] float64: S_b = sum_i p_i phi_i per image of the last step that ran with the boundary term"""
+        batch = self.max_batch if batch is None else int(batch)
+        out = np.empty(batch, np.float64)
+        check(self.lib.dnnca_boundary_loss_sums(self.handle, batch, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def boundary_distance(self, batch=None):
+        """[batch, H, W] float32: the signed distance map phi of the last step that ran with the boundary term"""
+        batch = self.max_batch if batch is None else int(batch)
+        out = np.empty((batch, self.in_shape[0], self.in_shape[1]), np.float32)
+        check(self.lib.dnnca_boundary_distance(self.handle, batch, fptr(out)))
+        return out
+
+    def signed_distance_of(self, y, want_d2=False):
+        """the signed distance map of label planes y [batch, h, w] of any size up to 16384 a side (batch within max_batch), by the
+        kernels of the boundary term: phi float32 [batch, h, w], and with want_d2 (phi, d2): the exact squared distances, int32 (0
+        where the other set is empty).  Touches nothing of the model"""
+        y = np.ascontiguousarray(y, np.float32)
+        if y.ndim != 3:
+            raise ValueError('signed_distance_of: y must be [batch, h, w], got shape %s' % (y.shape,))
+        phi = np.empty(y.shape, np.float32)
+        d2 = np.empty(y.shape, np.int32) if want_d2 else None
+        check(self.lib.dnnca_signed_distance_of(self.handle, fptr(y), y.shape[0], y.shape[1], y.shape[2], fptr(phi),
+                                                d2.ctypes.data_as(C.POINTER(C.c_int32)) if want_d2 else None))
+        return (phi, d2) if want_d2 else phi
+
     def last_step_out(self):
         out = _lib.StepOut()
         check(self.lib.dnnca_last_step_out(self.handle, C.byref(out)))

@@ -210,9 +210,12 @@ class TFKerasModel:
 
     def _set_region_loss(self, dm):
         """loss: TverskyCrossentropy / DiceCrossentropy -- the region term is stored in the device model once, and every later
-        train / eval step reads it there; any other loss leaves the model as it was built (no call)"""
+        train / eval step reads it there; any other loss leaves the model as it was built (no call).  BoundaryCrossentropy: the
+        boundary term behind it, which rides the region term's launches"""
         if isinstance(self.loss, custom_losses.TverskyCrossentropy):
             dm.set_region_loss(self.loss.region_cfg())
+        if isinstance(self.loss, custom_losses.BoundaryCrossentropy):
+            dm.set_boundary_loss(self.loss.boundary_cfg())
 
     def _join_ranks(self):
         if self.ctx.world > 1:

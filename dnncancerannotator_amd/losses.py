@@ -77,9 +77,36 @@ class DiceCrossentropy(TverskyCrossentropy):
         super().__init__(**kwargs)
 
 
+class BoundaryCrossentropy(TverskyCrossentropy):
+    """TverskyCrossentropy + boundary_weight * mean_b sum_i p_i phi_i / (H W): the boundary loss of Kervadec et al. (MIDL 2019).
+    phi is the signed Euclidean distance, in pixels, of pixel i to the labelled region { y > 0.5 } of its image (positive outside,
+    0 on the inner rim, negative deeper in; 0 everywhere on an image without a lesion), rebuilt on the device from every step's
+    raw labels.  A false positive costs by how far it lies from the lesion.  Every Tversky key keeps its meaning (the defaults are
+    soft Dice) and region_weight stays > 0: the term is not meant to train alone.  Not in the reference."""
+
+    name = 'boundary_crossentropy'
+
+    def __init__(self, boundary_weight=0.01, **kwargs):
+        super().__init__(**kwargs)
+        v = boundary_weight
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float('inf'), float('-inf')):
+            raise ValueError('BoundaryCrossentropy: boundary_weight must be a finite number, got %r' % (v,))
+        if not v > 0:
+            raise ValueError('boundary_weight must be > 0, got %r' % (v,))
+        self.boundary_weight = float(v)
+
+    def boundary_cfg(self):
+        """what DeviceModel.set_boundary_loss takes (after set_region_loss(region_cfg()))"""
+        return self.boundary_weight
+
+    def get_config(self):
+        return dict(super().get_config(), boundary_weight=self.boundary_weight)
+
+
 _REGISTRY = {'WeightedCrossentropy': WeightedCrossentropy, 'weighted_crossentropy': WeightedCrossentropy,
              'TverskyCrossentropy': TverskyCrossentropy, 'tversky_crossentropy': TverskyCrossentropy,
-             'DiceCrossentropy': DiceCrossentropy, 'dice_crossentropy': DiceCrossentropy}
+             'DiceCrossentropy': DiceCrossentropy, 'dice_crossentropy': DiceCrossentropy,
+             'BoundaryCrossentropy': BoundaryCrossentropy, 'boundary_crossentropy': BoundaryCrossentropy}
 
 
 def get(identifier):

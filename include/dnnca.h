@@ -302,6 +302,30 @@ int dnnca_model_set_region_loss(void* model, const dnnca_region_loss* cfg);
 /* I, P, Y per image of the last train / eval step that ran with the region loss on (out: batch x 3 doubles); waits for the stream */
 int dnnca_region_loss_sums(void* model, int batch, double* out);
 
+/* ---- boundary (signed-distance) term of the training loss (Kervadec et al., MIDL 2019) --------------------------------------
+ * Per image b, G = { y > 0.5 } of the step's RAW label (under label_smoothing: the label before the blur; the blurred one still
+ * feeds the cross-entropy and the region term).  For a pixel q of the H x W plane, d2(q) is the exact squared Euclidean distance
+ * to the nearest pixel of G (q outside G) or to the nearest pixel of the plane outside G (q inside), and
+ *   phi(q) = float(sqrt((double)d2))        outside G
+ *          = 1.0f - float(sqrt((double)d2)) inside G (0 on the inner rim, negative deeper in)
+ *          = 0                              on an image where G is empty or the whole plane
+ *   S_b = sum_i p_i phi_i (double),  loss += boundary_weight * mean_b S_b / (H W)
+ *   dloss/dlogit_i += boundary_weight * phi_i p_i (1 - p_i) / (H W B);  phi is a constant of the step.
+ * The term rides the launches of the region loss: a step runs boundary_cols, boundary_rows (the map, rebuilt from the step's labels)
+ * in front of them and their phi-reading variants; train and eval steps of every entry point carry it.  No atomics: map, sums,
+ * loss and gradients are bit-identical from run to run.  boundary_weight > 0 switches the term on, 0 off (every launch is then the
+ * region loss's own).  DNNCA_EINVAL, with nothing changed, for a negative or non-finite value and while no region loss is set;
+ * dnnca_model_set_region_loss(model, NULL) clears the term too, setting a region loss again keeps it.  Waits for the stream. */
+int dnnca_model_set_boundary_loss(void* model, float boundary_weight);
+/* S_b of the last train / eval step that ran with the term (out: batch doubles); DNNCA_ESTATE when there was none; waits */
+int dnnca_boundary_loss_sums(void* model, int batch, double* out);
+/* phi of the last such step, [batch, H, W] floats to host; DNNCA_ESTATE when there was none; waits */
+int dnnca_boundary_distance(void* model, int batch, float* phi_out);
+/* The same two kernels on host label planes y_hw [batch, h, w] of any size from 1 x 1 to 16384 pixels a side (batch within the
+ * model's): phi_out [batch, h, w] and, d2_out != NULL, the squared distances (0 where the other set is empty).  Touches no tensor
+ * of the model and no map of a step. */
+int dnnca_signed_distance_of(void* model, const float* y_hw, int batch, int h, int w, float* phi_out, int32_t* d2_out);
+
 /* pixel TP/FP/FN/TN of the last forward/eval probabilities against y at n thresholds (metrics.yaml:2-23 pixel metrics;
  * utils/metrics.py:37-77 FBetaScore builds on them). y_hw is a host buffer [B,H,W]. */
 int dnnca_pixel_confusion(void* model, const float* y_hw, int batch, const float* thresholds, int n, dnnca_confusion* out);

@@ -8,7 +8,13 @@ The plain step is also measured on a second library, built from the parent commi
 (-> dnncancerannotator_amd/libdnnca_parent.so), alternated with this build's in one visit: the untouched path must be untouched.
 Every arm is a child process of its own (a library is chosen when it is loaded, DNNCA_LIB), one at a time.
 
-    python tools/region_loss_rate.py [--steps 100] [--only unet] [--parent-lib PATH] [--out profiles/region_loss_rate.txt]"""
+--boundary adds the boundary (signed-distance) term, DeviceModel.set_boundary_loss: per config the step with Dice alone and with Dice +
+boundary, the plain and the Dice-only step also on the parent build (alternated; the spread of an arm is the difference between its
+runs), the device time of every launch the term adds or changes, and boundary_cols / boundary_rows per launch on three kinds of
+labels: a batch of healthy slices (no walk at all), one small lesion per slice (the long walks) and Bernoulli(0.5) labels (the short
+ones).
+
+    python tools/region_loss_rate.py [--boundary] [--steps 100] [--only unet] [--parent-lib PATH] [--out profiles/region_loss_rate.txt]"""
 import argparse
 import json
 import os
@@ -26,14 +32,30 @@ CONFIGS = {
     'mulmo_unet': ('mulmo', dict(BASE, n_filters_first=16, n_downsample=4, bn=True), 3, 8, 512),
     'unet_big': ('unet', dict(BASE, n_filters_first=64, n_downsample=4, bn=True), 1, 8, 512),
 }
-CHANGED = ('head_region', 'region_', 'head_reduce', 'head_train', 'tail3', 'pgfwd_head', 'g_loss', 'pg_fold', 'fold_adam')
+CHANGED = ('head_region', 'region_', 'head_reduce', 'head_train', 'tail3', 'pgfwd_head', 'g_loss', 'pg_fold', 'fold_adam', 'boundary_')
+BOUNDARY_SYMBOLS = ('dnnca_model_set_boundary_loss', 'dnnca_boundary_loss_sums', 'dnnca_boundary_distance', 'dnnca_signed_distance_of')
+LABELS = ('synthetic', 'healthy', 'lesion', 'bernoulli')
 
 
-def child(name, region, steps, profile):
+def labels_of(kind, y):
+    """the label planes of a leg: the synthetic batch's own, none, one disc of radius 6 per slice, Bernoulli(0.5)"""
+    import numpy as np
+    if kind == 'synthetic':
+        return y
+    out = np.zeros_like(y)
+    if kind == 'lesion':
+        yy, xx = np.mgrid[0:y.shape[1], 0:y.shape[2]]
+        out[:, (yy - y.shape[1] // 3) ** 2 + (xx - y.shape[2] // 4) ** 2 <= 36] = 1.0
+    elif kind == 'bernoulli':
+        out[:] = np.random.default_rng(300).random(y.shape) < 0.5
+    return out
+
+
+def child(name, region, steps, profile, boundary=0.0, labels='synthetic'):
     from dnncancerannotator_amd import _lib, device as dev
     from dnncancerannotator_amd.synthetic import synthetic_batch
-    if os.environ.get('DNNCA_LIB') and not region:       # the parent build has no region-loss entry points to bind
-        for sym in ('dnnca_model_set_region_loss', 'dnnca_region_loss_sums'):
+    if os.environ.get('DNNCA_LIB'):                      # an older build: no entry points of the later terms to bind
+        for sym in BOUNDARY_SYMBOLS + (() if region else ('dnnca_model_set_region_loss', 'dnnca_region_loss_sums')):
             _lib.SIGNATURES.pop(sym, None)
     arch, opts, C, B, S = CONFIGS[name]
     dev.init_device(0)
@@ -41,13 +63,16 @@ def child(name, region, steps, profile):
     m.init_glorot(seed=2)
     if region:
         m.set_region_loss({})
+    if boundary:
+        m.set_boundary_loss(boundary)
     x, y = synthetic_batch(B, S, S, C, seed_x=100, seed_y=200)
+    y = labels_of(labels, y)
     xb, yb = dev.DeviceBuffer(x), dev.DeviceBuffer(y)
     cfg = m.loss_cfg(weight_mul=3.0)
     for _ in range(20):
         m.train_step_dev(xb, yb, B, 1e-3, cfg)
     m.sync()
-    res = dict(name=name, region=region)
+    res = dict(name=name, region=region, boundary=boundary, labels=labels)
     if profile:
         m.profile_reset()
         m.profile_enable(1)
@@ -70,12 +95,12 @@ def child(name, region, steps, profile):
     print('RESULT ' + json.dumps(res), flush=True)
 
 
-def run_child(name, region, steps, profile=False, lib=None):
+def run_child(name, region, steps, profile=False, lib=None, boundary=0.0, labels='synthetic'):
     env = dict(os.environ)
     if lib:
         env['DNNCA_LIB'] = lib
     cmd = [sys.executable, os.path.abspath(__file__), '--child', name, '--steps', str(steps)] + (['--region'] if region else []) + \
-        (['--profile'] if profile else [])
+        (['--profile'] if profile else []) + ['--boundary-weight', str(boundary), '--labels', labels]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     if out.returncode != 0:
         raise RuntimeError('%s failed (%d): %s' % (' '.join(cmd), out.returncode, out.stderr[-2000:]))
@@ -91,9 +116,14 @@ def main():
     ap.add_argument('--child', default=None)
     ap.add_argument('--region', action='store_true')
     ap.add_argument('--profile', action='store_true')
+    ap.add_argument('--boundary', action='store_true', help='the legs of the boundary term (see the top of this file)')
+    ap.add_argument('--boundary-weight', type=float, default=0.0)
+    ap.add_argument('--labels', choices=LABELS, default='synthetic')
     a = ap.parse_args()
     if a.child:
-        return child(a.child, a.region, a.steps, a.profile)
+        return child(a.child, a.region, a.steps, a.profile, a.boundary_weight, a.labels)
+    if a.boundary:
+        return boundary_main(a)
     parent = a.parent_lib if os.path.exists(a.parent_lib) else None
     lines = ['region loss: ms per train step at 8 x 512 x 512 f32, %d steps x 3 (best), device-resident batches' % a.steps]
     if not parent:
@@ -120,6 +150,46 @@ def main():
     with open(a.out, 'w') as f:
         f.write('\n'.join(lines) + '\n')
     print('wrote', a.out)
+
+
+def boundary_main(a):
+    parent = a.parent_lib if os.path.exists(a.parent_lib) else None
+    lines = ['boundary loss: ms per train step at 8 x 512 x 512 f32, %d steps x 3 (best), device-resident batches, boundary_weight 0.01; '
+             'every arm twice, alternated' % a.steps]
+    if not parent:
+        lines.append('parent-commit library %s not found: the plain and Dice-only steps on the parent build were not measured' % a.parent_lib)
+    fmt = lambda v: '%.4f (%s)' % (min(v), ' '.join('%.4f' % t for t in v))      # noqa: E731
+    for name in CONFIGS:
+        if a.only and name != a.only:
+            continue
+        arms = {'plain': (False, 0.0, None), 'dice': (True, 0.0, None), 'dice + boundary': (True, 0.01, None)}
+        if parent:
+            arms.update({'plain, parent build': (False, 0.0, parent), 'dice, parent build': (True, 0.0, parent)})
+        ms = {k: [] for k in arms}
+        for _ in range(2):
+            for k in sorted(arms):
+                region, bw, lib = arms[k]
+                ms[k].append(run_child(name, region, a.steps, lib=lib, boundary=bw)['ms'])
+        lines.append('%-11s %s' % (name, '  '.join('%s %s' % (k, fmt(ms[k])) for k in sorted(arms))))
+        lines.append('%-11s boundary term +%.1f us per step over dice; spread of an arm (largest difference of its two runs) %.1f us' % (
+            '', (min(ms['dice + boundary']) - min(ms['dice'])) * 1e3, max(abs(v[0] - v[1]) for v in ms.values()) * 1e3))
+        for bw in (0.0, 0.01):
+            r = run_child(name, True, 40, profile=True, boundary=bw)
+            for k, per_step, us in sorted(r['kernels']):
+                lines.append('  %-15s %-24s %4.1f launches per step  %8.2f us per launch' % ('dice + boundary' if bw else 'dice', k, per_step, us))
+        print('\n'.join(lines[-16:]), flush=True)
+    for labels in LABELS[1:]:                       # the transform alone: it does not depend on the network
+        if a.only and a.only != 'unet':
+            break
+        r = run_child('unet', True, 40, profile=True, boundary=0.01, labels=labels)
+        for k, per_step, us in sorted(r['kernels']):
+            if k.startswith('boundary_'):
+                lines.append('  labels %-10s %-24s %4.1f launches per step  %8.2f us per launch' % (labels, k, per_step, us))
+    print('\n'.join(lines[-6:]), flush=True)
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, 'a') as f:                     # behind the region loss's own table
+        f.write('\n'.join(lines) + '\n')
+    print('appended to', a.out)
 
 
 if __name__ == '__main__':
