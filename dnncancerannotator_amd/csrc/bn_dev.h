@@ -38,6 +38,7 @@ struct BnSelfFold {
     float* mmean;
     float* mvar;
     float* coef;             // [4][C]: scale, shift, mean, 1 / sqrt(var + eps)
+    const float* shift;      // [C] a per-channel constant the contributors subtracted from every value before summing (nullptr: none)
 };
 
 // bucket row of a contribution (key: anything spread evenly over the contributors, e.g. the block or tile index)
@@ -96,9 +97,10 @@ __device__ __forceinline__ void bn_self_fold(const BnSelfFold& f, unsigned nbloc
         const double sum = bn_fold_column(f.tab, R, 2 * C, c), sumsq = bn_fold_column(f.tab, R, 2 * C, C + c);
         for (int r = 0; r < R; ++r) { f.tab[(size_t)r * 2 * C + c] = 0.0; f.tab[(size_t)r * 2 * C + C + c] = 0.0; }
         // raw moments -> coefficients and moving statistics: the contract of g_bn_finalize
-        const double mean_d = sum / f.n;
-        double var_d = sumsq / f.n - mean_d * mean_d;
+        const double mean_0 = sum / f.n;          // of the values as they were summed: less f.shift
+        double var_d = sumsq / f.n - mean_0 * mean_0;
         if (var_d < 0.0) var_d = 0.0;
+        const double mean_d = f.shift ? mean_0 + (double)f.shift[c] : mean_0;
         const float mean = (float)mean_d, var = (float)var_d;
         const float unbiased = (float)(var_d * (f.n > 1.0 ? f.n / (f.n - 1.0) : 1.0));
         f.mmean[c] = mm * f.momentum + mean * (1.f - f.momentum);

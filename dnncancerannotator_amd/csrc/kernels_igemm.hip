@@ -929,11 +929,14 @@ __global__ __launch_bounds__(256, 2) void k_ig_tconv_fwd2(TcArgs p) {
             float* op = p.out + tc_outpix(px, ae >> 1, ae & 1, p.H, p.W) * p.cout + co0 + 4 * q;
 #pragma unroll
             for (int mt = 0; mt < NCO; ++mt) {
-                const f32x4 v = acc[ae][mt][pt] + bias[mt];
-                *reinterpret_cast<f32x4*>(op + 16 * mt) = v;
-                bs[mt] += v;
+                // the moments are those of z - bias (BnSelfFold::shift = bias adds it back to the mean): the bias is the one
+                // per-channel constant this layer knows, and nothing else keeps it near 0 -- its gradient is analytically zero in
+                // front of a BatchNorm, so Adam walks it away -- while raw float32 moments lose (mean / sigma)^2 of their digits
+                const f32x4 z = acc[ae][mt][pt];
+                *reinterpret_cast<f32x4*>(op + 16 * mt) = z + bias[mt];
+                bs[mt] += z;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) bq[mt][i] = fmaf(v[i], v[i], bq[mt][i]);
+                for (int i = 0; i < 4; ++i) bq[mt][i] = fmaf(z[i], z[i], bq[mt][i]);
             }
         }
     }
@@ -3402,6 +3405,7 @@ bool ig_tconv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_nex
     ig::TcArgs a = tc_args(m, B, o);
     // batch statistics of the BatchNorm behind it ride in the epilogue
     const bool stats = bn_next && d.stats && bn_self_fold_args(m, *bn_next, B, &a.bnf);
+    if (stats && d.kern == DK_F32_TCONV2) a.bnf.shift = a.bias;          // k_ig_tconv_fwd2 sums z - bias
     switch (d.kern) {
     case DK_B16_TCONV2: case DK_B16_TCONV: {
         static const TcKernB k[2][2] = {{igb::k_igb_tconv_fwd<false>, igb::k_igb_tconv_fwd<true>},
