@@ -5,11 +5,13 @@
 
 namespace dnnca {
 
-int fast_prepare(Model* m);     // per-step operand preparation (weights -> MFMA B operands)
-int fast_finish_backward(Model* m);   // folds the weight-gradient slabs into the flat gradient vector (or defers: Model::fold_deferred)
+// per-pass operand preparation (weights -> MFMA B operands); train_step: a backward pass follows (StepRequest::defer_head) -- the
+// launch then also zeroes scalars, gradients and slabs (Step::step_init_done) and may wait for the first launch (Step::prep_flush)
+int fast_prepare(Model* m, bool train_step);
+int fast_finish_backward(Model* m);   // folds the weight-gradient slabs into the flat gradient vector (or defers: Step::fold_deferred)
 int fast_fold_adam(Model* m, float lr_t, const dnnca_loss_cfg& cfg, double n_label, double inv_batch_hw);   // the deferred fold + Adam + step outputs in one launch
-void fast_release(Model* m);
-unsigned long long* fast_debug_stamps(Model* m);   // tuning aid: in-kernel s_memtime stamps (DNNCA_STAMPS)    // drop the per-model plan
+void fast_release(Model* m);    // drop the model's pixel-group plan (Model::plan_pg)
+unsigned long long* fast_debug_stamps(const Model* m);   // tuning aid: in-kernel s_memtime stamps (DNNCA_STAMPS); nullptr: none (asking creates nothing)
 // `pool`: a max-pool op fused into the conv's epilogue (fast_pool_fusable), or nullptr
 bool fast_conv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* pool);
 bool fast_pool_fusable(const Model* m, const Op& conv, const Op& pool);
@@ -18,7 +20,7 @@ bool fast_conv_fwd_head(Model* m, int B, Op& o, Op& head, const float* y, const 
 // kernels_fused.hip: a whole Downsample / Upsample block (components.py:77-81, 158-166) of configs/unet.yaml in one launch;
 // ops[oi .. oi+2] are consumed when these return true.  store_mid: also write the block's intermediate tensors (a backward pass follows)
 bool fused_down_fwd(Model* m, int B, size_t oi, bool store_mid, const float* labels = nullptr);   // labels: also reduce them (first block only)
-// ... or, where the shape allows, that conv's forward, the head, the loss and the conv's whole backward in one launch (sets Model::tail_done)
+// ... or, where the shape allows, that conv's forward, the head, the loss and the conv's whole backward in one launch (sets Step::tail_done)
 bool fast_tail3(Model* m, int B, Op& o, Op& head, const float* y, const dnnca_loss_cfg& cfg, float gscale);
 bool fast_first3_fwd(Model* m, int B, Op& c1, Op& c2, Op& pool, float* y0, unsigned char* pool_idx, const float* labels, float* label_part,
                      double bytes, double flops, int* nblocks);      // first encoder block forward as one column-strip launch
@@ -33,8 +35,8 @@ bool fused_up_bwd(Model* m, int B, size_t oi);
 // kernels_mfma.hip: what the block-fused kernels need from the pixel-group plan
 constexpr int kPgBuckets = 16;                                 // partial-sum slabs per weight gradient
 bool fast_pg_conv_supported(const Model* m, const Op& o);      // a 3x3 conv of the pixel-group plan
-const float* fast_conv_bmat_dgrad(Model* m, const Op& o);      // prepared data-gradient B operands (all passes), or nullptr
-float* fast_wgrad_slabs(Model* m, const Op& o, int source);    // weight-gradient slabs of (op, source) -- transposed convs: source 0 -- or nullptr
+const float* fast_conv_bmat_dgrad(const Model* m, const Op& o);      // prepared data-gradient B operands (all passes), or nullptr
+float* fast_wgrad_slabs(const Model* m, const Op& o, int source);    // weight-gradient slabs of (op, source) -- transposed convs: source 0 -- or nullptr
 bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, double flops);
 // kernels_first.hip: the one-channel-input 3x3 convs (first layer of every encoder)
 bool fast_first_conv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_next);   // bn_next as for ig_conv_fwd

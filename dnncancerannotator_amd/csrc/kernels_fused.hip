@@ -469,7 +469,7 @@ __global__ __launch_bounds__(NT, MINW) void k_fz_up(UpArgs p) {
 }  // namespace fz
 
 // ================================================================================================ host side
-const float* fast_conv_bmat(Model* m, const Op& o);       // kernels_mfma.hip: prepared forward B operand of a pixel-group conv
+const float* fast_conv_bmat(const Model* m, const Op& o);       // kernels_mfma.hip: prepared forward B operand of a pixel-group conv
 
 
 constexpr int kFzPerCu = 6;      // resident blocks per CU that the persistent grids of this file count on, at most
@@ -511,7 +511,7 @@ bool fused_down_fwd(Model* m, int B, size_t oi, bool store_mid, const float* lab
     a.B = B; a.H = H; a.W = W;
     a.alpha1 = c1.alpha; a.alpha2 = c2.alpha;
     if (labels) {         // the caller (forward of a train step) wants this step's label statistics from this launch
-        m->label_part_valid = false;
+        m->step.label_part_valid = false;
         if (!m->label_part && m->alloc((void**)&m->label_part, 2048 * 16) != DNNCA_OK) return false;
         a.labels = labels;
         a.label_part = m->label_part;
@@ -521,7 +521,7 @@ bool fused_down_fwd(Model* m, int B, size_t oi, bool store_mid, const float* lab
     if (CIN == 1 && C1 == 3) {          // the full-resolution block of configs/unet.yaml: the column-strip kernel (any even size)
         int nblk = 0;
         if (fast_first3_fwd(m, B, c1, c2, pl, a.y0, a.pool_idx, a.labels, a.label_part, bytes, flops, &nblk)) {
-            if (labels) { m->label_part_valid = true; m->label_part_nblk = nblk; }
+            if (labels) { m->step.label_part_valid = true; m->step.label_part_nblk = nblk; }
             pl.pool_idx_valid = store_mid && (m->dry || a.pool_idx != nullptr);
             return true;
         }
@@ -534,7 +534,7 @@ bool fused_down_fwd(Model* m, int B, size_t oi, bool store_mid, const float* lab
         if (labels && (g > 2048 || W != c1.out.d.W)) return false;                                                \
         LAUNCH(m, "fz_down_" #cin "_" #c1v, bytes, flops,                                                         \
                hipLaunchKernelGGL((fz::k_fz_down<cin, c1v, tw, th, nt, mw>), dim3(g), dim3(nt), 0, m->stream, a));   \
-        if (labels) { m->label_part_valid = true; m->label_part_nblk = g; }                                       \
+        if (labels) { m->step.label_part_valid = true; m->step.label_part_nblk = g; }                                       \
         pl.pool_idx_valid = store_mid && (m->dry || a.pool_idx != nullptr);                                       \
         return true;                                                                                              \
     }

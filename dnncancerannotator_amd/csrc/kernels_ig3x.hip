@@ -20,7 +20,6 @@
 // step: forward layout [plane][tap][co][ci], data-gradient layout [plane][8 - tap][ci][co]).  Three planes of both operands take 1.5x
 // the LDS of the fp32 kernel, so there is ONE LDS buffer: the next item's global loads fly during this item's MFMAs and are committed
 // between two barriers.
-#include <map>
 
 #include "fast.h"
 #include "ig_dev.h"
@@ -890,9 +889,7 @@ struct Ig3xPlan {
     unsigned pstride = 0;
     int max_w = 0;
 };
-static std::map<Model*, Ig3xPlan> g_ig3x;
-
-void ig3x_release(Model* m) { g_ig3x.erase(m); }
+void ig3x_release(Model* m) { delete m->plan_ig3x; m->plan_ig3x = nullptr; }
 
 // fp32 models only; DNNCA_NO_X3=1 keeps the exact-fp32 MFMA kernels
 bool ig3x_enabled(const Model* m) { return !dense_switches().no_x3 && m->desc.dtype == DNNCA_F32 && !(m->desc.flags & 1); }
@@ -901,7 +898,8 @@ static unsigned ig3x_pstride(const Model* m) { return (unsigned)((m->nT + 15) / 
 
 int ig3x_prepare(Model* m) {
     if (!ig3x_enabled(m)) return DNNCA_OK;
-    Ig3xPlan& pl = g_ig3x[m];
+    if (!m->plan_ig3x) m->plan_ig3x = new Ig3xPlan;          // the one place that creates it
+    Ig3xPlan& pl = *m->plan_ig3x;
     if (!pl.built) {
         pl.built = true;
         for (const Op& o : m->ops) {
@@ -962,7 +960,8 @@ bool ig3x_conv_decide(const Model* m, const DenseSwitches& sw, int mode, int B, 
 
 // executes a DK_X3_CONV3 decision for the conv described by `a` (tiles already set from the decision)
 void ig3x_launch(Model* m, const DenseLaunch& d, int mode, const ig::ConvArgs& a, size_t w_off, const char* name, double bytes, double flops) {
-    Ig3xPlan& pl = g_ig3x[m];
+    static const Ig3xPlan none;          // (a model without a plan answers as an empty one; never created here)
+    const Ig3xPlan& pl = m->plan_ig3x ? *m->plan_ig3x : none;
     typedef void (*Kern)(ig::ConvArgs, const ig3x::bf16_t*, unsigned);
     // [mode: forward, data gradient, data gradient + BatchNorm backward sums][nn index][layout: 4 waves, 8 waves, 8 waves split]
     // (no <4, 2, 8>: that layout has no registers left for the sums -- ig3x_conv_decide leaves them to the BatchNorm's reduction pass)

@@ -2683,7 +2683,7 @@ struct IgPlan {
     igb::bf16_t* wd = nullptr;
     int max_wb = 0;
     float* wg_slabs = nullptr;       // WG_BUCKETS copies of a small layer's weight + bias gradient (ig_wgrad2; left zeroed by k_wg_fold)
-    std::map<std::pair<const void*, int>, std::pair<float*, size_t>> plain;      // (op, source) -> slabs of its plain-mode weight gradient, floats
+    std::vector<std::pair<float*, size_t>> plain;      // [2 * op index + source] -> slabs of its plain-mode weight gradient, floats
     // the folds of this backward pass, launched together by ig_finish_wgrad (single-replica steps); the device copies of the tables are
     // rewritten only when the list changes (first step, another batch size)
     std::vector<ig::FoldSeg> fold_pending, fold_on_dev;
@@ -2697,27 +2697,29 @@ struct IgPlan {
     bool fold_batch = false;
 };
 constexpr int WG_BUCKETS = 16, WG_SLAB_FLOATS = 131072 + 1024;
-static std::map<Model*, IgPlan> g_ig;
+// the model's plan: ig_plan creates it on first use; ig_find never creates -- a model without a plan answers as an empty one
+static IgPlan& ig_plan(Model* m) { return *(m->plan_ig ? m->plan_ig : (m->plan_ig = new IgPlan)); }
+static const IgPlan& ig_find(const Model* m) { static const IgPlan none; return m->plan_ig ? *m->plan_ig : none; }
 
 void ig_release(Model* m) {
-    g_ig.erase(m);
+    delete m->plan_ig; m->plan_ig = nullptr;
     ig3x_release(m);
 }
 
 // slabs of one weight-gradient launch in plain mode (WgArgs::plain): allocated once per (op, source), grown on demand
 static float* wg_plain_slabs(Model* m, const Op& o, int s, size_t floats) {
-    IgPlan& pl = g_ig[m];
-    const auto key = std::make_pair((const void*)&o, s);
-    auto it = pl.plain.find(key);
-    if (it != pl.plain.end() && it->second.second >= floats) return it->second.first;
+    IgPlan& pl = ig_plan(m);
+    if (pl.plain.empty()) pl.plain.resize(2 * m->ops.size());
+    auto& have = pl.plain[2 * (size_t)(&o - m->ops.data()) + s];
+    if (have.first && have.second >= floats) return have.first;
     float* ptr = nullptr;
     if (m->alloc((void**)&ptr, floats * 4) != DNNCA_OK) return nullptr;
-    pl.plain[key] = std::make_pair(ptr, floats);
+    have = std::make_pair(ptr, floats);
     return ptr;
 }
 // DNNCA_FOLD_BATCH=1: one fold launch per backward pass instead of one per weight-gradient launch -- unless this step sends gradient
 // buckets while the backward pass runs (they need each layer's gradient final as soon as its launches are)
-static bool wg_fold_batched(Model* m) { return g_ig[m].fold_batch && !m->bucketing; }
+static bool wg_fold_batched(const Model* m) { return ig_find(m).fold_batch && !m->step.bucketing; }
 
 // the one place that reads the dense path's environment (fast.h; DESIGN section 8 lists every name)
 const DenseSwitches& dense_switches() {
@@ -3035,7 +3037,7 @@ int ig_plan_half(Model* m) {
 
 int ig_prepare(Model* m) {
     if (m->desc.flags & 1) return DNNCA_OK;
-    IgPlan& pl = g_ig[m];
+    IgPlan& pl = ig_plan(m);
     if (!pl.built) {
         pl.built = true;
         // the data-gradient kernels of the exact-fp32 MFMA path read flipped / transposed weights (k_ig_flip, once per backward pass); the
@@ -3093,7 +3095,7 @@ int ig_prepare(Model* m) {
 int ig_begin_backward(Model* m) {
     for (Op& o : m->ops) o.bwd_sums_rode = false;          // (a pass that stopped on an error may have left one set)
     if (m->desc.flags & 1) return DNNCA_OK;
-    IgPlan& pl = g_ig[m];
+    const IgPlan& pl = ig_find(m);
     if (pl.flips.empty()) return DNNCA_OK;
     int bx = (pl.max_w + 255) / 256;
     if (bx > 1024) bx = 1024;
@@ -3119,7 +3121,7 @@ static void launch_conv(Model* m, const DenseLaunch& d, ig::ConvArgs a, size_t w
     const char* name = MODE == 0 ? "ig_conv_fwd" : "ig_conv_dgrad";
     const char* bname = MODE == 0 ? "igb_conv_fwd" : "igb_conv_dgrad";
     const int w8 = d.nw == 8;
-    const igb::bf16_t* w16 = (MODE == 0 ? g_ig[m].wf : g_ig[m].wd) + w_off;          // (bf16 kernels)
+    const igb::bf16_t* w16 = (MODE == 0 ? ig_find(m).wf : ig_find(m).wd) + w_off;          // (bf16 kernels)
     switch (d.kern) {
     case DK_X3_CONV3:
         ig3x_launch(m, d, MODE, a, w_off, MODE == 0 ? "ig3x_conv_fwd" : "ig3x_conv_dgrad", bytes, flops);
@@ -3203,7 +3205,7 @@ bool ig_conv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_next
 // folds the ps slabs of a plain-mode weight-gradient launch (source s of conv o) into the gradient -- now, or with the others of this
 // backward pass (ig_finish_wgrad)
 static void fold_plain(Model* m, const Op& o, int s, float* slabs, int ps, int pstride) {
-    IgPlan& pl = g_ig[m];
+    IgPlan& pl = ig_plan(m);
     const int CA = o.inA.d.C, CO = o.out.d.C, cs = s == 0 ? CA : o.inB.d.C, n_ws = 9 * cs * CO, n_b = s == 0 ? CO : 0;
     const ig::FoldSeg f{slabs, m->g + o.w_off, m->g + o.b_off, ps, pstride, cs, CO, CA + o.inB.d.C, s == 0 ? 0 : CA, n_b, n_ws + n_b < 32768};
     if (wg_fold_batched(m)) {
@@ -3218,7 +3220,7 @@ static void fold_plain(Model* m, const Op& o, int s, float* slabs, int ps, int p
 
 // weight (+ bias, with source 0) gradient of source s.  bucketed: the launches of this conv add into the WG_BUCKETS shared slabs
 static void conv_wgrad(Model* m, int B, const Op& o, int s, bool bucketed, double bytes, double flops) {
-    IgPlan& pl = g_ig[m];
+    const IgPlan& pl = ig_find(m);
     const DenseLaunch d = dense_conv_wgrad(m, B, o, s, dense_switches());
     const int CA = o.inA.d.C, CB = o.inB.d.C, CO = o.out.d.C, n_w = 9 * (CA + CB) * CO;
     ig::WgArgs w{};
@@ -3277,7 +3279,7 @@ static void conv_wgrad(Model* m, int B, const Op& o, int s, bool bucketed, doubl
 
 // bare: the data gradient and nothing else (the input-sensitivity pass) -- no activation mask on the stores, no BatchNorm sums
 static void conv_dgrad(Model* m, int B, Op& o, double bytes, double flops, bool bare = false) {
-    IgPlan& pl = g_ig[m];
+    const IgPlan& pl = ig_find(m);
     const DenseLaunch d = dense_conv_dgrad(m, B, o, dense_switches());
     ig::ConvArgs a{};
     a.src[0] = o.out.g.p; a.c_src0 = o.out.d.C; a.c_src1 = 0;
@@ -3298,7 +3300,7 @@ static void conv_dgrad(Model* m, int B, Op& o, double bytes, double flops, bool 
 
 bool ig_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, double flops) {
     if (!ig_conv_supported(m, o)) return false;
-    IgPlan& pl = g_ig[m];
+    IgPlan& pl = ig_plan(m);
     const int CA = o.inA.d.C, CB = o.inB.d.C, CO = o.out.d.C, n_w = 9 * (CA + CB) * CO, nsrc = CB ? 2 : 1;
     if (o.alpha >= 0.f && !o.premasked)
         LAUNCH(m, "g_act_bwd", 3 * out_bytes, out_bytes / 4,
@@ -3332,9 +3334,8 @@ bool ig_conv_dgrad_only(Model* m, int B, Op& o, double bytes, double flops) {
 // end of the backward pass: the pending folds (ig_conv_bwd, fold_plain) in one launch per 64 of them -- behind the weight-gradient
 // launches on their stream (the caller joins the streams afterwards)
 int ig_finish_wgrad(Model* m) {
-    auto it = g_ig.find(m);
-    if (it == g_ig.end() || it->second.fold_pending.empty()) return DNNCA_OK;
-    IgPlan& pl = it->second;
+    if (!m->plan_ig || m->plan_ig->fold_pending.empty()) return DNNCA_OK;
+    IgPlan& pl = *m->plan_ig;
     const size_t n = pl.fold_pending.size(), nchunks = (n + ig::kFoldBatch - 1) / ig::kFoldBatch;
     std::vector<int> first(nchunks * ig::kFoldBatch, 0), grid(nchunks, 0);
     for (size_t i = 0; i < n; ++i) {
@@ -3344,6 +3345,8 @@ int ig_finish_wgrad(Model* m) {
         grid[i / ig::kFoldBatch] += f.g16 ? (floats + 63) / 64 : (floats + 1023) / 1024;
     }
     if (!m->dry) {
+        // memcmp is right only while FoldSeg has no padding (3 pointers + 8 ints): whoever adds a field meets this line
+        static_assert(sizeof(ig::FoldSeg) == 56, "FoldSeg changed: check that it still has no padding, or compare field by field");
         const bool same = pl.fold_on_dev.size() == n && memcmp(pl.fold_on_dev.data(), pl.fold_pending.data(), n * sizeof(ig::FoldSeg)) == 0;
         if (!same) {
             HIP_TRY(hipDeviceSynchronize());          // the previous step's fold may still be reading the tables
@@ -3359,7 +3362,7 @@ int ig_finish_wgrad(Model* m) {
         }
     }
     hipStream_t main_stream = m->stream;
-    if (m->wg_pending && m->wg_stream) m->stream = m->wg_stream;
+    if (m->step.wg_pending && m->wg_stream) m->stream = m->wg_stream;
     for (size_t c = 0; c < nchunks; ++c) {
         const int ns = (int)std::min<size_t>(ig::kFoldBatch, n - c * ig::kFoldBatch);
         LAUNCH(m, "wg_fold_all", pl.fold_bytes / nchunks, 0,
@@ -3412,7 +3415,7 @@ bool ig_tconv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_nex
                                         {igb::k_igb_tconv_fwd2<false>, igb::k_igb_tconv_fwd2<true>}};
         m->set_variant(d.kern == DK_B16_TCONV2 ? "2h%d" : "h%d", (int)d.a16);
         LAUNCH(m, "igb_tconv_fwd", bytes, flops,
-               hipLaunchKernelGGL(k[d.kern == DK_B16_TCONV2][d.a16], d.grid, dim3(d.block), 0, m->stream, a, g_ig[m].wf + o.w_off));
+               hipLaunchKernelGGL(k[d.kern == DK_B16_TCONV2][d.a16], d.grid, dim3(d.block), 0, m->stream, a, ig_find(m).wf + o.w_off));
         break;
     }
     default: {          // fp32, second / first generation
@@ -3464,7 +3467,7 @@ static void tconv_dgrad(Model* m, int B, const Op& o, const ig::TcArgs& a, doubl
     if (d.kern == DK_B16_TCONV_DGRAD) {
         const TcKernB k = d.k64 ? igb::k_igb_tconv_dgrad<true, 64> : igb::k_igb_tconv_dgrad<false, 32>;
         m->set_variant("g%d%s", (int)d.g16, d.k64 ? "k64" : "");
-        LAUNCH(m, "igb_tconv_dgrad", bytes, flops, hipLaunchKernelGGL(k, d.grid, dim3(d.block), 0, m->stream, a, g_ig[m].wd + o.w_off));
+        LAUNCH(m, "igb_tconv_dgrad", bytes, flops, hipLaunchKernelGGL(k, d.grid, dim3(d.block), 0, m->stream, a, ig_find(m).wd + o.w_off));
         return;
     }
     static const TcKern k[3] = {ig::k_ig_tconv_dgrad<1>, ig::k_ig_tconv_dgrad<2>, ig::k_ig_tconv_dgrad<4>};

@@ -1383,10 +1383,13 @@ struct PgPlan {                      // per-model table built lazily on the firs
     unsigned long long* stamps = nullptr;
 };
 
-static std::map<Model*, PgPlan> g_plans;
+// the model's plan: pg_plan creates it on first use (fast_prepare, where the plan is built); pg_find never creates -- a model
+// without a plan (force_generic, or before its first forward pass) answers as an empty one
+static PgPlan& pg_plan(Model* m) { return *(m->plan_pg ? m->plan_pg : (m->plan_pg = new PgPlan)); }
+static const PgPlan& pg_find(const Model* m) { static const PgPlan none; return m->plan_pg ? *m->plan_pg : none; }
 
-void fast_release(Model* m) { g_plans.erase(m); }
-unsigned long long* fast_debug_stamps(Model* m) { return g_plans[m].stamps; }
+void fast_release(Model* m) { delete m->plan_pg; m->plan_pg = nullptr; }
+unsigned long long* fast_debug_stamps(const Model* m) { return pg_find(m).stamps; }
 
 static bool conv_supported(const Model* m, const Op& o) {
     if (o.type != OP_CONV || o.k != 3) return false;
@@ -1534,36 +1537,36 @@ static int build_plan(Model* m, PgPlan& pl) {
 }
 
 // the prepared forward B operand of a pixel-group conv (for the block-fused kernels of kernels_fused.hip); nullptr: not planned
-const float* fast_conv_bmat(Model* m, const Op& o) {
+const float* fast_conv_bmat(const Model* m, const Op& o) {
     if (!conv_supported(m, o)) return nullptr;
-    PgPlan& pl = g_plans[m];
+    const PgPlan& pl = pg_find(m);
     auto it = pl.slot.find({&o, 0});
     return it == pl.slot.end() ? nullptr : pl.bmat + it->second;
 }
 
 bool fast_pg_conv_supported(const Model* m, const Op& o) { return conv_supported(m, o); }
-const float* fast_conv_bmat_dgrad(Model* m, const Op& o) {
+const float* fast_conv_bmat_dgrad(const Model* m, const Op& o) {
     if (!conv_supported(m, o)) return nullptr;
-    PgPlan& pl = g_plans[m];
+    const PgPlan& pl = pg_find(m);
     auto it = pl.slot.find({&o, 1});
     return it == pl.slot.end() ? nullptr : pl.bmat + it->second;
 }
-float* fast_wgrad_slabs(Model* m, const Op& o, int source) {
-    PgPlan& pl = g_plans[m];
+float* fast_wgrad_slabs(const Model* m, const Op& o, int source) {
+    const PgPlan& pl = pg_find(m);
     auto it = pl.wslot.find({&o, source});
     return it == pl.wslot.end() ? nullptr : pl.slabs + pl.folds[it->second].slab_off;
 }
 
 // Called by model.hip at the top of every forward: (re)derive the B operands from the current weights.
-int fast_prepare(Model* m) {
+int fast_prepare(Model* m, bool train_step) {
     if (m->desc.flags & 1) return DNNCA_OK;
-    PgPlan& pl = g_plans[m];
+    PgPlan& pl = pg_plan(m);
     if (!pl.built) DN_TRY(build_plan(m, pl));
     if (pl.descs.empty()) return DNNCA_OK;
     const int nprep = (pl.bmat_n + 255) / 256;
     StepInit z{};
     int nz = 0;
-    if (m->defer_head && m->merged_launches() && !m->dry) {      // dnnca_train_step: a backward pass follows this forward pass
+    if (train_step && m->merged_launches() && !m->dry) {      // dnnca_train_step: a backward pass follows this forward pass
         z.scalars = m->scalars;
         z.a = reinterpret_cast<float4*>(m->g);
         z.na4 = (unsigned)((m->nT + 8 + 3) / 4);                // both buffers are allocated with >= 16 bytes of slack
@@ -1571,14 +1574,14 @@ int fast_prepare(Model* m) {
         z.nb4 = (unsigned)((m->extra_zero_n + 3) / 4);
         nz = (int)((z.na4 + z.nb4 + 1023) / 1024);
         nz = nz < 1 ? 1 : (nz > 1024 ? 1024 : nz);
-        m->step_init_done = true;
+        m->step.step_init_done = true;
     }
     pl.prep = PrepRide{pl.bindex, m->p, pl.bmat, pl.bmat_n, nprep, nprep + nz, z};
     if (nz && !m->sw.no_prep_ride) {
         // train step: the first launch of the forward pass decides -- the first encoder block's strip kernel takes the preparation
         // along as extra blocks (it needs none of its results); any other launch flushes it first (LAUNCH)
-        m->prep_flush = [](Model* mm) {
-            PgPlan& q = g_plans[mm];
+        m->step.prep_flush = [](Model* mm) {
+            const PgPlan& q = pg_find(mm);
             LAUNCH(mm, "pg_prep", 0, 0,
                    hipLaunchKernelGGL(k_pg_prep, dim3(q.prep.nblocks), dim3(256), 0, mm->stream, q.prep.index, q.prep.params, q.prep.bmat,
                                       q.prep.n, q.prep.nprep, q.prep.z));
@@ -1603,7 +1606,7 @@ static int pg_grid(const Model* m, int ntiles) {
 
 bool fast_conv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* pool) {
     if (!conv_supported(m, o)) return false;
-    PgPlan& pl = g_plans[m];
+    const PgPlan& pl = pg_find(m);
     auto it = pl.slot.find({&o, 0});
     if (it == pl.slot.end()) return false;
     FwdArgs a{};
@@ -1634,7 +1637,7 @@ bool fast_conv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* pool)
 // The op in front of conv `o` (C -> C channels, two sources) when it is a k = 2 transposed conv cin -> C that produces o's first
 // source and whose backward can ride in o's backward launch: whole tiles, and nothing accumulates or is masked on the way.  Fills
 // the launch's tc_* arguments; nullptr otherwise.
-static Op* riding_tconv(Model* m, PgPlan& pl, Op& o, int cin, BwdArgs& a) {
+static Op* riding_tconv(Model* m, const PgPlan& pl, Op& o, int cin, BwdArgs& a) {
     const size_t oi = (size_t)(&o - m->ops.data());
     if (oi < 1 || oi >= m->ops.size()) return nullptr;
     Op* tc = &m->ops[oi - 1];
@@ -1652,7 +1655,7 @@ static Op* riding_tconv(Model* m, PgPlan& pl, Op& o, int cin, BwdArgs& a) {
 
 bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, double flops) {
     if (!conv_supported(m, o)) return false;
-    PgPlan& pl = g_plans[m];
+    const PgPlan& pl = pg_find(m);
     const int C = o.inA.d.C, NS = o.inB.d.C ? 2 : 1, CO = o.out.d.C;
     // dz = dy * act'(y) in place unless the consumers already delivered the pre-activation gradient
     if (o.alpha >= 0.f && !o.premasked)
@@ -1672,8 +1675,8 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
     a.alpha = o.mask_alpha;
     const StepSwitches& sw = m->sw;
     a.dbg = sw.dbg;
-    if (sw.stamp_c == C && sw.stamp_ns == NS && sw.stamp_co == CO) {      // tuning aid: this is the kernel to stamp
-        if (!pl.stamps && m->alloc((void**)&pl.stamps, 1024 * 4 * 8 * 8) != DNNCA_OK) return false;
+    if (sw.stamp_c == C && sw.stamp_ns == NS && sw.stamp_co == CO && m->plan_pg) {      // tuning aid: this is the kernel to stamp
+        if (!m->plan_pg->stamps && m->alloc((void**)&m->plan_pg->stamps, 1024 * 4 * 8 * 8) != DNNCA_OK) return false;
         a.stamps = pl.stamps;
     }
     for (int s = 0; s < NS; ++s) {
@@ -1690,12 +1693,12 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
     const double fl = (o.need_din ? 2 : 1) * flops;
     // single-source 3 -> 3 channels: the all-vector-ALU backward (k_bwd3v), with or without the pool fold
     // the first encoder block: the second conv's backward (with the pool fold) and the first conv's weight gradient in one launch
-    if (m->pool_fold.conv == &o) {
+    if (m->step.pool_fold.conv == &o) {
         auto f3 = pl.first3.find(&o);
         if (f3 != pl.first3.end()) {
             Op* c0 = f3->second;
-            const Op& pool = *m->pool_fold.pool;
-            m->pool_fold.conv = nullptr;
+            const Op& pool = *m->step.pool_fold.pool;
+            m->step.pool_fold.conv = nullptr;          // consumed (as in the two arms below)
             FirstArgs f{};
             f.dskip = o.out.g.p; f.y1 = o.out.d.p;
             f.dpool = pool.out.g.p; f.idx = pool.pool_idx;
@@ -1713,16 +1716,16 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
             // second conv backward 3 + 3 + 3, first conv weight gradient 3 + 1 floats per pixel
             LAUNCH(m, "first3_bwd", 4.0 * npx * 20.5, 2.0 * npx * (162 + 30),
                    hipLaunchKernelGGL((k_first3<2, 40>), dim3(sg.nblocks), dim3(256), 0, m->stream, f));
-            m->first_done = c0;
+            m->step.first_done = c0;
             return true;
         }
     }
     if (!sw.no_bwd3v && o.need_din && C == 3 && CO == 3 && NS == 1 && !o.accA && a.W % 128 == 0 && a.H % TH == 0) {
-        const bool pf = m->pool_fold.conv == &o;
+        const bool pf = m->step.pool_fold.conv == &o;
         double pb = 0.0;
         if (pf) {
-            const Op& pool = *m->pool_fold.pool;
-            m->pool_fold.conv = nullptr;
+            const Op& pool = *m->step.pool_fold.pool;
+            m->step.pool_fold.conv = nullptr;
             a.pf_y = o.out.d.p;
             a.pf_dpool = pool.out.g.p;
             a.pf_idx = pool.pool_idx;
@@ -1747,9 +1750,9 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
         return true;
     }
     // this conv's output feeds a max-pool whose backward has been folded into this launch (fast_pool_fold)
-    if (m->pool_fold.conv == &o) {
-        const Op& pool = *m->pool_fold.pool;
-        m->pool_fold.conv = nullptr;
+    if (m->step.pool_fold.conv == &o) {
+        const Op& pool = *m->step.pool_fold.pool;
+        m->step.pool_fold.conv = nullptr;
         a.pf_y = o.out.d.p;
         a.pf_dpool = pool.out.g.p;
         a.pf_idx = pool.pool_idx;
@@ -1783,7 +1786,7 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
                 LAUNCH(m, "pgbwd_tc_3x2_3", bytes + 2 * tb, fl + 4.0 * B * a.H * a.W * 3 * 6,
                        hipLaunchKernelGGL((k_pgbwd<3, 2, 3, true, 512, true, false, true>), dim3(g), dim3(512), 0, m->stream, a));
             }
-            m->tconv_done = tc;
+            m->step.tconv_done = tc;
             return true;
         }
         const int g = pg_grid<k_pgbwd<3, 2, 3, true, 512, true>>(m, ntiles);
@@ -1800,7 +1803,7 @@ bool fast_conv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, do
                 const int g = pg_grid<k_pgbwd<c, 2, c, true, 512, false, false, false, true>>(m, ntiles);               \
                 LAUNCH(m, "pgbwd_tc_" #c "x2_" #c, bytes + 2 * tb, fl + tfl,                                            \
                        hipLaunchKernelGGL((k_pgbwd<c, 2, c, true, 512, false, false, false, true>), dim3(g), dim3(512), 0, m->stream, a)); \
-                m->tconv_done = tc;                                                                                     \
+                m->step.tconv_done = tc;                                                                                     \
                 return true;                                                                                            \
             }
             TCMX(6) TCMX(12)
@@ -1837,10 +1840,10 @@ bool fast_pool_fold(Model* m, Op& pool, Op& conv) {
     if (C != CO || !(C == 3 || C == 6 || C == 12)) return false;
     const int TW = 32 * (12 / CO);
     if (!dense(pool.out.g) || !dense(pool.out.d)) return false;
-    if ((conv.out.d.W % TW || conv.out.d.H % TH) && !g_plans[m].first3.count(&conv)) return false;      // the tile kernels fold whole tiles only
+    if ((conv.out.d.W % TW || conv.out.d.H % TH) && !pg_find(m).first3.count(&conv)) return false;      // the tile kernels fold whole tiles only
     pool.pool_idx_valid = false;
-    m->pool_fold.conv = &conv;
-    m->pool_fold.pool = &pool;
+    m->step.pool_fold.conv = &conv;
+    m->step.pool_fold.pool = &pool;
     return true;
 }
 
@@ -1859,8 +1862,8 @@ static void head_args(A& a, const Model* m, const Op& head, const float* y, cons
     a.hw = m->p + head.w_off; a.hb = m->p + head.b_off;
     a.hpartials = m->head_partials;
     a.hscalars = m->scalars;
-    a.hlabel_part = m->label_part_valid ? m->label_part : nullptr;
-    a.hlabel_nblk = m->label_part_nblk;
+    a.hlabel_part = m->step.label_part_valid ? m->label_part : nullptr;
+    a.hlabel_nblk = m->step.label_part_nblk;
     a.hcfg = cfg;
     a.hn_label = n_label;
     a.hgscale = gscale;
@@ -1868,8 +1871,8 @@ static void head_args(A& a, const Model* m, const Op& head, const float* y, cons
 }
 // ... and behind it: the block partial sums wait for the launch that ends the backward pass (k_pg_fold)
 static void head_launched(Model* m, const Op& head, int nblocks) {
-    m->head_pending.partials = m->head_partials; m->head_pending.nblocks = nblocks; m->head_pending.C = 3;
-    m->head_pending.dw = m->g + head.w_off; m->head_pending.dbias = m->g + head.b_off;
+    m->step.head_pending.partials = m->head_partials; m->step.head_pending.nblocks = nblocks; m->step.head_pending.C = 3;
+    m->step.head_pending.dw = m->g + head.w_off; m->step.head_pending.dbias = m->g + head.b_off;
 }
 
 // The conv that feeds the annotator head, in a training step: its forward launch also runs the head, the weighted BCE and the
@@ -1880,7 +1883,7 @@ bool fast_conv_fwd_head(Model* m, int B, Op& o, Op& head, const float* y, const 
     if (!conv_supported(m, o) || !m->head_defer_ok) return false;
     const int C = o.inA.d.C, NS = o.inB.d.C ? 2 : 1, CO = o.out.d.C;
     if (C != 3 || NS != 1 || CO != 3 || head.inA.d.p != o.out.d.p || head.inA.d.C != 3 || !dense(head.inA.d)) return false;
-    PgPlan& pl = g_plans[m];
+    const PgPlan& pl = pg_find(m);
     auto it = pl.slot.find({&o, 0});
     if (it == pl.slot.end()) return false;
     FwdArgs a{};
@@ -1936,9 +1939,9 @@ bool fast_first3_fwd(Model* m, int B, Op& c1, Op& c2, Op& pool, float* y0, unsig
     if (nblk > 2048) return false;
     a.nstrip_blocks = nblk;
     int nride = 0;
-    if (m->prep_flush) {            // the step's operand preparation rides in this launch (blocks nblk ..)
-        m->prep_flush = nullptr;
-        a.prep = g_plans[m].prep;
+    if (m->step.prep_flush) {            // the step's operand preparation rides in this launch (blocks nblk ..)
+        m->step.prep_flush = nullptr;
+        a.prep = pg_find(m).prep;
         nride = a.prep.nblocks;
     }
     LAUNCH(m, "first3_fwd", bytes, flops, hipLaunchKernelGGL((k_first3_fwd<0, 27>), dim3(nblk + nride), dim3(256), 0, m->stream, a));
@@ -1984,7 +1987,7 @@ bool fast_tail3(Model* m, int B, Op& o, Op& head, const float* y, const dnnca_lo
     if (!o.need_din || o.accA || !dense(o.inA.d) || !dense(o.inA.g) || (o.alpha >= 0.f && !o.premasked)) return false;
     const int H = o.out.d.H, W = o.out.d.W;
     if (!strip_shape_ok(B, H, W, false) || o.alpha > 1.f) return false;
-    PgPlan& pl = g_plans[m];
+    const PgPlan& pl = pg_find(m);
     auto it = pl.wslot.find({&o, 0});
     if (it == pl.wslot.end()) return false;
     TailArgs a{};
@@ -2033,13 +2036,13 @@ bool fast_tail3(Model* m, int B, Op& o, Op& head, const float* y, const dnnca_lo
                hipLaunchKernelGGL(kern, dim3(nblk), dim3(256), tail3_lds, m->stream, a));
     }
     head_launched(m, head, nblk);
-    m->tail_done = &o;
+    m->step.tail_done = &o;
     return true;
 }
 
 bool fast_tconv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, double flops) {
     if (!fast_tconv_supported(m, o)) return false;
-    PgPlan& pl = g_plans[m];
+    const PgPlan& pl = pg_find(m);
     auto it = pl.wslot.find({&o, 0});
     if (it == pl.wslot.end()) return false;
     const FoldDesc& f = pl.folds[it->second];
@@ -2069,21 +2072,21 @@ bool fast_tconv_bwd(Model* m, int B, Op& o, double out_bytes, double in_bytes, d
 // after the last backward op: fold every slab set into the flat gradient vector (one launch)
 int fast_finish_backward(Model* m) {
     if (m->desc.flags & 1) return DNNCA_OK;
-    PgPlan& pl = g_plans[m];
-    if (!pl.built || pl.folds.empty()) return DNNCA_OK;
+    if (!m->plan_pg || !m->plan_pg->built || m->plan_pg->folds.empty()) return DNNCA_OK;
+    PgPlan& pl = *m->plan_pg;
     HeadTail h{};
     int extra = 0;
-    if (m->head_pending.partials) {
-        h.partials = m->head_pending.partials; h.nblocks = m->head_pending.nblocks; h.C = m->head_pending.C;
-        h.dw = m->head_pending.dw; h.dbias = m->head_pending.dbias; h.scalars = m->scalars;
+    if (m->step.head_pending.partials) {
+        h.partials = m->step.head_pending.partials; h.nblocks = m->step.head_pending.nblocks; h.C = m->step.head_pending.C;
+        h.dw = m->step.head_pending.dw; h.dbias = m->step.head_pending.dbias; h.scalars = m->scalars;
         extra = h.C + 2;
-        m->head_pending.partials = nullptr;
+        m->step.head_pending.partials = nullptr;
     }
     // single-replica train step whose every gradient (and the loss) comes out of this launch: wait for optimizer_step and let the
     // fold apply Adam as well (fast_fold_adam)
     if (extra && !m->comm && !m->dry && m->merged_launches() && m->desc.l2 == 0.f && pl.fold_outputs + h.C + 1 == m->nT &&
         !m->sw.no_fold_adam) {
-        m->fold_deferred = true;
+        m->step.fold_deferred = true;
         pl.pending_head = h;
         return DNNCA_OK;
     }
@@ -2095,9 +2098,9 @@ int fast_finish_backward(Model* m) {
 
 // the deferred fold of fast_finish_backward with the Adam update (and the step outputs) in the same launch
 int fast_fold_adam(Model* m, float lr_t, const dnnca_loss_cfg& cfg, double n_label, double inv_batch_hw) {
-    PgPlan& pl = g_plans[m];
+    const PgPlan& pl = pg_find(m);
     const HeadTail h = pl.pending_head;
-    m->fold_deferred = false;
+    m->step.fold_deferred = false;
     AdamTail ad{m->p, m->m, m->v, lr_t, m->beta1, m->beta2, m->eps, cfg, n_label, inv_batch_hw, m->out5};
     LAUNCH(m, "pg_fold_adam", 28.0 * m->nT, 10.0 * m->nT,
            hipLaunchKernelGGL(k_pg_fold, dim3((unsigned)pl.folds.size() + h.C + 2, pl.fold_chunks), dim3(256), 0, m->stream,

@@ -480,8 +480,8 @@ bool fast_head_train(Model* m, int B, Op& o, const float* y, const dnnca_loss_cf
             else LAUNCH(m, "head_train_" #c, bytes, 30.0 * npix, hipLaunchKernelGGL((k_head_train<c, px>), dim3(blocks), dim3(256), 0, m->stream, a)); \
         }                                                                                                              \
         if (m->head_defer_ok && m->merged_launches()) {       /* reduced by the launch that ends the backward pass (k_pg_fold) */ \
-            m->head_pending.partials = m->head_partials; m->head_pending.nblocks = blocks; m->head_pending.C = c;       \
-            m->head_pending.dw = a.dw; m->head_pending.dbias = a.dbias;                                                \
+            m->step.head_pending.partials = m->head_partials; m->step.head_pending.nblocks = blocks; m->step.head_pending.C = c;       \
+            m->step.head_pending.dw = a.dw; m->step.head_pending.dbias = a.dbias;                                                \
             return true;                                                                                               \
         }                                                                                                              \
         LAUNCH(m, "head_reduce", 0, 0,                                                                                 \
@@ -498,8 +498,8 @@ bool fast_head_train(Model* m, int B, Op& o, const float* y, const dnnca_loss_cf
 // Model::head_partials: the fold launch reduces them, or head_reduce does
 void fast_head_partials_done(Model* m, int C, int blocks, float* dw, float* dbias) {
     if (m->head_defer_ok && m->merged_launches()) {
-        m->head_pending.partials = m->head_partials; m->head_pending.nblocks = blocks; m->head_pending.C = C;
-        m->head_pending.dw = dw; m->head_pending.dbias = dbias;
+        m->step.head_pending.partials = m->head_partials; m->step.head_pending.nblocks = blocks; m->step.head_pending.C = C;
+        m->step.head_pending.dw = dw; m->step.head_pending.dbias = dbias;
         return;
     }
 #define HEAD_CASE(c)                                                                                                   \

@@ -85,6 +85,7 @@ constexpr float kBnMomentum = 0.99f;   // Keras BatchNormalization defaults [TF-
 constexpr float kBnEps = 1e-3f;
 
 struct RegionState;                      // kernels_region.hip
+struct PgPlan; struct IgPlan; struct Ig3xPlan;      // kernels_mfma.hip, kernels_igemm.hip, kernels_ig3x.hip
 
 // the thresholds of a pixel-confusion histogram: sorted ascending on the device (the kernel bins by binary search); the counts go
 // back to the caller's order through `order`
@@ -123,6 +124,15 @@ struct StepSwitches {
 };
 StepSwitches step_switches();                   // model.hip: fills the table from the environment
 
+// What a train step asks of its forward pass (dnnca_train_step and its plan dump; the default asks for nothing).  An argument of
+// forward(), never model state: head_in_conv_requested (model.hip) is the one place that decides `head_in_conv`
+struct StepRequest {
+    const float* y = nullptr;        // the step's labels and loss configuration (the head-in-conv launches read them)
+    dnnca_loss_cfg cfg{};
+    bool defer_head = false;         // a backward pass follows: the head runs fused with the loss and its backward
+    bool head_in_conv = false;       // pixel-group plan: the head may ride in the epilogue of the conv that feeds it (fast_conv_fwd_head)
+};
+
 struct Model {
     dnnca_model_desc desc;
     StepSwitches sw;
@@ -136,12 +146,7 @@ struct Model {
     double* scalars = nullptr;           // kScalars doubles
     float* out5 = nullptr;               // = g + nT : [loss, positive_rate, weight, ymin, ymax]
     float *x_stage = nullptr, *y_stage = nullptr, *logits = nullptr, *dlogits = nullptr, *prob = nullptr;
-    // the fused head's partial sums wait for the launch that ends the backward pass (k_pg_fold reduces them: one launch less)
-    struct HeadPending { const float* partials = nullptr; int nblocks = 0, C = 0; float* dw = nullptr; float* dbias = nullptr; } head_pending;
     bool head_defer_ok = false;           // set by the pixel-group plan when a k_pg_fold launch exists
-    bool step_init_done = false;      // train step: the launch that prepares the pixel-group B operands already zeroed scalars / gradients / slabs
-    // single-replica training steps: the step outputs are written by the Adam launch instead of a launch of their own
-    struct FinalizePending { bool on = false; dnnca_loss_cfg cfg; double n_label = 0, inv_batch_hw = 0; } fin_pending;
     float* y_smooth = nullptr;           // smoothed labels of the step (label_smoothing, utils/losses.py:62-67)
     // region (Tversky) term of the loss (dnnca_model_set_region_loss, kernels_region_loss.hip).  ws: per image kRlStat doubles
     // (I, P, Y, A, C of the last step), then the block partials of the step's sums; sums_batch: images of the last step that wrote it
@@ -189,23 +194,36 @@ struct Model {
     int64_t iterations = 0;
     float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-7f;
     int last_batch = 0;
-    bool defer_head = false, head_deferred = false;   // train step: the head runs fused with the loss and its backward
-    // train step on the pixel-group plan: the head rides in the epilogue of the conv that feeds it (fast_conv_fwd_head); forward()
-    // then needs the step's labels and loss configuration, and loss_and_backward() finds label statistics and head already done
-    // label statistics of a train step as per-block partials (sum, min, max, -) written by the first encoder block's fused launch
-    // (kernels_fused.hip) and consumed by the head-in-conv kernel: no launch and no atomics of their own
-    float* label_part = nullptr;
-    int label_part_nblk = 0;
-    bool label_part_valid = false;
-    const Op* tconv_done = nullptr;      // the transposed conv whose backward rode in the launch of the conv behind it (k_pgbwd TCF)
-    const Op* first_done = nullptr;      // the first conv whose weight gradient rode in the backward launch of the conv behind it (k_first3)
-    // the step's operand preparation (k_pg_prep: B operands + zeroing) waits for the first launch of the forward pass: the first
-    // encoder block's strip kernel takes it along as extra blocks; any other launch flushes it first (LAUNCH)
-    void (*prep_flush)(Model*) = nullptr;
-    bool fold_deferred = false;          // the slab fold waits for optimizer_step: fold + Adam + step outputs in one launch (fast_fold_adam)
-    const Op* tail_done = nullptr;       // the conv whose backward already ran inside the forward pass (fast_tail3)
-    struct PoolFold { const Op* conv = nullptr; const Op* pool = nullptr; } pool_fold;     // fast_pool_fold -> fast_conv_bwd hand-over
-    struct HeadInConv { const float* y = nullptr; dnnca_loss_cfg cfg; bool requested = false, done = false, labels_done = false; } head_in_conv;
+    // What one step hands from launch to launch (and from forward() to loss_and_backward() to optimizer_step()).  forward() begins
+    // a pass with `step = Step{}`, in front of fast_prepare: nothing of an earlier step, finished or stopped on an error, survives
+    // it.  Every other write is a launch setting a hand-over or the launch it is meant for consuming it.  (The hand-overs inside a
+    // kernel family live in its plan: PgPlan::prep / pending_head, IgPlan::fold_pending; the per-op ones in Op.)
+    struct Step {
+        // the fused head's partial sums wait for the launch that ends the backward pass (k_pg_fold reduces them: one launch less)
+        struct HeadPending { const float* partials = nullptr; int nblocks = 0, C = 0; float* dw = nullptr; float* dbias = nullptr; } head_pending;
+        bool step_init_done = false;      // train step: the launch that prepares the pixel-group B operands already zeroed scalars / gradients / slabs
+        // single-replica training steps: the step outputs are written by the Adam launch instead of a launch of their own
+        struct FinalizePending { bool on = false; dnnca_loss_cfg cfg; double n_label = 0, inv_batch_hw = 0; } fin_pending;
+        bool head_deferred = false;       // train step: the head runs fused with the loss and its backward
+        // label statistics of a train step as per-block partials (sum, min, max, -) written into Model::label_part by the first
+        // encoder block's fused launch (kernels_fused.hip) and consumed by the head-in-conv kernel: no launch and no atomics of their own
+        int label_part_nblk = 0; bool label_part_valid = false;
+        const Op* tconv_done = nullptr;      // the transposed conv whose backward rode in the launch of the conv behind it (k_pgbwd TCF)
+        const Op* first_done = nullptr;      // the first conv whose weight gradient rode in the backward launch of the conv behind it (k_first3)
+        // the step's operand preparation (k_pg_prep: B operands + zeroing) waits for the first launch of the forward pass: the first
+        // encoder block's strip kernel takes it along as extra blocks; any other launch flushes it first (LAUNCH)
+        void (*prep_flush)(Model*) = nullptr;
+        bool fold_deferred = false;          // the slab fold waits for optimizer_step: fold + Adam + step outputs in one launch (fast_fold_adam)
+        const Op* tail_done = nullptr;       // the conv whose backward already ran inside the forward pass (fast_tail3)
+        struct PoolFold { const Op* conv = nullptr; const Op* pool = nullptr; } pool_fold;     // fast_pool_fold -> fast_conv_bwd hand-over
+        // the forward pass of a train step ran the label statistics (labels_done) and maybe the head (done) on the labels y
+        struct HeadInConv { const float* y = nullptr; bool done = false, labels_done = false; } head_in_conv;
+        bool wg_pending = false;             // the side stream holds work of this backward pass
+        bool bucketing = false;              // this step's backward pass sends buckets
+        int64_t bucket_hi = 0, bucket_fin = 0;   // [bucket_fin, bucket_hi) is final and not yet sent
+        std::vector<char> op_done;           // per pass: this op's work rode in an earlier launch of the pass
+    } step;
+    float* label_part = nullptr;         // the table behind Step::label_part_valid
     // data parallel
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
@@ -220,14 +238,11 @@ struct Model {
     // BatchNorm passes and data-gradient convs of the main chain instead of in front of them.
     hipStream_t wg_stream = nullptr;
     hipEvent_t wg_fork = nullptr, wg_join = nullptr, wg_bucket = nullptr;
-    bool wg_pending = false;             // the side stream holds work of this backward pass
     bool wg_side_begin();                // fork: later launches on `stream` go to the side stream; false: not in this mode
     void wg_side_end(hipStream_t main);  // back to the main stream
     int wg_side_join();                  // the main stream waits for the side stream (end of the backward pass)
     hipEvent_t ev_bucket = nullptr, ev_comm_done = nullptr;
     int bucket_state = 0;                // 0 undecided, 1 the op order finalises a suffix (bucketing possible), -1 it does not
-    bool bucketing = false;              // this step's backward pass sends buckets
-    int64_t bucket_hi = 0, bucket_fin = 0;   // [bucket_fin, bucket_hi) is final and not yet sent
     int collectives_last_step = 0;       // gradient all-reduce calls issued by the last train step
     int send_bucket(int64_t lo, int64_t hi);
     // Input pipeline (dnnca_stage_*): a batch travels host -> HBM on its own copy stream into one of a ring of staging slots
@@ -251,6 +266,9 @@ struct Model {
     ConfThresholds eval_thr;             // also the one-shot dnnca_pixel_confusion* (never inside an evaluation); counts in conf_dev
     // region metrics (kernels_region.hip): specs, accumulators and workspace; region_eval: the staged eval steps add region counts
     RegionState* region = nullptr;
+    // the kernel families' plans, built by the first forward pass (fast_prepare, ig_prepare, ig3x_prepare), dropped by fast_release /
+    // ig_release / ig3x_release; nullptr: none (force_generic, or no forward pass yet)
+    PgPlan* plan_pg = nullptr; IgPlan* plan_ig = nullptr; Ig3xPlan* plan_ig3x = nullptr;
     bool region_eval = false;
     float* out_ring = nullptr;           // pinned host memory: kStageSlots x 8 floats (out5 of the step that used the slot)
     // per-step training metrics (dnnca_train_metrics): the fused head kernels store the step's probabilities into `prob` (their
@@ -293,7 +311,6 @@ struct Model {
     int enc_ops = 0, n_enc = 0;
     bool lockstep() const;
     std::vector<int> pass_order(bool backward) const;      // op indices in the order a pass visits them
-    std::vector<char> op_done;                              // per pass: this op's work rode in an earlier launch of the pass
 
     // input sensitivity (dnnca_input_sensitivity): while sens_pass is set the inference forward keeps every tensor a backward pass
     // reads (no fused, elided or riding op) and leaves its logits in `dlogits`; the tensors' .g views are the pass's scratch.
@@ -342,7 +359,7 @@ struct Model {
     int build_multires();                // the MultiResUnet plan (desc.arch == DNNCA_ARCH_MULTIRES)
     int build_buffers();                 // flat parameter / gradient / optimizer vectors, staging and output buffers, Keras defaults
     int alloc(void** ptr, size_t bytes);
-    int forward(const float* x_dev, int B, bool training);
+    int forward(const float* x_dev, int B, bool training, const StepRequest& req = StepRequest());
     int loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cfg, bool backward);
     int optimizer_step(float lr);
     int flush_profile();
@@ -357,9 +374,9 @@ struct Model {
 // A launch is only "open" for profiling between begin() and end(); focus mode leaves other launches untouched.
 #define LAUNCH(m, name, bytes, flops, call)                \
     do {                                                   \
-        if ((m)->prep_flush) {      /* a deferred operand preparation that no launch has taken along: it goes first */ \
-            auto flush_ = (m)->prep_flush;                 \
-            (m)->prep_flush = nullptr;                     \
+        if ((m)->step.prep_flush) {      /* a deferred operand preparation that no launch has taken along: it goes first */ \
+            auto flush_ = (m)->step.prep_flush;                 \
+            (m)->step.prep_flush = nullptr;                     \
             flush_(m);                                     \
         }                                                  \
         bool prof_open_ = false;                           \

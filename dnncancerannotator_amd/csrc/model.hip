@@ -142,7 +142,7 @@ bool Model::wg_side_begin() {
     }
     if (!wg_fork || !wg_join || !wg_bucket) return false;
     if (hipEventRecord(wg_fork, stream) != hipSuccess || hipStreamWaitEvent(wg_stream, wg_fork, 0) != hipSuccess) return false;
-    wg_pending = true;
+    step.wg_pending = true;
     stream = wg_stream;
     return true;
 }
@@ -150,8 +150,8 @@ bool Model::wg_side_begin() {
 void Model::wg_side_end(hipStream_t main) { stream = main; }
 
 int Model::wg_side_join() {
-    if (!wg_pending) return DNNCA_OK;
-    wg_pending = false;
+    if (!step.wg_pending) return DNNCA_OK;
+    step.wg_pending = false;
     HIP_TRY(hipEventRecord(wg_join, wg_stream));
     HIP_TRY(hipStreamWaitEvent(stream, wg_join, 0));
     return DNNCA_OK;
@@ -731,7 +731,7 @@ bool Model::lockstep() const {
 
 std::vector<int> Model::pass_order(bool backward) const {
     std::vector<int> ord;
-    const int n = (int)ops.size(), ne = lockstep() && !(backward && bucketing) ? enc_ops * n_enc : 0;
+    const int n = (int)ops.size(), ne = lockstep() && !(backward && step.bucketing) ? enc_ops * n_enc : 0;
     // Only the levels whose tensors are small walk in lockstep: at full resolution an op's output (134 MB at 8 x 512 x 512 x 16) is
     // what the next op of the SAME encoder reads, largely out of the 256 MB Infinity Cache; with the other encoders' ops in between it
     // comes from HBM.  Measured on mulmo_unet (8.93 ms sequential, same box): lockstep over all four levels 9.23 ms, levels <= 256^2
@@ -755,7 +755,7 @@ std::vector<int> Model::pass_order(bool backward) const {
     return ord;
 }
 
-int Model::forward(const float* x_dev, int B, bool training) {
+int Model::forward(const float* x_dev, int B, bool training, const StepRequest& req) {
     if (B < 1 || B > desc.max_batch) { set_error("batch %d outside [1, max_batch=%d]", B, desc.max_batch); return DNNCA_EINVAL; }
     last_batch = B;
     if (!dry && !sens_pass) tta_spread_valid = false;   // the probabilities are about to change (dnnca_forward_tta_spread sets it again)
@@ -768,36 +768,33 @@ int Model::forward(const float* x_dev, int B, bool training) {
             o.inA.d.p = const_cast<float*>(x_dev) + off;
         }
     xin.d.p = const_cast<float*>(x_dev);
-    step_init_done = false;
-    if (!sens_pass) DN_TRY(fast_prepare(this));
+    step = Step{};          // a pass begins: no hand-over of an earlier step, finished or stopped on an error, survives this line
+    if (!sens_pass) DN_TRY(fast_prepare(this, req.defer_head));
     DN_TRY(ig_prepare(this));
-    head_in_conv.done = false;
-    tail_done = first_done = tconv_done = nullptr;
-    fold_deferred = false;
     // the head will ride in the last conv's epilogue: it needs the label statistics (positive rate) of this step, so they go first
     // (pg_prep has just zeroed the scalars)
-    bool head_in_conv_ok = head_in_conv.requested && !generic && (step_init_done || dry) && head_defer_ok && ops.size() >= 2 &&
+    bool head_in_conv_ok = req.head_in_conv && !generic && (step.step_init_done || dry) && head_defer_ok && ops.size() >= 2 &&
                            ops.back().type == OP_HEAD && fast_head_supported(this, ops.back());
     // ... either from the first encoder block's fused launch (when the head-in-conv kernel will be there to consume its partials
     // table; the label image is then the network's output geometry: the first block runs at full resolution) or from their own kernel
-    label_part_valid = false;
     const float* labels_in_first_block = nullptr;
     if (head_in_conv_ok) {
         if (!sw.no_label_fusion && fast_head_in_conv_possible(this) && ops[0].type == OP_CONV && !ops[0].need_din && ops[0].out.d.H == outH &&
             ops[0].out.d.W == outW)
-            labels_in_first_block = head_in_conv.y;
+            labels_in_first_block = req.y;
         else
-            head_in_conv_ok = fast_label_stats(this, (size_t)B * outH * outW, head_in_conv.y);
+            head_in_conv_ok = fast_label_stats(this, (size_t)B * outH * outW, req.y);
     }
-    head_in_conv.labels_done = head_in_conv_ok;
+    step.head_in_conv.y = req.y;
+    step.head_in_conv.labels_done = head_in_conv_ok;
 
     // op_done[i]: op i's work rode in an earlier launch of this pass (a max-pool in the preceding conv's / BatchNorm's launch, the
     // later layers of a fused block, the twin ops of the other mulmo encoders)
     const std::vector<int> order = pass_order(false);
-    op_done.assign(ops.size(), 0);
+    step.op_done.assign(ops.size(), 0);
     for (size_t ok_ = 0; ok_ < order.size(); ++ok_) {
         size_t oi = (size_t)order[ok_];
-        if (op_done[oi]) continue;
+        if (step.op_done[oi]) continue;
         Op& o = ops[oi];
         cur_op = &o.name;
         switch (o.type) {
@@ -808,34 +805,34 @@ int Model::forward(const float* x_dev, int B, bool training) {
                 if (head_in_conv_ok && oi + 2 == ops.size()) {                // the conv that feeds the head: head + loss + head backward in its epilogue
                     const float gs = (float)(1.0 / ((double)outH * outW * B));
                     const double npx = (double)B * outH * outW;
-                    if (fast_tail3(this, B, o, ops.back(), head_in_conv.y, head_in_conv.cfg, gs) ||
-                        fast_conv_fwd_head(this, B, o, ops.back(), head_in_conv.y, head_in_conv.cfg, gs, bytes + 4.0 * npx * (1 + o.out.d.C), flops + 30.0 * npx)) {
-                        head_in_conv.done = true;
+                    if (fast_tail3(this, B, o, ops.back(), req.y, req.cfg, gs) ||
+                        fast_conv_fwd_head(this, B, o, ops.back(), req.y, req.cfg, gs, bytes + 4.0 * npx * (1 + o.out.d.C), flops + 30.0 * npx)) {
+                        step.head_in_conv.done = true;
                         break;
                     }
-                    if (label_part_valid) { set_error("internal: label partials without the head-in-conv kernel"); return DNNCA_ESTATE; }
+                    if (step.label_part_valid) { set_error("internal: label partials without the head-in-conv kernel"); return DNNCA_ESTATE; }
                 }
                 if (oi == 0 && labels_in_first_block) {
                     if (!generic && fused_down_fwd(this, B, oi, training, labels_in_first_block)) {
-                        op_done[oi + 1] = op_done[oi + 2] = 1;
+                        step.op_done[oi + 1] = step.op_done[oi + 2] = 1;
                         break;
                     }
                     // the first block did not take them: the label statistics get their own launch after all
-                    head_in_conv_ok = fast_label_stats(this, (size_t)B * outH * outW, head_in_conv.y);
-                    head_in_conv.labels_done = head_in_conv_ok;
+                    head_in_conv_ok = fast_label_stats(this, (size_t)B * outH * outW, req.y);
+                    step.head_in_conv.labels_done = head_in_conv_ok;
                     labels_in_first_block = nullptr;
                 }
                 if (!generic && fused_down_fwd(this, B, oi, training)) {      // conv, conv, pool of one encoder block in one launch
-                    op_done[oi + 1] = op_done[oi + 2] = 1;
+                    step.op_done[oi + 1] = step.op_done[oi + 2] = 1;
                     break;
                 }
                 if (!generic && o.inB.d.C && fused_up2_fwd(this, B, oi, training)) {      // the two convs of a decoder block (its transposed conv rode earlier)
-                    op_done[oi + 1] = 1;
+                    step.op_done[oi + 1] = 1;
                     break;
                 }
                 Op* pool = (!generic && oi + 1 < ops.size() && fast_pool_fusable(this, o, ops[oi + 1])) ? &ops[oi + 1] : nullptr;
                 if (!generic && fast_conv_fwd(this, B, o, bytes + (pool ? 4.0 * nelem(B, pool->out.d) : 0.0), flops, pool)) {
-                    if (pool) op_done[pool - ops.data()] = 1;
+                    if (pool) step.op_done[pool - ops.data()] = 1;
                     break;
                 }
                 Op* bn_next = (training && oi + 1 < ops.size() && ops[oi + 1].type == OP_BN && ops[oi + 1].inA.d.p == o.out.d.p &&
@@ -862,7 +859,7 @@ int Model::forward(const float* x_dev, int B, bool training) {
                 Op* pool_bn = (bn_pool && training && oi + 2 < ops.size() && ops[oi + 2].type == OP_BN &&
                                ops[oi + 2].inA.d.p == bn_pool->out.d.p && fast_bn_supported(this, ops[oi + 2])) ? &ops[oi + 2] : nullptr;
                 if (!generic && fast_bn_fwd(this, B, o, training, kBnMomentum, kBnEps, bn_pool, pool_bn)) {
-                    if (bn_pool) op_done[bn_pool - ops.data()] = 1;
+                    if (bn_pool) step.op_done[bn_pool - ops.data()] = 1;
                     break;
                 }
                 if (!all_f32(o)) return DNNCA_ESTATE;
@@ -900,7 +897,7 @@ int Model::forward(const float* x_dev, int B, bool training) {
                        g_bn_finalize(stream, nb.inA.d.C, 1.0, nb.ws, p + nb.w_off, p + nb.b_off, state + nb.mm_off, state + nb.mv_off,
                                      nb.coef, 0, kBnMomentum, kBnEps));
                 LAUNCH(this, "join_infer", 3 * tb, tb, join_infer(stream, B, o.inA.d, o.inB.d, nb.out.d, nb.coef));
-                op_done[oi + 1] = 1;
+                step.op_done[oi + 1] = 1;
                 break;
             }
             case OP_POOL: {
@@ -916,11 +913,11 @@ int Model::forward(const float* x_dev, int B, bool training) {
                 double flops = 2.0 * nelem(B, o.out.d) * o.inA.d.C;
                 int used = 3;
                 if (!generic && fused_up_fwd(this, B, oi, training, &used)) { // tconv, conv, conv of one decoder block in one launch
-                    for (int t = 1; t < used; ++t) op_done[oi + t] = 1;       // (+ the next block's tconv when it rides along)
+                    for (int t = 1; t < used; ++t) step.op_done[oi + t] = 1;       // (+ the next block's tconv when it rides along)
                     break;
                 }
                 if (!generic && fast_up3_fwd(this, B, oi)) {                  // tconv + two-source conv of the 3-channel level
-                    op_done[oi + 1] = 1;
+                    step.op_done[oi + 1] = 1;
                     break;
                 }
                 Op* bn_next = (training && oi + 1 < ops.size() && ops[oi + 1].type == OP_BN && ops[oi + 1].inA.d.p == o.out.d.p &&
@@ -934,9 +931,8 @@ int Model::forward(const float* x_dev, int B, bool training) {
             }
             case OP_HEAD: {
                 double npix = (double)B * outH * outW;
-                head_deferred = false;
-                if (defer_head && !generic && fast_head_supported(this, o)) {
-                    head_deferred = true;   // runs fused with the loss and its own backward (fast_head_train)
+                if (req.defer_head && !generic && fast_head_supported(this, o)) {
+                    step.head_deferred = true;   // runs fused with the loss and its own backward (fast_head_train)
                     break;
                 }
                 if (!all_f32(o)) return DNNCA_ESTATE;
@@ -952,9 +948,8 @@ int Model::forward(const float* x_dev, int B, bool training) {
 // ---------------------------------------------------------------------------------------------- loss + backward
 int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cfg, bool backward) {
     cur_op = nullptr;
-    if (!(backward && head_in_conv.done && y_dev == head_in_conv.y))
-        head_pending.partials = nullptr;    // leftovers of a step that stopped on an error (not: the head that just ran in the forward pass)
-    fin_pending.on = false;
+    // the partial sums of a head that ran in this step's forward pass wait for the fold; no other head's do (that head runs again)
+    if (!(backward && step.head_in_conv.done && y_dev == step.head_in_conv.y)) step.head_pending.partials = nullptr;
     const float* y_raw = y_dev;         // the boundary term's distance map comes from the labels before the blur
     if (cfg.label_smoothing) {          // utils/losses.py:62-67: every later use of y_true (positive rate, assertions, loss) sees the blurred labels
         if (!y_smooth) DN_TRY(alloc((void**)&y_smooth, (size_t)desc.max_batch * outH * outW * 4));
@@ -967,15 +962,15 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
     }
     const bool generic = desc.flags & 1;
     size_t npix = (size_t)B * outH * outW;
-    const bool labels_done = backward && head_in_conv.labels_done && y_dev == head_in_conv.y;
-    const bool head_was_in_conv = labels_done && head_in_conv.done;
-    head_in_conv.labels_done = head_in_conv.done = false;
+    const bool labels_done = backward && step.head_in_conv.labels_done && y_dev == step.head_in_conv.y;
+    const bool head_was_in_conv = labels_done && step.head_in_conv.done;
+    step.head_in_conv.labels_done = step.head_in_conv.done = false;          // consumed: this pass is the one they were run for
     // scalars: label sum 0, min +inf, max -inf, loss 0, l2 0
-    if (!(step_init_done && backward))
+    if (!(step.step_init_done && backward))
         LAUNCH(this, "g_step_init", 0, 0,
                g_step_init(stream, scalars, g, backward ? (size_t)(nT + 8) : 0, multires() ? nogamma_scratch : extra_zero,
                            !backward ? 0 : (multires() ? nogamma_n : (generic ? 0 : extra_zero_n))));
-    step_init_done = false;
+    step.step_init_done = false;          // consumed, whether or not g_step_init ran
     if (labels_done) {
         // the forward pass of this train step already ran the label statistics (and maybe the head, in its last conv's epilogue)
     } else if (generic || !fast_label_stats(this, npix, y_dev))
@@ -991,7 +986,7 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
             boundary_transform(this, y_raw, B, outH, outW, boundary.cols, boundary.phi, nullptr);
             if (!dry) boundary.batch = B;
         }
-        if (backward && head_deferred) {
+        if (backward && step.head_deferred) {
             if (!region_loss_head_train(this, B, ops.back(), y_dev, cfg, gscale)) {
                 set_error("internal: deferred head has no region-loss kernel");
                 return DNNCA_ESTATE;
@@ -1002,7 +997,7 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
         }
     } else if (head_was_in_conv) {
         head_done = true;
-    } else if (backward && head_deferred) {
+    } else if (backward && step.head_deferred) {
         Op& ho = ops.back();
         double fb = 4.0 * nelem(B, ho.inA.d);
         if (!fast_head_train(this, B, ho, y_dev, cfg, gscale, 2 * fb + 4.0 * npix)) {
@@ -1020,7 +1015,6 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
         // bucketed gradient all-reduce (data parallel, large models): see model.h.  Not for the pixel-group plan (its slabs are
         // folded into the gradient vector by the launch that ENDS the backward pass; 34.7 KB anyway) and not with an L2
         // regulariser (its gradient is added after the loop).
-        bucketing = false;
         collectives_last_step = 0;
         if (comm && !dry && (size_t)nT * 4 > (1u << 20) && desc.l2 == 0.f && !head_defer_ok) {
             if (bucket_state == 0) {
@@ -1034,25 +1028,25 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
                     prev = lo;
                 }
             }
-            bucketing = bucket_state == 1;
-            bucket_hi = bucket_fin = nT;
+            step.bucketing = bucket_state == 1;
+            step.bucket_hi = step.bucket_fin = nT;
         }
         const std::vector<int> order = pass_order(true);          // (lockstep over the mulmo encoders unless this pass sends gradient buckets)
-        op_done.assign(ops.size(), 0);
+        step.op_done.assign(ops.size(), 0);
         for (size_t ok_ = 0; ok_ < order.size(); ++ok_) {
             const int i = order[ok_];
-            if (op_done[i]) continue;
+            if (step.op_done[i]) continue;
             Op& o = ops[i];
             cur_op = &o.name;
-            if (bucketing && i + 1 < (int)ops.size()) {
+            if (step.bucketing && i + 1 < (int)ops.size()) {
                 // everything from the previous (later) op's parameters to the end of the vector is final now
                 const Op& d = ops[i + 1];
                 int64_t lo = d.w_off >= 0 ? d.w_off : d.b_off;
                 if (d.b_off >= 0 && d.b_off < lo) lo = d.b_off;
-                if (lo >= 0 && lo < bucket_fin) bucket_fin = lo;
-                if ((size_t)(bucket_hi - bucket_fin) * 4 >= sw.bucket_bytes) {
-                    DN_TRY(send_bucket(bucket_fin, bucket_hi));
-                    bucket_hi = bucket_fin;
+                if (lo >= 0 && lo < step.bucket_fin) step.bucket_fin = lo;
+                if ((size_t)(step.bucket_hi - step.bucket_fin) * 4 >= sw.bucket_bytes) {
+                    DN_TRY(send_bucket(step.bucket_fin, step.bucket_hi));
+                    step.bucket_hi = step.bucket_fin;
                 }
             }
             switch (o.type) {
@@ -1068,16 +1062,16 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
                     int Cin = o.inA.d.C + o.inB.d.C;
                     double ob = 4.0 * nelem(B, o.out.d), ib = 4.0 * (nelem(B, o.inA.d) + nelem(B, o.inB.d));
                     double flops = 2.0 * B * o.out.d.H * o.out.d.W * o.k * o.k * Cin * o.out.d.C;
-                    if (first_done == &o) {                         // its weight gradient rode in the previous launch (k_first3)
-                        first_done = nullptr;
+                    if (step.first_done == &o) {                         // its weight gradient rode in the previous launch (k_first3)
+                        step.first_done = nullptr;
                         break;
                     }
-                    if (tail_done == &o && head_was_in_conv) {      // its backward ran with the head, inside the forward pass (fast_tail3)
-                        tail_done = nullptr;
+                    if (step.tail_done == &o && head_was_in_conv) {      // its backward ran with the head, inside the forward pass (fast_tail3)
+                        step.tail_done = nullptr;
                         break;
                     }
                     if (!generic && i >= 2 && fused_up_bwd(this, B, (size_t)i)) {       // second conv, first conv, transposed conv of a decoder block in one launch
-                        op_done[i - 1] = op_done[i - 2] = 1;
+                        step.op_done[i - 1] = step.op_done[i - 2] = 1;
                         break;
                     }
                     if (!generic && (fast_conv_bwd(this, B, o, ob, ib, flops) || fast_first_conv_bwd(this, B, o, ob, ib, flops) ||
@@ -1125,7 +1119,7 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
                 case OP_POOL: {
                     double bytes = 4.0 * (2 * nelem(B, o.inA.d) + 2 * nelem(B, o.out.d));
                     if (!generic && i >= 2 && fused_down_bwd(this, B, (size_t)i)) {     // pool, second conv, first conv of an encoder block in one launch
-                        op_done[i - 1] = op_done[i - 2] = 1;
+                        step.op_done[i - 1] = step.op_done[i - 2] = 1;
                         break;
                     }
                     if (!generic && i > 0 && fast_pool_into_bn(this, o, ops[i - 1])) break;   // rides in the backward passes of the BatchNorm in front of it
@@ -1140,8 +1134,8 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
                 case OP_TCONV: {
                     double ob = 4.0 * nelem(B, o.out.d), ib = 4.0 * nelem(B, o.inA.d);
                     double flops = 2.0 * nelem(B, o.out.d) * o.inA.d.C;
-                    if (tconv_done == &o) {                         // its backward rode in the previous launch (k_pgbwd TCF)
-                        tconv_done = nullptr;
+                    if (step.tconv_done == &o) {                         // its backward rode in the previous launch (k_pgbwd TCF)
+                        step.tconv_done = nullptr;
                         break;
                     }
                     if (!generic && (fast_tconv_bwd(this, B, o, ob, ib, flops) || ig_tconv_bwd(this, B, o, ob, ib, flops))) break;
@@ -1176,10 +1170,10 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
     }
     if (backward && !comm && !dry && merged_launches()) {
         // optimizer_step() follows every backward pass: its Adam launch also writes the step outputs (one launch fewer)
-        fin_pending.on = true;
-        fin_pending.cfg = cfg;
-        fin_pending.n_label = (double)npix;
-        fin_pending.inv_batch_hw = 1.0 / ((double)outH * outW * B);
+        step.fin_pending.on = true;
+        step.fin_pending.cfg = cfg;
+        step.fin_pending.n_label = (double)npix;
+        step.fin_pending.inv_batch_hw = 1.0 / ((double)outH * outW * B);
         return DNNCA_OK;
     }
     LAUNCH(this, "g_finalize_scalars", 0, 0,
@@ -1396,7 +1390,7 @@ int Model::send_bucket(int64_t lo, int64_t hi) {
     }
     HIP_TRY(hipEventRecord(ev_bucket, stream));
     HIP_TRY(hipStreamWaitEvent(comm_stream, ev_bucket, 0));
-    if (wg_pending) {          // weight gradients of the bucket's layers may still be running on the side stream (FIFO: one event covers them)
+    if (step.wg_pending) {          // weight gradients of the bucket's layers may still be running on the side stream (FIFO: one event covers them)
         HIP_TRY(hipEventRecord(wg_bucket, wg_stream));
         HIP_TRY(hipStreamWaitEvent(comm_stream, wg_bucket, 0));
     }
@@ -1409,11 +1403,11 @@ int Model::send_bucket(int64_t lo, int64_t hi) {
 int Model::optimizer_step(float lr) {
     cur_op = nullptr;
     float gscale = 1.0f;
-    if (comm && !dry && bucketing) {
+    if (comm && !dry && step.bucketing) {
         // the backward pass has sent the finalised suffix in buckets; what is left -- the first layers and the step's loss in the
         // tail -- follows on the same (communication) stream, and Adam waits for all of it
-        bucketing = false;
-        DN_TRY(send_bucket(0, bucket_hi));
+        step.bucketing = false;
+        DN_TRY(send_bucket(0, step.bucket_hi));
         DN_TRY(send_bucket(nT, nT + 1));
         HIP_TRY(hipEventRecord(ev_comm_done, comm_stream));
         HIP_TRY(hipStreamWaitEvent(stream, ev_comm_done, 0));
@@ -1428,16 +1422,16 @@ int Model::optimizer_step(float lr) {
     iterations += dry ? 0 : 1;
     double t = (double)(dry ? 1 : iterations);
     float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, t)) / (1.0 - std::pow((double)beta1, t)));
-    if (fin_pending.on && fold_deferred) {
-        fin_pending.on = false;
-        return fast_fold_adam(this, lr_t, fin_pending.cfg, fin_pending.n_label, fin_pending.inv_batch_hw);
+    if (step.fin_pending.on && step.fold_deferred) {
+        step.fin_pending.on = false;          // consumed (here and below): this launch writes the step outputs
+        return fast_fold_adam(this, lr_t, step.fin_pending.cfg, step.fin_pending.n_label, step.fin_pending.inv_batch_hw);
     }
-    if (fold_deferred) { set_error("internal: deferred gradient fold without a single-replica optimizer step"); return DNNCA_ESTATE; }
-    if (fin_pending.on) {
-        fin_pending.on = false;
+    if (step.fold_deferred) { set_error("internal: deferred gradient fold without a single-replica optimizer step"); return DNNCA_ESTATE; }
+    if (step.fin_pending.on) {
+        step.fin_pending.on = false;
         LAUNCH(this, "g_adam", 28.0 * nT, 10.0 * nT,
-               g_adam_finalize(stream, (size_t)nT, p, g, m, v, lr_t, beta1, beta2, eps, gscale, scalars, fin_pending.cfg,
-                               fin_pending.n_label, fin_pending.inv_batch_hw, out5));
+               g_adam_finalize(stream, (size_t)nT, p, g, m, v, lr_t, beta1, beta2, eps, gscale, scalars, step.fin_pending.cfg,
+                               step.fin_pending.n_label, step.fin_pending.inv_batch_hw, out5));
         return DNNCA_OK;
     }
     LAUNCH(this, "g_adam", 28.0 * nT, 10.0 * nT, g_adam(stream, (size_t)nT, p, g, m, v, lr_t, beta1, beta2, eps, gscale));
@@ -1693,22 +1687,22 @@ int dnnca_forward(void* model, const float* x_nhwc, int batch, int training, flo
     return M->flush_profile();
 }
 
-// row: the tm_hist / tm_pin row of the step's training-metric counts (its staging slot, or kStageSlots)
+// What a train step enqueues, for dnnca_train_step* and for the plan dump (dry): forward with the step's request, loss + backward,
+// optimizer, the training-metric count.  row: the tm_hist / tm_pin row of the counts (the step's staging slot, or kStageSlots)
+static int train_pass(Model* M, const float* x_dev, const float* y_dev, int batch, float lr, const dnnca_loss_cfg& cfg, int row) {
+    const StepRequest req{y_dev, cfg, true, head_in_conv_requested(M, cfg)};
+    DN_TRY(M->forward(x_dev, batch, true, req));
+    DN_TRY(M->loss_and_backward(y_dev, batch, cfg, true));
+    DN_TRY(M->optimizer_step(lr));
+    if (!M->dry) M->tm_ran[row] = 0;
+    if (M->train_metrics_on()) DN_TRY(train_metrics_count(M, y_dev, batch, row));      // the raw labels, never y_smooth
+    return DNNCA_OK;
+}
+
 static int train_step_impl(Model* M, const float* x_dev, const float* y_dev, int batch, float lr, const dnnca_loss_cfg* cfg,
                            dnnca_step_out* out, int row) {
     if (!cfg) { set_error("null loss cfg"); return DNNCA_EINVAL; }
-    M->defer_head = true;
-    M->head_in_conv.requested = head_in_conv_requested(M, *cfg);
-    M->head_in_conv.y = y_dev;
-    M->head_in_conv.cfg = *cfg;
-    int frc = M->forward(x_dev, batch, true);
-    M->defer_head = false;
-    M->head_in_conv.requested = false;
-    DN_TRY(frc);
-    DN_TRY(M->loss_and_backward(y_dev, batch, *cfg, true));
-    DN_TRY(M->optimizer_step(lr));
-    M->tm_ran[row] = 0;
-    if (M->train_metrics_on()) DN_TRY(train_metrics_count(M, y_dev, batch, row));      // the raw labels, never y_smooth
+    DN_TRY(train_pass(M, x_dev, y_dev, batch, lr, *cfg, row));
     if (out) return read_out(M, M->world, out);      // after the all-reduce the loss slot holds the sum over ranks of the local means
     return DNNCA_OK;
 }
@@ -2262,16 +2256,7 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
     const int B = batch;
     int rc;
     if (pass == DNNCA_PLAN_TRAIN) {
-        M->defer_head = true;
-        M->head_in_conv.requested = head_in_conv_requested(M, cfg);
-        M->head_in_conv.y = M->y_stage;
-        M->head_in_conv.cfg = cfg;
-        rc = M->forward(M->x_stage, B, true);
-        M->defer_head = false;
-        M->head_in_conv.requested = false;
-        if (rc == DNNCA_OK) rc = M->loss_and_backward(M->y_stage, B, cfg, true);
-        if (rc == DNNCA_OK) rc = M->optimizer_step(1e-3f);
-        if (rc == DNNCA_OK && M->train_metrics_on()) rc = train_metrics_count(M, M->y_stage, B, Model::kStageSlots);
+        rc = train_pass(M, M->x_stage, M->y_stage, B, 1e-3f, cfg, Model::kStageSlots);
     } else if (pass == DNNCA_PLAN_EVAL) {
         rc = M->forward(M->x_stage, B, false);
         if (rc == DNNCA_OK) rc = M->loss_and_backward(M->y_stage, B, cfg, false);
