@@ -127,6 +127,14 @@ def build_parser(prog='python3 -m annotator'):
     p.add_argument('--temperature', type=float, default=argparse.SUPPRESS, metavar='T',
                    help='temperature scaling: the tables and masks of sigmoid(logit(p) / T), T in [0.05, 20], e.g. the temperature '
                         '`evaluate --calibration` fitted (default: 1, no scaling)')
+    p.add_argument('--lesion_features', action='store_true', default=argparse.SUPPRESS,
+                   help='what every lesion looks like in the input modalities: also write lesion_features.csv (outline, axes, and per '
+                        'modality mean, deviation, extrema, percentiles and the contrast against the tissue around the lesion) and, '
+                        'with --link_slices, exam_lesion_features.csv')
+    p.add_argument('--feature_bins', type=int, default=argparse.SUPPRESS, metavar='N',
+                   help='histogram bins behind the percentiles of --lesion_features, 0..256 (0: no percentiles; default: 32)')
+    p.add_argument('--feature_ring', type=int, default=argparse.SUPPRESS, metavar='R',
+                   help='the tissue around a lesion of --lesion_features: background pixels within R pixels, 0..8 (0: none; default: 3)')
     return parser
 
 

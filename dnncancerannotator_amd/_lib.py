@@ -110,6 +110,16 @@ class SliceSpread(C.Structure):                    # dnnca_slice_spread (16 byte
     _fields_ = [('pixels', C.c_int32), ('max_spread', C.c_float), ('sum_spread_q24', C.c_uint64)]
 
 
+class LesionShape(C.Structure):                    # dnnca_lesion_shape (48 bytes, no padding)
+    _fields_ = [('slice', C.c_int32), ('row', C.c_int32), ('area', C.c_int32), ('boundary', C.c_int32), ('edges', C.c_int32),
+                ('reserved', C.c_int32), ('sum_xx', C.c_uint64), ('sum_yy', C.c_uint64), ('sum_xy', C.c_uint64)]
+
+
+class LesionIntensity(C.Structure):                # dnnca_lesion_intensity (40 bytes, no padding): a body or a ring record
+    _fields_ = [('slice', C.c_int32), ('row', C.c_int32), ('channel', C.c_int32), ('n', C.c_int32), ('min', C.c_float),
+                ('max', C.c_float), ('sum_q16', C.c_uint64), ('sum_sq_q16', C.c_uint64)]
+
+
 class SpreadOutcome(C.Structure):                  # dnnca_spread_outcome (64 bytes): classes TN, FP, FN, TP
     _fields_ = [('n', C.c_uint64 * 4), ('sum_q24', C.c_uint64 * 4)]
 
@@ -133,6 +143,12 @@ CALIB_MIN_T, CALIB_MAX_T = 0.05, 20.0              # the temperatures the librar
 LESION_SPREAD_DTYPE = np.dtype([('slice', '<i4'), ('row', '<i4'), ('area', '<i4'), ('max_spread', '<f4'), ('sum_spread_q24', '<u8')])
 SLICE_SPREAD_DTYPE = np.dtype([('pixels', '<i4'), ('max_spread', '<f4'), ('sum_spread_q24', '<u8')])
 SPREAD_OUTCOME_DTYPE = np.dtype([('n', '<u8', (4,)), ('sum_q24', '<u8', (4,))])
+# DeviceModel.lesion_table_features returns structured arrays of these dtypes
+LESION_SHAPE_DTYPE = np.dtype([('slice', '<i4'), ('row', '<i4'), ('area', '<i4'), ('boundary', '<i4'), ('edges', '<i4'),
+                               ('reserved', '<i4'), ('sum_xx', '<u8'), ('sum_yy', '<u8'), ('sum_xy', '<u8')])
+LESION_INTENSITY_DTYPE = np.dtype([('slice', '<i4'), ('row', '<i4'), ('channel', '<i4'), ('n', '<i4'), ('min', '<f4'), ('max', '<f4'),
+                                   ('sum_q16', '<u8'), ('sum_sq_q16', '<u8')])
+FEATURE_MAX_BINS, FEATURE_MAX_RING, FEATURE_MAX_CHANNELS = 256, 8, 16
 
 
 class LesionPlaneOut(C.Structure):                 # dnnca_lesion_plane_out: buffers and capacities in, counts out
@@ -225,6 +241,10 @@ SIGNATURES = {
     'dnnca_lesion_table_spread': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                             C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
                                             C.POINTER(C.c_int32), _FP, C.POINTER(LesionSpread), C.POINTER(SliceSpread)]),
+    'dnnca_lesion_table_features': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
+                                              C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP,
+                                              C.c_int64, C.POINTER(C.c_int32), _FP, C.c_int, C.c_int, C.c_int, C.POINTER(LesionShape),
+                                              C.POINTER(LesionIntensity), C.POINTER(LesionIntensity), C.POINTER(C.c_uint32)]),
     'dnnca_spread_by_outcome': (C.c_int, [_VP, _FP, _FP, _FP, C.c_int, C.c_int, C.c_int, _FP, C.c_int, C.POINTER(SpreadOutcome)]),
     'dnnca_calibration': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, _FP, C.c_int, C.POINTER(CalibBin),
                                     C.POINTER(CalibTotal), C.POINTER(C.c_double)]),

@@ -494,6 +494,135 @@ def surface_summary(slice_values, exam_values):
             [mean(v[i] for v in both) for i in (8, 9, 10, 11)] + [mean(v[i] for v in exams) for i in (-3, -2, -1)])
 
 
+# ---- `annotator predict --lesion_features`: what a lesion looks like in the input channels -------------------------------------------
+# DeviceModel.lesion_table_features gives, per lesion, integer moments and outline counts (shape), and per lesion and modality the
+# pixel count, float32 extrema and the integer sums of q = rint(v * 2^16) and q^2 of the lesion's own pixels (body) and of the
+# background around it (ring), plus a histogram of the body.  Every difference of products is taken in Python integers before the
+# one float64 division; floats are written with repr, float32 extrema with the 9 digits that give them back.
+FEATURE_BINS = 32                # --feature_bins
+FEATURE_RING = 3                 # --feature_ring
+FEATURE_BIN_RANGE = (0, 256)     # what the library accepts
+FEATURE_RING_RANGE = (0, 8)
+FEATURE_PERCENTILES = (10, 50, 90)
+FEATURE_SHAPE_COLUMNS = ['boundary_px', 'edge_len', 'extent', 'major_axis', 'minor_axis', 'eccentricity', 'orientation_deg']
+Q16 = float(1 << 16)             # sum_q16 is the sum of rint(v * 2^16)
+
+
+def check_features(lesion_features, bins=None, ring=None):
+    """the values of --feature_bins / --feature_ring (None: not given) -> (bins, ring) with the defaults filled in.  They mean
+    nothing without --lesion_features"""
+    if not lesion_features:
+        if bins is not None or ring is not None:
+            raise ValueError('--feature_bins / --feature_ring set the histogram and the ring of --lesion_features: add --lesion_features')
+        return None, None
+    bins = FEATURE_BINS if bins is None else int(bins)
+    ring = FEATURE_RING if ring is None else int(ring)
+    if not FEATURE_BIN_RANGE[0] <= bins <= FEATURE_BIN_RANGE[1]:
+        raise ValueError('--feature_bins %d outside %d..%d' % ((bins,) + FEATURE_BIN_RANGE))
+    if not FEATURE_RING_RANGE[0] <= ring <= FEATURE_RING_RANGE[1]:
+        raise ValueError('--feature_ring %d outside %d..%d' % ((ring,) + FEATURE_RING_RANGE))
+    return bins, ring
+
+
+def feature_intensity_columns(names):
+    cols = []
+    for m in names:
+        cols += ['%s_%s' % (c, m) for c in ['mean', 'std', 'min', 'max'] + ['p%d' % p for p in FEATURE_PERCENTILES] +
+                 ['ring_px', 'ring_mean', 'ring_std', 'contrast']]
+    return cols
+
+
+def lesion_feature_columns(names):
+    return ['exam', 'slice', 'lesion'] + FEATURE_SHAPE_COLUMNS + feature_intensity_columns(names)
+
+
+def exam_lesion_feature_columns(names):
+    return ['exam', 'exam_lesion', 'surface_px'] + feature_intensity_columns(names)
+
+
+def feature_shape_values(row, shape):
+    """boundary_px, edge_len, extent (area / box area), major_axis and minor_axis (4 sqrt(lambda) of the coordinate covariance),
+    eccentricity (sqrt(1 - lambda2 / lambda1); 0 for a point) and orientation_deg (0.5 atan2(2 cxy, cxx - cyy): the major axis
+    against the x axis, y pointing down) of one lesion: `row` its record of lesion_table's rows, `shape` the shape record beside it"""
+    if (int(shape['row']), int(shape['area'])) != (int(row['row']), int(row['area'])):
+        raise ValueError('shape record of lesion %d (%d px) beside lesion %d (%d px)' % (shape['row'], shape['area'], row['row'], row['area']))
+    n, sx, sy = int(row['area']), int(row['sum_x']), int(row['sum_y'])
+    cxx = (n * int(shape['sum_xx']) - sx * sx) / (n * n)
+    cyy = (n * int(shape['sum_yy']) - sy * sy) / (n * n)
+    cxy = (n * int(shape['sum_xy']) - sx * sy) / (n * n)
+    d = math.sqrt((cxx - cyy) ** 2 + 4.0 * cxy * cxy)
+    l1, l2 = (cxx + cyy + d) / 2.0, max((cxx + cyy - d) / 2.0, 0.0)
+    box = (int(row['x1']) - int(row['x0']) + 1) * (int(row['y1']) - int(row['y0']) + 1)
+    return [int(shape['boundary']), int(shape['edges']), repr(n / box), repr(4.0 * math.sqrt(l1)), repr(4.0 * math.sqrt(l2)),
+            repr(math.sqrt(max(1.0 - l2 / l1, 0.0)) if l1 > 0 else 0.0), repr(math.degrees(0.5 * math.atan2(2.0 * cxy, cxx - cyy)))]
+
+
+def feature_percentile(hist, fraction, lo, hi):
+    """the value below which `fraction` of the histogram's pixels lie: with t = fraction * n, k the first bin whose inclusive
+    cumulative count reaches t: (k + (t - count before k) / count of k) / bins, clipped to [lo, hi] (the extrema of the values)"""
+    counts = [int(c) for c in hist]
+    t, before = fraction * sum(counts), 0
+    for k, c in enumerate(counts):
+        if before + c >= t and c:
+            return min(max((k + (t - before) / c) / len(counts), lo), hi)
+        before += c
+    raise ValueError('feature_percentile: an empty histogram')
+
+
+def pool_intensity(records):
+    """body or ring records of one modality (one per part; None: none) -> (n, sum_q16, sum_sq_q16, min, max) over all their pixels;
+    records without a pixel have no extrema"""
+    held = [r for r in records or [] if int(r['n'])]
+    return (sum(int(r['n']) for r in held), sum(int(r['sum_q16']) for r in held), sum(int(r['sum_sq_q16']) for r in held),
+            min([float(r['min']) for r in held], default=0.0), max([float(r['max']) for r in held], default=0.0))
+
+
+def _mean_std(n, sq, ssq):
+    """mean and population standard deviation from the integer sums of q and q^2 over n pixels"""
+    return sq / n / Q16, math.sqrt(n * ssq - sq * sq) / n / Q16
+
+
+def feature_intensity_values(body, ring, hist):
+    """the cells of one modality: body / ring: (n, sum_q16, sum_sq_q16, min, max) as pool_intensity gives them (ring None: the ring
+    is off), hist: the body's counts per bin (None: --feature_bins 0).  Blank: the percentiles without a histogram; ring_px,
+    ring_mean, ring_std and contrast with the ring off; the last three also for a ring without a pixel"""
+    n, sq, ssq, lo, hi = body
+    mean, std = _mean_std(n, sq, ssq)
+    cells = [repr(mean), repr(std), '%.9g' % lo, '%.9g' % hi]
+    cells += ['' if hist is None else repr(feature_percentile(hist, p / 100.0, lo, hi)) for p in FEATURE_PERCENTILES]
+    if ring is None:
+        return cells + ['', '', '', '']
+    if not ring[0]:
+        return cells + [0, '', '', '']
+    ring_mean, ring_std = _mean_std(*ring[:3])
+    return cells + [int(ring[0]), repr(ring_mean), repr(ring_std), repr(mean - ring_mean)]
+
+
+def lesion_feature_values(exam, slice_id, row, shape, body, ring, hist):
+    """the lesion_features.csv line of one lesion: `row` its record of lesion_table's rows; shape, body [C], ring [C] or None, hist
+    [C, bins] or None: the records of lesion_table_features beside it"""
+    cells = [exam, int(slice_id), int(row['row'])] + feature_shape_values(row, shape)
+    for c in range(len(body)):
+        if (int(body[c]['row']), int(body[c]['n'])) != (int(row['row']), int(row['area'])):
+            raise ValueError('body record of lesion %d (%d px) beside lesion %d (%d px)' % (body[c]['row'], body[c]['n'], row['row'], row['area']))
+        cells += feature_intensity_values(pool_intensity([body[c]]), None if ring is None else pool_intensity([ring[c]]),
+                                          None if hist is None else hist[c])
+    return cells
+
+
+def exam_lesion_feature_values(exam, exam_lesion, parts):
+    """the exam_lesion_features.csv line of one exam lesion.  parts: the (shape, body, ring, hist) of its 2-D lesions.  Pooled from
+    the summed integers, the extrema and the summed histograms of the parts -- the values of all their pixels together, never a
+    mean of means; surface_px: the parts' edge_len summed (the faces towards the slices above and below are not counted)"""
+    cells = [exam, int(exam_lesion), sum(int(s['edges']) for s, _, _, _ in parts)]
+    _, body0, ring0, hist0 = parts[0]
+    for c in range(len(body0)):
+        hist = None if hist0 is None else [sum(col) for col in zip(*[[int(v) for v in h[c]] for _, _, _, h in parts])]
+        cells += feature_intensity_values(pool_intensity([b[c] for _, b, _, _ in parts]),
+                                          None if ring0 is None else pool_intensity([r[c] for _, _, r, _ in parts]), hist)
+    return cells
+
+
 # ---- `--uncertainty`: how much the test-time-augmentation views disagree ------------------------------------------------------------
 # DeviceModel.lesion_table_spread and spread_by_outcome give integer sums of rint(spread * 2^24) and float32 maxima; a mean is
 # sum / pixels / 2^24 in float64 (repr), a maximum is written with the 9 digits that give the float32 back.

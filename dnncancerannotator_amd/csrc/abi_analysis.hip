@@ -240,7 +240,8 @@ static int plane_resolve(Model* M, const char* who, const float* prob_hw, int ba
 }
 
 // the planes of one call: probabilities, the spread of the views, labels (nullptr: the entry has none); out: where a result plane goes
-struct Planes { const float *prob, *spread, *y; float* out; };
+// x: the input channels of dnnca_lesion_table_features, x_n floats (kScratchRegion, beside probabilities alone)
+struct Planes { const float *prob, *spread, *y; float* out; const float* x = nullptr; size_t x_n = 0; };
 
 // region_inputs forgets the labels kept for dnnca_render_composite, tta_io_buffers does not: every entry keeps the scratch it had
 enum Scratch { kScratchRegion, kScratchTtaIo };
@@ -248,17 +249,19 @@ enum Scratch { kScratchRegion, kScratchTtaIo };
 // The host planes of n floats each -> the scratch `which`; returns where the entry reads each plane on the device.  host.prob ==
 // nullptr: the model's own probabilities and spread plane, and the result goes where it came from.
 //   kScratchRegion  no host plane: nothing is touched.  Else the probabilities into the first buffer of region_inputs, the labels
-//                   (or, for an entry without labels, the spread) into the second
+//                   (or, for an entry without labels, the spread; or the channels host.x) into the second
 //   kScratchTtaIo   with host probabilities one allocation for every host plane and the want_out planes of the result, in the order
 //                   prob, spread, y, out; with the model's own the labels go to M->y_stage
 static int plane_stage(Model* M, Scratch which, size_t n, const Planes& host, int want_out, Planes* dev) {
     float* slot[4] = {nullptr, nullptr, nullptr, nullptr};          // prob, spread, y, out
     const float* src[3] = {host.prob, host.spread, host.y};
+    float* x_dev = nullptr;
     if (which == kScratchRegion && (host.prob || host.y)) {
         float *first = nullptr, *second = nullptr;
-        DN_TRY(region_inputs(M, n, &first, &second));
+        DN_TRY(region_inputs(M, std::max(n, host.x_n), &first, &second));
         if (host.prob) slot[0] = first;
-        slot[host.y ? 2 : 1] = second;
+        if (host.x) x_dev = second;
+        else slot[host.y ? 2 : 1] = second;
     } else if (which == kScratchTtaIo && host.prob) {
         int count = 0;
         for (int i = 0; i < 3; ++i) count += src[i] != nullptr;
@@ -272,7 +275,9 @@ static int plane_stage(Model* M, Scratch which, size_t n, const Planes& host, in
     }
     for (int i = 0; i < 3; ++i)
         if (src[i] && slot[i]) HIP_TRY(hipMemcpyAsync(slot[i], src[i], n * 4, hipMemcpyHostToDevice, M->stream));
-    *dev = {slot[0] ? slot[0] : M->prob, slot[1] ? slot[1] : M->tta_spread, slot[2] ? slot[2] : M->y_stage, slot[3] ? slot[3] : M->prob};
+    if (x_dev) HIP_TRY(hipMemcpyAsync(x_dev, host.x, host.x_n * 4, hipMemcpyHostToDevice, M->stream));
+    *dev = {slot[0] ? slot[0] : M->prob, slot[1] ? slot[1] : M->tta_spread, slot[2] ? slot[2] : M->y_stage, slot[3] ? slot[3] : M->prob,
+            x_dev ? x_dev : M->x_stage, host.x_n};
     return DNNCA_OK;
 }
 
@@ -434,16 +439,36 @@ struct LesionPlanesIn { const float* prob_hw; int batch, h, w; };
 struct LesionTableOut { dnnca_lesion_row* rows; int64_t rows_capacity, *n_rows; int32_t* totals; uint8_t* mask; int64_t mask_capacity; int32_t* out_hw; };
 struct LesionLinkOut { const uint8_t* continues; dnnca_lesion_link* links; int64_t links_capacity, *n_links; };
 struct LesionSpreadOut { const float* spread_hw; dnnca_lesion_spread* srows; dnnca_slice_spread* stotals; };
+struct LesionFeatOut {
+    const float* x_hwc; int channels, bins, ring;
+    dnnca_lesion_shape* shape; dnnca_lesion_intensity *body, *ring_out; uint32_t* hist;
+};
 
-// dnnca_lesion_table (link == spread == nullptr), dnnca_lesion_table_linked (link) and dnnca_lesion_table_spread (spread)
+// dnnca_lesion_table (link == spread == feat == nullptr), dnnca_lesion_table_linked (link), dnnca_lesion_table_spread (spread) and
+// dnnca_lesion_table_features (feat)
 static int lesion_call(void* model, const LesionPlanesIn& in, LesionArgs a, const LesionTableOut& o, const LesionLinkOut* link,
-                       const LesionSpreadOut* spread) {
+                       const LesionSpreadOut* spread, const LesionFeatOut* feat = nullptr) {
     MODEL(model);
     const int batch = in.batch;
     Plane pl;
     DN_TRY(plane_resolve(M, "lesion table", in.prob_hw, batch, in.h, in.w, 0, &pl));
     DN_TRY(lesion_check(a, pl.h, pl.w));
     if (!o.out_hw) { set_error("lesion table: null out_hw"); return DNNCA_EINVAL; }
+    int channels = 0;
+    if (feat) {                          // before out_hw: a refusal touches no output
+        if ((in.prob_hw == nullptr) != (feat->x_hwc == nullptr)) {
+            set_error("lesion features: prob_hw and x_hwc go together (both host planes, or both NULL for the model's own)");
+            return DNNCA_EINVAL;
+        }
+        channels = feat->channels;
+        if (!feat->x_hwc && (channels == 0 || channels == M->desc.in_channels)) channels = M->desc.in_channels;
+        else if (!feat->x_hwc) { set_error("lesion features: %d channels given, the staged batch has %d", channels, M->desc.in_channels); return DNNCA_EINVAL; }
+        DN_TRY(lesion_features_check(a, channels, feat->bins, feat->ring));
+        if (o.rows && (!feat->shape || !feat->body || (feat->ring && !feat->ring_out) || (feat->bins && !feat->hist))) {
+            set_error("lesion features: null shape / body / ring_out / hist");
+            return DNNCA_EINVAL;
+        }
+    }
     o.out_hw[0] = a.oh;
     o.out_hw[1] = a.ow;
     if (!o.rows) return DNNCA_OK;                 // size query
@@ -466,9 +491,25 @@ static int lesion_call(void* model, const LesionPlanesIn& in, LesionArgs a, cons
         if (!spread->srows || !spread->stotals) { set_error("lesion table: null srows / stotals"); return DNNCA_EINVAL; }
         if (!spread->spread_hw) DN_TRY(tta_spread_plane(M, batch, "dnnca_lesion_table_spread"));
     }
-    Planes dev;      // without labels the second buffer of region_inputs carries the spread plane
-    DN_TRY(plane_stage(M, kScratchRegion, pl.n, {in.prob_hw, spread ? spread->spread_hw : nullptr, nullptr, nullptr}, false, &dev));
+    if (feat && !feat->x_hwc) {
+        if (batch > M->last_batch) {
+            set_error("lesion features: %d slices asked for, the last forward staged %d", batch, M->last_batch);
+            return DNNCA_ESTATE;
+        }
+        if (M->outH != M->desc.height || M->outW != M->desc.width) {
+            set_error("lesion features: the output (%d x %d) differs from the input (%d x %d)", M->outH, M->outW, M->desc.height,
+                      M->desc.width);
+            return DNNCA_ESTATE;
+        }
+    }
+    Planes host = {in.prob_hw, spread ? spread->spread_hw : nullptr, nullptr, nullptr};
+    if (feat && feat->x_hwc) host.x = feat->x_hwc, host.x_n = pl.n * (size_t)channels;
+    Planes dev;      // without labels the second buffer of region_inputs carries the spread plane or the channels
+    DN_TRY(plane_stage(M, kScratchRegion, pl.n, host, false, &dev));
     const bool want_mask = o.mask != nullptr;
+    if (feat)
+        return lesion_table_features(M, dev.prob, dev.x, channels, batch, pl.h, pl.w, a, o.rows, o.n_rows, o.totals, o.mask, want_mask,
+                                     feat->bins, feat->ring, feat->shape, feat->body, feat->ring_out, feat->hist);
     if (spread)
         return lesion_table_spread(M, dev.prob, dev.spread, batch, pl.h, pl.w, a, o.rows, o.n_rows, o.totals, o.mask, want_mask,
                                    spread->srows, spread->stotals);
@@ -501,6 +542,16 @@ int dnnca_lesion_table_spread(void* model, const float* prob_hw, int batch, int 
     const LesionSpreadOut spread = {spread_hw, srows, stotals};
     return lesion_call(model, {prob_hw, batch, h, w}, lesion_args(threshold, resize_factor, filter_size, min_area, max_lesions),
                        {rows, rows_capacity, n_rows, totals, mask, mask_capacity, out_hw}, nullptr, &spread);
+}
+
+int dnnca_lesion_table_features(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
+                                int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
+                                int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw,
+                                const float* x_hwc, int channels, int bins, int ring, dnnca_lesion_shape* shape,
+                                dnnca_lesion_intensity* body, dnnca_lesion_intensity* ring_out, uint32_t* hist) {
+    const LesionFeatOut feat = {x_hwc, channels, bins, ring, shape, body, ring_out, hist};
+    return lesion_call(model, {prob_hw, batch, h, w}, lesion_args(threshold, resize_factor, filter_size, min_area, max_lesions),
+                       {rows, rows_capacity, n_rows, totals, mask, mask_capacity, out_hw}, nullptr, nullptr, &feat);
 }
 
 int dnnca_lesion_table_matched(void* model, const float* prob_hw, const float* y_hw, int batch, int h, int w, float threshold,

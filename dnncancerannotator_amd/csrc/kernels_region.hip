@@ -25,7 +25,8 @@
 //                   bytes per thread and one 32-bit store
 //
 // The lesion table of `annotator predict` (lesion_scan / lesion_stats / lesion_mask), its links and pairs (lesion_link, lesion_match),
-// the spread of the test-time-augmentation views per lesion, slice and pixel outcome (lesion_spread, spread_outcome)
+// the spread of the test-time-augmentation views per lesion, slice and pixel outcome (lesion_spread, spread_outcome),
+// what a lesion looks like in the input channels (lesion_features, lesion_ring)
 // and the boundary distances of `evaluate --surface_distances` (surface_edges / surface_cols / surface_sample) start from the same
 // prep / open / ccl / sizes launches; each is described above its kernels.
 #include <math.h>
@@ -693,6 +694,216 @@ __global__ __launch_bounds__(RB) void k_spread_outcome(const float* __restrict__
     }
 }
 
+// ---- what a lesion looks like in the input channels (dnnca_lesion_table_features): shape, body and ring records under the rows of
+// the lesion table.  A pixel's value in channel c is x' (the channel read through the resize the probabilities went through) as
+// v = min(max(x', 0), 1), NaN = 0.  It enters the sums as q = rint(v * 2^16): q16 and not the q24 of the probabilities, so that
+// q^2 <= 2^32 and a sum of q^2 over the 2^31 pixels a plane can have stays below 2^64.  Extrema go through the float's bits.
+struct FeatShapeAcc {                    // one lesion, zeroed by a memset
+    unsigned long long sxx, syy, sxy;
+    unsigned area, boundary, edges, pad;
+};
+struct FeatAcc {                         // one lesion and channel, body or ring, zeroed by a memset: nmn holds max(~bits) = ~min(bits)
+    unsigned long long sq, ssq;
+    unsigned n, nmn, mx, pad;
+};
+
+// resize_at on channel c of an interleaved plane [in_h, in_w, C]: the same operations in the same order
+__device__ __forceinline__ float resize_at_c(const float* __restrict__ src, const Resize& r, int i, int j, int C, int c) {
+    if (r.identity) return src[((size_t)i * r.in_w + j) * C + c];
+    const float fy = ((float)i + 0.5f) * r.sy - 0.5f;
+    const float fx = ((float)j + 0.5f) * r.sx - 0.5f;
+    const float fy0 = floorf(fy), fx0 = floorf(fx);
+    const int y0 = max((int)fy0, 0), y1 = min((int)ceilf(fy), r.in_h - 1);
+    const int x0 = max((int)fx0, 0), x1 = min((int)ceilf(fx), r.in_w - 1);
+    const float ly = fy - fy0, lx = fx - fx0;
+    const float tl = src[((size_t)y0 * r.in_w + x0) * C + c], tr = src[((size_t)y0 * r.in_w + x1) * C + c];
+    const float bl = src[((size_t)y1 * r.in_w + x0) * C + c], br = src[((size_t)y1 * r.in_w + x1) * C + c];
+    const float top = tl + (tr - tl) * lx;
+    const float bot = bl + (br - bl) * lx;
+    return top + (bot - top) * ly;
+}
+
+// The lanes of a wave that are `on` add pixel (y, x) of every channel to the records of their row `key` (acc, hist: the slice's).
+// Lanes are grouped by row as in lesion_stats; a lane loads its channels inside its own group's pass, so every value is read once.
+// hist == nullptr: no histogram; else one count per pixel and channel (calibration's bin rule: a float32 product, floor, clamp).
+// The counts of ONE row per block -- the first that a wave with all 64 lanes in one lesion claims in *lrow (-1: none yet) -- go to
+// the block's LDS histogram lh [C][bins], which the caller adds to `hist` at its end; everything else goes to `hist` one atomic
+// each.  A lesion that fills the block's 4096 pixels then costs C * bins global atomics per block, not 4096 C, and specks and
+// outlines never ask.  Every lane of the wave must call this.
+__device__ __forceinline__ void feat_intensity(bool on, unsigned key, int y, int x, const float* __restrict__ plane, const Resize& r, int C,
+                                               int bins, FeatAcc* __restrict__ acc, unsigned* __restrict__ hist, unsigned* lh, int* lrow,
+                                               int lane) {
+    unsigned long long pending = __ballot(on);
+    while (pending) {
+        const int leader = __ffsll((long long)pending) - 1;
+        const unsigned k0 = __shfl(key, leader);
+        const bool mine = on && key == k0;
+        const unsigned long long same = __ballot(mine);
+        bool local = false;              // this group's row is the block's
+        if (hist && same == ~0ull) {
+            int held = (int)k0;
+            if (lane == leader) {
+                const int was = atomicCAS(lrow, -1, (int)k0);
+                if (was != -1) held = was;
+            }
+            local = __shfl(held, leader) == (int)k0;
+        }
+        for (int c = 0; c < C; ++c) {
+            unsigned q = 0, bits = 0, nbits = 0;
+            if (mine) {
+                const float xv = resize_at_c(plane, r, y, x, C, c);
+                const float v = xv > 0.f ? (xv < 1.f ? xv : 1.f) : 0.f;      // a NaN compares false: 0
+                bits = __float_as_uint(v);
+                nbits = ~bits;
+                q = (unsigned)rintf(v * 65536.f);
+                if (hist) {
+                    const int bin = min(bins - 1, (int)floorf(v * (float)bins));
+                    if (local) atomicAdd(lh + c * bins + bin, 1u);
+                    else atomicAdd(hist + ((size_t)k0 * C + c) * bins + bin, 1u);
+                }
+            }
+            const unsigned sq = wave_sum(q);                                 // 64 lanes of at most 2^16
+            const unsigned long long ssq = wave_sum64((unsigned long long)q * q);
+            const unsigned mx = wave_max(bits), nmn = wave_max(nbits);
+            if (lane == leader) {
+                FeatAcc* a = acc + (size_t)k0 * C + c;
+                atomicAdd(&a->n, (unsigned)__popcll(same));
+                atomicAdd(&a->sq, (unsigned long long)sq);
+                atomicAdd(&a->ssq, ssq);
+                atomicMax(&a->nmn, nmn);
+                atomicMax(&a->mx, mx);
+            }
+        }
+        if (mine) on = false;
+        pending &= ~same;
+    }
+}
+
+// lesion_spread's grid, (ceil(hw / (RB kFeatU)), slices): a block walks kFeatU runs of RB pixels of ONE slice.  Every pixel of a
+// numbered lesion adds to its shape record -- area, the second moments of its coordinates, the faces that look out of the lesion (a
+// 4-neighbour with another root, or none: the plane's border) and whether it has one -- and to its body records.  No per-slice
+// total is kept here, so no cache line is shared by every block of a slice (what lesion_spread's comment measured).
+constexpr int kFeatU = 16;
+constexpr int kFeatMaxC = 16, kFeatMaxBins = 256;        // what dnnca_lesion_table_features accepts: an LDS histogram of 16 KiB at most
+__global__ __launch_bounds__(RB) void k_lesion_features(const float* __restrict__ x, Resize r, int C, int bins, const int* __restrict__ L,
+                                                        const int* __restrict__ row, int cap, FeatShapeAcc* __restrict__ shp,
+                                                        FeatAcc* __restrict__ body, unsigned* __restrict__ hist) {
+    const int oh = r.out_h, ow = r.out_w, hw = oh * ow, b = blockIdx.y;
+    const size_t g0 = (size_t)b * hw;
+    const float* plane = x + (size_t)b * r.in_h * r.in_w * C;
+    FeatShapeAcc* sh = shp + (size_t)b * cap;
+    FeatAcc* bd = body + (size_t)b * cap * C;
+    unsigned* hs = hist ? hist + (size_t)b * cap * C * bins : nullptr;
+    extern __shared__ unsigned lh[];     // [C][bins] with a histogram, nothing without
+    __shared__ int lrow;
+    if (hs) {
+        for (int i = threadIdx.x; i < C * bins; i += RB) lh[i] = 0;
+        if (threadIdx.x == 0) lrow = -1;
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63;
+    const int p0 = blockIdx.x * (RB * kFeatU) + (int)threadIdx.x;
+    for (int u = 0; u < kFeatU; ++u) {
+        const int p = p0 + u * RB;
+        if (p - (int)threadIdx.x >= hw) break;           // the whole run lies behind the slice: the same for every thread of the block
+        bool on = false;
+        unsigned key = 0, faces = 0;
+        int py = 0, px = 0;
+        if (p < hw) {
+            const int root = L[g0 + p];
+            if (root >= 0) {
+                const int rw = row[root];
+                if (rw >= 0 && rw < cap) {
+                    on = true;
+                    key = (unsigned)rw;
+                    py = p / ow, px = p - py * ow;
+                    faces = (px == 0 || L[g0 + p - 1] != root) + (px == ow - 1 || L[g0 + p + 1] != root) +
+                            (py == 0 || L[g0 + p - ow] != root) + (py == oh - 1 || L[g0 + p + ow] != root);
+                }
+            }
+        }
+        unsigned long long pending = __ballot(on);
+        while (pending) {
+            const int leader = __ffsll((long long)pending) - 1;
+            const unsigned k0 = __shfl(key, leader);
+            const bool mine = on && key == k0;
+            const unsigned long long same = __ballot(mine), edge = __ballot(mine && faces);
+            const unsigned long long ux = mine ? (unsigned long long)px : 0ull, uy = mine ? (unsigned long long)py : 0ull;
+            const unsigned long long sxx = wave_sum64(ux * ux), syy = wave_sum64(uy * uy), sxy = wave_sum64(ux * uy);
+            const unsigned nf = wave_sum(mine ? faces : 0u);
+            if (lane == leader) {
+                FeatShapeAcc* a = sh + k0;
+                atomicAdd(&a->area, (unsigned)__popcll(same));
+                atomicAdd(&a->boundary, (unsigned)__popcll(edge));
+                atomicAdd(&a->edges, nf);
+                atomicAdd(&a->sxx, sxx);
+                atomicAdd(&a->syy, syy);
+                atomicAdd(&a->sxy, sxy);
+            }
+            pending &= ~same;
+        }
+        feat_intensity(on, key, py, px, plane, r, C, bins, bd, hs, lh, &lrow, lane);
+    }
+    if (hs) {                            // every thread of the block gets here: the loop's break is the same for all of them
+        __syncthreads();
+        if (lrow >= 0)
+            for (int i = threadIdx.x; i < C * bins; i += RB)
+                if (lh[i]) atomicAdd(hs + (size_t)lrow * C * bins + i, lh[i]);
+    }
+}
+
+// The tissue around every numbered lesion: a background pixel (in no kept component) belongs to the ring of the smallest row number
+// among the numbered lesions in its (2R + 1)^2 window, clipped by the plane.  That minimum is separable.  grid (ceil(ow / kTile),
+// ceil(oh / kTile), slices): a block loads the row numbers of its tile with a halo of R into LDS (kRingKept: a kept component
+// that has no row; kRingNone: background or outside), takes the minimum along the rows, then along the columns, and adds its ring pixels
+// like lesion_features adds body pixels.  A block whose tile and halo hold no numbered lesion leaves after the load: on a real slice
+// that is nearly every block, and it has read 4 (1 + 2R / kTile)^2 bytes per pixel by then.
+constexpr int kRingMaxR = 8;
+constexpr int kRingE = kTile + 2 * kRingMaxR;
+constexpr int kRingKept = 0x7ffffffe, kRingNone = 0x7fffffff;
+__global__ __launch_bounds__(RB) void k_lesion_ring(const float* __restrict__ x, Resize r, int C, int R, const int* __restrict__ L,
+                                                    const int* __restrict__ row, int cap, FeatAcc* __restrict__ ring) {
+    __shared__ int m[kRingE * kRingE];
+    __shared__ int hm[kRingE * kTile];
+    const int oh = r.out_h, ow = r.out_w, b = blockIdx.z, E = kTile + 2 * R;
+    const size_t g0 = (size_t)b * oh * ow;
+    const int ty0 = blockIdx.y * kTile, tx0 = blockIdx.x * kTile;
+    int any = 0;
+    for (int i = threadIdx.x; i < E * E; i += RB) {
+        const int ty = i / E, tx = i - ty * E;
+        const int y = ty0 - R + ty, xx = tx0 - R + tx;
+        int v = kRingNone;
+        if (y >= 0 && y < oh && xx >= 0 && xx < ow) {
+            const int root = L[g0 + (size_t)y * ow + xx];
+            if (root >= 0) {
+                const int rw = row[root];
+                if (rw >= 0) v = rw < cap ? rw : kRingKept;
+            }
+        }
+        any |= v < cap;
+        m[i] = v;
+    }
+    if (!__syncthreads_or(any)) return;
+    for (int i = threadIdx.x; i < E * kTile; i += RB) {
+        const int ty = i / kTile, tx = i - ty * kTile;
+        int v = kRingNone;
+        for (int d = 0; d <= 2 * R; ++d) v = min(v, m[ty * E + tx + d]);
+        hm[i] = v;
+    }
+    __syncthreads();
+    const float* plane = x + (size_t)b * r.in_h * r.in_w * C;
+    FeatAcc* rg = ring + (size_t)b * cap * C;
+    const int lane = threadIdx.x & 63;
+    const int tx = threadIdx.x & (kTile - 1);
+    for (int ty = threadIdx.x / kTile; ty < kTile; ty += RB / kTile) {       // the same trip count for every thread
+        const int y = ty0 + ty, xx = tx0 + tx;
+        int owner = kRingNone;
+        for (int d = 0; d <= 2 * R; ++d) owner = min(owner, hm[(ty + d) * kTile + tx]);
+        const bool on = y < oh && xx < ow && m[(ty + R) * E + tx + R] == kRingNone && owner < cap;
+        feat_intensity(on, (unsigned)owner, y, xx, plane, r, C, 0, rg, nullptr, nullptr, nullptr, lane);
+    }
+}
+
 // ---- links between neighbouring slices (dnnca_lesion_table_linked).  A pixel's lesion is row[L[g]]: the row number of its root,
 // taken as -1 on background, in a component below min_area and at rows >= cap (they are in no table).
 __device__ __forceinline__ int lesion_row_at(const int* __restrict__ L, const int* __restrict__ row, size_t g, int cap) {
@@ -1015,6 +1226,9 @@ struct RegionState {
     float lesion_rf = 1.f;               // the last dnnca_lesion_table(_linked): what DNNCA_PLAN_LESION(_LINKED) replays
     int lesion_k = 5;
     bool lesion_mask = true;
+    float feat_rf = 1.f;                 // the last dnnca_lesion_table_features: what DNNCA_PLAN_LESION_FEATURES replays
+    int feat_k = 5, feat_bins = 32, feat_ring = 3;
+    bool feat_mask = true;
     // the carry plane of dnnca_lesion_table_linked: the row number (or -1) of every pixel of the last slice of the last linked
     // chunk.  A buffer of its own, not part of `ws`: it outlives every other call on the model
     int* carry = nullptr;
@@ -1035,6 +1249,7 @@ struct RegionState {
 };
 
 static constexpr size_t kRegionBudget = size_t(1) << 24;    // pixel-thresholds per chunk (~21 bytes each)
+static constexpr size_t kFeatBudget = size_t(1) << 30;      // bytes of feature records per chunk (dnnca_lesion_table_features)
 
 static size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
@@ -1393,11 +1608,27 @@ struct LesionWs {                        // carve-up of the workspace for nb sli
     LesionAcc* yacc;
     // spread calls only, behind everything else: the spread rows beside acc and the slices' totals
     SpreadAcc *sacc, *stot;
+    // feature calls only, behind everything else: shape, body and ring records beside acc, the histograms [row][channel][bins]
+    FeatShapeAcc* fshape;
+    FeatAcc *fbody, *fring;
+    unsigned* fhist;
     size_t bytes;
 };
 
+struct LesionFeatIO {                    // what a feature call adds: the channels (device [batch, h, w, channels]) and the host outputs
+    const float* x;
+    int channels, bins, ring;
+    dnnca_lesion_shape* shape;
+    dnnca_lesion_intensity *body, *ring_out;
+    uint32_t* hist;
+    // the feature records of one slice (cap rows) in the workspace
+    size_t slice_bytes(size_t cap) const {
+        return cap * (sizeof(FeatShapeAcc) + (size_t)channels * ((ring ? 2 : 1) * sizeof(FeatAcc) + (size_t)bins * 4));
+    }
+};
+
 static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap, size_t links_per_slice = 0, bool matched = false,
-                              bool spread = false) {
+                              bool spread = false, const LesionFeatIO* ft = nullptr) {
     const size_t n = nb * hw;
     LesionWs w;
     char* p = (char*)base;
@@ -1435,6 +1666,14 @@ static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap, size
     if (spread) {
         w.sacc = (SpreadAcc*)take(nb * cap * sizeof(SpreadAcc));
         w.stot = (SpreadAcc*)take(nb * sizeof(SpreadAcc));
+    }
+    w.fshape = nullptr, w.fbody = nullptr, w.fring = nullptr, w.fhist = nullptr;
+    if (ft) {
+        const size_t rc = nb * cap * ft->channels;
+        w.fshape = (FeatShapeAcc*)take(nb * cap * sizeof(FeatShapeAcc));
+        w.fbody = (FeatAcc*)take(rc * sizeof(FeatAcc));
+        if (ft->ring) w.fring = (FeatAcc*)take(rc * sizeof(FeatAcc));
+        if (ft->bins) w.fhist = (unsigned*)take(rc * ft->bins * 4);
     }
     w.bytes = off;
     return w;
@@ -1574,16 +1813,68 @@ static int lesion_spread_read(Model* M, const SpreadAcc* sacc_dev, const SpreadA
     return DNNCA_OK;
 }
 
+static void feat_record(dnnca_lesion_intensity& o, const FeatAcc& v, int slice, int row, int channel) {
+    const unsigned mn = v.n ? ~v.nmn : 0u, mx = v.n ? v.mx : 0u;      // no pixel (an empty ring): min = max = 0
+    o.slice = slice, o.row = row, o.channel = channel, o.n = (int32_t)v.n;
+    memcpy(&o.min, &mn, 4);
+    memcpy(&o.max, &mx, 4);
+    o.sum_q16 = v.sq, o.sum_sq_q16 = v.ssq;
+}
+
+// the feature records beside the rows that lesion_rows_read has just delivered (`first_row`: the chunk's first row in the caller's
+// buffers); synchronises
+static int lesion_feat_read(Model* M, const LesionWs& ws, const std::vector<int>& tot, int b0, size_t cap, const LesionFeatIO& ft,
+                            int64_t first_row) {
+    hipStream_t s = M->stream;
+    const int nb = (int)tot.size();
+    const size_t C = (size_t)ft.channels, bins = (size_t)ft.bins;
+    std::vector<size_t> first(nb + 1, 0);
+    for (int b = 0; b < nb; ++b) first[b + 1] = first[b] + std::min<size_t>((size_t)std::max(tot[b], 0), cap);
+    std::vector<FeatShapeAcc> sh(first[nb]);
+    std::vector<FeatAcc> bd(first[nb] * C), rg(ft.ring ? first[nb] * C : 0);
+    for (int b = 0; b < nb; ++b) {
+        const size_t cnt = first[b + 1] - first[b], at = first[b], dev = (size_t)b * cap;
+        if (!cnt) continue;
+        HIP_TRY(hipMemcpyAsync(sh.data() + at, ws.fshape + dev, cnt * sizeof(FeatShapeAcc), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(bd.data() + at * C, ws.fbody + dev * C, cnt * C * sizeof(FeatAcc), hipMemcpyDeviceToHost, s));
+        if (ft.ring) HIP_TRY(hipMemcpyAsync(rg.data() + at * C, ws.fring + dev * C, cnt * C * sizeof(FeatAcc), hipMemcpyDeviceToHost, s));
+        if (bins)                        // histograms are plain counts: straight into the caller's buffer
+            HIP_TRY(hipMemcpyAsync(ft.hist + ((size_t)first_row + at) * C * bins, ws.fhist + dev * C * bins, cnt * C * bins * 4,
+                                   hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int b = 0; b < nb; ++b)
+        for (size_t r = first[b]; r < first[b + 1]; ++r) {
+            const int slice = b0 + b, rw = (int)(r - first[b]);
+            const FeatShapeAcc& v = sh[r];
+            dnnca_lesion_shape& o = ft.shape[first_row + r];
+            o.slice = slice, o.row = rw, o.area = (int32_t)v.area, o.boundary = (int32_t)v.boundary, o.edges = (int32_t)v.edges;
+            o.reserved = 0;
+            o.sum_xx = v.sxx, o.sum_yy = v.syy, o.sum_xy = v.sxy;
+            for (size_t c = 0; c < C; ++c) {
+                feat_record(ft.body[((size_t)first_row + r) * C + c], bd[r * C + c], slice, rw, (int)c);
+                if (ft.ring) feat_record(ft.ring_out[((size_t)first_row + r) * C + c], rg[r * C + c], slice, rw, (int)c);
+            }
+        }
+    return DNNCA_OK;
+}
+
 // the chunk loop of lesion_table, lesion_table_linked (link != nullptr: the three link launches behind every chunk's table) and
 // lesion_table_matched (link and match: the label plane's table as well, then lesion_match / lesion_link_emit over the three
 // sets of tables / lesion_match_carry in the place of the link launches).  A matched chunk holds two planes and three sets of
 // tables and lists: its slices are a third of a linked chunk's (region_chunk with T = 3), which changes no result
 static int lesion_run(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows, int64_t* n_rows,
                       int32_t* totals, uint8_t* mask, bool want_mask, const LesionLinkIO* link, const LesionMatchIO* match = nullptr,
-                      const LesionSpreadIO* sp = nullptr) {
+                      const LesionSpreadIO* sp = nullptr, const LesionFeatIO* ft = nullptr) {
     DN_TRY(region_state(M));
     RegionState& R = *M->region;
-    if (match) {
+    if (ft) {
+        R.feat_rf = a.rf;
+        R.feat_k = a.k;
+        R.feat_mask = want_mask;
+        R.feat_bins = ft->bins;
+        R.feat_ring = ft->ring;
+    } else if (match) {
         R.match_rf = a.rf;
         R.match_k = a.k;
         R.match_mask = want_mask;
@@ -1596,8 +1887,10 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
     const size_t hw = (size_t)oh * ow, cap = (size_t)a.cap, slots = hw + 1;
     const size_t per_slice = link ? (size_t)a.links_per_slice() : 0;
     const int sets = match ? 3 : 1;
-    const int chunk = (int)region_chunk(match ? 3 : 1, hw, batch);
-    if (!M->dry) DN_TRY(region_ws_reserve(R, lesion_layout(nullptr, chunk, hw, cap, per_slice, match != nullptr, sp != nullptr).bytes));
+    int chunk = (int)region_chunk(match ? 3 : 1, hw, batch);
+    if (ft) chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk, kFeatBudget / ft->slice_bytes(cap)));
+    if (!M->dry)
+        DN_TRY(region_ws_reserve(R, lesion_layout(nullptr, chunk, hw, cap, per_slice, match != nullptr, sp != nullptr, ft).bytes));
     if (link && !match && !M->dry) {     // from here on the carry is this call's: valid again once every chunk has gone through
         R.carry_valid = false;
         if (hw > R.carry_n) {            // (a set continues[0] was checked against a carry of this size: that one is never regrown)
@@ -1628,7 +1921,7 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
         const size_t n = (size_t)nb * hw;
-        const LesionWs ws = lesion_layout(R.ws, nb, hw, cap, per_slice, match != nullptr, sp != nullptr);
+        const LesionWs ws = lesion_layout(R.ws, nb, hw, cap, per_slice, match != nullptr, sp != nullptr, ft);
         const float* pb = prob + (size_t)b0 * h * w;
         const float* yb = match ? match->y + (size_t)b0 * h * w : nullptr;
         if (!M->dry) HIP_TRY(hipMemcpyAsync(ws.thr, &a.threshold, 4, hipMemcpyHostToDevice, s));   // `a` outlives the chunk's sync
@@ -1655,6 +1948,26 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
             LAUNCH(M, "lesion_spread", n * 8.0 + (double)nb * h * w * 4, 0,
                    hipLaunchKernelGGL(k_lesion_spread, grid, dim3(RB), 0, s, sp->spread + (size_t)b0 * h * w, rz, ws.lp, ws.row, (int)cap,
                                       ws.sacc, ws.stot));
+        }
+        if (ft) {                        // the input channels under the prediction plane's rows, and around them
+            const size_t rc = (size_t)nb * cap * ft->channels;
+            const float* xb = ft->x + (size_t)b0 * h * w * ft->channels;
+            if (!M->dry) {
+                HIP_TRY(hipMemsetAsync(ws.fshape, 0, (size_t)nb * cap * sizeof(FeatShapeAcc), s));
+                HIP_TRY(hipMemsetAsync(ws.fbody, 0, rc * sizeof(FeatAcc), s));
+                if (ft->ring) HIP_TRY(hipMemsetAsync(ws.fring, 0, rc * sizeof(FeatAcc), s));
+                if (ft->bins) HIP_TRY(hipMemsetAsync(ws.fhist, 0, rc * ft->bins * 4, s));
+            }
+            const dim3 grid((unsigned)((hw + RB * kFeatU - 1) / (RB * kFeatU)), nb);
+            LAUNCH(M, "lesion_features", n * 8.0, 0,
+                   hipLaunchKernelGGL(k_lesion_features, grid, dim3(RB), (size_t)ft->channels * ft->bins * 4, s, xb, rz, ft->channels, ft->bins, ws.lp, ws.row, (int)cap,
+                                      ws.fshape, ws.fbody, ws.fhist));
+            if (ft->ring) {
+                const dim3 tiles((ow + kTile - 1) / kTile, (oh + kTile - 1) / kTile, nb);
+                LAUNCH(M, "lesion_ring", n * 8.0, 0,
+                       hipLaunchKernelGGL(k_lesion_ring, tiles, dim3(RB), 0, s, xb, rz, ft->channels, ft->ring, ws.lp, ws.row, (int)cap,
+                                          ws.fring));
+            }
         }
         if (match) {                     // the label plane: label' > 0.5, no opening, no area filter
             if (!M->dry) HIP_TRY(hipMemcpyAsync(ws.ythr, &kLabelThreshold, 4, hipMemcpyHostToDevice, s));
@@ -1716,6 +2029,7 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
         const int64_t out_before = out;
         DN_TRY(lesion_rows_read(M, ws.acc, tot, b0, cap, acc, rows, out, totals));
         if (sp) DN_TRY(lesion_spread_read(M, ws.sacc, ws.stot, tot, b0, cap, sp->srows + out_before, sp->stotals));
+        if (ft) DN_TRY(lesion_feat_read(M, ws, tot, b0, cap, *ft, out_before));
         if (match) DN_TRY(lesion_rows_read(M, ws.yacc, ytot, b0, cap, acc, match->rows, out_true, match->totals));
         for (int t = 0; t < sets && link; ++t) {
             std::sort(found[t].begin(), found[t].end(), [](const LesionLink& x, const LesionLink& y) {
@@ -1756,6 +2070,40 @@ int lesion_table_spread(Model* M, const float* prob, const float* spread, int ba
                         dnnca_lesion_spread* srows, dnnca_slice_spread* stotals) {
     const LesionSpreadIO io{spread, srows, stotals};
     return lesion_run(M, prob, batch, h, w, a, rows, n_rows, totals, mask, want_mask, nullptr, nullptr, &io);
+}
+
+int lesion_features_check(const LesionArgs& a, int channels, int bins, int ring) {
+    if (channels < 1 || channels > kFeatMaxC) { set_error("lesion features: %d channels outside 1..%d", channels, kFeatMaxC); return DNNCA_EINVAL; }
+    if (bins < 0 || bins > kFeatMaxBins) { set_error("lesion features: %d bins outside 0..%d", bins, kFeatMaxBins); return DNNCA_EINVAL; }
+    if (ring < 0 || ring > kRingMaxR) { set_error("lesion features: ring %d outside 0..%d", ring, kRingMaxR); return DNNCA_EINVAL; }
+    if (a.oh > 65535 || a.ow > 65535) {
+        set_error("lesion features: an analysed plane of %d x %d (a side above 65535: the moment sums would not fit 64 bits)", a.oh, a.ow);
+        return DNNCA_EINVAL;
+    }
+    const LesionFeatIO io{nullptr, channels, bins, ring, nullptr, nullptr, nullptr, nullptr};
+    if (io.slice_bytes((size_t)a.cap) > kFeatBudget) {
+        set_error("lesion features: %d rows x %d channels x %d bins per slice need more than %zu bytes of records (lower max_lesions)",
+                  a.cap, channels, bins, kFeatBudget);
+        return DNNCA_EINVAL;
+    }
+    return DNNCA_OK;
+}
+
+int lesion_table_features(Model* M, const float* prob, const float* x, int channels, int batch, int h, int w, const LesionArgs& a,
+                          dnnca_lesion_row* rows, int64_t* n_rows, int32_t* totals, uint8_t* mask, bool want_mask, int bins, int ring,
+                          dnnca_lesion_shape* shape, dnnca_lesion_intensity* body, dnnca_lesion_intensity* ring_out, uint32_t* hist) {
+    const LesionFeatIO io{x, channels, bins, ring, shape, body, ring_out, hist};
+    return lesion_run(M, prob, batch, h, w, a, rows, n_rows, totals, mask, want_mask, nullptr, nullptr, nullptr, &io);
+}
+
+void lesion_features_last(Model* M, float* rf, int* k, bool* want_mask, int* bins, int* ring) {
+    RegionState def;
+    const RegionState& R = M->region ? *M->region : def;
+    *rf = R.feat_rf;
+    *k = R.feat_k;
+    *want_mask = R.feat_mask;
+    *bins = R.feat_bins;
+    *ring = R.feat_ring;
 }
 
 int spread_by_outcome(Model* M, const float* prob, const float* spread, const float* y, int batch, size_t hw, const float* thresholds,

@@ -2248,7 +2248,7 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
     if (!buf || !cap) return DNNCA_EINVAL;
     if (pass != DNNCA_PLAN_TRAIN && pass != DNNCA_PLAN_EVAL && pass != DNNCA_PLAN_FORWARD && pass != DNNCA_PLAN_SENSITIVITY &&
         pass != DNNCA_PLAN_LESION && pass != DNNCA_PLAN_LESION_LINKED && pass != DNNCA_PLAN_LESION_MATCHED &&
-        pass != DNNCA_PLAN_SURFACE && pass != DNNCA_PLAN_ATTRIBUTION) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
+        pass != DNNCA_PLAN_SURFACE && pass != DNNCA_PLAN_ATTRIBUTION && pass != DNNCA_PLAN_LESION_FEATURES) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
     DN_TRY(check_batch(M, batch));
     M->plan_text.clear();
     M->dry = true;
@@ -2281,6 +2281,16 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
         rc = lesion_check(a, M->outH, M->outW);
         if (rc == DNNCA_OK)
             rc = lesion_table_matched(M, M->prob, M->y_stage, B, M->outH, M->outW, a, nullptr, nullptr, nullptr, want_mask, nullptr, nullptr);
+    } else if (pass == DNNCA_PLAN_LESION_FEATURES) {
+        LesionArgs a;
+        bool want_mask = true;
+        int bins = 32, ring = 3;
+        lesion_features_last(M, &a.rf, &a.k, &want_mask, &bins, &ring);
+        rc = lesion_check(a, M->outH, M->outW);
+        if (rc == DNNCA_OK) rc = lesion_features_check(a, M->desc.in_channels, bins, ring);
+        if (rc == DNNCA_OK)
+            rc = lesion_table_features(M, M->prob, M->x_stage, M->desc.in_channels, B, M->outH, M->outW, a, nullptr, nullptr, nullptr,
+                                       nullptr, want_mask, bins, ring, nullptr, nullptr, nullptr, nullptr);
     } else if (pass == DNNCA_PLAN_SURFACE) {
         LesionArgs a;
         surface_last(M, &a.rf, &a.k);

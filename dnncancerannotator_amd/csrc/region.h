@@ -66,6 +66,18 @@ int lesion_table(Model* M, const float* prob, int batch, int h, int w, const Les
 int lesion_table_spread(Model* M, const float* prob, const float* spread, int batch, int h, int w, const LesionArgs& a,
                         dnnca_lesion_row* rows, int64_t* n_rows, int32_t* totals, uint8_t* mask, bool want_mask,
                         dnnca_lesion_spread* srows, dnnca_slice_spread* stotals);
+// lesion_table plus what every numbered lesion looks like in the input channels (dnnca_lesion_table_features): the same chunk loop
+// with the same launches and, per chunk, lesion_features and (ring > 0) lesion_ring on x (device [batch, h, w, channels], read
+// through the resize of the probabilities).  shape (host, as many records as rows), body / ring_out (channels records per row) and
+// hist (channels * bins counts per row) receive the records beside `rows`; ring_out is not touched with ring == 0, hist not with
+// bins == 0.  The caller has checked lesion_features_check.  In a dry run none of the host pointers is read
+int lesion_features_check(const LesionArgs& a, int channels, int bins, int ring);
+int lesion_table_features(Model* M, const float* prob, const float* x, int channels, int batch, int h, int w, const LesionArgs& a,
+                          dnnca_lesion_row* rows, int64_t* n_rows, int32_t* totals, uint8_t* mask, bool want_mask, int bins, int ring,
+                          dnnca_lesion_shape* shape, dnnca_lesion_intensity* body, dnnca_lesion_intensity* ring_out, uint32_t* hist);
+// resize factor, filter size, mask choice, bins and ring of the last lesion_table_features (DNNCA_PLAN_LESION_FEATURES); the defaults
+// before any
+void lesion_features_last(Model* M, float* rf, int* k, bool* want_mask, int* bins, int* ring);
 // pixels and q24 spread sums per outcome class (dnnca_spread_by_outcome) of the device planes prob / spread / y [batch, hw] at
 // n_thresholds host thresholds: one spread_outcome launch; out (host) [n_thresholds][batch].  Synchronises
 int spread_by_outcome(Model* M, const float* prob, const float* spread, const float* y, int batch, size_t hw, const float* thresholds,

@@ -661,6 +661,26 @@ class DeviceModel:
         return self._lesion_call(batch, prob, None, threshold, resize_factor, filter_size, min_area, max_lesions, mask, spread=spread,
                                  with_spread=True)
 
+    def lesion_table_features(self, batch=None, prob=None, x=None, threshold=0.5, resize_factor=1.0, filter_size=5, min_area=0,
+                              max_lesions=256, mask=True, bins=32, ring=3):
+        """lesion_table plus what every lesion looks like in the input channels: (rows, totals, masks, shape, body, ring, hist); the
+        first three are what lesion_table returns.  The channels are the staged batch of the last forward (batch=...; under
+        forward_tta the untransformed batch), or `x` [B, h, w, C] beside `prob` (both host planes, or neither).  A value is x read
+        through the resize of the probabilities, clamped to [0, 1] (NaN: 0), and enters the sums as q = rint(v * 2^16).
+        shape (_lib.LESION_SHAPE_DTYPE: slice, row, area, boundary, edges, sum_xx, sum_yy, sum_xy) [n]; body and ring
+        (_lib.LESION_INTENSITY_DTYPE: slice, row, channel, n, min, max, sum_q16, sum_sq_q16) [n, C]: the lesion's own pixels, and
+        the background pixels within `ring` pixels (a square window) that are nearer to no lesion of a lower row -- ring=0: None;
+        hist uint32 [n, C, bins]: the body's values by bin min(bins - 1, floor(v * bins)) -- bins=0: None.  casewise.feature_* turn
+        the integers into means, deviations, percentiles and axes.  Exact integers and extrema: bit-identical from run to run."""
+        if (prob is None) != (x is None):
+            raise ValueError('lesion_table_features: prob and x go together (both host planes, or neither)')
+        if x is not None:
+            x, prob = as_f32(x), _slices(prob, 'prob')
+            if x.ndim != 4 or x.shape[:3] != prob.shape:
+                raise ValueError('x %s must be [B, h, w, C] beside prob %s' % (x.shape, prob.shape))
+        return self._lesion_call(batch, prob, None, threshold, resize_factor, filter_size, min_area, max_lesions, mask,
+                                 features=(x, int(bins), int(ring)))
+
     def spread_by_outcome(self, y, thresholds=(0.5,), batch=None, prob=None, spread=None):
         """pixels and spread per pixel outcome (dnnca_spread_by_outcome): structured array (_lib.SPREAD_OUTCOME_DTYPE: n [4],
         sum_q24 [4]) [T, B] over the classes TN, FP, FN, TP = 2 (y > 0.5) + (prob >= threshold).  y [B, h, w]; the probabilities
@@ -734,9 +754,9 @@ class DeviceModel:
         return self._lesion_call(batch, prob, continues, threshold, resize_factor, filter_size, min_area, max_lesions, mask)
 
     def _lesion_call(self, batch, prob, continues, threshold, resize_factor, filter_size, min_area, max_lesions, mask, spread=None,
-                     with_spread=False):
-        """dnnca_lesion_table, with `continues` dnnca_lesion_table_linked, with_spread dnnca_lesion_table_spread: the size query, then
-        the call on buffers of that size"""
+                     with_spread=False, features=None):
+        """dnnca_lesion_table, with `continues` dnnca_lesion_table_linked, with_spread dnnca_lesion_table_spread, with features (x or
+        None, bins, ring) dnnca_lesion_table_features: the size query, then the call on buffers of that size"""
         pp, h, w = None, 0, 0
         if prob is not None:
             prob = _slices(prob, 'prob')
@@ -753,6 +773,20 @@ class DeviceModel:
         n = C.c_int64()
         out = (rows.ctypes.data_as(C.POINTER(_lib.LesionRow)), len(rows), C.byref(n), totals.ctypes.data_as(C.POINTER(C.c_int32)),
                masks.ctypes.data_as(C.c_void_p) if mask else None, masks.nbytes if mask else 0, hw)
+        if features is not None:
+            x, bins, ring = features
+            ch = self.in_shape[2] if x is None else x.shape[3]
+            shape = np.zeros(len(rows), _lib.LESION_SHAPE_DTYPE)
+            body = np.zeros((len(rows), ch), _lib.LESION_INTENSITY_DTYPE)
+            rng = np.zeros((len(rows), ch), _lib.LESION_INTENSITY_DTYPE) if ring > 0 else None
+            hist = np.zeros((len(rows), ch, bins), np.uint32) if bins > 0 else None
+            rec = C.POINTER(_lib.LesionIntensity)
+            check(self.lib.dnnca_lesion_table_features(*args, *out, None if x is None else fptr(x), int(ch), bins, ring,
+                                                       shape.ctypes.data_as(C.POINTER(_lib.LesionShape)), body.ctypes.data_as(rec),
+                                                       None if rng is None else rng.ctypes.data_as(rec),
+                                                       None if hist is None else hist.ctypes.data_as(C.POINTER(C.c_uint32))))
+            cut = lambda a: None if a is None else a[:n.value].copy()
+            return rows[:n.value].copy(), totals, masks, cut(shape), cut(body), cut(rng), cut(hist)
         if with_spread:
             srows = np.zeros(len(rows), _lib.LESION_SPREAD_DTYPE)
             stotals = np.zeros(B, _lib.SLICE_SPREAD_DTYPE)
@@ -1000,7 +1034,7 @@ class DeviceModel:
         return out
 
     PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3, 'lesion': 4, 'lesion_linked': 5, 'lesion_matched': 6,
-                   'surface': 7, 'attribution': 8}
+                   'surface': 7, 'attribution': 8, 'lesion_features': 9}
 
     def plan(self, variants=False, mode='train', batch=None):
         """The launch schedule of one pass: [(kernel, algorithmic bytes, flops)].  mode 'train': one train step; 'eval': one
@@ -1009,7 +1043,9 @@ class DeviceModel:
         filter size and mask choice of the last lesion_table / lesion_table_linked call; 'lesion_linked': lesion_table_linked likewise;
         'lesion_matched': lesion_table_matched with the three values of the last lesion_table_matched call; 'surface':
         surface_distances with the resize factor and filter size of the last surface_distances call; 'attribution':
-        integrated_gradients with the steps and baseline of the last integrated_gradients call (before any: 32, 'black') and the map.
+        integrated_gradients with the steps and baseline of the last integrated_gradients call (before any: 32, 'black') and the map;
+        'lesion_features': lesion_table_features on the staged batch with the resize factor, filter size, mask choice, bins and ring
+        of the last lesion_table_features call (before any: 1.0, 5, with mask, 32, 3).
         batch: None = max_batch.  variants: keep the template variant the library appends to a launch name
         (`ig_conv_fwd#3n2w8`): the kernel-coverage test tells them apart.  A dry run: the model is unchanged."""
         if mode not in self.PLAN_PASSES:

@@ -996,7 +996,7 @@ class TFKerasModel:
 
     def annotate(self, dataset, save_path, output, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
                  max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
-                 temperature=None):
+                 temperature=None, lesion_features=False, feature_bins=None, feature_ring=None):
         """`annotator predict`: the lesions of slices that have no label.  Loads checkpoint `step` of save_path (None: the latest);
         per batch (x, paths, sliceIDs) of `dataset` (make_dataset(..., include_meta=True, labels=False)) one forward whose
         probabilities stay on the device, then DeviceModel.lesion_table: threshold, filter_size x filter_size opening, components
@@ -1018,9 +1018,17 @@ class TFKerasModel:
         are written beside the other files, which are what they are without the flag, and with export_images
         <exam>/<slice>/uncertainty.png (only then does a spread plane leave the device).  Needs a tta mode other than 'none'.
         temperature (`predict --temperature T`): the probabilities are scaled by DeviceModel.scale_temperature, once behind every
-        forward, before the table reads them; the spread stays that of the unscaled views.  None or 1: nothing new runs."""
+        forward, before the table reads them; the spread stays that of the unscaled views.  None or 1: nothing new runs.
+        lesion_features (`predict --lesion_features [--feature_bins 32] [--feature_ring 3]`): the table comes from
+        DeviceModel.lesion_table_features, which also reads the staged input batch -- the untransformed one under tta -- below and
+        around every lesion (with link_slices or uncertainty the table runs as it does without the flag and the feature records
+        come from a second call); lesion_features.csv (one line per line of lesions.csv, in its order: outline, axes and per
+        modality mean, deviation, extrema, percentiles and the contrast against the ring of feature_ring pixels around the
+        lesion) and with link_slices exam_lesion_features.csv (one line per line of exam_lesions.csv, pooled from the parts'
+        integers) are written beside the other files, which are what they are without the flag."""
         check_uncertainty(uncertainty, tta)
         temperature = check_temperature(temperature)
+        feature_bins, feature_ring = casewise.check_features(lesion_features, feature_bins, feature_ring)
         if self.ctx.world > 1:
             raise RuntimeError('annotate runs in a single process (WORLD_SIZE is %d): start it without the launcher' % self.ctx.world)
         tta_mask = None if tta == tta_modes.NONE else tta_modes.mask_of(tta, *_element_shape(dataset)[1:3])
@@ -1035,6 +1043,8 @@ class TFKerasModel:
         self.load(ckpts[step])
         lesion_rows, slice_rows = [], []
         lesion_spread_rows, slice_spread_rows = [], []
+        feature_rows, linked_features = [], []       # linked_features: beside `linked`, every slice's feature records per lesion
+        modalities = casewise.modality_names(getattr(dataset, 'slice_types', None), _element_shape(dataset)[3]) if lesion_features else None
         scale = {} if temperature is None else dict(temperature=temperature)      # the forward gets the keyword only with a temperature
         dm = None
         linked, last = [], None          # link_slices: (exam, slice, rows, total, links into it) per slice; the slice before: (exam, slice)
@@ -1066,8 +1076,15 @@ class TFKerasModel:
                             _, _, _, srows, stotals = dm.lesion_table_spread(**dict(kw, mask=False))
                     elif uncertainty:
                         rows, totals, masks, srows, stotals = dm.lesion_table_spread(**kw)
+                    elif lesion_features:
+                        rows, totals, masks, *feats = dm.lesion_table_features(bins=feature_bins, ring=feature_ring, **kw)
                     else:
                         rows, totals, masks = dm.lesion_table(**kw)
+                    if lesion_features:
+                        if link_slices or uncertainty:   # the feature records of the same rows, from a call of their own
+                            feats = dm.lesion_table_features(bins=feature_bins, ring=feature_ring, **dict(kw, mask=False))[3:]
+                        if len(feats[0]) != len(rows):
+                            raise RuntimeError('predict: %d feature records beside %d lesions' % (len(feats[0]), len(rows)))
                     if uncertainty:
                         if len(srows) != len(rows):
                             raise RuntimeError('predict: %d spread records beside %d lesions' % (len(srows), len(rows)))
@@ -1081,6 +1098,12 @@ class TFKerasModel:
                         slice_rows.append(casewise.slice_values(p, k, mine, totals[b]))
                         if export_images:
                             writer.submit(casewise.mask_path(output, casewise.tag_of(p, k)), casewise.encode_png, masks[b])
+                        if lesion_features:
+                            fmine = [None if f is None else f[rows['slice'] == b] for f in feats]
+                            per_lesion = [tuple(None if f is None else f[j] for f in fmine) for j in range(len(mine))]
+                            feature_rows += [casewise.lesion_feature_values(p, k, r, *f) for r, f in zip(mine, per_lesion)]
+                            if link_slices:
+                                linked_features.append(per_lesion)
                         if uncertainty:
                             smine = srows[rows['slice'] == b]
                             lesion_spread_rows += [casewise.lesion_uncertainty_values(p, k, r, q) for r, q in zip(mine, smine)]
@@ -1097,6 +1120,9 @@ class TFKerasModel:
         if uncertainty:
             tables += [('lesion_uncertainty.csv', casewise.LESION_UNCERTAINTY_COLUMNS, lesion_spread_rows),
                        ('slice_uncertainty.csv', casewise.SLICE_UNCERTAINTY_COLUMNS, slice_spread_rows)]
+        if lesion_features:
+            tables.append(('lesion_features.csv', casewise.lesion_feature_columns(modalities), feature_rows))
+        exam_feature_rows = []
         if link_slices:
             exams = {}                   # exam path -> the positions of its slices in `linked`, in the order of the data set
             for pos, rec in enumerate(linked):
@@ -1106,12 +1132,19 @@ class TFKerasModel:
                 table, parts = casewise.link_lesions(exam, [linked[pos][1:4] for pos in where], [linked[pos][4] for pos in where],
                                                      min_overlap=link_min_overlap)
                 exam_rows += table
+                if lesion_features:      # the parts are in the order of the exam's lesions: gather every exam lesion's
+                    of = [f for pos in where for f in linked_features[pos]]
+                    for e in range(len(table)):
+                        exam_feature_rows.append(casewise.exam_lesion_feature_values(
+                            exam, e, [f for f, part in zip(of, parts) if part[3] == e]))
                 for pos in where:        # the parts come slice after slice; lesions.csv is in the order of the data set
                     n = len(linked[pos][2])
                     parts_of[pos], parts = parts[:n], parts[n:]
             tables += [('exam_lesions.csv', casewise.EXAM_LESION_COLUMNS, exam_rows),
                        ('exam_lesion_parts.csv', casewise.EXAM_PART_COLUMNS, sum(parts_of, []))]
             res['exam_lesions'] = len(exam_rows)
+            if lesion_features:
+                tables.append(('exam_lesion_features.csv', casewise.exam_lesion_feature_columns(modalities), exam_feature_rows))
         for name, cols, table in tables:
             with open(os.path.join(output, name), 'w', newline='') as f:
                 f.write(casewise.plain_csv(cols, table))

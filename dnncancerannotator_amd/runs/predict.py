@@ -2,18 +2,20 @@
 checkpoint (lesions.csv, slices.csv and, with --export_images, one mask.png per slice; with --link_slices also exam_lesions.csv and
 exam_lesion_parts.csv: the lesions joined through the slices of an exam; with --tta MODE --uncertainty also lesion_uncertainty.csv,
 slice_uncertainty.csv and uncertainty.png: how much the views disagree; with --temperature T every table reads the probabilities
-scaled by T; engine.TFKerasModel.annotate)."""
+scaled by T; with --lesion_features also lesion_features.csv and, with --link_slices, exam_lesion_features.csv: outline, axes and
+per modality the intensities in and around every lesion; engine.TFKerasModel.annotate)."""
 
 import os
 
-from .. import engine, load
+from .. import casewise, engine, load
 from .train import make_dataset
 
 
 def predict(save_path, data_path, output, config=None, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
             max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
-            temperature=None):
+            temperature=None, lesion_features=False, feature_bins=None, feature_ring=None):
     engine.check_uncertainty(uncertainty, tta)       # before anything is read
+    casewise.check_features(lesion_features, feature_bins, feature_ring)      # likewise
     scaled = engine.check_temperature(temperature)   # likewise; None without the flag and with --temperature 1
     if link_min_overlap < 1:
         raise ValueError('link_min_overlap must be at least 1, got %d' % link_min_overlap)
@@ -27,6 +29,8 @@ def predict(save_path, data_path, output, config=None, step=None, threshold=0.5,
         more['uncertainty'] = True
     if scaled is not None:               # and the keyword of --temperature only with a temperature other than 1
         more['temperature'] = scaled
+    if lesion_features:                  # and the keywords of --lesion_features only with the flag
+        more.update(lesion_features=True, feature_bins=feature_bins, feature_ring=feature_ring)
     model = engine.TFKerasModel(config)
     return model.annotate(ds, save_path=save_path, output=output, step=step, threshold=threshold, min_area=min_area,
                           filter_size=filter_size, resize_factor=resize_factor, max_lesions=max_lesions,

@@ -440,6 +440,51 @@ int dnnca_lesion_table_spread(void* model, const float* prob_hw, int batch, int 
                               int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw,
                               const float* spread_hw, dnnca_lesion_spread* srows, dnnca_slice_spread* stotals);
 
+/* ---- the same table plus what each lesion looks like in the input channels (`annotator predict --lesion_features`) -----------------
+ * Every argument up to out_hw means what it means for dnnca_lesion_table (the size query with rows == NULL included), and rows,
+ * totals, mask and out_hw are bit-identical to that call's.  Every lesion that has a row gets a shape record, and per channel a
+ * body record, a ring record (ring > 0) and a histogram (bins > 0).
+ * The value of a pixel in channel c is x', the channel read through the bilinear resize the probabilities went through
+ * (resize_factor 1: the pixel itself), as v = min(max(x', 0), 1) with NaN = 0.  It enters every sum as q = rint(v * 2^16) in
+ * float32: q16, not the q24 of the probabilities, so that q^2 fits 33 bits and a sum of q^2 over the up to 2^31 pixels of a plane
+ * fits one uint64.  Extrema go through the float's bits.  All sums are integers: everything is bit-identical from run to run.
+ *   shape[i]        belongs to rows[i]: slice, row, area (rows[i].area); boundary: its pixels with at least one of the four
+ *                   neighbours outside the lesion or outside the plane (the BOUNDARY rule of dnnca_surface_distances); edges: the
+ *                   (pixel, direction) pairs that face out, i.e. the crack length of its outline, the plane's border included;
+ *                   sum_xx, sum_yy, sum_xy: sums of the coordinate products (sum_x, sum_y are in the row)
+ *   body[i * channels + c]       slice, row, channel, n (the area), min and max of v, sum_q16 = sum q, sum_sq_q16 = sum q^2
+ *   ring_out[i * channels + c]   the same over the lesion's ring.  A background pixel -- one in no kept component: what the opening
+ *                   removed and components below min_area are background, kept components beyond max_lesions are not and own no
+ *                   ring -- belongs to the ring of the smallest row number among the numbered lesions at (y + dy, x + dx), |dy| <=
+ *                   ring, |dx| <= ring, inside the plane; to none if there is none.  n == 0: min = max = 0
+ *   hist[(i * channels + c) * bins + k]   the body pixels with min(bins - 1, (int) floor(v * (float) bins)) == k, the product in
+ *                   float32 (the bin rule of dnnca_calibration).  The ring has no histogram
+ * shape holds rows_capacity records, body and ring_out rows_capacity * channels, hist rows_capacity * channels * bins counts.
+ * ring == 0: nothing of the ring launch runs, ring_out is not touched and may be NULL; bins == 0: the same for hist.
+ * x_hwc == NULL: the staged batch of the last forward (under dnnca_forward_tta* the untransformed batch) with the model's input
+ * channels (`channels` is then 0 or that number); prob_hw must be NULL too; DNNCA_ESTATE when the last forward staged fewer than
+ * `batch` slices or the model's output size is not its input size.  Otherwise x_hwc is a host plane [batch, h, w, channels],
+ * channels in 1..16, beside a host prob_hw.
+ * DNNCA_EINVAL, with nothing launched and no output touched: everything dnnca_lesion_table refuses, one of prob_hw / x_hwc given
+ * without the other, channels outside 1..16, bins outside 0..256, ring outside 0..8, shape or body NULL beside rows, ring_out NULL
+ * with ring > 0, hist NULL with bins > 0, an analysed plane with a side above 65535 (the moment sums must fit 64 bits), records of
+ * one slice (min(max_lesions, (oh * ow + 1) / 2) rows) above 2^30 bytes.  Variables, state, the probabilities of the last forward
+ * and the carry planes of the linked and matched calls are untouched.  Synchronises. */
+typedef struct dnnca_lesion_shape {
+    int32_t slice, row, area, boundary, edges, reserved;
+    uint64_t sum_xx, sum_yy, sum_xy;
+} dnnca_lesion_shape;                               /* 48 bytes, no padding */
+typedef struct dnnca_lesion_intensity {
+    int32_t slice, row, channel, n;
+    float min, max;
+    uint64_t sum_q16, sum_sq_q16;
+} dnnca_lesion_intensity;                           /* 40 bytes, no padding */
+int dnnca_lesion_table_features(void* model, const float* prob_hw, int batch, int h, int w, float threshold, float resize_factor,
+                                int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
+                                int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw,
+                                const float* x_hwc, int channels, int bins, int ring, dnnca_lesion_shape* shape,
+                                dnnca_lesion_intensity* body, dnnca_lesion_intensity* ring_out, uint32_t* hist);
+
 /* ---- is the spread larger where the model is wrong? (`annotator evaluate --tta MODE --uncertainty`) ---------------------------------
  * Per threshold t and slice b every pixel falls into the class 2 (y > 0.5) + (prob >= thresholds[t]): TN 0, FP 1, FN 2, TP 3 (the
  * label rule of dnnca_lesion_table_matched); out[t * batch + b] receives the pixels n[c] and the sums sum_q24[c] of
@@ -644,10 +689,13 @@ int dnnca_plan_dump(void* model, char* buf, size_t cap);
    with mask), or dnnca_lesion_table_linked with the same three values, or dnnca_lesion_table_matched with the three values of the
    last dnnca_lesion_table_matched call (before any: the same defaults), or dnnca_surface_distances with the resize factor and
    filter size of the last dnnca_surface_distances call (before any: 1.0, 5), or dnnca_integrated_gradients with the steps and
-   baseline of the last dnnca_integrated_gradients call (before any: 32, black) and the map requested.  A dry run: nothing is launched and the model is left
+   baseline of the last dnnca_integrated_gradients call (before any: 32, black) and the map requested, or
+   dnnca_lesion_table_features on the staged batch with the resize factor, filter size, mask choice, bins and ring of the last
+   dnnca_lesion_table_features call (before any: 1.0, 5, with mask, 32, 3).  A dry run: nothing is launched and the model is left
    as it was. */
 enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2, DNNCA_PLAN_SENSITIVITY = 3, DNNCA_PLAN_LESION = 4,
-       DNNCA_PLAN_LESION_LINKED = 5, DNNCA_PLAN_LESION_MATCHED = 6, DNNCA_PLAN_SURFACE = 7, DNNCA_PLAN_ATTRIBUTION = 8 };
+       DNNCA_PLAN_LESION_LINKED = 5, DNNCA_PLAN_LESION_MATCHED = 6, DNNCA_PLAN_SURFACE = 7, DNNCA_PLAN_ATTRIBUTION = 8,
+       DNNCA_PLAN_LESION_FEATURES = 9 };
 int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap);
 
 #ifdef __cplusplus

@@ -17,6 +17,8 @@ and prediction plane) plus pairs, match and count.
     python tools/lesion_rate.py --tta flips --uncertainty        # also: the spread of the views against the mean alone
     python tools/lesion_rate.py --calibration       # calibration and temperature scaling alone
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --tta flips      # forward / forward_tta on it
+    python tools/lesion_rate.py --features          # per-lesion features alone: the two launches, the call against its siblings
+    DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --table_only     # plain lesion_table on it
 
 --link adds the cost of linking neighbouring slices: lesion_table_linked against lesion_table (wall time per call, device time of
 the three link launches), its worst case for the pair table (a checkerboard on itself: every other pixel a lesion of its own in
@@ -44,6 +46,13 @@ wave's lanes by key is for), of calib_nll / calib_nll_sum at the 41 temperatures
 wall time per call; and a forward_tta_spread + calibration pass against a forward_tta_spread + spread_by_outcome pass (the pass of
 `evaluate --uncertainty`: the same forward, one table call), alternated in one process.
 
+--features measures DeviceModel.lesion_table_features on a model of 3 input channels and nothing else: lesion_features and
+lesion_ring per launch (event-bracketed) and the call's wall time against lesion_table and lesion_table_spread, alternated, on the
+mean that forward_tta_spread left on the device at the two thresholds of --uncertainty (next to no lesion; thousands of specks), on
+the drawn discs, and on the worst case (every slice one lesion: every pixel adds to one record and to its histogram).
+--table_only measures plain lesion_table on the drawn discs and nothing else: run it on this build and on a library built from the
+parent commit, in turns.
+
 The probabilities are drawn: the synthetic labels' discs at 0.55 .. 0.95 on a background of 0 .. 0.45 (a few lesions per slice,
 as a trained model gives), put into the model's probability buffer by pixel_confusion_of."""
 import argparse
@@ -68,8 +77,14 @@ ap.add_argument('--surface', action='store_true', help='also measure surface_dis
 ap.add_argument('--tta', default=None, metavar='MODE', help='measure forward_tta(MODE) against the plain forward, and nothing else')
 ap.add_argument('--uncertainty', action='store_true', help='with --tta: also measure forward_tta_spread, lesion_table_spread, spread_by_outcome')
 ap.add_argument('--calibration', action='store_true', help='measure calibration and scale_temperature, and nothing else')
+ap.add_argument('--features', action='store_true', help='measure lesion_table_features against lesion_table / lesion_table_spread, and nothing else')
+ap.add_argument('--table_only', action='store_true', help='measure plain lesion_table, and nothing else (also on a library built from the parent)')
 ap.add_argument('--out', default=None, help='append the report to this file as well')
 a = ap.parse_args()
+if a.features:                                                   # its siblings are lesion_table and lesion_table_spread
+    a.tta, a.uncertainty = a.tta or 'flips', True
+else:
+    _lib.SIGNATURES.pop('dnnca_lesion_table_features', None)     # a library built from the parent does not export it
 if a.calibration:                                                # its yardstick is the pass of --tta flips --uncertainty
     a.tta, a.uncertainty = a.tta or 'flips', True
 else:
@@ -142,7 +157,7 @@ def per_launch(dm, fn, prefixes):
 
 
 dev.init_device(0)
-x, y = synthetic_batch(B, S, S, 1, seed_x=3, seed_y=4)
+x, y = synthetic_batch(B, S, S, 3 if a.features else 1, seed_x=3, seed_y=4)
 yy, xx = np.mgrid[0:S, 0:S]
 prob = np.where(y > 0.5, 0.55 + ((xx * 5 + yy * 3) % 27) / 64.0, ((xx * 7 + yy * 11) % 30) / 64.0).astype(np.float32)
 DEPLOY = dict(optimizer='adam', enable_multigpu=False)
@@ -152,8 +167,58 @@ ds = ArrayDataset(np.concatenate([x] * NB), None, B, meta_path='/synthetic/p0/e0
     ArrayDataset(x, y, B)
 e._build(ds)
 dm = e.device_model
-say('%s: %d x %d x %d, library %s' % ('yardstick' if a.yardstick else 'calibration' if a.calibration else
-                                      'test-time augmentation' if a.tta else 'lesion table', B, S, S, os.path.basename(_lib.LIB_PATH)))
+say('%s: %d x %d x %d, library %s' % ('yardstick' if a.yardstick else 'lesion features' if a.features else 'plain lesion table' if a.table_only else
+                                      'calibration' if a.calibration else 'test-time augmentation' if a.tta else 'lesion table', B, S, S, os.path.basename(_lib.LIB_PATH)))
+if a.table_only:
+    dm.pixel_confusion_of(prob, y, [0.5])
+    for mask in (True, False) * 2:
+        med, lo, hi = wall(lambda: dm.lesion_table(batch=B, threshold=0.5, filter_size=5, mask=mask))
+        say('  lesion_table(mask=%s): %.3f ms per call (median of %d; %.3f .. %.3f)' % (mask, med, R, lo, hi))
+    dm.close()
+    if a.out:
+        with open(a.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    sys.exit(0)
+if a.features:
+    from dnncancerannotator_amd import tta as tta_modes
+    views = tta_modes.mask_of(a.tta, S, S)
+
+    def legs(what, kw, spread, **fkw):
+        """lesion_table, lesion_table_spread (where the spread plane is valid) and lesion_table_features on the same plane, alternated"""
+        say('  %s' % what)
+        calls = [('lesion_table', lambda: dm.lesion_table(**kw))]
+        if spread:
+            calls.append(('lesion_table_spread', lambda: dm.lesion_table_spread(**kw)))
+        calls.append(('lesion_table_features', lambda: dm.lesion_table_features(**kw, **fkw)))
+        took = {}
+        for name, fn in calls * 2:
+            took.setdefault(name, []).append(wall(fn))
+        for name, runs in took.items():
+            for med, lo, hi in runs:
+                say('  %-28s %.3f ms per call (median of %d; %.3f .. %.3f)' % (name, med, R, lo, hi))
+        best = {name: min(r[0] for r in runs) for name, runs in took.items()}
+        rows = dm.lesion_table_features(**kw, **fkw)[0]
+        say('  lesion_table_features / lesion_table, wall (best medians): %.3f; %d lesions, largest %d pixels' % (
+            best['lesion_table_features'] / best['lesion_table'], len(rows), int(rows['area'].max()) if len(rows) else 0))
+        per_launch(dm, lambda: dm.lesion_table_features(**kw, **fkw), ('lesion_features', 'lesion_ring', 'lesion_stats', 'lesion_spread'))
+    dm.forward_tta_spread(x, views, return_prob=False, return_spread=False)
+    last = dm.last_prob(B)
+    for thr, k in ((float(np.median(last)), 5), (float(np.percentile(last, 99.0)), 1)):
+        kw = dict(batch=B, threshold=thr, filter_size=k, mask=False, max_lesions=4096)
+        legs('threshold %.6f, filter_size %d, 32 bins, ring 3' % (thr, k), kw, True)
+        legs('the same, ring 8', kw, True, ring=8)
+        legs('the same, no histogram, no ring', kw, True, bins=0, ring=0)
+    dm.forward(x, return_prob=False)
+    dm.pixel_confusion_of(prob, y, [0.5])
+    legs('drawn discs, threshold 0.5, filter_size 5, 32 bins, ring 3', dict(batch=B, threshold=0.5, filter_size=5, mask=False), False)
+    dm.pixel_confusion_of(np.ones((B, S, S), np.float32), y, [0.5])
+    legs('every slice one lesion, 32 bins, ring 3', dict(batch=B, threshold=0.5, filter_size=5, mask=False), False)
+    legs('every slice one lesion, no histogram', dict(batch=B, threshold=0.5, filter_size=5, mask=False), False, bins=0)
+    dm.close()
+    if a.out:
+        with open(a.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    sys.exit(0)
 if a.calibration:
     from dnncancerannotator_amd import casewise, tta as tta_modes
     views = tta_modes.mask_of(a.tta, S, S)
