@@ -4,6 +4,9 @@
 #include "abi.h"
 #include "fast.h"
 #include "kernels.h"
+#include <cstring>
+#include <map>
+#include <string>
 #include <vector>
 
 using namespace dnnca;
@@ -165,6 +168,85 @@ int dnnca_debug_join(void* model, int what, int B, int H, int W, int C, int ps, 
     (void)hipFree(ticket);
     (void)hipFree(dcoef);
     return rc;
+}
+
+// test aids (tests/layerwise.py): what a pass left in the plan's own tensors, one launch at a time.  Every tensor of a plan has a data
+// and a gradient buffer of its own for the life of the model, so after forward() / a train step the stored inputs and the stored
+// output of every launch are still there.  These three only synchronise the stream and copy; bf16 storage is widened on the host.
+
+// One text line per Op, `key=value` tokens separated by blanks.  A view is H,W,C,ps,h(data),h(gradient),id: the id is the same for
+// equal data base pointers (1, 2, ... in order of first appearance; 0: no tensor), so the reader learns who reads and writes what
+// without seeing an address.  Returns DNNCA_EINVAL (and the size needed in the message) when `cap` is too small.
+int dnnca_debug_ops(void* model, char* buf, size_t cap) {
+    MODEL(model);
+    static const char* kType[] = {"CONV", "BN", "POOL", "TCONV", "HEAD", "JOIN"};
+    std::map<const float*, int> ids;
+    std::string s;
+    char t[512];
+    auto view = [&](const char* key, const T& v) {
+        int id = 0;
+        if (v.d.C) {
+            const float* base = v.d.p;
+            auto it = ids.find(base);
+            id = it != ids.end() ? it->second : (ids[base] = (int)ids.size() + 1);
+        }
+        snprintf(t, sizeof t, " %s=%d,%d,%d,%d,%d,%d,%d", key, v.d.H, v.d.W, v.d.C, v.d.ps, v.d.h, v.g.h, id);
+        s += t;
+    };
+    for (size_t i = 0; i < M->ops.size(); ++i) {
+        const Op& o = M->ops[i];
+        snprintf(t, sizeof t, "op=%zu type=%s name=%s k=%d alpha=%.9g w_off=%lld b_off=%lld mm_off=%lld mv_off=%lld need_din=%d accA=%d accB=%d "
+                 "maskA=%d maskB=%d premasked=%d mask_alpha=%.9g elided=%d src_bn=%d,%d", i, kType[o.type], o.name.c_str(), o.k, (double)o.alpha,
+                 (long long)o.w_off, (long long)o.b_off, (long long)o.mm_off, (long long)o.mv_off, (int)o.need_din, (int)o.accA, (int)o.accB,
+                 (int)o.maskA, (int)o.maskB, (int)o.premasked, (double)o.mask_alpha, (int)o.elided, o.src_bn[0], o.src_bn[1]);
+        s += t;
+        view("inA", o.inA); view("inB", o.inB); view("out", o.out);
+        s += "\n";
+    }
+    if (!buf || s.size() + 1 > cap) { set_error("dnnca_debug_ops: %zu bytes needed", s.size() + 1); return DNNCA_EINVAL; }
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return DNNCA_OK;
+}
+
+// The view `slot` (0 inA, 1 inB, 2 out) of op `op`, data (grad == 0) or gradient, as dense float32 [batch, H, W, C]: channel slices
+// (ps > C) are gathered, bf16 storage is converted exactly.  n: floats `out` holds.
+int dnnca_debug_tensor(void* model, int op, int slot, int grad, int batch, float* out, size_t n) {
+    MODEL(model);
+    if (op < 0 || op >= (int)M->ops.size() || slot < 0 || slot > 2 || !out) { set_error("dnnca_debug_tensor: no op %d / slot %d", op, slot); return DNNCA_EINVAL; }
+    DN_TRY(check_batch(M, batch));
+    const Op& o = M->ops[op];
+    const T& t = slot == 0 ? o.inA : (slot == 1 ? o.inB : o.out);
+    const View& v = grad ? t.g : t.d;
+    if (!v.C || !v.p) { set_error("dnnca_debug_tensor: %s has no %s buffer in slot %d", o.name.c_str(), grad ? "gradient" : "data", slot); return DNNCA_EINVAL; }
+    const size_t npix = (size_t)batch * v.H * v.W;
+    if (n != npix * v.C) { set_error("dnnca_debug_tensor: %zu floats expected, not %zu", npix * v.C, n); return DNNCA_EINVAL; }
+    const size_t stored = (npix - 1) * v.ps + v.C;          // elements from the view's first to its last
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    if (v.h) {
+        std::vector<uint16_t> h(stored);
+        HIP_TRY(hipMemcpy(h.data(), v.p, stored * 2, hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < npix; ++p)
+            for (int c = 0; c < v.C; ++c) {
+                const uint32_t u = (uint32_t)h[p * v.ps + c] << 16;
+                memcpy(out + p * v.C + c, &u, 4);
+            }
+    } else if (v.ps == v.C) {
+        HIP_TRY(hipMemcpy(out, v.p, stored * 4, hipMemcpyDeviceToHost));
+    } else {
+        std::vector<float> h(stored);
+        HIP_TRY(hipMemcpy(h.data(), v.p, stored * 4, hipMemcpyDeviceToHost));
+        for (size_t p = 0; p < npix; ++p) memcpy(out + p * v.C, h.data() + p * v.ps, (size_t)v.C * 4);
+    }
+    return DNNCA_OK;
+}
+
+// The coefficient table [scale, shift, mean, inv] x C of BatchNorm `op` as the last forward pass left it (out: 4 C floats).
+int dnnca_debug_bn_coef(void* model, int op, float* out) {
+    MODEL(model);
+    if (op < 0 || op >= (int)M->ops.size() || M->ops[op].type != OP_BN || !M->ops[op].coef || !out) { set_error("dnnca_debug_bn_coef: op %d is no BatchNorm", op); return DNNCA_EINVAL; }
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    HIP_TRY(hipMemcpy(out, M->ops[op].coef, (size_t)4 * M->ops[op].inA.d.C * 4, hipMemcpyDeviceToHost));
+    return DNNCA_OK;
 }
 
 }  // extern "C"

@@ -2283,8 +2283,11 @@ __global__ __launch_bounds__(256, 2) void k_igb_tconv_fwd(TcArgs p, const bf16_t
                     } else {
                         op[16 * j] = v;
                     }
-                    bs[j] += v;
-                    bq[j] = fmaf(v, v, bq[j]);
+                    // ... less the bias (BnSelfFold::shift = bias adds it back to the mean; see k_ig_tconv_fwd2): the moments of
+                    // STORED value - bias, not of the accumulator -- z is rounded with its bias in it, and the BatchNorm reads that
+                    const float d = v - bias[j];
+                    bs[j] += d;
+                    bq[j] = fmaf(d, d, bq[j]);
                 }
             }
         }
@@ -2420,9 +2423,13 @@ __global__ __launch_bounds__(512, 2) void k_igb_tconv_fwd2(TcArgs p, const bf16_
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 f32x4 v = acc[e][mt][pt] + bias[mt];
-                hbf16x4 h;          // the statistics are those of the stored values
+                // the statistics are those of the stored values less the bias (BnSelfFold::shift = bias adds it back to the mean, as in
+                // k_ig_tconv_fwd2): z is rounded WITH its bias in it and the BatchNorm reads that, so the moments are taken from
+                // (float)h - bias, one subtraction per value, not from the accumulator.  Raw float32 moments of h lose
+                // (mean / sigma)^2 of their digits, and nothing keeps this bias near 0 (its gradient is zero in front of a BatchNorm)
+                hbf16x4 h;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { h[i] = (hbf16)v[i]; v[i] = mine ? (float)h[i] : 0.f; }
+                for (int i = 0; i < 4; ++i) { h[i] = (hbf16)v[i]; v[i] = mine ? (float)h[i] - bias[mt][i] : 0.f; }
                 *reinterpret_cast<hbf16x4*>(reinterpret_cast<hbf16*>(wt) + m16 * ORS + e * 64 + 16 * mt + 4 * q) = h;
                 bs[mt] += v;
 #pragma unroll
@@ -3408,7 +3415,8 @@ bool ig_tconv_fwd(Model* m, int B, Op& o, double bytes, double flops, Op* bn_nex
     ig::TcArgs a = tc_args(m, B, o);
     // batch statistics of the BatchNorm behind it ride in the epilogue
     const bool stats = bn_next && d.stats && bn_self_fold_args(m, *bn_next, B, &a.bnf);
-    if (stats && d.kern == DK_F32_TCONV2) a.bnf.shift = a.bias;          // k_ig_tconv_fwd2 sums z - bias
+    // k_ig_tconv_fwd2 and the bf16 kernels sum the moments of z - bias (the bf16 ones: of the stored, rounded z less the bias)
+    if (stats && (d.kern == DK_F32_TCONV2 || d.kern == DK_B16_TCONV2 || d.kern == DK_B16_TCONV)) a.bnf.shift = a.bias;
     switch (d.kern) {
     case DK_B16_TCONV2: case DK_B16_TCONV: {
         static const TcKernB k[2][2] = {{igb::k_igb_tconv_fwd<false>, igb::k_igb_tconv_fwd<true>},

@@ -568,7 +568,8 @@ def test_bf16_kernels_against_bf16_emulating_oracle(gpu, f0, S, B, bn, n_down, n
     worst, err_l2 0.08 .. 0.14 -- the level of bf16 noise itself (emulating against exact oracle: 4e-2 .. 1e-1 per tensor on the
     one-level networks), identical for NW = 4 and 8 to seven digits.  Those two cases are held to median <= 0.25, err_l2 <= 0.25,
     worst tensor <= 0.8: a mis-indexed or dropped tensor is off by 1.0 and takes err_l2 with it; what they pin beyond that is that
-    both wave variants agree bit-for-bit in the loss and that every launch of the mix runs.  The tight bound stays with the cases above."""
+    both wave variants agree bit-for-bit in the loss and that every launch of the mix runs.  The tight bound stays with the cases above.
+    Every launch of this mix is held to the fp32 rule on its own stored inputs by tests/test_layerwise_gpu.py (the per-launch bound)."""
     import json
     import subprocess
     import sys
