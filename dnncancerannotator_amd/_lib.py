@@ -200,6 +200,7 @@ SIGNATURES = {
                                  _VP, _VP]),
     'dnnca_warp_groups_f32': (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
                                         C.POINTER(C.c_double), C.POINTER(C.c_double), _VP, _VP]),
+    'dnnca_affine_f32': (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _VP, _VP]),
     'dnnca_augment_u8': (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(AugParam), C.c_int, C.c_int,
                                    _VP, _VP]),
     'dnnca_memcpy_d2h': (C.c_int, [_VP, _VP, C.c_size_t]),

@@ -7,7 +7,10 @@ The reference applies, per image and in the order of `data_options.train.augment
     random_warp      tfa.image.sparse_image_warp                                                          (data.py:725-763)
 and, from the overlays configs/additionals/intra_channelwarp_std{3,5,10,20}.yaml,
     random_intrachannelwarp   a random_warp of its own for every channel group of the slice, label included (data.py:656-715)
-All five run on the device (`dnnca_augment_u8`, `dnnca_warp_f32`, `dnnca_warp_groups_f32`); this module draws their per-image
+and, this project's own (configs/additionals/affine_augment.yaml, d4_augment.yaml; the reference has no rotation, zoom or D4 view),
+    random_affine    rotation, zoom, shift and a flip / transpose of the plane about its centre, bilinear, zero outside
+All six run on the device (`dnnca_augment_u8`, `dnnca_affine_f32`, `dnnca_warp_f32`, `dnnca_warp_groups_f32`) in the fixed order
+crop, flip, contrast, affine, warp, intra-channel warp; this module draws their per-image
 parameters with a numpy generator (TensorFlow's own random streams cannot be reproduced without TensorFlow, so the draws are not
 bit-compatible with a TF run -- their distributions are the reference's) and solves the small spline systems of the warps.
 """
@@ -17,11 +20,12 @@ from collections import namedtuple
 
 import numpy as np
 
-AugmentPlan = namedtuple('AugmentPlan', ['crop', 'flip', 'contrast', 'warp', 'output_size', 'intrawarp'], defaults=(None,))
+AugmentPlan = namedtuple('AugmentPlan', ['crop', 'flip', 'contrast', 'warp', 'output_size', 'intrawarp', 'affine'], defaults=(None, None))
 # warp: (ctrl, wv) or None; intrawarp: (ctrl [B, G, n, 2], wv [B, G, n + 3, 2], group_of [Cs]: group of every raw-slice channel) or None
 # contrast_channels: the raw-slice channels random_contrast adjusts (target_channels), None: every feature channel
-RawBatch = namedtuple('RawBatch', ['raw', 'params', 'output_size', 'label_index', 'warp', 'intrawarp', 'contrast_channels'],
-                      defaults=(None, None))
+# affine: float64 [B, 2, 3] from draw_affine (output pixel -> source position, rows (row, column)) or None
+RawBatch = namedtuple('RawBatch', ['raw', 'params', 'output_size', 'label_index', 'warp', 'intrawarp', 'contrast_channels', 'affine'],
+                      defaults=(None, None, None))
 
 
 def contrast_channels(plan, n_channels, label_index):
@@ -67,7 +71,8 @@ def raw_to_float(batch):
     return x, y
 
 
-_KNOWN = ('random_crop', 'random_flip', 'random_contrast', 'random_warp', 'random_intrachannelwarp')
+_KNOWN = ('random_crop', 'random_flip', 'random_contrast', 'random_warp', 'random_intrachannelwarp', 'random_affine')
+AFFINE_SYMMETRIES = ('none', 'flips', 'd4')      # the names of the TTA modes (tta.MODES): what `--tta` averages over, train-time
 INTRAWARP_POINTS = 100          # data.py:706 passes n_points=100 to every group's random_warp, whatever the option says
 _warned = set()
 
@@ -76,7 +81,7 @@ def parse_augment_options(options, output_size):
     """data.py:538-551 + the defaults of train_ds (data.py:87-93).  options None -> {'random_crop': {}} like train_ds."""
     if options is None:
         options = {'random_crop': {}}
-    crop, flip, contrast, warp, intrawarp = None, False, None, None, None
+    crop, flip, contrast, warp, intrawarp, affine = None, False, None, None, None, None
     for name, conf in options.items():
         conf = dict(conf or {})
         if name not in _KNOWN:
@@ -109,7 +114,52 @@ def parse_augment_options(options, output_size):
                 _warned.add('intrawarp_n_points')
                 logging.warning('random_intrachannelwarp: n_points %r is ignored, every group is warped with %d control points '
                                 '(annotator/data.py:706)', conf['n_points'], INTRAWARP_POINTS)
-    return AugmentPlan(crop, flip, contrast, warp, tuple(output_size), intrawarp)
+        elif name == 'random_affine':
+            affine = _parse_affine(conf)
+    return AugmentPlan(crop, flip, contrast, warp, tuple(output_size), intrawarp, affine)
+
+
+def _parse_affine(conf):
+    """random_affine's keys with their defaults (all of them the identity), checked: a bad value is a ValueError here"""
+    unknown = set(conf) - {'rotate_deg', 'scale', 'shift', 'symmetry'}
+    if unknown:
+        raise TypeError('random_affine got unexpected options %s' % sorted(unknown))
+
+    def number(key, value):
+        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not np.isfinite(value):
+            raise ValueError('random_affine: %s = %r is not a finite number' % (key, value))
+        return float(value)
+    rotate = number('rotate_deg', conf.get('rotate_deg', 0))
+    if not 0.0 <= rotate <= 180.0:
+        raise ValueError('random_affine: rotate_deg = %r is outside [0, 180]' % (conf['rotate_deg'],))
+    scale = conf.get('scale', (1, 1))
+    if isinstance(scale, (str, bytes)) or not hasattr(scale, '__len__') or len(scale) != 2:
+        raise ValueError('random_affine: scale = %r is not a pair [lo, hi]' % (scale,))
+    lo, hi = number('scale[0]', scale[0]), number('scale[1]', scale[1])
+    if not 0.0 < lo <= hi:
+        raise ValueError('random_affine: scale = %r does not satisfy 0 < lo <= hi' % (scale,))
+    shift = number('shift', conf.get('shift', 0))
+    if shift < 0.0:
+        raise ValueError('random_affine: shift = %r is negative' % (conf['shift'],))
+    symmetry = conf.get('symmetry', 'none')
+    if symmetry not in AFFINE_SYMMETRIES:
+        raise ValueError('random_affine: symmetry = %r is none of %s' % (symmetry, ', '.join(AFFINE_SYMMETRIES)))
+    return dict(rotate_deg=rotate, scale=(lo, hi), shift=shift, symmetry=symmetry)
+
+
+def check_affine_size(plan, output_size):
+    """symmetry d4 transposes the plane: it needs a square one (as tta.mask_of asks of `--tta d4`)"""
+    if plan is not None and plan.affine is not None and plan.affine['symmetry'] == 'd4' and int(output_size[0]) != int(output_size[1]):
+        raise ValueError('random_affine: symmetry d4 transposes the slices and needs a square output_size, not %d x %d; '
+                         'the symmetry that works there is flips' % (output_size[0], output_size[1]))
+
+
+def d4_matrix(k):
+    """View k = 4 t + 2 v + h of tta.py as the exact integer 2 x 2 matrix G of its index map: out[q] = in[G (q - c) + c] in
+    (row, column).  v mirrors the rows, h the columns, t transposes the mirrored plane (square planes only)."""
+    h, v, t = k & 1, (k >> 1) & 1, (k >> 2) & 1
+    g = np.array([[-1.0 if v else 1.0, 0.0], [0.0, -1.0 if h else 1.0]])
+    return g[:, ::-1].copy() if t else g
 
 
 def draw_params(rng, n, plan):
@@ -124,6 +174,33 @@ def draw_params(rng, n, plan):
         flip = int(plan.flip and rng.random() < 0.5)
         contrast = float(rng.uniform(plan.contrast['lower'], plan.contrast['upper'])) if plan.contrast is not None else 1.0
         out.append((dy, dx, flip, contrast))
+    return out
+
+
+def draw_affine(rng, n, options, output_size):
+    """random_affine's draws for `n` images of `output_size`: float64 [n, 2, 3], row r = (L[r, 0], L[r, 1], o[r]) of the map from
+    an output pixel q to its source position s = L q + o in (row, column).  Per image, each only when its range is not a point:
+    theta ~ U[-R, R] degrees, z = exp(U[ln lo, ln hi]), t ~ U[-S, S]^2 (row, then column), then the symmetry element G (`flips`: view
+    0..3 of tta.py, `d4`: view 0..7, uniform).  With c the centre ((H - 1) / 2, (W - 1) / 2): L = G R(-theta) / z, o = c - L (c + t).
+    G is an exact integer matrix, so with theta = 0, z = 1, t = 0 every entry is an exact integer or half-integer."""
+    rot, (lo, hi), shift, symmetry = options['rotate_deg'], options['scale'], options['shift'], options['symmetry']
+    c = np.array([(int(output_size[0]) - 1) / 2.0, (int(output_size[1]) - 1) / 2.0])
+    out = np.empty((n, 2, 3), np.float64)
+    for b in range(n):
+        theta = float(rng.uniform(-rot, rot)) if rot > 0 else 0.0
+        z = float(np.exp(rng.uniform(np.log(lo), np.log(hi)))) if lo < hi else float(lo)
+        t = rng.uniform(-shift, shift, 2) if shift > 0 else np.zeros(2)
+        k = int(rng.integers(4 if symmetry == 'flips' else 8)) if symmetry != 'none' else 0
+        if theta == 0.0:
+            r = np.eye(2)
+        else:
+            cs, sn = np.cos(np.deg2rad(theta)), np.sin(np.deg2rad(theta))
+            r = np.array([[cs, sn], [-sn, cs]])                # R(-theta)
+        lin = d4_matrix(k) @ r
+        if z != 1.0:
+            lin = lin / z
+        out[b, :, :2] = lin
+        out[b, :, 2] = c - lin @ (c + t)
     return out
 
 

@@ -7,6 +7,7 @@
 // in two launches over a uint8 batch that was uploaded as stored (a quarter of the float bytes over PCIe).  The random draws are
 // made by the host (augment.py) and passed per image, so the arithmetic is checkable against the oracle draw for draw.
 // random_warp (tfa.image.sparse_image_warp) follows below as dnnca_warp_f32, random_intrachannelwarp as dnnca_warp_groups_f32.
+// random_affine (this project's own: rotation, zoom, shift and D4 view in one bilinear resampling) closes the file as dnnca_affine_f32.
 #include <stdlib.h>
 #include <string.h>
 #include "fast.h"
@@ -423,5 +424,167 @@ int dnnca_warp_groups_f32(void* model, const float* x_dev, const float* y_dev, i
     else
         LAUNCH(M, "aug_warp_groups", bytes, flops,
                hipLaunchKernelGGL(k_warp_groups<false>, dim3(bx, batch, n_groups), dim3(256), lds, M->stream, a));
+    return DNNCA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------- random_affine
+// This project's own option (augment.py draw_affine; the reference has no rotation, zoom, up-down mirror or transpose): output
+// pixel q of image b is sampled at s = L_b q + o_b (row, column), the host's composition of a rotation, a zoom, a shift and a
+// flip / transpose of the plane about its centre.  Bilinear in the shape of k_warp's lerp2, features and label with the same taps
+// and weights; OUTSIDE THE IMAGE IS ZERO (MRI background is black): a tap whose row or column is outside the plane contributes 0,
+// its address is never formed (the indices are clamped first, the value is selected away), and whether it is outside is decided in
+// double before anything is converted to int -- a position of 1e12 is an all-zero pixel.  H = 1 and W = 1 are valid.
+namespace dnnca {
+
+struct AffineArgs {
+    const float* x;          // [B, H, W, C] source features
+    const float* y;          // [B, H, W] source label
+    const double* mat;       // [B, 2, 3] rows (L[r][0], L[r][1], o[r]): s_r = L[r][0] q_row + L[r][1] q_col + o[r]
+    float* xo;
+    float* yo;
+    int B, H, W, C;
+};
+
+// one axis of the position: the cell floor(s) clamped to the two in-range tap indices, which of the two taps exist, the fraction
+struct AffineAxis {
+    int i0, i1;
+    bool in0, in1;
+    float a;
+};
+
+__device__ __forceinline__ AffineAxis affine_axis(double s, int size) {
+    AffineAxis t;
+    const double f = floor(s);
+    // taps f and f + 1: at least one of them is in [0, size - 1] exactly when -1 <= f <= size - 1 (false for NaN and +-inf too)
+    if (!(f >= -1.0 && f <= (double)(size - 1))) {
+        t.i0 = t.i1 = 0;
+        t.in0 = t.in1 = false;
+        t.a = 0.f;
+        return t;
+    }
+    const int i = (int)f;                  // -1 .. size - 1
+    t.in0 = i >= 0;
+    t.in1 = i + 1 <= size - 1;
+    t.i0 = t.in0 ? i : 0;
+    t.i1 = t.in1 ? i + 1 : size - 1;
+    t.a = (float)(s - f);
+    return t;
+}
+
+// grid (ceil(W / TX), ceil(H / TY), B), TX * TY threads: a block owns a TX x TY tile of output pixels, so that its source footprint
+// is a compact (rotated, mirrored or transposed) patch of about the same area whatever the matrix is -- a linear run of 256 output
+// pixels would read a 256-pixel COLUMN under the transposed D4 views, one cache line per lane.  One thread = one output pixel: the
+// position once, then the C channels (contiguous per tap in NHWC) and the label.
+template <int TX, int TY>
+__global__ __launch_bounds__(TX * TY) void k_affine(AffineArgs p) {
+    const int qx = blockIdx.x * TX + (int)(threadIdx.x % TX), qy = blockIdx.y * TY + (int)(threadIdx.x / TX), b = blockIdx.z;
+    if (qx >= p.W || qy >= p.H) return;
+    const double* m = p.mat + (size_t)b * 6;
+    const double sy = m[0] * (double)qy + m[1] * (double)qx + m[2];
+    const double sx = m[3] * (double)qy + m[4] * (double)qx + m[5];
+    const AffineAxis r = affine_axis(sy, p.H), c = affine_axis(sx, p.W);
+    const size_t img = (size_t)b * p.H * p.W;
+    const size_t o00 = img + (size_t)r.i0 * p.W + c.i0, o01 = img + (size_t)r.i0 * p.W + c.i1;
+    const size_t o10 = img + (size_t)r.i1 * p.W + c.i0, o11 = img + (size_t)r.i1 * p.W + c.i1;
+    const bool k00 = r.in0 && c.in0, k01 = r.in0 && c.in1, k10 = r.in1 && c.in0, k11 = r.in1 && c.in1;
+    const float ay = r.a, ax = c.a;
+    auto lerp2 = [&](float tl, float tr, float bl, float br) {
+        const float top = ax * (tr - tl) + tl, bot = ax * (br - bl) + bl;
+        return ay * (bot - top) + top;
+    };
+    const size_t oq = img + (size_t)qy * p.W + qx;
+    for (int ch = 0; ch < p.C; ++ch)
+        p.xo[oq * p.C + ch] = lerp2(k00 ? p.x[o00 * p.C + ch] : 0.f, k01 ? p.x[o01 * p.C + ch] : 0.f,
+                                    k10 ? p.x[o10 * p.C + ch] : 0.f, k11 ? p.x[o11 * p.C + ch] : 0.f);
+    p.yo[oq] = lerp2(k00 ? p.y[o00] : 0.f, k01 ? p.y[o01] : 0.f, k10 ? p.y[o10] : 0.f, k11 ? p.y[o11] : 0.f);
+}
+
+static bool affine_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const char *pa = (const char*)a, *pb = (const char*)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+}  // namespace dnnca
+
+int dnnca_affine_f32(void* model, const float* x_dev, const float* y_dev, int batch, int h, int w, int c, const double* mat_host,
+                     float* x_out_dev, float* y_out_dev) {
+    Model* M = reinterpret_cast<Model*>(model);
+    if (!M) { set_error("dnnca_affine_f32: null model"); return DNNCA_EINVAL; }
+    if (!x_dev || !y_dev || !mat_host || !x_out_dev || !y_out_dev) {
+        set_error("dnnca_affine_f32: null pointer");
+        return DNNCA_EINVAL;
+    }
+    if (batch < 1 || batch > 65535 || h < 1 || w < 1 || c < 1) {
+        set_error("dnnca_affine_f32: bad shape (batch %d in 1..65535, %d x %d x %d, each >= 1)", batch, h, w, c);
+        return DNNCA_EINVAL;
+    }
+    const size_t ny = (size_t)batch * h * w * 4, nx = ny * c;
+    if (affine_overlap(x_out_dev, nx, x_dev, nx) || affine_overlap(x_out_dev, nx, y_dev, ny) || affine_overlap(y_out_dev, ny, x_dev, nx) ||
+        affine_overlap(y_out_dev, ny, y_dev, ny) || affine_overlap(x_out_dev, nx, y_out_dev, ny)) {
+        set_error("dnnca_affine_f32: the outputs must not alias the inputs or each other");
+        return DNNCA_EINVAL;
+    }
+    for (int i = 0; i < batch * 6; ++i)
+        if (!(mat_host[i] - mat_host[i] == 0.0)) {         // NaN or +-inf
+            set_error("dnnca_affine_f32: matrix entry %d of image %d is not finite", i % 6, i / 6);
+            return DNNCA_EINVAL;
+        }
+    // DNNCA_AFFINE_TILE (tuning aid, read per call: tools/affine_rate.py walks it): the W x H tile of output pixels a block owns.
+    // 32 x 8 is the shipped one: at 8 x 512 x 512 x 3 it is the fastest on d4 draws and on affine_augment.yaml's draws and within
+    // 5 % of the fastest (64 x 4) on identity matrices; the linear 256 x 1 run is a third slower on d4 draws (profiles/affine_rate.txt)
+    static const char* const kTiles[] = {"32x8", "16x16", "8x32", "64x4", "8x8", "256x1"};
+    int tile = 0;
+    if (const char* name = getenv("DNNCA_AFFINE_TILE")) {
+        tile = -1;
+        for (int i = 0; i < 6; ++i)
+            if (!strcmp(name, kTiles[i])) tile = i;
+        if (tile < 0) {
+            set_error("dnnca_affine_f32: DNNCA_AFFINE_TILE=%s is none of 16x16, 32x8, 8x32, 64x4, 8x8, 256x1", name);
+            return DNNCA_EINVAL;
+        }
+    }
+    // one device row and a ring of pinned rows, as dnnca_warp_groups_f32: the caller's matrices are free when this call returns and
+    // the call does not wait for the stream.  Rows are sized for max_batch, so a ragged last batch does not grow them.
+    const size_t bytes_in = (size_t)batch * 6 * sizeof(double);
+    const size_t row = (size_t)M->desc.max_batch > (size_t)batch ? (size_t)M->desc.max_batch * 6 * sizeof(double) : bytes_in;
+    if (row > M->affine_scratch_bytes) {
+        void* p = nullptr;
+        DN_TRY(M->alloc(&p, row));
+        M->affine_scratch = p;
+        M->affine_scratch_bytes = row;
+    }
+    if (row > M->affine_pin_bytes) {
+        HIP_TRY(hipStreamSynchronize(M->stream));         // uploads from the old rows are complete
+        if (M->affine_pin) (void)hipHostFree(M->affine_pin);
+        M->affine_pin = nullptr;
+        M->affine_pin_bytes = 0;
+        HIP_TRY(hipHostMalloc(&M->affine_pin, row * Model::kAugRing, hipHostMallocDefault));
+        M->affine_pin_bytes = row;
+    }
+    const int k = M->affine_k;
+    M->affine_k = (k + 1) % Model::kAugRing;
+    if (!M->affine_ev[k]) HIP_TRY(hipEventCreateWithFlags(&M->affine_ev[k], hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(M->affine_ev[k]));
+    char* pin = (char*)M->affine_pin + (size_t)k * M->affine_pin_bytes;
+    memcpy(pin, mat_host, bytes_in);
+    HIP_TRY(hipMemcpyAsync(M->affine_scratch, pin, bytes_in, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipEventRecord(M->affine_ev[k], M->stream));
+    AffineArgs a{};
+    a.x = x_dev; a.y = y_dev; a.xo = x_out_dev; a.yo = y_out_dev;
+    a.mat = (const double*)M->affine_scratch;
+    a.B = batch; a.H = h; a.W = w; a.C = c;
+    const double bytes = (double)batch * h * w * (c + 1) * 8.0;
+#define AFFINE_GO(TX, TY)                                                                                                       \
+    LAUNCH(M, "aug_affine", bytes, 0,                                                                                           \
+           hipLaunchKernelGGL((k_affine<TX, TY>), dim3((w + TX - 1) / TX, (h + TY - 1) / TY, batch), dim3(TX * TY), 0, M->stream, a))
+    switch (tile) {
+        case 1: AFFINE_GO(16, 16); break;
+        case 2: AFFINE_GO(8, 32); break;
+        case 3: AFFINE_GO(64, 4); break;
+        case 4: AFFINE_GO(8, 8); break;
+        case 5: AFFINE_GO(256, 1); break;
+        default: AFFINE_GO(32, 8); break;
+    }
+#undef AFFINE_GO
     return DNNCA_OK;
 }

@@ -174,6 +174,13 @@ struct Model {
     size_t warpg_pin_bytes = 0;
     hipEvent_t warpg_ev[kAugRing] = {nullptr, nullptr, nullptr, nullptr};
     int warpg_k = 0;
+    // dnnca_affine_f32: the [batch, 2, 3] matrices of random_affine -- one device row and a pinned ring of the same rows (as aug_pin)
+    void* affine_scratch = nullptr;
+    size_t affine_scratch_bytes = 0;
+    void* affine_pin = nullptr;          // kAugRing x affine_pin_bytes, pinned
+    size_t affine_pin_bytes = 0;
+    hipEvent_t affine_ev[kAugRing] = {nullptr, nullptr, nullptr, nullptr};
+    int affine_k = 0;
     float* first_slabs = nullptr;        // bucket copies of the first-layer weight gradient (kernels_first.hip; kept zeroed)
     // bucket rows of the BN reductions that fold themselves (bn_dev.h): kBnTab doubles, then the ticket counter; kept zeroed
     static constexpr int kBnTab = 4096;

@@ -118,6 +118,9 @@ Model::~Model() {
     if (warpg_pin) (void)hipHostFree(warpg_pin);
     for (auto e : warpg_ev)
         if (e) (void)hipEventDestroy(e);
+    if (affine_pin) (void)hipHostFree(affine_pin);
+    for (auto e : affine_ev)
+        if (e) (void)hipEventDestroy(e);
     if (wg_fork) (void)hipEventDestroy(wg_fork);
     if (wg_join) (void)hipEventDestroy(wg_join);
     if (wg_bucket) (void)hipEventDestroy(wg_bucket);

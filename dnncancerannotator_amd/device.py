@@ -938,6 +938,21 @@ class DeviceModel:
             self.sync()
         return DeviceView(xb, (B, ho, wo, cs - 1)), DeviceView(yb, (B, ho, wo))
 
+    def affine(self, xv, yv, mats):
+        """random_affine on device-resident (x, y) views: mats float64 [B, 2, 3] from augment.draw_affine (output pixel -> source
+        position, bilinear, zero outside).  Asynchronous on the model's stream; the views are valid until the next call."""
+        B, h, w, c = xv.shape
+        mats = np.ascontiguousarray(mats, np.float64)
+        if mats.shape != (B, 2, 3):
+            raise ValueError('affine matrices %s are not [B, 2, 3] for a batch of %d' % (mats.shape, B))
+        if not hasattr(self, '_affine'):
+            self._affine = (RawDeviceBuffer(), RawDeviceBuffer())
+        xo, yo = self._affine
+        xo.reserve(xv.nbytes)
+        yo.reserve(yv.nbytes)
+        check(self.lib.dnnca_affine_f32(self.handle, xv.ptr, yv.ptr, B, h, w, c, mats.ctypes.data_as(C.POINTER(C.c_double)), xo.ptr, yo.ptr))
+        return DeviceView(xo, xv.shape), DeviceView(yo, yv.shape)
+
     def warp(self, xv, yv, ctrl, wv):
         """random_warp's dense part on device-resident (x, y) views: ctrl [B, n, 2], wv [B, n + 3, 2] from augment.solve_warp."""
         B, h, w, c = xv.shape

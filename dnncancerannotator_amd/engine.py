@@ -406,6 +406,8 @@ class TFKerasModel:
                     params, _ = shard(batch.params)
                     xb, yb = dm.augment_u8(shard(batch.raw)[0], params, batch.output_size, batch.label_index,
                                            contrast_channels=batch.contrast_channels, src_ptr=src)
+                    if batch.affine is not None:         # fixed place in the chain: crop, flip, contrast, affine, warp, intra-channel warp
+                        xb, yb = dm.affine(xb, yb, shard(batch.affine)[0])
                     if batch.warp is not None:
                         xb, yb = dm.warp(xb, yb, shard(batch.warp[0])[0], shard(batch.warp[1])[0])
                     if batch.intrawarp is not None:      # after random_warp: the overlay's key comes behind data_options.yaml's
@@ -420,6 +422,8 @@ class TFKerasModel:
                         raw, _ = shard(batch.raw)
                         params, _ = shard(batch.params)
                         xb, yb = dm.augment_u8(raw, params, batch.output_size, batch.label_index, contrast_channels=batch.contrast_channels)
+                        if batch.affine is not None:
+                            xb, yb = dm.affine(xb, yb, shard(batch.affine)[0])
                         if batch.warp is not None:
                             xb, yb = dm.warp(xb, yb, shard(batch.warp[0])[0], shard(batch.warp[1])[0])
                         if batch.intrawarp is not None:

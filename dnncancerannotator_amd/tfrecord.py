@@ -310,7 +310,7 @@ class TFRecordDataset:
     Training (`augment_options` a dict or None, data.py:62-111 train_ds): the slices are centre-cropped to 512 x 512 (the `base`
     call of train_ds, data.py:95-100), shuffled through a buffer of `buffer_size` slices (data.py:106) and handed on as uint8
     `augment.RawBatch`es with their random draws; crop / flip / contrast / the /255 and the feature-label split then run on the
-    device (`dnnca_augment_u8` / `dnnca_warp_f32` / `dnnca_warp_groups_f32`, engine.train).
+    device (`dnnca_augment_u8` / `dnnca_affine_f32` / `dnnca_warp_f32` / `dnnca_warp_groups_f32`, engine.train).
 
     include_meta (evaluation only, eval_ds(include_meta=True), data.py:488-510): batches (x, y, paths, sliceIDs) -- the same x and
     y as without it, each slice's exam `path` feature and its 0-based index in the exam record (tf.data.experimental.Counter).
@@ -338,6 +338,7 @@ class TFRecordDataset:
             self.output_size = self.plan.output_size
         # random_contrast.target_channels, checked here so that a bad index fails when the dataset is built
         self.contrast_channels = augment.contrast_channels(self.plan, len(self.slice_types), self.label_idx)
+        augment.check_affine_size(self.plan, self.output_size)      # random_affine's d4 on a non-square output_size fails here too
         self.include_meta = bool(include_meta)
         if self.include_meta and self.plan is not None:
             raise ValueError('include_meta is for evaluation datasets (augment_options=False)')
@@ -367,6 +368,12 @@ class TFRecordDataset:
         if self.normalize_exams and not (self.repeat and self.plan is not None):
             raise ValueError('normalize_exams makes an endless training stream: it needs repeat=True and augment_options')
         self.rng = np.random.default_rng(seed)
+        # random_affine draws from a stream of its own, spawned from the same seed: the shuffle and the draws of every other option
+        # are then, batch after batch, what they are without it
+        self.affine_rng = None
+        if self.plan is not None and self.plan.affine is not None:
+            own = isinstance(seed, (int, np.integer))
+            self.affine_rng = np.random.default_rng(np.random.SeedSequence(int(seed), spawn_key=(1,)) if own else None)
         self.element_spec = (Spec((self.batch_size,) + self.output_size + (len(self.feature_idx),), np.float32),)
         if self.labels:
             self.element_spec += (Spec((self.batch_size,) + self.output_size, np.float32),)
@@ -537,12 +544,16 @@ class TFRecordDataset:
             src, dst = augment.draw_intrawarp(self.rng, len(raws), self.output_size[0], len(groups), opt['max_diff'], opt['stddev'])
             intrawarp = augment.solve_intrawarp(self._mine(src), self._mine(dst)) + (augment.group_table(groups, len(self.slice_types)),)
         params = self._mine(augment.draw_params(self.rng, len(raws), self.plan))
+        # random_affine draws last and from its own stream: the draws of every other option for a seed are the same with and without it
+        affine = None
+        if self.plan.affine is not None:
+            affine = self._mine(augment.draw_affine(self.affine_rng, len(raws), self.plan.affine, self.output_size))      # global batch, then this rank's part
         # only the window the random crop can reach travels on (centre +- the jitter bound: the same centre, so the same pixels
         # come out of dnnca_augment_u8): 268 x 268 of 512 x 512 for the default crop -- a quarter of the bytes to stack and upload
         m = max(abs(int(self.plan.crop['min_'])), abs(int(self.plan.crop['max_']))) if self.plan.crop is not None else 0
         oh, ow = self.output_size
         mine = [self._centre(r[None], min(r.shape[0], oh + 2 * m), min(r.shape[1], ow + 2 * m))[0] for r in self._mine(raws)]
-        return augment.RawBatch(np.stack(mine), params, self.output_size, self.label_idx, warp, intrawarp, self.contrast_channels)
+        return augment.RawBatch(np.stack(mine), params, self.output_size, self.label_idx, warp, intrawarp, self.contrast_channels, affine)
 
     def _stacked(self, xs, ys):
         if not self.labels:                     # (x,): there is no label to stack

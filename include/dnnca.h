@@ -219,6 +219,17 @@ int dnnca_warp_f32(void* model, const float* x_dev, const float* y_dev, int batc
 int dnnca_warp_groups_f32(void* model, const float* x_dev, const float* y_dev, int batch, int h, int w, int c, int n_groups,
                           const int* group_of, int n_points, const double* ctrl_host, const double* wv_host, float* x_out_dev,
                           float* y_out_dev);
+/* random_affine (this project's own augmentation option; augment.py draw_affine): rotation, zoom, shift and a flip / transpose of
+   the plane in one bilinear resampling.  mat_host [batch, 2, 3] double: output pixel q = (row, column) of image b is sampled at
+   s_r = mat[b][r][0] * q_row + mat[b][r][1] * q_col + mat[b][r][2], formed in double; the cell is floor(s), the fractions are
+   float32, x [batch, h, w, c] and y [batch, h, w] are blended with the same four taps and weights (the label comes out soft).
+   Outside the image is zero: a tap outside [0, h-1] x [0, w-1] contributes 0 and is never addressed, however far away s lies.
+   h, w, c >= 1.  DNNCA_EINVAL (the message names the function, nothing is launched, the outputs are untouched) for: a null
+   pointer; batch (1..65535), h, w or c < 1; an output overlapping an input or the other output; a NaN or infinite matrix entry.
+   Asynchronous on the model's stream like dnnca_augment_u8: mat_host has been copied when the call returns; a host read of the
+   outputs needs dnnca_sync first. */
+int dnnca_affine_f32(void* model, const float* x_dev, const float* y_dev, int batch, int h, int w, int c, const double* mat_host,
+                     float* x_out_dev, float* y_out_dev);
 /* same as dnnca_train_step with x/y already in HBM; asynchronous on the model's stream; out may be NULL (no sync) */
 int dnnca_train_step_dev(void* model, const float* x_dev, const float* y_dev, int batch, float lr,
                          const dnnca_loss_cfg* cfg, dnnca_step_out* out);
