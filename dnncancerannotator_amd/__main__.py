@@ -101,6 +101,9 @@ def build_parser(prog='python3 -m annotator'):
     e.add_argument('--attribution_baseline', choices=('black', 'mean'), default=argparse.SUPPRESS,
                    help='where the path of --visualize_attribution starts: a zero image or the mean of each slice and modality '
                         '(default: black)')
+    e.add_argument('--weights', choices=('raw', 'ema'), default=argparse.SUPPRESS,
+                   help='which weights of each checkpoint to evaluate: the raw ones or their exponential moving average '
+                        '(deploy_options.ema at training time; a checkpoint without one is an error); default: raw')
     p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
     p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
     p.add_argument('--data_path', nargs='+', required=True)
@@ -135,6 +138,9 @@ def build_parser(prog='python3 -m annotator'):
                    help='histogram bins behind the percentiles of --lesion_features, 0..256 (0: no percentiles; default: 32)')
     p.add_argument('--feature_ring', type=int, default=argparse.SUPPRESS, metavar='R',
                    help='the tissue around a lesion of --lesion_features: background pixels within R pixels, 0..8 (0: none; default: 3)')
+    p.add_argument('--weights', choices=('raw', 'ema'), default=argparse.SUPPRESS,
+                   help='which weights of the checkpoint to annotate with: the raw ones or their exponential moving average '
+                        '(deploy_options.ema at training time; a checkpoint without one is an error); default: raw')
     return parser
 
 

@@ -184,6 +184,10 @@ SIGNATURES = {
     'dnnca_set_opt_state': (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int64]),
     'dnnca_get_opt_state': (C.c_int, [_VP, _FP, _FP, C.c_int64, C.POINTER(C.c_int64)]),
     'dnnca_set_adam': (C.c_int, [_VP, C.c_float, C.c_float, C.c_float]),
+    'dnnca_model_set_ema': (C.c_int, [_VP, C.c_float, C.c_int]),
+    'dnnca_get_ema': (C.c_int, [_VP, _FP, C.c_int64, C.POINTER(C.c_int64)]),
+    'dnnca_set_ema_state': (C.c_int, [_VP, _FP, C.c_int64, C.c_int64]),
+    'dnnca_ema_exchange': (C.c_int, [_VP]),
     'dnnca_forward': (C.c_int, [_VP, _FP, C.c_int, C.c_int, _FP, _FP]),
     'dnnca_forward_tta': (C.c_int, [_VP, _FP, C.c_int, C.c_uint, _FP]),
     'dnnca_tta_view_of': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _FP]),

@@ -80,10 +80,13 @@ void g_l2(hipStream_t s, size_t n, const float* w, float* g, float l2, double* s
 // writes [loss, positive_rate, weight, ymin, ymax] floats to out5 (device) from the scalar block
 void g_finalize_scalars(hipStream_t s, double* scalars, const dnnca_loss_cfg cfg, double n_label, double inv_batch_hw,
                         float* out5);
+// e != nullptr: the weight average rides the launch, e <- e - om * (e - p) with the p just written (Model::ema)
 void g_adam(hipStream_t s, size_t n, float* p, const float* g, float* m, float* v, float lr_t, float b1, float b2,
-            float eps, float gscale);
+            float eps, float gscale, float* e = nullptr, float om = 0.f);
 void g_adam_finalize(hipStream_t s, size_t n, float* p, const float* g, float* m, float* v, float lr_t, float b1, float b2, float eps,
-                     float gscale, double* scalars, const dnnca_loss_cfg cfg, double n_label, double inv_batch_hw, float* out5);
+                     float gscale, double* scalars, const dnnca_loss_cfg cfg, double n_label, double inv_batch_hw, float* out5,
+                     float* e = nullptr, float om = 0.f);
+void g_ema_exchange(hipStream_t s, size_t n, float* a, float* b);      // a <-> b, exact (dnnca_ema_exchange)
 constexpr int DNNCA_CONF_MAX_THR = 1024;
 // pixel-confusion histogram.  out == nullptr: the bins add up in `hist` [2][nthr + 1] over launches (zeroed by the caller).
 // out != nullptr (per-step training metrics): `hist` is scratch ([2][nthr + 1] + ticket, kept zeroed); the launch's last block

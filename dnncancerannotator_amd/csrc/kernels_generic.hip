@@ -694,8 +694,12 @@ struct AdamFinalize {
     float* out5;
 };
 
+// EMA: the thread that stores p[i] also moves the weight average e[i] towards it (Model::ema), e <- e - om * (e - p), TensorFlow's
+// assign_moving_average form; a template parameter, so that the plain kernel is the code it was
+template <bool EMA>
 __global__ void k_adam(size_t n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                       float* __restrict__ v, float lr_t, float b1, float b2, float eps, float gscale, AdamFinalize fin) {
+                       float* __restrict__ v, float lr_t, float b1, float b2, float eps, float gscale, AdamFinalize fin,
+                       float* __restrict__ e, float om) {
     size_t i = (size_t)blockIdx.x * TB + threadIdx.x;
     if (i == 0 && fin.out5) {
         fin.out5[0] = (float)(fin.scalars[3] * fin.inv_batch_hw + fin.scalars[4]);
@@ -710,18 +714,53 @@ __global__ void k_adam(size_t n, float* __restrict__ p, const float* __restrict_
     float vi = v[i] * b2 + (gi * gi) * (1.f - b2);
     m[i] = mi;
     v[i] = vi;
-    p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
+    const float pi = p[i] - lr_t * mi / (sqrtf(vi) + eps);
+    p[i] = pi;
+    if (EMA) {
+        const float ei = e[i];
+        e[i] = ei - om * (ei - pi);
+    }
 }
 
+// e == nullptr: the plain update
 void g_adam(hipStream_t s, size_t n, float* p, const float* g, float* m, float* v, float lr_t, float b1, float b2, float eps,
-            float gscale) {
-    hipLaunchKernelGGL(k_adam, dim3(nblk(n)), dim3(TB), 0, s, n, p, g, m, v, lr_t, b1, b2, eps, gscale, AdamFinalize{});
+            float gscale, float* e, float om) {
+    if (e) hipLaunchKernelGGL(k_adam<true>, dim3(nblk(n)), dim3(TB), 0, s, n, p, g, m, v, lr_t, b1, b2, eps, gscale, AdamFinalize{}, e, om);
+    else hipLaunchKernelGGL(k_adam<false>, dim3(nblk(n)), dim3(TB), 0, s, n, p, g, m, v, lr_t, b1, b2, eps, gscale, AdamFinalize{}, nullptr, 0.f);
 }
 
 void g_adam_finalize(hipStream_t s, size_t n, float* p, const float* g, float* m, float* v, float lr_t, float b1, float b2, float eps,
-                     float gscale, double* scalars, const dnnca_loss_cfg cfg, double n_label, double inv_batch_hw, float* out5) {
-    hipLaunchKernelGGL(k_adam, dim3(nblk(n)), dim3(TB), 0, s, n, p, g, m, v, lr_t, b1, b2, eps, gscale,
-                       AdamFinalize{scalars, cfg, n_label, inv_batch_hw, out5});
+                     float gscale, double* scalars, const dnnca_loss_cfg cfg, double n_label, double inv_batch_hw, float* out5,
+                     float* e, float om) {
+    const AdamFinalize fin{scalars, cfg, n_label, inv_batch_hw, out5};
+    if (e) hipLaunchKernelGGL(k_adam<true>, dim3(nblk(n)), dim3(TB), 0, s, n, p, g, m, v, lr_t, b1, b2, eps, gscale, fin, e, om);
+    else hipLaunchKernelGGL(k_adam<false>, dim3(nblk(n)), dim3(TB), 0, s, n, p, g, m, v, lr_t, b1, b2, eps, gscale, fin, nullptr, 0.f);
+}
+
+// ------------------------------------------------------------------------------------------------ weight-average exchange
+// a[i] <-> b[i] for i < n, one thread per float4 and one per element of the tail: exact, and its own inverse.  Both vectors start
+// at a hipMalloc address (16-byte aligned).
+__global__ __launch_bounds__(256) void k_ema_exchange(size_t n, float* __restrict__ a, float* __restrict__ b) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t n4 = n / 4;
+    if (i < n4) {
+        float4* a4 = reinterpret_cast<float4*>(a);
+        float4* b4 = reinterpret_cast<float4*>(b);
+        const float4 va = a4[i], vb = b4[i];
+        a4[i] = vb;
+        b4[i] = va;
+    } else if (i - n4 < n - 4 * n4) {
+        const size_t k = 4 * n4 + (i - n4);
+        const float va = a[k], vb = b[k];
+        a[k] = vb;
+        b[k] = va;
+    }
+}
+
+void g_ema_exchange(hipStream_t s, size_t n, float* a, float* b) {
+    if (n == 0) return;
+    const size_t threads = n / 4 + n % 4;
+    hipLaunchKernelGGL(k_ema_exchange, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, n, a, b);
 }
 
 // ------------------------------------------------------------------------------------------------ pixel confusion

@@ -1186,7 +1186,11 @@ struct AdamTail {
     dnnca_loss_cfg cfg;
     double n_label, inv_batch_hw;
     float* out5;
+    float* e;          // k_pg_fold<true> only: the weight average and 1 - decay of this step (Model::ema)
+    float om;
 };
+// EMA: the thread that stores p[i] also moves the weight average towards it, e <- e - om * (e - p) (g_adam's arithmetic again)
+template <bool EMA>
 __device__ __forceinline__ void fold_out(float* __restrict__ grads, const AdamTail& ad, int i, float gi) {
     grads[i] = gi;
     if (ad.p) {
@@ -1194,10 +1198,16 @@ __device__ __forceinline__ void fold_out(float* __restrict__ grads, const AdamTa
         const float vi = ad.v[i] * ad.b2 + (gi * gi) * (1.f - ad.b2);
         ad.m[i] = mi;
         ad.v[i] = vi;
-        ad.p[i] = ad.p[i] - ad.lr_t * mi / (sqrtf(vi) + ad.eps);
+        const float pi = ad.p[i] - ad.lr_t * mi / (sqrtf(vi) + ad.eps);
+        ad.p[i] = pi;
+        if (EMA) {
+            const float ei = ad.e[i];
+            ad.e[i] = ei - ad.om * (ei - pi);
+        }
     }
 }
 
+template <bool EMA>
 __global__ __launch_bounds__(256) void k_pg_fold(const FoldDesc* __restrict__ descs, const float* __restrict__ slabs,
                                                  float* __restrict__ grads, int nfolds, HeadTail h, AdamTail ad) {
     __shared__ float Dl[7 * 256];
@@ -1214,8 +1224,8 @@ __global__ __launch_bounds__(256) void k_pg_fold(const FoldDesc* __restrict__ de
             __syncthreads();
         }
         if (threadIdx.x == 0) {
-            if (k < h.C) fold_out(grads, ad, (int)(h.dw - grads) + k, (float)red[0]);       // (h.dw / h.dbias point into grads)
-            else if (k == h.C) fold_out(grads, ad, (int)(h.dbias - grads), (float)red[0]);
+            if (k < h.C) fold_out<EMA>(grads, ad, (int)(h.dw - grads) + k, (float)red[0]);       // (h.dw / h.dbias point into grads)
+            else if (k == h.C) fold_out<EMA>(grads, ad, (int)(h.dbias - grads), (float)red[0]);
             else {
                 h.scalars[3] = red[0];
                 if (ad.p) {          // the step outputs (no L2 penalty on this path: scalars[4] == 0)
@@ -1267,12 +1277,12 @@ __global__ __launch_bounds__(256) void k_pg_fold(const FoldDesc* __restrict__ de
         // rows m = (a, e, co) are exactly the [r, r, Cout, Cin] kernel rows; column Cin is the all-ones (bias) column
         const int nwt = 4 * d.CO * d.C;
         if (o < nwt) {
-            fold_out(grads, ad, d.w_off + o, Dl[slab_index(o / d.C, o % d.C)]);
+            fold_out<EMA>(grads, ad, d.w_off + o, Dl[slab_index(o / d.C, o % d.C)]);
         } else if (o < nwt + d.CO) {
             const int co = o - nwt;
             float a = 0.f;
             for (int ae = 0; ae < 4; ++ae) a += Dl[slab_index(ae * d.CO + co, d.C)];
-            fold_out(grads, ad, d.b_off + co, a);
+            fold_out<EMA>(grads, ad, d.b_off + co, a);
         }
         return;
     }
@@ -1285,11 +1295,11 @@ __global__ __launch_bounds__(256) void k_pg_fold(const FoldDesc* __restrict__ de
         int co = o % d.CO, ci = (o / d.CO) % d.C, tap = o / (d.CO * d.C);
         int dy = tap / 3, kx = tap % 3;
         for (int dx = 0; dx < d.G; ++dx) acc += Dl[slab_index(dy * WR + (dx + kx) * d.C + ci, dx * d.CO + co)];
-        fold_out(grads, ad, d.w_off + ((tap * d.cin_total) + d.ci_off + ci) * d.CO + co, acc);
+        fold_out<EMA>(grads, ad, d.w_off + ((tap * d.cin_total) + d.ci_off + ci) * d.CO + co, acc);
     } else {
         int co = o - nw;
         for (int dx = 0; dx < d.G; ++dx) acc += Dl[slab_index(3 * WR, dx * d.CO + co)];
-        fold_out(grads, ad, d.b_off + co, acc);
+        fold_out<EMA>(grads, ad, d.b_off + co, acc);
     }
 }
 
@@ -2091,19 +2101,25 @@ int fast_finish_backward(Model* m) {
         return DNNCA_OK;
     }
     LAUNCH(m, "pg_fold", 0, 0,
-           hipLaunchKernelGGL(k_pg_fold, dim3((unsigned)pl.folds.size() + extra, pl.fold_chunks), dim3(256), 0, m->stream,
+           hipLaunchKernelGGL(k_pg_fold<false>, dim3((unsigned)pl.folds.size() + extra, pl.fold_chunks), dim3(256), 0, m->stream,
                               pl.folds_dev, pl.slabs, m->g, (int)pl.folds.size(), h, AdamTail{}));
     return DNNCA_OK;
 }
 
 // the deferred fold of fast_finish_backward with the Adam update (and the step outputs) in the same launch
-int fast_fold_adam(Model* m, float lr_t, const dnnca_loss_cfg& cfg, double n_label, double inv_batch_hw) {
+int fast_fold_adam(Model* m, float lr_t, float ema_om, const dnnca_loss_cfg& cfg, double n_label, double inv_batch_hw) {
     const PgPlan& pl = pg_find(m);
     const HeadTail h = pl.pending_head;
     m->step.fold_deferred = false;
-    AdamTail ad{m->p, m->m, m->v, lr_t, m->beta1, m->beta2, m->eps, cfg, n_label, inv_batch_hw, m->out5};
+    AdamTail ad{m->p, m->m, m->v, lr_t, m->beta1, m->beta2, m->eps, cfg, n_label, inv_batch_hw, m->out5, m->ema.e, ema_om};
+    if (m->ema.e) {          // the weight average rides: 8 more bytes per parameter
+        LAUNCH(m, "pg_fold_adam_ema", 36.0 * m->nT, 13.0 * m->nT,
+               hipLaunchKernelGGL(k_pg_fold<true>, dim3((unsigned)pl.folds.size() + h.C + 2, pl.fold_chunks), dim3(256), 0, m->stream,
+                                  pl.folds_dev, pl.slabs, m->g, (int)pl.folds.size(), h, ad));
+        return DNNCA_OK;
+    }
     LAUNCH(m, "pg_fold_adam", 28.0 * m->nT, 10.0 * m->nT,
-           hipLaunchKernelGGL(k_pg_fold, dim3((unsigned)pl.folds.size() + h.C + 2, pl.fold_chunks), dim3(256), 0, m->stream,
+           hipLaunchKernelGGL(k_pg_fold<false>, dim3((unsigned)pl.folds.size() + h.C + 2, pl.fold_chunks), dim3(256), 0, m->stream,
                               pl.folds_dev, pl.slabs, m->g, (int)pl.folds.size(), h, ad));
     return DNNCA_OK;
 }

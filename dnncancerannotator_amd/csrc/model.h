@@ -201,6 +201,14 @@ struct Model {
     int64_t iterations = 0;
     float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-7f;
     int last_batch = 0;
+    // exponential moving average of the trainable variables (dnnca_model_set_ema; tf.train.ExponentialMovingAverage with
+    // num_updates): e [nT] rides every Adam launch (k_adam<true>, k_pg_fold<true>), one thread per element, nothing crosses to the
+    // host.  e == nullptr: off, and every launch is the one it was.  in_use: dnnca_ema_exchange has put the average into `p` (and
+    // the raw weights into `e`) -- contents, never pointers: kernel plans and prepared operands hold addresses derived from `p`,
+    // and every forward pass rebuilds its weight-derived operands from `p` (fast_prepare, ig_prepare, ig3x_prepare, ig_flip)
+    struct Ema { float* e = nullptr; float decay = 0.f; bool warmup = true; int64_t num_updates = 0; bool in_use = false; } ema;
+    float ema_next_om();                 // counts one update (never in a dry plan run) and returns (float)(1 - d_n) for it
+    int ema_refuse(const char* what);    // DNNCA_ESTATE while the averaged weights are in use, else DNNCA_OK
     // What one step hands from launch to launch (and from forward() to loss_and_backward() to optimizer_step()).  forward() begins
     // a pass with `step = Step{}`, in front of fast_prepare: nothing of an earlier step, finished or stopped on an error, survives
     // it.  Every other write is a launch setting a hand-over or the launch it is meant for consuming it.  (The hand-overs inside a

@@ -92,6 +92,7 @@ Model::~Model() {
     fast_release(this);
     ig_release(this);
     for (void* a : allocs) (void)hipFree(a);
+    if (ema.e) (void)hipFree(ema.e);
     if (tta_io) (void)hipFree(tta_io);
     if (calib_ws) (void)hipFree(calib_ws);
     for (auto& r : recs) {
@@ -1403,6 +1404,20 @@ int Model::send_bucket(int64_t lo, int64_t hi) {
     return DNNCA_OK;
 }
 
+// d_n = min(decay, (1 + n) / (10 + n)) with warm-up, decay without, in double; the kernels take (float)(1 - d_n) (as lr_t is made)
+float Model::ema_next_om() {
+    const int64_t n = dry ? ema.num_updates + 1 : ++ema.num_updates;
+    double d = (double)ema.decay;
+    if (ema.warmup) d = std::min(d, (1.0 + (double)n) / (10.0 + (double)n));
+    return (float)(1.0 - d);
+}
+
+int Model::ema_refuse(const char* what) {
+    if (!ema.in_use) return DNNCA_OK;
+    set_error("%s: the averaged weights are in use (dnnca_ema_exchange): exchange back first", what);
+    return DNNCA_ESTATE;
+}
+
 int Model::optimizer_step(float lr) {
     cur_op = nullptr;
     float gscale = 1.0f;
@@ -1425,16 +1440,27 @@ int Model::optimizer_step(float lr) {
     iterations += dry ? 0 : 1;
     double t = (double)(dry ? 1 : iterations);
     float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, t)) / (1.0 - std::pow((double)beta1, t)));
+    const float om = ema.e ? ema_next_om() : 0.f;          // the weight average rides whichever Adam launch runs
     if (step.fin_pending.on && step.fold_deferred) {
         step.fin_pending.on = false;          // consumed (here and below): this launch writes the step outputs
-        return fast_fold_adam(this, lr_t, step.fin_pending.cfg, step.fin_pending.n_label, step.fin_pending.inv_batch_hw);
+        return fast_fold_adam(this, lr_t, om, step.fin_pending.cfg, step.fin_pending.n_label, step.fin_pending.inv_batch_hw);
     }
     if (step.fold_deferred) { set_error("internal: deferred gradient fold without a single-replica optimizer step"); return DNNCA_ESTATE; }
     if (step.fin_pending.on) {
         step.fin_pending.on = false;
+        if (ema.e) {
+            LAUNCH(this, "g_adam_ema", 36.0 * nT, 13.0 * nT,
+                   g_adam_finalize(stream, (size_t)nT, p, g, m, v, lr_t, beta1, beta2, eps, gscale, scalars, step.fin_pending.cfg,
+                                   step.fin_pending.n_label, step.fin_pending.inv_batch_hw, out5, ema.e, om));
+            return DNNCA_OK;
+        }
         LAUNCH(this, "g_adam", 28.0 * nT, 10.0 * nT,
                g_adam_finalize(stream, (size_t)nT, p, g, m, v, lr_t, beta1, beta2, eps, gscale, scalars, step.fin_pending.cfg,
                                step.fin_pending.n_label, step.fin_pending.inv_batch_hw, out5));
+        return DNNCA_OK;
+    }
+    if (ema.e) {
+        LAUNCH(this, "g_adam_ema", 36.0 * nT, 13.0 * nT, g_adam(stream, (size_t)nT, p, g, m, v, lr_t, beta1, beta2, eps, gscale, ema.e, om));
         return DNNCA_OK;
     }
     LAUNCH(this, "g_adam", 28.0 * nT, 10.0 * nT, g_adam(stream, (size_t)nT, p, g, m, v, lr_t, beta1, beta2, eps, gscale));
@@ -1521,7 +1547,11 @@ static int copy_flat(Model* M, float* dev, int64_t have, const float* src, float
     return DNNCA_OK;
 }
 
-int dnnca_set_params(void* model, const float* flat, int64_t n) { MODEL(model); return copy_flat(M, M->p, M->nT, flat, nullptr, n); }
+int dnnca_set_params(void* model, const float* flat, int64_t n) {
+    MODEL(model);
+    DN_TRY(M->ema_refuse("dnnca_set_params"));
+    return copy_flat(M, M->p, M->nT, flat, nullptr, n);
+}
 int dnnca_get_params(void* model, float* flat, int64_t n) { MODEL(model); return copy_flat(M, M->p, M->nT, nullptr, flat, n); }
 int dnnca_set_state(void* model, const float* flat, int64_t n) { MODEL(model); return copy_flat(M, M->state, M->nS, flat, nullptr, n); }
 int dnnca_get_state(void* model, float* flat, int64_t n) { MODEL(model); return copy_flat(M, M->state, M->nS, nullptr, flat, n); }
@@ -1529,6 +1559,7 @@ int dnnca_get_grads(void* model, float* flat, int64_t n) { MODEL(model); return 
 
 int dnnca_set_opt_state(void* model, const float* m, const float* v, int64_t n, int64_t iterations) {
     MODEL(model);
+    DN_TRY(M->ema_refuse("dnnca_set_opt_state"));
     DN_TRY(copy_flat(M, M->m, M->nT, m, nullptr, n));
     DN_TRY(copy_flat(M, M->v, M->nT, v, nullptr, n));
     M->iterations = iterations;
@@ -1540,6 +1571,59 @@ int dnnca_get_opt_state(void* model, float* m, float* v, int64_t n, int64_t* ite
     DN_TRY(copy_flat(M, M->m, M->nT, nullptr, m, n));
     DN_TRY(copy_flat(M, M->v, M->nT, nullptr, v, n));
     if (iterations) *iterations = M->iterations;
+    return DNNCA_OK;
+}
+
+// ---- exponential moving average of the weights (Model::ema) -------------------------------------------------------------------
+int dnnca_model_set_ema(void* model, float decay, int warmup) {
+    MODEL(model);
+    DN_TRY(M->ema_refuse("dnnca_model_set_ema"));
+    if (!(decay == 0.f || (decay > 0.f && decay < 1.f))) { set_error("dnnca_model_set_ema: decay %g outside (0, 1) (0 switches it off)", (double)decay); return DNNCA_EINVAL; }
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    if (decay == 0.f) {
+        if (M->ema.e) HIP_TRY(hipFree(M->ema.e));
+        M->ema = Model::Ema{};
+        return DNNCA_OK;
+    }
+    if (!M->ema.e) HIP_TRY(hipMalloc((void**)&M->ema.e, (size_t)(M->nT + 4) * 4));
+    HIP_TRY(hipMemcpyAsync(M->ema.e, M->p, (size_t)M->nT * 4, hipMemcpyDeviceToDevice, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    M->ema.decay = decay;
+    M->ema.warmup = warmup != 0;
+    M->ema.num_updates = 0;
+    return DNNCA_OK;
+}
+
+static int ema_required(Model* M, const char* what) {
+    if (M->ema.e) return DNNCA_OK;
+    set_error("%s: no weight average (dnnca_model_set_ema)", what);
+    return DNNCA_ESTATE;
+}
+
+int dnnca_get_ema(void* model, float* flat, int64_t n, int64_t* num_updates) {
+    MODEL(model);
+    DN_TRY(ema_required(M, "dnnca_get_ema"));
+    if (flat) DN_TRY(copy_flat(M, M->ema.e, M->nT, nullptr, flat, n));
+    if (num_updates) *num_updates = M->ema.num_updates;
+    return DNNCA_OK;
+}
+
+int dnnca_set_ema_state(void* model, const float* flat, int64_t n, int64_t num_updates) {
+    MODEL(model);
+    DN_TRY(ema_required(M, "dnnca_set_ema_state"));
+    DN_TRY(M->ema_refuse("dnnca_set_ema_state"));
+    if (!flat || num_updates < 0) { set_error("dnnca_set_ema_state: null vector or negative num_updates"); return DNNCA_EINVAL; }
+    DN_TRY(copy_flat(M, M->ema.e, M->nT, flat, nullptr, n));
+    M->ema.num_updates = num_updates;
+    return DNNCA_OK;
+}
+
+int dnnca_ema_exchange(void* model) {
+    MODEL(model);
+    DN_TRY(ema_required(M, "dnnca_ema_exchange"));
+    M->cur_op = nullptr;
+    LAUNCH(M, "ema_exchange", 16.0 * M->nT, 0, g_ema_exchange(M->stream, (size_t)M->nT, M->p, M->ema.e));
+    M->ema.in_use = !M->ema.in_use;
     return DNNCA_OK;
 }
 
@@ -1705,6 +1789,7 @@ static int train_pass(Model* M, const float* x_dev, const float* y_dev, int batc
 static int train_step_impl(Model* M, const float* x_dev, const float* y_dev, int batch, float lr, const dnnca_loss_cfg* cfg,
                            dnnca_step_out* out, int row) {
     if (!cfg) { set_error("null loss cfg"); return DNNCA_EINVAL; }
+    DN_TRY(M->ema_refuse("train step"));
     DN_TRY(train_pass(M, x_dev, y_dev, batch, lr, *cfg, row));
     if (out) return read_out(M, M->world, out);      // after the all-reduce the loss slot holds the sum over ranks of the local means
     return DNNCA_OK;
@@ -1865,6 +1950,7 @@ static int staged_end(Model* M, int slot, int batch, bool is_eval) {
 int dnnca_train_step_staged(void* model, int slot, const float* x_dev, const float* y_dev, int batch, float lr,
                             const dnnca_loss_cfg* cfg) {
     MODEL(model);
+    DN_TRY(M->ema_refuse("dnnca_train_step_staged"));
     DN_TRY(staged_begin(M, slot, batch));
     DN_TRY(train_step_impl(M, x_dev, y_dev, batch, lr, cfg, nullptr, slot));
     return staged_end(M, slot, batch, false);
@@ -2113,7 +2199,17 @@ int dnnca_comm_collectives(void* model, int* count) {
 int dnnca_comm_broadcast_weights(void* model, int root) {
     MODEL(model);
     if (!M->comm) return DNNCA_OK;
-    struct { float* p; int64_t n; } bufs[4] = {{M->p, M->nT}, {M->state, M->nS}, {M->m, M->nT}, {M->v, M->nT}};
+    DN_TRY(M->ema_refuse("dnnca_comm_broadcast_weights"));
+    // ... and the weight average with its update count, when it is on (on every rank or on none)
+    struct { float* p; int64_t n; } bufs[5] = {{M->p, M->nT}, {M->state, M->nS}, {M->m, M->nT}, {M->v, M->nT}, {M->ema.e, M->ema.e ? M->nT : 0}};
+    if (M->ema.e) {
+        int64_t* cnt = reinterpret_cast<int64_t*>(M->conf_dev);
+        HIP_TRY(hipMemcpyAsync(cnt, &M->ema.num_updates, 8, hipMemcpyHostToDevice, M->stream));
+        ncclResult_t r = ncclBroadcast(cnt, cnt, 1, ncclInt64, root, M->comm, M->stream);
+        if (r != ncclSuccess) { set_error("ncclBroadcast: %s", ncclGetErrorString(r)); return DNNCA_ECOMM; }
+        HIP_TRY(hipMemcpyAsync(&M->ema.num_updates, cnt, 8, hipMemcpyDeviceToHost, M->stream));
+        HIP_TRY(hipStreamSynchronize(M->stream));
+    }
     for (auto& b : bufs) {
         if (b.n == 0) continue;
         ncclResult_t r = ncclBroadcast(b.p, b.p, (size_t)b.n, ncclFloat, root, M->comm, M->stream);

@@ -260,6 +260,21 @@ class StagingRing:
         return out
 
 
+class _AveragedWeights:
+    """`with dm.averaged_weights():` -- the averaged weights stand in for the raw ones inside the block (DeviceModel.exchange_ema)"""
+
+    def __init__(self, dm):
+        self.dm = dm
+
+    def __enter__(self):
+        self.dm.exchange_ema()
+        return self.dm
+
+    def __exit__(self, *exc):
+        self.dm.exchange_ema()
+        return False
+
+
 class DeviceModel:
     def __init__(self, arch, in_channels, height, width, max_batch, n_filters_first, n_downsample, rate=2, kernel_size=3,
                  conv_stride=1, bn=False, padding='valid', leaky_alpha=0.0, l2=0.0, reference_index=0, n_conv=2,
@@ -348,6 +363,34 @@ class DeviceModel:
 
     def set_adam(self, beta1=0.9, beta2=0.999, epsilon=1e-7):
         check(self.lib.dnnca_set_adam(self.handle, beta1, beta2, epsilon))
+
+    # ---- exponential moving average of the weights (dnnca_model_set_ema) ------------------------------------------
+    def set_ema(self, decay, warmup=True):
+        """decay in (0, 1): every later train step also moves a device-side average of the trainable variables towards the weights
+        it has just written (tf.train.ExponentialMovingAverage, with num_updates warm-up unless warmup=False); the average starts
+        as a copy of the weights.  decay 0 drops it: the model runs the launches it ran before"""
+        check(self.lib.dnnca_model_set_ema(self.handle, float(decay), int(bool(warmup))))
+
+    def get_ema(self):
+        """(the average as a flat float32 vector, num_updates); while averaged_weights() is active: the raw weights"""
+        out = np.empty(self.n_trainable, np.float32)
+        n = C.c_int64()
+        check(self.lib.dnnca_get_ema(self.handle, fptr(out), self.n_trainable, C.byref(n)))
+        return out, n.value
+
+    def set_ema_state(self, flat, num_updates):
+        flat = as_f32(flat).ravel()
+        check(self.lib.dnnca_set_ema_state(self.handle, fptr(flat), flat.size, int(num_updates)))
+
+    def exchange_ema(self):
+        """one launch on the model's stream that exchanges the contents of the weights and their average (exact; twice restores
+        both).  Until the second call every forward / eval_step / analysis call runs on the average, get_params returns it, and
+        train steps and set_params / set_opt_state are refused"""
+        check(self.lib.dnnca_ema_exchange(self.handle))
+
+    def averaged_weights(self):
+        """context manager: exchange_ema() on entry, and always again on exit"""
+        return _AveragedWeights(self)
 
     def named_params(self):
         """OrderedDict name -> ndarray (trainable and state variables)."""

@@ -108,6 +108,69 @@ def check_calibration(n_bins, temperatures):
     return int(n_bins), casewise.calibration_grid(temperatures)
 
 
+EMA_KEYS = ('decay', 'warmup', 'validate')
+WEIGHT_CHOICES = ('raw', 'ema')
+
+
+def check_ema(options):
+    """deploy_options.ema -> dict(decay, warmup, validate), or None without the key.  decay: finite, in (0, 1); warmup: the
+    num_updates warm-up of tf.train.ExponentialMovingAverage (default on); validate: 'ema' (default: validation inside train() and
+    early stopping read the averaged weights) or 'raw'.  Unknown keys and bad values are a ValueError"""
+    if options is None:
+        return None
+    if not isinstance(options, dict):
+        raise ValueError('deploy_options.ema must be a mapping of %s, got %r' % (', '.join(EMA_KEYS), options))
+    unknown = sorted(set(options) - set(EMA_KEYS))
+    if unknown:
+        raise ValueError('deploy_options.ema: unknown keys %s (known: %s)' % (unknown, ', '.join(EMA_KEYS)))
+    decay = options.get('decay', 0.999)
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not np.isfinite(decay) or not 0.0 < float(decay) < 1.0:
+        raise ValueError('deploy_options.ema.decay must be a finite number in (0, 1), got %r' % (decay,))
+    warmup = options.get('warmup', True)
+    if not isinstance(warmup, bool):
+        raise ValueError('deploy_options.ema.warmup must be true or false, got %r' % (warmup,))
+    validate = options.get('validate', 'ema')
+    if validate not in WEIGHT_CHOICES:
+        raise ValueError("deploy_options.ema.validate must be 'ema' or 'raw', got %r" % (validate,))
+    return dict(decay=float(decay), warmup=warmup, validate=validate)
+
+
+def check_weights(weights):
+    if weights not in WEIGHT_CHOICES:
+        raise ValueError("--weights must be 'raw' or 'ema', got %r" % (weights,))
+    return weights
+
+
+def select_ckpts(ckpts, min_interval=1, step_range=None):
+    """the checkpoints {step: path} (ascending) that `evaluate` visits: inside step_range and min_interval apart"""
+    lo, hi = (0, float('inf')) if step_range is None else step_range
+    out, previous = OrderedDict(), None
+    for step, path in ckpts.items():
+        if not lo <= step <= hi or (previous is not None and step - previous < min_interval):
+            continue
+        out[step] = path
+        previous = step
+    return out
+
+
+def list_ckpts(base_path, pattern='ckpt-{epoch}'):
+    """{step: path without extension}, ascending, of the complete checkpoints under base_path (TFKerasModel.get_ckpts without a model)"""
+    regex_pattern = fr'^{pattern}\.index$'.format(epoch=r'(\d+)')
+    files = [f for f in os.listdir(base_path) if re.match(regex_pattern, f)]
+    steps = [int(re.sub(regex_pattern, r'\1', f)) for f in files]
+    paths = [os.path.join(base_path, f[:-len('.index')]) for f in files]
+    return OrderedDict(sorted(zip(steps, paths), key=lambda x: x[0]))
+
+
+def check_ema_checkpoints(paths):
+    """--weights ema: every checkpoint that will be read must hold a weight average (`"ema"` in its index).  A ValueError that names
+    the first one that does not -- raised from the index files alone, before any data set is opened"""
+    for path in paths:
+        with open(path + '.index') as f:
+            if 'ema' not in json.load(f):
+                raise ValueError('--weights ema: checkpoint %s holds no weight average (it was trained without deploy_options.ema)' % path)
+
+
 def _csv_value(v):
     """one value of a train_log.csv line: %.8g, a list of them in brackets (a metric of several thresholds)"""
     if isinstance(v, (list, tuple)):
@@ -172,6 +235,8 @@ class TFKerasModel:
         self.train_metrics = train_mode == 'device'
         if self.train_metrics and any(region_metrics.is_region_spec(s) for s in deploy.get('metrics', [])):
             logging.warning('train_metrics: region-based metrics are not counted per train step (validation still runs them)')
+        # ema: {decay, warmup, validate} -- an exponential moving average of the weights, kept on the device by the Adam launches
+        self.ema = check_ema(deploy.pop('ema', None))
         if deploy.get('optimizer') != 'adam':
             raise NotImplementedError('only the reference\'s optimizer: adam is supported (engine.py:276-284)')
         self.learning_rate = 0.001          # engine.py:278
@@ -206,6 +271,7 @@ class TFKerasModel:
         self.device_model = self.model.build([per_rank] + self._input_shape, seed=0)
         self.device_model.set_adam(**self.adam)
         self._set_region_loss(self.device_model)
+        self._set_ema(self.device_model)
         self._join_ranks()
 
     def _set_region_loss(self, dm):
@@ -217,11 +283,17 @@ class TFKerasModel:
         if isinstance(self.loss, custom_losses.BoundaryCrossentropy):
             dm.set_boundary_loss(self.loss.boundary_cfg())
 
+    def _set_ema(self, dm):
+        """deploy_options.ema: the average starts as a copy of the weights; without the key no call is made"""
+        if self.ema is not None:
+            dm.set_ema(self.ema['decay'], self.ema['warmup'])
+
     def _join_ranks(self):
         if self.ctx.world > 1:
             self.device_model.comm_init(self.ctx.rank, self.ctx.world, distributed.exchange_unique_id(self.ctx, device.DeviceModel))
             distributed.cleanup(self.ctx)     # ncclCommInitRank returned: every rank has read the id file
-            # identical initial weights on every replica (MirroredStrategy mirrors rank 0's variables)
+            # identical initial weights on every replica (MirroredStrategy mirrors rank 0's variables); the weight average, which
+            # _set_ema has switched on by now, and its update count travel with them
             self.device_model.comm_broadcast_weights(0)
 
     def _ensure_capacity(self, per_rank_batch):
@@ -232,7 +304,10 @@ class TFKerasModel:
             return True
         if self.ctx.world > 1:
             return False      # the communicator belongs to the existing handle; _build sizes DP models up front
+        if getattr(self, '_averaged_in_use', False):
+            return False      # validation on the averaged weights: they live in this handle until the exchange back
         params, state, (m, v, it) = dm.get_params(), dm.get_state(), dm.get_opt_state()
+        average = dm.get_ema() if self.ema is not None else None
         try:
             bigger = self.model.build([per_rank_batch] + self._input_shape, seed=0)
         except Exception as e:           # out of HBM: keep the model we have
@@ -246,6 +321,9 @@ class TFKerasModel:
         bigger.set_opt_state(m, v, it)
         bigger.set_adam(**self.adam)
         self._set_region_loss(bigger)
+        if average is not None:
+            self._set_ema(bigger)
+            bigger.set_ema_state(*average)
         self.device_model = bigger
         return True
 
@@ -295,28 +373,47 @@ class TFKerasModel:
         if self.ctx.rank != 0:
             return self
         m, v, iterations = dm.get_opt_state()
+        # deploy_options.ema: the array `ema` and the index entry "ema" beside the raw weights (always written with the raw weights
+        # in place); without the option both files are what they were
+        more, more_index = {}, {}
+        if self.ema is not None:
+            average, num_updates = dm.get_ema()
+            more = dict(ema=average)
+            more_index = dict(ema=dict(decay=self.ema['decay'], warmup=self.ema['warmup'], num_updates=int(num_updates)))
         os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
         with open(path + '.data-00000-of-00001', 'wb') as f:
-            np.savez(f, params=dm.get_params(), state=dm.get_state(), adam_m=m, adam_v=v)
+            np.savez(f, params=dm.get_params(), state=dm.get_state(), adam_m=m, adam_v=v, **more)
         index = dict(format='dnnca-ckpt-1', step=int(self.current_step), iterations=int(iterations),
                      learning_rate=float(self.learning_rate),
-                     variables=[dict(name=n, shape=list(s), trainable=t, offset=o) for n, s, t, o in dm.param_infos()])
+                     variables=[dict(name=n, shape=list(s), trainable=t, offset=o) for n, s, t, o in dm.param_infos()], **more_index)
         with open(path + '.index', 'w') as f:      # written last: its presence marks a complete checkpoint
             json.dump(index, f)
         return self
 
-    def load(self, path):
+    def load(self, path, weights='raw'):
+        """weights='raw': the checkpoint as it was written; with deploy_options.ema the average and its update count come back too
+        (a checkpoint without one: the average restarts from the loaded weights, with a warning; an average in the file is ignored
+        without the option).  weights='ema': the file's averaged weights become the parameters (inference; needs no device average)"""
+        check_weights(weights)
         dm = self.device_model
         with open(path + '.index') as f:
             index = json.load(f)
         have = [(v['name'], tuple(v['shape']), v['trainable'], v['offset']) for v in index['variables']]
         if have != [(n, tuple(s), t, o) for n, s, t, o in dm.param_infos()]:
             raise ValueError(f'checkpoint {path} does not match the model (assert_existing_objects_matched)')
+        if weights == 'ema' and 'ema' not in index:
+            raise ValueError(f'checkpoint {path} holds no weight average (weights=\'ema\')')
         with np.load(path + '.data-00000-of-00001') as z:
-            dm.set_params(z['params'])
+            dm.set_params(z['ema' if weights == 'ema' else 'params'])
             if dm.n_state:
                 dm.set_state(z['state'])
             dm.set_opt_state(z['adam_m'], z['adam_v'], index['iterations'])
+            if self.ema is not None and weights == 'raw':
+                if 'ema' in index:
+                    dm.set_ema_state(z['ema'], index['ema']['num_updates'])
+                else:
+                    logging.warning('checkpoint %s holds no weight average: it restarts from the loaded weights', path)
+                    self._set_ema(dm)          # e <- p, num_updates = 0
         return self
 
     # ---- training (engine.py:80-137) -------------------------------------------------------------------------
@@ -451,7 +548,17 @@ class TFKerasModel:
                     self.save(os.path.join(save_path, 'checkpoints', self.ckpt_pattern.format(epoch=step)))
                 stop = False
                 if val_data is not None and step % save_freq == 0:
-                    val = self._evaluate(val_data, staged=feeder is not None)      # on the ring's evaluation slots
+                    if self.ema is not None and self.ema['validate'] == 'ema':
+                        # the exchange launches go on the model's stream, behind the step just read; val_* and early stopping
+                        # refer to the averaged weights, and the raw ones are back before the next step
+                        self._averaged_in_use = True          # (_ensure_capacity: this model cannot be replaced now)
+                        try:
+                            with dm.averaged_weights():
+                                val = self._evaluate(val_data, staged=feeder is not None)
+                        finally:
+                            self._averaged_in_use = False
+                    else:
+                        val = self._evaluate(val_data, staged=feeder is not None)      # on the ring's evaluation slots
                     extra.update({'val_' + k: v for k, v in val.items()})
                     if early_stop_steps is not None:
                         if val['loss'] < best_val:
@@ -635,8 +742,11 @@ class TFKerasModel:
              surface_min_area=0, surface_filter_size=5, surface_resize_factor=1.0, surface_max_samples=65536, tta='none',
              uncertainty_ds=None, uncertainty=False, uncertainty_thresholds=(0.5,), calibration_ds=None, calibration=False,
              calibration_bins=casewise.CALIBRATION_BINS, calibration_temperatures=None, temperature=None,
-             visualize_attribution=False, attribution_steps=None, attribution_baseline=None):
-        """exam_lesions (`evaluate --exam_lesions`): after every checkpoint's evaluation rank 0 also runs _exam_lesion_pass over
+             visualize_attribution=False, attribution_steps=None, attribution_baseline=None, weights='raw'):
+        """weights (`evaluate --weights ema`): every checkpoint is loaded with its averaged weights as the parameters (load(...,
+        weights='ema')); everything downstream reads that model unchanged.  Checkpoints without an average are an error that names
+        the first, raised before anything is evaluated.
+        exam_lesions (`evaluate --exam_lesions`): after every checkpoint's evaluation rank 0 also runs _exam_lesion_pass over
         exam_ds (batches (x, y, paths, sliceIDs), a data set of its own: viz_ds is not needed) and writes exam_lesion_results.csv,
         exam_lesion_cases.csv and exam_lesion_matches.csv under <export_path>/<tag>/; every other file is what it is without it.
         surface_distances (`evaluate --surface_distances`): likewise rank 0 runs _surface_pass over surface_ds (the same kind of data
@@ -675,6 +785,10 @@ class TFKerasModel:
         if attribution and not getattr(self.model, 'supports_sensitivity', True):
             raise NotImplementedError('--visualize_attribution is not implemented for model: %s (the input-gradient pass covers the '
                                       'U-Net models only)' % self.model_config['model'])
+        load_kw = {}
+        if check_weights(weights) == 'ema':
+            check_ema_checkpoints(select_ckpts(self.get_ckpts(os.path.join(save_path, 'checkpoints')), min_interval, step_range).values())
+            load_kw = dict(weights='ema')
         tta_mask = None if tta == tta_modes.NONE else tta_modes.mask_of(tta, *_element_shape(dataset)[1:3])
         self._build(dataset)
         if tta_mask is not None:
@@ -720,7 +834,7 @@ class TFKerasModel:
                 logging.warning(f'Ignored {ckpt_path_} due to min_interval:{min_interval}.')
                 continue
             previous_step = ckpt_step
-            self.load(ckpt_path_)
+            self.load(ckpt_path_, **load_kw)
             rows[ckpt_step] = self._evaluate(dataset, staged=True) if tta_mask is None and temperature is None else \
                 self._evaluate(dataset, staged=False, tta_mask=tta_mask, **more)
             if visualize:
@@ -1000,7 +1114,7 @@ class TFKerasModel:
 
     def annotate(self, dataset, save_path, output, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
                  max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
-                 temperature=None, lesion_features=False, feature_bins=None, feature_ring=None):
+                 temperature=None, lesion_features=False, feature_bins=None, feature_ring=None, weights='raw'):
         """`annotator predict`: the lesions of slices that have no label.  Loads checkpoint `step` of save_path (None: the latest);
         per batch (x, paths, sliceIDs) of `dataset` (make_dataset(..., include_meta=True, labels=False)) one forward whose
         probabilities stay on the device, then DeviceModel.lesion_table: threshold, filter_size x filter_size opening, components
@@ -1029,8 +1143,11 @@ class TFKerasModel:
         come from a second call); lesion_features.csv (one line per line of lesions.csv, in its order: outline, axes and per
         modality mean, deviation, extrema, percentiles and the contrast against the ring of feature_ring pixels around the
         lesion) and with link_slices exam_lesion_features.csv (one line per line of exam_lesions.csv, pooled from the parts'
-        integers) are written beside the other files, which are what they are without the flag."""
+        integers) are written beside the other files, which are what they are without the flag.
+        weights (`predict --weights ema`): the checkpoint's averaged weights become the parameters (load(..., weights='ema')); a
+        checkpoint without an average is an error that names it.  Every table and mask is then that of the averaged model."""
         check_uncertainty(uncertainty, tta)
+        check_weights(weights)
         temperature = check_temperature(temperature)
         feature_bins, feature_ring = casewise.check_features(lesion_features, feature_bins, feature_ring)
         if self.ctx.world > 1:
@@ -1044,7 +1161,11 @@ class TFKerasModel:
             step = max(ckpts)
         if step not in ckpts:
             raise ValueError(f'no checkpoint of step {step} under {save_path}/checkpoints (have {sorted(ckpts)})')
-        self.load(ckpts[step])
+        if weights == 'ema':
+            check_ema_checkpoints([ckpts[step]])
+            self.load(ckpts[step], weights='ema')
+        else:
+            self.load(ckpts[step])
         lesion_rows, slice_rows = [], []
         lesion_spread_rows, slice_spread_rows = [], []
         feature_rows, linked_features = [], []       # linked_features: beside `linked`, every slice's feature records per lesion

@@ -13,8 +13,11 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
              surface_distances=False, surface_threshold=(0.5,), surface_percentile=95.0, surface_min_area=0, surface_filter_size=5,
              surface_resize_factor=1.0, surface_max_samples=65536, tta='none', uncertainty=False, uncertainty_threshold=(0.5,),
              calibration=False, calibration_bins=15, calibration_temperatures=None, temperature=None, visualize_attribution=False,
-             attribution_steps=None, attribution_baseline=None):
+             attribution_steps=None, attribution_baseline=None, weights='raw'):
     engine.check_uncertainty(uncertainty, tta)       # before anything is read
+    if engine.check_weights(weights) == 'ema':       # likewise: the index of every checkpoint that will be evaluated
+        engine.check_ema_checkpoints(engine.select_ckpts(engine.list_ckpts(os.path.join(save_path, 'checkpoints')), min_interval,
+                                                         step_range).values())
     attribution = engine.check_attribution(visualize_attribution, attribution_steps, attribution_baseline, export_csv, export_images)
     scaled = engine.check_temperature(temperature)   # likewise; None without the flag and with --temperature 1
     if calibration:
@@ -47,6 +50,8 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
         more['temperature'] = scaled
     if attribution:                      # and those of --visualize_attribution only with the flag
         more.update(visualize_attribution=True, attribution_steps=attribution[0], attribution_baseline=attribution[1])
+    if weights == 'ema':                 # and the keyword of --weights only with the averaged weights
+        more['weights'] = 'ema'
     model = engine.TFKerasModel(config)
     return model.eval(ds, viz_ds=viz_ds, tag=tag, save_path=os.path.join(save_path), avoid_overwrite=avoid_overwrite,
                       export_path=export_path, export_images=export_images, export_csv=export_csv,

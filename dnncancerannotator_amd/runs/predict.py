@@ -13,8 +13,12 @@ from .train import make_dataset
 
 def predict(save_path, data_path, output, config=None, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
             max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
-            temperature=None, lesion_features=False, feature_bins=None, feature_ring=None):
+            temperature=None, lesion_features=False, feature_bins=None, feature_ring=None, weights='raw'):
     engine.check_uncertainty(uncertainty, tta)       # before anything is read
+    if engine.check_weights(weights) == 'ema':       # likewise: the index of the checkpoint that will be read
+        ckpts = engine.list_ckpts(os.path.join(save_path, 'checkpoints'))
+        if ckpts and (step is None or step in ckpts):          # (a missing checkpoint is annotate's error, as without the flag)
+            engine.check_ema_checkpoints([ckpts[max(ckpts) if step is None else step]])
     casewise.check_features(lesion_features, feature_bins, feature_ring)      # likewise
     scaled = engine.check_temperature(temperature)   # likewise; None without the flag and with --temperature 1
     if link_min_overlap < 1:
@@ -31,6 +35,8 @@ def predict(save_path, data_path, output, config=None, step=None, threshold=0.5,
         more['temperature'] = scaled
     if lesion_features:                  # and the keywords of --lesion_features only with the flag
         more.update(lesion_features=True, feature_bins=feature_bins, feature_ring=feature_ring)
+    if weights == 'ema':                 # and the keyword of --weights only with the averaged weights
+        more['weights'] = 'ema'
     model = engine.TFKerasModel(config)
     return model.annotate(ds, save_path=save_path, output=output, step=step, threshold=threshold, min_area=min_area,
                           filter_size=filter_size, resize_factor=resize_factor, max_lesions=max_lesions,

@@ -124,6 +124,29 @@ int dnnca_set_opt_state(void* model, const float* m, const float* v, int64_t n, 
 int dnnca_get_opt_state(void* model, float* m, float* v, int64_t n, int64_t* iterations);
 int dnnca_set_adam(void* model, float beta1, float beta2, float epsilon);
 
+/* Exponential moving average of the trainable variables (tf.train.ExponentialMovingAverage with num_updates): a float32 vector e of
+ * dnnca_num_trainable elements on the device; the BatchNorm moving statistics are averages already and stay what they are.
+ *   dnnca_model_set_ema    decay in (0, 1): allocates e, copies the weights into it and zeroes num_updates; decay == 0: frees it, and
+ *                          every launch is again the one a model without an average runs; anything else: DNNCA_EINVAL
+ * While it is on, the launch that applies Adam (pg_fold_adam_ema, g_adam_ema: 36 instead of 28 bytes per parameter) also moves e:
+ * the thread that stores weight i computes e_i <- e_i - om * (e_i - p_i) with the p_i it has just written and
+ * om = (float)(1 - d_n), d_n = min(decay, (1 + n) / (10 + n)) with warmup, d_n = decay without, formed in double for the n-th
+ * update since set_ema / set_ema_state (plan dumps never count).  One thread per element, no atomics, nothing crosses to the host;
+ * under data parallel every rank applies the same update to the same weights.
+ *   dnnca_get_ema          e to host `flat` (NULL: only the count) and num_updates; synchronises
+ *   dnnca_set_ema_state    `flat` into e and the count (checkpoint resume); synchronises
+ *   dnnca_ema_exchange     one launch (ema_exchange) that exchanges the CONTENTS of the weight vector and e, exactly; a second call
+ *                          restores both.  Every forward pass rebuilds its weight-derived operands from the weight vector, so all
+ *                          inference entry points then run on the average.  While the average is in the weight vector,
+ *                          dnnca_get_params returns it, dnnca_get_ema the raw weights, and dnnca_train_step*, dnnca_set_params,
+ *                          dnnca_set_opt_state, dnnca_set_ema_state, dnnca_comm_broadcast_weights and dnnca_model_set_ema return
+ *                          DNNCA_ESTATE.  Asynchronous: the launch goes on the model's stream.
+ * The last three return DNNCA_ESTATE while no average is set. */
+int dnnca_model_set_ema(void* model, float decay, int warmup);
+int dnnca_get_ema(void* model, float* flat, int64_t n, int64_t* num_updates);
+int dnnca_set_ema_state(void* model, const float* flat, int64_t n, int64_t num_updates);
+int dnnca_ema_exchange(void* model);
+
 /* ---- the hot path, host buffers ------------------------------------------------------------------------------ */
 /* UNetAnnotator.call (unet.py:279-282): probabilities [B,H,W,1]; logits = the tensor Keras caches as _keras_logits */
 int dnnca_forward(void* model, const float* x_nhwc, int batch, int training, float* prob_out, float* logit_out);
@@ -673,7 +696,8 @@ int dnnca_comm_world(void* model, int* rank, int* world);
 /* gradient all-reduce calls the last train step issued: 1, or several when a gradient vector above 1 MB was sent in buckets
  * (reverse layer order, second stream) while the backward pass was still running -- bit-identical to the single call */
 int dnnca_comm_collectives(void* model, int* count);
-int dnnca_comm_broadcast_weights(void* model, int root);   /* weights, BN statistics and Adam slots of `root` on every rank */
+/* weights, BN statistics and Adam slots of `root` on every rank; with a weight average (on every rank or on none) it and its count too */
+int dnnca_comm_broadcast_weights(void* model, int root);
 int dnnca_comm_average_state(void* model);          /* BN moving statistics: mean over ranks before a checkpoint */
 /* small host-side reductions (validation loss sums, metric counts: MirroredStrategy's metric aggregation); doubles, any length */
 int dnnca_comm_allreduce_host(void* model, double* values, int64_t n, int op /* 0 sum, 1 max */);
