@@ -44,6 +44,15 @@ class RegionLoss(C.Structure):                     # dnnca_region_loss
                 ('smooth', C.c_float)]
 
 
+class OptimizerCfg(C.Structure):                   # dnnca_optimizer_cfg
+    _fields_ = [('kind', C.c_int32), ('beta1', C.c_float), ('beta2', C.c_float), ('epsilon', C.c_float), ('momentum', C.c_float),
+                ('nesterov', C.c_int32), ('weight_decay', C.c_float), ('clipvalue', C.c_float), ('clipnorm', C.c_float),
+                ('global_clipnorm', C.c_float)]
+
+
+OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
+
+
 class StepOut(C.Structure):
     _fields_ = [('loss', C.c_float), ('positive_rate', C.c_float), ('weight', C.c_float),
                 ('label_min', C.c_float), ('label_max', C.c_float)]
@@ -184,6 +193,9 @@ SIGNATURES = {
     'dnnca_set_opt_state': (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int64]),
     'dnnca_get_opt_state': (C.c_int, [_VP, _FP, _FP, C.c_int64, C.POINTER(C.c_int64)]),
     'dnnca_set_adam': (C.c_int, [_VP, C.c_float, C.c_float, C.c_float]),
+    'dnnca_model_set_optimizer': (C.c_int, [_VP, C.POINTER(OptimizerCfg), C.POINTER(C.c_uint8), C.c_int]),
+    'dnnca_last_grad_norm': (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
+    'dnnca_apply_gradients': (C.c_int, [_VP, _FP, C.c_int64, C.c_float]),
     'dnnca_model_set_ema': (C.c_int, [_VP, C.c_float, C.c_int]),
     'dnnca_get_ema': (C.c_int, [_VP, _FP, C.c_int64, C.POINTER(C.c_int64)]),
     'dnnca_set_ema_state': (C.c_int, [_VP, _FP, C.c_int64, C.c_int64]),

@@ -2,6 +2,7 @@
 // They are the complete functional path (and the in-library cross-check of the tuned kernels); the hot configurations
 // are routed to kernels_direct.hip / kernels_mfma.hip by model.hip.
 #include "kernels.h"
+#include "optim.h"
 
 namespace dnnca {
 
@@ -587,17 +588,7 @@ void g_label_stats(hipStream_t s, size_t n, const float* y, double* scalars) {
     hipLaunchKernelGGL(k_label_stats, dim3(blocks), dim3(TB), 0, s, n, y, scalars);
 }
 
-__device__ __forceinline__ float loss_weight(const dnnca_loss_cfg cfg, double label_sum, double n_label) {
-    float w;
-    if (cfg.has_weight) {
-        w = cfg.weight;
-    } else {
-        float pr = (float)(label_sum / n_label);           // utils/losses.py:100
-        w = pr > 0.f ? 1.0f / pr : 1.0f;                   // utils/losses.py:27
-    }
-    return cfg.weight_mul * w + cfg.weight_add;            // utils/losses.py:29
-}
-
+// (loss_weight: optim.h -- the optimizer kernels of kernels_opt.hip write the step outputs with it too)
 __global__ void k_loss(size_t n, const float* __restrict__ logits, const float* __restrict__ y, const dnnca_loss_cfg cfg,
                        double n_label, double* __restrict__ scalars, float* __restrict__ dlogits, float* __restrict__ prob,
                        float grad_scale) {
@@ -685,14 +676,7 @@ void g_finalize_scalars(hipStream_t s, double* scalars, const dnnca_loss_cfg cfg
 }
 
 // ------------------------------------------------------------------------------------------------ Adam (Keras)
-// fin != nullptr: block 0 / thread 0 also turns the step's scalar block into the five step outputs (k_finalize_scalars' job;
-// single-replica steps only -- under data parallel the loss slot must be final before the all-reduce)
-struct AdamFinalize {
-    double* scalars;
-    dnnca_loss_cfg cfg;
-    double n_label, inv_batch_hw;
-    float* out5;
-};
+// fin.out5 != nullptr: block 0 / thread 0 also turns the step's scalar block into the five step outputs (AdamFinalize: optim.h)
 
 // EMA: the thread that stores p[i] also moves the weight average e[i] towards it (Model::ema), e <- e - om * (e - p), TensorFlow's
 // assign_moving_average form; a template parameter, so that the plain kernel is the code it was

@@ -2093,9 +2093,9 @@ int fast_finish_backward(Model* m) {
         m->step.head_pending.partials = nullptr;
     }
     // single-replica train step whose every gradient (and the loss) comes out of this launch: wait for optimizer_step and let the
-    // fold apply Adam as well (fast_fold_adam)
+    // fold apply Adam as well (fast_fold_adam).  A set optimizer (Model::opt) declines: its launches need the folded gradient
     if (extra && !m->comm && !m->dry && m->merged_launches() && m->desc.l2 == 0.f && pl.fold_outputs + h.C + 1 == m->nT &&
-        !m->sw.no_fold_adam) {
+        !m->sw.no_fold_adam && !m->opt.on) {
         m->step.fold_deferred = true;
         pl.pending_head = h;
         return DNNCA_OK;

@@ -12,6 +12,8 @@ typedef struct ncclComm* ncclComm_t;
 
 namespace dnnca {
 
+struct OptChunk;    // optim.h
+
 struct T {          // a tensor = data view + gradient view of identical geometry
     View d, g;
 };
@@ -209,6 +211,20 @@ struct Model {
     struct Ema { float* e = nullptr; float decay = 0.f; bool warmup = true; int64_t num_updates = 0; bool in_use = false; } ema;
     float ema_next_om();                 // counts one update (never in a dry plan run) and returns (float)(1 - d_n) for it
     int ema_refuse(const char* what);    // DNNCA_ESTATE while the averaged weights are in use, else DNNCA_OK
+    // configurable optimizer (dnnca_model_set_optimizer, optim.h).  on == false: plain Adam, no table, every launch is the one it
+    // was (pg_fold_adam / g_adam).  on: fast_finish_backward declines the deferred fold and optimizer_step runs
+    // [grad_sqnorm, grad_clip_scale,] opt_* on the chunk table.  One device allocation `table`: chunks [nchunks], var_first
+    // [nvars + 1], partials [nchunks] doubles, norms [1 + nvars] doubles (the global norm first), scales [nvars] floats.
+    // beta1 / beta2 / eps stay the model's own fields above, which dnnca_set_adam feeds too
+    struct Optim {
+        bool on = false;
+        dnnca_optimizer_cfg cfg{};
+        void* table = nullptr;
+        OptChunk* chunks = nullptr; int* var_first = nullptr; double* partials = nullptr; double* norms = nullptr; float* scales = nullptr;
+        int nchunks = 0, nvars = 0;
+        bool norm_clip() const { return on && (cfg.clipnorm > 0.f || cfg.global_clipnorm > 0.f); }
+    } opt;
+    int opt_launches(float lr, float lr_t, float gscale, float om);      // optimizer_step's launches while opt.on
     // What one step hands from launch to launch (and from forward() to loss_and_backward() to optimizer_step()).  forward() begins
     // a pass with `step = Step{}`, in front of fast_prepare: nothing of an earlier step, finished or stopped on an error, survives
     // it.  Every other write is a launch setting a hand-over or the launch it is meant for consuming it.  (The hand-overs inside a
@@ -376,7 +392,7 @@ struct Model {
     int alloc(void** ptr, size_t bytes);
     int forward(const float* x_dev, int B, bool training, const StepRequest& req = StepRequest());
     int loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cfg, bool backward);
-    int optimizer_step(float lr);
+    int optimizer_step(float lr, bool reduce = true);      // reduce == false: no all-reduce (dnnca_apply_gradients)
     int flush_profile();
 
     // launch accounting ------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 
 #include "fast.h"
 #include "kernels.h"
+#include "optim.h"
 #include "region.h"
 #include "region_loss.h"
 #include "boundary.h"
@@ -93,6 +94,7 @@ Model::~Model() {
     ig_release(this);
     for (void* a : allocs) (void)hipFree(a);
     if (ema.e) (void)hipFree(ema.e);
+    if (opt.table) (void)hipFree(opt.table);
     if (tta_io) (void)hipFree(tta_io);
     if (calib_ws) (void)hipFree(calib_ws);
     for (auto& r : recs) {
@@ -1418,10 +1420,47 @@ int Model::ema_refuse(const char* what) {
     return DNNCA_ESTATE;
 }
 
-int Model::optimizer_step(float lr) {
+// the launches of a set optimizer (Model::opt): the norm of the gradient the optimizer receives and the clip scales, when a clip by
+// norm is on, then the one pass that applies the update -- and, on a single replica, writes the step outputs
+int Model::opt_launches(float lr, float lr_t, float gscale, float om) {
+    const dnnca_optimizer_cfg& c = opt.cfg;
+    if (opt.norm_clip()) {
+        LAUNCH(this, "grad_sqnorm", 4.0 * nT, 3.0 * nT, g_grad_sqnorm(stream, opt.chunks, opt.nchunks, g, gscale, c.clipvalue, opt.partials));
+        LAUNCH(this, "grad_clip_scale", 16.0 * opt.nchunks, 2.0 * opt.nchunks,
+               g_grad_clip_scale(stream, opt.var_first, opt.nvars, opt.nchunks, opt.partials, c.clipnorm, c.global_clipnorm, opt.scales,
+                                 opt.norms));
+    }
+    OptArgs a{};
+    a.lr_t = lr_t;
+    a.lr = lr;
+    a.lrwd = (float)((double)lr * (double)c.weight_decay);
+    a.b1 = beta1; a.b2 = beta2; a.eps = eps;
+    a.momentum = c.momentum;
+    a.nesterov = c.nesterov;
+    a.gscale = gscale;
+    a.clipvalue = c.clipvalue;
+    a.scales = opt.norm_clip() ? opt.scales : nullptr;
+    a.om = om;
+    AdamFinalize fin{};
+    if (step.fin_pending.on) {
+        step.fin_pending.on = false;          // consumed: this launch writes the step outputs
+        fin = AdamFinalize{scalars, step.fin_pending.cfg, step.fin_pending.n_label, step.fin_pending.inv_batch_hw, out5};
+    }
+    // bytes per parameter: p and g read, p written, and the slots the kind touches (m, v read and written); the average adds 8
+    const bool sgd = c.kind == DNNCA_OPT_SGD;
+    const double per = (sgd ? (c.momentum == 0.f ? 12.0 : 20.0) : 28.0) + (ema.e ? 8.0 : 0.0);
+    const double fl = (sgd ? 4.0 : (c.kind == DNNCA_OPT_ADAMW ? 12.0 : 10.0)) + (ema.e ? 3.0 : 0.0);
+    static const char* const names[3][2] = {{"opt_adam", "opt_adam_ema"}, {"opt_adamw", "opt_adamw_ema"}, {"opt_sgd", "opt_sgd_ema"}};
+    LAUNCH(this, names[c.kind][ema.e ? 1 : 0], per * nT, fl * nT,
+           g_opt_step(stream, c.kind, opt.chunks, opt.nchunks, p, g, m, v, ema.e, a, fin));
+    return DNNCA_OK;
+}
+
+// reduce == false (dnnca_apply_gradients): the gradient vector is taken as it stands, without a communicator
+int Model::optimizer_step(float lr, bool reduce) {
     cur_op = nullptr;
     float gscale = 1.0f;
-    if (comm && !dry && step.bucketing) {
+    if (reduce && comm && !dry && step.bucketing) {
         // the backward pass has sent the finalised suffix in buckets; what is left -- the first layers and the step's loss in the
         // tail -- follows on the same (communication) stream, and Adam waits for all of it
         step.bucketing = false;
@@ -1430,7 +1469,7 @@ int Model::optimizer_step(float lr) {
         HIP_TRY(hipEventRecord(ev_comm_done, comm_stream));
         HIP_TRY(hipStreamWaitEvent(stream, ev_comm_done, 0));
         gscale = 1.0f / (float)world;
-    } else if (comm && !dry) {
+    } else if (reduce && comm && !dry) {
         // one all-reduce over [gradients ..., loss]: MirroredStrategy's cross-replica sum (engine.py:262) [TF-2.6]
         ncclResult_t r = ncclAllReduce(g, g, (size_t)nT + 1, ncclFloat, ncclSum, comm, stream);
         if (r != ncclSuccess) { set_error("ncclAllReduce: %s", ncclGetErrorString(r)); return DNNCA_ECOMM; }
@@ -1446,6 +1485,7 @@ int Model::optimizer_step(float lr) {
         return fast_fold_adam(this, lr_t, om, step.fin_pending.cfg, step.fin_pending.n_label, step.fin_pending.inv_batch_hw);
     }
     if (step.fold_deferred) { set_error("internal: deferred gradient fold without a single-replica optimizer step"); return DNNCA_ESTATE; }
+    if (opt.on) return opt_launches(lr, lr_t, gscale, om);
     if (step.fin_pending.on) {
         step.fin_pending.on = false;
         if (ema.e) {
@@ -1633,6 +1673,102 @@ int dnnca_set_adam(void* model, float beta1, float beta2, float epsilon) {
     M->beta2 = beta2;
     M->eps = epsilon;
     return DNNCA_OK;
+}
+
+// ---- configurable optimizers (Model::opt, optim.h) ----------------------------------------------------------------------------
+static int opt_bad(const char* what, double value, const char* want) {
+    set_error("dnnca_model_set_optimizer: %s %g: %s", what, value, want);
+    return DNNCA_EINVAL;
+}
+
+int dnnca_model_set_optimizer(void* model, const dnnca_optimizer_cfg* cfg, const uint8_t* decay_per_variable, int n_variables) {
+    MODEL(model);
+    DN_TRY(M->ema_refuse("dnnca_model_set_optimizer"));
+    if (!cfg) { set_error("dnnca_model_set_optimizer: null cfg"); return DNNCA_EINVAL; }
+    const dnnca_optimizer_cfg c = *cfg;
+    if (c.kind != DNNCA_OPT_ADAM && c.kind != DNNCA_OPT_ADAMW && c.kind != DNNCA_OPT_SGD) return opt_bad("kind", c.kind, "not one of DNNCA_OPT_ADAM / ADAMW / SGD");
+    const bool sgd = c.kind == DNNCA_OPT_SGD;
+    if (!sgd) {
+        if (!(c.beta1 >= 0.f && c.beta1 < 1.f)) return opt_bad("beta_1", c.beta1, "must lie in [0, 1)");
+        if (!(c.beta2 >= 0.f && c.beta2 < 1.f)) return opt_bad("beta_2", c.beta2, "must lie in [0, 1)");
+        if (!(c.epsilon >= 0.f && std::isfinite(c.epsilon))) return opt_bad("epsilon", c.epsilon, "must be finite and >= 0");
+    }
+    if (!(c.momentum >= 0.f && c.momentum < 1.f)) return opt_bad("momentum", c.momentum, "must lie in [0, 1)");
+    if (!(c.weight_decay >= 0.f && std::isfinite(c.weight_decay))) return opt_bad("weight_decay", c.weight_decay, "must be finite and >= 0");
+    if (c.nesterov != 0 && c.nesterov != 1) return opt_bad("nesterov", c.nesterov, "must be 0 or 1");
+    if (!sgd && (c.momentum != 0.f || c.nesterov)) return opt_bad("momentum", c.momentum, "momentum / nesterov belong to DNNCA_OPT_SGD");
+    if (c.kind != DNNCA_OPT_ADAMW && c.weight_decay != 0.f) return opt_bad("weight_decay", c.weight_decay, "belongs to DNNCA_OPT_ADAMW");
+    const struct { const char* name; float v; } clips[3] = {{"clipvalue", c.clipvalue}, {"clipnorm", c.clipnorm}, {"global_clipnorm", c.global_clipnorm}};
+    for (const auto& k : clips)
+        if (!(k.v >= 0.f && std::isfinite(k.v))) return opt_bad(k.name, k.v, "must be finite and > 0 (0: off)");
+    if (c.clipnorm > 0.f && c.global_clipnorm > 0.f) return opt_bad("clipnorm", c.clipnorm, "clipnorm and global_clipnorm exclude each other");
+    int nvars = 0;
+    for (const ParamInfo& pi : M->params) nvars += pi.trainable ? 1 : 0;
+    const bool plain = c.kind == DNNCA_OPT_ADAM && c.clipvalue == 0.f && c.clipnorm == 0.f && c.global_clipnorm == 0.f;
+    if (!plain && n_variables != nvars) return opt_bad("n_variables", n_variables, "is not the number of trainable variables");
+    if (c.kind == DNNCA_OPT_ADAMW && !decay_per_variable) { set_error("dnnca_model_set_optimizer: DNNCA_OPT_ADAMW without decay_per_variable"); return DNNCA_EINVAL; }
+    if (M->nT >= (int64_t)1 << 31) { set_error("dnnca_model_set_optimizer: %lld parameters do not fit the chunk table", (long long)M->nT); return DNNCA_EINVAL; }
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    if (!sgd) { M->beta1 = c.beta1; M->beta2 = c.beta2; M->eps = c.epsilon; }
+    if (M->opt.table) HIP_TRY(hipFree(M->opt.table));
+    M->opt = Model::Optim{};
+    if (plain) return DNNCA_OK;
+    // the chunk table: fixed-size chunks, none straddling a variable, each with its variable's index and decay flag
+    std::vector<OptChunk> chunks;
+    std::vector<int> var_first;
+    int v = 0;
+    for (const ParamInfo& pi : M->params) {
+        if (!pi.trainable) continue;
+        var_first.push_back((int)chunks.size());
+        const int decay = c.kind == DNNCA_OPT_ADAMW && decay_per_variable[v] ? 1 : 0;
+        for (int64_t lo = 0; lo < pi.size; lo += kOptChunk)
+            chunks.push_back(OptChunk{(int)(pi.offset + lo), (int)std::min<int64_t>(kOptChunk, pi.size - lo), v, decay});
+        ++v;
+    }
+    var_first.push_back((int)chunks.size());
+    Model::Optim& o = M->opt;
+    o.nchunks = (int)chunks.size();
+    o.nvars = nvars;
+    // doubles first (8-byte aligned), then the 16-byte chunks, then ints and floats
+    const size_t b_part = (size_t)o.nchunks * 8, b_norm = (size_t)(1 + nvars) * 8, b_chunk = (size_t)o.nchunks * sizeof(OptChunk);
+    const size_t b_first = (size_t)(nvars + 1) * 4, b_scale = (size_t)nvars * 4;
+    const size_t pad = (16 - (b_part + b_norm) % 16) % 16;
+    HIP_TRY(hipMalloc(&o.table, b_part + b_norm + pad + b_chunk + b_first + b_scale));
+    char* base = (char*)o.table;
+    o.partials = (double*)base;
+    o.norms = (double*)(base + b_part);
+    o.chunks = (OptChunk*)(base + b_part + b_norm + pad);
+    o.var_first = (int*)(base + b_part + b_norm + pad + b_chunk);
+    o.scales = (float*)(base + b_part + b_norm + pad + b_chunk + b_first);
+    HIP_TRY(hipMemsetAsync(o.table, 0, b_part + b_norm, M->stream));
+    HIP_TRY(hipMemcpyAsync(o.chunks, chunks.data(), b_chunk, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipMemcpyAsync(o.var_first, var_first.data(), b_first, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));          // the tables are locals
+    o.cfg = c;
+    o.on = true;
+    return DNNCA_OK;
+}
+
+int dnnca_last_grad_norm(void* model, double* global, double* per_variable, int n) {
+    MODEL(model);
+    if (!M->opt.norm_clip()) { set_error("dnnca_last_grad_norm: no clipping by norm is set (dnnca_model_set_optimizer)"); return DNNCA_ESTATE; }
+    if (n != 0 && n != M->opt.nvars) { set_error("dnnca_last_grad_norm: n %d is neither 0 nor the %d trainable variables", n, M->opt.nvars); return DNNCA_EINVAL; }
+    std::vector<double> h((size_t)1 + M->opt.nvars);
+    HIP_TRY(hipMemcpyAsync(h.data(), M->opt.norms, h.size() * 8, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    if (global) *global = h[0];
+    if (per_variable && n) memcpy(per_variable, h.data() + 1, (size_t)n * 8);
+    return DNNCA_OK;
+}
+
+int dnnca_apply_gradients(void* model, const float* g_host, int64_t n, float lr) {
+    MODEL(model);
+    DN_TRY(M->ema_refuse("dnnca_apply_gradients"));
+    if (!g_host || n != M->nT) { set_error("dnnca_apply_gradients: null vector or %lld elements for %lld trainable parameters", (long long)n, (long long)M->nT); return DNNCA_EINVAL; }
+    M->step = Model::Step{};          // no pass is under way: nothing is pending, nothing deferred
+    HIP_TRY(hipMemcpyAsync(M->g, g_host, (size_t)n * 4, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));          // the caller's vector may be reused at once
+    return M->optimizer_step(lr, false);
 }
 
 }  // extern "C"

@@ -364,6 +364,46 @@ class DeviceModel:
     def set_adam(self, beta1=0.9, beta2=0.999, epsilon=1e-7):
         check(self.lib.dnnca_set_adam(self.handle, beta1, beta2, epsilon))
 
+    # ---- configurable optimizers (dnnca_model_set_optimizer) -------------------------------------------------------
+    OPTIMIZER_KINDS = {'adam': _lib.OPT_ADAM, 'adamw': _lib.OPT_ADAMW, 'sgd': _lib.OPT_SGD}
+
+    def trainable_names(self):
+        """the names of the trainable variables, in the order the per-variable arrays of the optimizer use"""
+        return [name for name, _, trainable, _ in self.param_infos() if trainable]
+
+    def decay_mask(self, exclude=('bias', 'beta', 'gamma')):
+        """one flag per trainable variable: it takes AdamW's weight decay unless its name contains one of `exclude`"""
+        return np.array([not any(e in name for e in exclude) for name in self.trainable_names()], np.uint8)
+
+    def set_optimizer(self, kind='adam', beta1=0.9, beta2=0.999, epsilon=1e-7, momentum=0.0, nesterov=False, weight_decay=0.0,
+                      clipvalue=0.0, clipnorm=0.0, global_clipnorm=0.0, decay_mask=None):
+        """kind 'adam' | 'adamw' | 'sgd' with Keras' gradient transforms (0: off).  'adam' with nothing else stores the betas and
+        epsilon and leaves the model launching what it launched before; anything else makes the train step run pg_fold
+        [grad_sqnorm grad_clip_scale] opt_<kind>[_ema].  decay_mask: one flag per trainable variable ('adamw'; default decay_mask())"""
+        cfg = _lib.OptimizerCfg()
+        cfg.kind = self.OPTIMIZER_KINDS[kind]
+        cfg.beta1, cfg.beta2, cfg.epsilon = float(beta1), float(beta2), float(epsilon)
+        cfg.momentum, cfg.nesterov, cfg.weight_decay = float(momentum), int(bool(nesterov)), float(weight_decay)
+        cfg.clipvalue, cfg.clipnorm, cfg.global_clipnorm = float(clipvalue), float(clipnorm), float(global_clipnorm)
+        if decay_mask is None:
+            decay_mask = self.decay_mask()
+        mask = np.ascontiguousarray(decay_mask, np.uint8).ravel()
+        check(self.lib.dnnca_model_set_optimizer(self.handle, C.byref(cfg), mask.ctypes.data_as(C.POINTER(C.c_uint8)), mask.size))
+
+    def last_grad_norm(self):
+        """(global norm, per-variable norms) of the gradient the last optimizer step received, after clipvalue: float64, accumulated
+        in double on the device; needs clipnorm or global_clipnorm.  Waits for the stream"""
+        n = len(self.trainable_names())
+        total, per = C.c_double(), np.empty(n, np.float64)
+        check(self.lib.dnnca_last_grad_norm(self.handle, C.byref(total), per.ctypes.data_as(C.POINTER(C.c_double)), n))
+        return total.value, per
+
+    def apply_gradients(self, g, lr):
+        """Keras' optimizer.apply_gradients: the flat gradient vector g goes to the device and the optimizer's launches run on it
+        (no all-reduce, scale 1); counts one iteration"""
+        g = as_f32(g).ravel()
+        check(self.lib.dnnca_apply_gradients(self.handle, fptr(g), g.size, float(lr)))
+
     # ---- exponential moving average of the weights (dnnca_model_set_ema) ------------------------------------------
     def set_ema(self, decay, warmup=True):
         """decay in (0, 1): every later train step also moves a device-side average of the trainable variables towards the weights

@@ -135,6 +135,93 @@ def check_ema(options):
     return dict(decay=float(decay), warmup=warmup, validate=validate)
 
 
+# deploy_options.optimizer as a mapping: what Keras' optimizers.get takes in model.compile (engine.py:276-284) [TF-2.6]
+OPTIMIZER_KINDS = {'Adam': 'adam', 'AdamW': 'adamw', 'SGD': 'sgd'}
+_CLIP_KEYS = ('clipvalue', 'clipnorm', 'global_clipnorm')
+OPTIMIZER_KEYS = {
+    'Adam': ('learning_rate', 'beta_1', 'beta_2', 'epsilon', 'amsgrad') + _CLIP_KEYS,
+    'AdamW': ('learning_rate', 'weight_decay', 'exclude_from_weight_decay', 'beta_1', 'beta_2', 'epsilon', 'amsgrad') + _CLIP_KEYS,
+    'SGD': ('learning_rate', 'momentum', 'nesterov') + _CLIP_KEYS,
+}
+# Keras' defaults: Adam / AdamW start at 0.001, SGD at 0.01; AdamW decays by 0.004 [TF-2.6 / Keras 2.11 for AdamW]
+OPTIMIZER_DEFAULTS = dict(beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, momentum=0.0, nesterov=False, weight_decay=0.004,
+                          exclude_from_weight_decay=('bias', 'beta', 'gamma'), clipvalue=None, clipnorm=None, global_clipnorm=None)
+
+
+def _number(where, key, value, lo, hi=None, lo_open=False):
+    """a finite int / float (no bool, no string) in [lo, hi) -- or (lo, ...) with lo_open -- as a float, or a ValueError"""
+    ok = not isinstance(value, bool) and isinstance(value, (int, float)) and np.isfinite(value)
+    if ok:
+        ok = (value > lo if lo_open else value >= lo) and (hi is None or value < hi)
+    if not ok:
+        rng = '%s%g, %s' % ('(' if lo_open else '[', lo, 'inf)' if hi is None else '%g)' % hi)
+        raise ValueError('%s.%s must be a finite number in %s, got %r' % (where, key, rng, value))
+    return float(value)
+
+
+def check_optimizer(spec):
+    """deploy_options.optimizer -> None for the string 'adam' (the reference's compile call: nothing changes), else a dict
+    class_name, config (every key of the class with its value, as it goes into a checkpoint's index), learning_rate (the starting
+    value the LearningRateScheduler lambda receives), exclude (AdamW), and device (the keywords of DeviceModel.set_optimizer).
+    Accepted: the strings 'adamw' / 'sgd' (the class with its defaults) or {class_name: Adam | AdamW | SGD, config: {...}}.
+    Unknown classes, unknown keys, amsgrad, clipnorm together with global_clipnorm and bad values are a ValueError"""
+    if spec == 'adam':
+        return None
+    if isinstance(spec, str):
+        by_lower = {k.lower(): k for k in OPTIMIZER_KINDS}
+        if spec.lower() not in by_lower:
+            raise ValueError("deploy_options.optimizer: unknown optimizer %r (known: adam, adamw, sgd, or a mapping)" % (spec,))
+        spec = {'class_name': by_lower[spec.lower()], 'config': {}}
+    if not isinstance(spec, dict) or set(spec) - {'class_name', 'config'} or 'class_name' not in spec:
+        raise ValueError("deploy_options.optimizer must be 'adam' or a mapping {class_name, config}, got %r" % (spec,))
+    cls = spec['class_name']
+    if cls not in OPTIMIZER_KINDS:
+        raise ValueError('deploy_options.optimizer: unknown class_name %r (known: %s)' % (cls, ', '.join(OPTIMIZER_KINDS)))
+    given = spec.get('config') or {}
+    if not isinstance(given, dict):
+        raise ValueError('deploy_options.optimizer.config must be a mapping, got %r' % (given,))
+    unknown = sorted(set(given) - set(OPTIMIZER_KEYS[cls]))
+    if unknown:
+        raise ValueError('deploy_options.optimizer.config: unknown keys %s for %s (known: %s)' % (unknown, cls, ', '.join(OPTIMIZER_KEYS[cls])))
+    where = 'deploy_options.optimizer.config'
+    defaults = dict(OPTIMIZER_DEFAULTS, learning_rate=0.01 if cls == 'SGD' else 0.001)
+    cfg = {k: given.get(k, defaults[k]) for k in OPTIMIZER_KEYS[cls]}
+    cfg['learning_rate'] = _number(where, 'learning_rate', cfg['learning_rate'], 0.0)
+    dev = dict(kind=OPTIMIZER_KINDS[cls])
+    for k in _CLIP_KEYS:          # None: off, as in Keras
+        if cfg[k] is not None:
+            cfg[k] = _number(where, k, cfg[k], 0.0, lo_open=True)
+        dev[k] = cfg[k] or 0.0
+    if cfg['clipnorm'] is not None and cfg['global_clipnorm'] is not None:
+        raise ValueError('%s: clipnorm and global_clipnorm exclude each other (as in Keras)' % where)
+    if cls == 'SGD':
+        dev['momentum'] = cfg['momentum'] = _number(where, 'momentum', cfg['momentum'], 0.0, 1.0)
+        if not isinstance(cfg['nesterov'], bool):
+            raise ValueError('%s.nesterov must be true or false, got %r' % (where, cfg['nesterov']))
+        dev['nesterov'] = cfg['nesterov']
+    else:
+        dev['beta1'] = cfg['beta_1'] = _number(where, 'beta_1', cfg['beta_1'], 0.0, 1.0)
+        dev['beta2'] = cfg['beta_2'] = _number(where, 'beta_2', cfg['beta_2'], 0.0, 1.0)
+        dev['epsilon'] = cfg['epsilon'] = _number(where, 'epsilon', cfg['epsilon'], 0.0)
+        if not isinstance(cfg['amsgrad'], bool):
+            raise ValueError('%s.amsgrad must be true or false, got %r' % (where, cfg['amsgrad']))
+        if cfg['amsgrad']:
+            raise ValueError('%s.amsgrad: true is not supported (AMSGrad needs a third slot per weight)' % where)
+    exclude = ()
+    if cls == 'AdamW':
+        dev['weight_decay'] = cfg['weight_decay'] = _number(where, 'weight_decay', cfg['weight_decay'], 0.0)
+        exclude = cfg['exclude_from_weight_decay']
+        if isinstance(exclude, str) or not isinstance(exclude, (list, tuple)) or not all(isinstance(e, str) and e for e in exclude):
+            raise ValueError('%s.exclude_from_weight_decay must be a list of name fragments, got %r' % (where, exclude))
+        exclude = cfg['exclude_from_weight_decay'] = list(exclude)
+    return dict(class_name=cls, config=cfg, learning_rate=cfg['learning_rate'], exclude=tuple(exclude), device=dev)
+
+
+def slot_family(class_name):
+    """what a checkpoint's adam_m / adam_v arrays hold: Adam's two moments (Adam, AdamW), or SGD's accumulator and zeros"""
+    return 'sgd' if class_name == 'SGD' else 'adam'
+
+
 def check_weights(weights):
     if weights not in WEIGHT_CHOICES:
         raise ValueError("--weights must be 'raw' or 'ema', got %r" % (weights,))
@@ -237,10 +324,14 @@ class TFKerasModel:
             logging.warning('train_metrics: region-based metrics are not counted per train step (validation still runs them)')
         # ema: {decay, warmup, validate} -- an exponential moving average of the weights, kept on the device by the Adam launches
         self.ema = check_ema(deploy.pop('ema', None))
-        if deploy.get('optimizer') != 'adam':
-            raise NotImplementedError('only the reference\'s optimizer: adam is supported (engine.py:276-284)')
+        # optimizer: adam -- the reference's compile call (engine.py:276-284), unchanged; a mapping {class_name, config} or the
+        # strings adamw / sgd: the configurable optimizers with Keras' gradient clipping (check_optimizer)
+        self.optimizer = check_optimizer(deploy.get('optimizer'))
         self.learning_rate = 0.001          # engine.py:278
         self.adam = dict(beta1=0.9, beta2=0.999, epsilon=1e-7)
+        if self.optimizer is not None:
+            self.learning_rate = self.optimizer['learning_rate']
+            self.adam = {k: self.optimizer['device'].get(k, v) for k, v in self.adam.items()}
         return model
 
     def _build(self, dataset, max_batch=None, also=()):
@@ -270,6 +361,7 @@ class TFKerasModel:
         self._input_shape = list(shape[1:])
         self.device_model = self.model.build([per_rank] + self._input_shape, seed=0)
         self.device_model.set_adam(**self.adam)
+        self._set_optimizer(self.device_model)
         self._set_region_loss(self.device_model)
         self._set_ema(self.device_model)
         self._join_ranks()
@@ -282,6 +374,14 @@ class TFKerasModel:
             dm.set_region_loss(self.loss.region_cfg())
         if isinstance(self.loss, custom_losses.BoundaryCrossentropy):
             dm.set_boundary_loss(self.loss.boundary_cfg())
+
+    def _set_optimizer(self, dm):
+        """a mapping in deploy_options.optimizer: stored in the device model once (kind, betas, momentum, decay, clips and the decay
+        mask: every trainable variable whose name contains none of exclude_from_weight_decay); the string adam makes no call"""
+        if self.optimizer is not None:
+            names = [name for name, _, trainable, _ in dm.param_infos() if trainable]
+            mask = np.array([not any(e in name for e in self.optimizer['exclude']) for name in names], np.uint8)
+            dm.set_optimizer(decay_mask=mask, **self.optimizer['device'])
 
     def _set_ema(self, dm):
         """deploy_options.ema: the average starts as a copy of the weights; without the key no call is made"""
@@ -320,6 +420,7 @@ class TFKerasModel:
             bigger.set_state(state)
         bigger.set_opt_state(m, v, it)
         bigger.set_adam(**self.adam)
+        self._set_optimizer(bigger)
         self._set_region_loss(bigger)
         if average is not None:
             self._set_ema(bigger)
@@ -380,6 +481,10 @@ class TFKerasModel:
             average, num_updates = dm.get_ema()
             more = dict(ema=average)
             more_index = dict(ema=dict(decay=self.ema['decay'], warmup=self.ema['warmup'], num_updates=int(num_updates)))
+        # a mapping in deploy_options.optimizer: the index entry "optimizer" (class name and config).  The data file keeps its
+        # arrays: SGD's accumulator is adam_m, its adam_v zeros.  With the string adam both files are what they were
+        if self.optimizer is not None:
+            more_index['optimizer'] = dict(class_name=self.optimizer['class_name'], config=self.optimizer['config'])
         os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
         with open(path + '.data-00000-of-00001', 'wb') as f:
             np.savez(f, params=dm.get_params(), state=dm.get_state(), adam_m=m, adam_v=v, **more)
@@ -401,6 +506,11 @@ class TFKerasModel:
         have = [(v['name'], tuple(v['shape']), v['trainable'], v['offset']) for v in index['variables']]
         if have != [(n, tuple(s), t, o) for n, s, t, o in dm.param_infos()]:
             raise ValueError(f'checkpoint {path} does not match the model (assert_existing_objects_matched)')
+        # the slots of another family (Adam / AdamW <-> SGD) mean something else; a checkpoint without the entry was written by Adam
+        wrote = index.get('optimizer', {}).get('class_name', 'Adam')
+        mine = 'Adam' if self.optimizer is None else self.optimizer['class_name']
+        if slot_family(wrote) != slot_family(mine):
+            raise ValueError(f'checkpoint {path} holds the optimizer slots of {wrote}: they cannot resume {mine}')
         if weights == 'ema' and 'ema' not in index:
             raise ValueError(f'checkpoint {path} holds no weight average (weights=\'ema\')')
         with np.load(path + '.data-00000-of-00001') as z:

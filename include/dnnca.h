@@ -147,6 +147,50 @@ int dnnca_get_ema(void* model, float* flat, int64_t n, int64_t* num_updates);
 int dnnca_set_ema_state(void* model, const float* flat, int64_t n, int64_t num_updates);
 int dnnca_ema_exchange(void* model);
 
+/* ---- configurable optimizers: Adam, AdamW, SGD and gradient clipping (Keras 2.6 OptimizerV2 semantics [TF-2.6]) ---------------
+ * g is the vector the optimizer receives: the folded gradient with the kernel_regularizer term, under data parallel after the
+ * all-reduce and times 1 / world.  A "variable" is one trainable entry of dnnca_param_info, in that order.  Keras' order of the
+ * gradient transforms: clipvalue c (g_i <- min(max(g_i, -c), c)), then clipnorm c (per variable V: g_V <- g_V * c / max(|g_V|, c))
+ * or global_clipnorm c (the same with the norm over all of g).  The squares are summed in double in a fixed order (launches
+ * grad_sqnorm, grad_clip_scale: no atomics), the scale c / max(norm, c) is formed in double and rounded to float once -- exactly 1
+ * while norm <= c, so that such a gradient passes bit for bit -- and stays on the device: nothing synchronises with the host.
+ *   DNNCA_OPT_ADAM   today's update, lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) formed on the host in double (launch opt_adam;
+ *                    with every scale 1 bit-identical to g_adam)
+ *   DNNCA_OPT_ADAMW  the same behind the decoupled decay p <- p - lr * weight_decay * p of the variables whose decay flag is set,
+ *                    lr being this step's learning rate (Keras >= 2.11 / PyTorch; tfa.optimizers.AdamW leaves the lr factor out)
+ *   DNNCA_OPT_SGD    momentum 0: p <- p - lr g; else a <- momentum a - lr g, p <- p + a, with nesterov p <- p + momentum a - lr g.
+ *                    a lives in Adam's m slot (dnnca_get_opt_state), the v slot stays untouched, iterations counts as before
+ * With a weight average (dnnca_model_set_ema) the launches are opt_adam_ema / opt_adamw_ema / opt_sgd_ema and carry it.
+ *   dnnca_model_set_optimizer  a value of 0 switches its feature off.  kind ADAM with momentum, nesterov, weight_decay and the three
+ *                    clips 0 stores beta1 / beta2 / epsilon (as dnnca_set_adam does), frees the tables, and the model launches what
+ *                    it launched before (pg_fold_adam, g_adam).  Anything else builds a chunk table (fixed-size chunks, none across
+ *                    two variables) once; train steps then run pg_fold [grad_sqnorm grad_clip_scale] opt_*: the fold does not wait
+ *                    for the optimizer launch.  decay_per_variable: n_variables flags (kind ADAMW; may be NULL otherwise).
+ *                    DNNCA_EINVAL, with nothing changed: an unknown kind; beta1 / beta2 outside [0, 1), epsilon < 0, momentum
+ *                    outside [0, 1), weight_decay < 0, a clip < 0, or any of them not finite; clipnorm together with
+ *                    global_clipnorm; momentum / nesterov with a kind other than SGD, weight_decay with one other than ADAMW;
+ *                    n_variables other than the number of trainable variables.  DNNCA_ESTATE while the averaged weights are in
+ *                    use.  Waits for the stream.
+ *   dnnca_last_grad_norm  waits for the stream; *global = the norm over all of g (after clipvalue) of the last optimizer step,
+ *                    per_variable[0 .. n) = the variables' norms (either may be NULL; n = 0 or the number of trainable variables);
+ *                    zeros before the first step.  DNNCA_ESTATE when no clipping by norm is set
+ *   dnnca_apply_gradients  Keras' optimizer.apply_gradients: uploads g_host [n = dnnca_num_trainable] into the gradient vector and
+ *                    runs exactly the optimizer launches of a train step on it with learning rate lr (g_adam when no optimizer is
+ *                    set), without a communicator: no all-reduce, scale 1.  Counts one iteration.  g_host has been copied when the call
+ *                    returns; the launches go on the model's stream */
+enum { DNNCA_OPT_ADAM = 0, DNNCA_OPT_ADAMW = 1, DNNCA_OPT_SGD = 2 };
+typedef struct dnnca_optimizer_cfg {
+    int32_t kind;               /* DNNCA_OPT_* */
+    float beta1, beta2, epsilon;
+    float momentum;             /* SGD, in [0, 1) */
+    int32_t nesterov;           /* SGD with momentum > 0 */
+    float weight_decay;         /* ADAMW, >= 0 */
+    float clipvalue, clipnorm, global_clipnorm;      /* 0: off */
+} dnnca_optimizer_cfg;
+int dnnca_model_set_optimizer(void* model, const dnnca_optimizer_cfg* cfg, const uint8_t* decay_per_variable, int n_variables);
+int dnnca_last_grad_norm(void* model, double* global, double* per_variable, int n);
+int dnnca_apply_gradients(void* model, const float* g_host, int64_t n, float lr);
+
 /* ---- the hot path, host buffers ------------------------------------------------------------------------------ */
 /* UNetAnnotator.call (unet.py:279-282): probabilities [B,H,W,1]; logits = the tensor Keras caches as _keras_logits */
 int dnnca_forward(void* model, const float* x_nhwc, int batch, int training, float* prob_out, float* logit_out);
