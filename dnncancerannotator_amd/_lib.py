@@ -58,6 +58,9 @@ class StepOut(C.Structure):
                 ('label_min', C.c_float), ('label_max', C.c_float)]
 
 
+INTENSITY_WORDS = 32                               # uint32 words of a random_intensity record (include/dnnca.h)
+
+
 class AugParam(C.Structure):                       # dnnca_aug_param
     _fields_ = [('dy', C.c_int32), ('dx', C.c_int32), ('flip', C.c_int32), ('contrast', C.c_float)]
 
@@ -217,6 +220,7 @@ SIGNATURES = {
     'dnnca_warp_groups_f32': (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
                                         C.POINTER(C.c_double), C.POINTER(C.c_double), _VP, _VP]),
     'dnnca_affine_f32': (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), _VP, _VP]),
+    'dnnca_intensity_f32': (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), _VP]),
     'dnnca_augment_u8': (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(AugParam), C.c_int, C.c_int,
                                    _VP, _VP]),
     'dnnca_memcpy_d2h': (C.c_int, [_VP, _VP, C.c_size_t]),

@@ -9,8 +9,11 @@ and, from the overlays configs/additionals/intra_channelwarp_std{3,5,10,20}.yaml
     random_intrachannelwarp   a random_warp of its own for every channel group of the slice, label included (data.py:656-715)
 and, this project's own (configs/additionals/affine_augment.yaml, d4_augment.yaml; the reference has no rotation, zoom or D4 view),
     random_affine    rotation, zoom, shift and a flip / transpose of the plane about its centre, bilinear, zero outside
-All six run on the device (`dnnca_augment_u8`, `dnnca_affine_f32`, `dnnca_warp_f32`, `dnnca_warp_groups_f32`) in the fixed order
-crop, flip, contrast, affine, warp, intra-channel warp; this module draws their per-image
+    random_intensity gamma, smooth bias field, Gaussian blur and Gaussian / Rician noise, drawn per image AND feature channel
+                     (configs/additionals/intensity_augment.yaml)
+All seven run on the device (`dnnca_augment_u8`, `dnnca_affine_f32`, `dnnca_warp_f32`, `dnnca_warp_groups_f32`,
+`dnnca_intensity_f32`) in the fixed order crop, flip, contrast, affine, warp, intra-channel warp, intensity (noise added before a
+resampling would be smoothed away by it); this module draws their per-image
 parameters with a numpy generator (TensorFlow's own random streams cannot be reproduced without TensorFlow, so the draws are not
 bit-compatible with a TF run -- their distributions are the reference's) and solves the small spline systems of the warps.
 """
@@ -20,12 +23,15 @@ from collections import namedtuple
 
 import numpy as np
 
-AugmentPlan = namedtuple('AugmentPlan', ['crop', 'flip', 'contrast', 'warp', 'output_size', 'intrawarp', 'affine'], defaults=(None, None))
+AugmentPlan = namedtuple('AugmentPlan', ['crop', 'flip', 'contrast', 'warp', 'output_size', 'intrawarp', 'intensity', 'affine'],
+                         defaults=(None, None, None))
 # warp: (ctrl, wv) or None; intrawarp: (ctrl [B, G, n, 2], wv [B, G, n + 3, 2], group_of [Cs]: group of every raw-slice channel) or None
 # contrast_channels: the raw-slice channels random_contrast adjusts (target_channels), None: every feature channel
 # affine: float64 [B, 2, 3] from draw_affine (output pixel -> source position, rows (row, column)) or None
-RawBatch = namedtuple('RawBatch', ['raw', 'params', 'output_size', 'label_index', 'warp', 'intrawarp', 'contrast_channels', 'affine'],
-                      defaults=(None, None, None))
+# intensity: uint32 [B, C, 32] from draw_intensity (one record per image and feature channel) or None
+# (`affine` stays the last field of both tuples; build them with intensity= and affine= by keyword)
+RawBatch = namedtuple('RawBatch', ['raw', 'params', 'output_size', 'label_index', 'warp', 'intrawarp', 'contrast_channels', 'intensity',
+                                   'affine'], defaults=(None, None, None, None))
 
 
 def contrast_channels(plan, n_channels, label_index):
@@ -71,7 +77,7 @@ def raw_to_float(batch):
     return x, y
 
 
-_KNOWN = ('random_crop', 'random_flip', 'random_contrast', 'random_warp', 'random_intrachannelwarp', 'random_affine')
+_KNOWN = ('random_crop', 'random_flip', 'random_contrast', 'random_warp', 'random_intrachannelwarp', 'random_affine', 'random_intensity')
 AFFINE_SYMMETRIES = ('none', 'flips', 'd4')      # the names of the TTA modes (tta.MODES): what `--tta` averages over, train-time
 INTRAWARP_POINTS = 100          # data.py:706 passes n_points=100 to every group's random_warp, whatever the option says
 _warned = set()
@@ -81,7 +87,7 @@ def parse_augment_options(options, output_size):
     """data.py:538-551 + the defaults of train_ds (data.py:87-93).  options None -> {'random_crop': {}} like train_ds."""
     if options is None:
         options = {'random_crop': {}}
-    crop, flip, contrast, warp, intrawarp, affine = None, False, None, None, None, None
+    crop, flip, contrast, warp, intrawarp, affine, intensity = None, False, None, None, None, None, None
     for name, conf in options.items():
         conf = dict(conf or {})
         if name not in _KNOWN:
@@ -116,7 +122,9 @@ def parse_augment_options(options, output_size):
                                 '(annotator/data.py:706)', conf['n_points'], INTRAWARP_POINTS)
         elif name == 'random_affine':
             affine = _parse_affine(conf)
-    return AugmentPlan(crop, flip, contrast, warp, tuple(output_size), intrawarp, affine)
+        elif name == 'random_intensity':
+            intensity = _parse_intensity(conf)
+    return AugmentPlan(crop, flip, contrast, warp, tuple(output_size), intrawarp, intensity=intensity, affine=affine)
 
 
 def _parse_affine(conf):
@@ -145,6 +153,180 @@ def _parse_affine(conf):
     if symmetry not in AFFINE_SYMMETRIES:
         raise ValueError('random_affine: symmetry = %r is none of %s' % (symmetry, ', '.join(AFFINE_SYMMETRIES)))
     return dict(rotate_deg=rotate, scale=(lo, hi), shift=shift, symmetry=symmetry)
+
+
+INTENSITY_WORDS = 32            # uint32 words of one record of draw_intensity (include/dnnca.h: dnnca_intensity_f32)
+INTENSITY_GAMMA, INTENSITY_BIAS, INTENSITY_BLUR, INTENSITY_NOISE, INTENSITY_RICIAN = 1, 2, 4, 8, 16      # word 0
+INTENSITY_MAX_RADIUS = 8        # the halo the kernel stages: blur sigma <= 8 / 3
+INTENSITY_DISTRIBUTIONS = ('rician', 'gaussian')
+# the nine (i, j) of the bias polynomial sum a_ij P_i(u) P_j(v), 1 <= i + j <= 3, in the order of the record's words 2..10
+INTENSITY_BIAS_TERMS = ((1, 0), (0, 1), (2, 0), (1, 1), (0, 2), (3, 0), (2, 1), (1, 2), (0, 3))
+
+
+def _parse_intensity(conf):
+    """random_intensity's terms, checked: {'gamma': {range, prob}, 'bias_field': {strength, prob}, 'blur': {sigma, prob}, 'noise':
+    {sigma, prob, distribution}, 'target_channels'}.  A term that is absent, has prob 0 or can only draw the identity (gamma range
+    [1, 1], strength 0, no blur sigma, noise sigma [0, 0]) is None: it is off and takes no draw.  `prob` defaults to 1, a range may
+    be given as one number, `distribution` defaults to rician (magnitude MRI).  A bad value is a ValueError here."""
+    unknown = set(conf) - {'gamma', 'bias_field', 'blur', 'noise', 'target_channels'}
+    if unknown:
+        raise TypeError('random_intensity got unexpected options %s' % sorted(unknown))
+
+    def number(key, value):
+        if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not np.isfinite(value):
+            raise ValueError('random_intensity: %s = %r is not a finite number' % (key, value))
+        return float(value)
+
+    def pair(key, value):
+        if isinstance(value, (list, tuple)) and len(value) == 2:
+            lo, hi = number(key + '[0]', value[0]), number(key + '[1]', value[1])
+        elif isinstance(value, (list, tuple, str, bytes, dict)) or value is None:
+            raise ValueError('random_intensity: %s = %r is neither a number nor a pair [lo, hi]' % (key, value))
+        else:
+            lo = hi = number(key, value)
+        if lo > hi:
+            raise ValueError('random_intensity: %s = %r has lo > hi' % (key, value))
+        return lo, hi
+
+    def term(name, keys):
+        sub = conf.get(name)
+        if sub is None:
+            return None, 0.0
+        if not isinstance(sub, dict):
+            raise ValueError('random_intensity: %s = %r is not a mapping' % (name, sub))
+        unknown = set(sub) - set(keys) - {'prob'}
+        if unknown:
+            raise TypeError('random_intensity.%s got unexpected options %s' % (name, sorted(unknown)))
+        prob = number(name + '.prob', sub.get('prob', 1.0))
+        if not 0.0 <= prob <= 1.0:
+            raise ValueError('random_intensity: %s.prob = %r is outside [0, 1]' % (name, sub['prob']))
+        return sub, prob
+
+    out = dict(gamma=None, bias_field=None, blur=None, noise=None, target_channels=None)
+    sub, prob = term('gamma', ('range',))
+    if sub is not None:
+        lo, hi = pair('gamma.range', sub.get('range', (1.0, 1.0)))
+        if lo <= 0.0:
+            raise ValueError('random_intensity: gamma.range = %r does not satisfy 0 < lo' % (sub['range'],))
+        if prob > 0.0 and (lo, hi) != (1.0, 1.0):
+            out['gamma'] = dict(range=(lo, hi), prob=prob)
+    sub, prob = term('bias_field', ('strength',))
+    if sub is not None:
+        strength = number('bias_field.strength', sub.get('strength', 0.0))
+        if strength < 0.0:
+            raise ValueError('random_intensity: bias_field.strength = %r is negative' % (sub['strength'],))
+        if prob > 0.0 and strength > 0.0:
+            out['bias_field'] = dict(strength=strength, prob=prob)
+    sub, prob = term('blur', ('sigma',))
+    if sub is not None and 'sigma' in sub:
+        lo, hi = pair('blur.sigma', sub['sigma'])
+        if lo <= 0.0 or hi > INTENSITY_MAX_RADIUS / 3.0:
+            raise ValueError('random_intensity: blur.sigma = %r is outside (0, 8/3] (the radius ceil(3 sigma) is at most %d)'
+                             % (sub['sigma'], INTENSITY_MAX_RADIUS))
+        if prob > 0.0:
+            out['blur'] = dict(sigma=(lo, hi), prob=prob)
+    sub, prob = term('noise', ('sigma', 'distribution'))
+    if sub is not None:
+        lo, hi = pair('noise.sigma', sub.get('sigma', (0.0, 0.0)))
+        if lo < 0.0:
+            raise ValueError('random_intensity: noise.sigma = %r is negative' % (sub['sigma'],))
+        distribution = sub.get('distribution', INTENSITY_DISTRIBUTIONS[0])
+        if not isinstance(distribution, str) or distribution not in INTENSITY_DISTRIBUTIONS:
+            raise ValueError('random_intensity: noise.distribution = %r is none of %s' % (distribution, ', '.join(INTENSITY_DISTRIBUTIONS)))
+        if prob > 0.0 and hi > 0.0:
+            out['noise'] = dict(sigma=(lo, hi), prob=prob, distribution=distribution)
+    if conf.get('target_channels') is not None:
+        out['target_channels'] = tuple(conf['target_channels'])
+    return out
+
+
+def intensity_is_on(plan):
+    """whether random_intensity can change anything: the key is there and at least one of its terms is on"""
+    return plan is not None and plan.intensity is not None and any(plan.intensity[k] is not None for k in ('gamma', 'bias_field', 'blur', 'noise'))
+
+
+def intensity_channels(plan, n_channels, label_index):
+    """random_intensity's `target_channels`, raw-slice channels checked as contrast_channels() checks random_contrast's (an index
+    outside the `n_channels` raw channels, or the label's, is a ValueError), returned as the FEATURE channels draw_intensity takes
+    (the raw index less one behind the label).  None -- no random_intensity, or no `target_channels` -- is every feature channel."""
+    if plan is None or plan.intensity is None or plan.intensity.get('target_channels') is None:
+        return None
+    out = []
+    for c in plan.intensity['target_channels']:
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+            raise ValueError('random_intensity: target channel %r is not an integer' % (c,))
+        c = int(c)
+        if not 0 <= c < n_channels:
+            raise ValueError('random_intensity: target channel %d is outside the %d channels of the raw slice' % (c, n_channels))
+        if c == label_index:
+            raise ValueError('random_intensity: target channel %d is the label channel' % c)
+        out.append(c - (1 if label_index is not None and c > label_index else 0))
+    return tuple(out)
+
+
+def blur_taps(sigma):
+    """(R, float32 [9]): the radius ceil(3 sigma) and the taps w_k ~ exp(-k^2 / 2 sigma^2), k = 0..R, normalised in float64 so that
+    w_0 + 2 sum w_k = 1 and then rounded to float32; 0 beyond R"""
+    radius = min(int(np.ceil(3.0 * sigma)), INTENSITY_MAX_RADIUS)
+    e = np.exp(-np.arange(radius + 1, dtype=np.float64) ** 2 / (2.0 * sigma * sigma))
+    taps = np.zeros(INTENSITY_MAX_RADIUS + 1, np.float32)
+    taps[:radius + 1] = e / (e[0] + 2.0 * e[1:].sum())
+    return radius, taps
+
+
+def draw_intensity(rng, n, options, n_feature_channels, targets=None):
+    """random_intensity's draws for `n` images of `n_feature_channels` channels: uint32 [n, C, 32], one 128-byte record per image
+    and feature channel in the layout of include/dnnca.h (floats as their float32 bit patterns):
+        0 flags (1 gamma, 2 bias, 4 blur, 8 noise, 16 Rician) | 1 gamma | 2..10 bias a[9] | 11 blur radius R | 12..20 taps w[0..8]
+        | 21 noise sigma | 22, 23 Philox key | 24..31 zero
+    targets: the feature channels the option acts on (intensity_channels), None: all; any other channel gets an all-zero record and
+    takes no draw.  The order of the draws is part of the contract: images, then channels; within a channel gamma, bias, blur,
+    noise; within a term one uniform < prob decides whether it is active (only when 0 < prob < 1) and an active term then draws its
+    values (only where the range is not a point):
+        gamma  g = exp(U[ln lo, ln hi])
+        bias   a ~ U[-1, 1]^9, then t ~ U[0, strength]; a <- a t / sum|a|, so |f| <= sum|a| <= strength on the plane
+        blur   sigma ~ U[lo, hi] -> blur_taps
+        noise  sigma ~ U[lo, hi], then the key: two 32-bit words
+    A term that is off in `options` takes no draw at all, and a record with nothing active is all zero."""
+    rec = np.zeros((n, n_feature_channels, INTENSITY_WORDS), np.uint32)
+    fl = rec.view(np.float32)
+    gamma, bias, blur, noise = (options[k] for k in ('gamma', 'bias_field', 'blur', 'noise'))
+    channels = range(n_feature_channels) if targets is None else sorted(set(int(c) for c in targets))
+
+    def active(term):
+        return term is not None and (term['prob'] >= 1.0 or bool(rng.random() < term['prob']))
+
+    def ranged(lo, hi, log=False):
+        if not lo < hi:
+            return float(lo)
+        return float(np.exp(rng.uniform(np.log(lo), np.log(hi)))) if log else float(rng.uniform(lo, hi))
+
+    for b in range(n):
+        for c in channels:
+            flags = 0
+            if active(gamma):
+                flags |= INTENSITY_GAMMA
+                fl[b, c, 1] = ranged(*gamma['range'], log=True)
+            if active(bias):
+                flags |= INTENSITY_BIAS
+                a = rng.uniform(-1.0, 1.0, 9)
+                t = float(rng.uniform(0.0, bias['strength']))
+                norm = np.abs(a).sum()
+                a32 = (a * (t / norm) if norm > 0 else np.zeros(9)).astype(np.float32)
+                while np.abs(a32.astype(np.float64)).sum() > bias['strength']:      # float32 rounding must not lift the bound
+                    a32 = np.nextafter(a32, np.float32(0))
+                fl[b, c, 2:11] = a32
+            if active(blur):
+                flags |= INTENSITY_BLUR
+                radius, taps = blur_taps(ranged(*blur['sigma']))
+                rec[b, c, 11] = radius
+                fl[b, c, 12:21] = taps
+            if active(noise):
+                flags |= INTENSITY_NOISE | (INTENSITY_RICIAN if noise['distribution'] == 'rician' else 0)
+                fl[b, c, 21] = ranged(*noise['sigma'])
+                rec[b, c, 22:24] = rng.integers(0, 1 << 32, 2, dtype=np.uint64)
+            rec[b, c, 0] = flags
+    return rec
 
 
 def check_affine_size(plan, output_size):

@@ -7,7 +7,8 @@
 // in two launches over a uint8 batch that was uploaded as stored (a quarter of the float bytes over PCIe).  The random draws are
 // made by the host (augment.py) and passed per image, so the arithmetic is checkable against the oracle draw for draw.
 // random_warp (tfa.image.sparse_image_warp) follows below as dnnca_warp_f32, random_intrachannelwarp as dnnca_warp_groups_f32.
-// random_affine (this project's own: rotation, zoom, shift and D4 view in one bilinear resampling) closes the file as dnnca_affine_f32.
+// random_affine (this project's own: rotation, zoom, shift and D4 view in one bilinear resampling) is dnnca_affine_f32;
+// random_intensity (this project's own: gamma, bias field, blur and noise per image and channel) closes the file as dnnca_intensity_f32.
 #include <stdlib.h>
 #include <string.h>
 #include "fast.h"
@@ -586,5 +587,290 @@ int dnnca_affine_f32(void* model, const float* x_dev, const float* y_dev, int ba
         default: AFFINE_GO(32, 8); break;
     }
 #undef AFFINE_GO
+    return DNNCA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------- random_intensity
+// This project's own option (augment.py draw_intensity; the reference changes values only through random_contrast): what differs
+// between scanners and sessions, per image AND feature channel -- a gamma, a smooth multiplicative bias field, an in-plane Gaussian
+// blur and Gaussian or Rician noise.  The host draws one 128-byte record per (image, channel) (layout: include/dnnca.h); the device
+// never sees a probability or a sigma of the blur, only flags, coefficients, taps and a Philox key.  Per active plane, in float32:
+//   1. gamma   v <= 0 ? 0 : powf(v, g)
+//   2. bias    v * expf(f),  f = sum a_ij P_i(u) P_j(v) over 1 <= i + j <= 3, Legendre P on the pixel's own coordinates in [-1, 1]
+//   3. blur    rows, then columns, taps w[0..R]; a tap outside the image reads the nearest edge pixel (after steps 1 and 2)
+//   4. noise   Philox4x32-10(counter (row * W + col, 0, 0, 0), the record's key) -> Box-Muller -> v + s z0, or sqrt((v + s z0)^2 + (s z1)^2)
+//   5. clamp   to [0, 1]
+// A plane whose flags are 0 is copied bit for bit.  Every address is a function of the thread's coordinates alone (clamped to the
+// plane for the halo): nothing in a record or in the data moves one.  The label is not an argument.
+namespace dnnca {
+
+constexpr int INTENSITY_WORDS = 32, INTENSITY_RMAX = 8;
+constexpr unsigned INTENSITY_GAMMA = 1u, INTENSITY_BIAS = 2u, INTENSITY_BLUR = 4u, INTENSITY_NOISE = 8u, INTENSITY_RICIAN = 16u;
+constexpr unsigned INTENSITY_FLAGS = 31u;
+
+struct IntensityArgs {
+    const float* x;          // [B, H, W, C] source features
+    const unsigned* rec;     // [B, C, 32] records (device copy)
+    float* xo;
+    int B, H, W, C;
+};
+
+// Philox4x32-10 (Salmon et al., SC'11) on the counter (c0, 0, 0, 0): the first two of its four output words
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned k0, unsigned k1, unsigned& r0, unsigned& r1) {
+    unsigned c1 = 0u, c2 = 0u, c3 = 0u;
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned)p1;
+        c3 = (unsigned)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    r0 = c0;
+    r1 = c1;
+}
+
+// coordinate i of a size-n axis on [-1, 1] (0 where the axis has one point)
+__device__ __forceinline__ float intensity_coord(int i, int n) {
+#pragma clang fp contract(off)
+    const float d = (float)(n - 1);
+    return n > 1 ? ((float)i * 2.0f - d) / d : 0.0f;
+}
+
+// steps 1 and 2 on the pixel (row, col) of a plane with record r.  No contraction: the two instantiations of k_intensity, and the
+// halo pixels of neighbouring tiles, must give the same bits for the same pixel.
+__device__ __forceinline__ float intensity_point(float v, unsigned flags, const unsigned* __restrict__ r, int row, int col, int H, int W) {
+#pragma clang fp contract(off)
+    if (flags & INTENSITY_GAMMA) v = v <= 0.0f ? 0.0f : powf(v, __uint_as_float(r[1]));
+    if (flags & INTENSITY_BIAS) {
+        const float u = intensity_coord(row, H), t = intensity_coord(col, W);
+        const float u2 = 1.5f * u * u - 0.5f, u3 = (2.5f * u * u - 1.5f) * u;
+        const float t2 = 1.5f * t * t - 0.5f, t3 = (2.5f * t * t - 1.5f) * t;
+        float f = __uint_as_float(r[2]) * u;
+        f += __uint_as_float(r[3]) * t;
+        f += __uint_as_float(r[4]) * u2;
+        f += __uint_as_float(r[5]) * (u * t);
+        f += __uint_as_float(r[6]) * t2;
+        f += __uint_as_float(r[7]) * u3;
+        f += __uint_as_float(r[8]) * (u2 * t);
+        f += __uint_as_float(r[9]) * (u * t2);
+        f += __uint_as_float(r[10]) * t3;
+        v = v * expf(f);
+    }
+    return v;
+}
+
+// steps 4 and 5
+__device__ __forceinline__ float intensity_finish(float v, unsigned flags, const unsigned* __restrict__ r, unsigned index) {
+#pragma clang fp contract(off)
+    if (flags & INTENSITY_NOISE) {
+        unsigned r0, r1;
+        philox4x32_10(index, r[22], r[23], r0, r1);
+        const float u1 = (float)((r0 >> 9) + 1u) * 0x1p-23f;          // (0, 1], exact
+        const float a2 = (float)(r1 >> 8) * 0x1p-23f;                  // 2 u2 in [0, 2), exact
+        const float sigma = __uint_as_float(r[21]);
+        const float rad = sqrtf(-2.0f * logf(u1));
+        v = v + sigma * (rad * cospif(a2));
+        if (flags & INTENSITY_RICIAN) {
+            const float q = sigma * (rad * sinpif(a2));
+            v = sqrtf(v * v + q * q);
+        }
+    }
+    return fminf(fmaxf(v, 0.0f), 1.0f);
+}
+
+// grid (ceil(W / TX), ceil(H / TY), B), TX * TY threads, one thread = one output pixel, the channels in a loop (as k_affine).
+// HALO false: no record of the batch blurs -- no LDS, no barrier.
+// HALO true:  a blurred plane (a block-uniform property: the record belongs to blockIdx.z and the channel) is staged with a halo of
+//   R pixels, after steps 1 and 2, as one float plane of row stride TX + 16, filtered along the rows into a second plane of row
+//   stride TX and along the columns from there.  One plane at a time keeps the LDS independent of C (at most 15 KB, the 32 x 32
+//   tile) and makes every pass read consecutive dwords with consecutive lanes.  By the bank rule of 4-byte LDS accesses (bank
+//   (a / 4) % 32, lanes conflict within a 32-lane half of the wave): the column pass and the write of the row pass are linear in
+//   the thread index -- no conflict at any TX; the row pass reads one staged row per half-wave when TX >= 32 -- no conflict -- and
+//   two rows of 16 when TX = 16, which lie 32 dwords apart (stride 16 + 16) on the same banks: 2-way, the one tile that pays; the
+//   staging write is linear where R = 8 and skips 16 - 2 R dwords at a row's end otherwise (2-way for the lanes behind the skip).
+//   An interleaved [pixel][C] plane would have had odd lane strides (C = 3, 5: conflict-free too) but an LDS size that grows
+//   with C.  Planes without blur take the pointwise route of the other instantiation, statement for statement.
+template <int TX, int TY, bool HALO>
+__global__ __launch_bounds__(TX * TY) void k_intensity(IntensityArgs p) {
+    constexpr int NT = TX * TY, SW = TX + 2 * INTENSITY_RMAX, SH = TY + 2 * INTENSITY_RMAX;
+    __shared__ float s_in[HALO ? SH * SW : 1];
+    __shared__ float s_row[HALO ? SH * TX : 1];
+    const int tx = (int)(threadIdx.x % TX), ty = (int)(threadIdx.x / TX);
+    const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY, b = blockIdx.z;
+    const int qx = x0 + tx, qy = y0 + ty;
+    const bool inside = qx < p.W && qy < p.H;
+    if (!HALO && !inside) return;
+    const size_t img = (size_t)b * p.H * p.W;
+    const size_t oq = img + (size_t)qy * p.W + qx;                     // formed for every thread, used by the inside ones
+    const unsigned index = (unsigned)qy * (unsigned)p.W + (unsigned)qx;
+    for (int c = 0; c < p.C; ++c) {
+        const unsigned* __restrict__ r = p.rec + ((size_t)b * p.C + c) * INTENSITY_WORDS;
+        const unsigned flags = r[0];
+        float v;
+        if (HALO && (flags & INTENSITY_BLUR)) {
+            const int R = (int)min(r[11], (unsigned)INTENSITY_RMAX);      // (the host refuses more)
+            const int sw = TX + 2 * R, sh = TY + 2 * R;
+            __syncthreads();                                            // the passes of the channel before this one are over
+            for (int i = threadIdx.x; i < sh * sw; i += NT) {
+                const int ry = i / sw, rx = i - ry * sw;
+                const int gy = min(max(y0 - R + ry, 0), p.H - 1), gx = min(max(x0 - R + rx, 0), p.W - 1);      // nearest edge pixel
+                const float s = p.x[(img + (size_t)gy * p.W + gx) * p.C + c];
+                s_in[ry * SW + rx] = intensity_point(s, flags, r, gy, gx, p.H, p.W);
+            }
+            __syncthreads();
+            for (int i = threadIdx.x; i < sh * TX; i += NT) {
+                const int ry = i / TX, rx = i - ry * TX;
+                const float* s = s_in + ry * SW + rx + R;
+                float acc = __uint_as_float(r[12]) * s[0];
+                for (int k = 1; k <= R; ++k) acc = fmaf(__uint_as_float(r[12 + k]), s[-k] + s[k], acc);
+                s_row[ry * TX + rx] = acc;
+            }
+            __syncthreads();
+            const float* s = s_row + (ty + R) * TX + tx;
+            v = __uint_as_float(r[12]) * s[0];
+            for (int k = 1; k <= R; ++k) v = fmaf(__uint_as_float(r[12 + k]), s[-k * TX] + s[k * TX], v);
+            if (!inside) continue;
+        } else {
+            if (!inside) continue;
+            v = p.x[oq * p.C + c];
+            if (flags == 0u) {                                          // nothing drawn, or not a target channel: the bits as they are
+                p.xo[oq * p.C + c] = v;
+                continue;
+            }
+            v = intensity_point(v, flags, r, qy, qx, p.H, p.W);
+        }
+        p.xo[oq * p.C + c] = intensity_finish(v, flags, r, index);
+    }
+}
+
+static bool intensity_finite(unsigned bits) { return (bits & 0x7F800000u) != 0x7F800000u; }
+
+}  // namespace dnnca
+
+int dnnca_intensity_f32(void* model, const float* x_dev, int batch, int h, int w, int c, const unsigned* rec_host, float* x_out_dev) {
+    Model* M = reinterpret_cast<Model*>(model);
+    if (!M) { set_error("dnnca_intensity_f32: null model"); return DNNCA_EINVAL; }
+    if (!x_dev || !rec_host || !x_out_dev) {
+        set_error("dnnca_intensity_f32: null pointer");
+        return DNNCA_EINVAL;
+    }
+    if (batch < 1 || batch > 65535 || h < 1 || w < 1 || c < 1 || (unsigned long long)h * (unsigned long long)w > 0xFFFFFFFFull) {
+        set_error("dnnca_intensity_f32: bad shape (batch %d in 1..65535, %d x %d x %d, each >= 1, h * w < 2^32)", batch, h, w, c);
+        return DNNCA_EINVAL;
+    }
+    const size_t nx = (size_t)batch * h * w * c * 4;
+    if (affine_overlap(x_out_dev, nx, x_dev, nx)) {
+        set_error("dnnca_intensity_f32: the output must not alias the input");
+        return DNNCA_EINVAL;
+    }
+    bool any_blur = false;
+    for (int i = 0; i < batch * c; ++i) {
+        const unsigned* r = rec_host + (size_t)i * INTENSITY_WORDS;
+        auto f = [&](int k) { float v; memcpy(&v, r + k, 4); return v; };
+        const int b = i / c, ch = i % c;
+        if (r[0] & ~INTENSITY_FLAGS) {
+            set_error("dnnca_intensity_f32: record (%d, %d) has unknown flag bits 0x%x", b, ch, r[0]);
+            return DNNCA_EINVAL;
+        }
+        for (int k = 1; k <= 21; ++k)
+            if (k != 11 && !intensity_finite(r[k])) {
+                set_error("dnnca_intensity_f32: word %d of record (%d, %d) is not a finite float", k, b, ch);
+                return DNNCA_EINVAL;
+            }
+        for (int k = 24; k < INTENSITY_WORDS; ++k)
+            if (r[k]) {
+                set_error("dnnca_intensity_f32: reserved word %d of record (%d, %d) is not 0", k, b, ch);
+                return DNNCA_EINVAL;
+            }
+        if ((r[0] & INTENSITY_GAMMA) && !(f(1) > 0.0f)) {
+            set_error("dnnca_intensity_f32: gamma %g of record (%d, %d) is not positive", (double)f(1), b, ch);
+            return DNNCA_EINVAL;
+        }
+        if (r[11] > (unsigned)INTENSITY_RMAX) {
+            set_error("dnnca_intensity_f32: blur radius %u of record (%d, %d) is above %d", r[11], b, ch, INTENSITY_RMAX);
+            return DNNCA_EINVAL;
+        }
+        double sum = f(12);
+        for (int k = 0; k <= INTENSITY_RMAX; ++k) {
+            if (f(12 + k) < 0.0f) {
+                set_error("dnnca_intensity_f32: tap %d of record (%d, %d) is negative", k, b, ch);
+                return DNNCA_EINVAL;
+            }
+            if (k) sum += 2.0 * f(12 + k);
+        }
+        if ((r[0] & INTENSITY_BLUR) && !(sum - 1.0 <= 1e-5 && 1.0 - sum <= 1e-5)) {
+            set_error("dnnca_intensity_f32: the taps of record (%d, %d) sum to %.9g, not 1", b, ch, sum);
+            return DNNCA_EINVAL;
+        }
+        if (f(21) < 0.0f) {
+            set_error("dnnca_intensity_f32: noise sigma %g of record (%d, %d) is negative", (double)f(21), b, ch);
+            return DNNCA_EINVAL;
+        }
+        any_blur = any_blur || (r[0] & INTENSITY_BLUR);
+    }
+    // DNNCA_INTENSITY_TILE (tuning aid, read per call: tools/intensity_rate.py walks it): the W x H tile of output pixels a block owns.
+    // 32 x 8 is the shipped one: at 8 x 512 x 512 x 3 it is the fastest or within the spread of the fastest on a copy, on pointwise
+    // terms, on noise and on intensity_augment.yaml's draws; 32 x 16 is 20 % faster only where every plane blurs at R = 8 (its
+    // halo is 3 x the tile, not 4.5 x) and 2 % slower on the overlay's draws (profiles/intensity_rate.txt)
+    static const char* const kTiles[] = {"32x8", "16x16", "64x4", "32x16", "32x32"};
+    int tile = 0;
+    if (const char* name = getenv("DNNCA_INTENSITY_TILE")) {
+        tile = -1;
+        for (int i = 0; i < 5; ++i)
+            if (!strcmp(name, kTiles[i])) tile = i;
+        if (tile < 0) {
+            set_error("dnnca_intensity_f32: DNNCA_INTENSITY_TILE=%s is none of 32x8, 16x16, 64x4, 32x16, 32x32", name);
+            return DNNCA_EINVAL;
+        }
+    }
+    // one device row and a ring of pinned rows, as dnnca_affine_f32: the caller's records are free when this call returns and the
+    // call does not wait for the stream.  Rows are sized for max_batch, so a ragged last batch does not grow them.
+    const size_t bytes_in = (size_t)batch * c * INTENSITY_WORDS * 4;
+    const size_t row = (size_t)M->desc.max_batch > (size_t)batch ? (size_t)M->desc.max_batch * c * INTENSITY_WORDS * 4 : bytes_in;
+    if (row > M->intensity_scratch_bytes) {
+        void* p = nullptr;
+        DN_TRY(M->alloc(&p, row));
+        M->intensity_scratch = p;
+        M->intensity_scratch_bytes = row;
+    }
+    if (row > M->intensity_pin_bytes) {
+        HIP_TRY(hipStreamSynchronize(M->stream));         // uploads from the old rows are complete
+        if (M->intensity_pin) (void)hipHostFree(M->intensity_pin);
+        M->intensity_pin = nullptr;
+        M->intensity_pin_bytes = 0;
+        HIP_TRY(hipHostMalloc(&M->intensity_pin, row * Model::kAugRing, hipHostMallocDefault));
+        M->intensity_pin_bytes = row;
+    }
+    const int k = M->intensity_k;
+    M->intensity_k = (k + 1) % Model::kAugRing;
+    if (!M->intensity_ev[k]) HIP_TRY(hipEventCreateWithFlags(&M->intensity_ev[k], hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(M->intensity_ev[k]));
+    char* pin = (char*)M->intensity_pin + (size_t)k * M->intensity_pin_bytes;
+    memcpy(pin, rec_host, bytes_in);
+    HIP_TRY(hipMemcpyAsync(M->intensity_scratch, pin, bytes_in, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipEventRecord(M->intensity_ev[k], M->stream));
+    IntensityArgs a{};
+    a.x = x_dev; a.xo = x_out_dev;
+    a.rec = (const unsigned*)M->intensity_scratch;
+    a.B = batch; a.H = h; a.W = w; a.C = c;
+    const double bytes = (double)batch * h * w * c * 8.0;
+#define INTENSITY_GO(TX, TY)                                                                                                    \
+    do {                                                                                                                        \
+        const dim3 grid((w + TX - 1) / TX, (h + TY - 1) / TY, batch);                                                           \
+        if (any_blur) LAUNCH(M, "aug_intensity", bytes, 0, hipLaunchKernelGGL((k_intensity<TX, TY, true>), grid, dim3(TX * TY), 0, M->stream, a)); \
+        else LAUNCH(M, "aug_intensity", bytes, 0, hipLaunchKernelGGL((k_intensity<TX, TY, false>), grid, dim3(TX * TY), 0, M->stream, a)); \
+    } while (0)
+    switch (tile) {
+        case 1: INTENSITY_GO(16, 16); break;
+        case 2: INTENSITY_GO(64, 4); break;
+        case 3: INTENSITY_GO(32, 16); break;
+        case 4: INTENSITY_GO(32, 32); break;
+        default: INTENSITY_GO(32, 8); break;
+    }
+#undef INTENSITY_GO
     return DNNCA_OK;
 }

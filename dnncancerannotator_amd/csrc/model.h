@@ -183,6 +183,13 @@ struct Model {
     size_t affine_pin_bytes = 0;
     hipEvent_t affine_ev[kAugRing] = {nullptr, nullptr, nullptr, nullptr};
     int affine_k = 0;
+    // dnnca_intensity_f32: the [batch, c, 32] records of random_intensity -- one device row and a pinned ring of the same rows (as aug_pin)
+    void* intensity_scratch = nullptr;
+    size_t intensity_scratch_bytes = 0;
+    void* intensity_pin = nullptr;       // kAugRing x intensity_pin_bytes, pinned
+    size_t intensity_pin_bytes = 0;
+    hipEvent_t intensity_ev[kAugRing] = {nullptr, nullptr, nullptr, nullptr};
+    int intensity_k = 0;
     float* first_slabs = nullptr;        // bucket copies of the first-layer weight gradient (kernels_first.hip; kept zeroed)
     // bucket rows of the BN reductions that fold themselves (bn_dev.h): kBnTab doubles, then the ticket counter; kept zeroed
     static constexpr int kBnTab = 4096;

@@ -124,6 +124,9 @@ Model::~Model() {
     if (affine_pin) (void)hipHostFree(affine_pin);
     for (auto e : affine_ev)
         if (e) (void)hipEventDestroy(e);
+    if (intensity_pin) (void)hipHostFree(intensity_pin);
+    for (auto e : intensity_ev)
+        if (e) (void)hipEventDestroy(e);
     if (wg_fork) (void)hipEventDestroy(wg_fork);
     if (wg_join) (void)hipEventDestroy(wg_join);
     if (wg_bucket) (void)hipEventDestroy(wg_bucket);

@@ -1074,6 +1074,22 @@ class DeviceModel:
                                              ctrl.shape[2], dptr(ctrl), dptr(wv), xo.ptr, yo.ptr))
         return DeviceView(xo, xv.shape), DeviceView(yo, yv.shape)
 
+    def intensity(self, xv, records):
+        """random_intensity on a device-resident x view: records uint32 [B, C, 32] from augment.draw_intensity (one per image and
+        feature channel: gamma, bias field, blur taps, noise sigma and key; include/dnnca.h).  The label is not touched.
+        Asynchronous on the model's stream; the view is valid until the next call."""
+        B, h, w, c = xv.shape
+        records = np.ascontiguousarray(records, np.uint32)
+        if records.shape != (B, c, _lib.INTENSITY_WORDS):
+            raise ValueError('intensity records %s are not [B, C, %d] for a batch of %d with %d channels'
+                             % (records.shape, _lib.INTENSITY_WORDS, B, c))
+        if not hasattr(self, '_intensity'):
+            self._intensity = RawDeviceBuffer()
+        xo = self._intensity
+        xo.reserve(xv.nbytes)
+        check(self.lib.dnnca_intensity_f32(self.handle, xv.ptr, B, h, w, c, records.ctypes.data_as(C.POINTER(C.c_uint32)), xo.ptr))
+        return DeviceView(xo, xv.shape)
+
     # ---- data parallel ----------------------------------------------------------------------------------------
     @staticmethod
     def comm_unique_id():

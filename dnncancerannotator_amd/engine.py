@@ -613,13 +613,15 @@ class TFKerasModel:
                     params, _ = shard(batch.params)
                     xb, yb = dm.augment_u8(shard(batch.raw)[0], params, batch.output_size, batch.label_index,
                                            contrast_channels=batch.contrast_channels, src_ptr=src)
-                    if batch.affine is not None:         # fixed place in the chain: crop, flip, contrast, affine, warp, intra-channel warp
+                    if batch.affine is not None:         # fixed place in the chain: crop, flip, contrast, affine, warp, intra-channel warp, intensity
                         xb, yb = dm.affine(xb, yb, shard(batch.affine)[0])
                     if batch.warp is not None:
                         xb, yb = dm.warp(xb, yb, shard(batch.warp[0])[0], shard(batch.warp[1])[0])
                     if batch.intrawarp is not None:      # after random_warp: the overlay's key comes behind data_options.yaml's
                         xb, yb = dm.warp_groups(xb, yb, batch.intrawarp[2], shard(batch.intrawarp[0])[0], shard(batch.intrawarp[1])[0],
                                                 label_index=batch.label_index)
+                    if batch.intensity is not None:      # last: noise added before a resampling would be smoothed away by it
+                        xb = dm.intensity(xb, shard(batch.intensity)[0])
                     dm.check_dev(xb, yb, n)
                     feeder.ring.train_step(slot, xb.ptr, yb.ptr, n, self.learning_rate, cfg)
                 else:
@@ -636,6 +638,8 @@ class TFKerasModel:
                         if batch.intrawarp is not None:
                             xb, yb = dm.warp_groups(xb, yb, batch.intrawarp[2], shard(batch.intrawarp[0])[0], shard(batch.intrawarp[1])[0],
                                                     label_index=batch.label_index)
+                        if batch.intensity is not None:
+                            xb = dm.intensity(xb, shard(batch.intensity)[0])
                         out = dm.train_step_dev(xb, yb, len(raw), self.learning_rate, cfg, want_out=True)
                     else:
                         x, y = shard(np.asarray(batch[0]), np.asarray(batch[1]))

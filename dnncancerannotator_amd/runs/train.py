@@ -7,7 +7,7 @@ from .. import data, dump, engine, load
 
 def make_dataset(paths, options, training, include_meta=False, labels=True):
     """Dataset for `--data_path`.  Supported sources: the reference's `.tfrecords` exam files (tfrecord.py; for training with the
-    `augment_options` of data_options.train -- random crop / flip / contrast / random_affine / random_warp / random_intrachannelwarp run on the device),
+    `augment_options` of data_options.train -- random crop / flip / contrast / random_affine / random_warp / random_intrachannelwarp / random_intensity run on the device),
     `synthetic[:HxW[xC]]` (seeded synthetic slices) and `.npz` files holding `x` [N,H,W,C] in [0,1] and `y` [N,H,W].
     The image-folder pipeline (data.py:170-180) is outside the accelerated hot path.
     include_meta (evaluation only; eval_ds(include_meta=True) of the reference): batches (x, y, paths, sliceIDs) with the same x

@@ -310,7 +310,8 @@ class TFRecordDataset:
     Training (`augment_options` a dict or None, data.py:62-111 train_ds): the slices are centre-cropped to 512 x 512 (the `base`
     call of train_ds, data.py:95-100), shuffled through a buffer of `buffer_size` slices (data.py:106) and handed on as uint8
     `augment.RawBatch`es with their random draws; crop / flip / contrast / the /255 and the feature-label split then run on the
-    device (`dnnca_augment_u8` / `dnnca_affine_f32` / `dnnca_warp_f32` / `dnnca_warp_groups_f32`, engine.train).
+    device (`dnnca_augment_u8` / `dnnca_affine_f32` / `dnnca_warp_f32` / `dnnca_warp_groups_f32` / `dnnca_intensity_f32`,
+    engine.train).
 
     include_meta (evaluation only, eval_ds(include_meta=True), data.py:488-510): batches (x, y, paths, sliceIDs) -- the same x and
     y as without it, each slice's exam `path` feature and its 0-based index in the exam record (tf.data.experimental.Counter).
@@ -374,6 +375,12 @@ class TFRecordDataset:
         if self.plan is not None and self.plan.affine is not None:
             own = isinstance(seed, (int, np.integer))
             self.affine_rng = np.random.default_rng(np.random.SeedSequence(int(seed), spawn_key=(1,)) if own else None)
+        # random_intensity likewise, from the next spawned stream; its target_channels are checked here like random_contrast's
+        self.intensity_channels = augment.intensity_channels(self.plan, len(self.slice_types), self.label_idx)
+        self.intensity_rng = None
+        if augment.intensity_is_on(self.plan):
+            own = isinstance(seed, (int, np.integer))
+            self.intensity_rng = np.random.default_rng(np.random.SeedSequence(int(seed), spawn_key=(2,)) if own else None)
         self.element_spec = (Spec((self.batch_size,) + self.output_size + (len(self.feature_idx),), np.float32),)
         if self.labels:
             self.element_spec += (Spec((self.batch_size,) + self.output_size, np.float32),)
@@ -548,12 +555,19 @@ class TFRecordDataset:
         affine = None
         if self.plan.affine is not None:
             affine = self._mine(augment.draw_affine(self.affine_rng, len(raws), self.plan.affine, self.output_size))      # global batch, then this rank's part
+        # random_intensity: one record per image and feature channel, from its own stream as well; an option with every term off
+        # hands on no records, and the engine then launches nothing
+        intensity = None
+        if self.intensity_rng is not None:
+            intensity = self._mine(augment.draw_intensity(self.intensity_rng, len(raws), self.plan.intensity, len(self.feature_idx),
+                                                          self.intensity_channels))
         # only the window the random crop can reach travels on (centre +- the jitter bound: the same centre, so the same pixels
         # come out of dnnca_augment_u8): 268 x 268 of 512 x 512 for the default crop -- a quarter of the bytes to stack and upload
         m = max(abs(int(self.plan.crop['min_'])), abs(int(self.plan.crop['max_']))) if self.plan.crop is not None else 0
         oh, ow = self.output_size
         mine = [self._centre(r[None], min(r.shape[0], oh + 2 * m), min(r.shape[1], ow + 2 * m))[0] for r in self._mine(raws)]
-        return augment.RawBatch(np.stack(mine), params, self.output_size, self.label_idx, warp, intrawarp, self.contrast_channels, affine)
+        return augment.RawBatch(np.stack(mine), params, self.output_size, self.label_idx, warp, intrawarp, self.contrast_channels,
+                                intensity=intensity, affine=affine)
 
     def _stacked(self, xs, ys):
         if not self.labels:                     # (x,): there is no label to stack

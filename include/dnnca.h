@@ -297,6 +297,29 @@ int dnnca_warp_groups_f32(void* model, const float* x_dev, const float* y_dev, i
    outputs needs dnnca_sync first. */
 int dnnca_affine_f32(void* model, const float* x_dev, const float* y_dev, int batch, int h, int w, int c, const double* mat_host,
                      float* x_out_dev, float* y_out_dev);
+/* random_intensity (this project's own augmentation option; augment.py draw_intensity): per image and feature channel a gamma, a
+   smooth multiplicative bias field, a separable Gaussian blur and Gaussian or Rician noise, in that order, then a clamp to [0, 1].
+   rec_host [batch, c, 32] uint32, one 128-byte record per plane, floats as their float32 bit patterns:
+       word 0        flags: bit 0 gamma, bit 1 bias, bit 2 blur, bit 3 noise, bit 4 Rician (with bit 3; Gaussian without it)
+       word 1        gamma g                                  v <- v <= 0 ? 0 : powf(v, g)
+       words 2..10   bias coefficients a[9]                   v <- v * expf(f),  f = sum a[n] P_i(u) P_j(t) over (i, j) = (1,0) (0,1)
+                     (2,0) (1,1) (0,2) (3,0) (2,1) (1,2) (0,3), P Legendre, u = 2 row / (h - 1) - 1, t = 2 col / (w - 1) - 1 (0 where
+                     the size is 1)
+       word 11       blur radius R (integer, 0..8)
+       words 12..20  taps w[0..8], w[0] the centre, 0 beyond R: rows, then columns; a tap outside the image reads the nearest edge
+                     pixel (after gamma and bias on that pixel)
+       word 21       noise sigma s
+       words 22, 23  Philox4x32-10 key; counter (row * w + col, 0, 0, 0); output words r0, r1: u1 = ((r0 >> 9) + 1) * 2^-23,
+                     u2 = (r1 >> 8) * 2^-24, rad = sqrtf(-2 logf(u1)), z0 = rad cospif(2 u2), z1 = rad sinpif(2 u2);
+                     v <- v + s z0 (Gaussian) or sqrtf((v + s z0)^2 + (s z1)^2) (Rician)
+       words 24..31  0
+   A plane whose flags are 0 is copied bit for bit (no clamp).  Out of place; h, w, c >= 1 and h * w < 2^32.  DNNCA_EINVAL (the
+   message names the function, nothing is launched, the output is untouched) for: a null pointer; batch (1..65535), h, w or c < 1; an
+   output overlapping the input; unknown flag bits; a NaN or infinite float word; gamma <= 0 with bit 0; R > 8; a negative tap;
+   |w[0] + 2 sum w[k] - 1| > 1e-5 with bit 2; s < 0; a non-zero reserved word.
+   Asynchronous on the model's stream like dnnca_augment_u8: rec_host has been copied when the call returns; a host read of the
+   output needs dnnca_sync first. */
+int dnnca_intensity_f32(void* model, const float* x_dev, int batch, int h, int w, int c, const unsigned* rec_host, float* x_out_dev);
 /* same as dnnca_train_step with x/y already in HBM; asynchronous on the model's stream; out may be NULL (no sync) */
 int dnnca_train_step_dev(void* model, const float* x_dev, const float* y_dev, int batch, float lr,
                          const dnnca_loss_cfg* cfg, dnnca_step_out* out);
