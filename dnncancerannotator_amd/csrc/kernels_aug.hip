@@ -115,40 +115,16 @@ int dnnca_augment_u8(void* model, const void* src_dev, int batch, int hs, int ws
             return DNNCA_EINVAL;
         }
     }
-    const size_t need = (size_t)batch * sizeof(dnnca_aug_param) + (size_t)batch * AUG_MAXC * 4;
-    if (need > M->aug_scratch_bytes) {
-        void* p = nullptr;
-        DN_TRY(M->alloc(&p, need));
-        M->aug_scratch = p;
-        M->aug_scratch_bytes = need;
-    }
+    // the draws, padded to max_batch, with room for the channel sums behind them on the device
+    const size_t prm_bytes = (size_t)batch * sizeof(dnnca_aug_param);
+    DN_TRY(M->aug_ring.upload(M, {{params_host, prm_bytes}}, (size_t)batch * AUG_MAXC * 4, (size_t)M->desc.max_batch * sizeof(dnnca_aug_param)));
     AugArgs a{};
     a.src = (const unsigned char*)src_dev;
-    a.prm = (const dnnca_aug_param*)M->aug_scratch;
-    a.sums = (unsigned*)((char*)M->aug_scratch + (size_t)batch * sizeof(dnnca_aug_param));
+    a.prm = (const dnnca_aug_param*)M->aug_ring.dev;
+    a.sums = (unsigned*)(M->aug_ring.dev + prm_bytes);
     a.x = x_dev; a.y = y_dev;
     a.B = batch; a.Hs = hs; a.Ws = ws; a.Cs = cs; a.Ho = ho; a.Wo = wo; a.label_index = label_index;
     a.contrast_mask = contrast_mask & ~(1u << label_index);
-    // the draws travel through a pinned row of the model's ring: the caller's buffer is free when this call returns, and the call
-    // does not wait for the stream (a row is only waited for when it comes round again, four calls later)
-    const size_t prm_bytes = (size_t)batch * sizeof(dnnca_aug_param);
-    if (prm_bytes > M->aug_pin_bytes) {
-        HIP_TRY(hipStreamSynchronize(M->stream));         // uploads from the old rows are complete
-        if (M->aug_pin) (void)hipHostFree(M->aug_pin);
-        M->aug_pin = nullptr;
-        M->aug_pin_bytes = 0;
-        const size_t row = (size_t)M->desc.max_batch * sizeof(dnnca_aug_param) > prm_bytes ? (size_t)M->desc.max_batch * sizeof(dnnca_aug_param) : prm_bytes;
-        HIP_TRY(hipHostMalloc(&M->aug_pin, row * Model::kAugRing, hipHostMallocDefault));
-        M->aug_pin_bytes = row;
-    }
-    const int k = M->aug_k;
-    M->aug_k = (k + 1) % Model::kAugRing;
-    if (!M->aug_ev[k]) HIP_TRY(hipEventCreateWithFlags(&M->aug_ev[k], hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(M->aug_ev[k]));
-    char* pin = (char*)M->aug_pin + (size_t)k * M->aug_pin_bytes;
-    memcpy(pin, params_host, prm_bytes);
-    HIP_TRY(hipMemcpyAsync((void*)a.prm, pin, prm_bytes, hipMemcpyHostToDevice, M->stream));
-    HIP_TRY(hipEventRecord(M->aug_ev[k], M->stream));
     HIP_TRY(hipMemsetAsync(a.sums, 0, (size_t)batch * cs * 4, M->stream));
     const int n = ho * wo;
     int bx = (n + 256 * 16 - 1) / (256 * 16);
@@ -182,46 +158,72 @@ struct WarpArgs {
     int B, H, W, C, n;
 };
 
+// control points + weights of spline s (an image of k_warp, a group of an image of k_warp_groups) into sm (n * 4 + 6 doubles); the
+// caller synchronises
+__device__ __forceinline__ void warp_coeffs_to_lds(const double* ctrl, const double* wv, int n, size_t s, double* sm) {
+    for (int i = threadIdx.x; i < n * 2; i += 256) {
+        sm[i] = ctrl[s * n * 2 + i];
+        sm[n * 2 + i] = wv[s * (n + 3) * 2 + i];
+    }
+    if (threadIdx.x < 6) sm[n * 4 + threadIdx.x] = wv[(s * (n + 3) + n) * 2 + threadIdx.x];
+}
+
+// the bilinear taps of output pixel (qy, qx) under the spline in sm, then tfa's interpolate_bilinear at q - flow with the floor
+// clamped to [0, size - 2] and alpha clipped to [0, 1] -- the clamps keep every tap inside the image however far the flow throws
+// the position (max_diff 100 in the shipped overlays).  The thin-plate weights cancel massively (|phi| ~ 1e4, flows ~ 1): the flow
+// is evaluated in double (the float32 sum is only good to ~1e-2 pixel, which is also all that tfa's own float32 evaluation is good for).
+struct WarpTaps {
+    int iy, ix;
+    float ay, ax;
+    __device__ __forceinline__ float operator()(float tl, float tr, float bl, float br) const {
+        const float top = ax * (tr - tl) + tl, bot = ax * (br - bl) + bl;
+        return ay * (bot - top) + top;
+    }
+};
+
+__device__ __forceinline__ WarpTaps warp_taps(const double* sm, int n, int H, int W, int qy, int qx) {
+    const double* v = sm + n * 4;
+    double d0 = qy * v[0] + qx * v[2] + v[4];             // linear term [q, 1] v  (v rows: y, x, 1; columns: flow_y, flow_x)
+    double d1 = qy * v[1] + qx * v[3] + v[5];
+    for (int i = 0; i < n; ++i) {
+        const double dy = qy - sm[2 * i], dx = qx - sm[2 * i + 1];
+        const double r = dy * dy + dx * dx;
+        const double ph = 0.5 * r * log(fmax(r, 1e-10));
+        d0 = fma(ph, sm[n * 2 + 2 * i], d0);
+        d1 = fma(ph, sm[n * 2 + 2 * i + 1], d1);
+    }
+    const float sy = (float)qy - (float)d0, sx = (float)qx - (float)d1;
+    const float fy = fminf(fmaxf(floorf(sy), 0.f), (float)(H - 2)), fx = fminf(fmaxf(floorf(sx), 0.f), (float)(W - 2));
+    WarpTaps t;
+    t.ay = fminf(fmaxf(sy - fy, 0.f), 1.f);
+    t.ax = fminf(fmaxf(sx - fx, 0.f), 1.f);
+    t.iy = (int)fy;
+    t.ix = (int)fx;
+    return t;
+}
+
 __global__ __launch_bounds__(256) void k_warp(WarpArgs p) {
-    // The thin-plate weights cancel massively (|phi| ~ 1e4, flows ~ 1): the flow is evaluated in double (the float32 sum is only
-    // good to ~1e-2 pixel, which is also all that tfa's own float32 evaluation is good for).
     extern __shared__ double sm[];         // control points + weights of this image: n * 4 + 6 doubles
     const int b = blockIdx.y;
-    for (int i = threadIdx.x; i < p.n * 2; i += 256) {
-        sm[i] = p.ctrl[(size_t)b * p.n * 2 + i];
-        sm[p.n * 2 + i] = p.wv[(size_t)b * (p.n + 3) * 2 + i];
-    }
-    if (threadIdx.x < 6) sm[p.n * 4 + threadIdx.x] = p.wv[((size_t)b * (p.n + 3) + p.n) * 2 + threadIdx.x];
+    warp_coeffs_to_lds(p.ctrl, p.wv, p.n, b, sm);
     __syncthreads();
     const int id = blockIdx.x * 256 + threadIdx.x;
     if (id >= p.H * p.W) return;
     const int qy = id / p.W, qx = id - qy * p.W;
-    const float fqy = (float)qy, fqx = (float)qx;
-    const double* v = sm + p.n * 4;
-    double d0 = qy * v[0] + qx * v[2] + v[4];             // linear term [q, 1] v  (v rows: y, x, 1; columns: flow_y, flow_x)
-    double d1 = qy * v[1] + qx * v[3] + v[5];
-    for (int i = 0; i < p.n; ++i) {
-        const double dy = qy - sm[2 * i], dx = qx - sm[2 * i + 1];
-        const double r = dy * dy + dx * dx;
-        const double ph = 0.5 * r * log(fmax(r, 1e-10));
-        d0 = fma(ph, sm[p.n * 2 + 2 * i], d0);
-        d1 = fma(ph, sm[p.n * 2 + 2 * i + 1], d1);
-    }
-    const float f0 = (float)d0, f1 = (float)d1;
-    // interpolate_bilinear at (qy - f0, qx - f1): floor clamped to [0, size - 2], alpha clipped to [0, 1]
-    const float sy = fqy - f0, sx = fqx - f1;
-    const float fy = fminf(fmaxf(floorf(sy), 0.f), (float)(p.H - 2)), fx = fminf(fmaxf(floorf(sx), 0.f), (float)(p.W - 2));
-    const float ay = fminf(fmaxf(sy - fy, 0.f), 1.f), ax = fminf(fmaxf(sx - fx, 0.f), 1.f);
-    const int iy = (int)fy, ix = (int)fx;
-    const size_t o00 = ((size_t)b * p.H + iy) * p.W + ix, o01 = o00 + 1, o10 = o00 + p.W, o11 = o10 + 1;
+    const WarpTaps t = warp_taps(sm, p.n, p.H, p.W, qy, qx);
+    const size_t o00 = ((size_t)b * p.H + t.iy) * p.W + t.ix, o01 = o00 + 1, o10 = o00 + p.W, o11 = o10 + 1;
     const size_t oq = ((size_t)b * p.H + qy) * p.W + qx;
-    auto lerp2 = [&](float tl, float tr, float bl, float br) {
-        const float top = ax * (tr - tl) + tl, bot = ax * (br - bl) + bl;
-        return ay * (bot - top) + top;
-    };
     for (int c = 0; c < p.C; ++c)
-        p.xo[oq * p.C + c] = lerp2(p.x[o00 * p.C + c], p.x[o01 * p.C + c], p.x[o10 * p.C + c], p.x[o11 * p.C + c]);
-    p.yo[oq] = lerp2(p.y[o00], p.y[o01], p.y[o10], p.y[o11]);
+        p.xo[oq * p.C + c] = t(p.x[o00 * p.C + c], p.x[o01 * p.C + c], p.x[o10 * p.C + c], p.x[o11 * p.C + c]);
+    p.yo[oq] = t(p.y[o00], p.y[o01], p.y[o10], p.y[o11]);
+}
+
+// dnnca_warp_f32 and dnnca_warp_groups_f32: the coefficients of one spline must fit the LDS of a launch
+static bool warp_points_fit(const char* fn, int n_points) {
+    if (n_points <= WARP_MAX_POINTS) return true;
+    set_error("%s: %d control points, at most %d (their %zu bytes of coefficients must fit %zu bytes of LDS)", fn, n_points,
+              WARP_MAX_POINTS, (size_t)(n_points * 4 + 6) * 8, WARP_LDS_MAX);
+    return false;
 }
 
 }  // namespace dnnca
@@ -235,28 +237,17 @@ int dnnca_warp_f32(void* model, const float* x_dev, const float* y_dev, int batc
         set_error("dnnca_warp_f32: bad arguments");
         return DNNCA_EINVAL;
     }
-    if (n_points > WARP_MAX_POINTS) {
-        set_error("dnnca_warp_f32: %d control points, at most %d (their %zu bytes of coefficients must fit %zu bytes of LDS)", n_points,
-                  WARP_MAX_POINTS, (size_t)(n_points * 4 + 6) * 8, WARP_LDS_MAX);
-        return DNNCA_EINVAL;
-    }
+    if (!warp_points_fit("dnnca_warp_f32", n_points)) return DNNCA_EINVAL;
     const size_t nc = (size_t)batch * n_points * 2 * 8, nw = (size_t)batch * (n_points + 3) * 2 * 8;
-    if (nc + nw > M->warp_scratch_bytes) {
-        void* p = nullptr;
-        DN_TRY(M->alloc(&p, nc + nw));
-        M->warp_scratch = p;
-        M->warp_scratch_bytes = nc + nw;
-    }
+    DN_TRY(M->warp_ring.upload(M, {{ctrl_host, nc}, {wv_host, nw}}));
     WarpArgs a{};
     a.x = x_dev; a.y = y_dev; a.xo = x_out_dev; a.yo = y_out_dev;
-    a.ctrl = (const double*)M->warp_scratch;
-    a.wv = (const double*)((char*)M->warp_scratch + nc);
+    a.ctrl = (const double*)M->warp_ring.dev;
+    a.wv = (const double*)(M->warp_ring.dev + nc);
     a.B = batch; a.H = h; a.W = w; a.C = c; a.n = n_points;
-    HIP_TRY(hipMemcpyAsync((void*)a.ctrl, ctrl_host, nc, hipMemcpyHostToDevice, M->stream));
-    HIP_TRY(hipMemcpyAsync((void*)a.wv, wv_host, nw, hipMemcpyHostToDevice, M->stream));
     LAUNCH(M, "aug_warp", (double)batch * h * w * (c + 1) * 8.0, (double)batch * h * w * n_points * 8.0,
            hipLaunchKernelGGL(k_warp, dim3((h * w + 255) / 256, batch), dim3(256), (size_t)(n_points * 4 + 6) * 8, M->stream, a));
-    HIP_TRY(hipStreamSynchronize(M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));      // this call has always returned with its outputs complete: callers may rely on it
     return DNNCA_OK;
 }
 
@@ -278,49 +269,6 @@ struct WarpGroupsArgs {
     int B, H, W, C, G, n;
 };
 
-// control points + weights of group g of image b into sm (n * 4 + 6 doubles, the layout of k_warp); the caller synchronises
-__device__ __forceinline__ void warp_coeffs_to_lds(const WarpGroupsArgs& p, int b, int g, double* sm) {
-    const size_t bg = (size_t)b * p.G + g;
-    for (int i = threadIdx.x; i < p.n * 2; i += 256) {
-        sm[i] = p.ctrl[bg * p.n * 2 + i];
-        sm[p.n * 2 + i] = p.wv[bg * (p.n + 3) * 2 + i];
-    }
-    if (threadIdx.x < 6) sm[p.n * 4 + threadIdx.x] = p.wv[(bg * (p.n + 3) + p.n) * 2 + threadIdx.x];
-}
-
-// the bilinear taps of output pixel (qy, qx) under the spline in sm: flow in double (see k_warp), then tfa's interpolate_bilinear
-// at q - flow with the floor clamped to [0, size - 2] and alpha clipped to [0, 1] -- the clamps keep every tap inside the image
-// however far the flow throws the position (max_diff 100 in the shipped overlays)
-struct WarpTaps {
-    int iy, ix;
-    float ay, ax;
-    __device__ __forceinline__ float operator()(float tl, float tr, float bl, float br) const {
-        const float top = ax * (tr - tl) + tl, bot = ax * (br - bl) + bl;
-        return ay * (bot - top) + top;
-    }
-};
-
-__device__ __forceinline__ WarpTaps warp_taps(const double* sm, int n, int H, int W, int qy, int qx) {
-    const double* v = sm + n * 4;
-    double d0 = qy * v[0] + qx * v[2] + v[4];
-    double d1 = qy * v[1] + qx * v[3] + v[5];
-    for (int i = 0; i < n; ++i) {
-        const double dy = qy - sm[2 * i], dx = qx - sm[2 * i + 1];
-        const double r = dy * dy + dx * dx;
-        const double ph = 0.5 * r * log(fmax(r, 1e-10));
-        d0 = fma(ph, sm[n * 2 + 2 * i], d0);
-        d1 = fma(ph, sm[n * 2 + 2 * i + 1], d1);
-    }
-    const float sy = (float)qy - (float)d0, sx = (float)qx - (float)d1;
-    const float fy = fminf(fmaxf(floorf(sy), 0.f), (float)(H - 2)), fx = fminf(fmaxf(floorf(sx), 0.f), (float)(W - 2));
-    WarpTaps t;
-    t.ay = fminf(fmaxf(sy - fy, 0.f), 1.f);
-    t.ax = fminf(fmaxf(sx - fx, 0.f), 1.f);
-    t.iy = (int)fy;
-    t.ix = (int)fx;
-    return t;
-}
-
 // the channels of group g (and the label when it is in g) of output pixel (qy, qx) of image b
 __device__ __forceinline__ void warp_group_sample(const WarpGroupsArgs& p, int b, int g, int qy, int qx, const WarpTaps& t) {
     const size_t o00 = ((size_t)b * p.H + t.iy) * p.W + t.ix, o01 = o00 + 1, o10 = o00 + p.W, o11 = o10 + 1;
@@ -339,9 +287,9 @@ __global__ __launch_bounds__(256) void k_warp_groups(WarpGroupsArgs p) {
     extern __shared__ double sm[];
     const int b = blockIdx.y, stride = p.n * 4 + 6;
     if (PIXEL)
-        for (int g = 0; g < p.G; ++g) warp_coeffs_to_lds(p, b, g, sm + g * stride);
+        for (int g = 0; g < p.G; ++g) warp_coeffs_to_lds(p.ctrl, p.wv, p.n, (size_t)b * p.G + g, sm + g * stride);
     else
-        warp_coeffs_to_lds(p, b, blockIdx.z, sm);
+        warp_coeffs_to_lds(p.ctrl, p.wv, p.n, (size_t)b * p.G + blockIdx.z, sm);
     __syncthreads();
     const int id = blockIdx.x * 256 + threadIdx.x;
     if (id >= p.H * p.W) return;
@@ -365,11 +313,7 @@ int dnnca_warp_groups_f32(void* model, const float* x_dev, const float* y_dev, i
         set_error("dnnca_warp_groups_f32: bad arguments");
         return DNNCA_EINVAL;
     }
-    if (n_points > WARP_MAX_POINTS) {
-        set_error("dnnca_warp_groups_f32: %d control points, at most %d (their %zu bytes of coefficients must fit %zu bytes of LDS)",
-                  n_points, WARP_MAX_POINTS, (size_t)(n_points * 4 + 6) * 8, WARP_LDS_MAX);
-        return DNNCA_EINVAL;
-    }
+    if (!warp_points_fit("dnnca_warp_groups_f32", n_points)) return DNNCA_EINVAL;
     if (n_groups < 1 || n_groups > c + 1) {
         set_error("dnnca_warp_groups_f32: %d groups for %d channels + label", n_groups, c);
         return DNNCA_EINVAL;
@@ -381,38 +325,12 @@ int dnnca_warp_groups_f32(void* model, const float* x_dev, const float* y_dev, i
         }
     // one row: control points, weights, group table -- the device copy has the same layout, so the row travels in one copy
     const size_t nc = (size_t)batch * n_groups * n_points * 2 * 8, nw = (size_t)batch * n_groups * (n_points + 3) * 2 * 8;
-    const size_t row = nc + nw + (size_t)(c + 1) * 4;
-    if (row > M->warpg_scratch_bytes) {
-        void* p = nullptr;
-        DN_TRY(M->alloc(&p, row));
-        M->warpg_scratch = p;
-        M->warpg_scratch_bytes = row;
-    }
-    // like the draws of dnnca_augment_u8 the coefficients wait for their upload in a ring of pinned rows: the caller's buffers are
-    // free when this call returns and the call does not wait for the stream (a row is waited for when it comes round again)
-    if (row > M->warpg_pin_bytes) {
-        HIP_TRY(hipStreamSynchronize(M->stream));         // uploads from the old rows are complete
-        if (M->warpg_pin) (void)hipHostFree(M->warpg_pin);
-        M->warpg_pin = nullptr;
-        M->warpg_pin_bytes = 0;
-        HIP_TRY(hipHostMalloc(&M->warpg_pin, row * Model::kAugRing, hipHostMallocDefault));
-        M->warpg_pin_bytes = row;
-    }
-    const int k = M->warpg_k;
-    M->warpg_k = (k + 1) % Model::kAugRing;
-    if (!M->warpg_ev[k]) HIP_TRY(hipEventCreateWithFlags(&M->warpg_ev[k], hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(M->warpg_ev[k]));
-    char* pin = (char*)M->warpg_pin + (size_t)k * M->warpg_pin_bytes;
-    memcpy(pin, ctrl_host, nc);
-    memcpy(pin + nc, wv_host, nw);
-    memcpy(pin + nc + nw, group_of, (size_t)(c + 1) * 4);
-    HIP_TRY(hipMemcpyAsync(M->warpg_scratch, pin, row, hipMemcpyHostToDevice, M->stream));
-    HIP_TRY(hipEventRecord(M->warpg_ev[k], M->stream));
+    DN_TRY(M->warpg_ring.upload(M, {{ctrl_host, nc}, {wv_host, nw}, {group_of, (size_t)(c + 1) * 4}}));
     WarpGroupsArgs a{};
     a.x = x_dev; a.y = y_dev; a.xo = x_out_dev; a.yo = y_out_dev;
-    a.ctrl = (const double*)M->warpg_scratch;
-    a.wv = (const double*)((char*)M->warpg_scratch + nc);
-    a.group_of = (const int*)((char*)M->warpg_scratch + nc + nw);
+    a.ctrl = (const double*)M->warpg_ring.dev;
+    a.wv = (const double*)(M->warpg_ring.dev + nc);
+    a.group_of = (const int*)(M->warpg_ring.dev + nc + nw);
     a.B = batch; a.H = h; a.W = w; a.C = c; a.G = n_groups; a.n = n_points;
     const size_t lds = (size_t)(n_points * 4 + 6) * 8;
     const unsigned bx = (unsigned)(((size_t)h * w + 255) / 256);
@@ -500,7 +418,7 @@ __global__ __launch_bounds__(TX * TY) void k_affine(AffineArgs p) {
     p.yo[oq] = lerp2(k00 ? p.y[o00] : 0.f, k01 ? p.y[o01] : 0.f, k10 ? p.y[o10] : 0.f, k11 ? p.y[o11] : 0.f);
 }
 
-static bool affine_overlap(const void* a, size_t na, const void* b, size_t nb) {
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const char *pa = (const char*)a, *pb = (const char*)b;
     return pa < pb + nb && pb < pa + na;
 }
@@ -520,8 +438,8 @@ int dnnca_affine_f32(void* model, const float* x_dev, const float* y_dev, int ba
         return DNNCA_EINVAL;
     }
     const size_t ny = (size_t)batch * h * w * 4, nx = ny * c;
-    if (affine_overlap(x_out_dev, nx, x_dev, nx) || affine_overlap(x_out_dev, nx, y_dev, ny) || affine_overlap(y_out_dev, ny, x_dev, nx) ||
-        affine_overlap(y_out_dev, ny, y_dev, ny) || affine_overlap(x_out_dev, nx, y_out_dev, ny)) {
+    if (ranges_overlap(x_out_dev, nx, x_dev, nx) || ranges_overlap(x_out_dev, nx, y_dev, ny) || ranges_overlap(y_out_dev, ny, x_dev, nx) ||
+        ranges_overlap(y_out_dev, ny, y_dev, ny) || ranges_overlap(x_out_dev, nx, y_out_dev, ny)) {
         set_error("dnnca_affine_f32: the outputs must not alias the inputs or each other");
         return DNNCA_EINVAL;
     }
@@ -544,35 +462,10 @@ int dnnca_affine_f32(void* model, const float* x_dev, const float* y_dev, int ba
             return DNNCA_EINVAL;
         }
     }
-    // one device row and a ring of pinned rows, as dnnca_warp_groups_f32: the caller's matrices are free when this call returns and
-    // the call does not wait for the stream.  Rows are sized for max_batch, so a ragged last batch does not grow them.
-    const size_t bytes_in = (size_t)batch * 6 * sizeof(double);
-    const size_t row = (size_t)M->desc.max_batch > (size_t)batch ? (size_t)M->desc.max_batch * 6 * sizeof(double) : bytes_in;
-    if (row > M->affine_scratch_bytes) {
-        void* p = nullptr;
-        DN_TRY(M->alloc(&p, row));
-        M->affine_scratch = p;
-        M->affine_scratch_bytes = row;
-    }
-    if (row > M->affine_pin_bytes) {
-        HIP_TRY(hipStreamSynchronize(M->stream));         // uploads from the old rows are complete
-        if (M->affine_pin) (void)hipHostFree(M->affine_pin);
-        M->affine_pin = nullptr;
-        M->affine_pin_bytes = 0;
-        HIP_TRY(hipHostMalloc(&M->affine_pin, row * Model::kAugRing, hipHostMallocDefault));
-        M->affine_pin_bytes = row;
-    }
-    const int k = M->affine_k;
-    M->affine_k = (k + 1) % Model::kAugRing;
-    if (!M->affine_ev[k]) HIP_TRY(hipEventCreateWithFlags(&M->affine_ev[k], hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(M->affine_ev[k]));
-    char* pin = (char*)M->affine_pin + (size_t)k * M->affine_pin_bytes;
-    memcpy(pin, mat_host, bytes_in);
-    HIP_TRY(hipMemcpyAsync(M->affine_scratch, pin, bytes_in, hipMemcpyHostToDevice, M->stream));
-    HIP_TRY(hipEventRecord(M->affine_ev[k], M->stream));
+    DN_TRY(M->affine_ring.upload(M, {{mat_host, (size_t)batch * 6 * sizeof(double)}}, 0, (size_t)M->desc.max_batch * 6 * sizeof(double)));
     AffineArgs a{};
     a.x = x_dev; a.y = y_dev; a.xo = x_out_dev; a.yo = y_out_dev;
-    a.mat = (const double*)M->affine_scratch;
+    a.mat = (const double*)M->affine_ring.dev;
     a.B = batch; a.H = h; a.W = w; a.C = c;
     const double bytes = (double)batch * h * w * (c + 1) * 8.0;
 #define AFFINE_GO(TX, TY)                                                                                                       \
@@ -763,7 +656,7 @@ int dnnca_intensity_f32(void* model, const float* x_dev, int batch, int h, int w
         return DNNCA_EINVAL;
     }
     const size_t nx = (size_t)batch * h * w * c * 4;
-    if (affine_overlap(x_out_dev, nx, x_dev, nx)) {
+    if (ranges_overlap(x_out_dev, nx, x_dev, nx)) {
         set_error("dnnca_intensity_f32: the output must not alias the input");
         return DNNCA_EINVAL;
     }
@@ -827,35 +720,11 @@ int dnnca_intensity_f32(void* model, const float* x_dev, int batch, int h, int w
             return DNNCA_EINVAL;
         }
     }
-    // one device row and a ring of pinned rows, as dnnca_affine_f32: the caller's records are free when this call returns and the
-    // call does not wait for the stream.  Rows are sized for max_batch, so a ragged last batch does not grow them.
-    const size_t bytes_in = (size_t)batch * c * INTENSITY_WORDS * 4;
-    const size_t row = (size_t)M->desc.max_batch > (size_t)batch ? (size_t)M->desc.max_batch * c * INTENSITY_WORDS * 4 : bytes_in;
-    if (row > M->intensity_scratch_bytes) {
-        void* p = nullptr;
-        DN_TRY(M->alloc(&p, row));
-        M->intensity_scratch = p;
-        M->intensity_scratch_bytes = row;
-    }
-    if (row > M->intensity_pin_bytes) {
-        HIP_TRY(hipStreamSynchronize(M->stream));         // uploads from the old rows are complete
-        if (M->intensity_pin) (void)hipHostFree(M->intensity_pin);
-        M->intensity_pin = nullptr;
-        M->intensity_pin_bytes = 0;
-        HIP_TRY(hipHostMalloc(&M->intensity_pin, row * Model::kAugRing, hipHostMallocDefault));
-        M->intensity_pin_bytes = row;
-    }
-    const int k = M->intensity_k;
-    M->intensity_k = (k + 1) % Model::kAugRing;
-    if (!M->intensity_ev[k]) HIP_TRY(hipEventCreateWithFlags(&M->intensity_ev[k], hipEventDisableTiming));
-    else HIP_TRY(hipEventSynchronize(M->intensity_ev[k]));
-    char* pin = (char*)M->intensity_pin + (size_t)k * M->intensity_pin_bytes;
-    memcpy(pin, rec_host, bytes_in);
-    HIP_TRY(hipMemcpyAsync(M->intensity_scratch, pin, bytes_in, hipMemcpyHostToDevice, M->stream));
-    HIP_TRY(hipEventRecord(M->intensity_ev[k], M->stream));
+    const size_t rec_bytes = (size_t)c * INTENSITY_WORDS * 4;
+    DN_TRY(M->intensity_ring.upload(M, {{rec_host, batch * rec_bytes}}, 0, M->desc.max_batch * rec_bytes));
     IntensityArgs a{};
     a.x = x_dev; a.xo = x_out_dev;
-    a.rec = (const unsigned*)M->intensity_scratch;
+    a.rec = (const unsigned*)M->intensity_ring.dev;
     a.B = batch; a.H = h; a.W = w; a.C = c;
     const double bytes = (double)batch * h * w * c * 8.0;
 #define INTENSITY_GO(TX, TY)                                                                                                    \

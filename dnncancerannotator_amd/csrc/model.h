@@ -135,6 +135,28 @@ struct StepRequest {
     bool head_in_conv = false;       // pixel-group plan: the head may ride in the epilogue of the conv that feeds it (fast_conv_fwd_head)
 };
 
+// How a small host array of an augmentation call reaches the device (kernels_aug.hip): the pieces are laid out back to back in a
+// pinned row of a ring of kAugRing rows and go to the one device row in one asynchronous copy on Model::stream, with an event
+// recorded right behind it.  The caller's buffers are free when upload() returns, and upload() does not wait for the stream (the
+// exam-file train loop keeps a step queued behind the running one): a pinned row is only waited for when it comes round again,
+// kAugRing calls later.  A call that outgrows the pinned rows drains the stream (uploads from the old rows are complete) and
+// replaces them; a device row that is outgrown stays in Model::allocs until the model closes -- a queued kernel may still read it.
+struct Model;
+struct HostRowRing {
+    static constexpr int kAugRing = 4;
+    struct Piece { const void* host; size_t bytes; };
+    char* dev = nullptr;                 // the device row: the pieces of the last upload, then extra_dev bytes
+    size_t dev_bytes = 0;
+    char* pin = nullptr;                 // kAugRing x pin_bytes, pinned
+    size_t pin_bytes = 0;
+    hipEvent_t ev[kAugRing] = {nullptr, nullptr, nullptr, nullptr};      // recorded behind the upload that read row k
+    int k = 0;
+    // min_row: rows are at least this long (sized for max_batch, a ragged last batch does not grow them); extra_dev: device bytes
+    // behind the uploaded part that the call's kernels use (zeroed when the row is allocated, not by an upload)
+    int upload(Model* M, std::initializer_list<Piece> pieces, size_t extra_dev = 0, size_t min_row = 0);
+    void release();                      // ~Model: the pinned rows and the events (the device row goes with Model::allocs)
+};
+
 struct Model {
     dnnca_model_desc desc;
     StepSwitches sw;
@@ -157,39 +179,10 @@ struct Model {
     // it rides.  phi [max_batch, outH, outW]: the signed distance map of the last step's raw labels (kernels_boundary.hip), cols its
     // column pass; both allocated once.  batch: images of the last step that wrote phi; sums_batch: ... that wrote S into region_loss.ws
     struct Boundary { float weight = 0.f; float* phi = nullptr; uint32_t* cols = nullptr; int batch = 0, sums_batch = 0; } boundary;
-    void* warp_scratch = nullptr;        // control points + spline weights of dnnca_warp_f32
-    size_t warp_scratch_bytes = 0;
-    void* aug_scratch = nullptr;         // per-image augmentation draws + channel sums (kernels_aug.hip)
-    size_t aug_scratch_bytes = 0;
-    // the caller's draws wait for their asynchronous upload in a small ring of pinned rows, so that dnnca_augment_u8 returns
-    // without synchronising the stream (the exam-file train loop keeps a step queued behind the running one)
-    static constexpr int kAugRing = 4;
-    void* aug_pin = nullptr;             // kAugRing x aug_pin_bytes, pinned
-    size_t aug_pin_bytes = 0;
-    hipEvent_t aug_ev[kAugRing] = {nullptr, nullptr, nullptr, nullptr};      // recorded behind the upload that read row k
-    int aug_k = 0;
-    // dnnca_warp_groups_f32: control points, spline weights and group table of every group of every image -- one device row, and
-    // a pinned ring of the same rows for the asynchronous upload (as aug_pin)
-    void* warpg_scratch = nullptr;
-    size_t warpg_scratch_bytes = 0;
-    void* warpg_pin = nullptr;           // kAugRing x warpg_pin_bytes, pinned
-    size_t warpg_pin_bytes = 0;
-    hipEvent_t warpg_ev[kAugRing] = {nullptr, nullptr, nullptr, nullptr};
-    int warpg_k = 0;
-    // dnnca_affine_f32: the [batch, 2, 3] matrices of random_affine -- one device row and a pinned ring of the same rows (as aug_pin)
-    void* affine_scratch = nullptr;
-    size_t affine_scratch_bytes = 0;
-    void* affine_pin = nullptr;          // kAugRing x affine_pin_bytes, pinned
-    size_t affine_pin_bytes = 0;
-    hipEvent_t affine_ev[kAugRing] = {nullptr, nullptr, nullptr, nullptr};
-    int affine_k = 0;
-    // dnnca_intensity_f32: the [batch, c, 32] records of random_intensity -- one device row and a pinned ring of the same rows (as aug_pin)
-    void* intensity_scratch = nullptr;
-    size_t intensity_scratch_bytes = 0;
-    void* intensity_pin = nullptr;       // kAugRing x intensity_pin_bytes, pinned
-    size_t intensity_pin_bytes = 0;
-    hipEvent_t intensity_ev[kAugRing] = {nullptr, nullptr, nullptr, nullptr};
-    int intensity_k = 0;
+    // the host arrays of the augmentation entry points (kernels_aug.hip), one ring per entry point: dnnca_augment_u8's draws (+ the
+    // channel sums behind them on the device), dnnca_warp_f32's and dnnca_warp_groups_f32's control points, spline weights (and
+    // group table), dnnca_affine_f32's [batch, 2, 3] matrices, dnnca_intensity_f32's [batch, c, 32] records
+    HostRowRing aug_ring, warp_ring, warpg_ring, affine_ring, intensity_ring;
     float* first_slabs = nullptr;        // bucket copies of the first-layer weight gradient (kernels_first.hip; kept zeroed)
     // bucket rows of the BN reductions that fold themselves (bn_dev.h): kBnTab doubles, then the ticket counter; kept zeroed
     static constexpr int kBnTab = 4096;

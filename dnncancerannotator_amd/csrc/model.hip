@@ -114,19 +114,8 @@ Model::~Model() {
     }
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
     if (out_ring) (void)hipHostFree(out_ring);
-    if (aug_pin) (void)hipHostFree(aug_pin);
     if (tm_pin) (void)hipHostFree(tm_pin);
-    for (auto e : aug_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (warpg_pin) (void)hipHostFree(warpg_pin);
-    for (auto e : warpg_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (affine_pin) (void)hipHostFree(affine_pin);
-    for (auto e : affine_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (intensity_pin) (void)hipHostFree(intensity_pin);
-    for (auto e : intensity_ev)
-        if (e) (void)hipEventDestroy(e);
+    for (HostRowRing* r : {&aug_ring, &warp_ring, &warpg_ring, &affine_ring, &intensity_ring}) r->release();
     if (wg_fork) (void)hipEventDestroy(wg_fork);
     if (wg_join) (void)hipEventDestroy(wg_join);
     if (wg_bucket) (void)hipEventDestroy(wg_bucket);
@@ -172,6 +161,45 @@ int Model::alloc(void** ptr, size_t bytes) {
     allocs.push_back(*ptr);
     HIP_TRY(hipMemsetAsync(*ptr, 0, bytes, stream));
     return DNNCA_OK;
+}
+
+int HostRowRing::upload(Model* M, std::initializer_list<Piece> pieces, size_t extra_dev, size_t min_row) {
+    size_t bytes = 0;
+    for (const Piece& q : pieces) bytes += q.bytes;
+    const size_t row = bytes > min_row ? bytes : min_row;
+    if (row + extra_dev > dev_bytes) {
+        void* p = nullptr;
+        DN_TRY(M->alloc(&p, row + extra_dev));
+        dev = (char*)p;
+        dev_bytes = row + extra_dev;
+    }
+    if (row > pin_bytes) {
+        HIP_TRY(hipStreamSynchronize(M->stream));         // uploads from the old rows are complete
+        if (pin) (void)hipHostFree(pin);
+        pin = nullptr;
+        pin_bytes = 0;
+        HIP_TRY(hipHostMalloc((void**)&pin, row * kAugRing, hipHostMallocDefault));
+        pin_bytes = row;
+    }
+    const int r = k;
+    k = (r + 1) % kAugRing;
+    if (!ev[r]) HIP_TRY(hipEventCreateWithFlags(&ev[r], hipEventDisableTiming));
+    else HIP_TRY(hipEventSynchronize(ev[r]));
+    char* dst = pin + (size_t)r * pin_bytes;
+    size_t at = 0;
+    for (const Piece& q : pieces) {
+        memcpy(dst + at, q.host, q.bytes);
+        at += q.bytes;
+    }
+    HIP_TRY(hipMemcpyAsync(dev, dst, bytes, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipEventRecord(ev[r], M->stream));
+    return DNNCA_OK;
+}
+
+void HostRowRing::release() {
+    if (pin) (void)hipHostFree(pin);
+    for (auto e : ev)
+        if (e) (void)hipEventDestroy(e);
 }
 
 void Model::set_variant(const char* fmt, ...) {

@@ -987,6 +987,13 @@ class DeviceModel:
         return Attribution(signed, absolute, ends, amap)
 
     # ---- device-side augmentation (annotator/data.py:62-111 train_ds) ------------------------------------------
+    def _aug_buffers(self, name, *nbytes):
+        """the buffers of the augmentation call `name` (kept as self._<name>, made by its first call), each reserved to its size"""
+        bufs = self.__dict__.setdefault('_' + name, tuple(RawDeviceBuffer() for _ in nbytes))
+        for buf, n in zip(bufs, nbytes):
+            buf.reserve(n)
+        return bufs
+
     def augment_u8(self, raw, params, out_size, label_index, contrast_channels=None, src_ptr=None):
         """raw uint8 [B, Hs, Ws, Cs] (host) + per-image draws [(dy, dx, flip, contrast)] -> device-resident (x [B, Ho, Wo, Cs-1],
         y [B, Ho, Wo]) views, valid until the next call.  contrast_channels: source channels to adjust (default: all features).
@@ -1004,15 +1011,11 @@ class DeviceModel:
         mask = 0
         for c in contrast_channels:
             mask |= 1 << int(c)
-        if not hasattr(self, '_aug'):
-            self._aug = (RawDeviceBuffer(), RawDeviceBuffer(), RawDeviceBuffer())
-        src, xb, yb = self._aug
+        src, xb, yb = self._aug_buffers('aug', 0, B * ho * wo * (cs - 1) * 4, B * ho * wo * 4)      # (src: sized by its upload)
         own_upload = src_ptr is None
         if own_upload:
             src.upload(raw)
             src_ptr = src.ptr
-        xb.reserve(B * ho * wo * (cs - 1) * 4)
-        yb.reserve(B * ho * wo * 4)
         prm = (_lib.AugParam * B)(*[_lib.AugParam(int(p[0]), int(p[1]), int(p[2]), float(p[3])) for p in params])
         check(self.lib.dnnca_augment_u8(self.handle, src_ptr, B, hs, ws, cs, int(label_index), mask, prm, ho, wo, xb.ptr, yb.ptr))
         if own_upload:
@@ -1028,11 +1031,7 @@ class DeviceModel:
         mats = np.ascontiguousarray(mats, np.float64)
         if mats.shape != (B, 2, 3):
             raise ValueError('affine matrices %s are not [B, 2, 3] for a batch of %d' % (mats.shape, B))
-        if not hasattr(self, '_affine'):
-            self._affine = (RawDeviceBuffer(), RawDeviceBuffer())
-        xo, yo = self._affine
-        xo.reserve(xv.nbytes)
-        yo.reserve(yv.nbytes)
+        xo, yo = self._aug_buffers('affine', xv.nbytes, yv.nbytes)
         check(self.lib.dnnca_affine_f32(self.handle, xv.ptr, yv.ptr, B, h, w, c, mats.ctypes.data_as(C.POINTER(C.c_double)), xo.ptr, yo.ptr))
         return DeviceView(xo, xv.shape), DeviceView(yo, yv.shape)
 
@@ -1041,11 +1040,7 @@ class DeviceModel:
         B, h, w, c = xv.shape
         ctrl, wv = np.ascontiguousarray(ctrl, np.float64), np.ascontiguousarray(wv, np.float64)
         dptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))        # noqa: E731
-        if not hasattr(self, '_warp'):
-            self._warp = (RawDeviceBuffer(), RawDeviceBuffer())
-        xo, yo = self._warp
-        xo.reserve(xv.nbytes)
-        yo.reserve(yv.nbytes)
+        xo, yo = self._aug_buffers('warp', xv.nbytes, yv.nbytes)
         check(self.lib.dnnca_warp_f32(self.handle, xv.ptr, yv.ptr, B, h, w, c, ctrl.shape[1], dptr(ctrl), dptr(wv), xo.ptr, yo.ptr))
         return DeviceView(xo, xv.shape), DeviceView(yo, yv.shape)
 
@@ -1065,11 +1060,7 @@ class DeviceModel:
         if ctrl.ndim != 4 or ctrl.shape[0] != B or wv.shape != ctrl.shape[:2] + (ctrl.shape[2] + 3, 2):
             raise ValueError('ctrl %s / wv %s are not [B, G, n, 2] / [B, G, n + 3, 2] for a batch of %d' % (ctrl.shape, wv.shape, B))
         dptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))        # noqa: E731
-        if not hasattr(self, '_warp_groups'):
-            self._warp_groups = (RawDeviceBuffer(), RawDeviceBuffer())
-        xo, yo = self._warp_groups
-        xo.reserve(xv.nbytes)
-        yo.reserve(yv.nbytes)
+        xo, yo = self._aug_buffers('warp_groups', xv.nbytes, yv.nbytes)
         check(self.lib.dnnca_warp_groups_f32(self.handle, xv.ptr, yv.ptr, B, h, w, c, ctrl.shape[1], group_of.ctypes.data_as(C.POINTER(C.c_int)),
                                              ctrl.shape[2], dptr(ctrl), dptr(wv), xo.ptr, yo.ptr))
         return DeviceView(xo, xv.shape), DeviceView(yo, yv.shape)
@@ -1083,10 +1074,7 @@ class DeviceModel:
         if records.shape != (B, c, _lib.INTENSITY_WORDS):
             raise ValueError('intensity records %s are not [B, C, %d] for a batch of %d with %d channels'
                              % (records.shape, _lib.INTENSITY_WORDS, B, c))
-        if not hasattr(self, '_intensity'):
-            self._intensity = RawDeviceBuffer()
-        xo = self._intensity
-        xo.reserve(xv.nbytes)
+        xo, = self._aug_buffers('intensity', xv.nbytes)
         check(self.lib.dnnca_intensity_f32(self.handle, xv.ptr, B, h, w, c, records.ctypes.data_as(C.POINTER(C.c_uint32)), xo.ptr))
         return DeviceView(xo, xv.shape)
 

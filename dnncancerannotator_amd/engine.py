@@ -279,6 +279,25 @@ def _log_value(metric):
     return float(r) if np.ndim(r) == 0 else [float(v) for v in r]
 
 
+def augment_on_device(dm, batch, shard, src_ptr=None):
+    """The train-time augmentation chain of an augment.RawBatch (uint8 slices + their random draws) on the device `dm`: crop /
+    flip / contrast / 255 / feature-label split, then every option the batch carries draws for, in its fixed place: affine, warp,
+    intra-channel warp, intensity.  shard: this rank's part of an array; src_ptr: the slices are in a staging slot already.
+    Returns the device-resident (x, y) views."""
+    part = lambda a: shard(a)[0]        # noqa: E731
+    xb, yb = dm.augment_u8(part(batch.raw), part(batch.params), batch.output_size, batch.label_index,
+                           contrast_channels=batch.contrast_channels, src_ptr=src_ptr)
+    if batch.affine is not None:
+        xb, yb = dm.affine(xb, yb, part(batch.affine))
+    if batch.warp is not None:
+        xb, yb = dm.warp(xb, yb, part(batch.warp[0]), part(batch.warp[1]))
+    if batch.intrawarp is not None:      # after random_warp: the overlay's key comes behind data_options.yaml's
+        xb, yb = dm.warp_groups(xb, yb, batch.intrawarp[2], part(batch.intrawarp[0]), part(batch.intrawarp[1]), label_index=batch.label_index)
+    if batch.intensity is not None:      # last: noise added before a resampling would be smoothed away by it
+        xb = dm.intensity(xb, part(batch.intensity))
+    return xb, yb
+
+
 class TFKerasModel:
     """Encapsulates the DNN model and the library behind it (name kept from the reference for drop-in use)."""
 
@@ -610,37 +629,14 @@ class TFKerasModel:
                 elif item[0] == 'raw':               # uint8 source batch in a staging slot: augmentation kernels, then the step
                     _, slot, src, batch, n = item
                     feeder.ring.wait(slot)
-                    params, _ = shard(batch.params)
-                    xb, yb = dm.augment_u8(shard(batch.raw)[0], params, batch.output_size, batch.label_index,
-                                           contrast_channels=batch.contrast_channels, src_ptr=src)
-                    if batch.affine is not None:         # fixed place in the chain: crop, flip, contrast, affine, warp, intra-channel warp, intensity
-                        xb, yb = dm.affine(xb, yb, shard(batch.affine)[0])
-                    if batch.warp is not None:
-                        xb, yb = dm.warp(xb, yb, shard(batch.warp[0])[0], shard(batch.warp[1])[0])
-                    if batch.intrawarp is not None:      # after random_warp: the overlay's key comes behind data_options.yaml's
-                        xb, yb = dm.warp_groups(xb, yb, batch.intrawarp[2], shard(batch.intrawarp[0])[0], shard(batch.intrawarp[1])[0],
-                                                label_index=batch.label_index)
-                    if batch.intensity is not None:      # last: noise added before a resampling would be smoothed away by it
-                        xb = dm.intensity(xb, shard(batch.intensity)[0])
+                    xb, yb = augment_on_device(dm, batch, shard, src_ptr=src)
                     dm.check_dev(xb, yb, n)
                     feeder.ring.train_step(slot, xb.ptr, yb.ptr, n, self.learning_rate, cfg)
                 else:
                     batch = item[1]
                     if isinstance(batch, augment.RawBatch):
-                        # uint8 slices + their random draws: crop / flip / contrast / 255 / feature-label split on the device
-                        raw, _ = shard(batch.raw)
-                        params, _ = shard(batch.params)
-                        xb, yb = dm.augment_u8(raw, params, batch.output_size, batch.label_index, contrast_channels=batch.contrast_channels)
-                        if batch.affine is not None:
-                            xb, yb = dm.affine(xb, yb, shard(batch.affine)[0])
-                        if batch.warp is not None:
-                            xb, yb = dm.warp(xb, yb, shard(batch.warp[0])[0], shard(batch.warp[1])[0])
-                        if batch.intrawarp is not None:
-                            xb, yb = dm.warp_groups(xb, yb, batch.intrawarp[2], shard(batch.intrawarp[0])[0], shard(batch.intrawarp[1])[0],
-                                                    label_index=batch.label_index)
-                        if batch.intensity is not None:
-                            xb = dm.intensity(xb, shard(batch.intensity)[0])
-                        out = dm.train_step_dev(xb, yb, len(raw), self.learning_rate, cfg, want_out=True)
+                        xb, yb = augment_on_device(dm, batch, shard)
+                        out = dm.train_step_dev(xb, yb, xb.shape[0], self.learning_rate, cfg, want_out=True)
                     else:
                         x, y = shard(np.asarray(batch[0]), np.asarray(batch[1]))
                         out = dm.train_step(x, y, self.learning_rate, cfg)

@@ -158,6 +158,37 @@ def test_workload_shape_with_drawn_matrices(gpu, model):
 
 
 @pytest.mark.gpu
+def test_six_calls_in_flight_and_a_batch_that_outgrows_the_ring(gpu):
+    """max_batch 2, 8 x 8 x 2: six calls of batch 2 back to back, more than the pinned ring has rows, through ONE host array that is
+    overwritten as soon as a call returns, then a seventh of batch 5 (its matrices outgrow the ring's rows), ONE sync, and all seven
+    against the oracle of their own matrices"""
+    m = gpu.DeviceModel('unet', 2, 8, 8, 2, n_filters_first=2, n_downsample=1, rate=2, kernel_size=3, conv_stride=1, padding='same')
+    try:
+        h, w, c = 8, 8, 2
+        mats = [np.stack([O.matrix(h, w, 20.0 * i - 50.0 + 7.0 * b, 0.8 + 0.07 * i, (0.5 * i - 1.0, 0.25 * b - 0.5 * i))
+                          for b in range(2 if i < 6 else 5)]) for i in range(7)]
+        small, big = _planes(2, h, w, c, seed=20), _planes(5, h, w, c, seed=21)
+        planes = [small] * 6 + [big]
+        dev = {2: tuple(map(gpu.DeviceBuffer, small)), 5: tuple(map(gpu.DeviceBuffer, big))}
+        outs = [(gpu.DeviceBuffer(np.zeros_like(x)), gpu.DeviceBuffer(np.zeros_like(y))) for x, y in planes]
+        hosts = {2: np.zeros((2, 2, 3)), 5: np.zeros((5, 2, 3))}
+        dptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))        # noqa: E731
+        m.sync()
+        for mt, (xo, yo) in zip(mats, outs):
+            (xd, yd), host = dev[len(mt)], hosts[len(mt)]
+            host[...] = mt
+            assert m.lib.dnnca_affine_f32(m.handle, xd.ptr, yd.ptr, len(mt), h, w, c, dptr(host), xo.ptr, yo.ptr) == 0
+            host[...] = np.nan                                          # the caller's array is free when the call returns
+        m.sync()
+        for i, (mt, (x, y), (xo, yo)) in enumerate(zip(mats, planes, outs)):
+            got = xo.to_host()
+            _held_to_oracle(x, y, mt, got, yo.to_host(), 'call %d of seven' % i)
+            assert np.abs(got - x).max() > 0.05
+    finally:
+        m.close()
+
+
+@pytest.mark.gpu
 def test_refusals_leave_the_outputs_and_the_profile_alone(gpu, model):
     B, h, w, c = 3, 5, 7, 3
     x, y = _planes(B, h, w, c, seed=10)

@@ -164,6 +164,33 @@ def test_calls_repeat_and_six_in_flight_keep_their_own_records(gpu, model):
 
 
 @pytest.mark.gpu
+def test_six_calls_in_flight_and_a_batch_that_outgrows_the_ring(gpu):
+    """max_batch 2, 8 x 8 x 2: six calls of batch 2 back to back through ONE host array that is overwritten as soon as a call
+    returns, then a seventh of batch 5 (its records outgrow the ring's rows), ONE sync, and all seven against the oracle of their
+    own records"""
+    m = gpu.DeviceModel('unet', 2, 8, 8, 2, n_filters_first=2, n_downsample=1, rate=2, kernel_size=3, conv_stride=1, padding='same')
+    try:
+        cases = [O.case((2 if i < 6 else 5, 8, 8, 2), which, seed=20 + i) for i, which in enumerate(O.TERMS)]
+        assert len(cases) == 7
+        ins = [gpu.DeviceBuffer(x) for x, _ in cases]
+        outs = [gpu.DeviceBuffer(np.zeros_like(x)) for x, _ in cases]
+        hosts = {2: np.zeros((2, 2, 32), np.uint32), 5: np.zeros((5, 2, 32), np.uint32)}
+        m.sync()
+        for (x, rec), xd, out in zip(cases, ins, outs):
+            host = hosts[len(rec)]
+            host[...] = rec
+            assert m.lib.dnnca_intensity_f32(m.handle, xd.ptr, *x.shape, host.ctypes.data_as(C.POINTER(C.c_uint32)), out.ptr) == 0
+            host[...] = 0                                               # the caller's array is free when the call returns
+        m.sync()
+        for i, ((x, rec), out) in enumerate(zip(cases, outs)):
+            got = out.to_host()
+            _held_to_oracle(x, rec, got, 'call %d of seven' % i)
+            assert np.abs(got - x).max() > 1e-3
+    finally:
+        m.close()
+
+
+@pytest.mark.gpu
 def test_refusals_leave_the_output_and_the_profile_alone(gpu, model):
     B, h, w, c = 2, 5, 7, 3
     x = np.random.default_rng(10).random((B, h, w, c)).astype(np.float32)
