@@ -199,6 +199,9 @@ SIGNATURES = {
     'dnnca_model_set_optimizer': (C.c_int, [_VP, C.POINTER(OptimizerCfg), C.POINTER(C.c_uint8), C.c_int]),
     'dnnca_last_grad_norm': (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
     'dnnca_apply_gradients': (C.c_int, [_VP, _FP, C.c_int64, C.c_float]),
+    'dnnca_model_set_accumulation': (C.c_int, [_VP, C.c_int]),
+    'dnnca_get_accumulation': (C.c_int, [_VP, _FP, C.c_int64, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'dnnca_grad_accumulate_of': (C.c_int, [_VP, _FP, _FP, C.c_int64, C.c_int, _FP]),
     'dnnca_model_set_ema': (C.c_int, [_VP, C.c_float, C.c_int]),
     'dnnca_get_ema': (C.c_int, [_VP, _FP, C.c_int64, C.POINTER(C.c_int64)]),
     'dnnca_set_ema_state': (C.c_int, [_VP, _FP, C.c_int64, C.c_int64]),
@@ -287,6 +290,7 @@ SIGNATURES = {
     'dnnca_comm_init': (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_size_t]),
     'dnnca_comm_world': (C.c_int, [_VP, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'dnnca_comm_collectives': (C.c_int, [_VP, C.POINTER(C.c_int)]),
+    'dnnca_comm_collective_floats': (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     'dnnca_comm_broadcast_weights': (C.c_int, [_VP, C.c_int]),
     'dnnca_comm_average_state': (C.c_int, [_VP]),
     'dnnca_comm_allreduce_host': (C.c_int, [_VP, C.POINTER(C.c_double), C.c_int64, C.c_int]),

@@ -10,6 +10,7 @@ namespace dnnca {
 int fast_prepare(Model* m, bool train_step);
 int fast_finish_backward(Model* m);   // folds the weight-gradient slabs into the flat gradient vector (or defers: Step::fold_deferred)
 int fast_fold_adam(Model* m, float lr_t, float ema_om, const dnnca_loss_cfg& cfg, double n_label, double inv_batch_hw);   // the deferred fold + Adam + step outputs in one launch
+int fast_fold_acc(Model* m, bool first, const dnnca_loss_cfg& cfg, double n_label, double inv_batch_hw);   // gradient accumulation: the deferred fold + accumulate + step outputs in one launch
 void fast_release(Model* m);    // drop the model's pixel-group plan (Model::plan_pg)
 unsigned long long* fast_debug_stamps(const Model* m);   // tuning aid: in-kernel s_memtime stamps (DNNCA_STAMPS); nullptr: none (asking creates nothing)
 // `pool`: a max-pool op fused into the conv's epilogue (fast_pool_fusable), or nullptr

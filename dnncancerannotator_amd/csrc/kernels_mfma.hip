@@ -1188,11 +1188,15 @@ struct AdamTail {
     float* out5;
     float* e;          // k_pg_fold<true> only: the weight average and 1 - decay of this step (Model::ema)
     float om;
+    float* acc;        // k_pg_fold<false, ACC> only: the gradient accumulator (Model::accum); p is nullptr there
 };
 // EMA: the thread that stores p[i] also moves the weight average towards it, e <- e - om * (e - p) (g_adam's arithmetic again)
-template <bool EMA>
+// ACC (gradient accumulation, micro-steps that end in no update): the thread that finishes a gradient also adds it to the
+// accumulator, 1: acc <- g (the cycle's first micro-step), 2: acc <- acc + g -- the float32 add grad_accumulate makes of the stored value
+template <bool EMA, int ACC = 0>
 __device__ __forceinline__ void fold_out(float* __restrict__ grads, const AdamTail& ad, int i, float gi) {
     grads[i] = gi;
+    if (ACC) ad.acc[i] = ACC == 1 ? gi : ad.acc[i] + gi;
     if (ad.p) {
         const float mi = ad.m[i] * ad.b1 + gi * (1.f - ad.b1);
         const float vi = ad.v[i] * ad.b2 + (gi * gi) * (1.f - ad.b2);
@@ -1207,7 +1211,7 @@ __device__ __forceinline__ void fold_out(float* __restrict__ grads, const AdamTa
     }
 }
 
-template <bool EMA>
+template <bool EMA, int ACC = 0>
 __global__ __launch_bounds__(256) void k_pg_fold(const FoldDesc* __restrict__ descs, const float* __restrict__ slabs,
                                                  float* __restrict__ grads, int nfolds, HeadTail h, AdamTail ad) {
     __shared__ float Dl[7 * 256];
@@ -1224,11 +1228,11 @@ __global__ __launch_bounds__(256) void k_pg_fold(const FoldDesc* __restrict__ de
             __syncthreads();
         }
         if (threadIdx.x == 0) {
-            if (k < h.C) fold_out<EMA>(grads, ad, (int)(h.dw - grads) + k, (float)red[0]);       // (h.dw / h.dbias point into grads)
-            else if (k == h.C) fold_out<EMA>(grads, ad, (int)(h.dbias - grads), (float)red[0]);
+            if (k < h.C) fold_out<EMA, ACC>(grads, ad, (int)(h.dw - grads) + k, (float)red[0]);       // (h.dw / h.dbias point into grads)
+            else if (k == h.C) fold_out<EMA, ACC>(grads, ad, (int)(h.dbias - grads), (float)red[0]);
             else {
                 h.scalars[3] = red[0];
-                if (ad.p) {          // the step outputs (no L2 penalty on this path: scalars[4] == 0)
+                if (ad.p || ACC) {          // the step outputs (no L2 penalty on this path: scalars[4] == 0)
                     const double lsum = h.scalars[0];
                     float wgt;
                     if (ad.cfg.has_weight) wgt = ad.cfg.weight;
@@ -1277,12 +1281,12 @@ __global__ __launch_bounds__(256) void k_pg_fold(const FoldDesc* __restrict__ de
         // rows m = (a, e, co) are exactly the [r, r, Cout, Cin] kernel rows; column Cin is the all-ones (bias) column
         const int nwt = 4 * d.CO * d.C;
         if (o < nwt) {
-            fold_out<EMA>(grads, ad, d.w_off + o, Dl[slab_index(o / d.C, o % d.C)]);
+            fold_out<EMA, ACC>(grads, ad, d.w_off + o, Dl[slab_index(o / d.C, o % d.C)]);
         } else if (o < nwt + d.CO) {
             const int co = o - nwt;
             float a = 0.f;
             for (int ae = 0; ae < 4; ++ae) a += Dl[slab_index(ae * d.CO + co, d.C)];
-            fold_out<EMA>(grads, ad, d.b_off + co, a);
+            fold_out<EMA, ACC>(grads, ad, d.b_off + co, a);
         }
         return;
     }
@@ -1295,11 +1299,11 @@ __global__ __launch_bounds__(256) void k_pg_fold(const FoldDesc* __restrict__ de
         int co = o % d.CO, ci = (o / d.CO) % d.C, tap = o / (d.CO * d.C);
         int dy = tap / 3, kx = tap % 3;
         for (int dx = 0; dx < d.G; ++dx) acc += Dl[slab_index(dy * WR + (dx + kx) * d.C + ci, dx * d.CO + co)];
-        fold_out<EMA>(grads, ad, d.w_off + ((tap * d.cin_total) + d.ci_off + ci) * d.CO + co, acc);
+        fold_out<EMA, ACC>(grads, ad, d.w_off + ((tap * d.cin_total) + d.ci_off + ci) * d.CO + co, acc);
     } else {
         int co = o - nw;
         for (int dx = 0; dx < d.G; ++dx) acc += Dl[slab_index(3 * WR, dx * d.CO + co)];
-        fold_out<EMA>(grads, ad, d.b_off + co, acc);
+        fold_out<EMA, ACC>(grads, ad, d.b_off + co, acc);
     }
 }
 
@@ -2093,9 +2097,14 @@ int fast_finish_backward(Model* m) {
         m->step.head_pending.partials = nullptr;
     }
     // single-replica train step whose every gradient (and the loss) comes out of this launch: wait for optimizer_step and let the
-    // fold apply Adam as well (fast_fold_adam).  A set optimizer (Model::opt) declines: its launches need the folded gradient
-    if (extra && !m->comm && !m->dry && m->merged_launches() && m->desc.l2 == 0.f && pl.fold_outputs + h.C + 1 == m->nT &&
-        !m->sw.no_fold_adam && !m->opt.on) {
+    // fold apply Adam as well (fast_fold_adam).  A set optimizer (Model::opt) declines: its launches need the folded gradient.
+    // Gradient accumulation (Model::accum) declines too: the update takes the accumulator.  Its micro-steps that end in no update
+    // defer under the same conditions, and the fold feeds the accumulator and writes the step outputs (fast_fold_acc); the dry
+    // plan lists that arm as well: it is the micro-step that would run next
+    const bool whole = extra && !m->comm && m->merged_launches() && m->desc.l2 == 0.f && pl.fold_outputs + h.C + 1 == m->nT;
+    const bool defer = m->accum.a ? !m->sw.no_fold_acc && m->accum.pos + 1 < m->accum.steps
+                                  : !m->dry && !m->sw.no_fold_adam && !m->opt.on;
+    if (whole && defer) {
         m->step.fold_deferred = true;
         pl.pending_head = h;
         return DNNCA_OK;
@@ -2121,6 +2130,24 @@ int fast_fold_adam(Model* m, float lr_t, float ema_om, const dnnca_loss_cfg& cfg
     LAUNCH(m, "pg_fold_adam", 28.0 * m->nT, 10.0 * m->nT,
            hipLaunchKernelGGL(k_pg_fold<false>, dim3((unsigned)pl.folds.size() + h.C + 2, pl.fold_chunks), dim3(256), 0, m->stream,
                               pl.folds_dev, pl.slabs, m->g, (int)pl.folds.size(), h, ad));
+    return DNNCA_OK;
+}
+
+// the deferred fold of a micro-step that ends in no update (gradient accumulation): fold + accumulate + step outputs in one launch
+int fast_fold_acc(Model* m, bool first, const dnnca_loss_cfg& cfg, double n_label, double inv_batch_hw) {
+    const PgPlan& pl = pg_find(m);
+    const HeadTail h = pl.pending_head;
+    m->step.fold_deferred = false;
+    AdamTail ad{};
+    ad.cfg = cfg; ad.n_label = n_label; ad.inv_batch_hw = inv_batch_hw; ad.out5 = m->out5; ad.acc = m->accum.a;
+    const dim3 grid((unsigned)pl.folds.size() + h.C + 2, pl.fold_chunks);
+    if (first) {
+        LAUNCH(m, "pg_fold_acc", 4.0 * m->nT, 0,
+               hipLaunchKernelGGL((k_pg_fold<false, 1>), grid, dim3(256), 0, m->stream, pl.folds_dev, pl.slabs, m->g, (int)pl.folds.size(), h, ad));
+        return DNNCA_OK;
+    }
+    LAUNCH(m, "pg_fold_acc", 8.0 * m->nT, 1.0 * m->nT,
+           hipLaunchKernelGGL((k_pg_fold<false, 2>), grid, dim3(256), 0, m->stream, pl.folds_dev, pl.slabs, m->g, (int)pl.folds.size(), h, ad));
     return DNNCA_OK;
 }
 

@@ -105,6 +105,7 @@ struct StepSwitches {
     // fallbacks: the fused / riding launch is off and the launches it replaced run
     bool no_fused = false, no_fused_bwd = false, no_first3 = false, no_first3f = false, no_up3f = false, no_tail3 = false;
     bool no_tcf = false, no_tcm = false, no_tconv_ride = false, no_prep_ride = false, no_fold_adam = false, no_pool_fold = false;
+    bool no_fold_acc = false;      // gradient accumulation: pg_fold + grad_accumulate instead of the fused pg_fold_acc
     bool no_bwd3v = false, no_vw = false, no_head_in_conv = false, no_label_fusion = false, no_wg_stream = false;
     bool pgbwd_old = false;      // pgbwd_tc_3x2_3 without the counted waits (the kernel the A/B of that change compares against)
     // opt-in
@@ -224,7 +225,13 @@ struct Model {
         int nchunks = 0, nvars = 0;
         bool norm_clip() const { return on && (cfg.clipnorm > 0.f || cfg.global_clipnorm > 0.f); }
     } opt;
-    int opt_launches(float lr, float lr_t, float gscale, float om);      // optimizer_step's launches while opt.on
+    int opt_launches(const float* grad, float lr, float lr_t, float gscale, float om);      // optimizer_step's launches while opt.on
+    // gradient accumulation (dnnca_model_set_accumulation, accum.h): one optimizer update per `steps` micro-steps.  a [nT + 4]: the
+    // float32 sum of the cycle's gradients (a <- g on its first micro-step, a <- a + g after; slot nT carries the loss through the
+    // all-reduce under data parallel); pos: micro-steps in `a` (0: between cycles, `a` then holds the sum that was last applied).
+    // steps == 1: off, a == nullptr, and every launch is the one it was.  `g` is never overwritten by the sum
+    struct Accum { float* a = nullptr; int steps = 1; int pos = 0; } accum;
+    int accumulate(bool reduce);         // optimizer_step's first part while accum.a: the launch (unless the fold did it) and the reduction
     // What one step hands from launch to launch (and from forward() to loss_and_backward() to optimizer_step()).  forward() begins
     // a pass with `step = Step{}`, in front of fast_prepare: nothing of an earlier step, finished or stopped on an error, survives
     // it.  Every other write is a launch setting a hand-over or the launch it is meant for consuming it.  (The hand-overs inside a
@@ -245,6 +252,7 @@ struct Model {
         // encoder block's strip kernel takes it along as extra blocks; any other launch flushes it first (LAUNCH)
         void (*prep_flush)(Model*) = nullptr;
         bool fold_deferred = false;          // the slab fold waits for optimizer_step: fold + Adam + step outputs in one launch (fast_fold_adam)
+        bool fold_accumulated = false;       // gradient accumulation: the fold has added this micro-step's gradient to Model::accum (pg_fold_acc)
         const Op* tail_done = nullptr;       // the conv whose backward already ran inside the forward pass (fast_tail3)
         struct PoolFold { const Op* conv = nullptr; const Op* pool = nullptr; } pool_fold;     // fast_pool_fold -> fast_conv_bwd hand-over
         // the forward pass of a train step ran the label statistics (labels_done) and maybe the head (done) on the labels y
@@ -275,6 +283,7 @@ struct Model {
     hipEvent_t ev_bucket = nullptr, ev_comm_done = nullptr;
     int bucket_state = 0;                // 0 undecided, 1 the op order finalises a suffix (bucketing possible), -1 it does not
     int collectives_last_step = 0;       // gradient all-reduce calls issued by the last train step
+    int64_t collective_floats_last_step = 0;      // floats the last of them covered (the single-call arms; a bucketed step: its last bucket)
     int send_bucket(int64_t lo, int64_t hi);
     // Input pipeline (dnnca_stage_*): a batch travels host -> HBM on its own copy stream into one of a ring of staging slots
     // while the main stream is still working on the previous step; the main stream waits for the slot's `uploaded` event, runs

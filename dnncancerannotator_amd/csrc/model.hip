@@ -14,6 +14,7 @@
 #include "fast.h"
 #include "kernels.h"
 #include "optim.h"
+#include "accum.h"
 #include "region.h"
 #include "region_loss.h"
 #include "boundary.h"
@@ -50,6 +51,7 @@ StepSwitches step_switches() {
     s.no_tconv_ride = on("DNNCA_NO_TCONV_RIDE");
     s.no_prep_ride = on("DNNCA_NO_PREP_RIDE");
     s.no_fold_adam = on("DNNCA_NO_FOLD_ADAM");
+    s.no_fold_acc = on("DNNCA_NO_FOLD_ACC");
     s.no_pool_fold = on("DNNCA_NO_POOL_FOLD");
     s.no_bwd3v = on("DNNCA_NO_BWD3V");
     s.no_vw = on("DNNCA_NO_VW");
@@ -94,6 +96,7 @@ Model::~Model() {
     ig_release(this);
     for (void* a : allocs) (void)hipFree(a);
     if (ema.e) (void)hipFree(ema.e);
+    if (accum.a) (void)hipFree(accum.a);
     if (opt.table) (void)hipFree(opt.table);
     if (tta_io) (void)hipFree(tta_io);
     if (calib_ws) (void)hipFree(calib_ws);
@@ -1053,7 +1056,8 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
         // folded into the gradient vector by the launch that ENDS the backward pass; 34.7 KB anyway) and not with an L2
         // regulariser (its gradient is added after the loop).
         collectives_last_step = 0;
-        if (comm && !dry && (size_t)nT * 4 > (1u << 20) && desc.l2 == 0.f && !head_defer_ok) {
+        // Nor with gradient accumulation: buckets would reduce this micro-step's g, not the accumulator.
+        if (comm && !dry && (size_t)nT * 4 > (1u << 20) && desc.l2 == 0.f && !head_defer_ok && !accum.a) {
             if (bucket_state == 0) {
                 int64_t prev = -1;
                 bucket_state = 1;
@@ -1205,8 +1209,9 @@ int Model::loss_and_backward(const float* y_dev, int B, const dnnca_loss_cfg& cf
                    g_l2(stream, (size_t)pi.size, p + pi.offset, g + pi.offset, desc.l2, scalars));
         }
     }
-    if (backward && !comm && !dry && merged_launches()) {
-        // optimizer_step() follows every backward pass: its Adam launch also writes the step outputs (one launch fewer)
+    if (backward && !comm && merged_launches() && (!dry || step.fold_deferred)) {
+        // optimizer_step() follows every backward pass: its Adam launch also writes the step outputs (one launch fewer).  (In a dry
+        // run only the deferred fold of an accumulating micro-step takes them: the plan lists that launch.)
         step.fin_pending.on = true;
         step.fin_pending.cfg = cfg;
         step.fin_pending.n_label = (double)npix;
@@ -1434,6 +1439,7 @@ int Model::send_bucket(int64_t lo, int64_t hi) {
     ncclResult_t r = ncclAllReduce(g + lo, g + lo, (size_t)(hi - lo), ncclFloat, ncclSum, comm, comm_stream);
     if (r != ncclSuccess) { set_error("ncclAllReduce(bucket): %s", ncclGetErrorString(r)); return DNNCA_ECOMM; }
     ++collectives_last_step;
+    collective_floats_last_step = hi - lo;
     return DNNCA_OK;
 }
 
@@ -1453,10 +1459,10 @@ int Model::ema_refuse(const char* what) {
 
 // the launches of a set optimizer (Model::opt): the norm of the gradient the optimizer receives and the clip scales, when a clip by
 // norm is on, then the one pass that applies the update -- and, on a single replica, writes the step outputs
-int Model::opt_launches(float lr, float lr_t, float gscale, float om) {
+int Model::opt_launches(const float* grad, float lr, float lr_t, float gscale, float om) {
     const dnnca_optimizer_cfg& c = opt.cfg;
     if (opt.norm_clip()) {
-        LAUNCH(this, "grad_sqnorm", 4.0 * nT, 3.0 * nT, g_grad_sqnorm(stream, opt.chunks, opt.nchunks, g, gscale, c.clipvalue, opt.partials));
+        LAUNCH(this, "grad_sqnorm", 4.0 * nT, 3.0 * nT, g_grad_sqnorm(stream, opt.chunks, opt.nchunks, grad, gscale, c.clipvalue, opt.partials));
         LAUNCH(this, "grad_clip_scale", 16.0 * opt.nchunks, 2.0 * opt.nchunks,
                g_grad_clip_scale(stream, opt.var_first, opt.nvars, opt.nchunks, opt.partials, c.clipnorm, c.global_clipnorm, opt.scales,
                                  opt.norms));
@@ -1483,7 +1489,44 @@ int Model::opt_launches(float lr, float lr_t, float gscale, float om) {
     const double fl = (sgd ? 4.0 : (c.kind == DNNCA_OPT_ADAMW ? 12.0 : 10.0)) + (ema.e ? 3.0 : 0.0);
     static const char* const names[3][2] = {{"opt_adam", "opt_adam_ema"}, {"opt_adamw", "opt_adamw_ema"}, {"opt_sgd", "opt_sgd_ema"}};
     LAUNCH(this, names[c.kind][ema.e ? 1 : 0], per * nT, fl * nT,
-           g_opt_step(stream, c.kind, opt.chunks, opt.nchunks, p, g, m, v, ema.e, a, fin));
+           g_opt_step(stream, c.kind, opt.chunks, opt.nchunks, p, grad, m, v, ema.e, a, fin));
+    return DNNCA_OK;
+}
+
+// Gradient accumulation, the first part of optimizer_step while accum.a: this micro-step's gradient goes into the accumulator
+// (grad_accumulate, unless the deferred fold takes it along: pg_fold_acc), and under a communicator the reduction follows on the
+// model's stream: the loss slot alone on a micro-step that ends in no update (the reported loss stays the cross-replica mean), the
+// accumulator with the loss slot behind it on the one that does.  Moves accum.pos (never in a dry plan run).  Returns with
+// accum.pos == 0 when the update is due
+int Model::accumulate(bool reduce) {
+    const int j = accum.pos + 1;                       // this micro-step's place in the cycle, 1 .. steps
+    const bool last = j == accum.steps, first = j == 1;
+    const bool reduces = reduce && comm && !dry;
+    if (step.fold_deferred) {
+        if (!step.fin_pending.on || last) { set_error("internal: deferred gradient fold without an accumulating micro-step"); return DNNCA_ESTATE; }
+        step.fin_pending.on = false;          // consumed: this launch writes the step outputs
+        DN_TRY(fast_fold_acc(this, first, step.fin_pending.cfg, step.fin_pending.n_label, step.fin_pending.inv_batch_hw));
+    } else {
+        AdamFinalize fin{};
+        if (!last && step.fin_pending.on) {      // no optimizer launch follows: this one writes the step outputs
+            step.fin_pending.on = false;
+            fin = AdamFinalize{scalars, step.fin_pending.cfg, step.fin_pending.n_label, step.fin_pending.inv_batch_hw, out5};
+        }
+        // bytes per parameter: g read and a written; a read as well once the cycle has begun
+        LAUNCH(this, "grad_accumulate", (first ? 8.0 : 12.0) * nT, (first ? 0.0 : 1.0) * nT,
+               g_grad_accumulate(stream, (size_t)nT, accum.a, g, first, fin, reduces && last));
+    }
+    if (reduces) {
+        // the loss slot travels as a[nT] on the update micro-step: one all-reduce over [accumulated gradients ..., loss]
+        float* buf = last ? accum.a : out5;
+        const size_t count = last ? (size_t)nT + 1 : 1;
+        ncclResult_t r = ncclAllReduce(buf, buf, count, ncclFloat, ncclSum, comm, stream);
+        if (r != ncclSuccess) { set_error("ncclAllReduce(accumulation): %s", ncclGetErrorString(r)); return DNNCA_ECOMM; }
+        collectives_last_step = 1;
+        collective_floats_last_step = (int64_t)count;
+        if (last) HIP_TRY(hipMemcpyAsync(out5, accum.a + nT, 4, hipMemcpyDeviceToDevice, stream));
+    }
+    if (!dry) accum.pos = last ? 0 : j;
     return DNNCA_OK;
 }
 
@@ -1491,7 +1534,14 @@ int Model::opt_launches(float lr, float lr_t, float gscale, float om) {
 int Model::optimizer_step(float lr, bool reduce) {
     cur_op = nullptr;
     float gscale = 1.0f;
-    if (reduce && comm && !dry && step.bucketing) {
+    const float* grad = g;          // what the optimizer receives: this step's gradient, or the accumulator at the end of a cycle
+    if (accum.a) {
+        const bool last = accum.pos + 1 == accum.steps;
+        DN_TRY(accumulate(reduce));
+        if (!last) return DNNCA_OK;          // nothing else changes: weights, slots, iterations and the weight average stay
+        grad = accum.a;
+        gscale = (float)(1.0 / ((double)accum.steps * (double)(reduce && comm && !dry ? world : 1)));      // the mean, rounded once
+    } else if (reduce && comm && !dry && step.bucketing) {
         // the backward pass has sent the finalised suffix in buckets; what is left -- the first layers and the step's loss in the
         // tail -- follows on the same (communication) stream, and Adam waits for all of it
         step.bucketing = false;
@@ -1505,6 +1555,7 @@ int Model::optimizer_step(float lr, bool reduce) {
         ncclResult_t r = ncclAllReduce(g, g, (size_t)nT + 1, ncclFloat, ncclSum, comm, stream);
         if (r != ncclSuccess) { set_error("ncclAllReduce: %s", ncclGetErrorString(r)); return DNNCA_ECOMM; }
         collectives_last_step = 1;
+        collective_floats_last_step = nT + 1;
         gscale = 1.0f / (float)world;
     }
     iterations += dry ? 0 : 1;
@@ -1516,25 +1567,25 @@ int Model::optimizer_step(float lr, bool reduce) {
         return fast_fold_adam(this, lr_t, om, step.fin_pending.cfg, step.fin_pending.n_label, step.fin_pending.inv_batch_hw);
     }
     if (step.fold_deferred) { set_error("internal: deferred gradient fold without a single-replica optimizer step"); return DNNCA_ESTATE; }
-    if (opt.on) return opt_launches(lr, lr_t, gscale, om);
+    if (opt.on) return opt_launches(grad, lr, lr_t, gscale, om);
     if (step.fin_pending.on) {
         step.fin_pending.on = false;
         if (ema.e) {
             LAUNCH(this, "g_adam_ema", 36.0 * nT, 13.0 * nT,
-                   g_adam_finalize(stream, (size_t)nT, p, g, m, v, lr_t, beta1, beta2, eps, gscale, scalars, step.fin_pending.cfg,
+                   g_adam_finalize(stream, (size_t)nT, p, grad, m, v, lr_t, beta1, beta2, eps, gscale, scalars, step.fin_pending.cfg,
                                    step.fin_pending.n_label, step.fin_pending.inv_batch_hw, out5, ema.e, om));
             return DNNCA_OK;
         }
         LAUNCH(this, "g_adam", 28.0 * nT, 10.0 * nT,
-               g_adam_finalize(stream, (size_t)nT, p, g, m, v, lr_t, beta1, beta2, eps, gscale, scalars, step.fin_pending.cfg,
+               g_adam_finalize(stream, (size_t)nT, p, grad, m, v, lr_t, beta1, beta2, eps, gscale, scalars, step.fin_pending.cfg,
                                step.fin_pending.n_label, step.fin_pending.inv_batch_hw, out5));
         return DNNCA_OK;
     }
     if (ema.e) {
-        LAUNCH(this, "g_adam_ema", 36.0 * nT, 13.0 * nT, g_adam(stream, (size_t)nT, p, g, m, v, lr_t, beta1, beta2, eps, gscale, ema.e, om));
+        LAUNCH(this, "g_adam_ema", 36.0 * nT, 13.0 * nT, g_adam(stream, (size_t)nT, p, grad, m, v, lr_t, beta1, beta2, eps, gscale, ema.e, om));
         return DNNCA_OK;
     }
-    LAUNCH(this, "g_adam", 28.0 * nT, 10.0 * nT, g_adam(stream, (size_t)nT, p, g, m, v, lr_t, beta1, beta2, eps, gscale));
+    LAUNCH(this, "g_adam", 28.0 * nT, 10.0 * nT, g_adam(stream, (size_t)nT, p, grad, m, v, lr_t, beta1, beta2, eps, gscale));
     return DNNCA_OK;
 }
 
@@ -1621,7 +1672,9 @@ static int copy_flat(Model* M, float* dev, int64_t have, const float* src, float
 int dnnca_set_params(void* model, const float* flat, int64_t n) {
     MODEL(model);
     DN_TRY(M->ema_refuse("dnnca_set_params"));
-    return copy_flat(M, M->p, M->nT, flat, nullptr, n);
+    DN_TRY(copy_flat(M, M->p, M->nT, flat, nullptr, n));
+    M->accum.pos = 0;          // new weights: a partial cycle of gradients taken at the old ones is dropped
+    return DNNCA_OK;
 }
 int dnnca_get_params(void* model, float* flat, int64_t n) { MODEL(model); return copy_flat(M, M->p, M->nT, nullptr, flat, n); }
 int dnnca_set_state(void* model, const float* flat, int64_t n) { MODEL(model); return copy_flat(M, M->state, M->nS, flat, nullptr, n); }
@@ -1634,6 +1687,7 @@ int dnnca_set_opt_state(void* model, const float* m, const float* v, int64_t n, 
     DN_TRY(copy_flat(M, M->m, M->nT, m, nullptr, n));
     DN_TRY(copy_flat(M, M->v, M->nT, v, nullptr, n));
     M->iterations = iterations;
+    M->accum.pos = 0;
     return DNNCA_OK;
 }
 
@@ -1800,6 +1854,58 @@ int dnnca_apply_gradients(void* model, const float* g_host, int64_t n, float lr)
     HIP_TRY(hipMemcpyAsync(M->g, g_host, (size_t)n * 4, hipMemcpyHostToDevice, M->stream));
     HIP_TRY(hipStreamSynchronize(M->stream));          // the caller's vector may be reused at once
     return M->optimizer_step(lr, false);
+}
+
+// ---- gradient accumulation (Model::accum, accum.h) ----------------------------------------------------------------------------
+int dnnca_model_set_accumulation(void* model, int steps) {
+    MODEL(model);
+    if (steps < 1 || steps > kAccumMaxSteps) { set_error("dnnca_model_set_accumulation: steps %d outside [1, %d]", steps, kAccumMaxSteps); return DNNCA_EINVAL; }
+    DN_TRY(M->ema_refuse("dnnca_model_set_accumulation"));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    if (steps == 1) {
+        if (M->accum.a) HIP_TRY(hipFree(M->accum.a));
+        M->accum = Model::Accum{};
+        return DNNCA_OK;
+    }
+    if (!M->accum.a) {
+        // nT floats, the loss slot behind them, padding to whole float4s; zeroed: readable before the first micro-step
+        HIP_TRY(hipMalloc((void**)&M->accum.a, (size_t)(M->nT + 4) * 4));
+        HIP_TRY(hipMemsetAsync(M->accum.a, 0, (size_t)(M->nT + 4) * 4, M->stream));
+        HIP_TRY(hipStreamSynchronize(M->stream));
+    }
+    M->accum.steps = steps;
+    M->accum.pos = 0;          // a partial cycle is discarded: the next micro-step starts one (a <- g)
+    return DNNCA_OK;
+}
+
+int dnnca_get_accumulation(void* model, float* flat, int64_t n, int* steps, int* position) {
+    MODEL(model);
+    if (!M->accum.a) { set_error("dnnca_get_accumulation: gradient accumulation is off (dnnca_model_set_accumulation)"); return DNNCA_ESTATE; }
+    if (flat) DN_TRY(copy_flat(M, M->accum.a, M->nT, nullptr, flat, n));
+    else HIP_TRY(hipStreamSynchronize(M->stream));
+    if (steps) *steps = M->accum.steps;
+    if (position) *position = M->accum.pos;
+    return DNNCA_OK;
+}
+
+int dnnca_grad_accumulate_of(void* model, const float* acc_host, const float* g_host, int64_t n, int first, float* out_host) {
+    MODEL(model);
+    if (n < 1 || n >= (int64_t)1 << 40) { set_error("dnnca_grad_accumulate_of: %lld elements", (long long)n); return DNNCA_EINVAL; }
+    if (!g_host || !out_host || (!first && !acc_host)) { set_error("dnnca_grad_accumulate_of: null buffer"); return DNNCA_EINVAL; }
+    float* dev = nullptr;          // [a | g], each n + 4 floats: whole float4s and the (unused) loss slot
+    const size_t row = (size_t)n + 4;
+    HIP_TRY(hipMalloc((void**)&dev, 2 * row * 4));
+    hipError_t e = hipSuccess;
+    if (!first) e = hipMemcpyAsync(dev, acc_host, (size_t)n * 4, hipMemcpyHostToDevice, M->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dev + row, g_host, (size_t)n * 4, hipMemcpyHostToDevice, M->stream);
+    if (e == hipSuccess) {
+        g_grad_accumulate(M->stream, (size_t)n, dev, dev + row, first != 0, AdamFinalize{}, false);
+        e = hipMemcpyAsync(out_host, dev, (size_t)n * 4, hipMemcpyDeviceToHost, M->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(M->stream);
+    (void)hipFree(dev);
+    if (e != hipSuccess) { set_error("dnnca_grad_accumulate_of: %s", hipGetErrorString(e)); return DNNCA_EHIP; }
+    return DNNCA_OK;
 }
 
 }  // extern "C"
@@ -2360,6 +2466,13 @@ int dnnca_comm_collectives(void* model, int* count) {
     MODEL(model);
     if (!count) return DNNCA_EINVAL;
     *count = M->collectives_last_step;
+    return DNNCA_OK;
+}
+
+int dnnca_comm_collective_floats(void* model, int64_t* count) {
+    MODEL(model);
+    if (!count) return DNNCA_EINVAL;
+    *count = M->collective_floats_last_step;
     return DNNCA_OK;
 }
 

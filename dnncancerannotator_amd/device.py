@@ -404,6 +404,33 @@ class DeviceModel:
         g = as_f32(g).ravel()
         check(self.lib.dnnca_apply_gradients(self.handle, fptr(g), g.size, float(lr)))
 
+    # ---- gradient accumulation (dnnca_model_set_accumulation) -------------------------------------------------------
+    def set_accumulation(self, steps):
+        """steps 2..4096: every later train_step / apply_gradients is a micro-step that adds its gradient to a device-side float32
+        accumulator, and every steps-th one applies the optimizer to their mean (one iteration, one weight-average update per
+        cycle).  steps 1 drops it: the model runs the launches it ran before.  Discards a partial cycle; waits for the stream"""
+        check(self.lib.dnnca_model_set_accumulation(self.handle, int(steps)))
+
+    def get_accumulation(self):
+        """(the accumulator as a flat float32 vector, steps, position): position micro-steps are in it; right after an update
+        position is 0 and the vector is the sum that was applied.  Waits for the stream"""
+        out = np.empty(self.n_trainable, np.float32)
+        steps, pos = C.c_int(), C.c_int()
+        check(self.lib.dnnca_get_accumulation(self.handle, fptr(out), self.n_trainable, C.byref(steps), C.byref(pos)))
+        return out, steps.value, pos.value
+
+    def grad_accumulate_of(self, acc, g, first):
+        """the accumulation kernel alone on host vectors of any length: g when first, else acc + g (acc may be None when first)"""
+        g = as_f32(g).ravel()
+        out = np.empty(g.size, np.float32)
+        if acc is not None:
+            acc = as_f32(acc).ravel()
+            if acc.size != g.size:
+                raise ValueError('grad_accumulate_of: %d accumulator elements for %d gradient elements' % (acc.size, g.size))
+        check(self.lib.dnnca_grad_accumulate_of(self.handle, fptr(acc) if acc is not None else None, fptr(g), g.size,
+                                                int(bool(first)), fptr(out)))
+        return out
+
     # ---- exponential moving average of the weights (dnnca_model_set_ema) ------------------------------------------
     def set_ema(self, decay, warmup=True):
         """decay in (0, 1): every later train step also moves a device-side average of the trainable variables towards the weights
@@ -1092,6 +1119,12 @@ class DeviceModel:
         """gradient all-reduce calls of the last train step (> 1: bucketed)"""
         n = C.c_int()
         check(self.lib.dnnca_comm_collectives(self.handle, C.byref(n)))
+        return n.value
+
+    def comm_collective_floats(self):
+        """floats the last of those calls covered (n_trainable + 1: gradients and the loss slot; 1: the loss slot alone)"""
+        n = C.c_int64()
+        check(self.lib.dnnca_comm_collective_floats(self.handle, C.byref(n)))
         return n.value
 
     def comm_broadcast_weights(self, root=0):

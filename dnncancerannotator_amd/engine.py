@@ -135,6 +135,34 @@ def check_ema(options):
     return dict(decay=float(decay), warmup=warmup, validate=validate)
 
 
+ACCUMULATION_MAX = 4096
+
+
+def check_accumulation(value):
+    """deploy_options.gradient_accumulation_steps -> k, an int in 1..4096 (None, the key absent: 1, nothing changes).  One optimizer
+    update takes the mean gradient of k consecutive train steps (micro-steps).  Bools, floats, strings and values outside the range
+    are a ValueError"""
+    if value is None:
+        return 1
+    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= ACCUMULATION_MAX:
+        raise ValueError('deploy_options.gradient_accumulation_steps must be an integer in 1..%d, got %r' % (ACCUMULATION_MAX, value))
+    return int(value)
+
+
+def check_accumulation_schedule(k, save_freq, max_steps, resumed_step):
+    """train() with k > 1: checkpoints, validation passes and the end of the run must fall between cycles, and a resumed run must
+    start on one; a ValueError that names the numbers otherwise"""
+    if k <= 1:
+        return
+    key = 'deploy_options.gradient_accumulation_steps'
+    if save_freq % k:
+        raise ValueError('%s %d does not divide save_freq %d: a checkpoint would fall inside a cycle' % (key, k, save_freq))
+    if max_steps is not None and max_steps % k:
+        raise ValueError('%s %d does not divide max_steps %d: the run would end inside a cycle' % (key, k, max_steps))
+    if resumed_step % k:
+        raise ValueError('%s %d does not divide the resumed step %d: the checkpoint was written inside a cycle' % (key, k, resumed_step))
+
+
 # deploy_options.optimizer as a mapping: what Keras' optimizers.get takes in model.compile (engine.py:276-284) [TF-2.6]
 OPTIMIZER_KINDS = {'Adam': 'adam', 'AdamW': 'adamw', 'SGD': 'sgd'}
 _CLIP_KEYS = ('clipvalue', 'clipnorm', 'global_clipnorm')
@@ -343,6 +371,8 @@ class TFKerasModel:
             logging.warning('train_metrics: region-based metrics are not counted per train step (validation still runs them)')
         # ema: {decay, warmup, validate} -- an exponential moving average of the weights, kept on the device by the Adam launches
         self.ema = check_ema(deploy.pop('ema', None))
+        # gradient_accumulation_steps: k -- one optimizer update from the mean gradient of k consecutive train steps (micro-steps)
+        self.accumulation = check_accumulation(deploy.pop('gradient_accumulation_steps', None))
         # optimizer: adam -- the reference's compile call (engine.py:276-284), unchanged; a mapping {class_name, config} or the
         # strings adamw / sgd: the configurable optimizers with Keras' gradient clipping (check_optimizer)
         self.optimizer = check_optimizer(deploy.get('optimizer'))
@@ -383,6 +413,7 @@ class TFKerasModel:
         self._set_optimizer(self.device_model)
         self._set_region_loss(self.device_model)
         self._set_ema(self.device_model)
+        self._set_accumulation(self.device_model)
         self._join_ranks()
 
     def _set_region_loss(self, dm):
@@ -401,6 +432,11 @@ class TFKerasModel:
             names = [name for name, _, trainable, _ in dm.param_infos() if trainable]
             mask = np.array([not any(e in name for e in self.optimizer['exclude']) for name in names], np.uint8)
             dm.set_optimizer(decay_mask=mask, **self.optimizer['device'])
+
+    def _set_accumulation(self, dm):
+        """deploy_options.gradient_accumulation_steps: k > 1 is stored in the device model; without the key (or with 1) no call"""
+        if self.accumulation > 1:
+            dm.set_accumulation(self.accumulation)
 
     def _set_ema(self, dm):
         """deploy_options.ema: the average starts as a copy of the weights; without the key no call is made"""
@@ -444,6 +480,7 @@ class TFKerasModel:
         if average is not None:
             self._set_ema(bigger)
             bigger.set_ema_state(*average)
+        self._set_accumulation(bigger)
         self.device_model = bigger
         return True
 
@@ -548,10 +585,14 @@ class TFKerasModel:
     # ---- training (engine.py:80-137) -------------------------------------------------------------------------
     def train(self, dataset, val_data=None, save_path=None, save_freq=100, max_steps=None, early_stop_steps=None,
               visualization=None, auto_resume=True, profile=False):
+        # gradient accumulation: a train step is a micro-step, and everything below keeps counting micro-steps; checkpoints,
+        # validation passes and the end of the run only ever fall between cycles (refused here, before any data is read)
+        check_accumulation_schedule(self.accumulation, save_freq, max_steps, 0)
         self._build(dataset, also=(val_data,))
         dm = self.device_model
         if auto_resume and save_path is not None:
             self._auto_resume(os.path.join(save_path, 'checkpoints'))
+        check_accumulation_schedule(self.accumulation, save_freq, max_steps, self.current_step)
         schedule = eval(self.learning_rate_scheduler) if self.learning_rate_scheduler is not None else None  # engine.py:98-100
         log_file = None
         if save_path is not None and self.ctx.rank == 0:
@@ -681,6 +722,11 @@ class TFKerasModel:
                     logging.warning('early stopping at step %d', step)
                     break
             read_pending()
+            if self.accumulation > 1 and step % self.accumulation:
+                # the data set ended (or the run stopped) inside a cycle: its gradients are dropped, never applied as a short mean
+                logging.warning('gradient accumulation: step %d ends %d micro-steps into a cycle of %d; the partial cycle is dropped',
+                                step, step % self.accumulation, self.accumulation)
+                dm.set_accumulation(self.accumulation)
         finally:
             if feeder is not None:
                 feeder.close()

@@ -191,6 +191,34 @@ int dnnca_model_set_optimizer(void* model, const dnnca_optimizer_cfg* cfg, const
 int dnnca_last_grad_norm(void* model, double* global, double* per_variable, int n);
 int dnnca_apply_gradients(void* model, const float* g_host, int64_t n, float lr);
 
+/* ---- gradient accumulation: one optimizer update from k micro-batches (deploy_options.gradient_accumulation_steps) -------------
+ * A micro-step is one dnnca_train_step* (or dnnca_apply_gradients) call; a cycle is `steps` consecutive ones.  Every micro-step runs
+ * forward, loss and backward as before (BatchNorm statistics per micro-batch, the step outputs of that micro-batch alone) and
+ * leaves its gradient in g; a float32 accumulator a of dnnca_num_trainable elements takes a <- g on the first micro-step of a cycle
+ * and a <- a + g on the later ones: one add per element per micro-step, in micro-step order, no atomics, bit-identical from run to
+ * run (launch grad_accumulate: 8 bytes per parameter when it starts a cycle, 12 when it adds; on the pixel-group plan the fold of
+ * such a micro-step takes the add and the step outputs along: pg_fold_acc, unless DNNCA_NO_FOLD_ACC is set when the model is
+ * created).  Micro-steps 1 .. steps - 1 change nothing else: weights, optimizer slots, iterations, the weight average and its
+ * num_updates stay bit for bit.  On micro-step `steps` the optimizer's launches (grad_sqnorm, grad_clip_scale, opt_*, g_adam[_ema])
+ * read a in the place of g with gscale = (float)(1 / (steps * world)), formed in double: the mean of the cycle's gradients, a mean
+ * of per-batch means.  The clips and dnnca_last_grad_norm refer to that mean; iterations and the weight average count one update
+ * per cycle; lr is the value passed to that micro-step.  dnnca_get_grads keeps returning the last micro-batch's gradient.
+ * Data parallel: micro-steps 1 .. steps - 1 all-reduce the loss slot alone (1 float), micro-step `steps` the accumulator with the
+ * loss slot behind it (dnnca_num_trainable + 1 floats), one call each on the model's stream; the backward pass sends no buckets.
+ * Plan dumps never move the position; DNNCA_PLAN_TRAIN lists the micro-step that would run next.
+ *   dnnca_model_set_accumulation  steps 1: off, frees a, and every launch is again the one a model without it runs; 2 .. 4096:
+ *                    allocates a (zeroed).  Sets the position to 0 -- a partial cycle is discarded -- and waits for the stream.
+ *                    DNNCA_EINVAL outside [1, 4096], with nothing changed; DNNCA_ESTATE while the averaged weights are in use
+ *   dnnca_get_accumulation  waits for the stream; a to host `flat` (NULL: none), *steps and *position = the micro-steps in a
+ *                    (either may be NULL).  Right after an update: position 0 and the sum that was applied.  DNNCA_ESTATE while
+ *                    accumulation is off
+ *   dnnca_grad_accumulate_of  the kernel alone on host vectors of any length n >= 1: out_host = first ? g_host : acc_host + g_host
+ *                    (with `first`, acc_host may be NULL); none of the model's vectors is touched.  Synchronises
+ * dnnca_set_params and dnnca_set_opt_state set the position to 0; dnnca_model_set_optimizer and dnnca_model_set_ema keep it. */
+int dnnca_model_set_accumulation(void* model, int steps);
+int dnnca_get_accumulation(void* model, float* flat /* nullable */, int64_t n, int* steps, int* position);
+int dnnca_grad_accumulate_of(void* model, const float* acc_host, const float* g_host, int64_t n, int first, float* out_host);
+
 /* ---- the hot path, host buffers ------------------------------------------------------------------------------ */
 /* UNetAnnotator.call (unet.py:279-282): probabilities [B,H,W,1]; logits = the tensor Keras caches as _keras_logits */
 int dnnca_forward(void* model, const float* x_nhwc, int batch, int training, float* prob_out, float* logit_out);
@@ -763,6 +791,9 @@ int dnnca_comm_world(void* model, int* rank, int* world);
 /* gradient all-reduce calls the last train step issued: 1, or several when a gradient vector above 1 MB was sent in buckets
  * (reverse layer order, second stream) while the backward pass was still running -- bit-identical to the single call */
 int dnnca_comm_collectives(void* model, int* count);
+/* floats the last of those calls covered: dnnca_num_trainable + 1 (gradients and the loss slot) for the single call, 1 for a
+ * micro-step of gradient accumulation that ends in no update, the last bucket's length for a bucketed step; 0 before any */
+int dnnca_comm_collective_floats(void* model, int64_t* count);
 /* weights, BN statistics and Adam slots of `root` on every rank; with a weight average (on every rank or on none) it and its count too */
 int dnnca_comm_broadcast_weights(void* model, int root);
 int dnnca_comm_average_state(void* model);          /* BN moving statistics: mean over ranks before a checkpoint */
