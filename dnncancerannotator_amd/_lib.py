@@ -309,6 +309,7 @@ SIGNATURES = {
                                     C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'dnnca_plan_dump': (C.c_int, [_VP, C.c_char_p, C.c_size_t]),
     'dnnca_plan_dump_pass': (C.c_int, [_VP, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    'dnnca_store_image_fits': (C.c_int, [C.c_longlong, C.c_longlong, C.c_longlong]),
 }
 
 _lib = None

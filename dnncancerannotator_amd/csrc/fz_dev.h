@@ -2,6 +2,7 @@
 // LDS tile geometry, register-prefetched staging, the pixel-group 3x3 convolution between LDS tiles on the fp32 matrix cores.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "store_dev.h"
 
 namespace dnnca {
 namespace fz {
@@ -73,17 +74,19 @@ struct Stager {
 };
 
 // Store the interior (rows [HALO, HALO + TH), pixels [HALO, HALO + TW)) of an LDS tile to the dense NHWC image.
-template <int C, int G, int RG, int ROWS, int HALO, int TW, int TH, int NT>
+template <int C, int G, int RG, int ROWS, int HALO, int TW, int TH, int NT, int AUX = DNNCA_STORE_AUX_MFMA_FWD>
 __device__ __forceinline__ void store_interior(const float* lds, float* __restrict__ dst, int b, int y0, int x0, int H, int W, int tid) {
     using TL = Tile<C, G, RG, ROWS, HALO>;
     constexpr int R4 = TW * C / 4;                       // float4's per tile row (TW * C is a multiple of 4: TW is a multiple of 16)
     constexpr int OFF = TL::LEAD + HALO * C;             // multiple of 4 by construction of LEAD
     static_assert(OFF % 4 == 0 && (TW * C) % 4 == 0, "unaligned tile interior");
-    float* base = dst + ((size_t)b * H + y0) * W * C + (size_t)x0 * C;
+    // (image b as a raw buffer, byte offsets within the image; the loop's bound is the only predicate)
+    const __amdgpu_buffer_rsrc_t rs = store_rsrc(dst + (size_t)b * H * W * C, (unsigned)(H * W * C) * 4u);
+    const unsigned base = ((unsigned)y0 * (unsigned)W + (unsigned)x0) * (unsigned)(C * 4);
     for (int idx = tid; idx < TH * R4; idx += NT) {
         const int r = idx / R4, c4 = idx - r * R4;
         const float4 v = *reinterpret_cast<const float4*>(lds + (HALO + r) * TL::LS + OFF + 4 * c4);
-        *reinterpret_cast<float4*>(base + (size_t)r * W * C + 4 * c4) = v;
+        store16<AUX>(rs, base + (unsigned)r * (unsigned)(W * C * 4) + 16u * c4, v);
     }
 }
 

@@ -174,7 +174,8 @@ __global__ __launch_bounds__(NT, MINW) void k_fz_down(DownArgs p) {
         {   // MaxPool2D([2,2], 2) of the tile: TH/2 rows of TW/2 pixels
             constexpr int PR4 = (TW / 2) * C1 / 4;
             const int Wp = p.W >> 1, Hp = p.H >> 1;
-            float* pb = p.pool + ((size_t)cb * Hp + (cy0 >> 1)) * Wp * C1 + (size_t)(cx0 >> 1) * C1;
+            const __amdgpu_buffer_rsrc_t rs_pool = store_rsrc(p.pool + (size_t)cb * Hp * Wp * C1, (unsigned)(Hp * Wp * C1) * 4u);
+            const unsigned pb = ((unsigned)(cy0 >> 1) * (unsigned)Wp + (unsigned)(cx0 >> 1)) * (unsigned)(C1 * 4);
             for (int idx = tid; idx < (TH / 2) * PR4; idx += NT) {
                 const int r = idx / PR4, c4 = idx - r * PR4;
                 float o[4];
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(NT, MINW) void k_fz_down(DownArgs p) {
                     o[e] = mx;
                     where |= (a0 == mx ? 0u : (a1 == mx ? 1u : (a2 == mx ? 2u : 3u))) << (8 * e);     // the order g_pool_bwd searches in
                 }
-                *reinterpret_cast<float4*>(pb + (size_t)r * Wp * C1 + 4 * c4) = make_float4(o[0], o[1], o[2], o[3]);
+                store16<DNNCA_STORE_AUX_MFMA_FWD>(rs_pool, pb + (unsigned)r * (unsigned)(Wp * C1 * 4) + 16u * c4, make_float4(o[0], o[1], o[2], o[3]));
                 if (p.pool_idx)
                     *reinterpret_cast<unsigned*>(p.pool_idx + ((size_t)cb * Hp + (cy0 >> 1) + r) * Wp * C1 + (size_t)(cx0 >> 1) * C1 + 4 * c4) = where;
             }

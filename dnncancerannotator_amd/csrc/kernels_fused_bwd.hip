@@ -472,24 +472,25 @@ __global__ __launch_bounds__(NT, 1) void k_fzb(BArgs p) {
                 const int r0 = (wv / MPR2) * RPW, cbk = wv % MPR2;
                 if constexpr (UP) {
                     // skip gradient: channels [F, 2F) of the first conv's data gradient, 16 pixels per row
-                    float* base = p.dxb + ((size_t)cb * p.H + cy0 + r0) * p.W * F + (size_t)(cx0 + cbk * 16) * F;
+                    // (this image as a raw buffer; lanes 48 .. 63 have no part of a row: they read what lane 0 reads and store to nowhere)
+                    const __amdgpu_buffer_rsrc_t rs_dx = store_rsrc(p.dxb + (size_t)cb * p.H * p.W * F, (unsigned)(p.H * p.W * F) * 4u);
+                    const unsigned base = ((unsigned)(cy0 + r0) * (unsigned)p.W + (unsigned)(cx0 + cbk * 16)) * (unsigned)(F * 4);
+                    const int sl = lane < 48 ? lane : 0;
                     if constexpr (NPASS == 2) {           // pass 1 is the skip half: 16 x F floats = 48 float4 per row
                         static_assert(F == 12, "two passes: 12 channels per pass");
-                        if (lane < 48) {
+                        const unsigned lo = lane < 48 ? base + 16u * lane : kStoreNowhere;
 #pragma unroll
-                            for (int rr = 0; rr < RPW; ++rr)
-                                *reinterpret_cast<float4*>(base + (size_t)rr * p.W * F + 4 * lane) =
-                                    *reinterpret_cast<const float4*>(lds + O_OUT + OUT2 + (r0 + rr) * ROWF + cbk * 192 + 4 * lane);
-                        }
+                        for (int rr = 0; rr < RPW; ++rr)
+                            store16<DNNCA_STORE_AUX_MFMA_BWD>(rs_dx, lo + (unsigned)rr * (unsigned)(p.W * F * 4),
+                                                              *reinterpret_cast<const float4*>(lds + O_OUT + OUT2 + (r0 + rr) * ROWF + cbk * 192 + 4 * sl));
                     } else {                              // one pass: 12 floats per pixel = [up (F) | skip (F)]; 16 x F floats = 48 float2 per row
                         static_assert(F == 6, "one pass: [up | skip] of 6 channels each");
-                        if (lane < 48) {
-                            const int px = (2 * lane) / F, ch = 2 * lane - px * F;
+                        const int px = (2 * sl) / F, ch = 2 * sl - px * F;
+                        const unsigned lo = lane < 48 ? base + 8u * lane : kStoreNowhere;
 #pragma unroll
-                            for (int rr = 0; rr < RPW; ++rr)
-                                *reinterpret_cast<float2*>(base + (size_t)rr * p.W * F + 2 * lane) =
-                                    *reinterpret_cast<const float2*>(lds + O_OUT + (r0 + rr) * ROWF + (cbk * 16 + px) * 12 + F + ch);
-                        }
+                        for (int rr = 0; rr < RPW; ++rr)
+                            store8<DNNCA_STORE_AUX_MFMA_BWD>(rs_dx, lo + (unsigned)rr * (unsigned)(p.W * F * 4),
+                                                             *reinterpret_cast<const float2*>(lds + O_OUT + (r0 + rr) * ROWF + (cbk * 16 + px) * 12 + F + ch));
                     }
                     // the transposed conv's backward on the wave's 8 x RPW/2 input pixels; the gradient of its output is the `up` half of the
                     // stage-2 tile: pixel (r, c) channel co at O_OUT + r * ROWF + c * 12 + co
@@ -538,7 +539,10 @@ __global__ __launch_bounds__(NT, 1) void k_fzb(BArgs p) {
                                 v.z *= xv.z > 0.f ? 1.0f : p.tc_alpha;
                                 v.w *= xv.w > 0.f ? 1.0f : p.tc_alpha;
                             }
-                            reinterpret_cast<float4*>(p.tc_din)[(((size_t)cb * (p.H >> 1) + (cy0 >> 1) + oi) * (p.W >> 1) + (cx0 >> 1) + oj) * 3 + c4] = v;
+                            const __amdgpu_buffer_rsrc_t rs_tc =
+                                store_rsrc(p.tc_din + (size_t)cb * (p.H >> 1) * (p.W >> 1) * 12, (unsigned)((p.H >> 1) * (p.W >> 1)) * 48u);
+                            store16<DNNCA_STORE_AUX_MFMA_BWD>(
+                                rs_tc, (((unsigned)((cy0 >> 1) + oi) * (unsigned)(p.W >> 1) + (unsigned)((cx0 >> 1) + oj)) * 3u + (unsigned)c4) * 16u, v);
                         }
                         __builtin_amdgcn_wave_barrier();
                     }
@@ -570,13 +574,13 @@ __global__ __launch_bounds__(NT, 1) void k_fzb(BArgs p) {
                 } else {
                     // gradient of the block's input: the wave's RPW full-width rows of TW * CA floats (= 48 float4)
                     static_assert(MPR2 == 1 && TW * CA == 192, "DOWN: a wave stores whole rows of 48 float4");
-                    float* base = p.dxb + ((size_t)cb * p.H + cy0 + r0) * p.W * CA + (size_t)cx0 * CA;
-                    if (lane < 48) {
+                    const __amdgpu_buffer_rsrc_t rs_dx = store_rsrc(p.dxb + (size_t)cb * p.H * p.W * CA, (unsigned)(p.H * p.W * CA) * 4u);
+                    const unsigned lo = lane < 48 ? ((unsigned)(cy0 + r0) * (unsigned)p.W + (unsigned)cx0) * (unsigned)(CA * 4) + 16u * lane : kStoreNowhere;
+                    const int sl = lane < 48 ? lane : 0;          // (lanes 48 .. 63: lane 0's LDS words, a store to nowhere)
 #pragma unroll
-                        for (int rr = 0; rr < RPW; ++rr)
-                            *reinterpret_cast<float4*>(base + (size_t)rr * p.W * CA + 4 * lane) =
-                                *reinterpret_cast<const float4*>(lds + O_OUT + (r0 + rr) * (TW * CA) + 4 * lane);
-                    }
+                    for (int rr = 0; rr < RPW; ++rr)
+                        store16<DNNCA_STORE_AUX_MFMA_BWD>(rs_dx, lo + (unsigned)rr * (unsigned)(p.W * CA * 4),
+                                                          *reinterpret_cast<const float4*>(lds + O_OUT + (r0 + rr) * (TW * CA) + 4 * sl));
                 }
             } else {
 #pragma unroll 1

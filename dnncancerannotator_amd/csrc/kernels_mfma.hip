@@ -25,6 +25,7 @@
 #include "fast.h"
 #include "kernels.h"
 #include "tconv2_dev.h"
+#include "store_dev.h"
 
 namespace dnnca {
 
@@ -254,6 +255,10 @@ __global__ __launch_bounds__(NT) void k_pgfwd(std::conditional_t<PROB, FwdProbAr
     while (tile < ntiles) {
         int b, x0, y0;
         decode(tile, b, x0, y0);
+        // this tile's image of the output (and of the head's feature-map gradient) as raw buffers: byte offsets within the image
+        const unsigned img_bytes = (unsigned)(p.H * p.W * CO) * 4u;
+        const __amdgpu_buffer_rsrc_t rs_dst = store_rsrc(p.dst + (size_t)b * p.H * p.W * CO, img_bytes);
+        [[maybe_unused]] const __amdgpu_buffer_rsrc_t rs_hdf = store_rsrc(HEAD ? p.hdfeat + (size_t)b * p.H * p.W * CO : nullptr, HEAD ? img_bytes : 0u);
 #pragma unroll
         for (int s = 0; s < NSRC; ++s) tile_commit<C, TW, NT>(pre[s], okm, lds4 + s * T::N4, tid);
         lds_barrier();
@@ -316,10 +321,10 @@ __global__ __launch_bounds__(NT) void k_pgfwd(std::conditional_t<PROB, FwdProbAr
                 }
                 __builtin_amdgcn_wave_barrier();
                 const int f0 = (x0 + tx * 16 * G) * CO + 4 * lane;          // float index within the image row
-                if (lane < 48 && f0 < p.W * CO && y < p.H) {
-                    const float4 v = reinterpret_cast<const float4*>(orw)[lane];
-                    *reinterpret_cast<float4*>(p.dst + ((size_t)b * p.H + y) * p.W * CO + f0) = v;
-                }
+                // byte offset within this image; past the image: a store to nowhere (lanes 48 .. 63 have no float4 of the row and sit
+                // out under the execution mask: an LDS read for them costs the one-source 6-channel instance three registers)
+                const unsigned ooff = f0 < p.W * CO && y < p.H ? ((unsigned)y * (unsigned)(p.W * CO) + (unsigned)f0) * 4u : kStoreNowhere;
+                if (lane < 48) store16<DNNCA_STORE_AUX_MFMA_FWD>(rs_dst, ooff, reinterpret_cast<const float4*>(orw)[lane]);
                 if constexpr (HEAD) {
                     // one lane = one pixel of the 64-pixel row segment: logit -> weighted BCE -> dlogit -> dW, db, d(feature map)
                     const int px = x0 + tx * 64 + lane;
@@ -351,10 +356,7 @@ __global__ __launch_bounds__(NT) void k_pgfwd(std::conditional_t<PROB, FwdProbAr
 #pragma unroll
                     for (int c = 0; c < CO; ++c) orw[lane * CO + c] = df[c];
                     __builtin_amdgcn_wave_barrier();
-                    if (lane < 48 && f0 < p.W * CO && y < p.H) {
-                        const float4 v = reinterpret_cast<const float4*>(orw)[lane];
-                        *reinterpret_cast<float4*>(p.hdfeat + ((size_t)b * p.H + y) * p.W * CO + f0) = v;
-                    }
+                    if (lane < 48) store16<DNNCA_STORE_AUX_MFMA_FWD>(rs_hdf, ooff, reinterpret_cast<const float4*>(orw)[lane]);
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -362,7 +364,7 @@ __global__ __launch_bounds__(NT) void k_pgfwd(std::conditional_t<PROB, FwdProbAr
                 // both rows of the pair are in LDS: pooled row = max over the 2x2 windows, 8G pixels x CO = 96 floats
                 const int yp = (y0 >> 1) + ty0, Wp = p.W >> 1;
                 const int fp0 = ((x0 + tx * 16 * G) >> 1) * CO + 4 * lane;   // float index within the pooled row
-                if (lane < 24 && fp0 < Wp * CO && 2 * yp + 1 < p.H) {
+                if (lane < 24) {
                     float o[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
@@ -370,7 +372,9 @@ __global__ __launch_bounds__(NT) void k_pgfwd(std::conditional_t<PROB, FwdProbAr
                         const int i0 = (2 * pp) * CO + c;
                         o[e] = fmaxf(fmaxf(orow[i0], orow[i0 + CO]), fmaxf(orow[192 + i0], orow[192 + i0 + CO]));
                     }
-                    *reinterpret_cast<float4*>(p.pool_dst + ((size_t)b * (p.H >> 1) + yp) * Wp * CO + fp0) = make_float4(o[0], o[1], o[2], o[3]);
+                    const __amdgpu_buffer_rsrc_t rs_pool = store_rsrc(p.pool_dst + (size_t)b * (p.H >> 1) * Wp * CO, (unsigned)((p.H >> 1) * Wp * CO) * 4u);
+                    const unsigned poff = fp0 < Wp * CO && 2 * yp + 1 < p.H ? ((unsigned)yp * (unsigned)(Wp * CO) + (unsigned)fp0) * 4u : kStoreNowhere;
+                    store16<DNNCA_STORE_AUX_MFMA_FWD>(rs_pool, poff, make_float4(o[0], o[1], o[2], o[3]));
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -1405,12 +1409,30 @@ static const PgPlan& pg_find(const Model* m) { static const PgPlan none; return 
 void fast_release(Model* m) { delete m->plan_pg; m->plan_pg = nullptr; }
 unsigned long long* fast_debug_stamps(const Model* m) { return pg_find(m).stamps; }
 
+// The pixel-group and block-fused kernels store through one raw buffer per image (store_dev.h): 32-bit byte offsets inside the
+// image, the 64-bit part in the descriptor's base (the strip kernels: one per tensor, strip_shape_ok).  An image of H x W pixels with C float channels qualifies while its bytes stay
+// below 2^31; the launchers decline (to the per-layer or generic path) beyond that.  Host function of the C ABI: testable without
+// allocating such a tensor.
+extern "C" int dnnca_store_image_fits(long long H, long long W, long long C) {
+    if (H <= 0 || W <= 0 || C <= 0) return 0;
+    // (H * W * C * 4 without overflow: each factor is checked against what is left of the bound)
+    unsigned long long lim = kStoreMaxBytes / 4;
+    if ((unsigned long long)H > lim) return 0;
+    lim /= (unsigned long long)H;
+    if ((unsigned long long)W > lim) return 0;
+    lim /= (unsigned long long)W;
+    if ((unsigned long long)C > lim) return 0;
+    return store_fits((unsigned long long)H * (unsigned long long)W * (unsigned long long)C * 4ull) ? 1 : 0;
+}
+
 static bool conv_supported(const Model* m, const Op& o) {
     if (o.type != OP_CONV || o.k != 3) return false;
     if (!dense(o.inA.d) || !dense(o.inB.d) || !dense(o.out.d)) return false;
     const int CA = o.inA.d.C, CB = o.inB.d.C, CO = o.out.d.C;
     if (CB && CB != CA) return false;
     if (o.out.d.W % 4) return false;
+    // (the largest tensor any launch of this conv stores: its output / input gradient image; a riding transposed conv's is smaller)
+    if (!dnnca_store_image_fits(o.out.d.H, o.out.d.W, CA > CO ? CA : CO)) return false;
     const int ns = CB ? 2 : 1;
     // the instantiated (C, NSRC, CO) set: every 3x3 conv of configs/unet.yaml
     if (ns == 1)

@@ -134,7 +134,7 @@
                             const __amdgpu_buffer_rsrc_t rs_dx1 = __builtin_amdgcn_make_buffer_rsrc(
                                 (void*)(p.dx[1] + (size_t)b * p.H * p.W * C), 0, p.H * p.W * C * 4, PG_RSRC);
                             const unsigned off = sp == 1 ? ((unsigned)y * (unsigned)(p.W * C) + (unsigned)f0) * 4u : PG_NOWHERE;
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pg_u4, v), rs_dx1, off, 0, 0);
+                            store16<DNNCA_STORE_AUX_MFMA_BWD>(rs_dx1, off, v);
                         } else if (TCF && sp == 0) {
                             // the first source's gradient (= the transposed conv's output gradient) stays in LDS (whole tiles only)
                             if (lane < PER4) dta4[(ty * 4 + tx) * 24 + i4] = reinterpret_cast<const float4*>(orow)[lane];
@@ -155,7 +155,13 @@
                                 v.z *= xv.z > 0.f ? 1.0f : p.alpha;
                                 v.w *= xv.w > 0.f ? 1.0f : p.alpha;
                             }
-                            *reinterpret_cast<float4*>(dst) = v;
+                            if constexpr (SPL == 1) {
+                                // one destination per pass (uniform): the store goes through this image's raw buffer
+                                const __amdgpu_buffer_rsrc_t rs_dx = store_rsrc(dxs + (size_t)b * p.H * p.W * C, (unsigned)(p.H * p.W * C) * 4u);
+                                store16<DNNCA_STORE_AUX_MFMA_BWD>(rs_dx, ((unsigned)y * (unsigned)(p.W * C) + (unsigned)f0) * 4u, v);
+                            } else {
+                                *reinterpret_cast<float4*>(dst) = v;      // (the destination differs between lanes: no uniform descriptor)
+                            }
                         }
                         __builtin_amdgcn_wave_barrier();
                     }
@@ -204,7 +210,8 @@
                         v.z *= xv.z > 0.f ? 1.0f : p.tc_alpha;
                         v.w *= xv.w > 0.f ? 1.0f : p.tc_alpha;
                     }
-                    reinterpret_cast<float4*>(p.tc_din)[(((size_t)b * (p.H >> 1) + (y0 >> 1) + li) * (p.W >> 1) + (x0 >> 1) + mx * 16) * 3 + lane] = v;
+                    const __amdgpu_buffer_rsrc_t rs_tc = store_rsrc(p.tc_din + (size_t)b * (p.H >> 1) * (p.W >> 1) * 12, (unsigned)((p.H >> 1) * (p.W >> 1)) * 48u);
+                    store16<DNNCA_STORE_AUX_MFMA_BWD>(rs_tc, ((unsigned)((y0 >> 1) + li) * (unsigned)(p.W >> 1) + (unsigned)((x0 >> 1) + mx * 16)) * 48u + lane * 16u, v);
                 }
                 __builtin_amdgcn_wave_barrier();
             }
@@ -262,9 +269,13 @@
 #pragma unroll
                     for (int ci = 0; ci < 6; ++ci) din[ci] *= tin[ci] > 0.f ? 1.0f : p.tc_alpha;
                 }
-                float* op = p.tc_din + ((((size_t)b * (p.H >> 1) + (y0 >> 1) + pr) * (p.W >> 1)) + (x0 >> 1) + wave * 16 + pc) * 6;
-#pragma unroll
-                for (int ci = 0; ci < 6; ++ci) op[ci] = din[ci];
+                // a pixel's 24 bytes as two 12-byte stores through this image's raw buffer.  Plain stores whatever the policy: written
+                // through, the 12-byte pieces reach memory one by one (WRITE_SIZE of the launch 37.5 -> 49.7 MB, this tensor twice);
+                // as plain stores the L2 merges them into whole lines
+                const __amdgpu_buffer_rsrc_t rs_tc = store_rsrc(p.tc_din + (size_t)b * (p.H >> 1) * (p.W >> 1) * 6, (unsigned)((p.H >> 1) * (p.W >> 1)) * 24u);
+                const unsigned toff = ((unsigned)((y0 >> 1) + pr) * (unsigned)(p.W >> 1) + (unsigned)((x0 >> 1) + wave * 16 + pc)) * 24u;
+                store12<0>(rs_tc, toff, din[0], din[1], din[2]);
+                store12<0>(rs_tc, toff + 12u, din[3], din[4], din[5]);
                 __builtin_amdgcn_wave_barrier();
             }
         }

@@ -20,6 +20,7 @@
 //   gradients never exist in memory (4 of 7 full-resolution tensor passes of the two launches it replaces).
 #pragma once
 #include <type_traits>
+#include "store_dev.h"
 
 namespace dnnca {
 
@@ -323,9 +324,7 @@ __global__ __launch_bounds__(256, 2) void k_tail3(std::conditional_t<PROB, TailP
             for (int co = 0; co < 3; ++co) acc[81 + co] = fmaf(dzw[(u + 2) % 3][3 + co], ownj, acc[81 + co]);
 #pragma unroll
             for (int ci = 0; ci < 3; ++ci) dx[ci] *= xc[ci] > 0.f ? 1.0f : xslope;
-            const f3 dv = {dx[0], dx[1], dx[2]};
-            __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b96(rsd, 0, 0, 0)), dv), rsd,
-                                                  cold + rowpart(j, rowj, 12u), 0, 0);
+            store12<DNNCA_STORE_AUX_TAIL>(rsd, cold + rowpart(j, rowj, 12u), dx[0], dx[1], dx[2]);
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -759,8 +758,7 @@ __global__ __launch_bounds__(256, WPS) void k_first3_fwd(FirstFwdArgs p) {
 #pragma unroll
             for (int co = 0; co < 3; ++co) f[co] = fmaxf(f[co], f[co] * a0) * imgf;
             const unsigned mine = inside(rf, r0, r1);
-            __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b96(rs0, 0, 0, 0)), f3{f[0], f[1], f[2]}),
-                                                  rs0, own12 + rowpart(img0, rf, mine, (unsigned)p.W * 12u), 0, 0);
+            store12<DNNCA_STORE_AUX_STRIP>(rs0, own12 + rowpart(img0, rf, mine, (unsigned)p.W * 12u), f[0], f[1], f[2]);
             strip_expand<1>(f, yw[u], la, ra);            // y0 window slots: row i-3 -> (u+1)%3, i-2 -> (u+2)%3, i-1 -> u
         }
         if constexpr (C1) {
@@ -784,8 +782,7 @@ __global__ __launch_bounds__(256, WPS) void k_first3_fwd(FirstFwdArgs p) {
                 g[co] = fmaxf(g[co], g[co] * a1);
             }
             const unsigned mine = inside(j, r0, r1);
-            __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b96(rs1, 0, 0, 0)), f3{g[0], g[1], g[2]}),
-                                                  rs1, own12 + rowpart(img0, j, mine, (unsigned)p.W * 12u), 0, 0);
+            store12<DNNCA_STORE_AUX_STRIP>(rs1, own12 + rowpart(img0, j, mine, (unsigned)p.W * 12u), g[0], g[1], g[2]);
             // pool: on odd rows the window (rows j-1, j; this lane's column and its pair partner's) is complete.  First maximum in
             // row-major order: (j-1, even) = 0, (j-1, odd) = 1, (j, even) = 2, (j, odd) = 3.  (On even rows the values are computed and
             // dropped: the store offset is out of range.)
@@ -801,8 +798,7 @@ __global__ __launch_bounds__(256, WPS) void k_first3_fwd(FirstFwdArgs p) {
                 prev[co] = g[co];
             }
             const unsigned podd = mine & (unsigned)-(j & 1);          // an odd row of this chunk
-            __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b96(rsp, 0, 0, 0)), f3{pm[0], pm[1], pm[2]}),
-                                                  rsp, ownp12 + rowpart(imgp0, j >> 1, podd, (unsigned)Wp * 12u), 0, 0);
+            store12<DNNCA_STORE_AUX_STRIP>(rsp, ownp12 + rowpart(imgp0, j >> 1, podd, (unsigned)Wp * 12u), pm[0], pm[1], pm[2]);
             const unsigned o3 = ownp3 + rowpart(imgp0, j >> 1, podd, (unsigned)Wp * 3u);
 #pragma unroll
             for (int co = 0; co < 3; ++co) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)pos[co], rsk, o3 + co, 0, 0);
@@ -960,8 +956,7 @@ __global__ __launch_bounds__(256, 2) void k_up3_fwd(UpFwdArgs p) {
             for (int ci = 0; ci < 6; ++ci) acc = fmaf(x6[ci], wt[a][co][ci], acc);
             tv[co] = acc * imgf;
         }
-        __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b96(rst, 0, 0, 0)), f3{tv[0], tv[1], tv[2]}),
-                                              rst, own12 + rowpart(img0, i, inside(i, r0, r1), (unsigned)p.W * 12u), 0, 0);
+        store12<DNNCA_STORE_AUX_STRIP>(rst, own12 + rowpart(img0, i, inside(i, r0, r1), (unsigned)p.W * 12u), tv[0], tv[1], tv[2]);
         strip_expand<1>(tv, ta[u], la, ra);             // rows j-1 -> (u+1)%3, j -> (u+2)%3, j+1 -> u
         strip_expand<1>(s3, sk[u], la, ra);
         if constexpr (CONV) {
@@ -984,8 +979,7 @@ __global__ __launch_bounds__(256, 2) void k_up3_fwd(UpFwdArgs p) {
                 g[co] += g2[co];
                 g[co] = fmaxf(g[co], g[co] * aslope);
             }
-            __builtin_amdgcn_raw_buffer_store_b96(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b96(rso, 0, 0, 0)), f3{g[0], g[1], g[2]}),
-                                                  rso, own12 + rowpart(img0, j, inside(j, r0, r1), (unsigned)p.W * 12u), 0, 0);
+            store12<DNNCA_STORE_AUX_STRIP>(rso, own12 + rowpart(img0, j, inside(j, r0, r1), (unsigned)p.W * 12u), g[0], g[1], g[2]);
         }
         __builtin_amdgcn_sched_barrier(0);
     };

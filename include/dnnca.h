@@ -858,6 +858,10 @@ enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2, DNNCA_
        DNNCA_PLAN_LESION_LINKED = 5, DNNCA_PLAN_LESION_MATCHED = 6, DNNCA_PLAN_SURFACE = 7, DNNCA_PLAN_ATTRIBUTION = 8,
        DNNCA_PLAN_LESION_FEATURES = 9 };
 int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap);
+/* the small-channel launchers' size predicate (a host function, no model needed): 1 when one image of H x W pixels with C float
+   channels stays below 2^31 bytes, so that the kernels can address it with a 32-bit byte offset through one buffer descriptor;
+   0 otherwise (such a conv declines to the per-layer or generic path) */
+int dnnca_store_image_fits(long long H, long long W, long long C);
 
 #ifdef __cplusplus
 }
