@@ -17,6 +17,23 @@ def _at_least_one(text):
     return n
 
 
+def _detection_arguments(p):
+    """the candidate extraction shared by `evaluate --detection` and `predict --detection_map`; absent unless given"""
+    p.add_argument('--detection_min_confidence', type=float, default=argparse.SUPPRESS,
+                   help='the weakest peak that still starts a candidate, [0.001, 1] (default: 0.1)')
+    p.add_argument('--detection_factor', type=float, default=argparse.SUPPRESS,
+                   help='a candidate is the region around its peak above this fraction of the peak, [0.01, 1] (default: 0.4)')
+    p.add_argument('--detection_max_candidates', type=int, default=argparse.SUPPRESS, help='candidates per slice, 1..64 (default: 5)')
+    p.add_argument('--detection_min_area', type=int, default=argparse.SUPPRESS,
+                   help='smallest region kept as a candidate, in pixels (default: 10)')
+    p.add_argument('--detection_rounds', type=int, default=argparse.SUPPRESS,
+                   help='peaks tried per slice, kept or dropped, max_candidates..256 (default: 16)')
+    p.add_argument('--detection_link_min_overlap', type=int, default=argparse.SUPPRESS,
+                   help='common pixels that join two candidates of neighbouring slices (default: 1)')
+    p.add_argument('--detection_max_lesions', type=int, default=argparse.SUPPRESS,
+                   help='rows per slice and plane of the table read from the map (default: 256)')
+
+
 def build_parser(prog='python3 -m annotator'):
     parser = argparse.ArgumentParser(prog=prog, description='DNNAnnotator: DNN model to predict cancer segmentation (MI355X engine)')
     sub = parser.add_subparsers(dest='command', help='command')
@@ -104,6 +121,13 @@ def build_parser(prog='python3 -m annotator'):
     e.add_argument('--weights', choices=('raw', 'ema'), default=argparse.SUPPRESS,
                    help='which weights of each checkpoint to evaluate: the raw ones or their exponential moving average '
                         '(deploy_options.ema at training time; a checkpoint without one is an error); default: raw')
+    e.add_argument('--detection', action='store_true', default=argparse.SUPPRESS,
+                   help='lesion detection without a fixed threshold: ranked candidates from the detection map, lesion-level average '
+                        'precision and FROC, exam-level AUROC: also write detection_results.csv, detection_froc.csv, '
+                        'detection_cases.csv and detection_candidates.csv')
+    _detection_arguments(e)
+    e.add_argument('--detection_iou', type=float, default=argparse.SUPPRESS,
+                   help='voxel IoU at which a candidate of --detection hits a tumour (default: 0.10)')
     p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
     p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
     p.add_argument('--data_path', nargs='+', required=True)
@@ -141,6 +165,10 @@ def build_parser(prog='python3 -m annotator'):
     p.add_argument('--weights', choices=('raw', 'ema'), default=argparse.SUPPRESS,
                    help='which weights of the checkpoint to annotate with: the raw ones or their exponential moving average '
                         '(deploy_options.ema at training time; a checkpoint without one is an error); default: raw')
+    p.add_argument('--detection_map', action='store_true', default=argparse.SUPPRESS,
+                   help='ranked lesion candidates without a fixed threshold: also write candidates.csv, slice_candidates.csv, with '
+                        '--link_slices exam_candidates.csv and with --export_images detection.png (the map a detection challenge asks for)')
+    _detection_arguments(p)
     return parser
 
 

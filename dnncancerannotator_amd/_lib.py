@@ -151,6 +151,24 @@ CALIB_MAX_BINS, CALIB_MAX_TEMPERATURES = 256, 64
 CALIB_MIN_T, CALIB_MAX_T = 0.05, 20.0              # the temperatures the library accepts
 
 
+class DetectionCfg(C.Structure):                   # dnnca_detection_cfg
+    _fields_ = [('min_confidence', C.c_float), ('factor', C.c_float), ('max_candidates', C.c_int32), ('min_area', C.c_int32),
+                ('rounds', C.c_int32)]
+
+
+class DetectionRow(C.Structure):                   # dnnca_detection_row (20 bytes)
+    _fields_ = [('slice', C.c_int32), ('number', C.c_int32), ('seed', C.c_int32), ('area', C.c_int32), ('confidence', C.c_float)]
+
+
+class DetectionSlice(C.Structure):                 # dnnca_detection_slice (16 bytes)
+    _fields_ = [('candidates', C.c_int32), ('rounds', C.c_int32), ('dropped', C.c_int32), ('exhausted', C.c_int32)]
+
+
+# DeviceModel.detection_map / detection_map_of return structured arrays of these dtypes
+DETECTION_ROW_DTYPE = np.dtype([('slice', '<i4'), ('number', '<i4'), ('seed', '<i4'), ('area', '<i4'), ('confidence', '<f4')])
+DETECTION_SLICE_DTYPE = np.dtype([('candidates', '<i4'), ('rounds', '<i4'), ('dropped', '<i4'), ('exhausted', '<i4')])
+
+
 # DeviceModel.lesion_table_spread / spread_by_outcome return structured arrays of these dtypes
 LESION_SPREAD_DTYPE = np.dtype([('slice', '<i4'), ('row', '<i4'), ('area', '<i4'), ('max_spread', '<f4'), ('sum_spread_q24', '<u8')])
 SLICE_SPREAD_DTYPE = np.dtype([('pixels', '<i4'), ('max_spread', '<f4'), ('sum_spread_q24', '<u8')])
@@ -277,6 +295,8 @@ SIGNATURES = {
     'dnnca_calibration': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, _FP, C.c_int, C.POINTER(CalibBin),
                                     C.POINTER(CalibTotal), C.POINTER(C.c_double)]),
     'dnnca_prob_temperature': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, _FP]),
+    'dnnca_detection_map': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.POINTER(DetectionCfg), _FP, C.POINTER(DetectionRow),
+                                      C.POINTER(C.c_int64), C.POINTER(DetectionSlice)]),
     'dnnca_lesion_table_linked': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                             C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
                                             C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(LesionLink), C.c_int64,

@@ -349,6 +349,32 @@ EXAM_IOU = 0.30                  # IoU_threshold / pr_IoU_threshold of the refer
 EXAM_EPSILON = 1e-07             # region_metrics._RegionBasedMetric's epsilon
 
 
+def exam_overlaps(true_slices, pred_slices, true_linked, pred_linked, pairs, who='match_exam_lesions'):
+    """the common voxels of the labelled and the predicted exam lesions of one exam: ({(T, P): overlap}, volumes of the labelled,
+    volumes of the predicted ones), from the arguments of match_exam_lesions (shared with detection_match)"""
+    if not len(true_slices) == len(pred_slices) == len(pairs):
+        raise ValueError('%s: %d / %d slices and %d pair lists' % (who, len(true_slices), len(pred_slices), len(pairs)))
+
+    def part_numbers(slices, parts):
+        """[slice][row] -> the exam lesion; the parts come one per row, slice after slice"""
+        out, at = [], 0
+        for _, rows, _ in slices:
+            out.append([int(p[3]) for p in parts[at:at + len(rows)]])
+            at += len(rows)
+        if at != len(parts):
+            raise ValueError('%s: %d parts for %d rows' % (who, len(parts), at))
+        return out
+    of_true, of_pred = part_numbers(true_slices, true_linked[1]), part_numbers(pred_slices, pred_linked[1])
+    overlap = {}                                                    # (T, P) -> common voxels
+    for i, mine in enumerate(pairs):
+        for row_true, row, n in mine:
+            if not (0 <= int(row_true) < len(of_true[i]) and 0 <= int(row) < len(of_pred[i])):
+                raise ValueError('%s: pair (%d, %d) of slice %d of the exam joins no rows' % (who, row_true, row, i))
+            key = of_true[i][int(row_true)], of_pred[i][int(row)]
+            overlap[key] = overlap.get(key, 0) + int(n)
+    return overlap, [int(r[6]) for r in true_linked[0]], [int(r[6]) for r in pred_linked[0]]
+
+
 def match_exam_lesions(exam, true_slices, pred_slices, true_linked, pred_linked, pairs, iou=EXAM_IOU):
     """The labelled and the predicted exam lesions of one exam held against each other: (case values, match values).
 
@@ -363,27 +389,7 @@ def match_exam_lesions(exam, true_slices, pred_slices, true_linked, pred_linked,
     rows.  Match values (EXAM_MATCH_COLUMNS): one line per tumour, the labelled ones (kind 'true') before the predicted ones, each
     with its best partner on the other side -- the largest IoU, the smaller number on a tie; -1, 0, 0.0, 0.0 without any -- and
     hit = 1 for detected / matched.  iou and dice (2 overlap / (volume(T) + volume(P))) are float64 quotients written with repr."""
-    if not len(true_slices) == len(pred_slices) == len(pairs):
-        raise ValueError('match_exam_lesions: %d / %d slices and %d pair lists' % (len(true_slices), len(pred_slices), len(pairs)))
-
-    def part_numbers(slices, parts):
-        """[slice][row] -> the exam lesion; the parts come one per row, slice after slice"""
-        out, at = [], 0
-        for _, rows, _ in slices:
-            out.append([int(p[3]) for p in parts[at:at + len(rows)]])
-            at += len(rows)
-        if at != len(parts):
-            raise ValueError('match_exam_lesions: %d parts for %d rows' % (len(parts), at))
-        return out
-    of_true, of_pred = part_numbers(true_slices, true_linked[1]), part_numbers(pred_slices, pred_linked[1])
-    overlap = {}                                                    # (T, P) -> common voxels
-    for i, mine in enumerate(pairs):
-        for row_true, row, n in mine:
-            if not (0 <= int(row_true) < len(of_true[i]) and 0 <= int(row) < len(of_pred[i])):
-                raise ValueError('match_exam_lesions: pair (%d, %d) of slice %d of the exam joins no rows' % (row_true, row, i))
-            key = of_true[i][int(row_true)], of_pred[i][int(row)]
-            overlap[key] = overlap.get(key, 0) + int(n)
-    vol_true, vol_pred = [int(r[6]) for r in true_linked[0]], [int(r[6]) for r in pred_linked[0]]
+    overlap, vol_true, vol_pred = exam_overlaps(true_slices, pred_slices, true_linked, pred_linked, pairs)
     best = {'true': [None] * len(vol_true), 'predicted': [None] * len(vol_pred)}      # (iou, -partner, overlap, dice, hit)
     hit = {'true': [0] * len(vol_true), 'predicted': [0] * len(vol_pred)}
     for (t, q), n in sorted(overlap.items()):
@@ -418,6 +424,133 @@ def exam_match_summary(cases):
     f1 = f32(2) * precision * recall / (precision + recall + f32(EXAM_EPSILON))
     return [len(cases)] + n + [repr(float(recall)), repr(float(precision)), repr(float(f1)),
                                repr(n[5] / len(cases) if cases else 0.0)]
+
+
+# ---- `annotator evaluate --detection`: ranked lesion candidates, AP, FROC and AUROC -----------------------------------------------
+# DeviceModel.detection_map gives every candidate one confidence (the peak it grew from); lesion_table_matched on the map gives the
+# candidates as rows (max_prob = confidence) and their overlaps with the labelled lesions; link_lesions joins both planes through the
+# slices.  Everything here is Python integers and float64; pooled values come from summed counts, never from per-exam ratios.
+DETECTION_DEFAULTS = dict(min_confidence=0.1, factor=0.4, max_candidates=5, min_area=10, rounds=16)      # PI-CAI: factor = 1 / 2.5
+DETECTION_RANGES = dict(min_confidence=(0.001, 1.0), factor=(0.01, 1.0), max_candidates=(1, 64), min_area=(1, 1 << 30), rounds=(1, 256))
+DETECTION_IOU = 0.10             # --detection_iou: PI-CAI's hit criterion
+DETECTION_FP_RATES = (0.125, 0.25, 0.5, 1.0, 2.0, 4.0, 8.0)       # false positives per exam at which the sensitivity is read (CPM)
+DETECTION_RESULT_COLUMNS = (['exams', 'positive_exams', 'tumours', 'candidates', 'tp', 'fp', 'fn', 'ap', 'auroc', 'score'] +
+                            ['sensitivity_at_%g' % x for x in DETECTION_FP_RATES] + ['cpm', 'slices_exhausted'])
+DETECTION_FROC_COLUMNS = ['confidence', 'tp', 'fp', 'sensitivity', 'fp_per_exam', 'precision']
+DETECTION_CASE_COLUMNS = ['exam', 'positive', 'score', 'candidates', 'tp', 'fp', 'fn']
+DETECTION_CANDIDATE_COLUMNS = ['exam', 'candidate', 'first_slice', 'last_slice', 'volume_px', 'confidence', 'tumour', 'iou', 'outcome']
+CANDIDATE_COLUMNS = LESION_COLUMNS + ['confidence']               # predict --detection_map: candidates.csv
+SLICE_CANDIDATE_COLUMNS = ['exam', 'slice', 'candidates', 'rounds', 'dropped', 'exhausted']
+EXAM_CANDIDATE_COLUMNS = EXAM_LESION_COLUMNS + ['confidence']
+
+
+def detection_table_args(cfg, max_lesions=256):
+    """the lesion_table* keywords that read a detection map: every pixel of a candidate is >= min_confidence, nothing is opened,
+    resized or filtered, so the rows are the candidates (touching ones joined, max_prob = the larger confidence)"""
+    return dict(threshold=float(cfg['min_confidence']), filter_size=1, resize_factor=1.0, min_area=0, max_lesions=int(max_lesions))
+
+
+def detection_match(exam, true_slices, pred_slices, true_linked, pred_linked, pairs, iou=DETECTION_IOU):
+    """The candidates of one exam held against its labelled tumours: (case, candidate lines).  The arguments are those of
+    match_exam_lesions, the prediction plane being the detection map.  A candidate's confidence is the largest max_prob of its parts.
+    Voxel IoU per candidate / tumour pair = overlap / (volume(T) + volume(P) - overlap).  Candidates in descending confidence (ties:
+    the lower number): each takes the not-yet-taken tumour of largest IoU >= iou with overlap >= 1 (ties: the lower number) and is
+    a TP; otherwise -- no tumour reached, or only taken ones -- it is an FP.  Tumours never taken are FN.
+    case: dict(exam, tumours, confidences [float per candidate, by number], hits [1 TP / 0 FP per candidate]).
+    Lines (DETECTION_CANDIDATE_COLUMNS), by candidate number: tumour and iou are the tumour a TP took; for an FP the tumour of largest
+    IoU whatever it is (-1 and 0.0 without any overlap)."""
+    overlap, vol_true, vol_pred = exam_overlaps(true_slices, pred_slices, true_linked, pred_linked, pairs, who='detection_match')
+    conf = [float(np.float32(r[15])) for r in pred_linked[0]]      # the 9 digits of link_lesions give the float32 back
+    reach = [[] for _ in vol_pred]                                  # per candidate: (iou, tumour)
+    for (t, q), n in sorted(overlap.items()):
+        if n >= 1:
+            reach[q].append((n / (vol_true[t] + vol_pred[q] - n), t))
+    taken, hits, partner = set(), [0] * len(vol_pred), [(-1, 0.0)] * len(vol_pred)
+    for q in sorted(range(len(vol_pred)), key=lambda q: (-conf[q], q)):
+        free = [(s, -t) for s, t in reach[q] if s >= iou and t not in taken]
+        if free:
+            s, t = max(free)
+            taken.add(-t)
+            hits[q], partner[q] = 1, (-t, s)
+        elif reach[q]:
+            s, t = max((s, -t) for s, t in reach[q])
+            partner[q] = (-t, s)
+    lines = [[exam, int(r[1]), int(r[2]), int(r[3]), int(r[6]), '%.9g' % conf[q], partner[q][0], repr(float(partner[q][1])),
+              'tp' if hits[q] else 'fp'] for q, r in enumerate(pred_linked[0])]
+    return dict(exam=exam, tumours=len(vol_true), confidences=conf, hits=hits), lines
+
+
+def detection_case_values(case):
+    """the DETECTION_CASE_COLUMNS values of one detection_match case: the exam's score is its largest confidence, 0 without one"""
+    tp = sum(case['hits'])
+    return [case['exam'], int(case['tumours'] > 0), '%.9g' % max(case['confidences'], default=0.0), len(case['hits']), tp,
+            len(case['hits']) - tp, case['tumours'] - tp]
+
+
+def detection_curves(cases):
+    """The lesion-level ranking statistics of all exams: dict(exams, tumours, candidates, tp, fp, fn, levels, ap, sensitivities, cpm).
+    levels: one (confidence, TP, FP, sensitivity, FP per exam, precision) per distinct confidence in descending order -- equal
+    confidences enter together -- with cumulative counts; sensitivity = TP / tumours (None without tumours), precision = TP /
+    (TP + FP).  ap = sum_k (R_k - R_{k-1}) P_k over the levels, R_0 = 0 (None without tumours; 0.0 without candidates).
+    sensitivities: at every one of DETECTION_FP_RATES the largest sensitivity of a level whose FP per exam is <= x (the comparison
+    is FP <= x * exams in integers), 0.0 when none (None without tumours); cpm their mean."""
+    exams, tumours = len(cases), sum(int(c['tumours']) for c in cases)
+    ranked = sorted(((float(s), int(h)) for c in cases for s, h in zip(c['confidences'], c['hits'])), key=lambda v: -v[0])
+    levels, tp, fp, i = [], 0, 0, 0
+    while i < len(ranked):
+        j = i
+        while j < len(ranked) and ranked[j][0] == ranked[i][0]:
+            tp, fp, j = tp + ranked[j][1], fp + 1 - ranked[j][1], j + 1
+        levels.append((ranked[i][0], tp, fp, tp / tumours if tumours else None, fp / exams, tp / (tp + fp)))
+        i = j
+    ap = sens = cpm = None
+    if tumours:
+        ap, before = 0.0, 0.0
+        for _, _, _, recall, _, precision in levels:
+            ap, before = ap + (recall - before) * precision, recall
+        sens = [max([l[1] for l in levels if l[2] * 8 <= int(x * 8) * exams], default=0) / tumours for x in DETECTION_FP_RATES]
+        cpm = math.fsum(sens) / len(sens)
+    return dict(exams=exams, tumours=tumours, candidates=len(ranked), tp=tp, fp=fp, fn=tumours - tp, levels=levels, ap=ap,
+                sensitivities=sens, cpm=cpm)
+
+
+def detection_auroc(cases):
+    """exam-level AUROC: an exam's score is its largest candidate confidence (0 without a candidate), it is positive when it has a
+    labelled tumour.  (#[s+ > s-] + 1/2 #[s+ = s-]) / (P N), the pairs counted exactly; None when one class is absent"""
+    pos = [max(c['confidences'], default=0.0) for c in cases if c['tumours'] > 0]
+    neg = [max(c['confidences'], default=0.0) for c in cases if c['tumours'] == 0]
+    if not pos or not neg:
+        return None
+    twice = sum(2 * (p > n) + (p == n) for p in pos for n in neg)
+    return twice / (2 * len(pos) * len(neg))
+
+
+def detection_summary(cases, slices_exhausted=0):
+    """all exams' detection_match cases -> (the DETECTION_RESULT_COLUMNS values, the DETECTION_FROC_COLUMNS lines); undefined values
+    are blank cells; score = (AP + AUROC) / 2"""
+    c, auroc = detection_curves(cases), detection_auroc(cases)
+    score = None if c['ap'] is None or auroc is None else (c['ap'] + auroc) / 2
+    result = ([c['exams'], sum(1 for k in cases if k['tumours'] > 0), c['tumours'], c['candidates'], c['tp'], c['fp'], c['fn'],
+               _blank(c['ap']), _blank(auroc), _blank(score)] +
+              [_blank(None if c['sensitivities'] is None else s) for s in (c['sensitivities'] or DETECTION_FP_RATES)] +
+              [_blank(c['cpm']), int(slices_exhausted)])
+    froc = [['%.9g' % l[0], l[1], l[2], _blank(l[3]), repr(l[4]), repr(l[5])] for l in c['levels']]
+    return result, froc
+
+
+def candidate_values(exam, slice_id, row):
+    """the candidates.csv line of one row of the lesion table read from a detection map: the lesions.csv values plus the confidence"""
+    return lesion_values(exam, slice_id, row) + ['%.9g' % float(row['max_prob'])]
+
+
+def detection_image(D):
+    """detection.png of one slice: 8-bit grey, rint(D * 255)"""
+    return np.rint(np.asarray(D, np.float64) * 255.0).astype(np.uint8)
+
+
+def detection_path(root, tag):
+    """<root>/<last 3 components of the exam path>/<sliceID %02d>/detection.png"""
+    return os.path.join(export_dir(root, '', tag), 'detection.png')
 
 
 # ---- `annotator evaluate --surface_distances`: how far the predicted outline lies from the labelled one ----------------------------

@@ -10,6 +10,7 @@
 
 #include "boundary.h"
 #include "calib.h"
+#include "detect.h"
 #include "kernels.h"
 #include "region.h"
 #include "topk.h"
@@ -686,6 +687,21 @@ int dnnca_prob_temperature(void* model, const float* prob_hw, int batch, int h, 
     Planes dev;      // a host plane is scaled into a buffer behind it, the model's own in place
     DN_TRY(plane_stage(M, kScratchTtaIo, pl.n, {prob_hw, nullptr, nullptr, nullptr}, true, &dev));
     DN_TRY(prob_temperature(M, dev.prob, dev.out, pl.n, temperature, out_hw));
+    return M->flush_profile();
+}
+
+// ---- the detection map (kernels_detect.hip) --------------------------------------------------------------------------------------
+int dnnca_detection_map(void* model, const float* prob_hw, int batch, int h, int w, const dnnca_detection_cfg* cfg, float* out_hw,
+                        dnnca_detection_row* rows, int64_t* n_rows, dnnca_detection_slice* slices) {
+    MODEL(model);
+    if (!cfg || !rows || !n_rows || !slices) { set_error("detection: null cfg / rows / n_rows / slices"); return DNNCA_EINVAL; }
+    DN_TRY(detection_check(*cfg));
+    if (prob_hw && !out_hw) { set_error("detection: a host plane needs out_hw"); return DNNCA_EINVAL; }
+    Plane pl;
+    DN_TRY(plane_resolve(M, "detection", prob_hw, batch, h, w, kPlaneBelow2G | kPlaneGridBatch | kPlaneHeld, &pl));
+    Planes dev;      // a host plane's map goes into a buffer behind it, the model's own is replaced in place
+    DN_TRY(plane_stage(M, kScratchTtaIo, pl.n, {prob_hw, nullptr, nullptr, nullptr}, true, &dev));
+    DN_TRY(detection_map(M, dev.prob, dev.out, batch, pl.h, pl.w, *cfg, out_hw, rows, n_rows, slices));
     return M->flush_profile();
 }
 

@@ -35,6 +35,7 @@
 #include <algorithm>
 #include <tuple>
 
+#include "ccl_dev.h"
 #include "region.h"
 
 namespace dnnca {
@@ -147,33 +148,7 @@ __device__ __forceinline__ bool fg_at(const uint32_t* __restrict__ words, size_t
     return (words[(size_t)(t >> 5) * n + q] >> (t & 31)) & 1u;
 }
 
-__device__ __forceinline__ int ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int find_root(const int* L, int x) {
-    int y;
-    while ((y = ld_agent(L + x)) != x) x = y;
-    return x;
-}
-
-// union by atomicMin on roots (Playne & Hawick 2018): the larger root is linked to the smaller one; a lost race retries from the
-// value atomicMin returned
-__device__ void unite(int* L, int a, int b) {
-    for (;;) {
-        a = find_root(L, a);
-        b = find_root(L, b);
-        if (a == b) return;
-        if (a > b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(L + b, a);
-        if (old == b) return;
-        b = old;
-    }
-}
-
-__device__ __forceinline__ int lds_find(volatile int* l, int x) {
-    int y;
-    while ((y = l[x]) != x) x = y;
-    return x;
-}
+// ld_agent, find_root, unite (union by atomicMin on roots) and lds_find: ccl_dev.h, shared with kernels_detect.hip
 
 // one kTile x kTile tile of one plane labelled in LDS; L[g] = the global index of the pixel's root inside the tile (the tile's
 // row-major order is the global order, so that root is the smallest global index of the tile-local component)

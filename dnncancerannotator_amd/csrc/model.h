@@ -396,6 +396,11 @@ struct Model {
     // calibration (dnnca_calibration): the device tables, the temperatures and the block partials of the NLL, grown on demand
     void* calib_ws = nullptr;
     size_t calib_ws_bytes = 0;
+    // the detection map (dnnca_detection_map, kernels_detect.hip): scratch plane, parents, slice states and records, grown on
+    // demand; detect_last: the parameters of the last call (what DNNCA_PLAN_DETECTION replays)
+    void* detect_ws = nullptr;
+    size_t detect_ws_bytes = 0;
+    dnnca_detection_cfg detect_last = {0.1f, 0.4f, 5, 10, 16};
 
     ~Model();
     int build();

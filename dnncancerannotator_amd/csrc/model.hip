@@ -18,6 +18,7 @@
 #include "region.h"
 #include "region_loss.h"
 #include "boundary.h"
+#include "detect.h"
 #include "topk.h"
 #include "sens.h"
 #include "attr.h"
@@ -101,6 +102,7 @@ Model::~Model() {
     if (opt.table) (void)hipFree(opt.table);
     if (tta_io) (void)hipFree(tta_io);
     if (calib_ws) (void)hipFree(calib_ws);
+    if (detect_ws) (void)hipFree(detect_ws);
     for (auto& r : recs) {
         (void)hipEventDestroy(r.a);
         (void)hipEventDestroy(r.b);
@@ -2689,7 +2691,8 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
     if (!buf || !cap) return DNNCA_EINVAL;
     if (pass != DNNCA_PLAN_TRAIN && pass != DNNCA_PLAN_EVAL && pass != DNNCA_PLAN_FORWARD && pass != DNNCA_PLAN_SENSITIVITY &&
         pass != DNNCA_PLAN_LESION && pass != DNNCA_PLAN_LESION_LINKED && pass != DNNCA_PLAN_LESION_MATCHED &&
-        pass != DNNCA_PLAN_SURFACE && pass != DNNCA_PLAN_ATTRIBUTION && pass != DNNCA_PLAN_LESION_FEATURES) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
+        pass != DNNCA_PLAN_SURFACE && pass != DNNCA_PLAN_ATTRIBUTION && pass != DNNCA_PLAN_LESION_FEATURES &&
+        pass != DNNCA_PLAN_DETECTION) { set_error("unknown plan pass %d", pass); return DNNCA_EINVAL; }
     DN_TRY(check_batch(M, batch));
     M->plan_text.clear();
     M->dry = true;
@@ -2738,6 +2741,8 @@ int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap
         rc = lesion_check(a, M->outH, M->outW);
         if (rc == DNNCA_OK)
             rc = surface_distances(M, M->prob, M->y_stage, B, M->outH, M->outW, a, 1, nullptr, nullptr, nullptr, nullptr);
+    } else if (pass == DNNCA_PLAN_DETECTION) {
+        rc = detection_map(M, M->prob, M->prob, B, M->outH, M->outW, M->detect_last, nullptr, nullptr, nullptr, nullptr);
     } else {
         rc = dnnca_forward_dev(model, M->x_stage, B, 0);
     }

@@ -1,5 +1,6 @@
 // region.h -- region-based (lesion-level) metrics on the device (kernels_region.hip): the host side of the pipeline that the C ABI
-// of abi_analysis.hip drives (dnnca_region_confusion*, dnnca_eval_region_*, the lesion tables, the boundary distances).
+// of abi_analysis.hip drives (dnnca_region_confusion*, dnnca_eval_region_*, the lesion tables, the boundary distances).  The device
+// helpers of its connected-component kernels are in ccl_dev.h, which kernels_detect.hip shares.
 #pragma once
 #include <algorithm>
 

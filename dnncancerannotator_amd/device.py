@@ -888,6 +888,32 @@ class DeviceModel:
                                               fptr(out)))
         return out
 
+    def _detection(self, prob, batch, min_confidence=0.1, factor=0.4, max_candidates=5, min_area=10, rounds=16):
+        cfg = _lib.DetectionCfg(float(min_confidence), float(factor), int(max_candidates), int(min_area), int(rounds))
+        B = int(batch) if prob is None else prob.shape[0]
+        rows = np.zeros(max(B, 0) * min(max(int(max_candidates), 0), 64), _lib.DETECTION_ROW_DTYPE)
+        slices = np.zeros(max(B, 0), _lib.DETECTION_SLICE_DTYPE)
+        n_rows = C.c_int64(0)
+        out = None if prob is None else np.empty_like(prob)
+        h, w = (0, 0) if prob is None else prob.shape[1:]
+        check(self.lib.dnnca_detection_map(self.handle, None if prob is None else fptr(prob), B, h, w, C.byref(cfg),
+                                           None if out is None else fptr(out), rows.ctypes.data_as(C.POINTER(_lib.DetectionRow)),
+                                           C.byref(n_rows), slices.ctypes.data_as(C.POINTER(_lib.DetectionSlice))))
+        return out, rows[:n_rows.value].copy(), slices
+
+    def detection_map(self, batch, **cfg):
+        """the detection map of the last forward's `batch` slices (dnnca_detection_map), IN PLACE: the model's probability buffer is
+        replaced by the map D (a candidate's confidence on every one of its pixels, 0 elsewhere), so every later consumer of "the last
+        forward" reads D.  Returns (rows, slices): rows a structured array (_lib.DETECTION_ROW_DTYPE: slice, number, seed, area,
+        confidence) sorted by (slice, number), slices (_lib.DETECTION_SLICE_DTYPE: candidates, rounds, dropped, exhausted) [batch].
+        cfg: min_confidence 0.1, factor 0.4, max_candidates 5, min_area 10, rounds 16.  Everything is bit-identical from run to run."""
+        _, rows, slices = self._detection(None, batch, **cfg)
+        return rows, slices
+
+    def detection_map_of(self, prob, **cfg):
+        """the same of a host plane `prob` [B, h, w] of any size: (D, rows, slices); the model's buffer stays untouched."""
+        return self._detection(_slices(prob, 'prob'), None, **cfg)
+
     def lesion_table_linked(self, batch=None, prob=None, continues=None, threshold=0.5, resize_factor=1.0, filter_size=5, min_area=0,
                             max_lesions=256, mask=True):
         """lesion_table plus the links between neighbouring slices: (rows, totals, masks, links); the first three are what
@@ -1206,7 +1232,7 @@ class DeviceModel:
         return out
 
     PLAN_PASSES = {'train': 0, 'eval': 1, 'forward': 2, 'sensitivity': 3, 'lesion': 4, 'lesion_linked': 5, 'lesion_matched': 6,
-                   'surface': 7, 'attribution': 8, 'lesion_features': 9}
+                   'surface': 7, 'attribution': 8, 'lesion_features': 9, 'detection': 10}
 
     def plan(self, variants=False, mode='train', batch=None):
         """The launch schedule of one pass: [(kernel, algorithmic bytes, flops)].  mode 'train': one train step; 'eval': one
@@ -1217,7 +1243,8 @@ class DeviceModel:
         surface_distances with the resize factor and filter size of the last surface_distances call; 'attribution':
         integrated_gradients with the steps and baseline of the last integrated_gradients call (before any: 32, 'black') and the map;
         'lesion_features': lesion_table_features on the staged batch with the resize factor, filter size, mask choice, bins and ring
-        of the last lesion_table_features call (before any: 1.0, 5, with mask, 32, 3).
+        of the last lesion_table_features call (before any: 1.0, 5, with mask, 32, 3); 'detection': detection_map in place with the
+        parameters of the last detection_map / detection_map_of call (before any: the defaults).
         batch: None = max_batch.  variants: keep the template variant the library appends to a launch name
         (`ig_conv_fwd#3n2w8`): the kernel-coverage test tells them apart.  A dry run: the model is unchanged."""
         if mode not in self.PLAN_PASSES:

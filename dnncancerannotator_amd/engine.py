@@ -108,6 +108,44 @@ def check_calibration(n_bins, temperatures):
     return int(n_bins), casewise.calibration_grid(temperatures)
 
 
+def check_detection(detection, min_confidence=None, factor=None, max_candidates=None, min_area=None, rounds=None, iou=None,
+                    link_min_overlap=None, max_lesions=None, flag='--detection'):
+    """the values of the --detection_* flags (None: not given) -> None without `detection` (any value given is then a ValueError:
+    they mean nothing without the flag), else dict(cfg=the keywords of DeviceModel.detection_map with the defaults filled in, iou,
+    link_min_overlap, max_lesions).  Every value outside what the library accepts (casewise.DETECTION_RANGES; rounds at least
+    max_candidates), NaN included, is a ValueError -- before anything is read"""
+    given = dict(min_confidence=min_confidence, factor=factor, max_candidates=max_candidates, min_area=min_area, rounds=rounds)
+    if not detection:
+        if any(v is not None for v in list(given.values()) + [iou, link_min_overlap, max_lesions]):
+            raise ValueError('the --detection_* options set the candidate extraction of %s: add %s' % (flag, flag))
+        return None
+    cfg = {}
+    for key, default in casewise.DETECTION_DEFAULTS.items():
+        v = default if given[key] is None else given[key]
+        lo, hi = casewise.DETECTION_RANGES[key]
+        if isinstance(default, int):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError('--detection_%s must be an integer, got %r' % (key, v))
+            v = int(v)
+        else:
+            v = float(v)
+        if not lo <= v <= hi:                                       # (False for a NaN)
+            raise ValueError('--detection_%s must lie in [%g, %g], got %r' % (key, lo, hi, given[key]))
+        cfg[key] = v
+    if cfg['rounds'] < cfg['max_candidates']:
+        raise ValueError('--detection_rounds %d is below --detection_max_candidates %d: every candidate costs a round'
+                         % (cfg['rounds'], cfg['max_candidates']))
+    iou = casewise.DETECTION_IOU if iou is None else float(iou)
+    if not 0.0 < iou <= 1.0:
+        raise ValueError('--detection_iou must lie in (0, 1], got %r' % (iou,))
+    link_min_overlap = 1 if link_min_overlap is None else int(link_min_overlap)
+    max_lesions = 256 if max_lesions is None else int(max_lesions)
+    if link_min_overlap < 1 or max_lesions < 1:
+        raise ValueError('--detection_link_min_overlap and --detection_max_lesions must be at least 1, got %d and %d'
+                         % (link_min_overlap, max_lesions))
+    return dict(cfg=cfg, iou=iou, link_min_overlap=link_min_overlap, max_lesions=max_lesions)
+
+
 EMA_KEYS = ('decay', 'warmup', 'validate')
 WEIGHT_CHOICES = ('raw', 'ema')
 
@@ -900,7 +938,10 @@ class TFKerasModel:
              surface_min_area=0, surface_filter_size=5, surface_resize_factor=1.0, surface_max_samples=65536, tta='none',
              uncertainty_ds=None, uncertainty=False, uncertainty_thresholds=(0.5,), calibration_ds=None, calibration=False,
              calibration_bins=casewise.CALIBRATION_BINS, calibration_temperatures=None, temperature=None,
-             visualize_attribution=False, attribution_steps=None, attribution_baseline=None, weights='raw'):
+             visualize_attribution=False, attribution_steps=None, attribution_baseline=None, weights='raw', detection_ds=None,
+             detection=False, detection_min_confidence=None, detection_factor=None, detection_max_candidates=None,
+             detection_min_area=None, detection_rounds=None, detection_iou=None, detection_link_min_overlap=None,
+             detection_max_lesions=None):
         """weights (`evaluate --weights ema`): every checkpoint is loaded with its averaged weights as the parameters (load(...,
         weights='ema')); everything downstream reads that model unchanged.  Checkpoints without an average are an error that names
         the first, raised before anything is evaluated.
@@ -931,8 +972,15 @@ class TFKerasModel:
         each plain forward left on the device and writes per slice step_<step>_attribution.csv (export_csv) and
         step_<step>_attribution.png (export_images: only then does a map leave the device), and per checkpoint a line of
         attribution_results.csv under <export_path>/<tag>/.  Like the sensitivity it is the attribution of the plain forward, also
-        under tta / temperature.  Needs export_csv or export_images; every other file is what it is without the flag."""
+        under tta / temperature.  Needs export_csv or export_images; every other file is what it is without the flag.
+        detection (`evaluate --detection`): after every checkpoint's evaluation rank 0 also runs _detection_pass over detection_ds
+        (the same kind of data set as exam_ds; the flags may share one) and writes detection_results.csv, detection_froc.csv,
+        detection_cases.csv and detection_candidates.csv under <export_path>/<tag>/: ranked lesion candidates of the detection map
+        (DeviceModel.detection_map with the detection_* values, check_detection), lesion-level AP and FROC, exam-level AUROC.  Under
+        tta / temperature / weights the map is that of the probabilities they give.  Every other file is what it is without it."""
         check_uncertainty(uncertainty, tta)
+        detection = check_detection(detection, detection_min_confidence, detection_factor, detection_max_candidates, detection_min_area,
+                                    detection_rounds, detection_iou, detection_link_min_overlap, detection_max_lesions)
         attribution = check_attribution(visualize_attribution, attribution_steps, attribution_baseline, export_csv, export_images)
         temperature = check_temperature(temperature)
         if calibration:
@@ -983,6 +1031,8 @@ class TFKerasModel:
         calibration_pass = bool(calibration) and calibration_ds is not None and self.ctx.rank == 0
         calibration_tables = [], [], []  # the lines of calibration_results.csv, calibration_bins.csv and calibration_slices.csv
         attribution_table, attribution_names = [], []      # the lines of attribution_results.csv; the modalities of its share columns
+        detection_pass = detection is not None and detection_ds is not None and self.ctx.rank == 0
+        detection_tables = [], [], [], []    # the lines of detection_results.csv, _froc.csv, _cases.csv and _candidates.csv
         rows = OrderedDict()
         previous_step = None
         for ckpt_step, ckpt_path_ in self.get_ckpts(ckpt_path).items():
@@ -1020,6 +1070,16 @@ class TFKerasModel:
                 for t, new in zip(calibration_tables, self._calibration_pass(calibration_ds, ckpt_step, calibration_bins,
                                                                              calibration_grid, tta_mask, **more)):
                     t += new
+            if detection_pass:
+                for t, new in zip(detection_tables, self._detection_pass(detection_ds, ckpt_step, detection, tta_mask=tta_mask, **more)):
+                    t += new
+        if detection_pass:
+            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
+            for name, cols, table in zip(('detection_results.csv', 'detection_froc.csv', 'detection_cases.csv', 'detection_candidates.csv'),
+                                         (casewise.DETECTION_RESULT_COLUMNS, casewise.DETECTION_FROC_COLUMNS,
+                                          casewise.DETECTION_CASE_COLUMNS, casewise.DETECTION_CANDIDATE_COLUMNS), detection_tables):
+                with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
+                    f.write(casewise.plain_csv(['step'] + cols, table))
         if calibration_pass:
             os.makedirs(os.path.join(export_path, tag), exist_ok=True)
             for name, cols, table in zip(('calibration_results.csv', 'calibration_bins.csv', 'calibration_slices.csv'),
@@ -1198,6 +1258,49 @@ class TFKerasModel:
             results.append(lead + casewise.exam_match_summary(mine_cases))
         return results, cases, matches
 
+    def _detection_pass(self, ds, step, det, tta_mask=None, temperature=None):
+        """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --detection`: per max_batch split one forward whose
+        probabilities stay on the device, DeviceModel.detection_map in place (the buffer then holds the map) and one
+        DeviceModel.lesion_table_matched on it (casewise.detection_table_args: the rows are the candidates, max_prob their
+        confidence); then per exam casewise.link_lesions on either plane and casewise.detection_match, and casewise.detection_summary
+        over all exams.  det: what check_detection returned.  Returns the new lines of (detection_results.csv, detection_froc.csv,
+        detection_cases.csv, detection_candidates.csv), each led by step.  Slices continue each other by _exam_lesion_pass's rule."""
+        kw = casewise.detection_table_args(det['cfg'], det['max_lesions'])
+        found, exhausted = [], 0             # per slice: (exam, slice, rows, total, links, true rows, total, links, pairs)
+        before, last = None, None
+        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature):
+            if last is not None and dm is not before:
+                logging.warning('evaluate: the model was re-sized before slice %s of %s: it is not linked to the slice before', pk[0][1], pk[0][0])
+                last = None
+            before = dm
+            continues = []
+            for p, k in pk:
+                continues.append(last is not None and p == last[0] and int(k) == last[1] + 1)
+                last = (p, int(k))
+            _, slice_records = dm.detection_map(len(xb), **det['cfg'])
+            exhausted += int(slice_records['exhausted'].sum())
+            out = dm.lesion_table_matched(yb, batch=len(xb), continues=continues, **kw)
+            by_slice = [[o[o['slice'] == b] for b in range(len(xb))] for o in (out[0], out[3], out[4], out[6], out[7])]
+            for b, (p, k) in enumerate(pk):
+                rows, links, true_rows, true_links, pairs = [s[b] for s in by_slice]
+                found.append((p, int(k), rows, out[1][b], [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in links],
+                              true_rows, out[5][b], [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in true_links],
+                              [(int(q['row_true']), int(q['row']), int(q['overlap'])) for q in pairs]))
+        exams = OrderedDict()                # exam path -> its slices, in the order of the data set
+        for rec in found:
+            exams.setdefault(rec[0], []).append(rec)
+        lead, cases, candidates = [int(step)], [], []
+        for exam, recs in exams.items():
+            pred_slices, true_slices = [r[1:4] for r in recs], [(r[1], r[5], r[6]) for r in recs]
+            pred_linked = casewise.link_lesions(exam, pred_slices, [r[4] for r in recs], min_overlap=det['link_min_overlap'])
+            true_linked = casewise.link_lesions(exam, true_slices, [r[7] for r in recs], min_overlap=det['link_min_overlap'])
+            case, lines = casewise.detection_match(exam, true_slices, pred_slices, true_linked, pred_linked, [r[8] for r in recs],
+                                                   iou=det['iou'])
+            cases.append(case)
+            candidates += [lead + l for l in lines]
+        result, froc = casewise.detection_summary(cases, exhausted)
+        return [lead + result], [lead + l for l in froc], [lead + casewise.detection_case_values(c) for c in cases], candidates
+
     def _surface_pass(self, ds, step, thresholds, percentile, kw, tta_mask=None, temperature=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --surface_distances`: per max_batch split one forward whose
         probabilities stay on the device and one DeviceModel.surface_distances per threshold; only the counts and the boundary
@@ -1272,7 +1375,9 @@ class TFKerasModel:
 
     def annotate(self, dataset, save_path, output, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
                  max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
-                 temperature=None, lesion_features=False, feature_bins=None, feature_ring=None, weights='raw'):
+                 temperature=None, lesion_features=False, feature_bins=None, feature_ring=None, weights='raw', detection_map=False,
+                 detection_min_confidence=None, detection_factor=None, detection_max_candidates=None, detection_min_area=None,
+                 detection_rounds=None, detection_link_min_overlap=None, detection_max_lesions=None):
         """`annotator predict`: the lesions of slices that have no label.  Loads checkpoint `step` of save_path (None: the latest);
         per batch (x, paths, sliceIDs) of `dataset` (make_dataset(..., include_meta=True, labels=False)) one forward whose
         probabilities stay on the device, then DeviceModel.lesion_table: threshold, filter_size x filter_size opening, components
@@ -1303,8 +1408,17 @@ class TFKerasModel:
         lesion) and with link_slices exam_lesion_features.csv (one line per line of exam_lesions.csv, pooled from the parts'
         integers) are written beside the other files, which are what they are without the flag.
         weights (`predict --weights ema`): the checkpoint's averaged weights become the parameters (load(..., weights='ema')); a
-        checkpoint without an average is an error that names it.  Every table and mask is then that of the averaged model."""
+        checkpoint without an average is an error that names it.  Every table and mask is then that of the averaged model.
+        detection_map (`predict --detection_map [--detection_* ...]`, check_detection): per chunk, LAST -- it replaces the
+        probability buffer -- DeviceModel.detection_map in place, then a table read from the map (casewise.detection_table_args):
+        DeviceModel.lesion_table, or with link_slices DeviceModel.lesion_table_matched against empty labels, whose carry is a chain
+        of its own, so the candidates' links do not disturb those of the lesions.  candidates.csv (the columns of lesions.csv plus
+        confidence), slice_candidates.csv (candidates, rounds, dropped, exhausted per slice), with link_slices exam_candidates.csv
+        and with export_images <exam>/<slice>/detection.png (8-bit grey, rint(D * 255): only then does a map leave the device) are
+        written beside the other files, which are what they are without the flag; the returned dict gains 'candidates'."""
         check_uncertainty(uncertainty, tta)
+        det = check_detection(detection_map, detection_min_confidence, detection_factor, detection_max_candidates, detection_min_area,
+                              detection_rounds, None, detection_link_min_overlap, detection_max_lesions, flag='--detection_map')
         check_weights(weights)
         temperature = check_temperature(temperature)
         feature_bins, feature_ring = casewise.check_features(lesion_features, feature_bins, feature_ring)
@@ -1329,6 +1443,7 @@ class TFKerasModel:
         feature_rows, linked_features = [], []       # linked_features: beside `linked`, every slice's feature records per lesion
         modalities = casewise.modality_names(getattr(dataset, 'slice_types', None), _element_shape(dataset)[3]) if lesion_features else None
         scale = {} if temperature is None else dict(temperature=temperature)      # the forward gets the keyword only with a temperature
+        candidate_rows, slice_candidate_rows, candidates_linked = [], [], []         # detection_map: as lesion_rows / slice_rows / linked
         dm = None
         linked, last = [], None          # link_slices: (exam, slice, rows, total, links into it) per slice; the slice before: (exam, slice)
         writer = casewise.Writer() if export_images else None
@@ -1372,6 +1487,27 @@ class TFKerasModel:
                         if len(srows) != len(rows):
                             raise RuntimeError('predict: %d spread records beside %d lesions' % (len(srows), len(rows)))
                         spread = dm.last_spread(len(xb)) if export_images else None
+                    if det:                          # last: from here on the buffer holds the map
+                        _, drecs = dm.detection_map(len(xb), **det['cfg'])
+                        dkw = casewise.detection_table_args(det['cfg'], det['max_lesions'])
+                        if link_slices:
+                            dout = dm.lesion_table_matched(np.zeros((len(xb),) + xb.shape[1:3], np.float32), batch=len(xb),
+                                                           continues=continues, **dkw)
+                            drows, dtotals, dlinks = dout[0], dout[1], dout[3]
+                        else:
+                            drows, dtotals, _ = dm.lesion_table(batch=len(xb), mask=False, **dkw)
+                        dmaps = dm.last_prob(len(xb)) if export_images else None
+                        for b, (p, k) in enumerate(pk):
+                            mine = drows[drows['slice'] == b]
+                            candidate_rows += [casewise.candidate_values(p, k, r) for r in mine]
+                            slice_candidate_rows.append([p, int(k)] + [int(drecs[b][f]) for f in ('candidates', 'rounds', 'dropped', 'exhausted')])
+                            if link_slices:
+                                into = dlinks[dlinks['slice'] == b]
+                                candidates_linked.append((p, int(k), mine, dtotals[b],
+                                                          [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in into]))
+                            if export_images:
+                                writer.submit(casewise.detection_path(output, casewise.tag_of(p, k)),
+                                              lambda d_: casewise.encode_png(casewise.detection_image(d_)), dmaps[b])
                     for b, (p, k) in enumerate(pk):
                         mine = rows[rows['slice'] == b]
                         if link_slices:
@@ -1428,6 +1564,19 @@ class TFKerasModel:
             res['exam_lesions'] = len(exam_rows)
             if lesion_features:
                 tables.append(('exam_lesion_features.csv', casewise.exam_lesion_feature_columns(modalities), exam_feature_rows))
+        if det:
+            tables += [('candidates.csv', casewise.CANDIDATE_COLUMNS, candidate_rows),
+                       ('slice_candidates.csv', casewise.SLICE_CANDIDATE_COLUMNS, slice_candidate_rows)]
+            res['candidates'] = len(candidate_rows)
+            if link_slices:
+                exams = OrderedDict()
+                for rec in candidates_linked:
+                    exams.setdefault(rec[0], []).append(rec)
+                exam_candidates = []
+                for exam, recs in exams.items():
+                    table, _ = casewise.link_lesions(exam, [r[1:4] for r in recs], [r[4] for r in recs], min_overlap=det['link_min_overlap'])
+                    exam_candidates += [r + [r[15]] for r in table]
+                tables.append(('exam_candidates.csv', casewise.EXAM_CANDIDATE_COLUMNS, exam_candidates))
         for name, cols, table in tables:
             with open(os.path.join(output, name), 'w', newline='') as f:
                 f.write(casewise.plain_csv(cols, table))

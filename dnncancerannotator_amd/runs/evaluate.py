@@ -13,8 +13,15 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
              surface_distances=False, surface_threshold=(0.5,), surface_percentile=95.0, surface_min_area=0, surface_filter_size=5,
              surface_resize_factor=1.0, surface_max_samples=65536, tta='none', uncertainty=False, uncertainty_threshold=(0.5,),
              calibration=False, calibration_bins=15, calibration_temperatures=None, temperature=None, visualize_attribution=False,
-             attribution_steps=None, attribution_baseline=None, weights='raw'):
+             attribution_steps=None, attribution_baseline=None, weights='raw', detection=False, detection_min_confidence=None,
+             detection_factor=None, detection_max_candidates=None, detection_min_area=None, detection_rounds=None, detection_iou=None,
+             detection_link_min_overlap=None, detection_max_lesions=None):
     engine.check_uncertainty(uncertainty, tta)       # before anything is read
+    detection_values = dict(detection_min_confidence=detection_min_confidence, detection_factor=detection_factor,
+                            detection_max_candidates=detection_max_candidates, detection_min_area=detection_min_area,
+                            detection_rounds=detection_rounds, detection_iou=detection_iou,
+                            detection_link_min_overlap=detection_link_min_overlap, detection_max_lesions=detection_max_lesions)
+    engine.check_detection(detection, *detection_values.values())      # likewise, the --detection_* flags without --detection included
     if engine.check_weights(weights) == 'ema':       # likewise: the index of every checkpoint that will be evaluated
         engine.check_ema_checkpoints(engine.select_ckpts(engine.list_ckpts(os.path.join(save_path, 'checkpoints')), min_interval,
                                                          step_range).values())
@@ -34,7 +41,7 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
     # --exam_lesions, --surface_distances, --uncertainty and --calibration read a data set of their own (the slices with their labels, exam path and sliceID;
     # --skip_visualization does not touch it): one is built and shared when several are given
     meta_ds = make_dataset(data_path, config.get('data_options', {}).get('eval', {}), training=False, include_meta=True) \
-        if exam_lesions or surface_distances or uncertainty or calibration else None
+        if exam_lesions or surface_distances or uncertainty or calibration or detection else None
     exam_ds = meta_ds if exam_lesions else None
     # the keywords of --surface_distances go to model.eval only with the flag
     surface = dict(surface_ds=meta_ds, surface_distances=surface_distances, surface_threshold=surface_threshold,
@@ -52,6 +59,8 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
         more.update(visualize_attribution=True, attribution_steps=attribution[0], attribution_baseline=attribution[1])
     if weights == 'ema':                 # and the keyword of --weights only with the averaged weights
         more['weights'] = 'ema'
+    if detection:                        # and those of --detection only with the flag
+        more.update(detection_ds=meta_ds, detection=True, **detection_values)
     model = engine.TFKerasModel(config)
     return model.eval(ds, viz_ds=viz_ds, tag=tag, save_path=os.path.join(save_path), avoid_overwrite=avoid_overwrite,
                       export_path=export_path, export_images=export_images, export_csv=export_csv,

@@ -3,7 +3,9 @@ checkpoint (lesions.csv, slices.csv and, with --export_images, one mask.png per 
 exam_lesion_parts.csv: the lesions joined through the slices of an exam; with --tta MODE --uncertainty also lesion_uncertainty.csv,
 slice_uncertainty.csv and uncertainty.png: how much the views disagree; with --temperature T every table reads the probabilities
 scaled by T; with --lesion_features also lesion_features.csv and, with --link_slices, exam_lesion_features.csv: outline, axes and
-per modality the intensities in and around every lesion; engine.TFKerasModel.annotate)."""
+per modality the intensities in and around every lesion; with --detection_map also candidates.csv, slice_candidates.csv, with
+--link_slices exam_candidates.csv and with --export_images detection.png: ranked lesion candidates without a fixed threshold;
+engine.TFKerasModel.annotate)."""
 
 import os
 
@@ -13,8 +15,16 @@ from .train import make_dataset
 
 def predict(save_path, data_path, output, config=None, step=None, threshold=0.5, min_area=0, filter_size=5, resize_factor=1.0,
             max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
-            temperature=None, lesion_features=False, feature_bins=None, feature_ring=None, weights='raw'):
+            temperature=None, lesion_features=False, feature_bins=None, feature_ring=None, weights='raw', detection_map=False,
+            detection_min_confidence=None, detection_factor=None, detection_max_candidates=None, detection_min_area=None,
+            detection_rounds=None, detection_link_min_overlap=None, detection_max_lesions=None):
     engine.check_uncertainty(uncertainty, tta)       # before anything is read
+    detection_values = dict(detection_min_confidence=detection_min_confidence, detection_factor=detection_factor,
+                            detection_max_candidates=detection_max_candidates, detection_min_area=detection_min_area,
+                            detection_rounds=detection_rounds, detection_link_min_overlap=detection_link_min_overlap,
+                            detection_max_lesions=detection_max_lesions)
+    engine.check_detection(detection_map, detection_min_confidence, detection_factor, detection_max_candidates, detection_min_area,
+                           detection_rounds, None, detection_link_min_overlap, detection_max_lesions, flag='--detection_map')      # likewise
     if engine.check_weights(weights) == 'ema':       # likewise: the index of the checkpoint that will be read
         ckpts = engine.list_ckpts(os.path.join(save_path, 'checkpoints'))
         if ckpts and (step is None or step in ckpts):          # (a missing checkpoint is annotate's error, as without the flag)
@@ -37,6 +47,8 @@ def predict(save_path, data_path, output, config=None, step=None, threshold=0.5,
         more.update(lesion_features=True, feature_bins=feature_bins, feature_ring=feature_ring)
     if weights == 'ema':                 # and the keyword of --weights only with the averaged weights
         more['weights'] = 'ema'
+    if detection_map:                    # and those of --detection_map only with the flag
+        more.update(detection_map=True, **detection_values)
     model = engine.TFKerasModel(config)
     return model.annotate(ds, save_path=save_path, output=output, step=step, threshold=threshold, min_area=min_area,
                           filter_size=filter_size, resize_factor=resize_factor, max_lesions=max_lesions,

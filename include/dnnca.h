@@ -690,6 +690,34 @@ int dnnca_calibration(void* model, const float* prob_hw, const float* y_hw, int 
  * Variables and state stay untouched.  Synchronises. */
 int dnnca_prob_temperature(void* model, const float* prob_hw, int batch, int h, int w, float temperature, float* out_hw);
 
+/* ---- the detection map: ranked lesion candidates without a fixed threshold (`evaluate --detection`, `predict --detection_map`) ---
+ * The dynamic candidate extraction of PI-CAI's extract_lesion_candidates, per slice of h x w float32 values p:
+ *     w = min(max(p, 0), 1), a NaN counts as 0;  D = 0;  n = 0
+ *     for round = 1 .. rounds:
+ *         m = max(w);  s = the smallest pixel index with w == m;  if m < min_confidence: stop
+ *         t = (float32) m * (float32) factor                       (one float32 product)
+ *         C = the 4-connected component of { w >= t } that contains s
+ *         if |C| >= min_area: D[C] = m, candidate n = (seed s, area |C|, confidence m), n += 1;  else dropped += 1
+ *         w[C] = 0;  if n == max_candidates: stop
+ * Candidates never overlap and nothing depends on a thread order: map, rows and slice records are bit-identical from run to run.
+ * slices[b] = (candidates, rounds spent, regions dropped below min_area, exhausted); exhausted = 1 says that all `rounds` rounds
+ * are spent, fewer than max_candidates were found and a value >= min_confidence is still left.  rows receives *n_rows records
+ * sorted by (slice, number); a slice's numbers run from 0 in the order of the rounds, i.e. in descending confidence.
+ * prob_hw == NULL: the model's probability buffer (the last forward's, the mean of dnnca_forward_tta, scaled by
+ * dnnca_prob_temperature) is replaced IN PLACE by D for `batch` slices (DNNCA_ESTATE when the last forward had fewer) -- every
+ * later consumer of "the last forward" reads the detection map; out_hw may be NULL, or receives a copy.  With a host plane prob_hw
+ * [batch, h, w] of any size out_hw is required and the model's buffer stays untouched.
+ * DNNCA_EINVAL, with nothing launched and nothing touched: batch outside [1, max_batch], min_confidence outside [0.001, 1], factor
+ * outside [0.01, 1], max_candidates outside 1..64, min_area outside 1..2^30, rounds outside max_candidates..256, a NaN, a NULL cfg /
+ * rows / slices / n_rows, a host plane without out_hw, a plane that is empty or has 2^31 pixels or more.  Variables, state and the
+ * carried rows of dnnca_lesion_table_linked / _matched stay untouched.  Synchronises. */
+typedef struct dnnca_detection_cfg { float min_confidence, factor; int32_t max_candidates, min_area, rounds; } dnnca_detection_cfg;
+typedef struct dnnca_detection_row { int32_t slice, number, seed, area; float confidence; } dnnca_detection_row;   /* 20 bytes */
+typedef struct dnnca_detection_slice { int32_t candidates, rounds, dropped, exhausted; } dnnca_detection_slice;  /* 16 bytes */
+int dnnca_detection_map(void* model, const float* prob_hw, int batch, int h, int w, const dnnca_detection_cfg* cfg,
+                        float* out_hw, dnnca_detection_row* rows /* [batch * max_candidates] */, int64_t* n_rows,
+                        dnnca_detection_slice* slices /* [batch] */);
+
 /* ---- the same table plus the links between neighbouring slices of an exam (`annotator predict --link_slices`) ------------------
  * Every argument up to out_hw means what it means for dnnca_lesion_table (the size query with rows == NULL included), and rows,
  * totals and mask are bit-identical to that call's.  continues [batch]: continues[b] != 0 says that slice b is the next slice of
@@ -852,11 +880,12 @@ int dnnca_plan_dump(void* model, char* buf, size_t cap);
    filter size of the last dnnca_surface_distances call (before any: 1.0, 5), or dnnca_integrated_gradients with the steps and
    baseline of the last dnnca_integrated_gradients call (before any: 32, black) and the map requested, or
    dnnca_lesion_table_features on the staged batch with the resize factor, filter size, mask choice, bins and ring of the last
-   dnnca_lesion_table_features call (before any: 1.0, 5, with mask, 32, 3).  A dry run: nothing is launched and the model is left
+   dnnca_lesion_table_features call (before any: 1.0, 5, with mask, 32, 3), or dnnca_detection_map in place with the parameters
+   of the last dnnca_detection_map call (before any: 0.1, 0.4, 5, 10, 16).  A dry run: nothing is launched and the model is left
    as it was. */
 enum { DNNCA_PLAN_TRAIN = 0, DNNCA_PLAN_EVAL = 1, DNNCA_PLAN_FORWARD = 2, DNNCA_PLAN_SENSITIVITY = 3, DNNCA_PLAN_LESION = 4,
        DNNCA_PLAN_LESION_LINKED = 5, DNNCA_PLAN_LESION_MATCHED = 6, DNNCA_PLAN_SURFACE = 7, DNNCA_PLAN_ATTRIBUTION = 8,
-       DNNCA_PLAN_LESION_FEATURES = 9 };
+       DNNCA_PLAN_LESION_FEATURES = 9, DNNCA_PLAN_DETECTION = 10 };
 int dnnca_plan_dump_pass(void* model, int pass, int batch, char* buf, size_t cap);
 /* the small-channel launchers' size predicate (a host function, no model needed): 1 when one image of H x W pixels with C float
    channels stays below 2^31 bytes, so that the kernels can address it with a 32-bit byte offset through one buffer descriptor;

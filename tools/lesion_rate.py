@@ -19,6 +19,8 @@ and prediction plane) plus pairs, match and count.
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --tta flips      # forward / forward_tta on it
     python tools/lesion_rate.py --features          # per-lesion features alone: the two launches, the call against its siblings
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --table_only     # plain lesion_table on it
+    python tools/lesion_rate.py --detection         # the detection map alone: its launches, the call beside lesion_table, the pass
+    DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --matched_only   # plain lesion_table_matched on it
 
 --link adds the cost of linking neighbouring slices: lesion_table_linked against lesion_table (wall time per call, device time of
 the three link launches), its worst case for the pair table (a checkerboard on itself: every other pixel a lesion of its own in
@@ -53,6 +55,14 @@ the drawn discs, and on the worst case (every slice one lesion: every pixel adds
 --table_only measures plain lesion_table on the drawn discs and nothing else: run it on this build and on a library built from the
 parent commit, in turns.
 
+--detection measures DeviceModel.detection_map (in place, the plane put back before every call) and nothing else, on three planes:
+the output of the random network as it is (smooth, pushed up: a candidate grows over much of the plane), the drawn discs, and the
+network's output above its 99th percentile on zeros (thousands of specks: every round finds a region below min_area).  Per plane the
+det_* launches event-bracketed and the call's wall time beside lesion_table on the same plane; then a forward + detection_map +
+lesion_table_matched pass against a forward + lesion_table_matched pass, alternated in one process.
+--matched_only measures plain lesion_table_matched on the drawn discs and nothing else: run it on this build and on a library built
+from the parent commit, in turns.
+
 The probabilities are drawn: the synthetic labels' discs at 0.55 .. 0.95 on a background of 0 .. 0.45 (a few lesions per slice,
 as a trained model gives), put into the model's probability buffer by pixel_confusion_of."""
 import argparse
@@ -79,6 +89,8 @@ ap.add_argument('--uncertainty', action='store_true', help='with --tta: also mea
 ap.add_argument('--calibration', action='store_true', help='measure calibration and scale_temperature, and nothing else')
 ap.add_argument('--features', action='store_true', help='measure lesion_table_features against lesion_table / lesion_table_spread, and nothing else')
 ap.add_argument('--table_only', action='store_true', help='measure plain lesion_table, and nothing else (also on a library built from the parent)')
+ap.add_argument('--detection', action='store_true', help='measure detection_map beside lesion_table and in an evaluation pass, and nothing else')
+ap.add_argument('--matched_only', action='store_true', help='measure plain lesion_table_matched, and nothing else (also on a library built from the parent)')
 ap.add_argument('--out', default=None, help='append the report to this file as well')
 a = ap.parse_args()
 if a.features:                                                   # its siblings are lesion_table and lesion_table_spread
@@ -90,6 +102,10 @@ if a.calibration:                                                # its yardstick
 else:
     for name in ('dnnca_calibration', 'dnnca_prob_temperature'):
         _lib.SIGNATURES.pop(name, None)                          # a library built from the parent does not export them
+if a.detection or a.matched_only:                                # their yardstick is lesion_table_matched
+    a.link = a.match = True
+if not a.detection:
+    _lib.SIGNATURES.pop('dnnca_detection_map', None)             # a library built from the parent does not export it
 if a.yardstick:
     _lib.SIGNATURES.pop('dnnca_lesion_table', None)              # a library built from the parent does not export it
 if not a.link:
@@ -168,12 +184,76 @@ ds = ArrayDataset(np.concatenate([x] * NB), None, B, meta_path='/synthetic/p0/e0
 e._build(ds)
 dm = e.device_model
 say('%s: %d x %d x %d, library %s' % ('yardstick' if a.yardstick else 'lesion features' if a.features else 'plain lesion table' if a.table_only else
+                                      'detection map' if a.detection else 'plain matched table' if a.matched_only else
                                       'calibration' if a.calibration else 'test-time augmentation' if a.tta else 'lesion table', B, S, S, os.path.basename(_lib.LIB_PATH)))
 if a.table_only:
     dm.pixel_confusion_of(prob, y, [0.5])
     for mask in (True, False) * 2:
         med, lo, hi = wall(lambda: dm.lesion_table(batch=B, threshold=0.5, filter_size=5, mask=mask))
         say('  lesion_table(mask=%s): %.3f ms per call (median of %d; %.3f .. %.3f)' % (mask, med, R, lo, hi))
+    dm.close()
+    if a.out:
+        with open(a.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    sys.exit(0)
+if a.matched_only:
+    dm.pixel_confusion_of(prob, y, [0.5])
+    flags = [b > 0 for b in range(B)]
+    for _ in range(4):
+        med, lo, hi = wall(lambda: dm.lesion_table_matched(y, continues=flags, batch=B, threshold=0.5, filter_size=5))
+        say('  lesion_table_matched(mask=False): %.3f ms per call (median of %d; %.3f .. %.3f)' % (med, R, lo, hi))
+    dm.close()
+    if a.out:
+        with open(a.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    sys.exit(0)
+if a.detection:
+    dm.forward(x, return_prob=False)
+    net = dm.last_prob(B)
+    planes = (('network output as it is', net), ('drawn discs', prob),
+              ('network output above its 99th percentile', np.where(net >= np.percentile(net, 99.0), net, 0).astype(np.float32)))
+    for what, plane in planes:
+        def put_back():
+            dm.pixel_confusion_of(plane, y, [0.5])                # the plane into the model's buffer (synchronises)
+
+        def timed(fn):
+            ts = []
+            for _ in range(R + 1):                                # the first one warms up
+                put_back()
+                t0 = time.perf_counter()
+                fn()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            ts = sorted(ts[1:])
+            return ts[len(ts) // 2], ts[0], ts[-1]
+        put_back()
+        rows, recs = dm.detection_map(B)
+        say('  %s: %d candidates, %d rounds, %d dropped, %d slices exhausted, largest %d pixels' % (
+            what, len(rows), int(recs['rounds'].sum()), int(recs['dropped'].sum()), int(recs['exhausted'].sum()),
+            int(rows['area'].max()) if len(rows) else 0))
+        for name, fn in (('detection_map', lambda: dm.detection_map(B)),
+                         ('lesion_table', lambda: dm.lesion_table(batch=B, threshold=0.5, filter_size=5, mask=False))) * 2:
+            med, lo, hi = timed(fn)
+            say('  %-28s %.3f ms per call (median of %d; %.3f .. %.3f)' % (name, med, R, lo, hi))
+        per_launch(dm, lambda: (put_back(), dm.detection_map(B)), ('det_',))
+    ys = np.concatenate([y] * NB)
+    table = dict(threshold=0.1, filter_size=1, resize_factor=1.0, min_area=0)
+
+    def eval_pass(detect):
+        """a forward and the calls of engine._detection_pass per batch; without `detect` the matched call alone"""
+        t0 = time.perf_counter()
+        for i, (xb, _, _) in enumerate(ds):
+            dm.forward(xb, return_prob=False)
+            if detect:
+                dm.detection_map(len(xb))
+            dm.lesion_table_matched(ys[i * B:i * B + len(xb)], batch=len(xb), continues=[i > 0 or b > 0 for b in range(len(xb))], **table)
+        return time.perf_counter() - t0
+    eval_pass(False), eval_pass(True)                             # warm-up: the carries, either workspace
+    took = {False: [], True: []}
+    for i in range(8):
+        took[bool(i % 2)].append(eval_pass(bool(i % 2)))
+        say('  %-44s %9.1f slices/s  (%.2f ms per batch)' % ('forward + ' + ('detection_map + ' if i % 2 else '') + 'matched pass',
+                                                             B * NB / took[bool(i % 2)][-1], took[bool(i % 2)][-1] / NB * 1e3))
+    say('  detection / plain matched pass (medians of 4, alternated): %.3f' % (sorted(took[True])[2] / sorted(took[False])[2]))
     dm.close()
     if a.out:
         with open(a.out, 'a') as f:
