@@ -128,6 +128,16 @@ def build_parser(prog='python3 -m annotator'):
     _detection_arguments(e)
     e.add_argument('--detection_iou', type=float, default=argparse.SUPPRESS,
                    help='voxel IoU at which a candidate of --detection hits a tumour (default: 0.10)')
+    e.add_argument('--bootstrap', type=int, default=argparse.SUPPRESS, metavar='R',
+                   help='with --detection / --exam_lesions: resample the exams R times (100..1048576) on the GPU and also write '
+                        'detection_bootstrap.csv, detection_bootstrap_replicates.csv and exam_lesion_bootstrap.csv: every figure with '
+                        'the mean, deviation and interval of its replicates')
+    e.add_argument('--bootstrap_seed', type=int, default=argparse.SUPPRESS,
+                   help='seed of --bootstrap, 0..2^64-1; the same seed over the same data set resamples identically (default: 0)')
+    e.add_argument('--bootstrap_level', type=float, default=argparse.SUPPRESS,
+                   help='coverage of the intervals of --bootstrap, strictly between 0.5 and 1 (default: 0.95)')
+    e.add_argument('--bootstrap_stratified', action='store_true', default=argparse.SUPPRESS,
+                   help='--bootstrap with --detection: draw the exams with and without a labelled tumour separately')
     p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
     p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
     p.add_argument('--data_path', nargs='+', required=True)

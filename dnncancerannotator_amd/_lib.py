@@ -169,6 +169,30 @@ DETECTION_ROW_DTYPE = np.dtype([('slice', '<i4'), ('number', '<i4'), ('seed', '<
 DETECTION_SLICE_DTYPE = np.dtype([('candidates', '<i4'), ('rounds', '<i4'), ('dropped', '<i4'), ('exhausted', '<i4')])
 
 
+class BootstrapExam(C.Structure):                  # dnnca_bootstrap_exam (8 bytes)
+    _fields_ = [('tumours', C.c_int32), ('score_rank', C.c_int32)]
+
+
+class BootstrapCandidate(C.Structure):             # dnnca_bootstrap_candidate (12 bytes)
+    _fields_ = [('exam', C.c_int32), ('hit', C.c_int32), ('level', C.c_int32)]
+
+
+class BootstrapDetectionRow(C.Structure):          # dnnca_bootstrap_detection_row (120 bytes)
+    _fields_ = [('positive_exams', C.c_int64), ('tumours', C.c_int64), ('candidates', C.c_int64), ('tp', C.c_int64), ('fp', C.c_int64),
+                ('auroc_pairs', C.c_int64), ('auroc_twice', C.c_int64), ('tp_at', C.c_int64 * 7), ('ap', C.c_double)]
+
+
+# DeviceModel.bootstrap_detection takes and returns structured arrays of these dtypes
+BOOTSTRAP_EXAM_DTYPE = np.dtype([('tumours', '<i4'), ('score_rank', '<i4')])
+BOOTSTRAP_CANDIDATE_DTYPE = np.dtype([('exam', '<i4'), ('hit', '<i4'), ('level', '<i4')])
+BOOTSTRAP_DETECTION_ROW_DTYPE = np.dtype([('positive_exams', '<i8'), ('tumours', '<i8'), ('candidates', '<i8'), ('tp', '<i8'),
+                                          ('fp', '<i8'), ('auroc_pairs', '<i8'), ('auroc_twice', '<i8'), ('tp_at', '<i8', (7,)),
+                                          ('ap', '<f8')])
+BOOTSTRAP_TILE = 1024                              # DNNCA_BOOTSTRAP_TILE: candidates per step of the detection kernel
+BOOTSTRAP_MAX_EXAMS, BOOTSTRAP_MAX_CANDIDATES, BOOTSTRAP_MAX_REPLICATES = 16384, 1 << 22, 1 << 20
+BOOTSTRAP_MAX_COLUMNS, BOOTSTRAP_MAX_STRATA = 64, 8
+
+
 # DeviceModel.lesion_table_spread / spread_by_outcome return structured arrays of these dtypes
 LESION_SPREAD_DTYPE = np.dtype([('slice', '<i4'), ('row', '<i4'), ('area', '<i4'), ('max_spread', '<f4'), ('sum_spread_q24', '<u8')])
 SLICE_SPREAD_DTYPE = np.dtype([('pixels', '<i4'), ('max_spread', '<f4'), ('sum_spread_q24', '<u8')])
@@ -297,6 +321,11 @@ SIGNATURES = {
     'dnnca_prob_temperature': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, _FP]),
     'dnnca_detection_map': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.POINTER(DetectionCfg), _FP, C.POINTER(DetectionRow),
                                       C.POINTER(C.c_int64), C.POINTER(DetectionSlice)]),
+    'dnnca_bootstrap_sums': (C.c_int, [_VP, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
+                                       C.c_int, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_uint16)]),
+    'dnnca_bootstrap_detection': (C.c_int, [_VP, C.POINTER(BootstrapExam), C.c_int, C.POINTER(BootstrapCandidate), C.c_int,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_uint64,
+                                            C.POINTER(BootstrapDetectionRow), C.POINTER(C.c_uint16)]),
     'dnnca_lesion_table_linked': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                             C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
                                             C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(LesionLink), C.c_int64,

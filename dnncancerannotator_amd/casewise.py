@@ -417,13 +417,18 @@ def exam_match_summary(cases):
     """the EXAM_CASE_COLUMNS values of every exam -> the EXAM_RESULT_COLUMNS values: the summed counts, recall = detected / true and
     precision = matched / predicted as region_metrics writes region/recall and region/precision (float32 count / (float32 sum +
     epsilon)), F1 = 2 P R / (P + R + epsilon) likewise, false_per_exam = false / exams (0.0 without exams)"""
-    f32 = np.float32
     n = [sum(int(c[i]) for c in cases) for i in range(1, 7)]        # true, predicted, detected, missed, matched, false
-    recall = f32(n[2]) / (f32(n[2] + n[3]) + f32(EXAM_EPSILON))
-    precision = f32(n[4]) / (f32(n[4] + n[5]) + f32(EXAM_EPSILON))
-    f1 = f32(2) * precision * recall / (precision + recall + f32(EXAM_EPSILON))
-    return [len(cases)] + n + [repr(float(recall)), repr(float(precision)), repr(float(f1)),
-                               repr(n[5] / len(cases) if cases else 0.0)]
+    return [len(cases)] + n + [repr(v) for v in _exam_match_ratios(n, len(cases), EXAM_EPSILON)]
+
+
+def _exam_match_ratios(n, exams, epsilon):
+    """the summed counts (true, predicted, detected, missed, matched, false) of `exams` exams -> [recall, precision, f1,
+    false_per_exam] as Python floats: the float32 arithmetic of exam_match_summary, shared with exam_match_replicate_values"""
+    f32 = np.float32
+    recall = f32(n[2]) / (f32(n[2] + n[3]) + f32(epsilon))
+    precision = f32(n[4]) / (f32(n[4] + n[5]) + f32(epsilon))
+    f1 = f32(2) * precision * recall / (precision + recall + f32(epsilon))
+    return [float(recall), float(precision), float(f1), n[5] / exams if exams else 0.0]
 
 
 # ---- `annotator evaluate --detection`: ranked lesion candidates, AP, FROC and AUROC -----------------------------------------------
@@ -551,6 +556,105 @@ def detection_image(D):
 def detection_path(root, tag):
     """<root>/<last 3 components of the exam path>/<sliceID %02d>/detection.png"""
     return os.path.join(export_dir(root, '', tag), 'detection.png')
+
+
+# ---- `annotator evaluate --bootstrap`: intervals of the detection and exam-lesion figures from a bootstrap over exams -------------
+# DeviceModel.bootstrap_detection / bootstrap_sums resample the exams (include/dnnca.h states the draws) and return, per replicate,
+# the integers from which the functions here form the same values as detection_summary / exam_match_summary, by the same arithmetic.
+BOOTSTRAP_RANGE = (100, 1 << 20)         # --bootstrap
+BOOTSTRAP_LEVEL = 0.95                   # --bootstrap_level, strictly between 0.5 and 1
+BOOTSTRAP_COLUMNS = ['metric', 'estimate', 'mean', 'std', 'lo', 'hi', 'level', 'replicates', 'undefined', 'seed', 'stratified']
+DETECTION_BOOTSTRAP_METRICS = ['ap', 'auroc', 'score'] + ['sensitivity_at_%g' % x for x in DETECTION_FP_RATES] + ['cpm']
+DETECTION_REPLICATE_INTEGERS = (['positive_exams', 'tumours', 'candidates', 'tp', 'fp', 'auroc_pairs', 'auroc_twice'] +
+                                ['tp_at_%g' % x for x in DETECTION_FP_RATES])
+DETECTION_REPLICATE_COLUMNS = ['replicate'] + DETECTION_REPLICATE_INTEGERS + DETECTION_BOOTSTRAP_METRICS
+EXAM_BOOTSTRAP_METRICS = ['recall', 'precision', 'f1', 'false_per_exam']
+
+
+def bootstrap_pool(positive_flags, stratified):
+    """(pool int32 [E], strata int32 [S]) of the exams 0 .. E-1 for DeviceModel.bootstrap_*: plain, the identity and one stratum;
+    stratified, the exams whose flag is set first, then the others, each in their order, an empty stratum left out"""
+    flags = [bool(f) for f in positive_flags]
+    if not stratified:
+        return np.arange(len(flags), dtype=np.int32), np.array([len(flags)], np.int32)
+    groups = [[e for e, f in enumerate(flags) if f], [e for e, f in enumerate(flags) if not f]]
+    return np.array(groups[0] + groups[1], np.int32), np.array([len(g) for g in groups if g], np.int32)
+
+
+def detection_bootstrap_inputs(cases):
+    """all exams' detection_match cases (what detection_summary reads) -> (exams, candidates) for DeviceModel.bootstrap_detection:
+    exams [E] (tumours, score_rank: the dense rank of the exam's score -- its largest confidence, 0.0 without a candidate -- among
+    all exams, 0 the lowest); candidates [N] (exam, hit, level) sorted by descending confidence, ties by (exam, number), level the
+    index of the distinct confidence, 0 the highest"""
+    from . import _lib
+    scores = [max((float(s) for s in c['confidences']), default=0.0) for c in cases]
+    rank = {s: i for i, s in enumerate(sorted(set(scores)))}
+    exams = np.zeros(len(cases), _lib.BOOTSTRAP_EXAM_DTYPE)
+    exams['tumours'] = [int(c['tumours']) for c in cases]
+    exams['score_rank'] = [rank[s] for s in scores]
+    ranked = sorted((-float(s), e, k, int(h)) for e, c in enumerate(cases) for k, (s, h) in enumerate(zip(c['confidences'], c['hits'])))
+    cands = np.zeros(len(ranked), _lib.BOOTSTRAP_CANDIDATE_DTYPE)
+    level = -1
+    for i, (s, e, _, h) in enumerate(ranked):
+        level += int(i == 0 or s != ranked[i - 1][0])
+        cands[i] = (e, h, level)
+    return exams, cands
+
+
+def detection_replicate_values(row, exams):
+    """one row of DeviceModel.bootstrap_detection over `exams` exams -> the DETECTION_BOOTSTRAP_METRICS values of the resample: ap,
+    auroc, score, the seven sensitivities, cpm; None where detection_curves / detection_auroc give None (no tumour drawn; one class
+    of exams not drawn), by their float64 arithmetic on the row's integers"""
+    tumours, pairs = int(row['tumours']), int(row['auroc_pairs'])
+    ap = float(row['ap']) if tumours else None
+    sens = [int(t) / tumours for t in row['tp_at']] if tumours else [None] * len(DETECTION_FP_RATES)
+    cpm = math.fsum(sens) / len(sens) if tumours else None
+    auroc = int(row['auroc_twice']) / (2 * pairs) if pairs else None
+    score = None if ap is None or auroc is None else (ap + auroc) / 2
+    return [ap, auroc, score] + sens + [cpm]
+
+
+def exam_match_replicate_values(sums, exams):
+    """one row of DeviceModel.bootstrap_sums over the EXAM_CASE_COLUMNS counts (true, predicted, detected, missed, matched, false)
+    of `exams` exams -> the EXAM_BOOTSTRAP_METRICS values of the resample, by exam_match_summary's float32 arithmetic"""
+    return _exam_match_ratios([int(v) for v in sums], int(exams), EXAM_EPSILON)
+
+
+def bootstrap_interval(values, level=BOOTSTRAP_LEVEL):
+    """the replicate values of one metric (None: undefined in that replicate) -> dict(mean, std, lo, hi, n, undefined): over the n
+    defined values v sorted ascending, lo and hi the quantiles at (1 - level) / 2 and 1 - (1 - level) / 2, a quantile at q being
+    v[i] + (h - i) (v[i + 1] - v[i]) with h = q (n - 1) and i = floor(h); mean = fsum / n; std the population standard deviation.
+    With n = 0 the four values are None (blank cells)"""
+    v = sorted(float(x) for x in values if x is not None)
+    n, out = len(v), dict(mean=None, std=None, lo=None, hi=None, n=len(v), undefined=len(values) - len(v))
+    if not n:
+        return out
+
+    def quantile(q):
+        h = q * (n - 1)
+        i = min(int(math.floor(h)), n - 1)
+        return v[i] + (h - i) * (v[min(i + 1, n - 1)] - v[i])
+    mean = math.fsum(v) / n
+    out.update(mean=mean, std=math.sqrt(math.fsum((x - mean) ** 2 for x in v) / n), lo=quantile((1 - level) / 2),
+               hi=quantile(1 - (1 - level) / 2))
+    return out
+
+
+def bootstrap_lines(metrics, estimates, replicate_values, cfg):
+    """the BOOTSTRAP_COLUMNS lines of one summary: per metric its estimate (the cell of the results file, as written there) and the
+    interval of its column of replicate_values [R][len(metrics)].  cfg: what engine.check_bootstrap returned"""
+    lines = []
+    for k, (name, estimate) in enumerate(zip(metrics, estimates)):
+        b = bootstrap_interval([r[k] for r in replicate_values], cfg['level'])
+        lines.append([name, estimate, _blank(b['mean']), _blank(b['std']), _blank(b['lo']), _blank(b['hi']), repr(cfg['level']),
+                      len(replicate_values), b['undefined'], cfg['seed'], int(cfg['stratified'])])
+    return lines
+
+
+def detection_replicate_line(replicate, row, values):
+    """the DETECTION_REPLICATE_COLUMNS line of one replicate: its number, the row's integers and detection_replicate_values"""
+    return ([int(replicate)] + [int(row[k]) for k in DETECTION_REPLICATE_INTEGERS[:7]] + [int(t) for t in row['tp_at']] +
+            [_blank(v) for v in values])
 
 
 # ---- `annotator evaluate --surface_distances`: how far the predicted outline lies from the labelled one ----------------------------

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "bootstrap.h"
 #include "boundary.h"
 #include "calib.h"
 #include "detect.h"
@@ -702,6 +703,28 @@ int dnnca_detection_map(void* model, const float* prob_hw, int batch, int h, int
     Planes dev;      // a host plane's map goes into a buffer behind it, the model's own is replaced in place
     DN_TRY(plane_stage(M, kScratchTtaIo, pl.n, {prob_hw, nullptr, nullptr, nullptr}, true, &dev));
     DN_TRY(detection_map(M, dev.prob, dev.out, batch, pl.h, pl.w, *cfg, out_hw, rows, n_rows, slices));
+    return M->flush_profile();
+}
+
+// ---- the bootstrap over exams (kernels_bootstrap.hip) ----------------------------------------------------------------------------
+int dnnca_bootstrap_sums(void* model, const int32_t* cols, int E, int K, const int32_t* pool, const int32_t* strata, int S, int R,
+                         uint64_t seed, int64_t* out, uint16_t* mult_out) {
+    MODEL(model);
+    if (!cols || !out) { set_error("bootstrap sums: null cols / out"); return DNNCA_EINVAL; }
+    if (K < 1 || K > kBootMaxColumns) { set_error("bootstrap sums: %d columns outside 1..%d", K, kBootMaxColumns); return DNNCA_EINVAL; }
+    DN_TRY(bootstrap_check_resampling(E, pool, strata, S, R));
+    DN_TRY(bootstrap_sums(M, cols, E, K, pool, strata, S, R, seed, out, mult_out));
+    return M->flush_profile();
+}
+
+int dnnca_bootstrap_detection(void* model, const dnnca_bootstrap_exam* exams, int E, const dnnca_bootstrap_candidate* cands, int N,
+                              const int32_t* pool, const int32_t* strata, int S, int R, uint64_t seed,
+                              dnnca_bootstrap_detection_row* out, uint16_t* mult_out) {
+    MODEL(model);
+    if (!out) { set_error("bootstrap detection: null out"); return DNNCA_EINVAL; }
+    DN_TRY(bootstrap_check_resampling(E, pool, strata, S, R));
+    DN_TRY(bootstrap_check_detection(exams, E, cands, N));
+    DN_TRY(bootstrap_detection(M, exams, E, cands, N, pool, strata, S, R, seed, out, mult_out));
     return M->flush_profile();
 }
 

@@ -13,6 +13,7 @@
 #include <string.h>
 #include "fast.h"
 #include "kernels.h"
+#include "philox_dev.h"
 
 namespace dnnca {
 
@@ -508,24 +509,6 @@ struct IntensityArgs {
     int B, H, W, C;
 };
 
-// Philox4x32-10 (Salmon et al., SC'11) on the counter (c0, 0, 0, 0): the first two of its four output words
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned k0, unsigned k1, unsigned& r0, unsigned& r1) {
-    unsigned c1 = 0u, c2 = 0u, c3 = 0u;
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned)p1;
-        c3 = (unsigned)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    r0 = c0;
-    r1 = c1;
-}
-
 // coordinate i of a size-n axis on [-1, 1] (0 where the axis has one point)
 __device__ __forceinline__ float intensity_coord(int i, int n) {
 #pragma clang fp contract(off)
@@ -560,8 +543,9 @@ __device__ __forceinline__ float intensity_point(float v, unsigned flags, const 
 __device__ __forceinline__ float intensity_finish(float v, unsigned flags, const unsigned* __restrict__ r, unsigned index) {
 #pragma clang fp contract(off)
     if (flags & INTENSITY_NOISE) {
-        unsigned r0, r1;
-        philox4x32_10(index, r[22], r[23], r0, r1);
+        unsigned word[4];                                             // the first two of the four words are used
+        philox4x32_10(index, 0u, 0u, 0u, r[22], r[23], word);
+        const unsigned r0 = word[0], r1 = word[1];
         const float u1 = (float)((r0 >> 9) + 1u) * 0x1p-23f;          // (0, 1], exact
         const float a2 = (float)(r1 >> 8) * 0x1p-23f;                  // 2 u2 in [0, 2), exact
         const float sigma = __uint_as_float(r[21]);

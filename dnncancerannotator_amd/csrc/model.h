@@ -401,6 +401,9 @@ struct Model {
     void* detect_ws = nullptr;
     size_t detect_ws_bytes = 0;
     dnnca_detection_cfg detect_last = {0.1f, 0.4f, 5, 10, 16};
+    // the bootstrap (dnnca_bootstrap_sums / _detection, kernels_bootstrap.hip): inputs and a chunk of outputs, grown on demand
+    void* boot_ws = nullptr;
+    size_t boot_ws_bytes = 0;
 
     ~Model();
     int build();

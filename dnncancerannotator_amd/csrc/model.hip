@@ -103,6 +103,7 @@ Model::~Model() {
     if (tta_io) (void)hipFree(tta_io);
     if (calib_ws) (void)hipFree(calib_ws);
     if (detect_ws) (void)hipFree(detect_ws);
+    if (boot_ws) (void)hipFree(boot_ws);
     for (auto& r : recs) {
         (void)hipEventDestroy(r.a);
         (void)hipEventDestroy(r.b);

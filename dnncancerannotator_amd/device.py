@@ -914,6 +914,65 @@ class DeviceModel:
         """the same of a host plane `prob` [B, h, w] of any size: (D, rows, slices); the model's buffer stays untouched."""
         return self._detection(_slices(prob, 'prob'), None, **cfg)
 
+    # ---- `evaluate --bootstrap` (kernels_bootstrap.hip) ---------------------------------------------------------
+    @staticmethod
+    def _bootstrap_resampling(E, strata):
+        """(pool, sizes) int32 from `strata`: None (plain: the identity, one stratum) or what casewise.bootstrap_pool returned"""
+        if strata is None:
+            return np.arange(E, dtype=np.int32), np.array([E], np.int32)
+        pool, sizes = strata
+        return np.ascontiguousarray(pool, np.int32).reshape(-1), np.ascontiguousarray(sizes, np.int32).reshape(-1)
+
+    def bootstrap_sums(self, cols, replicates, seed=0, strata=None, multiplicities=False):
+        """R = `replicates` bootstrap resamples of the E rows of cols [E, K] (integers that fit int32, K <= 64), drawn with
+        replacement by the definition of include/dnnca.h (Philox4x32-10 keyed by `seed`; within the strata of `strata` = (pool,
+        sizes), casewise.bootstrap_pool, when given): a structured array [R] with 'sums' int64 [K], sums[r][k] = sum_e m_r[e]
+        cols[e][k], exact, and with `multiplicities` also 'multiplicities' uint16 [E], the m_r themselves.  The draws depend on
+        (seed, E, strata) alone.  Bit-identical from run to run; touches nothing of the model"""
+        cols = np.ascontiguousarray(cols, np.int32)
+        if cols.ndim != 2:
+            raise ValueError('bootstrap_sums: cols must be [E, K], got shape %s' % (cols.shape,))
+        E, K = cols.shape
+        R = int(replicates)
+        pool, sizes = self._bootstrap_resampling(E, strata)
+        out = np.zeros(max(R, 0), [('sums', '<i8', (K,))] + ([('multiplicities', '<u2', (E,))] if multiplicities else []))
+        sums = np.zeros((max(R, 0), K), np.int64)
+        mult = np.zeros((max(R, 0), E), np.uint16) if multiplicities else None
+        i32 = C.POINTER(C.c_int32)
+        check(self.lib.dnnca_bootstrap_sums(self.handle, cols.ctypes.data_as(i32), E, K, pool.ctypes.data_as(i32), sizes.ctypes.data_as(i32),
+                                            sizes.size, R, int(seed), sums.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            mult.ctypes.data_as(C.POINTER(C.c_uint16)) if multiplicities else None))
+        out['sums'] = sums
+        if multiplicities:
+            out['multiplicities'] = mult
+        return out
+
+    def bootstrap_detection(self, exams, candidates, replicates, seed=0, strata=None, multiplicities=False):
+        """R = `replicates` bootstrap resamples of the exams of a detection pass: exams (_lib.BOOTSTRAP_EXAM_DTYPE) [E] and
+        candidates (_lib.BOOTSTRAP_CANDIDATE_DTYPE) [N] as casewise.detection_bootstrap_inputs makes them; seed, strata and
+        multiplicities as in bootstrap_sums.  Returns a structured array [R] (_lib.BOOTSTRAP_DETECTION_ROW_DTYPE: positive_exams,
+        tumours, candidates, tp, fp, auroc_pairs, auroc_twice, tp_at [7], ap), with `multiplicities` plus 'multiplicities' uint16 [E].
+        casewise.detection_replicate_values turns a row into AP, AUROC, the sensitivities and CPM.  Bit-identical from run to run"""
+        exams = np.ascontiguousarray(exams, _lib.BOOTSTRAP_EXAM_DTYPE).reshape(-1)
+        cands = np.ascontiguousarray(candidates, _lib.BOOTSTRAP_CANDIDATE_DTYPE).reshape(-1)
+        E, R = exams.size, int(replicates)
+        pool, sizes = self._bootstrap_resampling(E, strata)
+        rows = np.zeros(max(R, 0), _lib.BOOTSTRAP_DETECTION_ROW_DTYPE)
+        mult = np.zeros((max(R, 0), E), np.uint16) if multiplicities else None
+        i32 = C.POINTER(C.c_int32)
+        check(self.lib.dnnca_bootstrap_detection(self.handle, exams.ctypes.data_as(C.POINTER(_lib.BootstrapExam)), E,
+                                                 cands.ctypes.data_as(C.POINTER(_lib.BootstrapCandidate)), cands.size,
+                                                 pool.ctypes.data_as(i32), sizes.ctypes.data_as(i32), sizes.size, R, int(seed),
+                                                 rows.ctypes.data_as(C.POINTER(_lib.BootstrapDetectionRow)),
+                                                 mult.ctypes.data_as(C.POINTER(C.c_uint16)) if multiplicities else None))
+        if not multiplicities:
+            return rows
+        out = np.zeros(rows.size, _lib.BOOTSTRAP_DETECTION_ROW_DTYPE.descr + [('multiplicities', '<u2', (E,))])
+        for name in rows.dtype.names:
+            out[name] = rows[name]
+        out['multiplicities'] = mult
+        return out
+
     def lesion_table_linked(self, batch=None, prob=None, continues=None, threshold=0.5, resize_factor=1.0, filter_size=5, min_area=0,
                             max_lesions=256, mask=True):
         """lesion_table plus the links between neighbouring slices: (rows, totals, masks, links); the first three are what

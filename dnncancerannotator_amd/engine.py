@@ -150,6 +150,33 @@ EMA_KEYS = ('decay', 'warmup', 'validate')
 WEIGHT_CHOICES = ('raw', 'ema')
 
 
+def check_bootstrap(bootstrap=None, seed=None, level=None, stratified=False, detection=False, exam_lesions=False):
+    """the values of --bootstrap R and the --bootstrap_* flags (None / False: not given) -> None without `bootstrap` (a
+    --bootstrap_* flag is then a ValueError: it means nothing without it), else dict(replicates, seed, level, stratified) with the
+    defaults filled in.  ValueError: R no integer in casewise.BOOTSTRAP_RANGE, neither --detection nor --exam_lesions (there is
+    nothing to resample), a seed outside 0 .. 2^64 - 1, a level not strictly between 0.5 and 1, --bootstrap_stratified without
+    --detection (the exam-lesion pass has no positive-exam flag to split on)."""
+    if bootstrap is None:
+        if seed is not None or level is not None or stratified:
+            raise ValueError('the --bootstrap_* options set the resampling of --bootstrap: add --bootstrap R')
+        return None
+    lo, hi = casewise.BOOTSTRAP_RANGE
+    if isinstance(bootstrap, bool) or not isinstance(bootstrap, (int, np.integer)) or not lo <= bootstrap <= hi:
+        raise ValueError('--bootstrap must be an integer in [%d, %d], got %r' % (lo, hi, bootstrap))
+    if not (detection or exam_lesions):
+        raise ValueError('--bootstrap resamples the exams of --detection / --exam_lesions: add one of them')
+    seed = 0 if seed is None else seed
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64:
+        raise ValueError('--bootstrap_seed must be an integer in [0, 2^64 - 1], got %r' % (seed,))
+    level = casewise.BOOTSTRAP_LEVEL if level is None else level
+    if isinstance(level, bool) or not isinstance(level, (int, float, np.floating)) or not 0.5 < level < 1.0:
+        raise ValueError('--bootstrap_level must lie strictly between 0.5 and 1, got %r' % (level,))
+    if stratified and not detection:
+        raise ValueError('--bootstrap_stratified splits the exams of --detection by their labelled tumours; --exam_lesions has no '
+                         'such flag to split on: add --detection or drop it')
+    return dict(replicates=int(bootstrap), seed=int(seed), level=float(level), stratified=bool(stratified))
+
+
 def check_ema(options):
     """deploy_options.ema -> dict(decay, warmup, validate), or None without the key.  decay: finite, in (0, 1); warmup: the
     num_updates warm-up of tf.train.ExponentialMovingAverage (default on); validate: 'ema' (default: validation inside train() and
@@ -941,7 +968,7 @@ class TFKerasModel:
              visualize_attribution=False, attribution_steps=None, attribution_baseline=None, weights='raw', detection_ds=None,
              detection=False, detection_min_confidence=None, detection_factor=None, detection_max_candidates=None,
              detection_min_area=None, detection_rounds=None, detection_iou=None, detection_link_min_overlap=None,
-             detection_max_lesions=None):
+             detection_max_lesions=None, bootstrap=None, bootstrap_seed=None, bootstrap_level=None, bootstrap_stratified=False):
         """weights (`evaluate --weights ema`): every checkpoint is loaded with its averaged weights as the parameters (load(...,
         weights='ema')); everything downstream reads that model unchanged.  Checkpoints without an average are an error that names
         the first, raised before anything is evaluated.
@@ -977,8 +1004,14 @@ class TFKerasModel:
         (the same kind of data set as exam_ds; the flags may share one) and writes detection_results.csv, detection_froc.csv,
         detection_cases.csv and detection_candidates.csv under <export_path>/<tag>/: ranked lesion candidates of the detection map
         (DeviceModel.detection_map with the detection_* values, check_detection), lesion-level AP and FROC, exam-level AUROC.  Under
-        tta / temperature / weights the map is that of the probabilities they give.  Every other file is what it is without it."""
+        tta / temperature / weights the map is that of the probabilities they give.  Every other file is what it is without it.
+        bootstrap (`evaluate --bootstrap R`, check_bootstrap): the detection and the exam-lesion pass also resample their exams R
+        times on the device (DeviceModel.bootstrap_detection / bootstrap_sums, once per checkpoint and threshold) and write
+        detection_bootstrap.csv, detection_bootstrap_replicates.csv and exam_lesion_bootstrap.csv under <export_path>/<tag>/: per
+        metric the estimate, and mean, deviation and the bootstrap_level interval of its replicates.  bootstrap_stratified draws
+        within the exams with and without a labelled tumour (detection only).  Every other file is what it is without it."""
         check_uncertainty(uncertainty, tta)
+        bootstrap = check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level, bootstrap_stratified, detection, exam_lesions)
         detection = check_detection(detection, detection_min_confidence, detection_factor, detection_max_candidates, detection_min_area,
                                     detection_rounds, detection_iou, detection_link_min_overlap, detection_max_lesions)
         attribution = check_attribution(visualize_attribution, attribution_steps, attribution_baseline, export_csv, export_images)
@@ -1024,6 +1057,8 @@ class TFKerasModel:
         writer = casewise.Writer() if visualize else None
         exam_pass = bool(exam_lesions) and exam_ds is not None and self.ctx.rank == 0
         exam_tables = [], [], []         # the lines of the three exam_lesion_*.csv files
+        if bootstrap:                    # and those of exam_lesion_bootstrap.csv
+            exam_tables += ([],)
         surface_pass = bool(surface_distances) and surface_ds is not None and self.ctx.rank == 0
         surface_tables = [], [], []      # the lines of surface_results.csv, surface_cases.csv and surface_slices.csv
         uncertainty_pass = bool(uncertainty) and uncertainty_ds is not None and self.ctx.rank == 0
@@ -1033,6 +1068,11 @@ class TFKerasModel:
         attribution_table, attribution_names = [], []      # the lines of attribution_results.csv; the modalities of its share columns
         detection_pass = detection is not None and detection_ds is not None and self.ctx.rank == 0
         detection_tables = [], [], [], []    # the lines of detection_results.csv, _froc.csv, _cases.csv and _candidates.csv
+        if bootstrap:                        # and those of detection_bootstrap.csv and detection_bootstrap_replicates.csv
+            detection_tables += ([], [])
+        # the exam-lesion pass has no strata; the keyword goes to the passes only with the flag
+        exam_more = dict(bootstrap=dict(bootstrap, stratified=False)) if bootstrap else {}
+        detection_more = dict(bootstrap=bootstrap) if bootstrap else {}
         rows = OrderedDict()
         previous_step = None
         for ckpt_step, ckpt_path_ in self.get_ckpts(ckpt_path).items():
@@ -1053,7 +1093,7 @@ class TFKerasModel:
                 for t, new in zip(exam_tables, self._exam_lesion_pass(
                         exam_ds, ckpt_step, [float(t) for t in exam_threshold], exam_iou, exam_link_min_overlap,
                         dict(resize_factor=exam_resize_factor, filter_size=exam_filter_size, min_area=exam_min_area,
-                             max_lesions=exam_max_lesions), tta_mask=tta_mask, **more)):
+                             max_lesions=exam_max_lesions), tta_mask=tta_mask, **more, **exam_more)):
                     t += new
             if surface_pass:
                 for t, new in zip(surface_tables, self._surface_pass(
@@ -1071,13 +1111,16 @@ class TFKerasModel:
                                                                              calibration_grid, tta_mask, **more)):
                     t += new
             if detection_pass:
-                for t, new in zip(detection_tables, self._detection_pass(detection_ds, ckpt_step, detection, tta_mask=tta_mask, **more)):
+                for t, new in zip(detection_tables, self._detection_pass(detection_ds, ckpt_step, detection, tta_mask=tta_mask, **more,
+                                                                           **detection_more)):
                     t += new
         if detection_pass:
             os.makedirs(os.path.join(export_path, tag), exist_ok=True)
-            for name, cols, table in zip(('detection_results.csv', 'detection_froc.csv', 'detection_cases.csv', 'detection_candidates.csv'),
+            for name, cols, table in zip(('detection_results.csv', 'detection_froc.csv', 'detection_cases.csv', 'detection_candidates.csv',
+                                          'detection_bootstrap.csv', 'detection_bootstrap_replicates.csv'),
                                          (casewise.DETECTION_RESULT_COLUMNS, casewise.DETECTION_FROC_COLUMNS,
-                                          casewise.DETECTION_CASE_COLUMNS, casewise.DETECTION_CANDIDATE_COLUMNS), detection_tables):
+                                          casewise.DETECTION_CASE_COLUMNS, casewise.DETECTION_CANDIDATE_COLUMNS,
+                                          casewise.BOOTSTRAP_COLUMNS, casewise.DETECTION_REPLICATE_COLUMNS), detection_tables):
                 with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
                     f.write(casewise.plain_csv(['step'] + cols, table))
         if calibration_pass:
@@ -1102,9 +1145,10 @@ class TFKerasModel:
                     f.write(casewise.plain_csv(['step', 'threshold'] + cols, table))
         if exam_pass:
             os.makedirs(os.path.join(export_path, tag), exist_ok=True)
-            for name, cols, table in zip(('exam_lesion_results.csv', 'exam_lesion_cases.csv', 'exam_lesion_matches.csv'),
-                                         (casewise.EXAM_RESULT_COLUMNS, casewise.EXAM_CASE_COLUMNS, casewise.EXAM_MATCH_COLUMNS),
-                                         exam_tables):
+            for name, cols, table in zip(('exam_lesion_results.csv', 'exam_lesion_cases.csv', 'exam_lesion_matches.csv',
+                                          'exam_lesion_bootstrap.csv'),
+                                         (casewise.EXAM_RESULT_COLUMNS, casewise.EXAM_CASE_COLUMNS, casewise.EXAM_MATCH_COLUMNS,
+                                          casewise.BOOTSTRAP_COLUMNS), exam_tables):
                 with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
                     f.write(casewise.plain_csv(['step', 'threshold'] + cols, table))
         if attribution and visualize:
@@ -1203,7 +1247,7 @@ class TFKerasModel:
                 _forward_on_device(dm, xb, tta_mask, spread=spread, temperature=temperature)
                 yield dm, xb, yb, list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
 
-    def _exam_lesion_pass(self, ds, step, thresholds, iou, min_overlap, kw, tta_mask=None, temperature=None):
+    def _exam_lesion_pass(self, ds, step, thresholds, iou, min_overlap, kw, tta_mask=None, temperature=None, bootstrap=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --exam_lesions`: per max_batch split one forward whose
         probabilities stay on the device and one DeviceModel.lesion_table_matched per threshold; then per threshold and exam
         casewise.link_lesions on either plane and casewise.match_exam_lesions.  Returns the new lines of (exam_lesion_results.csv,
@@ -1211,7 +1255,9 @@ class TFKerasModel:
         A slice continues the one before it by annotate's rule: the same exam path and the next slice number, across splits and
         batches.  continues[0] of a matched call refers to the model's last matched call, which with several thresholds was
         another threshold's: the call is then led by a one-slice call that puts this threshold's rows of the slice before back
-        (its probabilities and labels are kept on the host for that; a single threshold needs neither)."""
+        (its probabilities and labels are kept on the host for that; a single threshold needs neither).
+        bootstrap (what check_bootstrap returned): per threshold one DeviceModel.bootstrap_sums over the exams' counts after the
+        summary, and a fourth table, the new lines of exam_lesion_bootstrap.csv."""
         several = len(thresholds) > 1
         found = [[] for _ in thresholds]     # per threshold and slice: (exam, slice, rows, total, links, true rows, total, links, pairs)
         before, last, tail, carry_of = None, None, None, None
@@ -1239,7 +1285,7 @@ class TFKerasModel:
                                       [(int(q['row_true']), int(q['row']), int(q['overlap'])) for q in pairs]))
             if several:
                 tail = dm.last_prob(len(xb))[-1:], yb[-1:].reshape(1, *yb.shape[1:3])
-        results, cases, matches = [], [], []
+        results, cases, matches, intervals = [], [], [], []
         for thr, mine in zip(thresholds, found):
             lead = [int(step), repr(thr)]
             exams = OrderedDict()            # exam path -> its slices, in the order of the data set
@@ -1256,15 +1302,23 @@ class TFKerasModel:
                 matches += [lead + l for l in lines]
             cases += [lead + c for c in mine_cases]
             results.append(lead + casewise.exam_match_summary(mine_cases))
-        return results, cases, matches
+            if bootstrap and mine_cases:
+                sums = self.device_model.bootstrap_sums(np.array([c[1:7] for c in mine_cases], np.int32), bootstrap['replicates'],
+                                                        seed=bootstrap['seed'])['sums']
+                values = [casewise.exam_match_replicate_values(s, len(mine_cases)) for s in sums]
+                intervals += [lead + l for l in casewise.bootstrap_lines(casewise.EXAM_BOOTSTRAP_METRICS, results[-1][-4:], values,
+                                                                         bootstrap)]
+        return (results, cases, matches, intervals) if bootstrap else (results, cases, matches)
 
-    def _detection_pass(self, ds, step, det, tta_mask=None, temperature=None):
+    def _detection_pass(self, ds, step, det, tta_mask=None, temperature=None, bootstrap=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --detection`: per max_batch split one forward whose
         probabilities stay on the device, DeviceModel.detection_map in place (the buffer then holds the map) and one
         DeviceModel.lesion_table_matched on it (casewise.detection_table_args: the rows are the candidates, max_prob their
         confidence); then per exam casewise.link_lesions on either plane and casewise.detection_match, and casewise.detection_summary
         over all exams.  det: what check_detection returned.  Returns the new lines of (detection_results.csv, detection_froc.csv,
-        detection_cases.csv, detection_candidates.csv), each led by step.  Slices continue each other by _exam_lesion_pass's rule."""
+        detection_cases.csv, detection_candidates.csv), each led by step.  Slices continue each other by _exam_lesion_pass's rule.
+        bootstrap (what check_bootstrap returned): one DeviceModel.bootstrap_detection over the same cases after the summary, and
+        two more tables, the new lines of detection_bootstrap.csv and detection_bootstrap_replicates.csv."""
         kw = casewise.detection_table_args(det['cfg'], det['max_lesions'])
         found, exhausted = [], 0             # per slice: (exam, slice, rows, total, links, true rows, total, links, pairs)
         before, last = None, None
@@ -1299,7 +1353,18 @@ class TFKerasModel:
             cases.append(case)
             candidates += [lead + l for l in lines]
         result, froc = casewise.detection_summary(cases, exhausted)
-        return [lead + result], [lead + l for l in froc], [lead + casewise.detection_case_values(c) for c in cases], candidates
+        tables = [lead + result], [lead + l for l in froc], [lead + casewise.detection_case_values(c) for c in cases], candidates
+        if not bootstrap:
+            return tables
+        intervals, replicates = [], []
+        if cases:
+            exams, ranked = casewise.detection_bootstrap_inputs(cases)
+            rows = self.device_model.bootstrap_detection(exams, ranked, bootstrap['replicates'], seed=bootstrap['seed'],
+                                                         strata=casewise.bootstrap_pool(exams['tumours'] > 0, bootstrap['stratified']))
+            values = [casewise.detection_replicate_values(r, len(cases)) for r in rows]
+            intervals = [lead + l for l in casewise.bootstrap_lines(casewise.DETECTION_BOOTSTRAP_METRICS, result[7:18], values, bootstrap)]
+            replicates = [lead + casewise.detection_replicate_line(i, r, v) for i, (r, v) in enumerate(zip(rows, values))]
+        return tables + (intervals, replicates)
 
     def _surface_pass(self, ds, step, thresholds, percentile, kw, tta_mask=None, temperature=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --surface_distances`: per max_batch split one forward whose

@@ -15,8 +15,10 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
              calibration=False, calibration_bins=15, calibration_temperatures=None, temperature=None, visualize_attribution=False,
              attribution_steps=None, attribution_baseline=None, weights='raw', detection=False, detection_min_confidence=None,
              detection_factor=None, detection_max_candidates=None, detection_min_area=None, detection_rounds=None, detection_iou=None,
-             detection_link_min_overlap=None, detection_max_lesions=None):
+             detection_link_min_overlap=None, detection_max_lesions=None, bootstrap=None, bootstrap_seed=None, bootstrap_level=None,
+             bootstrap_stratified=False):
     engine.check_uncertainty(uncertainty, tta)       # before anything is read
+    resampling = engine.check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level, bootstrap_stratified, detection, exam_lesions)
     detection_values = dict(detection_min_confidence=detection_min_confidence, detection_factor=detection_factor,
                             detection_max_candidates=detection_max_candidates, detection_min_area=detection_min_area,
                             detection_rounds=detection_rounds, detection_iou=detection_iou,
@@ -61,6 +63,9 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
         more['weights'] = 'ema'
     if detection:                        # and those of --detection only with the flag
         more.update(detection_ds=meta_ds, detection=True, **detection_values)
+    if resampling:                       # and those of --bootstrap
+        more.update(bootstrap=resampling['replicates'], bootstrap_seed=resampling['seed'], bootstrap_level=resampling['level'],
+                    bootstrap_stratified=resampling['stratified'])
     model = engine.TFKerasModel(config)
     return model.eval(ds, viz_ds=viz_ds, tag=tag, save_path=os.path.join(save_path), avoid_overwrite=avoid_overwrite,
                       export_path=export_path, export_images=export_images, export_csv=export_csv,

@@ -718,6 +718,47 @@ int dnnca_detection_map(void* model, const float* prob_hw, int batch, int h, int
                         float* out_hw, dnnca_detection_row* rows /* [batch * max_candidates] */, int64_t* n_rows,
                         dnnca_detection_slice* slices /* [batch] */);
 
+/* ---- bootstrap over exams: confidence intervals of the detection and exam-lesion figures (`evaluate --bootstrap`) ------------------
+ * The resampling, the same for both calls: the exams of a pass are numbered 0 .. E-1; pool [E] is a permutation of them ordered by
+ * stratum, strata [S] (1 <= S <= 8) the positive sizes n_s of the strata, summing to E, o_s their offsets into pool.  Replicate r in
+ * [0, R) makes E draws; draw j lies in the stratum s with o_s <= j < o_s + n_s and picks pool[o_s + ((uint64) x * n_s >> 32)], x
+ * being word j & 3 of Philox4x32-10 on the counter (j >> 2, r, 0, 0) under the key (seed & 0xffffffff, seed >> 32).  The
+ * multiply-shift maps the 2^32 values of x onto n_s exams with a bias below n_s / 2^32 (under 2^-18 at the largest E).  m_r[e] is the
+ * number of draws that picked exam e: it sums to E, and to n_s within stratum s.  The draws depend on (seed, E, strata) alone, not on
+ * what is resampled: two calls with the same three resample identically and can be differenced replicate by replicate.
+ * mult_out (NULL, or [R, E]) receives m_r.  One workgroup per replicate builds m_r in LDS; everything is integers but ap, whose terms
+ * are added in an order fixed by (N, the block size): both calls are bit-identical from run to run.
+ *
+ * dnnca_bootstrap_sums: out[r][k] = sum_e m_r[e] * cols[e][k], exact, for 1 <= K <= 64 columns of int32.
+ *
+ * dnnca_bootstrap_detection: exams[e] = (tumours >= 0, score_rank >= 0: the dense rank of the exam's score among all exams, 0 the
+ * lowest, equal scores equal ranks); cands [N] sorted by descending confidence, each (exam, hit 0 / 1, level: the index of its
+ * distinct confidence, 0 the highest, non-decreasing without gaps).  The device never sees a float.  With w_c = m_r[exam_c] and
+ * cumulative weighted counts TP_k, FP_k at the end of level k, out[r] holds
+ *     positive_exams = sum m [tumours > 0],  tumours T = sum m tumours,  candidates = sum w,  tp = sum w hit,  fp = sum w (1 - hit)
+ *     auroc_pairs = positive_exams * (E - positive_exams)
+ *     auroc_twice = sum over positive p, negative n of m_p m_n (2 [rank_p > rank_n] + [rank_p == rank_n])
+ *     tp_at[i]    = TP_k of the last level with FP_k * 8 <= (1 << i) * E   (false positives per exam 1/8 .. 8), 0 when none
+ *     ap          = sum_k (TP_k - TP_{k-1}) * TP_k / (T * (TP_k + FP_k)) in double; a level with TP_k + FP_k == 0 adds 0; 0.0 when
+ *                   T == 0 (told by tumours == 0) or nothing is drawn
+ * DNNCA_EINVAL, with nothing launched and the outputs untouched: E outside 1..16384, N outside 0..2^22, R outside 1..2^20, K outside
+ * 1..64, S outside 1..8, a size that is not positive or sizes that do not sum to E, a pool that is no permutation of 0..E-1, an exam
+ * index out of range, a hit that is not 0 / 1, a level that decreases or skips (the first is 0), negative tumours or rank, a NULL
+ * cols / exams / cands (with N > 0) / pool / strata / out.  The model gives its stream and a scratch of the calls' own: no variable,
+ * state, probability buffer or carried lesion rows are touched.  Synchronises. */
+#define DNNCA_BOOTSTRAP_TILE 1024                    /* candidates a workgroup of dnnca_bootstrap_detection takes per step */
+typedef struct dnnca_bootstrap_exam { int32_t tumours, score_rank; } dnnca_bootstrap_exam;                      /* 8 bytes */
+typedef struct dnnca_bootstrap_candidate { int32_t exam, hit, level; } dnnca_bootstrap_candidate;               /* 12 bytes */
+typedef struct dnnca_bootstrap_detection_row {                                                                    /* 120 bytes */
+    int64_t positive_exams, tumours, candidates, tp, fp, auroc_pairs, auroc_twice, tp_at[7];
+    double ap;
+} dnnca_bootstrap_detection_row;
+int dnnca_bootstrap_sums(void* model, const int32_t* cols /* [E, K] */, int E, int K, const int32_t* pool, const int32_t* strata,
+                         int S, int R, uint64_t seed, int64_t* out /* [R, K] */, uint16_t* mult_out /* [R, E] or NULL */);
+int dnnca_bootstrap_detection(void* model, const dnnca_bootstrap_exam* exams /* [E] */, int E,
+                              const dnnca_bootstrap_candidate* cands /* [N] */, int N, const int32_t* pool, const int32_t* strata,
+                              int S, int R, uint64_t seed, dnnca_bootstrap_detection_row* out /* [R] */, uint16_t* mult_out);
+
 /* ---- the same table plus the links between neighbouring slices of an exam (`annotator predict --link_slices`) ------------------
  * Every argument up to out_hw means what it means for dnnca_lesion_table (the size query with rows == NULL included), and rows,
  * totals and mask are bit-identical to that call's.  continues [batch]: continues[b] != 0 says that slice b is the next slice of
