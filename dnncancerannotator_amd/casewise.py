@@ -22,6 +22,7 @@ import os
 import re
 import struct
 import zlib
+from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -337,6 +338,55 @@ def link_lesions(exam, slices, links, min_overlap=1):
                       int(any(int(slices[i][2]) > len(slices[i][1]) for i in touched))])
     parts = [[exam, int(slices[i][0]), int(r['row']), number[find(n)]] for n, (i, r) in enumerate(nodes)]
     return table, parts
+
+
+# one slice of a DeviceModel.lesion_table_matched call: rows / total / links of the predicted plane, the same of the labelled one and
+# the pairs between them.  A lesion_table_linked call has one plane: its records leave the last four fields None
+SliceRecord = namedtuple('SliceRecord', 'exam slice rows total links true_rows true_total true_links pairs', defaults=(None,) * 4)
+
+
+def triples(records, first='row_prev'):
+    """link records -> [(row_prev, row, overlap)] as link_lesions takes them; pair records with first='row_true'"""
+    return [(int(r[first]), int(r['row']), int(r['overlap'])) for r in records]
+
+
+def slice_records(out, pk):
+    """what lesion_table_matched returned (rows, totals, masks, links, true_rows, true_totals, true_links, pairs) -- or the four values
+    of lesion_table_linked -- for the slices pk = [(path, sliceID)] of one call -> one SliceRecord per slice, in their order"""
+    rows, totals, _, links, *labelled = out
+    of = lambda records, b: records[records['slice'] == b]          # noqa: E731
+    found = []
+    for b, (p, k) in enumerate(pk):
+        rec = SliceRecord(p, int(k), of(rows, b), totals[b], triples(of(links, b)))
+        if labelled:
+            true_rows, true_totals, true_links, pairs = labelled
+            rec = rec._replace(true_rows=of(true_rows, b), true_total=true_totals[b], true_links=triples(of(true_links, b)),
+                               pairs=triples(of(pairs, b), 'row_true'))
+        found.append(rec)
+    return found
+
+
+def by_exam(records):
+    """records whose first field is the exam path -> {exam: its records}, exams and records in the order of the data set (the slices
+    of two exams may come interleaved)"""
+    exams = {}
+    for rec in records:
+        exams.setdefault(rec[0], []).append(rec)
+    return exams
+
+
+def link_records(exam, records, min_overlap=1):
+    """link_lesions on the predicted plane of an exam's SliceRecords"""
+    return link_lesions(exam, [(r.slice, r.rows, r.total) for r in records], [r.links for r in records], min_overlap=min_overlap)
+
+
+def match_records(matcher, exam, records, min_overlap=1, **kw):
+    """an exam's SliceRecords: either plane linked through the slices (link_lesions), then both handed to `matcher`
+    (match_exam_lesions or detection_match, which get **kw) -> what it returns"""
+    pred_slices, true_slices = [(r.slice, r.rows, r.total) for r in records], [(r.slice, r.true_rows, r.true_total) for r in records]
+    pred_linked = link_records(exam, records, min_overlap)
+    true_linked = link_lesions(exam, true_slices, [r.true_links for r in records], min_overlap=min_overlap)
+    return matcher(exam, true_slices, pred_slices, true_linked, pred_linked, [r.pairs for r in records], **kw)
 
 
 # ---- `annotator evaluate --exam_lesions`: the predicted exam lesions of link_lesions scored against the labelled ones --------------

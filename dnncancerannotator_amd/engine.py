@@ -15,7 +15,7 @@ import logging
 import os
 import re
 import time
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 
@@ -62,6 +62,49 @@ def _forward_on_device(dm, xb, tta_mask, spread=False, temperature=None):
         dm.forward_tta(xb, tta_mask, return_prob=False)
     if temperature is not None:
         dm.scale_temperature(temperature, len(xb))
+
+
+class _SliceChain:
+    """Which slices of a split continue the slice before them, for the linked and matched lesion tables: the same exam path and the
+    next slice number, across splits and batches.  A model that was re-sized since the last split broke the chain -- the row numbers
+    of the slice before stayed behind on the model the batch outgrew -- with a warning led by `who`."""
+
+    def __init__(self, who):
+        self.who, self.model, self.last = who, None, None       # last: (exam, slice) of the slice before
+
+    def continues(self, dm, pk):
+        """one flag per slice of pk = [(path, sliceID)], the split that `dm` has just forwarded"""
+        if self.last is not None and dm is not self.model:
+            logging.warning('%s: the model was re-sized before slice %s of %s: it is not linked to the slice before', self.who, pk[0][1], pk[0][0])
+            self.last = None
+        self.model = dm
+        flags = []
+        for p, k in pk:
+            flags.append(self.last is not None and p == self.last[0] and int(k) == self.last[1] + 1)
+            self.last = (p, int(k))
+        return flags
+
+
+_SplitTables = namedtuple('_SplitTables', 'rows totals masks links srows stotals feats')     # annotate's tables of one split
+
+
+class _Pass:
+    """One extra pass of eval: whether it is on, run(step) -> the new lines of each of its files after a checkpoint, its files
+    [(file name, lead columns, columns)] and their lines so far, one list per file"""
+
+    def __init__(self, on, run, files, tables=None):
+        self.on, self.run, self.files = on, run, files
+        self.tables = [[] for _ in files] if tables is None else tables
+
+    def append(self, new):
+        for table, lines in zip(self.tables, new):
+            table += lines
+
+    def write(self, root):
+        os.makedirs(root, exist_ok=True)
+        for (name, lead, cols), table in zip(self.files, self.tables):
+            with open(os.path.join(root, name), 'w', newline='') as f:
+                f.write(casewise.plain_csv(lead + cols, table))
 
 
 def check_uncertainty(uncertainty, tta):
@@ -572,11 +615,7 @@ class TFKerasModel:
 
     # ---- checkpoints (engine.py:55-78, 103-106, 224-231) -----------------------------------------------------
     def get_ckpts(self, base_path):
-        regex_pattern = fr'^{self.ckpt_pattern}\.index$'.format(epoch=r'(\d+)')
-        files = [f for f in os.listdir(base_path) if re.match(regex_pattern, f)]
-        steps = [int(re.sub(regex_pattern, r'\1', f)) for f in files]
-        paths = [os.path.join(base_path, f[:-len('.index')]) for f in files]
-        return OrderedDict(sorted(zip(steps, paths), key=lambda x: x[0]))
+        return list_ckpts(base_path, self.ckpt_pattern)
 
     def _auto_resume(self, base_path):
         if not os.path.exists(base_path):
@@ -1018,12 +1057,10 @@ class TFKerasModel:
         temperature = check_temperature(temperature)
         if calibration:
             calibration_bins, calibration_grid = check_calibration(calibration_bins, calibration_temperatures)
-        if visualize_sensitivity and not getattr(self.model, 'supports_sensitivity', True):
-            raise NotImplementedError('--visualize_sensitivity is not implemented for model: %s (the input-gradient pass covers the '
-                                      'U-Net models only)' % self.model_config['model'])
-        if attribution and not getattr(self.model, 'supports_sensitivity', True):
-            raise NotImplementedError('--visualize_attribution is not implemented for model: %s (the input-gradient pass covers the '
-                                      'U-Net models only)' % self.model_config['model'])
+        for flag, given in (('--visualize_sensitivity', visualize_sensitivity), ('--visualize_attribution', attribution)):
+            if given and not getattr(self.model, 'supports_sensitivity', True):
+                raise NotImplementedError('%s is not implemented for model: %s (the input-gradient pass covers the U-Net models only)'
+                                          % (flag, self.model_config['model']))
         load_kw = {}
         if check_weights(weights) == 'ema':
             check_ema_checkpoints(select_ckpts(self.get_ckpts(os.path.join(save_path, 'checkpoints')), min_interval, step_range).values())
@@ -1055,24 +1092,44 @@ class TFKerasModel:
         viz_root = os.path.join(export_path, tag)
         casewise_rows = []
         writer = casewise.Writer() if visualize else None
-        exam_pass = bool(exam_lesions) and exam_ds is not None and self.ctx.rank == 0
-        exam_tables = [], [], []         # the lines of the three exam_lesion_*.csv files
-        if bootstrap:                    # and those of exam_lesion_bootstrap.csv
-            exam_tables += ([],)
-        surface_pass = bool(surface_distances) and surface_ds is not None and self.ctx.rank == 0
-        surface_tables = [], [], []      # the lines of surface_results.csv, surface_cases.csv and surface_slices.csv
-        uncertainty_pass = bool(uncertainty) and uncertainty_ds is not None and self.ctx.rank == 0
-        uncertainty_tables = [], []      # the lines of uncertainty_results.csv and uncertainty_slices.csv
-        calibration_pass = bool(calibration) and calibration_ds is not None and self.ctx.rank == 0
-        calibration_tables = [], [], []  # the lines of calibration_results.csv, calibration_bins.csv and calibration_slices.csv
         attribution_table, attribution_names = [], []      # the lines of attribution_results.csv; the modalities of its share columns
-        detection_pass = detection is not None and detection_ds is not None and self.ctx.rank == 0
-        detection_tables = [], [], [], []    # the lines of detection_results.csv, _froc.csv, _cases.csv and _candidates.csv
-        if bootstrap:                        # and those of detection_bootstrap.csv and detection_bootstrap_replicates.csv
-            detection_tables += ([], [])
-        # the exam-lesion pass has no strata; the keyword goes to the passes only with the flag
+        # the keywords travel only with their flags: the temperature to every pass, the bootstrap to the two that resample exams
+        # (the exam-lesion pass has no strata)
         exam_more = dict(bootstrap=dict(bootstrap, stratified=False)) if bootstrap else {}
         detection_more = dict(bootstrap=bootstrap) if bootstrap else {}
+        on = lambda flag, ds: bool(flag) and ds is not None and self.ctx.rank == 0       # noqa: E731
+        lead, C = ['step', 'threshold'], casewise
+        passes = [          # in the order they run, after a checkpoint's evaluation and its Visualizer pass
+            _Pass(on(exam_lesions, exam_ds),
+                  lambda step: self._exam_lesion_pass(
+                      exam_ds, step, [float(t) for t in exam_threshold], exam_iou, exam_link_min_overlap,
+                      dict(resize_factor=exam_resize_factor, filter_size=exam_filter_size, min_area=exam_min_area,
+                           max_lesions=exam_max_lesions), tta_mask=tta_mask, **more, **exam_more),
+                  [('exam_lesion_results.csv', lead, C.EXAM_RESULT_COLUMNS), ('exam_lesion_cases.csv', lead, C.EXAM_CASE_COLUMNS),
+                   ('exam_lesion_matches.csv', lead, C.EXAM_MATCH_COLUMNS)] +
+                  ([('exam_lesion_bootstrap.csv', lead, C.BOOTSTRAP_COLUMNS)] if bootstrap else [])),
+            _Pass(on(surface_distances, surface_ds),
+                  lambda step: self._surface_pass(
+                      surface_ds, step, [float(t) for t in surface_threshold], float(surface_percentile),
+                      dict(resize_factor=surface_resize_factor, filter_size=surface_filter_size, min_area=surface_min_area,
+                           max_samples=surface_max_samples), tta_mask=tta_mask, **more),
+                  [('surface_results.csv', lead, C.SURFACE_RESULT_COLUMNS), ('surface_cases.csv', lead, C.SURFACE_CASE_COLUMNS),
+                   ('surface_slices.csv', lead, C.SURFACE_SLICE_COLUMNS)]),
+            _Pass(on(uncertainty, uncertainty_ds),
+                  lambda step: self._uncertainty_pass(uncertainty_ds, step, [float(t) for t in uncertainty_thresholds], tta_mask, **more),
+                  [('uncertainty_results.csv', lead, C.UNCERTAINTY_RESULT_COLUMNS), ('uncertainty_slices.csv', lead, C.UNCERTAINTY_SLICE_COLUMNS)]),
+            _Pass(on(calibration, calibration_ds),
+                  lambda step: self._calibration_pass(calibration_ds, step, calibration_bins, calibration_grid, tta_mask, **more),
+                  [('calibration_results.csv', ['step'], C.CALIBRATION_RESULT_COLUMNS),
+                   ('calibration_bins.csv', ['step'], C.CALIBRATION_BIN_COLUMNS),
+                   ('calibration_slices.csv', ['step'], C.CALIBRATION_SLICE_COLUMNS)]),
+            _Pass(on(detection, detection_ds),
+                  lambda step: self._detection_pass(detection_ds, step, detection, tta_mask=tta_mask, **more, **detection_more),
+                  [('detection_results.csv', ['step'], C.DETECTION_RESULT_COLUMNS), ('detection_froc.csv', ['step'], C.DETECTION_FROC_COLUMNS),
+                   ('detection_cases.csv', ['step'], C.DETECTION_CASE_COLUMNS),
+                   ('detection_candidates.csv', ['step'], C.DETECTION_CANDIDATE_COLUMNS)] +
+                  ([('detection_bootstrap.csv', ['step'], C.BOOTSTRAP_COLUMNS),
+                    ('detection_bootstrap_replicates.csv', ['step'], C.DETECTION_REPLICATE_COLUMNS)] if bootstrap else []))]
         rows = OrderedDict()
         previous_step = None
         for ckpt_step, ckpt_path_ in self.get_ckpts(ckpt_path).items():
@@ -1089,74 +1146,15 @@ class TFKerasModel:
                 self._visualize(viz_ds, ckpt_step, viz_root, export_csv, export_images, overlay, casewise_rows, writer,
                                 sensitivity=bool(visualize_sensitivity), tta_mask=tta_mask, **more,
                                 **(dict(attribution=attribution + (attribution_table, attribution_names)) if attribution else {}))
-            if exam_pass:
-                for t, new in zip(exam_tables, self._exam_lesion_pass(
-                        exam_ds, ckpt_step, [float(t) for t in exam_threshold], exam_iou, exam_link_min_overlap,
-                        dict(resize_factor=exam_resize_factor, filter_size=exam_filter_size, min_area=exam_min_area,
-                             max_lesions=exam_max_lesions), tta_mask=tta_mask, **more, **exam_more)):
-                    t += new
-            if surface_pass:
-                for t, new in zip(surface_tables, self._surface_pass(
-                        surface_ds, ckpt_step, [float(t) for t in surface_threshold], float(surface_percentile),
-                        dict(resize_factor=surface_resize_factor, filter_size=surface_filter_size, min_area=surface_min_area,
-                             max_samples=surface_max_samples), tta_mask=tta_mask, **more)):
-                    t += new
-            if uncertainty_pass:
-                for t, new in zip(uncertainty_tables, self._uncertainty_pass(uncertainty_ds, ckpt_step,
-                                                                             [float(t) for t in uncertainty_thresholds], tta_mask,
-                                                                             **more)):
-                    t += new
-            if calibration_pass:
-                for t, new in zip(calibration_tables, self._calibration_pass(calibration_ds, ckpt_step, calibration_bins,
-                                                                             calibration_grid, tta_mask, **more)):
-                    t += new
-            if detection_pass:
-                for t, new in zip(detection_tables, self._detection_pass(detection_ds, ckpt_step, detection, tta_mask=tta_mask, **more,
-                                                                           **detection_more)):
-                    t += new
-        if detection_pass:
-            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
-            for name, cols, table in zip(('detection_results.csv', 'detection_froc.csv', 'detection_cases.csv', 'detection_candidates.csv',
-                                          'detection_bootstrap.csv', 'detection_bootstrap_replicates.csv'),
-                                         (casewise.DETECTION_RESULT_COLUMNS, casewise.DETECTION_FROC_COLUMNS,
-                                          casewise.DETECTION_CASE_COLUMNS, casewise.DETECTION_CANDIDATE_COLUMNS,
-                                          casewise.BOOTSTRAP_COLUMNS, casewise.DETECTION_REPLICATE_COLUMNS), detection_tables):
-                with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
-                    f.write(casewise.plain_csv(['step'] + cols, table))
-        if calibration_pass:
-            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
-            for name, cols, table in zip(('calibration_results.csv', 'calibration_bins.csv', 'calibration_slices.csv'),
-                                         (casewise.CALIBRATION_RESULT_COLUMNS, casewise.CALIBRATION_BIN_COLUMNS,
-                                          casewise.CALIBRATION_SLICE_COLUMNS), calibration_tables):
-                with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
-                    f.write(casewise.plain_csv(['step'] + cols, table))
-        if uncertainty_pass:
-            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
-            for name, cols, table in zip(('uncertainty_results.csv', 'uncertainty_slices.csv'),
-                                         (casewise.UNCERTAINTY_RESULT_COLUMNS, casewise.UNCERTAINTY_SLICE_COLUMNS), uncertainty_tables):
-                with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
-                    f.write(casewise.plain_csv(['step', 'threshold'] + cols, table))
-        if surface_pass:
-            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
-            for name, cols, table in zip(('surface_results.csv', 'surface_cases.csv', 'surface_slices.csv'),
-                                         (casewise.SURFACE_RESULT_COLUMNS, casewise.SURFACE_CASE_COLUMNS, casewise.SURFACE_SLICE_COLUMNS),
-                                         surface_tables):
-                with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
-                    f.write(casewise.plain_csv(['step', 'threshold'] + cols, table))
-        if exam_pass:
-            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
-            for name, cols, table in zip(('exam_lesion_results.csv', 'exam_lesion_cases.csv', 'exam_lesion_matches.csv',
-                                          'exam_lesion_bootstrap.csv'),
-                                         (casewise.EXAM_RESULT_COLUMNS, casewise.EXAM_CASE_COLUMNS, casewise.EXAM_MATCH_COLUMNS,
-                                          casewise.BOOTSTRAP_COLUMNS), exam_tables):
-                with open(os.path.join(export_path, tag, name), 'w', newline='') as f:
-                    f.write(casewise.plain_csv(['step', 'threshold'] + cols, table))
+            for ps in passes:
+                if ps.on:
+                    ps.append(ps.run(ckpt_step))
         if attribution and visualize:
-            os.makedirs(os.path.join(export_path, tag), exist_ok=True)
-            with open(os.path.join(export_path, tag, 'attribution_results.csv'), 'w', newline='') as f:
-                cols = casewise.ATTRIBUTION_RESULT_COLUMNS + ['share_%s' % n for n in attribution_names] + \
-                    ['mean_relative_gap', 'max_relative_gap']
-                f.write(casewise.plain_csv(['step'] + cols, attribution_table))
+            cols = casewise.ATTRIBUTION_RESULT_COLUMNS + ['share_%s' % n for n in attribution_names] + ['mean_relative_gap', 'max_relative_gap']
+            passes.append(_Pass(True, None, [('attribution_results.csv', ['step'], cols)], [attribution_table]))
+        for ps in passes:
+            if ps.on:
+                ps.write(os.path.join(export_path, tag))
         if writer is not None:
             writer.close()
         if export_csv and self.ctx.rank == 0:
@@ -1184,66 +1182,60 @@ class TFKerasModel:
         spec = casewise.device_spec()
         attr_shares, attr_gaps = [], []
         names = casewise.column_names()
-        for x, y, paths, ids in viz_ds:
-            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
-            if not len(x):
-                continue
-            self._ensure_capacity(len(x))
-            dm = self.device_model
-            for i in range(0, len(x), dm.max_batch):
-                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
-                tags = [casewise.tag_of(p, k) for p, k in zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch])]
-                _forward_on_device(dm, xb, tta_mask, temperature=temperature)
-                if export_csv:
-                    counts = dm.region_confusion_slices(yb, [spec])
-                    for t, c in zip(tags, counts):
-                        values = casewise.row_values(c, t)
-                        casewise_rows.append(values)
-                        writer.submit(casewise.csv_path(root, t, step), casewise.series_csv, names, values)
-                if export_images:
-                    # the labels went up with the counts already: the renderer reuses them
-                    images = dm.render_composite(None if export_csv else yb, len(xb), casewise.RATIO, overlay)
-                    for t, im in zip(tags, images):
-                        writer.submit(casewise.image_path(root, t, step), casewise.encode_png, im)
-                if sensitivity:
-                    sens = casewise.normalise_sensitivity(dm.input_sensitivity(batch=len(xb)))
-                    mods = casewise.modality_names(getattr(viz_ds, 'slice_types', None), sens.shape[1])
-                    for t, row in zip(tags, sens):
-                        if export_csv:
-                            writer.submit(casewise.sensitivity_path(root, t, step, 'csv'), casewise.sensitivity_csv, mods, row)
-                        if export_images:
-                            writer.submit(casewise.sensitivity_path(root, t, step, 'images'),
-                                          lambda r: casewise.encode_png(casewise.sensitivity_chart(r)), row)
-                if attribution:
-                    ig = dm.integrated_gradients(batch=len(xb), steps=attribution[0], baseline=attribution[1],
-                                                 return_map=bool(export_images))
-                    shares = casewise.attribution_shares(ig.absolute)
-                    mods = casewise.modality_names(getattr(viz_ds, 'slice_types', None), shares.shape[1])
-                    attribution[3][:] = mods
-                    attr_shares += list(shares)
-                    attr_gaps += list(casewise.attribution_gap(ig.signed, ig.endpoints)[1])
-                    for b, t in enumerate(tags):
-                        if export_csv:
-                            writer.submit(casewise.attribution_path(root, t, step, 'csv'), casewise.attribution_csv, mods, shares[b],
-                                          ig.signed[b], ig.absolute[b], ig.endpoints[b])
-                        if export_images:
-                            writer.submit(casewise.attribution_path(root, t, step, 'images'),
-                                          lambda m, n: casewise.encode_png(casewise.attribution_image(m, n)), ig.map[b], mods)
+        for dm, xb, yb, pk in self._forwarded_splits(viz_ds, tta_mask, temperature=temperature):
+            tags = [casewise.tag_of(p, k) for p, k in pk]
+            if export_csv:
+                counts = dm.region_confusion_slices(yb, [spec])
+                for t, c in zip(tags, counts):
+                    values = casewise.row_values(c, t)
+                    casewise_rows.append(values)
+                    writer.submit(casewise.csv_path(root, t, step), casewise.series_csv, names, values)
+            if export_images:
+                # the labels went up with the counts already: the renderer reuses them
+                images = dm.render_composite(None if export_csv else yb, len(xb), casewise.RATIO, overlay)
+                for t, im in zip(tags, images):
+                    writer.submit(casewise.image_path(root, t, step), casewise.encode_png, im)
+            if sensitivity:
+                sens = casewise.normalise_sensitivity(dm.input_sensitivity(batch=len(xb)))
+                mods = casewise.modality_names(getattr(viz_ds, 'slice_types', None), sens.shape[1])
+                for t, row in zip(tags, sens):
+                    if export_csv:
+                        writer.submit(casewise.sensitivity_path(root, t, step, 'csv'), casewise.sensitivity_csv, mods, row)
+                    if export_images:
+                        writer.submit(casewise.sensitivity_path(root, t, step, 'images'),
+                                      lambda r: casewise.encode_png(casewise.sensitivity_chart(r)), row)
+            if attribution:
+                ig = dm.integrated_gradients(batch=len(xb), steps=attribution[0], baseline=attribution[1],
+                                             return_map=bool(export_images))
+                shares = casewise.attribution_shares(ig.absolute)
+                mods = casewise.modality_names(getattr(viz_ds, 'slice_types', None), shares.shape[1])
+                attribution[3][:] = mods
+                attr_shares += list(shares)
+                attr_gaps += list(casewise.attribution_gap(ig.signed, ig.endpoints)[1])
+                for b, t in enumerate(tags):
+                    if export_csv:
+                        writer.submit(casewise.attribution_path(root, t, step, 'csv'), casewise.attribution_csv, mods, shares[b],
+                                      ig.signed[b], ig.absolute[b], ig.endpoints[b])
+                    if export_images:
+                        writer.submit(casewise.attribution_path(root, t, step, 'images'),
+                                      lambda m, n: casewise.encode_png(casewise.attribution_image(m, n)), ig.map[b], mods)
         if attribution:
             attribution[2].append([int(step)] + casewise.attribution_summary(attribution[0], attribution[1], attr_shares, attr_gaps))
 
-    def _forwarded_splits(self, ds, tta_mask, spread=False, temperature=None):
-        """The analysis passes' walk over ds batches (x, y, paths, sliceIDs): empty batches skipped, the model grown to the batch,
-        the batch split by max_batch and every split forwarded with its probabilities left on the device (_forward_on_device).
-        Yields (the device model, x and y of the split, [(path, sliceID)] of its slices)."""
-        for x, y, paths, ids in ds:
-            x, y = np.asarray(x, np.float32), np.asarray(y, np.float32)
+    def _forwarded_splits(self, ds, tta_mask, spread=False, temperature=None, labels=True):
+        """The one walk over an analysis data set, ds batches (x, y, paths, sliceIDs) or, with labels=False, annotate's (x, ...,
+        paths, sliceIDs), where a label in between is never looked at: empty batches skipped, the model grown to the batch, the
+        batch split by max_batch and every split forwarded with its probabilities left on the device (_forward_on_device).
+        Yields (the device model, x and y of the split, [(path, sliceID)] of its slices); y is None with labels=False."""
+        for el in ds:
+            x, paths, ids = np.asarray(el[0], np.float32), el[-2], el[-1]
+            y = np.asarray(el[1], np.float32) if labels else None
             if not len(x):
                 continue
             self._ensure_capacity(len(x))
             dm = self.device_model
             for i in range(0, len(x), dm.max_batch):
-                xb, yb = x[i:i + dm.max_batch], y[i:i + dm.max_batch]
+                xb, yb = x[i:i + dm.max_batch], None if y is None else y[i:i + dm.max_batch]
                 _forward_on_device(dm, xb, tta_mask, spread=spread, temperature=temperature)
                 yield dm, xb, yb, list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
 
@@ -1252,52 +1244,30 @@ class TFKerasModel:
         probabilities stay on the device and one DeviceModel.lesion_table_matched per threshold; then per threshold and exam
         casewise.link_lesions on either plane and casewise.match_exam_lesions.  Returns the new lines of (exam_lesion_results.csv,
         exam_lesion_cases.csv, exam_lesion_matches.csv), each led by step and threshold.
-        A slice continues the one before it by annotate's rule: the same exam path and the next slice number, across splits and
+        A slice continues the one before it by _SliceChain's rule: the same exam path and the next slice number, across splits and
         batches.  continues[0] of a matched call refers to the model's last matched call, which with several thresholds was
         another threshold's: the call is then led by a one-slice call that puts this threshold's rows of the slice before back
         (its probabilities and labels are kept on the host for that; a single threshold needs neither).
         bootstrap (what check_bootstrap returned): per threshold one DeviceModel.bootstrap_sums over the exams' counts after the
         summary, and a fourth table, the new lines of exam_lesion_bootstrap.csv."""
         several = len(thresholds) > 1
-        found = [[] for _ in thresholds]     # per threshold and slice: (exam, slice, rows, total, links, true rows, total, links, pairs)
-        before, last, tail, carry_of = None, None, None, None
+        found = [[] for _ in thresholds]     # per threshold: the casewise.SliceRecord of every slice
+        chain, tail, carry_of = _SliceChain('evaluate'), None, None
         for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature):
-            if last is not None and dm is not before:
-                # the row numbers of the slice before stayed behind on the model this batch outgrew: the chain breaks here
-                logging.warning('evaluate: the model was re-sized before slice %s of %s: it is not linked to the slice before', pk[0][1], pk[0][0])
-                last = None
-            before = dm
-            continues = []
-            for p, k in pk:
-                continues.append(last is not None and p == last[0] and int(k) == last[1] + 1)
-                last = (p, int(k))
+            continues = chain.continues(dm, pk)
             for ti, thr in enumerate(thresholds):
                 if continues[0] and carry_of != ti:
                     dm.lesion_table_matched(tail[1], prob=tail[0], continues=[False], threshold=thr, **kw)
-                out = dm.lesion_table_matched(yb, batch=len(xb), continues=continues, threshold=thr, **kw)
+                found[ti] += casewise.slice_records(dm.lesion_table_matched(yb, batch=len(xb), continues=continues, threshold=thr, **kw), pk)
                 carry_of = ti
-                by_slice = [[o[o['slice'] == b] for b in range(len(xb))] for o in (out[0], out[3], out[4], out[6], out[7])]
-                for b, (p, k) in enumerate(pk):
-                    rows, links, true_rows, true_links, pairs = [s[b] for s in by_slice]
-                    found[ti].append((p, int(k), rows, out[1][b], [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in links],
-                                      true_rows, out[5][b],
-                                      [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in true_links],
-                                      [(int(q['row_true']), int(q['row']), int(q['overlap'])) for q in pairs]))
             if several:
                 tail = dm.last_prob(len(xb))[-1:], yb[-1:].reshape(1, *yb.shape[1:3])
         results, cases, matches, intervals = [], [], [], []
         for thr, mine in zip(thresholds, found):
             lead = [int(step), repr(thr)]
-            exams = OrderedDict()            # exam path -> its slices, in the order of the data set
-            for rec in mine:
-                exams.setdefault(rec[0], []).append(rec)
             mine_cases = []
-            for exam, recs in exams.items():
-                pred_slices, true_slices = [r[1:4] for r in recs], [(r[1], r[5], r[6]) for r in recs]
-                pred_linked = casewise.link_lesions(exam, pred_slices, [r[4] for r in recs], min_overlap=min_overlap)
-                true_linked = casewise.link_lesions(exam, true_slices, [r[7] for r in recs], min_overlap=min_overlap)
-                case, lines = casewise.match_exam_lesions(exam, true_slices, pred_slices, true_linked, pred_linked, [r[8] for r in recs],
-                                                          iou=iou)
+            for exam, recs in casewise.by_exam(mine).items():
+                case, lines = casewise.match_records(casewise.match_exam_lesions, exam, recs, min_overlap, iou=iou)
                 mine_cases.append(case)
                 matches += [lead + l for l in lines]
             cases += [lead + c for c in mine_cases]
@@ -1316,40 +1286,20 @@ class TFKerasModel:
         DeviceModel.lesion_table_matched on it (casewise.detection_table_args: the rows are the candidates, max_prob their
         confidence); then per exam casewise.link_lesions on either plane and casewise.detection_match, and casewise.detection_summary
         over all exams.  det: what check_detection returned.  Returns the new lines of (detection_results.csv, detection_froc.csv,
-        detection_cases.csv, detection_candidates.csv), each led by step.  Slices continue each other by _exam_lesion_pass's rule.
+        detection_cases.csv, detection_candidates.csv), each led by step.  Slices continue each other by _SliceChain's rule.
         bootstrap (what check_bootstrap returned): one DeviceModel.bootstrap_detection over the same cases after the summary, and
         two more tables, the new lines of detection_bootstrap.csv and detection_bootstrap_replicates.csv."""
         kw = casewise.detection_table_args(det['cfg'], det['max_lesions'])
-        found, exhausted = [], 0             # per slice: (exam, slice, rows, total, links, true rows, total, links, pairs)
-        before, last = None, None
+        found, exhausted = [], 0             # the casewise.SliceRecord of every slice
+        chain = _SliceChain('evaluate')
         for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature):
-            if last is not None and dm is not before:
-                logging.warning('evaluate: the model was re-sized before slice %s of %s: it is not linked to the slice before', pk[0][1], pk[0][0])
-                last = None
-            before = dm
-            continues = []
-            for p, k in pk:
-                continues.append(last is not None and p == last[0] and int(k) == last[1] + 1)
-                last = (p, int(k))
-            _, slice_records = dm.detection_map(len(xb), **det['cfg'])
-            exhausted += int(slice_records['exhausted'].sum())
-            out = dm.lesion_table_matched(yb, batch=len(xb), continues=continues, **kw)
-            by_slice = [[o[o['slice'] == b] for b in range(len(xb))] for o in (out[0], out[3], out[4], out[6], out[7])]
-            for b, (p, k) in enumerate(pk):
-                rows, links, true_rows, true_links, pairs = [s[b] for s in by_slice]
-                found.append((p, int(k), rows, out[1][b], [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in links],
-                              true_rows, out[5][b], [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in true_links],
-                              [(int(q['row_true']), int(q['row']), int(q['overlap'])) for q in pairs]))
-        exams = OrderedDict()                # exam path -> its slices, in the order of the data set
-        for rec in found:
-            exams.setdefault(rec[0], []).append(rec)
+            continues = chain.continues(dm, pk)
+            _, map_records = dm.detection_map(len(xb), **det['cfg'])
+            exhausted += int(map_records['exhausted'].sum())
+            found += casewise.slice_records(dm.lesion_table_matched(yb, batch=len(xb), continues=continues, **kw), pk)
         lead, cases, candidates = [int(step)], [], []
-        for exam, recs in exams.items():
-            pred_slices, true_slices = [r[1:4] for r in recs], [(r[1], r[5], r[6]) for r in recs]
-            pred_linked = casewise.link_lesions(exam, pred_slices, [r[4] for r in recs], min_overlap=det['link_min_overlap'])
-            true_linked = casewise.link_lesions(exam, true_slices, [r[7] for r in recs], min_overlap=det['link_min_overlap'])
-            case, lines = casewise.detection_match(exam, true_slices, pred_slices, true_linked, pred_linked, [r[8] for r in recs],
-                                                   iou=det['iou'])
+        for exam, recs in casewise.by_exam(found).items():
+            case, lines = casewise.match_records(casewise.detection_match, exam, recs, det['link_min_overlap'], iou=det['iou'])
             cases.append(case)
             candidates += [lead + l for l in lines]
         result, froc = casewise.detection_summary(cases, exhausted)
@@ -1383,11 +1333,9 @@ class TFKerasModel:
         results, cases, slices = [], [], []
         for thr, mine in zip(thresholds, found):
             lead = [int(step), repr(thr)]
-            exams = OrderedDict()            # exam path -> its slices, in the order of the data set
-            for rec in mine:
-                exams.setdefault(rec[0], []).append(rec)
             slice_values = [casewise.surface_slice_values(*rec, percentile=percentile) for rec in mine]
-            exam_values = [casewise.surface_exam_values(exam, [r[2:] for r in recs], percentile=percentile) for exam, recs in exams.items()]
+            exam_values = [casewise.surface_exam_values(exam, [(c, d2_pred, d2_true) for _, _, c, d2_pred, d2_true in recs], percentile=percentile)
+                           for exam, recs in casewise.by_exam(mine).items()]
             slices += [lead + v for v in slice_values]
             cases += [lead + v for v in exam_values]
             results.append(lead + casewise.surface_summary(slice_values, exam_values))
@@ -1491,110 +1439,47 @@ class TFKerasModel:
             raise RuntimeError('annotate runs in a single process (WORLD_SIZE is %d): start it without the launcher' % self.ctx.world)
         tta_mask = None if tta == tta_modes.NONE else tta_modes.mask_of(tta, *_element_shape(dataset)[1:3])
         self._build(dataset)
-        ckpts = self.get_ckpts(os.path.join(save_path, 'checkpoints'))
-        if not ckpts:
-            raise ValueError(f'no checkpoint under {save_path}/checkpoints')
-        if step is None:
-            step = max(ckpts)
-        if step not in ckpts:
-            raise ValueError(f'no checkpoint of step {step} under {save_path}/checkpoints (have {sorted(ckpts)})')
-        if weights == 'ema':
-            check_ema_checkpoints([ckpts[step]])
-            self.load(ckpts[step], weights='ema')
-        else:
-            self.load(ckpts[step])
-        lesion_rows, slice_rows = [], []
-        lesion_spread_rows, slice_spread_rows = [], []
-        feature_rows, linked_features = [], []       # linked_features: beside `linked`, every slice's feature records per lesion
+        step = self._load_step(save_path, step, weights)
+        features = dict(bins=feature_bins, ring=feature_ring) if lesion_features else None
         modalities = casewise.modality_names(getattr(dataset, 'slice_types', None), _element_shape(dataset)[3]) if lesion_features else None
         scale = {} if temperature is None else dict(temperature=temperature)      # the forward gets the keyword only with a temperature
+        lesion_rows, slice_rows, lesion_spread_rows, slice_spread_rows = [], [], [], []
+        feature_rows, linked_features = [], []       # linked_features: beside `linked`, every slice's feature records per lesion
         candidate_rows, slice_candidate_rows, candidates_linked = [], [], []         # detection_map: as lesion_rows / slice_rows / linked
-        dm = None
-        linked, last = [], None          # link_slices: (exam, slice, rows, total, links into it) per slice; the slice before: (exam, slice)
+        linked, chain = [], _SliceChain('predict')   # link_slices: the casewise.SliceRecord of every slice
         writer = casewise.Writer() if export_images else None
         try:
-            for el in dataset:
-                x, paths, ids = np.asarray(el[0], np.float32), el[-2], el[-1]      # a label between them is never looked at
-                if not len(x):
-                    continue
-                self._ensure_capacity(len(x))
-                if link_slices and last is not None and dm is not self.device_model:
-                    # the row numbers of the slice before stayed behind on the model this batch outgrew: the chain breaks here
-                    logging.warning('predict: the model was re-sized before slice %s of %s: it is not linked to the slice before', ids[0], paths[0])
-                    last = None
-                dm = self.device_model
-                for i in range(0, len(x), dm.max_batch):
-                    xb = x[i:i + dm.max_batch]
-                    _forward_on_device(dm, xb, tta_mask, spread=bool(uncertainty), **scale)
-                    pk = list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
-                    kw = dict(batch=len(xb), threshold=threshold, resize_factor=resize_factor, filter_size=filter_size,
-                              min_area=min_area, max_lesions=max_lesions, mask=bool(export_images))
-                    if link_slices:
-                        continues = []
-                        for p, k in pk:
-                            continues.append(last is not None and p == last[0] and int(k) == last[1] + 1)
-                            last = (p, int(k))
-                        rows, totals, masks, links = dm.lesion_table_linked(continues=continues, **kw)
-                        if uncertainty:              # the spread records of the same rows (there is no linked table with spread)
-                            _, _, _, srows, stotals = dm.lesion_table_spread(**dict(kw, mask=False))
-                    elif uncertainty:
-                        rows, totals, masks, srows, stotals = dm.lesion_table_spread(**kw)
-                    elif lesion_features:
-                        rows, totals, masks, *feats = dm.lesion_table_features(bins=feature_bins, ring=feature_ring, **kw)
-                    else:
-                        rows, totals, masks = dm.lesion_table(**kw)
+            for dm, xb, _, pk in self._forwarded_splits(dataset, tta_mask, spread=bool(uncertainty), labels=False, **scale):
+                continues = chain.continues(dm, pk) if link_slices else None
+                t = self._lesion_tables(dm, dict(batch=len(xb), threshold=threshold, resize_factor=resize_factor, filter_size=filter_size,
+                                                 min_area=min_area, max_lesions=max_lesions, mask=bool(export_images)),
+                                        continues, uncertainty, features)
+                spread = dm.last_spread(len(xb)) if uncertainty and export_images else None
+                if det:                              # last: from here on the buffer holds the map
+                    for table, new in zip((candidate_rows, slice_candidate_rows, candidates_linked),
+                                          self._candidate_tables(dm, xb, pk, det, continues, writer, output)):
+                        table += new
+                if link_slices:
+                    linked += casewise.slice_records((t.rows, t.totals, t.masks, t.links), pk)
+                for b, (p, k) in enumerate(pk):
+                    mine = t.rows[t.rows['slice'] == b]
+                    lesion_rows += [casewise.lesion_values(p, k, r) for r in mine]
+                    slice_rows.append(casewise.slice_values(p, k, mine, t.totals[b]))
+                    if export_images:
+                        writer.submit(casewise.mask_path(output, casewise.tag_of(p, k)), casewise.encode_png, t.masks[b])
                     if lesion_features:
-                        if link_slices or uncertainty:   # the feature records of the same rows, from a call of their own
-                            feats = dm.lesion_table_features(bins=feature_bins, ring=feature_ring, **dict(kw, mask=False))[3:]
-                        if len(feats[0]) != len(rows):
-                            raise RuntimeError('predict: %d feature records beside %d lesions' % (len(feats[0]), len(rows)))
+                        fmine = [None if f is None else f[t.rows['slice'] == b] for f in t.feats]
+                        per_lesion = [tuple(None if f is None else f[j] for f in fmine) for j in range(len(mine))]
+                        feature_rows += [casewise.lesion_feature_values(p, k, r, *f) for r, f in zip(mine, per_lesion)]
+                        if link_slices:
+                            linked_features.append(per_lesion)
                     if uncertainty:
-                        if len(srows) != len(rows):
-                            raise RuntimeError('predict: %d spread records beside %d lesions' % (len(srows), len(rows)))
-                        spread = dm.last_spread(len(xb)) if export_images else None
-                    if det:                          # last: from here on the buffer holds the map
-                        _, drecs = dm.detection_map(len(xb), **det['cfg'])
-                        dkw = casewise.detection_table_args(det['cfg'], det['max_lesions'])
-                        if link_slices:
-                            dout = dm.lesion_table_matched(np.zeros((len(xb),) + xb.shape[1:3], np.float32), batch=len(xb),
-                                                           continues=continues, **dkw)
-                            drows, dtotals, dlinks = dout[0], dout[1], dout[3]
-                        else:
-                            drows, dtotals, _ = dm.lesion_table(batch=len(xb), mask=False, **dkw)
-                        dmaps = dm.last_prob(len(xb)) if export_images else None
-                        for b, (p, k) in enumerate(pk):
-                            mine = drows[drows['slice'] == b]
-                            candidate_rows += [casewise.candidate_values(p, k, r) for r in mine]
-                            slice_candidate_rows.append([p, int(k)] + [int(drecs[b][f]) for f in ('candidates', 'rounds', 'dropped', 'exhausted')])
-                            if link_slices:
-                                into = dlinks[dlinks['slice'] == b]
-                                candidates_linked.append((p, int(k), mine, dtotals[b],
-                                                          [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in into]))
-                            if export_images:
-                                writer.submit(casewise.detection_path(output, casewise.tag_of(p, k)),
-                                              lambda d_: casewise.encode_png(casewise.detection_image(d_)), dmaps[b])
-                    for b, (p, k) in enumerate(pk):
-                        mine = rows[rows['slice'] == b]
-                        if link_slices:
-                            into = links[links['slice'] == b]
-                            linked.append((p, int(k), mine, totals[b], [(int(l['row_prev']), int(l['row']), int(l['overlap'])) for l in into]))
-                        lesion_rows += [casewise.lesion_values(p, k, r) for r in mine]
-                        slice_rows.append(casewise.slice_values(p, k, mine, totals[b]))
+                        smine = t.srows[t.rows['slice'] == b]
+                        lesion_spread_rows += [casewise.lesion_uncertainty_values(p, k, r, q) for r, q in zip(mine, smine)]
+                        slice_spread_rows.append(casewise.slice_uncertainty_values(p, k, mine, smine, t.totals[b], t.stotals[b]))
                         if export_images:
-                            writer.submit(casewise.mask_path(output, casewise.tag_of(p, k)), casewise.encode_png, masks[b])
-                        if lesion_features:
-                            fmine = [None if f is None else f[rows['slice'] == b] for f in feats]
-                            per_lesion = [tuple(None if f is None else f[j] for f in fmine) for j in range(len(mine))]
-                            feature_rows += [casewise.lesion_feature_values(p, k, r, *f) for r, f in zip(mine, per_lesion)]
-                            if link_slices:
-                                linked_features.append(per_lesion)
-                        if uncertainty:
-                            smine = srows[rows['slice'] == b]
-                            lesion_spread_rows += [casewise.lesion_uncertainty_values(p, k, r, q) for r, q in zip(mine, smine)]
-                            slice_spread_rows.append(casewise.slice_uncertainty_values(p, k, mine, smine, totals[b], stotals[b]))
-                            if export_images:
-                                writer.submit(casewise.uncertainty_path(output, casewise.tag_of(p, k)),
-                                              lambda s_: casewise.encode_png(casewise.uncertainty_image(s_)), spread[b])
+                            writer.submit(casewise.uncertainty_path(output, casewise.tag_of(p, k)),
+                                          lambda s_: casewise.encode_png(casewise.uncertainty_image(s_)), spread[b])
         finally:
             if writer is not None:
                 writer.close()
@@ -1606,26 +1491,10 @@ class TFKerasModel:
                        ('slice_uncertainty.csv', casewise.SLICE_UNCERTAINTY_COLUMNS, slice_spread_rows)]
         if lesion_features:
             tables.append(('lesion_features.csv', casewise.lesion_feature_columns(modalities), feature_rows))
-        exam_feature_rows = []
         if link_slices:
-            exams = {}                   # exam path -> the positions of its slices in `linked`, in the order of the data set
-            for pos, rec in enumerate(linked):
-                exams.setdefault(rec[0], []).append(pos)
-            exam_rows, parts_of = [], [None] * len(linked)
-            for exam, where in exams.items():
-                table, parts = casewise.link_lesions(exam, [linked[pos][1:4] for pos in where], [linked[pos][4] for pos in where],
-                                                     min_overlap=link_min_overlap)
-                exam_rows += table
-                if lesion_features:      # the parts are in the order of the exam's lesions: gather every exam lesion's
-                    of = [f for pos in where for f in linked_features[pos]]
-                    for e in range(len(table)):
-                        exam_feature_rows.append(casewise.exam_lesion_feature_values(
-                            exam, e, [f for f, part in zip(of, parts) if part[3] == e]))
-                for pos in where:        # the parts come slice after slice; lesions.csv is in the order of the data set
-                    n = len(linked[pos][2])
-                    parts_of[pos], parts = parts[:n], parts[n:]
+            exam_rows, part_rows, exam_feature_rows = self._exam_tables(linked, linked_features if lesion_features else None, link_min_overlap)
             tables += [('exam_lesions.csv', casewise.EXAM_LESION_COLUMNS, exam_rows),
-                       ('exam_lesion_parts.csv', casewise.EXAM_PART_COLUMNS, sum(parts_of, []))]
+                       ('exam_lesion_parts.csv', casewise.EXAM_PART_COLUMNS, part_rows)]
             res['exam_lesions'] = len(exam_rows)
             if lesion_features:
                 tables.append(('exam_lesion_features.csv', casewise.exam_lesion_feature_columns(modalities), exam_feature_rows))
@@ -1634,18 +1503,98 @@ class TFKerasModel:
                        ('slice_candidates.csv', casewise.SLICE_CANDIDATE_COLUMNS, slice_candidate_rows)]
             res['candidates'] = len(candidate_rows)
             if link_slices:
-                exams = OrderedDict()
-                for rec in candidates_linked:
-                    exams.setdefault(rec[0], []).append(rec)
                 exam_candidates = []
-                for exam, recs in exams.items():
-                    table, _ = casewise.link_lesions(exam, [r[1:4] for r in recs], [r[4] for r in recs], min_overlap=det['link_min_overlap'])
+                for exam, recs in casewise.by_exam(candidates_linked).items():
+                    table, _ = casewise.link_records(exam, recs, det['link_min_overlap'])
                     exam_candidates += [r + [r[15]] for r in table]
                 tables.append(('exam_candidates.csv', casewise.EXAM_CANDIDATE_COLUMNS, exam_candidates))
         for name, cols, table in tables:
             with open(os.path.join(output, name), 'w', newline='') as f:
                 f.write(casewise.plain_csv(cols, table))
         return res
+
+    def _load_step(self, save_path, step, weights):
+        """annotate's checkpoint: `step` of save_path (None: the latest) loaded, raw or with its averaged weights -> its step"""
+        ckpts = self.get_ckpts(os.path.join(save_path, 'checkpoints'))
+        if not ckpts:
+            raise ValueError(f'no checkpoint under {save_path}/checkpoints')
+        if step is None:
+            step = max(ckpts)
+        if step not in ckpts:
+            raise ValueError(f'no checkpoint of step {step} under {save_path}/checkpoints (have {sorted(ckpts)})')
+        if weights == 'ema':
+            check_ema_checkpoints([ckpts[step]])
+        self.load(ckpts[step], **(dict(weights='ema') if weights == 'ema' else {}))
+        return step
+
+    @staticmethod
+    def _lesion_tables(dm, kw, continues, uncertainty, features):
+        """annotate's table calls on the split `dm` has just forwarded -> _SplitTables.  kw: the keywords every lesion_table* call
+        takes; continues (link_slices, else None): lesion_table_linked; uncertainty: lesion_table_spread; features (lesion_features:
+        dict(bins, ring), else None): lesion_table_features.  There is no linked table with spread or features and none with both:
+        the spread and feature records of the same rows then come from a call of their own, without masks"""
+        links = srows = stotals = feats = None
+        if continues is not None:
+            rows, totals, masks, links = dm.lesion_table_linked(continues=continues, **kw)
+            if uncertainty:
+                _, _, _, srows, stotals = dm.lesion_table_spread(**dict(kw, mask=False))
+        elif uncertainty:
+            rows, totals, masks, srows, stotals = dm.lesion_table_spread(**kw)
+        elif features:
+            rows, totals, masks, *feats = dm.lesion_table_features(**features, **kw)
+        else:
+            rows, totals, masks = dm.lesion_table(**kw)
+        if features:
+            if continues is not None or uncertainty:
+                feats = dm.lesion_table_features(**features, **dict(kw, mask=False))[3:]
+            if len(feats[0]) != len(rows):
+                raise RuntimeError('predict: %d feature records beside %d lesions' % (len(feats[0]), len(rows)))
+        if uncertainty and len(srows) != len(rows):
+            raise RuntimeError('predict: %d spread records beside %d lesions' % (len(srows), len(rows)))
+        return _SplitTables(rows, totals, masks, links, srows, stotals, feats)
+
+    @staticmethod
+    def _candidate_tables(dm, xb, pk, det, continues, writer, output):
+        """annotate's detection-map part on a split, after every other read of the probabilities: DeviceModel.detection_map in
+        place, then the table read from the map -- lesion_table, or with `continues` (link_slices) lesion_table_matched against
+        empty labels -- and with a writer (export_images) the map itself.  Returns the split's (candidates.csv lines,
+        slice_candidates.csv lines, SliceRecords for exam_candidates.csv: none without link_slices)"""
+        _, map_records = dm.detection_map(len(xb), **det['cfg'])
+        kw = casewise.detection_table_args(det['cfg'], det['max_lesions'])
+        if continues is not None:
+            rows, totals, masks, links, *_ = dm.lesion_table_matched(np.zeros((len(xb),) + xb.shape[1:3], np.float32), batch=len(xb),
+                                                                     continues=continues, **kw)
+        else:
+            rows, _, _ = dm.lesion_table(batch=len(xb), mask=False, **kw)
+        maps = dm.last_prob(len(xb)) if writer is not None else None
+        candidates, slices = [], []
+        for b, (p, k) in enumerate(pk):
+            candidates += [casewise.candidate_values(p, k, r) for r in rows[rows['slice'] == b]]
+            slices.append([p, int(k)] + [int(map_records[b][f]) for f in ('candidates', 'rounds', 'dropped', 'exhausted')])
+            if writer is not None:
+                writer.submit(casewise.detection_path(output, casewise.tag_of(p, k)),
+                              lambda d_: casewise.encode_png(casewise.detection_image(d_)), maps[b])
+        return candidates, slices, casewise.slice_records((rows, totals, masks, links), pk) if continues is not None else []
+
+    @staticmethod
+    def _exam_tables(linked, linked_features, min_overlap):
+        """annotate --link_slices after the walk: the SliceRecords of every slice (and with lesion_features, beside them, every
+        slice's feature records per lesion; else None) -> the lines of (exam_lesions.csv, exam_lesion_parts.csv,
+        exam_lesion_features.csv)"""
+        exam_rows, exam_feature_rows, parts_of = [], [], [None] * len(linked)
+        # exam path -> the positions of its slices in `linked`, in the order of the data set
+        for exam, where in casewise.by_exam([(rec.exam, pos) for pos, rec in enumerate(linked)]).items():
+            where = [pos for _, pos in where]
+            table, parts = casewise.link_records(exam, [linked[pos] for pos in where], min_overlap)
+            exam_rows += table
+            if linked_features is not None:      # the parts are in the order of the exam's lesions: gather every exam lesion's
+                of = [f for pos in where for f in linked_features[pos]]
+                exam_feature_rows += [casewise.exam_lesion_feature_values(exam, e, [f for f, part in zip(of, parts) if part[3] == e])
+                                      for e in range(len(table))]
+            for pos in where:        # the parts come slice after slice; lesions.csv is in the order of the data set
+                n = len(linked[pos].rows)
+                parts_of[pos], parts = parts[:n], parts[n:]
+        return exam_rows, sum(parts_of, []), exam_feature_rows
 
     def get_config(self):
         return self.model_config

@@ -192,3 +192,81 @@ def test_make_dataset_meta(tmp_path, monkeypatch):
 def test_array_dataset_without_meta_unchanged():
     ds = data.ArrayDataset(np.zeros((3, 4, 4, 1)), np.zeros((3, 4, 4)), 2)
     assert [len(b) for b in ds] == [2, 2]
+
+
+# ---- the records of a matched call, the exam grouping and the slice chain (shared by evaluate's passes and predict) -------------
+def _matched_tuple():
+    """what lesion_table_matched returns for two slices: slice 0 has two predicted lesions and one labelled, slice 1 has none"""
+    from dnncancerannotator_amd import _lib
+    rows = np.zeros(2, _lib.LESION_ROW_DTYPE)
+    rows['row'], rows['area'] = [0, 1], [5, 7]
+    true_rows = np.zeros(1, _lib.LESION_ROW_DTYPE)
+    true_rows['area'] = 9
+    links = np.array([(0, 3, 1, 4)], _lib.LESION_LINK_DTYPE)                 # lesion 1 of slice 0 continues row 3 of the slice before
+    true_links = np.array([(0, 2, 0, 6)], _lib.LESION_LINK_DTYPE)
+    pairs = np.array([(0, 0, 0, 2), (0, 0, 1, 3)], _lib.LESION_PAIR_DTYPE)
+    return (rows, np.array([2, 0], np.int32), np.zeros((2, 0, 0), np.uint8), links, true_rows, np.array([1, 0], np.int32),
+            true_links, pairs)
+
+
+def test_slice_records_of_a_matched_call():
+    out = _matched_tuple()
+    first, second = CW.slice_records(out, [('exam/a', np.int64(4)), ('exam/a', np.int64(5))])
+    assert (first.exam, first.slice, second.exam, second.slice) == ('exam/a', 4, 'exam/a', 5) and type(first.slice) is int
+    assert first.rows.tolist() == out[0].tolist() and first.total == 2 and first.links == [(3, 1, 4)]
+    assert first.true_rows.tolist() == out[4].tolist() and first.true_total == 1 and first.true_links == [(2, 0, 6)]
+    assert first.pairs == [(0, 0, 2), (0, 1, 3)]
+    assert len(second.rows) == 0 and second.total == 0 and second.links == [] and len(second.true_rows) == 0
+    assert second.true_total == 0 and second.true_links == [] and second.pairs == []
+    # the four values of lesion_table_linked: one plane, the labelled fields stay None
+    linked = CW.slice_records(out[:4], [('exam/a', 4), ('exam/a', 5)])
+    assert (linked[0].exam, linked[0].slice, linked[0].total, linked[0].links) == ('exam/a', 4, 2, [(3, 1, 4)])
+    assert linked[0].rows.tolist() == out[0].tolist() and linked[0][5:] == (None,) * 4 and linked[1].links == []
+    assert CW.triples(out[7], 'row_true') == [(0, 0, 2), (0, 1, 3)] and all(type(v) is int for t in first.pairs for v in t)
+
+
+def test_by_exam_keeps_the_order_of_the_data_set():
+    recs = [('b', 0), ('a', 0), ('b', 1), ('c', 7), ('a', 1)]                # the slices of b and a come interleaved
+    exams = CW.by_exam(recs)
+    assert list(exams) == ['b', 'a', 'c']
+    assert exams == {'b': [('b', 0), ('b', 1)], 'a': [('a', 0), ('a', 1)], 'c': [('c', 7)]}
+    assert CW.by_exam([]) == {}
+    named = CW.slice_records(_matched_tuple(), [('x', 1), ('y', 1)])
+    assert CW.by_exam(named) == {'x': [named[0]], 'y': [named[1]]}
+
+
+def test_match_records_links_both_planes_and_calls_the_matcher():
+    recs = CW.slice_records(_matched_tuple(), [('e', 4), ('e', 5)])
+    recs = [recs[0]._replace(links=[], true_links=[]), recs[1]]              # the exam's first slice continues nothing
+    seen = []
+    got = CW.match_records(lambda *a, **k: seen.append((a, k)) or 'result', 'e', recs, 2, iou=0.25)
+    (exam, true_slices, pred_slices, true_linked, pred_linked, pairs), kw = seen[0]
+    assert got == 'result' and exam == 'e' and kw == dict(iou=0.25)
+    assert [(s[0], len(s[1]), s[2]) for s in pred_slices] == [(4, 2, 2), (5, 0, 0)]
+    assert [(s[0], len(s[1]), s[2]) for s in true_slices] == [(4, 1, 1), (5, 0, 0)]
+    assert pred_linked == CW.link_lesions('e', pred_slices, [[], []], min_overlap=2) == CW.link_records('e', recs, 2)
+    assert true_linked == CW.link_lesions('e', true_slices, [[], []], min_overlap=2)
+    assert pairs == [[(0, 0, 2), (0, 1, 3)], []]
+    assert CW.match_records(CW.match_exam_lesions, 'e', recs)[0] == ['e', 1, 2, 0, 1, 0, 2, 0]
+
+
+def test_slice_chain(caplog):
+    from dnncancerannotator_amd.engine import _SliceChain
+    chain, dm = _SliceChain('evaluate'), object()
+    # the first slice of a run continues nothing; the same exam and the next number continues; a gap and another exam do not
+    assert chain.continues(dm, [('a', 3), ('a', 4), ('a', 6), ('b', 7), ('b', np.int64(8))]) == [False, True, False, False, True]
+    # the first slice of a second batch continues the last of the first
+    assert chain.continues(dm, [('b', '9'), ('b', 9)]) == [True, False]
+    assert not caplog.records
+    # a re-sized model: a warning, and the chain breaks
+    with caplog.at_level('WARNING'):
+        assert chain.continues(object(), [('b', 10), ('b', 11)]) == [False, True]
+    assert [r.getMessage() for r in caplog.records] == [
+        'evaluate: the model was re-sized before slice 10 of b: it is not linked to the slice before']
+    caplog.clear()
+    other = _SliceChain('predict')
+    first = object()
+    other.continues(first, [('c', 0)])
+    with caplog.at_level('WARNING'):
+        assert other.continues(object(), [('c', 1)]) == [False]
+    assert caplog.records[0].getMessage().startswith('predict: the model was re-sized before slice 1 of c')
