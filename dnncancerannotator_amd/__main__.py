@@ -94,8 +94,8 @@ def build_parser(prog='python3 -m annotator'):
                    help='test-time augmentation: every probability read is the mean over the flip views (flips) or over all eight '
                         'flip / transpose views (d4, square slices only); default: none')
     e.add_argument('--uncertainty', action='store_true', default=argparse.SUPPRESS,
-                   help='with --tta flips / d4: how much the views disagree (their standard deviation per pixel) on wrong and on right '
-                        'pixels: also write uncertainty_results.csv and uncertainty_slices.csv')
+                   help='with --tta flips / d4 (or --ensemble): how much the views disagree (their standard deviation per pixel) on '
+                        'wrong and on right pixels: also write uncertainty_results.csv and uncertainty_slices.csv')
     e.add_argument('--uncertainty_threshold', type=float, nargs='+', default=argparse.SUPPRESS, metavar='T',
                    help='probability threshold(s) of --uncertainty (default: 0.5)')
     e.add_argument('--calibration', action='store_true', default=argparse.SUPPRESS,
@@ -138,6 +138,12 @@ def build_parser(prog='python3 -m annotator'):
                    help='coverage of the intervals of --bootstrap, strictly between 0.5 and 1 (default: 0.95)')
     e.add_argument('--bootstrap_stratified', action='store_true', default=argparse.SUPPRESS,
                    help='--bootstrap with --detection: draw the exams with and without a labelled tumour separately')
+    e.add_argument('--ensemble', nargs='+', default=argparse.SUPPRESS, metavar='MEMBER',
+                   help='average further models on the GPU: MEMBER = RUN_DIR[:STEP], at most 15 (cross-validation folds, or snapshots '
+                        'of one run: --ensemble RUN:800 RUN:900).  Every probability read is the mean over the checkpoint of '
+                        '--save_path (member 0) and each member\'s checkpoint of the step being evaluated, or of its pinned STEP; '
+                        '`loss` stays the loss of member 0\'s untransformed view.  Allows --uncertainty without --tta (the spread '
+                        'between the members) and then also writes ensemble_uncertainty_results.csv')
     p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
     p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
     p.add_argument('--data_path', nargs='+', required=True)
@@ -179,6 +185,12 @@ def build_parser(prog='python3 -m annotator'):
                    help='ranked lesion candidates without a fixed threshold: also write candidates.csv, slice_candidates.csv, with '
                         '--link_slices exam_candidates.csv and with --export_images detection.png (the map a detection challenge asks for)')
     _detection_arguments(p)
+    p.add_argument('--ensemble', nargs='+', default=argparse.SUPPRESS, metavar='MEMBER',
+                   help='average further models on the GPU: MEMBER = RUN_DIR[:STEP], at most 15 (cross-validation folds, or snapshots '
+                        'of one run).  The tables and masks are those of the mean probability over the checkpoint of --save_path '
+                        '(member 0) and each member\'s checkpoint: its pinned STEP, else --step, else its run\'s latest.  Allows '
+                        '--uncertainty without --tta (the spread between the members) and then also writes '
+                        'slice_ensemble_uncertainty.csv')
     return parser
 
 

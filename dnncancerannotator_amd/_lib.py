@@ -255,6 +255,12 @@ SIGNATURES = {
     'dnnca_forward_tta_spread': (C.c_int, [_VP, _FP, C.c_int, C.c_uint, _FP, _FP]),
     'dnnca_tta_spread_of': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, _FP, _FP]),
     'dnnca_get_tta_spread': (C.c_int, [_VP, C.c_int, _FP]),
+    'dnnca_model_set_members': (C.c_int, [_VP, C.c_int]),
+    'dnnca_member_store': (C.c_int, [_VP, C.c_int, _FP, C.c_int64, _FP, C.c_int64]),
+    'dnnca_member_get': (C.c_int, [_VP, C.c_int, _FP, _FP]),
+    'dnnca_forward_ensemble': (C.c_int, [_VP, _FP, C.c_int, C.c_uint, C.c_int, _FP]),
+    'dnnca_get_ensemble_spread': (C.c_int, [_VP, C.c_int, _FP, _FP]),
+    'dnnca_ensemble_of': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_int, C.c_int, C.c_int, _FP, _FP, _FP, _FP]),
     'dnnca_train_step': (C.c_int, [_VP, _FP, _FP, C.c_int, C.c_float, C.POINTER(LossCfg), C.POINTER(StepOut)]),
     'dnnca_eval_step': (C.c_int, [_VP, _FP, _FP, C.c_int, C.POINTER(LossCfg), C.POINTER(StepOut), _FP]),
     'dnnca_dev_alloc': (C.c_int, [C.POINTER(_VP), C.c_size_t]),

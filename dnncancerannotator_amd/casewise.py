@@ -961,6 +961,34 @@ def outcome_summary(outcomes):
     return [len(outcomes)] + _outcome_values(n, q)
 
 
+# `--ensemble ... --uncertainty`: the spread of an ensemble in its two components.  between: how much the members' means disagree;
+# within: the root mean square of the members' own view spreads; total^2 = between^2 + within^2 is what every other file reads
+ENSEMBLE_COMPONENTS = ['between', 'within', 'total']
+ENSEMBLE_UNCERTAINTY_RESULT_COLUMNS = (['slices'] + ['%s_px' % o for o in OUTCOMES] +
+                                       sum([['mean_%s_%s' % (c, o) for o in OUTCOMES + ['wrong', 'right']] + ['%s_wrong_to_right' % c]
+                                            for c in ENSEMBLE_COMPONENTS], []))
+SLICE_ENSEMBLE_UNCERTAINTY_COLUMNS = ['exam', 'slice', 'mean_between', 'max_between', 'mean_within', 'max_within']
+
+
+def ensemble_outcome_summary(between, within, total):
+    """the spread_by_outcome entries of all slices at one threshold on the three planes -> the ensemble_uncertainty_results.csv
+    values: the pixels per outcome (the same on every plane: the classes come from the mean), then per component what
+    outcome_summary gives behind them"""
+    sums = [outcome_summary(list(o)) for o in (between, within, total)]
+    if len({tuple(s[:5]) for s in sums}) != 1:
+        raise ValueError('the three spread planes of an ensemble were classed differently: %s' % [s[:5] for s in sums])
+    return sums[0][:5] + sum([s[5:] for s in sums], [])
+
+
+def slice_ensemble_uncertainty_values(exam, slice_id, between, within):
+    """the slice_ensemble_uncertainty.csv line of one slice from its two planes [h, w] read back: mean (float64) and maximum"""
+    out = [exam, int(slice_id)]
+    for plane in (between, within):
+        plane = np.asarray(plane, np.float32)
+        out += [repr(float(plane.astype(np.float64).mean())), '%.9g' % float(plane.max())]
+    return out
+
+
 def uncertainty_image(spread):
     """float32 spread [h, w] -> uint8 grey: min(255, rint(spread * 510)) (the product is exact in float64)"""
     return np.minimum(255, np.rint(np.asarray(spread, np.float32).astype(np.float64) * UNCERTAINTY_WHITE)).astype(np.uint8)

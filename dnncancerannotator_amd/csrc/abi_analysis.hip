@@ -79,13 +79,12 @@ static int tta_check_plane(int batch, int h, int w, int c) {
     return DNNCA_OK;
 }
 
-// dnnca_forward_tta and, with_spread, dnnca_forward_tta_spread up to their read-back: one inference forward per view, the mean in
-// M->prob and the spread in M->tta_spread
-static int tta_forward(Model* M, const float* x_nhwc, int batch, unsigned views, bool with_spread) {
+// what dnnca_forward_tta*, and dnnca_forward_ensemble for every member, do before their first forward: validate, allocate what the
+// views (and, with_spread, their spread) need, stage the batch.  ks receives the views in ascending order; returns their number in *n
+static int tta_prepare(Model* M, const float* x_nhwc, int batch, unsigned views, bool with_spread, int* ks, int* n) {
     const int H = M->desc.height, W = M->desc.width, C = M->desc.in_channels;
-    int ks[8];
-    const int n = tta_views_of(views, H, W, ks);
-    if (!n) return DNNCA_EINVAL;
+    *n = tta_views_of(views, H, W, ks);
+    if (!*n) return DNNCA_EINVAL;
     if (!x_nhwc) { set_error("tta: null x"); return DNNCA_EINVAL; }
     if (M->outH != H || M->outW != W) {
         set_error("tta: the output (%d x %d) differs from the input (%d x %d)", M->outH, M->outW, H, W);
@@ -97,7 +96,14 @@ static int tta_forward(Model* M, const float* x_nhwc, int batch, unsigned views,
     if (!M->tta_view && views != 1u) DN_TRY(M->alloc((void**)&M->tta_view, plane * C * 4));
     if (with_spread && !M->tta_spread) DN_TRY(M->alloc((void**)&M->tta_spread, plane * 4));
     if (with_spread && !M->tta_mom) DN_TRY(M->alloc((void**)&M->tta_mom, 3 * plane * 4));
-    DN_TRY(stage_inputs(M, batch, x_nhwc, nullptr, false));
+    return stage_inputs(M, batch, x_nhwc, nullptr, false);
+}
+
+// one inference forward per view of the staged batch with the weights that are in place, the mean in M->prob and, with_spread, the
+// spread in M->tta_spread
+static int tta_body(Model* M, int batch, const int* ks, int n, bool with_spread) {
+    const int H = M->desc.height, W = M->desc.width, C = M->desc.in_channels;
+    const size_t plane = (size_t)M->desc.max_batch * H * W;
     const TtaTarget t = {M->prob, with_spread ? M->tta_spread : nullptr, M->tta_mom, plane, batch, H, W, true};
     for (int i = 0; i < n; ++i) {
         const float* x = M->x_stage;                      // view 0 forwards from the staged batch itself
@@ -109,6 +115,13 @@ static int tta_forward(Model* M, const float* x_nhwc, int batch, unsigned views,
         tta_launch_view(M, t, M->logits, ks[i], i, n);
     }
     return DNNCA_OK;
+}
+
+// dnnca_forward_tta and, with_spread, dnnca_forward_tta_spread up to their read-back
+static int tta_forward(Model* M, const float* x_nhwc, int batch, unsigned views, bool with_spread) {
+    int ks[8], n = 0;
+    DN_TRY(tta_prepare(M, x_nhwc, batch, views, with_spread, ks, &n));
+    return tta_body(M, batch, ks, n, with_spread);
 }
 
 int dnnca_forward_tta(void* model, const float* x_nhwc, int batch, unsigned views, float* prob_out) {
@@ -127,6 +140,7 @@ int dnnca_forward_tta_spread(void* model, const float* x_nhwc, int batch, unsign
     DN_TRY(tta_forward(M, x_nhwc, batch, views, true));
     M->tta_spread_valid = true;
     M->tta_spread_batch = batch;
+    M->members.spread_valid = false;
     const size_t npix = (size_t)batch * M->outH * M->outW;
     if (prob_out) HIP_TRY(hipMemcpyAsync(prob_out, M->prob, npix * 4, hipMemcpyDeviceToHost, M->stream));
     if (spread_out) HIP_TRY(hipMemcpyAsync(spread_out, M->tta_spread, npix * 4, hipMemcpyDeviceToHost, M->stream));
@@ -207,6 +221,182 @@ int dnnca_get_tta_spread(void* model, int batch, float* out) {
     HIP_TRY(hipMemcpyAsync(out, M->tta_spread, (size_t)batch * M->outH * M->outW * 4, hipMemcpyDeviceToHost, M->stream));
     HIP_TRY(hipStreamSynchronize(M->stream));
     return DNNCA_OK;
+}
+
+// ---- ensembles (kernels_ensemble.hip) ------------------------------------------------------------------------------------------
+// member `pos` of n joins: floats moved per pixel, as tta_launch_view counts them.  Without between_out: the mean in, es in (from
+// member 1 on), es or the mean out.  With it also: the within spread in (when there is one); e0 out (member 0) or in; sum d and
+// sum d^2 in (from member 2 on) and out (members 1 up to the last but one); sum s^2 in (from member 1 on) and out (up to the last
+// but one); between, within and total out (last member)
+static void ens_launch_join(Model* M, size_t npix, const float* mean_in, const float* within_in, float* run, size_t pitch, int pos, int n,
+                            float* mean_out, float* between_out, float* within_out, float* total_out) {
+    const bool last = pos == n - 1;
+    double moved = 1 + (pos ? 1 : 0) + 1;
+    if (between_out)
+        moved += (within_in ? 1 : 0) + (last && !pos ? 0 : 1) + (pos > 1 ? 2 : 0) + (pos && !last ? 2 : 0) + (pos ? 1 : 0) + (last ? 3 : 1);
+    LAUNCH(M, "ens_join", 4.0 * moved * (double)npix, (between_out ? 12.0 : 2.0) * (double)npix,
+           g_ens_join(M->stream, npix, mean_in, within_in, run, pitch, pos, n, mean_out, between_out, within_out, total_out));
+}
+
+static constexpr int kEnsPlanes = 7;      // es, e0, sum d, sum d^2, sum s^2, between, within (Model::members)
+
+static int member_check(Model* M, int m, const char* who) {
+    if (m < 0 || m >= M->members.n) { set_error("%s: member %d outside 0..%d (dnnca_model_set_members)", who, m, M->members.n - 1); return DNNCA_EINVAL; }
+    return DNNCA_OK;
+}
+static float* member_slot(Model* M, int m) { return M->members.w + (size_t)m * (size_t)(M->nT + M->nS); }
+
+int dnnca_model_set_members(void* model, int n) {
+    MODEL(model);
+    if (n < 0 || n > DNNCA_MAX_MEMBERS) { set_error("dnnca_model_set_members: %d members outside 0..%d", n, DNNCA_MAX_MEMBERS); return DNNCA_EINVAL; }
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    if (M->members.w) HIP_TRY(hipFree(M->members.w));
+    M->members.w = nullptr;
+    M->members.n = 0;
+    M->members.stored = 0;
+    if (n == 0) {
+        if (M->members.planes) HIP_TRY(hipFree(M->members.planes));
+        M->members.planes = nullptr;
+        if (M->members.spread_valid) M->tta_spread_valid = false;      // the two components are gone: so is the total's claim to them
+        M->members.spread_valid = false;
+        return DNNCA_OK;
+    }
+    HIP_TRY(hipMalloc((void**)&M->members.w, (size_t)(n + 1) * (size_t)(M->nT + M->nS) * 4));
+    M->members.n = n;
+    return DNNCA_OK;
+}
+
+int dnnca_member_store(void* model, int m, const float* params, int64_t nT, const float* state, int64_t nS) {
+    MODEL(model);
+    DN_TRY(member_check(M, m, "dnnca_member_store"));
+    if (nT != M->nT || nS != M->nS) {
+        set_error("dnnca_member_store: vectors of %lld and %lld floats, the model has %lld and %lld", (long long)nT, (long long)nS,
+                  (long long)M->nT, (long long)M->nS);
+        return DNNCA_EINVAL;
+    }
+    if (!params || (!state && nS)) { set_error("dnnca_member_store: null vector"); return DNNCA_EINVAL; }
+    float* slot = member_slot(M, m);
+    HIP_TRY(hipMemcpyAsync(slot, params, (size_t)nT * 4, hipMemcpyHostToDevice, M->stream));
+    if (nS) HIP_TRY(hipMemcpyAsync(slot + nT, state, (size_t)nS * 4, hipMemcpyHostToDevice, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    M->members.stored |= 1u << m;
+    return DNNCA_OK;
+}
+
+int dnnca_member_get(void* model, int m, float* params, float* state) {
+    MODEL(model);
+    DN_TRY(member_check(M, m, "dnnca_member_get"));
+    if (!(M->members.stored >> m & 1u)) { set_error("dnnca_member_get: member %d was never stored", m); return DNNCA_ESTATE; }
+    const float* slot = member_slot(M, m);
+    if (params) HIP_TRY(hipMemcpyAsync(params, slot, (size_t)M->nT * 4, hipMemcpyDeviceToHost, M->stream));
+    if (state && M->nS) HIP_TRY(hipMemcpyAsync(state, slot + M->nT, (size_t)M->nS * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return DNNCA_OK;
+}
+
+// (p, state) <- slot `from`, or slot `to` <- (p, state): contents on the model's stream, in order with the forwards around them
+static int member_copy(Model* M, int slot, bool into_model) {
+    float* w = member_slot(M, slot);
+    float *dp = into_model ? M->p : w, *ds = into_model ? M->state : w + M->nT;
+    const float *sp = into_model ? w : M->p, *ss = into_model ? w + M->nT : M->state;
+    HIP_TRY(hipMemcpyAsync(dp, sp, (size_t)M->nT * 4, hipMemcpyDeviceToDevice, M->stream));
+    if (M->nS) HIP_TRY(hipMemcpyAsync(ds, ss, (size_t)M->nS * 4, hipMemcpyDeviceToDevice, M->stream));
+    return DNNCA_OK;
+}
+
+// the members of dnnca_forward_ensemble, one after the other, while the model's own weights wait in the spare slot
+static int ens_members(Model* M, int batch, const int* ks, int nviews, bool with_spread) {
+    const int n = M->members.n;
+    const size_t pitch = (size_t)M->desc.max_batch * M->outH * M->outW, npix = (size_t)batch * M->outH * M->outW;
+    float* run = M->members.planes;
+    const bool member_spread = with_spread && nviews > 1;
+    for (int m = 0; m < n; ++m) {
+        DN_TRY(member_copy(M, m, true));
+        DN_TRY(tta_body(M, batch, ks, nviews, member_spread));
+        ens_launch_join(M, npix, M->prob, member_spread ? M->tta_spread : nullptr, run, pitch, m, n, M->prob,
+                        with_spread ? run + 5 * pitch : nullptr, run + 6 * pitch, M->tta_spread);
+    }
+    return DNNCA_OK;
+}
+
+int dnnca_forward_ensemble(void* model, const float* x_nhwc, int batch, unsigned views, int with_spread, float* prob_out) {
+    MODEL(model);
+    DN_TRY(M->ema_refuse("dnnca_forward_ensemble"));
+    const int n = M->members.n;
+    if (n < 1) { set_error("dnnca_forward_ensemble: the model has no members (dnnca_model_set_members)"); return DNNCA_ESTATE; }
+    for (int m = 0; m < n; ++m)
+        if (!(M->members.stored >> m & 1u)) {
+            set_error("dnnca_forward_ensemble: member %d of %d was never stored (dnnca_member_store)", m, n);
+            return DNNCA_ESTATE;
+        }
+    int ks[8], nviews = 0;
+    // the spread plane carries the total also where a single view leaves no within-member spread to take
+    DN_TRY(tta_prepare(M, x_nhwc, batch, views, with_spread != 0, ks, &nviews));
+    if (!M->members.planes) {
+        const size_t bytes = (size_t)kEnsPlanes * M->desc.max_batch * M->outH * M->outW * 4;
+        HIP_TRY(hipMalloc((void**)&M->members.planes, bytes));
+    }
+    DN_TRY(member_copy(M, n, false));
+    const int rc = ens_members(M, batch, ks, nviews, with_spread != 0);
+    DN_TRY(member_copy(M, n, true));           // whatever a member's forward said, the model's own weights are back
+    DN_TRY(rc);
+    if (with_spread) {
+        M->tta_spread_valid = true;
+        M->tta_spread_batch = batch;
+        M->members.spread_valid = true;
+    }
+    if (prob_out) {
+        HIP_TRY(hipMemcpyAsync(prob_out, M->prob, (size_t)batch * M->outH * M->outW * 4, hipMemcpyDeviceToHost, M->stream));
+        HIP_TRY(hipStreamSynchronize(M->stream));
+        return M->flush_profile();
+    }
+    return DNNCA_OK;
+}
+
+int dnnca_get_ensemble_spread(void* model, int batch, float* between_out, float* within_out) {
+    MODEL(model);
+    DN_TRY(check_batch(M, batch));
+    DN_TRY(tta_spread_plane(M, batch, "dnnca_get_ensemble_spread"));
+    if (!M->members.spread_valid || !M->members.planes) {
+        set_error("dnnca_get_ensemble_spread: the model's spread plane is not an ensemble's (dnnca_forward_ensemble with_spread makes it one)");
+        return DNNCA_ESTATE;
+    }
+    const size_t pitch = (size_t)M->desc.max_batch * M->outH * M->outW, npix = (size_t)batch * M->outH * M->outW;
+    if (between_out) HIP_TRY(hipMemcpyAsync(between_out, M->members.planes + 5 * pitch, npix * 4, hipMemcpyDeviceToHost, M->stream));
+    if (within_out) HIP_TRY(hipMemcpyAsync(within_out, M->members.planes + 6 * pitch, npix * 4, hipMemcpyDeviceToHost, M->stream));
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return DNNCA_OK;
+}
+
+int dnnca_ensemble_of(void* model, const float* means, const float* withins, int n, int batch, int h, int w, float* mean_out,
+                      float* between_out, float* within_out, float* total_out) {
+    MODEL(model);
+    if (n < 1 || n > DNNCA_MAX_MEMBERS) { set_error("ensemble: %d members outside 1..%d", n, DNNCA_MAX_MEMBERS); return DNNCA_EINVAL; }
+    if (!means || !mean_out) { set_error("ensemble: null buffer"); return DNNCA_EINVAL; }
+    const bool spread = between_out != nullptr;
+    if ((within_out != nullptr) != spread || (total_out != nullptr) != spread) {
+        set_error("ensemble: between_out, within_out and total_out go together");
+        return DNNCA_EINVAL;
+    }
+    DN_TRY(check_batch(M, batch));
+    DN_TRY(tta_check_plane(batch, h, w, 1));
+    const size_t npix = (size_t)batch * h * w;
+    // in: the means, then the within spreads; out: mean, between, within, total, then the five running planes, npix floats apart
+    float *in = nullptr, *out = nullptr;
+    DN_TRY(tta_io_buffers(M, npix * n * (withins ? 2 : 1), npix * 9, &in, &out));
+    HIP_TRY(hipMemcpyAsync(in, means, npix * n * 4, hipMemcpyHostToDevice, M->stream));
+    if (withins) HIP_TRY(hipMemcpyAsync(in + npix * n, withins, npix * n * 4, hipMemcpyHostToDevice, M->stream));
+    for (int m = 0; m < n; ++m)
+        ens_launch_join(M, npix, in + npix * m, withins ? in + npix * (n + m) : nullptr, out + 4 * npix, npix, m, n, out,
+                        spread ? out + npix : nullptr, out + 2 * npix, out + 3 * npix);
+    HIP_TRY(hipMemcpyAsync(mean_out, out, npix * 4, hipMemcpyDeviceToHost, M->stream));
+    if (spread) {
+        HIP_TRY(hipMemcpyAsync(between_out, out + npix, npix * 4, hipMemcpyDeviceToHost, M->stream));
+        HIP_TRY(hipMemcpyAsync(within_out, out + 2 * npix, npix * 4, hipMemcpyDeviceToHost, M->stream));
+        HIP_TRY(hipMemcpyAsync(total_out, out + 3 * npix, npix * 4, hipMemcpyDeviceToHost, M->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(M->stream));
+    return M->flush_profile();
 }
 
 // ---- plane inputs: the model's own planes or the caller's --------------------------------------------------------------------

@@ -76,6 +76,17 @@ void g_tta_accumulate(hipStream_t s, const float* src, float* prob, int B, int H
 void g_tta_moments(hipStream_t s, const float* src, float* prob, float* mom, float* spread, size_t plane, int B, int H, int W, int k,
                    bool is_logits, int pos, int n);
 
+// ----------------------------------------------------------------------------- ensembles (kernels_ensemble.hip)
+// Member number `pos` (0 .. n - 1, in launch order) of n joins the ensemble, per pixel of npix.  mean_in: the member's mean
+// probability; within_in: its within-member spread, nullptr for 0.  run: the running planes, `pitch` floats apart: the sum es, the
+// first member's mean e0, sum d, sum d^2 (d = mean_m - e0), sum s_m^2; every member but the last writes them, and without
+// between_out only es is touched.  The last member writes mean_out = es / n (float32 sum in launch order, one division: the
+// operations of g_tta_accumulate) and, with between_out, between = sqrt(max(0, (sum d^2 - (sum d)^2 / n) / n)), within =
+// sqrt(sum s^2 / n) and total = sqrt of the sum of the two variances.  mean_out may be mean_in and total_out may be within_in (a
+// pixel is read and written by one thread); no other buffer may alias another
+void g_ens_join(hipStream_t s, size_t npix, const float* mean_in, const float* within_in, float* run, size_t pitch, int pos, int n,
+                float* mean_out, float* between_out, float* within_out, float* total_out);
+
 void g_l2(hipStream_t s, size_t n, const float* w, float* g, float l2, double* scalars);   // g += 2*l2*w ; penalty += l2*sum w^2
 // writes [loss, positive_rate, weight, ymin, ymax] floats to out5 (device) from the scalar block
 void g_finalize_scalars(hipStream_t s, double* scalars, const dnnca_loss_cfg cfg, double n_label, double inv_batch_hw,

@@ -393,6 +393,14 @@ struct Model {
     float* tta_mom = nullptr;
     bool tta_spread_valid = false;
     int tta_spread_batch = 0;
+    // the ensemble (dnnca_model_set_members, dnnca_forward_ensemble; kernels_ensemble.hip).  w: n + 1 slots of nT + nS floats, one
+    // per member (its trainable vector, then its BatchNorm state) and the spare that keeps the model's own (p, state) while a call
+    // has a member's in their place -- contents, never pointers, as with Ema; stored: bit m set once slot m was filled.  planes:
+    // seven planes [max_batch, H, W] allocated by the first dnnca_forward_ensemble: the running sum es, the first member's mean e0,
+    // sum d, sum d^2 (d = mean_m - e0), sum s_m^2 (written by every member but the last, read by every member but the first), then
+    // between and within (written by the last member alone).  spread_valid: the last call that wrote tta_spread was an ensemble's
+    // (the two components are then valid as long as tta_spread_valid is).  n == 0: off, nothing allocated, no launch differs
+    struct Members { float* w = nullptr; int n = 0; unsigned stored = 0; float* planes = nullptr; bool spread_valid = false; } members;
     // calibration (dnnca_calibration): the device tables, the temperatures and the block partials of the NLL, grown on demand
     void* calib_ws = nullptr;
     size_t calib_ws_bytes = 0;

@@ -101,6 +101,8 @@ Model::~Model() {
     if (accum.a) (void)hipFree(accum.a);
     if (opt.table) (void)hipFree(opt.table);
     if (tta_io) (void)hipFree(tta_io);
+    if (members.w) (void)hipFree(members.w);
+    if (members.planes) (void)hipFree(members.planes);
     if (calib_ws) (void)hipFree(calib_ws);
     if (detect_ws) (void)hipFree(detect_ws);
     if (boot_ws) (void)hipFree(boot_ws);

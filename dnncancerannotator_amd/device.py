@@ -301,6 +301,7 @@ class DeviceModel:
         check(self.lib.dnnca_num_state(self.handle, C.byref(n)))
         self.n_state = n.value
         self._tm_n = 0
+        self.n_members = 0
 
     # ---- life-cycle -------------------------------------------------------------------------------------------
     def close(self):
@@ -536,10 +537,65 @@ class DeviceModel:
         return prob, spread
 
     def last_spread(self, batch):
-        """the spread plane [batch, H, W] of the last forward_tta_spread (an error once it is no longer valid)"""
+        """the spread plane [batch, H, W] of the last forward_tta_spread, or the total spread of the last forward_ensemble(spread=True)
+        (an error once it is no longer valid)"""
         out = np.empty((int(batch), self.in_shape[0], self.in_shape[1]), np.float32)
         check(self.lib.dnnca_get_tta_spread(self.handle, int(batch), fptr(out)))
         return out
+
+    # ---- ensembles (dnnca_model_set_members, dnnca_forward_ensemble) -------------------------------------------------
+    MAX_MEMBERS = 16
+
+    def set_members(self, members):
+        """members: a list of up to 16 (params, state) pairs, the flat vectors of get_params / get_state (what a checkpoint holds);
+        they live on the device inside this model until the next set_members.  An empty list frees them"""
+        members = [(as_f32(p).ravel(), as_f32(s).ravel()) for p, s in members]
+        check(self.lib.dnnca_model_set_members(self.handle, len(members)))
+        for m, (p, s) in enumerate(members):
+            check(self.lib.dnnca_member_store(self.handle, m, fptr(p), p.size, fptr(s) if s.size else None, s.size))
+        self.n_members = len(members)
+
+    def member(self, m):
+        """(params, state) of member m as they are on the device"""
+        p, s = np.empty(self.n_trainable, np.float32), np.empty(self.n_state, np.float32)
+        check(self.lib.dnnca_member_get(self.handle, int(m), fptr(p), fptr(s) if s.size else None))
+        return p, s
+
+    def forward_ensemble(self, x, views=1, spread=False, return_prob=True):
+        """One call per batch for all members (dnnca_forward_ensemble): for each member in turn its weights are copied in, the body of
+        forward_tta (spread and more than one view: forward_tta_spread) runs on the staged batch -- views 1 is the plain forward --
+        and ens_join takes the member in.  Afterwards the probability buffer holds the mean of the members' means and, with spread,
+        the spread plane the total spread (last_spread; its two components: last_ensemble_spread); the model's own weights are back
+        bit for bit.  return_prob=False: the mean stays on the device; returns None"""
+        x = self._check_x(x)
+        B = x.shape[0]
+        prob = np.empty((B, self.in_shape[0], self.in_shape[1], 1), np.float32) if return_prob else None
+        check(self.lib.dnnca_forward_ensemble(self.handle, fptr(x), B, int(views), int(bool(spread)), fptr(prob) if return_prob else None))
+        return prob
+
+    def last_ensemble_spread(self, batch):
+        """(between, within) [batch, H, W] of the last forward_ensemble(spread=True): how much the members' means disagree and the
+        root mean square of their own view spreads; last_spread's total is sqrt(between^2 + within^2)"""
+        between = np.empty((int(batch), self.in_shape[0], self.in_shape[1]), np.float32)
+        within = np.empty_like(between)
+        check(self.lib.dnnca_get_ensemble_spread(self.handle, int(batch), fptr(between), fptr(within)))
+        return between, within
+
+    def ensemble_of(self, means, withins=None, spread=True):
+        """ens_join alone on host planes means [n, B, h, w] (and the members' own spreads withins, same shape; None: zeros); none of
+        the model's planes is touched.  Returns (mean, between, within, total) [B, h, w], or the mean alone with spread=False"""
+        means = as_f32(means)
+        if means.ndim != 4:
+            raise ValueError('ensemble_of: means %s is not [n, B, h, w]' % (means.shape,))
+        if withins is not None:
+            withins = as_f32(withins)
+            if withins.shape != means.shape:
+                raise ValueError('ensemble_of: withins %s against means %s' % (withins.shape, means.shape))
+        n, B, h, w = means.shape
+        outs = [np.empty((B, h, w), np.float32) for _ in range(4 if spread else 1)]
+        ptrs = [fptr(o) for o in outs] + [None] * (4 - len(outs))
+        check(self.lib.dnnca_ensemble_of(self.handle, fptr(means), fptr(withins) if withins is not None else None, n, B, h, w, *ptrs))
+        return tuple(outs) if spread else outs[0]
 
     def train_step(self, x, y, lr, cfg):
         x = self._check_x(x)

@@ -49,12 +49,16 @@ def _element_shape(dataset):
     raise ValueError('empty dataset')
 
 
-def _forward_on_device(dm, xb, tta_mask, spread=False, temperature=None):
+def _forward_on_device(dm, xb, tta_mask, spread=False, temperature=None, ensemble=None):
     """the inference forward whose probabilities stay on the device: the plain one or, with a view mask (tta.mask_of), the test-time
-    augmented one; with `spread` the augmented one that also keeps the views' spread on the device (--uncertainty).  With a
-    temperature (--temperature, check_temperature) the probabilities are then scaled once, in place: every consumer reads the
-    calibrated values; the spread stays that of the unscaled views"""
-    if tta_mask is None:
+    augmented one; with `spread` the augmented one that also keeps the views' spread on the device (--uncertainty).  With
+    `ensemble` (--ensemble: the members are set in dm) one DeviceModel.forward_ensemble in place of the three: the mean over the
+    members of what each of them gives, and with `spread` the total spread.  With a temperature (--temperature,
+    check_temperature) the probabilities are then scaled once, in place: every consumer reads the calibrated values; the spread
+    stays that of the unscaled views"""
+    if ensemble:
+        dm.forward_ensemble(xb, tta_mask or 1, spread=spread, return_prob=False)
+    elif tta_mask is None:
         dm.forward(xb, training=False, return_prob=False)
     elif spread:
         dm.forward_tta_spread(xb, tta_mask, return_prob=False, return_spread=False)
@@ -107,9 +111,10 @@ class _Pass:
                 f.write(casewise.plain_csv(lead + cols, table))
 
 
-def check_uncertainty(uncertainty, tta):
-    """--uncertainty measures the disagreement of the test-time-augmentation views: without views there is nothing to measure"""
-    if uncertainty and tta == tta_modes.NONE:
+def check_uncertainty(uncertainty, tta, ensemble=None):
+    """--uncertainty measures the disagreement of the test-time-augmentation views and of the members of an ensemble: without views
+    and without members there is nothing to measure.  With --ensemble alone the spread is purely between the members"""
+    if uncertainty and tta == tta_modes.NONE and not ensemble:
         raise ValueError('--uncertainty needs the views of test-time augmentation: add --tta flips (or --tta d4 on square slices)')
 
 
@@ -394,6 +399,82 @@ def check_ema_checkpoints(paths):
                 raise ValueError('--weights ema: checkpoint %s holds no weight average (it was trained without deploy_options.ema)' % path)
 
 
+MAX_ENSEMBLE_MEMBERS = 15       # --ensemble: members beside the checkpoint of save_path (DeviceModel.MAX_MEMBERS - 1)
+
+
+def parse_member(text):
+    """one MEMBER of --ensemble, RUN_DIR[:STEP] -> (run directory, pinned step or None: the step being evaluated)"""
+    if isinstance(text, (tuple, list)):
+        run, step = text
+        return str(run), None if step is None else int(step)
+    run, sep, step = str(text).rpartition(':')
+    if sep and run and step.isdigit():
+        return run, int(step)
+    return str(text), None
+
+
+def _index_variables(path):
+    with open(path + '.index') as f:
+        return [(v['name'], tuple(v['shape']), v['trainable'], v['offset']) for v in json.load(f)['variables']]
+
+
+def check_ensemble(save_path, members, steps, weights='raw', param_infos=None):
+    """--ensemble: every member (parse_member) resolved to a checkpoint for every step of save_path that will be read -> {step:
+    [path of each member, in the order given]}.  The checkpoint of save_path itself is member 0 and not in the lists.  A member
+    without a pinned step follows the step; a step of None (predict without --step) stands for the latest checkpoint, of save_path
+    and of every such member alike.  One ValueError that names the first checkpoint that is missing, and one for more than
+    MAX_ENSEMBLE_MEMBERS members, for a member whose variables are not the model's (param_infos: DeviceModel.param_infos(); None:
+    those of save_path's own checkpoint, before a model exists) and, with weights='ema', for one without a weight average
+    (check_ema_checkpoints) -- raised from the index files alone, before any data is read"""
+    members = [parse_member(m) for m in members]
+    if not members:
+        raise ValueError('--ensemble needs at least one member (RUN_DIR[:STEP])')
+    if len(members) > MAX_ENSEMBLE_MEMBERS:
+        raise ValueError('--ensemble takes at most %d members beside the checkpoint of --save_path, got %d' % (MAX_ENSEMBLE_MEMBERS, len(members)))
+    listed = {}
+
+    def ckpts_of(run):
+        if run not in listed:
+            base = os.path.join(run, 'checkpoints')
+            listed[run] = list_ckpts(base) if os.path.isdir(base) else OrderedDict()
+        return listed[run]
+    out = OrderedDict()
+    own = ckpts_of(save_path)
+    for step in steps:
+        paths = []
+        for run, pinned in members:
+            have = ckpts_of(run)
+            want = pinned if pinned is not None else step
+            if want is None and have:
+                want = max(have)
+            if want is None:
+                raise ValueError('--ensemble: no checkpoint under %s/checkpoints' % run)
+            if want not in have:
+                raise ValueError('--ensemble: no checkpoint of step %s under %s/checkpoints (have %s)' % (want, run, sorted(have)))
+            paths.append(have[want])
+        out[step] = paths
+    for step, paths in out.items():          # every member is there: now what the index files say
+        want_vars = param_infos
+        if want_vars is None:
+            mine = max(own) if step is None and own else step
+            want_vars = _index_variables(own[mine]) if mine in own else None
+        if want_vars is not None:
+            want_vars = [(n, tuple(s), t, o) for n, s, t, o in want_vars]
+            for path in paths:
+                if _index_variables(path) != want_vars:
+                    raise ValueError(f'--ensemble: checkpoint {path} does not match the model (every member must have its architecture)')
+        if weights == 'ema':
+            check_ema_checkpoints(paths)
+    return out
+
+
+def read_member(path, weights='raw'):
+    """(params, state) of a checkpoint as flat float32 vectors: what load() would make the parameters and the BatchNorm state"""
+    with np.load(path + '.data-00000-of-00001') as z:
+        return (np.ascontiguousarray(z['ema' if weights == 'ema' else 'params'], np.float32).ravel(),
+                np.ascontiguousarray(z['state'], np.float32).ravel())
+
+
 def _csv_value(v):
     """one value of a train_log.csv line: %.8g, a list of them in brackets (a metric of several thresholds)"""
     if isinstance(v, (list, tuple)):
@@ -591,8 +672,16 @@ class TFKerasModel:
             self._set_ema(bigger)
             bigger.set_ema_state(*average)
         self._set_accumulation(bigger)
+        if getattr(self, '_members', None):       # --ensemble: the members lived in the model the batch outgrew
+            bigger.set_members(self._members)
         self.device_model = bigger
         return True
+
+    def _set_ensemble(self, own_path, paths, weights='raw'):
+        """--ensemble: the checkpoint own_path (member 0: what load() has just put into the model) and those of `paths` are read
+        from their data files and stored in the device model; kept for _ensure_capacity"""
+        self._members = [read_member(p, weights) for p in [own_path] + list(paths)]
+        self.device_model.set_members(self._members)
 
     def _shard(self, x, y=None):
         """Contiguous shard of a global batch for this rank (Keras splits the batch across replicas [TF-2.6]); a batch
@@ -870,14 +959,18 @@ class TFKerasModel:
         return OrderedDict((m.name, _log_value(m)) for m in objs)
 
     # ---- evaluation (engine.py:139-210) ----------------------------------------------------------------------
-    def _evaluate(self, dataset, staged=False, tta_mask=None, temperature=None):
+    def _evaluate(self, dataset, staged=False, tta_mask=None, temperature=None, ensemble=None):
         """keras Model.evaluate(return_dict=True): mean loss over batches + pixel metrics, training=False.  One batch of
         the dataset is one test step per replica: the positive-rate class weight (utils/losses.py:24-27) is taken over the
         whole per-replica batch, never over a chunk of it.
         tta_mask (evaluate --tta): after a batch's test step DeviceModel.forward_tta runs on the same slices, so the pixel and
         region metrics read the mean over the views; `loss` stays the loss of the untransformed view (the test step's own).
         temperature (evaluate --temperature): the probabilities the metrics read are scaled once behind the test step (and behind
-        forward_tta when that runs); `loss` stays the unscaled test step's."""
+        forward_tta when that runs); `loss` stays the unscaled test step's.
+        ensemble (evaluate --ensemble: the members are set in the device model): after a batch's test step
+        DeviceModel.forward_ensemble runs on the same slices in the place of forward_tta, so the metrics read the mean over the
+        members (and their views); `loss` stays the loss of member 0's untransformed view.  Under data parallel every rank holds
+        the same members."""
         cfg_kw = self.loss.device_cfg()
         for m in self.metrics + self.region_metrics:
             m.reset_state()
@@ -890,7 +983,9 @@ class TFKerasModel:
             out = dm_.eval_step(xb, yb, cfg)
             total += float(out.loss) * len(xb)
             count += len(xb)
-            if tta_mask is not None:
+            if ensemble:
+                dm_.forward_ensemble(xb, tta_mask or 1, return_prob=False)
+            elif tta_mask is not None:
                 dm_.forward_tta(xb, tta_mask, return_prob=False)
             if temperature is not None:
                 dm_.scale_temperature(temperature, len(xb))
@@ -1007,7 +1102,8 @@ class TFKerasModel:
              visualize_attribution=False, attribution_steps=None, attribution_baseline=None, weights='raw', detection_ds=None,
              detection=False, detection_min_confidence=None, detection_factor=None, detection_max_candidates=None,
              detection_min_area=None, detection_rounds=None, detection_iou=None, detection_link_min_overlap=None,
-             detection_max_lesions=None, bootstrap=None, bootstrap_seed=None, bootstrap_level=None, bootstrap_stratified=False):
+             detection_max_lesions=None, bootstrap=None, bootstrap_seed=None, bootstrap_level=None, bootstrap_stratified=False,
+             ensemble=None):
         """weights (`evaluate --weights ema`): every checkpoint is loaded with its averaged weights as the parameters (load(...,
         weights='ema')); everything downstream reads that model unchanged.  Checkpoints without an average are an error that names
         the first, raised before anything is evaluated.
@@ -1048,8 +1144,16 @@ class TFKerasModel:
         times on the device (DeviceModel.bootstrap_detection / bootstrap_sums, once per checkpoint and threshold) and write
         detection_bootstrap.csv, detection_bootstrap_replicates.csv and exam_lesion_bootstrap.csv under <export_path>/<tag>/: per
         metric the estimate, and mean, deviation and the bootstrap_level interval of its replicates.  bootstrap_stratified draws
-        within the exams with and without a labelled tumour (detection only).  Every other file is what it is without it."""
-        check_uncertainty(uncertainty, tta)
+        within the exams with and without a labelled tumour (detection only).  Every other file is what it is without it.
+        ensemble (`evaluate --ensemble MEMBER [MEMBER ...]`, MEMBER = RUN_DIR[:STEP], at most 15): every probability read -- by
+        the pixel and region metrics, the Visualizer and every extra pass -- is the mean over the checkpoint of save_path (member
+        0) and the members' checkpoints of the same step (or of their pinned step), each under the tta mode when one is given
+        (DeviceModel.forward_ensemble, one call per batch; check_ensemble resolves and checks every member before anything is
+        evaluated).  The evaluation then runs batch by batch; `loss`, --visualize_sensitivity and --visualize_attribution stay
+        those of member 0's plain forward.  With uncertainty (which --ensemble allows without a tta mode) the spread every file
+        reads is the total over members and views, and ensemble_uncertainty_results.csv is written too: the mean between-member,
+        within-member and total spread per pixel outcome.  None: nothing new runs."""
+        check_uncertainty(uncertainty, tta, ensemble)
         bootstrap = check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level, bootstrap_stratified, detection, exam_lesions)
         detection = check_detection(detection, detection_min_confidence, detection_factor, detection_max_candidates, detection_min_area,
                                     detection_rounds, detection_iou, detection_link_min_overlap, detection_max_lesions)
@@ -1065,13 +1169,22 @@ class TFKerasModel:
         if check_weights(weights) == 'ema':
             check_ema_checkpoints(select_ckpts(self.get_ckpts(os.path.join(save_path, 'checkpoints')), min_interval, step_range).values())
             load_kw = dict(weights='ema')
+        visited = select_ckpts(self.get_ckpts(os.path.join(save_path, 'checkpoints')), min_interval, step_range) if ensemble else {}
+        if ensemble:
+            check_ensemble(save_path, ensemble, list(visited), weights)
         tta_mask = None if tta == tta_modes.NONE else tta_modes.mask_of(tta, *_element_shape(dataset)[1:3])
         self._build(dataset)
+        member_paths = check_ensemble(save_path, ensemble, list(visited), weights, self.device_model.param_infos()) if ensemble else {}
+        if ensemble:
+            logging.info('evaluate --ensemble: %d members beside %s; the evaluation runs batch by batch (the staged ring has no '
+                         'ensemble) and `loss` stays the loss of member 0\'s untransformed view', len(ensemble), save_path)
         if tta_mask is not None:
             logging.info('evaluate --tta %s: the evaluation runs batch by batch (the staged ring has no test-time augmentation)', tta)
         if temperature is not None:
             logging.info('evaluate --temperature %g: the evaluation runs batch by batch (the staged ring does not scale)', temperature)
         more = {} if temperature is None else dict(temperature=temperature)     # the passes get the keyword only with a temperature
+        if ensemble:                         # and that of --ensemble only with members
+            more['ensemble'] = True
         ckpt_path = os.path.join(save_path, 'checkpoints')
         if not export_path:
             export_path = os.path.join(save_path, 'tfevents')
@@ -1117,7 +1230,8 @@ class TFKerasModel:
                    ('surface_slices.csv', lead, C.SURFACE_SLICE_COLUMNS)]),
             _Pass(on(uncertainty, uncertainty_ds),
                   lambda step: self._uncertainty_pass(uncertainty_ds, step, [float(t) for t in uncertainty_thresholds], tta_mask, **more),
-                  [('uncertainty_results.csv', lead, C.UNCERTAINTY_RESULT_COLUMNS), ('uncertainty_slices.csv', lead, C.UNCERTAINTY_SLICE_COLUMNS)]),
+                  [('uncertainty_results.csv', lead, C.UNCERTAINTY_RESULT_COLUMNS), ('uncertainty_slices.csv', lead, C.UNCERTAINTY_SLICE_COLUMNS)] +
+                  ([('ensemble_uncertainty_results.csv', lead, C.ENSEMBLE_UNCERTAINTY_RESULT_COLUMNS)] if ensemble else [])),
             _Pass(on(calibration, calibration_ds),
                   lambda step: self._calibration_pass(calibration_ds, step, calibration_bins, calibration_grid, tta_mask, **more),
                   [('calibration_results.csv', ['step'], C.CALIBRATION_RESULT_COLUMNS),
@@ -1140,7 +1254,9 @@ class TFKerasModel:
                 continue
             previous_step = ckpt_step
             self.load(ckpt_path_, **load_kw)
-            rows[ckpt_step] = self._evaluate(dataset, staged=True) if tta_mask is None and temperature is None else \
+            if ensemble:
+                self._set_ensemble(ckpt_path_, member_paths[ckpt_step], weights)
+            rows[ckpt_step] = self._evaluate(dataset, staged=True) if tta_mask is None and not more else \
                 self._evaluate(dataset, staged=False, tta_mask=tta_mask, **more)
             if visualize:
                 self._visualize(viz_ds, ckpt_step, viz_root, export_csv, export_images, overlay, casewise_rows, writer,
@@ -1170,7 +1286,7 @@ class TFKerasModel:
         return rows
 
     def _visualize(self, viz_ds, step, root, export_csv, export_images, overlay, casewise_rows, writer, sensitivity=False,
-                   tta_mask=None, temperature=None, attribution=None):
+                   tta_mask=None, temperature=None, attribution=None, ensemble=None):
         """One Visualizer pass (callbacks.py process_batch / _emit) over viz_ds batches (x, y, paths, sliceIDs): forward
         (training=False), the per-slice region counts (export_csv), the composite images (export_images), then the files.  The
         probabilities stay on the device; only the counts and the uint8 images come back.  casewise_rows gains one row per slice,
@@ -1182,7 +1298,7 @@ class TFKerasModel:
         spec = casewise.device_spec()
         attr_shares, attr_gaps = [], []
         names = casewise.column_names()
-        for dm, xb, yb, pk in self._forwarded_splits(viz_ds, tta_mask, temperature=temperature):
+        for dm, xb, yb, pk in self._forwarded_splits(viz_ds, tta_mask, temperature=temperature, **self._with(ensemble)):
             tags = [casewise.tag_of(p, k) for p, k in pk]
             if export_csv:
                 counts = dm.region_confusion_slices(yb, [spec])
@@ -1222,7 +1338,12 @@ class TFKerasModel:
         if attribution:
             attribution[2].append([int(step)] + casewise.attribution_summary(attribution[0], attribution[1], attr_shares, attr_gaps))
 
-    def _forwarded_splits(self, ds, tta_mask, spread=False, temperature=None, labels=True):
+    @staticmethod
+    def _with(ensemble):
+        """the keyword of --ensemble for _forwarded_splits: it travels only with the flag"""
+        return dict(ensemble=True) if ensemble else {}
+
+    def _forwarded_splits(self, ds, tta_mask, spread=False, temperature=None, labels=True, ensemble=None):
         """The one walk over an analysis data set, ds batches (x, y, paths, sliceIDs) or, with labels=False, annotate's (x, ...,
         paths, sliceIDs), where a label in between is never looked at: empty batches skipped, the model grown to the batch, the
         batch split by max_batch and every split forwarded with its probabilities left on the device (_forward_on_device).
@@ -1236,10 +1357,11 @@ class TFKerasModel:
             dm = self.device_model
             for i in range(0, len(x), dm.max_batch):
                 xb, yb = x[i:i + dm.max_batch], None if y is None else y[i:i + dm.max_batch]
-                _forward_on_device(dm, xb, tta_mask, spread=spread, temperature=temperature)
+                _forward_on_device(dm, xb, tta_mask, spread=spread, temperature=temperature, **self._with(ensemble))
                 yield dm, xb, yb, list(zip(paths[i:i + dm.max_batch], ids[i:i + dm.max_batch]))
 
-    def _exam_lesion_pass(self, ds, step, thresholds, iou, min_overlap, kw, tta_mask=None, temperature=None, bootstrap=None):
+    def _exam_lesion_pass(self, ds, step, thresholds, iou, min_overlap, kw, tta_mask=None, temperature=None, bootstrap=None,
+                          ensemble=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --exam_lesions`: per max_batch split one forward whose
         probabilities stay on the device and one DeviceModel.lesion_table_matched per threshold; then per threshold and exam
         casewise.link_lesions on either plane and casewise.match_exam_lesions.  Returns the new lines of (exam_lesion_results.csv,
@@ -1253,7 +1375,7 @@ class TFKerasModel:
         several = len(thresholds) > 1
         found = [[] for _ in thresholds]     # per threshold: the casewise.SliceRecord of every slice
         chain, tail, carry_of = _SliceChain('evaluate'), None, None
-        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature):
+        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature, **self._with(ensemble)):
             continues = chain.continues(dm, pk)
             for ti, thr in enumerate(thresholds):
                 if continues[0] and carry_of != ti:
@@ -1280,7 +1402,7 @@ class TFKerasModel:
                                                                          bootstrap)]
         return (results, cases, matches, intervals) if bootstrap else (results, cases, matches)
 
-    def _detection_pass(self, ds, step, det, tta_mask=None, temperature=None, bootstrap=None):
+    def _detection_pass(self, ds, step, det, tta_mask=None, temperature=None, bootstrap=None, ensemble=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --detection`: per max_batch split one forward whose
         probabilities stay on the device, DeviceModel.detection_map in place (the buffer then holds the map) and one
         DeviceModel.lesion_table_matched on it (casewise.detection_table_args: the rows are the candidates, max_prob their
@@ -1292,7 +1414,7 @@ class TFKerasModel:
         kw = casewise.detection_table_args(det['cfg'], det['max_lesions'])
         found, exhausted = [], 0             # the casewise.SliceRecord of every slice
         chain = _SliceChain('evaluate')
-        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature):
+        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature, **self._with(ensemble)):
             continues = chain.continues(dm, pk)
             _, map_records = dm.detection_map(len(xb), **det['cfg'])
             exhausted += int(map_records['exhausted'].sum())
@@ -1316,7 +1438,7 @@ class TFKerasModel:
             replicates = [lead + casewise.detection_replicate_line(i, r, v) for i, (r, v) in enumerate(zip(rows, values))]
         return tables + (intervals, replicates)
 
-    def _surface_pass(self, ds, step, thresholds, percentile, kw, tta_mask=None, temperature=None):
+    def _surface_pass(self, ds, step, thresholds, percentile, kw, tta_mask=None, temperature=None, ensemble=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --surface_distances`: per max_batch split one forward whose
         probabilities stay on the device and one DeviceModel.surface_distances per threshold; only the counts and the boundary
         pixels' squared distances come back.  Then per threshold casewise.surface_slice_values per slice, surface_exam_values per
@@ -1324,7 +1446,7 @@ class TFKerasModel:
         (surface_results.csv, surface_cases.csv, surface_slices.csv), each led by step and threshold.  No slice depends on another:
         nothing is carried between calls."""
         found = [[] for _ in thresholds]     # per threshold and slice: (exam, slice, counts, d2 of the prediction, d2 of the label)
-        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature):
+        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature, **self._with(ensemble)):
             for ti, thr in enumerate(thresholds):
                 counts, samples, _ = dm.surface_distances(yb, batch=len(xb), threshold=thr, **kw)
                 for b, (p, k) in enumerate(pk):
@@ -1341,32 +1463,43 @@ class TFKerasModel:
             results.append(lead + casewise.surface_summary(slice_values, exam_values))
         return results, cases, slices
 
-    def _uncertainty_pass(self, ds, step, thresholds, tta_mask, temperature=None):
+    def _uncertainty_pass(self, ds, step, thresholds, tta_mask, temperature=None, ensemble=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --tta MODE --uncertainty`: per max_batch split one
         DeviceModel.forward_tta_spread whose mean and spread stay on the device and one DeviceModel.spread_by_outcome for all
         thresholds (in runs of 64); only the counts and sums per outcome come back.  Returns the new lines of
-        (uncertainty_results.csv, uncertainty_slices.csv), each led by step and threshold."""
+        (uncertainty_results.csv, uncertainty_slices.csv), each led by step and threshold.
+        ensemble (--ensemble): the forward is DeviceModel.forward_ensemble and the spread those two files read the total; the
+        between- and within-member planes are then read back with the mean and go through spread_by_outcome's plane inputs too,
+        and a third table comes back, the new lines of ensemble_uncertainty_results.csv."""
         found = [[] for _ in thresholds]     # per threshold and slice: (exam, slice, outcome entry)
-        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, spread=True, temperature=temperature):
+        parts = [[[] for _ in thresholds] for _ in range(2)] if ensemble else []      # between, within: per threshold the outcome entries
+        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, spread=True, temperature=temperature, **self._with(ensemble)):
+            y = yb.reshape(len(xb), *yb.shape[1:3])
+            planes = (dm.last_prob(len(xb)),) + dm.last_ensemble_spread(len(xb)) if ensemble else None
             for t0 in range(0, len(thresholds), 64):
-                out = dm.spread_by_outcome(yb.reshape(len(xb), *yb.shape[1:3]), thresholds[t0:t0 + 64], batch=len(xb))
+                out = dm.spread_by_outcome(y, thresholds[t0:t0 + 64], batch=len(xb))
                 for ti, per_slice in enumerate(out, t0):
                     found[ti] += [(p, int(k), o) for (p, k), o in zip(pk, per_slice)]
-        results, slices = [], []
-        for thr, mine in zip(thresholds, found):
+                for part, plane in zip(parts, planes[1:] if ensemble else ()):
+                    for ti, per_slice in enumerate(dm.spread_by_outcome(y, thresholds[t0:t0 + 64], prob=planes[0], spread=plane), t0):
+                        part[ti] += list(per_slice)
+        results, slices, components = [], [], []
+        for ti, (thr, mine) in enumerate(zip(thresholds, found)):
             lead = [int(step), repr(thr)]
             slices += [lead + casewise.outcome_slice_values(*rec) for rec in mine]
             results.append(lead + casewise.outcome_summary([rec[2] for rec in mine]))
-        return results, slices
+            if ensemble:
+                components.append(lead + casewise.ensemble_outcome_summary(parts[0][ti], parts[1][ti], [rec[2] for rec in mine]))
+        return (results, slices, components) if ensemble else (results, slices)
 
-    def _calibration_pass(self, ds, step, n_bins, temperatures, tta_mask=None, temperature=None):
+    def _calibration_pass(self, ds, step, n_bins, temperatures, tta_mask=None, temperature=None, ensemble=None):
         """One pass over ds batches (x, y, paths, sliceIDs) for `evaluate --calibration`: per max_batch split one forward whose
         probabilities stay on the device and one DeviceModel.calibration for all temperatures; only the integer tables and the NLL
         sums come back.  Returns the new lines of (calibration_results.csv, calibration_bins.csv, calibration_slices.csv), each led
         by step; the pooled values come from the tables and NLL rows of all slices summed (casewise.calibration_summary)."""
         at_1 = [float(t) for t in temperatures].index(1.0)
         bins, totals, nll, slices = [], [], [], []
-        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature):
+        for dm, xb, yb, pk in self._forwarded_splits(ds, tta_mask, temperature=temperature, **self._with(ensemble)):
             b, t, n = dm.calibration(yb.reshape(len(xb), *yb.shape[1:3]), n_bins, temperatures, batch=len(xb))
             bins.append(b), totals.append(t), nll.append(n)
             slices += [[int(step)] + casewise.calibration_slice_values(p, k, b[j], t[j], n[j, at_1]) for j, (p, k) in enumerate(pk)]
@@ -1390,7 +1523,7 @@ class TFKerasModel:
                  max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
                  temperature=None, lesion_features=False, feature_bins=None, feature_ring=None, weights='raw', detection_map=False,
                  detection_min_confidence=None, detection_factor=None, detection_max_candidates=None, detection_min_area=None,
-                 detection_rounds=None, detection_link_min_overlap=None, detection_max_lesions=None):
+                 detection_rounds=None, detection_link_min_overlap=None, detection_max_lesions=None, ensemble=None):
         """`annotator predict`: the lesions of slices that have no label.  Loads checkpoint `step` of save_path (None: the latest);
         per batch (x, paths, sliceIDs) of `dataset` (make_dataset(..., include_meta=True, labels=False)) one forward whose
         probabilities stay on the device, then DeviceModel.lesion_table: threshold, filter_size x filter_size opening, components
@@ -1428,8 +1561,14 @@ class TFKerasModel:
         of its own, so the candidates' links do not disturb those of the lesions.  candidates.csv (the columns of lesions.csv plus
         confidence), slice_candidates.csv (candidates, rounds, dropped, exhausted per slice), with link_slices exam_candidates.csv
         and with export_images <exam>/<slice>/detection.png (8-bit grey, rint(D * 255): only then does a map leave the device) are
-        written beside the other files, which are what they are without the flag; the returned dict gains 'candidates'."""
-        check_uncertainty(uncertainty, tta)
+        written beside the other files, which are what they are without the flag; the returned dict gains 'candidates'.
+        ensemble (`predict --ensemble MEMBER [MEMBER ...]`, MEMBER = RUN_DIR[:STEP], at most 15): the one forward per chunk is
+        DeviceModel.forward_ensemble over the checkpoint of save_path (member 0) and the members' checkpoints -- of their pinned
+        step, else of `step`, else their run's latest -- each under the tta mode when one is given; every table and mask is that
+        of the mean over the members.  With uncertainty (which --ensemble allows without a tta mode) the spread every file reads
+        is the total over members and views, and slice_ensemble_uncertainty.csv is written too: per slice the mean and largest
+        between-member and within-member spread (the two planes leave the device only then).  None: nothing new runs."""
+        check_uncertainty(uncertainty, tta, ensemble)
         det = check_detection(detection_map, detection_min_confidence, detection_factor, detection_max_candidates, detection_min_area,
                               detection_rounds, None, detection_link_min_overlap, detection_max_lesions, flag='--detection_map')
         check_weights(weights)
@@ -1438,11 +1577,18 @@ class TFKerasModel:
         if self.ctx.world > 1:
             raise RuntimeError('annotate runs in a single process (WORLD_SIZE is %d): start it without the launcher' % self.ctx.world)
         tta_mask = None if tta == tta_modes.NONE else tta_modes.mask_of(tta, *_element_shape(dataset)[1:3])
+        if ensemble:
+            check_ensemble(save_path, ensemble, [step], weights)
         self._build(dataset)
+        member_paths = check_ensemble(save_path, ensemble, [step], weights, self.device_model.param_infos())[step] if ensemble else None
         step = self._load_step(save_path, step, weights)
+        if ensemble:
+            self._set_ensemble(self.get_ckpts(os.path.join(save_path, 'checkpoints'))[step], member_paths, weights)
         features = dict(bins=feature_bins, ring=feature_ring) if lesion_features else None
         modalities = casewise.modality_names(getattr(dataset, 'slice_types', None), _element_shape(dataset)[3]) if lesion_features else None
         scale = {} if temperature is None else dict(temperature=temperature)      # the forward gets the keyword only with a temperature
+        scale.update(self._with(ensemble))   # and that of --ensemble only with members
+        component_rows = []                  # ensemble + uncertainty: the lines of slice_ensemble_uncertainty.csv
         lesion_rows, slice_rows, lesion_spread_rows, slice_spread_rows = [], [], [], []
         feature_rows, linked_features = [], []       # linked_features: beside `linked`, every slice's feature records per lesion
         candidate_rows, slice_candidate_rows, candidates_linked = [], [], []         # detection_map: as lesion_rows / slice_rows / linked
@@ -1455,6 +1601,9 @@ class TFKerasModel:
                                                  min_area=min_area, max_lesions=max_lesions, mask=bool(export_images)),
                                         continues, uncertainty, features)
                 spread = dm.last_spread(len(xb)) if uncertainty and export_images else None
+                if ensemble and uncertainty:
+                    component_rows += [casewise.slice_ensemble_uncertainty_values(p, k, b_, w_)
+                                       for (p, k), b_, w_ in zip(pk, *dm.last_ensemble_spread(len(xb)))]
                 if det:                              # last: from here on the buffer holds the map
                     for table, new in zip((candidate_rows, slice_candidate_rows, candidates_linked),
                                           self._candidate_tables(dm, xb, pk, det, continues, writer, output)):
@@ -1489,6 +1638,8 @@ class TFKerasModel:
         if uncertainty:
             tables += [('lesion_uncertainty.csv', casewise.LESION_UNCERTAINTY_COLUMNS, lesion_spread_rows),
                        ('slice_uncertainty.csv', casewise.SLICE_UNCERTAINTY_COLUMNS, slice_spread_rows)]
+            if ensemble:
+                tables.append(('slice_ensemble_uncertainty.csv', casewise.SLICE_ENSEMBLE_UNCERTAINTY_COLUMNS, component_rows))
         if lesion_features:
             tables.append(('lesion_features.csv', casewise.lesion_feature_columns(modalities), feature_rows))
         if link_slices:

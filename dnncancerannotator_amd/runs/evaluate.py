@@ -16,8 +16,8 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
              attribution_steps=None, attribution_baseline=None, weights='raw', detection=False, detection_min_confidence=None,
              detection_factor=None, detection_max_candidates=None, detection_min_area=None, detection_rounds=None, detection_iou=None,
              detection_link_min_overlap=None, detection_max_lesions=None, bootstrap=None, bootstrap_seed=None, bootstrap_level=None,
-             bootstrap_stratified=False):
-    engine.check_uncertainty(uncertainty, tta)       # before anything is read
+             bootstrap_stratified=False, ensemble=None):
+    engine.check_uncertainty(uncertainty, tta, ensemble)       # before anything is read
     resampling = engine.check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level, bootstrap_stratified, detection, exam_lesions)
     detection_values = dict(detection_min_confidence=detection_min_confidence, detection_factor=detection_factor,
                             detection_max_candidates=detection_max_candidates, detection_min_area=detection_min_area,
@@ -27,6 +27,10 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
     if engine.check_weights(weights) == 'ema':       # likewise: the index of every checkpoint that will be evaluated
         engine.check_ema_checkpoints(engine.select_ckpts(engine.list_ckpts(os.path.join(save_path, 'checkpoints')), min_interval,
                                                          step_range).values())
+    if ensemble:                         # likewise: every member's checkpoint for every step that will be evaluated
+        ensemble = [engine.parse_member(m) for m in ensemble]
+        visited = engine.select_ckpts(engine.list_ckpts(os.path.join(save_path, 'checkpoints')), min_interval, step_range)
+        engine.check_ensemble(save_path, ensemble, list(visited), weights)
     attribution = engine.check_attribution(visualize_attribution, attribution_steps, attribution_baseline, export_csv, export_images)
     scaled = engine.check_temperature(temperature)   # likewise; None without the flag and with --temperature 1
     if calibration:
@@ -63,6 +67,8 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
         more['weights'] = 'ema'
     if detection:                        # and those of --detection only with the flag
         more.update(detection_ds=meta_ds, detection=True, **detection_values)
+    if ensemble:                         # and that of --ensemble only with members
+        more['ensemble'] = ensemble
     if resampling:                       # and those of --bootstrap
         more.update(bootstrap=resampling['replicates'], bootstrap_seed=resampling['seed'], bootstrap_level=resampling['level'],
                     bootstrap_stratified=resampling['stratified'])

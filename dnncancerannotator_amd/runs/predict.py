@@ -4,8 +4,9 @@ exam_lesion_parts.csv: the lesions joined through the slices of an exam; with --
 slice_uncertainty.csv and uncertainty.png: how much the views disagree; with --temperature T every table reads the probabilities
 scaled by T; with --lesion_features also lesion_features.csv and, with --link_slices, exam_lesion_features.csv: outline, axes and
 per modality the intensities in and around every lesion; with --detection_map also candidates.csv, slice_candidates.csv, with
---link_slices exam_candidates.csv and with --export_images detection.png: ranked lesion candidates without a fixed threshold;
-engine.TFKerasModel.annotate)."""
+--link_slices exam_candidates.csv and with --export_images detection.png: ranked lesion candidates without a fixed threshold; with
+--ensemble MEMBER ... every table reads the mean probability over the members' checkpoints, and with --uncertainty also
+slice_ensemble_uncertainty.csv is written; engine.TFKerasModel.annotate)."""
 
 import os
 
@@ -17,8 +18,8 @@ def predict(save_path, data_path, output, config=None, step=None, threshold=0.5,
             max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
             temperature=None, lesion_features=False, feature_bins=None, feature_ring=None, weights='raw', detection_map=False,
             detection_min_confidence=None, detection_factor=None, detection_max_candidates=None, detection_min_area=None,
-            detection_rounds=None, detection_link_min_overlap=None, detection_max_lesions=None):
-    engine.check_uncertainty(uncertainty, tta)       # before anything is read
+            detection_rounds=None, detection_link_min_overlap=None, detection_max_lesions=None, ensemble=None):
+    engine.check_uncertainty(uncertainty, tta, ensemble)       # before anything is read
     detection_values = dict(detection_min_confidence=detection_min_confidence, detection_factor=detection_factor,
                             detection_max_candidates=detection_max_candidates, detection_min_area=detection_min_area,
                             detection_rounds=detection_rounds, detection_link_min_overlap=detection_link_min_overlap,
@@ -29,6 +30,9 @@ def predict(save_path, data_path, output, config=None, step=None, threshold=0.5,
         ckpts = engine.list_ckpts(os.path.join(save_path, 'checkpoints'))
         if ckpts and (step is None or step in ckpts):          # (a missing checkpoint is annotate's error, as without the flag)
             engine.check_ema_checkpoints([ckpts[max(ckpts) if step is None else step]])
+    if ensemble:                         # likewise: every member's checkpoint (a missing one of save_path is annotate's error)
+        ensemble = [engine.parse_member(m) for m in ensemble]
+        engine.check_ensemble(save_path, ensemble, [step], weights)
     casewise.check_features(lesion_features, feature_bins, feature_ring)      # likewise
     scaled = engine.check_temperature(temperature)   # likewise; None without the flag and with --temperature 1
     if link_min_overlap < 1:
@@ -47,6 +51,8 @@ def predict(save_path, data_path, output, config=None, step=None, threshold=0.5,
         more.update(lesion_features=True, feature_bins=feature_bins, feature_ring=feature_ring)
     if weights == 'ema':                 # and the keyword of --weights only with the averaged weights
         more['weights'] = 'ema'
+    if ensemble:                         # and that of --ensemble only with members
+        more['ensemble'] = ensemble
     if detection_map:                    # and those of --detection_map only with the flag
         more.update(detection_map=True, **detection_values)
     model = engine.TFKerasModel(config)

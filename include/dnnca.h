@@ -268,6 +268,45 @@ int dnnca_forward_tta_spread(void* model, const float* x_nhwc, int batch, unsign
 int dnnca_tta_spread_of(void* model, const float* vals, int batch, int h, int w, unsigned views, int is_logits, float* prob_out,
                         float* spread_out);
 int dnnca_get_tta_spread(void* model, int batch, float* out);
+/* ---- ensembles (`evaluate --ensemble`, `predict --ensemble`; the reference has none) ---------------------------------------------------
+ * The members of an ensemble (cross-validation folds, snapshots of one run) are weight sets of ONE architecture that live on the
+ * device inside the one model: no second model, no second stream, one set of activations.
+ *   dnnca_model_set_members  n in 0..DNNCA_MAX_MEMBERS; allocates n + 1 slots of num_trainable + num_state floats (the members and
+ *                            the spare that keeps the model's own weights during a call) and forgets every member stored before;
+ *                            0 frees the slots and the ensemble's planes.  Waits for the stream
+ *   dnnca_member_store       member m <- the host vectors params [nT] and state [nS] (the flat vectors of dnnca_get_params /
+ *                            dnnca_get_state, what a checkpoint holds); state may be NULL when nS == 0.  Synchronises
+ *   dnnca_member_get         reads member m back (either output may be NULL); DNNCA_ESTATE for a slot never stored
+ * dnnca_forward_ensemble stages x as dnnca_forward does, saves the model's own (p, state) to the spare slot and then, for every
+ * member in ascending order: copies the member's vectors over (p, state) on the model's stream (device to device; nothing is cached
+ * from the weights, as dnnca_set_params shows), runs the body of dnnca_forward_tta (with_spread and more than one view: of
+ * dnnca_forward_tta_spread) on the staged batch -- views == 1 is the plain forward --, so that the probability buffer and the spread
+ * plane hold bit for bit what those calls give with the member's weights loaded, and launches ens_join.  After the last member
+ * (p, state) are put back, bit for bit, and
+ *     prob    = (sum over the members, ascending, in float32, of mean_m) / n                       (float32 division)
+ * and, with_spread, the model's spread plane (valid for `batch`, exactly as after dnnca_forward_tta_spread) holds
+ *     total   = sqrt(between^2 + within^2)                  (the law of total variance over the n x V forwards)
+ *     between = sqrt(max(0, (sum d^2 - (sum d)^2 / n) / n)),  d = mean_m - mean_0        (exactly 0 for n == 1 and for equal members)
+ *     within  = sqrt((sum s_m^2) / n),  s_m the member's spread over its views           (exactly 0 for one view)
+ * each within 2^-18 want + 2^-23 of the float64 value `want` of the same float32 inputs.  Every consumer of the probabilities and of
+ * the spread plane reads them unchanged.  No atomics: bit-identical from run to run.  The planes of running state are allocated by
+ * the first call (a model without members allocates none).  prob_out: NULL, or host [batch, H, W]; synchronises when it is given.
+ * DNNCA_EINVAL: what dnnca_forward_tta refuses.  DNNCA_ESTATE, with nothing launched: no members; a member slot that was never
+ * stored; the averaged weights exchanged in (dnnca_ema_exchange).
+ *   dnnca_get_ensemble_spread  between and within of the last dnnca_forward_ensemble with_spread, host [batch, H, W] each (either
+ *                              may be NULL); DNNCA_ESTATE once the spread plane is no longer valid or is not an ensemble's
+ *   dnnca_ensemble_of          ens_join alone on host planes means [n, batch, h, w] and withins (same shape, or NULL for zeros),
+ *                              1 <= n <= DNNCA_MAX_MEMBERS, any plane size; none of the model's planes is touched.  mean_out is
+ *                              required; between_out, within_out and total_out go together (all three, or all NULL for the mean
+ *                              alone); synchronises */
+#define DNNCA_MAX_MEMBERS 16
+int dnnca_model_set_members(void* model, int n);
+int dnnca_member_store(void* model, int m, const float* params, int64_t nT, const float* state, int64_t nS);
+int dnnca_member_get(void* model, int m, float* params /* nullable */, float* state /* nullable */);
+int dnnca_forward_ensemble(void* model, const float* x_nhwc, int batch, unsigned views, int with_spread, float* prob_out /* nullable */);
+int dnnca_get_ensemble_spread(void* model, int batch, float* between_out /* nullable */, float* within_out /* nullable */);
+int dnnca_ensemble_of(void* model, const float* means, const float* withins /* nullable */, int n, int batch, int h, int w,
+                      float* mean_out, float* between_out, float* within_out, float* total_out);
 /* keras Model.train_step under engine.py:126-135: forward(training=True) + TFWeightedCrossentropy (losses.py:60-72)
  * + backward + [RCCL all-reduce] + Adam apply with learning rate lr (LearningRateScheduler, engine.py:97-100) */
 int dnnca_train_step(void* model, const float* x_nhwc, const float* y_hw, int batch, float lr,

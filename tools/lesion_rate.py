@@ -21,6 +21,7 @@ and prediction plane) plus pairs, match and count.
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --table_only     # plain lesion_table on it
     python tools/lesion_rate.py --detection         # the detection map alone: its launches, the call beside lesion_table, the pass
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --matched_only   # plain lesion_table_matched on it
+    python tools/lesion_rate.py --ensemble 5 [--tta flips] [--uncertainty]     # forward_ensemble alone, against its parts
 
 --link adds the cost of linking neighbouring slices: lesion_table_linked against lesion_table (wall time per call, device time of
 the three link launches), its worst case for the pair table (a checkerboard on itself: every other pixel a lesion of its own in
@@ -63,6 +64,14 @@ lesion_table_matched pass against a forward + lesion_table_matched pass, alterna
 --matched_only measures plain lesion_table_matched on the drawn discs and nothing else: run it on this build and on a library built
 from the parent commit, in turns.
 
+--ensemble M measures DeviceModel.forward_ensemble of M members (under --tta MODE when given, with the spread under --uncertainty,
+which here needs no --tta) and nothing else: wall time per call against M plain forwards and against M forward_tta_spread calls on
+the same host batch, alternated; device time per call and ens_join per launch (event-bracketed); and what one more member costs
+beyond its forward -- the device-to-device copy of its weights and BatchNorm state -- for the widths of configs/unet.yaml,
+mulmo_unet.yaml and unet_big.yaml on a 1 x 16 x 16 batch, where the forward is small: (ensemble of M - ensemble of 1) / (M - 1)
+against the plain forward there.  (forward / forward_tta on this build against a library built from the parent commit: --tta MODE
+on either, in turns.)
+
 The probabilities are drawn: the synthetic labels' discs at 0.55 .. 0.95 on a background of 0 .. 0.45 (a few lesions per slice,
 as a trained model gives), put into the model's probability buffer by pixel_confusion_of."""
 import argparse
@@ -91,6 +100,7 @@ ap.add_argument('--features', action='store_true', help='measure lesion_table_fe
 ap.add_argument('--table_only', action='store_true', help='measure plain lesion_table, and nothing else (also on a library built from the parent)')
 ap.add_argument('--detection', action='store_true', help='measure detection_map beside lesion_table and in an evaluation pass, and nothing else')
 ap.add_argument('--matched_only', action='store_true', help='measure plain lesion_table_matched, and nothing else (also on a library built from the parent)')
+ap.add_argument('--ensemble', type=int, default=0, metavar='M', help='measure forward_ensemble of M members against its parts, and nothing else')
 ap.add_argument('--out', default=None, help='append the report to this file as well')
 a = ap.parse_args()
 if a.features:                                                   # its siblings are lesion_table and lesion_table_spread
@@ -121,13 +131,20 @@ if a.surface and not a.match:
 if not a.surface:
     _lib.SIGNATURES.pop('dnnca_surface_distances', None)         # nor does one from before the boundary distances
 
-if not a.tta:
+if not a.tta and not a.ensemble:
     for name in ('dnnca_forward_tta', 'dnnca_tta_view_of', 'dnnca_tta_mean_of'):
         _lib.SIGNATURES.pop(name, None)                          # nor does one from before test-time augmentation
 
-if a.uncertainty and not a.tta:
+if not a.ensemble:
+    for name in ('dnnca_model_set_members', 'dnnca_member_store', 'dnnca_member_get', 'dnnca_forward_ensemble', 'dnnca_get_ensemble_spread',
+                 'dnnca_ensemble_of'):
+        _lib.SIGNATURES.pop(name, None)                          # nor does one from before the ensembles
+elif not 1 <= a.ensemble <= 16:
+    ap.error('--ensemble M: 1..16')
+
+if a.uncertainty and not a.tta and not a.ensemble:
     ap.error('--uncertainty needs --tta MODE')
-if not a.uncertainty:
+if not a.uncertainty and not a.ensemble:
     for name in ('dnnca_forward_tta_spread', 'dnnca_tta_spread_of', 'dnnca_get_tta_spread', 'dnnca_lesion_table_spread',
                  'dnnca_spread_by_outcome'):
         _lib.SIGNATURES.pop(name, None)                          # nor does one from before the spread
@@ -185,7 +202,84 @@ e._build(ds)
 dm = e.device_model
 say('%s: %d x %d x %d, library %s' % ('yardstick' if a.yardstick else 'lesion features' if a.features else 'plain lesion table' if a.table_only else
                                       'detection map' if a.detection else 'plain matched table' if a.matched_only else
-                                      'calibration' if a.calibration else 'test-time augmentation' if a.tta else 'lesion table', B, S, S, os.path.basename(_lib.LIB_PATH)))
+                                      'ensemble' if a.ensemble else 'calibration' if a.calibration else 'test-time augmentation' if a.tta else 'lesion table', B, S, S, os.path.basename(_lib.LIB_PATH)))
+if a.ensemble:
+    from dnncancerannotator_amd import tta as tta_modes           # noqa: E402
+    M = a.ensemble
+    views = tta_modes.mask_of(a.tta, S, S) if a.tta else 1
+    n_views = bin(views).count('1')
+    spread = bool(a.uncertainty)
+
+    def drawn_members(model, n):
+        rng = np.random.default_rng(11)
+        out = []
+        for _ in range(n):
+            model.init_glorot(seed=int(rng.integers(1 << 30)))
+            out.append((model.get_params(), model.get_state()))
+        return out
+    dm.set_members(drawn_members(dm, M))
+    say('  %d members, %d view(s) each, spread %s; %d weights + %d state floats per member' % (M, n_views, spread, dm.n_trainable, dm.n_state))
+
+    def ensemble():
+        dm.forward_ensemble(x, views, spread=spread, return_prob=False)
+        dm.sync()
+
+    def forwards():
+        for _ in range(M):
+            dm.forward(x, return_prob=False)
+        dm.sync()
+
+    def spreads():
+        for _ in range(M):
+            dm.forward_tta_spread(x, 0x0F, return_prob=False, return_spread=False)
+        dm.sync()
+    took = {}
+    arms = (('forward_ensemble', ensemble), ('%d x forward' % M, forwards), ('%d x forward_tta_spread(flips)' % M, spreads))
+    for name, fn in arms * 3:                                     # alternated
+        took.setdefault(name, []).append(wall(fn))
+    for name, runs in took.items():
+        for med, lo, hi in runs:
+            say('  %-32s %.3f ms per call, upload(s) included (median of %d; %.3f .. %.3f)' % (name, med, R, lo, hi))
+    best = {name: min(r[0] for r in runs) for name, runs in took.items()}
+    say('  forward_ensemble / %d x forward, wall (best medians): %.3f;  / %d x forward_tta_spread(flips): %.3f' % (
+        M, best[arms[0][0]] / best[arms[1][0]], M, best[arms[0][0]] / best[arms[2][0]]))
+    say('  run-to-run, forward_ensemble: medians %s' % ', '.join('%.3f' % r[0] for r in took[arms[0][0]]))
+    dm.profile_reset()
+    dm.profile_enable(1)
+    for _ in range(R):
+        ensemble()
+    rows = dm.profile()
+    dm.profile_enable(0)
+    dm.profile_reset()
+    total = sum(r[2] for r in rows) / R
+    say('  device time per call (event-bracketed launches; the weight copies are not launches): %.3f ms' % total)
+    for name, n, ms, by, fl in [r for r in rows if r[0].startswith(('ens_', 'tta_'))]:
+        say('    %-22s launches/call %4.1f  %9.2f us per launch  %7.1f GB/s' % (name, n / R, ms / n * 1e3, by / (ms / n * 1e-3) / 1e9))
+    dm.close()
+    # what one more member costs beyond its forward: the copy of its weights
+    BASE = dict(rate=2, kernel_size=3, conv_stride=1, padding='same')
+    for name, arch, opts, ch, dtype in (('unet', 'unet', dict(BASE, n_filters_first=3, n_downsample=3, bn=False), 1, 'f32'),
+                                        ('mulmo_unet', 'mulmo', dict(BASE, n_filters_first=16, n_downsample=4, bn=True), 3, 'f32'),
+                                        ('unet_big', 'unet', dict(BASE, n_filters_first=64, n_downsample=4, bn=True), 1, 'bf16')):
+        m = dev.DeviceModel(arch, ch, 16, 16, 1, dtype=dtype, **opts)
+        xs = np.random.default_rng(12).random((1, 16, 16, ch)).astype(np.float32)
+        members = drawn_members(m, M)
+        res = {}
+        for rnd in range(2):
+            for k in (1, M):
+                m.set_members(members[:k])
+                res.setdefault(k, []).append(wall(lambda: (m.forward_ensemble(xs, 1, return_prob=False), m.sync()))[0])
+            res.setdefault('forward', []).append(wall(lambda: (m.forward(xs, return_prob=False), m.sync()))[0])
+        one, many, fwd = min(res[1]), min(res[M]), min(res['forward'])
+        step = (many - one) / max(M - 1, 1)
+        say('  %-11s %9d floats per member: ensemble of 1 %.3f ms, of %d %.3f ms: %.1f us per further member; forward alone %.3f ms; '
+            'further member - forward: %.1f us (%.1f MB copied)' % (name, m.n_trainable + m.n_state, one, M, many, step * 1e3, fwd,
+                                                                   (step - fwd) * 1e3, (m.n_trainable + m.n_state) * 4 / 1e6))
+        m.close()
+    if a.out:
+        with open(a.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    sys.exit(0)
 if a.table_only:
     dm.pixel_confusion_of(prob, y, [0.5])
     for mask in (True, False) * 2:
