@@ -34,6 +34,17 @@ def _detection_arguments(p):
                    help='rows per slice and plane of the table read from the map (default: 256)')
 
 
+def _refine_arguments(p, what):
+    """the mask refinement shared by `predict` and `evaluate`; absent unless given"""
+    p.add_argument('--refine_hysteresis', type=float, default=argparse.SUPPRESS, metavar='LOW',
+                   help='outline %s at LOW, in (0, 1) and below the threshold: the regions at LOW that hold a pixel at the '
+                        'threshold (default: off)' % what)
+    p.add_argument('--refine_closing', type=int, default=argparse.SUPPRESS, metavar='K',
+                   help='close gaps below K pixels in %s after the opening: K x K closing, K odd, 3..15 (default: off)' % what)
+    p.add_argument('--refine_fill_holes', action='store_true', default=argparse.SUPPRESS,
+                   help='fill the holes of %s: background that does not reach the border of the slice' % what)
+
+
 def build_parser(prog='python3 -m annotator'):
     parser = argparse.ArgumentParser(prog=prog, description='DNNAnnotator: DNN model to predict cancer segmentation (MI355X engine)')
     sub = parser.add_subparsers(dest='command', help='command')
@@ -144,6 +155,7 @@ def build_parser(prog='python3 -m annotator'):
                         '--save_path (member 0) and each member\'s checkpoint of the step being evaluated, or of its pinned STEP; '
                         '`loss` stays the loss of member 0\'s untransformed view.  Allows --uncertainty without --tta (the spread '
                         'between the members) and then also writes ensemble_uncertainty_results.csv')
+    _refine_arguments(e, 'the predicted masks of --exam_lesions / --surface_distances')
     p = sub.add_parser('predict', help='Annotate slices that have no label: lesion tables and masks of one checkpoint.')
     p.add_argument('--save_path', required=True, help='the directory `train` wrote (options.yaml, checkpoints/)')
     p.add_argument('--data_path', nargs='+', required=True)
@@ -191,6 +203,7 @@ def build_parser(prog='python3 -m annotator'):
                         '(member 0) and each member\'s checkpoint: its pinned STEP, else --step, else its run\'s latest.  Allows '
                         '--uncertainty without --tta (the spread between the members) and then also writes '
                         'slice_ensemble_uncertainty.csv')
+    _refine_arguments(p, 'the mask every table and mask.png reads')
     return parser
 
 

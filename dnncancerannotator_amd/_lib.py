@@ -44,6 +44,10 @@ class RegionLoss(C.Structure):                     # dnnca_region_loss
                 ('smooth', C.c_float)]
 
 
+class LesionRefine(C.Structure):                   # dnnca_lesion_refine
+    _fields_ = [('hysteresis_low', C.c_float), ('closing_size', C.c_int32), ('fill_holes', C.c_int32)]
+
+
 class OptimizerCfg(C.Structure):                   # dnnca_optimizer_cfg
     _fields_ = [('kind', C.c_int32), ('beta1', C.c_float), ('beta2', C.c_float), ('epsilon', C.c_float), ('momentum', C.c_float),
                 ('nesterov', C.c_int32), ('weight_decay', C.c_float), ('clipvalue', C.c_float), ('clipnorm', C.c_float),
@@ -314,6 +318,8 @@ SIGNATURES = {
     'dnnca_lesion_table': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
                                      C.POINTER(C.c_int32)]),
+    'dnnca_model_set_lesion_refine': (C.c_int, [_VP, C.POINTER(LesionRefine)]),
+    'dnnca_model_get_lesion_refine': (C.c_int, [_VP, C.POINTER(LesionRefine)]),
     'dnnca_lesion_table_spread': (C.c_int, [_VP, _FP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                             C.POINTER(LesionRow), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _VP, C.c_int64,
                                             C.POINTER(C.c_int32), _FP, C.POINTER(LesionSpread), C.POINTER(SliceSpread)]),

@@ -13,6 +13,7 @@
 #include "calib.h"
 #include "detect.h"
 #include "kernels.h"
+#include "refine.h"
 #include "region.h"
 #include "topk.h"
 
@@ -613,11 +614,37 @@ int dnnca_eval_region_end(void* model, dnnca_region_counts* out) {
     return DNNCA_OK;
 }
 
+// ---- mask refinement of the lesion tables and the boundary distances (kernels_refine.hip) -------------------------------------
+int dnnca_model_set_lesion_refine(void* model, const dnnca_lesion_refine* cfg) {
+    MODEL(model);
+    const dnnca_lesion_refine next = cfg ? *cfg : dnnca_lesion_refine{0.f, 0, 0};
+    if (const char* why = refine_invalid(next)) { set_error("lesion refine: %s", why); return DNNCA_EINVAL; }
+    // the kept planes of the linked and matched chains remember the configuration that made them (lesion_carry_is): under another
+    // one they do not count, so no chain mixes masks made under two rules
+    M->refine = next;
+    return DNNCA_OK;
+}
+
+int dnnca_model_get_lesion_refine(void* model, dnnca_lesion_refine* out) {
+    MODEL(model);
+    if (!out) { set_error("lesion refine: null output"); return DNNCA_EINVAL; }
+    *out = M->refine;
+    return DNNCA_OK;
+}
+
 // ---- `annotator predict`: the lesion table (kernels_region.hip) ---------------------------------------------------------------
 static LesionArgs lesion_args(float threshold, float resize_factor, int filter_size, int min_area, int max_lesions) {
     LesionArgs a;
     a.threshold = threshold, a.rf = resize_factor, a.k = filter_size, a.min_area = min_area, a.max_lesions = max_lesions;
     return a;
+}
+
+// hysteresis keeps the region at hysteresis_low around the pixels at `threshold`: a call's threshold lies above a set low one
+static int lesion_refine_threshold(Model* M, const char* what, float threshold) {
+    if (M->refine.hysteresis_low == 0.f || threshold > M->refine.hysteresis_low) return DNNCA_OK;
+    set_error("%s: threshold %g is not above the refinement's hysteresis_low %g (dnnca_model_set_lesion_refine)", what, (double)threshold,
+              (double)M->refine.hysteresis_low);
+    return DNNCA_EINVAL;
 }
 
 // the caller's buffer `what` (have: it was given) must hold per_slice entries for each of `batch` slices
@@ -648,6 +675,7 @@ static int lesion_call(void* model, const LesionPlanesIn& in, LesionArgs a, cons
     Plane pl;
     DN_TRY(plane_resolve(M, "lesion table", in.prob_hw, batch, in.h, in.w, 0, &pl));
     DN_TRY(lesion_check(a, pl.h, pl.w));
+    DN_TRY(lesion_refine_threshold(M, "lesion table", a.threshold));
     if (!o.out_hw) { set_error("lesion table: null out_hw"); return DNNCA_EINVAL; }
     int channels = 0;
     if (feat) {                          // before out_hw: a refusal touches no output
@@ -758,6 +786,7 @@ int dnnca_lesion_table_matched(void* model, const float* prob_hw, const float* y
     DN_TRY(plane_resolve(M, "lesion table", prob_hw, batch, h, w, 0, &pl));
     LesionArgs a = lesion_args(threshold, resize_factor, filter_size, min_area, max_lesions);
     DN_TRY(lesion_check(a, pl.h, pl.w));
+    DN_TRY(lesion_refine_threshold(M, "lesion table", a.threshold));
     if (!out_hw) { set_error("lesion table: null out_hw"); return DNNCA_EINVAL; }
     out_hw[0] = a.oh;
     out_hw[1] = a.ow;
@@ -790,6 +819,7 @@ int dnnca_surface_distances(void* model, const float* prob_hw, const float* y_hw
     DN_TRY(plane_resolve(M, "surface distances", prob_hw, batch, h, w, 0, &pl));
     LesionArgs a = lesion_args(threshold, resize_factor, filter_size, min_area, LesionArgs().max_lesions);      // not looked at
     DN_TRY(lesion_check(a, pl.h, pl.w));
+    DN_TRY(lesion_refine_threshold(M, "surface distances", a.threshold));
     if (a.oh > kSurfaceMaxSide || a.ow > kSurfaceMaxSide) {
         set_error("surface distances: planes of %d x %d exceed %d pixels a side", a.oh, a.ow, kSurfaceMaxSide);
         return DNNCA_EINVAL;

@@ -36,6 +36,7 @@
 #include <tuple>
 
 #include "ccl_dev.h"
+#include "refine.h"
 #include "region.h"
 
 namespace dnnca {
@@ -46,12 +47,6 @@ constexpr int RB = 256;
 constexpr int kTile = 32;                                  // opening and LDS-labelling tile (kTile x kTile pixels)
 constexpr int kOpenE = kTile + 2 * (kRegionMaxK - 1);      // opening: input tile edge with the halo of erosion + dilation
 constexpr unsigned long long kEmpty = ~0ull;
-
-struct Resize {
-    int in_h, in_w, out_h, out_w;
-    float sy, sx;                        // in / out as float (TF's CalculateResizeScale), computed on the host
-    int identity;
-};
 
 #pragma clang fp contract(off)
 // tf.image.resize(method=bilinear, antialias=False) [TF-2.6 resize_bilinear_op.cc, restated]: half-pixel centres, float32,
@@ -1209,13 +1204,15 @@ struct RegionState {
     int* carry = nullptr;
     size_t carry_n = 0;                  // allocated pixels
     bool carry_valid = false;            // written by a linked call that succeeded ...
-    int carry_oh = 0, carry_ow = 0;      // ... on planes of this size
+    int carry_oh = 0, carry_ow = 0;      // ... on planes of this size ...
+    dnnca_lesion_refine carry_refine = {0.f, 0, 0};      // ... under this mask refinement (a chain never mixes two)
     // dnnca_lesion_table_matched keeps all of this apart from the linked call's: two carry planes in one buffer (the prediction's
     // rows, then from mcarry + mcarry_n the label's rows) and what DNNCA_PLAN_LESION_MATCHED replays
     int* mcarry = nullptr;
     size_t mcarry_n = 0;                 // allocated pixels per plane
     bool mcarry_valid = false;
     int mcarry_oh = 0, mcarry_ow = 0;
+    dnnca_lesion_refine mcarry_refine = {0.f, 0, 0};
     float match_rf = 1.f;
     int match_k = 5;
     bool match_mask = true;
@@ -1380,7 +1377,7 @@ int region_prepare(Model* M, const std::vector<RegionSpecHost>& specs, int max_b
 }
 
 // connected components of the T planes of `words` (nb slices of h x w) into L
-static void region_ccl(Model* M, const uint32_t* words, int T, int nb, int h, int w, int* L) {
+void region_ccl(Model* M, const uint32_t* words, int T, int nb, int h, int w, int* L) {
     const size_t total = (size_t)T * nb * h * w;
     const dim3 tiles((w + kTile - 1) / kTile, (h + kTile - 1) / kTile, T * nb);
     LAUNCH(M, "region_ccl_tile", total * 8.0 / 32 * (T > 32 ? 2 : 1) + total * 4.0, 0,
@@ -1389,6 +1386,19 @@ static void region_ccl(Model* M, const uint32_t* words, int T, int nb, int h, in
            hipLaunchKernelGGL(k_region_ccl_merge, dim3(nblocks(total)), dim3(RB), 0, M->stream, L, total, h, w));
     LAUNCH(M, "region_ccl_compress", total * 8.0, 0,
            hipLaunchKernelGGL(k_region_ccl_compress, dim3(nblocks(total)), dim3(RB), 0, M->stream, L, total));
+}
+
+// region_prep and region_open as the mask refinement launches them (refine.h): one word plane of nb slices
+void region_prep_launch(Model* M, const float* src, const Resize& rz, int nb, const float* thr_dev, int T, uint32_t* words) {
+    const size_t n = (size_t)nb * rz.out_h * rz.out_w;
+    LAUNCH(M, "region_prep", n * 4.0 + (double)nb * rz.in_h * rz.in_w * 4, 0,
+           hipLaunchKernelGGL(k_region_prep, dim3(nblocks(n)), dim3(RB), 0, M->stream, src, rz, nb, thr_dev, T, words));
+}
+
+void region_open_launch(Model* M, const uint32_t* in, uint32_t* out, int oh, int ow, int k, int nb) {
+    const size_t n = (size_t)nb * oh * ow;
+    const dim3 tiles((ow + kTile - 1) / kTile, (oh + kTile - 1) / kTile, nb);
+    LAUNCH(M, "region_open", n * 8.0, 0, hipLaunchKernelGGL(k_region_open, tiles, dim3(RB), 0, M->stream, in, out, oh, ow, k, n, nb));
 }
 
 int region_accumulate(Model* M, const float* prob, const float* y, int batch, int h, int w, bool per_slice) {
@@ -1615,7 +1625,7 @@ static LesionWs lesion_layout(void* base, size_t nb, size_t hw, size_t cap, size
     w.sp = (unsigned*)take(n * 4);
     w.row = (int*)take(n * 4);
     w.tot = (int*)take(nb * 4);
-    w.thr = (float*)take(4);
+    w.thr = (float*)take(2 * 4);         // (two with the hysteresis of the mask refinement; a piece is 256 bytes at least)
     w.acc = (LesionAcc*)take(nb * cap * sizeof(LesionAcc));
     w.mask = (uint32_t*)take((n + 3) / 4 * 4);
     w.lkeys = nullptr, w.lcnt = nullptr, w.cont = nullptr, w.list = nullptr, w.n_list = nullptr;
@@ -1893,22 +1903,25 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
     std::vector<LesionLink> found[3];
     int64_t out = 0, out_true = 0, out_list[3] = {0, 0, 0};
     Resize rz{h, w, oh, ow, (float)h / (float)oh, (float)w / (float)ow, (oh == h && ow == w) ? 1 : 0};
+    const bool refine = refine_on(M->refine);
+    const float refine_thr[2] = {M->refine.hysteresis_low, a.threshold};     // outlives every chunk's sync
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
         const size_t n = (size_t)nb * hw;
         const LesionWs ws = lesion_layout(R.ws, nb, hw, cap, per_slice, match != nullptr, sp != nullptr, ft);
         const float* pb = prob + (size_t)b0 * h * w;
         const float* yb = match ? match->y + (size_t)b0 * h * w : nullptr;
-        if (!M->dry) HIP_TRY(hipMemcpyAsync(ws.thr, &a.threshold, 4, hipMemcpyHostToDevice, s));   // `a` outlives the chunk's sync
+        if (!refine && !M->dry) HIP_TRY(hipMemcpyAsync(ws.thr, &a.threshold, 4, hipMemcpyHostToDevice, s));   // `a` outlives the chunk's sync
         if (link && !M->dry) HIP_TRY(hipMemcpyAsync(ws.cont, link->continues + b0, (size_t)nb, hipMemcpyHostToDevice, s));
-        LAUNCH(M, "region_prep", n * 4.0 + (double)nb * h * w * 4, 0,
-               hipLaunchKernelGGL(k_region_prep, dim3(nblocks(n)), dim3(RB), 0, s, pb, rz, nb, (const float*)ws.thr, 1, ws.w0));
         const uint32_t* fg = ws.w0;
-        if (a.k > 1) {
-            const dim3 tiles((ow + kTile - 1) / kTile, (oh + kTile - 1) / kTile, nb);
-            LAUNCH(M, "region_open", n * 8.0, 0,
-                   hipLaunchKernelGGL(k_region_open, tiles, dim3(RB), 0, s, ws.w0, ws.w1, oh, ow, a.k, n, nb));
-            fg = ws.w1;
+        if (refine) {                    // the refined mask in the place of prep / open; lp and sp are written only behind it
+            DN_TRY(refine_chunk(M, M->refine, pb, rz, nb, refine_thr, a.k, RefineWs{ws.w0, ws.w1, ws.lp, ws.sp, ws.thr}, &fg));
+        } else {
+            region_prep_launch(M, pb, rz, nb, ws.thr, 1, ws.w0);
+            if (a.k > 1) {
+                region_open_launch(M, ws.w0, ws.w1, oh, ow, a.k, nb);
+                fg = ws.w1;
+            }
         }
         DN_TRY(lesion_plane(M, pb, rz, nb, fg, a.min_area, cap, ws.lp, ws.sp, ws.row, ws.tot, ws.acc));
         if (want_mask)
@@ -2023,6 +2036,7 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
         R.carry_valid = true;
         R.carry_oh = oh;
         R.carry_ow = ow;
+        R.carry_refine = M->refine;
     }
     if (match && !M->dry) {
         *match->n_rows = out_true;
@@ -2031,6 +2045,7 @@ static int lesion_run(Model* M, const float* prob, int batch, int h, int w, cons
         R.mcarry_valid = true;
         R.mcarry_oh = oh;
         R.mcarry_ow = ow;
+        R.mcarry_refine = M->refine;
     }
     return DNNCA_OK;
 }
@@ -2145,7 +2160,7 @@ static SurfaceWs surface_layout(void* base, size_t nb, size_t hw, size_t per) {
     w.lp = (int*)take(n * 4);
     w.sp = (unsigned*)take(n * 4);
     w.yw = (uint32_t*)take(n * 4);
-    w.thr = (float*)take(4);
+    w.thr = (float*)take(2 * 4);         // (two with the hysteresis of the mask refinement)
     w.ythr = (float*)take(4);
     w.edges = (unsigned char*)take(n);
     w.cols = (unsigned short*)take(2 * n * 2);
@@ -2170,6 +2185,8 @@ int surface_distances(Model* M, const float* prob, const float* y, int batch, in
     std::vector<SurfaceSample> found;
     int64_t out = 0;
     Resize rz{h, w, oh, ow, (float)h / (float)oh, (float)w / (float)ow, (oh == h && ow == w) ? 1 : 0};
+    const bool refine = refine_on(M->refine);
+    const float refine_thr[2] = {M->refine.hysteresis_low, a.threshold};     // outlives every chunk's sync
     for (int b0 = 0; b0 < batch; b0 += chunk) {
         const int nb = std::min(chunk, batch - b0);
         const size_t n = (size_t)nb * hw, list_cap = (size_t)nb * 2 * per;
@@ -2177,17 +2194,18 @@ int surface_distances(Model* M, const float* prob, const float* y, int batch, in
         const float* pb = prob + (size_t)b0 * h * w;
         const float* yb = y + (size_t)b0 * h * w;
         if (!M->dry) {
-            HIP_TRY(hipMemcpyAsync(ws.thr, &a.threshold, 4, hipMemcpyHostToDevice, s));       // `a` outlives the chunk's sync
+            if (!refine) HIP_TRY(hipMemcpyAsync(ws.thr, &a.threshold, 4, hipMemcpyHostToDevice, s));       // `a` outlives the chunk's sync
             HIP_TRY(hipMemcpyAsync(ws.ythr, &kLabelThreshold, 4, hipMemcpyHostToDevice, s));
         }
-        LAUNCH(M, "region_prep", n * 4.0 + (double)nb * h * w * 4, 0,
-               hipLaunchKernelGGL(k_region_prep, dim3(nblocks(n)), dim3(RB), 0, s, pb, rz, nb, (const float*)ws.thr, 1, ws.w0));
         const uint32_t* fg = ws.w0;
-        if (a.k > 1) {
-            const dim3 tiles((ow + kTile - 1) / kTile, (oh + kTile - 1) / kTile, nb);
-            LAUNCH(M, "region_open", n * 8.0, 0,
-                   hipLaunchKernelGGL(k_region_open, tiles, dim3(RB), 0, s, ws.w0, ws.w1, oh, ow, a.k, n, nb));
-            fg = ws.w1;
+        if (refine) {                    // the refined mask in the place of prep / open; lp and sp are written only behind it
+            DN_TRY(refine_chunk(M, M->refine, pb, rz, nb, refine_thr, a.k, RefineWs{ws.w0, ws.w1, ws.lp, ws.sp, ws.thr}, &fg));
+        } else {
+            region_prep_launch(M, pb, rz, nb, ws.thr, 1, ws.w0);
+            if (a.k > 1) {
+                region_open_launch(M, ws.w0, ws.w1, oh, ow, a.k, nb);
+                fg = ws.w1;
+            }
         }
         region_ccl(M, fg, 1, nb, oh, ow, ws.lp);
         if (!M->dry) {
@@ -2241,7 +2259,8 @@ void surface_last(Model* M, float* rf, int* k) {
 }
 
 bool lesion_match_carry_is(Model* M, int oh, int ow) {
-    return M->region && M->region->mcarry_valid && M->region->mcarry_oh == oh && M->region->mcarry_ow == ow;
+    return M->region && M->region->mcarry_valid && M->region->mcarry_oh == oh && M->region->mcarry_ow == ow &&
+           refine_same(M->region->mcarry_refine, M->refine);
 }
 
 void lesion_match_last(Model* M, float* rf, int* k, bool* want_mask) {
@@ -2253,7 +2272,8 @@ void lesion_match_last(Model* M, float* rf, int* k, bool* want_mask) {
 }
 
 bool lesion_carry_is(Model* M, int oh, int ow) {
-    return M->region && M->region->carry_valid && M->region->carry_oh == oh && M->region->carry_ow == ow;
+    return M->region && M->region->carry_valid && M->region->carry_oh == oh && M->region->carry_ow == ow &&
+           refine_same(M->region->carry_refine, M->refine);
 }
 
 void lesion_last(Model* M, float* rf, int* k, bool* want_mask) {

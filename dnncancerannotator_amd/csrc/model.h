@@ -311,6 +311,8 @@ struct Model {
     ConfThresholds eval_thr;             // also the one-shot dnnca_pixel_confusion* (never inside an evaluation); counts in conf_dev
     // region metrics (kernels_region.hip): specs, accumulators and workspace; region_eval: the staged eval steps add region counts
     RegionState* region = nullptr;
+    // mask refinement of the lesion tables and the boundary distances (dnnca_model_set_lesion_refine, refine.h); all zero: off
+    dnnca_lesion_refine refine = {0.f, 0, 0};
     // the kernel families' plans, built by the first forward pass (fast_prepare, ig_prepare, ig3x_prepare), dropped by fast_release /
     // ig_release / ig3x_release; nullptr: none (force_generic, or no forward pass yet)
     PgPlan* plan_pg = nullptr; IgPlan* plan_ig = nullptr; Ig3xPlan* plan_ig3x = nullptr;

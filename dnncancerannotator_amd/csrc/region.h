@@ -13,6 +13,13 @@ constexpr int kRegionMaxK = 15;          // morphological filter size
 constexpr int kSurfaceMaxSide = 16384;   // boundary distances: analysed planes of up to this many pixels a side (squares in int32)
 constexpr unsigned kSurfaceFar = 0x7fffu;   // column distance "none" of surface_cols / boundary_cols: above every real distance
 
+// the bilinear resize of a plane as the kernels take it (kernels_region.hip resize_at; identity: in == out, plain reads)
+struct Resize {
+    int in_h, in_w, out_h, out_w;
+    float sy, sx;                        // in / out as float (TF's CalculateResizeScale), computed on the host
+    int identity;
+};
+
 // one validated spec: the caller's thresholds (in their order), IoU threshold, resize factor, filter size, and the resized plane
 struct RegionSpecHost {
     std::vector<float> thr;
@@ -91,7 +98,8 @@ int spread_by_outcome(Model* M, const float* prob, const float* spread, const fl
 int lesion_table_linked(Model* M, const float* prob, int batch, int h, int w, const LesionArgs& a, dnnca_lesion_row* rows,
                         int64_t* n_rows, int32_t* totals, uint8_t* mask, bool want_mask, const uint8_t* continues,
                         dnnca_lesion_link* links, int64_t* n_links);
-// the carry plane holds the rows of the last slice of a successful lesion_table_linked on planes of oh x ow
+// the carry plane holds the rows of the last slice of a successful lesion_table_linked on planes of oh x ow under the model's
+// current mask refinement
 bool lesion_carry_is(Model* M, int oh, int ow);
 // lesion_table_linked on prob plus the same on the labels y (device [batch, h, w]: label' > 0.5, no opening, no area filter, the
 // same cap) plus the pairs of a labelled and a predicted lesion of one slice (dnnca_lesion_table_matched): per chunk the launches

@@ -837,6 +837,22 @@ class DeviceModel:
                                               out.ctypes.data_as(C.c_void_p), out.nbytes, hwc))
         return out
 
+    # ---- mask refinement of the lesion tables and the boundary distances (kernels_refine.hip) --------------------
+    def set_lesion_refine(self, hysteresis=None, closing=0, fill_holes=False):
+        """every later lesion_table*, lesion_table_matched (its prediction side) and surface_distances call refines the prediction
+        mask on the analysed plane (dnnca_model_set_lesion_refine): hysteresis (a low threshold in (0, 1) below the call's own: the
+        4-connected regions at `hysteresis` that hold a pixel at the threshold), then the opening, a closing x closing closing (odd, 3
+        .. 15; 0 or 1: none), then hole filling.  No argument switches it off.  Changing the configuration ends the chains of
+        lesion_table_linked and lesion_table_matched"""
+        c = _lib.LesionRefine(0.0 if hysteresis is None else float(hysteresis), int(closing), int(fill_holes))
+        check(self.lib.dnnca_model_set_lesion_refine(self.handle, C.byref(c)))
+
+    def lesion_refine(self):
+        """(hysteresis or None, closing, fill_holes) as set_lesion_refine last set them"""
+        c = _lib.LesionRefine()
+        check(self.lib.dnnca_model_get_lesion_refine(self.handle, C.byref(c)))
+        return (float(c.hysteresis_low) if c.hysteresis_low != 0.0 else None, int(c.closing_size), bool(c.fill_holes))
+
     # ---- `annotator predict` (kernels_region.hip: lesion_scan / lesion_stats / lesion_mask) ---------------------
     def lesion_table(self, batch=None, prob=None, threshold=0.5, resize_factor=1.0, filter_size=5, min_area=0, max_lesions=256,
                      mask=True):

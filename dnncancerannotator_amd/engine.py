@@ -9,6 +9,7 @@ Data parallel (deploy_options.enable_multigpu, engine.py:260-263): one process p
 shard of every global batch, libdnnca sums the gradients with one RCCL all-reduce per step, rank 0 writes files.
 Ranks come from RANK / LOCAL_RANK / WORLD_SIZE (set by `python -m dnncancerannotator_amd.launch` or torchrun)."""
 
+import contextlib
 import copy
 import json
 import logging
@@ -192,6 +193,40 @@ def check_detection(detection, min_confidence=None, factor=None, max_candidates=
         raise ValueError('--detection_link_min_overlap and --detection_max_lesions must be at least 1, got %d and %d'
                          % (link_min_overlap, max_lesions))
     return dict(cfg=cfg, iou=iou, link_min_overlap=link_min_overlap, max_lesions=max_lesions)
+
+
+REFINE_MAX_CLOSING = 15
+
+
+def check_refine(hysteresis=None, closing=None, fill_holes=False, thresholds=(), consumers=True):
+    """the values of --refine_hysteresis LOW, --refine_closing K and --refine_fill_holes (None / False: not given) -> None when
+    nothing is asked for (no flag, or a closing of 0 or 1 alone), else the keywords of DeviceModel.set_lesion_refine.
+    thresholds: every threshold the run's refined tables will use.  A ValueError that names the flag -- before anything is read --
+    for: LOW outside (0, 1) or NaN, or not below every threshold (as float32, the comparison the library makes); K negative, even
+    (its window is asymmetric: the closed mask would not contain its input) or above 15; any of the flags without a pass that
+    reads the refined mask (consumers=False: `evaluate` without --exam_lesions / --surface_distances)"""
+    if hysteresis is None and closing is None and not fill_holes:
+        return None
+    if not consumers:
+        raise ValueError('the --refine_* options refine the masks of --exam_lesions / --surface_distances: add one of them')
+    low = None
+    if hysteresis is not None:
+        low = float(hysteresis)
+        if not 0.0 < low < 1.0:                                         # (False for a NaN)
+            raise ValueError('--refine_hysteresis must lie strictly between 0 and 1, got %r' % (hysteresis,))
+        above = [float(t) for t in thresholds]
+        if above and not np.float32(low) < np.float32(min(above)):
+            raise ValueError('--refine_hysteresis %r must lie below every threshold of the run (the smallest is %r): it is the low '
+                             'threshold around the pixels at the high one' % (hysteresis, min(above)))
+    k = 0 if closing is None else closing
+    if isinstance(k, bool) or int(k) != k:
+        raise ValueError('--refine_closing must be an integer, got %r' % (closing,))
+    k = int(k)
+    if k < 0 or k > REFINE_MAX_CLOSING or (k > 1 and k % 2 == 0):
+        raise ValueError('--refine_closing must be an odd size in 3..%d (0 or 1: no closing), got %r' % (REFINE_MAX_CLOSING, closing))
+    if low is None and k <= 1 and not fill_holes:
+        return None
+    return dict(hysteresis=low, closing=k, fill_holes=bool(fill_holes))
 
 
 EMA_KEYS = ('decay', 'warmup', 'validate')
@@ -674,6 +709,8 @@ class TFKerasModel:
         self._set_accumulation(bigger)
         if getattr(self, '_members', None):       # --ensemble: the members lived in the model the batch outgrew
             bigger.set_members(self._members)
+        if getattr(self, '_refine', None):        # --refine_*: so did the mask refinement
+            bigger.set_lesion_refine(**self._refine)
         self.device_model = bigger
         return True
 
@@ -682,6 +719,27 @@ class TFKerasModel:
         from their data files and stored in the device model; kept for _ensure_capacity"""
         self._members = [read_member(p, weights) for p in [own_path] + list(paths)]
         self.device_model.set_members(self._members)
+
+    def _set_refine(self, refine):
+        """--refine_*: what check_refine returned is stored in the device model once, before the first table call, and every later
+        lesion_table* / surface_distances call reads it there; kept for _ensure_capacity.  None: no call is made"""
+        self._refine = refine
+        if refine:
+            self.device_model.set_lesion_refine(**refine)
+
+    @contextlib.contextmanager
+    def _unrefined(self, dm):
+        """around the table calls on a detection map, whose regions are already final: the refinement off, and back on afterwards.
+        The kept planes of the lesions' chain count again once it is back (they remember the configuration that made them).  Without
+        --refine_* no call is made"""
+        refine = getattr(self, '_refine', None)
+        if refine:
+            dm.set_lesion_refine()
+        try:
+            yield
+        finally:
+            if refine:
+                dm.set_lesion_refine(**refine)
 
     def _shard(self, x, y=None):
         """Contiguous shard of a global batch for this rank (Keras splits the batch across replicas [TF-2.6]); a batch
@@ -1103,7 +1161,7 @@ class TFKerasModel:
              detection=False, detection_min_confidence=None, detection_factor=None, detection_max_candidates=None,
              detection_min_area=None, detection_rounds=None, detection_iou=None, detection_link_min_overlap=None,
              detection_max_lesions=None, bootstrap=None, bootstrap_seed=None, bootstrap_level=None, bootstrap_stratified=False,
-             ensemble=None):
+             ensemble=None, refine_hysteresis=None, refine_closing=None, refine_fill_holes=False):
         """weights (`evaluate --weights ema`): every checkpoint is loaded with its averaged weights as the parameters (load(...,
         weights='ema')); everything downstream reads that model unchanged.  Checkpoints without an average are an error that names
         the first, raised before anything is evaluated.
@@ -1152,8 +1210,18 @@ class TFKerasModel:
         evaluated).  The evaluation then runs batch by batch; `loss`, --visualize_sensitivity and --visualize_attribution stay
         those of member 0's plain forward.  With uncertainty (which --ensemble allows without a tta mode) the spread every file
         reads is the total over members and views, and ensemble_uncertainty_results.csv is written too: the mean between-member,
-        within-member and total spread per pixel outcome.  None: nothing new runs."""
+        within-member and total spread per pixel outcome.  None: nothing new runs.
+        refine_hysteresis, refine_closing, refine_fill_holes (`evaluate --refine_hysteresis LOW --refine_closing K
+        --refine_fill_holes`, check_refine): stored in the device model once (DeviceModel.set_lesion_refine), before the first
+        table call; the prediction masks of the exam-lesion and the surface pass are then the refined ones -- one setting for both;
+        LOW lies below every exam_threshold and surface_threshold.  Labels, the region metrics, the casewise counts and the
+        detection pass (the refinement is switched off around its table calls and back on) are what they are without the flags.
+        Needs exam_lesions or surface_distances; without the flags no call is made."""
         check_uncertainty(uncertainty, tta, ensemble)
+        refine = check_refine(refine_hysteresis, refine_closing, refine_fill_holes,
+                              [float(t) for t in (exam_threshold if exam_lesions else ())] +
+                              [float(t) for t in (surface_threshold if surface_distances else ())],
+                              consumers=bool(exam_lesions or surface_distances))
         bootstrap = check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level, bootstrap_stratified, detection, exam_lesions)
         detection = check_detection(detection, detection_min_confidence, detection_factor, detection_max_candidates, detection_min_area,
                                     detection_rounds, detection_iou, detection_link_min_overlap, detection_max_lesions)
@@ -1174,6 +1242,7 @@ class TFKerasModel:
             check_ensemble(save_path, ensemble, list(visited), weights)
         tta_mask = None if tta == tta_modes.NONE else tta_modes.mask_of(tta, *_element_shape(dataset)[1:3])
         self._build(dataset)
+        self._set_refine(refine)
         member_paths = check_ensemble(save_path, ensemble, list(visited), weights, self.device_model.param_infos()) if ensemble else {}
         if ensemble:
             logging.info('evaluate --ensemble: %d members beside %s; the evaluation runs batch by batch (the staged ring has no '
@@ -1418,7 +1487,8 @@ class TFKerasModel:
             continues = chain.continues(dm, pk)
             _, map_records = dm.detection_map(len(xb), **det['cfg'])
             exhausted += int(map_records['exhausted'].sum())
-            found += casewise.slice_records(dm.lesion_table_matched(yb, batch=len(xb), continues=continues, **kw), pk)
+            with self._unrefined(dm):        # the map's regions are final
+                found += casewise.slice_records(dm.lesion_table_matched(yb, batch=len(xb), continues=continues, **kw), pk)
         lead, cases, candidates = [int(step)], [], []
         for exam, recs in casewise.by_exam(found).items():
             case, lines = casewise.match_records(casewise.detection_match, exam, recs, det['link_min_overlap'], iou=det['iou'])
@@ -1523,7 +1593,8 @@ class TFKerasModel:
                  max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
                  temperature=None, lesion_features=False, feature_bins=None, feature_ring=None, weights='raw', detection_map=False,
                  detection_min_confidence=None, detection_factor=None, detection_max_candidates=None, detection_min_area=None,
-                 detection_rounds=None, detection_link_min_overlap=None, detection_max_lesions=None, ensemble=None):
+                 detection_rounds=None, detection_link_min_overlap=None, detection_max_lesions=None, ensemble=None,
+                 refine_hysteresis=None, refine_closing=None, refine_fill_holes=False):
         """`annotator predict`: the lesions of slices that have no label.  Loads checkpoint `step` of save_path (None: the latest);
         per batch (x, paths, sliceIDs) of `dataset` (make_dataset(..., include_meta=True, labels=False)) one forward whose
         probabilities stay on the device, then DeviceModel.lesion_table: threshold, filter_size x filter_size opening, components
@@ -1567,8 +1638,14 @@ class TFKerasModel:
         step, else of `step`, else their run's latest -- each under the tta mode when one is given; every table and mask is that
         of the mean over the members.  With uncertainty (which --ensemble allows without a tta mode) the spread every file reads
         is the total over members and views, and slice_ensemble_uncertainty.csv is written too: per slice the mean and largest
-        between-member and within-member spread (the two planes leave the device only then).  None: nothing new runs."""
+        between-member and within-member spread (the two planes leave the device only then).  None: nothing new runs.
+        refine_hysteresis, refine_closing, refine_fill_holes (`predict --refine_hysteresis LOW --refine_closing K
+        --refine_fill_holes`, check_refine): stored in the device model once (DeviceModel.set_lesion_refine), before the first
+        table call; every table and mask.png then reads the refined mask -- the region at LOW around the pixels at `threshold`,
+        opened, closed by K x K, its holes filled.  The table read from a detection map is not refined: the refinement is switched
+        off around it and back on.  No file gains or loses a column; without the flags no call is made."""
         check_uncertainty(uncertainty, tta, ensemble)
+        refine = check_refine(refine_hysteresis, refine_closing, refine_fill_holes, [threshold])
         det = check_detection(detection_map, detection_min_confidence, detection_factor, detection_max_candidates, detection_min_area,
                               detection_rounds, None, detection_link_min_overlap, detection_max_lesions, flag='--detection_map')
         check_weights(weights)
@@ -1580,6 +1657,7 @@ class TFKerasModel:
         if ensemble:
             check_ensemble(save_path, ensemble, [step], weights)
         self._build(dataset)
+        self._set_refine(refine)
         member_paths = check_ensemble(save_path, ensemble, [step], weights, self.device_model.param_infos())[step] if ensemble else None
         step = self._load_step(save_path, step, weights)
         if ensemble:
@@ -1604,9 +1682,10 @@ class TFKerasModel:
                 if ensemble and uncertainty:
                     component_rows += [casewise.slice_ensemble_uncertainty_values(p, k, b_, w_)
                                        for (p, k), b_, w_ in zip(pk, *dm.last_ensemble_spread(len(xb)))]
-                if det:                              # last: from here on the buffer holds the map
-                    for table, new in zip((candidate_rows, slice_candidate_rows, candidates_linked),
-                                          self._candidate_tables(dm, xb, pk, det, continues, writer, output)):
+                if det:                              # last: from here on the buffer holds the map, whose regions are final
+                    with self._unrefined(dm):
+                        new_tables = self._candidate_tables(dm, xb, pk, det, continues, writer, output)
+                    for table, new in zip((candidate_rows, slice_candidate_rows, candidates_linked), new_tables):
                         table += new
                 if link_slices:
                     linked += casewise.slice_records((t.rows, t.totals, t.masks, t.links), pk)

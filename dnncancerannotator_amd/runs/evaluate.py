@@ -16,8 +16,11 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
              attribution_steps=None, attribution_baseline=None, weights='raw', detection=False, detection_min_confidence=None,
              detection_factor=None, detection_max_candidates=None, detection_min_area=None, detection_rounds=None, detection_iou=None,
              detection_link_min_overlap=None, detection_max_lesions=None, bootstrap=None, bootstrap_seed=None, bootstrap_level=None,
-             bootstrap_stratified=False, ensemble=None):
+             bootstrap_stratified=False, ensemble=None, refine_hysteresis=None, refine_closing=None, refine_fill_holes=False):
     engine.check_uncertainty(uncertainty, tta, ensemble)       # before anything is read
+    refine = engine.check_refine(refine_hysteresis, refine_closing, refine_fill_holes,      # likewise: below every threshold in use
+                                 list(exam_threshold if exam_lesions else ()) + list(surface_threshold if surface_distances else ()),
+                                 consumers=bool(exam_lesions or surface_distances))
     resampling = engine.check_bootstrap(bootstrap, bootstrap_seed, bootstrap_level, bootstrap_stratified, detection, exam_lesions)
     detection_values = dict(detection_min_confidence=detection_min_confidence, detection_factor=detection_factor,
                             detection_max_candidates=detection_max_candidates, detection_min_area=detection_min_area,
@@ -69,6 +72,8 @@ def evaluate(save_path, data_path, tag, config=None, avoid_overwrite=False, expo
         more.update(detection_ds=meta_ds, detection=True, **detection_values)
     if ensemble:                         # and that of --ensemble only with members
         more['ensemble'] = ensemble
+    if refine:                           # and those of --refine_* only when they ask for something
+        more.update(refine_hysteresis=refine_hysteresis, refine_closing=refine_closing, refine_fill_holes=refine_fill_holes)
     if resampling:                       # and those of --bootstrap
         more.update(bootstrap=resampling['replicates'], bootstrap_seed=resampling['seed'], bootstrap_level=resampling['level'],
                     bootstrap_stratified=resampling['stratified'])

@@ -6,7 +6,8 @@ scaled by T; with --lesion_features also lesion_features.csv and, with --link_sl
 per modality the intensities in and around every lesion; with --detection_map also candidates.csv, slice_candidates.csv, with
 --link_slices exam_candidates.csv and with --export_images detection.png: ranked lesion candidates without a fixed threshold; with
 --ensemble MEMBER ... every table reads the mean probability over the members' checkpoints, and with --uncertainty also
-slice_ensemble_uncertainty.csv is written; engine.TFKerasModel.annotate)."""
+slice_ensemble_uncertainty.csv is written; with --refine_hysteresis LOW, --refine_closing K and --refine_fill_holes every table and
+mask.png reads the refined mask; engine.TFKerasModel.annotate)."""
 
 import os
 
@@ -18,8 +19,10 @@ def predict(save_path, data_path, output, config=None, step=None, threshold=0.5,
             max_lesions=256, export_images=False, link_slices=False, link_min_overlap=1, tta='none', uncertainty=False,
             temperature=None, lesion_features=False, feature_bins=None, feature_ring=None, weights='raw', detection_map=False,
             detection_min_confidence=None, detection_factor=None, detection_max_candidates=None, detection_min_area=None,
-            detection_rounds=None, detection_link_min_overlap=None, detection_max_lesions=None, ensemble=None):
+            detection_rounds=None, detection_link_min_overlap=None, detection_max_lesions=None, ensemble=None, refine_hysteresis=None,
+            refine_closing=None, refine_fill_holes=False):
     engine.check_uncertainty(uncertainty, tta, ensemble)       # before anything is read
+    refine = engine.check_refine(refine_hysteresis, refine_closing, refine_fill_holes, [threshold])      # likewise
     detection_values = dict(detection_min_confidence=detection_min_confidence, detection_factor=detection_factor,
                             detection_max_candidates=detection_max_candidates, detection_min_area=detection_min_area,
                             detection_rounds=detection_rounds, detection_link_min_overlap=detection_link_min_overlap,
@@ -55,6 +58,8 @@ def predict(save_path, data_path, output, config=None, step=None, threshold=0.5,
         more['ensemble'] = ensemble
     if detection_map:                    # and those of --detection_map only with the flag
         more.update(detection_map=True, **detection_values)
+    if refine:                           # and those of --refine_* only when they ask for something
+        more.update(refine_hysteresis=refine_hysteresis, refine_closing=refine_closing, refine_fill_holes=refine_fill_holes)
     model = engine.TFKerasModel(config)
     return model.annotate(ds, save_path=save_path, output=output, step=step, threshold=threshold, min_area=min_area,
                           filter_size=filter_size, resize_factor=resize_factor, max_lesions=max_lesions,

@@ -608,6 +608,37 @@ int dnnca_lesion_table(void* model, const float* prob_hw, int batch, int h, int 
                        int filter_size, int min_area, int max_lesions, dnnca_lesion_row* rows, int64_t rows_capacity,
                        int64_t* n_rows, int32_t* totals, uint8_t* mask, int64_t mask_capacity, int32_t* out_hw);
 
+/* ---- mask refinement: hysteresis, closing and hole filling (`--refine_hysteresis`, `--refine_closing`, `--refine_fill_holes`) -----
+ * Model state, like the region loss: dnnca_lesion_table, _spread, _features, _linked, _matched and dnnca_surface_distances apply it
+ * to the PREDICTION plane (the last forward's or prob_hw), on the analysed (resized) plane, in this order:
+ *   hysteresis_low   0: off.  Else in (0, 1) and below the call's threshold: M_low = prob' >= hysteresis_low, M_high = prob' >=
+ *                    threshold (float32, the same prob'); kept are the 4-connected components of M_low that hold a pixel of M_high
+ *   (the opening)    filter_size, as without the refinement
+ *   closing_size     0 or 1: off.  Else odd, 3 .. 15: dilation (OR over the in-plane part of [y - c, y + c] x [x - c, x + c],
+ *                    c = (closing_size - 1) / 2), then erosion (AND over the in-plane part of the same window).  The closed mask
+ *                    contains the opened one; closing twice is closing once
+ *   fill_holes       0 or 1.  A 4-connected component of the background with no pixel in the plane's first or last row or column
+ *                    becomes foreground (scipy.ndimage.binary_fill_holes's default)
+ * then components, area filter, numbering, statistics and mask as before, over all pixels of the refined components.  Nothing
+ * crosses from one slice into the next.  The label plane of the matched and surface calls, dnnca_region_confusion* and
+ * dnnca_detection_map are not refined.  Off (the default; cfg == NULL or all zero): every launch, plan string and output byte is
+ * what it is without these functions, and nothing is allocated.  On: the stage borrows planes of the call's own workspace.
+ * dnnca_model_set_lesion_refine: DNNCA_EINVAL, with nothing changed: hysteresis_low NaN, or not 0 and outside (0, 1); closing_size
+ * negative, even and above 1, or above 15; fill_holes other than 0 or 1.  The kept predecessor planes of dnnca_lesion_table_linked
+ * and dnnca_lesion_table_matched count only under the configuration that made them: after a call that CHANGES it, continues[0] != 0
+ * is refused as before the first such call, so no chain mixes masks made under two rules (a caller that switches the refinement
+ * off for one kind of call and back on keeps the chain of the other kind).  A table call whose threshold is not above a set hysteresis_low
+ * returns DNNCA_EINVAL with nothing launched.  Every mark of the stage is an integer flag: results are bit-identical from run to
+ * run.  dnnca_plan_dump_pass lists the stage's launches (region_hyst_seed, region_hyst_keep, region_close, region_complement,
+ * region_hole_border, region_hole_fill, and one region_ccl_* set per labelling) while it is on. */
+typedef struct dnnca_lesion_refine {
+    float hysteresis_low;
+    int32_t closing_size;
+    int32_t fill_holes;
+} dnnca_lesion_refine;
+int dnnca_model_set_lesion_refine(void* model, const dnnca_lesion_refine* cfg);
+int dnnca_model_get_lesion_refine(void* model, dnnca_lesion_refine* out);
+
 /* ---- the same table plus the spread of the views under it (`annotator predict --tta MODE --uncertainty`) -----------------------------
  * Every argument up to out_hw means what it means for dnnca_lesion_table (the size query with rows == NULL included), and rows,
  * totals, mask and out_hw are bit-identical to that call's.  The spread plane is resized like the probabilities (the same bilinear

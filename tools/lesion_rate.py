@@ -22,6 +22,7 @@ and prediction plane) plus pairs, match and count.
     python tools/lesion_rate.py --detection         # the detection map alone: its launches, the call beside lesion_table, the pass
     DNNCA_LIB=<a library built from the parent commit> python tools/lesion_rate.py --matched_only   # plain lesion_table_matched on it
     python tools/lesion_rate.py --ensemble 5 [--tta flips] [--uncertainty]     # forward_ensemble alone, against its parts
+    python tools/lesion_rate.py --refine            # mask refinement alone: its launches, the refined call against the plain one
 
 --link adds the cost of linking neighbouring slices: lesion_table_linked against lesion_table (wall time per call, device time of
 the three link launches), its worst case for the pair table (a checkerboard on itself: every other pixel a lesion of its own in
@@ -72,6 +73,12 @@ mulmo_unet.yaml and unet_big.yaml on a 1 x 16 x 16 batch, where the forward is s
 against the plain forward there.  (forward / forward_tta on this build against a library built from the parent commit: --tta MODE
 on either, in turns.)
 
+--refine measures DeviceModel.set_lesion_refine and nothing else, on the three planes of --detection (the random network's output
+as it is, the drawn discs, specks): hysteresis, a 5 x 5 closing and hole filling each alone and all three together.  Per plane and
+setting the refined lesion_table against the plain one (wall time per call, alternated, and the ratio of the best medians) and the
+region_* launches of the refined call event-bracketed: the stage's own six and the region_ccl_* sets it adds.  (Plain lesion_table /
+lesion_table_matched on this build against a library built from the parent commit: --table_only / --matched_only on either, in turns.)
+
 The probabilities are drawn: the synthetic labels' discs at 0.55 .. 0.95 on a background of 0 .. 0.45 (a few lesions per slice,
 as a trained model gives), put into the model's probability buffer by pixel_confusion_of."""
 import argparse
@@ -101,6 +108,7 @@ ap.add_argument('--table_only', action='store_true', help='measure plain lesion_
 ap.add_argument('--detection', action='store_true', help='measure detection_map beside lesion_table and in an evaluation pass, and nothing else')
 ap.add_argument('--matched_only', action='store_true', help='measure plain lesion_table_matched, and nothing else (also on a library built from the parent)')
 ap.add_argument('--ensemble', type=int, default=0, metavar='M', help='measure forward_ensemble of M members against its parts, and nothing else')
+ap.add_argument('--refine', action='store_true', help='measure the mask refinement against the plain lesion_table, and nothing else')
 ap.add_argument('--out', default=None, help='append the report to this file as well')
 a = ap.parse_args()
 if a.features:                                                   # its siblings are lesion_table and lesion_table_spread
@@ -116,6 +124,9 @@ if a.detection or a.matched_only:                                # their yardsti
     a.link = a.match = True
 if not a.detection:
     _lib.SIGNATURES.pop('dnnca_detection_map', None)             # a library built from the parent does not export it
+if not a.refine:
+    for name in ('dnnca_model_set_lesion_refine', 'dnnca_model_get_lesion_refine'):
+        _lib.SIGNATURES.pop(name, None)                          # a library built from the parent does not export them
 if a.yardstick:
     _lib.SIGNATURES.pop('dnnca_lesion_table', None)              # a library built from the parent does not export it
 if not a.link:
@@ -201,7 +212,7 @@ ds = ArrayDataset(np.concatenate([x] * NB), None, B, meta_path='/synthetic/p0/e0
 e._build(ds)
 dm = e.device_model
 say('%s: %d x %d x %d, library %s' % ('yardstick' if a.yardstick else 'lesion features' if a.features else 'plain lesion table' if a.table_only else
-                                      'detection map' if a.detection else 'plain matched table' if a.matched_only else
+                                      'mask refinement' if a.refine else 'detection map' if a.detection else 'plain matched table' if a.matched_only else
                                       'ensemble' if a.ensemble else 'calibration' if a.calibration else 'test-time augmentation' if a.tta else 'lesion table', B, S, S, os.path.basename(_lib.LIB_PATH)))
 if a.ensemble:
     from dnncancerannotator_amd import tta as tta_modes           # noqa: E402
@@ -296,6 +307,45 @@ if a.matched_only:
     for _ in range(4):
         med, lo, hi = wall(lambda: dm.lesion_table_matched(y, continues=flags, batch=B, threshold=0.5, filter_size=5))
         say('  lesion_table_matched(mask=False): %.3f ms per call (median of %d; %.3f .. %.3f)' % (med, R, lo, hi))
+    dm.close()
+    if a.out:
+        with open(a.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+    sys.exit(0)
+if a.refine:
+    dm.forward(x, return_prob=False)
+    net = dm.last_prob(B)
+    specks = np.where(net >= np.percentile(net, 99.0), net, 0).astype(np.float32)
+    planes = (('network output as it is', net, float(np.percentile(net, 60.0)), float(np.percentile(net, 40.0))),
+              ('drawn discs', prob, 0.5, 0.3),
+              ('network output above its 99th percentile', specks, float(np.percentile(net, 99.5)), float(np.percentile(net, 98.0))))
+    settings = (('hysteresis', dict(hysteresis=True)), ('closing 5', dict(closing=5)), ('fill_holes', dict(fill_holes=True)),
+                ('all three', dict(hysteresis=True, closing=5, fill_holes=True)))
+    for what, plane, thr, low in planes:
+        dm.pixel_confusion_of(plane, y, [0.5])                    # the plane into the model's buffer (synchronises)
+        kw = dict(batch=B, threshold=thr, filter_size=5, mask=False, max_lesions=4096)
+        say('  %s: threshold %.6f, hysteresis %.6f' % (what, thr, low))
+        for name, cfg in settings:
+            cfg = dict(cfg, hysteresis=low) if cfg.get('hysteresis') else cfg
+            took = {False: [], True: []}
+            for on in (False, True) * 2:                          # alternated
+                dm.set_lesion_refine(**(cfg if on else {}))
+                took[on].append(wall(lambda: dm.lesion_table(**kw)))
+            for on in (False, True):
+                for med, lo, hi in took[on]:
+                    say('  %-28s %.3f ms per call (median of %d; %.3f .. %.3f)' % ('lesion_table, ' + (name if on else 'plain'), med, R, lo, hi))
+            plain_runs, refined_runs = [r[0] for r in took[False]], [r[0] for r in took[True]]
+            areas = []
+            for on in (False, True):
+                dm.set_lesion_refine(**(cfg if on else {}))
+                rows = dm.lesion_table(**kw)[0]
+                areas.append((len(rows), int(rows['area'].sum())))
+            say('  %s: refined / plain, wall (best medians): %.3f; plain run to run %.3f; %d -> %d lesions, %d -> %d pixels' % (
+                name, min(refined_runs) / min(plain_runs), max(plain_runs) / min(plain_runs), areas[0][0], areas[1][0], areas[0][1],
+                areas[1][1]))
+            dm.set_lesion_refine(**cfg)
+            per_launch(dm, lambda: dm.lesion_table(**kw), ('region_',))
+        dm.set_lesion_refine()
     dm.close()
     if a.out:
         with open(a.out, 'a') as f:
